@@ -112,6 +112,41 @@ def run_case(name: str, c: dict) -> None:
     print("wrote", path, f"{os.path.getsize(path) / 1e6:.2f} MB")
 
 
+# tests/test_oracle_vs_reference.py: n, k, latent(=hidden), nh, L, box, seed -- noisy windows with a target frame
+FRESH_SEED_CASES = [(300, 8, 32, 2, 2, 1.0, 11), (200, 16, 64, 1, 3, 25.0, 12), (64, 32, 32, 3, 1, 1.0, 13)]
+LAYOUT_SHAPE = (64, 128, 2, 3, 3)       # EncodeProcessDecode(latent, hidden, nh, L, out) whose state_dict layout is stored
+
+
+def run_fresh_seeds() -> None:
+    """``tests/golden/fresh_seeds.npz``: the reference's ``preprocess`` (with noise, on the seed's RNG stream) and forward
+    on each of FRESH_SEED_CASES (weights ``make_state_dict(seed=seed)``), and the reference's state_dict layout (keys in
+    order, shapes of the entries LazyLinear does not leave unmaterialised) at LAYOUT_SHAPE."""
+    gn, du = reference_shim.load()
+    out = {}
+    for n, k, d, nh, steps, box, seed in FRESH_SEED_CASES:
+        snap = synthetic.make_snapshot(n, 5, box, 0.01, seed)
+        meta = synthetic.make_metadata(box, 0.01)
+        c, e = snap["Coordinates"], snap["InternalEnergy"]
+        torch.manual_seed(seed)
+        g = du.preprocess(c[:5].clone(), e[:5].clone(), meta, c[5].clone(), e[5].clone(), 0.0003, k, meta["dt"], box)
+        model = gn.EncodeProcessDecode(d, d, nh, steps, 3)
+        model.load_state_dict(synthetic.make_state_dict(d, d, nh, steps, 3, seed=seed))
+        with torch.no_grad():
+            o = model(g)
+        for key in ("edge_index", "x", "edge_attr", "y_acc", "y_temp_rate", "pos"):
+            out[f"s{seed}:{key}"] = getattr(g, key).numpy()
+        for key in ("acceleration", "temp_rate"):
+            out[f"s{seed}:{key}"] = o[key].numpy()
+    sd = gn.EncodeProcessDecode(*LAYOUT_SHAPE).state_dict()
+    out["layout:keys"] = np.array(list(sd.keys()))
+    for key, val in sd.items():
+        if not isinstance(val, torch.nn.parameter.UninitializedParameter):
+            out["layout:shape:" + key] = np.asarray(val.shape, dtype=np.int64)
+    path = os.path.join(GOLDEN, "fresh_seeds.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, f"{os.path.getsize(path) / 1e6:.2f} MB")
+
+
 HARNESS_META = dict(vel_mean=0.02, vel_std=1.3, acc_mean=0.01, acc_std=0.7, temp_mean=1.0, temp_std=0.5,
                     temp_rate_mean=-0.1, temp_rate_std=2.0, dt=0.01, box_size=1.0)
 
@@ -234,6 +269,8 @@ def main() -> None:
             run_case(name, c)
     if not only or "harness" in only:
         run_harness()
+    if not only or "fresh_seeds" in only:
+        run_fresh_seeds()
 
 
 if __name__ == "__main__":

@@ -1,11 +1,10 @@
 """Run the reference's own ``graph_network.py`` / ``data_utils.py`` in the build
 container, behind stand-ins for the packages the image lacks.
 
-TEST INFRASTRUCTURE, build container only.  ``/root/reference`` does not exist
-on the GPU box; nothing reachable from ``pytest -m gpu``, ``smoke()`` or
-``bench.py`` imports this module.  It is used by ``oracle/make_golden.py`` to
-produce the committed fixtures under ``tests/golden/`` and by the container-only
-test ``tests/test_oracle_vs_reference.py`` (skipped when the checkout is absent).
+TEST INFRASTRUCTURE, fixture generation only: its functions run in
+``oracle/make_golden.py``, which produces the committed fixtures under
+``tests/golden/`` where a reference checkout exists.  No test, ``smoke()`` or
+``bench.py`` calls them: the tests read the stored fixtures.
 
 The reference files are imported from where they lie (never copied, no
 bytecode written).  They need three third-party names the image does not have

@@ -10,7 +10,7 @@ OUT=$REPO/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== bench under rocprofv3 --kernel-trace --stats"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err || echo "bench profile failed"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || echo "bench profile failed"
 cp $OUT/bench/*/*kernel_stats.csv $OUT/bench_kernel_stats.csv 2>/dev/null
 pmc() {   # name op args... -- then counter sets      (ONLY="edge_stream node_block": just those passes)
   local name=$1 op=$2; shift 2

@@ -275,8 +275,8 @@ def test_integration_notes_name_every_abi_entry():
 
 def test_bench_presets_follow_baseline_json(monkeypatch):
     """bench.py's --config presets are BASELINE.json's configs (particles, neighbours, latent, rounds), seeds 1234 + the
-    configuration number; N > 1 defaults to weak scaling WITH the strong-scaling leg of the headline box
-    (BASELINE.json: 'at 1M particles ... 1/2/4/8 GPU'), cfg4 / cfg5 to strong scaling of their own totals."""
+    configuration number; N > 1 defaults to weak scaling WITH (under --full) the strong-scaling leg of the
+    headline box (BASELINE.json: 'at 1M particles ... 1/2/4/8 GPU'), cfg4 / cfg5 to strong scaling of their own totals."""
     import json
     import sys
     sys.path.insert(0, ROOT)
@@ -306,3 +306,39 @@ def test_bench_presets_follow_baseline_json(monkeypatch):
     assert parse("--gpus", "8", "--config", "cfg4").scaling == "strong"
     assert parse("--gpus", "8", "--config", "cfg5").scaling == "strong"
     assert parse("--gpus", "8", "--scaling=strong").scaling == "strong"
+
+
+def test_bench_plain_run_options_and_output_dump(monkeypatch, tmp_path):
+    """A plain bench.py run measures only the headline (--full off by default) and --steps must time at least one step;
+    --dump-outputs writes the last step's arrays as float32 .npy, a seeded sample of rows (the same rows in every array,
+    the same from run to run) when they exceed the budget."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.pop(0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    acc = torch.arange(3000, dtype=torch.float32).reshape(1000, 3)
+    out = {"acceleration": acc, "temp_rate": acc[:, :1].double() * 0.5}
+    bench.dump_outputs(out, str(tmp_path / "all"), 0, 1)
+    got = {n: np.load(str(tmp_path / "all" / f"{n}.npy")) for n in out}
+    assert got["acceleration"].dtype == np.float32 and np.array_equal(got["acceleration"], acc.numpy())
+    assert got["temp_rate"].dtype == np.float32 and got["temp_rate"].shape == (1000, 1)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 16)            # room for 100 rows of 3 + 1 floats
+    for name in ("s1", "s2"):
+        bench.dump_outputs(out, str(tmp_path / name), 0, 1)
+    s1 = {n: np.load(str(tmp_path / "s1" / f"{n}.npy")) for n in out}
+    s2 = {n: np.load(str(tmp_path / "s2" / f"{n}.npy")) for n in out}
+    assert s1["acceleration"].shape == (100, 3) and s1["temp_rate"].shape == (100, 1)
+    assert all(np.array_equal(s1[n], s2[n]) for n in out)
+    rows = s1["acceleration"][:, 0].astype(np.int64) // 3
+    assert np.array_equal(s1["temp_rate"][:, 0], rows * 1.5) and np.all(np.diff(rows) > 0)
+    bench.dump_outputs(out, str(tmp_path / "ranks"), 1, 2)      # N > 1: each rank's rows, half the budget each
+    assert np.load(str(tmp_path / "ranks" / "acceleration_rank1.npy")).shape == (50, 3)
