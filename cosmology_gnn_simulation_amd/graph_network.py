@@ -504,6 +504,10 @@ class EncodeProcessDecode(nn.Module):
         self.edge_precision = "fp32"
         self.train_precision = "fp32"  # arithmetic of the differentiable forward + backward: "fp32" or "fp32x3"
         self.locality_sort = True     # run in the k-NN build's spatial order when the graph carries it
+        # message_source "edge": allow training (keeps every round's edge latents and an edge-row backward scratch, about
+        # L E D 4 + (2 nh + 3) E H 4 bytes more than x_j mode: ~37 GB at cfg2's shape, ~139 GB at cfg3's; a step whose
+        # estimate exceeds the free device memory is refused before it allocates).  No effect under message_source "x_j"
+        self.train_edge_messages = False
         self.fuse_rounds = True       # x_j mode: all rounds of the edge stream in one launch
         # which one-launch kernel: "tile32" = cgnn_edge_stream_run (32-edge MFMA tiles, one wave per SIMD, two tiles per
         # wave), "tile32w" = cgnn_edge_stream_run_w8 (32-edge tiles, two waves per SIMD, one tile each; latent 128 only,
@@ -632,11 +636,11 @@ class EncodeProcessDecode(nn.Module):
         """Same as :meth:`forward` plus ``x_latent`` / ``edge_latent`` after the last round."""
         return self._forward(input_graph, want_latents=True)
 
-    def _train_packs(self):
-        from .training import TrainPacks
-        key = _params_key(self, "train", getattr(self, "train_precision", "fp32"))
+    def _train_packs(self, edge: bool = False):
+        from .training import EdgeTrainPacks, TrainPacks
+        key = _params_key(self, "train", getattr(self, "train_precision", "fp32"), edge)
         if self._train_packed is None or self._train_packed[0] != key:
-            self._train_packed = (key, TrainPacks(self))
+            self._train_packed = (key, EdgeTrainPacks(self) if edge else TrainPacks(self))
         return self._train_packed[1]
 
     def _forward_train(self, g) -> dict:
@@ -644,8 +648,11 @@ class EncodeProcessDecode(nn.Module):
         gradient, exactly as under the reference."""
         from . import training
         if self.message_source != "x_j":
-            raise NotImplementedError("training is built for the reference-faithful message_source='x_j'; the "
-                                      "'edge' extension has no backward kernels")
+            if self.message_source != "edge" or not getattr(self, "train_edge_messages", False):
+                raise NotImplementedError("training is built for the reference-faithful message_source='x_j'; the "
+                                          "'edge' extension trains with model.train_edge_messages = True (it keeps "
+                                          "every round's edge latents: see training.edge_training_bytes)")
+            return self._forward_train_edge(g)
         x = g.x
         require_device(x, "input_graph.x")
         edge_attr = getattr(g, "edge_attr", None)
@@ -681,6 +688,55 @@ class EncodeProcessDecode(nn.Module):
             packs.edge_stream_fn = lambda xs: training.edge_stream_of(self, xs, src, dst, fixed_k, ea, node_in)
         acc, tr = training.forward_train(self, x, src, dst, fixed_k, packs, cached[1])
         packs.edge_stream_fn = None
+        if plan is not None:
+            acc = training.permute_rows(acc, inv, order)
+            tr = training.permute_rows(tr, inv, order)
+        return {"acceleration": acc, "temp_rate": tr}
+
+    def _forward_train_edge(self, g) -> dict:
+        """Differentiable forward under ``message_source="edge"`` (``train_edge_messages``): both streams, every
+        parameter (edge models included) receives a gradient, and ``edge_attr`` one when it requires it.  See
+        :class:`.training._EdgeStreams`."""
+        from . import training
+        x = g.x
+        require_device(x, "input_graph.x")
+        edge_attr = getattr(g, "edge_attr", None)
+        if edge_attr is None:
+            raise ValueError("edge_attr must not be None in InteractionNetwork")
+        glob = getattr(g, "globals", None)
+        if glob is not None:
+            x = torch.cat([x, glob.unsqueeze(0).expand(x.shape[0], -1)], dim=-1)
+        x = x.float().contiguous()
+        ea = edge_attr.float().contiguous()
+        n, ne = x.shape[0], ea.shape[0]
+        with torch.no_grad():
+            src, dst, fixed_k = _graph_arrays(g, n)
+            plan = _locality_plan(g, n, fixed_k, src) if (self.locality_sort and fixed_k > 0) else None
+            self._materialize_all(x.shape[1], ea.shape[1])
+            D, H = self._latent_size, self._mlp_hidden_size
+            need = training.edge_training_bytes(ne, D, H, self._mlp_num_hidden_layers, len(self.processor))
+            # free device memory plus what the caching allocator holds reserved but unused (a previous step's scratch)
+            free = torch.cuda.mem_get_info(x.device)[0] + \
+                torch.cuda.memory_reserved(x.device) - torch.cuda.memory_allocated(x.device)
+            if need > free:
+                raise CgnnError(f"edge-mode training needs about {need / 2**30:.1f} GiB of device memory for the edge "
+                                f"latents of every round and the edge-row backward scratch ({ne} edges, latent {D}, hidden "
+                                f"{H}, {len(self.processor)} rounds); {free / 2**30:.1f} GiB are free")
+            packs = self._train_packs(edge=True)
+        if plan is not None:
+            order, inv, src, dst = plan
+            x = training.permute_rows(x, order, inv)
+            # edges are receiver-major, fixed_k per receiver: permute whole receiver blocks (un-permuted in the backward)
+            ea = training.permute_rows(ea.view(n, -1), order, inv).view(ne, -1)
+        cached = getattr(g, "_cgnn_edges_by_node", None)      # edge CSRs (sender-major, receiver-major), once per graph
+        if cached is None or cached[0] is not src:
+            by_receiver = ops.SenderCsr(dst, None, n) if fixed_k == 0 else None
+            cached = (src, ops.SenderCsr(src, None, n), by_receiver)
+            try:
+                g._cgnn_edges_by_node = cached
+            except Exception:
+                pass
+        acc, tr = training.forward_train_edge(self, x, ea, src, dst, fixed_k, packs, cached[1], cached[2])
         if plan is not None:
             acc = training.permute_rows(acc, inv, order)
             tr = training.permute_rows(tr, inv, order)

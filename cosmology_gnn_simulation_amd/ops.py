@@ -181,11 +181,16 @@ class TiledRows:
         return relayout(x)
 
 
-def relayout(x):
-    """``TiledRows -> row-major tensor`` or ``row-major tensor -> TiledRows``."""
+def relayout(x, out: Optional[torch.Tensor] = None):
+    """``TiledRows -> row-major tensor`` or ``row-major tensor -> TiledRows``.  ``out`` (TiledRows -> rows only): a
+    contiguous float32 tensor of at least ``n`` rows of ``width`` to write the rows into (its first ``n`` rows)."""
     lib = _lib.load()
     if isinstance(x, TiledRows):
-        out = torch.empty((x.n, x.width), dtype=torch.float32, device=x.device)
+        if out is None:
+            out = torch.empty((x.n, x.width), dtype=torch.float32, device=x.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != x.width or \
+                out.shape[0] < x.n or out.device != x.device:
+            raise CgnnError("relayout: out must be contiguous float32 [>= n, width] on the tiles' device")
         if x.n:
             with _timed("relayout", x.device):
                 check(lib.cgnn_relayout(x.buf.data_ptr(), _lib.TILED32, out.data_ptr(), _lib.ROWS, x.n, x.width,
@@ -838,3 +843,96 @@ def col_dot2(a: torch.Tensor, ld_a: int, b: torch.Tensor, ld_b: int, n: int, wid
                                                out_a.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(a.device)),
               "cgnn_col_dot_ordered")
     return out_ab, out_a
+
+
+# ---- backward of the edge stream, message_source "edge" (include/cgnn.h: cgnn_edge_mlp_backward / cgnn_linear2_rows) ----
+
+# (hidden, latent) pairs the edge backward is compiled for (CGNN_FOR_EACH_PAIR)
+EDGE_BWD_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 64), (128, 256))
+_EDGE_BWD_PRECISIONS = ((F32, F32), (_lib.F32X3, _lib.F32X3), (_lib.F16X2, _lib.F32X3))
+
+
+def edge_mlp_backward(fwd: PackedMLP, bwd: PackedMLP, ps: torch.Tensor, pd: torch.Tensor, src: torch.Tensor,
+                      dst: torch.Tensor, e_in: TiledRows, d_agg: torch.Tensor, de_in: Optional[TiledRows],
+                      scratch: BackwardScratch, dy: torch.Tensor, de_out, de_out_rows: bool = False):
+    """Data gradients of one round's edge model under ``message_source="edge"`` (``cgnn_edge_mlp_backward``): recomputes
+    ``u = LN(MLP(ps[src] + pd[dst] + e_in We^T))`` per 32-edge tile, forms ``dy = d_agg[dst] + de_in`` (``de_in`` None:
+    zero), fills ``scratch`` (``h``, ``g_a``, ``g_o``, ``zhat`` over the edge rows) and ``dy`` ([>= E, latent] float32,
+    row-major) and writes ``de_out = de_in + We^T g_a[0]``: a :class:`TiledRows`, or with ``de_out_rows`` a row-major
+    tensor of at least E rows (either may share memory with ``de_in``).  ``fwd`` is the edge model packed for
+    ``edge_block`` (layer 0 = the We column block), ``bwd`` the transposed weights; ``ps`` / ``pd`` float32
+    ``project_nodes`` tables.  Shapes or precisions the kernel is not built for raise :class:`CgnnError` before launch."""
+    if not isinstance(e_in, TiledRows) or (de_in is not None and not isinstance(de_in, TiledRows)):
+        raise CgnnError("edge_mlp_backward: e_in / de_in must be TiledRows (the layout edge_block leaves them in)")
+    ne, latent = e_in.n, e_in.width
+    hidden, nh = fwd.hidden, fwd.num_hidden_layers
+    if (fwd.precision, bwd.precision) not in _EDGE_BWD_PRECISIONS:
+        raise CgnnError("edge_mlp_backward: (fwd, bwd) packings must be (fp32, fp32), (fp32x3, fp32x3) or (fp16x2, fp32x3)")
+    if (hidden, latent) not in EDGE_BWD_PAIRS:
+        raise CgnnError(f"edge_mlp_backward: no kernel for hidden {hidden}, latent {latent} (built for {EDGE_BWD_PAIRS})")
+    if fwd.in_dim != latent or fwd.out_dim != latent or fwd.gamma is None or bwd.num_hidden_layers != nh or \
+            bwd.layers[0].in_dim != hidden or bwd.layers[0].out_dim != latent:
+        raise CgnnError("edge_mlp_backward: the packed edge model does not match the edge latents (layer 0 must be the We "
+                        "block, LayerNorm required, bwd the transposed weights)")
+    src, dst = i32c(src, "src"), i32c(dst, "dst")
+    if src.numel() != ne or dst.numel() != ne:
+        raise CgnnError("edge_mlp_backward: src/dst length does not match the edge latents")
+    n = ps.shape[0] if ps.dim() == 2 else -1
+    for t, name in ((ps, "ps"), (pd, "pd")):
+        require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, hidden):
+            raise CgnnError(f"edge_mlp_backward: {name} must be a contiguous float32 [nodes, {hidden}] table (CGNN_P_F32)")
+    require_device(d_agg, "d_agg")
+    if d_agg.dtype != torch.float32 or not d_agg.is_contiguous() or tuple(d_agg.shape) != (n, latent):
+        raise CgnnError(f"edge_mlp_backward: d_agg must be contiguous float32 [{n}, {latent}]")
+    if de_in is not None and (de_in.n != ne or de_in.width != latent):
+        raise CgnnError("edge_mlp_backward: de_in does not match the edge latents")
+    if ne > scratch.n or scratch.hidden != hidden or scratch.nh < nh or scratch.out_padded < latent:
+        raise CgnnError("edge_mlp_backward: scratch does not fit (edge rows, hidden width or depth)")
+    for t, name in ((dy, "dy"),) + ((() if not de_out_rows else ((de_out, "de_out"),))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] < ne or t.shape[1] != latent:
+            raise CgnnError(f"edge_mlp_backward: {name} must be contiguous float32 [>= {ne}, {latent}]")
+    if de_out_rows:
+        de_ptr = de_out.data_ptr()
+    else:
+        if not isinstance(de_out, TiledRows) or de_out.n != ne or de_out.width != latent:
+            raise CgnnError("edge_mlp_backward: de_out must be TiledRows of the edge latents' shape")
+        de_ptr = de_out.buf.data_ptr()
+    _same_device(ps, pd, src, dst, e_in.buf, d_agg, dy, scratch.g_o, de_in.buf if de_in is not None else None)
+    bufs = scratch.struct(nh, latent)
+    with _timed("edge_mlp_backward", e_in.device):
+        check(_lib.load().cgnn_edge_mlp_backward(
+            C.byref(fwd.struct()), C.byref(bwd.struct()), ps.data_ptr(), pd.data_ptr(), src.data_ptr(), dst.data_ptr(), ne,
+            e_in.buf.data_ptr(), d_agg.data_ptr(), None if de_in is None else de_in.buf.data_ptr(), C.byref(bufs),
+            dy.data_ptr(), de_ptr, _lib.ROWS if de_out_rows else _lib.TILED32, stream_ptr(e_in.device)),
+            "cgnn_edge_mlp_backward")
+    return de_out
+
+
+def linear2_rows(wa: PackedLinear, wb: PackedLinear, a: torch.Tensor, b: torch.Tensor, add1: Optional[torch.Tensor] = None,
+                 add2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out = add1 + add2 + a Wa^T + b Wb^T`` over rows (``cgnn_linear2_rows``); ``out`` may be ``add1`` or ``add2``."""
+    a, b = f32c(a, "a"), f32c(b, "b")
+    n = a.shape[0]
+    if wa.precision != wb.precision or wa.precision not in (F32, _lib.F32X3):
+        raise CgnnError("linear2_rows: both parts must be packed fp32 or fp32x3")
+    if (wa.in_dim, wa.out_dim) != (wb.in_dim, wb.out_dim) or (wa.in_dim, wa.out_dim) not in EDGE_BWD_PAIRS or \
+            wa.bias is not None or wb.bias is not None:
+        raise CgnnError(f"linear2_rows: no kernel for in {wa.in_dim}, out {wa.out_dim} (two bias-free parts of a pair in "
+                        f"{EDGE_BWD_PAIRS})")
+    if tuple(a.shape) != (n, wa.in_dim) or tuple(b.shape) != (n, wa.in_dim):
+        raise CgnnError(f"linear2_rows: inputs must be [n, {wa.in_dim}]")
+    shape = (n, wa.out_dim)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=a.device)
+    for t, name in ((add1, "add1"), (add2, "add2"), (out, "out")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.device != a.device):
+            raise CgnnError(f"linear2_rows: {name} must be contiguous float32 {shape} on the inputs' device")
+    _same_device(a, b, wa.packed, wb.packed)
+    sa, sb = wa.struct(), wb.struct()
+    with _timed("linear2_rows", a.device):
+        check(_lib.load().cgnn_linear2_rows(C.byref(sa), C.byref(sb), wa.precision, a.data_ptr(), b.data_ptr(), n,
+                                            ptr(add1), ptr(add2), out.data_ptr(), stream_ptr(a.device)),
+              "cgnn_linear2_rows")
+    return out

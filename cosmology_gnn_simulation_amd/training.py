@@ -15,7 +15,13 @@ recomputes the activations tile by tile (``cgnn_mlp_backward``), transposes the 
 the sender-major adjacency (``cgnn_csr_build`` once per graph, ``cgnn_aggregate_csr``) and reduces the parameter
 gradients with ``cgnn_weight_grad`` / ``cgnn_col_dot``.
 
-``message_source="edge"`` (the engine's extension, not the reference's behaviour) has no backward yet.
+``message_source="edge"`` (the engine's extension, not the reference's behaviour) trains with
+``model.train_edge_messages = True`` (:class:`_EdgeStreams`): both streams are differentiated, every parameter -- the edge
+models' included -- receives a gradient, ``edge_attr`` one when it requires it.  Per round the backward recomputes the edge
+model tile by tile (``cgnn_edge_mlp_backward``: dy = d_agg[dst] + de formed in registers, de <- de + We^T dh1), reduces its
+parameter gradients over the edge rows, sums dh1 at the senders (edge CSR) and receivers (fixed-k segments or a CSR) and
+adds Ws^T dPs + Wd^T dPd to dx in one N-row pass (``cgnn_linear2_rows``).  That mode keeps every round's edge latents:
+see :func:`edge_training_bytes`.
 """
 from __future__ import annotations
 
@@ -192,6 +198,210 @@ class _NodeStream(torch.autograd.Function):
         flat = [g for m in packs.all for g in grads_of[id(m)]]
         ctx.xs = None
         return (None, None, dx0, *flat)
+
+
+class _TrainEdge:
+    """One round's edge model under ``message_source="edge"``, packed for training: the forward (``project_nodes`` +
+    ``edge_block`` with ``e_upd``, f32-accurate), the recomputing backward (``cgnn_edge_mlp_backward``), the transposed
+    first-layer blocks ``Ws^T`` / ``Wd^T`` of ``cgnn_linear2_rows``, and the parameter list in ``module.parameters()``
+    order.  Arithmetic by ``train_precision``: "fp32" exact throughout; "fp32x3" runs the forward on the two-fp16-term
+    edge kernel (``CGNN_F16X2_N16``, latent = hidden = 128, <= 3 hidden layers) and recomputes it on two fp16 terms (edge
+    latents and P rows are O(1) behind LayerNorms), or, at every other shape, runs it in exact f32 and recomputes it on
+    three bf16 terms; the gradient chain runs on three bf16 terms."""
+
+    def __init__(self, linears: Sequence[nn.Module], ln: nn.LayerNorm, latent: int, precision: str = "fp32"):
+        if ops._prec(precision) not in (_lib.F32, _lib.F32X3):
+            raise CgnnError(f"training arithmetic must be 'fp32' or 'fp32x3', got {precision!r}")
+        self.linears, self.ln, self.precision = list(linears), ln, precision
+        D = self.latent = int(latent)
+        w0 = linears[0].weight
+        self.hidden, self.nh = int(w0.shape[0]), len(self.linears) - 1
+        if (self.hidden, D) not in ops.EDGE_BWD_PAIRS:
+            raise CgnnError(f"edge-mode training kernels are built for (hidden, latent) in {ops.EDGE_BWD_PAIRS}; got "
+                            f"({self.hidden}, {D})")
+        wb = [(l.weight, l.bias) for l in self.linears]
+        lnp = (ln.weight, ln.bias)
+        x3 = ops._prec(precision) == _lib.F32X3
+        two_terms = x3 and D == 128 and self.hidden == 128 and self.nh <= 3 and all(l.bias is not None for l in self.linears)
+        fwd_prec, proj_prec = ("fp16x2_n16", "fp16x2") if two_terms else ("fp32", "fp32")
+        self.ws = ops.PackedLinear(w0, None, proj_prec, 0, D)            # P_F32 tables, b1 in Pd
+        self.wd = ops.PackedLinear(w0, linears[0].bias, proj_prec, D, D)
+        self.fwd = ops.PackedMLP(wb, lnp, fwd_prec, first_layer_cols=(2 * D, D))
+        # the recomputed forward matches the forward's arithmetic class: two fp16 terms behind the two-fp16-term edge kernel,
+        # three bf16 terms (the (F32X3, F32X3) pairing) where the forward ran exact f32 -- both f32-accurate, neither the
+        # forward's bits (the kernels sum in other orders), so a ReLU whose input rounds to zero can take the other branch
+        rec_prec = ("fp16x2" if two_terms else "fp32x3") if x3 else "fp32"
+        self.rec = ops.PackedMLP(wb, lnp, rec_prec, first_layer_cols=(2 * D, D))
+        t = lambda w: w.detach().t().contiguous()  # noqa: E731
+        self.bwd = ops.PackedMLP([(t(w0[:, 2 * D:]), None)] + [(t(l.weight), None) for l in self.linears[1:]], None,
+                                 precision)
+        self.wst = ops.PackedLinear(t(w0[:, :D]), None, precision)       # [D, H]: dx += dPs Ws
+        self.wdt = ops.PackedLinear(t(w0[:, D:2 * D]), None, precision)
+
+    def params(self) -> List[torch.Tensor]:
+        out: List[torch.Tensor] = []
+        for l in self.linears:
+            out += [l.weight, l.bias]
+        return out + [self.ln.weight, self.ln.bias]
+
+
+class EdgeTrainPacks(TrainPacks):
+    """:class:`TrainPacks` plus the edge encoder and every round's edge model (``message_source="edge"``)."""
+
+    def __init__(self, model):
+        super().__init__(model)
+        from .graph_network import _split_mlp
+        prec, D = self.precision, self.latent
+        self.enc_edge = _TrainMLP(*_split_mlp(model.encoder.edge_model), precision=prec)
+        self.edges = [_TrainEdge(*_split_mlp(net.edge_model), latent=D, precision=prec) for net in model.processor]
+        if self.enc_edge.hidden != self.hidden or any(e.hidden != self.hidden or e.nh != self.nh for e in self.edges):
+            raise CgnnError("edge-mode training needs one hidden width and depth across the model's MLPs")
+        if self.enc_edge.in1 > 32:
+            raise CgnnError(f"edge-mode training takes at most 32 edge features (got {self.enc_edge.in1})")
+
+    def params(self) -> List[torch.Tensor]:
+        """In ``model.parameters()`` order: encoder (node, edge), per round (edge, node), decoders."""
+        out = self.enc.params() + self.enc_edge.params()
+        for e, r in zip(self.edges, self.rounds):
+            out += e.params() + r.params()
+        return out + self.dec_acc.params() + self.dec_tr.params()
+
+
+def edge_training_bytes(num_edges: int, latent: int, hidden: int, num_hidden_layers: int, rounds: int) -> int:
+    """Device memory edge-mode training keeps beyond x_j mode: every round's input edge latents (``L E D`` floats) and the
+    E-row backward scratch (``h`` and ``g_a`` per hidden layer, ``g_o``, ``zhat``, ``dy``: ``(2 nh + 3) E H`` floats;
+    ``g_o`` / ``zhat`` / ``dy`` are ``latent`` wide, counted at ``hidden``)."""
+    return 4 * (rounds * num_edges * latent + (2 * num_hidden_layers + 3) * num_edges * hidden)
+
+
+class _EdgeStreams(torch.autograd.Function):
+    """acceleration, temp_rate = f(x0, edge_attr; all parameters) under ``message_source="edge"``: node AND edge stream.
+    Non-tensor context first, then ``x0``, ``edge_attr`` and the parameters in ``EdgeTrainPacks.params()`` order."""
+
+    @staticmethod
+    def forward(ctx, packs: EdgeTrainPacks, graph, x0: torch.Tensor, edge_attr: torch.Tensor, *params: torch.Tensor):
+        src, dst, fixed_k, _, _ = graph
+        n, ne = x0.shape[0], src.numel()
+        xs = [ops.mlp_rows(packs.enc.fwd, x0)]
+        es = [ops.mlp_rows(packs.enc_edge.fwd, edge_attr, tiled=True)]       # raw features: three bf16 terms or exact
+        aggs = []
+        e_upd = es[0].empty_like()
+        for i, (ep, r) in enumerate(zip(packs.edges, packs.rounds)):
+            x, e = xs[-1], es[-1]
+            ps, pd = ops.project_nodes(ep.ws, ep.wd, x, p_format=_lib.P_F32)
+            last = i == len(packs.rounds) - 1
+            # e_{i+1} = e_i + u into a new buffer (e_i is kept for the backward); the last round's e_L is not needed
+            e_next = None if last else e.empty_like()
+            if last:
+                ops.edge_block(ep.fwd, ps, pd, src, dst, e, e_upd, None, residual=False)
+            else:
+                ops.edge_block(ep.fwd, ps, pd, src, dst, e, e_next, e_upd, residual=True)
+            agg = ops.aggregate(e_upd, None, dst, n, fixed_k, ne)
+            aggs.append(agg)
+            xs.append(ops.node_block(r.run, r.run.layers[0], r.run2, x, agg, None, residual=True))
+            if not last:
+                es.append(e_next)
+        del e_upd
+        acc = ops.mlp_rows(packs.dec_acc.run, xs[-1])
+        tr = ops.mlp_rows(packs.dec_tr.run, xs[-1])
+        ctx.packs, ctx.graph, ctx.x0, ctx.edge_attr, ctx.xs, ctx.es, ctx.aggs = packs, graph, x0, edge_attr, xs, es, aggs
+        return acc, tr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_acc, d_tr):
+        packs, (src, dst, fixed_k, by_sender_e, by_receiver_e), x0, xs, es = ctx.packs, ctx.graph, ctx.x0, ctx.xs, ctx.es
+        n, D, H, nh = x0.shape[0], packs.latent, packs.hidden, packs.nh
+        ne = src.numel()
+        dev = x0.device
+        scratch = ops.BackwardScratch(n, H, max(D, 32), nh, dev)
+        escratch = ops.BackwardScratch(ne, H, max(D, 32), nh, dev)
+        dy = torch.empty((max(ne, 1), D), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i as rows
+        de = es[0].empty_like()        # d e_i, updated in place: TILED32 between rounds, row-major after round 0
+        grads_of = {}
+        xl = xs[-1]
+        zero = lambda t, w: torch.zeros((n, w), dtype=torch.float32, device=dev) if t is None else t  # noqa: E731
+        dx, _, grads_of[id(packs.dec_acc)] = packs.dec_acc.backward(xl, None, zero(d_acc, packs.dec_acc.out_dim), scratch, True)
+        dx2, _, grads_of[id(packs.dec_tr)] = packs.dec_tr.backward(xl, None, zero(d_tr, packs.dec_tr.out_dim), scratch, True)
+        dx = dx.add_(dx2)
+        L = len(packs.rounds)
+        for i in range(L - 1, -1, -1):
+            r, ep, x, e = packs.rounds[i], packs.edges[i], xs[i], es[i]
+            agg = ctx.aggs[i]
+            ctx.aggs[i] = None
+            du1, d_agg, grads_of[id(r)] = r.backward(x, agg, dx, scratch, True, True)
+            ps, pd = ops.project_nodes(ep.ws, ep.wd, x, p_format=_lib.P_F32)     # the forward's tables, bit for bit
+            first = i == 0
+            ops.edge_mlp_backward(ep.rec, ep.bwd, ps, pd, src, dst, e, d_agg, None if i == L - 1 else de, escratch, dy,
+                                  de.buf if first else de, de_out_rows=first)
+            del ps, pd
+            grads_of[id(ep)], dps, dpd = edge_round_grads(ep, escratch, dy, e, x, dst, fixed_k, by_sender_e, by_receiver_e)
+            # dx_i = dx_{i+1} + du1 + Ws^T dPs + Wd^T dPd
+            dx = ops.linear2_rows(ep.wst, ep.wdt, dps, dpd, add1=dx, add2=du1, out=dx)
+            es[i] = None
+        need_dx0, need_dea = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dx0, _, grads_of[id(packs.enc)] = packs.enc.backward(x0, None, dx, scratch, need_dx0)
+        if L == 0:
+            de.buf.zero_()             # no round reads the edge encoder's output
+        de_rows = de.buf[:ne]          # round 0 wrote d e_0 in rows: what the encoder's backward reads as dy
+        dea, _, grads_of[id(packs.enc_edge)] = packs.enc_edge.backward(ctx.edge_attr, None, de_rows, escratch, need_dea)
+        flat = grads_of[id(packs.enc)] + grads_of[id(packs.enc_edge)]
+        for ep, r in zip(packs.edges, packs.rounds):
+            flat += grads_of[id(ep)] + grads_of[id(r)]
+        flat += grads_of[id(packs.dec_acc)] + grads_of[id(packs.dec_tr)]
+        ctx.xs = ctx.es = None
+        return (None, None, dx0 if need_dx0 else None, dea if need_dea else None, *flat)
+
+
+def edge_round_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Tensor, e: "ops.TiledRows", x: torch.Tensor,
+                     dst: torch.Tensor, fixed_k: int, by_sender_e: "ops.SenderCsr",
+                     by_receiver_e: Optional["ops.SenderCsr"]):
+    """After ``ops.edge_mlp_backward`` of round ``ep`` (``escratch`` / ``dy`` filled, ``e`` the round's input edge latents,
+    ``x`` its node latents): -> (parameter gradients in ``ep.params()`` order, dPs, dPd) with every reduction in a fixed
+    order.  ``dy`` is overwritten (it receives ``e`` in rows for ``dWe``)."""
+    ne, n = e.n, x.shape[0]
+    D, H, nh, prec = ep.latent, ep.hidden, ep.nh, ep.precision
+    dev = x.device
+    g_a0 = escratch.g_a[0]
+    dw0 = torch.zeros_like(ep.linears[0].weight, memory_format=torch.contiguous_format)
+    db0 = torch.zeros(H, dtype=torch.float32, device=dev)
+    dgamma = torch.zeros(D, dtype=torch.float32, device=dev)
+    dbeta = torch.zeros_like(dgamma)
+    layer_grads = []
+    if ne:
+        ops.col_dot2(dy, D, escratch.zhat, D, ne, D, dgamma, dbeta)     # LayerNorm affine: colsum(dy zhat), colsum(dy)
+    for l in range(1, nh + 1):
+        lin = ep.linears[l]
+        last = l == nh
+        out_dim = lin.weight.shape[0]
+        dw = torch.zeros_like(lin.weight, memory_format=torch.contiguous_format)
+        db = torch.zeros(out_dim, dtype=torch.float32, device=dev)
+        if ne:
+            ops.weight_grad(escratch.g_o if last else escratch.g_a[l], D if last else H, out_dim, escratch.h[l - 1], H, ne,
+                            dw, 0, db, prec)
+        layer_grads += [dw, db]
+    # first layer [Ws | Wd | We]: dWe = g_a[0]^T e over the edge rows (e relaid out to rows into dy, read above: one
+    # E x D read + write), dWs = dPs^T x and dWd = dPd^T x over the node rows, db1 = colsum(dPd)
+    if ne:
+        ops.weight_grad(g_a0, H, H, ops.relayout(e, out=dy), D, ne, dw0, 2 * D, None, prec)
+        dps = ops.aggregate_csr(g_a0, by_sender_e)
+        dpd = ops.aggregate(g_a0, None, dst, n, fixed_k, ne) if fixed_k > 0 else ops.aggregate_csr(g_a0, by_receiver_e)
+    else:
+        dps = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        dpd = torch.zeros_like(dps)
+    ops.weight_grad(dps, H, H, x, D, n, dw0, 0, None, prec)
+    ops.weight_grad(dpd, H, H, x, D, n, dw0, D, db0, prec)
+    return [dw0, db0] + layer_grads + [dgamma, dbeta], dps, dpd
+
+
+def forward_train_edge(model, x0: torch.Tensor, edge_attr: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,
+                       fixed_k: int, packs: EdgeTrainPacks, by_sender_e: "ops.SenderCsr",
+                       by_receiver_e: Optional["ops.SenderCsr"]):
+    """Differentiable ``(acceleration, temp_rate)`` under ``message_source="edge"`` for node features ``x0`` and edge
+    features ``edge_attr`` (float32, contiguous, in the kernels' particle / edge order).  ``by_sender_e``: the edges
+    grouped by sender (``ops.SenderCsr(src, None, n)``); ``by_receiver_e``: grouped by receiver (general edge lists
+    only; ``fixed_k > 0`` sums receiver segments)."""
+    return _EdgeStreams.apply(packs, (src, dst, fixed_k, by_sender_e, by_receiver_e), x0, edge_attr, *packs.params())
 
 
 def edge_stream_of(model, xs: Sequence[torch.Tensor], src: torch.Tensor, dst: torch.Tensor, fixed_k: int,

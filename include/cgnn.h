@@ -340,6 +340,42 @@ int cgnn_mlp_backward(const cgnn_mlp* fwd, const cgnn_linear* fwd_part2, const c
                       const float* dy, int32_t ld_dy, int64_t n, const cgnn_mlp_bwd_buffers* buf,
                       float* du1, int32_t ld_du1, float* du2, int32_t ld_du2, void* stream);
 
+/* ---- backward of the edge model under message_source "edge" (graph_network.py:89-92 with the message overridden) ----
+ * The edge update u = LayerNorm(MLP(cat[x[src], x[dst], e])) of cgnn_edge_block, its sum at the receivers
+ * (agg[i] = sum_{dst[e]==i} u[e]) and the residual e_out = e + u, differentiated over the E edge rows.  Per 32-edge
+ * tile the call recomputes the forward exactly as cgnn_edge_block evaluates it -- first layer ps[src] + pd[dst] +
+ * e_in * We^T -- forms dy = d_agg[dst] + de_in in registers, and walks the chain back like cgnn_mlp_backward, writing
+ * the same cgnn_mlp_bwd_buffers -- h[l], g_a[l], g_o, zhat; rows = edges, row-major, g_o / zhat latent wide -- plus
+ *   dy      [E, latent] row-major: d_agg[dst] + de_in, for dgamma = colsum(dy * zhat), dbeta = colsum(dy)
+ *           (cgnn_col_dot_ordered: fixed summation order)
+ *   de_out  de_in + We^T g_a[0]: the edge-latent gradient the previous round (or the edge encoder) continues from;
+ *           de_out_layout CGNN_TILED32 (what the previous round's call reads as de_in) or CGNN_ROWS (what
+ *           cgnn_mlp_backward of the edge encoder reads as dy).  de_out may alias de_in, in either layout.
+ * g_a[0] is dL/dh1 (h1 the first layer's pre-activation): the caller forms dPs[n] = sum_{src[e]==n} g_a[0][e] and
+ * dPd[n] = sum_{dst[e]==n} g_a[0][e] (cgnn_aggregate_csr through an edge CSR, or cgnn_aggregate at a fixed in-degree),
+ * then dWs = dPs^T x, dWd = dPd^T x, db1 = colsum(dPd), dWe = g_a[0]^T e_in (e_in in rows: cgnn_relayout) and
+ * dx += Ws^T dPs + Wd^T dPd (cgnn_linear2_rows).
+ *   fwd      the edge model as packed for cgnn_edge_block (layer[0] = the We column block, in_dim = latent; its bias is
+ *            ignored: b1 is in pd), LayerNorm required
+ *   bwd      the transposed weights packed the same way (bwd->layer[0] = We^T, bwd->layer[l] = W_l^T)
+ *   ps, pd   cgnn_project_nodes tables in CGNN_P_F32 (float [num_nodes, hidden], b1 in pd)
+ *   e_in     the round's input edge latents, CGNN_TILED32; de_in CGNN_TILED32 or NULL (= zero: the last round)
+ *   d_agg    [num_nodes, latent] row-major: dL/d(aggregate) from the node model's backward
+ * Arithmetic (fwd->precision, bwd->precision) as cgnn_mlp_backward: (CGNN_F32, CGNN_F32), (CGNN_F32X3, CGNN_F32X3),
+ * (CGNN_F16X2, CGNN_F32X3).  Shapes: (hidden, latent) = (32, 32), (64, 64), (128, 128), (256, 256), (128, 64),
+ * (128, 256); 1..CGNN_MAX_HIDDEN_LAYERS hidden layers; any num_edges. */
+int cgnn_edge_mlp_backward(const cgnn_mlp* fwd, const cgnn_mlp* bwd, const void* ps, const void* pd, const int32_t* src,
+                           const int32_t* dst, int64_t num_edges, const float* e_in, const float* d_agg,
+                           const float* de_in, const cgnn_mlp_bwd_buffers* buf, float* dy, float* de_out,
+                           int32_t de_out_layout, void* stream);
+
+/* out[r] = add1[r] + add2[r] + a[r] * Wa^T + b[r] * Wb^T   for r < n (row-major, rows of wa->in_dim / wa->out_dim floats):
+ * the edge model's first-layer gradient into the node latents, dx += Ws^T dPs + Wd^T dPd, as one N-row product
+ * (wa / wb: Ws^T and Wd^T packed as Linears, no bias).  precision CGNN_F32 or CGNN_F32X3; (in, out) one of the
+ * (hidden, latent) pairs above.  add1 / add2 may be NULL; out may alias either. */
+int cgnn_linear2_rows(const cgnn_linear* wa, const cgnn_linear* wb, int32_t precision, const float* a, const float* b,
+                      int64_t n, const float* add1, const float* add2, float* out, void* stream);
+
 /* dw[o, col0 + i] += sum_r g[r, o] * a[r, i]   (o < out_dim, i < in_dim; f32 MFMA, float atomics across row chunks:
  * the caller zeroes dw; summation order over row chunks is not reproducible).  db (optional): db[o] += sum_r g[r, o],
  * the bias gradient, from the operands already loaded. */

@@ -22,6 +22,8 @@ ap.add_argument("--hidden", type=int, default=None, help="mlp_hidden_size (defau
 ap.add_argument("--with-edge-stream", action="store_true",
                 help="also run the edge stream's forward (model.train_edge_stream): under the reference nothing reads it "
                      "(SURVEY F1) but its step computes it -- the like-for-like step time")
+ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"],
+                help="edge: train the Interaction Network that aggregates the edge updates (model.train_edge_messages)")
 a = ap.parse_args()
 dev = "cuda"
 n, k, d, L = a.particles, a.neighbors, a.latent, a.mp_steps
@@ -35,6 +37,8 @@ m.load_state_dict(synthetic.make_state_dict(d, hd, 2, L, 3))
 m = m.to(dev).train()
 m.train_precision = a.train_precision
 m.train_edge_stream = a.with_edge_stream
+m.message_source = a.message_source
+m.train_edge_messages = a.message_source == "edge"
 if a.with_edge_stream:
     m.edge_precision, m.node_precision = "bf16", "fp16x2"      # bench.py's edge stream
 opt = torch.optim.Adam(m.parameters(), lr=1e-4)
@@ -59,7 +63,9 @@ for _ in range(a.iters):
     step()
 torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) / a.iters * 1e3
-print(f"training step ({'edge stream forward included' if a.with_edge_stream else 'edge stream skipped (F1)'}): {ms:.2f} ms  "
+what = ("message_source edge (both streams differentiated)" if a.message_source == "edge" else
+        "edge stream forward included" if a.with_edge_stream else "edge stream skipped (F1)")
+print(f"training step ({what}, {a.train_precision}): {ms:.2f} ms  "
       f"({n} particles, k={k}, latent {d}, hidden {hd}, {L} rounds; "
       f"{n * k * L / ms / 1e6:.3f} G edge-updates/s)", flush=True)
 with ops.OpTimer() as tm:
@@ -67,3 +73,13 @@ with ops.OpTimer() as tm:
 for name, (calls, total) in sorted(tm.summary().items(), key=lambda kv: -kv[1][1]):
     print(f"  {name:16s} {calls:4d} calls {total:9.3f} ms", flush=True)
 print(f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB")
+if a.message_source == "edge":      # cgnn_edge_mlp_backward per call against its byte and matrix floors
+    ne, H, nh = n * k, hd, 2
+    calls, total = tm.summary().get("edge_mlp_backward", (0, 0.0))
+    if calls:
+        per = total / calls
+        # read e, de_in, d_agg rows, P rows; write h, g_a (nh each), g_o, zhat, dy, de_out
+        nbytes = 4 * ne * (2 * d + 2 * H + 2 * nh * H + 4 * d)
+        flops = 2 * ne * (2 * (d * H + (nh - 1) * H * H + H * d) + H * d)     # recompute + data gradient
+        print(f"  edge_mlp_backward {per:.3f} ms per call: {nbytes / 1e9:.2f} GB -> byte floor {nbytes / 6.3e12 * 1e3:.3f} ms "
+              f"at 6.3 TB/s; {flops / 1e12:.3f} TFLOP -> matrix floor {flops / 157e12 * 1e3:.3f} ms (f32 MFMA, 157 TFLOP/s)")
