@@ -39,7 +39,7 @@ EXPORTS = (
     "cgnn_col_dot", "cgnn_col_dot2", "cgnn_col_dot_workspace_bytes", "cgnn_col_dot_ordered", "cgnn_weight_grad_workspace_bytes", "cgnn_weight_grad_ordered", "cgnn_csr_workspace_bytes", "cgnn_csr_build",
     "cgnn_aggregate_csr", "cgnn_aggregate_csr_add", "cgnn_edge_stream", "cgnn_edge_stream_image_bytes", "cgnn_edge_stream_image_build",
     "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
-    "cgnn_edge_mlp_backward", "cgnn_linear2_rows",
+    "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add",
 )
 ROWS, TILED32 = 0, 1
 
@@ -114,6 +114,7 @@ def load() -> C.CDLL:
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_gather_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_scatter_rows.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.cgnn_halo_return_add.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, i64, vp]
     lib.cgnn_mlp_backward.argtypes = [C.POINTER(Mlp), C.POINTER(Linear), C.POINTER(Mlp), C.POINTER(Linear), vp, i32, vp,
                                       i32, vp, i32, i64, C.POINTER(MlpBwdBuffers), vp, i32, vp, i32, vp]
     lib.cgnn_edge_mlp_backward.argtypes = [C.POINTER(Mlp), C.POINTER(Mlp), vp, vp, vp, vp, i64, vp, vp, vp,

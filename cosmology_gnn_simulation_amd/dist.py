@@ -26,6 +26,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops, synthetic
+from ._lib import CgnnError
 
 
 # ----------------------------------------------------------------------------
@@ -248,6 +249,7 @@ class HaloExchange:
         self.sh, self.group = sh, group
         self.pack = pack_fn or (lambda table, idx, out: ops.gather_rows(table, idx, out))
         self._buf = None
+        self._ret = None
 
     def start(self, table: torch.Tensor):
         """Pack the rows the peers asked for and start the all-to-all into ``table``'s ghost block; returns a handle
@@ -279,6 +281,53 @@ class HaloExchange:
 
     def __call__(self, table: torch.Tensor) -> None:
         self.finish(self.start(table))
+
+    # backward: the reverse all-to-all (the forward's split sizes swapped)
+    def start_return(self, grad_ghost: torch.Tensor):
+        """Send the gradient of every ghost row (``grad_ghost`` [n_ghost, W], grouped by owner like the ghost block) back
+        to its owner; returns a handle for :meth:`finish_return`.  What comes back is, per peer in rank order, the
+        gradients of the rows this rank sent it (``send_idx`` order): [sum(send_counts), W]."""
+        import torch.distributed as dist
+        sh = self.sh
+        shape = (int(sum(sh.send_counts)), grad_ghost.shape[1])
+        cdev = _comm_device(grad_ghost.device, self.group)
+        if cdev == grad_ghost.device:
+            if self._ret is None or tuple(self._ret.shape) != shape or self._ret.device != grad_ghost.device:
+                self._ret = torch.empty(shape, dtype=grad_ghost.dtype, device=grad_ghost.device)
+            work = dist.all_to_all_single(self._ret, grad_ghost, output_split_sizes=sh.send_counts,
+                                          input_split_sizes=sh.recv_counts, group=self.group, async_op=True)
+            return (work, None, self._ret)
+        # gloo rehearsal with device tensors: stage through host memory
+        recv = torch.empty(shape, dtype=grad_ghost.dtype, device=cdev)
+        work = dist.all_to_all_single(recv, grad_ghost.to(cdev), output_split_sizes=sh.send_counts,
+                                      input_split_sizes=sh.recv_counts, group=self.group, async_op=True)
+        return (work, recv, grad_ghost.device)
+
+    def finish_return(self, handle) -> torch.Tensor:
+        """Wait for :meth:`start_return`; returns the received gradient rows on the gradients' device."""
+        work, recv, out = handle
+        work.wait()
+        return out if recv is None else recv.to(out)
+
+
+def halo_return_plan(send_idx: torch.Tensor, send_counts: Sequence[int], n_owned: int):
+    """The plan of ``ops.halo_return_add`` for one shard: ``(rows, seg_ptr, col)`` int32 on ``send_idx``'s device.
+    Position p of the reverse exchange's output carries the gradient for owned row ``send_idx[p]`` (the forward's pack
+    order: grouped by peer, ascending rank).  ``rows``: the distinct requested rows, ascending; ``col[seg_ptr[j] ..
+    seg_ptr[j + 1]]``: row j's positions, ascending, hence in ascending peer rank.  Validated here, once per shard."""
+    idx = send_idx.reshape(-1).long()
+    counts = [int(c) for c in send_counts]
+    if any(c < 0 for c in counts) or sum(counts) != idx.numel():
+        raise CgnnError(f"halo_return_plan: send counts {counts} do not add up to the {idx.numel()} rows of send_idx")
+    if idx.numel() >= 2 ** 31:
+        raise CgnnError("halo_return_plan: more than 2^31 - 1 returned rows")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_owned):
+        raise CgnnError(f"halo_return_plan: send_idx holds rows outside the {n_owned} owned rows")
+    vals, pos = torch.sort(idx, stable=True)
+    rows, cnt = torch.unique_consecutive(vals, return_counts=True)
+    seg_ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=idx.device)
+    torch.cumsum(cnt, 0, out=seg_ptr[1:])
+    return rows.to(torch.int32), seg_ptr.to(torch.int32), pos.to(torch.int32)
 
 
 # ----------------------------------------------------------------------------
@@ -471,6 +520,274 @@ class ShardedForward:
                     self.halo(self.x_all)
                     self.round(i)
             return self.decode()
+
+
+# ----------------------------------------------------------------------------
+# sharded training (message_source="x_j")
+# ----------------------------------------------------------------------------
+
+def _all_reduce_(t: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place SUM over the group (staged through host memory under gloo with device tensors)."""
+    import torch.distributed as dist
+    cdev = _comm_device(t.device, group)
+    if cdev == t.device:
+        dist.all_reduce(t, group=group)
+        return t
+    h = t.to(cdev)
+    dist.all_reduce(h, group=group)
+    return t.copy_(h)
+
+
+class _AllReduceSum(torch.autograd.Function):
+    """Sum over the ranks of a value every rank then uses in full; the backward is the identity (each rank's
+    contribution enters the sum with weight one, and the term built on it is replicated, not summed)."""
+
+    @staticmethod
+    def forward(ctx, t, group):
+        return _all_reduce_(t.detach().clone(), group)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def sharded_training_loss(pred: dict, y_acc: torch.Tensor, y_tr: torch.Tensor, n_total: int, dt: float,
+                          acc_w: float = 1.0, tr_w: float = 1.0, mom_w: float = 0.0, group=None, batch=None):
+    """The reference's ``combined_loss`` (train.py:255-260) of a snapshot split over the ranks, from this rank's owned
+    predictions ``pred`` and targets.  Returns ``(loss_to_backprop, global_value)``:
+
+    * the MSE terms are this rank's sums of squares over the *global* element counts, so that the ranks' terms add up
+      to the global means;
+    * the momentum term is built on the global per-graph column sums (``ops.segment_colsum`` in float64, summed over
+      the ranks with an identity backward): it is the same on every rank, and each rank's rows receive their share
+      of its gradient once;
+    * ``global_value`` (0-d float64) is the all-reduced loss, the value ``combined_loss`` has on the whole snapshot.
+
+    Summing the ranks' parameter gradients of ``loss_to_backprop`` gives the gradient of ``global_value``."""
+    from .losses import _SegmentColsum
+    if batch is not None:
+        raise NotImplementedError("sharded training takes one graph (snapshot) per shard; multi-graph batches are not "
+                                  "supported")
+    acc, tr = pred["acceleration"], pred["temp_rate"]
+    mse = acc_w * ((acc - y_acc) ** 2).sum() / float(n_total * acc.shape[1]) + \
+        tr_w * ((tr - y_tr) ** 2).sum() / float(n_total * tr.shape[1])
+    sums = _AllReduceSum.apply(_SegmentColsum.apply(acc, None, 1), group)          # [1, 3] float64, global
+    mom = (mom_w * torch.sum((sums * float(dt)) ** 2)).to(torch.float32)
+    part = mse.detach().double().reshape(1).clone()
+    value = _all_reduce_(part, group)[0] + mom.detach().double()
+    return mse + mom, value
+
+
+class ShardedTraining:
+    """A training step of ``EncodeProcessDecode`` (``message_source="x_j"``, ``train_precision`` "fp32" / "fp32x3") over one
+    spatial tile: the node stream of :class:`training._NodeStream` on the owned rows, with one halo exchange of the f32
+    latents per round in the forward and one reverse exchange of their gradients per round in the backward.
+
+    Forward of round i: ``x_i`` (owned rows) is staged into the local table ``[owned | ghosts]``, the exchange fills the
+    ghosts while the interior receivers (no ghost sender) aggregate and run the node block, then the boundary receivers
+    do.  Only the owned rows of ``x_i`` and ``agg_i`` are kept for the backward.
+
+    Backward of round i (``dx`` = dL/dx_{i+1} on the owned rows): ``du1, du2 = backward of the node MLP``; the ghost pass
+    ``A^T du2`` on the ghost rows of the local sender CSR, written into the send buffer; the reverse all-to-all starts;
+    the owned pass ``dx <- dx + du1 + A^T du2`` runs under it; the returned rows are added into ``dx``
+    (``ops.halo_return_add``).  The encoder's backward gives ``dx0`` of the owned particles.  The ranks' parameter
+    gradients are summed by ONE all-reduce of a flat buffer, so ``.grad`` is the global gradient on every rank.
+
+    The pieces are methods so that one process can interleave several shards (tests); ``__call__`` runs them through a
+    ``torch.autograd.Function`` for a real process group.  ``halo`` needs ``start`` / ``finish`` and ``start_return`` /
+    ``finish_return`` (:class:`HaloExchange`, the default)."""
+
+    def __init__(self, model, shard: Shard, halo=None, group=None):
+        if model.message_source != "x_j":
+            raise NotImplementedError("sharded training is built for message_source='x_j'; 'edge' models train on one "
+                                      "GPU (model.train_edge_messages)")
+        if getattr(model, "train_edge_stream", False):
+            raise NotImplementedError("sharded training does not run the (dead) edge stream: model.train_edge_stream "
+                                      "is single-GPU only")
+        if getattr(shard, "batch", None) is not None:
+            raise NotImplementedError("sharded training takes one graph (snapshot) per shard; multi-graph batches are "
+                                      "not supported")
+        if shard.send_idx is None:
+            raise CgnnError("ShardedTraining: the shard has no send plan (finish_shard / exchange_requests first)")
+        self.model, self.sh, self.group = model, shard, group
+        self.halo = halo if halo is not None else HaloExchange(shard, group)
+        self.packs = None
+        self._table = None
+        self._ghost = None
+        self._csr = None
+        self._plan = None
+
+    # -- set-up ------------------------------------------------------------------------------------------------------
+    def _prepare(self, x0: torch.Tensor) -> None:
+        m, sh = self.model, self.sh
+        with torch.no_grad():
+            m._materialize_all(x0.shape[1], sh.edge_attr.shape[1])
+            self.packs = m._train_packs()       # refuses what the training kernels do not take (CgnnError)
+        if self._csr is None:
+            self._csr = ops.SenderCsr(sh.src_local, sh.dst_local, sh.n_local)       # senders <- receivers, once per shard
+            self._plan = halo_return_plan(sh.send_idx.to(x0.device), sh.send_counts, sh.n_owned)
+
+    def _src_part(self, a: int, b: int) -> torch.Tensor:
+        """The sender list of owned receivers [a, b) as one tensor OBJECT per part (the aggregation plan is cached on it)."""
+        parts = self.__dict__.setdefault("_src_parts", {})
+        if (a, b) not in parts:
+            k = self.sh.k
+            parts[(a, b)] = self.sh.src_local[a * k:b * k]
+        return parts[(a, b)]
+
+    # -- forward pieces ----------------------------------------------------------------------------------------------
+    def encode(self, x0: Optional[torch.Tensor] = None) -> None:
+        """Node encoder on the owned rows (``x0`` defaults to ``shard.x_feat``)."""
+        sh = self.sh
+        x0 = (sh.x_feat if x0 is None else x0).detach().float().contiguous()
+        if x0.shape[0] != sh.n_owned:
+            raise CgnnError(f"ShardedTraining: {x0.shape[0]} input rows for {sh.n_owned} owned particles")
+        self._prepare(x0)
+        D = self.packs.latent
+        self.x0 = x0
+        self.xs = [ops.mlp_rows(self.packs.enc.fwd, x0)]      # raw features: three bf16 terms or exact
+        self.aggs = []
+        if self._table is None or tuple(self._table.shape) != (sh.n_local, D) or self._table.device != x0.device:
+            self._table = torch.empty((sh.n_local, D), dtype=torch.float32, device=x0.device)
+
+    def stage(self, i: int) -> torch.Tensor:
+        """Round ``i``'s local table: the owned rows hold ``x_i``; the exchange is to fill the ghost rows."""
+        no, D = self.sh.n_owned, self.packs.latent
+        self._table[:no].copy_(self.xs[i])
+        self.aggs.append(torch.empty((no, D), dtype=torch.float32, device=self._table.device))
+        self.xs.append(torch.empty((no, D), dtype=torch.float32, device=self._table.device))
+        return self._table
+
+    def round_nodes(self, i: int, part: str = "all") -> None:
+        """Aggregation and node block of round ``i`` for the owned receivers of ``part``: ``"interior"`` (no ghost sender:
+        may run under the exchange), ``"boundary"`` (after it) or ``"all"``."""
+        sh = self.sh
+        no, ni, k = sh.n_owned, sh.n_interior, sh.k
+        a, b = {"all": (0, no), "interior": (0, ni), "boundary": (ni, no)}[part]
+        if b <= a:
+            return
+        r = self.packs.rounds[i]
+        src = self._src_part(a, b)
+        agg = self.aggs[i][a:b]
+        ops.aggregate(self._table, src, None, b - a, k, (b - a) * k, agg,
+                      plan=ops.AggregatePlan.of(src, b - a, k, self._table.shape[1]))
+        ops.node_block(r.run, r.run.layers[0], r.run2, self.xs[i][a:b], agg, self.xs[i + 1][a:b], residual=True)
+
+    def decode(self):
+        xl = self.xs[-1]
+        return ops.mlp_rows(self.packs.dec_acc.run, xl), ops.mlp_rows(self.packs.dec_tr.run, xl)
+
+    # -- backward pieces ---------------------------------------------------------------------------------------------
+    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
+        """Seeds ``dx`` = dL/dx_L from the decoders' output gradients (``None``: zero)."""
+        p, sh = self.packs, self.sh
+        no, D = sh.n_owned, p.latent
+        dev = self.x0.device
+        self.scratch = ops.BackwardScratch(no, p.hidden, max(D, 32), p.nh, dev)
+        self.grads_of = {}
+        zero = lambda t, w: torch.zeros((no, w), dtype=torch.float32, device=dev) if t is None else t  # noqa: E731
+        xl = self.xs[-1]
+        dx, _, self.grads_of[id(p.dec_acc)] = p.dec_acc.backward(xl, None, zero(d_acc, p.dec_acc.out_dim), self.scratch, True)
+        dx2, _, self.grads_of[id(p.dec_tr)] = p.dec_tr.backward(xl, None, zero(d_tr, p.dec_tr.out_dim), self.scratch, True)
+        self.dx = dx.add_(dx2)
+
+    def round_backward_local(self, i: int) -> torch.Tensor:
+        """Steps 1-2 of round ``i``: the node MLP's backward on the owned rows, then ``A^T du2`` for the ghost rows,
+        written into (and returned as) the send buffer of the reverse exchange, [n_ghost, D]."""
+        sh = self.sh
+        r = self.packs.rounds[i]
+        du1, du2, self.grads_of[id(r)] = r.backward(self.xs[i], self.aggs[i], self.dx, self.scratch, True, True)
+        self.aggs[i] = None
+        self._du = (du1, du2)
+        shape = (sh.n_ghost, self.packs.latent)
+        if self._ghost is None or tuple(self._ghost.shape) != shape or self._ghost.device != du2.device:
+            self._ghost = torch.empty(shape, dtype=torch.float32, device=du2.device)
+        if sh.n_ghost:
+            ops.aggregate_csr(du2, self._csr, out=self._ghost, row_range=(sh.n_owned, sh.n_local))
+        return self._ghost
+
+    def round_backward_owned(self, i: int) -> None:
+        """Step 4 (runs under the reverse exchange): ``dx <- dx + du1 + A^T du2`` on the owned rows."""
+        du1, du2 = self._du
+        self._du = None
+        ops.aggregate_csr(du2, self._csr, out=self.dx, add1=self.dx, add2=du1, row_range=(0, self.sh.n_owned))
+        self.xs[i + 1] = None
+
+    def round_backward_return(self, ret: torch.Tensor) -> None:
+        """Step 5: the gradient rows the peers returned, added into ``dx`` at the rows they had requested."""
+        if ret.shape[0]:
+            ops.halo_return_add(self.dx, ret, *self._plan)
+
+    def encode_backward(self, need_dx0: bool = True) -> Optional[torch.Tensor]:
+        p = self.packs
+        dx0, _, self.grads_of[id(p.enc)] = p.enc.backward(self.x0, None, self.dx, self.scratch, need_dx0)
+        self.dx = None
+        return dx0
+
+    def local_grads(self) -> List[torch.Tensor]:
+        """This rank's partial parameter gradients, in ``TrainPacks.params()`` order."""
+        return [g for m in self.packs.all for g in self.grads_of[id(m)]]
+
+    # -- one step through a process group ----------------------------------------------------------------------------
+    def run_forward(self, x0: Optional[torch.Tensor] = None):
+        """Encoder, rounds with the exchange hidden behind the interior receivers, decoders: ``(acc, temp_rate)``."""
+        self.encode(x0)
+        overlap = 0 < self.sh.n_interior
+        for i in range(len(self.packs.rounds)):
+            table = self.stage(i)
+            if overlap:
+                handle = self.halo.start(table)
+                self.round_nodes(i, "interior")
+                self.halo.finish(handle)
+                self.round_nodes(i, "boundary")
+            else:
+                self.halo.finish(self.halo.start(table))
+                self.round_nodes(i, "all")
+        return self.decode()
+
+    def run_backward(self, d_acc, d_tr, need_dx0: bool = True):
+        """-> (dx0 of the owned rows, global parameter gradients in ``TrainPacks.params()`` order)."""
+        self.decode_backward(d_acc, d_tr)
+        for i in range(len(self.packs.rounds) - 1, -1, -1):
+            handle = self.halo.start_return(self.round_backward_local(i))
+            self.round_backward_owned(i)
+            self.round_backward_return(self.halo.finish_return(handle))
+        dx0 = self.encode_backward(need_dx0)
+        grads = self.local_grads()
+        self.xs = self.aggs = None
+        flat = torch.cat([g.reshape(-1) for g in grads])
+        _all_reduce_(flat, self.group)              # one all-reduce of every parameter gradient
+        out, off = [], 0
+        for g in grads:
+            out.append(flat[off:off + g.numel()].view_as(g))
+            off += g.numel()
+        return dx0, out
+
+    def __call__(self, x0: Optional[torch.Tensor] = None) -> dict:
+        """Differentiable predictions of the owned particles (local order; ``shard.owned_global`` maps them back).  The
+        backward leaves the global gradient in every node-stream parameter's ``.grad``; edge-model parameters keep
+        ``grad = None``, as on one GPU."""
+        x = self.sh.x_feat if x0 is None else x0
+        self._prepare(x.detach().float())
+        acc, tr = _ShardedNodeStream.apply(self, x, *self.packs.params())
+        return {"acceleration": acc, "temp_rate": tr}
+
+
+class _ShardedNodeStream(torch.autograd.Function):
+    """``acceleration, temp_rate`` of the owned rows = f(x0 owned; node-stream parameters) over a process group."""
+
+    @staticmethod
+    def forward(ctx, runner: ShardedTraining, x0: torch.Tensor, *params: torch.Tensor):
+        ctx.runner = runner
+        return runner.run_forward(x0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_acc, d_tr):
+        runner = ctx.runner
+        ctx.runner = None
+        dx0, grads = runner.run_backward(d_acc, d_tr, ctx.needs_input_grad[1])
+        return (None, dx0, *grads)
 
 
 # ----------------------------------------------------------------------------

@@ -784,10 +784,16 @@ class SenderCsr:
 
 
 def aggregate_csr(table: torch.Tensor, csr: SenderCsr, out: Optional[torch.Tensor] = None,
-                  add1: Optional[torch.Tensor] = None, add2: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``out[r] = (add1[r] + add2[r] +) sum_{p in row r} table[csr.col[p]]``; ``out`` may be ``add1`` or ``add2``."""
+                  add1: Optional[torch.Tensor] = None, add2: Optional[torch.Tensor] = None,
+                  row_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """``out[r] = (add1[r] + add2[r] +) sum_{p in row r} table[csr.col[p]]``; ``out`` may be ``add1`` or ``add2``.
+    ``row_range = (a, b)``: only the CSR's rows [a, b), written to (and added from) rows [0, b - a) of ``out`` / ``add1`` /
+    ``add2`` (``row_ptr`` holds absolute positions, so the range is a pointer offset)."""
     table = f32c(table, "table")
-    shape = (csr.rows, table.shape[1])
+    a, b = (0, csr.rows) if row_range is None else (int(row_range[0]), int(row_range[1]))
+    if not 0 <= a <= b <= csr.rows:
+        raise CgnnError(f"aggregate_csr: row range [{a}, {b}) outside the CSR's {csr.rows} rows")
+    shape = (b - a, table.shape[1])
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=table.device)
     for t, name in ((add1, "add1"), (add2, "add2"), (out, "out")):
@@ -795,10 +801,33 @@ def aggregate_csr(table: torch.Tensor, csr: SenderCsr, out: Optional[torch.Tenso
                               or t.device != table.device):
             raise CgnnError(f"aggregate_csr: {name} must be contiguous float32 {shape} on the table's device")
     with _timed("aggregate_csr", table.device):
-        check(_lib.load().cgnn_aggregate_csr_add(table.data_ptr(), csr.row_ptr.data_ptr(), csr.col.data_ptr(), csr.rows,
-                                                 table.shape[1], ptr(add1), ptr(add2), out.data_ptr(),
+        check(_lib.load().cgnn_aggregate_csr_add(table.data_ptr(), csr.row_ptr.data_ptr() + 4 * a, csr.col.data_ptr(),
+                                                 b - a, table.shape[1], ptr(add1), ptr(add2), out.data_ptr(),
                                                  stream_ptr(table.device)), "cgnn_aggregate_csr_add")
     return out
+
+
+def halo_return_add(table: torch.Tensor, ret: torch.Tensor, rows: torch.Tensor, seg_ptr: torch.Tensor,
+                    col: torch.Tensor) -> torch.Tensor:
+    """``table[rows[j]] += sum_{p in [seg_ptr[j], seg_ptr[j + 1])} ret[col[p]]`` in place, in ascending ``p``
+    (``cgnn_halo_return_add``): the gradient rows peers return through the reverse halo exchange.  The plan
+    ``(rows, seg_ptr, col)`` comes from :func:`dist.halo_return_plan`."""
+    require_device(table, "table")
+    if table.dim() != 2 or table.dtype != torch.float32 or not table.is_contiguous():
+        raise CgnnError("halo_return_add: table must be a contiguous float32 [rows, width] tensor")
+    width = table.shape[1]
+    ret = f32c(ret, "ret")
+    if ret.dim() != 2 or ret.shape[1] != width:
+        raise CgnnError(f"halo_return_add: ret is {tuple(ret.shape)}, the table's rows are {width} wide")
+    rows, seg_ptr, col = i32c(rows, "rows"), i32c(seg_ptr, "seg_ptr"), i32c(col, "col")
+    if seg_ptr.numel() != rows.numel() + 1:
+        raise CgnnError(f"halo_return_add: seg_ptr has {seg_ptr.numel()} entries for {rows.numel()} rows (need rows + 1)")
+    _same_device(table, ret, rows, seg_ptr, col)
+    with _timed("halo_return_add", table.device):
+        check(_lib.load().cgnn_halo_return_add(ret.data_ptr(), ret.shape[0], rows.data_ptr(), seg_ptr.data_ptr(),
+                                               col.data_ptr(), rows.numel(), width, table.data_ptr(), table.shape[0],
+                                               stream_ptr(table.device)), "cgnn_halo_return_add")
+    return table
 
 
 _COLDOT_WORKSPACE = {}

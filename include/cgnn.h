@@ -478,6 +478,22 @@ int cgnn_gather_rows(const float* table, const int32_t* idx, int64_t n_idx, int3
 int cgnn_scatter_rows(const float* rows, const int32_t* idx, int64_t n_idx, int32_t width,
                       float* table, void* stream);
 
+/* ---- backward of the halo exchange (multi-GPU training) --------------------------
+ * The gradient rows the peers return for the owned rows they read as ghosts, added in place:
+ *   table[rows[j], :] += sum_{p in [seg_ptr[j], seg_ptr[j+1])} ret[col[p], :]      for j in [0, num_rows)
+ * summed in the fixed order ((table[r] + ret[col[p0]]) + ret[col[p0+1]]) + ..., no atomics, one launch touching only
+ * the listed rows.
+ *   ret      float [num_ret, width]: the received gradient rows, in peer order
+ *   rows     int32 [num_rows]: the distinct owned rows at least one peer requested (ascending), < table_rows
+ *   seg_ptr  int32 [num_rows + 1]: row j's positions are col[seg_ptr[j] .. seg_ptr[j+1])
+ *   col      int32 [seg_ptr[num_rows]]: positions in ret, < num_ret, in ascending peer rank
+ *   width    a multiple of 4 in [4, 256]; ret and table rows are `width` floats, 16-byte aligned
+ * The plan (rows, seg_ptr, col) is host logic, built and validated once per shard (dist.halo_return_plan); rows or
+ * positions outside the tables are skipped, never read or written. */
+int cgnn_halo_return_add(const float* ret, int64_t num_ret, const int32_t* rows, const int32_t* seg_ptr,
+                         const int32_t* col, int64_t num_rows, int32_t width, float* table, int64_t table_rows,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
