@@ -489,13 +489,17 @@ __device__ __forceinline__ float torch_remainder(float a, float b) {   // torch.
     return r;
 }
 
+// rows == nullptr: row i of the output is particle i (n_rows == n); else particle rows[i] of the [W, n, 3] window.
+// One arithmetic serves both entries (cgnn_window_features / cgnn_window_features_rows); rows outside [0, n) are skipped.
 __global__ void window_features_kernel(const float* __restrict__ pos_seq, const float* __restrict__ temp_seq,
                                        const float* __restrict__ pos_noise, const float* __restrict__ temp_noise,
-                                       int W, int64_t n, float box, float dt, float vel_mean, float vel_std,
-                                       float temp_mean, float temp_std, float* __restrict__ x,
-                                       float* __restrict__ recent_pos) {
+                                       int W, int64_t n, const int64_t* __restrict__ rows, int64_t n_rows, float box,
+                                       float dt, float vel_mean, float vel_std, float temp_mean, float temp_std,
+                                       float* __restrict__ x, float* __restrict__ recent_pos) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n_rows) return;
+    const int64_t g = rows != nullptr ? rows[i] : i;
+    if (g < 0 || g >= n) return;
     const int F = 3 * (W - 1) + W;
     const float half = box * 0.5f, nhalf = -half;
     float* xr = x + i * F;
@@ -504,8 +508,8 @@ __global__ void window_features_kernel(const float* __restrict__ pos_seq, const 
         float cur[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float p = pos_seq[((int64_t)t * n + i) * 3 + c];
-            if (pos_noise != nullptr) p = __fadd_rn(p, pos_noise[(i * W + t) * 3 + c]);
+            float p = pos_seq[((int64_t)t * n + g) * 3 + c];
+            if (pos_noise != nullptr) p = __fadd_rn(p, pos_noise[(g * W + t) * 3 + c]);
             cur[c] = torch_remainder(p, box);
         }
         if (t > 0) {
@@ -520,12 +524,71 @@ __global__ void window_features_kernel(const float* __restrict__ pos_seq, const 
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) prev[c] = cur[c];
-        float T = temp_seq[(int64_t)t * n + i];
-        if (temp_noise != nullptr) T = __fadd_rn(T, temp_noise[i * W + t]);
+        float T = temp_seq[(int64_t)t * n + g];
+        if (temp_noise != nullptr) T = __fadd_rn(T, temp_noise[g * W + t]);
         xr[3 * (W - 1) + t] = __fdiv_rn(__fsub_rn(T, temp_mean), temp_std);
     }
+    if (recent_pos != nullptr) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) recent_pos[i * 3 + c] = prev[c];
+        for (int c = 0; c < 3; ++c) recent_pos[i * 3 + c] = prev[c];
+    }
+}
+
+// ------------------------------------------------------------------ rollout step (integrate, frame unpack)
+struct IntegrateStats {
+    float acc_std[3], acc_mean[3], tr_std, tr_mean;
+};
+
+// one_step.integrate_one_step for the listed particles, in torch's float32 order with one rounding per operation:
+//   acc = pred * std + mean;  v = (p1 - p2) * inv_dt;  nv = v + acc * dt;  np = remainder(p1 + nv * dt, box)
+//   rate = pred_t * std_t + mean_t;  nt = T1 + rate * dt
+// (ATen divides by a host scalar as a multiplication by its float32 reciprocal, inv_dt).  Row i of out is
+// (np[0..2], nt, id bits); rows [n_rows, n_out) and rows with an id outside [0, n) are padding: zeros and id -1.
+__global__ void rollout_integrate_kernel(const float* __restrict__ pos_prev2, const float* __restrict__ pos_prev1,
+                                         const float* __restrict__ temp_prev1, int64_t n,
+                                         const float* __restrict__ acc_pred, const float* __restrict__ rate_pred,
+                                         const int64_t* __restrict__ ids, int64_t n_rows, int64_t n_out,
+                                         IntegrateStats s, float dt, float inv_dt, float box, float* __restrict__ out) {
+#pragma clang fp contract(off)      // no a * b + c of this scope is fused into an FMA (HIP's __fmul_rn / __fadd_rn are plain
+                                    // operators in a header, outside this pragma: plain operators here instead)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    float* o = out + i * CGNN_ROLLOUT_ROW;
+    const int64_t g = i < n_rows ? ids[i] : -1;
+    if (g < 0 || g >= n) {
+        o[0] = 0.f;
+        o[1] = 0.f;
+        o[2] = 0.f;
+        o[3] = 0.f;
+        o[4] = __int_as_float(-1);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = acc_pred[i * 3 + c] * s.acc_std[c] + s.acc_mean[c];
+        const float p1 = pos_prev1[g * 3 + c];
+        const float v = (p1 - pos_prev2[g * 3 + c]) * inv_dt;
+        const float nv = v + a * dt;
+        o[c] = torch_remainder(p1 + nv * dt, box);
+    }
+    const float r = rate_pred[i] * s.tr_std + s.tr_mean;
+    o[3] = temp_prev1[g] + r * dt;
+    o[4] = __int_as_float((int32_t)g);
+}
+
+// pos[id] = row[0..2], temp[id] = row[3] for every row whose id (bits of row[4]) lies in [0, n); one thread per row
+__global__ void frame_unpack_kernel(const float* __restrict__ rows, int64_t n_rows, int64_t n, float* __restrict__ pos,
+                                    float* __restrict__ temp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const float* r = rows + i * CGNN_ROLLOUT_ROW;
+    const int64_t id = __float_as_int(r[4]);
+    if (id < 0 || id >= n) return;
+    const float x = r[0], y = r[1], z = r[2], t = r[3];
+    pos[id * 3 + 0] = x;
+    pos[id * 3 + 1] = y;
+    pos[id * 3 + 2] = z;
+    temp[id] = t;
 }
 
 // ------------------------------------------------------------------ momentum
@@ -779,9 +842,61 @@ int cgnn_window_features(const float* pos_seq, const float* temp_seq, const floa
     }
     if (n == 0) return CGNN_OK;
     window_features_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
-        pos_seq, temp_seq, pos_noise, temp_noise, window, n, box_size, dt, vel_mean, vel_std, temp_mean, temp_std, x,
-        recent_pos);
+        pos_seq, temp_seq, pos_noise, temp_noise, window, n, nullptr, n, box_size, dt, vel_mean, vel_std, temp_mean,
+        temp_std, x, recent_pos);
     return check_hip(hipGetLastError(), "cgnn_window_features launch");
+}
+
+int cgnn_window_features_rows(const float* pos_seq, const float* temp_seq, int32_t window, int64_t n_total,
+                              const int64_t* rows, int64_t n_rows, float box_size, float dt, float vel_mean,
+                              float vel_std, float temp_mean, float temp_std, float* x, float* recent_pos,
+                              void* stream) {
+    if (window < 2 || n_total < 0 || n_rows < 0 || !(box_size > 0.f) || dt == 0.f || vel_std == 0.f ||
+        temp_std == 0.f || (n_rows > 0 && (!pos_seq || !temp_seq || !rows || !x || n_total == 0))) {
+        set_error("cgnn_window_features_rows: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n_rows == 0) return CGNN_OK;
+    window_features_kernel<<<(unsigned)((n_rows + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        pos_seq, temp_seq, nullptr, nullptr, window, n_total, rows, n_rows, box_size, dt, vel_mean, vel_std, temp_mean,
+        temp_std, x, recent_pos);
+    return check_hip(hipGetLastError(), "cgnn_window_features_rows launch");
+}
+
+int cgnn_rollout_integrate(const float* pos_prev2, const float* pos_prev1, const float* temp_prev1, int64_t n_total,
+                           const float* acc_pred, const float* temp_rate_pred, const int64_t* ids, int64_t n_rows,
+                           int64_t n_out, const float* stats, float dt, float box_size, float* out, void* stream) {
+    if (n_total < 0 || n_total > INT32_MAX || n_rows < 0 || n_out < n_rows || !stats || !(box_size > 0.f) ||
+        dt == 0.f || (n_out > 0 && !out) ||
+        (n_rows > 0 && (!pos_prev2 || !pos_prev1 || !temp_prev1 || !acc_pred || !temp_rate_pred || !ids ||
+                        n_total == 0))) {
+        set_error("cgnn_rollout_integrate: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n_out == 0) return CGNN_OK;
+    IntegrateStats s;
+    for (int c = 0; c < 3; ++c) {
+        s.acc_std[c] = stats[c];
+        s.acc_mean[c] = stats[3 + c];
+    }
+    s.tr_std = stats[6];
+    s.tr_mean = stats[7];
+    const float inv_dt = 1.0f / dt;      // float32, as ATen forms the reciprocal of a host scalar divisor
+    rollout_integrate_kernel<<<(unsigned)((n_out + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        pos_prev2, pos_prev1, temp_prev1, n_total, acc_pred, temp_rate_pred, ids, n_rows, n_out, s, dt, inv_dt,
+        box_size, out);
+    return check_hip(hipGetLastError(), "cgnn_rollout_integrate launch");
+}
+
+int cgnn_frame_unpack(const float* rows, int64_t n_rows, int64_t n_total, float* pos, float* temp, void* stream) {
+    if (n_rows < 0 || n_total < 0 || n_total > INT32_MAX || (n_rows > 0 && (!rows || !pos || !temp || n_total == 0))) {
+        set_error("cgnn_frame_unpack: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n_rows == 0) return CGNN_OK;
+    frame_unpack_kernel<<<(unsigned)((n_rows + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        rows, n_rows, n_total, pos, temp);
+    return check_hip(hipGetLastError(), "cgnn_frame_unpack launch");
 }
 
 int cgnn_segment_colsum(const float* acc, const int32_t* batch, int64_t n, int32_t width, int32_t num_graphs,

@@ -201,6 +201,7 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
     sh = Shard(rank, world, k, n_owned, ghosts.numel(), owned, ghosts, src_local, dst_local, edge_attr,
                recv_counts, want_global=want, knn_ms=knn_ms, n_interior=n_interior)
     sh._g2l = g2l
+    sh._owner = owner            # every particle's rank (the sharded rollout sizes its send blocks from it)
     sh.subset_build_ms = build_ms
     return sh
 
@@ -788,6 +789,215 @@ class _ShardedNodeStream(torch.autograd.Function):
         ctx.runner = None
         dx0, grads = runner.run_backward(d_acc, d_tr, ctx.needs_input_grad[1])
         return (None, dx0, *grads)
+
+
+# ----------------------------------------------------------------------------
+# sharded rollout (reference render_rollout.rollout over spatial tiles)
+# ----------------------------------------------------------------------------
+
+def _world_of(group=None) -> Tuple[int, int]:
+    """``(world, rank)`` of the group; a world of one when no process group is up."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size(group), dist.get_rank(group)
+    return 1, 0
+
+
+def rollout_arguments(data: dict, window_size: int, num_neighbors: int, num_steps: Optional[int]):
+    """Checks a rollout's arguments before any device work; returns ``(coords, energy [T, N, 1], total_time)`` with
+    ``total_time`` the frame count ``rollout.rollout`` produces."""
+    coords, energy = data["Coordinates"], data["InternalEnergy"]
+    if energy.dim() == 2:
+        energy = energy.unsqueeze(-1)
+    if window_size < 2:
+        raise ValueError(f"sharded rollout: window_size {window_size} < 2 (velocities need two frames)")
+    if coords.dim() != 3 or coords.shape[2] != 3 or energy.dim() != 3 or tuple(energy.shape[:2]) != tuple(coords.shape[:2]):
+        raise ValueError(f"sharded rollout: Coordinates [T, N, 3] and InternalEnergy [T, N(, 1)], got "
+                         f"{tuple(coords.shape)} / {tuple(data['InternalEnergy'].shape)}")
+    n = coords.shape[1]
+    if coords.shape[0] < window_size:
+        raise ValueError(f"sharded rollout: {coords.shape[0]} frames, fewer than the window of {window_size}")
+    if num_neighbors < 1 or num_neighbors > n:
+        raise ValueError(f"sharded rollout: num_neighbors {num_neighbors} outside [1, {n}] (N = {n})")
+    if n >= 2 ** 31:
+        raise ValueError("sharded rollout: more than 2^31 - 1 particles (ids travel as int32)")
+    if num_steps is not None and num_steps < 0:
+        raise ValueError(f"sharded rollout: num_steps {num_steps} < 0")
+    total = coords.shape[0] if num_steps is None else window_size + num_steps
+    return coords, energy, total
+
+
+def rollout_capacity(owner: torch.Tensor, world: int) -> Tuple[List[int], int]:
+    """``(owned count of every rank, cap = the largest)`` from the replicated owner of every particle: every rank knows
+    every rank's count, hence the common send-block size, without a collective."""
+    counts = torch.bincount(owner.reshape(-1).long(), minlength=world)
+    if counts.numel() != world:
+        raise CgnnError(f"rollout_capacity: owners outside [0, {world})")
+    counts = counts.tolist()
+    return counts, max(counts)
+
+
+def window_checksum(coords_w: torch.Tensor, energy_w: torch.Tensor) -> torch.Tensor:
+    """float64 [4] fingerprint of an initial window (plain and position-weighted sums, frame by frame), computed on the
+    window's own device; non-finite sums are mapped to fixed values so that equal data compare equal."""
+    out = []
+    for t in (coords_w, energy_w):
+        s1 = torch.zeros((), dtype=torch.float64, device=t.device)
+        s2 = torch.zeros((), dtype=torch.float64, device=t.device)
+        w = None
+        for f in range(t.shape[0]):
+            x = t[f].reshape(-1).double()
+            if w is None:
+                w = torch.arange(x.numel(), dtype=torch.float64, device=t.device).remainder_(1021).add_(1.0)
+            s1 += x.sum()
+            s2 += (x * w).sum() * float(f + 1)
+        out += [s1, s2]
+    return torch.nan_to_num(torch.stack(out), nan=-1.0, posinf=1e300, neginf=-1e300)
+
+
+def _all_reduce_max_(t: torch.Tensor, group=None) -> torch.Tensor:
+    import torch.distributed as dist
+    cdev = _comm_device(t.device, group)
+    h = t if cdev == t.device else t.to(cdev)
+    dist.all_reduce(h, op=dist.ReduceOp.MAX, group=group)
+    return t if h is t else t.copy_(h)
+
+
+def check_same_data(coords_w: torch.Tensor, energy_w: torch.Tensor, device, group=None) -> None:
+    """One all-reduce (MAX of the checksum and of its negation): every rank raises ``ValueError`` together when the
+    ranks' initial windows differ, instead of running apart into mismatched collectives."""
+    c = window_checksum(coords_w, energy_w).to(device)
+    both = _all_reduce_max_(torch.cat([c, -c]), group).cpu()
+    hi, lo = both[:4], -both[4:]
+    if not torch.equal(hi, lo):
+        raise ValueError("sharded rollout: the ranks passed different data (initial-window checksums differ)")
+
+
+def all_gather_rows(block: torch.Tensor, group=None) -> torch.Tensor:
+    """``[world * cap, W]``: every rank's ``[cap, W]`` block in rank order (one ``all_gather_into_tensor``; staged
+    through host memory under gloo with device tensors)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    shape = (world * block.shape[0], block.shape[1])
+    cdev = _comm_device(block.device, group)
+    if cdev == block.device:
+        out = torch.empty(shape, dtype=block.dtype, device=block.device)
+        dist.all_gather_into_tensor(out, block.contiguous(), group=group)
+        return out
+    out = torch.empty(shape, dtype=block.dtype, device=cdev)
+    dist.all_gather_into_tensor(out, block.to(cdev).contiguous(), group=group)
+    return out.to(block.device)
+
+
+class ShardedRollout:
+    """One rank's part of a rollout over spatial tiles.  The trajectory ``[T, N, 3]`` / ``[T, N, 1]`` is replicated on
+    every rank (as ``rollout.rollout`` holds it); ownership is recomputed from each step's last frame, so a particle
+    that crossed a tile plane belongs to its new tile from the next step on and nothing per particle has to move.
+
+    A step ``t`` is five pieces, separate so that one process can interleave several ranks (tests):
+
+    1. :meth:`plan`: the wrapped last frame of all N particles (``cgnn_window_features``' bits, what ``preprocess``
+       hands the k-NN) -> :func:`build_shard`, every rank's owned count and the send-block capacity ``cap``; the caller
+       then completes the ghost plan (:func:`exchange_requests` or :func:`finish_shard`);
+    2. :meth:`features`: the owned rows' node features straight from the window ``traj[t-W:t]``
+       (``cgnn_window_features_rows``);
+    3. :meth:`forward`: a :class:`ShardedForward` with the given halo;
+    4. :meth:`integrate`: ``cgnn_rollout_integrate`` -> the send block ``[cap, ROLLOUT_ROW]`` (padding id -1);
+    5. :meth:`publish`: the gathered ``[world * cap, ROLLOUT_ROW]`` rows -> frame ``t`` (``cgnn_frame_unpack``).
+
+    Buffers that depend on the owned count are made per step."""
+
+    def __init__(self, model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int = 6,
+                 num_neighbors: int = 16, num_steps: Optional[int] = None, device=None, world: int = 1, rank: int = 0):
+        coords, energy, total = rollout_arguments(data, window_size, num_neighbors, num_steps)
+        if not 0 <= rank < world:
+            raise ValueError(f"sharded rollout: rank {rank} outside a world of {world}")
+        if device is None:
+            device = next(model.parameters()).device
+        self.device = torch.device(device)
+        self.model, self.world, self.rank = model, world, rank
+        self.W, self.k, self.total_time = window_size, int(num_neighbors), total
+        self.n = coords.shape[1]
+        self.dt, self.box = float(dt), float(box_size)
+        self.meta = dict(metadata)
+        self.meta["dt"], self.meta["box_size"] = dt, box_size
+        self.stats = ops.integration_stats(self.meta)
+        # NaN until published: a particle no rank delivered cannot pass for a result
+        self.pos = torch.full((total, self.n, 3), float("nan"), dtype=torch.float32, device=self.device)
+        self.tmp = torch.full((total, self.n, 1), float("nan"), dtype=torch.float32, device=self.device)
+        self.pos[:window_size] = coords[:window_size].to(self.device).float()
+        self.tmp[:window_size] = energy[:window_size].to(self.device).float()
+        self.counts: List[int] = []
+        self.cap = 0
+
+    def plan(self, t: int) -> Shard:
+        """Step ``t``'s shard (no send plan yet) from the wrapped frame ``t - 1``; sets ``counts`` and ``cap``."""
+        _, recent = ops.window_features(self.pos[t - 2:t], self.tmp[t - 2:t], self.meta, self.dt, self.box)
+        if not bool(torch.isfinite(recent).all()):        # the neighbour search must never see a NaN position
+            raise CgnnError(f"sharded rollout: frame {t - 1} holds non-finite positions (rows that were never published, "
+                            f"or a diverged model)")
+        sh = build_shard(recent, self.box, self.k, self.world, self.rank)
+        self.counts, self.cap = rollout_capacity(sh._owner, self.world)
+        if self.counts[self.rank] != sh.n_owned:
+            raise CgnnError(f"rank {self.rank}: {sh.n_owned} owned particles, the owner map says {self.counts[self.rank]}")
+        return sh
+
+    def features(self, sh: Shard, t: int) -> torch.Tensor:
+        sh.x_feat, _ = ops.window_features_rows(self.pos[t - self.W:t], self.tmp[t - self.W:t], sh.owned_global,
+                                                self.meta, self.dt, self.box)
+        return sh.x_feat
+
+    def forward(self, sh: Shard, halo: Optional[Callable] = None) -> ShardedForward:
+        return ShardedForward(self.model, sh, halo)
+
+    def integrate(self, sh: Shard, pred: dict, t: int) -> torch.Tensor:
+        return ops.rollout_integrate(pred["acceleration"], pred["temp_rate"], self.pos[t - 2], self.pos[t - 1],
+                                     self.tmp[t - 1], sh.owned_global, self.meta, n_out=self.cap, stats=self.stats)
+
+    def publish(self, rows: torch.Tensor, t: int) -> None:
+        ops.frame_unpack(rows, self.pos[t], self.tmp[t])
+
+    def result(self) -> dict:
+        return {"Coordinates": self.pos, "InternalEnergy": self.tmp}
+
+
+def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: float, box_size: float,
+                    window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None, device=None,
+                    group=None) -> dict:
+    """``rollout.rollout`` over the ranks of ``group`` (a world of one when no process group is up): same arguments,
+    return value and frame count, and the same bits.  Every rank passes the same ``data`` (checked once, by one
+    all-reduce of a checksum) and returns the whole trajectory.  ``noise_std`` is ignored, as there.
+
+    Per step: the shard of the wrapped last frame, the ghost-id all-to-all, the forward with one halo all-to-all per
+    round, the integration of the owned particles and one all-gather of the packed rows into the next frame."""
+    del noise_std
+    rollout_arguments(data, window_size, num_neighbors, num_steps)
+    world, rank = _world_of(group)
+    import torch.distributed as dist
+    distributed = dist.is_available() and dist.is_initialized()
+    if device is None:
+        device = next(model.parameters()).device
+    device = torch.device(device)
+    model.eval()
+    with torch.no_grad():
+        if distributed:
+            energy = data["InternalEnergy"]
+            check_same_data(data["Coordinates"][:window_size], energy[:window_size], device, group)
+        runner = ShardedRollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps, device,
+                                world, rank)
+        for t in range(window_size, runner.total_time):
+            sh = runner.plan(t)
+            if distributed:
+                sh = exchange_requests(sh, group)
+                halo = HaloExchange(sh, group)
+            else:
+                sh = finish_shard(sh, sh.want_global)
+                halo = lambda table: None      # noqa: E731  (a world of one has no ghosts)
+            runner.features(sh, t)
+            pred = runner.forward(sh, halo)()
+            block = runner.integrate(sh, pred, t)
+            runner.publish(all_gather_rows(block, group) if distributed else block, t)
+    return runner.result()
 
 
 # ----------------------------------------------------------------------------

@@ -628,6 +628,114 @@ def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dic
     return x, recent
 
 
+def _scalar_stat(metadata: dict, key: str, what: str) -> float:
+    t = torch.as_tensor(metadata[key], dtype=torch.float32).reshape(-1)
+    if t.numel() != 1:
+        raise CgnnError(f"{what}: metadata statistic {key} must be a scalar")
+    return float(t[0])
+
+
+def _i64c(t: torch.Tensor, name: str) -> torch.Tensor:
+    require_device(t, name)
+    if t.dtype != torch.int64:
+        t = t.to(torch.int64)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def window_features_rows(pos_seq: torch.Tensor, temp_seq: torch.Tensor, rows: torch.Tensor, metadata: dict, dt: float,
+                         box_size: float, want_recent: bool = False):
+    """:func:`window_features` of the particles ``rows`` (int64 ids) of a ``[W, N, 3]`` / ``[W, N(, 1)]`` window, without
+    gathering the window first: ``(x [n_rows, 3(W-1)+W], recent_pos [n_rows, 3] or None)``, the same bits as
+    ``window_features(pos_seq[:, rows], temp_seq[:, rows], ...)``.  No noise.  Ids outside [0, N) leave their rows
+    unwritten (callers pass valid ids; the shard's owned list always is)."""
+    pos_seq = f32c(pos_seq, "position window")
+    temp_seq = f32c(temp_seq, "temperature window")
+    rows = _i64c(rows, "rows").reshape(-1)
+    w, n = pos_seq.shape[0], pos_seq.shape[1]
+    if pos_seq.dim() != 3 or pos_seq.shape != (w, n, 3) or temp_seq.numel() != w * n:
+        raise CgnnError(f"window_features_rows: expected [W, N, 3] and [W, N(, 1)], got {tuple(pos_seq.shape)} / "
+                        f"{tuple(temp_seq.shape)}")
+    nr = rows.numel()
+    x = torch.empty((nr, 3 * (w - 1) + w), dtype=torch.float32, device=pos_seq.device)
+    recent = torch.empty((nr, 3), dtype=torch.float32, device=pos_seq.device) if want_recent else None
+    _same_device(pos_seq, temp_seq, rows)
+    what = "window_features_rows"
+    with _timed(what, pos_seq.device):
+        check(_lib.load().cgnn_window_features_rows(
+            pos_seq.data_ptr(), temp_seq.data_ptr(), w, n, rows.data_ptr(), nr, float(box_size), float(dt),
+            _scalar_stat(metadata, "vel_mean", what), _scalar_stat(metadata, "vel_std", what),
+            _scalar_stat(metadata, "temp_mean", what), _scalar_stat(metadata, "temp_std", what), x.data_ptr(),
+            ptr(recent), stream_ptr(pos_seq.device)), "cgnn_window_features_rows")
+    return x, recent
+
+
+def integration_stats(metadata: dict) -> "C.Array":
+    """The 8 host floats :func:`rollout_integrate` takes (acc_std[3], acc_mean[3], temp_rate_std, temp_rate_mean):
+    every statistic is one float32 per component, or one value broadcast, as ``integrate_one_step`` broadcasts it."""
+    out = []
+    for key, width in (("acc_std", 3), ("acc_mean", 3), ("temp_rate_std", 1), ("temp_rate_mean", 1)):
+        t = torch.as_tensor(metadata[key], dtype=torch.float32).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(width)
+        if t.numel() != width:
+            raise CgnnError(f"rollout_integrate: metadata {key} must hold 1 or {width} values, got {t.numel()}")
+        out += [float(v) for v in t]
+    return (C.c_float * 8)(*out)
+
+
+def rollout_integrate(acc_pred: torch.Tensor, temp_rate_pred: torch.Tensor, pos_prev2: torch.Tensor,
+                      pos_prev1: torch.Tensor, temp_prev1: torch.Tensor, ids: torch.Tensor, metadata: dict,
+                      n_out: Optional[int] = None, stats=None) -> torch.Tensor:
+    """``one_step.integrate_one_step`` of the particles ``ids`` (predictions row i = particle ids[i]) in one launch,
+    packed: ``[n_out, ROLLOUT_ROW]`` rows (new position, new temperature, id bits), rows past ``ids.numel()`` padding
+    (id -1).  ``pos_prev2`` / ``pos_prev1`` [N, 3] and ``temp_prev1`` [N(, 1)]: the raw frames t-2 and t-1.  ``stats``:
+    :func:`integration_stats` of ``metadata`` (made here when omitted)."""
+    ids = _i64c(ids, "ids").reshape(-1)
+    nr = ids.numel()
+    n_out = nr if n_out is None else int(n_out)
+    if n_out < nr:
+        raise CgnnError(f"rollout_integrate: {nr} rows do not fit an output of {n_out}")
+    acc_pred, temp_rate_pred = f32c(acc_pred, "acc_pred"), f32c(temp_rate_pred, "temp_rate_pred")
+    pos_prev2, pos_prev1 = f32c(pos_prev2, "pos_prev2"), f32c(pos_prev1, "pos_prev1")
+    temp_prev1 = f32c(temp_prev1, "temp_prev1")
+    n = pos_prev1.shape[0]
+    if pos_prev1.shape != (n, 3) or pos_prev2.shape != (n, 3) or temp_prev1.numel() != n:
+        raise CgnnError(f"rollout_integrate: frames must be [N, 3], [N, 3], [N(, 1)], got {tuple(pos_prev2.shape)}, "
+                        f"{tuple(pos_prev1.shape)}, {tuple(temp_prev1.shape)}")
+    if acc_pred.shape != (nr, 3) or temp_rate_pred.numel() != nr:
+        raise CgnnError(f"rollout_integrate: predictions {tuple(acc_pred.shape)} / {tuple(temp_rate_pred.shape)} for "
+                        f"{nr} rows")
+    if stats is None:
+        stats = integration_stats(metadata)
+    out = torch.empty((n_out, _lib.ROLLOUT_ROW), dtype=torch.float32, device=pos_prev1.device)
+    _same_device(acc_pred, temp_rate_pred, pos_prev2, pos_prev1, temp_prev1, ids)
+    with _timed("rollout_integrate", pos_prev1.device):
+        check(_lib.load().cgnn_rollout_integrate(pos_prev2.data_ptr(), pos_prev1.data_ptr(), temp_prev1.data_ptr(), n,
+                                                 acc_pred.data_ptr(), temp_rate_pred.data_ptr(), ids.data_ptr(), nr,
+                                                 n_out, stats, float(metadata["dt"]), float(metadata["box_size"]),
+                                                 out.data_ptr(), stream_ptr(pos_prev1.device)), "cgnn_rollout_integrate")
+    return out
+
+
+def frame_unpack(rows: torch.Tensor, pos: torch.Tensor, temp: torch.Tensor) -> None:
+    """Scatter packed rows ``[R, ROLLOUT_ROW]`` into one frame, in place: ``pos [N, 3]``, ``temp [N(, 1)]`` (contiguous
+    float32, e.g. ``traj[t]``) at each row's embedded id; padding rows (id < 0) touch nothing."""
+    rows = f32c(rows, "rows")
+    require_device(pos, "pos")
+    require_device(temp, "temp")
+    if pos.dtype != torch.float32 or temp.dtype != torch.float32 or not pos.is_contiguous() or \
+            not temp.is_contiguous():
+        raise CgnnError("frame_unpack: pos / temp must be contiguous float32 (written in place)")
+    n = pos.shape[0]
+    if rows.dim() != 2 or rows.shape[1] != _lib.ROLLOUT_ROW or pos.shape != (n, 3) or temp.numel() != n:
+        raise CgnnError(f"frame_unpack: rows [R, {_lib.ROLLOUT_ROW}], pos [N, 3], temp [N(, 1)], got "
+                        f"{tuple(rows.shape)}, {tuple(pos.shape)}, {tuple(temp.shape)}")
+    _same_device(rows, pos, temp)
+    with _timed("frame_unpack", pos.device):
+        check(_lib.load().cgnn_frame_unpack(rows.data_ptr(), rows.shape[0], n, pos.data_ptr(), temp.data_ptr(),
+                                            stream_ptr(pos.device)), "cgnn_frame_unpack")
+
+
 def segment_colsum(acc: torch.Tensor, batch: Optional[torch.Tensor], num_graphs: int) -> torch.Tensor:
     acc = f32c(acc, "acc")
     if batch is not None:

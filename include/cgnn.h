@@ -464,6 +464,34 @@ int cgnn_window_features(const float* pos_seq, const float* temp_seq, const floa
                          int32_t window, int64_t n, float box_size, float dt, float vel_mean, float vel_std,
                          float temp_mean, float temp_std, float* x, float* recent_pos, void* stream);
 
+/* The same features for a list of rows of a [W, n_total, 3] / [W, n_total] window (the sharded rollout's owned
+ * particles, straight from the trajectory buffers): row i of x (and of recent_pos, which may be NULL) is particle
+ * rows[i].  Same kernel body and bits as cgnn_window_features, no noise; rows outside [0, n_total) are skipped. */
+int cgnn_window_features_rows(const float* pos_seq, const float* temp_seq, int32_t window, int64_t n_total,
+                              const int64_t* rows, int64_t n_rows, float box_size, float dt, float vel_mean,
+                              float vel_std, float temp_mean, float temp_std, float* x, float* recent_pos,
+                              void* stream);
+
+/* ---- sharded rollout step (reference render_rollout.py:73-85; one_step_test.py:84-105) ----------------------
+ * A packed frame row is CGNN_ROLLOUT_ROW floats: (x, y, z, temperature, int32 particle id bit-cast to float);
+ * id -1 marks a padding row.
+ *
+ * cgnn_rollout_integrate: one_step.integrate_one_step for the particles ids[0, n_rows), bit for bit:
+ *   acc = acc_pred[i] * acc_std + acc_mean;  v = (p1 - p2) * (1 / dt);  nv = v + acc * dt;
+ *   out[i] = (remainder(p1 + nv * dt, box), T1 + (rate_pred[i] * tr_std + tr_mean) * dt, ids[i])
+ * with p1, p2 = pos_prev1 / pos_prev2 [n_total, 3] at ids[i] (the raw stored frames t-1 and t-2) and T1 =
+ * temp_prev1 [n_total] at ids[i]; float32, one rounding per operation, no contraction (1 / dt is the float32
+ * reciprocal ATen uses for a host-scalar divisor).  stats (HOST memory, 8 floats): acc_std[3], acc_mean[3],
+ * temp_rate_std, temp_rate_mean.  Rows [n_rows, n_out) of out [n_out, CGNN_ROLLOUT_ROW] are padding.
+ *
+ * cgnn_frame_unpack: pos[id] = row[0..2] and temp[id] = row[3] for every row of rows [n_rows, CGNN_ROLLOUT_ROW]
+ * whose id lies in [0, n_total); other rows touch nothing.  One thread per row, no atomics (each id once). */
+#define CGNN_ROLLOUT_ROW 5
+int cgnn_rollout_integrate(const float* pos_prev2, const float* pos_prev1, const float* temp_prev1, int64_t n_total,
+                           const float* acc_pred, const float* temp_rate_pred, const int64_t* ids, int64_t n_rows,
+                           int64_t n_out, const float* stats, float dt, float box_size, float* out, void* stream);
+int cgnn_frame_unpack(const float* rows, int64_t n_rows, int64_t n_total, float* pos, float* temp, void* stream);
+
 /* ---- K11: momentum-conservation term ------------------------------------------
  * sums[g, c] = sum_{i: batch[i]==g} acc[i, c] in float64 (batch sorted ascending,
  * NULL = one graph); reference train.py:107-118.  sums is [num_graphs, width] f64,

@@ -1,0 +1,117 @@
+"""Developer tool: one rank's share of a sharded rollout step (dist.ShardedRollout) on ONE GPU, without the exchanges (a
+halo stand-in that moves nothing, the rank's own block published instead of the all-gather), next to rollout.rollout on
+the whole box and on a box of N / world on the same GPU.  The step is split into graph build (the wrapped last frame and
+dist.build_shard with its host synchronisations), features, forward and integrate + unpack; medians over the
+iterations.  The same step t is repeated (only this rank's rows are ever published).  Not part of the product or tests.
+    python scripts/time_sharded_rollout.py [--world 8] [--particles 4000000] [--iters 5]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cosmology_gnn_simulation_amd import dist as cdist, graph_network, rollout, synthetic  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--world", type=int, default=8)
+ap.add_argument("--rank", type=int, default=0)
+ap.add_argument("--particles", type=int, default=4_000_000)
+ap.add_argument("--neighbors", type=int, default=16)
+ap.add_argument("--latent", type=int, default=128)
+ap.add_argument("--mp-steps", type=int, default=10)
+ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--rollout-steps", type=int, default=3)
+a = ap.parse_args()
+dev = torch.device("cuda")
+W, dt, box = 6, 0.01, 1.0
+k, d, L = a.neighbors, a.latent, a.mp_steps
+meta = synthetic.make_metadata(box, dt)
+
+
+def window(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    p0 = torch.rand(n, 3, generator=g)
+    v = torch.randn(n, 3, generator=g) * 0.2
+    t = torch.arange(W, dtype=torch.float32).view(-1, 1, 1)
+    return {"Coordinates": p0.unsqueeze(0) + v.unsqueeze(0) * (dt * t),
+            "InternalEnergy": 1.0 + 0.1 * torch.randn(W, n, 1, generator=g).cumsum(dim=0)}
+
+
+m = graph_network.EncodeProcessDecode(d, d, 2, L, 3)
+m.load_state_dict(synthetic.make_state_dict(d, d, 2, L, 3, node_in=3 * (W - 1) + W))
+m = m.to(dev).eval()
+m.edge_precision, m.node_precision = "bf16", "fp16x2"        # bench.py's presets
+
+
+class NoExchange:
+    """The interface ShardedForward overlaps with; ghost rows keep whatever they hold."""
+
+    def start(self, table):
+        return None
+
+    def finish(self, handle):
+        return None
+
+
+def sharded_step_ms(data):
+    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, a.rank)
+    t = W
+    parts = {"graph": [], "features": [], "forward": [], "integrate+unpack": []}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    with torch.no_grad():
+        for it in range(a.iters + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sh = rn.plan(t)
+            sh.send_idx = torch.empty(0, dtype=torch.int32, device=dev)       # no peers: nothing to pack
+            sh.send_counts = [0] * a.world
+            torch.cuda.synchronize()
+            graph_ms = (time.perf_counter() - t0) * 1e3
+            ev[0].record()
+            rn.features(sh, t)
+            ev[1].record()
+            pred = rn.forward(sh, NoExchange())()
+            ev[2].record()
+            rn.publish(rn.integrate(sh, pred, t), t)
+            ev[3].record()
+            torch.cuda.synchronize()
+            if it == 0:
+                continue                                                      # weight packing, allocator warm-up
+            parts["graph"].append(graph_ms)
+            parts["features"].append(ev[0].elapsed_time(ev[1]))
+            parts["forward"].append(ev[1].elapsed_time(ev[2]))
+            parts["integrate+unpack"].append(ev[2].elapsed_time(ev[3]))
+    med = {key: statistics.median(v) for key, v in parts.items()}
+    return med, sh.n_owned, sh.n_ghost, rn.cap
+
+
+def rollout_step_ms(data):
+    with torch.no_grad():
+        rollout.rollout(m, data, meta, 0.0, dt, box, W, k, 1)                 # warm-up (weight packing)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(a.iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rollout.rollout(m, data, meta, 0.0, dt, box, W, k, a.rollout_steps)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3 / a.rollout_steps)
+    return statistics.median(times)
+
+
+data = window(a.particles, seed=1238)
+med, n_owned, n_ghost, cap = sharded_step_ms(data)
+total = sum(med.values())
+print(f"sharded rollout, rank {a.rank} of {a.world}, N={a.particles} k={k} latent={d} rounds={L} (bf16 edges, fp16x2 "
+      f"nodes), no exchange: owned {n_owned}, ghosts {n_ghost}, send-block rows {cap}")
+print("  per step: " + ", ".join(f"{key} {v:.2f} ms" for key, v in med.items()) + f"; total {total:.2f} ms")
+torch.cuda.empty_cache()
+whole = rollout_step_ms(data)
+print(f"rollout.rollout, whole box N={a.particles}: {whole:.2f} ms/step")
+del data
+torch.cuda.empty_cache()
+part = rollout_step_ms(window(a.particles // a.world, seed=1239))
+print(f"rollout.rollout, box of N/{a.world}={a.particles // a.world}: {part:.2f} ms/step")
