@@ -25,8 +25,10 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, ops, synthetic
+from . import ops, synthetic
 from ._lib import CgnnError
+from .graph_network import _next_projection, _node_half, _run_edge_stream, _run_round
+from .training import NodeStreamSteps
 
 
 # ----------------------------------------------------------------------------
@@ -224,19 +226,35 @@ def _comm_device(tensor_device: torch.device, group=None) -> torch.device:
     return tensor_device if dist.get_backend(group) == "nccl" else torch.device("cpu")
 
 
+def _collective(collective: Callable, out: torch.Tensor, *inputs: torch.Tensor, group=None,
+                **kwargs) -> Callable[[], torch.Tensor]:
+    """``collective(out, *inputs, group=group, **kwargs)``, a ``torch.distributed`` collective, run on the group's device
+    (:func:`_comm_device`); device tensors are staged through host memory under gloo.  No ``inputs``: ``out`` is
+    reduced in place.  Returns ``wait()``, which waits for the collective (RCCL, ``async_op=True``: the current stream
+    waits) and returns ``out``, holding the result."""
+    cdev = _comm_device(out.device, group)
+    if cdev == out.device:
+        host = out
+    else:
+        host = torch.empty(out.shape, dtype=out.dtype, device=cdev) if inputs else out.to(cdev)
+    work = collective(host, *[t.to(cdev) for t in inputs], group=group, **kwargs)
+
+    def wait() -> torch.Tensor:
+        if work is not None:
+            work.wait()
+        return out if host is out else out.copy_(host)
+    return wait
+
+
 def exchange_requests(sh: Shard, group=None) -> Shard:
     """Setup-time all-to-all of the ghost id lists (sizes, then ids)."""
     import torch.distributed as dist
-    dev = sh.owned_global.device
-    cdev = _comm_device(dev, group)
-    counts_out = torch.tensor(sh.recv_counts, dtype=torch.int64, device=cdev)
-    counts_in = torch.empty_like(counts_out)
-    dist.all_to_all_single(counts_in, counts_out, group=group)
-    counts_in_l = counts_in.tolist()
-    recv = torch.empty(int(sum(counts_in_l)), dtype=torch.int64, device=cdev)
-    dist.all_to_all_single(recv, sh.ghost_global.to(cdev).contiguous(), output_split_sizes=counts_in_l,
-                           input_split_sizes=sh.recv_counts, group=group)
-    return finish_shard(sh, [t.to(dev) for t in torch.split(recv, counts_in_l)])
+    counts_out = torch.tensor(sh.recv_counts, dtype=torch.int64, device=sh.owned_global.device)
+    counts_in = _collective(dist.all_to_all_single, torch.empty_like(counts_out), counts_out, group=group)().tolist()
+    recv = torch.empty(int(sum(counts_in)), dtype=torch.int64, device=counts_out.device)
+    _collective(dist.all_to_all_single, recv, sh.ghost_global.contiguous(), output_split_sizes=counts_in,
+                input_split_sizes=sh.recv_counts, group=group)()
+    return finish_shard(sh, list(torch.split(recv, counts_in)))
 
 
 # ----------------------------------------------------------------------------
@@ -262,23 +280,11 @@ class HaloExchange:
             self._buf = torch.empty((sh.send_idx.numel(), width), dtype=table.dtype, device=table.device)
         if sh.send_idx.numel():
             self.pack(table, sh.send_idx, self._buf)
-        ghosts = table[sh.n_owned:]
-        cdev = _comm_device(table.device, self.group)
-        if cdev == table.device:
-            work = dist.all_to_all_single(ghosts, self._buf, output_split_sizes=sh.recv_counts,
-                                          input_split_sizes=sh.send_counts, group=self.group, async_op=True)
-            return (work, None, ghosts)
-        # gloo rehearsal with device tensors: stage through host memory
-        recv = torch.empty(ghosts.shape, dtype=ghosts.dtype, device=cdev)
-        work = dist.all_to_all_single(recv, self._buf.to(cdev), output_split_sizes=sh.recv_counts,
-                                      input_split_sizes=sh.send_counts, group=self.group, async_op=True)
-        return (work, recv, ghosts)
+        return _collective(dist.all_to_all_single, table[sh.n_owned:], self._buf, output_split_sizes=sh.recv_counts,
+                           input_split_sizes=sh.send_counts, group=self.group, async_op=True)
 
     def finish(self, handle) -> None:
-        work, recv, ghosts = handle
-        work.wait()                       # RCCL: the current stream waits for the exchange
-        if recv is not None:
-            ghosts.copy_(recv)
+        handle()                          # RCCL: the current stream waits for the exchange
 
     def __call__(self, table: torch.Tensor) -> None:
         self.finish(self.start(table))
@@ -291,24 +297,14 @@ class HaloExchange:
         import torch.distributed as dist
         sh = self.sh
         shape = (int(sum(sh.send_counts)), grad_ghost.shape[1])
-        cdev = _comm_device(grad_ghost.device, self.group)
-        if cdev == grad_ghost.device:
-            if self._ret is None or tuple(self._ret.shape) != shape or self._ret.device != grad_ghost.device:
-                self._ret = torch.empty(shape, dtype=grad_ghost.dtype, device=grad_ghost.device)
-            work = dist.all_to_all_single(self._ret, grad_ghost, output_split_sizes=sh.send_counts,
-                                          input_split_sizes=sh.recv_counts, group=self.group, async_op=True)
-            return (work, None, self._ret)
-        # gloo rehearsal with device tensors: stage through host memory
-        recv = torch.empty(shape, dtype=grad_ghost.dtype, device=cdev)
-        work = dist.all_to_all_single(recv, grad_ghost.to(cdev), output_split_sizes=sh.send_counts,
-                                      input_split_sizes=sh.recv_counts, group=self.group, async_op=True)
-        return (work, recv, grad_ghost.device)
+        if self._ret is None or tuple(self._ret.shape) != shape or self._ret.device != grad_ghost.device:
+            self._ret = torch.empty(shape, dtype=grad_ghost.dtype, device=grad_ghost.device)
+        return _collective(dist.all_to_all_single, self._ret, grad_ghost, output_split_sizes=sh.send_counts,
+                           input_split_sizes=sh.recv_counts, group=self.group, async_op=True)
 
     def finish_return(self, handle) -> torch.Tensor:
         """Wait for :meth:`start_return`; returns the received gradient rows on the gradients' device."""
-        work, recv, out = handle
-        work.wait()
-        return out if recv is None else recv.to(out)
+        return handle()
 
 
 def halo_return_plan(send_idx: torch.Tensor, send_counts: Sequence[int], n_owned: int):
@@ -335,6 +331,32 @@ def halo_return_plan(send_idx: torch.Tensor, send_counts: Sequence[int], n_owned
 # sharded forward
 # ----------------------------------------------------------------------------
 
+def _src_part(runner, a: int, b: int) -> torch.Tensor:
+    """The sender list of ``runner``'s owned receivers [a, b) as one tensor OBJECT per part (the aggregation plan is
+    cached on it)."""
+    parts = runner.__dict__.setdefault("_src_parts", {})
+    if (a, b) not in parts:
+        k = runner.sh.k
+        parts[(a, b)] = runner.sh.src_local[a * k:b * k]
+    return parts[(a, b)]
+
+
+def _exchange_rounds(halo, n_rounds: int, table_of: Callable, nodes: Callable, overlap: bool) -> None:
+    """The rounds of a shard runner: round ``i``'s table ``table_of(i)`` gets its ghost rows from ``halo``, and
+    ``nodes(i, part)`` runs the round for the owned receivers of ``part``.  With ``overlap`` the exchange runs under
+    the ``"interior"`` receivers (no ghost sender) and the ``"boundary"`` ones follow it; else ``"all"`` run after it."""
+    for i in range(n_rounds):
+        table = table_of(i)
+        if overlap:
+            handle = halo.start(table)
+            nodes(i, "interior")
+            halo.finish(handle)
+            nodes(i, "boundary")
+        else:
+            halo(table) if callable(halo) else halo.finish(halo.start(table))
+            nodes(i, "all")
+
+
 class ShardedForward:
     """``EncodeProcessDecode.forward`` over one spatial tile.  ``halo(table)`` must fill the ghost rows of
     ``table`` ([n_owned + n_ghost, D]) from their owners; by default it is the RCCL all-to-all above.
@@ -347,10 +369,10 @@ class ShardedForward:
 
     def _buffers(self, D: int, H: int, dev):
         sh = self.sh
-        key = (D, H, dev, self.model.edge_precision, self.fused, self.p_fmt)
+        key = (D, H, dev, self.model.edge_precision, self.fused, self.plan.p_format)
         if self._bufs is None or self._bufs[0] != key:
             x_all = torch.empty((sh.n_local, D), dtype=torch.float32, device=dev)
-            pdt = ops.p_format_dtype(self.p_fmt) if self.P["rounds"] else torch.float32
+            pdt = ops.p_format_dtype(self.plan.p_format)
             if self.fused:      # every round's tables are kept for the one-launch edge stream (same row stride for both)
                 L = len(self.P["rounds"])
                 ps = torch.empty((L, sh.n_local, H), dtype=pdt, device=dev)
@@ -368,65 +390,33 @@ class ShardedForward:
     # the pieces are separate methods so that a single-process test can interleave several shards
     def encode(self):
         m, sh = self.model, self.sh
-        P = m._pack(sh.x_feat.shape[1], sh.edge_attr.shape[1])
+        P = self.P = m._pack(sh.x_feat.shape[1], sh.edge_attr.shape[1])
         D = m._latent_size
         H = P["rounds"][0].ws.out_dim if P["rounds"] else D
-        self.P = P
-        # reference data flow (x_j): the node stream runs round by round with its halo exchanges and leaves every
-        # round's Ps / Pd behind; the edge stream then is one launch (cgnn_edge_stream), as on one GPU
-        self.image = P["image"]          # cgnn_edge_stream_run's chunk image (None: first-generation kernel or per round)
-        self.fused = self.image is not None or m._can_fuse_rounds(P["rounds"], D)
-        # fused mode: the table format the one-launch edge stream of this shard will take (fp16 rows for the
-        # two-waves-per-SIMD kernel, graph_network.stream_table_format); per round: each round's own
-        self.p_fmt = P["rounds"][0].p_format if P["rounds"] else _lib.P_F32
-        if self.fused and self.image is not None:
-            from .graph_network import stream_table_format
-            attr0 = sh.edge_attr if bool(self.image.enc_in) else None
-            _, kern = m._edge_stream_plan(P, sh.k, sh.src_local.numel(), attr0)
-            self.p_fmt = stream_table_format(P["rounds"], kern, int(getattr(m, "edge_stream_lag", 0)))
+        # the same plan as on one GPU: under the reference data flow (x_j) the node stream runs round by round with its
+        # halo exchanges and leaves every round's Ps / Pd behind; the edge stream then is one launch
+        self.plan = m._stream_plan(P, sh.k, sh.src_local.numel(), sh.edge_attr)
+        self.fused = self.plan.fused
         self.x_all, self.ps, self.pd, self.agg, self.x_alt = self._buffers(D, H, sh.x_feat.device)
         ops.mlp_rows(P["enc_node"], sh.x_feat, out=self.x_all[:sh.n_owned])
         self._projected = False
         self._edges_pending = False
-        # fused mode: the edge encoder runs inside cgnn_edge_stream when it has the rounds' shape
-        self._enc_in_stream = bool(self.image.enc_in) if self.image is not None else \
-            (self.fused and m._encoder_fits_stream(P))
-        self.el = None if self._enc_in_stream else ops.mlp_rows(P["enc_edge"], sh.edge_attr, tiled=True)
+        self.el = None if self.plan.enc_in_stream else ops.mlp_rows(P["enc_edge"], sh.edge_attr, tiled=True)
         self.e_upd = self.el.empty_like() if m.message_source == "edge" else None
 
     def round(self, i: int):
         if self.fused:
             return self._round_nodes(i)
-        m, sh = self.model, self.sh
-        rounds = self.P["rounds"]
+        sh, rounds = self.sh, self.P["rounds"]
         p = rounds[i]
-        x_own = self.x_all[:sh.n_owned]
-        ps_own, ps_ghost = self.ps[:sh.n_owned], self.ps[sh.n_owned:]
         # sender projections of the ghost rows that just arrived (receivers are always owned: no Pd for ghosts)
         if sh.n_ghost:
-            ops.project_nodes(p.ws, None, self.x_all[sh.n_owned:], ps_ghost, None, p.p_format)
-        if not self._projected:     # first round: the owned rows too (later rounds: emitted by the node kernel)
-            ops.project_nodes(p.ws, p.wd, x_own, ps_own, self.pd, p.p_format)
-        edge_mode = m.message_source == "edge"
-        if edge_mode and p.edge.precision == _lib.BF16_N16 and sh.k in (8, 16) and self.x_all.shape[1] <= 128:   # aggregation folded in
-            ops.edge_block(p.edge, self.ps, self.pd, sh.src_local, sh.dst_local, self.el, self.el, None, True,
-                           agg_out=self.agg, x_gather=None, seg_k=sh.k)
-        else:
-            ops.edge_block(p.edge, self.ps, self.pd, sh.src_local, sh.dst_local, self.el, self.el,
-                           self.e_upd if edge_mode else None, True)
-            if edge_mode:
-                ops.aggregate(self.e_upd, None, sh.dst_local, sh.n_owned, sh.k, sh.src_local.numel(), self.agg)
-            else:
-                ops.aggregate(self.x_all, sh.src_local, sh.dst_local, sh.n_owned, sh.k, sh.src_local.numel(),
-                              self.agg, plan=ops.AggregatePlan.of(sh.src_local, sh.n_owned, sh.k, self.x_all.shape[1]))
-        nxt = None
-        if i + 1 < len(rounds):
-            q = rounds[i + 1]
-            if q.p_format == p.p_format and q.p_dtype == self.ps.dtype:
-                fused_ok = p.node.precision in _lib.N16_NODE and q.ws_fused.precision == _lib.BF16_N16
-                nxt = (q.ws_fused if fused_ok else q.ws, q.wd_fused if fused_ok else q.wd, ps_own, self.pd, q.p_format)
-        ops.node_block(p.node, p.wx, p.wa, x_own, self.agg, x_own, True, nxt)
-        self._projected = nxt is not None
+            ops.project_nodes(p.ws, None, self.x_all[sh.n_owned:], self.ps[sh.n_owned:], None, p.p_format)
+        nxt = rounds[i + 1] if i + 1 < len(rounds) else None
+        _, self.el, self._projected = _run_round(
+            p, self.x_all, self.el, sh.src_local, sh.dst_local, sh.k, self.model.message_source, True,
+            x_out=self.x_all[:sh.n_owned], e_out=self.el, scratch=(self.ps, self.pd, self.agg, self.e_upd),
+            projected=self._projected, next_round=nxt, n_recv=sh.n_owned)
 
     def _interior_launch_rows(self) -> int:
         """Rows of the "interior" launches: ``n_interior`` rounded DOWN to whole grid waves of the node kernel.  A launch of
@@ -446,14 +436,6 @@ class ShardedForward:
         self._ni_launch = (ni, rows)
         return rows
 
-    def _src_part(self, a: int, b: int) -> torch.Tensor:
-        """The sender list of owned receivers [a, b) as one tensor OBJECT per part (the aggregation plan is cached on it)."""
-        parts = self.__dict__.setdefault("_src_parts", {})
-        if (a, b) not in parts:
-            k = self.sh.k
-            parts[(a, b)] = self.sh.src_local[a * k:b * k]
-        return parts[(a, b)]
-
     def _round_nodes(self, i: int, part: str = "all"):
         """Fused mode: the node half of round ``i`` for the owned rows of ``part``: ``"interior"`` (receivers whose
         senders are all owned: needs no ghost row, runs under the halo exchange), ``"boundary"`` (the rest, after the
@@ -461,25 +443,16 @@ class ShardedForward:
         when the round is complete."""
         sh = self.sh
         rounds = self.P["rounds"]
-        p = rounds[i]
-        no, ni, k = sh.n_owned, self._interior_launch_rows(), sh.k
+        p, fmt = rounds[i], self.plan.p_format
+        no, ni = sh.n_owned, self._interior_launch_rows()
         a, b = {"all": (0, no), "interior": (0, ni), "boundary": (ni, no)}[part]
         if part != "interior" and sh.n_ghost:
-            ops.project_nodes(p.ws, None, self.x_all[no:], self.ps[i][no:], None, self.p_fmt)
+            ops.project_nodes(p.ws, None, self.x_all[no:], self.ps[i][no:], None, fmt)
         if b > a:
-            x_in = self.x_all[a:b]
             if i == 0:
-                ops.project_nodes(p.ws, p.wd, x_in, self.ps[0][a:b], self.pd[0][a:b], self.p_fmt)
-            src_part = self._src_part(a, b)
-            ops.aggregate(self.x_all, src_part, None, b - a, k, (b - a) * k, self.agg[a:b],
-                          plan=ops.AggregatePlan.of(src_part, b - a, k, self.x_all.shape[1]))
-            nxt = None
-            if i + 1 < len(rounds):
-                q = rounds[i + 1]
-                fused_ok = p.node.precision in _lib.N16_NODE and q.ws_fused.precision == _lib.BF16_N16
-                nxt = (q.ws_fused if fused_ok else q.ws, q.wd_fused if fused_ok else q.wd, self.ps[i + 1][a:b],
-                       self.pd[i + 1][a:b], self.p_fmt)
-            ops.node_block(p.node, p.wx, p.wa, x_in, self.agg[a:b], self.x_alt[a:b], True, nxt)
+                ops.project_nodes(p.ws, p.wd, self.x_all[a:b], self.ps[0][a:b], self.pd[0][a:b], fmt)
+            nxt = _next_projection(p, rounds[i + 1], self.ps[i + 1], self.pd[i + 1], fmt) if i + 1 < len(rounds) else None
+            _node_half((p.node, p.wx, p.wa), self.x_all, _src_part(self, a, b), None, sh.k, a, b, self.agg, self.x_alt, nxt)
         if part != "interior":
             self.x_all, self.x_alt = self.x_alt, self.x_all
             self._edges_pending = i + 1 == len(rounds)
@@ -488,15 +461,8 @@ class ShardedForward:
         """Fused mode: all edge updates in one launch, once the last round's node half has run."""
         if self.fused and self._edges_pending:
             sh = self.sh
-            enc = self.P["enc_edge"] if self._enc_in_stream else None
-            if self.image is not None:
-                attr = sh.edge_attr if self._enc_in_stream else None
-                image, kernel = self.model._edge_stream_plan(self.P, sh.k, sh.src_local.numel(), attr)
-                self.el = ops.edge_stream_run(image, self.ps, self.pd, sh.src_local, sh.dst_local, self.el, self.el, attr,
-                                              kernel=kernel, lag=int(getattr(self.model, "edge_stream_lag", 0)), fixed_k=sh.k)
-            else:
-                self.el = ops.edge_stream([p.edge for p in self.P["rounds"]], self.ps, self.pd, sh.src_local,
-                                          sh.dst_local, self.el, self.el, enc, sh.edge_attr if enc is not None else None)
+            self.el = _run_edge_stream(self.P, self.plan, self.ps, self.pd, sh.src_local, sh.dst_local, self.el,
+                                       sh.edge_attr, sh.k)
             self._edges_pending = False
 
     def decode(self) -> dict:
@@ -508,18 +474,10 @@ class ShardedForward:
     def __call__(self) -> dict:
         with torch.no_grad():
             self.encode()
-            n_rounds = len(self.P["rounds"])
+            # x_j aggregation and the sender projections both read ghost latents of the current round
             overlap = self.fused and hasattr(self.halo, "start") and 0 < self.sh.n_interior
-            for i in range(n_rounds):
-                # x_j aggregation and the sender projections both read ghost latents of the current round
-                if overlap:     # interior receivers need no ghost row: their half of the round hides the exchange
-                    handle = self.halo.start(self.x_all)
-                    self._round_nodes(i, "interior")
-                    self.halo.finish(handle)
-                    self._round_nodes(i, "boundary")
-                else:
-                    self.halo(self.x_all)
-                    self.round(i)
+            _exchange_rounds(self.halo, len(self.P["rounds"]), lambda i: self.x_all,
+                             lambda i, part: self._round_nodes(i, part) if self.fused else self.round(i), overlap)
             return self.decode()
 
 
@@ -528,15 +486,9 @@ class ShardedForward:
 # ----------------------------------------------------------------------------
 
 def _all_reduce_(t: torch.Tensor, group=None) -> torch.Tensor:
-    """In-place SUM over the group (staged through host memory under gloo with device tensors)."""
+    """In-place SUM over the group."""
     import torch.distributed as dist
-    cdev = _comm_device(t.device, group)
-    if cdev == t.device:
-        dist.all_reduce(t, group=group)
-        return t
-    h = t.to(cdev)
-    dist.all_reduce(h, group=group)
-    return t.copy_(h)
+    return _collective(dist.all_reduce, t, group=group)()
 
 
 class _AllReduceSum(torch.autograd.Function):
@@ -579,7 +531,7 @@ def sharded_training_loss(pred: dict, y_acc: torch.Tensor, y_tr: torch.Tensor, n
     return mse + mom, value
 
 
-class ShardedTraining:
+class ShardedTraining(NodeStreamSteps):
     """A training step of ``EncodeProcessDecode`` (``message_source="x_j"``, ``train_precision`` "fp32" / "fp32x3") over one
     spatial tile: the node stream of :class:`training._NodeStream` on the owned rows, with one halo exchange of the f32
     latents per round in the forward and one reverse exchange of their gradients per round in the backward.
@@ -628,14 +580,6 @@ class ShardedTraining:
             self._csr = ops.SenderCsr(sh.src_local, sh.dst_local, sh.n_local)       # senders <- receivers, once per shard
             self._plan = halo_return_plan(sh.send_idx.to(x0.device), sh.send_counts, sh.n_owned)
 
-    def _src_part(self, a: int, b: int) -> torch.Tensor:
-        """The sender list of owned receivers [a, b) as one tensor OBJECT per part (the aggregation plan is cached on it)."""
-        parts = self.__dict__.setdefault("_src_parts", {})
-        if (a, b) not in parts:
-            k = self.sh.k
-            parts[(a, b)] = self.sh.src_local[a * k:b * k]
-        return parts[(a, b)]
-
     # -- forward pieces ----------------------------------------------------------------------------------------------
     def encode(self, x0: Optional[torch.Tensor] = None) -> None:
         """Node encoder on the owned rows (``x0`` defaults to ``shard.x_feat``)."""
@@ -644,62 +588,32 @@ class ShardedTraining:
         if x0.shape[0] != sh.n_owned:
             raise CgnnError(f"ShardedTraining: {x0.shape[0]} input rows for {sh.n_owned} owned particles")
         self._prepare(x0)
+        self._encode(self.packs, x0)
         D = self.packs.latent
-        self.x0 = x0
-        self.xs = [ops.mlp_rows(self.packs.enc.fwd, x0)]      # raw features: three bf16 terms or exact
-        self.aggs = []
         if self._table is None or tuple(self._table.shape) != (sh.n_local, D) or self._table.device != x0.device:
             self._table = torch.empty((sh.n_local, D), dtype=torch.float32, device=x0.device)
 
     def stage(self, i: int) -> torch.Tensor:
         """Round ``i``'s local table: the owned rows hold ``x_i``; the exchange is to fill the ghost rows."""
-        no, D = self.sh.n_owned, self.packs.latent
-        self._table[:no].copy_(self.xs[i])
-        self.aggs.append(torch.empty((no, D), dtype=torch.float32, device=self._table.device))
-        self.xs.append(torch.empty((no, D), dtype=torch.float32, device=self._table.device))
+        self._table[:self.sh.n_owned].copy_(self.xs[i])
+        self._new_round()
         return self._table
 
     def round_nodes(self, i: int, part: str = "all") -> None:
         """Aggregation and node block of round ``i`` for the owned receivers of ``part``: ``"interior"`` (no ghost sender:
         may run under the exchange), ``"boundary"`` (after it) or ``"all"``."""
         sh = self.sh
-        no, ni, k = sh.n_owned, sh.n_interior, sh.k
+        no, ni = sh.n_owned, sh.n_interior
         a, b = {"all": (0, no), "interior": (0, ni), "boundary": (ni, no)}[part]
-        if b <= a:
-            return
-        r = self.packs.rounds[i]
-        src = self._src_part(a, b)
-        agg = self.aggs[i][a:b]
-        ops.aggregate(self._table, src, None, b - a, k, (b - a) * k, agg,
-                      plan=ops.AggregatePlan.of(src, b - a, k, self._table.shape[1]))
-        ops.node_block(r.run, r.run.layers[0], r.run2, self.xs[i][a:b], agg, self.xs[i + 1][a:b], residual=True)
+        if b > a:
+            self._round_nodes(i, self._table, _src_part(self, a, b), None, sh.k, a, b)
 
-    def decode(self):
-        xl = self.xs[-1]
-        return ops.mlp_rows(self.packs.dec_acc.run, xl), ops.mlp_rows(self.packs.dec_tr.run, xl)
-
-    # -- backward pieces ---------------------------------------------------------------------------------------------
-    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
-        """Seeds ``dx`` = dL/dx_L from the decoders' output gradients (``None``: zero)."""
-        p, sh = self.packs, self.sh
-        no, D = sh.n_owned, p.latent
-        dev = self.x0.device
-        self.scratch = ops.BackwardScratch(no, p.hidden, max(D, 32), p.nh, dev)
-        self.grads_of = {}
-        zero = lambda t, w: torch.zeros((no, w), dtype=torch.float32, device=dev) if t is None else t  # noqa: E731
-        xl = self.xs[-1]
-        dx, _, self.grads_of[id(p.dec_acc)] = p.dec_acc.backward(xl, None, zero(d_acc, p.dec_acc.out_dim), self.scratch, True)
-        dx2, _, self.grads_of[id(p.dec_tr)] = p.dec_tr.backward(xl, None, zero(d_tr, p.dec_tr.out_dim), self.scratch, True)
-        self.dx = dx.add_(dx2)
-
+    # -- backward pieces (decode_backward, encode_backward, local_grads: NodeStreamSteps) --------------------------------
     def round_backward_local(self, i: int) -> torch.Tensor:
         """Steps 1-2 of round ``i``: the node MLP's backward on the owned rows, then ``A^T du2`` for the ghost rows,
         written into (and returned as) the send buffer of the reverse exchange, [n_ghost, D]."""
         sh = self.sh
-        r = self.packs.rounds[i]
-        du1, du2, self.grads_of[id(r)] = r.backward(self.xs[i], self.aggs[i], self.dx, self.scratch, True, True)
-        self.aggs[i] = None
-        self._du = (du1, du2)
+        self._du = du1, du2 = self.round_backward(i)
         shape = (sh.n_ghost, self.packs.latent)
         if self._ghost is None or tuple(self._ghost.shape) != shape or self._ghost.device != du2.device:
             self._ghost = torch.empty(shape, dtype=torch.float32, device=du2.device)
@@ -719,31 +633,11 @@ class ShardedTraining:
         if ret.shape[0]:
             ops.halo_return_add(self.dx, ret, *self._plan)
 
-    def encode_backward(self, need_dx0: bool = True) -> Optional[torch.Tensor]:
-        p = self.packs
-        dx0, _, self.grads_of[id(p.enc)] = p.enc.backward(self.x0, None, self.dx, self.scratch, need_dx0)
-        self.dx = None
-        return dx0
-
-    def local_grads(self) -> List[torch.Tensor]:
-        """This rank's partial parameter gradients, in ``TrainPacks.params()`` order."""
-        return [g for m in self.packs.all for g in self.grads_of[id(m)]]
-
     # -- one step through a process group ----------------------------------------------------------------------------
     def run_forward(self, x0: Optional[torch.Tensor] = None):
         """Encoder, rounds with the exchange hidden behind the interior receivers, decoders: ``(acc, temp_rate)``."""
         self.encode(x0)
-        overlap = 0 < self.sh.n_interior
-        for i in range(len(self.packs.rounds)):
-            table = self.stage(i)
-            if overlap:
-                handle = self.halo.start(table)
-                self.round_nodes(i, "interior")
-                self.halo.finish(handle)
-                self.round_nodes(i, "boundary")
-            else:
-                self.halo.finish(self.halo.start(table))
-                self.round_nodes(i, "all")
+        _exchange_rounds(self.halo, len(self.packs.rounds), self.stage, self.round_nodes, 0 < self.sh.n_interior)
         return self.decode()
 
     def run_backward(self, d_acc, d_tr, need_dx0: bool = True):
@@ -857,10 +751,7 @@ def window_checksum(coords_w: torch.Tensor, energy_w: torch.Tensor) -> torch.Ten
 
 def _all_reduce_max_(t: torch.Tensor, group=None) -> torch.Tensor:
     import torch.distributed as dist
-    cdev = _comm_device(t.device, group)
-    h = t if cdev == t.device else t.to(cdev)
-    dist.all_reduce(h, op=dist.ReduceOp.MAX, group=group)
-    return t if h is t else t.copy_(h)
+    return _collective(dist.all_reduce, t, op=dist.ReduceOp.MAX, group=group)()
 
 
 def check_same_data(coords_w: torch.Tensor, energy_w: torch.Tensor, device, group=None) -> None:
@@ -874,19 +765,11 @@ def check_same_data(coords_w: torch.Tensor, energy_w: torch.Tensor, device, grou
 
 
 def all_gather_rows(block: torch.Tensor, group=None) -> torch.Tensor:
-    """``[world * cap, W]``: every rank's ``[cap, W]`` block in rank order (one ``all_gather_into_tensor``; staged
-    through host memory under gloo with device tensors)."""
+    """``[world * cap, W]``: every rank's ``[cap, W]`` block in rank order (one ``all_gather_into_tensor``)."""
     import torch.distributed as dist
-    world = dist.get_world_size(group)
-    shape = (world * block.shape[0], block.shape[1])
-    cdev = _comm_device(block.device, group)
-    if cdev == block.device:
-        out = torch.empty(shape, dtype=block.dtype, device=block.device)
-        dist.all_gather_into_tensor(out, block.contiguous(), group=group)
-        return out
-    out = torch.empty(shape, dtype=block.dtype, device=cdev)
-    dist.all_gather_into_tensor(out, block.to(cdev).contiguous(), group=group)
-    return out.to(block.device)
+    out = torch.empty((dist.get_world_size(group) * block.shape[0], block.shape[1]), dtype=block.dtype,
+                      device=block.device)
+    return _collective(dist.all_gather_into_tensor, out, block.contiguous(), group=group)()
 
 
 class ShardedRollout:

@@ -30,7 +30,7 @@ is untouched):
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -337,17 +337,43 @@ class _PackedProcessor:
             self.wd_fused = ops.PackedLinear(w1e, b1e, "bf16_n16", D, D)
 
 
+def _next_projection(p: _PackedProcessor, q: _PackedProcessor, ps: torch.Tensor, pd: torch.Tensor, p_format: int):
+    """``next_projection`` of ``ops.node_block`` for round ``p``'s node kernel: round ``q``'s Ps / Pd tables, written into
+    ``ps`` / ``pd`` in ``p_format``, with the projection weights in the packing that node kernel can fuse."""
+    fused_ok = p.node.precision in _lib.N16_NODE and q.ws_fused.precision == _lib.BF16_N16
+    return (q.ws_fused if fused_ok else q.ws, q.wd_fused if fused_ok else q.wd, ps, pd, p_format)
+
+
+def _node_half(node, table: torch.Tensor, src: torch.Tensor, dst: Optional[torch.Tensor], fixed_k: int, a: int, b: int,
+              agg: torch.Tensor, x_out: torch.Tensor, nxt=None) -> None:
+    """Aggregation of the sender rows ``table[src]`` and residual node block of one round for receivers [a, b): the
+    receivers are the first rows of ``table``, rows of senders that are not receivers (a shard's ghosts) may follow.
+    ``src`` / ``dst``: the edges of these receivers only (``dst`` None: ``fixed_k`` consecutive edges per receiver).
+    ``node``: ``(mlp, w_x, w_agg)``.  Writes ``agg[a:b]`` and ``x_out[a:b]`` (``x_out`` may be ``table``); ``nxt``:
+    ``node_block``'s ``next_projection`` over whole tables, of which rows [a, b) are written."""
+    n = b - a
+    agg = agg[a:b]
+    ops.aggregate(table, src, dst, n, fixed_k, src.numel(), agg,
+                  plan=ops.AggregatePlan.of(src, n, fixed_k, table.shape[1]))     # built once, cached on the sender list
+    if nxt is not None:
+        nxt = nxt[:2] + (nxt[2][a:b], nxt[3][a:b], nxt[4])
+    ops.node_block(*node, table[a:b], agg, x_out[a:b], True, nxt)
+
+
 def _run_round(p: _PackedProcessor, x: torch.Tensor, e: torch.Tensor, src, dst, fixed_k: int, message_source: str,
                residual: bool, x_out=None, e_out=None, scratch=None, projected: bool = False,
-               next_round: Optional[_PackedProcessor] = None):
-    """One message-passing round.  Returns (x_new, e_new).  ``projected``: the Ps/Pd tables in ``scratch`` were
-    already filled for this round (by the previous round's node kernel); ``next_round``: fill them for the next."""
-    n = x.shape[0]
+               next_round: Optional[_PackedProcessor] = None, n_recv: Optional[int] = None):
+    """One message-passing round.  Returns (x_new, e_new, projected).  ``projected``: the Ps/Pd tables in ``scratch``
+    were already filled for this round (by the previous round's node kernel); ``next_round``: fill them for the next.
+    ``n_recv``: the receivers are the first ``n_recv`` rows of ``x`` (default: all); the sender projections of the rows
+    after them (a shard's ghosts) must already be in ``scratch``'s Ps table."""
+    n = x.shape[0] if n_recv is None else n_recv
     ps = pd = agg = e_upd = None
     if scratch is not None:
         ps, pd, agg, e_upd = scratch
     if not projected:
-        ps, pd = ops.project_nodes(p.ws, p.wd, x, ps, pd, p.p_format)
+        ps_recv, pd = ops.project_nodes(p.ws, p.wd, x[:n], None if ps is None else ps[:n], pd, p.p_format)
+        ps = ps_recv if ps is None else ps
     if message_source not in ("x_j", "edge"):
         raise ValueError(f"message_source must be 'x_j' or 'edge', got {message_source!r}")
     if message_source == "edge" and p.edge.precision == _lib.BF16_N16 and fixed_k in (8, 16) and x.shape[1] <= 128:
@@ -371,10 +397,8 @@ def _run_round(p: _PackedProcessor, x: torch.Tensor, e: torch.Tensor, src, dst, 
             agg = ops.aggregate(e_upd, None, dst, n, fixed_k, src.numel(), agg)
     nxt = None
     if next_round is not None and next_round.p_format == p.p_format and next_round.p_dtype == ps.dtype:
-        fused_ok = p.node.precision in _lib.N16_NODE and next_round.ws_fused.precision == _lib.BF16_N16
-        nxt = (next_round.ws_fused if fused_ok else next_round.ws, next_round.wd_fused if fused_ok else next_round.wd,
-               ps, pd, next_round.p_format)
-    x_new = ops.node_block(p.node, p.wx, p.wa, x, agg, x_out, residual, nxt)
+        nxt = _next_projection(p, next_round, ps[:n], pd, next_round.p_format)
+    x_new = ops.node_block(p.node, p.wx, p.wa, x[:n], agg, x_out, residual, nxt)
     return x_new, e_new, nxt is not None
 
 
@@ -389,40 +413,49 @@ def stream_table_format(rounds, stream_kernel: Optional[str], stream_lag: int = 
     return fmt
 
 
-def _run_rounds_fused(rounds, x: torch.Tensor, e, src, dst, fixed_k: int, agg: Optional[torch.Tensor],
-                      encoder=None, edge_attr: Optional[torch.Tensor] = None, image=None, keep: Optional[dict] = None,
-                      stream_kernel: str = "tile32", stream_lag: int = 0):
+class StreamPlan(NamedTuple):
+    """How a forward runs its rounds (``EncodeProcessDecode._stream_plan``)."""
+    fused: bool                # the node stream first, then every round's edge update in one launch
+    image: Optional[ops.StreamImage]    # cgnn_edge_stream_run's image for ``kernel``; None: "tile16", or per round
+    kernel: Optional[str]      # the one-launch kernel: "tile32w", "tile32" or "tile16" (None: per round)
+    lag: int                   # "tile32w": second wave of a SIMD one layer behind the first (1) or in step (0)
+    p_format: int              # cgnn_ptable format of the Ps / Pd tables the node stream writes (per round: round 0's)
+    enc_in_stream: bool        # the edge encoder runs inside the one launch (its latents are never written)
+
+
+def _run_edge_stream(P: dict, plan: StreamPlan, ps_all, pd_all, src, dst, e, edge_attr, fixed_k: int):
+    """The one-launch edge stream of ``plan`` over every round's Ps / Pd tables (and the encoder, if it is in the
+    stream): ``cgnn_edge_stream_run`` / ``_w8`` from the plan's image, or the first-generation ``cgnn_edge_stream``.
+    Updates ``e`` in place (``e`` is None when the encoder runs inside) and returns the final edge latents."""
+    attr = edge_attr if plan.enc_in_stream else None
+    if plan.image is not None:
+        return ops.edge_stream_run(plan.image, ps_all, pd_all, src, dst, e, e, attr, kernel=plan.kernel, lag=plan.lag,
+                                   fixed_k=fixed_k)
+    return ops.edge_stream([p.edge for p in P["rounds"]], ps_all, pd_all, src, dst, e, e,
+                           P["enc_edge"] if plan.enc_in_stream else None, attr)
+
+
+def _run_rounds_fused(P: dict, plan: StreamPlan, x: torch.Tensor, e, src, dst, fixed_k: int, agg: torch.Tensor,
+                      edge_attr: Optional[torch.Tensor] = None, keep: Optional[dict] = None):
     """All residual rounds under the reference's data flow (aggregation of sender NODE latents): the node
     stream does not read the edge stream, so it runs first and leaves every round's Ps / Pd tables behind (the node
     kernel's epilogue writes round i+1's); then one launch applies all edge updates while each edge tile stays in
     registers.  Same kernels' arithmetic as the round-by-round path: results are bit-identical."""
+    rounds = P["rounds"]
     n, L = x.shape[0], len(rounds)
     H = rounds[0].ws.out_dim
-    fmt = stream_table_format(rounds, stream_kernel if image is not None else None, stream_lag)
+    fmt = plan.p_format
     pdt = ops.p_format_dtype(fmt)
     ps_all = torch.empty((L, n, H), dtype=pdt, device=x.device)
     pd_all = torch.empty((L, n, H), dtype=pdt, device=x.device)
     ops.project_nodes(rounds[0].ws, rounds[0].wd, x, ps_all[0], pd_all[0], fmt)
-    plan = ops.AggregatePlan.of(src, n, fixed_k, x.shape[1])       # built once per graph, cached on its sender list
-    for i, p in enumerate(rounds):
-        agg = ops.aggregate(x, src, dst, n, fixed_k, src.numel(), agg, plan=plan)
-        nxt = None
-        if i + 1 < L:
-            q = rounds[i + 1]
-            fused_ok = p.node.precision in _lib.N16_NODE and q.ws_fused.precision == _lib.BF16_N16
-            nxt = (q.ws_fused if fused_ok else q.ws, q.wd_fused if fused_ok else q.wd, ps_all[i + 1], pd_all[i + 1], fmt)
-        x = ops.node_block(p.node, p.wx, p.wa, x, agg, x, True, nxt)
+    for i, p in enumerate(rounds):      # residual stream updated in place
+        nxt = _next_projection(p, rounds[i + 1], ps_all[i + 1], pd_all[i + 1], fmt) if i + 1 < L else None
+        _node_half((p.node, p.wx, p.wa), x, src, dst, fixed_k, 0, n, agg, x, nxt)
     if keep is not None:      # tests: what the one-launch edge stream is about to consume (EncodeProcessDecode.keep_stream_inputs)
         keep.update(ps_all=ps_all, pd_all=pd_all, src=src, dst=dst, edge_attr=edge_attr, p_format=fmt,
-                    e_in=None if e is None else e.to_rows(), folded=bool(image is not None and image.folded))
-    # `encoder` (the packed edge encoder) given: the initial edge latents are computed inside the same launch and
-    # never written to memory (e is None then)
-    if image is not None:      # cgnn_edge_stream_run: the rounds (and the encoder, if it is part of the image) as one image
-        e = ops.edge_stream_run(image, ps_all, pd_all, src, dst, e, e, edge_attr if image.enc_in else None,
-                                kernel=stream_kernel, lag=stream_lag, fixed_k=fixed_k)
-    else:
-        e = ops.edge_stream([p.edge for p in rounds], ps_all, pd_all, src, dst, e, e, encoder, edge_attr)
-    return x, e
+                    e_in=None if e is None else e.to_rows(), folded=bool(plan.image is not None and plan.image.folded))
+    return x, _run_edge_stream(P, plan, ps_all, pd_all, src, dst, e, edge_attr, fixed_k)
 
 
 class InteractionNetwork(nn.Module):
@@ -616,6 +649,20 @@ class EncodeProcessDecode(nn.Module):
         return (enc.num_hidden_layers == e0.num_hidden_layers and enc.hidden == e0.hidden and enc.out_dim == latent and
                 enc.in_dim <= 32 and (len(rounds) + 1) * (e0.num_hidden_layers + 1) <= 64 and lds <= 160 * 1024)
 
+    def _stream_plan(self, P, fixed_k: int, num_edges: int, edge_attr: Optional[torch.Tensor]) -> StreamPlan:
+        """How the rounds of the packed model ``P`` run on a graph of fixed in-degree ``fixed_k`` (0: any other edge
+        list) with ``num_edges`` edges of features ``edge_attr``: one-launch edge stream or one round at a time, which
+        kernel, the P-table format and whether the edge encoder runs inside the stream (the single-GPU and the sharded
+        forward both follow it).  Reads no device value."""
+        rounds = P["rounds"]
+        lag = int(getattr(self, "edge_stream_lag", 0))
+        if P["image"] is not None:      # cgnn_edge_stream_run(_w8): 32-edge tiles, the rounds (and the encoder) as one image
+            image, kernel = self._edge_stream_plan(P, fixed_k, num_edges, edge_attr)
+            return StreamPlan(True, image, kernel, lag, stream_table_format(rounds, kernel, lag), bool(image.enc_in))
+        fused = self._can_fuse_rounds(rounds, self._latent_size)      # cgnn_edge_stream: 16-edge tiles
+        return StreamPlan(fused, None, "tile16" if fused else None, lag, rounds[0].p_format if rounds else _lib.P_F32,
+                          fused and self._encoder_fits_stream(P))
+
     def invalidate_packed(self) -> None:
         """Forget the MFMA-packed copies of the weights.  They are rebuilt when a parameter tensor is replaced or
         modified in place THROUGH autograd-visible operations (``optimizer.step()``, ``load_state_dict``, ``p.copy_``):
@@ -766,38 +813,28 @@ class EncodeProcessDecode(nn.Module):
                 x = ops.gather_rows(x, order)
                 edge_attr = ops.gather_rows(edge_attr.view(n, -1), order).view(n * fixed_k, -1)
             P = self._pack(x.shape[1], edge_attr.shape[1])
-            xl = ops.mlp_rows(P["enc_node"], x)
-            image = P["image"]
-            fuse = image is not None or self._can_fuse_rounds(P["rounds"], xl.shape[1])
-            enc_in_stream = bool(image.enc_in) if image is not None else (fuse and self._encoder_fits_stream(P))
-            # edge latents live in TILED32 layout; in the fused path the encoder runs inside cgnn_edge_stream
-            el = None if enc_in_stream else ops.mlp_rows(P["enc_edge"], edge_attr, tiled=True)
-            H = P["rounds"][0].ws.out_dim if P["rounds"] else 0
-            scratch = None
-            if P["rounds"]:
-                dev = x.device
-                pdt = P["rounds"][0].p_dtype
-                ps = torch.empty((n, H), dtype=pdt, device=dev)
-                pd = torch.empty((n, H), dtype=pdt, device=dev)
-                agg = torch.empty((n, xl.shape[1]), dtype=torch.float32, device=dev)
-                e_upd = el.empty_like() if (self.message_source == "edge" and el is not None) else None
-                scratch = (ps, pd, agg, e_upd)
-            projected = False
             rounds = P["rounds"]
+            stream = self._stream_plan(P, fixed_k, src.numel(), edge_attr)
+            xl = ops.mlp_rows(P["enc_node"], x)
+            # edge latents live in TILED32 layout; in the fused path the encoder may run inside the edge stream's launch
+            el = None if stream.enc_in_stream else ops.mlp_rows(P["enc_edge"], edge_attr, tiled=True)
+            agg = torch.empty((n, xl.shape[1]), dtype=torch.float32, device=x.device) if rounds else None
             keep = {} if (want_latents and getattr(self, "keep_stream_inputs", False)) else None
-            if fuse:
-                image, stream_kernel = self._edge_stream_plan(P, fixed_k, src.numel(), edge_attr)
-                xl, el = _run_rounds_fused(rounds, xl, el, src, dst, fixed_k, agg,
-                                           P["enc_edge"] if enc_in_stream else None, edge_attr, image, keep,
-                                           stream_kernel, int(getattr(self, "edge_stream_lag", 0)))
-                rounds = []
-            for i, p in enumerate(rounds):
-                # residual streams updated in place (reference graph_network.py:181-182); the node kernel also
-                # emits the next round's sender / receiver projections
-                nxt = rounds[i + 1] if i + 1 < len(rounds) else None
-                xl, el, projected = _run_round(p, xl, el, src, dst, fixed_k, self.message_source, residual=True,
-                                               x_out=xl, e_out=el, scratch=scratch, projected=projected,
-                                               next_round=nxt)
+            if stream.fused:
+                xl, el = _run_rounds_fused(P, stream, xl, el, src, dst, fixed_k, agg, edge_attr, keep)
+            elif rounds:
+                H, pdt = rounds[0].ws.out_dim, rounds[0].p_dtype
+                ps = torch.empty((n, H), dtype=pdt, device=x.device)
+                pd = torch.empty((n, H), dtype=pdt, device=x.device)
+                e_upd = el.empty_like() if self.message_source == "edge" else None
+                projected = False
+                for i, p in enumerate(rounds):
+                    # residual streams updated in place (reference graph_network.py:181-182); the node kernel also
+                    # emits the next round's sender / receiver projections
+                    nxt = rounds[i + 1] if i + 1 < len(rounds) else None
+                    xl, el, projected = _run_round(p, xl, el, src, dst, fixed_k, self.message_source, residual=True,
+                                                   x_out=xl, e_out=el, scratch=(ps, pd, agg, e_upd),
+                                                   projected=projected, next_round=nxt)
             out = {"acceleration": ops.mlp_rows(P["dec_acc"], xl), "temp_rate": ops.mlp_rows(P["dec_tr"], xl)}
             if want_latents:
                 out["x_latent"], out["edge_latent"] = xl, el.to_rows()

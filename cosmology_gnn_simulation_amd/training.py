@@ -149,6 +149,66 @@ class TrainPacks:
         return [p for m in self.all for p in m.params()]
 
 
+class NodeStreamSteps:
+    """The node stream of one training step as pieces over the rows a runner holds: the forward keeps ``x_i`` and
+    ``agg_i`` per round; the backward seeds ``dx`` from the decoders, runs each round's node MLP backward and ends with
+    the encoder's, collecting the parameter gradients.  :class:`_NodeStream` runs them over a whole graph;
+    ``dist.ShardedTraining`` over one spatial tile's owned rows, with its halo exchanges in between.  Between
+    :meth:`round_backward` of round i and the next, the caller adds ``A^T du2`` (and ``du1``) into ``dx``."""
+
+    def _encode(self, packs: TrainPacks, x0: torch.Tensor) -> None:
+        self.packs, self.x0 = packs, x0
+        self.xs = [ops.mlp_rows(packs.enc.fwd, x0)]      # raw features: keep the f32 exponent range (three bf16 terms)
+        self.aggs = []                   # kept for the backward (N x D x 4 bytes per round; recomputing them cost 6 % of a step)
+
+    def _new_round(self) -> None:
+        """Room for the next round's ``agg_i`` and ``x_{i+1}`` (the rows of ``x0``)."""
+        shape, dev = (self.x0.shape[0], self.packs.latent), self.x0.device
+        self.aggs.append(torch.empty(shape, dtype=torch.float32, device=dev))
+        self.xs.append(torch.empty(shape, dtype=torch.float32, device=dev))
+
+    def _round_nodes(self, i: int, table: torch.Tensor, src, dst, fixed_k: int, a: int, b: int) -> None:
+        """Aggregation and node block of round ``i`` for receivers [a, b); ``table`` holds ``x_i`` in its first rows
+        (``graph_network._node_half``)."""
+        from .graph_network import _node_half
+        r = self.packs.rounds[i]
+        _node_half((r.run, r.run.layers[0], r.run2), table, src, dst, fixed_k, a, b, self.aggs[i], self.xs[i + 1])
+
+    def decode(self):
+        xl = self.xs[-1]
+        return ops.mlp_rows(self.packs.dec_acc.run, xl), ops.mlp_rows(self.packs.dec_tr.run, xl)
+
+    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
+        """Seeds ``dx`` = dL/dx_L from the decoders' output gradients (``None``: zero)."""
+        p = self.packs
+        n, D, dev = self.x0.shape[0], p.latent, self.x0.device
+        self.scratch = ops.BackwardScratch(n, p.hidden, max(D, 32), p.nh, dev)
+        self.grads_of = {}
+        zero = lambda t, w: torch.zeros((n, w), dtype=torch.float32, device=dev) if t is None else t  # noqa: E731
+        xl = self.xs[-1]
+        dx, _, self.grads_of[id(p.dec_acc)] = p.dec_acc.backward(xl, None, zero(d_acc, p.dec_acc.out_dim), self.scratch, True)
+        dx2, _, self.grads_of[id(p.dec_tr)] = p.dec_tr.backward(xl, None, zero(d_tr, p.dec_tr.out_dim), self.scratch, True)
+        self.dx = dx.add_(dx2)
+
+    def round_backward(self, i: int):
+        """Round ``i``'s node MLP backward: -> ``(du1, du2)``.  With x_{i+1} = x_i + f(x_i, agg(x_i)) the caller then
+        forms dx_i = dx_{i+1} + du1 + A^T du2 (A^T: senders <- receivers)."""
+        r = self.packs.rounds[i]
+        du1, du2, self.grads_of[id(r)] = r.backward(self.xs[i], self.aggs[i], self.dx, self.scratch, True, True)
+        self.aggs[i] = None
+        return du1, du2
+
+    def encode_backward(self, need_dx0: bool = True) -> Optional[torch.Tensor]:
+        p = self.packs
+        dx0, _, self.grads_of[id(p.enc)] = p.enc.backward(self.x0, None, self.dx, self.scratch, need_dx0)
+        self.dx = None
+        return dx0
+
+    def local_grads(self) -> List[torch.Tensor]:
+        """The parameter gradients of the rows held here, in ``TrainPacks.params()`` order."""
+        return [g for m in self.packs.all for g in self.grads_of[id(m)]]
+
+
 class _NodeStream(torch.autograd.Function):
     """acceleration, temp_rate = f(x0; node-stream parameters).  Non-tensor context first, then ``x0`` and the
     parameters (so autograd routes one gradient to each)."""
@@ -156,48 +216,28 @@ class _NodeStream(torch.autograd.Function):
     @staticmethod
     def forward(ctx, packs: TrainPacks, graph, x0: torch.Tensor, *params: torch.Tensor):
         src, dst, fixed_k, _ = graph
-        n = x0.shape[0]
-        xs = [ops.mlp_rows(packs.enc.fwd, x0)]      # raw features: keep the f32 exponent range (three bf16 terms)
-        aggs = []                   # kept for the backward (N x D x 4 bytes per round; recomputing them cost 6 % of a step)
-        plan = ops.AggregatePlan.of(src, n, fixed_k, xs[0].shape[1]) if fixed_k > 0 else None
-        for r in packs.rounds:
-            x = xs[-1]
-            agg = ops.aggregate(x, src, dst, n, fixed_k, src.numel(), plan=plan)
-            aggs.append(agg)
-            xs.append(ops.node_block(r.run, r.run.layers[0], r.run2, x, agg, None, residual=True))
-        acc = ops.mlp_rows(packs.dec_acc.run, xs[-1])
-        tr = ops.mlp_rows(packs.dec_tr.run, xs[-1])
+        run = NodeStreamSteps()
+        run._encode(packs, x0)
+        for i in range(len(packs.rounds)):
+            run._new_round()
+            run._round_nodes(i, run.xs[i], src, dst, fixed_k, 0, x0.shape[0])
+        acc, tr = run.decode()
         if packs.edge_stream_fn is not None:      # model.train_edge_stream: the (dead) edge stream, for like-for-like step times
-            packs.edge_stream_fn(xs)
-        ctx.packs, ctx.graph, ctx.x0, ctx.xs, ctx.aggs = packs, graph, x0, xs, aggs
+            packs.edge_stream_fn(run.xs)
+        ctx.run, ctx.by_sender = run, graph[3]
         return acc, tr
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_acc, d_tr):
-        packs, (src, dst, fixed_k, by_sender), x0, xs = ctx.packs, ctx.graph, ctx.x0, ctx.xs
-        n, D = x0.shape[0], packs.latent
-        scratch = ops.BackwardScratch(n, packs.hidden, max(D, 32), packs.nh, x0.device)
-        grads_of = {}
-        xl = xs[-1]
-        zero = lambda t, w: torch.zeros((n, w), dtype=torch.float32, device=x0.device) if t is None else t  # noqa: E731
-        dx, _, grads_of[id(packs.dec_acc)] = packs.dec_acc.backward(xl, None, zero(d_acc, packs.dec_acc.out_dim),
-                                                                    scratch, True)
-        dx2, _, grads_of[id(packs.dec_tr)] = packs.dec_tr.backward(xl, None, zero(d_tr, packs.dec_tr.out_dim),
-                                                                   scratch, True)
-        dx = dx.add_(dx2)
-        for i in range(len(packs.rounds) - 1, -1, -1):
-            r, x = packs.rounds[i], xs[i]
-            agg = ctx.aggs[i]
-            ctx.aggs[i] = None
-            du1, du2, grads_of[id(r)] = r.backward(x, agg, dx, scratch, True, True)
-            # x_{i+1} = x_i + f(x_i, agg(x_i)):  dx_i = dx_{i+1} + du1 + A^T du2     (A^T: senders <- receivers)
-            dx = ops.aggregate_csr(du2, by_sender, out=dx, add1=dx, add2=du1)      # one pass instead of three
-        need_dx0 = ctx.needs_input_grad[2]
-        dx0, _, grads_of[id(packs.enc)] = packs.enc.backward(x0, None, dx, scratch, need_dx0)
-        flat = [g for m in packs.all for g in grads_of[id(m)]]
-        ctx.xs = None
-        return (None, None, dx0, *flat)
+        run, by_sender = ctx.run, ctx.by_sender
+        ctx.run = None
+        run.decode_backward(d_acc, d_tr)
+        for i in range(len(run.packs.rounds) - 1, -1, -1):
+            du1, du2 = run.round_backward(i)
+            run.dx = ops.aggregate_csr(du2, by_sender, out=run.dx, add1=run.dx, add2=du1)      # one pass instead of three
+        dx0 = run.encode_backward(ctx.needs_input_grad[2])
+        return (None, None, dx0, *run.local_grads())
 
 
 class _TrainEdge:

@@ -59,13 +59,10 @@ if a.op == "edge_stream":
     mL.edge_stream_kernel = os.environ.get("CGNN_RUN_STREAM_KERNEL", "tile32w")
     PL = mL._pack(17, 4)
     roundsL = [r.edge for r in PL["rounds"]]
-    imageL = PL["image"]
-    kernL = "tile32"
-    if imageL is not None:
-        imageL, kernL = mL._edge_stream_plan(PL, fk, n * k, ea)
-    encL = None if imageL is not None else (PL["enc_edge"] if mL._encoder_fits_stream(PL) else None)
-    # the table format the model itself would hand this kernel (fp16 rows for the two-waves-per-SIMD kernel)
-    pdtL = ops.p_format_dtype(graph_network.stream_table_format(PL["rounds"], kernL if imageL is not None else None, mL.edge_stream_lag))
+    planL = mL._stream_plan(PL, fk, n * k, ea)       # the kernel, encoder and table format the model itself would use
+    imageL, kernL = planL.image, planL.kernel
+    encL = PL["enc_edge"] if imageL is None and planL.enc_in_stream else None
+    pdtL = ops.p_format_dtype(planL.p_format)
     ps_all = torch.randn(L, n, d, device=dev, generator=gen).to(pdtL)
     pd_all = torch.randn(L, n, d, device=dev, generator=gen).to(pdtL)
 if a.op == "node_block_proj":     # the node block as the fused forward runs it: next round's projections inside
@@ -75,9 +72,8 @@ if a.op == "node_block_proj":     # the node block as the fused forward runs it:
     m2.edge_precision, m2.node_precision = a.edge_precision, a.node_precision
     P2 = m2._pack(17, 4)
     r0, r1 = P2["rounds"]
-    # ... in the table format of the forward's edge stream (graph_network.stream_table_format)
-    kern2 = m2._edge_stream_plan(P2, fk, n * k, ea)[1] if P2["image"] is not None else None
-    fmt2 = graph_network.stream_table_format(P2["rounds"], kern2, int(getattr(m2, "edge_stream_lag", 0)))
+    # ... in the table format of the forward's edge stream
+    fmt2 = m2._stream_plan(P2, fk, n * k, ea).p_format
     ps2, pd2 = ops.project_nodes(r1.ws, r1.wd, x, None, None, fmt2)
 if a.op == "aggregate_planned":
     plan_ = ops.AggregatePlan(src, n, fk)

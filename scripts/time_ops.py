@@ -73,6 +73,7 @@ mL = mL.to(dev).eval()
 mL.edge_precision, mL.node_precision, mL.edge_stream_kernel = a.edge_precision, a.node_precision, a.stream_kernel
 PL_ = mL._pack(17, 4)
 roundsL = PL_["rounds"]
+planL = mL._stream_plan(PL_, fk, E, ea)
 if a.edge_precision == "bf16" and (not a.only or a.only.startswith("edge_stream")):
     ps_all = torch.randn(L, n, d, device=dev).to(torch.bfloat16)
     pd_all = torch.randn(L, n, d, device=dev).to(torch.bfloat16)
@@ -87,7 +88,7 @@ if a.edge_precision == "bf16" and (not a.only or a.only.startswith("edge_stream"
     else:
         t("edge_stream", lambda: ops.edge_stream([r.edge for r in roundsL], ps_all, pd_all, src, dst, e, e),
           2 * E * d * 4 + 2 * E * 4 + L * 2 * n * d * 2, L * 6.0 * E * d * d)
-        if mL._encoder_fits_stream(PL_):
+        if planL.enc_in_stream:
             t("edge_stream+enc", lambda: ops.edge_stream([r.edge for r in roundsL], ps_all, pd_all, src, dst, None, e,
                                                          PL_["enc_edge"], ea),
               E * d * 4 + E * 16 + 2 * E * 4 + L * 2 * n * d * 2, L * 6.0 * E * d * d + enc_flops)
@@ -117,8 +118,7 @@ t("node_block", lambda: ops.node_block(p.node, p.wx, p.wa, x, agg, x, True), 3 *
 if len(roundsL) > 1 and roundsL[0].node.precision in _lib.N16_NODE:      # 16-row node kernels: projections of the next round fused in
     q_ = roundsL[1]
     # ... in the table format the forward's edge stream takes (fp16 rows for the two-waves-per-SIMD kernel)
-    kern_ = mL._edge_stream_plan(PL_, fk, E, ea)[1] if PL_["image"] is not None else None
-    fmt_ = graph_network.stream_table_format(roundsL, kern_, int(getattr(mL, "edge_stream_lag", 0)))
+    fmt_ = planL.p_format
     psf_, pdf_ = ps.to(ops.p_format_dtype(fmt_)), pd.to(ops.p_format_dtype(fmt_))
     t("node_block+proj", lambda: ops.node_block(roundsL[0].node, roundsL[0].wx, roundsL[0].wa, x, agg, x, True,
                                                 (q_.ws_fused, q_.wd_fused, psf_, pdf_, fmt_)),
