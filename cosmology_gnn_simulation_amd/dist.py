@@ -19,13 +19,14 @@ per graph with torch indexing; the per-round data path is HIP kernels + RCCL.
 """
 from __future__ import annotations
 
+import math
 import time
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops, synthetic
+from . import _lib, ops, synthetic, training
 from ._lib import CgnnError
 from .graph_network import _next_projection, _node_half, _run_edge_stream, _run_round
 from .training import NodeStreamSteps
@@ -531,9 +532,21 @@ def sharded_training_loss(pred: dict, y_acc: torch.Tensor, y_tr: torch.Tensor, n
     return mse + mom, value
 
 
+def _all_reduce_grads(grads: Sequence[torch.Tensor], group=None) -> List[torch.Tensor]:
+    """The ranks' parameter gradients summed by ONE all-reduce of a flat buffer; -> views of it shaped like ``grads``."""
+    flat = torch.cat([g.reshape(-1) for g in grads])
+    _all_reduce_(flat, group)
+    out, off = [], 0
+    for g in grads:
+        out.append(flat[off:off + g.numel()].view_as(g))
+        off += g.numel()
+    return out
+
+
 class ShardedTraining(NodeStreamSteps):
     """A training step of ``EncodeProcessDecode`` (``message_source="x_j"``, ``train_precision`` "fp32" / "fp32x3") over one
-    spatial tile: the node stream of :class:`training._NodeStream` on the owned rows, with one halo exchange of the f32
+    spatial tile.  An edge model with ``model.train_edge_messages`` gets a :class:`ShardedEdgeTraining` instead (the
+    constructor picks it).  Under x_j: the node stream of :class:`training._NodeStream` on the owned rows, with one halo exchange of the f32
     latents per round in the forward and one reverse exchange of their gradients per round in the backward.
 
     Forward of round i: ``x_i`` (owned rows) is staged into the local table ``[owned | ghosts]``, the exchange fills the
@@ -550,10 +563,16 @@ class ShardedTraining(NodeStreamSteps):
     ``torch.autograd.Function`` for a real process group.  ``halo`` needs ``start`` / ``finish`` and ``start_return`` /
     ``finish_return`` (:class:`HaloExchange`, the default)."""
 
+    def __new__(cls, model, shard: Shard, halo=None, group=None):
+        if cls is ShardedTraining and model.message_source == "edge" and getattr(model, "train_edge_messages", False):
+            cls = ShardedEdgeTraining
+        return super().__new__(cls)
+
     def __init__(self, model, shard: Shard, halo=None, group=None):
-        if model.message_source != "x_j":
-            raise NotImplementedError("sharded training is built for message_source='x_j'; 'edge' models train on one "
-                                      "GPU (model.train_edge_messages)")
+        edge = isinstance(self, ShardedEdgeTraining)
+        if model.message_source != ("edge" if edge else "x_j") or (edge and not getattr(model, "train_edge_messages", False)):
+            raise NotImplementedError("sharded training is built for message_source='x_j', and for 'edge' with "
+                                      "model.train_edge_messages = True")
         if getattr(model, "train_edge_stream", False):
             raise NotImplementedError("sharded training does not run the (dead) edge stream: model.train_edge_stream "
                                       "is single-GPU only")
@@ -650,13 +669,7 @@ class ShardedTraining(NodeStreamSteps):
         dx0 = self.encode_backward(need_dx0)
         grads = self.local_grads()
         self.xs = self.aggs = None
-        flat = torch.cat([g.reshape(-1) for g in grads])
-        _all_reduce_(flat, self.group)              # one all-reduce of every parameter gradient
-        out, off = [], 0
-        for g in grads:
-            out.append(flat[off:off + g.numel()].view_as(g))
-            off += g.numel()
-        return dx0, out
+        return dx0, _all_reduce_grads(grads, self.group)
 
     def __call__(self, x0: Optional[torch.Tensor] = None) -> dict:
         """Differentiable predictions of the owned particles (local order; ``shard.owned_global`` maps them back).  The
@@ -683,6 +696,270 @@ class _ShardedNodeStream(torch.autograd.Function):
         ctx.runner = None
         dx0, grads = runner.run_backward(d_acc, d_tr, ctx.needs_input_grad[1])
         return (None, dx0, *grads)
+
+
+# ----------------------------------------------------------------------------
+# sharded training (message_source="edge", model.train_edge_messages)
+# ----------------------------------------------------------------------------
+
+def edge_split_rows(n_interior: int, k: int, tile: int = 32) -> int:
+    """Receivers of an edge-mode round's interior part: ``n_interior`` rounded DOWN so that ``n_split * k`` is a multiple of
+    ``tile``, so that the TILED32 edge tensors split at a tile boundary; 0 when no positive count aligns."""
+    if n_interior < 0 or k < 1 or tile < 1:
+        raise ValueError(f"edge_split_rows: n_interior {n_interior}, k {k}, tile {tile}")
+    step = tile // math.gcd(k, tile)
+    return n_interior - n_interior % step
+
+
+def shard_edge_training_bytes(n_owned: int, n_ghost: int, k: int, latent: int, hidden: int, num_hidden_layers: int,
+                              rounds: int) -> int:
+    """One rank's share of the edge-mode training memory: ``training.edge_training_bytes`` over the shard's
+    ``n_owned * k`` edges, plus the node tables kept per round with their ghost rows (``L n_local D`` floats)."""
+    return training.edge_training_bytes(n_owned * k, latent, hidden, num_hidden_layers, rounds) + \
+        4 * rounds * (n_owned + n_ghost) * latent
+
+
+def _edge_rows(t: "ops.TiledRows", lo: int, hi: int) -> "ops.TiledRows":
+    """Edges [lo, hi) of TILED32 edge rows as a view of ``t.buf`` (``lo`` on a tile boundary)."""
+    if lo % 32 or not 0 <= lo <= hi <= t.n:
+        raise CgnnError(f"edge rows [{lo}, {hi}) of {t.n} do not start on a 32-edge tile")
+    rows = (hi - lo + 31) // 32 * 32
+    return ops.TiledRows(hi - lo, t.width, t.device, buf=t.buf[lo:lo + rows])
+
+
+class ShardedEdgeTraining(ShardedTraining):
+    """A training step of an ``EncodeProcessDecode`` with ``message_source="edge"`` and ``model.train_edge_messages`` over
+    one spatial tile: :class:`training._EdgeStreams` on the shard's local rows, both streams differentiated.
+    ``ShardedTraining(model, shard)`` returns one for such a model.
+
+    Forward of round i: ``x_i`` sits in the owned rows of the kept local table ``[owned | ghosts]`` (:meth:`stage`), the
+    exchange fills the ghosts.  Under it the interior part projects ``Ps`` / ``Pd`` of the owned rows, runs the edge
+    block over the edges of receivers ``[0, n_split)``, their fixed-k aggregate of ``e_upd`` and the node block; after
+    it the boundary part projects ``Ps`` of the ghosts and does the same for ``[n_split, n_owned)``.  ``n_split``
+    (:func:`edge_split_rows`) puts the split on a 32-edge tile.  Kept: every round's local table (ghost rows included),
+    ``agg_i`` of the owned rows and the input edge latents ``e_i`` of every round but the last's output.
+
+    Backward of round i (``dx`` = dL/dx_{i+1} on the owned rows): node MLP backward; ``Ps`` / ``Pd`` recomputed from the
+    kept table; ``edge_mlp_backward`` over the local edges; ``dPs`` of the ghost senders into the send buffer (a ghost row
+    reaches the loss only through its ``Ps`` row, so ``dPs``, H wide, is what crosses ranks); under the reverse exchange
+    the edge-row reductions, ``dPs`` of the owned rows and ``dPd``; then the returned rows are added into ``dPs``
+    (``ops.halo_return_add``), ``dWs`` / ``dWd`` / ``db1`` are reduced over the owned rows and
+    ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``.  The encoders' backwards give ``dx0`` of the owned rows and
+    ``d edge_attr`` of the local edges; one all-reduce sums the parameter gradients in ``EdgeTrainPacks.params()`` order."""
+
+    def __init__(self, model, shard: Shard, halo=None, group=None):
+        super().__init__(model, shard, halo, group)
+        self.n_split = edge_split_rows(shard.n_interior, shard.k)
+        self.d_edge_attr = None
+
+    # -- set-up ------------------------------------------------------------------------------------------------------
+    def _prepare(self, x0: torch.Tensor, edge_attr: Optional[torch.Tensor] = None) -> None:
+        m, sh = self.model, self.sh
+        ea = sh.edge_attr if edge_attr is None else edge_attr
+        with torch.no_grad():
+            m._materialize_all(x0.shape[1], ea.shape[1])
+            D, H, nh, L = m._latent_size, m._mlp_hidden_size, m._mlp_num_hidden_layers, len(m.processor)
+            need = shard_edge_training_bytes(sh.n_owned, sh.n_ghost, sh.k, D, H, nh, L)
+            free = training.free_device_bytes(x0.device)
+            if need > free:
+                raise CgnnError(f"rank {sh.rank}: edge-mode training needs about {need / 2**30:.1f} GiB of device memory for "
+                                f"the edge latents of every round, the edge-row backward scratch and the local node tables "
+                                f"({sh.n_owned * sh.k} local edges, {sh.n_local} local rows, latent {D}, hidden {H}, {L} "
+                                f"rounds); {free / 2**30:.1f} GiB are free")
+            self.packs = m._train_packs(edge=True)      # refuses what the edge training kernels do not take (CgnnError)
+        if self._csr is None:
+            self._csr = ops.SenderCsr(sh.src_local, None, sh.n_local)      # the local edges by sender, once per shard
+            self._plan = halo_return_plan(sh.send_idx.to(x0.device), sh.send_counts, sh.n_owned)
+
+    # -- forward pieces ----------------------------------------------------------------------------------------------
+    def encode(self, x0: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None) -> None:
+        """Node encoder on the owned rows, edge encoder on the local edges (defaults: ``shard.x_feat`` /
+        ``shard.edge_attr``)."""
+        sh = self.sh
+        x0 = (sh.x_feat if x0 is None else x0).detach().float().contiguous()
+        ea = (sh.edge_attr if edge_attr is None else edge_attr).detach().float().contiguous()
+        if x0.shape[0] != sh.n_owned or ea.shape[0] != sh.n_owned * sh.k:
+            raise CgnnError(f"ShardedTraining: {x0.shape[0]} input rows and {ea.shape[0]} edges for {sh.n_owned} owned "
+                            f"particles with k = {sh.k}")
+        self._prepare(x0, ea)
+        p = self.packs
+        self.x0, self.edge_attr = x0, ea
+        D, H, dev = p.latent, p.hidden, x0.device
+        self.xs = [torch.empty((sh.n_local if p.rounds else sh.n_owned, D), dtype=torch.float32, device=dev)]
+        ops.mlp_rows(p.enc.fwd, x0, out=self.xs[0][:sh.n_owned])
+        self.es = [ops.mlp_rows(p.enc_edge.fwd, ea, tiled=True)]       # raw features: three bf16 terms or exact
+        self.aggs = []
+        self._e_upd = self.es[0].empty_like()
+        self._ps = torch.empty((sh.n_local, H), dtype=torch.float32, device=dev)
+        self._pd = torch.empty((sh.n_owned, H), dtype=torch.float32, device=dev)
+
+    def stage(self, i: int) -> torch.Tensor:
+        """Round ``i``'s local table, kept for the backward: ``x_i`` is in its owned rows, the exchange is to fill the
+        ghost rows.  Makes room for ``agg_i``, ``x_{i+1}`` and ``e_{i+1}``."""
+        sh, p = self.sh, self.packs
+        last = i + 1 == len(p.rounds)
+        dev = self.x0.device
+        self.aggs.append(torch.empty((sh.n_owned, p.latent), dtype=torch.float32, device=dev))
+        self.xs.append(torch.empty((sh.n_owned if last else sh.n_local, p.latent), dtype=torch.float32, device=dev))
+        if not last:
+            self.es.append(self.es[i].empty_like())
+        return self.xs[i]
+
+    def _project(self, i: int, part: str) -> None:
+        """Round ``i``'s P_F32 tables: ``Ps`` / ``Pd`` of the owned rows (``"owned"``) or ``Ps`` of the ghost rows."""
+        sh, ep, x = self.sh, self.packs.edges[i], self.xs[i]
+        no = sh.n_owned
+        if part == "owned":
+            ops.project_nodes(ep.ws, ep.wd, x[:no], self._ps[:no], self._pd, p_format=_lib.P_F32)
+        elif sh.n_ghost:
+            ops.project_nodes(ep.ws, None, x[no:], self._ps[no:], None, p_format=_lib.P_F32)
+
+    def round_nodes(self, i: int, part: str = "all") -> None:
+        """Round ``i`` for the owned receivers of ``part``: ``"interior"`` ([0, n_split): no ghost sender, may run under
+        the exchange; projects the owned rows), ``"boundary"`` (after it; projects the ghost rows) or ``"all"``."""
+        sh, p = self.sh, self.packs
+        no, k = sh.n_owned, sh.k
+        a, b = {"all": (0, no), "interior": (0, self.n_split), "boundary": (self.n_split, no)}[part]
+        if part != "boundary":
+            self._project(i, "owned")
+        if part != "interior":
+            self._project(i, "ghosts")
+        if b <= a:
+            return
+        ep, r, x = p.edges[i], p.rounds[i], self.xs[i]
+        src, dst = sh.src_local[a * k:b * k], sh.dst_local[a * k:b * k]
+        e, e_upd = _edge_rows(self.es[i], a * k, b * k), _edge_rows(self._e_upd, a * k, b * k)
+        if i + 1 == len(p.rounds):          # e_L is not kept: the update alone, as on one GPU
+            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, e_upd, None, residual=False)
+        else:
+            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, _edge_rows(self.es[i + 1], a * k, b * k), e_upd,
+                           residual=True)
+        agg = self.aggs[i][a:b]
+        ops.aggregate(e_upd, None, dst, b - a, k, (b - a) * k, agg)
+        ops.node_block(r.run, r.run.layers[0], r.run2, x[a:b], agg, self.xs[i + 1][a:b], True)
+
+    # -- backward pieces ---------------------------------------------------------------------------------------------
+    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
+        super().decode_backward(d_acc, d_tr)
+        p, ne, dev = self.packs, self.es[0].n, self.x0.device
+        self._escratch = ops.BackwardScratch(ne, p.hidden, max(p.latent, 32), p.nh, dev)
+        self._dy = torch.empty((max(ne, 1), p.latent), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i
+        self._de = self.es[0].empty_like()      # d e_i, in place: TILED32 between rounds, rows after round 0
+
+    def round_backward_local(self, i: int) -> torch.Tensor:
+        """Steps 1-4 of round ``i``: node MLP backward on the owned rows, the forward's ``Ps`` / ``Pd`` recomputed, the edge
+        model's backward over the local edges, then ``dPs`` of the ghost senders, written into (and returned as) the send
+        buffer of the reverse exchange, [n_ghost, H]."""
+        sh, p = self.sh, self.packs
+        no = sh.n_owned
+        r, ep = p.rounds[i], p.edges[i]
+        agg = self.aggs[i]
+        self.aggs[i] = None
+        self._round = i
+        self._du1, d_agg, self.grads_of[id(r)] = r.backward(self.xs[i][:no], agg, self.dx, self.scratch, True, True)
+        self._project(i, "owned")           # the forward's tables, bit for bit (the same calls on the same rows)
+        self._project(i, "ghosts")
+        de, first = self._de, i == 0
+        ops.edge_mlp_backward(ep.rec, ep.bwd, self._ps, self._pd, sh.src_local, sh.dst_local, self.es[i], d_agg,
+                              None if i + 1 == len(p.rounds) else de, self._escratch, self._dy, de.buf if first else de,
+                              de_out_rows=first, n_recv=no)
+        shape = (sh.n_ghost, p.hidden)
+        if self._ghost is None or tuple(self._ghost.shape) != shape or self._ghost.device != d_agg.device:
+            self._ghost = torch.empty(shape, dtype=torch.float32, device=d_agg.device)
+        if sh.n_ghost:
+            ops.aggregate_csr(self._escratch.g_a[0], self._csr, out=self._ghost, row_range=(no, sh.n_local))
+        return self._ghost
+
+    def round_backward_owned(self, i: int) -> None:
+        """Step 6 (runs under the reverse exchange): the edge-row reductions, ``dPs`` of the owned rows and ``dPd``."""
+        sh, ep = self.sh, self.packs.edges[i]
+        no, g_a0 = sh.n_owned, self._escratch.g_a[0]
+        self._row_grads = training.edge_row_grads(ep, self._escratch, self._dy, self.es[i])
+        self._dps = ops.aggregate_csr(g_a0, self._csr, row_range=(0, no))
+        self._dpd = ops.aggregate(g_a0, None, sh.dst_local, no, sh.k, no * sh.k)
+        self.es[i] = None
+
+    def round_backward_return(self, ret: torch.Tensor) -> None:
+        """Steps 7-8: the ``dPs`` rows the peers returned, added at the rows they had requested; ``dWs`` / ``dWd`` / ``db1``
+        over the owned rows; ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``."""
+        i, no = self._round, self.sh.n_owned
+        ep = self.packs.edges[i]
+        if ret.shape[0]:
+            ops.halo_return_add(self._dps, ret, *self._plan)
+        dw0, layer_grads, dgamma, dbeta = self._row_grads
+        db0 = training.edge_node_grads(ep, dw0, self._dps, self._dpd, self.xs[i][:no])
+        self.grads_of[id(ep)] = [dw0, db0] + layer_grads + [dgamma, dbeta]
+        self.dx = ops.linear2_rows(ep.wst, ep.wdt, self._dps, self._dpd, add1=self.dx, add2=self._du1, out=self.dx)
+        self._du1 = self._dps = self._dpd = self._row_grads = None
+        self.xs[i + 1] = None
+
+    def encode_backward(self, need_dx0: bool = True, need_dea: bool = False) -> Optional[torch.Tensor]:
+        """The node encoder's backward (-> ``dx0`` of the owned rows) and the edge encoder's: ``d_edge_attr`` of the local
+        edges when ``need_dea``, else None."""
+        p = self.packs
+        dx0 = super().encode_backward(need_dx0)
+        de = self._de
+        if not p.rounds:
+            de.buf.zero_()                  # no round reads the edge encoder's output
+        dea, _, self.grads_of[id(p.enc_edge)] = p.enc_edge.backward(self.edge_attr, None, de.buf[:de.n], self._escratch,
+                                                                    need_dea)
+        self.d_edge_attr = dea if need_dea else None
+        self._de = self._dy = self._escratch = None
+        return dx0
+
+    def local_grads(self) -> List[torch.Tensor]:
+        """The parameter gradients of the rows held here, in ``EdgeTrainPacks.params()`` order."""
+        p = self.packs
+        order = [p.enc, p.enc_edge] + [m for pair in zip(p.edges, p.rounds) for m in pair] + [p.dec_acc, p.dec_tr]
+        return [g for m in order for g in self.grads_of[id(m)]]
+
+    # -- one step through a process group ----------------------------------------------------------------------------
+    def run_forward(self, x0: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None):
+        """Encoders, rounds with the exchange hidden behind the interior receivers, decoders: ``(acc, temp_rate)``."""
+        self.encode(x0, edge_attr)
+        _exchange_rounds(self.halo, len(self.packs.rounds), self.stage, self.round_nodes, 0 < self.n_split)
+        return self.decode()
+
+    def run_backward(self, d_acc, d_tr, need_dx0: bool = True, need_dea: bool = False):
+        """-> (dx0 of the owned rows, d edge_attr of the local edges or None, global parameter gradients in
+        ``EdgeTrainPacks.params()`` order)."""
+        self.decode_backward(d_acc, d_tr)
+        for i in range(len(self.packs.rounds) - 1, -1, -1):
+            handle = self.halo.start_return(self.round_backward_local(i))
+            self.round_backward_owned(i)
+            self.round_backward_return(self.halo.finish_return(handle))
+        dx0 = self.encode_backward(need_dx0, need_dea)
+        grads = self.local_grads()
+        self.xs = self.aggs = self.es = None
+        self._e_upd = self._ps = self._pd = None
+        return dx0, self.d_edge_attr, _all_reduce_grads(grads, self.group)
+
+    def __call__(self, x0: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None) -> dict:
+        """Differentiable predictions of the owned particles (local order).  The backward leaves the global gradient in
+        every parameter's ``.grad``, the edge models' included, and ``d edge_attr`` of the local edges in the edge
+        features' ``.grad`` when they require one (default: ``shard.edge_attr``)."""
+        x = self.sh.x_feat if x0 is None else x0
+        ea = self.sh.edge_attr if edge_attr is None else edge_attr
+        self._prepare(x.detach().float(), ea)
+        acc, tr = _ShardedEdgeStreams.apply(self, x, ea, *self.packs.params())
+        return {"acceleration": acc, "temp_rate": tr}
+
+
+class _ShardedEdgeStreams(torch.autograd.Function):
+    """``acceleration, temp_rate`` of the owned rows = f(x0 owned, edge_attr local; all parameters) over a process group."""
+
+    @staticmethod
+    def forward(ctx, runner: ShardedEdgeTraining, x0: torch.Tensor, edge_attr: torch.Tensor, *params: torch.Tensor):
+        ctx.runner = runner
+        return runner.run_forward(x0, edge_attr)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_acc, d_tr):
+        runner = ctx.runner
+        ctx.runner = None
+        dx0, dea, grads = runner.run_backward(d_acc, d_tr, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return (None, dx0, dea, *grads)
 
 
 # ----------------------------------------------------------------------------

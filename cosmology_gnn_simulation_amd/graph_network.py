@@ -762,9 +762,7 @@ class EncodeProcessDecode(nn.Module):
             self._materialize_all(x.shape[1], ea.shape[1])
             D, H = self._latent_size, self._mlp_hidden_size
             need = training.edge_training_bytes(ne, D, H, self._mlp_num_hidden_layers, len(self.processor))
-            # free device memory plus what the caching allocator holds reserved but unused (a previous step's scratch)
-            free = torch.cuda.mem_get_info(x.device)[0] + \
-                torch.cuda.memory_reserved(x.device) - torch.cuda.memory_allocated(x.device)
+            free = training.free_device_bytes(x.device)
             if need > free:
                 raise CgnnError(f"edge-mode training needs about {need / 2**30:.1f} GiB of device memory for the edge "
                                 f"latents of every round and the edge-row backward scratch ({ne} edges, latent {D}, hidden "

@@ -991,14 +991,17 @@ _EDGE_BWD_PRECISIONS = ((F32, F32), (_lib.F32X3, _lib.F32X3), (_lib.F16X2, _lib.
 
 def edge_mlp_backward(fwd: PackedMLP, bwd: PackedMLP, ps: torch.Tensor, pd: torch.Tensor, src: torch.Tensor,
                       dst: torch.Tensor, e_in: TiledRows, d_agg: torch.Tensor, de_in: Optional[TiledRows],
-                      scratch: BackwardScratch, dy: torch.Tensor, de_out, de_out_rows: bool = False):
+                      scratch: BackwardScratch, dy: torch.Tensor, de_out, de_out_rows: bool = False,
+                      n_recv: Optional[int] = None):
     """Data gradients of one round's edge model under ``message_source="edge"`` (``cgnn_edge_mlp_backward``): recomputes
     ``u = LN(MLP(ps[src] + pd[dst] + e_in We^T))`` per 32-edge tile, forms ``dy = d_agg[dst] + de_in`` (``de_in`` None:
     zero), fills ``scratch`` (``h``, ``g_a``, ``g_o``, ``zhat`` over the edge rows) and ``dy`` ([>= E, latent] float32,
     row-major) and writes ``de_out = de_in + We^T g_a[0]``: a :class:`TiledRows`, or with ``de_out_rows`` a row-major
     tensor of at least E rows (either may share memory with ``de_in``).  ``fwd`` is the edge model packed for
     ``edge_block`` (layer 0 = the We column block), ``bwd`` the transposed weights; ``ps`` / ``pd`` float32
-    ``project_nodes`` tables.  Shapes or precisions the kernel is not built for raise :class:`CgnnError` before launch."""
+    ``project_nodes`` tables.  ``n_recv``: the rows of ``pd`` and ``d_agg`` (default: those of ``ps``), when the receivers
+    are the first ``n_recv`` of the ``ps`` rows (a shard's owned rows; its ghost senders follow); every ``dst`` must be
+    below it.  Shapes or precisions the kernel is not built for raise :class:`CgnnError` before launch."""
     if not isinstance(e_in, TiledRows) or (de_in is not None and not isinstance(de_in, TiledRows)):
         raise CgnnError("edge_mlp_backward: e_in / de_in must be TiledRows (the layout edge_block leaves them in)")
     ne, latent = e_in.n, e_in.width
@@ -1015,13 +1018,16 @@ def edge_mlp_backward(fwd: PackedMLP, bwd: PackedMLP, ps: torch.Tensor, pd: torc
     if src.numel() != ne or dst.numel() != ne:
         raise CgnnError("edge_mlp_backward: src/dst length does not match the edge latents")
     n = ps.shape[0] if ps.dim() == 2 else -1
-    for t, name in ((ps, "ps"), (pd, "pd")):
+    nr = n if n_recv is None else int(n_recv)
+    if not 0 <= nr <= n:
+        raise CgnnError(f"edge_mlp_backward: n_recv {n_recv} outside [0, {n}] (the rows of ps)")
+    for t, name, rows in ((ps, "ps", n), (pd, "pd", nr)):
         require_device(t, name)
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, hidden):
-            raise CgnnError(f"edge_mlp_backward: {name} must be a contiguous float32 [nodes, {hidden}] table (CGNN_P_F32)")
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (rows, hidden):
+            raise CgnnError(f"edge_mlp_backward: {name} must be a contiguous float32 [{rows}, {hidden}] table (CGNN_P_F32)")
     require_device(d_agg, "d_agg")
-    if d_agg.dtype != torch.float32 or not d_agg.is_contiguous() or tuple(d_agg.shape) != (n, latent):
-        raise CgnnError(f"edge_mlp_backward: d_agg must be contiguous float32 [{n}, {latent}]")
+    if d_agg.dtype != torch.float32 or not d_agg.is_contiguous() or tuple(d_agg.shape) != (nr, latent):
+        raise CgnnError(f"edge_mlp_backward: d_agg must be contiguous float32 [{nr}, {latent}]")
     if de_in is not None and (de_in.n != ne or de_in.width != latent):
         raise CgnnError("edge_mlp_backward: de_in does not match the edge latents")
     if ne > scratch.n or scratch.hidden != hidden or scratch.nh < nh or scratch.out_padded < latent:

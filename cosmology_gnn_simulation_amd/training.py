@@ -314,6 +314,12 @@ def edge_training_bytes(num_edges: int, latent: int, hidden: int, num_hidden_lay
     return 4 * (rounds * num_edges * latent + (2 * num_hidden_layers + 3) * num_edges * hidden)
 
 
+def free_device_bytes(device) -> int:
+    """Free device memory plus what the caching allocator holds reserved but unused (a previous step's scratch): what the
+    memory guards of edge-mode training compare their estimates with."""
+    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
 class _EdgeStreams(torch.autograd.Function):
     """acceleration, temp_rate = f(x0, edge_attr; all parameters) under ``message_source="edge"``: node AND edge stream.
     Non-tensor context first, then ``x0``, ``edge_attr`` and the parameters in ``EdgeTrainPacks.params()`` order."""
@@ -400,11 +406,28 @@ def edge_round_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Te
     ``x`` its node latents): -> (parameter gradients in ``ep.params()`` order, dPs, dPd) with every reduction in a fixed
     order.  ``dy`` is overwritten (it receives ``e`` in rows for ``dWe``)."""
     ne, n = e.n, x.shape[0]
-    D, H, nh, prec = ep.latent, ep.hidden, ep.nh, ep.precision
+    H = ep.hidden
     dev = x.device
     g_a0 = escratch.g_a[0]
+    dw0, layer_grads, dgamma, dbeta = edge_row_grads(ep, escratch, dy, e)
+    if ne:
+        dps = ops.aggregate_csr(g_a0, by_sender_e)
+        dpd = ops.aggregate(g_a0, None, dst, n, fixed_k, ne) if fixed_k > 0 else ops.aggregate_csr(g_a0, by_receiver_e)
+    else:
+        dps = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        dpd = torch.zeros_like(dps)
+    db0 = edge_node_grads(ep, dw0, dps, dpd, x)
+    return [dw0, db0] + layer_grads + [dgamma, dbeta], dps, dpd
+
+
+def edge_row_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Tensor, e: "ops.TiledRows"):
+    """The edge-row reductions of :func:`edge_round_grads`: -> (dW1 holding dWe in its columns [2D, 3D), [weight, bias
+    gradients of the later Linears], dgamma, dbeta).  ``dy`` is overwritten (it receives ``e`` in rows for ``dWe``)."""
+    ne = e.n
+    D, H, nh, prec = ep.latent, ep.hidden, ep.nh, ep.precision
+    dev = dy.device
+    g_a0 = escratch.g_a[0]
     dw0 = torch.zeros_like(ep.linears[0].weight, memory_format=torch.contiguous_format)
-    db0 = torch.zeros(H, dtype=torch.float32, device=dev)
     dgamma = torch.zeros(D, dtype=torch.float32, device=dev)
     dbeta = torch.zeros_like(dgamma)
     layer_grads = []
@@ -421,17 +444,21 @@ def edge_round_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Te
                             dw, 0, db, prec)
         layer_grads += [dw, db]
     # first layer [Ws | Wd | We]: dWe = g_a[0]^T e over the edge rows (e relaid out to rows into dy, read above: one
-    # E x D read + write), dWs = dPs^T x and dWd = dPd^T x over the node rows, db1 = colsum(dPd)
+    # E x D read + write); dWs, dWd and db1 over the node rows follow in edge_node_grads
     if ne:
         ops.weight_grad(g_a0, H, H, ops.relayout(e, out=dy), D, ne, dw0, 2 * D, None, prec)
-        dps = ops.aggregate_csr(g_a0, by_sender_e)
-        dpd = ops.aggregate(g_a0, None, dst, n, fixed_k, ne) if fixed_k > 0 else ops.aggregate_csr(g_a0, by_receiver_e)
-    else:
-        dps = torch.zeros((n, H), dtype=torch.float32, device=dev)
-        dpd = torch.zeros_like(dps)
+    return dw0, layer_grads, dgamma, dbeta
+
+
+def edge_node_grads(ep: _TrainEdge, dw0: torch.Tensor, dps: torch.Tensor, dpd: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The node-row part of the first layer's gradient: dWs = dPs^T x and dWd = dPd^T x into ``dw0`` over the rows of
+    ``x``; -> db1 = colsum(dPd)."""
+    D, H, prec = ep.latent, ep.hidden, ep.precision
+    n = x.shape[0]
+    db0 = torch.zeros(H, dtype=torch.float32, device=x.device)
     ops.weight_grad(dps, H, H, x, D, n, dw0, 0, None, prec)
     ops.weight_grad(dpd, H, H, x, D, n, dw0, D, db0, prec)
-    return [dw0, db0] + layer_grads + [dgamma, dbeta], dps, dpd
+    return db0
 
 
 def forward_train_edge(model, x0: torch.Tensor, edge_attr: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,

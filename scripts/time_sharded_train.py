@@ -1,8 +1,10 @@
 """Developer tool: one rank's share of a sharded training step (dist.ShardedTraining) on ONE GPU, without the exchanges (a
 halo stand-in that moves nothing in either direction), next to the unsharded training step of the same total size on the
-same GPU.  Both are forward + backward through the HIP node-stream kernels; HIP-event medians.  Not part of the product
-or tests.
-    python scripts/time_sharded_train.py [--world 8] [--particles 1000000] [--scaling strong] [--train-precision fp32x3]"""
+same GPU.  Both are forward + backward through the HIP node-stream kernels (``--message-source edge``: both streams, with
+``model.train_edge_messages``; where the unsharded edge step is refused for memory, its estimate is printed instead of a
+time); HIP-event medians.  Not part of the product or tests.
+    python scripts/time_sharded_train.py [--world 8] [--particles 1000000] [--scaling strong] [--train-precision fp32x3]
+                                         [--message-source x_j|edge]"""
 import argparse
 import os
 import sys
@@ -11,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cosmology_gnn_simulation_amd import data_utils, dist as cdist, graph_network, losses, ops, synthetic  # noqa: E402
+from cosmology_gnn_simulation_amd._lib import CgnnError  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--world", type=int, default=8)
@@ -22,7 +25,9 @@ ap.add_argument("--latent", type=int, default=128)
 ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--iters", type=int, default=7)
 ap.add_argument("--train-precision", default="fp32x3", choices=["fp32", "fp32x3"])
+ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"])
 a = ap.parse_args()
+edge = a.message_source == "edge"
 dev = torch.device("cuda")
 n_total = a.particles * (a.world if a.scaling == "weak" else 1)
 k, d, L = a.neighbors, a.latent, a.mp_steps
@@ -56,6 +61,9 @@ m = graph_network.EncodeProcessDecode(d, d, 2, L, 3)
 m.load_state_dict(synthetic.make_state_dict(d, d, 2, L, 3))
 m = m.to(dev).train()
 m.train_precision = a.train_precision
+if edge:
+    m.message_source = "edge"
+    m.train_edge_messages = True
 mse = torch.nn.functional.mse_loss
 
 
@@ -94,6 +102,8 @@ for p in range(world):
         wants.append(cdist.build_shard(pos, 1.0, k, world, p).want_global[a.rank])
 cdist.finish_shard(sh, wants)
 sh.x_feat = g.x[sh.owned_global].contiguous()
+if edge:      # the unsharded graph's edge features, receiver-major with k per receiver
+    sh.edge_attr = g.edge_attr[(sh.owned_global.view(-1, 1) * k + torch.arange(k, device=dev)).reshape(-1)].contiguous()
 y_acc, y_tr = g.y_acc[sh.owned_global], g.y_temp_rate[sh.owned_global]
 runner = cdist.ShardedTraining(m, sh, halo=NoExchange(sh))
 
@@ -119,20 +129,33 @@ def shard_step():
         runner.local_grads()
 
 
-print(f"{n_total} particles, k={k}, latent {d}, {L} rounds, train_precision {a.train_precision}; shard of rank "
-      f"{a.rank}/{world}: {sh.n_owned} owned ({sh.n_interior} interior), {sh.n_ghost} ghosts, {sum(sh.send_counts)} rows "
-      f"returned to it per round", flush=True)
-med_u, all_u = timed(unsharded_step, a.iters)
-print(f"unsharded training step (forward + backward): {med_u:.2f} ms median of {a.iters} "
-      f"({', '.join(f'{x:.1f}' for x in all_u)})", flush=True)
+split = f", n_split {runner.n_split}" if edge else ""
+print(f"{n_total} particles, k={k}, latent {d}, {L} rounds, message_source {a.message_source}, train_precision "
+      f"{a.train_precision}; shard of rank {a.rank}/{world}: {sh.n_owned} owned ({sh.n_interior} interior{split}), "
+      f"{sh.n_ghost} ghosts, {sum(sh.send_counts)} rows returned to it per round", flush=True)
+med_u = None
+try:
+    med_u, all_u = timed(unsharded_step, a.iters)
+    print(f"unsharded training step (forward + backward): {med_u:.2f} ms median of {a.iters} "
+          f"({', '.join(f'{x:.1f}' for x in all_u)})", flush=True)
+except CgnnError as err:          # the edge step's memory guard: its estimate instead of a time
+    if not edge:
+        raise
+    print(f"unsharded training step refused: {err}", flush=True)
+m.zero_grad(set_to_none=True)
+torch.cuda.empty_cache()
+torch.cuda.reset_peak_memory_stats()
 med_s, all_s = timed(shard_step, a.iters)
 print(f"one rank's training step, no exchange:        {med_s:.2f} ms median of {a.iters} "
       f"({', '.join(f'{x:.1f}' for x in all_s)})", flush=True)
-print(f"ratio unsharded / rank: {med_u / med_s:.2f} x  (measured without any exchange)")
+if med_u is not None:
+    print(f"ratio unsharded / rank: {med_u / med_s:.2f} x  (measured without any exchange)")
+peak = torch.cuda.max_memory_allocated() / 2**30
 with ops.OpTimer() as tm:
     shard_step()
 for name, (calls, total) in sorted(tm.summary().items(), key=lambda kv: -kv[1][1]):
     print(f"  {name:16s} {calls:4d} calls {total:9.3f} ms", flush=True)
-reverse_mb = sh.n_ghost * d * 4 / 1e6
-print(f"reverse exchange per round: {sh.n_ghost} ghost rows x {d} x 4 B = {reverse_mb:.1f} MB sent by this rank; "
-      f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB")
+width = runner.packs.hidden if edge else d         # edge mode returns dPs rows (hidden wide), x_j mode dx rows
+reverse_mb = sh.n_ghost * width * 4 / 1e6
+print(f"reverse exchange per round: {sh.n_ghost} ghost rows x {width} x 4 B = {reverse_mb:.1f} MB sent by this rank; "
+      f"peak memory of the rank's steps {peak:.2f} GiB (the graph and model of the whole box included)")
