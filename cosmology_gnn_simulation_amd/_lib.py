@@ -40,7 +40,7 @@ EXPORTS = (
     "cgnn_aggregate_csr", "cgnn_aggregate_csr_add", "cgnn_edge_stream", "cgnn_edge_stream_image_bytes", "cgnn_edge_stream_image_build",
     "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
     "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
-    "cgnn_rollout_integrate", "cgnn_frame_unpack",
+    "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
 )
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
 ROWS, TILED32 = 0, 1
@@ -117,6 +117,8 @@ def load() -> C.CDLL:
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_rollout_integrate.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, f32, f32, vp, vp]
     lib.cgnn_frame_unpack.argtypes = [vp, i64, i64, vp, vp, vp]
+    lib.cgnn_training_sample.argtypes = [vp, vp, vp, vp, i32, i64, vp, i64, C.c_double, C.c_uint64, C.c_uint64, f32, f32,
+                                         f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cgnn_gather_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_scatter_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_halo_return_add.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, i64, vp]

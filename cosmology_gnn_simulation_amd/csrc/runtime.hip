@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "cgnn_common.hpp"
+#include "window_features.hpp"
 
 namespace cgnn {
 
@@ -483,12 +484,6 @@ __global__ void scatter_rows_scalar_kernel(const float* __restrict__ rows, const
 }
 
 // ------------------------------------------------------------------ window features
-__device__ __forceinline__ float torch_remainder(float a, float b) {   // torch.remainder for float32
-    float r = fmodf(a, b);
-    if (r != 0.f && ((r < 0.f) != (b < 0.f))) r = __fadd_rn(r, b);
-    return r;
-}
-
 // rows == nullptr: row i of the output is particle i (n_rows == n); else particle rows[i] of the [W, n, 3] window.
 // One arithmetic serves both entries (cgnn_window_features / cgnn_window_features_rows); rows outside [0, n) are skipped.
 __global__ void window_features_kernel(const float* __restrict__ pos_seq, const float* __restrict__ temp_seq,
@@ -500,37 +495,13 @@ __global__ void window_features_kernel(const float* __restrict__ pos_seq, const 
     if (i >= n_rows) return;
     const int64_t g = rows != nullptr ? rows[i] : i;
     if (g < 0 || g >= n) return;
-    const int F = 3 * (W - 1) + W;
-    const float half = box * 0.5f, nhalf = -half;
-    float* xr = x + i * F;
-    float prev[3];
-    for (int t = 0; t < W; ++t) {
-        float cur[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float p = pos_seq[((int64_t)t * n + g) * 3 + c];
-            if (pos_noise != nullptr) p = __fadd_rn(p, pos_noise[(g * W + t) * 3 + c]);
-            cur[c] = torch_remainder(p, box);
-        }
-        if (t > 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float d = __fsub_rn(cur[c], prev[c]);
-                if (d < nhalf) d = __fadd_rn(d, box);
-                if (d > half) d = __fsub_rn(d, box);
-                const float v = __fdiv_rn(d, dt);
-                xr[3 * (t - 1) + c] = __fdiv_rn(__fsub_rn(v, vel_mean), vel_std);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) prev[c] = cur[c];
-        float T = temp_seq[(int64_t)t * n + g];
-        if (temp_noise != nullptr) T = __fadd_rn(T, temp_noise[g * W + t]);
-        xr[3 * (W - 1) + t] = __fdiv_rn(__fsub_rn(T, temp_mean), temp_std);
-    }
+    TableNoise noise{pos_noise, temp_noise, g * W};
+    WindowRow row;
+    window_features_row(pos_seq, temp_seq, W, n, g, box, dt, vel_mean, vel_std, temp_mean, temp_std, noise,
+                        x + i * (3 * (W - 1) + W), row);
     if (recent_pos != nullptr) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) recent_pos[i * 3 + c] = prev[c];
+        for (int c = 0; c < 3; ++c) recent_pos[i * 3 + c] = row.recent[c];
     }
 }
 

@@ -12,6 +12,8 @@ Faithfulness notes
   (``randn_like`` on ``[N, W-1, 3]`` then ``[N, W-1, 1]``, even when
   ``noise_std == 0``, :47,:63), so seeded runs see the same noise and the same RNG
   stream afterwards;
+  ``noise_rng="device"`` (extension) instead makes the noise, the features and the targets in one kernel
+  (``cgnn_training_sample``) from a counter-based generator: the reference's distribution and arithmetic, not its stream;
 * node features (wrap, velocities, normalisation: :91-145) come from one HIP kernel
   (``cgnn_window_features``) with the reference's float32 operation order;
 * edge displacements use the un-shifted sender (not minimum-image), as :151-164 do;
@@ -107,7 +109,8 @@ def _draw_reference_noise(pos_seq: torch.Tensor, tmp_seq: torch.Tensor, noise_st
 
 def preprocess(position_seq, temperature_seq, metadata, target_position=None, target_temperature=None,
                noise_std=0.0, num_neighbors=16, dt=None, box_size=None, device: Optional[torch.device] = None,
-               reference_rng: bool = True, check_bounds: bool = True):
+               reference_rng: bool = True, check_bounds: bool = True, noise_rng: str = "reference",
+               noise_seed: Optional[int] = None, noise_draw: int = 0):
     """Window ``[W, N, 3]`` / ``[W, N, 1]`` -> graph (reference data_utils.py:72-228).
 
     ``device`` (extension) selects the GPU; by default the inputs' device if they
@@ -116,12 +119,31 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
     (extension, only honoured when ``noise_std == 0``) skips the two CPU random draws
     the reference makes even for zero noise; results are identical, only the global
     RNG stream is left untouched (used by the on-device rollout).  ``check_bounds=False`` (extension) drops the
-    reference's sender-index assertion (:158-159), which costs one device-to-host synchronisation per call."""
+    reference's sender-index assertion (:158-159), which costs one device-to-host synchronisation per call.
+
+    ``noise_rng`` (extension) selects where the random-walk noise comes from.  ``"reference"`` (default) draws it on
+    the CPU from torch's global generator with the reference's call sequence, bit for bit.  ``"device"`` makes it in
+    the kernel that also forms ``x``, ``pos``, ``y_acc`` and ``y_temp_rate`` (``cgnn_training_sample``): a
+    counter-based generator gives every (particle, time step) its four normals as a pure function of ``(noise_seed,
+    noise_draw, particle id, step)``.  The noise then has the reference's distribution and the reference's arithmetic
+    downstream of the normals, NOT its random stream: seeded comparisons against the reference stay on
+    ``"reference"``.  The same ``(noise_seed, noise_draw)`` gives the same sample, so a training loop must pass a new
+    ``noise_draw`` for every sample (``step * batch_size + i``); ``noise_seed=None`` means ``torch.initial_seed()``.
+    The device path draws nothing on the CPU, leaves torch's global generator where it was, copies nothing from the
+    host when the inputs live on the device, and does NOT add the noise into the caller's target tensors (the
+    reference's in-place ``+=`` on them is a side effect of its host code, kept only on the ``"reference"`` path)."""
+    if noise_rng not in ("reference", "device"):
+        raise ValueError(f"noise_rng must be 'reference' or 'device', got {noise_rng!r}")
     dt = float(dt)
     box_size = float(box_size)
     if device is None:
         device = position_seq.device if position_seq.is_cuda else _default_device()
     device = torch.device(device)
+
+    if noise_rng == "device":
+        return _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature,
+                                        noise_std, int(num_neighbors), dt, box_size, device, check_bounds, noise_seed,
+                                        noise_draw)
 
     pos_seq = position_seq.float().permute(1, 0, 2)                       # [N, W, 3]
     tmp_seq = temperature_seq.float()
@@ -194,17 +216,55 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
         temp_rate = (tt - recent_temperature) / dt
         temp_rate = (temp_rate - _meta(metadata, "temp_rate_mean", device)) / _meta(metadata, "temp_rate_std", device)
 
+    return _graph(node_features.float(), edge_index, edge_attr, acceleration.float() if acceleration is not None else None,
+                  temp_rate.float() if temp_rate is not None else None, recent_position, order, dt, box_size,
+                  int(num_neighbors), device)
+
+
+def _graph(x, edge_index, edge_attr, y_acc, y_temp_rate, recent_position, order, dt: float, box_size: float, k: int,
+           device) -> Data:
     graph = Data(
-        x=node_features.float(),
+        x=x,
         edge_index=edge_index,
         edge_attr=edge_attr,
-        y_acc=acceleration.float() if acceleration is not None else None,
-        y_temp_rate=temp_rate.float() if temp_rate is not None else None,
+        y_acc=y_acc,
+        y_temp_rate=y_temp_rate,
         pos=recent_position,
         dt=torch.full((1,), dt, dtype=torch.float32, device=device),            # (a fill kernel: torch.tensor([dt],
         box_size=torch.full((1,), box_size, dtype=torch.float32, device=device),  # device=...) would synchronise)
     )
-    graph._cgnn_fixed_k = int(num_neighbors)
+    graph._cgnn_fixed_k = k
     graph._cgnn_fixed_k_for = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape))
     graph._cgnn_order = order          # spatial (cell-sorted) particle order: a locality hint for the engine
     return graph
+
+
+def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature, noise_std,
+                             k: int, dt: float, box_size: float, device, check_bounds: bool, noise_seed, noise_draw):
+    """``preprocess(noise_rng="device")``: one launch for noise, features, last frame and targets, then the k-NN."""
+    n = position_seq.shape[1]
+    pos_w = position_seq.to(device)                                       # [W, N, 3], as the kernel reads it
+    tmp_w = temperature_seq.to(device)
+    if tmp_w.dim() == 3 and tmp_w.shape[0] == n and tmp_w.shape[1] == pos_w.shape[0]:
+        tmp_w = tmp_w.permute(1, 0, 2)                                    # [N, W, 1] -> [W, N, 1]
+    want = ["x", "recent_pos"]
+    if target_position is not None:
+        if target_position.numel() != n * 3:
+            raise CgnnError(f"preprocess: target_position {tuple(target_position.shape)} does not hold [N, 3]")
+        target_position = target_position.to(device).reshape(n, 3)       # [N, 3] or [1, N, 3]
+        want.append("y_acc")
+    if target_temperature is not None:
+        if target_temperature.numel() != n:
+            raise CgnnError(f"preprocess: target_temperature {tuple(target_temperature.shape)} does not hold N values")
+        target_temperature = target_temperature.to(device).reshape(n)    # [N], [N, 1] or [1, N, 1]
+        want.append("y_temp_rate")
+    seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
+    s = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, float(noise_std), seed % 2 ** 64, noise_draw,
+                            target_position, target_temperature, None, want)
+    recent_position = s["recent_pos"]
+    edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, k, want_order=True)
+    if check_bounds:    # reference :158-159 (a host round trip)
+        assert int(senders.max()) < n, f"Max sender index {int(senders.max())} >= {n}"
+    y_tr = s.get("y_temp_rate")
+    return _graph(s["x"], edge_index, edge_attr, s.get("y_acc"), y_tr.reshape(n, 1) if y_tr is not None else None,
+                  recent_position, order, dt, box_size, k, device)

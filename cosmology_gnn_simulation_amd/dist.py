@@ -83,6 +83,8 @@ class Shard:
     x_feat: Optional[torch.Tensor] = None      # [n_owned, F] encoder inputs of the owned particles
     knn_ms: float = 0.0
     n_interior: int = 0               # owned rows [0, n_interior) have only owned senders (no halo needed)
+    y_acc: Optional[torch.Tensor] = None       # [n_owned, 3] training targets of the owned particles
+    y_temp_rate: Optional[torch.Tensor] = None  # [n_owned, 1]   (sharded_training_sample)
 
     @property
     def n_local(self) -> int:
@@ -256,6 +258,43 @@ def exchange_requests(sh: Shard, group=None) -> Shard:
     _collective(dist.all_to_all_single, recv, sh.ghost_global.contiguous(), output_split_sizes=counts_in,
                 input_split_sizes=sh.recv_counts, group=group)()
     return finish_shard(sh, list(torch.split(recv, counts_in)))
+
+
+def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.Tensor, metadata: dict,
+                            target_position: torch.Tensor, target_temperature: torch.Tensor, noise_std: float,
+                            num_neighbors: int, dt: float, box_size: float, world: int, rank: int, noise_seed: int,
+                            noise_draw: int = 0, device=None) -> Shard:
+    """Rank ``rank``'s part of the training sample ``data_utils.preprocess(..., noise_rng="device")`` makes on one GPU,
+    with the same bits: the window ``[W, N, 3]`` / ``[W, N(, 1)]`` and the next frame ``[N, 3]`` / ``[N(, 1)]`` (or
+    ``[1, N, ...]``) of ALL particles go in, every rank passing the same data, ``noise_seed`` and ``noise_draw``.
+
+    The device noise is a function of (seed, draw, particle id, step), so every rank first makes the noisy wrapped last
+    frame of all N particles (identical bits everywhere: ``owner_of`` agrees without communication) and builds its
+    shard on it, then makes ``x``, ``y_acc`` and ``y_temp_rate`` for the rows it owns only.  Returns the shard as
+    :func:`build_shard` does, with ``x_feat``, ``y_acc [n_owned, 3]`` and ``y_temp_rate [n_owned, 1]`` set (local row
+    order, ``owned_global``); :func:`exchange_requests` / :func:`finish_shard` remain the caller's next call."""
+    if device is None:
+        if not position_seq.is_cuda:
+            raise CgnnError("sharded_training_sample: pass device= or device-resident windows")
+        device = position_seq.device
+    device = torch.device(device)
+    dt, box_size = float(dt), float(box_size)
+    n = position_seq.shape[1]
+    pos_w = position_seq.to(device).float().contiguous()
+    tmp_w = temperature_seq.to(device).float().contiguous()
+    if target_position.numel() != n * 3 or target_temperature.numel() != n:
+        raise CgnnError(f"sharded_training_sample: targets {tuple(target_position.shape)} / "
+                        f"{tuple(target_temperature.shape)} do not hold [N, 3] / [N] for N = {n}")
+    tgt_p = target_position.to(device).float().reshape(n, 3)
+    tgt_t = target_temperature.to(device).float().reshape(n)
+    stats = ops.integration_stats(metadata)
+    recent = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw,
+                                 want=("recent_pos",), stats=stats)["recent_pos"]
+    sh = build_shard(recent, box_size, int(num_neighbors), world, rank)
+    own = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw, tgt_p, tgt_t,
+                              rows=sh.owned_global, want=("x", "y_acc", "y_temp_rate"), stats=stats)
+    sh.x_feat, sh.y_acc, sh.y_temp_rate = own["x"], own["y_acc"], own["y_temp_rate"].reshape(-1, 1)
+    return sh
 
 
 # ----------------------------------------------------------------------------

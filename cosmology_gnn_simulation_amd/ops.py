@@ -683,6 +683,74 @@ def integration_stats(metadata: dict) -> "C.Array":
     return (C.c_float * 8)(*out)
 
 
+TRAINING_SAMPLE_OUTPUTS = ("x", "recent_pos", "y_acc", "y_temp_rate", "pos_noise", "temp_noise")
+
+
+def training_sample(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,
+                    noise_std: float, seed: int, draw: int = 0, target_pos: Optional[torch.Tensor] = None,
+                    target_temp: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None,
+                    want: Sequence[str] = ("x", "recent_pos", "y_acc", "y_temp_rate"), stats=None) -> dict:
+    """A training sample of a ``[W, N, 3]`` / ``[W, N(, 1)]`` window in one launch (``cgnn_training_sample``): the
+    reference's random-walk noise made on the device from ``(seed, draw, particle id, step)``, the node features and
+    wrapped last frame of the noisy window, and the normalised targets from ``target_pos [N, 3]`` / ``target_temp
+    [N(, 1)]`` (the frame after the window).  ``rows`` (int64 ids) selects particles; row i of every output is then
+    particle ``rows[i]``, with the bits the all-rows call gives that particle.  ``want`` names the outputs to make
+    (:data:`TRAINING_SAMPLE_OUTPUTS`); the result is a dict of them: ``x [R, 4W-3]``, ``recent_pos [R, 3]``, ``y_acc
+    [R, 3]``, ``y_temp_rate [R]``, ``pos_noise [R, W, 3]``, ``temp_noise [R, W]``.  The same ``(seed, draw)`` gives the
+    same sample.  Nothing is read back from the device."""
+    what = "training_sample"
+    unknown = [name for name in want if name not in TRAINING_SAMPLE_OUTPUTS]
+    if unknown:
+        raise CgnnError(f"{what}: unknown outputs {unknown}; known: {TRAINING_SAMPLE_OUTPUTS}")
+    seed, draw = int(seed), int(draw)
+    if not (0 <= seed < 2 ** 64 and 0 <= draw < 2 ** 64):
+        raise CgnnError(f"{what}: seed and draw must fit 64 unsigned bits, got {seed}, {draw}")
+    pos_seq = f32c(pos_seq, "position window")
+    temp_seq = f32c(temp_seq, "temperature window")
+    if pos_seq.dim() != 3:
+        raise CgnnError(f"{what}: expected a [W, N, 3] window, got {tuple(pos_seq.shape)}")
+    w, n = pos_seq.shape[0], pos_seq.shape[1]
+    if pos_seq.shape != (w, n, 3) or temp_seq.numel() != w * n:
+        raise CgnnError(f"{what}: expected [W, N, 3] and [W, N(, 1)], got {tuple(pos_seq.shape)} / "
+                        f"{tuple(temp_seq.shape)}")
+    if "y_acc" in want:
+        if target_pos is None:
+            raise CgnnError(f"{what}: y_acc needs target_pos")
+        target_pos = f32c(target_pos, "target positions")
+        if target_pos.shape != (n, 3):
+            raise CgnnError(f"{what}: target_pos must be [N, 3], got {tuple(target_pos.shape)}")
+    else:
+        target_pos = None
+    if "y_temp_rate" in want:
+        if target_temp is None:
+            raise CgnnError(f"{what}: y_temp_rate needs target_temp")
+        target_temp = f32c(target_temp, "target temperatures")
+        if target_temp.numel() != n:
+            raise CgnnError(f"{what}: target_temp must hold N values, got {tuple(target_temp.shape)}")
+    else:
+        target_temp = None
+    if rows is not None:
+        rows = _i64c(rows, "rows").reshape(-1)
+    nr = n if rows is None else rows.numel()
+    if stats is None:
+        stats = integration_stats(metadata)
+    dev = pos_seq.device
+    shapes = {"x": (nr, 4 * w - 3), "recent_pos": (nr, 3), "y_acc": (nr, 3), "y_temp_rate": (nr,),
+              "pos_noise": (nr, w, 3), "temp_noise": (nr, w)}
+    out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in want}
+    _same_device(pos_seq, temp_seq, target_pos, target_temp, rows)
+    if nr == 0:
+        return out
+    with _timed(what, dev):
+        check(_lib.load().cgnn_training_sample(
+            pos_seq.data_ptr(), temp_seq.data_ptr(), ptr(target_pos), ptr(target_temp), w, n, ptr(rows), nr,
+            float(noise_std), seed, draw, float(box_size), float(dt), _scalar_stat(metadata, "vel_mean", what),
+            _scalar_stat(metadata, "vel_std", what), _scalar_stat(metadata, "temp_mean", what),
+            _scalar_stat(metadata, "temp_std", what), stats, *(ptr(out.get(name)) for name in TRAINING_SAMPLE_OUTPUTS),
+            stream_ptr(dev)), "cgnn_training_sample")
+    return out
+
+
 def rollout_integrate(acc_pred: torch.Tensor, temp_rate_pred: torch.Tensor, pos_prev2: torch.Tensor,
                       pos_prev1: torch.Tensor, temp_prev1: torch.Tensor, ids: torch.Tensor, metadata: dict,
                       n_out: Optional[int] = None, stats=None) -> torch.Tensor:

@@ -472,6 +472,37 @@ int cgnn_window_features_rows(const float* pos_seq, const float* temp_seq, int32
                               float vel_std, float temp_mean, float temp_std, float* x, float* recent_pos,
                               void* stream);
 
+/* ---- window (+ next frame) -> training sample with on-device noise (reference data_utils.py:36-70, :91-145, :166-214) --
+ * One launch, one thread per output row.  Row i is particle g = rows[i] (int64 ids; ids outside [0, n_total) are
+ * skipped), or g = i when rows is NULL (then n_rows must equal n_total).  pos_seq [W, n_total, 3], temp_seq
+ * [W, n_total]; target_pos [n_total, 3] / target_temp [n_total] (the frame after the window) are needed only for
+ * y_acc / y_temp_rate.  Every output may be NULL:
+ *   x [n_rows, 4W-3], recent_pos [n_rows, 3]   as cgnn_window_features forms them (the same device function)
+ *   y_acc [n_rows, 3]      ((wrap(tp - recent_pos) / dt - vel[W-2]) / dt - acc_mean) / acc_std,  tp = target_pos + pos_noise[W-1]
+ *   y_temp_rate [n_rows]   (((target_temp + temp_noise[W-1]) - (temp[W-1] + temp_noise[W-1])) / dt - tr_mean) / tr_std
+ *   pos_noise [n_rows, W, 3], temp_noise [n_rows, W]   the noise itself
+ * float32, one rounding per operation, true divisions, no contraction, in the order of the reference's expressions.
+ *
+ * Noise (S = W - 1 steps): for particle g and step t in [0, S) one Philox4x32-10 block with counter
+ * (g, t, draw & 0xffffffff, draw >> 32) and key (seed & 0xffffffff, seed >> 32); each word w gives
+ * u = ((w >> 9) + 0.5) * 2^-23; Box-Muller on (u0, u1) gives z_x = r cos(2 pi u1), z_y = r sin(2 pi u1) with
+ * r = sqrt(-2 log u0), and on (u2, u3) likewise z_z and z_T (logf, sincospif, sqrtf: the accurate functions).  The walk
+ * is the reference's: step = z * float32(noise_std / sqrt(S)) for positions and z_T * ((float32(noise_std) *
+ * tr_std) / float32(sqrt(S))) for the temperature; rate noise = running sum of the steps; noise at frame t + 1 =
+ * running sum of the rate noise, times dt; frame 0 gets 0.  Both running sums are kept in float64 and every element
+ * is rounded to float32, as torch's CPU cumsum does.  noise_std == 0: no RNG work, nothing is added.
+ * The sample is a pure function of (seed, draw, g, t): any subset of rows, on any rank, gets the same bits.
+ *
+ * stats (HOST memory, 8 floats, as cgnn_rollout_integrate takes them): acc_std[3], acc_mean[3], temp_rate_std,
+ * temp_rate_mean; may be NULL when noise_std == 0 and no target is asked for.  Invalid (nothing is launched):
+ * window < 2, n_total >= 2^31, rows == NULL with n_rows != n_total, dt == 0, a zero std, box_size <= 0, a target
+ * output without its target frame. */
+int cgnn_training_sample(const float* pos_seq, const float* temp_seq, const float* target_pos, const float* target_temp,
+                         int32_t window, int64_t n_total, const int64_t* rows, int64_t n_rows, double noise_std,
+                         uint64_t seed, uint64_t draw, float box_size, float dt, float vel_mean, float vel_std,
+                         float temp_mean, float temp_std, const float* stats, float* x, float* recent_pos, float* y_acc,
+                         float* y_temp_rate, float* pos_noise, float* temp_noise, void* stream);
+
 /* ---- sharded rollout step (reference render_rollout.py:73-85; one_step_test.py:84-105) ----------------------
  * A packed frame row is CGNN_ROLLOUT_ROW floats: (x, y, z, temperature, int32 particle id bit-cast to float);
  * id -1 marks a padding row.

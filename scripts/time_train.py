@@ -24,6 +24,9 @@ ap.add_argument("--with-edge-stream", action="store_true",
                      "(SURVEY F1) but its step computes it -- the like-for-like step time")
 ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"],
                 help="edge: train the Interaction Network that aggregates the edge updates (model.train_edge_messages)")
+ap.add_argument("--noise-std", type=float, default=0.0,
+                help="> 0: rebuild the training sample inside every timed step with noise made on the device "
+                     "(preprocess(noise_rng='device'), windows resident on the GPU, a new draw per step)")
 a = ap.parse_args()
 dev = "cuda"
 n, k, d, L = a.particles, a.neighbors, a.latent, a.mp_steps
@@ -43,9 +46,17 @@ if a.with_edge_stream:
     m.edge_precision, m.node_precision = "bf16", "fp16x2"      # bench.py's edge stream
 opt = torch.optim.Adam(m.parameters(), lr=1e-4)
 mse = torch.nn.functional.mse_loss
+if a.noise_std > 0:
+    c, e = c.to(dev), e.to(dev)
+draws = 0
 
 
 def step():
+    global g, draws
+    if a.noise_std > 0:
+        g = data_utils.preprocess(c[:5], e[:5], meta, c[5], e[5], a.noise_std, k, 0.01, 1.0, check_bounds=False,
+                                  noise_rng="device", noise_seed=1236, noise_draw=draws)
+        draws += 1
     pred = m(g)
     loss = (mse(pred["acceleration"], g.y_acc) + mse(pred["temp_rate"], g.y_temp_rate)
             + losses.momentum_conservation_loss(pred["acceleration"], g, 0.01, 0.1))
@@ -65,6 +76,8 @@ torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) / a.iters * 1e3
 what = ("message_source edge (both streams differentiated)" if a.message_source == "edge" else
         "edge stream forward included" if a.with_edge_stream else "edge stream skipped (F1)")
+if a.noise_std > 0:
+    what += f"; sample rebuilt in the step with device noise, noise_std {a.noise_std:g}"
 print(f"training step ({what}, {a.train_precision}): {ms:.2f} ms  "
       f"({n} particles, k={k}, latent {d}, hidden {hd}, {L} rounds; "
       f"{n * k * L / ms / 1e6:.3f} G edge-updates/s)", flush=True)
