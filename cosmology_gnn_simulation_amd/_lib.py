@@ -41,6 +41,7 @@ EXPORTS = (
     "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
     "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
     "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
+    "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
 )
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
 ROWS, TILED32 = 0, 1
@@ -119,6 +120,11 @@ def load() -> C.CDLL:
     lib.cgnn_frame_unpack.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.cgnn_training_sample.argtypes = [vp, vp, vp, vp, i32, i64, vp, i64, C.c_double, C.c_uint64, C.c_uint64, f32, f32,
                                          f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cgnn_balanced_planes_workspace_bytes.restype = sz
+    lib.cgnn_balanced_planes_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.cgnn_balanced_planes.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.cgnn_tile_classify.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.c_double, C.c_double, vp, vp, vp, vp]
     lib.cgnn_gather_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_scatter_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_halo_return_add.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, i64, vp]

@@ -51,9 +51,76 @@ def tile_grid(world: int) -> Tuple[int, int, int]:
     return tuple(sorted(dims, reverse=True))
 
 
-def owner_of(pos: torch.Tensor, box_size: float, world: int) -> torch.Tensor:
-    """Rank owning each particle: the tile of the periodic box that contains it."""
+DECOMPOSITIONS = ("uniform", "balanced")
+
+
+@dataclass
+class TilePlanes:
+    """The cutting planes of a ``"balanced"`` decomposition (:func:`balanced_planes`) and their tile grid: ``x [px-1]``,
+    ``y [px, py-1]`` (one row per x-slab), ``z [px, py, pz-1]`` (one row per (x, y) column), float32."""
+    grid: Tuple[int, int, int]
+    x: torch.Tensor
+    y: torch.Tensor
+    z: torch.Tensor
+
+    def tensors(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.x, self.y, self.z
+
+
+def _quantile_planes(v: torch.Tensor, p: int) -> torch.Tensor:
+    """``c_j = s[(j * m) // p]``, ``j = 1 .. p-1``, ``s`` = ``v`` sorted ascending (``m`` = its length); zeros (no plane)
+    for an empty segment.  ``-0`` counts as ``+0``."""
+    m = v.numel()
+    if m == 0 or p == 1:
+        return torch.zeros(p - 1, dtype=torch.float32, device=v.device)
+    s = torch.sort(v + 0.0).values
+    return s[[(j * m) // p for j in range(1, p)]]
+
+
+def _part_of(planes: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """``#{ j : c_j <= v }`` per element: ``planes [n, p-1]`` (each element's own planes) or ``[p-1]``."""
+    return (planes <= v.unsqueeze(1)).sum(dim=1)
+
+
+def balanced_planes(pos: torch.Tensor, box_size: float, world: int) -> TilePlanes:
+    """Planes that cut the ``tile_grid(world)`` tiles at particle-count quantiles, nested x -> y -> z: for a segment of
+    ``m`` particles and an axis with ``p`` parts the planes are ``c_j = s[(j * m) // p]`` (``s``: the segment's
+    coordinates sorted ascending), and a coordinate ``v`` lies in part ``#{ j : c_j <= v }``.  All particles are cut
+    into ``px`` slabs on x, every slab into ``py`` columns on y, every column into ``pz`` tiles on z.  A pure function
+    of the position bits: every rank derives the same planes without communication.  Device tensors go through
+    ``cgnn_balanced_planes`` (radix select); CPU tensors through this torch restatement (sort)."""
+    del box_size        # the planes are data driven; the box only closes the end parts (tile_bounds)
+    grid = px, py, pz = tile_grid(world)
+    if pos.is_cuda:
+        cx, cy, cz, _ = ops.balanced_planes(pos, grid)
+        return TilePlanes(grid, cx, cy, cz)
+    pos = pos.float()
+    cx = _quantile_planes(pos[:, 0], px)
+    ix = _part_of(cx, pos[:, 0])
+    cy = torch.zeros((px, py - 1), dtype=torch.float32)
+    cz = torch.zeros((px, py, pz - 1), dtype=torch.float32)
+    for i in range(px):
+        slab = torch.nonzero(ix == i).squeeze(1)
+        cy[i] = _quantile_planes(pos[slab, 1], py)
+        iy = _part_of(cy[i], pos[slab, 1])
+        for j in range(py):
+            cz[i, j] = _quantile_planes(pos[slab[iy == j], 2], pz)
+    return TilePlanes(grid, cx, cy, cz)
+
+
+def owner_of(pos: torch.Tensor, box_size: float, world: int, planes: Optional[TilePlanes] = None) -> torch.Tensor:
+    """Rank owning each particle: the tile of the periodic box that contains it (equal-volume tiles, or the tiles of
+    ``planes``)."""
     px, py, pz = tile_grid(world)
+    if planes is not None:
+        if tuple(planes.grid) != (px, py, pz):
+            raise CgnnError(f"owner_of: planes of a {planes.grid} tile grid for a world of {world}")
+        if pos.is_cuda:
+            return ops.tile_classify(pos, planes.tensors(), want_counts=False)[0]
+        ix = _part_of(planes.x, pos[:, 0])
+        iy = _part_of(planes.y[ix], pos[:, 1])
+        iz = _part_of(planes.z[ix, iy], pos[:, 2])
+        return ((ix * py + iy) * pz + iz).to(torch.int32)
     g = torch.tensor([px, py, pz], device=pos.device, dtype=torch.float32)
     cell = torch.floor(pos / box_size * g).to(torch.int64)
     cell = torch.minimum(cell.clamp_min_(0), (g - 1).to(torch.int64))
@@ -91,10 +158,22 @@ class Shard:
         return self.n_owned + self.n_ghost
 
 
-def tile_bounds(box_size: float, world: int, rank: int):
-    """``(lo [3], hi [3])`` of rank ``rank``'s tile (the inverse of :func:`owner_of`)."""
+def tile_bounds(box_size: float, world: int, rank: int, planes: Optional[TilePlanes] = None):
+    """``(lo [3], hi [3])`` of rank ``rank``'s tile (the inverse of :func:`owner_of`).  With ``planes``: part ``j`` of a
+    segment spans ``[c_j, c_{j+1})``, ``c_0 = 0`` and ``c_p = box_size`` (reads the rank's planes back from the device)."""
     px, py, pz = tile_grid(world)
     ix, iy, iz = rank // (py * pz), (rank // pz) % py, rank % pz
+    if planes is not None:
+        if tuple(planes.grid) != (px, py, pz):
+            raise CgnnError(f"tile_bounds: planes of a {planes.grid} tile grid for a world of {world}")
+        cuts = torch.cat([planes.x, planes.y[ix], planes.z[ix, iy]]).tolist()       # one read-back
+        lo, hi, off = [], [], 0
+        for i, p in ((ix, px), (iy, py), (iz, pz)):
+            c = [0.0] + cuts[off:off + p - 1] + [float(box_size)]
+            lo.append(c[i])
+            hi.append(c[i + 1])
+            off += p - 1
+        return lo, hi
     lo = [ix * box_size / px, iy * box_size / py, iz * box_size / pz]
     hi = [(ix + 1) * box_size / px, (iy + 1) * box_size / py, (iz + 1) * box_size / pz]
     return lo, hi
@@ -115,7 +194,8 @@ def _near_tile(pos: torch.Tensor, box_size: float, lo, hi, margin: float) -> tor
 
 
 def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, rank: int,
-                knn_fn: Optional[Callable] = None, margin_factor: float = 2.0) -> Shard:
+                knn_fn: Optional[Callable] = None, margin_factor: float = 2.0,
+                decomposition: str = "uniform") -> Shard:
     """Everything rank ``rank`` can derive locally from the global positions: its owned set, their k-NN
     senders, the ghost set and the global->local renumbering.  ``knn_fn(pos, box, k, query_ids)`` defaults to
     the HIP k-NN; it returns ``(senders int32 [nq*k], edge_attr [nq*k, 4], order)``.
@@ -123,10 +203,21 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
     The neighbour search runs over the rank's tile plus a margin, not over the whole box ("graph
     build"): margin = ``margin_factor`` x the radius that holds k particles at mean density.  It is then CHECKED --
     every owned particle's k-th neighbour must be closer than the margin, or some neighbour outside the subset could
-    have been missed -- and doubled until the check holds (clustered inputs), so the result is the global one."""
+    have been missed -- and doubled until the check holds (clustered inputs), so the result is the global one.
+
+    ``decomposition``: ``"uniform"`` cuts tiles of equal volume; ``"balanced"`` cuts them at particle-count quantiles
+    (:func:`balanced_planes`, kept as ``shard._planes``), so that every rank owns about ``N / world`` particles however
+    clustered they are.  The tile is an axis-aligned box that holds every owned particle either way, so the search and
+    its check are the same; only who owns a particle changes, never a result."""
+    if decomposition not in DECOMPOSITIONS:
+        raise ValueError(f"build_shard: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
     dev = pos_global.device
     n_total = pos_global.shape[0]
-    owner = owner_of(pos_global, box_size, world)
+    planes = balanced_planes(pos_global, box_size, world) if decomposition == "balanced" else None
+    classify = planes is not None and dev.type == "cuda"       # owner, counts and the margin mask in one HIP pass
+    counts = None
+    if not classify:
+        owner = owner_of(pos_global, box_size, world, planes)
     knn = knn_fn or (lambda p, b, kk, q: ops.knn_periodic(p, b, kk, query_ids=q, want_edge_attr=True,
                                                           want_order=True))
     t0 = time.perf_counter()
@@ -144,12 +235,23 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
         search_ms += e0.elapsed_time(e1)
         return out
 
-    lo, hi = tile_bounds(box_size, world, rank)
+    lo, hi = tile_bounds(box_size, world, rank, planes)
     margin = margin_factor * box_size * (3.0 * k / (4.0 * 3.141592653589793 * max(n_total, 1))) ** (1.0 / 3.0)
+    searches = 0
     while True:
-        near = _near_tile(pos_global, box_size, lo, hi, margin) if world > 1 else None
-        if near is not None:
-            near |= owner == rank      # owner_of clamps coordinates outside [0, box) into edge tiles: owned is always searched
+        searches += 1
+        if classify:        # near = within the margin of the tile, or owned (as below), from cgnn_tile_classify
+            first = counts is None
+            own_, counts_, near = ops.tile_classify(pos_global, planes.tensors(), rank, lo, hi, margin, box_size,
+                                                    want_owner=first, want_counts=first)
+            if first:
+                owner, counts = own_, counts_
+            if world == 1:
+                near = None
+        else:
+            near = _near_tile(pos_global, box_size, lo, hi, margin) if world > 1 else None
+            if near is not None:
+                near |= owner == rank      # owner_of clamps coordinates outside [0, box) into edge tiles: owned is always searched
         whole = near is None or bool(near.all())
         sub = None if whole else torch.nonzero(near).squeeze(1)        # ascending global ids: ties order as globally
         pos_sub = pos_global if whole else pos_global[sub].contiguous()
@@ -162,7 +264,11 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
             if order is not None:
                 order = order.long()
                 owned_s = order[own_sub[order] == rank]
-        senders_s, edge_attr, _ = timed_knn(pos_sub, box_size, k, owned_s.to(torch.int32))
+        if owned_s.numel():
+            senders_s, edge_attr, _ = timed_knn(pos_sub, box_size, k, owned_s.to(torch.int32))
+        else:           # an empty tile (balanced tiles of coincident coordinates): no query, nothing to search
+            senders_s = torch.empty(0, dtype=torch.int32, device=dev)
+            edge_attr = torch.empty((0, 4), dtype=torch.float32, device=dev)
         if whole or owned_s.numel() == 0:
             break
         # k-th neighbour distance (minimum image) of every owned particle against the margin
@@ -207,7 +313,11 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
                recv_counts, want_global=want, knn_ms=knn_ms, n_interior=n_interior)
     sh._g2l = g2l
     sh._owner = owner            # every particle's rank (the sharded rollout sizes its send blocks from it)
+    sh._planes = planes          # the balanced decomposition's cutting planes (None: equal-volume tiles)
+    sh._counts = counts          # int64 [world] on the device (cgnn_tile_classify), or None: bincount of _owner
     sh.subset_build_ms = build_ms
+    sh.searches = searches       # 1: the first margin held; every further one doubled it
+    sh.subset_rows = pos_sub.shape[0]
     return sh
 
 
@@ -263,7 +373,7 @@ def exchange_requests(sh: Shard, group=None) -> Shard:
 def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.Tensor, metadata: dict,
                             target_position: torch.Tensor, target_temperature: torch.Tensor, noise_std: float,
                             num_neighbors: int, dt: float, box_size: float, world: int, rank: int, noise_seed: int,
-                            noise_draw: int = 0, device=None) -> Shard:
+                            noise_draw: int = 0, device=None, decomposition: str = "uniform") -> Shard:
     """Rank ``rank``'s part of the training sample ``data_utils.preprocess(..., noise_rng="device")`` makes on one GPU,
     with the same bits: the window ``[W, N, 3]`` / ``[W, N(, 1)]`` and the next frame ``[N, 3]`` / ``[N(, 1)]`` (or
     ``[1, N, ...]``) of ALL particles go in, every rank passing the same data, ``noise_seed`` and ``noise_draw``.
@@ -272,7 +382,9 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     frame of all N particles (identical bits everywhere: ``owner_of`` agrees without communication) and builds its
     shard on it, then makes ``x``, ``y_acc`` and ``y_temp_rate`` for the rows it owns only.  Returns the shard as
     :func:`build_shard` does, with ``x_feat``, ``y_acc [n_owned, 3]`` and ``y_temp_rate [n_owned, 1]`` set (local row
-    order, ``owned_global``); :func:`exchange_requests` / :func:`finish_shard` remain the caller's next call."""
+    order, ``owned_global``); :func:`exchange_requests` / :func:`finish_shard` remain the caller's next call.
+    ``decomposition``: as in :func:`build_shard` (the planes of ``"balanced"`` come from the noisy frame, the same on
+    every rank)."""
     if device is None:
         if not position_seq.is_cuda:
             raise CgnnError("sharded_training_sample: pass device= or device-resident windows")
@@ -290,7 +402,7 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     stats = ops.integration_stats(metadata)
     recent = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw,
                                  want=("recent_pos",), stats=stats)["recent_pos"]
-    sh = build_shard(recent, box_size, int(num_neighbors), world, rank)
+    sh = build_shard(recent, box_size, int(num_neighbors), world, rank, decomposition=decomposition)
     own = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw, tgt_p, tgt_t,
                               rows=sh.owned_global, want=("x", "y_acc", "y_temp_rate"), stats=stats)
     sh.x_feat, sh.y_acc, sh.y_temp_rate = own["x"], own["y_acc"], own["y_temp_rate"].reshape(-1, 1)
@@ -400,7 +512,10 @@ def _exchange_rounds(halo, n_rounds: int, table_of: Callable, nodes: Callable, o
 class ShardedForward:
     """``EncodeProcessDecode.forward`` over one spatial tile.  ``halo(table)`` must fill the ghost rows of
     ``table`` ([n_owned + n_ghost, D]) from their owners; by default it is the RCCL all-to-all above.
-    Returns the predictions of the owned particles (local order; ``shard.owned_global`` maps them back)."""
+    Returns the predictions of the owned particles (local order; ``shard.owned_global`` maps them back).
+
+    A rank that owns nothing (a balanced tile between coincident planes) has no receivers, hence no edges and no
+    ghosts: it launches nothing, takes part in every exchange with empty blocks and returns empty predictions."""
 
     def __init__(self, model, shard: Shard, halo: Optional[Callable] = None):
         self.model, self.sh = model, shard
@@ -432,6 +547,11 @@ class ShardedForward:
         m, sh = self.model, self.sh
         P = self.P = m._pack(sh.x_feat.shape[1], sh.edge_attr.shape[1])
         D = m._latent_size
+        self.empty = sh.n_owned == 0
+        if self.empty:
+            self.fused, self._edges_pending, self.el = False, False, None
+            self.x_all = torch.empty((0, D), dtype=torch.float32, device=sh.x_feat.device)
+            return
         H = P["rounds"][0].ws.out_dim if P["rounds"] else D
         # the same plan as on one GPU: under the reference data flow (x_j) the node stream runs round by round with its
         # halo exchanges and leaves every round's Ps / Pd behind; the edge stream then is one launch
@@ -445,6 +565,8 @@ class ShardedForward:
         self.e_upd = self.el.empty_like() if m.message_source == "edge" else None
 
     def round(self, i: int):
+        if self.empty:
+            return
         if self.fused:
             return self._round_nodes(i)
         sh, rounds = self.sh, self.P["rounds"]
@@ -481,6 +603,8 @@ class ShardedForward:
         senders are all owned: needs no ghost row, runs under the halo exchange), ``"boundary"`` (the rest, after the
         exchange; also projects the ghost rows) or ``"all"``.  Reads ``x_all``, writes ``x_alt``; the tables swap
         when the round is complete."""
+        if self.empty:
+            return
         sh = self.sh
         rounds = self.P["rounds"]
         p, fmt = rounds[i], self.plan.p_format
@@ -507,6 +631,10 @@ class ShardedForward:
 
     def decode(self) -> dict:
         self.finish_edges()
+        if self.empty:
+            dev = self.x_all.device
+            return {"acceleration": torch.empty((0, self.P["dec_acc"].out_dim), dtype=torch.float32, device=dev),
+                    "temp_rate": torch.empty((0, 1), dtype=torch.float32, device=dev)}
         x_own = self.x_all[:self.sh.n_owned]
         return {"acceleration": ops.mlp_rows(self.P["dec_acc"], x_own),
                 "temp_rate": ops.mlp_rows(self.P["dec_tr"], x_own)}
@@ -1104,11 +1232,16 @@ class ShardedRollout:
     4. :meth:`integrate`: ``cgnn_rollout_integrate`` -> the send block ``[cap, ROLLOUT_ROW]`` (padding id -1);
     5. :meth:`publish`: the gathered ``[world * cap, ROLLOUT_ROW]`` rows -> frame ``t`` (``cgnn_frame_unpack``).
 
-    Buffers that depend on the owned count are made per step."""
+    Buffers that depend on the owned count are made per step.  ``decomposition``: as in :func:`build_shard`; with
+    ``"balanced"`` the planes follow the particles from step to step and ``cap`` stays near ``N / world``."""
 
     def __init__(self, model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int = 6,
-                 num_neighbors: int = 16, num_steps: Optional[int] = None, device=None, world: int = 1, rank: int = 0):
+                 num_neighbors: int = 16, num_steps: Optional[int] = None, device=None, world: int = 1, rank: int = 0,
+                 decomposition: str = "uniform"):
         coords, energy, total = rollout_arguments(data, window_size, num_neighbors, num_steps)
+        if decomposition not in DECOMPOSITIONS:
+            raise ValueError(f"sharded rollout: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
+        self.decomposition = decomposition
         if not 0 <= rank < world:
             raise ValueError(f"sharded rollout: rank {rank} outside a world of {world}")
         if device is None:
@@ -1135,8 +1268,12 @@ class ShardedRollout:
         if not bool(torch.isfinite(recent).all()):        # the neighbour search must never see a NaN position
             raise CgnnError(f"sharded rollout: frame {t - 1} holds non-finite positions (rows that were never published, "
                             f"or a diverged model)")
-        sh = build_shard(recent, self.box, self.k, self.world, self.rank)
-        self.counts, self.cap = rollout_capacity(sh._owner, self.world)
+        sh = build_shard(recent, self.box, self.k, self.world, self.rank, decomposition=self.decomposition)
+        if sh._counts is not None:      # the balanced plan on the device: cgnn_tile_classify counted every rank's rows
+            self.counts = sh._counts.tolist()
+            self.cap = max(self.counts)
+        else:
+            self.counts, self.cap = rollout_capacity(sh._owner, self.world)
         if self.counts[self.rank] != sh.n_owned:
             raise CgnnError(f"rank {self.rank}: {sh.n_owned} owned particles, the owner map says {self.counts[self.rank]}")
         return sh
@@ -1150,6 +1287,10 @@ class ShardedRollout:
         return ShardedForward(self.model, sh, halo)
 
     def integrate(self, sh: Shard, pred: dict, t: int) -> torch.Tensor:
+        if sh.n_owned == 0:        # an empty rank sends padding rows only
+            block = torch.zeros((self.cap, _lib.ROLLOUT_ROW), dtype=torch.float32, device=self.device)
+            block.view(torch.int32)[:, _lib.ROLLOUT_ROW - 1] = -1
+            return block
         return ops.rollout_integrate(pred["acceleration"], pred["temp_rate"], self.pos[t - 2], self.pos[t - 1],
                                      self.tmp[t - 1], sh.owned_global, self.meta, n_out=self.cap, stats=self.stats)
 
@@ -1162,10 +1303,11 @@ class ShardedRollout:
 
 def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: float, box_size: float,
                     window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None, device=None,
-                    group=None) -> dict:
+                    group=None, decomposition: str = "uniform") -> dict:
     """``rollout.rollout`` over the ranks of ``group`` (a world of one when no process group is up): same arguments,
     return value and frame count, and the same bits.  Every rank passes the same ``data`` (checked once, by one
     all-reduce of a checksum) and returns the whole trajectory.  ``noise_std`` is ignored, as there.
+    ``decomposition``: as in :func:`build_shard`; it changes who computes a row, never the row.
 
     Per step: the shard of the wrapped last frame, the ghost-id all-to-all, the forward with one halo all-to-all per
     round, the integration of the owned particles and one all-gather of the packed rows into the next frame."""
@@ -1183,7 +1325,7 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
             energy = data["InternalEnergy"]
             check_same_data(data["Coordinates"][:window_size], energy[:window_size], device, group)
         runner = ShardedRollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps, device,
-                                world, rank)
+                                world, rank, decomposition)
         for t in range(window_size, runner.total_time):
             sh = runner.plan(t)
             if distributed:
@@ -1204,7 +1346,7 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
 # ----------------------------------------------------------------------------
 
 def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int, seed: int, device, metadata: dict,
-                          group=None) -> Shard:
+                          group=None, decomposition: str = "uniform") -> Shard:
     n_total = particles_per_gpu * world
     # the box of synthetic.make_snapshot(n_total, seed), bit for bit, but only one global frame (positions: ownership and the
     # neighbour search need all of them) and the feature window of the OWNED particles are built and uploaded: per rank the
@@ -1213,7 +1355,7 @@ def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int,
     box, dt = metadata["box_size"], metadata["dt"]
     W = 5
     pos = torch.remainder(snap.frame(W - 1).to(device), box).contiguous()     # the window's last frame
-    sh = build_shard(pos, box, k, world, rank)
+    sh = build_shard(pos, box, k, world, rank, decomposition=decomposition)
     sh = exchange_requests(sh, group)
     coords, energy = snap.window_of(sh.owned_global)
     # node features of the owned particles: the same kernel data_utils.preprocess uses

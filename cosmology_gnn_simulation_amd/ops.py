@@ -751,6 +751,65 @@ def training_sample(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dic
     return out
 
 
+def _pos3(pos: torch.Tensor, what: str) -> torch.Tensor:
+    pos = f32c(pos, "pos")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise CgnnError(f"{what}: pos must be [n, 3], got {tuple(pos.shape)}")
+    return pos
+
+
+def balanced_planes(pos: torch.Tensor, grid: Sequence[int], want_owner: bool = False):
+    """The cutting planes of the balanced decomposition of ``pos [N, 3]`` into the tile grid ``(px, py, pz)``
+    (``cgnn_balanced_planes``: exact radix select on the device, nothing read back): ``(planes_x [px-1], planes_y [px,
+    py-1], planes_z [px, py, pz-1], owner int32 [N] | None)``."""
+    lib = _lib.load()
+    pos = _pos3(pos, "balanced_planes")
+    px, py, pz = (int(g) for g in grid)
+    n, dev = pos.shape[0], pos.device
+    ws_bytes = lib.cgnn_balanced_planes_workspace_bytes(n, px, py, pz)
+    if ws_bytes == 0:
+        raise CgnnError(f"balanced_planes: no workspace for {n} particles on a tile grid of {(px, py, pz)}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    cx = torch.empty((px - 1,), dtype=torch.float32, device=dev)
+    cy = torch.empty((px, py - 1), dtype=torch.float32, device=dev)
+    cz = torch.empty((px, py, pz - 1), dtype=torch.float32, device=dev)
+    owner = torch.empty(n, dtype=torch.int32, device=dev) if want_owner else None
+    with _timed("balanced_planes", dev):
+        check(lib.cgnn_balanced_planes(pos.data_ptr(), n, px, py, pz, cx.data_ptr(), cy.data_ptr(), cz.data_ptr(),
+                                       ptr(owner), ws.data_ptr(), ws_bytes, stream_ptr(dev)), "cgnn_balanced_planes")
+    return cx, cy, cz, owner
+
+
+def tile_classify(pos: torch.Tensor, planes: Sequence[torch.Tensor], rank: Optional[int] = None, lo=None, hi=None,
+                  margin: float = 0.0, box_size: float = 0.0, want_owner: bool = True, want_counts: bool = True):
+    """One pass over ``pos [N, 3]`` given the planes ``(planes_x [px-1], planes_y [px, py-1], planes_z [px, py, pz-1])``
+    (``cgnn_tile_classify``): ``(owner int32 [N] | None, counts int64 [world] | None, mask bool [N] | None)``.  The mask
+    is made when ``rank`` is given: the particles ``rank`` owns or that lie within ``margin`` of its box ``[lo, hi)`` on
+    every axis (periodic), the bits of ``dist._near_tile(pos, box_size, lo, hi, margin) | (owner == rank)``."""
+    lib = _lib.load()
+    pos = _pos3(pos, "tile_classify")
+    cx, cy, cz = (f32c(c, "planes") for c in planes)
+    px, py, pz = cx.numel() + 1, cy.shape[-1] + 1, cz.shape[-1] + 1
+    if cy.shape != (px, py - 1) or cz.shape != (px, py, pz - 1):
+        raise CgnnError(f"tile_classify: planes of shapes {tuple(cx.shape)}, {tuple(cy.shape)}, {tuple(cz.shape)} are "
+                        f"not those of one tile grid")
+    n, dev = pos.shape[0], pos.device
+    _same_device(pos, cx, cy, cz)
+    owner = torch.empty(n, dtype=torch.int32, device=dev) if want_owner else None
+    counts = torch.empty(px * py * pz, dtype=torch.int64, device=dev) if want_counts else None
+    mask, lo_c, hi_c = None, None, None
+    if rank is not None:
+        if lo is None or hi is None or len(lo) != 3 or len(hi) != 3:
+            raise CgnnError("tile_classify: the mask needs the box lo [3], hi [3] of the rank")
+        mask = torch.empty(n, dtype=torch.bool, device=dev)
+        lo_c, hi_c = (C.c_double * 3)(*[float(v) for v in lo]), (C.c_double * 3)(*[float(v) for v in hi])
+    with _timed("tile_classify", dev):
+        check(lib.cgnn_tile_classify(pos.data_ptr(), n, px, py, pz, cx.data_ptr(), cy.data_ptr(), cz.data_ptr(),
+                                     -1 if rank is None else int(rank), lo_c, hi_c, float(margin), float(box_size),
+                                     ptr(owner), ptr(counts), ptr(mask), stream_ptr(dev)), "cgnn_tile_classify")
+    return owner, counts, mask
+
+
 def rollout_integrate(acc_pred: torch.Tensor, temp_rate_pred: torch.Tensor, pos_prev2: torch.Tensor,
                       pos_prev1: torch.Tensor, temp_prev1: torch.Tensor, ids: torch.Tensor, metadata: dict,
                       n_out: Optional[int] = None, stats=None) -> torch.Tensor:

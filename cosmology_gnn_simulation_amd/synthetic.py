@@ -41,6 +41,36 @@ def make_snapshot(num_particles: int, window: int = 5, box_size: float = 1.0, dt
                 BoxSize=torch.tensor(box_size), TimeStep=torch.tensor(dt))
 
 
+def make_clustered_positions(n: int, box_size: float = 1.0, seed: int = 0, blob_fraction: float = 0.5,
+                             blob_sigma: float = 0.05) -> torch.Tensor:
+    """A clustered frame ``[n, 3]``: ``int(blob_fraction * n)`` particles from an isotropic Gaussian of width
+    ``blob_sigma * box_size`` centred at ``(0.25, 0.25, 0.25) * box_size`` (one halo), wrapped into the box, the rest
+    uniform; then one fixed permutation, so that ids carry no spatial order.  Deterministic in ``seed``."""
+    g = torch.Generator().manual_seed(seed)
+    n_blob = int(blob_fraction * n)
+    blob = 0.25 * box_size + blob_sigma * box_size * torch.randn(n_blob, 3, generator=g, dtype=torch.float32)
+    rest = torch.rand(n - n_blob, 3, generator=g, dtype=torch.float32) * box_size
+    pos = torch.remainder(torch.cat([blob, rest]), box_size)
+    pos = torch.where(pos >= box_size, pos - box_size, pos)
+    return pos[torch.randperm(n, generator=g)].contiguous()
+
+
+def make_clustered_snapshot(num_particles: int, window: int = 5, box_size: float = 1.0, dt: float = 0.01,
+                            seed: int = 1234, blob_fraction: float = 0.5,
+                            blob_sigma: float = 0.05) -> Dict[str, torch.Tensor]:
+    """The window :func:`make_snapshot` builds, started from :func:`make_clustered_positions` instead of a uniform
+    frame."""
+    p0 = make_clustered_positions(num_particles, box_size, seed, blob_fraction, blob_sigma)
+    g = torch.Generator().manual_seed(seed + 1)
+    v = torch.randn(num_particles, 3, generator=g, dtype=torch.float32) * 0.05
+    t = torch.arange(window + 1, dtype=torch.float32).view(-1, 1, 1)
+    coords = torch.remainder(p0.unsqueeze(0) + v.unsqueeze(0) * (dt * t), box_size)
+    coords = torch.where(coords >= box_size, coords - box_size, coords)
+    energy = 1.0 + 0.1 * torch.randn(window + 1, num_particles, 1, generator=g, dtype=torch.float32).cumsum(dim=0)
+    return dict(Coordinates=coords, InternalEnergy=energy,
+                BoxSize=torch.tensor(box_size), TimeStep=torch.tensor(dt))
+
+
 class LazySnapshot:
     """The box of :func:`make_snapshot` (same seed -> the same numbers, bit for bit) without materialising the
     ``[W+1, N, 3]`` trajectories: the random draws are kept (they have to be made in full to keep the generator's

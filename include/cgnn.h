@@ -523,6 +523,36 @@ int cgnn_rollout_integrate(const float* pos_prev2, const float* pos_prev1, const
                            int64_t n_out, const float* stats, float dt, float box_size, float* out, void* stream);
 int cgnn_frame_unpack(const float* rows, int64_t n_rows, int64_t n_total, float* pos, float* temp, void* stream);
 
+/* ---- balanced spatial decomposition (multi-GPU tiles cut by particle count) ------------------------------------
+ * The tile grid (px, py, pz) is cut at particle-count quantiles, nested x -> y -> z.  For a segment of m particles and
+ * an axis with p parts, s = the segment's float32 coordinates on that axis sorted ascending (-0 counts as +0):
+ *   planes  c_j = s[(j * m) / p],  j = 1 .. p-1;      part of a coordinate v = #{ j : c_j <= v }
+ * level 1: all n particles on x (px parts); level 2: every x-slab on y; level 3: every (x, y) column on z;
+ * owner = (ix * py + iy) * pz + iz.  A segment without particles has no planes; 0 is stored for them.
+ *
+ * cgnn_balanced_planes: planes_x [px-1], planes_y [px, py-1], planes_z [px, py, pz-1] from pos [n, 3], by an exact
+ * radix select (three digits of 11 / 11 / 10 bits of the order-preserving uint32 image of the float; integer
+ * histograms, so the result is a pure function of the position bits).  owner int32 [n] may be NULL.  A planes
+ * pointer may be NULL when its axis has one part.  workspace: device memory of
+ * cgnn_balanced_planes_workspace_bytes(n, px, py, pz) bytes (0: invalid arguments).  No host synchronisation.
+ * Invalid: n >= 2^31, a part count < 1, more than 4096 tiles.
+ *
+ * cgnn_tile_classify: one pass over pos given the planes.  Each output may be NULL:
+ *   owner  int32 [n]
+ *   counts int64 [px * py * pz]: particles per tile (zeroed by the call)
+ *   mask   uint8 [n]: 1 where the particle is owned by `rank` or lies within `margin` of the box [lo, hi) on every
+ *          axis, periodic:  for each axis with (hi - lo) + 2 margin < box_size:
+ *              d = |v - float(0.5 (lo + hi))|;  d = min(d, float(box_size) - d);  d <= float(0.5 (hi - lo) + margin)
+ *          float32, one rounding per operation; the constants are formed in float64 first (lo, hi: HOST memory,
+ *          3 doubles each). */
+size_t cgnn_balanced_planes_workspace_bytes(int64_t n, int32_t px, int32_t py, int32_t pz);
+int cgnn_balanced_planes(const float* pos, int64_t n, int32_t px, int32_t py, int32_t pz, float* planes_x,
+                         float* planes_y, float* planes_z, int32_t* owner, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int cgnn_tile_classify(const float* pos, int64_t n, int32_t px, int32_t py, int32_t pz, const float* planes_x,
+                       const float* planes_y, const float* planes_z, int32_t rank, const double* lo, const double* hi,
+                       double margin, double box_size, int32_t* owner, int64_t* counts, uint8_t* mask, void* stream);
+
 /* ---- K11: momentum-conservation term ------------------------------------------
  * sums[g, c] = sum_{i: batch[i]==g} acc[i, c] in float64 (batch sorted ascending,
  * NULL = one graph); reference train.py:107-118.  sums is [num_graphs, width] f64,

@@ -3,7 +3,11 @@ halo stand-in that moves nothing, the rank's own block published instead of the 
 the whole box and on a box of N / world on the same GPU.  The step is split into graph build (the wrapped last frame and
 dist.build_shard with its host synchronisations), features, forward and integrate + unpack; medians over the
 iterations.  The same step t is repeated (only this rank's rows are ever published).  Not part of the product or tests.
-    python scripts/time_sharded_rollout.py [--world 8] [--particles 4000000] [--iters 5]"""
+    python scripts/time_sharded_rollout.py [--world 8] [--particles 4000000] [--iters 5]
+    python scripts/time_sharded_rollout.py --clustered --decomposition balanced --all-ranks --no-baselines
+--clustered starts the window from synthetic.make_clustered_positions (half of the particles in one halo);
+--decomposition picks the tiling (dist.build_shard); --all-ranks runs every rank in turn and prints owned, ghosts,
+interior fraction, step time and peak memory per rank; --no-baselines leaves the two rollout.rollout runs out."""
 import argparse
 import os
 import statistics
@@ -24,6 +28,10 @@ ap.add_argument("--latent", type=int, default=128)
 ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rollout-steps", type=int, default=3)
+ap.add_argument("--decomposition", choices=cdist.DECOMPOSITIONS, default="uniform")
+ap.add_argument("--clustered", action="store_true")
+ap.add_argument("--all-ranks", action="store_true")
+ap.add_argument("--no-baselines", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda")
 W, dt, box = 6, 0.01, 1.0
@@ -33,7 +41,7 @@ meta = synthetic.make_metadata(box, dt)
 
 def window(n, seed):
     g = torch.Generator().manual_seed(seed)
-    p0 = torch.rand(n, 3, generator=g)
+    p0 = synthetic.make_clustered_positions(n, box, seed) if a.clustered else torch.rand(n, 3, generator=g)
     v = torch.randn(n, 3, generator=g) * 0.2
     t = torch.arange(W, dtype=torch.float32).view(-1, 1, 1)
     return {"Coordinates": p0.unsqueeze(0) + v.unsqueeze(0) * (dt * t),
@@ -56,8 +64,8 @@ class NoExchange:
         return None
 
 
-def sharded_step_ms(data):
-    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, a.rank)
+def sharded_step_ms(data, rank):
+    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition)
     t = W
     parts = {"graph": [], "features": [], "forward": [], "integrate+unpack": []}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -85,7 +93,7 @@ def sharded_step_ms(data):
             parts["forward"].append(ev[1].elapsed_time(ev[2]))
             parts["integrate+unpack"].append(ev[2].elapsed_time(ev[3]))
     med = {key: statistics.median(v) for key, v in parts.items()}
-    return med, sh.n_owned, sh.n_ghost, rn.cap
+    return med, sh, rn.cap
 
 
 def rollout_step_ms(data):
@@ -103,11 +111,23 @@ def rollout_step_ms(data):
 
 
 data = window(a.particles, seed=1238)
-med, n_owned, n_ghost, cap = sharded_step_ms(data)
-total = sum(med.values())
-print(f"sharded rollout, rank {a.rank} of {a.world}, N={a.particles} k={k} latent={d} rounds={L} (bf16 edges, fp16x2 "
-      f"nodes), no exchange: owned {n_owned}, ghosts {n_ghost}, send-block rows {cap}")
-print("  per step: " + ", ".join(f"{key} {v:.2f} ms" for key, v in med.items()) + f"; total {total:.2f} ms")
+print(f"sharded rollout, {a.decomposition} tiles of a {'clustered' if a.clustered else 'uniform'} box, world {a.world}, "
+      f"N={a.particles} k={k} latent={d} rounds={L} (bf16 edges, fp16x2 nodes), no exchange", flush=True)
+for rank in (range(a.world) if a.all_ranks else [a.rank]):
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    med, sh, cap = sharded_step_ms(data, rank)
+    total = sum(med.values())
+    peak = (torch.cuda.max_memory_allocated() - base) / 2 ** 30
+    print(f"  rank {rank}: owned {sh.n_owned}, ghosts {sh.n_ghost}, interior {sh.n_interior / max(sh.n_owned, 1):.3f}, "
+          f"send-block rows {cap}, searched {sh.subset_rows} rows in {sh.searches} margin round(s) ({sh.knn_ms:.2f} ms of k-NN kernels), "
+          f"peak {peak:.2f} GiB above the resident model")
+    print("    per step: " + ", ".join(f"{key} {v:.2f} ms" for key, v in med.items()) + f"; total {total:.2f} ms",
+          flush=True)
+    del sh
+if a.no_baselines:
+    sys.exit(0)
 torch.cuda.empty_cache()
 whole = rollout_step_ms(data)
 print(f"rollout.rollout, whole box N={a.particles}: {whole:.2f} ms/step")

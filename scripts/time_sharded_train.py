@@ -4,7 +4,10 @@ same GPU.  Both are forward + backward through the HIP node-stream kernels (``--
 ``model.train_edge_messages``; where the unsharded edge step is refused for memory, its estimate is printed instead of a
 time); HIP-event medians.  Not part of the product or tests.
     python scripts/time_sharded_train.py [--world 8] [--particles 1000000] [--scaling strong] [--train-precision fp32x3]
-                                         [--message-source x_j|edge]"""
+                                         [--message-source x_j|edge] [--decomposition uniform|balanced]
+                                         [--clustered] [--no-unsharded]
+--clustered: the snapshot is synthetic.make_clustered_snapshot's (half of the particles in one halo); --no-unsharded
+leaves the unsharded step out (a clustered run over every rank needs it once at most)."""
 import argparse
 import os
 import sys
@@ -26,6 +29,9 @@ ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--iters", type=int, default=7)
 ap.add_argument("--train-precision", default="fp32x3", choices=["fp32", "fp32x3"])
 ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"])
+ap.add_argument("--decomposition", choices=cdist.DECOMPOSITIONS, default="uniform")
+ap.add_argument("--clustered", action="store_true")
+ap.add_argument("--no-unsharded", action="store_true")
 a = ap.parse_args()
 edge = a.message_source == "edge"
 dev = torch.device("cuda")
@@ -53,7 +59,7 @@ class NoExchange:
         return handle
 
 
-snap = synthetic.make_snapshot(n_total, seed=1236)
+snap = (synthetic.make_clustered_snapshot if a.clustered else synthetic.make_snapshot)(n_total, seed=1236)
 meta = synthetic.make_metadata()
 c, e = snap["Coordinates"], snap["InternalEnergy"]
 g = data_utils.preprocess(c[:5], e[:5], meta, c[5], e[5], 0.0, k, dt, 1.0, device=dev)
@@ -93,13 +99,13 @@ def unsharded_step():
 # the other shards of the same box, so that the ghost pass, the return plan and its add have their real sizes
 world = a.world
 pos = g.pos
-sh = cdist.build_shard(pos, 1.0, k, world, a.rank)
+sh = cdist.build_shard(pos, 1.0, k, world, a.rank, decomposition=a.decomposition)
 wants = []
 for p in range(world):
     if p == a.rank:
         wants.append(torch.empty(0, dtype=torch.int64, device=dev))
     else:
-        wants.append(cdist.build_shard(pos, 1.0, k, world, p).want_global[a.rank])
+        wants.append(cdist.build_shard(pos, 1.0, k, world, p, decomposition=a.decomposition).want_global[a.rank])
 cdist.finish_shard(sh, wants)
 sh.x_feat = g.x[sh.owned_global].contiguous()
 if edge:      # the unsharded graph's edge features, receiver-major with k per receiver
@@ -130,16 +136,18 @@ def shard_step():
 
 
 split = f", n_split {runner.n_split}" if edge else ""
-print(f"{n_total} particles, k={k}, latent {d}, {L} rounds, message_source {a.message_source}, train_precision "
+print(f"{a.decomposition} tiles, {'clustered' if a.clustered else 'uniform'} box; {n_total} particles, k={k}, latent {d}, {L} rounds, message_source {a.message_source}, train_precision "
       f"{a.train_precision}; shard of rank {a.rank}/{world}: {sh.n_owned} owned ({sh.n_interior} interior{split}), "
       f"{sh.n_ghost} ghosts, {sum(sh.send_counts)} rows returned to it per round", flush=True)
 med_u = None
 try:
+    if a.no_unsharded:
+        raise CgnnError("left out (--no-unsharded)")
     med_u, all_u = timed(unsharded_step, a.iters)
     print(f"unsharded training step (forward + backward): {med_u:.2f} ms median of {a.iters} "
           f"({', '.join(f'{x:.1f}' for x in all_u)})", flush=True)
 except CgnnError as err:          # the edge step's memory guard: its estimate instead of a time
-    if not edge:
+    if not edge and not a.no_unsharded:
         raise
     print(f"unsharded training step refused: {err}", flush=True)
 m.zero_grad(set_to_none=True)
