@@ -42,6 +42,7 @@ EXPORTS = (
     "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
     "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
     "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
+    "cgnn_knn_adaptive_workspace_bytes", "cgnn_knn_periodic_adaptive", "cgnn_knn_adaptive_sorted_order",
 )
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
 ROWS, TILED32 = 0, 1
@@ -113,6 +114,10 @@ def load() -> C.CDLL:
     lib.cgnn_knn_workspace_bytes.argtypes = [i64, i32]
     lib.cgnn_knn_periodic.argtypes = [vp, i64, f32, i32, vp, i64, vp, vp, vp, sz, vp]
     lib.cgnn_knn_sorted_order.argtypes = [vp, i64, vp, vp]
+    lib.cgnn_knn_adaptive_workspace_bytes.restype = sz
+    lib.cgnn_knn_adaptive_workspace_bytes.argtypes = [i64, i32]
+    lib.cgnn_knn_periodic_adaptive.argtypes = [vp, i64, f32, i32, vp, i64, vp, vp, vp, sz, vp]
+    lib.cgnn_knn_adaptive_sorted_order.argtypes = [vp, i64, vp, vp]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

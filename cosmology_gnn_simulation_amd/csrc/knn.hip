@@ -211,6 +211,299 @@ __global__ void knn_perm_kernel(const float4* __restrict__ sorted, int64_t n, in
     if (i < n) perm[i] = __float_as_int(sorted[i].w);
 }
 
+// ===================================================================================================================
+// grid = "adaptive": the same coarse grid, every crowded cell refined into 8^s Morton-numbered leaves.
+//
+// The uniform search above evaluates every particle of every cell of a shell; a cell inside a halo holds hundreds.
+// Here a cell with more than CGNN_KNNA_T particles gets the smallest depth s (at most CGNN_KNNA_SMAX) with at most
+// CGNN_KNNA_OCC particles per leaf on average, every other cell is its own single leaf (s = 0).  Leaves are numbered
+// cell after cell (leaf_base = scan of 8^s over the Morton cell ids) and, inside a cell, along the Morton curve, so
+// one counting sort of the particles by leaf id orders them by (coarse Morton id, leaf Morton id), and every aligned
+// block of 8^j leaves -- the whole cell is the block j = s -- is the contiguous range
+// leaf_start[b] .. leaf_start[b + 8^j]: an octree with no storage of its own.  8^s < 8 count / OCC, so there are fewer
+// than cells + 2 n leaves.
+//
+// The search keeps the shell walk over coarse cells and its stopping rule, so the uniform mode's exactness argument
+// holds as it stands; a visited cell is walked block by block and a block is passed over when its box cannot hold
+// anything as close as the current K-th candidate (block_out_of_reach).  Results are the uniform mode's bit for bit:
+// the same float32 distance expression, the same (d2, image index) order, and only candidates that could not have
+// entered the list are left out.
+#define CGNN_KNNA_T 32     // a cell with at most this many particles stays one leaf
+#define CGNN_KNNA_OCC 4    // refined cells: mean leaf occupancy in (OCC / 8, OCC]
+#define CGNN_KNNA_SMAX 6   // at most 64 leaves per axis and cell (G <= 256: fine coordinates stay below 2^14)
+#define CGNN_KNNA_DIRECT 8 // a block with at most this many particles is scanned without descending further
+
+struct KnnAdaptiveLayout {
+    int G;
+    int64_t cells;        // as KnnLayout
+    int64_t max_leaves;   // cells + 2 n bounds the number of leaves for every input
+    size_t off_nleaf, off_lbase, off_lcount, off_lstart, off_bsum, off_leafof, off_sorted, total;
+};
+
+static KnnAdaptiveLayout knn_adaptive_layout(int64_t n) {
+    const KnnLayout U = knn_layout(n);
+    KnnAdaptiveLayout L;
+    L.G = U.G;
+    L.cells = U.cells;
+    L.max_leaves = U.cells + 2 * n;
+    size_t off = 0;
+    L.off_nleaf = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
+    L.off_lbase = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
+    L.off_lcount = off; off = align256(off + (size_t)(L.max_leaves + 1) * 4);
+    L.off_lstart = off; off = align256(off + (size_t)(L.max_leaves + 1) * 4);
+    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(L.max_leaves + 1) + 1) * 4);
+    L.off_leafof = off; off = align256(off + (size_t)n * 4);
+    L.off_sorted = off; off = align256(off + (size_t)n * 16);
+    L.total = off;
+    return L;
+}
+
+__device__ __forceinline__ int compact3(unsigned v) {   // every third bit -> 10 bits (inverse of spread3)
+    v &= 0x09249249u;
+    v = (v | (v >> 2)) & 0x030C30C3u;
+    v = (v | (v >> 4)) & 0x0300F00Fu;
+    v = (v | (v >> 8)) & 0x030000FFu;
+    v = (v | (v >> 16)) & 0x3FFu;
+    return (int)v;
+}
+
+// Leaf coordinate inside coarse cell coordinate c at depth s.  u = fl32(p * inv_h) is the product cell_coord floors,
+// and scaling it by 2^s is exact, so floor(u 2^s) >> s == floor(u): an unclamped particle's leaf lies inside its cell,
+// and the leaf [F, F + 1) 2^-s h of fine coordinate F = (c << s) + result holds it up to the rounding of that one
+// product.  Particles cell_coord clamped into an edge cell are clamped into its edge leaves.
+__device__ __forceinline__ int leaf_coord(float p, float inv_h, int c, int s) {
+    const float u = __fmul_rn(p, inv_h);
+    int f = (int)floorf(__fmul_rn(u, (float)(1 << s))) - (c << s);
+    f = f < 0 ? 0 : f;
+    const int top = (1 << s) - 1;
+    return f > top ? top : f;
+}
+
+__device__ __forceinline__ int depth_of_leaves(int nleaf) { return (31 - __clz(nleaf)) / 3; }   // nleaf = 8^s
+
+// count[c] -> number of leaves of cell c (in place); entry `cells` stays 0 so that the scan ends in the leaf total
+__global__ void knna_depth_kernel(int32_t* __restrict__ count, int64_t cells) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cells) return;
+    const int cnt = count[c];
+    int s = 0;
+    if (cnt > CGNN_KNNA_T)
+        while (s < CGNN_KNNA_SMAX && ((int64_t)CGNN_KNNA_OCC << (3 * s)) < cnt) ++s;
+    count[c] = 1 << (3 * s);
+}
+
+__global__ void knna_leaf_count_kernel(const float* __restrict__ pos, int64_t n, float inv_h, int G,
+                                       const int32_t* __restrict__ lbase, int32_t* __restrict__ leaf_of,
+                                       int32_t* __restrict__ lcount) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float px = pos[3 * i + 0], py = pos[3 * i + 1], pz = pos[3 * i + 2];
+    const int cx = cell_coord(px, inv_h, G), cy = cell_coord(py, inv_h, G), cz = cell_coord(pz, inv_h, G);
+    const int cell = morton3(cx, cy, cz);
+    const int lb = lbase[cell];
+    const int s = depth_of_leaves(lbase[cell + 1] - lb);
+    const int leaf = lb + morton3(leaf_coord(px, inv_h, cx, s), leaf_coord(py, inv_h, cy, s),
+                                  leaf_coord(pz, inv_h, cz, s));
+    leaf_of[i] = leaf;
+    atomicAdd(&lcount[leaf], 1);
+}
+
+// lcount is counted down to zero: no cursor array of its own
+__global__ void knna_fill_kernel(const float* __restrict__ pos, int64_t n, const int32_t* __restrict__ leaf_of,
+                                 const int32_t* __restrict__ lstart, int32_t* __restrict__ lcount,
+                                 float4* __restrict__ sorted) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int leaf = leaf_of[i];
+    const int slot = lstart[leaf] + atomicSub(&lcount[leaf], 1) - 1;
+    sorted[slot] = make_float4(pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], __int_as_float((int)i));
+}
+
+// The uniform kernel's candidate loop over sorted[p0..p1): same expressions, same insertion.
+template <int K>
+__device__ __forceinline__ void knn_scan_range(float (&bd)[K], unsigned (&bi)[K], const float4* __restrict__ sorted,
+                                               int p0, int p1, float shx, float shy, float shz, unsigned shift_id,
+                                               float qx, float qy, float qz) {
+    for (int p = p0; p < p1; ++p) {
+        const float4 c = sorted[p];
+        const float ex = __fadd_rn(c.x, shx), ey = __fadd_rn(c.y, shy), ez = __fadd_rn(c.z, shz);
+        const float ddx = __fsub_rn(ex, qx), ddy = __fsub_rn(ey, qy), ddz = __fsub_rn(ez, qz);
+        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)), __fmul_rn(ddz, ddz));
+        const unsigned key = (shift_id << CGNN_KNN_IDX_BITS) | (unsigned)__float_as_int(c.w);
+        if (d2 < bd[K - 1] || (d2 == bd[K - 1] && key < bi[K - 1])) {
+            bd[K - 1] = d2;
+            bi[K - 1] = key;
+#pragma unroll
+            for (int j = K - 1; j > 0; --j) {
+                const bool sw = bd[j] < bd[j - 1] || (bd[j] == bd[j - 1] && bi[j] < bi[j - 1]);
+                const float td = bd[j];
+                const unsigned ti = bi[j];
+                bd[j] = sw ? bd[j - 1] : td;
+                bi[j] = sw ? bi[j - 1] : ti;
+                bd[j - 1] = sw ? td : bd[j - 1];
+                bi[j - 1] = sw ? ti : bi[j - 1];
+            }
+        }
+    }
+}
+
+// True only when no image in the box [lo, hi) (per axis, already shifted) can enter a list whose last entry is
+// `worst`.  A particle sorted into the box lies inside it up to the rounding of p * inv_h, of lo / hi themselves and
+// of fl32(p + shift): under 1e-6 box together, covered by the 1e-5 box taken off every gap.  The candidate loop's d2
+// differs from the real squared distance by a few units in the last place, covered by the factor (1 - 1e-5).  The
+// comparison is strict: a candidate that ties `worst` and wins on the image index is still looked at.
+__device__ __forceinline__ bool block_out_of_reach(float lox, float hix, float loy, float hiy, float loz, float hiz,
+                                                   float qx, float qy, float qz, float slack, float worst) {
+    const float gx = fmaxf(fmaxf(lox - qx, qx - hix) - slack, 0.f);
+    const float gy = fmaxf(fmaxf(loy - qy, qy - hiy) - slack, 0.f);
+    const float gz = fmaxf(fmaxf(loz - qz, qz - hiz) - slack, 0.f);
+    return (gx * gx + gy * gy + gz * gz) * (1.0f - 1e-5f) > worst;
+}
+
+template <int K>
+__global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
+    const float* __restrict__ pos, int64_t n, float box, float h, float inv_h, int G,
+    const int32_t* __restrict__ lbase, const int32_t* __restrict__ lstart, const float4* __restrict__ sorted,
+    const int32_t* __restrict__ query_ids, int64_t nq, int k, int32_t* __restrict__ senders,
+    float* __restrict__ edge_attr) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nq) return;
+    float qx, qy, qz;
+    int64_t out_row;
+    if (query_ids != nullptr) {
+        const int q = query_ids[t];
+        qx = pos[3 * (int64_t)q + 0];
+        qy = pos[3 * (int64_t)q + 1];
+        qz = pos[3 * (int64_t)q + 2];
+        out_row = t;
+    } else {
+        const float4 s = sorted[t];  // leaf order: neighbouring lanes share cells and, in a refined cell, leaves
+        qx = s.x;
+        qy = s.y;
+        qz = s.z;
+        out_row = __float_as_int(s.w);
+    }
+    const int cx = cell_coord(qx, inv_h, G), cy = cell_coord(qy, inv_h, G), cz = cell_coord(qz, inv_h, G);
+    const float slack = 1e-5f * box;
+
+    float bd[K];
+    unsigned bi[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        bd[j] = __builtin_inff();
+        bi[j] = 0xFFFFFFFFu;
+    }
+
+    // The query's own surroundings first: the smallest aligned block of leaves around its leaf that holds K particles
+    // (level home_j, at most one below the cell).  The list is then full of near candidates before the walk begins, so
+    // the walk prunes from its first block on; it passes over this block when it meets it (shell 0).
+    int home_m = 0, home_j = -1;  // a one-leaf home cell is scanned by the walk itself
+    {
+        const int cell = morton3(cx, cy, cz);
+        const int lb = lbase[cell];
+        const int s = depth_of_leaves(lbase[cell + 1] - lb);
+        if (s > 0) {
+            home_m = morton3(leaf_coord(qx, inv_h, cx, s), leaf_coord(qy, inv_h, cy, s), leaf_coord(qz, inv_h, cz, s));
+            int p0 = 0, p1 = 0;
+            for (home_j = 0; home_j < s; ++home_j) {   // at most SMAX trips
+                const int b = lb + ((home_m >> (3 * home_j)) << (3 * home_j));
+                p0 = lstart[b];
+                p1 = lstart[b + (1 << (3 * home_j))];
+                if (p1 - p0 >= K || home_j == s - 1) break;
+            }
+            knn_scan_range<K>(bd, bi, sorted, p0, p1, 0.f, 0.f, 0.f, 13u, qx, qy, qz);
+        }
+    }
+
+    const int rmax = 2 * G - 1;  // beyond this every one of the 27 images has been visited
+    for (int r = 0; r <= rmax; ++r) {
+        for (int dx = -r; dx <= r; ++dx) {
+            const int ux = cx + dx;
+            if (ux < -G || ux >= 2 * G) continue;
+            const int sx = ux < 0 ? -1 : (ux >= G ? 1 : 0);
+            const int wx = ux - sx * G;
+            const float shx = (float)sx * box;
+            const bool edge_x = (dx == -r) || (dx == r);
+            for (int dy = -r; dy <= r; ++dy) {
+                const int uy = cy + dy;
+                if (uy < -G || uy >= 2 * G) continue;
+                const int sy = uy < 0 ? -1 : (uy >= G ? 1 : 0);
+                const int wy = uy - sy * G;
+                const float shy = (float)sy * box;
+                const bool edge_xy = edge_x || (dy == -r) || (dy == r);
+                const int zstep = edge_xy ? 1 : (2 * r > 0 ? 2 * r : 1);  // interior columns: only the two end caps
+                for (int dz = -r; dz <= r; dz += zstep) {
+                    const int uz = cz + dz;
+                    if (uz < -G || uz >= 2 * G) continue;
+                    const int sz = uz < 0 ? -1 : (uz >= G ? 1 : 0);
+                    const int wz = uz - sz * G;
+                    const float shz = (float)sz * box;
+                    // the whole cell first: needs no memory
+                    if (r > 0 && block_out_of_reach((float)wx * h + shx, (float)(wx + 1) * h + shx,
+                                                    (float)wy * h + shy, (float)(wy + 1) * h + shy,
+                                                    (float)wz * h + shz, (float)(wz + 1) * h + shz, qx, qy, qz,
+                                                    slack, bd[K - 1]))
+                        continue;
+                    const unsigned shift_id = (unsigned)((sx + 1) * 9 + (sy + 1) * 3 + (sz + 1));
+                    const int cell = morton3(wx, wy, wz);
+                    const int lb = lbase[cell];
+                    const int nl = lbase[cell + 1] - lb;
+                    const int s = depth_of_leaves(nl);
+                    const float hs = h * __int_as_float((127 - s) << 23);  // leaf edge h 2^-s, exact
+                    // Morton-order walk without a stack.  At leaf m, aligned to 8^j: take the block [m, m + 8^j) as
+                    // a whole (empty, out of reach, already scanned, or few enough to scan) or descend to j - 1 at
+                    // the same m.  After a block, the next one is the largest aligned at the new m.  Every trip
+                    // advances m or lowers j: at most (s + 1) trips per leaf of the cell.
+                    int m = 0, j = s;
+                    while (m < nl) {
+                        const int bs = 1 << (3 * j);
+                        const int p0 = lstart[lb + m], p1 = lstart[lb + m + bs];
+                        const bool around_home = r == 0 && ((m ^ home_m) >> (3 * j)) == 0;
+                        bool pass = p0 == p1 || (around_home && j <= home_j);
+                        if (!pass && j < s && !around_home) {
+                            const int fx = (wx << s) + compact3((unsigned)m >> 2), fy = (wy << s) + compact3((unsigned)m >> 1),
+                                      fz = (wz << s) + compact3((unsigned)m);
+                            const int w = 1 << j;
+                            pass = block_out_of_reach((float)fx * hs + shx, (float)(fx + w) * hs + shx,
+                                                      (float)fy * hs + shy, (float)(fy + w) * hs + shy,
+                                                      (float)fz * hs + shz, (float)(fz + w) * hs + shz, qx, qy, qz,
+                                                      slack, bd[K - 1]);
+                        }
+                        if (!pass && j > 0 && (around_home || p1 - p0 > CGNN_KNNA_DIRECT)) {
+                            --j;
+                            continue;
+                        }
+                        if (!pass) knn_scan_range<K>(bd, bi, sorted, p0, p1, shx, shy, shz, shift_id, qx, qy, qz);
+                        m += bs;
+                        j = m < nl ? (__ffs(m) - 1) / 3 : 0;
+                    }
+                }
+            }
+        }
+        // the uniform kernel's stopping rule, unchanged: the pruning above never removes a candidate that rule counts on
+        const float bound = (float)r * h * (1.0f - 1e-5f) - 1e-5f * box;
+        float kth = bd[K - 1];
+#pragma unroll
+        for (int j = 0; j < K; ++j) kth = (j == k - 1) ? bd[j] : kth;
+        if (bound > 0.f && kth <= bound * bound) break;
+    }
+    const float px = qx, py = qy, pz = qz;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (j < k) {
+            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
+            senders[out_row * k + j] = snd;
+            if (edge_attr != nullptr) {
+                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], px);
+                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], py);
+                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], pz);
+                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
+                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
+            }
+        }
+    }
+}
+
 }  // namespace cgnn
 
 using namespace cgnn;
@@ -305,6 +598,102 @@ int cgnn_knn_sorted_order(const void* workspace, int64_t n, int32_t* perm, void*
     knn_perm_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, n,
                                                                                                         perm);
     return check_hip(hipGetLastError(), "cgnn_knn_sorted_order launch");
+}
+
+size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k) {
+    (void)k;
+    if (n <= 0) return 256;
+    return knn_adaptive_layout(n).total;
+}
+
+int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                               int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    if (!pos || !senders || !workspace || n <= 0 || k <= 0 || !(box_size > 0.f)) {
+        set_error("cgnn_knn_periodic_adaptive: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (k > 64) {
+        set_error("cgnn_knn_periodic_adaptive: k=%d > 64 is not compiled", k);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)k > 27 * n) {
+        set_error("cgnn_knn_periodic_adaptive: k=%d exceeds the 27*n=%lld periodic images", k, (long long)(27 * n));
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) {
+        set_error("cgnn_knn_periodic_adaptive: n=%lld >= 2^%d particles per call is not supported", (long long)n,
+                  CGNN_KNN_IDX_BITS);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+        set_error("cgnn_knn_periodic_adaptive: workspace must be 16-byte aligned");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const KnnAdaptiveLayout L = knn_adaptive_layout(n);
+    if (workspace_bytes < L.total) {
+        set_error("cgnn_knn_periodic_adaptive: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+        return CGNN_ERR_WORKSPACE;
+    }
+    if (query_ids == nullptr) nq = n;
+    if (nq < 0) {
+        set_error("cgnn_knn_periodic_adaptive: negative query count");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    int32_t* nleaf = reinterpret_cast<int32_t*>(ws + L.off_nleaf);    // coarse counts, then leaves per cell
+    int32_t* lbase = reinterpret_cast<int32_t*>(ws + L.off_lbase);
+    int32_t* lcount = reinterpret_cast<int32_t*>(ws + L.off_lcount);
+    int32_t* lstart = reinterpret_cast<int32_t*>(ws + L.off_lstart);
+    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
+    int32_t* leaf_of = reinterpret_cast<int32_t*>(ws + L.off_leafof);
+    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
+    const int G = L.G;
+    const float h = box_size / (float)G;
+    const float inv_h = (float)G / box_size;
+    const int64_t mc = L.cells + 1;       // nleaf[cells] = 0 so that lbase[cells] = number of leaves
+    const int64_t ml = L.max_leaves + 1;  // lcount is 0 from the last leaf on so that lstart = n there
+    int rc = check_hip(hipMemsetAsync(nleaf, 0, (size_t)mc * 4, st), "knn adaptive memset cell counts");
+    if (rc) return rc;
+    rc = check_hip(hipMemsetAsync(lcount, 0, (size_t)ml * 4, st), "knn adaptive memset leaf counts");
+    if (rc) return rc;
+    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
+    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, leaf_of, nleaf);   // leaf_of: overwritten below
+    knna_depth_kernel<<<(unsigned)((L.cells + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(nleaf, L.cells);
+    exclusive_scan_i32(nleaf, mc, bsum, lbase, st);
+    knna_leaf_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, lbase, leaf_of, lcount);
+    exclusive_scan_i32(lcount, ml, bsum, lstart, st);
+    knna_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, leaf_of, lstart, lcount, sorted);
+    rc = check_hip(hipGetLastError(), "cgnn_knn_periodic_adaptive build launches");
+    if (rc) return rc;
+    if (nq == 0) return CGNN_OK;
+    const unsigned qb = (unsigned)((nq + CGNN_BLOCK - 1) / CGNN_BLOCK);
+#define CGNN_KNNA_LAUNCH(KK)                                                                                        \
+    knn_adaptive_search_kernel<KK><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, lbase, lstart, sorted, \
+                                                              query_ids, nq, k, senders, edge_attr)
+    if (k <= 8)
+        CGNN_KNNA_LAUNCH(8);
+    else if (k <= 16)
+        CGNN_KNNA_LAUNCH(16);
+    else if (k <= 32)
+        CGNN_KNNA_LAUNCH(32);
+    else
+        CGNN_KNNA_LAUNCH(64);
+#undef CGNN_KNNA_LAUNCH
+    return check_hip(hipGetLastError(), "cgnn_knn_periodic_adaptive search launch");
+}
+
+int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {
+    if (!workspace || !perm || n <= 0) {
+        set_error("cgnn_knn_adaptive_sorted_order: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const KnnAdaptiveLayout L = knn_adaptive_layout(n);
+    const float4* sorted = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(workspace) + L.off_sorted);
+    knn_perm_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, n,
+                                                                                                        perm);
+    return check_hip(hipGetLastError(), "cgnn_knn_adaptive_sorted_order launch");
 }
 
 }  // extern "C"

@@ -80,10 +80,12 @@ def generate_temperature_noise(temperature_seq: torch.Tensor, noise_std: float, 
     return torch.cat((torch.zeros_like(t_noise)[:, 0:1], t_noise), dim=1)
 
 
-def knn_graph_periodic(pos: torch.Tensor, box_size: float, k: int, want_order: bool = False):
+def knn_graph_periodic(pos: torch.Tensor, box_size: float, k: int, want_order: bool = False, *,
+                       grid: str = "uniform"):
     """Periodic k-NN on the device.  Returns ``(edge_index int64 [2, N*k],
-    edge_attr [N*k, 4], senders int32, order|None)``."""
-    senders, edge_attr, order = ops.knn_periodic(pos, box_size, k, None, True, want_order)
+    edge_attr [N*k, 4], senders int32, order|None)``.  ``grid``: as in ``ops.knn_periodic``."""
+    ops.check_knn_grid(grid, "knn_graph_periodic")
+    senders, edge_attr, order = ops.knn_periodic(pos, box_size, k, None, True, want_order, grid=grid)
     n = pos.shape[0]
     receivers = torch.arange(n, device=pos.device, dtype=torch.int64).repeat_interleave(k)
     edge_index = torch.stack([senders.to(torch.int64), receivers], dim=0)
@@ -110,7 +112,7 @@ def _draw_reference_noise(pos_seq: torch.Tensor, tmp_seq: torch.Tensor, noise_st
 def preprocess(position_seq, temperature_seq, metadata, target_position=None, target_temperature=None,
                noise_std=0.0, num_neighbors=16, dt=None, box_size=None, device: Optional[torch.device] = None,
                reference_rng: bool = True, check_bounds: bool = True, noise_rng: str = "reference",
-               noise_seed: Optional[int] = None, noise_draw: int = 0):
+               noise_seed: Optional[int] = None, noise_draw: int = 0, *, knn_grid: str = "uniform"):
     """Window ``[W, N, 3]`` / ``[W, N, 1]`` -> graph (reference data_utils.py:72-228).
 
     ``device`` (extension) selects the GPU; by default the inputs' device if they
@@ -131,7 +133,11 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
     ``noise_draw`` for every sample (``step * batch_size + i``); ``noise_seed=None`` means ``torch.initial_seed()``.
     The device path draws nothing on the CPU, leaves torch's global generator where it was, copies nothing from the
     host when the inputs live on the device, and does NOT add the noise into the caller's target tensors (the
-    reference's in-place ``+=`` on them is a side effect of its host code, kept only on the ``"reference"`` path)."""
+    reference's in-place ``+=`` on them is a side effect of its host code, kept only on the ``"reference"`` path).
+
+    ``knn_grid`` (extension): the cell grid of the neighbour search, ``"uniform"`` or ``"adaptive"``
+    (``ops.knn_periodic``); the graph is the same bit for bit, ``"adaptive"`` builds it faster on clustered snapshots."""
+    ops.check_knn_grid(knn_grid, "preprocess")
     if noise_rng not in ("reference", "device"):
         raise ValueError(f"noise_rng must be 'reference' or 'device', got {noise_rng!r}")
     dt = float(dt)
@@ -143,7 +149,7 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
     if noise_rng == "device":
         return _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature,
                                         noise_std, int(num_neighbors), dt, box_size, device, check_bounds, noise_seed,
-                                        noise_draw)
+                                        noise_draw, knn_grid)
 
     pos_seq = position_seq.float().permute(1, 0, 2)                       # [N, W, 3]
     tmp_seq = temperature_seq.float()
@@ -187,7 +193,7 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
 
     # --- periodic k-NN graph + edge features on the device ---
     edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, int(num_neighbors),
-                                                                want_order=True)
+                                                                want_order=True, grid=knn_grid)
     n = recent_position.shape[0]
     if check_bounds:    # reference :158-159 (a host round trip: the on-device rollout turns it off)
         assert int(senders.max()) < n, f"Max sender index {int(senders.max())} >= {n}"
@@ -240,7 +246,8 @@ def _graph(x, edge_index, edge_attr, y_acc, y_temp_rate, recent_position, order,
 
 
 def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature, noise_std,
-                             k: int, dt: float, box_size: float, device, check_bounds: bool, noise_seed, noise_draw):
+                             k: int, dt: float, box_size: float, device, check_bounds: bool, noise_seed, noise_draw,
+                             knn_grid: str = "uniform"):
     """``preprocess(noise_rng="device")``: one launch for noise, features, last frame and targets, then the k-NN."""
     n = position_seq.shape[1]
     pos_w = position_seq.to(device)                                       # [W, N, 3], as the kernel reads it
@@ -262,7 +269,8 @@ def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_pos
     s = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, float(noise_std), seed % 2 ** 64, noise_draw,
                             target_position, target_temperature, None, want)
     recent_position = s["recent_pos"]
-    edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, k, want_order=True)
+    edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, k, want_order=True,
+                                                                grid=knn_grid)
     if check_bounds:    # reference :158-159 (a host round trip)
         assert int(senders.max()) < n, f"Max sender index {int(senders.max())} >= {n}"
     y_tr = s.get("y_temp_rate")

@@ -195,7 +195,7 @@ def _near_tile(pos: torch.Tensor, box_size: float, lo, hi, margin: float) -> tor
 
 def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, rank: int,
                 knn_fn: Optional[Callable] = None, margin_factor: float = 2.0,
-                decomposition: str = "uniform") -> Shard:
+                decomposition: str = "uniform", *, knn_grid: str = "uniform") -> Shard:
     """Everything rank ``rank`` can derive locally from the global positions: its owned set, their k-NN
     senders, the ghost set and the global->local renumbering.  ``knn_fn(pos, box, k, query_ids)`` defaults to
     the HIP k-NN; it returns ``(senders int32 [nq*k], edge_attr [nq*k, 4], order)``.
@@ -208,9 +208,14 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
     ``decomposition``: ``"uniform"`` cuts tiles of equal volume; ``"balanced"`` cuts them at particle-count quantiles
     (:func:`balanced_planes`, kept as ``shard._planes``), so that every rank owns about ``N / world`` particles however
     clustered they are.  The tile is an axis-aligned box that holds every owned particle either way, so the search and
-    its check are the same; only who owns a particle changes, never a result."""
+    its check are the same; only who owns a particle changes, never a result.
+
+    ``knn_grid``: the cell grid of the default search (``ops.knn_periodic``'s ``grid``: ``"uniform"`` or ``"adaptive"``;
+    same neighbours, ``"adaptive"`` is the faster one for a tile that holds a halo).  A caller's ``knn_fn`` is left
+    alone."""
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"build_shard: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
+    ops.check_knn_grid(knn_grid, "build_shard")
     dev = pos_global.device
     n_total = pos_global.shape[0]
     planes = balanced_planes(pos_global, box_size, world) if decomposition == "balanced" else None
@@ -219,7 +224,7 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
     if not classify:
         owner = owner_of(pos_global, box_size, world, planes)
     knn = knn_fn or (lambda p, b, kk, q: ops.knn_periodic(p, b, kk, query_ids=q, want_edge_attr=True,
-                                                          want_order=True))
+                                                          want_order=True, grid=knn_grid))
     t0 = time.perf_counter()
     search_ms = 0.0
 
@@ -373,7 +378,8 @@ def exchange_requests(sh: Shard, group=None) -> Shard:
 def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.Tensor, metadata: dict,
                             target_position: torch.Tensor, target_temperature: torch.Tensor, noise_std: float,
                             num_neighbors: int, dt: float, box_size: float, world: int, rank: int, noise_seed: int,
-                            noise_draw: int = 0, device=None, decomposition: str = "uniform") -> Shard:
+                            noise_draw: int = 0, device=None, decomposition: str = "uniform", *,
+                            knn_grid: str = "uniform") -> Shard:
     """Rank ``rank``'s part of the training sample ``data_utils.preprocess(..., noise_rng="device")`` makes on one GPU,
     with the same bits: the window ``[W, N, 3]`` / ``[W, N(, 1)]`` and the next frame ``[N, 3]`` / ``[N(, 1)]`` (or
     ``[1, N, ...]``) of ALL particles go in, every rank passing the same data, ``noise_seed`` and ``noise_draw``.
@@ -384,7 +390,8 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     :func:`build_shard` does, with ``x_feat``, ``y_acc [n_owned, 3]`` and ``y_temp_rate [n_owned, 1]`` set (local row
     order, ``owned_global``); :func:`exchange_requests` / :func:`finish_shard` remain the caller's next call.
     ``decomposition``: as in :func:`build_shard` (the planes of ``"balanced"`` come from the noisy frame, the same on
-    every rank)."""
+    every rank); ``knn_grid``: as there."""
+    ops.check_knn_grid(knn_grid, "sharded_training_sample")
     if device is None:
         if not position_seq.is_cuda:
             raise CgnnError("sharded_training_sample: pass device= or device-resident windows")
@@ -402,7 +409,8 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     stats = ops.integration_stats(metadata)
     recent = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw,
                                  want=("recent_pos",), stats=stats)["recent_pos"]
-    sh = build_shard(recent, box_size, int(num_neighbors), world, rank, decomposition=decomposition)
+    sh = build_shard(recent, box_size, int(num_neighbors), world, rank, decomposition=decomposition,
+                     knn_grid=knn_grid)
     own = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw, tgt_p, tgt_t,
                               rows=sh.owned_global, want=("x", "y_acc", "y_temp_rate"), stats=stats)
     sh.x_feat, sh.y_acc, sh.y_temp_rate = own["x"], own["y_acc"], own["y_temp_rate"].reshape(-1, 1)
@@ -1233,11 +1241,13 @@ class ShardedRollout:
     5. :meth:`publish`: the gathered ``[world * cap, ROLLOUT_ROW]`` rows -> frame ``t`` (``cgnn_frame_unpack``).
 
     Buffers that depend on the owned count are made per step.  ``decomposition``: as in :func:`build_shard`; with
-    ``"balanced"`` the planes follow the particles from step to step and ``cap`` stays near ``N / world``."""
+    ``"balanced"`` the planes follow the particles from step to step and ``cap`` stays near ``N / world``.
+    ``knn_grid``: as in :func:`build_shard`, for every step's search."""
 
     def __init__(self, model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int = 6,
                  num_neighbors: int = 16, num_steps: Optional[int] = None, device=None, world: int = 1, rank: int = 0,
-                 decomposition: str = "uniform"):
+                 decomposition: str = "uniform", *, knn_grid: str = "uniform"):
+        self.knn_grid = ops.check_knn_grid(knn_grid, "sharded rollout")
         coords, energy, total = rollout_arguments(data, window_size, num_neighbors, num_steps)
         if decomposition not in DECOMPOSITIONS:
             raise ValueError(f"sharded rollout: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
@@ -1268,7 +1278,8 @@ class ShardedRollout:
         if not bool(torch.isfinite(recent).all()):        # the neighbour search must never see a NaN position
             raise CgnnError(f"sharded rollout: frame {t - 1} holds non-finite positions (rows that were never published, "
                             f"or a diverged model)")
-        sh = build_shard(recent, self.box, self.k, self.world, self.rank, decomposition=self.decomposition)
+        sh = build_shard(recent, self.box, self.k, self.world, self.rank, decomposition=self.decomposition,
+                         knn_grid=self.knn_grid)
         if sh._counts is not None:      # the balanced plan on the device: cgnn_tile_classify counted every rank's rows
             self.counts = sh._counts.tolist()
             self.cap = max(self.counts)
@@ -1303,15 +1314,17 @@ class ShardedRollout:
 
 def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: float, box_size: float,
                     window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None, device=None,
-                    group=None, decomposition: str = "uniform") -> dict:
+                    group=None, decomposition: str = "uniform", *, knn_grid: str = "uniform") -> dict:
     """``rollout.rollout`` over the ranks of ``group`` (a world of one when no process group is up): same arguments,
     return value and frame count, and the same bits.  Every rank passes the same ``data`` (checked once, by one
     all-reduce of a checksum) and returns the whole trajectory.  ``noise_std`` is ignored, as there.
-    ``decomposition``: as in :func:`build_shard`; it changes who computes a row, never the row.
+    ``decomposition``, ``knn_grid``: as in :func:`build_shard`; they change who computes a row and how its neighbours
+    are found, never the row.
 
     Per step: the shard of the wrapped last frame, the ghost-id all-to-all, the forward with one halo all-to-all per
     round, the integration of the owned particles and one all-gather of the packed rows into the next frame."""
     del noise_std
+    ops.check_knn_grid(knn_grid, "sharded_rollout")
     rollout_arguments(data, window_size, num_neighbors, num_steps)
     world, rank = _world_of(group)
     import torch.distributed as dist
@@ -1325,7 +1338,7 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
             energy = data["InternalEnergy"]
             check_same_data(data["Coordinates"][:window_size], energy[:window_size], device, group)
         runner = ShardedRollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps, device,
-                                world, rank, decomposition)
+                                world, rank, decomposition, knn_grid=knn_grid)
         for t in range(window_size, runner.total_time):
             sh = runner.plan(t)
             if distributed:
@@ -1346,7 +1359,8 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
 # ----------------------------------------------------------------------------
 
 def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int, seed: int, device, metadata: dict,
-                          group=None, decomposition: str = "uniform") -> Shard:
+                          group=None, decomposition: str = "uniform", *, knn_grid: str = "uniform") -> Shard:
+    ops.check_knn_grid(knn_grid, "build_synthetic_shard")
     n_total = particles_per_gpu * world
     # the box of synthetic.make_snapshot(n_total, seed), bit for bit, but only one global frame (positions: ownership and the
     # neighbour search need all of them) and the feature window of the OWNED particles are built and uploaded: per rank the
@@ -1355,7 +1369,7 @@ def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int,
     box, dt = metadata["box_size"], metadata["dt"]
     W = 5
     pos = torch.remainder(snap.frame(W - 1).to(device), box).contiguous()     # the window's last frame
-    sh = build_shard(pos, box, k, world, rank, decomposition=decomposition)
+    sh = build_shard(pos, box, k, world, rank, decomposition=decomposition, knn_grid=knn_grid)
     sh = exchange_requests(sh, group)
     coords, energy = snap.window_of(sh.owned_global)
     # node features of the owned particles: the same kernel data_utils.preprocess uses

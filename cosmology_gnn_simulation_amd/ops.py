@@ -568,10 +568,31 @@ def node_block(mlp: PackedMLP, w_x: PackedLinear, w_agg: PackedLinear, x: torch.
     return x_out
 
 
+KNN_GRIDS = ("uniform", "adaptive")
+
+
+def check_knn_grid(grid: str, who: str) -> str:
+    """``ValueError`` for a grid name ``knn_periodic`` does not know; callers check before any device work."""
+    if grid not in KNN_GRIDS:
+        raise ValueError(f"{who}: k-NN grid {grid!r}; known: {KNN_GRIDS}")
+    return grid
+
+
 def knn_periodic(pos: torch.Tensor, box_size: float, k: int, query_ids: Optional[torch.Tensor] = None,
-                 want_edge_attr: bool = True, want_order: bool = False):
-    """Returns ``(senders int32 [nq*k], edge_attr float32 [nq*k, 4] | None, order int32 [n] | None)``."""
+                 want_edge_attr: bool = True, want_order: bool = False, *, grid: str = "uniform"):
+    """Returns ``(senders int32 [nq*k], edge_attr float32 [nq*k, 4] | None, order int32 [n] | None)``.
+
+    ``grid``: ``"uniform"`` bins the particles into one uniform cell grid; ``"adaptive"`` refines every crowded cell
+    into leaves and passes over the leaves that are out of reach (``cgnn_knn_periodic_adaptive``): the same
+    ``senders`` and ``edge_attr`` bit for bit, less work where particles cluster.  ``order`` is cell-sorted either
+    way; inside a cell the two modes (like two runs of one mode) may differ."""
+    check_knn_grid(grid, "knn_periodic")
     lib = _lib.load()
+    if grid == "adaptive":
+        ws_fn, knn_fn, order_fn = (lib.cgnn_knn_adaptive_workspace_bytes, lib.cgnn_knn_periodic_adaptive,
+                                   lib.cgnn_knn_adaptive_sorted_order)
+    else:
+        ws_fn, knn_fn, order_fn = lib.cgnn_knn_workspace_bytes, lib.cgnn_knn_periodic, lib.cgnn_knn_sorted_order
     pos = f32c(pos, "pos")
     if pos.dim() != 2 or pos.shape[1] != 3:
         raise CgnnError(f"knn_periodic: pos must be [n, 3], got {tuple(pos.shape)}")
@@ -581,18 +602,18 @@ def knn_periodic(pos: torch.Tensor, box_size: float, k: int, query_ids: Optional
         nq = query_ids.numel()
     else:
         nq = n
-    ws_bytes = lib.cgnn_knn_workspace_bytes(n, k)
+    ws_bytes = ws_fn(n, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
     senders = torch.empty(nq * k, dtype=torch.int32, device=pos.device)
     edge_attr = torch.empty((nq * k, 4), dtype=torch.float32, device=pos.device) if want_edge_attr else None
     st = stream_ptr(pos.device)
     with _timed("knn_periodic", pos.device):
-        check(lib.cgnn_knn_periodic(pos.data_ptr(), n, float(box_size), k, ptr(query_ids), nq, senders.data_ptr(),
-                                ptr(edge_attr), ws.data_ptr(), ws_bytes, st), "cgnn_knn_periodic")
+        check(knn_fn(pos.data_ptr(), n, float(box_size), k, ptr(query_ids), nq, senders.data_ptr(),
+                     ptr(edge_attr), ws.data_ptr(), ws_bytes, st), knn_fn.__name__)
     order = None
     if want_order:
         order = torch.empty(n, dtype=torch.int32, device=pos.device)
-        check(lib.cgnn_knn_sorted_order(ws.data_ptr(), n, order.data_ptr(), st), "cgnn_knn_sorted_order")
+        check(order_fn(ws.data_ptr(), n, order.data_ptr(), st), order_fn.__name__)
     return senders, edge_attr, order
 
 

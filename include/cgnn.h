@@ -452,6 +452,25 @@ int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k,
  * index of the i-th particle in sorted order. */
 int cgnn_knn_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream);
 
+/* The same search over a density-adaptive grid: the same arguments, checks, error codes and -- for every input --
+ * the same bits in senders and edge_attr as cgnn_knn_periodic.  Every coarse cell that holds more than 32 particles
+ * is refined into 8^s Morton-numbered leaves of about 4 particles or fewer, and the search passes over every block
+ * of leaves whose box cannot hold anything as close as the current k-th candidate, so its cost follows k and not the
+ * local density (clustered inputs).  No host synchronisation, everything on `stream`.
+ * Workspace: a function of n alone, O(n): at most CGNN_KNN_ADAPTIVE_BYTES_PER_PARTICLE * n +
+ * CGNN_KNN_ADAPTIVE_BYTES_FIXED bytes (cell and leaf tables for at most 4 n cells and 6 n leaves, the leaf id and the
+ * sorted float4 of every particle), never less than cgnn_knn_workspace_bytes(n, k).
+ * cgnn_knn_adaptive_sorted_order: the (coarse cell, leaf)-sorted order of the last cgnn_knn_periodic_adaptive on this
+ * workspace.  Its coarse-cell sequence is that of cgnn_knn_sorted_order; inside a cell the two may differ. */
+#define CGNN_KNN_ADAPTIVE_BYTES_PER_PARTICLE 104
+#define CGNN_KNN_ADAPTIVE_BYTES_FIXED 4096
+size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k);
+int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k,
+                               const int32_t* query_ids, int64_t nq,
+                               int32_t* senders, float* edge_attr,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes

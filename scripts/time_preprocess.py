@@ -2,7 +2,7 @@
 the device (noise_rng="device"), windows resident on the GPU.  Both modes alternate in one process after a warm-up; each
 call is timed with the host clock around a final synchronise; medians are printed, with the split into the sample
 (noise + features + targets) and the k-NN graph build.  Not part of the product or tests.
-    python scripts/time_preprocess.py [--particles 1000000] [--window 6] [--iters 10]
+    python scripts/time_preprocess.py [--particles 1000000] [--window 6] [--iters 10] [--knn-grid uniform|adaptive]
     rocprofv3 --kernel-trace --stats -- python scripts/time_preprocess.py --device-only     (the kernel's own time)"""
 import argparse
 import os
@@ -21,6 +21,7 @@ ap.add_argument("--neighbors", type=int, default=16)
 ap.add_argument("--window", type=int, default=6)
 ap.add_argument("--noise-std", type=float, default=3e-4)
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--knn-grid", choices=ops.KNN_GRIDS, default="uniform")
 ap.add_argument("--device-only", action="store_true", help="skip the CPU-drawn mode (for a profiler run)")
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -46,7 +47,7 @@ def whole(mode):
     # the reference path adds the noise into the targets it is given: hand it copies, as a loader hands over a new sample
     tp, tt = (c[w].clone(), e[w].clone()) if mode == "reference" else (c[w], e[w])
     return data_utils.preprocess(c[:w], e[:w], meta, tp, tt, a.noise_std, k, dt, box, check_bounds=False, noise_rng=mode,
-                                 noise_seed=1237, noise_draw=draw)
+                                 noise_seed=1237, noise_draw=draw, knn_grid=a.knn_grid)
 
 
 def sample():
@@ -62,13 +63,14 @@ for it in range(a.iters + 2):                          # two warm-up rounds
         if it >= 2:
             times[m].append(ms)
     ms_s, s = timed(sample)
-    ms_k, _ = timed(lambda: data_utils.knn_graph_periodic(s["recent_pos"], box, k, want_order=True))
+    ms_k, _ = timed(lambda: data_utils.knn_graph_periodic(s["recent_pos"], box, k, want_order=True,
+                                                          grid=a.knn_grid))
     if it >= 2:
         times["sample kernel call"].append(ms_s)
         times["k-NN"].append(ms_k)
 med = {name: statistics.median(v) for name, v in times.items()}
 nbytes = 4 * n * ((w * 4 + 4) + (4 * w - 3) + 3 + 3 + 1)
-print(f"preprocess with noise_std {a.noise_std:g}: {n} particles, W = {w}, k = {k}, windows on the device; "
+print(f"preprocess with noise_std {a.noise_std:g}, k-NN grid {a.knn_grid}: {n} particles, W = {w}, k = {k}, windows on the device; "
       f"medians of {a.iters} (host clock around a synchronise)")
 for m in modes:
     print(f"  noise_rng={m!r:12s} whole call {med[m]:9.2f} ms   of which k-NN {med['k-NN']:.2f} ms, "

@@ -1,7 +1,7 @@
 """Developer tool: one rank's share of `bench.py --gpus N` on ONE GPU, without the exchange (a halo stand-in that copies
 nothing): what a rank computes per forward next to the unsharded forward of the same size.
     python scripts/time_shard.py [--world 8] [--particles 1000000] [--scaling weak]
-                                 [--decomposition uniform|balanced] [--clustered]
+                                 [--decomposition uniform|balanced] [--clustered] [--knn-grid uniform|adaptive]
 --clustered: the last frame is synthetic.make_clustered_snapshot's (half of the particles in one halo)."""
 import argparse
 import os
@@ -23,6 +23,7 @@ ap.add_argument("--latent", type=int, default=128)
 ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--decomposition", choices=cdist.DECOMPOSITIONS, default="uniform")
+ap.add_argument("--knn-grid", choices=ops.KNN_GRIDS, default="uniform")
 ap.add_argument("--clustered", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -46,15 +47,16 @@ snap = (synthetic.make_clustered_snapshot if a.clustered else synthetic.make_sna
 coords = snap["Coordinates"][:5].to(dev)
 energy = snap["InternalEnergy"][:5].to(dev)
 pos = torch.remainder(coords[-1], meta["box_size"]).contiguous()
-sh = cdist.build_shard(pos, meta["box_size"], a.neighbors, a.world, a.rank, decomposition=a.decomposition)
+sh = cdist.build_shard(pos, meta["box_size"], a.neighbors, a.world, a.rank, decomposition=a.decomposition,
+                       knn_grid=a.knn_grid)
 sh = cdist.build_shard(pos, meta["box_size"], a.neighbors, a.world, a.rank,        # second call: allocator and kernels warm
-                       decomposition=a.decomposition)
+                       decomposition=a.decomposition, knn_grid=a.knn_grid)
 # every peer's request list is needed to finish the plan; without peers the send side stays empty
 cdist.finish_shard(sh, [torch.empty(0, dtype=torch.int64, device=dev) for _ in range(a.world)])
 sh.x_feat, _ = ops.window_features(coords[:, sh.owned_global].contiguous(), energy[:, sh.owned_global].contiguous(), meta,
                                    meta["dt"], meta["box_size"])
 torch.cuda.synchronize()
-print(f"{a.decomposition} tiles, {'clustered' if a.clustered else 'uniform'} box; "
+print(f"{a.decomposition} tiles, k-NN grid {a.knn_grid}, {'clustered' if a.clustered else 'uniform'} box; "
       f"shard of rank {a.rank}/{a.world}: {sh.n_owned} owned ({sh.n_interior} interior), {sh.n_ghost} ghosts, "
       f"k-NN searches over tile + margin {sh.knn_ms:.2f} ms (subset selection + searches + margin check "
       f"{sh.subset_build_ms:.1f} ms), everything incl. snapshot {time.perf_counter() - t0:.1f} s", flush=True)

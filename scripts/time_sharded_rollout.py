@@ -7,7 +7,8 @@ iterations.  The same step t is repeated (only this rank's rows are ever publish
     python scripts/time_sharded_rollout.py --clustered --decomposition balanced --all-ranks --no-baselines
 --clustered starts the window from synthetic.make_clustered_positions (half of the particles in one halo);
 --decomposition picks the tiling (dist.build_shard); --all-ranks runs every rank in turn and prints owned, ghosts,
-interior fraction, step time and peak memory per rank; --no-baselines leaves the two rollout.rollout runs out."""
+interior fraction, step time and peak memory per rank; --no-baselines leaves the two rollout.rollout runs out;
+--knn-grid picks the cell grid of every neighbour search (ops.KNN_GRIDS)."""
 import argparse
 import os
 import statistics
@@ -17,7 +18,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cosmology_gnn_simulation_amd import dist as cdist, graph_network, rollout, synthetic  # noqa: E402
+from cosmology_gnn_simulation_amd import dist as cdist, graph_network, ops, rollout, synthetic  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--world", type=int, default=8)
@@ -29,6 +30,7 @@ ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rollout-steps", type=int, default=3)
 ap.add_argument("--decomposition", choices=cdist.DECOMPOSITIONS, default="uniform")
+ap.add_argument("--knn-grid", choices=ops.KNN_GRIDS, default="uniform")
 ap.add_argument("--clustered", action="store_true")
 ap.add_argument("--all-ranks", action="store_true")
 ap.add_argument("--no-baselines", action="store_true")
@@ -65,7 +67,7 @@ class NoExchange:
 
 
 def sharded_step_ms(data, rank):
-    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition)
+    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition, knn_grid=a.knn_grid)
     t = W
     parts = {"graph": [], "features": [], "forward": [], "integrate+unpack": []}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -98,20 +100,20 @@ def sharded_step_ms(data, rank):
 
 def rollout_step_ms(data):
     with torch.no_grad():
-        rollout.rollout(m, data, meta, 0.0, dt, box, W, k, 1)                 # warm-up (weight packing)
+        rollout.rollout(m, data, meta, 0.0, dt, box, W, k, 1, knn_grid=a.knn_grid)                 # warm-up (weight packing)
         torch.cuda.synchronize()
         times = []
         for _ in range(a.iters):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            rollout.rollout(m, data, meta, 0.0, dt, box, W, k, a.rollout_steps)
+            rollout.rollout(m, data, meta, 0.0, dt, box, W, k, a.rollout_steps, knn_grid=a.knn_grid)
             torch.cuda.synchronize()
             times.append((time.perf_counter() - t0) * 1e3 / a.rollout_steps)
     return statistics.median(times)
 
 
 data = window(a.particles, seed=1238)
-print(f"sharded rollout, {a.decomposition} tiles of a {'clustered' if a.clustered else 'uniform'} box, world {a.world}, "
+print(f"sharded rollout, k-NN grid {a.knn_grid}, {a.decomposition} tiles of a {'clustered' if a.clustered else 'uniform'} box, world {a.world}, "
       f"N={a.particles} k={k} latent={d} rounds={L} (bf16 edges, fp16x2 nodes), no exchange", flush=True)
 for rank in (range(a.world) if a.all_ranks else [a.rank]):
     torch.cuda.empty_cache()
