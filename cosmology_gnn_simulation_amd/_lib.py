@@ -43,8 +43,12 @@ EXPORTS = (
     "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
     "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
     "cgnn_knn_adaptive_workspace_bytes", "cgnn_knn_periodic_adaptive", "cgnn_knn_adaptive_sorted_order",
+    "cgnn_history_features", "cgnn_rollout_advance", "cgnn_halo_select", "cgnn_halo_pack", "cgnn_migrate_pack",
+    "cgnn_migrate_unpack",
 )
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
+MIGRATE_BLOCK = 256     # CGNN_MIGRATE_BLOCK: rows per workgroup of the migration kernels (block_counts / offsets rows)
+MIGRATE_MAX_WORLD = 64  # ranks a peer mask holds
 ROWS, TILED32 = 0, 1
 
 
@@ -130,6 +134,14 @@ def load() -> C.CDLL:
     lib.cgnn_balanced_planes.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.cgnn_tile_classify.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.c_double, C.c_double, vp, vp, vp, vp]
+    dp = C.POINTER(C.c_double)
+    lib.cgnn_history_features.argtypes = [vp, i32, i64, i64, i32, vp, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp]
+    lib.cgnn_rollout_advance.argtypes = [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, vp, f32, f32, i32, i32, i32, i32, vp,
+                                         vp, vp, vp, vp, vp, vp, vp]
+    lib.cgnn_halo_select.argtypes = [vp, i64, i32, i32, dp, dp, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.cgnn_halo_pack.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp]
+    lib.cgnn_migrate_pack.argtypes = [vp, i32, i64, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp]
+    lib.cgnn_migrate_unpack.argtypes = [vp, i64, i32, vp, i64, i64, vp, vp]
     lib.cgnn_gather_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_scatter_rows.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.cgnn_halo_return_add.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, i64, vp]

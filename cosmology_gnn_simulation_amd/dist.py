@@ -364,15 +364,16 @@ def _collective(collective: Callable, out: torch.Tensor, *inputs: torch.Tensor, 
     return wait
 
 
-def exchange_requests(sh: Shard, group=None) -> Shard:
-    """Setup-time all-to-all of the ghost id lists (sizes, then ids)."""
+def exchange_requests(sh: Shard, group=None, finish: Optional[Callable] = None) -> Shard:
+    """Setup-time all-to-all of the ghost id lists (sizes, then ids).  ``finish(sh, requests)`` makes the send plan
+    (:func:`finish_shard`; :func:`finish_shard_by_search` for a shard numbered in subset space)."""
     import torch.distributed as dist
     counts_out = torch.tensor(sh.recv_counts, dtype=torch.int64, device=sh.owned_global.device)
     counts_in = _collective(dist.all_to_all_single, torch.empty_like(counts_out), counts_out, group=group)().tolist()
     recv = torch.empty(int(sum(counts_in)), dtype=torch.int64, device=counts_out.device)
     _collective(dist.all_to_all_single, recv, sh.ghost_global.contiguous(), output_split_sizes=counts_in,
                 input_split_sizes=sh.recv_counts, group=group)()
-    return finish_shard(sh, list(torch.split(recv, counts_in)))
+    return (finish or finish_shard)(sh, list(torch.split(recv, counts_in)))
 
 
 def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.Tensor, metadata: dict,
@@ -1314,7 +1315,8 @@ class ShardedRollout:
 
 def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: float, box_size: float,
                     window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None, device=None,
-                    group=None, decomposition: str = "uniform", *, knn_grid: str = "uniform") -> dict:
+                    group=None, decomposition: str = "uniform", storage: str = "replicated", *,
+                    knn_grid: str = "uniform") -> dict:
     """``rollout.rollout`` over the ranks of ``group`` (a world of one when no process group is up): same arguments,
     return value and frame count, and the same bits.  Every rank passes the same ``data`` (checked once, by one
     all-reduce of a checksum) and returns the whole trajectory.  ``noise_std`` is ignored, as there.
@@ -1322,11 +1324,31 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
     are found, never the row.
 
     Per step: the shard of the wrapped last frame, the ghost-id all-to-all, the forward with one halo all-to-all per
-    round, the integration of the owned particles and one all-gather of the packed rows into the next frame."""
+    round, the integration of the owned particles and one all-gather of the packed rows into the next frame.
+
+    ``storage="owned"``: every rank keeps and returns only the particles it holds (:class:`MigratingRollout`):
+    ``{"frames": [rows_0, ..., rows_{T-1}], "n_total": N, "world": w, "rank": r}``, ``rows_t [n_held_t, ROLLOUT_ROW]``
+    the packed rows (x, y, z, temperature, int32 id bits) of the particles this rank held at frame t; the first
+    ``window_size`` frames are its initially owned particles (``owner_of`` of the wrapped frame W-1), stored raw.
+    After start-up, which slices the given window, nothing of length N exists on any rank; a particle that crosses a
+    tile plane is sent to its new rank with its window history.  The same frames and bits
+    (:func:`assemble_frames`, :func:`owned_frame_errors`).  With ``decomposition="balanced"`` the planes are those of
+    the initial frame and stay fixed for the run: re-balancing needs a distributed quantile search and is not built.
+    At most 64 ranks."""
     del noise_std
     ops.check_knn_grid(knn_grid, "sharded_rollout")
     rollout_arguments(data, window_size, num_neighbors, num_steps)
     world, rank = _world_of(group)
+    check_rollout_storage(storage, world, "sharded_rollout")
+    if storage == "owned":
+        if decomposition not in DECOMPOSITIONS:
+            raise ValueError(f"sharded rollout: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
+        if device is None:
+            device = next(model.parameters()).device
+        model.eval()
+        with torch.no_grad():
+            return _owned_rollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps,
+                                  torch.device(device), group, decomposition, knn_grid)
     import torch.distributed as dist
     distributed = dist.is_available() and dist.is_initialized()
     if device is None:
@@ -1352,6 +1374,458 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
             block = runner.integrate(sh, pred, t)
             runner.publish(all_gather_rows(block, group) if distributed else block, t)
     return runner.result()
+
+
+# ----------------------------------------------------------------------------
+# sharded rollout with particle migration (storage="owned"): every rank keeps only its tile
+# ----------------------------------------------------------------------------
+
+ROLLOUT_STORAGE = ("replicated", "owned")
+MAX_MIGRATING_WORLD = _lib.MIGRATE_MAX_WORLD      # a held row's peer mask is one 64-bit word
+
+
+def check_rollout_storage(storage: str, world: int, what: str = "sharded rollout") -> str:
+    if storage not in ROLLOUT_STORAGE:
+        raise ValueError(f"{what}: storage {storage!r}; known: {ROLLOUT_STORAGE}")
+    if storage == "owned" and world > MAX_MIGRATING_WORLD:
+        raise ValueError(f"{what}: storage='owned' supports at most {MAX_MIGRATING_WORLD} ranks (the per-particle peer "
+                         f"mask is one 64-bit word), got a world of {world}")
+    return storage
+
+
+def first_margin(box_size: float, k: int, n_total: int, margin_factor: float = 2.0) -> float:
+    """:func:`build_shard`'s first search margin: ``margin_factor`` x the radius that holds k particles at mean density."""
+    return margin_factor * box_size * (3.0 * k / (4.0 * 3.141592653589793 * max(n_total, 1))) ** (1.0 / 3.0)
+
+
+def peer_mask(pos: torch.Tensor, box_size: float, world: int, rank: int, margin: float,
+              planes: Optional[TilePlanes] = None) -> torch.Tensor:
+    """bool ``[n, world]``: column p marks the rows of ``pos`` (positions rank ``rank`` holds) that peer p's search needs
+    for ``margin``: those within the margin of p's tile, one test per tile (:func:`_near_tile`, not one per periodic
+    image, so nothing is marked twice).  The rank's own column stays empty.  The torch restatement of
+    ``cgnn_halo_select``."""
+    out = torch.zeros((pos.shape[0], world), dtype=torch.bool, device=pos.device)
+    for p in range(world):
+        if p != rank:
+            lo, hi = tile_bounds(box_size, world, p, planes)
+            out[:, p] = _near_tile(pos, box_size, lo, hi, margin)
+    return out
+
+
+def subset_shard(rank: int, world: int, k: int, owned_s: torch.Tensor, senders_s: torch.Tensor, edge_attr: torch.Tensor,
+                 owner_sub: torch.Tensor, sub_ids: Optional[torch.Tensor] = None) -> Shard:
+    """:func:`build_shard`'s tail in subset space, with nothing of length N: the search set has ``n_sub`` rows in
+    ascending global id (``sub_ids`` int64; ``None``: the set is the whole box and a row is its id), ``owner_sub`` is
+    the rank holding each, ``owned_s`` the subset rows of the queries (the rank's own particles, in the local order
+    wanted) and ``senders_s [n_owned * k]`` their neighbours as subset rows.  Interior receivers first, ghosts grouped
+    by the rank they came from in ascending id, local numbering ``[owned | ghosts]``: every field as
+    :func:`build_shard` makes it.  The send plan comes from :func:`finish_shard_by_search`."""
+    dev = owner_sub.device
+    n_sub = owner_sub.numel()
+    owned = owned_s.long()
+    n_owned = owned.numel()
+    senders = senders_s.long()
+    remote = owner_sub[senders] != rank
+    is_boundary = remote.view(n_owned, k).any(dim=1) if n_owned else remote.new_zeros((0,))
+    n_interior = int((~is_boundary).sum())
+    if 0 < n_interior < n_owned:
+        regroup = torch.cat([torch.nonzero(~is_boundary).squeeze(1), torch.nonzero(is_boundary).squeeze(1)])
+        owned = owned[regroup]
+        senders = senders.view(n_owned, k)[regroup].reshape(-1)
+        edge_attr = edge_attr.view(n_owned, k, -1)[regroup].reshape(n_owned * k, -1).contiguous()
+        remote = remote.view(n_owned, k)[regroup].reshape(-1)
+    ghosts = torch.unique(senders[remote])
+    g_owner = owner_sub[ghosts].long()
+    perm = torch.argsort(g_owner * max(n_sub, 1) + ghosts)       # by rank, ascending subset row (= ascending id) inside
+    ghosts, g_owner = ghosts[perm], g_owner[perm]
+    recv_counts = torch.bincount(g_owner, minlength=world).tolist()
+    s2l = torch.full((n_sub,), -1, dtype=torch.int32, device=dev)
+    s2l[owned] = torch.arange(n_owned, dtype=torch.int32, device=dev)
+    s2l[ghosts] = n_owned + torch.arange(ghosts.numel(), dtype=torch.int32, device=dev)
+    src_local = s2l[senders].contiguous()
+    dst_local = torch.arange(n_owned, dtype=torch.int32, device=dev).repeat_interleave(k)
+    own_sorted = torch.sort(owned).values
+    if sub_ids is None:
+        owned_global, ghost_global, held_sorted = owned, ghosts, own_sorted
+    else:
+        owned_global, ghost_global, held_sorted = sub_ids[owned], sub_ids[ghosts], sub_ids[own_sorted]
+    sh = Shard(rank, world, k, n_owned, ghosts.numel(), owned_global, ghost_global, src_local, dst_local, edge_attr,
+               recv_counts, want_global=list(torch.split(ghost_global, recv_counts)), n_interior=n_interior)
+    sh._s2l = s2l                             # subset row -> local row (-1: neither owned nor a ghost)
+    sh._held_sorted = held_sorted             # the held global ids, ascending
+    sh._local_of_sorted = s2l[own_sorted]     # ... and the local row of each
+    return sh
+
+
+def held_rows_of(held_sorted: torch.Tensor, local_of_sorted: torch.Tensor, request: torch.Tensor, what: str) -> torch.Tensor:
+    """Local rows of the requested global ids, by a search in the ascending held ids; raises on an id not held."""
+    req = request.long()
+    if req.numel() == 0:
+        return local_of_sorted[:0]
+    if held_sorted.numel() == 0:
+        raise RuntimeError(f"{what} requested rows this rank does not own")
+    at = torch.searchsorted(held_sorted, req).clamp_(max=held_sorted.numel() - 1)
+    if not bool((held_sorted[at] == req).all()):
+        raise RuntimeError(f"{what} requested rows this rank does not own")
+    return local_of_sorted[at]
+
+
+def finish_shard_by_search(sh: Shard, requests_from_peers: Sequence[torch.Tensor]) -> Shard:
+    """:func:`finish_shard` for a :func:`subset_shard`: the requested global ids are found in the sorted held ids (no
+    ``[n_total]`` map)."""
+    idx = [held_rows_of(sh._held_sorted, sh._local_of_sorted, req, f"rank {sh.rank}: rank {r}")
+           for r, req in enumerate(requests_from_peers)]
+    sh.send_counts = [int(t.numel()) for t in idx]
+    sh.send_idx = torch.cat(idx).to(torch.int32).contiguous() if idx else torch.empty(0, dtype=torch.int32)
+    return sh
+
+
+class MigratingRollout:
+    """One rank's part of a rollout over spatial tiles that holds this rank's particles only (``storage="owned"``).
+    It is built from the rank's own rows -- ``ids`` (global ids), ``coords_w [W, n_own, 3]`` and ``energy_w [W, n_own(,
+    1)]``, the initial window of those particles -- and the integer ``n_total``; no tensor of length N is passed in or
+    made afterwards.  The frames and bits are those of ``rollout.rollout``.
+
+    State: the window histories in a frame-major ring ``hist [W, cap, 4]`` of (x, y, z, T) (frame f in slot f mod W: the
+    same phase on every rank), ``ids int32 [cap]``, a second ring of the same size that migration gathers into, and the
+    recorded frame blocks (``[n_held_t, ROLLOUT_ROW]`` each): ``n_held * (16 W + 4)`` bytes per ring plus ``20 n_held``
+    per recorded frame.
+
+    A step is these pieces, separate so that one process can interleave several ranks (tests); ``sharded_rollout``
+    joins them with the collectives:
+
+    1. :meth:`begin`: wrapped last positions of the held rows from the ring (``cgnn_history_features``);
+    2. :meth:`halo_out`: ``(x, y, z, id)`` rows for every peer whose tile, grown by the margin, holds them
+       (``cgnn_halo_select`` / ``cgnn_halo_pack``), one all-to-all-v;
+    3. :meth:`search`: held rows + imports sorted by global id (:func:`build_shard`'s ``sub`` for that margin), the
+       owned queries through ``ops.knn_periodic``, the k-th neighbour checked against the margin; returns "my check
+       failed": after a MAX all-reduce all ranks :meth:`widen` (double the margin) and repeat 2-3 together;
+    4. :meth:`number` (:func:`subset_shard`), then the ghost-id exchange with :func:`finish_shard_by_search`;
+    5. :meth:`features` and :meth:`forward` (an unchanged :class:`ShardedForward`);
+    6. :meth:`advance`: ``cgnn_rollout_advance`` integrates, writes the ring slot of the oldest frame, records the
+       frame rows and counts the rows per destination rank;
+    7. :meth:`migrate_out` / :meth:`receive`: leavers ``(id, W float4)`` grouped by destination, one all-to-all-v,
+       stayers and arrivals gathered into the second ring (``cgnn_migrate_pack`` / ``cgnn_migrate_unpack``);
+       :meth:`check_total` on the all-reduced held counts: a lost particle raises on every rank.
+
+    ``planes``: the cutting planes of a balanced decomposition, fixed for the run (the ranks cannot re-balance without
+    a distributed quantile search over all particles, which is not built); ``None``: equal-volume tiles."""
+
+    def __init__(self, model, ids: torch.Tensor, coords_w: torch.Tensor, energy_w: torch.Tensor, *, n_total: int,
+                 metadata: dict, dt: float, box_size: float, window_size: int = 6, num_neighbors: int = 16,
+                 num_steps: int = 0, device=None, world: int = 1, rank: int = 0, planes: Optional[TilePlanes] = None,
+                 knn_grid: str = "uniform", margin_factor: float = 2.0):
+        what = "migrating rollout"
+        self.knn_grid = ops.check_knn_grid(knn_grid, what)
+        check_rollout_storage("owned", world, what)
+        if isinstance(n_total, torch.Tensor) or int(n_total) != n_total:
+            raise ValueError(f"{what}: n_total must be an integer")
+        n_total, W, k = int(n_total), int(window_size), int(num_neighbors)
+        if not 2 <= W <= 32:
+            raise ValueError(f"{what}: window_size {W} outside [2, 32]")
+        if not 0 <= rank < world:
+            raise ValueError(f"{what}: rank {rank} outside a world of {world}")
+        if n_total >= 2 ** 31 or k < 1 or k > n_total or num_steps < 0:
+            raise ValueError(f"{what}: n_total {n_total}, num_neighbors {k}, num_steps {num_steps}")
+        if energy_w.dim() == 2:
+            energy_w = energy_w.unsqueeze(-1)
+        n = ids.numel()
+        if coords_w.shape != (W, n, 3) or energy_w.shape != (W, n, 1):
+            raise ValueError(f"{what}: the rank's window must be [W, n_own, 3] / [W, n_own(, 1)] for its {n} ids and W = "
+                             f"{W}, got {tuple(coords_w.shape)} / {tuple(energy_w.shape)}")
+        if planes is not None and tuple(planes.grid) != tile_grid(world):
+            raise ValueError(f"{what}: planes of a {planes.grid} tile grid for a world of {world}")
+        if device is None:
+            device = next(model.parameters()).device
+        self.device = dev = torch.device(device)
+        self.model, self.world, self.rank, self.planes = model, world, rank, planes
+        self.W, self.k, self.n_total, self.total_time = W, k, n_total, W + int(num_steps)
+        self.dt, self.box = float(dt), float(box_size)
+        self.meta = dict(metadata)
+        self.meta["dt"], self.meta["box_size"] = dt, box_size
+        self.stats = ops.integration_stats(self.meta)
+        self.grid = tile_grid(world)
+        bounds = [tile_bounds(self.box, world, r, planes) for r in range(world)]        # start-up read-backs (planes)
+        self.boxes = ops.tile_boxes([b[0] for b in bounds], [b[1] for b in bounds])
+        self.margin0 = first_margin(self.box, k, n_total, margin_factor)
+        self.n_held = n
+        self.hist, self.ids = self._ring(n)
+        self.hist[:, :n, :3] = coords_w.to(dev).float()
+        self.hist[:, :n, 3:] = energy_w.to(dev).float()
+        self.ids[:n] = ids.to(dev).to(torch.int32)
+        self._spare = None
+        self.frames: List[torch.Tensor] = []
+        for f in range(W):          # the initial frames, raw, in the packed row format
+            rows = torch.empty((n, _lib.ROLLOUT_ROW), dtype=torch.float32, device=dev)
+            rows[:, :4] = self.hist[f, :n]
+            rows.view(torch.int32)[:, 4] = self.ids[:n]
+            self.frames.append(rows)
+        self.t = W
+        self.margin, self.searches = self.margin0, 0
+        self.arrivals: List[int] = []
+
+    def _ring(self, rows: int):
+        cap = rows + rows // 8 + 256
+        return (torch.empty((self.W, cap, 4), dtype=torch.float32, device=self.device),     # rows >= n_held: never read
+                torch.full((cap,), -1, dtype=torch.int32, device=self.device))
+
+    @property
+    def phase(self) -> int:
+        return self.t % self.W
+
+    # -- 1-3: positions, halo, search ----------------------------------------------------------------------------------
+    def begin(self) -> None:
+        """Step ``self.t``: the wrapped last positions (and id bits) of the held rows, storage order."""
+        _, self.recent = ops.history_features(self.hist, self.n_held, self.phase, self.meta, self.dt, self.box,
+                                              ids=self.ids, want_x=False, want_recent=True)
+        if not bool(torch.isfinite(self.recent[:, :3]).all()):      # the neighbour search must never see a NaN position
+            raise CgnnError(f"migrating rollout: rank {self.rank} holds non-finite positions at frame {self.t - 1} (a "
+                            f"diverged model)")
+        self.margin, self.searches = self.margin0, 0
+
+    def widen(self) -> None:
+        self.margin *= 2.0
+
+    def halo_out(self):
+        """``(rows [S, 4], send_counts)``: the held ``(x, y, z, id)`` rows every peer's search needs for the current
+        margin, grouped by peer in storage order.  One read-back (the counts)."""
+        mask, block_counts, counts = ops.halo_select(self.recent, self.rank, self.boxes, self.margin, self.box)
+        send_counts = counts.tolist()
+        starts = torch.cumsum(counts, 0) - counts
+        rows = ops.halo_pack(self.recent, mask, ops.group_offsets(block_counts, starts), sum(send_counts))
+        return rows, send_counts
+
+    def search(self, imports: torch.Tensor, recv_counts: Sequence[int]) -> bool:
+        """``imports [R, 4]``: the rows the peers sent, grouped by peer (``recv_counts``).  Builds the search set (held
+        rows + imports in ascending global id), runs the owned queries and checks the k-th neighbours against the
+        margin; returns whether the check failed (the margin must grow)."""
+        self.searches += 1
+        dev, n, k, rank = self.device, self.n_held, self.k, self.rank
+        rows = torch.cat([self.recent, imports.to(dev)]) if imports.shape[0] else self.recent
+        held_by = torch.full((n,), rank, dtype=torch.int32, device=dev)
+        if imports.shape[0]:
+            came = torch.repeat_interleave(torch.arange(self.world, dtype=torch.int32, device=dev),
+                                           torch.tensor(list(recv_counts), device=dev))
+            held_by = torch.cat([held_by, came])
+        sub_ids, perm = torch.sort(rows[:, 3].contiguous().view(torch.int32).long())
+        pos_sub = rows[perm, :3].contiguous()
+        owner_sub = held_by[perm]
+        n_sub = pos_sub.shape[0]
+        if n_sub > self.n_total or (n_sub > 1 and bool((sub_ids[1:] == sub_ids[:-1]).any())):
+            raise CgnnError(f"migrating rollout: rank {rank}'s search set holds a particle twice")
+        whole = n_sub == self.n_total
+        knn = lambda q: ops.knn_periodic(pos_sub, self.box, k, query_ids=q, want_edge_attr=True, want_order=True,   # noqa: E731
+                                         grid=self.knn_grid)
+        owned_s = torch.nonzero(owner_sub == rank).squeeze(1)
+        failed = False
+        if n:
+            if n_sub < k:
+                raise CgnnError(f"migrating rollout: rank {rank} searches {n_sub} particles for {k} neighbours")
+            _, _, order = knn(owned_s[:1].to(torch.int32))
+            if order is not None:
+                order = order.long()
+                owned_s = order[owner_sub[order] == rank]
+            senders_s, edge_attr, _ = knn(owned_s.to(torch.int32))
+            if not whole:
+                kth = senders_s.view(-1, k)[:, k - 1].long()
+                dlt = torch.abs(pos_sub[kth] - pos_sub[owned_s])
+                dlt = torch.minimum(dlt, self.box - dlt)
+                failed = float(dlt.norm(dim=1).max()) > self.margin
+        else:
+            senders_s = torch.empty(0, dtype=torch.int32, device=dev)
+            edge_attr = torch.empty((0, 4), dtype=torch.float32, device=dev)
+        inv = torch.empty(n_sub, dtype=torch.int64, device=dev)
+        inv[perm] = torch.arange(n_sub, device=dev)
+        self._found = (owned_s, senders_s, edge_attr, owner_sub, sub_ids, inv[:n])
+        return failed
+
+    # -- 4-5: numbering, features, forward -----------------------------------------------------------------------------
+    def number(self) -> Shard:
+        """The step's :class:`Shard` (no send plan yet) from the last :meth:`search`."""
+        owned_s, senders_s, edge_attr, owner_sub, sub_ids, held_s = self._found
+        self._found = None
+        n = self.n_held
+        sh = subset_shard(self.rank, self.world, self.k, owned_s, senders_s, edge_attr, owner_sub, sub_ids)
+        self._pred_row = sh._s2l[held_s].contiguous()           # storage row -> local row (its prediction)
+        sh._rows = torch.empty(n, dtype=torch.int32, device=self.device)
+        sh._rows[self._pred_row.long()] = torch.arange(n, dtype=torch.int32, device=self.device)   # local -> storage
+        sh._sub_ids = sub_ids
+        sh.searches, sh.subset_rows = self.searches, sub_ids.numel()
+        return sh
+
+    def features(self, sh: Shard) -> torch.Tensor:
+        sh.x_feat, _ = ops.history_features(self.hist, self.n_held, self.phase, self.meta, self.dt, self.box,
+                                            rows=sh._rows)
+        return sh.x_feat
+
+    def forward(self, sh: Shard, halo: Optional[Callable] = None) -> ShardedForward:
+        return ShardedForward(self.model, sh, halo)
+
+    # -- 6-7: advance, migrate -------------------------------------------------------------------------------------------
+    def advance(self, pred: dict) -> List[int]:
+        """Integrates the held rows, writes the new frame into the ring and records it; returns the rows leaving for
+        every rank (0 for this one).  One read-back (the counts)."""
+        record, dest, block_counts, counts = ops.rollout_advance(
+            self.hist, self.n_held, self.phase, self.ids, pred["acceleration"], pred["temp_rate"], self.meta, self.grid,
+            None if self.planes is None else self.planes.tensors(), pred_row=self._pred_row, stats=self.stats)
+        self.frames.append(record)
+        send_counts = counts.tolist()
+        self._moving = (dest, block_counts, send_counts[self.rank])
+        send_counts[self.rank] = 0
+        self.send_counts = send_counts
+        return send_counts
+
+    def migrate_out(self, n_arriving: int) -> torch.Tensor:
+        """Stayers into the second ring (sized for the ``n_arriving`` rows to come); returns the leavers ``[S, W + 1, 4]``
+        grouped by destination, storage order inside a group."""
+        dest, block_counts, n_stay = self._moving
+        need = n_stay + int(n_arriving)
+        if self._spare is None or self._spare[0].shape[1] < need:
+            self._spare = self._ring(need)
+        starts, run = [], 0
+        for p, c in enumerate(self.send_counts):
+            starts.append(0 if p == self.rank else run)
+            run += c
+        offsets = ops.group_offsets(block_counts, torch.tensor(starts, dtype=torch.int64, device=self.device))
+        return ops.migrate_pack(self.hist, self.n_held, self.ids, dest, self.rank, offsets, self._spare[0],
+                                self._spare[1], run)
+
+    def receive(self, arrivals: torch.Tensor) -> int:
+        """Appends the arrivals behind the stayers and makes the second ring the current one; returns the held count."""
+        n_stay = self._moving[2]
+        arrivals = arrivals.to(self.device)
+        ops.migrate_unpack(arrivals, self._spare[0], self._spare[1], n_stay)
+        (self.hist, self.ids), self._spare = self._spare, (self.hist, self.ids)
+        self.n_held = n_stay + arrivals.shape[0]
+        self.arrivals.append(arrivals.shape[0])
+        self._moving = None
+        self.t += 1
+        return self.n_held
+
+    def check_total(self, held_by_all: int) -> None:
+        if int(held_by_all) != self.n_total:
+            raise CgnnError(f"migrating rollout: after frame {self.t - 1} the ranks hold {int(held_by_all)} particles, not "
+                            f"{self.n_total}: a migration lost or duplicated rows")
+
+    def result(self) -> dict:
+        return {"frames": self.frames, "n_total": self.n_total, "world": self.world, "rank": self.rank}
+
+
+def exchange_counts(send_counts: Sequence[int], device, group=None) -> List[int]:
+    """All-to-all of one count per peer: what every peer is about to send this rank."""
+    import torch.distributed as dist
+    out = torch.tensor(list(send_counts), dtype=torch.int64, device=device)
+    return _collective(dist.all_to_all_single, torch.empty_like(out), out, group=group)().tolist()
+
+
+def exchange_rows(rows: torch.Tensor, send_counts: Sequence[int], recv_counts: Sequence[int], group=None) -> torch.Tensor:
+    """All-to-all-v of row blocks grouped by peer (split along dim 0)."""
+    import torch.distributed as dist
+    recv = torch.empty((int(sum(recv_counts)),) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    return _collective(dist.all_to_all_single, recv, rows.contiguous(), output_split_sizes=list(recv_counts),
+                       input_split_sizes=list(send_counts), group=group)()
+
+
+def _owned_rollout(model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int, num_neighbors: int,
+                   num_steps: Optional[int], device, group, decomposition: str, knn_grid: str) -> dict:
+    """``sharded_rollout(storage="owned")``: start-up slices the full initial window by the initial owner (the only place
+    that touches N), then every step runs on the rank's rows."""
+    import torch.distributed as dist
+    coords, energy, total = rollout_arguments(data, window_size, num_neighbors, num_steps)
+    world, rank = _world_of(group)
+    distributed = dist.is_available() and dist.is_initialized()
+    W, n_total = window_size, coords.shape[1]
+    meta = dict(metadata)
+    meta["dt"], meta["box_size"] = dt, box_size
+    if distributed:
+        check_same_data(coords[:W], energy[:W], device, group)
+    _, recent = ops.window_features(coords[W - 2:W].to(device).float(), energy[W - 2:W].to(device).float(), meta, dt,
+                                    box_size)
+    planes = balanced_planes(recent, box_size, world) if decomposition == "balanced" else None
+    own = torch.nonzero(owner_of(recent, box_size, world, planes) == rank).squeeze(1)
+    del recent
+    at = own.to(coords.device)
+    runner = MigratingRollout(model, own, coords[:W, at], energy[:W, at], n_total=n_total, metadata=metadata, dt=dt,
+                              box_size=box_size, window_size=W, num_neighbors=num_neighbors, num_steps=total - W,
+                              device=device, world=world, rank=rank, planes=planes, knn_grid=knn_grid)
+    nobody = torch.empty((0, 4), dtype=torch.float32, device=device)
+    for _ in range(W, total):
+        runner.begin()
+        while True:
+            rows, send_counts = runner.halo_out()
+            if distributed:
+                recv_counts = exchange_counts(send_counts, device, group)
+                failed = runner.search(exchange_rows(rows, send_counts, recv_counts, group), recv_counts)
+                flag = torch.tensor([1 if failed else 0], dtype=torch.int32, device=device)
+                failed = bool(_all_reduce_max_(flag, group)[0])
+            else:
+                failed = runner.search(nobody, [0])
+            if not failed:
+                break
+            runner.widen()
+        sh = runner.number()
+        if distributed:
+            sh = exchange_requests(sh, group, finish_shard_by_search)
+            halo = HaloExchange(sh, group)
+        else:
+            sh = finish_shard_by_search(sh, sh.want_global)
+            halo = lambda table: None      # noqa: E731  (a world of one has no ghosts)
+        runner.features(sh)
+        pred = runner.forward(sh, halo)()
+        send_counts = runner.advance(pred)
+        if distributed:
+            recv_counts = exchange_counts(send_counts, device, group)
+            leavers = runner.migrate_out(sum(recv_counts))
+            held = runner.receive(exchange_rows(leavers, send_counts, recv_counts, group))
+            held = int(_all_reduce_(torch.tensor([held], dtype=torch.int64, device=device), group)[0])
+        else:
+            leavers = runner.migrate_out(0)
+            held = runner.receive(leavers[:0])
+        runner.check_total(held)
+    return runner.result()
+
+
+def assemble_frames(results: Sequence[dict], n_total: int) -> dict:
+    """The ranks' ``storage="owned"`` results -> ``{"Coordinates" [T, N, 3], "InternalEnergy" [T, N, 1]}`` on the first
+    result's device (``cgnn_frame_unpack``); rows no rank delivered stay NaN.  For tests and small runs: it holds the
+    whole trajectory."""
+    frames = [r["frames"] for r in results]
+    T = len(frames[0])
+    if any(len(f) != T for f in frames):
+        raise ValueError("assemble_frames: the ranks recorded different numbers of frames")
+    dev = frames[0][0].device
+    pos = torch.full((T, n_total, 3), float("nan"), dtype=torch.float32, device=dev)
+    tmp = torch.full((T, n_total, 1), float("nan"), dtype=torch.float32, device=dev)
+    for t in range(T):
+        for f in frames:
+            if f[t].shape[0]:
+                ops.frame_unpack(f[t].to(dev), pos[t], tmp[t])
+    return {"Coordinates": pos, "InternalEnergy": tmp}
+
+
+def owned_frame_errors(result: dict, ground_truth: dict, group=None) -> dict:
+    """``rollout.calculate_errors`` of a ``storage="owned"`` rollout without assembling it: per frame, float64 partial
+    sums of the squared errors over the rows this rank recorded (the ground truth ``[T, N, 3]`` / ``[T, N(, 1)]`` is
+    read at those ids), ONE all-reduce of all partial sums, then the means over N."""
+    import torch.distributed as dist
+    frames, n = result["frames"], int(result["n_total"])
+    tc, tt = ground_truth["Coordinates"], ground_truth["InternalEnergy"]
+    count = min(len(frames), len(tc), len(tt))
+    dev = frames[0].device if frames else torch.device("cpu")
+    sums = torch.zeros(2 * count, dtype=torch.float64, device=dev)
+    for t in range(count):
+        rows = frames[t]
+        ids = rows[:, 4].contiguous().view(torch.int32).long()
+        at = ids.to(tc.device)
+        sums[t] = ((rows[:, :3].double() - tc[t][at].to(dev).double()) ** 2).sum()
+        sums[count + t] = ((rows[:, 3].double() - tt[t].reshape(-1)[at.to(tt.device)].to(dev).double()) ** 2).sum()
+    if dist.is_available() and dist.is_initialized():
+        _all_reduce_(sums, group)
+    pos = (sums[:count] / (3.0 * n)).tolist()
+    tmp = (sums[count:] / float(n)).tolist()
+    return {"position_errors": pos, "temperature_errors": tmp,
+            "mean_position_error": sum(pos) / len(pos) if pos else None,
+            "mean_temperature_error": sum(tmp) / len(tmp) if tmp else None}
 
 
 # ----------------------------------------------------------------------------

@@ -884,6 +884,215 @@ def frame_unpack(rows: torch.Tensor, pos: torch.Tensor, temp: torch.Tensor) -> N
                                             stream_ptr(pos.device)), "cgnn_frame_unpack")
 
 
+# ---- sharded rollout with particle migration (csrc/migrate.hip): a rank's step on its own rows --------------------------
+
+def migrate_blocks(n: int) -> int:
+    """Workgroups (rows of ``block_counts`` / ``offsets``) of a migration kernel over ``n`` rows."""
+    return (int(n) + _lib.MIGRATE_BLOCK - 1) // _lib.MIGRATE_BLOCK
+
+
+def _ring(hist: torch.Tensor, n_held: int, what: str) -> Tuple[int, int]:
+    """``(W, cap)`` of a history ring ``[W, cap, 4]`` (contiguous float32 on the device, used in place)."""
+    require_device(hist, "hist")
+    if hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 3 or hist.shape[2] != 4:
+        raise CgnnError(f"{what}: the history ring must be contiguous float32 [W, cap, 4], got {tuple(hist.shape)} "
+                        f"{hist.dtype}")
+    w, cap = hist.shape[0], hist.shape[1]
+    if not 0 <= n_held <= cap:
+        raise CgnnError(f"{what}: {n_held} held rows in a ring of capacity {cap}")
+    return w, cap
+
+
+def _i32_ids(t: torch.Tensor, n: int, name: str, what: str) -> torch.Tensor:
+    require_device(t, name)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1 or t.numel() < n:
+        raise CgnnError(f"{what}: {name} must be contiguous int32 [>= {n}], got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def group_offsets(block_counts: torch.Tensor, starts: torch.Tensor) -> torch.Tensor:
+    """``offsets int32 [blocks, world]`` of the pack kernels: ``starts[p]`` (where group p begins in the output) plus the
+    rows of group p in earlier workgroups (an exclusive prefix sum down ``block_counts [blocks, world]``)."""
+    per_group = block_counts.t().contiguous()          # [world, blocks]: torch scans an inner dimension far faster
+    run = torch.cumsum(per_group, dim=1, dtype=torch.int32)
+    run -= per_group
+    run += starts.to(torch.int32).unsqueeze(1)
+    return run.t().contiguous()
+
+
+def history_features(hist: torch.Tensor, n_held: int, phase: int, metadata: dict, dt: float, box_size: float,
+                     rows: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, want_x: bool = True,
+                     want_recent: bool = False):
+    """``(x [R, 4W-3] | None, recent [R, 4] | None)`` of ring rows ``rows`` (int32; all ``n_held`` rows in storage order
+    when omitted) of the ring ``hist [W, cap, 4]`` whose oldest frame sits in slot ``phase`` (``cgnn_history_features``):
+    the bits of :func:`window_features_rows` on the same frames.  ``recent`` rows are (wrapped last position, id bits of
+    ``ids`` int32 ``[cap]``)."""
+    what = "history_features"
+    w, cap = _ring(hist, n_held, what)
+    dev = hist.device
+    if rows is not None:
+        rows = _i32_ids(rows, 0, "rows", what)
+    nr = n_held if rows is None else rows.numel()
+    if ids is not None:
+        ids = _i32_ids(ids, n_held, "ids", what)
+    x = torch.empty((nr, 3 * (w - 1) + w), dtype=torch.float32, device=dev) if want_x else None
+    recent = torch.empty((nr, 4), dtype=torch.float32, device=dev) if want_recent else None
+    _same_device(hist, rows, ids)
+    if nr == 0 or (x is None and recent is None):
+        return x, recent
+    with _timed(what, dev):
+        check(_lib.load().cgnn_history_features(
+            hist.data_ptr(), w, cap, n_held, int(phase), ptr(rows), nr, ptr(ids), float(box_size), float(dt),
+            _scalar_stat(metadata, "vel_mean", what), _scalar_stat(metadata, "vel_std", what),
+            _scalar_stat(metadata, "temp_mean", what), _scalar_stat(metadata, "temp_std", what), ptr(x), ptr(recent),
+            stream_ptr(dev)), "cgnn_history_features")
+    return x, recent
+
+
+def rollout_advance(hist: torch.Tensor, n_held: int, phase: int, ids: torch.Tensor, acc_pred: torch.Tensor,
+                    temp_rate_pred: torch.Tensor, metadata: dict, grid: Sequence[int],
+                    planes: Optional[Sequence[torch.Tensor]] = None, pred_row: Optional[torch.Tensor] = None, stats=None):
+    """One rollout step of the ``n_held`` ring rows, in place (``cgnn_rollout_advance``): :func:`rollout_integrate`'s
+    arithmetic on the two newest ring frames, the new frame written into slot ``phase``.  Predictions row
+    ``pred_row[i]`` (int32; i when omitted) belongs to ring row i.  Returns ``(record [n_held, ROLLOUT_ROW], dest int32
+    [n_held], block_counts int32 [blocks, world], counts int32 [world])``: the packed frame rows, the tile of every new
+    position on the tile grid ``grid`` (equal volume, or cut at ``planes``), and the rows per destination."""
+    what = "rollout_advance"
+    w, cap = _ring(hist, n_held, what)
+    dev = hist.device
+    px, py, pz = (int(g) for g in grid)
+    world = px * py * pz
+    if min(px, py, pz) < 1 or world > _lib.MIGRATE_MAX_WORLD:
+        raise CgnnError(f"{what}: a tile grid of {(px, py, pz)} (at most {_lib.MIGRATE_MAX_WORLD} tiles)")
+    ids = _i32_ids(ids, n_held, "ids", what)
+    acc_pred, temp_rate_pred = f32c(acc_pred, "acc_pred"), f32c(temp_rate_pred, "temp_rate_pred")
+    n_pred = acc_pred.shape[0]
+    if acc_pred.shape != (n_pred, 3) or temp_rate_pred.numel() != n_pred or (pred_row is None and n_pred != n_held):
+        raise CgnnError(f"{what}: predictions {tuple(acc_pred.shape)} / {tuple(temp_rate_pred.shape)} for {n_held} rows")
+    if pred_row is not None:
+        pred_row = _i32_ids(pred_row, n_held, "pred_row", what)
+    cx = cy = cz = None
+    if planes is not None:
+        cx, cy, cz = (f32c(c, "planes") for c in planes)
+        if cx.numel() != px - 1 or cy.shape != (px, py - 1) or cz.shape != (px, py, pz - 1):
+            raise CgnnError(f"{what}: planes of shapes {tuple(cx.shape)}, {tuple(cy.shape)}, {tuple(cz.shape)} are not "
+                            f"those of the tile grid {(px, py, pz)}")
+    if stats is None:
+        stats = integration_stats(metadata)
+    record = torch.empty((n_held, _lib.ROLLOUT_ROW), dtype=torch.float32, device=dev)
+    dest = torch.empty(n_held, dtype=torch.int32, device=dev)
+    block_counts = torch.empty((migrate_blocks(n_held), world), dtype=torch.int32, device=dev)
+    counts = torch.empty(world, dtype=torch.int32, device=dev)
+    _same_device(hist, ids, acc_pred, temp_rate_pred, pred_row, cx, cy, cz)
+    with _timed(what, dev):
+        check(_lib.load().cgnn_rollout_advance(
+            hist.data_ptr(), w, cap, n_held, int(phase), ids.data_ptr(), ptr(pred_row), acc_pred.data_ptr(),
+            temp_rate_pred.data_ptr(), n_pred, stats, float(metadata["dt"]), float(metadata["box_size"]), px, py, pz,
+            0 if planes is None else 1, ptr(cx), ptr(cy), ptr(cz), record.data_ptr(), dest.data_ptr(),
+            block_counts.data_ptr(), counts.data_ptr(), stream_ptr(dev)), "cgnn_rollout_advance")
+    return record, dest, block_counts, counts
+
+
+def tile_boxes(lo: Sequence[Sequence[float]], hi: Sequence[Sequence[float]]):
+    """The host arrays :func:`halo_select` takes: every tile's ``lo [3]`` / ``hi [3]``, rank by rank."""
+    if len(lo) != len(hi) or any(len(v) != 3 for v in list(lo) + list(hi)):
+        raise CgnnError("tile_boxes: lo [world][3] and hi [world][3]")
+    flat_lo = [float(v) for box in lo for v in box]
+    flat_hi = [float(v) for box in hi for v in box]
+    return (C.c_double * len(flat_lo))(*flat_lo), (C.c_double * len(flat_hi))(*flat_hi), len(lo)
+
+
+def halo_select(recent: torch.Tensor, rank: int, boxes, margin: float, box_size: float):
+    """``(mask int64 [n], block_counts int32 [blocks, world], counts int32 [world])`` (``cgnn_halo_select``): bit p of
+    ``mask[i]`` says that row i of ``recent [n, 4]`` lies within ``margin`` of peer p's tile (``boxes``:
+    :func:`tile_boxes`), by ``dist._near_tile``'s arithmetic; the rank's own bit is never set."""
+    what = "halo_select"
+    recent = f32c(recent, "recent")
+    if recent.dim() != 2 or recent.shape[1] != 4:
+        raise CgnnError(f"{what}: recent must be [n, 4], got {tuple(recent.shape)}")
+    lo_c, hi_c, world = boxes
+    if world > _lib.MIGRATE_MAX_WORLD or not 0 <= rank < world:
+        raise CgnnError(f"{what}: rank {rank} of {world} tiles (at most {_lib.MIGRATE_MAX_WORLD})")
+    n, dev = recent.shape[0], recent.device
+    mask = torch.empty(n, dtype=torch.int64, device=dev)
+    block_counts = torch.empty((migrate_blocks(n), world), dtype=torch.int32, device=dev)
+    counts = torch.empty(world, dtype=torch.int32, device=dev)
+    with _timed(what, dev):
+        check(_lib.load().cgnn_halo_select(recent.data_ptr(), n, world, int(rank), lo_c, hi_c, float(margin),
+                                           float(box_size), mask.data_ptr(), block_counts.data_ptr(), counts.data_ptr(),
+                                           stream_ptr(dev)), "cgnn_halo_select")
+    return mask, block_counts, counts
+
+
+def halo_pack(recent: torch.Tensor, mask: torch.Tensor, offsets: torch.Tensor, n_out: int) -> torch.Tensor:
+    """``[n_out, 4]``: the rows of ``recent`` grouped by the peers of their ``mask`` bits, storage order inside a group
+    (``cgnn_halo_pack``); ``offsets``: :func:`group_offsets` of :func:`halo_select`'s block counts."""
+    what = "halo_pack"
+    recent = f32c(recent, "recent")
+    n, dev = recent.shape[0], recent.device
+    require_device(mask, "mask")
+    require_device(offsets, "offsets")
+    if recent.dim() != 2 or recent.shape[1] != 4 or mask.dtype != torch.int64 or mask.shape != (n,) or \
+            not mask.is_contiguous() or offsets.dtype != torch.int32 or not offsets.is_contiguous() or \
+            offsets.dim() != 2 or offsets.shape[0] != migrate_blocks(n):
+        raise CgnnError(f"{what}: recent [n, 4], mask int64 [n], offsets int32 [blocks, world], got "
+                        f"{tuple(recent.shape)}, {tuple(mask.shape)} {mask.dtype}, {tuple(offsets.shape)} {offsets.dtype}")
+    out = torch.empty((int(n_out), 4), dtype=torch.float32, device=dev)
+    _same_device(recent, mask, offsets)
+    if n == 0 or n_out == 0:
+        return out
+    with _timed(what, dev):
+        check(_lib.load().cgnn_halo_pack(recent.data_ptr(), mask.data_ptr(), n, offsets.shape[1], offsets.data_ptr(),
+                                         int(n_out), out.data_ptr(), stream_ptr(dev)), "cgnn_halo_pack")
+    return out
+
+
+def migrate_pack(hist: torch.Tensor, n_held: int, ids: torch.Tensor, dest: torch.Tensor, rank: int,
+                 offsets: torch.Tensor, hist_out: torch.Tensor, ids_out: torch.Tensor, n_send: int) -> torch.Tensor:
+    """Rows with ``dest == rank`` go to the second ring ``hist_out`` / ``ids_out``, the others into the returned send
+    buffer ``[n_send, W + 1, 4]`` (id bits, then the W ring slots), each at its group position (``offsets``:
+    :func:`group_offsets` of :func:`rollout_advance`'s block counts) (``cgnn_migrate_pack``)."""
+    what = "migrate_pack"
+    w, cap = _ring(hist, n_held, what)
+    w2, cap_out = _ring(hist_out, 0, what)
+    dev = hist.device
+    ids, dest = _i32_ids(ids, n_held, "ids", what), _i32_ids(dest, n_held, "dest", what)
+    ids_out = _i32_ids(ids_out, cap_out, "ids_out", what)
+    require_device(offsets, "offsets")
+    if w2 != w or hist_out.data_ptr() == hist.data_ptr() or offsets.dtype != torch.int32 or not offsets.is_contiguous() \
+            or offsets.dim() != 2 or offsets.shape[0] != migrate_blocks(n_held):
+        raise CgnnError(f"{what}: a second ring of the same window and offsets int32 [blocks, world] are needed")
+    world = offsets.shape[1]
+    send = torch.empty((int(n_send), w + 1, 4), dtype=torch.float32, device=dev)
+    _same_device(hist, ids, dest, offsets, hist_out, ids_out)
+    if n_held == 0:
+        return send
+    with _timed(what, dev):
+        check(_lib.load().cgnn_migrate_pack(hist.data_ptr(), w, cap, n_held, ids.data_ptr(), dest.data_ptr(), world,
+                                            int(rank), offsets.data_ptr(), hist_out.data_ptr(), cap_out,
+                                            ids_out.data_ptr(), send.data_ptr(), int(n_send), stream_ptr(dev)),
+              "cgnn_migrate_pack")
+    return send
+
+
+def migrate_unpack(recv: torch.Tensor, hist_out: torch.Tensor, ids_out: torch.Tensor, first: int) -> None:
+    """The arrivals ``recv [R, W + 1, 4]`` become ring rows ``first .. first + R - 1`` of ``hist_out`` / ``ids_out``
+    (``cgnn_migrate_unpack``)."""
+    what = "migrate_unpack"
+    w, cap_out = _ring(hist_out, 0, what)
+    recv = f32c(recv, "recv")
+    if recv.dim() != 3 or recv.shape[1:] != (w + 1, 4) or first < 0 or first + recv.shape[0] > cap_out:
+        raise CgnnError(f"{what}: arrivals {tuple(recv.shape)} behind {first} rows do not fit a ring of window {w}, "
+                        f"capacity {cap_out}")
+    ids_out = _i32_ids(ids_out, cap_out, "ids_out", what)
+    _same_device(recv, hist_out, ids_out)
+    if recv.shape[0] == 0:
+        return
+    with _timed(what, hist_out.device):
+        check(_lib.load().cgnn_migrate_unpack(recv.data_ptr(), recv.shape[0], w, hist_out.data_ptr(), cap_out, int(first),
+                                              ids_out.data_ptr(), stream_ptr(hist_out.device)), "cgnn_migrate_unpack")
+
+
 def segment_colsum(acc: torch.Tensor, batch: Optional[torch.Tensor], num_graphs: int) -> torch.Tensor:
     acc = f32c(acc, "acc")
     if batch is not None:

@@ -572,6 +572,67 @@ int cgnn_tile_classify(const float* pos, int64_t n, int32_t px, int32_t py, int3
                        const float* planes_y, const float* planes_z, int32_t rank, const double* lo, const double* hi,
                        double margin, double box_size, int32_t* owner, int64_t* counts, uint8_t* mask, void* stream);
 
+/* ---- sharded rollout with particle migration (dist.MigratingRollout): a rank's step on its own rows only -----------
+ * A rank keeps the window histories of the n_held particles it holds in a frame-major ring hist [window, cap] of
+ * float4 (x, y, z, temperature), 16-byte aligned: frame f lives in slot f mod window, so at step t the oldest frame,
+ * and the slot the new frame is written to, is phase = t mod window on every rank; ids int32 [cap] are the global ids.
+ * window in [2, 32], world <= 64 (a row's peer mask is one 64-bit word).  One thread per row, workgroups of
+ * CGNN_MIGRATE_BLOCK rows: row i belongs to block i / CGNN_MIGRATE_BLOCK.  Placement into groups (peers, destinations)
+ * is deterministic: block_counts int32 [blocks, world] (written whole, plain stores) holds every block's rows per
+ * group, the caller turns it into offsets int32 [blocks, world] = (start of group p in the output) + (rows of group p
+ * in earlier blocks), and a row lands at offsets[block, p] + its rank among the block's rows of group p (ascending
+ * row index).  counts int32 [world] (zeroed by the call) are the totals, by integer atomics.  Every entry validates
+ * its arguments and launches nothing on error.
+ *
+ * cgnn_history_features: for i in [0, n_rows), ring row r = rows[i] (i when rows is NULL; then n_rows == n_held):
+ *   x [n_rows, 4 window - 3]   the bits cgnn_window_features_rows gives on the [window, n, 3] window of the same
+ *                              frames, oldest first (the same device function); may be NULL
+ *   recent [n_rows, 4]         (wrapped last position, int32 bits of ids[r], or of 0 when ids is NULL); may be NULL
+ *   rows outside [0, n_held) are skipped.
+ *
+ * cgnn_rollout_advance: cgnn_rollout_integrate's arithmetic (no contraction, the float32 reciprocal of dt) for every
+ * held row i, with p1 / p2 / T1 the two newest ring frames and the predictions of row pred_row[i] (i when NULL) of
+ * acc_pred [n_pred, 3] / temp_rate_pred [n_pred]; stats as there (HOST memory, 8 floats).  Writes the new float4 into
+ * slot phase, record [n_held, CGNN_ROLLOUT_ROW] (the packed row), dest int32 [n_held] = the tile of the new position
+ * and block_counts / counts over dest.  The tile: use_planes == 0: per axis floor(v * float(1 / box_size) * parts)
+ * clamped to [0, parts - 1] (dist.owner_of's float32 expression); else #{ j : c_j <= v } nested x -> y -> z over
+ * planes_x [px-1], planes_y [px, py-1], planes_z [px, py, pz-1] as cgnn_tile_classify counts them.
+ *
+ * cgnn_halo_select: bit p of mask uint64 [n] is set when p != rank and recent [n, 4] row i lies within margin of the
+ * box [lo[3p..], hi[3p..]) (HOST memory, 3 world doubles each) on every axis, periodic: cgnn_tile_classify's mask
+ * arithmetic per tile (one test per tile, not per periodic image; an axis with (hi - lo) + 2 margin >= box_size
+ * counts as covered).  block_counts / counts over the set bits.
+ *
+ * cgnn_halo_pack: out [n_out, 4] row offsets[block, p] + rank = recent row i, for every set bit p of mask[i]
+ * (storage order inside a peer's block; positions outside [0, n_out) are skipped).
+ *
+ * cgnn_migrate_pack: row i with dest[i] == rank goes to the second ring hist_out [window, cap_out] / ids_out (all
+ * window slots, same slots) at its group position; any other row to send [n_send, window + 1, 4] at its group
+ * position: (id bits, 0, 0, 0) then the window ring slots in slot order.  hist_out must not be hist.
+ *
+ * cgnn_migrate_unpack: recv [n_recv, window + 1, 4] rows (as packed above) become ring rows first .. first + n_recv - 1
+ * of hist_out / ids_out; first + n_recv <= cap_out. */
+#define CGNN_MIGRATE_BLOCK 256
+int cgnn_history_features(const float* hist, int32_t window, int64_t cap, int64_t n_held, int32_t phase,
+                          const int32_t* rows, int64_t n_rows, const int32_t* ids, float box_size, float dt,
+                          float vel_mean, float vel_std, float temp_mean, float temp_std, float* x, float* recent,
+                          void* stream);
+int cgnn_rollout_advance(float* hist, int32_t window, int64_t cap, int64_t n_held, int32_t phase, const int32_t* ids,
+                         const int32_t* pred_row, const float* acc_pred, const float* temp_rate_pred, int64_t n_pred,
+                         const float* stats, float dt, float box_size, int32_t px, int32_t py, int32_t pz,
+                         int32_t use_planes, const float* planes_x, const float* planes_y, const float* planes_z,
+                         float* record, int32_t* dest, int32_t* block_counts, int32_t* counts, void* stream);
+int cgnn_halo_select(const float* recent, int64_t n, int32_t world, int32_t rank, const double* lo, const double* hi,
+                     double margin, double box_size, uint64_t* mask, int32_t* block_counts, int32_t* counts,
+                     void* stream);
+int cgnn_halo_pack(const float* recent, const uint64_t* mask, int64_t n, int32_t world, const int32_t* offsets,
+                   int64_t n_out, float* out, void* stream);
+int cgnn_migrate_pack(const float* hist, int32_t window, int64_t cap, int64_t n_held, const int32_t* ids,
+                      const int32_t* dest, int32_t world, int32_t rank, const int32_t* offsets, float* hist_out,
+                      int64_t cap_out, int32_t* ids_out, float* send, int64_t n_send, void* stream);
+int cgnn_migrate_unpack(const float* recv, int64_t n_recv, int32_t window, float* hist_out, int64_t cap_out,
+                        int64_t first, int32_t* ids_out, void* stream);
+
 /* ---- K11: momentum-conservation term ------------------------------------------
  * sums[g, c] = sum_{i: batch[i]==g} acc[i, c] in float64 (batch sorted ascending,
  * NULL = one graph); reference train.py:107-118.  sums is [num_graphs, width] f64,

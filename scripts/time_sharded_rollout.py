@@ -8,7 +8,16 @@ iterations.  The same step t is repeated (only this rank's rows are ever publish
 --clustered starts the window from synthetic.make_clustered_positions (half of the particles in one halo);
 --decomposition picks the tiling (dist.build_shard); --all-ranks runs every rank in turn and prints owned, ghosts,
 interior fraction, step time and peak memory per rank; --no-baselines leaves the two rollout.rollout runs out;
---knn-grid picks the cell grid of every neighbour search (ops.KNN_GRIDS)."""
+--knn-grid picks the cell grid of every neighbour search (ops.KNN_GRIDS).
+    python scripts/time_sharded_rollout.py --storage owned
+--storage owned times the same rank's step of dist.MigratingRollout (storage="owned": the rank holds only its tile) next
+to the replicated step, in one process, alternating replicated / owned / replicated per iteration after a warm-up of
+each: the two replicated medians show the spread of the box.  The owned step gets the halo rows its peers would send
+(cut from the global frame outside the timed region) and sends its leavers nowhere; a fresh runner per iteration
+repeats the same step.  Same split: graph and plan, features, forward, advance + record + migration packing.  Also
+prints each mode's peak memory above the resident model for one step.  --owned-only runs the owned steps alone (for a
+kernel trace of that path: rocprofv3 --kernel-trace --stats -- python scripts/time_sharded_rollout.py --storage owned
+--owned-only)."""
 import argparse
 import os
 import statistics
@@ -34,6 +43,8 @@ ap.add_argument("--knn-grid", choices=ops.KNN_GRIDS, default="uniform")
 ap.add_argument("--clustered", action="store_true")
 ap.add_argument("--all-ranks", action="store_true")
 ap.add_argument("--no-baselines", action="store_true")
+ap.add_argument("--storage", choices=cdist.ROLLOUT_STORAGE, default="replicated")
+ap.add_argument("--owned-only", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda")
 W, dt, box = 6, 0.01, 1.0
@@ -66,36 +77,154 @@ class NoExchange:
         return None
 
 
-def sharded_step_ms(data, rank):
-    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition, knn_grid=a.knn_grid)
+PARTS = ("graph", "features", "forward", "integrate+unpack")
+
+
+def replicated_step(rn):
+    """One step of ``rn`` (dist.ShardedRollout) at t = W: ``({part: ms}, shard)``."""
     t = W
-    parts = {"graph": [], "features": [], "forward": [], "integrate+unpack": []}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     with torch.no_grad():
-        for it in range(a.iters + 1):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            sh = rn.plan(t)
-            sh.send_idx = torch.empty(0, dtype=torch.int32, device=dev)       # no peers: nothing to pack
-            sh.send_counts = [0] * a.world
-            torch.cuda.synchronize()
-            graph_ms = (time.perf_counter() - t0) * 1e3
-            ev[0].record()
-            rn.features(sh, t)
-            ev[1].record()
-            pred = rn.forward(sh, NoExchange())()
-            ev[2].record()
-            rn.publish(rn.integrate(sh, pred, t), t)
-            ev[3].record()
-            torch.cuda.synchronize()
-            if it == 0:
-                continue                                                      # weight packing, allocator warm-up
-            parts["graph"].append(graph_ms)
-            parts["features"].append(ev[0].elapsed_time(ev[1]))
-            parts["forward"].append(ev[1].elapsed_time(ev[2]))
-            parts["integrate+unpack"].append(ev[2].elapsed_time(ev[3]))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sh = rn.plan(t)
+        sh.send_idx = torch.empty(0, dtype=torch.int32, device=dev)       # no peers: nothing to pack
+        sh.send_counts = [0] * a.world
+        torch.cuda.synchronize()
+        graph_ms = (time.perf_counter() - t0) * 1e3
+        ev[0].record()
+        rn.features(sh, t)
+        ev[1].record()
+        pred = rn.forward(sh, NoExchange())()
+        ev[2].record()
+        rn.publish(rn.integrate(sh, pred, t), t)
+        ev[3].record()
+        torch.cuda.synchronize()
+    return dict(zip(PARTS, [graph_ms] + [ev[i].elapsed_time(ev[i + 1]) for i in range(3)])), sh
+
+
+def sharded_step_ms(data, rank):
+    rn = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition, knn_grid=a.knn_grid)
+    parts = {key: [] for key in PARTS}
+    for it in range(a.iters + 1):
+        got, sh = replicated_step(rn)
+        if it:                                                            # 0: weight packing, allocator warm-up
+            for key in PARTS:
+                parts[key].append(got[key])
     med = {key: statistics.median(v) for key, v in parts.items()}
     return med, sh, rn.cap
+
+
+# ---- storage="owned": the same rank's step of dist.MigratingRollout -------------------------------------------------
+def owned_inputs(data, rank):
+    """What rank ``rank`` starts from and what its peers would send it at t = W (made from the whole box, outside every
+    timed region): its slice of the window, the planes, and per margin the halo rows grouped by peer."""
+    coords, energy = data["Coordinates"], data["InternalEnergy"]
+    _, frame = ops.window_features(coords[W - 2:W].to(dev), energy[W - 2:W].to(dev), meta, dt, box)
+    planes = cdist.balanced_planes(frame, box, a.world) if a.decomposition == "balanced" else None
+    owner = cdist.owner_of(frame, box, a.world, planes)
+    ids = torch.nonzero(owner == rank).squeeze(1).cpu()
+    lo, hi = cdist.tile_bounds(box, a.world, rank, planes)
+
+    def imports(margin):
+        near = cdist._near_tile(frame, box, lo, hi, margin) & (owner != rank)
+        rows = torch.nonzero(near).squeeze(1)
+        rows = rows[torch.argsort(owner[rows].long() * frame.shape[0] + rows)]         # by peer, ascending id inside
+        block = torch.cat([frame[rows], torch.zeros(rows.numel(), 1, device=dev)], dim=1).contiguous()
+        block.view(torch.int32)[:, 3] = rows.to(torch.int32)
+        return block, torch.bincount(owner[rows].long(), minlength=a.world).tolist()
+
+    return {"ids": ids, "coords": coords[:, ids].contiguous(), "energy": energy[:, ids].contiguous(), "planes": planes,
+            "imports": imports, "n": coords.shape[1], "rank": rank, "halo": {}}
+
+
+def owned_step(inp):
+    """One step of a fresh dist.MigratingRollout at t = W, no exchange: ``({part: ms}, shard, runner)``."""
+    rn = cdist.MigratingRollout(m, inp["ids"], inp["coords"], inp["energy"], n_total=inp["n"], metadata=meta, dt=dt,
+                                box_size=box, window_size=W, num_neighbors=k, num_steps=1, device=dev, world=a.world,
+                                rank=inp["rank"], planes=inp["planes"], knn_grid=a.knn_grid)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    nothing = [torch.empty(0, dtype=torch.int64, device=dev)] * a.world
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0, setup = time.perf_counter(), 0.0
+        rn.begin()
+        while True:
+            rn.halo_out()                                                # select + pack for the peers (sent nowhere)
+            if rn.margin not in inp["halo"]:                             # the peers' rows: not this rank's work
+                torch.cuda.synchronize()
+                s0 = time.perf_counter()
+                inp["halo"][rn.margin] = inp["imports"](rn.margin)
+                torch.cuda.synchronize()
+                setup += time.perf_counter() - s0
+            if not rn.search(*inp["halo"][rn.margin]):
+                break
+            rn.widen()
+        sh = cdist.finish_shard_by_search(rn.number(), nothing)           # no peers: nothing to pack
+        torch.cuda.synchronize()
+        graph_ms = (time.perf_counter() - t0 - setup) * 1e3
+        ev[0].record()
+        rn.features(sh)
+        ev[1].record()
+        pred = rn.forward(sh, NoExchange())()
+        ev[2].record()
+        rn.advance(pred)
+        leavers = rn.migrate_out(0)
+        rn.receive(leavers[:0])                                           # nobody arrives
+        ev[3].record()
+        torch.cuda.synchronize()
+    return dict(zip(PARTS, [graph_ms] + [ev[i].elapsed_time(ev[i + 1]) for i in range(3)])), sh, rn
+
+
+def compare_storage(data, rank):
+    """Replicated / owned / replicated per iteration, after one warm-up step of each that also measures the peak memory."""
+    n_part = 4 * W - 3
+    inp = owned_inputs(data, rank)
+    if a.owned_only:
+        steps = [owned_step(inp)[0] for _ in range(a.iters + 1)][1:]
+        print("  owned: " + ", ".join(f"{key} {statistics.median(s[key] for s in steps):.2f} ms" for key in PARTS), flush=True)
+        return
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    rep = cdist.ShardedRollout(m, data, meta, dt, box, W, k, 1, dev, a.world, rank, a.decomposition, knn_grid=a.knn_grid)
+    _, sh = replicated_step(rep)
+    peak_rep = torch.cuda.max_memory_allocated() - base
+    held_rep = torch.cuda.memory_allocated() - base
+    shape_rep = rep.pos.numel() * 4 + rep.tmp.numel() * 4
+    print(f"  replicated: owned {sh.n_owned}, ghosts {sh.n_ghost}, searched {sh.subset_rows} rows in {sh.searches} round(s); "
+          f"persistent {shape_rep / 2 ** 20:.1f} MiB from shapes ([T, N, 4] floats, T = {rep.total_time}), "
+          f"{held_rep / 2 ** 20:.1f} MiB allocated after the step, peak {peak_rep / 2 ** 20:.1f} MiB above the resident model")
+    del sh
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    mid = torch.cuda.memory_allocated()
+    _, sh, rn = owned_step(inp)
+    peak_own = torch.cuda.max_memory_allocated() - mid
+    shape_own = rn.n_held * (16 * W + 4) + sum(20 * f.shape[0] for f in rn.frames)
+    rings = 2 * (rn.hist.numel() * 4 + rn.ids.numel() * 4)
+    print(f"  owned: holds {sh.n_owned}, ghosts {sh.n_ghost}, searched {sh.subset_rows} rows in {sh.searches} round(s), "
+          f"{sum(rn.send_counts)} leavers; persistent {shape_own / 2 ** 20:.1f} MiB from shapes (n (16 W + 4) + 20 n per "
+          f"frame, T = {rn.total_time}), two rings with head room {rings / 2 ** 20:.1f} MiB, peak {peak_own / 2 ** 20:.1f} "
+          f"MiB above the resident model and the replicated runner ({n_part} features)", flush=True)
+    del sh, rn
+    legs = {"replicated (1st)": [], "owned": [], "replicated (2nd)": []}
+    for _ in range(a.iters):
+        legs["replicated (1st)"].append(replicated_step(rep)[0])
+        legs["owned"].append(owned_step(inp)[0])
+        legs["replicated (2nd)"].append(replicated_step(rep)[0])
+    out = {}
+    for name, steps in legs.items():
+        med = {key: statistics.median(s[key] for s in steps) for key in PARTS}
+        rest = statistics.median(sum(s.values()) - s["forward"] for s in steps)
+        out[name] = rest
+        print(f"  {name}: " + ", ".join(f"{key} {v:.2f} ms" for key, v in med.items()) +
+              f"; total {sum(med.values()):.2f} ms, without the forward {rest:.2f} ms (median of {len(steps)})", flush=True)
+    spread = abs(out["replicated (1st)"] - out["replicated (2nd)"])
+    worst = max(out["replicated (1st)"], out["replicated (2nd)"])
+    print(f"  step without the forward: owned {out['owned']:.2f} ms against replicated {out['replicated (1st)']:.2f} / "
+          f"{out['replicated (2nd)']:.2f} ms (spread {spread:.2f} ms): "
+          f"{'not slower' if out['owned'] <= worst + spread else 'SLOWER'} by that spread; the exchanges: not measured")
 
 
 def rollout_step_ms(data):
@@ -115,6 +244,11 @@ def rollout_step_ms(data):
 data = window(a.particles, seed=1238)
 print(f"sharded rollout, k-NN grid {a.knn_grid}, {a.decomposition} tiles of a {'clustered' if a.clustered else 'uniform'} box, world {a.world}, "
       f"N={a.particles} k={k} latent={d} rounds={L} (bf16 edges, fp16x2 nodes), no exchange", flush=True)
+if a.storage == "owned":
+    for rank in (range(a.world) if a.all_ranks else [a.rank]):
+        print(f" rank {rank} of {a.world}:")
+        compare_storage(data, rank)
+    sys.exit(0)
 for rank in (range(a.world) if a.all_ranks else [a.rank]):
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats()
