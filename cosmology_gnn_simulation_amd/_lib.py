@@ -44,8 +44,9 @@ EXPORTS = (
     "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
     "cgnn_knn_adaptive_workspace_bytes", "cgnn_knn_periodic_adaptive", "cgnn_knn_adaptive_sorted_order",
     "cgnn_history_features", "cgnn_rollout_advance", "cgnn_halo_select", "cgnn_halo_pack", "cgnn_migrate_pack",
-    "cgnn_migrate_unpack",
+    "cgnn_migrate_unpack", "cgnn_knn_periodic_mode", "cgnn_knn_periodic_adaptive_mode",
 )
+KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
 MIGRATE_BLOCK = 256     # CGNN_MIGRATE_BLOCK: rows per workgroup of the migration kernels (block_counts / offsets rows)
 MIGRATE_MAX_WORLD = 64  # ranks a peer mask holds
@@ -122,6 +123,8 @@ def load() -> C.CDLL:
     lib.cgnn_knn_adaptive_workspace_bytes.argtypes = [i64, i32]
     lib.cgnn_knn_periodic_adaptive.argtypes = [vp, i64, f32, i32, vp, i64, vp, vp, vp, sz, vp]
     lib.cgnn_knn_adaptive_sorted_order.argtypes = [vp, i64, vp, vp]
+    lib.cgnn_knn_periodic_mode.argtypes = lib.cgnn_knn_periodic.argtypes + [i32]
+    lib.cgnn_knn_periodic_adaptive_mode.argtypes = lib.cgnn_knn_periodic_adaptive.argtypes + [i32]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

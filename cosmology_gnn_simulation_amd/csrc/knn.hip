@@ -93,7 +93,23 @@ __global__ void knn_fill_kernel(const float* __restrict__ pos, int64_t n, const 
 #define CGNN_KNN_IDX_BITS 27
 #define CGNN_KNN_IDX_MASK ((1u << CGNN_KNN_IDX_BITS) - 1u)
 
-template <int K>
+// Edge features of CGNN_KNN_EDGE_ATTR_IMAGE (cgnn.h): the displacement to the image the scan loop ranked,
+// fl32(fl32(pos[snd] + shift) - q), shift decoded from the top bits of the candidate's key
+// (shift_id = (sx + 1) * 9 + (sy + 1) * 3 + (sz + 1)); the same roundings as there, so the norm is the ranked distance.
+__device__ __forceinline__ float4 knn_image_edge_attr(const float* __restrict__ pos, int snd, unsigned shift_id,
+                                                      float box, float qx, float qy, float qz) {
+    const int sx = (int)(shift_id / 9u) - 1, sy = (int)((shift_id / 3u) % 3u) - 1, sz = (int)(shift_id % 3u) - 1;
+    const float ex = __fadd_rn(pos[3 * (int64_t)snd + 0], (float)sx * box);
+    const float ey = __fadd_rn(pos[3 * (int64_t)snd + 1], (float)sy * box);
+    const float ez = __fadd_rn(pos[3 * (int64_t)snd + 2], (float)sz * box);
+    const float ax = __fsub_rn(ex, qx), ay = __fsub_rn(ey, qy), az = __fsub_rn(ez, qz);
+    const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
+    return make_float4(ax, ay, az, nn);
+}
+
+// MODE (both search kernels): CGNN_KNN_EDGE_ATTR_REFERENCE or CGNN_KNN_EDGE_ATTR_IMAGE, a compile-time parameter of
+// the epilogue alone; the reference instantiation is instruction for instruction the kernel without the parameter.
+template <int K, int MODE>
 __global__ __launch_bounds__(CGNN_BLOCK) void knn_search_kernel(const float* __restrict__ pos, int64_t n, float box,
                                                                 float h, float inv_h, int G,
                                                                 const int32_t* __restrict__ start,
@@ -194,7 +210,11 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_search_kernel(const float* __r
         if (j < k) {
             const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
             senders[out_row * k + j] = snd;
-            if (edge_attr != nullptr) {
+            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
+                if (edge_attr != nullptr)
+                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
+                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, px, py, pz);
+            } else if (edge_attr != nullptr) {
                 // reference data_utils.py:162-164: mapped (un-shifted) sender minus receiver
                 const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], px);
                 const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], py);
@@ -360,7 +380,7 @@ __device__ __forceinline__ bool block_out_of_reach(float lox, float hix, float l
     return (gx * gx + gy * gy + gz * gz) * (1.0f - 1e-5f) > worst;
 }
 
-template <int K>
+template <int K, int MODE>
 __global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
     const float* __restrict__ pos, int64_t n, float box, float h, float inv_h, int G,
     const int32_t* __restrict__ lbase, const int32_t* __restrict__ lstart, const float4* __restrict__ sorted,
@@ -493,7 +513,11 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
         if (j < k) {
             const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
             senders[out_row * k + j] = snd;
-            if (edge_attr != nullptr) {
+            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
+                if (edge_attr != nullptr)
+                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
+                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, px, py, pz);
+            } else if (edge_attr != nullptr) {
                 const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], px);
                 const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], py);
                 const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], pz);
@@ -516,37 +540,43 @@ size_t cgnn_knn_workspace_bytes(int64_t n, int32_t k) {
     return knn_layout(n).total;
 }
 
-int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids, int64_t nq,
-                      int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
+// cgnn_knn_periodic and cgnn_knn_periodic_mode: `who` names the entry in error messages
+static int knn_periodic_run(const char* who, int32_t mode, const float* pos, int64_t n, float box_size, int32_t k,
+                            const int32_t* query_ids, int64_t nq, int32_t* senders, float* edge_attr, void* workspace,
+                            size_t workspace_bytes, void* stream) {
     if (!pos || !senders || !workspace || n <= 0 || k <= 0 || !(box_size > 0.f)) {
-        set_error("cgnn_knn_periodic: invalid argument");
+        set_error("%s: invalid argument", who);
         return CGNN_ERR_INVALID_ARG;
     }
+    if (mode != CGNN_KNN_EDGE_ATTR_REFERENCE && mode != CGNN_KNN_EDGE_ATTR_IMAGE) {
+        set_error("%s: unknown edge-feature mode %d", who, (int)mode);
+        return CGNN_ERR_UNSUPPORTED;
+    }
     if (k > 64) {
-        set_error("cgnn_knn_periodic: k=%d > 64 is not compiled", k);
+        set_error("%s: k=%d > 64 is not compiled", who, k);
         return CGNN_ERR_UNSUPPORTED;
     }
     if ((int64_t)k > 27 * n) {
-        set_error("cgnn_knn_periodic: k=%d exceeds the 27*n=%lld periodic images", k, (long long)(27 * n));
+        set_error("%s: k=%d exceeds the 27*n=%lld periodic images", who, k, (long long)(27 * n));
         return CGNN_ERR_INVALID_ARG;
     }
     if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) {
-        set_error("cgnn_knn_periodic: n=%lld >= 2^%d particles per call is not supported", (long long)n,
+        set_error("%s: n=%lld >= 2^%d particles per call is not supported", who, (long long)n,
                   CGNN_KNN_IDX_BITS);
         return CGNN_ERR_UNSUPPORTED;
     }
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_knn_periodic: workspace must be 16-byte aligned");
+        set_error("%s: workspace must be 16-byte aligned", who);
         return CGNN_ERR_INVALID_ARG;
     }
     const KnnLayout L = knn_layout(n);
     if (workspace_bytes < L.total) {
-        set_error("cgnn_knn_periodic: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
         return CGNN_ERR_WORKSPACE;
     }
     if (query_ids == nullptr) nq = n;
     if (nq < 0) {
-        set_error("cgnn_knn_periodic: negative query count");
+        set_error("%s: negative query count", who);
         return CGNN_ERR_INVALID_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -569,13 +599,20 @@ int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k, co
     knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, cell_of, count);
     exclusive_scan_i32(count, m, bsum, start, st);
     knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, cell_of, start, cursor, sorted);
-    rc = check_hip(hipGetLastError(), "cgnn_knn_periodic build launches");
+    rc = check_hip(hipGetLastError(), who);
     if (rc) return rc;
     if (nq == 0) return CGNN_OK;
     const unsigned qb = (unsigned)((nq + CGNN_BLOCK - 1) / CGNN_BLOCK);
-#define CGNN_KNN_LAUNCH(KK)                                                                                       \
-    knn_search_kernel<KK><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, start, cell_of, sorted, query_ids, nq, \
-                                                     k, senders, edge_attr)
+#define CGNN_KNN_LAUNCH_MODE(KK, MM)                                                                              \
+    knn_search_kernel<KK, MM><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, start, cell_of, sorted,       \
+                                                         query_ids, nq, k, senders, edge_attr)
+#define CGNN_KNN_LAUNCH(KK)                                                      \
+    do {                                                                         \
+        if (mode == CGNN_KNN_EDGE_ATTR_IMAGE)                                    \
+            CGNN_KNN_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                  \
+        else                                                                     \
+            CGNN_KNN_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);              \
+    } while (0)
     if (k <= 8)
         CGNN_KNN_LAUNCH(8);
     else if (k <= 16)
@@ -585,7 +622,21 @@ int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k, co
     else
         CGNN_KNN_LAUNCH(64);
 #undef CGNN_KNN_LAUNCH
-    return check_hip(hipGetLastError(), "cgnn_knn_periodic search launch");
+#undef CGNN_KNN_LAUNCH_MODE
+    return check_hip(hipGetLastError(), who);
+}
+
+int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids, int64_t nq,
+                      int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
+    return knn_periodic_run("cgnn_knn_periodic", CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k, query_ids, nq,
+                            senders, edge_attr, workspace, workspace_bytes, stream);
+}
+
+int cgnn_knn_periodic_mode(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                           int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                           void* stream, int32_t edge_attr_mode) {
+    return knn_periodic_run("cgnn_knn_periodic_mode", edge_attr_mode, pos, n, box_size, k, query_ids, nq, senders,
+                            edge_attr, workspace, workspace_bytes, stream);
 }
 
 int cgnn_knn_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {
@@ -606,38 +657,42 @@ size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k) {
     return knn_adaptive_layout(n).total;
 }
 
-int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
-                               int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+static int knn_periodic_adaptive_run(const char* who, int32_t mode, const float* pos, int64_t n, float box_size,
+                                     int32_t k, const int32_t* query_ids, int64_t nq, int32_t* senders,
+                                     float* edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
     if (!pos || !senders || !workspace || n <= 0 || k <= 0 || !(box_size > 0.f)) {
-        set_error("cgnn_knn_periodic_adaptive: invalid argument");
+        set_error("%s: invalid argument", who);
         return CGNN_ERR_INVALID_ARG;
     }
+    if (mode != CGNN_KNN_EDGE_ATTR_REFERENCE && mode != CGNN_KNN_EDGE_ATTR_IMAGE) {
+        set_error("%s: unknown edge-feature mode %d", who, (int)mode);
+        return CGNN_ERR_UNSUPPORTED;
+    }
     if (k > 64) {
-        set_error("cgnn_knn_periodic_adaptive: k=%d > 64 is not compiled", k);
+        set_error("%s: k=%d > 64 is not compiled", who, k);
         return CGNN_ERR_UNSUPPORTED;
     }
     if ((int64_t)k > 27 * n) {
-        set_error("cgnn_knn_periodic_adaptive: k=%d exceeds the 27*n=%lld periodic images", k, (long long)(27 * n));
+        set_error("%s: k=%d exceeds the 27*n=%lld periodic images", who, k, (long long)(27 * n));
         return CGNN_ERR_INVALID_ARG;
     }
     if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) {
-        set_error("cgnn_knn_periodic_adaptive: n=%lld >= 2^%d particles per call is not supported", (long long)n,
+        set_error("%s: n=%lld >= 2^%d particles per call is not supported", who, (long long)n,
                   CGNN_KNN_IDX_BITS);
         return CGNN_ERR_UNSUPPORTED;
     }
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_knn_periodic_adaptive: workspace must be 16-byte aligned");
+        set_error("%s: workspace must be 16-byte aligned", who);
         return CGNN_ERR_INVALID_ARG;
     }
     const KnnAdaptiveLayout L = knn_adaptive_layout(n);
     if (workspace_bytes < L.total) {
-        set_error("cgnn_knn_periodic_adaptive: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
         return CGNN_ERR_WORKSPACE;
     }
     if (query_ids == nullptr) nq = n;
     if (nq < 0) {
-        set_error("cgnn_knn_periodic_adaptive: negative query count");
+        set_error("%s: negative query count", who);
         return CGNN_ERR_INVALID_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -665,13 +720,20 @@ int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int3
     knna_leaf_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, lbase, leaf_of, lcount);
     exclusive_scan_i32(lcount, ml, bsum, lstart, st);
     knna_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, leaf_of, lstart, lcount, sorted);
-    rc = check_hip(hipGetLastError(), "cgnn_knn_periodic_adaptive build launches");
+    rc = check_hip(hipGetLastError(), who);
     if (rc) return rc;
     if (nq == 0) return CGNN_OK;
     const unsigned qb = (unsigned)((nq + CGNN_BLOCK - 1) / CGNN_BLOCK);
-#define CGNN_KNNA_LAUNCH(KK)                                                                                        \
-    knn_adaptive_search_kernel<KK><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, lbase, lstart, sorted, \
-                                                              query_ids, nq, k, senders, edge_attr)
+#define CGNN_KNNA_LAUNCH_MODE(KK, MM)                                                                           \
+    knn_adaptive_search_kernel<KK, MM><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, lbase, lstart,      \
+                                                                  sorted, query_ids, nq, k, senders, edge_attr)
+#define CGNN_KNNA_LAUNCH(KK)                                                     \
+    do {                                                                         \
+        if (mode == CGNN_KNN_EDGE_ATTR_IMAGE)                                    \
+            CGNN_KNNA_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                 \
+        else                                                                     \
+            CGNN_KNNA_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);             \
+    } while (0)
     if (k <= 8)
         CGNN_KNNA_LAUNCH(8);
     else if (k <= 16)
@@ -681,7 +743,22 @@ int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int3
     else
         CGNN_KNNA_LAUNCH(64);
 #undef CGNN_KNNA_LAUNCH
-    return check_hip(hipGetLastError(), "cgnn_knn_periodic_adaptive search launch");
+#undef CGNN_KNNA_LAUNCH_MODE
+    return check_hip(hipGetLastError(), who);
+}
+
+int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                               int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return knn_periodic_adaptive_run("cgnn_knn_periodic_adaptive", CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k,
+                                     query_ids, nq, senders, edge_attr, workspace, workspace_bytes, stream);
+}
+
+int cgnn_knn_periodic_adaptive_mode(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                                    int64_t nq, int32_t* senders, float* edge_attr, void* workspace,
+                                    size_t workspace_bytes, void* stream, int32_t edge_attr_mode) {
+    return knn_periodic_adaptive_run("cgnn_knn_periodic_adaptive_mode", edge_attr_mode, pos, n, box_size, k,
+                                     query_ids, nq, senders, edge_attr, workspace, workspace_bytes, stream);
 }
 
 int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {

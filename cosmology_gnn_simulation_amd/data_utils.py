@@ -81,11 +81,13 @@ def generate_temperature_noise(temperature_seq: torch.Tensor, noise_std: float, 
 
 
 def knn_graph_periodic(pos: torch.Tensor, box_size: float, k: int, want_order: bool = False, *,
-                       grid: str = "uniform"):
+                       min_image_edge_attr: bool = False, grid: str = "uniform"):
     """Periodic k-NN on the device.  Returns ``(edge_index int64 [2, N*k],
-    edge_attr [N*k, 4], senders int32, order|None)``.  ``grid``: as in ``ops.knn_periodic``."""
+    edge_attr [N*k, 4], senders int32, order|None)``.  ``grid``, ``min_image_edge_attr``: as in ``ops.knn_periodic``."""
     ops.check_knn_grid(grid, "knn_graph_periodic")
-    senders, edge_attr, order = ops.knn_periodic(pos, box_size, k, None, True, want_order, grid=grid)
+    ops.check_min_image(min_image_edge_attr, "knn_graph_periodic")
+    senders, edge_attr, order = ops.knn_periodic(pos, box_size, k, None, True, want_order, grid=grid,
+                                                 min_image_edge_attr=min_image_edge_attr)
     n = pos.shape[0]
     receivers = torch.arange(n, device=pos.device, dtype=torch.int64).repeat_interleave(k)
     edge_index = torch.stack([senders.to(torch.int64), receivers], dim=0)
@@ -112,7 +114,8 @@ def _draw_reference_noise(pos_seq: torch.Tensor, tmp_seq: torch.Tensor, noise_st
 def preprocess(position_seq, temperature_seq, metadata, target_position=None, target_temperature=None,
                noise_std=0.0, num_neighbors=16, dt=None, box_size=None, device: Optional[torch.device] = None,
                reference_rng: bool = True, check_bounds: bool = True, noise_rng: str = "reference",
-               noise_seed: Optional[int] = None, noise_draw: int = 0, *, knn_grid: str = "uniform"):
+               noise_seed: Optional[int] = None, noise_draw: int = 0, *, min_image_edge_attr: bool = False,
+               knn_grid: str = "uniform"):
     """Window ``[W, N, 3]`` / ``[W, N, 1]`` -> graph (reference data_utils.py:72-228).
 
     ``device`` (extension) selects the GPU; by default the inputs' device if they
@@ -136,8 +139,14 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
     reference's in-place ``+=`` on them is a side effect of its host code, kept only on the ``"reference"`` path).
 
     ``knn_grid`` (extension): the cell grid of the neighbour search, ``"uniform"`` or ``"adaptive"``
-    (``ops.knn_periodic``); the graph is the same bit for bit, ``"adaptive"`` builds it faster on clustered snapshots."""
+    (``ops.knn_periodic``); the graph is the same bit for bit, ``"adaptive"`` builds it faster on clustered snapshots.
+
+    ``min_image_edge_attr`` (extension, on both noise paths): ``False`` keeps the reference's edge features,
+    ``pos[sender] - pos[receiver]``, which are about one box length long for every edge that crosses a box face;
+    ``True`` writes the displacement to the periodic image the search ranked, and its norm (``ops.knn_periodic``).
+    ``x``, ``edge_index``, ``pos`` and the targets do not depend on it."""
     ops.check_knn_grid(knn_grid, "preprocess")
+    ops.check_min_image(min_image_edge_attr, "preprocess")
     if noise_rng not in ("reference", "device"):
         raise ValueError(f"noise_rng must be 'reference' or 'device', got {noise_rng!r}")
     dt = float(dt)
@@ -149,7 +158,7 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
     if noise_rng == "device":
         return _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature,
                                         noise_std, int(num_neighbors), dt, box_size, device, check_bounds, noise_seed,
-                                        noise_draw, knn_grid)
+                                        noise_draw, knn_grid, min_image_edge_attr)
 
     pos_seq = position_seq.float().permute(1, 0, 2)                       # [N, W, 3]
     tmp_seq = temperature_seq.float()
@@ -193,7 +202,8 @@ def preprocess(position_seq, temperature_seq, metadata, target_position=None, ta
 
     # --- periodic k-NN graph + edge features on the device ---
     edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, int(num_neighbors),
-                                                                want_order=True, grid=knn_grid)
+                                                                want_order=True, grid=knn_grid,
+                                                                min_image_edge_attr=min_image_edge_attr)
     n = recent_position.shape[0]
     if check_bounds:    # reference :158-159 (a host round trip: the on-device rollout turns it off)
         assert int(senders.max()) < n, f"Max sender index {int(senders.max())} >= {n}"
@@ -247,7 +257,7 @@ def _graph(x, edge_index, edge_attr, y_acc, y_temp_rate, recent_position, order,
 
 def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature, noise_std,
                              k: int, dt: float, box_size: float, device, check_bounds: bool, noise_seed, noise_draw,
-                             knn_grid: str = "uniform"):
+                             knn_grid: str = "uniform", min_image_edge_attr: bool = False):
     """``preprocess(noise_rng="device")``: one launch for noise, features, last frame and targets, then the k-NN."""
     n = position_seq.shape[1]
     pos_w = position_seq.to(device)                                       # [W, N, 3], as the kernel reads it
@@ -270,7 +280,8 @@ def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_pos
                             target_position, target_temperature, None, want)
     recent_position = s["recent_pos"]
     edge_index, edge_attr, senders, order = knn_graph_periodic(recent_position, box_size, k, want_order=True,
-                                                                grid=knn_grid)
+                                                                grid=knn_grid,
+                                                                min_image_edge_attr=min_image_edge_attr)
     if check_bounds:    # reference :158-159 (a host round trip)
         assert int(senders.max()) < n, f"Max sender index {int(senders.max())} >= {n}"
     y_tr = s.get("y_temp_rate")

@@ -195,7 +195,8 @@ def _near_tile(pos: torch.Tensor, box_size: float, lo, hi, margin: float) -> tor
 
 def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, rank: int,
                 knn_fn: Optional[Callable] = None, margin_factor: float = 2.0,
-                decomposition: str = "uniform", *, knn_grid: str = "uniform") -> Shard:
+                decomposition: str = "uniform", *, min_image_edge_attr: bool = False,
+                knn_grid: str = "uniform") -> Shard:
     """Everything rank ``rank`` can derive locally from the global positions: its owned set, their k-NN
     senders, the ghost set and the global->local renumbering.  ``knn_fn(pos, box, k, query_ids)`` defaults to
     the HIP k-NN; it returns ``(senders int32 [nq*k], edge_attr [nq*k, 4], order)``.
@@ -212,10 +213,15 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
 
     ``knn_grid``: the cell grid of the default search (``ops.knn_periodic``'s ``grid``: ``"uniform"`` or ``"adaptive"``;
     same neighbours, ``"adaptive"`` is the faster one for a tile that holds a halo).  A caller's ``knn_fn`` is left
-    alone."""
+    alone.
+
+    ``min_image_edge_attr``: the default search writes minimum-image edge features (``ops.knn_periodic``); the search
+    over the tile's subset ranks the same periodic images as the global one, so the rows are the global graph's.  A
+    caller's ``knn_fn`` decides for itself."""
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"build_shard: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
     ops.check_knn_grid(knn_grid, "build_shard")
+    ops.check_min_image(min_image_edge_attr, "build_shard")
     dev = pos_global.device
     n_total = pos_global.shape[0]
     planes = balanced_planes(pos_global, box_size, world) if decomposition == "balanced" else None
@@ -224,7 +230,8 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
     if not classify:
         owner = owner_of(pos_global, box_size, world, planes)
     knn = knn_fn or (lambda p, b, kk, q: ops.knn_periodic(p, b, kk, query_ids=q, want_edge_attr=True,
-                                                          want_order=True, grid=knn_grid))
+                                                          want_order=True, grid=knn_grid,
+                                                          min_image_edge_attr=min_image_edge_attr))
     t0 = time.perf_counter()
     search_ms = 0.0
 
@@ -380,7 +387,7 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
                             target_position: torch.Tensor, target_temperature: torch.Tensor, noise_std: float,
                             num_neighbors: int, dt: float, box_size: float, world: int, rank: int, noise_seed: int,
                             noise_draw: int = 0, device=None, decomposition: str = "uniform", *,
-                            knn_grid: str = "uniform") -> Shard:
+                            min_image_edge_attr: bool = False, knn_grid: str = "uniform") -> Shard:
     """Rank ``rank``'s part of the training sample ``data_utils.preprocess(..., noise_rng="device")`` makes on one GPU,
     with the same bits: the window ``[W, N, 3]`` / ``[W, N(, 1)]`` and the next frame ``[N, 3]`` / ``[N(, 1)]`` (or
     ``[1, N, ...]``) of ALL particles go in, every rank passing the same data, ``noise_seed`` and ``noise_draw``.
@@ -391,8 +398,9 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     :func:`build_shard` does, with ``x_feat``, ``y_acc [n_owned, 3]`` and ``y_temp_rate [n_owned, 1]`` set (local row
     order, ``owned_global``); :func:`exchange_requests` / :func:`finish_shard` remain the caller's next call.
     ``decomposition``: as in :func:`build_shard` (the planes of ``"balanced"`` come from the noisy frame, the same on
-    every rank); ``knn_grid``: as there."""
+    every rank); ``knn_grid``, ``min_image_edge_attr``: as there."""
     ops.check_knn_grid(knn_grid, "sharded_training_sample")
+    ops.check_min_image(min_image_edge_attr, "sharded_training_sample")
     if device is None:
         if not position_seq.is_cuda:
             raise CgnnError("sharded_training_sample: pass device= or device-resident windows")
@@ -411,7 +419,7 @@ def sharded_training_sample(position_seq: torch.Tensor, temperature_seq: torch.T
     recent = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw,
                                  want=("recent_pos",), stats=stats)["recent_pos"]
     sh = build_shard(recent, box_size, int(num_neighbors), world, rank, decomposition=decomposition,
-                     knn_grid=knn_grid)
+                     knn_grid=knn_grid, min_image_edge_attr=min_image_edge_attr)
     own = ops.training_sample(pos_w, tmp_w, metadata, dt, box_size, noise_std, noise_seed, noise_draw, tgt_p, tgt_t,
                               rows=sh.owned_global, want=("x", "y_acc", "y_temp_rate"), stats=stats)
     sh.x_feat, sh.y_acc, sh.y_temp_rate = own["x"], own["y_acc"], own["y_temp_rate"].reshape(-1, 1)
@@ -1243,12 +1251,13 @@ class ShardedRollout:
 
     Buffers that depend on the owned count are made per step.  ``decomposition``: as in :func:`build_shard`; with
     ``"balanced"`` the planes follow the particles from step to step and ``cap`` stays near ``N / world``.
-    ``knn_grid``: as in :func:`build_shard`, for every step's search."""
+    ``knn_grid``, ``min_image_edge_attr``: as in :func:`build_shard`, for every step's search."""
 
     def __init__(self, model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int = 6,
                  num_neighbors: int = 16, num_steps: Optional[int] = None, device=None, world: int = 1, rank: int = 0,
-                 decomposition: str = "uniform", *, knn_grid: str = "uniform"):
+                 decomposition: str = "uniform", *, min_image_edge_attr: bool = False, knn_grid: str = "uniform"):
         self.knn_grid = ops.check_knn_grid(knn_grid, "sharded rollout")
+        self.min_image_edge_attr = ops.check_min_image(min_image_edge_attr, "sharded rollout")
         coords, energy, total = rollout_arguments(data, window_size, num_neighbors, num_steps)
         if decomposition not in DECOMPOSITIONS:
             raise ValueError(f"sharded rollout: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
@@ -1280,7 +1289,7 @@ class ShardedRollout:
             raise CgnnError(f"sharded rollout: frame {t - 1} holds non-finite positions (rows that were never published, "
                             f"or a diverged model)")
         sh = build_shard(recent, self.box, self.k, self.world, self.rank, decomposition=self.decomposition,
-                         knn_grid=self.knn_grid)
+                         knn_grid=self.knn_grid, min_image_edge_attr=self.min_image_edge_attr)
         if sh._counts is not None:      # the balanced plan on the device: cgnn_tile_classify counted every rank's rows
             self.counts = sh._counts.tolist()
             self.cap = max(self.counts)
@@ -1316,12 +1325,12 @@ class ShardedRollout:
 def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: float, box_size: float,
                     window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None, device=None,
                     group=None, decomposition: str = "uniform", storage: str = "replicated", *,
-                    knn_grid: str = "uniform") -> dict:
+                    min_image_edge_attr: bool = False, knn_grid: str = "uniform") -> dict:
     """``rollout.rollout`` over the ranks of ``group`` (a world of one when no process group is up): same arguments,
     return value and frame count, and the same bits.  Every rank passes the same ``data`` (checked once, by one
     all-reduce of a checksum) and returns the whole trajectory.  ``noise_std`` is ignored, as there.
     ``decomposition``, ``knn_grid``: as in :func:`build_shard`; they change who computes a row and how its neighbours
-    are found, never the row.
+    are found, never the row.  ``min_image_edge_attr``: as in ``rollout.rollout``, for both storages.
 
     Per step: the shard of the wrapped last frame, the ghost-id all-to-all, the forward with one halo all-to-all per
     round, the integration of the owned particles and one all-gather of the packed rows into the next frame.
@@ -1337,6 +1346,7 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
     At most 64 ranks."""
     del noise_std
     ops.check_knn_grid(knn_grid, "sharded_rollout")
+    ops.check_min_image(min_image_edge_attr, "sharded_rollout")
     rollout_arguments(data, window_size, num_neighbors, num_steps)
     world, rank = _world_of(group)
     check_rollout_storage(storage, world, "sharded_rollout")
@@ -1348,7 +1358,7 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
         model.eval()
         with torch.no_grad():
             return _owned_rollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps,
-                                  torch.device(device), group, decomposition, knn_grid)
+                                  torch.device(device), group, decomposition, knn_grid, min_image_edge_attr)
     import torch.distributed as dist
     distributed = dist.is_available() and dist.is_initialized()
     if device is None:
@@ -1360,7 +1370,8 @@ def sharded_rollout(model, data: dict, metadata: dict, noise_std: float, dt: flo
             energy = data["InternalEnergy"]
             check_same_data(data["Coordinates"][:window_size], energy[:window_size], device, group)
         runner = ShardedRollout(model, data, metadata, dt, box_size, window_size, num_neighbors, num_steps, device,
-                                world, rank, decomposition, knn_grid=knn_grid)
+                                world, rank, decomposition, knn_grid=knn_grid,
+                                min_image_edge_attr=min_image_edge_attr)
         for t in range(window_size, runner.total_time):
             sh = runner.plan(t)
             if distributed:
@@ -1509,14 +1520,16 @@ class MigratingRollout:
        :meth:`check_total` on the all-reduced held counts: a lost particle raises on every rank.
 
     ``planes``: the cutting planes of a balanced decomposition, fixed for the run (the ranks cannot re-balance without
-    a distributed quantile search over all particles, which is not built); ``None``: equal-volume tiles."""
+    a distributed quantile search over all particles, which is not built); ``None``: equal-volume tiles.
+    ``min_image_edge_attr``: as in :func:`build_shard`, for every search."""
 
     def __init__(self, model, ids: torch.Tensor, coords_w: torch.Tensor, energy_w: torch.Tensor, *, n_total: int,
                  metadata: dict, dt: float, box_size: float, window_size: int = 6, num_neighbors: int = 16,
                  num_steps: int = 0, device=None, world: int = 1, rank: int = 0, planes: Optional[TilePlanes] = None,
-                 knn_grid: str = "uniform", margin_factor: float = 2.0):
+                 knn_grid: str = "uniform", margin_factor: float = 2.0, min_image_edge_attr: bool = False):
         what = "migrating rollout"
         self.knn_grid = ops.check_knn_grid(knn_grid, what)
+        self.min_image_edge_attr = ops.check_min_image(min_image_edge_attr, what)
         check_rollout_storage("owned", world, what)
         if isinstance(n_total, torch.Tensor) or int(n_total) != n_total:
             raise ValueError(f"{what}: n_total must be an integer")
@@ -1615,7 +1628,7 @@ class MigratingRollout:
             raise CgnnError(f"migrating rollout: rank {rank}'s search set holds a particle twice")
         whole = n_sub == self.n_total
         knn = lambda q: ops.knn_periodic(pos_sub, self.box, k, query_ids=q, want_edge_attr=True, want_order=True,   # noqa: E731
-                                         grid=self.knn_grid)
+                                         grid=self.knn_grid, min_image_edge_attr=self.min_image_edge_attr)
         owned_s = torch.nonzero(owner_sub == rank).squeeze(1)
         failed = False
         if n:
@@ -1727,7 +1740,8 @@ def exchange_rows(rows: torch.Tensor, send_counts: Sequence[int], recv_counts: S
 
 
 def _owned_rollout(model, data: dict, metadata: dict, dt: float, box_size: float, window_size: int, num_neighbors: int,
-                   num_steps: Optional[int], device, group, decomposition: str, knn_grid: str) -> dict:
+                   num_steps: Optional[int], device, group, decomposition: str, knn_grid: str,
+                   min_image_edge_attr: bool = False) -> dict:
     """``sharded_rollout(storage="owned")``: start-up slices the full initial window by the initial owner (the only place
     that touches N), then every step runs on the rank's rows."""
     import torch.distributed as dist
@@ -1747,7 +1761,8 @@ def _owned_rollout(model, data: dict, metadata: dict, dt: float, box_size: float
     at = own.to(coords.device)
     runner = MigratingRollout(model, own, coords[:W, at], energy[:W, at], n_total=n_total, metadata=metadata, dt=dt,
                               box_size=box_size, window_size=W, num_neighbors=num_neighbors, num_steps=total - W,
-                              device=device, world=world, rank=rank, planes=planes, knn_grid=knn_grid)
+                              device=device, world=world, rank=rank, planes=planes, knn_grid=knn_grid,
+                              min_image_edge_attr=min_image_edge_attr)
     nobody = torch.empty((0, 4), dtype=torch.float32, device=device)
     for _ in range(W, total):
         runner.begin()
@@ -1833,8 +1848,10 @@ def owned_frame_errors(result: dict, ground_truth: dict, group=None) -> dict:
 # ----------------------------------------------------------------------------
 
 def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int, seed: int, device, metadata: dict,
-                          group=None, decomposition: str = "uniform", *, knn_grid: str = "uniform") -> Shard:
+                          group=None, decomposition: str = "uniform", *, min_image_edge_attr: bool = False,
+                          knn_grid: str = "uniform") -> Shard:
     ops.check_knn_grid(knn_grid, "build_synthetic_shard")
+    ops.check_min_image(min_image_edge_attr, "build_synthetic_shard")
     n_total = particles_per_gpu * world
     # the box of synthetic.make_snapshot(n_total, seed), bit for bit, but only one global frame (positions: ownership and the
     # neighbour search need all of them) and the feature window of the OWNED particles are built and uploaded: per rank the
@@ -1843,7 +1860,8 @@ def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int,
     box, dt = metadata["box_size"], metadata["dt"]
     W = 5
     pos = torch.remainder(snap.frame(W - 1).to(device), box).contiguous()     # the window's last frame
-    sh = build_shard(pos, box, k, world, rank, decomposition=decomposition, knn_grid=knn_grid)
+    sh = build_shard(pos, box, k, world, rank, decomposition=decomposition, knn_grid=knn_grid,
+                     min_image_edge_attr=min_image_edge_attr)
     sh = exchange_requests(sh, group)
     coords, energy = snap.window_of(sh.owned_global)
     # node features of the owned particles: the same kernel data_utils.preprocess uses

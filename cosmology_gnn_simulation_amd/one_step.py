@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import synthetic
+from . import ops, synthetic
 from .data_utils import preprocess
 from .graph_network import EncodeProcessDecode
 
@@ -64,9 +64,11 @@ def integrate_one_step(acc_pred: torch.Tensor, temp_rate_pred: torch.Tensor, coo
 
 def validate_one_step(model, data: Union[str, Dict[str, torch.Tensor]], metadata: dict, window_size: int, device,
                       num_neighbors: int = 16, num_timesteps: int = 10, noise_std: float = 0.0,
-                      start_indices: Optional[Sequence[int]] = None) -> dict:
+                      start_indices: Optional[Sequence[int]] = None, *, min_image_edge_attr: bool = False) -> dict:
     """reference one_step_test.py:26-124.  ``data`` is a snapshot dict or an ``.npz``
-    path with ``Coordinates [T, N, 3]`` and ``InternalEnergy [T, N(,1)]``."""
+    path with ``Coordinates [T, N, 3]`` and ``InternalEnergy [T, N(,1)]``.  ``min_image_edge_attr`` (extension): as in
+    ``preprocess``."""
+    ops.check_min_image(min_image_edge_attr, "validate_one_step")
     model.eval()
     snap = synthetic.load_snapshot(data) if isinstance(data, str) else data
     coords_all, energy_all = snap["Coordinates"], snap["InternalEnergy"]
@@ -89,7 +91,7 @@ def validate_one_step(model, data: Union[str, Dict[str, torch.Tensor]], metadata
             next_temp = next_temp.unsqueeze(-1)
         graph = preprocess(position_seq=coords_seq, temperature_seq=temp_seq, metadata=metadata,
                            noise_std=noise_std, num_neighbors=num_neighbors, box_size=box_size, dt=dt,
-                           device=device)
+                           device=device, min_image_edge_attr=min_image_edge_attr)
         with torch.no_grad():
             pred = model(graph)
         new_p, new_t = integrate_one_step(pred["acceleration"], pred["temp_rate"], coords_seq, temp_seq, metadata)

@@ -578,21 +578,40 @@ def check_knn_grid(grid: str, who: str) -> str:
     return grid
 
 
+def check_min_image(flag: bool, who: str) -> bool:
+    """``TypeError`` for a ``min_image_edge_attr`` that is not a bool; callers check before any device work."""
+    if not isinstance(flag, bool):
+        raise TypeError(f"{who}: min_image_edge_attr must be a bool, got {flag!r}")
+    return flag
+
+
 def knn_periodic(pos: torch.Tensor, box_size: float, k: int, query_ids: Optional[torch.Tensor] = None,
-                 want_edge_attr: bool = True, want_order: bool = False, *, grid: str = "uniform"):
+                 want_edge_attr: bool = True, want_order: bool = False, *, min_image_edge_attr: bool = False,
+                 grid: str = "uniform"):
     """Returns ``(senders int32 [nq*k], edge_attr float32 [nq*k, 4] | None, order int32 [n] | None)``.
 
     ``grid``: ``"uniform"`` bins the particles into one uniform cell grid; ``"adaptive"`` refines every crowded cell
     into leaves and passes over the leaves that are out of reach (``cgnn_knn_periodic_adaptive``): the same
     ``senders`` and ``edge_attr`` bit for bit, less work where particles cluster.  ``order`` is cell-sorted either
-    way; inside a cell the two modes (like two runs of one mode) may differ."""
+    way; inside a cell the two modes (like two runs of one mode) may differ.
+
+    ``min_image_edge_attr``: ``False`` writes the reference's features, ``pos[sender] - pos[receiver]`` (an edge that
+    crosses a box face carries about one box length); ``True`` writes the displacement to the periodic image the
+    search ranked, ``fl32(fl32(pos[sender] + shift) - pos[receiver])``, and its norm (``CGNN_KNN_EDGE_ATTR_IMAGE``).
+    ``senders`` and ``order`` do not depend on it."""
     check_knn_grid(grid, "knn_periodic")
+    check_min_image(min_image_edge_attr, "knn_periodic")
     lib = _lib.load()
     if grid == "adaptive":
         ws_fn, knn_fn, order_fn = (lib.cgnn_knn_adaptive_workspace_bytes, lib.cgnn_knn_periodic_adaptive,
                                    lib.cgnn_knn_adaptive_sorted_order)
+        if min_image_edge_attr:
+            knn_fn = lib.cgnn_knn_periodic_adaptive_mode
     else:
         ws_fn, knn_fn, order_fn = lib.cgnn_knn_workspace_bytes, lib.cgnn_knn_periodic, lib.cgnn_knn_sorted_order
+        if min_image_edge_attr:
+            knn_fn = lib.cgnn_knn_periodic_mode
+    mode = (_lib.KNN_EDGE_ATTR_IMAGE,) if min_image_edge_attr else ()   # the default keeps its own entries
     pos = f32c(pos, "pos")
     if pos.dim() != 2 or pos.shape[1] != 3:
         raise CgnnError(f"knn_periodic: pos must be [n, 3], got {tuple(pos.shape)}")
@@ -609,7 +628,7 @@ def knn_periodic(pos: torch.Tensor, box_size: float, k: int, query_ids: Optional
     st = stream_ptr(pos.device)
     with _timed("knn_periodic", pos.device):
         check(knn_fn(pos.data_ptr(), n, float(box_size), k, ptr(query_ids), nq, senders.data_ptr(),
-                     ptr(edge_attr), ws.data_ptr(), ws_bytes, st), knn_fn.__name__)
+                     ptr(edge_attr), ws.data_ptr(), ws_bytes, st, *mode), knn_fn.__name__)
     order = None
     if want_order:
         order = torch.empty(n, dtype=torch.int32, device=pos.device)

@@ -23,14 +23,17 @@ from .one_step import integrate_one_step, integration_constants
 def rollout(model, data: Dict[str, torch.Tensor], metadata: dict, noise_std: float, dt: float, box_size: float,
             window_size: int = 6, num_neighbors: int = 16, num_steps: Optional[int] = None,
             device: Optional[torch.device] = None, reference_rng: bool = False, *,
-            knn_grid: str = "uniform") -> Dict[str, torch.Tensor]:
+            min_image_edge_attr: bool = False, knn_grid: str = "uniform") -> Dict[str, torch.Tensor]:
     """Same arguments and return value as the reference (``Coordinates [T, N, 3]``,
     ``InternalEnergy [T, N, 1]``, the first ``window_size`` frames copied from ``data``).  ``noise_std`` is
     accepted for signature compatibility only: the reference builds every rollout graph with ``noise_std=0.0``
     whatever the argument says (render_rollout.py:44-52, "Build a graph with no noise for rollout").
-    ``knn_grid``: the cell grid of every step's neighbour search, as in ``preprocess``; the frames do not depend on it."""
+    ``knn_grid``: the cell grid of every step's neighbour search, as in ``preprocess``; the frames do not depend on it.
+    ``min_image_edge_attr``: every step's graph carries minimum-image edge features, as in ``preprocess``; the frames
+    of a model that reads its edges (``message_source="edge"``) depend on it."""
     del noise_std
     ops.check_knn_grid(knn_grid, "rollout")
+    ops.check_min_image(min_image_edge_attr, "rollout")
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)
@@ -54,7 +57,8 @@ def rollout(model, data: Dict[str, torch.Tensor], metadata: dict, noise_std: flo
             win_t = tmp_traj[t - window_size:t]
             graph = preprocess(position_seq=win_p, temperature_seq=win_t, metadata=meta, noise_std=0.0,
                                num_neighbors=num_neighbors, box_size=box_size, dt=dt, device=device,
-                               reference_rng=reference_rng, check_bounds=False, knn_grid=knn_grid)
+                               reference_rng=reference_rng, check_bounds=False, knn_grid=knn_grid,
+                               min_image_edge_attr=min_image_edge_attr)
             pred = model(graph)
             new_p, new_t = integrate_one_step(pred["acceleration"], pred["temp_rate"], win_p, win_t, meta, consts)
             pos_traj[t] = new_p

@@ -471,6 +471,30 @@ int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int3
                                void* workspace, size_t workspace_bytes, void* stream);
 int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream);
 
+/* Both searches with a choice of edge features: the arguments of cgnn_knn_periodic / cgnn_knn_periodic_adaptive plus
+ * edge_attr_mode, the same workspace functions, sorted-order by-products, checks and error codes; an unknown mode is
+ * CGNN_ERR_UNSUPPORTED.  senders, their order and the self edge (all zeros) do not depend on the mode.
+ *   CGNN_KNN_EDGE_ATTR_REFERENCE  (pos[sender] - pos[query], |.|): the bits of the entries above (the reference's
+ *                                 features: an edge that crosses a box face carries about one box length)
+ *   CGNN_KNN_EDGE_ATTR_IMAGE      minimum image: the displacement to the periodic image the search ranked,
+ *                                   ext  = fl32(pos[sender] + shift)        shift in {-L, 0, +L}^3
+ *                                   disp = fl32(ext - pos[query])
+ *                                   edge_attr = (disp, sqrt(fl32(fl32(dx*dx + dy*dy) + dz*dz)))
+ *                                 one float32 rounding per operation, no FMA: the norm is the distance the neighbours
+ *                                 are ordered by.  In the reference's terms this is
+ *                                 extended_positions[ext_idx] - recent_position[receiver], before `mapping`.  Rows
+ *                                 whose image is the centre one hold the bits of the reference mode. */
+#define CGNN_KNN_EDGE_ATTR_REFERENCE 0
+#define CGNN_KNN_EDGE_ATTR_IMAGE 1
+int cgnn_knn_periodic_mode(const float* pos, int64_t n, float box_size, int32_t k,
+                           const int32_t* query_ids, int64_t nq,
+                           int32_t* senders, float* edge_attr,
+                           void* workspace, size_t workspace_bytes, void* stream, int32_t edge_attr_mode);
+int cgnn_knn_periodic_adaptive_mode(const float* pos, int64_t n, float box_size, int32_t k,
+                                    const int32_t* query_ids, int64_t nq,
+                                    int32_t* senders, float* edge_attr,
+                                    void* workspace, size_t workspace_bytes, void* stream, int32_t edge_attr_mode);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes

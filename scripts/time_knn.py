@@ -2,6 +2,7 @@
 queries, in ONE process: every shape is warmed in both modes, then the modes alternate; each call sits between two
 device events.  Prints median, min and max per mode and input.  Not part of the product or tests.
     python scripts/time_knn.py [--iters 12] [--neighbors 16] [--inputs uniform:1000000 clustered:1000000 clustered:4000000]
+    python scripts/time_knn.py --edge-attr reference image      (both edge-feature modes on both grids, all alternating)
     rocprofv3 --kernel-trace --stats -- python scripts/time_knn.py --iters 10       (build kernels against the search)
 clustered:N is synthetic.make_clustered_positions(N) (half of the particles in one Gaussian halo of 0.05 box)."""
 import argparse
@@ -18,6 +19,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=12)
 ap.add_argument("--neighbors", type=int, default=16)
 ap.add_argument("--inputs", nargs="+", default=["uniform:1000000", "clustered:1000000", "clustered:4000000"])
+ap.add_argument("--edge-attr", nargs="+", choices=["reference", "image"], default=["reference"],
+                help="edge-feature modes to time: reference (the default of ops.knn_periodic) and / or image "
+                     "(min_image_edge_attr=True)")
 ap.add_argument("--no-order", action="store_true", help="leave the sorted-order by-product out of the timed call")
 a = ap.parse_args()
 if a.iters < 10:
@@ -36,36 +40,50 @@ def frame(spec):
     raise SystemExit(f"unknown input {spec!r}: uniform:N or clustered:N")
 
 
-def call(pos, grid):
+VARIANTS = [(grid, mode) for grid in ops.KNN_GRIDS for mode in dict.fromkeys(a.edge_attr)]
+
+
+def call(pos, grid, mode):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = ops.knn_periodic(pos, box, k, want_order=not a.no_order, grid=grid)
+    out = ops.knn_periodic(pos, box, k, want_order=not a.no_order, grid=grid, min_image_edge_attr=mode == "image")
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1), out
 
 
 frames = {spec: frame(spec) for spec in a.inputs}
-for pos in frames.values():                          # warm every shape in both modes before any timing
-    for grid in ops.KNN_GRIDS:
+for pos in frames.values():                          # warm every shape in every mode before any timing
+    for grid, mode in VARIANTS:
         for _ in range(2):
-            call(pos, grid)
+            call(pos, grid, mode)
 print(f"ops.knn_periodic, k={k}, all queries, edge_attr{'' if a.no_order else ' and order'}; device events around the "
       f"call, modes alternating, {a.iters} timed calls per mode and input", flush=True)
 for spec, pos in frames.items():
-    times = {grid: [] for grid in ops.KNN_GRIDS}
+    times = {v: [] for v in VARIANTS}
     same = True
     for _ in range(a.iters):
         outs = {}
-        for grid in ops.KNN_GRIDS:
-            ms, outs[grid] = call(pos, grid)
-            times[grid].append(ms)
-        same = same and torch.equal(outs["uniform"][0], outs["adaptive"][0]) \
-            and torch.equal(outs["uniform"][1], outs["adaptive"][1])
+        for v in VARIANTS:
+            ms, outs[v] = call(pos, *v)
+            times[v].append(ms)
+        for mode in a.edge_attr:                     # the two grids give one graph in either edge-feature mode
+            same = same and torch.equal(outs["uniform", mode][0], outs["adaptive", mode][0]) \
+                and torch.equal(outs["uniform", mode][1], outs["adaptive", mode][1])
         del outs
-    med = {g: statistics.median(v) for g, v in times.items()}
-    for g, v in times.items():
-        print(f"  {spec:>18s}  {g:>8s}: median {med[g]:8.3f} ms   min {min(v):8.3f}   max {max(v):8.3f}")
-    apart = max(times["adaptive"]) < min(times["uniform"]) or max(times["uniform"]) < min(times["adaptive"])
-    print(f"  {spec:>18s}  uniform / adaptive = {med['uniform'] / med['adaptive']:.2f} x; ranges "
-          f"{'do not overlap' if apart else 'overlap'}; same bits: {same}", flush=True)
+    med = {v: statistics.median(t) for v, t in times.items()}
+    for (grid, mode), t in times.items():
+        print(f"  {spec:>18s}  {grid:>8s} {mode:>9s}: median {med[grid, mode]:8.3f} ms   min {min(t):8.3f}   "
+              f"max {max(t):8.3f}")
+    for mode in dict.fromkeys(a.edge_attr):
+        u, ad = times["uniform", mode], times["adaptive", mode]
+        apart = max(ad) < min(u) or max(u) < min(ad)
+        print(f"  {spec:>18s}  {mode}: uniform / adaptive = {med['uniform', mode] / med['adaptive', mode]:.2f} x; ranges "
+              f"{'do not overlap' if apart else 'overlap'}", flush=True)
+    if len(set(a.edge_attr)) == 2:
+        for grid in ops.KNN_GRIDS:
+            r, im = times[grid, "reference"], times[grid, "image"]
+            apart = max(im) < min(r) or max(r) < min(im)
+            print(f"  {spec:>18s}  {grid}: image / reference = {med[grid, 'image'] / med[grid, 'reference']:.3f} x; ranges "
+                  f"{'do not overlap' if apart else 'overlap'}", flush=True)
+    print(f"  {spec:>18s}  same bits on both grids: {same}", flush=True)
