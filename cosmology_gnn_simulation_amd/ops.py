@@ -7,6 +7,7 @@ non-zero status.  Outputs are torch tensors so callers keep normal ownership.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
@@ -789,6 +790,127 @@ def training_sample(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dic
             _scalar_stat(metadata, "temp_std", what), stats, *(ptr(out.get(name)) for name in TRAINING_SAMPLE_OUTPUTS),
             stream_ptr(dev)), "cgnn_training_sample")
     return out
+
+
+UNROLL_MAX_WINDOW = 32     # CGNN_UNROLL_MAX_WINDOW: the LDS tile of cgnn_training_sample_backward
+
+
+def _grad_rows(t: Optional[torch.Tensor], shape: Tuple[int, ...], name: str, what: str) -> Optional[torch.Tensor]:
+    """An optional gradient input as contiguous float32 of ``shape`` (a trailing 1 may be missing or extra)."""
+    if t is None:
+        return None
+    t = f32c(t, name)
+    if t.numel() != math.prod(shape) or t.shape[0] != shape[0]:
+        raise CgnnError(f"{what}: {name} must be {shape}, got {tuple(t.shape)}")
+    return t
+
+
+def training_sample_backward(window: int, n_rows: int, metadata: dict, dt: float, box_size: float, *,
+                             d_x: Optional[torch.Tensor] = None, d_recent_pos: Optional[torch.Tensor] = None,
+                             d_y_acc: Optional[torch.Tensor] = None, d_y_temp_rate: Optional[torch.Tensor] = None,
+                             rows: Optional[torch.Tensor] = None, n_total: Optional[int] = None, first_frame: int = 0,
+                             stats=None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """The transpose of :func:`training_sample` (``cgnn_training_sample_backward``): from the gradients of its outputs
+    (``d_x [R, 4W-3]``, ``d_recent_pos [R, 3]``, ``d_y_acc [R, 3]``, ``d_y_temp_rate [R(, 1)]``; ``None`` is zero) the
+    gradients of the window, ``(d_pos [W, R, 3], d_temp [W, R])``.  Frames before ``first_frame`` are left unwritten
+    (``out`` supplies the two tensors; else they are new, uninitialised there).  ``rows`` / ``n_total``: the row list
+    the forward took (ids outside ``[0, n_total)`` are skipped, as there)."""
+    what = "training_sample_backward"
+    w, nr = int(window), int(n_rows)
+    if not 2 <= w <= UNROLL_MAX_WINDOW:
+        raise CgnnError(f"{what}: window must lie in [2, {UNROLL_MAX_WINDOW}], got {w}")
+    if not 0 <= int(first_frame) < w:
+        raise CgnnError(f"{what}: first_frame {first_frame} outside [0, {w})")
+    given = [t for t in (d_x, d_recent_pos, d_y_acc, d_y_temp_rate, rows) if t is not None]
+    if not given and out is None:
+        raise CgnnError(f"{what}: no gradient given (pass `out` to name the device)")
+    d_x = _grad_rows(d_x, (nr, 4 * w - 3), "d_x", what)
+    d_recent_pos = _grad_rows(d_recent_pos, (nr, 3), "d_recent_pos", what)
+    d_y_acc = _grad_rows(d_y_acc, (nr, 3), "d_y_acc", what)
+    d_y_temp_rate = _grad_rows(d_y_temp_rate, (nr,), "d_y_temp_rate", what)
+    if rows is not None:
+        rows = _i64c(rows, "rows").reshape(-1)
+        if rows.numel() != nr:
+            raise CgnnError(f"{what}: {rows.numel()} row ids for {nr} rows")
+        if n_total is None:
+            raise CgnnError(f"{what}: a row list needs n_total")
+    n_total = nr if n_total is None else int(n_total)
+    if rows is None and n_total != nr:
+        raise CgnnError(f"{what}: without a row list n_rows must equal n_total ({nr} != {n_total})")
+    if stats is None:
+        stats = integration_stats(metadata)
+    dev = (given[0] if given else out[0]).device
+    if out is None:
+        out = (torch.empty((w, nr, 3), dtype=torch.float32, device=dev),
+               torch.empty((w, nr), dtype=torch.float32, device=dev))
+    d_pos, d_temp = out
+    for t, shape, name in ((d_pos, (w, nr, 3), "d_pos"), (d_temp, (w, nr), "d_temp")):
+        require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise CgnnError(f"{what}: {name} must be contiguous float32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    _same_device(d_x, d_recent_pos, d_y_acc, d_y_temp_rate, rows, d_pos, d_temp)
+    if nr == 0:
+        return d_pos, d_temp
+    with _timed(what, dev):
+        check(_lib.load().cgnn_training_sample_backward(
+            ptr(d_x), ptr(d_recent_pos), ptr(d_y_acc), ptr(d_y_temp_rate), w, n_total, ptr(rows), nr, int(first_frame),
+            float(box_size), float(dt), _scalar_stat(metadata, "vel_std", what), _scalar_stat(metadata, "temp_std", what),
+            stats, d_pos.data_ptr(), d_temp.data_ptr(), stream_ptr(dev)), "cgnn_training_sample_backward")
+    return d_pos, d_temp
+
+
+def rollout_integrate_backward(d_new_pos: Optional[torch.Tensor], d_new_temp: Optional[torch.Tensor], metadata: dict,
+                               want: Sequence[str] = ("acc_pred", "temp_rate_pred", "p1", "p2", "t1"), stats=None) -> dict:
+    """The transpose of :func:`rollout_integrate` / ``one_step.integrate_one_step`` (``cgnn_rollout_integrate_backward``):
+    from ``d_new_pos [R, 3]`` / ``d_new_temp [R(, 1)]`` (``None`` is zero, not both) a dict of the gradients named in
+    ``want``: ``acc_pred [R, 3]``, ``temp_rate_pred [R]``, ``p1 [R, 3]``, ``p2 [R, 3]`` (the frames t-1 and t-2) and
+    ``t1 [R]``."""
+    what = "rollout_integrate_backward"
+    known = ("acc_pred", "temp_rate_pred", "p1", "p2", "t1")
+    unknown = [name for name in want if name not in known]
+    if unknown or not want:
+        raise CgnnError(f"{what}: outputs {list(want)}; known: {known}")
+    ref = d_new_pos if d_new_pos is not None else d_new_temp
+    if ref is None:
+        raise CgnnError(f"{what}: no gradient given")
+    nr = ref.shape[0]
+    d_new_pos = _grad_rows(d_new_pos, (nr, 3), "d_new_pos", what)
+    d_new_temp = _grad_rows(d_new_temp, (nr,), "d_new_temp", what)
+    if stats is None:
+        stats = integration_stats(metadata)
+    dev = ref.device
+    widths = {"acc_pred": (nr, 3), "temp_rate_pred": (nr,), "p1": (nr, 3), "p2": (nr, 3), "t1": (nr,)}
+    out = {name: torch.empty(widths[name], dtype=torch.float32, device=dev) for name in want}
+    _same_device(d_new_pos, d_new_temp)
+    with _timed(what, dev):
+        check(_lib.load().cgnn_rollout_integrate_backward(
+            ptr(d_new_pos), ptr(d_new_temp), nr, stats, float(metadata["dt"]), float(metadata["box_size"]),
+            *(ptr(out.get(name)) for name in known), stream_ptr(dev)), "cgnn_rollout_integrate_backward")
+    return out
+
+
+def edge_attr_backward(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, senders: torch.Tensor, k: int,
+                       by_sender: "SenderCsr") -> torch.Tensor:
+    """``d_pos [N, 3]`` from the gradient of the k-NN's edge features (``cgnn_edge_attr_backward``): ``edge_attr [N k, 4]``
+    as :func:`knn_periodic` made it (either ``min_image_edge_attr`` mode), ``senders`` its int32 sender list,
+    ``by_sender = SenderCsr(senders, None, N)``.  Fixed summation order, no atomics."""
+    what = "edge_attr_backward"
+    d_edge_attr, edge_attr = f32c(d_edge_attr, "d_edge_attr"), f32c(edge_attr, "edge_attr")
+    senders = i32c(senders, "senders").reshape(-1)
+    k, n = int(k), int(by_sender.rows)
+    if k < 1 or edge_attr.shape != (n * k, 4) or d_edge_attr.shape != (n * k, 4) or senders.numel() != n * k:
+        raise CgnnError(f"{what}: edge_attr / d_edge_attr must be [{n} * {k}, 4] with as many senders, got "
+                        f"{tuple(edge_attr.shape)}, {tuple(d_edge_attr.shape)}, {senders.numel()} senders")
+    if by_sender.col.numel() < n * k:
+        raise CgnnError(f"{what}: the CSR holds {by_sender.col.numel()} edges, the list {n * k}")
+    _same_device(d_edge_attr, edge_attr, senders, by_sender.row_ptr, by_sender.col)
+    d_pos = torch.empty((n, 3), dtype=torch.float32, device=edge_attr.device)
+    with _timed(what, edge_attr.device):
+        check(_lib.load().cgnn_edge_attr_backward(d_edge_attr.data_ptr(), edge_attr.data_ptr(), senders.data_ptr(), n, k,
+                                                  by_sender.row_ptr.data_ptr(), by_sender.col.data_ptr(),
+                                                  d_pos.data_ptr(), stream_ptr(edge_attr.device)),
+              "cgnn_edge_attr_backward")
+    return d_pos
 
 
 def _pos3(pos: torch.Tensor, what: str) -> torch.Tensor:

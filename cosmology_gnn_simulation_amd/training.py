@@ -25,6 +25,7 @@ see :func:`edge_training_bytes`.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -523,3 +524,303 @@ class _Permute(torch.autograd.Function):
 
 def permute_rows(rows: torch.Tensor, idx: torch.Tensor, inv: torch.Tensor) -> torch.Tensor:
     return _Permute.apply(rows, idx, inv)
+
+
+# ---- multi-step training: the loss of S unrolled model steps, differentiated through the chain ---------------------------
+#
+# One step is  window --sample--> (x, recent, y) ; recent --k-NN--> (senders, edge_attr) ; model ; loss ;
+# (pred, two last frames) --integrate--> next frame.  The model's backward exists (``_NodeStream`` / ``_EdgeStreams`` return
+# d x0 and d edge_attr); the three links around it are HIP kernel pairs wrapped here (csrc/unroll.hip).  remainder and wrap
+# are piecewise translations, the neighbour selection is discrete and the noise a constant: every link is linear.
+
+class _LinkConfig:
+    """What the links of one :func:`unrolled_loss` call share: metadata with ``dt`` / ``box_size``, the host statistics
+    block and the identity row list of ``ops.rollout_integrate``, each made once."""
+
+    def __init__(self, metadata: dict, dt: float, box_size: float, n: int, device):
+        self.meta = dict(metadata, dt=float(dt), box_size=float(box_size))
+        self.dt, self.box = float(dt), float(box_size)
+        self.stats = ops.integration_stats(self.meta)
+        self.ids = torch.arange(n, dtype=torch.int64, device=device)
+
+
+class _SampleLink(torch.autograd.Function):
+    """``(x, recent_pos, y_acc, y_temp_rate) = cgnn_training_sample(window)`` without noise, the window given as W position
+    frames ``[N, 3]`` followed by W temperature frames ``[N]``; the targets are constants.  The backward
+    (``cgnn_training_sample_backward``) writes the frames from the first one that requires a gradient on."""
+
+    @staticmethod
+    def forward(ctx, cfg: _LinkConfig, target_pos, target_temp, *frames):
+        w = len(frames) // 2
+        pos_w, tmp_w = torch.stack(frames[:w]), torch.stack(frames[w:])
+        s = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, 0.0, 0, 0, target_pos, target_temp,
+                                stats=cfg.stats)
+        ctx.cfg, ctx.w, ctx.n = cfg, w, pos_w.shape[1]
+        ctx.set_materialize_grads(False)
+        return s["x"], s["recent_pos"], s["y_acc"], s["y_temp_rate"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_x, d_recent, d_y_acc, d_y_tr):
+        w, cfg = ctx.w, ctx.cfg
+        needs = ctx.needs_input_grad[3:]
+        first = min(t % w for t in range(2 * w) if needs[t])
+        if d_x is None and d_recent is None and d_y_acc is None and d_y_tr is None:
+            return (None,) * (3 + 2 * w)
+        d_pos, d_temp = ops.training_sample_backward(w, ctx.n, cfg.meta, cfg.dt, cfg.box, d_x=d_x, d_recent_pos=d_recent,
+                                                     d_y_acc=d_y_acc, d_y_temp_rate=d_y_tr, first_frame=first,
+                                                     stats=cfg.stats)
+        return (None, None, None, *(d_pos[t] if needs[t] else None for t in range(w)),
+                *(d_temp[t] if needs[w + t] else None for t in range(w)))
+
+
+class _KnnEdgeAttr(torch.autograd.Function):
+    """``(edge_attr, senders) = ops.knn_periodic(recent)``: the graph build, differentiable in its edge features
+    (``cgnn_edge_attr_backward``; the senders are discrete).  The sender-major edge CSR is built in the backward, so a
+    call nobody differentiates (``message_source="x_j"``) pays nothing for it."""
+
+    @staticmethod
+    def forward(ctx, recent, box: float, k: int, grid: str, min_image: bool):
+        senders, edge_attr, _ = ops.knn_periodic(recent, box, k, None, True, False, min_image_edge_attr=min_image,
+                                                 grid=grid)
+        ctx.k, ctx.n = k, recent.shape[0]
+        ctx.save_for_backward(edge_attr, senders)
+        ctx.mark_non_differentiable(senders)
+        ctx.set_materialize_grads(False)
+        return edge_attr, senders
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_edge_attr, _d_senders):
+        if d_edge_attr is None:
+            return None, None, None, None, None
+        edge_attr, senders = ctx.saved_tensors
+        by_sender = ops.SenderCsr(senders, None, ctx.n)
+        return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender), None, None, None, None
+
+
+def _spread3(v: torch.Tensor) -> torch.Tensor:
+    """10 bits -> every third bit (the Morton spread of csrc/knn.hip, on int64 tensors)."""
+    v = (v | (v << 16)) & 0x030000FF
+    v = (v | (v << 8)) & 0x0300F00F
+    v = (v | (v << 4)) & 0x030C30C3
+    return (v | (v << 2)) & 0x09249249
+
+
+def spatial_order(pos: torch.Tensor, box: float, per_cell: int = 8) -> torch.Tensor:
+    """A cell-sorted particle order (int32 [N]) along a Morton curve, ties in particle order: the locality hint a
+    ``Data`` object carries for the engine (``_cgnn_order``), as the k-NN build returns one -- but a pure function of the
+    positions.  The k-NN's own order fills each cell through an atomic cursor, so two builds of one graph may number
+    the particles of a cell differently, and the engine's float32 sums over rows then differ in their last bits; an
+    unrolled step builds its graphs inside the call and has to give the same bits twice.  Index bookkeeping (a few
+    integer element-wise kernels and one stable sort per graph), no host synchronisation."""
+    n = pos.shape[0]
+    bits = max(0, min(10, int(math.log2(max(n / per_cell, 1.0)) / 3)))
+    g = 1 << bits
+    c = _spread3((pos.detach() * (g / float(box))).floor_().clamp_(0, g - 1).to(torch.int64))
+    key = (c[:, 0] << 2) | (c[:, 1] << 1) | c[:, 2]
+    return torch.argsort(key, stable=True).to(torch.int32)
+
+
+class _IntegrateLink(torch.autograd.Function):
+    """``(new_pos, new_temp) = one_step.integrate_one_step`` through ``cgnn_rollout_integrate`` (its bits), with
+    ``cgnn_rollout_integrate_backward`` behind it."""
+
+    @staticmethod
+    def forward(ctx, cfg: _LinkConfig, acc_pred, rate_pred, p2, p1, t1):
+        out = ops.rollout_integrate(acc_pred, rate_pred, p2, p1, t1, cfg.ids, cfg.meta, stats=cfg.stats)
+        ctx.cfg = cfg
+        ctx.shapes = (rate_pred.shape, t1.shape)
+        ctx.set_materialize_grads(False)
+        return out[:, :3].contiguous(), out[:, 3].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_new_pos, d_new_temp):
+        names = ("acc_pred", "temp_rate_pred", "p2", "p1", "t1")
+        want = [name for name, need in zip(names, ctx.needs_input_grad[1:]) if need]
+        if (d_new_pos is None and d_new_temp is None) or not want:
+            return (None,) * 6
+        g = ops.rollout_integrate_backward(d_new_pos, d_new_temp, ctx.cfg.meta, want, stats=ctx.cfg.stats)
+        if "temp_rate_pred" in g:
+            g["temp_rate_pred"] = g["temp_rate_pred"].view(ctx.shapes[0])
+        if "t1" in g:
+            g["t1"] = g["t1"].view(ctx.shapes[1])
+        return (None, *(g.get(name) for name in names))
+
+
+def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
+                            num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False) -> int:
+    """Device memory S unrolled steps keep alive until the backward: S times the one-step activations -- the node
+    features, ``x_i`` and ``agg_i`` of every round (:class:`NodeStreamSteps`), the edge features, and under
+    ``message_source="edge"`` every round's input edge latents (:func:`edge_training_bytes`) -- plus one backward
+    scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn."""
+    n, ne = int(num_particles), int(num_particles) * int(num_neighbors)
+    per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
+    scratch = (2 * num_hidden_layers + 3) * n * hidden
+    if edge_messages:
+        per_step += rounds * ne * latent
+        scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    return 4 * (int(steps) * per_step + scratch)
+
+
+class UnrolledLoss:
+    """Result of :func:`unrolled_loss`: ``loss`` (0-d float32 with a ``grad_fn``), ``step_losses`` (detached ``[S, 3]``:
+    acceleration, temperature-rate and momentum term per step), ``frames`` (detached predicted ``Coordinates [S, N, 3]``
+    and ``InternalEnergy [S, N, 1]``) and ``graphs`` (the S ``Data`` objects under ``keep_graphs``, else ``None``)."""
+
+    def __init__(self, loss, step_losses, frames, graphs):
+        self.loss, self.step_losses, self.frames, self.graphs = loss, step_losses, frames, graphs
+
+
+def _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures, step_weights,
+                      backprop_steps, num_neighbors, knn_grid, min_image_edge_attr):
+    """The checks of :func:`unrolled_loss` that need no device: -> (W, N, S, weights)."""
+    from .graph_network import EncodeProcessDecode
+    ops.check_knn_grid(knn_grid, "unrolled_loss")
+    ops.check_min_image(min_image_edge_attr, "unrolled_loss")
+    if not isinstance(model, EncodeProcessDecode):
+        raise NotImplementedError("unrolled_loss trains one EncodeProcessDecode on one GPU; sharded training "
+                                  "(dist.ShardedTraining) unrolls no steps")
+    if isinstance(position_seq, (list, tuple)) or not torch.is_tensor(position_seq) or position_seq.dim() == 4:
+        raise NotImplementedError("unrolled_loss takes one graph per call ([W, N, 3]); multi-graph batches are not "
+                                  "unrolled")
+    if position_seq.dim() != 3 or position_seq.shape[2] != 3:
+        raise ValueError(f"unrolled_loss: position_seq must be [W, N, 3], got {tuple(position_seq.shape)}")
+    w, n = int(position_seq.shape[0]), int(position_seq.shape[1])
+    if w < 2:
+        raise ValueError(f"unrolled_loss: a window holds at least 2 frames, got {w}")
+    if w > ops.UNROLL_MAX_WINDOW:
+        raise ValueError(f"unrolled_loss: windows of up to {ops.UNROLL_MAX_WINDOW} frames, got {w}")
+    if temperature_seq.numel() != w * n or temperature_seq.shape[0] != w:
+        raise ValueError(f"unrolled_loss: temperature_seq {tuple(temperature_seq.shape)} does not hold [{w}, {n}(, 1)]")
+    if target_positions.dim() != 3 or target_positions.shape[0] < 1 or tuple(target_positions.shape[1:]) != (n, 3):
+        raise ValueError(f"unrolled_loss: target_positions {tuple(target_positions.shape)} does not hold [S, {n}, 3] "
+                         f"with S >= 1")
+    s = int(target_positions.shape[0])
+    if target_temperatures.dim() < 2 or target_temperatures.shape[0] != s or target_temperatures.numel() != s * n:
+        raise ValueError(f"unrolled_loss: target_temperatures {tuple(target_temperatures.shape)} does not hold "
+                         f"[{s}, {n}(, 1)]")
+    if backprop_steps is not None and (int(backprop_steps) != backprop_steps or backprop_steps < 0):
+        raise ValueError(f"unrolled_loss: backprop_steps must be None or an integer >= 0, got {backprop_steps!r}")
+    if int(num_neighbors) < 1:
+        raise ValueError(f"unrolled_loss: num_neighbors must be positive, got {num_neighbors}")
+    weights = [1.0 / s] * s if step_weights is None else [float(v) for v in step_weights]
+    if len(weights) != s:
+        raise ValueError(f"unrolled_loss: {len(weights)} step weights for {s} steps")
+    if getattr(model, "train_edge_stream", False):
+        raise NotImplementedError("unrolled_loss does not run the dead edge stream (model.train_edge_stream)")
+    source = getattr(model, "message_source", "x_j")
+    if source not in ("x_j", "edge") or (source == "edge" and not getattr(model, "train_edge_messages", False)):
+        raise NotImplementedError("unrolled_loss trains message_source='x_j', or 'edge' with model.train_edge_messages = "
+                                  "True")
+    prec = getattr(model, "train_precision", "fp32")
+    if ops._prec(prec) not in (_lib.F32, _lib.F32X3):
+        raise CgnnError(f"unrolled_loss: train_precision must be 'fp32' or 'fp32x3', got {prec!r}")
+    return w, n, s, weights
+
+
+def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tensor, target_positions: torch.Tensor,
+                  target_temperatures: torch.Tensor, metadata: dict, *, dt: float, box_size: float, num_neighbors: int = 16,
+                  noise_std: float = 0.0, noise_seed: Optional[int] = None, noise_draw: int = 0,
+                  acc_loss_weight: float = 1.0, temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
+                  step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
+                  min_image_edge_attr: bool = False, knn_grid: str = "uniform", keep_graphs: bool = False,
+                  device: Optional[torch.device] = None) -> UnrolledLoss:
+    """The multi-step training loss: S model steps unrolled from one window ``position_seq [W, N, 3]`` /
+    ``temperature_seq [W, N(, 1)]``, every step compared with the true frames ``target_positions [S, N, 3]`` /
+    ``target_temperatures [S, N(, 1)]``, differentiable through the whole chain.
+
+    Step s takes the last W frames (true ones, then its own predictions), forms the one-step sample
+    (``cgnn_training_sample``'s arithmetic: features, wrapped last frame, normalised targets), builds the k-NN graph of
+    the last frame, runs the model's training forward, and scores ``acc_loss_weight * MSE(acc) + temp_rate_loss_weight *
+    MSE(temp_rate) + momentum_conservation_loss`` (reference train.py:255-260); ``one_step.integrate_one_step``'s
+    arithmetic then makes the next frame.  ``loss = sum_s step_weights[s] * loss_s`` (default ``1 / S`` each); for S = 1
+    this is the one-step loss of ``preprocess(noise_rng="device")`` -> ``model`` -> the three terms.  Both the prediction
+    and the target of a later step carry gradient (the target is computed from predicted frames).  The neighbour lists
+    carry none.
+
+    ``backprop_steps = b`` lets the gradient through the last ``b`` of the S - 1 links between steps only: frames
+    predicted before are detached (``0``: every step trains on detached inputs; ``None``: all links).
+
+    Noise (``noise_std``, ``noise_seed``, ``noise_draw``: the counter-based generator of ``preprocess(noise_rng=
+    "device")``) is added to the W true frames only; every target is shifted by the last frame's noise, as the
+    reference shifts its one target.  It is a constant for the gradient.
+
+    Memory: S steps of activations stay alive until ``loss.backward()`` (:func:`unrolled_training_bytes`); the call
+    refuses when that estimate exceeds the free device memory.  No host synchronisation beyond the one-step path's."""
+    from . import data_utils, losses
+    w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
+                                         step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr)
+    k = int(num_neighbors)
+    if device is None:
+        device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
+    device = torch.device(device)
+    edge = getattr(model, "message_source", "x_j") == "edge"
+    need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
+                                   len(model.processor), S, edge)
+    free = free_device_bytes(device)
+    if need > free:
+        raise CgnnError(f"unrolled_loss needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
+                        f"steps ({n} particles, {k} neighbours, latent {model._latent_size}, {len(model.processor)} "
+                        f"rounds); {free / 2**30:.1f} GiB are free")
+    cfg = _LinkConfig(metadata, dt, box_size, n, device)
+    pos_w = _lib.f32c(position_seq.to(device), "position_seq")
+    tmp_w = _lib.f32c(temperature_seq.to(device), "temperature_seq").reshape(w, n)
+    tgt_p = _lib.f32c(target_positions.to(device), "target_positions")
+    tgt_t = _lib.f32c(target_temperatures.to(device), "target_temperatures").reshape(S, n)
+    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
+
+    # step 0: the one-step sample, with noise from the counter-based generator
+    seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
+    noisy = float(noise_std) != 0.0
+    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
+    s0 = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
+                             tgt_p[0], tgt_t[0], None, want, stats=cfg.stats)
+    if noisy:       # the noisy frames later windows read, and the shift of every later target
+        pos_w = pos_w + s0["pos_noise"].permute(1, 0, 2)
+        tmp_w = tmp_w + s0["temp_noise"].t()
+        if S > 1:
+            tgt_p = tgt_p + s0["pos_noise"][:, -1]
+            tgt_t = tgt_t + s0["temp_noise"][:, -1]
+    pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
+
+    total = None
+    receivers = cfg.ids.repeat_interleave(k)
+    step_losses, graphs, out_p, out_t = [], [], [], []
+    mse = torch.nn.functional.mse_loss
+    for s in range(S):
+        if s == 0:
+            x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
+        else:
+            x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p[s], tgt_t[s], *pos_frames[-w:], *tmp_frames[-w:])
+        # the edge features carry gradient only where the model reads them
+        edge_attr, senders = _KnnEdgeAttr.apply(recent if edge else recent.detach(), cfg.box, k, knn_grid,
+                                                min_image_edge_attr)
+        order = spatial_order(recent, cfg.box)
+        edge_index = torch.stack([senders.to(torch.int64), receivers], dim=0)
+        graph = data_utils._graph(x, edge_index, edge_attr, y_acc, y_tr.reshape(n, 1), recent.detach(), order, cfg.dt,
+                                  cfg.box, k, device)
+        pred = model(graph)
+        acc, rate = pred["acceleration"], pred["temp_rate"]
+        terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
+                 losses.momentum_conservation_loss(acc, graph, cfg.dt, momentum_loss_weight))
+        loss_s = acc_loss_weight * terms[0] + temp_rate_loss_weight * terms[1] + terms[2]
+        total = weights[s] * loss_s if total is None else total + weights[s] * loss_s
+        step_losses.append(torch.stack([t.detach() for t in terms]))
+        if keep_graphs:
+            graphs.append(graph)
+        # the next frame; link s feeds step s + 1 and carries gradient when it is one of the last `links`
+        live = s < S - 1 and s >= S - 1 - links
+        if live:
+            new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, pos_frames[-2], pos_frames[-1], tmp_frames[-1])
+        else:
+            with torch.no_grad():
+                new_p, new_t = _IntegrateLink.apply(cfg, acc.detach(), rate.detach(), pos_frames[-2].detach(),
+                                                    pos_frames[-1].detach(), tmp_frames[-1].detach())
+        out_p.append(new_p.detach())
+        out_t.append(new_t.detach())
+        pos_frames.append(new_p)
+        tmp_frames.append(new_t)
+    frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
+    return UnrolledLoss(total, torch.stack(step_losses), frames, graphs if keep_graphs else None)

@@ -546,6 +546,46 @@ int cgnn_training_sample(const float* pos_seq, const float* temp_seq, const floa
                          float temp_mean, float temp_std, const float* stats, float* x, float* recent_pos, float* y_acc,
                          float* y_temp_rate, float* pos_noise, float* temp_noise, void* stream);
 
+/* ---- links of an unrolled training step (training.unrolled_loss): the transposes of the sample, the integration and
+ * the k-NN's edge features.  remainder and wrap are piecewise translations (derivative 1), the noise is a constant, so
+ * every link is a linear map per particle; these entries apply its exact transpose in float32, one rounding per
+ * operation, in a fixed order, without atomics: two runs give the same bits.  None reads a position.
+ *
+ * cgnn_training_sample_backward: for output row i (particle g = rows[i], or i when rows is NULL and n_rows ==
+ * n_total; rows with g outside [0, n_total) are skipped, as in cgnn_training_sample), from the gradients of that
+ * entry's outputs -- d_x [n_rows, 4W-3], d_recent_pos [n_rows, 3], d_y_acc [n_rows, 3], d_y_temp_rate [n_rows], each
+ * may be NULL (zero) -- the gradients of the window, d_pos [W, n_rows, 3] and d_temp [W, n_rows]:
+ *   a = (d_y_acc / acc_std) / dt
+ *   gd_t = ((d_x[3 (t-1) + c] / vel_std) [- a at t = W-1]) / dt  for t = 1 .. W-1,  gd_0 = gd_W = 0
+ *   d_pos[t] = gd_t - gd_{t+1}  [+ (d_recent_pos - a / dt) at t = W-1]
+ *   d_temp[t] = d_x[3 (W-1) + t] / temp_std  [- (d_y_temp_rate / tr_std) / dt at t = W-1]
+ * Frames t < first_frame (ground truth: nothing to train) are not written.  window in [2, 32]; box_size, dt, vel_std,
+ * temp_std and stats (HOST memory, 8 floats; may be NULL without target gradients) as cgnn_training_sample takes them.
+ * Invalid (nothing is launched): a window outside [2, 32], first_frame outside [0, window), n_total >= 2^31, rows ==
+ * NULL with n_rows != n_total, dt == 0, a zero std, box_size <= 0, a NULL output.
+ *
+ * cgnn_rollout_integrate_backward: for row i of d_new_pos [n_rows, 3] / d_new_temp [n_rows] (each may be NULL: zero),
+ * the transpose of cgnn_rollout_integrate's arithmetic:
+ *   d_nv = d_new_pos * dt;  d_acc_pred = (d_nv * dt) * acc_std;  u = d_nv * (1 / dt);  d_p1 = d_new_pos + u;  d_p2 = -u
+ *   d_t1 = d_new_temp;  d_temp_rate_pred = (d_new_temp * dt) * tr_std
+ * Every output ([n_rows, 3] or [n_rows]) may be NULL, not all of them.  stats: HOST memory, 8 floats, as there.
+ *
+ * cgnn_edge_attr_backward: d_pos [n, 3] from d_edge_attr [n k, 4] and the forward's edge_attr [n k, 4] (16-byte
+ * aligned) of a receiver-sorted list with k edges per receiver (cgnn_knn_periodic, either edge-feature mode: the
+ * image shift is a constant).  g_e = d_disp + d_dist * disp / dist, the second term 0 where dist == 0;
+ *   d_pos[r] = - sum_{j < k} g_{r k + j}  +  sum_{p in [row_ptr[r], row_ptr[r+1])} g_{col[p]}
+ * in that order, (row_ptr int32 [n + 1], col int32 [n k]) the edges grouped by sender (cgnn_csr_build with val ==
+ * NULL); an entry of col outside [0, n k) or whose sender is not r is skipped. */
+int cgnn_training_sample_backward(const float* d_x, const float* d_recent_pos, const float* d_y_acc,
+                                  const float* d_y_temp_rate, int32_t window, int64_t n_total, const int64_t* rows,
+                                  int64_t n_rows, int32_t first_frame, float box_size, float dt, float vel_std,
+                                  float temp_std, const float* stats, float* d_pos, float* d_temp, void* stream);
+int cgnn_rollout_integrate_backward(const float* d_new_pos, const float* d_new_temp, int64_t n_rows, const float* stats,
+                                    float dt, float box_size, float* d_acc_pred, float* d_temp_rate_pred, float* d_p1,
+                                    float* d_p2, float* d_t1, void* stream);
+int cgnn_edge_attr_backward(const float* d_edge_attr, const float* edge_attr, const int32_t* senders, int64_t n,
+                            int32_t k, const int32_t* row_ptr, const int32_t* col, float* d_pos, void* stream);
+
 /* ---- sharded rollout step (reference render_rollout.py:73-85; one_step_test.py:84-105) ----------------------
  * A packed frame row is CGNN_ROLLOUT_ROW floats: (x, y, z, temperature, int32 particle id bit-cast to float);
  * id -1 marks a padding row.
