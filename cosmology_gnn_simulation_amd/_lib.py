@@ -46,6 +46,7 @@ EXPORTS = (
     "cgnn_history_features", "cgnn_rollout_advance", "cgnn_halo_select", "cgnn_halo_pack", "cgnn_migrate_pack",
     "cgnn_migrate_unpack", "cgnn_knn_periodic_mode", "cgnn_knn_periodic_adaptive_mode",
     "cgnn_training_sample_backward", "cgnn_rollout_integrate_backward", "cgnn_edge_attr_backward",
+    "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows",
 )
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -137,6 +138,9 @@ def load() -> C.CDLL:
                                                   vp]
     lib.cgnn_rollout_integrate_backward.argtypes = [vp, vp, i64, vp, f32, f32, vp, vp, vp, vp, vp, vp]
     lib.cgnn_edge_attr_backward.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp]
+    lib.cgnn_edge_attr_backward_rows.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]
+    lib.cgnn_rows_to_frames.argtypes = [vp, vp, vp, i32, i64, i64, vp, vp, vp]
+    lib.cgnn_frame_grad_rows.argtypes = [vp, vp, i64, i64, vp, vp, vp]
     lib.cgnn_balanced_planes_workspace_bytes.restype = sz
     lib.cgnn_balanced_planes_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.cgnn_balanced_planes.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]

@@ -4,6 +4,9 @@
 //                                    d x, d recent_pos, d y_acc, d y_temp_rate
 //   cgnn_rollout_integrate_backward  transpose of cgnn_rollout_integrate
 //   cgnn_edge_attr_backward          transpose of the k-NN's edge features: d pos from d edge_attr
+//   cgnn_edge_attr_backward_rows     the same over a shard's local rows [owned | ghosts]
+//   cgnn_rows_to_frames              transpose of the row gathers of the sample / the integration (rows -> whole frames)
+//   cgnn_frame_grad_rows             transpose of cgnn_frame_unpack (whole-frame gradient -> the rows a rank integrated)
 //
 // remainder and wrap are piecewise translations, |disp| is smooth away from 0: every link is a small linear map per
 // particle, and these kernels are its exact transpose in float32, one rounding per operation in a fixed order, without
@@ -150,18 +153,23 @@ __device__ __forceinline__ void edge_attr_grad(const float4* __restrict__ d_ea, 
     }
 }
 
+// Shard form: n_recv receivers with k edges each (edge e = r k + j), senders index a table of n_pos >= n_recv position rows
+// [owned | ghosts], the CSR covers all n_pos rows.  Rows past n_recv receive nothing as receivers.  n_pos == n_recv is the
+// one-graph case (cgnn_edge_attr_backward): the same operations in the same order.
 __global__ void edge_attr_backward_kernel(const float4* __restrict__ d_ea, const float4* __restrict__ ea,
-                                          const int32_t* __restrict__ senders, int64_t n, int k,
+                                          const int32_t* __restrict__ senders, int64_t n_recv, int64_t n_pos, int k,
                                           const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                           float* __restrict__ d_pos) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const int64_t ne = n * k;
+    if (r >= n_pos) return;
+    const int64_t ne = n_recv * k;
     float acc[3] = {0.f, 0.f, 0.f}, g[3];
-    for (int j = 0; j < k; ++j) {
-        edge_attr_grad(d_ea, ea, r * k + j, g);
+    if (r < n_recv) {
+        for (int j = 0; j < k; ++j) {
+            edge_attr_grad(d_ea, ea, r * k + j, g);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = __fsub_rn(acc[c], g[c]);
+            for (int c = 0; c < 3; ++c) acc[c] = __fsub_rn(acc[c], g[c]);
+        }
     }
     int64_t p0 = row_ptr[r], p1 = row_ptr[r + 1];
     if (p0 < 0) p0 = 0;
@@ -175,6 +183,42 @@ __global__ void edge_attr_backward_kernel(const float4* __restrict__ d_ea, const
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) d_pos[r * 3 + c] = acc[c];
+}
+
+// ---- rows <-> whole frames (the links of a sharded unrolled step) ------------------------------------------------------
+// A rank's sample and integration read the rows `ids` of whole frames; their transposes put the rows' gradients back at
+// `ids` of whole-frame gradients (every other row zero: the entry clears the frames first), and the transpose of
+// cgnn_frame_unpack reads the whole-frame gradient [N, 4] (x, y, z, temperature) at the rows a rank integrated.  Pure
+// copies, one thread per row, ids unique within a rank (no atomics); an id outside [0, n_total) is skipped / reads zero.
+__global__ void rows_to_frames_kernel(const float* __restrict__ rows_pos, const float* __restrict__ rows_temp,
+                                      const int64_t* __restrict__ ids, int frames, int64_t n_rows, int64_t n_total,
+                                      float* __restrict__ frames_pos, float* __restrict__ frames_temp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t g = ids[i];
+    if (g < 0 || g >= n_total) return;
+    for (int f = 0; f < frames; ++f) {
+        if (rows_pos != nullptr) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) frames_pos[((int64_t)f * n_total + g) * 3 + c] = rows_pos[((int64_t)f * n_rows + i) * 3 + c];
+        }
+        if (rows_temp != nullptr) frames_temp[(int64_t)f * n_total + g] = rows_temp[(int64_t)f * n_rows + i];
+    }
+}
+
+__global__ void frame_grad_rows_kernel(const float4* __restrict__ grad, const int64_t* __restrict__ ids, int64_t n_rows,
+                                       int64_t n_total, float* __restrict__ d_new_pos, float* __restrict__ d_new_temp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t g = ids[i];
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (g >= 0 && g < n_total) v = grad[g];
+    if (d_new_pos != nullptr) {
+        d_new_pos[i * 3 + 0] = v.x;
+        d_new_pos[i * 3 + 1] = v.y;
+        d_new_pos[i * 3 + 2] = v.z;
+    }
+    if (d_new_temp != nullptr) d_new_temp[i] = v.w;
 }
 
 }  // namespace cgnn
@@ -226,6 +270,22 @@ int cgnn_rollout_integrate_backward(const float* d_new_pos, const float* d_new_t
     return check_hip(hipGetLastError(), "cgnn_rollout_integrate_backward launch");
 }
 
+int cgnn_edge_attr_backward_rows(const float* d_edge_attr, const float* edge_attr, const int32_t* senders,
+                                 int64_t n_recv, int64_t n_pos, int32_t k, const int32_t* row_ptr, const int32_t* col,
+                                 float* d_pos, void* stream) {
+    if (n_recv < 0 || n_pos < n_recv || n_pos > INT32_MAX || k < 1 || n_recv * (int64_t)k > INT32_MAX ||
+        (n_recv > 0 && (!d_edge_attr || !edge_attr || !senders)) || (n_pos > 0 && (!row_ptr || !col || !d_pos)) ||
+        ((uintptr_t)d_edge_attr & 15) != 0 || ((uintptr_t)edge_attr & 15) != 0) {
+        set_error("cgnn_edge_attr_backward_rows: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n_pos == 0) return CGNN_OK;
+    edge_attr_backward_kernel<<<(unsigned)((n_pos + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        reinterpret_cast<const float4*>(d_edge_attr), reinterpret_cast<const float4*>(edge_attr), senders, n_recv, n_pos, k,
+        row_ptr, col, d_pos);
+    return check_hip(hipGetLastError(), "cgnn_edge_attr_backward_rows launch");
+}
+
 int cgnn_edge_attr_backward(const float* d_edge_attr, const float* edge_attr, const int32_t* senders, int64_t n,
                             int32_t k, const int32_t* row_ptr, const int32_t* col, float* d_pos, void* stream) {
     if (n < 0 || n > INT32_MAX || k < 1 || n * (int64_t)k > INT32_MAX ||
@@ -234,11 +294,46 @@ int cgnn_edge_attr_backward(const float* d_edge_attr, const float* edge_attr, co
         set_error("cgnn_edge_attr_backward: invalid argument");
         return CGNN_ERR_INVALID_ARG;
     }
-    if (n == 0) return CGNN_OK;
-    edge_attr_backward_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
-        reinterpret_cast<const float4*>(d_edge_attr), reinterpret_cast<const float4*>(edge_attr), senders, n, k, row_ptr,
-        col, d_pos);
-    return check_hip(hipGetLastError(), "cgnn_edge_attr_backward launch");
+    return cgnn_edge_attr_backward_rows(d_edge_attr, edge_attr, senders, n, n, k, row_ptr, col, d_pos, stream);
+}
+
+int cgnn_rows_to_frames(const float* rows_pos, const float* rows_temp, const int64_t* ids, int32_t frames, int64_t n_rows,
+                        int64_t n_total, float* frames_pos, float* frames_temp, void* stream) {
+    if (frames < 1 || n_rows < 0 || n_total < 0 || n_total > INT32_MAX || (!frames_pos && !frames_temp) ||
+        (n_rows > 0 && (!ids || (frames_pos && !rows_pos) || (frames_temp && !rows_temp)))) {
+        set_error("cgnn_rows_to_frames: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_total == 0) return CGNN_OK;
+    if (frames_pos) {
+        int rc = check_hip(hipMemsetAsync(frames_pos, 0, (size_t)frames * n_total * 3 * sizeof(float), st),
+                           "cgnn_rows_to_frames memset");
+        if (rc != CGNN_OK) return rc;
+    }
+    if (frames_temp) {
+        int rc = check_hip(hipMemsetAsync(frames_temp, 0, (size_t)frames * n_total * sizeof(float), st),
+                           "cgnn_rows_to_frames memset");
+        if (rc != CGNN_OK) return rc;
+    }
+    if (n_rows == 0) return CGNN_OK;
+    rows_to_frames_kernel<<<(unsigned)((n_rows + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
+        frames_pos ? rows_pos : nullptr, frames_temp ? rows_temp : nullptr, ids, frames, n_rows, n_total, frames_pos,
+        frames_temp);
+    return check_hip(hipGetLastError(), "cgnn_rows_to_frames launch");
+}
+
+int cgnn_frame_grad_rows(const float* grad, const int64_t* ids, int64_t n_rows, int64_t n_total, float* d_new_pos,
+                         float* d_new_temp, void* stream) {
+    if (n_rows < 0 || n_total < 0 || n_total > INT32_MAX || (!d_new_pos && !d_new_temp) ||
+        (n_rows > 0 && (!ids || (n_total > 0 && !grad))) || ((uintptr_t)grad & 15) != 0) {
+        set_error("cgnn_frame_grad_rows: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n_rows == 0) return CGNN_OK;
+    frame_grad_rows_kernel<<<(unsigned)((n_rows + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        reinterpret_cast<const float4*>(grad), ids, n_rows, n_total, d_new_pos, d_new_temp);
+    return check_hip(hipGetLastError(), "cgnn_frame_grad_rows launch");
 }
 
 }  // extern "C"

@@ -52,6 +52,7 @@ def tile_grid(world: int) -> Tuple[int, int, int]:
 
 
 DECOMPOSITIONS = ("uniform", "balanced")
+ROW_ORDERS = ("knn", "spatial")
 
 
 @dataclass
@@ -195,7 +196,7 @@ def _near_tile(pos: torch.Tensor, box_size: float, lo, hi, margin: float) -> tor
 
 def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, rank: int,
                 knn_fn: Optional[Callable] = None, margin_factor: float = 2.0,
-                decomposition: str = "uniform", *, min_image_edge_attr: bool = False,
+                decomposition: str = "uniform", *, row_order: str = "knn", min_image_edge_attr: bool = False,
                 knn_grid: str = "uniform") -> Shard:
     """Everything rank ``rank`` can derive locally from the global positions: its owned set, their k-NN
     senders, the ghost set and the global->local renumbering.  ``knn_fn(pos, box, k, query_ids)`` defaults to
@@ -217,9 +218,16 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
 
     ``min_image_edge_attr``: the default search writes minimum-image edge features (``ops.knn_periodic``); the search
     over the tile's subset ranks the same periodic images as the global one, so the rows are the global graph's.  A
-    caller's ``knn_fn`` decides for itself."""
+    caller's ``knn_fn`` decides for itself.
+
+    ``row_order``: how the owned rows are numbered.  ``"knn"`` (default): the search's own cell order, which fills a
+    cell through an atomic cursor, so two builds of one shard may number the particles of a cell differently (and
+    float32 sums over the rows then differ in their last bits).  ``"spatial"``: ``training.spatial_order`` of the
+    searched subset, a pure function of the positions: two builds give the same shard (``sharded_unrolled_loss``)."""
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"build_shard: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
+    if row_order not in ROW_ORDERS:
+        raise ValueError(f"build_shard: row_order {row_order!r}; known: {ROW_ORDERS}")
     ops.check_knn_grid(knn_grid, "build_shard")
     ops.check_min_image(min_image_edge_attr, "build_shard")
     dev = pos_global.device
@@ -271,7 +279,10 @@ def build_shard(pos_global: torch.Tensor, box_size: float, k: int, world: int, r
         owned_s = torch.nonzero(own_sub == rank).squeeze(1)            # indices into the subset
         # a one-query pass builds the cell grid and yields the spatial (cell-sorted) order, so that the local
         # numbering is cache friendly; then the real pass over the owned queries in that order
-        if owned_s.numel():
+        if owned_s.numel() and row_order == "spatial":
+            order = training.spatial_order(pos_sub, box_size).long()
+            owned_s = order[own_sub[order] == rank]
+        elif owned_s.numel():
             _, _, order = timed_knn(pos_sub, box_size, k, owned_s[:1].to(torch.int32))
             if order is not None:
                 order = order.long()
@@ -670,9 +681,16 @@ class ShardedForward:
 # sharded training (message_source="x_j")
 # ----------------------------------------------------------------------------
 
-def _all_reduce_(t: torch.Tensor, group=None) -> torch.Tensor:
-    """In-place SUM over the group."""
+def _group_up() -> bool:
     import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized()
+
+
+def _all_reduce_(t: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place SUM over the group (no process group up: a world of one, ``t`` as it is)."""
+    import torch.distributed as dist
+    if not _group_up():
+        return t
     return _collective(dist.all_reduce, t, group=group)()
 
 
@@ -690,7 +708,8 @@ class _AllReduceSum(torch.autograd.Function):
 
 
 def sharded_training_loss(pred: dict, y_acc: torch.Tensor, y_tr: torch.Tensor, n_total: int, dt: float,
-                          acc_w: float = 1.0, tr_w: float = 1.0, mom_w: float = 0.0, group=None, batch=None):
+                          acc_w: float = 1.0, tr_w: float = 1.0, mom_w: float = 0.0, group=None, batch=None,
+                          terms: bool = False):
     """The reference's ``combined_loss`` (train.py:255-260) of a snapshot split over the ranks, from this rank's owned
     predictions ``pred`` and targets.  Returns ``(loss_to_backprop, global_value)``:
 
@@ -701,16 +720,25 @@ def sharded_training_loss(pred: dict, y_acc: torch.Tensor, y_tr: torch.Tensor, n
       of its gradient once;
     * ``global_value`` (0-d float64) is the all-reduced loss, the value ``combined_loss`` has on the whole snapshot.
 
-    Summing the ranks' parameter gradients of ``loss_to_backprop`` gives the gradient of ``global_value``."""
+    Summing the ranks' parameter gradients of ``loss_to_backprop`` gives the gradient of ``global_value``.
+
+    ``terms=True`` returns ``(loss_to_backprop, global_value, global_terms)``, ``global_terms`` float64 ``[3]``: the two
+    global means and the momentum term, what ``unrolled_loss`` reports per step (the same collectives: the two partial
+    sums travel in one all-reduce)."""
     from .losses import _SegmentColsum
     if batch is not None:
         raise NotImplementedError("sharded training takes one graph (snapshot) per shard; multi-graph batches are not "
                                   "supported")
     acc, tr = pred["acceleration"], pred["temp_rate"]
-    mse = acc_w * ((acc - y_acc) ** 2).sum() / float(n_total * acc.shape[1]) + \
-        tr_w * ((tr - y_tr) ** 2).sum() / float(n_total * tr.shape[1])
+    acc_part = ((acc - y_acc) ** 2).sum() / float(n_total * acc.shape[1])
+    tr_part = ((tr - y_tr) ** 2).sum() / float(n_total * tr.shape[1])
+    mse = acc_w * acc_part + tr_w * tr_part
     sums = _AllReduceSum.apply(_SegmentColsum.apply(acc, None, 1), group)          # [1, 3] float64, global
     mom = (mom_w * torch.sum((sums * float(dt)) ** 2)).to(torch.float32)
+    if terms:
+        parts = _all_reduce_(torch.stack([acc_part.detach().double(), tr_part.detach().double()]), group)
+        value = acc_w * parts[0] + tr_w * parts[1] + mom.detach().double()
+        return mse + mom, value, torch.stack([parts[0], parts[1], mom.detach().double()])
     part = mse.detach().double().reshape(1).clone()
     value = _all_reduce_(part, group)[0] + mom.detach().double()
     return mse + mom, value
@@ -745,7 +773,11 @@ class ShardedTraining(NodeStreamSteps):
 
     The pieces are methods so that one process can interleave several shards (tests); ``__call__`` runs them through a
     ``torch.autograd.Function`` for a real process group.  ``halo`` needs ``start`` / ``finish`` and ``start_return`` /
-    ``finish_return`` (:class:`HaloExchange`, the default)."""
+    ``finish_return`` (:class:`HaloExchange`, the default).
+
+    A rank that owns nothing (``n_owned == 0``, hence no edges and no ghosts) launches no kernel: every piece returns
+    empty rows or zero parameter gradients, and the exchanges and the gradient all-reduce around the pieces run as on
+    every other rank, with empty blocks."""
 
     def __new__(cls, model, shard: Shard, halo=None, group=None):
         if cls is ShardedTraining and model.message_source == "edge" and getattr(model, "train_edge_messages", False):
@@ -779,7 +811,7 @@ class ShardedTraining(NodeStreamSteps):
         with torch.no_grad():
             m._materialize_all(x0.shape[1], sh.edge_attr.shape[1])
             self.packs = m._train_packs()       # refuses what the training kernels do not take (CgnnError)
-        if self._csr is None:
+        if self._csr is None and sh.n_owned:
             self._csr = ops.SenderCsr(sh.src_local, sh.dst_local, sh.n_local)       # senders <- receivers, once per shard
             self._plan = halo_return_plan(sh.send_idx.to(x0.device), sh.send_counts, sh.n_owned)
 
@@ -791,8 +823,11 @@ class ShardedTraining(NodeStreamSteps):
         if x0.shape[0] != sh.n_owned:
             raise CgnnError(f"ShardedTraining: {x0.shape[0]} input rows for {sh.n_owned} owned particles")
         self._prepare(x0)
-        self._encode(self.packs, x0)
         D = self.packs.latent
+        if sh.n_owned == 0:
+            self.x0, self.xs, self.aggs = x0, [x0.new_empty((0, D))], []
+        else:
+            self._encode(self.packs, x0)
         if self._table is None or tuple(self._table.shape) != (sh.n_local, D) or self._table.device != x0.device:
             self._table = torch.empty((sh.n_local, D), dtype=torch.float32, device=x0.device)
 
@@ -811,11 +846,39 @@ class ShardedTraining(NodeStreamSteps):
         if b > a:
             self._round_nodes(i, self._table, _src_part(self, a, b), None, sh.k, a, b)
 
-    # -- backward pieces (decode_backward, encode_backward, local_grads: NodeStreamSteps) --------------------------------
+    def decode(self):
+        if self.sh.n_owned == 0:
+            p, x = self.packs, self.x0
+            return x.new_empty((0, p.dec_acc.out_dim)), x.new_empty((0, p.dec_tr.out_dim))
+        return super().decode()
+
+    # -- backward pieces (local_grads: NodeStreamSteps) ------------------------------------------------------------------
+    def _zero_grads(self, packed) -> None:
+        """No rows: the parameter gradients of the MLPs ``packed`` are zeros (this rank's term of the all-reduce)."""
+        for m in packed:
+            self.grads_of[id(m)] = [torch.zeros_like(q, memory_format=torch.contiguous_format) for q in m.params()]
+
+    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
+        if self.sh.n_owned == 0:
+            self.grads_of, self.scratch = {}, None
+            self._zero_grads(self.packs.all)
+            self.dx = self.x0.new_empty((0, self.packs.latent))
+            return
+        super().decode_backward(d_acc, d_tr)
+
+    def encode_backward(self, need_dx0: bool = True) -> Optional[torch.Tensor]:
+        if self.sh.n_owned == 0:
+            self.dx = None
+            return torch.zeros_like(self.x0) if need_dx0 else None
+        return super().encode_backward(need_dx0)
+
     def round_backward_local(self, i: int) -> torch.Tensor:
         """Steps 1-2 of round ``i``: the node MLP's backward on the owned rows, then ``A^T du2`` for the ghost rows,
         written into (and returned as) the send buffer of the reverse exchange, [n_ghost, D]."""
         sh = self.sh
+        if sh.n_owned == 0:
+            self._du = None
+            return self.x0.new_empty((0, self.packs.latent))
         self._du = du1, du2 = self.round_backward(i)
         shape = (sh.n_ghost, self.packs.latent)
         if self._ghost is None or tuple(self._ghost.shape) != shape or self._ghost.device != du2.device:
@@ -826,6 +889,8 @@ class ShardedTraining(NodeStreamSteps):
 
     def round_backward_owned(self, i: int) -> None:
         """Step 4 (runs under the reverse exchange): ``dx <- dx + du1 + A^T du2`` on the owned rows."""
+        if self.sh.n_owned == 0:
+            return
         du1, du2 = self._du
         self._du = None
         ops.aggregate_csr(du2, self._csr, out=self.dx, add1=self.dx, add2=du1, row_range=(0, self.sh.n_owned))
@@ -951,7 +1016,7 @@ class ShardedEdgeTraining(ShardedTraining):
                                 f"({sh.n_owned * sh.k} local edges, {sh.n_local} local rows, latent {D}, hidden {H}, {L} "
                                 f"rounds); {free / 2**30:.1f} GiB are free")
             self.packs = m._train_packs(edge=True)      # refuses what the edge training kernels do not take (CgnnError)
-        if self._csr is None:
+        if self._csr is None and sh.n_owned:
             self._csr = ops.SenderCsr(sh.src_local, None, sh.n_local)      # the local edges by sender, once per shard
             self._plan = halo_return_plan(sh.send_idx.to(x0.device), sh.send_counts, sh.n_owned)
 
@@ -969,6 +1034,9 @@ class ShardedEdgeTraining(ShardedTraining):
         p = self.packs
         self.x0, self.edge_attr = x0, ea
         D, H, dev = p.latent, p.hidden, x0.device
+        if sh.n_owned == 0:         # no rows, no edges, no ghosts: nothing to encode
+            self.xs, self.es, self.aggs = [x0.new_empty((0, D))], [], []
+            return
         self.xs = [torch.empty((sh.n_local if p.rounds else sh.n_owned, D), dtype=torch.float32, device=dev)]
         ops.mlp_rows(p.enc.fwd, x0, out=self.xs[0][:sh.n_owned])
         self.es = [ops.mlp_rows(p.enc_edge.fwd, ea, tiled=True)]       # raw features: three bf16 terms or exact
@@ -983,6 +1051,9 @@ class ShardedEdgeTraining(ShardedTraining):
         sh, p = self.sh, self.packs
         last = i + 1 == len(p.rounds)
         dev = self.x0.device
+        if sh.n_owned == 0:
+            self.xs.append(self.x0.new_empty((0, p.latent)))
+            return self.xs[i]
         self.aggs.append(torch.empty((sh.n_owned, p.latent), dtype=torch.float32, device=dev))
         self.xs.append(torch.empty((sh.n_owned if last else sh.n_local, p.latent), dtype=torch.float32, device=dev))
         if not last:
@@ -1003,6 +1074,8 @@ class ShardedEdgeTraining(ShardedTraining):
         the exchange; projects the owned rows), ``"boundary"`` (after it; projects the ghost rows) or ``"all"``."""
         sh, p = self.sh, self.packs
         no, k = sh.n_owned, sh.k
+        if no == 0:
+            return
         a, b = {"all": (0, no), "interior": (0, self.n_split), "boundary": (self.n_split, no)}[part]
         if part != "boundary":
             self._project(i, "owned")
@@ -1025,6 +1098,9 @@ class ShardedEdgeTraining(ShardedTraining):
     # -- backward pieces ---------------------------------------------------------------------------------------------
     def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
         super().decode_backward(d_acc, d_tr)
+        if self.sh.n_owned == 0:
+            self._zero_grads([self.packs.enc_edge] + self.packs.edges)
+            return
         p, ne, dev = self.packs, self.es[0].n, self.x0.device
         self._escratch = ops.BackwardScratch(ne, p.hidden, max(p.latent, 32), p.nh, dev)
         self._dy = torch.empty((max(ne, 1), p.latent), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i
@@ -1036,6 +1112,9 @@ class ShardedEdgeTraining(ShardedTraining):
         buffer of the reverse exchange, [n_ghost, H]."""
         sh, p = self.sh, self.packs
         no = sh.n_owned
+        if no == 0:
+            self._round = i
+            return self.x0.new_empty((0, p.hidden))
         r, ep = p.rounds[i], p.edges[i]
         agg = self.aggs[i]
         self.aggs[i] = None
@@ -1057,6 +1136,8 @@ class ShardedEdgeTraining(ShardedTraining):
     def round_backward_owned(self, i: int) -> None:
         """Step 6 (runs under the reverse exchange): the edge-row reductions, ``dPs`` of the owned rows and ``dPd``."""
         sh, ep = self.sh, self.packs.edges[i]
+        if sh.n_owned == 0:
+            return
         no, g_a0 = sh.n_owned, self._escratch.g_a[0]
         self._row_grads = training.edge_row_grads(ep, self._escratch, self._dy, self.es[i])
         self._dps = ops.aggregate_csr(g_a0, self._csr, row_range=(0, no))
@@ -1067,6 +1148,8 @@ class ShardedEdgeTraining(ShardedTraining):
         """Steps 7-8: the ``dPs`` rows the peers returned, added at the rows they had requested; ``dWs`` / ``dWd`` / ``db1``
         over the owned rows; ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``."""
         i, no = self._round, self.sh.n_owned
+        if no == 0:
+            return
         ep = self.packs.edges[i]
         if ret.shape[0]:
             ops.halo_return_add(self._dps, ret, *self._plan)
@@ -1082,6 +1165,9 @@ class ShardedEdgeTraining(ShardedTraining):
         edges when ``need_dea``, else None."""
         p = self.packs
         dx0 = super().encode_backward(need_dx0)
+        if self.sh.n_owned == 0:
+            self.d_edge_attr = torch.zeros_like(self.edge_attr) if need_dea else None
+            return dx0
         de = self._de
         if not p.rounds:
             de.buf.zero_()                  # no round reads the edge encoder's output
@@ -1212,6 +1298,8 @@ def window_checksum(coords_w: torch.Tensor, energy_w: torch.Tensor) -> torch.Ten
 
 def _all_reduce_max_(t: torch.Tensor, group=None) -> torch.Tensor:
     import torch.distributed as dist
+    if not _group_up():
+        return t
     return _collective(dist.all_reduce, t, op=dist.ReduceOp.MAX, group=group)()
 
 
@@ -1867,3 +1955,269 @@ def build_synthetic_shard(particles_per_gpu: int, world: int, rank: int, k: int,
     # node features of the owned particles: the same kernel data_utils.preprocess uses
     sh.x_feat, _ = ops.window_features(coords[:W].to(device).contiguous(), energy[:W].to(device).contiguous(), metadata, dt, box)
     return sh
+
+
+# ----------------------------------------------------------------------------
+# multi-step training over spatial shards (training.unrolled_loss over the ranks of a group)
+# ----------------------------------------------------------------------------
+#
+# Frames are replicated: every rank holds the W true frames and every predicted frame of all N particles, and keeps
+# activations only for the rows it owns.  A predicted frame is made from rows that each rank integrated (one all-gather,
+# cgnn_frame_unpack) and is later read by other ranks' rows: a particle that changed tile, and under
+# message_source="edge" every ghost sender's position.  The transpose of that all-gather is the sum over the ranks of
+# every rank's gradient of the frame (:func:`reduce_frame_gradient`), of which each rank takes the rows it integrated.
+#
+# Every rank issues the same collectives in the same order whatever it owns: the links below never skip on a row count
+# or on a missing gradient (the publish link materialises zeros), and every rank builds the same autograd structure.
+
+class _LocalHalo:
+    """The halo of a world of one without a process group: a tile that is the whole box has no ghosts."""
+
+    def start(self, table: torch.Tensor):
+        return None
+
+    def finish(self, handle) -> None:
+        pass
+
+    def __call__(self, table: torch.Tensor) -> None:
+        pass
+
+    def start_return(self, grad_ghost: torch.Tensor):
+        return grad_ghost.new_empty((0, grad_ghost.shape[1]))
+
+    def finish_return(self, handle) -> torch.Tensor:
+        return handle
+
+
+def reduce_frame_gradient(grad: torch.Tensor, group=None) -> torch.Tensor:
+    """The transpose of a predicted frame's all-gather: ``grad [N, 4]`` (three position components and the temperature of
+    every particle: this rank's contributions to the gradient of one predicted frame) summed over the ranks, in place,
+    by one all-reduce of ``16 N`` bytes.  Every rank then reads the rows it integrated (``ops.frame_grad_rows``)."""
+    return _all_reduce_(grad, group)
+
+
+class _PublishLink(torch.autograd.Function):
+    """Rows a rank integrated -> the next frame of all particles.  Forward: the packed ``block [cap, ROLLOUT_ROW]`` of
+    every rank gathered (one all-gather; a world of one keeps its block) and scattered by ``cgnn_frame_unpack`` into
+    ``(pos [N, 3], temp [N])``.  ``new_pos [R, 3]`` / ``new_temp [R]`` are the block's differentiable rows (particles
+    ``ids``).  Backward: the frame's gradient as ``[N, 4]``, zeros where no gradient arrived, summed over the ranks
+    (:func:`reduce_frame_gradient`), read at ``ids`` (``cgnn_frame_grad_rows``)."""
+
+    @staticmethod
+    def forward(ctx, new_pos, new_temp, block, ids, n_total: int, group, gather: bool):
+        rows = all_gather_rows(block, group) if gather else block
+        dev = block.device
+        # NaN until published: a particle no rank delivered cannot pass for a result
+        pos = torch.full((n_total, 3), float("nan"), dtype=torch.float32, device=dev)
+        temp = torch.full((n_total,), float("nan"), dtype=torch.float32, device=dev)
+        ops.frame_unpack(rows, pos, temp)
+        ctx.ids, ctx.n, ctx.group, ctx.dev = ids, int(n_total), group, dev
+        ctx.set_materialize_grads(False)
+        return pos, temp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_pos, d_temp):
+        n, dev = ctx.n, ctx.dev
+        grad = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        if d_pos is not None:
+            grad[:, :3] = d_pos
+        if d_temp is not None:
+            grad[:, 3] = d_temp.reshape(n)
+        grad = reduce_frame_gradient(grad, ctx.group)
+        d_new_pos, d_new_temp = ops.frame_grad_rows(grad, ctx.ids)
+        return d_new_pos, d_new_temp, None, None, None, None, None
+
+
+def publish_frame(new_pos: torch.Tensor, new_temp: torch.Tensor, ids: torch.Tensor, n_total: int, cap: int, group=None,
+                  block: Optional[torch.Tensor] = None):
+    """The publish link on its own: the rows ``new_pos [R, 3]`` / ``new_temp [R]`` of the particles ``ids`` a rank
+    integrated -> ``(pos [N, 3], temp [N])`` of all particles on every rank, differentiable in the rows.  ``cap``: the
+    common block size (at least every rank's row count); ``block``: the packed rows when ``cgnn_rollout_integrate``
+    made them already (``training._IntegrateRowsLink``), else they are packed here."""
+    r = ids.numel()
+    if block is None:
+        block = torch.zeros((int(cap), _lib.ROLLOUT_ROW), dtype=torch.float32, device=new_pos.device)
+        block.view(torch.int32)[:, _lib.ROLLOUT_ROW - 1] = -1
+        block[:r, :3] = new_pos.detach()
+        block[:r, 3] = new_temp.detach().reshape(r)
+        block.view(torch.int32)[:r, _lib.ROLLOUT_ROW - 1] = ids.to(torch.int32)
+    return _PublishLink.apply(new_pos, new_temp, block, ids, int(n_total), group, _group_up())
+
+
+def sharded_unrolled_training_bytes(n_owned: int, n_ghost: int, num_particles: int, num_neighbors: int, window: int,
+                                    latent: int, hidden: int, num_hidden_layers: int, rounds: int, steps: int,
+                                    edge_messages: bool = False) -> int:
+    """Device memory one rank of :func:`sharded_unrolled_loss` keeps alive until the backward: S times the shard's
+    one-step activations (``training.unrolled_training_bytes`` over the ``n_owned`` rows and their ``n_owned k`` edges;
+    under ``message_source="edge"`` also every round's input edge latents and local node table with its ghost rows,
+    :func:`shard_edge_training_bytes`), one backward scratch, and the replicated frames: the W true and S predicted
+    frames of all N particles, 16 bytes per particle and frame."""
+    n, ne, S = int(n_owned), int(n_owned) * int(num_neighbors), int(steps)
+    per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
+    scratch = (2 * num_hidden_layers + 3) * n * hidden
+    if edge_messages:
+        per_step += rounds * ne * latent + rounds * (n + int(n_ghost)) * latent + 3 * int(n_ghost)
+        scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    frames = (int(window) + S) * int(num_particles) * 4
+    return 4 * (S * per_step + scratch + frames)
+
+
+def _step_capacity(sh: Shard, world: int) -> int:
+    """The common send-block size of a step (``ShardedRollout.plan``): the largest owned count over the ranks, known on
+    every rank from the replicated owner map without a collective."""
+    if sh._counts is not None:
+        counts = sh._counts.tolist()
+    else:
+        counts, _ = rollout_capacity(sh._owner, world)
+    if counts[sh.rank] != sh.n_owned:
+        raise CgnnError(f"rank {sh.rank}: {sh.n_owned} owned particles, the owner map says {counts[sh.rank]}")
+    return max(counts)
+
+
+def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tensor,
+                          target_positions: torch.Tensor, target_temperatures: torch.Tensor, metadata: dict, *, dt: float,
+                          box_size: float, num_neighbors: int = 16, noise_std: float = 0.0,
+                          noise_seed: Optional[int] = None, noise_draw: int = 0, acc_loss_weight: float = 1.0,
+                          temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
+                          step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
+                          min_image_edge_attr: bool = False, knn_grid: str = "uniform", decomposition: str = "uniform",
+                          group=None, device=None) -> "training.UnrolledLoss":
+    """``training.unrolled_loss`` over the ranks of ``group`` (a world of one when no process group is up): the same
+    arguments and meaning, S model steps unrolled from one window and differentiated through the whole chain, each rank
+    computing the rows of its spatial tile.  Every rank passes the same windows and targets of all N particles (checked
+    once, by one all-reduce of a checksum).  ``message_source="x_j"``, or ``"edge"`` with ``model.train_edge_messages``;
+    ``train_precision`` "fp32" / "fp32x3"; one graph per call.
+
+    Frames are replicated (``(W + S) N 16`` bytes per rank); activations are kept for the owned rows only
+    (:func:`sharded_unrolled_training_bytes`; the ranks agree on the memory guard by one all-reduce after step 0's shard is
+    known, and raise ``CgnnError`` together).  Step s on a rank: the wrapped last frame of all particles (detached) ->
+    :func:`build_shard` (``row_order="spatial"``, so two calls give the same bits) and the ghost-id exchange, ownership
+    following the particles from step to step; the sample of the owned rows (step 0 with the counter-based noise, later
+    windows read the noisy frames, later targets are shifted by the last frame's noise); under ``"edge"`` the ghost
+    rows' wrapped positions, the shard's edge features being a differentiable function of the local rows;
+    :class:`ShardedTraining`; :func:`sharded_training_loss`; the integration of the owned rows; one all-gather into the
+    next frame.  In the backward one all-reduce per live link sums the ranks' gradients of a predicted frame
+    (:func:`reduce_frame_gradient`).
+
+    Returns a ``training.UnrolledLoss``: ``loss`` is this rank's part to call ``.backward()`` on (afterwards every
+    parameter's ``.grad`` is the global gradient on every rank), ``value`` the all-reduced global loss (0-d float64),
+    ``step_losses [S, 3]`` the global terms, ``frames`` the whole predicted frames, ``graphs`` ``None``.
+    ``noise_seed=None`` with noise in a world above one raises ``ValueError`` (``torch.initial_seed()`` differs between
+    ranks)."""
+    from . import data_utils
+    w, n, S, weights = training._unroll_arguments(model, position_seq, temperature_seq, target_positions,
+                                                  target_temperatures, step_weights, backprop_steps, num_neighbors,
+                                                  knn_grid, min_image_edge_attr)
+    if decomposition not in DECOMPOSITIONS:
+        raise ValueError(f"sharded_unrolled_loss: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
+    world, rank = _world_of(group)
+    noisy = float(noise_std) != 0.0
+    if noisy and noise_seed is None and world > 1:
+        raise ValueError("sharded_unrolled_loss: noise needs an explicit noise_seed in a world above one "
+                         "(torch.initial_seed() differs between ranks)")
+    k = int(num_neighbors)
+    distributed = _group_up()
+    if device is None:
+        device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
+    device = torch.device(device)
+    edge = getattr(model, "message_source", "x_j") == "edge"
+    tmp_in = temperature_seq.reshape(w, n)
+    tgt_t_in = target_temperatures.reshape(S, n)
+    if distributed:
+        check_same_data(torch.cat([position_seq, target_positions.to(position_seq.device)]),
+                        torch.cat([tmp_in, tgt_t_in.to(tmp_in.device)]), device, group)
+    cfg = training._LinkConfig(metadata, dt, box_size, n, device)
+    pos_w = _lib.f32c(position_seq.to(device), "position_seq")
+    tmp_w = _lib.f32c(tmp_in.to(device), "temperature_seq")
+    tgt_p = _lib.f32c(target_positions.to(device), "target_positions")
+    tgt_t = _lib.f32c(tgt_t_in.to(device), "target_temperatures")
+    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
+    seed = (torch.initial_seed() if noise_seed is None else int(noise_seed)) % 2 ** 64
+    std = float(noise_std)
+
+    def sample0(rows, want, targets=True):      # step 0: the counter-based noise is a function of the particle id
+        return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, std, seed, noise_draw,
+                                   tgt_p[0] if targets else None, tgt_t[0] if targets else None, rows, want,
+                                   stats=cfg.stats)
+
+    pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
+    tgt_p_s, tgt_t_s = tgt_p, tgt_t
+    if noisy:       # replicated, like the frames: the noisy frames later windows read, and the shift of every later target
+        nz = sample0(None, ("pos_noise", "temp_noise"), targets=False)
+        pos_frames = list((pos_w + nz["pos_noise"].permute(1, 0, 2)).unbind(0))
+        tmp_frames = list((tmp_w + nz["temp_noise"].t()).unbind(0))
+        if S > 1:
+            tgt_p_s = tgt_p + nz["pos_noise"][:, -1]
+            tgt_t_s = tgt_t + nz["temp_noise"][:, -1]
+        del nz
+    sample_want = ("x", "recent_pos", "y_acc", "y_temp_rate")
+    total, value = None, None
+    step_losses, out_p, out_t = [], [], []
+    for s in range(S):
+        with torch.no_grad():
+            if s == 0:
+                recent_all = sample0(None, ("recent_pos",), targets=False)["recent_pos"]
+            else:
+                recent_all = ops.training_sample(torch.stack([f.detach() for f in pos_frames[-2:]]),
+                                                 torch.stack([f.detach() for f in tmp_frames[-2:]]), cfg.meta, cfg.dt,
+                                                 cfg.box, 0.0, 0, 0, want=("recent_pos",), stats=cfg.stats)["recent_pos"]
+            if not bool(torch.isfinite(recent_all).all()):        # the neighbour search must never see a NaN position
+                raise CgnnError(f"sharded_unrolled_loss: the frame before step {s} holds non-finite positions (rows that "
+                                f"were never published, or a diverged model)")
+            sh = build_shard(recent_all, cfg.box, k, world, rank, decomposition=decomposition, knn_grid=knn_grid,
+                             min_image_edge_attr=min_image_edge_attr, row_order="spatial")
+            sh = exchange_requests(sh, group) if distributed else finish_shard(sh, sh.want_global)
+            cap = _step_capacity(sh, world)
+        if s == 0:      # the memory guard, agreed by all ranks: one all-reduce (max) of a flag
+            need = sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, n, k, w, model._latent_size,
+                                                   model._mlp_hidden_size, model._mlp_num_hidden_layers,
+                                                   len(model.processor), S, edge)
+            free = training.free_device_bytes(device)
+            flag = _all_reduce_max_(torch.tensor([1.0 if need > free else 0.0], device=device), group)
+            if float(flag[0]) > 0.0:
+                raise CgnnError(f"sharded_unrolled_loss: a rank lacks device memory for the activations of {S} steps "
+                                f"(rank {rank}: about {need / 2**30:.2f} GiB for {sh.n_owned} owned and {sh.n_ghost} ghost "
+                                f"rows of {n} particles, {k} neighbours, latent {model._latent_size}, "
+                                f"{len(model.processor)} rounds; {free / 2**30:.2f} GiB are free)")
+        own, ghosts = sh.owned_global, sh.ghost_global
+        window = (*pos_frames[-w:], *tmp_frames[-w:])
+        if s == 0:
+            s0 = sample0(own, sample_want)
+            x, recent, y_acc, y_tr = (s0[name] for name in sample_want)
+        else:
+            x, recent, y_acc, y_tr = training._SampleRowsLink.apply(cfg, own, sample_want, tgt_p_s[s], tgt_t_s[s], *window)
+        runner = ShardedTraining(model, sh, None if distributed else _LocalHalo(), group)
+        if edge:        # the shard's edge features as a function of the local rows [owned | ghosts]
+            if s == 0:
+                recent_g = sample0(ghosts, ("recent_pos",), targets=False)["recent_pos"]
+            else:
+                recent_g, = training._SampleRowsLink.apply(cfg, ghosts, ("recent_pos",), None, None, *window)
+            edge_attr = training._EdgeAttrRowsLink.apply(torch.cat([recent, recent_g]), sh.edge_attr, sh.src_local, k,
+                                                         sh.n_owned, lambda runner=runner: runner._csr)
+            pred = runner(x, edge_attr)
+        else:
+            pred = runner(x)
+        acc, rate = pred["acceleration"], pred["temp_rate"]
+        loss_s, value_s, terms = sharded_training_loss(pred, y_acc, y_tr.reshape(-1, 1), n, cfg.dt, acc_loss_weight,
+                                                       temp_rate_loss_weight, momentum_loss_weight, group, terms=True)
+        total = weights[s] * loss_s if total is None else total + weights[s] * loss_s
+        value = weights[s] * value_s if value is None else value + weights[s] * value_s
+        step_losses.append(terms.to(torch.float32))
+        # the next frame; link s feeds step s + 1 and carries gradient when it is one of the last `links`
+        live = s < S - 1 and s >= S - 1 - links
+        frames_in = (pos_frames[-2], pos_frames[-1], tmp_frames[-1])
+        if live:
+            rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, cap, acc, rate, *frames_in)
+            new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
+        else:
+            with torch.no_grad():
+                rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, cap, acc.detach(), rate.detach(),
+                                                                          *(f.detach() for f in frames_in))
+                new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
+        out_p.append(new_p.detach())
+        out_t.append(new_t.detach())
+        pos_frames.append(new_p)
+        tmp_frames.append(new_t)
+    frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
+    return training.UnrolledLoss(total, torch.stack(step_losses), frames, None, value)

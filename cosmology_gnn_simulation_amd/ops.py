@@ -882,6 +882,8 @@ def rollout_integrate_backward(d_new_pos: Optional[torch.Tensor], d_new_temp: Op
     widths = {"acc_pred": (nr, 3), "temp_rate_pred": (nr,), "p1": (nr, 3), "p2": (nr, 3), "t1": (nr,)}
     out = {name: torch.empty(widths[name], dtype=torch.float32, device=dev) for name in want}
     _same_device(d_new_pos, d_new_temp)
+    if nr == 0:
+        return out
     with _timed(what, dev):
         check(_lib.load().cgnn_rollout_integrate_backward(
             ptr(d_new_pos), ptr(d_new_temp), nr, stats, float(metadata["dt"]), float(metadata["box_size"]),
@@ -911,6 +913,100 @@ def edge_attr_backward(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, sende
                                                   d_pos.data_ptr(), stream_ptr(edge_attr.device)),
               "cgnn_edge_attr_backward")
     return d_pos
+
+
+def edge_attr_backward_rows(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, senders: torch.Tensor, k: int,
+                            n_recv: int, by_sender: "SenderCsr") -> torch.Tensor:
+    """The shard form of :func:`edge_attr_backward` (``cgnn_edge_attr_backward_rows``): ``n_recv`` receivers with ``k``
+    edges each, ``senders`` (int32) rows of a local table of ``n_pos = by_sender.rows >= n_recv`` positions ``[owned |
+    ghosts]``, ``by_sender = SenderCsr(senders, None, n_pos)``.  -> ``d_pos [n_pos, 3]``: a row below ``n_recv`` receives
+    minus the sum of its own ``k`` edges plus the edges it sends, a row from ``n_recv`` on only the edges it sends.
+    ``n_pos == n_recv`` gives :func:`edge_attr_backward`'s bits.  Zero rows launch nothing."""
+    what = "edge_attr_backward_rows"
+    d_edge_attr, edge_attr = f32c(d_edge_attr, "d_edge_attr"), f32c(edge_attr, "edge_attr")
+    senders = i32c(senders, "senders").reshape(-1)
+    k, nr, n = int(k), int(n_recv), int(by_sender.rows)
+    if k < 1 or not 0 <= nr <= n:
+        raise CgnnError(f"{what}: k {k}, {nr} receivers of {n} position rows")
+    if edge_attr.shape != (nr * k, 4) or d_edge_attr.shape != (nr * k, 4) or senders.numel() != nr * k:
+        raise CgnnError(f"{what}: edge_attr / d_edge_attr must be [{nr} * {k}, 4] with as many senders, got "
+                        f"{tuple(edge_attr.shape)}, {tuple(d_edge_attr.shape)}, {senders.numel()} senders")
+    if by_sender.col.numel() < nr * k:
+        raise CgnnError(f"{what}: the CSR holds {by_sender.col.numel()} edges, the list {nr * k}")
+    _same_device(d_edge_attr, edge_attr, senders, by_sender.row_ptr, by_sender.col)
+    d_pos = torch.empty((n, 3), dtype=torch.float32, device=edge_attr.device)
+    if n == 0:
+        return d_pos
+    with _timed(what, edge_attr.device):
+        check(_lib.load().cgnn_edge_attr_backward_rows(ptr(d_edge_attr) if nr else None, ptr(edge_attr) if nr else None,
+                                                       ptr(senders) if nr else None, nr, n, k,
+                                                       by_sender.row_ptr.data_ptr(), by_sender.col.data_ptr(),
+                                                       d_pos.data_ptr(), stream_ptr(edge_attr.device)),
+              "cgnn_edge_attr_backward_rows")
+    return d_pos
+
+
+def rows_to_frames(ids: torch.Tensor, n_total: int, rows_pos: Optional[torch.Tensor] = None,
+                   rows_temp: Optional[torch.Tensor] = None):
+    """Gradient rows back into whole frames (``cgnn_rows_to_frames``), the transpose of the row gathers of
+    ``training_sample(rows=)`` and ``rollout_integrate(ids=)``: ``rows_pos [F, R, 3]`` / ``rows_temp [F, R]`` (a single
+    frame may come as ``[R, 3]`` / ``[R]``; either may be ``None``) -> ``(frames_pos [F, N, 3] | None, frames_temp [F, N] |
+    None)`` with row ``ids[i]`` (int64, unique) of frame f holding row i and every other row zero; ids outside
+    ``[0, N)`` are skipped.  A copy; nothing is read back from the device."""
+    what = "rows_to_frames"
+    ids = _i64c(ids, "ids").reshape(-1)
+    r, n = ids.numel(), int(n_total)
+    if rows_pos is None and rows_temp is None:
+        raise CgnnError(f"{what}: no rows given")
+    frames = None
+    if rows_pos is not None:
+        rows_pos = f32c(rows_pos, "rows_pos")
+        if rows_pos.dim() == 2:
+            rows_pos = rows_pos.unsqueeze(0)
+        if rows_pos.dim() != 3 or tuple(rows_pos.shape[1:]) != (r, 3):
+            raise CgnnError(f"{what}: rows_pos must be [F, {r}, 3], got {tuple(rows_pos.shape)}")
+        frames = rows_pos.shape[0]
+    if rows_temp is not None:
+        rows_temp = f32c(rows_temp, "rows_temp")
+        if rows_temp.dim() == 1:
+            rows_temp = rows_temp.unsqueeze(0)
+        if rows_temp.dim() != 2 or rows_temp.shape[1] != r or (frames is not None and rows_temp.shape[0] != frames):
+            raise CgnnError(f"{what}: rows_temp must be [F, {r}], got {tuple(rows_temp.shape)}")
+        frames = rows_temp.shape[0]
+    if frames < 1 or n < 0:
+        raise CgnnError(f"{what}: {frames} frames of {n} particles")
+    dev = ids.device
+    _same_device(ids, rows_pos, rows_temp)
+    out_pos = None if rows_pos is None else torch.empty((frames, n, 3), dtype=torch.float32, device=dev)
+    out_temp = None if rows_temp is None else torch.empty((frames, n), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out_pos, out_temp
+    with _timed(what, dev):
+        check(_lib.load().cgnn_rows_to_frames(ptr(rows_pos) if r else None, ptr(rows_temp) if r else None,
+                                              ptr(ids) if r else None, frames, r, n, ptr(out_pos), ptr(out_temp),
+                                              stream_ptr(dev)), "cgnn_rows_to_frames")
+    return out_pos, out_temp
+
+
+def frame_grad_rows(grad: torch.Tensor, ids: torch.Tensor):
+    """The transpose of :func:`frame_unpack` (``cgnn_frame_grad_rows``): the gradient of a whole frame ``grad [N, 4]``
+    (x, y, z, temperature) read at ``ids`` (int64) -> ``(d_new_pos [R, 3], d_new_temp [R])``, what
+    :func:`rollout_integrate_backward` takes; an id outside ``[0, N)`` reads zero.  Zero rows launch nothing."""
+    what = "frame_grad_rows"
+    grad = f32c(grad, "grad")
+    ids = _i64c(ids, "ids").reshape(-1)
+    if grad.dim() != 2 or grad.shape[1] != 4:
+        raise CgnnError(f"{what}: grad must be [N, 4], got {tuple(grad.shape)}")
+    r, n, dev = ids.numel(), grad.shape[0], grad.device
+    _same_device(grad, ids)
+    d_pos = torch.empty((r, 3), dtype=torch.float32, device=dev)
+    d_temp = torch.empty((r,), dtype=torch.float32, device=dev)
+    if r == 0:
+        return d_pos, d_temp
+    with _timed(what, dev):
+        check(_lib.load().cgnn_frame_grad_rows(ptr(grad) if n else None, ids.data_ptr(), r, n, d_pos.data_ptr(),
+                                               d_temp.data_ptr(), stream_ptr(dev)), "cgnn_frame_grad_rows")
+    return d_pos, d_temp
 
 
 def _pos3(pos: torch.Tensor, what: str) -> torch.Tensor:
@@ -1239,6 +1335,8 @@ def segment_colsum(acc: torch.Tensor, batch: Optional[torch.Tensor], num_graphs:
     if batch is not None:
         batch = i32c(batch, "batch")
     n, width = acc.shape
+    if n == 0:          # a rank that owns nothing: zero sums, nothing launched
+        return torch.zeros((num_graphs, width), dtype=torch.float64, device=acc.device)
     sums = torch.empty((num_graphs, width), dtype=torch.float64, device=acc.device)
     _same_device(acc, batch)
     with _timed("segment_colsum", acc.device):

@@ -649,6 +649,109 @@ class _IntegrateLink(torch.autograd.Function):
         return (None, *(g.get(name) for name in names))
 
 
+# ---- the same links over the rows one rank holds (dist.sharded_unrolled_loss) ---------------------------------------------
+#
+# Frames are whole ([N, 3] / [N], replicated on every rank); a rank samples and integrates the rows it owns.  The forward
+# kernels take a row list already; the backward puts the rows' gradients back into whole-frame gradients, zero elsewhere
+# (``cgnn_rows_to_frames``), which the publish link (dist._PublishLink) sums over the ranks.  Zero rows launch nothing and
+# still return (zero) frame gradients: a rank that owns nothing keeps the autograd structure of every other rank.
+
+class _SampleRowsLink(torch.autograd.Function):
+    """:class:`_SampleLink` for the particles ``rows`` (int64 ids) of whole frames: the outputs named in ``want`` (of
+    ``x``, ``recent_pos``, ``y_acc``, ``y_temp_rate``), row i belonging to particle ``rows[i]``.  The backward is
+    ``cgnn_training_sample_backward`` on the compact rows followed by ``cgnn_rows_to_frames``."""
+
+    @staticmethod
+    def forward(ctx, cfg: _LinkConfig, rows, want, target_pos, target_temp, *frames):
+        w = len(frames) // 2
+        pos_w, tmp_w = torch.stack(frames[:w]), torch.stack(frames[w:])
+        s = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, 0.0, 0, 0, target_pos, target_temp, rows, want,
+                                stats=cfg.stats)
+        ctx.cfg, ctx.w, ctx.n, ctx.rows, ctx.want = cfg, w, pos_w.shape[1], rows, tuple(want)
+        ctx.set_materialize_grads(False)
+        return tuple(s[name] for name in want)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *d_out):
+        w, cfg, rows = ctx.w, ctx.cfg, ctx.rows
+        needs = ctx.needs_input_grad[5:]
+        first = min(t % w for t in range(2 * w) if needs[t])
+        g = dict(zip(ctx.want, d_out))
+        if all(d is None for d in d_out):
+            return (None,) * (5 + 2 * w)
+        d_pos, d_temp = ops.training_sample_backward(w, rows.numel(), cfg.meta, cfg.dt, cfg.box, d_x=g.get("x"),
+                                                     d_recent_pos=g.get("recent_pos"), d_y_acc=g.get("y_acc"),
+                                                     d_y_temp_rate=g.get("y_temp_rate"), rows=rows, n_total=ctx.n,
+                                                     first_frame=first, stats=cfg.stats)
+        f_pos, f_temp = ops.rows_to_frames(rows, ctx.n, d_pos[first:], d_temp[first:])
+        return (None,) * 5 + tuple(f_pos[t - first] if needs[t] else None for t in range(w)) + \
+            tuple(f_temp[t - first] if needs[w + t] else None for t in range(w))
+
+
+class _EdgeAttrRowsLink(torch.autograd.Function):
+    """A shard's edge features as a function of its local position rows ``[owned | ghosts]`` (``pos_local [n_local, 3]``):
+    the forward hands on the features the shard's neighbour search made (the global graph's rows), the backward is
+    ``cgnn_edge_attr_backward_rows``.  ``by_sender()`` returns ``ops.SenderCsr(src_local, None, n_local)`` (the one the
+    shard's training runner keeps)."""
+
+    @staticmethod
+    def forward(ctx, pos_local, edge_attr, src_local, k: int, n_recv: int, by_sender):
+        ctx.k, ctx.n_recv, ctx.n_local, ctx.by_sender = int(k), int(n_recv), pos_local.shape[0], by_sender
+        ctx.save_for_backward(edge_attr, src_local)
+        ctx.set_materialize_grads(False)
+        return edge_attr.view_as(edge_attr)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_edge_attr):
+        if d_edge_attr is None:
+            return (None,) * 6
+        edge_attr, src_local = ctx.saved_tensors
+        if ctx.n_local == 0:
+            return (torch.zeros((0, 3), dtype=torch.float32, device=edge_attr.device),) + (None,) * 5
+        return (ops.edge_attr_backward_rows(d_edge_attr, edge_attr, src_local, ctx.k, ctx.n_recv, ctx.by_sender()),) + \
+            (None,) * 5
+
+
+class _IntegrateRowsLink(torch.autograd.Function):
+    """:class:`_IntegrateLink` for the particles ``ids`` of whole frames ``p2`` / ``p1`` ``[N, 3]`` and ``t1 [N]``
+    (predictions row i = particle ``ids[i]``): -> ``(new_pos [R, 3], new_temp [R], block)``, ``block [n_out,
+    ROLLOUT_ROW]`` the packed rows ``cgnn_rollout_integrate`` made (what the ranks gather; not differentiable -- the two
+    row tensors are its differentiable view).  The backward is ``cgnn_rollout_integrate_backward`` on the rows, the frames'
+    gradients then go back to whole frames (``cgnn_rows_to_frames``)."""
+
+    @staticmethod
+    def forward(ctx, cfg: _LinkConfig, ids, n_out: int, acc_pred, rate_pred, p2, p1, t1):
+        block = ops.rollout_integrate(acc_pred, rate_pred, p2, p1, t1, ids, cfg.meta, n_out=n_out, stats=cfg.stats)
+        r = ids.numel()
+        ctx.cfg, ctx.ids, ctx.n = cfg, ids, p1.shape[0]
+        ctx.shapes = (rate_pred.shape, t1.shape)
+        ctx.mark_non_differentiable(block)
+        ctx.set_materialize_grads(False)
+        return block[:r, :3].contiguous(), block[:r, 3].contiguous(), block
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_new_pos, d_new_temp, _d_block):
+        names = ("acc_pred", "temp_rate_pred", "p2", "p1", "t1")
+        want = [name for name, need in zip(names, ctx.needs_input_grad[3:]) if need]
+        if (d_new_pos is None and d_new_temp is None) or not want:
+            return (None,) * 8
+        g = ops.rollout_integrate_backward(d_new_pos, d_new_temp, ctx.cfg.meta, want, stats=ctx.cfg.stats)
+        if "temp_rate_pred" in g:
+            g["temp_rate_pred"] = g["temp_rate_pred"].view(ctx.shapes[0])
+        if "p1" in g or "t1" in g:
+            f_pos, f_temp = ops.rows_to_frames(ctx.ids, ctx.n, g.get("p1"), g.get("t1"))
+            if "p1" in g:
+                g["p1"] = f_pos[0]
+            if "t1" in g:
+                g["t1"] = f_temp[0].view(ctx.shapes[1])
+        if "p2" in g:
+            g["p2"] = ops.rows_to_frames(ctx.ids, ctx.n, g["p2"], None)[0][0]
+        return (None, None, None, *(g.get(name) for name in names))
+
+
 def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
                             num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False) -> int:
     """Device memory S unrolled steps keep alive until the backward: S times the one-step activations -- the node
@@ -667,10 +770,12 @@ def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int,
 class UnrolledLoss:
     """Result of :func:`unrolled_loss`: ``loss`` (0-d float32 with a ``grad_fn``), ``step_losses`` (detached ``[S, 3]``:
     acceleration, temperature-rate and momentum term per step), ``frames`` (detached predicted ``Coordinates [S, N, 3]``
-    and ``InternalEnergy [S, N, 1]``) and ``graphs`` (the S ``Data`` objects under ``keep_graphs``, else ``None``)."""
+    and ``InternalEnergy [S, N, 1]``) and ``graphs`` (the S ``Data`` objects under ``keep_graphs``, else ``None``).
+    ``value``: ``None`` on one GPU; from ``dist.sharded_unrolled_loss`` the all-reduced global loss (0-d float64, the same
+    on every rank), ``loss`` then being this rank's part to differentiate."""
 
-    def __init__(self, loss, step_losses, frames, graphs):
-        self.loss, self.step_losses, self.frames, self.graphs = loss, step_losses, frames, graphs
+    def __init__(self, loss, step_losses, frames, graphs, value=None):
+        self.loss, self.step_losses, self.frames, self.graphs, self.value = loss, step_losses, frames, graphs, value
 
 
 def _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures, step_weights,
@@ -680,8 +785,8 @@ def _unroll_arguments(model, position_seq, temperature_seq, target_positions, ta
     ops.check_knn_grid(knn_grid, "unrolled_loss")
     ops.check_min_image(min_image_edge_attr, "unrolled_loss")
     if not isinstance(model, EncodeProcessDecode):
-        raise NotImplementedError("unrolled_loss trains one EncodeProcessDecode on one GPU; sharded training "
-                                  "(dist.ShardedTraining) unrolls no steps")
+        raise NotImplementedError("unrolled_loss trains one EncodeProcessDecode on one GPU; over spatial shards "
+                                  "dist.sharded_unrolled_loss unrolls the steps (dist.ShardedTraining is one step)")
     if isinstance(position_seq, (list, tuple)) or not torch.is_tensor(position_seq) or position_seq.dim() == 4:
         raise NotImplementedError("unrolled_loss takes one graph per call ([W, N, 3]); multi-graph batches are not "
                                   "unrolled")

@@ -575,7 +575,22 @@ int cgnn_training_sample(const float* pos_seq, const float* temp_seq, const floa
  * image shift is a constant).  g_e = d_disp + d_dist * disp / dist, the second term 0 where dist == 0;
  *   d_pos[r] = - sum_{j < k} g_{r k + j}  +  sum_{p in [row_ptr[r], row_ptr[r+1])} g_{col[p]}
  * in that order, (row_ptr int32 [n + 1], col int32 [n k]) the edges grouped by sender (cgnn_csr_build with val ==
- * NULL); an entry of col outside [0, n k) or whose sender is not r is skipped. */
+ * NULL); an entry of col outside [0, n k) or whose sender is not r is skipped.
+ *
+ * cgnn_edge_attr_backward_rows: the shard form.  n_recv receivers with k edges each (edge e = r k + j) whose senders
+ * index a local table of n_pos >= n_recv position rows [owned | ghosts]; (row_ptr int32 [n_pos + 1], col) groups the
+ * n_recv k edges by sender over all n_pos rows.  d_pos [n_pos, 3]: row r < n_recv receives both sums above, row r >=
+ * n_recv only the edges it sends.  n_pos == n_recv gives cgnn_edge_attr_backward's bits (that entry calls this one).
+ *
+ * cgnn_rows_to_frames: the transpose of the row gathers of cgnn_training_sample(rows) / cgnn_rollout_integrate(ids):
+ * gradient rows rows_pos [frames, n_rows, 3] / rows_temp [frames, n_rows] are written at ids [n_rows] (int64, unique)
+ * of frames_pos [frames, n_total, 3] / frames_temp [frames, n_total]; every other row of the frames is set to zero;
+ * ids outside [0, n_total) are skipped.  Either pair may be NULL, not both.  A copy: no arithmetic, no atomics, no
+ * host synchronisation; n_rows == 0 clears the frames and launches no kernel.
+ *
+ * cgnn_frame_grad_rows: the transpose of cgnn_frame_unpack: from the gradient of a whole frame grad [n_total, 4]
+ * (x, y, z, temperature; 16-byte aligned) the rows ids [n_rows] as d_new_pos [n_rows, 3] / d_new_temp [n_rows] (what
+ * cgnn_rollout_integrate_backward takes; either may be NULL, not both); an id outside [0, n_total) reads zero. */
 int cgnn_training_sample_backward(const float* d_x, const float* d_recent_pos, const float* d_y_acc,
                                   const float* d_y_temp_rate, int32_t window, int64_t n_total, const int64_t* rows,
                                   int64_t n_rows, int32_t first_frame, float box_size, float dt, float vel_std,
@@ -585,6 +600,13 @@ int cgnn_rollout_integrate_backward(const float* d_new_pos, const float* d_new_t
                                     float* d_p2, float* d_t1, void* stream);
 int cgnn_edge_attr_backward(const float* d_edge_attr, const float* edge_attr, const int32_t* senders, int64_t n,
                             int32_t k, const int32_t* row_ptr, const int32_t* col, float* d_pos, void* stream);
+int cgnn_edge_attr_backward_rows(const float* d_edge_attr, const float* edge_attr, const int32_t* senders,
+                                 int64_t n_recv, int64_t n_pos, int32_t k, const int32_t* row_ptr, const int32_t* col,
+                                 float* d_pos, void* stream);
+int cgnn_rows_to_frames(const float* rows_pos, const float* rows_temp, const int64_t* ids, int32_t frames, int64_t n_rows,
+                        int64_t n_total, float* frames_pos, float* frames_temp, void* stream);
+int cgnn_frame_grad_rows(const float* grad, const int64_t* ids, int64_t n_rows, int64_t n_total, float* d_new_pos,
+                         float* d_new_temp, void* stream);
 
 /* ---- sharded rollout step (reference render_rollout.py:73-85; one_step_test.py:84-105) ----------------------
  * A packed frame row is CGNN_ROLLOUT_ROW floats: (x, y, z, temperature, int32 particle id bit-cast to float);
