@@ -2045,20 +2045,35 @@ def publish_frame(new_pos: torch.Tensor, new_temp: torch.Tensor, ids: torch.Tens
     return _PublishLink.apply(new_pos, new_temp, block, ids, int(n_total), group, _group_up())
 
 
+def shard_record_bytes(n_owned: int, n_ghost: int, num_particles: int, num_neighbors: int) -> int:
+    """What one rank of ``sharded_unrolled_loss(checkpoint="steps")`` keeps of one step until the backward, the small
+    record: the replicated frame the step made (``16 N`` bytes) and the step's :class:`Shard` -- per edge its local
+    sender and receiver rows and its features (``24 k n_owned``), the global ids of the owned and ghost rows and the send
+    plan (``8 n_owned + 12 n_ghost``; the send plan counted at the ghost count).  The shard's whole-box maps (owner, global
+    -> local) are dropped once the step's send plan and capacity are known."""
+    n, g = int(n_owned), int(n_ghost)
+    return 16 * int(num_particles) + 24 * n * int(num_neighbors) + 8 * n + 12 * g
+
+
 def sharded_unrolled_training_bytes(n_owned: int, n_ghost: int, num_particles: int, num_neighbors: int, window: int,
                                     latent: int, hidden: int, num_hidden_layers: int, rounds: int, steps: int,
-                                    edge_messages: bool = False) -> int:
+                                    edge_messages: bool = False, checkpoint: str = "none") -> int:
     """Device memory one rank of :func:`sharded_unrolled_loss` keeps alive until the backward: S times the shard's
     one-step activations (``training.unrolled_training_bytes`` over the ``n_owned`` rows and their ``n_owned k`` edges;
     under ``message_source="edge"`` also every round's input edge latents and local node table with its ghost rows,
     :func:`shard_edge_training_bytes`), one backward scratch, and the replicated frames: the W true and S predicted
-    frames of all N particles, 16 bytes per particle and frame."""
+    frames of all N particles, 16 bytes per particle and frame.  ``checkpoint="steps"``: one step's activations, the
+    scratch, the W true frames and S small records (:func:`shard_record_bytes`, which holds a step's predicted frame)."""
+    training.check_checkpoint(checkpoint, "sharded_unrolled_training_bytes")
     n, ne, S = int(n_owned), int(n_owned) * int(num_neighbors), int(steps)
     per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
     scratch = (2 * num_hidden_layers + 3) * n * hidden
     if edge_messages:
         per_step += rounds * ne * latent + rounds * (n + int(n_ghost)) * latent + 3 * int(n_ghost)
         scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    if checkpoint == "steps":
+        return 4 * (per_step + scratch + int(window) * int(num_particles) * 4) + \
+            S * shard_record_bytes(n, n_ghost, num_particles, num_neighbors)
     frames = (int(window) + S) * int(num_particles) * 4
     return 4 * (S * per_step + scratch + frames)
 
@@ -2075,6 +2090,96 @@ def _step_capacity(sh: Shard, world: int) -> int:
     return max(counts)
 
 
+class _ShardedCheckpointedUnroll:
+    """The steps of one ``sharded_unrolled_loss(checkpoint="steps")`` call on one rank: :meth:`step` is one step of the
+    plain loop behind the shard build -- the samples of the owned (and ghost) rows, :class:`ShardedTraining` with its halo
+    exchanges, :func:`sharded_training_loss` with its all-reduces, the integration of the owned rows -- for the first run
+    of a checkpointed step (no autograd), its recomputation on the kept shard, and the last step.  Whatever a rank holds,
+    a step issues the same collectives in the same order: a rank that owns nothing runs it on empty blocks."""
+
+    def __init__(self, model, cfg, w: int, n: int, k: int, edge: bool, group, distributed: bool, loss_weights, sample0):
+        self.model, self.cfg, self.w, self.n, self.k, self.edge = model, cfg, w, n, k, edge
+        self.group, self.distributed, self.loss_weights, self.sample0 = group, distributed, loss_weights, sample0
+        self.params = list(model.parameters())
+
+    def step(self, rec, tgt_p, tgt_t, frames, integrate: bool):
+        """-> (this rank's weighted loss term, rows_pos | None, rows_temp | None, block | None); fills ``rec.value`` and
+        ``rec.terms`` (the global figures).  ``frames``: the W whole position frames, then the W temperature frames."""
+        cfg, w, n, k, sh = self.cfg, self.w, self.n, self.k, rec.shard
+        grad = torch.is_grad_enabled()
+        own, ghosts = sh.owned_global, sh.ghost_global
+        want = ("x", "recent_pos", "y_acc", "y_temp_rate")
+        if rec.s == 0:      # the counter-based noise again: the same (seed, draw), the same sample
+            s0 = self.sample0(own, want)
+            x, recent, y_acc, y_tr = (s0[name] for name in want)
+        else:
+            x, recent, y_acc, y_tr = training._SampleRowsLink.apply(cfg, own, want, tgt_p, tgt_t, *frames)
+        runner = ShardedTraining(self.model, sh, None if self.distributed else _LocalHalo(), self.group)
+        if self.edge:       # the shard's edge features as a function of the local rows [owned | ghosts]
+            if rec.s == 0:
+                recent_g = self.sample0(ghosts, ("recent_pos",), targets=False)["recent_pos"]
+            else:
+                recent_g, = training._SampleRowsLink.apply(cfg, ghosts, ("recent_pos",), None, None, *frames)
+            edge_attr = training._EdgeAttrRowsLink.apply(torch.cat([recent, recent_g]), sh.edge_attr, sh.src_local, k,
+                                                         sh.n_owned, lambda runner=runner: runner._csr)
+            pred = runner(x, edge_attr)
+        else:
+            pred = runner(x)
+        acc, rate = pred["acceleration"], pred["temp_rate"]
+        loss_s, rec.value, terms = sharded_training_loss(pred, y_acc, y_tr.reshape(-1, 1), n, cfg.dt, *self.loss_weights,
+                                                         self.group, terms=True)
+        rec.terms = terms.to(torch.float32)
+        rows_p = rows_t = block = None
+        if integrate:
+            frames_in = (frames[w - 2], frames[w - 1], frames[2 * w - 1])
+            if rec.live and grad:
+                rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, rec.cap, acc, rate, *frames_in)
+            else:
+                with torch.no_grad():
+                    rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, rec.cap, acc.detach(), rate.detach(),
+                                                                              *(f.detach() for f in frames_in))
+        return rec.weight * loss_s, rows_p, rows_t, block
+
+
+class _ShardedCheckpointedStep(torch.autograd.Function):
+    """``training._CheckpointedStep`` on one rank: ``(this rank's weighted loss term, rows_pos, rows_temp, block) =
+    step(W whole position frames, W temperature frames; parameters)`` on the step's shard.  The backward runs the step
+    again on the kept shard with autograd (halo exchanges and loss all-reduces included) and differentiates it at once
+    (reverse halo exchanges, the all-reduce of the parameter gradients).  The publish link stays outside: the frame is
+    known, and its backward hands this Function the gradient of the rows."""
+
+    @staticmethod
+    def forward(ctx, unroll: _ShardedCheckpointedUnroll, rec, tgt_p, tgt_t, *tensors):
+        frames = tensors[:2 * unroll.w]
+        loss_c, rows_p, rows_t, block = unroll.step(rec, tgt_p, tgt_t, frames, integrate=True)
+        ctx.unroll, ctx.rec = unroll, rec
+        ctx.save_for_backward(tgt_p, tgt_t, *frames)
+        ctx.mark_non_differentiable(*((block,) if rec.live else (rows_p, rows_t, block)))
+        ctx.set_materialize_grads(False)
+        return loss_c, rows_p, rows_t, block
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, d_rows_p, d_rows_t, _d_block):
+        unroll, rec = ctx.unroll, ctx.rec
+        tgt_p, tgt_t, *frames = ctx.saved_tensors
+        n_frames = len(frames)
+        link = rec.live and (d_rows_p is not None or d_rows_t is not None)
+        if d_loss is None and not link:     # no rank gets here: every step's loss term is part of the loss
+            return (None,) * (4 + n_frames + len(unroll.params))
+        needs = ctx.needs_input_grad[4:4 + n_frames]
+        with torch.enable_grad():
+            ins = [f.detach().requires_grad_(need) for f, need in zip(frames, needs)]
+            loss_c, rows_p, rows_t, _ = unroll.step(rec, tgt_p, tgt_t, ins, integrate=link)
+            outs = [(o, g) for o, g in ((loss_c, d_loss), (rows_p, d_rows_p), (rows_t, d_rows_t))
+                    if g is not None and o is not None and o.requires_grad]
+            wrt = [f for f, need in zip(ins, needs) if need] + [q for q in unroll.params if q.requires_grad]
+            grads = iter(torch.autograd.grad([o for o, _ in outs], wrt, [g for _, g in outs], allow_unused=True))
+        d_frames = [next(grads) if need else None for need in needs]
+        d_params = [next(grads) if q.requires_grad else None for q in unroll.params]
+        return (None, None, None, None, *d_frames, *d_params)
+
+
 def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tensor,
                           target_positions: torch.Tensor, target_temperatures: torch.Tensor, metadata: dict, *, dt: float,
                           box_size: float, num_neighbors: int = 16, noise_std: float = 0.0,
@@ -2082,7 +2187,7 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
                           temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
                           step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
                           min_image_edge_attr: bool = False, knn_grid: str = "uniform", decomposition: str = "uniform",
-                          group=None, device=None) -> "training.UnrolledLoss":
+                          group=None, device=None, checkpoint: str = "none") -> "training.UnrolledLoss":
     """``training.unrolled_loss`` over the ranks of ``group`` (a world of one when no process group is up): the same
     arguments and meaning, S model steps unrolled from one window and differentiated through the whole chain, each rank
     computing the rows of its spatial tile.  Every rank passes the same windows and targets of all N particles (checked
@@ -2104,11 +2209,20 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
     parameter's ``.grad`` is the global gradient on every rank), ``value`` the all-reduced global loss (0-d float64),
     ``step_losses [S, 3]`` the global terms, ``frames`` the whole predicted frames, ``graphs`` ``None``.
     ``noise_seed=None`` with noise in a world above one raises ``ValueError`` (``torch.initial_seed()`` differs between
-    ranks)."""
+    ranks).
+
+    ``checkpoint="steps"``: ``training.unrolled_loss``'s activation checkpointing across steps, with the same meaning.
+    Steps 0 .. S - 2 run without autograd; per step a rank keeps the :class:`Shard` (with the edge features its search
+    made), the send capacity and the frames (:func:`shard_record_bytes`), so the backward neither searches nor
+    synchronises with the host to build a shard.  The recomputation of a step runs :class:`ShardedTraining` with its
+    halo exchanges, :func:`sharded_training_loss` with its all-reduces, the sample links and the integration of the
+    owned rows again; the published frame is known and is not gathered again, its backward stays where it is.  Every
+    rank issues the same collectives in the same order whatever it holds: a rank that owns nothing recomputes with empty
+    blocks.  Frames, ``value`` and ``step_losses`` are those of ``"none"`` bit for bit."""
     from . import data_utils
     w, n, S, weights = training._unroll_arguments(model, position_seq, temperature_seq, target_positions,
                                                   target_temperatures, step_weights, backprop_steps, num_neighbors,
-                                                  knn_grid, min_image_edge_attr)
+                                                  knn_grid, min_image_edge_attr, checkpoint)
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"sharded_unrolled_loss: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
     world, rank = _world_of(group)
@@ -2152,6 +2266,10 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
             tgt_t_s = tgt_t + nz["temp_noise"][:, -1]
         del nz
     sample_want = ("x", "recent_pos", "y_acc", "y_temp_rate")
+    unroll, params = None, list(model.parameters())
+    if checkpoint == "steps" and S > 1 and any(q.requires_grad for q in params):
+        unroll = _ShardedCheckpointedUnroll(model, cfg, w, n, k, edge, group, distributed,
+                                            (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), sample0)
     total, value = None, None
     step_losses, out_p, out_t = [], [], []
     for s in range(S):
@@ -2172,16 +2290,39 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
         if s == 0:      # the memory guard, agreed by all ranks: one all-reduce (max) of a flag
             need = sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, n, k, w, model._latent_size,
                                                    model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                                   len(model.processor), S, edge)
+                                                   len(model.processor), S, edge, checkpoint)
             free = training.free_device_bytes(device)
             flag = _all_reduce_max_(torch.tensor([1.0 if need > free else 0.0], device=device), group)
             if float(flag[0]) > 0.0:
                 raise CgnnError(f"sharded_unrolled_loss: a rank lacks device memory for the activations of {S} steps "
-                                f"(rank {rank}: about {need / 2**30:.2f} GiB for {sh.n_owned} owned and {sh.n_ghost} ghost "
+                                f"under checkpoint={checkpoint!r} (rank {rank}: about {need / 2**30:.2f} GiB for {sh.n_owned} owned and {sh.n_ghost} ghost "
                                 f"rows of {n} particles, {k} neighbours, latent {model._latent_size}, "
                                 f"{len(model.processor)} rounds; {free / 2**30:.2f} GiB are free)")
         own, ghosts = sh.owned_global, sh.ghost_global
         window = (*pos_frames[-w:], *tmp_frames[-w:])
+        if unroll is not None:
+            # link s feeds step s + 1 and carries gradient when it is one of the last `links`
+            rec = training._StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
+            sh._g2l = sh._owner = None      # the whole-box maps have served (send plan, capacity): not part of the record
+            rec.shard, rec.cap = sh, cap
+            if s < S - 1:
+                loss_c, rows_p, rows_t, block = _ShardedCheckpointedStep.apply(unroll, rec, tgt_p_s[s], tgt_t_s[s], *window,
+                                                                               *params)
+            else:       # the plain path: its activations are the ones the backward needs first
+                loss_c, rows_p, rows_t, block = unroll.step(rec, tgt_p_s[s], tgt_t_s[s], window, integrate=True)
+            total = loss_c if total is None else total + loss_c
+            value = weights[s] * rec.value if value is None else value + weights[s] * rec.value
+            step_losses.append(rec.terms)
+            if rec.live:
+                new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
+            else:
+                with torch.no_grad():
+                    new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
+            out_p.append(new_p.detach())
+            out_t.append(new_t.detach())
+            pos_frames.append(new_p)
+            tmp_frames.append(new_t)
+            continue
         if s == 0:
             s0 = sample0(own, sample_want)
             x, recent, y_acc, y_tr = (s0[name] for name in sample_want)

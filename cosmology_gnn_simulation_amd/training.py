@@ -752,18 +752,42 @@ class _IntegrateRowsLink(torch.autograd.Function):
         return (None, None, None, *(g.get(name) for name in names))
 
 
+CHECKPOINTS = ("none", "steps")
+
+
+def check_checkpoint(checkpoint: str, who: str) -> str:
+    """``ValueError`` for a ``checkpoint`` mode multi-step training does not know; callers check before any device work."""
+    if checkpoint not in CHECKPOINTS:
+        raise ValueError(f"{who}: checkpoint {checkpoint!r}; known: {CHECKPOINTS}")
+    return checkpoint
+
+
+def step_record_bytes(num_particles: int, num_neighbors: int, edge_messages: bool = False) -> int:
+    """What ``checkpoint="steps"`` keeps of one step until the backward, the small record: the frame the step made
+    (``16 N`` bytes), the senders of its graph (int32, ``4 k N``) and its ``spatial_order`` (int32, ``4 N``).  The window a
+    step reads consists of frames that exist already.  Under ``message_source="edge"`` the graph's edge features are kept
+    with the lists (``16 k N``): the recomputation differentiates them on the kept lists instead of searching again."""
+    n, ne = int(num_particles), int(num_particles) * int(num_neighbors)
+    return 16 * n + 4 * ne + 4 * n + (16 * ne if edge_messages else 0)
+
+
 def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
-                            num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False) -> int:
+                            num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False,
+                            checkpoint: str = "none") -> int:
     """Device memory S unrolled steps keep alive until the backward: S times the one-step activations -- the node
     features, ``x_i`` and ``agg_i`` of every round (:class:`NodeStreamSteps`), the edge features, and under
     ``message_source="edge"`` every round's input edge latents (:func:`edge_training_bytes`) -- plus one backward
-    scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn."""
+    scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn.
+    ``checkpoint="steps"``: one step's activations, the scratch, and S small records (:func:`step_record_bytes`)."""
+    check_checkpoint(checkpoint, "unrolled_training_bytes")
     n, ne = int(num_particles), int(num_particles) * int(num_neighbors)
     per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
     scratch = (2 * num_hidden_layers + 3) * n * hidden
     if edge_messages:
         per_step += rounds * ne * latent
         scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    if checkpoint == "steps":
+        return 4 * (per_step + scratch) + int(steps) * step_record_bytes(n, num_neighbors, edge_messages)
     return 4 * (int(steps) * per_step + scratch)
 
 
@@ -778,10 +802,187 @@ class UnrolledLoss:
         self.loss, self.step_losses, self.frames, self.graphs, self.value = loss, step_losses, frames, graphs, value
 
 
+# ---- activation checkpointing across steps (unrolled_loss(checkpoint="steps")) -------------------------------------------
+#
+# A step is a pure function of its input frames, its targets and the parameters once its graph is fixed: deterministic
+# forward kernels, ``spatial_order`` instead of the search's own order, counter-based noise.  So steps 0 .. S - 2 run
+# without autograd, keep their graph's lists, and run again -- the same kernels on the same inputs -- when the backward
+# reaches them.
+
+class _KeptEdgeAttr(torch.autograd.Function):
+    """:class:`_KnnEdgeAttr` on kept lists: ``edge_attr`` as the search of the first run made it, handed on as a
+    differentiable function of ``recent`` (``cgnn_edge_attr_backward`` on the kept ``senders``); no second search."""
+
+    @staticmethod
+    def forward(ctx, recent, edge_attr, senders, k: int):
+        ctx.k, ctx.n = int(k), recent.shape[0]
+        ctx.save_for_backward(edge_attr, senders)
+        ctx.set_materialize_grads(False)
+        return edge_attr.view_as(edge_attr)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_edge_attr):
+        if d_edge_attr is None:
+            return None, None, None, None
+        edge_attr, senders = ctx.saved_tensors
+        by_sender = ops.SenderCsr(senders, None, ctx.n)
+        return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender), None, None, None
+
+
+class _StepRecord:
+    """What a checkpointed step keeps (:func:`step_record_bytes`; the frames are the tensors autograd holds anyway)."""
+
+    def __init__(self, s: int, weight: float, live: bool):
+        self.s, self.weight, self.live = s, weight, live
+        self.senders = self.order = self.edge_attr = self.terms = self.graph = None
+        self.shard = self.cap = self.value = None       # dist.sharded_unrolled_loss: the step's Shard and send capacity
+
+
+class _CheckpointedUnroll:
+    """The steps of one ``unrolled_loss(checkpoint="steps")`` call: :meth:`step` is one step of the plain loop, written
+    once for its three uses -- the first run of a checkpointed step (no autograd, it fills the record), its
+    recomputation (autograd, the kept graph) and the last step (autograd, a search: the plain path)."""
+
+    def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, edge: bool, knn_grid: str, min_image: bool,
+                 loss_weights, keep_graphs: bool):
+        self.model, self.cfg, self.w, self.n, self.k, self.edge = model, cfg, w, n, k, edge
+        self.knn_grid, self.min_image, self.loss_weights, self.keep_graphs = knn_grid, min_image, loss_weights, keep_graphs
+        self.params = list(model.parameters())
+        self.receivers = cfg.ids.repeat_interleave(k)
+        self.first = None       # step 0's true window, target and noise arguments
+        self.s0 = None          # step 0's sample of the first run
+
+    def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool, integrate: bool):
+        """-> (weighted loss term, new_pos | None, new_temp | None).  ``frames``: the W position frames, then the W
+        temperature frames.  ``kept``: build the graph from ``rec``'s lists; else search and, without autograd, fill
+        ``rec``."""
+        from . import data_utils, losses
+        cfg, w, n, k, edge = self.cfg, self.w, self.n, self.k, self.edge
+        grad = torch.is_grad_enabled()
+        if rec.s == 0:
+            if self.s0 is not None:
+                s0, self.s0 = self.s0, None
+            else:
+                pos_w, tmp_w, tgt_p0, tgt_t0, std, seed, draw = self.first
+                s0 = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, std, seed, draw, tgt_p0, tgt_t0, None,
+                                         ["x", "recent_pos", "y_acc", "y_temp_rate"], stats=cfg.stats)
+            x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
+        else:
+            x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p, tgt_t, *frames)
+        if kept:
+            senders, order = rec.senders, rec.order
+            if edge:
+                edge_attr = _KeptEdgeAttr.apply(recent, rec.edge_attr, senders, k)
+            else:       # x_j reads the width of the edge features only (the edge stream is dead): no N k rows for it
+                edge_attr = recent.new_zeros((1, 4)).expand(n * k, 4)
+        else:
+            # the edge features carry gradient only where the model reads them
+            edge_attr, senders = _KnnEdgeAttr.apply(recent if edge else recent.detach(), cfg.box, k, self.knn_grid,
+                                                    self.min_image)
+            order = spatial_order(recent, cfg.box)
+            if not grad:
+                rec.senders, rec.order = senders, order
+                rec.edge_attr = edge_attr if edge else None
+        edge_index = torch.stack([senders.to(torch.int64), self.receivers], dim=0)
+        graph = data_utils._graph(x, edge_index, edge_attr, y_acc, y_tr.reshape(n, 1), recent.detach(), order, cfg.dt,
+                                  cfg.box, k, x.device)
+        pred = self.model._forward_train(graph)         # the training forward with or without autograd: the same kernels
+        acc, rate = pred["acceleration"], pred["temp_rate"]
+        mse = torch.nn.functional.mse_loss
+        terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
+                 losses.momentum_conservation_loss(acc, graph, cfg.dt, self.loss_weights[2]))
+        loss_s = self.loss_weights[0] * terms[0] + self.loss_weights[1] * terms[1] + terms[2]
+        if not kept:
+            rec.terms = torch.stack([t.detach() for t in terms])
+            if self.keep_graphs:        # detached tensors: the last step's graph does not hold its autograd graph
+                rec.graph = graph if not grad else data_utils._graph(
+                    x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach().reshape(n, 1),
+                    recent.detach(), order, cfg.dt, cfg.box, k, x.device)
+        new_p = new_t = None
+        if integrate:
+            p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
+            if rec.live and grad:
+                new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, p2, p1, t1)
+            else:
+                with torch.no_grad():
+                    new_p, new_t = _IntegrateLink.apply(cfg, acc.detach(), rate.detach(), p2.detach(), p1.detach(),
+                                                        t1.detach())
+        return rec.weight * loss_s, new_p, new_t
+
+    def run(self, s0, pos_frames, tmp_frames, tgt_p, tgt_t, weights, links: int) -> UnrolledLoss:
+        w, S = self.w, len(weights)
+        self.s0 = s0
+        total = None
+        records, out_p, out_t = [], [], []
+        for s in range(S):
+            last = s == S - 1
+            # link s feeds step s + 1 and carries gradient when it is one of the last `links`
+            rec = _StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
+            frames = (*pos_frames[-w:], *tmp_frames[-w:])
+            if last:        # the plain path: its activations are the ones the backward needs first
+                loss_c, new_p, new_t = self.step(rec, tgt_p[s], tgt_t[s], frames, kept=False, integrate=True)
+            else:
+                loss_c, new_p, new_t = _CheckpointedStep.apply(self, rec, tgt_p[s], tgt_t[s], *frames, *self.params)
+            total = loss_c if total is None else total + loss_c
+            records.append(rec)
+            out_p.append(new_p.detach())
+            out_t.append(new_t.detach())
+            pos_frames.append(new_p)
+            tmp_frames.append(new_t)
+        frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
+        graphs = [rec.graph for rec in records] if self.keep_graphs else None
+        for rec in records:
+            rec.graph = None
+        return UnrolledLoss(total, torch.stack([rec.terms for rec in records]), frames, graphs)
+
+
+class _CheckpointedStep(torch.autograd.Function):
+    """One checkpointed step: ``(weighted loss term, new_pos, new_temp) = step(W position frames, W temperature frames;
+    parameters)`` with the step's targets as constants.  The forward runs the step without autograd and keeps the record;
+    the backward runs it again with autograd from detached copies of the frames, on the kept graph, takes
+    ``torch.autograd.grad`` of the outputs a gradient arrived for, and drops the rebuilt step.  Autograd sums a frame's
+    gradient over the steps that read it, and a parameter's over the steps, as it does on the plain path."""
+
+    @staticmethod
+    def forward(ctx, unroll: "_CheckpointedUnroll", rec: _StepRecord, tgt_p, tgt_t, *tensors):
+        frames = tensors[:2 * unroll.w]
+        loss_c, new_p, new_t = unroll.step(rec, tgt_p, tgt_t, frames, kept=False, integrate=True)
+        ctx.unroll, ctx.rec = unroll, rec
+        ctx.save_for_backward(tgt_p, tgt_t, *frames)
+        if not rec.live:
+            ctx.mark_non_differentiable(new_p, new_t)
+        ctx.set_materialize_grads(False)
+        return loss_c, new_p, new_t
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, d_new_p, d_new_t):
+        unroll, rec = ctx.unroll, ctx.rec
+        tgt_p, tgt_t, *frames = ctx.saved_tensors
+        n_frames = len(frames)
+        nothing = (None,) * (4 + n_frames + len(unroll.params))
+        link = rec.live and (d_new_p is not None or d_new_t is not None)
+        if d_loss is None and not link:
+            return nothing
+        needs = ctx.needs_input_grad[4:4 + n_frames]
+        with torch.enable_grad():
+            ins = [f.detach().requires_grad_(need) for f, need in zip(frames, needs)]
+            loss_c, new_p, new_t = unroll.step(rec, tgt_p, tgt_t, ins, kept=True, integrate=link)
+            outs = [(o, g) for o, g in ((loss_c, d_loss), (new_p, d_new_p), (new_t, d_new_t))
+                    if g is not None and o is not None and o.requires_grad]
+            wrt = [f for f, need in zip(ins, needs) if need] + [q for q in unroll.params if q.requires_grad]
+            grads = iter(torch.autograd.grad([o for o, _ in outs], wrt, [g for _, g in outs], allow_unused=True))
+        d_frames = [next(grads) if need else None for need in needs]
+        d_params = [next(grads) if q.requires_grad else None for q in unroll.params]
+        return (None, None, None, None, *d_frames, *d_params)
+
+
 def _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures, step_weights,
-                      backprop_steps, num_neighbors, knn_grid, min_image_edge_attr):
+                      backprop_steps, num_neighbors, knn_grid, min_image_edge_attr, checkpoint="none"):
     """The checks of :func:`unrolled_loss` that need no device: -> (W, N, S, weights)."""
     from .graph_network import EncodeProcessDecode
+    check_checkpoint(checkpoint, "unrolled_loss")
     ops.check_knn_grid(knn_grid, "unrolled_loss")
     ops.check_min_image(min_image_edge_attr, "unrolled_loss")
     if not isinstance(model, EncodeProcessDecode):
@@ -831,7 +1032,7 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
                   acc_loss_weight: float = 1.0, temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
                   step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
                   min_image_edge_attr: bool = False, knn_grid: str = "uniform", keep_graphs: bool = False,
-                  device: Optional[torch.device] = None) -> UnrolledLoss:
+                  device: Optional[torch.device] = None, checkpoint: str = "none") -> UnrolledLoss:
     """The multi-step training loss: S model steps unrolled from one window ``position_seq [W, N, 3]`` /
     ``temperature_seq [W, N(, 1)]``, every step compared with the true frames ``target_positions [S, N, 3]`` /
     ``target_temperatures [S, N(, 1)]``, differentiable through the whole chain.
@@ -853,21 +1054,38 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     reference shifts its one target.  It is a constant for the gradient.
 
     Memory: S steps of activations stay alive until ``loss.backward()`` (:func:`unrolled_training_bytes`); the call
-    refuses when that estimate exceeds the free device memory.  No host synchronisation beyond the one-step path's."""
+    refuses when that estimate exceeds the free device memory.  No host synchronisation beyond the one-step path's.
+
+    ``checkpoint="steps"`` (activation checkpointing across steps) keeps one step's activations instead of S: steps
+    0 .. S - 2 run without autograd and keep only a small record each -- the frame they made, the senders and the
+    ``spatial_order`` of their graph, the detached loss terms (:func:`step_record_bytes`); under ``message_source="edge"``
+    the graph's edge features as well -- and step S - 1 runs as under ``"none"``.  When ``loss.backward()`` reaches a
+    checkpointed step, the step is run again from its input frames on the kept graph, with autograd this time, and
+    differentiated at once (:class:`_CheckpointedStep`): the same kernels on the same inputs, so the same bits as the
+    first run (step 0 draws its noise again from ``(noise_seed, noise_draw)``); its activations are freed before the step
+    before it is rebuilt.  The loss, the step losses and the frames are those of ``"none"`` bit for bit; a gradient is the
+    same sum of the same terms, which autograd may add in another order (float32 rounding of a sum, far inside the
+    tolerance of the kernels).  Every option keeps its meaning; a step whose outgoing link ``backprop_steps`` cuts is
+    still recomputed, for its own loss term.  The price is at most S - 1 extra model forwards per call, no second
+    neighbour search.  ``keep_graphs=True`` returns graphs of detached tensors, which hold ``x`` and ``edge_attr`` of
+    every step (``(4 W - 3 + 4 k) 4 N`` bytes each): not part of the small record, and not counted by the estimate.
+    S = 1, or a model without a parameter that requires a gradient, takes the ``"none"`` path.  Any other value raises
+    ``ValueError`` before a launch."""
     from . import data_utils, losses
     w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
-                                         step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr)
+                                         step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr,
+                                         checkpoint)
     k = int(num_neighbors)
     if device is None:
         device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
     device = torch.device(device)
     edge = getattr(model, "message_source", "x_j") == "edge"
     need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                   len(model.processor), S, edge)
+                                   len(model.processor), S, edge, checkpoint)
     free = free_device_bytes(device)
     if need > free:
         raise CgnnError(f"unrolled_loss needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
-                        f"steps ({n} particles, {k} neighbours, latent {model._latent_size}, {len(model.processor)} "
+                        f"steps under checkpoint={checkpoint!r} ({n} particles, {k} neighbours, latent {model._latent_size}, {len(model.processor)} "
                         f"rounds); {free / 2**30:.1f} GiB are free")
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
     pos_w = _lib.f32c(position_seq.to(device), "position_seq")
@@ -882,6 +1100,7 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
     s0 = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
                              tgt_p[0], tgt_t[0], None, want, stats=cfg.stats)
+    true_window = (pos_w, tmp_w, tgt_p[0], tgt_t[0])
     if noisy:       # the noisy frames later windows read, and the shift of every later target
         pos_w = pos_w + s0["pos_noise"].permute(1, 0, 2)
         tmp_w = tmp_w + s0["temp_noise"].t()
@@ -889,6 +1108,12 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
             tgt_p = tgt_p + s0["pos_noise"][:, -1]
             tgt_t = tgt_t + s0["temp_noise"][:, -1]
     pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
+    if checkpoint == "steps" and S > 1 and any(q.requires_grad for q in model.parameters()):
+        unroll = _CheckpointedUnroll(model, cfg, w, n, k, edge, knn_grid, min_image_edge_attr,
+                                     (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), keep_graphs)
+        # step 0 draws again from the true window in its recomputation: the same (seed, draw), the same sample
+        unroll.first = (*true_window, float(noise_std), seed % 2 ** 64, noise_draw)
+        return unroll.run(s0, pos_frames, tmp_frames, tgt_p, tgt_t, weights, links)
 
     total = None
     receivers = cfg.ids.repeat_interleave(k)

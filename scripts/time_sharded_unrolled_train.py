@@ -6,9 +6,11 @@
       taken from the unsharded run's frames; all-reduces the identity): step time and peak memory against (a)'s;
   (c) the HIP-event time of the three new kernels in (b)'s step (cgnn_edge_attr_backward_rows also on its own: x_j mode
       never launches it) and the bytes of the frame-gradient all-reduce.
-Not part of the product or tests.
+``--checkpoint steps`` adds activation checkpointing across steps to (a) and (b): the world of one and the rank's share
+run plain and checkpointed alternating in this process.  Not part of the product or tests.
     python scripts/time_sharded_unrolled_train.py [--particles 1000000] [--latent 128] [--mp-steps 10] [--steps 1 2 4]
-                                                  [--world 8] [--rank 0] [--message-source x_j|edge]"""
+                                                  [--world 8] [--rank 0] [--message-source x_j|edge]
+                                                  [--checkpoint steps]"""
 import argparse
 import os
 import sys
@@ -32,6 +34,7 @@ ap.add_argument("--rank", type=int, default=0)
 ap.add_argument("--train-precision", default="fp32x3", choices=["fp32", "fp32x3"])
 ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"])
 ap.add_argument("--noise-std", type=float, default=3e-4)
+ap.add_argument("--checkpoint", default="none", choices=list(training.CHECKPOINTS))
 a = ap.parse_args()
 dev = torch.device("cuda")
 n, k, d, L, w = a.particles, a.neighbors, a.latent, a.mp_steps, a.window
@@ -49,8 +52,8 @@ kw = dict(dt=0.01, box_size=1.0, num_neighbors=k, noise_std=a.noise_std, noise_s
 last = {}
 
 
-def step(fn, s):
-    out = fn(m, c[:w], e[:w], c[w:w + s], e[w:w + s], meta, **kw)
+def step(fn, s, checkpoint="none"):
+    out = fn(m, c[:w], e[:w], c[w:w + s], e[w:w + s], meta, checkpoint=checkpoint, **kw)
     opt.zero_grad()
     out.loss.backward()
     opt.step()
@@ -118,12 +121,12 @@ fakes = dict(_world_of=lambda group=None: (a.world, a.rank), _group_up=lambda: T
              _all_reduce_max_=lambda t, group=None: t, check_same_data=lambda *args, **kwargs: None)
 
 
-def rank_step(s):
+def rank_step(s, checkpoint="none"):
     for name, fn in fakes.items():
         setattr(cdist, name, fn)
     fake_gather.step = 0
     try:
-        step(cdist.sharded_unrolled_loss, s)
+        step(cdist.sharded_unrolled_loss, s, checkpoint)
     finally:
         for name, fn in real.items():
             setattr(cdist, name, fn)
@@ -147,6 +150,11 @@ for s in a.steps:
     print(f"S={s} (a) training.unrolled_loss {one_ms:.1f} ms, peak {one_gib:.2f} GiB; world of one "
           f"{w1_ms:.1f} ms, peak {w1_gib:.2f} GiB: + {w1_ms - one_ms:.1f} ms ({(w1_ms - one_ms) / s:.1f} ms per step)",
           flush=True)
+    if a.checkpoint != "none":
+        (p_ms, p_gib), (c_ms, c_gib) = median_ms([lambda: step(cdist.sharded_unrolled_loss, s),
+                                                  lambda: step(cdist.sharded_unrolled_loss, s, a.checkpoint)], a.iters)
+        print(f"S={s} (a) world of one, checkpoint={a.checkpoint}: {c_ms:.1f} ms, peak {c_gib:.2f} GiB against plain "
+              f"{p_ms:.1f} ms, peak {p_gib:.2f} GiB", flush=True)
     step(training.unrolled_loss, s)
     reference = {name: v.clone() for name, v in last["frames"].items()}
     torch.cuda.empty_cache()
@@ -155,6 +163,12 @@ for s in a.steps:
     print(f"S={s} (b) rank {a.rank} of {a.world}, no exchange: {r_ms:.1f} ms ({one_ms / r_ms:.2f} x below the unsharded "
           f"step), peak {r_gib:.2f} GiB against {one_gib:.2f} GiB (the windows, targets and reference frames of all "
           f"particles included; estimate of the rank's need {est:.2f} GiB)", flush=True)
+    if a.checkpoint != "none":
+        (p_ms, p_gib), (c_ms, c_gib) = median_ms([lambda: rank_step(s), lambda: rank_step(s, a.checkpoint)], a.iters)
+        est = cdist.sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, n, k, w, d, d, 2, L, s, edge,
+                                                    a.checkpoint) / 2 ** 30
+        print(f"S={s} (b) rank {a.rank} of {a.world}, checkpoint={a.checkpoint}: {c_ms:.1f} ms, peak {c_gib:.2f} GiB "
+              f"against plain {p_ms:.1f} ms, peak {p_gib:.2f} GiB (estimate of the rank's need {est:.2f} GiB)", flush=True)
     with ops.OpTimer() as tm:
         rank_step(s)
     summary = tm.summary()

@@ -1,7 +1,10 @@
 """Developer tool: step time and peak memory of multi-step training (training.unrolled_loss: forward + backward through
 S unrolled model steps + Adam) for S = 1 .. --max-steps, at the shapes scripts/time_train.py uses, next to S x the
-one-step time of the same model, and the per-op split of the largest S.  Not part of the product or tests.
-    python scripts/time_unrolled_train.py [--particles 1000000] [--latent 128] [--mp-steps 10] [--max-steps 4]"""
+one-step time of the same model, and the per-op split of the largest S.  ``--checkpoint steps`` times activation
+checkpointing across steps next to the plain path, the two alternating per S in this process; a size the plain path's
+memory guard refuses is reported as refused.  Not part of the product or tests.
+    python scripts/time_unrolled_train.py [--particles 1000000] [--latent 128] [--mp-steps 10] [--max-steps 4]
+                                          [--checkpoint steps]"""
 import argparse
 import os
 import sys
@@ -10,7 +13,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cosmology_gnn_simulation_amd import data_utils, graph_network, losses, ops, synthetic, training  # noqa: E402
+from cosmology_gnn_simulation_amd import _lib, data_utils, graph_network, losses, ops, synthetic, training  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--particles", type=int, default=1_000_000)
@@ -23,6 +26,7 @@ ap.add_argument("--iters", type=int, default=3)
 ap.add_argument("--train-precision", default="fp32x3", choices=["fp32", "fp32x3"])
 ap.add_argument("--message-source", default="x_j", choices=["x_j", "edge"])
 ap.add_argument("--noise-std", type=float, default=3e-4)
+ap.add_argument("--checkpoint", default="none", choices=list(training.CHECKPOINTS))
 a = ap.parse_args()
 dev = "cuda"
 n, k, d, L, w = a.particles, a.neighbors, a.latent, a.mp_steps, a.window
@@ -55,11 +59,11 @@ def one_step():
     opt.step()
 
 
-def unrolled_step(s):
+def unrolled_step(s, checkpoint="none"):
     global draws
     out = training.unrolled_loss(m, c[:w], e[:w], c[w:w + s], e[w:w + s], meta, dt=0.01, box_size=1.0, num_neighbors=k,
                                  noise_std=a.noise_std, noise_seed=1236, noise_draw=draws, momentum_loss_weight=0.1,
-                                 min_image_edge_attr=a.message_source == "edge")
+                                 min_image_edge_attr=a.message_source == "edge", checkpoint=checkpoint)
     draws += 1
     opt.zero_grad()
     out.loss.backward()
@@ -78,16 +82,28 @@ def timed(fn):
     return (time.perf_counter() - t0) / a.iters * 1e3, torch.cuda.max_memory_allocated() / 2 ** 30
 
 
+def report(s, checkpoint):
+    est = training.unrolled_training_bytes(n, k, w, d, d, 2, L, s, a.message_source == "edge", checkpoint) / 2 ** 30
+    try:
+        ms, gib = timed(lambda: unrolled_step(s, checkpoint))
+    except _lib.CgnnError as exc:
+        if "device memory" not in str(exc):
+            raise
+        print(f"unrolled S={s} checkpoint={checkpoint}: refused by the memory guard (estimate {est:.2f} GiB)", flush=True)
+        return
+    print(f"unrolled S={s} checkpoint={checkpoint}: {ms:.2f} ms per step ({ms / (s * base_ms):.3f} of S x one-step), peak "
+          f"{gib:.2f} GiB (estimate of what is kept {est:.2f} GiB)", flush=True)
+
+
 base_ms, base_gib = timed(one_step)
 print(f"one-step path ({a.message_source}, {a.train_precision}, {n} particles, k={k}, latent {d}, {L} rounds, W={w}): "
       f"{base_ms:.2f} ms per step, peak {base_gib:.2f} GiB", flush=True)
 for s in range(1, a.max_steps + 1):
-    ms, gib = timed(lambda: unrolled_step(s))
-    est = training.unrolled_training_bytes(n, k, w, d, d, 2, L, s, a.message_source == "edge") / 2 ** 30
-    print(f"unrolled S={s}: {ms:.2f} ms per step ({ms / (s * base_ms):.3f} of S x one-step), peak {gib:.2f} GiB "
-          f"(estimate of the kept activations {est:.2f} GiB)", flush=True)
+    report(s, "none")
+    if a.checkpoint != "none":      # alternating with the plain path, in this process
+        report(s, a.checkpoint)
 with ops.OpTimer() as tm:
-    unrolled_step(a.max_steps)
+    unrolled_step(a.max_steps, a.checkpoint)
 summary = tm.summary()
 total = sum(v[1] for v in summary.values())
 for name, (calls, ms) in sorted(summary.items(), key=lambda kv: -kv[1][1]):
