@@ -46,7 +46,7 @@ EXPORTS = (
     "cgnn_history_features", "cgnn_rollout_advance", "cgnn_halo_select", "cgnn_halo_pack", "cgnn_migrate_pack",
     "cgnn_migrate_unpack", "cgnn_knn_periodic_mode", "cgnn_knn_periodic_adaptive_mode",
     "cgnn_training_sample_backward", "cgnn_rollout_integrate_backward", "cgnn_edge_attr_backward",
-    "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows",
+    "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows", "cgnn_mlp_rows_project",
 )
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -96,6 +96,8 @@ def load() -> C.CDLL:
     lib.cgnn_packed_linear_bytes.argtypes = [i32, i32, i32]
     lib.cgnn_pack_linear.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     lib.cgnn_mlp_rows.argtypes = [C.POINTER(Mlp), vp, i64, i32, vp, i32, i32, vp]
+    lib.cgnn_mlp_rows_project.argtypes = [C.POINTER(Mlp), vp, vp, i64, i32, vp, i32, C.POINTER(Linear), C.POINTER(Linear),
+                                          i32, vp, vp, i32, vp]
     lib.cgnn_tiled_rows.restype = i64
     lib.cgnn_tiled_rows.argtypes = [i64]
     lib.cgnn_relayout.argtypes = [vp, i32, vp, i32, i64, i32, vp]

@@ -152,6 +152,9 @@ static int launch_project(const void* ws, const void* wd, const float* bd, int h
 
 int mlp_rows_n16_encoder(const MlpDev& m, size_t lds, const float* x, int64_t n, int ld_x, float* y,
                          hipStream_t st);   // edge_block.hip
+int mlp_rows_f2ring(const MlpDev& m, const float* x, const int32_t* index, int64_t n, int ld_x, float* y, int ld_y,
+                    const cgnn_linear* ws, const cgnn_linear* wd, void* ps, void* pd, int p_format,
+                    hipStream_t st);        // mlp_rows_f2.hip
 
 template <int PREC, bool WLDS, int K0T, int HT, int OT>
 static int launch_mlp_rows(const MlpDev& m, size_t lds, const float* x, int64_t n, int ld_x, float* y, int ld_y,
@@ -197,6 +200,13 @@ int cgnn_mlp_rows(const cgnn_mlp* mlp, const float* x, int64_t n, int32_t ld_x, 
     if (mlp->precision == CGNN_F32X3_N16) {
         set_error("cgnn_mlp_rows: CGNN_F32X3_N16 weights are for cgnn_node_block only");
         return CGNN_ERR_UNSUPPORTED;
+    }
+    if (mlp->precision == CGNN_F16X2_N16) {  // node encoder / decoders on the two-wave ring kernel (mlp_rows_f2.hip)
+        if (y_layout != CGNN_ROWS) {
+            set_error("cgnn_mlp_rows: CGNN_F16X2_N16 weights write CGNN_ROWS output only");
+            return CGNN_ERR_UNSUPPORTED;
+        }
+        return mlp_rows_f2ring(m, x, nullptr, n, ld_x, y, ld_y, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
     }
     if (mlp->precision == CGNN_BF16_N16) {   // the edge encoder: narrow input -> TILED32 latents, 16 edges per wave
         if (y_layout != CGNN_TILED32) {
@@ -266,6 +276,29 @@ int cgnn_mlp_rows(const cgnn_mlp* mlp, const float* x, int64_t n, int32_t ld_x, 
               "(hidden,latent) in {(32,32),(64,64),(128,128),(256,256),(128,64),(128,256)})",
               m.in_dim[0], hidden, m.out_dim[m.nh]);
     return CGNN_ERR_UNSUPPORTED;
+}
+
+int cgnn_mlp_rows_project(const cgnn_mlp* mlp, const float* x, const int32_t* index, int64_t n, int32_t ld_x, float* y,
+                          int32_t ld_y, const cgnn_linear* ws, const cgnn_linear* wd, int32_t proj_precision, void* ps,
+                          void* pd, int32_t p_format, void* stream) {
+    MlpDev m;
+    int rc = make_mlp_dev(mlp, &m, nullptr, "cgnn_mlp_rows_project");
+    if (rc != CGNN_OK) return rc;
+    if (!x || !y || n < 0 || ld_x < m.in_dim[0] || ld_y < m.out_dim[m.nh]) {
+        set_error("cgnn_mlp_rows_project: invalid argument (n=%lld ld_x=%d in=%d ld_y=%d out=%d)", (long long)n, ld_x,
+                  m.in_dim[0], ld_y, m.out_dim[m.nh]);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (mlp->precision != CGNN_F16X2_N16) {
+        set_error("cgnn_mlp_rows_project: CGNN_F16X2_N16 weights only (got precision %d)", mlp->precision);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    if (ws && proj_precision != CGNN_BF16_N16) {
+        set_error("cgnn_mlp_rows_project: the projection epilogue takes CGNN_BF16_N16 weights (got precision %d)",
+                  proj_precision);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    return mlp_rows_f2ring(m, x, index, n, ld_x, y, ld_y, ws, wd, ps, pd, p_format, (hipStream_t)stream);
 }
 
 int cgnn_project_nodes(const cgnn_linear* ws, const cgnn_linear* wd, int32_t precision, const float* x, int64_t n,

@@ -435,20 +435,32 @@ def _run_edge_stream(P: dict, plan: StreamPlan, ps_all, pd_all, src, dst, e, edg
                            P["enc_edge"] if plan.enc_in_stream else None, attr)
 
 
-def _run_rounds_fused(P: dict, plan: StreamPlan, x: torch.Tensor, e, src, dst, fixed_k: int, agg: torch.Tensor,
+def _run_rounds_fused(P: dict, plan: StreamPlan, x, e, src, dst, fixed_k: int, agg: torch.Tensor,
                       edge_attr: Optional[torch.Tensor] = None, keep: Optional[dict] = None):
     """All residual rounds under the reference's data flow (aggregation of sender NODE latents): the node
     stream does not read the edge stream, so it runs first and leaves every round's Ps / Pd tables behind (the node
     kernel's epilogue writes round i+1's); then one launch applies all edge updates while each edge tile stays in
-    registers.  Same kernels' arithmetic as the round-by-round path: results are bit-identical."""
+    registers.  Same kernels' arithmetic as the round-by-round path: results are bit-identical.
+
+    ``x``: the node latents, or ``(n, device, encode)`` -- the node encoder has not run yet and ``encode(next_projection)``
+    runs it with round 0's Ps / Pd tables written from its epilogue (``ops.mlp_rows(..., next_projection=...)``), which
+    saves the ``project_nodes`` launch and its read of the fresh latents."""
     rounds = P["rounds"]
-    n, L = x.shape[0], len(rounds)
+    L = len(rounds)
+    encode = None
+    if isinstance(x, tuple):
+        n, dev, encode = x
+    else:
+        n, dev = x.shape[0], x.device
     H = rounds[0].ws.out_dim
     fmt = plan.p_format
     pdt = ops.p_format_dtype(fmt)
-    ps_all = torch.empty((L, n, H), dtype=pdt, device=x.device)
-    pd_all = torch.empty((L, n, H), dtype=pdt, device=x.device)
-    ops.project_nodes(rounds[0].ws, rounds[0].wd, x, ps_all[0], pd_all[0], fmt)
+    ps_all = torch.empty((L, n, H), dtype=pdt, device=dev)
+    pd_all = torch.empty((L, n, H), dtype=pdt, device=dev)
+    if encode is not None:
+        x = encode((rounds[0].ws_fused, rounds[0].wd_fused, ps_all[0], pd_all[0], fmt))
+    else:
+        ops.project_nodes(rounds[0].ws, rounds[0].wd, x, ps_all[0], pd_all[0], fmt)
     for i, p in enumerate(rounds):      # residual stream updated in place
         nxt = _next_projection(p, rounds[i + 1], ps_all[i + 1], pd_all[i + 1], fmt) if i + 1 < L else None
         _node_half((p.node, p.wx, p.wa), x, src, dst, fixed_k, 0, n, agg, x, nxt)
@@ -542,6 +554,9 @@ class EncodeProcessDecode(nn.Module):
         # estimate exceeds the free device memory is refused before it allocates).  No effect under message_source "x_j"
         self.train_edge_messages = False
         self.fuse_rounds = True       # x_j mode: all rounds of the edge stream in one launch
+        # node encoder on the ring kernel ("fp16x2_n16" pack): round 0's Ps / Pd tables come from its epilogue instead of a
+        # project_nodes launch (tests turn it off to compare)
+        self.fuse_encoder_projection = True
         # which one-launch kernel: "tile32" = cgnn_edge_stream_run (32-edge MFMA tiles, one wave per SIMD, two tiles per
         # wave), "tile32w" = cgnn_edge_stream_run_w8 (32-edge tiles, two waves per SIMD, one tile each; latent 128 only,
         # other shapes take "tile32"), "tile16" = cgnn_edge_stream (16-edge tiles; the first generation, kept for comparison)
@@ -594,12 +609,19 @@ class EncodeProcessDecode(nn.Module):
                                    folded_edge=folded[i] if folded is not None else None)
                   for i, net in enumerate(self.processor)]
         enc_image = _pack_mlp_centred(self.encoder.edge_model, self.edge_precision) if enc_in_image else None
+        # two fp16 terms at latent = hidden = 128: the node encoder and the decoders run the two-waves-per-SIMD ring kernel
+        # (csrc/mlp_rows_f2.hip; narrow side <= 32 in / <= 16 out, <= 3 hidden layers, a bias on every Linear)
+        ends = (self.encoder.node_model, self.decoder_acc, self.decoder_temp_rate)
+        ring_ends = ops._prec(self.node_precision) == _lib.F16X2 and D == 128 and H == 128 and 1 <= nh <= 3 and \
+            node_in <= 32 and self._output_size <= 16 and \
+            all(l.bias is not None for m in ends for l in _split_mlp(m)[0])
+        end_precision = "fp16x2_n16" if ring_ends else self.node_precision
         packed = dict(
-            enc_node=_pack_mlp(self.encoder.node_model, self.node_precision),
+            enc_node=_pack_mlp(self.encoder.node_model, end_precision),
             enc_edge=enc_edge,
             rounds=rounds,
-            dec_acc=_pack_mlp(self.decoder_acc, self.node_precision),
-            dec_tr=_pack_mlp(self.decoder_temp_rate, self.node_precision),
+            dec_acc=_pack_mlp(self.decoder_acc, end_precision),
+            dec_tr=_pack_mlp(self.decoder_temp_rate, end_precision),
             image=ops.StreamImage([p.edge for p in rounds], enc_image, folded=True) if tile32 else None,
             image_w8=None,      # the same for cgnn_edge_stream_run_w8 (every bias one chunk early), built on first use
             image_parts=([p.edge for p in rounds], enc_image) if tile32 else None,
@@ -806,20 +828,33 @@ class EncodeProcessDecode(nn.Module):
             n = x.shape[0]
             src, dst, fixed_k = _graph_arrays(g, n)
             plan = _locality_plan(g, n, fixed_k, src) if (self.locality_sort and fixed_k > 0) else None
+            P = self._pack(x.shape[1], edge_attr.shape[1])
+            # the ring kernel of the node encoder / the decoders takes the permutation as a row index: no launch of its own
+            ring = P["enc_node"].precision == _lib.F16X2_N16
+            order = inv = None
             if plan is not None:
                 order, inv, src, dst = plan
-                x = ops.gather_rows(x, order)
+                if not ring:
+                    x = ops.gather_rows(x, order)
                 edge_attr = ops.gather_rows(edge_attr.view(n, -1), order).view(n * fixed_k, -1)
-            P = self._pack(x.shape[1], edge_attr.shape[1])
             rounds = P["rounds"]
             stream = self._stream_plan(P, fixed_k, src.numel(), edge_attr)
-            xl = ops.mlp_rows(P["enc_node"], x)
+
+            def encode(next_projection=None):
+                return ops.mlp_rows(P["enc_node"], x, next_projection=next_projection, index=order if ring else None)
+
+            # round 0's Ps / Pd tables from the encoder's epilogue, where it can write the stream's table format
+            fuse0 = ring and stream.fused and bool(rounds) and getattr(self, "fuse_encoder_projection", True) and \
+                rounds[0].ws_fused.precision == _lib.BF16_N16 and \
+                stream.p_format in (_lib.P_F16_S32, _lib.P_BF16_S32, _lib.P_BF16_S16)
+            xl = None if fuse0 else encode()
             # edge latents live in TILED32 layout; in the fused path the encoder may run inside the edge stream's launch
             el = None if stream.enc_in_stream else ops.mlp_rows(P["enc_edge"], edge_attr, tiled=True)
-            agg = torch.empty((n, xl.shape[1]), dtype=torch.float32, device=x.device) if rounds else None
+            agg = torch.empty((n, self._latent_size), dtype=torch.float32, device=x.device) if rounds else None
             keep = {} if (want_latents and getattr(self, "keep_stream_inputs", False)) else None
             if stream.fused:
-                xl, el = _run_rounds_fused(P, stream, xl, el, src, dst, fixed_k, agg, edge_attr, keep)
+                xl, el = _run_rounds_fused(P, stream, (n, x.device, encode) if fuse0 else xl, el, src, dst, fixed_k, agg,
+                                           edge_attr, keep)
             elif rounds:
                 H, pdt = rounds[0].ws.out_dim, rounds[0].p_dtype
                 ps = torch.empty((n, H), dtype=pdt, device=x.device)
@@ -833,15 +868,19 @@ class EncodeProcessDecode(nn.Module):
                     xl, el, projected = _run_round(p, xl, el, src, dst, fixed_k, self.message_source, residual=True,
                                                    x_out=xl, e_out=el, scratch=(ps, pd, agg, e_upd),
                                                    projected=projected, next_round=nxt)
-            out = {"acceleration": ops.mlp_rows(P["dec_acc"], xl), "temp_rate": ops.mlp_rows(P["dec_tr"], xl)}
+            # (a decoder on the ring kernel writes row order[i] for its row i: the caller's particle numbering)
+            back = order if ring else None
+            out = {"acceleration": ops.mlp_rows(P["dec_acc"], xl, index=back),
+                   "temp_rate": ops.mlp_rows(P["dec_tr"], xl, index=back)}
             if want_latents:
                 out["x_latent"], out["edge_latent"] = xl, el.to_rows()
                 if keep:       # engine numbering (the locality order), next to the edge latents in that same numbering
                     keep["edge_latent_sorted"] = out["edge_latent"]
                     out["stream_inputs"] = keep
             if plan is not None:   # back to the caller's particle numbering
-                out["acceleration"] = ops.gather_rows(out["acceleration"], inv)
-                out["temp_rate"] = ops.gather_rows(out["temp_rate"], inv)
+                if not ring:
+                    out["acceleration"] = ops.gather_rows(out["acceleration"], inv)
+                    out["temp_rate"] = ops.gather_rows(out["temp_rate"], inv)
                 if want_latents:
                     out["x_latent"] = ops.gather_rows(xl, inv)
                     out["edge_latent"] = ops.gather_rows(out["edge_latent"].view(n, -1), inv).view(n * fixed_k, -1)

@@ -206,21 +206,54 @@ def relayout(x, out: Optional[torch.Tensor] = None):
     return t
 
 
-def mlp_rows(mlp: PackedMLP, x: torch.Tensor, out=None, tiled: bool = False):
-    """Row-wise MLP.  ``tiled=True`` (or ``out`` a :class:`TiledRows`) writes the result in TILED32 layout."""
-    x = f32c(x, "x")
-    n = x.shape[0]
+def mlp_rows(mlp: PackedMLP, x: torch.Tensor, out=None, tiled: bool = False, next_projection=None,
+             index: Optional[torch.Tensor] = None):
+    """Row-wise MLP.  ``tiled=True`` (or ``out`` a :class:`TiledRows`) writes the result in TILED32 layout.
+
+    ``"fp16x2_n16"`` packs (the two-waves-per-SIMD ring kernel: a 128-wide encoder or decoder) take two extras:
+    ``next_projection = (ws, wd, ps, pd, p_format)``, the tuple :func:`node_block` takes, makes an encoder fill the
+    first round's Ps/Pd tables from its own epilogue; ``index`` (int32 ``[n]``) makes an encoder read input row
+    ``index[i]`` for output row ``i`` and a decoder write output row ``index[i]`` for input row ``i``."""
+    if not (mlp.precision == _lib.F16X2_N16 and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and
+            x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]):     # the ring kernel reads rows at any stride
+        x = f32c(x, "x")
     if x.dim() != 2 or x.shape[1] != mlp.in_dim:
         raise CgnnError(f"mlp_rows: input is {tuple(x.shape)}, the MLP expects [n, {mlp.in_dim}]")
+    n = x.shape[0] if index is None else int(index.numel())
     if tiled or isinstance(out, TiledRows):
         y = out if out is not None else TiledRows(n, mlp.out_dim, x.device)
         yb, layout = y.buf, _lib.TILED32
     else:
         y = out if out is not None else torch.empty((n, mlp.out_dim), dtype=torch.float32, device=x.device)
         yb, layout = y, _lib.ROWS
+    if next_projection is None and index is None:
+        with _timed("mlp_rows", x.device):
+            check(_lib.load().cgnn_mlp_rows(C.byref(mlp.struct()), x.data_ptr(), n, x.stride(0), yb.data_ptr(),
+                                            yb.stride(0), layout, stream_ptr(x.device)), "cgnn_mlp_rows")
+        return y
+    if mlp.precision != _lib.F16X2_N16 or layout != _lib.ROWS:
+        raise CgnnError("mlp_rows: next_projection / index need an 'fp16x2_n16' pack and row-major output")
+    if index is not None:
+        index = i32c(index, "index")
+        if y.shape[0] < n or (mlp.gamma is None and x.shape[0] < n):
+            raise CgnnError("mlp_rows: index is longer than the rows it addresses")
+    if next_projection is not None:
+        ws, wd, ps, pd, p_format = next_projection
+        s1, s2 = ws.struct(), wd.struct()
+        pdt = p_format_dtype(p_format)
+        for t in (ps, pd):
+            require_device(t, "projection table")
+            if t.dtype != pdt or not t.is_contiguous() or t.shape != (n, ws.out_dim):
+                raise CgnnError("mlp_rows: projection tables have the wrong dtype/shape")
+        proj = (C.byref(s1), C.byref(s2), ws.precision, ps.data_ptr(), pd.data_ptr(), p_format)
+    else:
+        ps = pd = None
+        proj = (None, None, 0, None, None, 0)
+    _same_device(x, index, y, ps, pd)
     with _timed("mlp_rows", x.device):
-        check(_lib.load().cgnn_mlp_rows(C.byref(mlp.struct()), x.data_ptr(), n, x.stride(0), yb.data_ptr(),
-                                        yb.stride(0), layout, stream_ptr(x.device)), "cgnn_mlp_rows")
+        check(_lib.load().cgnn_mlp_rows_project(C.byref(mlp.struct()), x.data_ptr(), ptr(index), n, x.stride(0),
+                                                yb.data_ptr(), yb.stride(0), *proj, stream_ptr(x.device)),
+              "cgnn_mlp_rows_project")
     return y
 
 

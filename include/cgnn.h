@@ -63,7 +63,8 @@ typedef enum {
                           CGNN_F32X3 at the same error.  Range: |activation| < 65520 (fp16), beyond it the
                           row turns into inf/NaN (never a silently wrong number); use CGNN_F32X3 for
                           unnormalised inputs.  16-row packing; cgnn_node_block (square layers <= 128,
-                          projection epilogue CGNN_BF16_N16) and cgnn_edge_block                  */
+                          projection epilogue CGNN_BF16_N16), cgnn_edge_block, and cgnn_mlp_rows /
+                          cgnn_mlp_rows_project as a 128-wide encoder or decoder                  */
     CGNN_F16X2 = 6      /* the same two-fp16-term arithmetic in the 32-row packing (v_mfma_f32_32x32x16_f16):
                           wherever CGNN_F32X3 is accepted -- cgnn_mlp_rows, cgnn_node_block (any supported
                           latent / hidden pair), cgnn_project_nodes (CGNN_P_F32 tables), cgnn_mlp_backward --
@@ -138,6 +139,19 @@ int cgnn_pack_linear(const float* w, int32_t out_dim, int32_t ld, int32_t col0, 
  * :158-159 (decoders).  ld_x / ld_y are row strides in floats. */
 int cgnn_mlp_rows(const cgnn_mlp* mlp, const float* x, int64_t n, int32_t ld_x,
                   float* y, int32_t ld_y, int32_t y_layout, void* stream);
+
+/* The same for CGNN_F16X2_N16 weights (hidden = 128, 1..3 hidden layers, a bias on every Linear; the two-waves-per-SIMD
+ * ring kernel that cgnn_mlp_rows runs for this packing), with two optional extras:
+ *   index   (or NULL) an encoder (input <= 32 features, output 128, LayerNorm) READS input row index[i] for output row
+ *           i; a decoder (input 128, output <= 16, no LayerNorm) WRITES output row index[i] for input row i.
+ *   ws, wd  (encoder only, or NULL) the first round's projections, CGNN_BF16_N16 128 x 128 (proj_precision), wd with its
+ *           bias: the epilogue also writes ps[n,128] = y Ws^T and pd[n,128] = y Wd^T + b in p_format (CGNN_P_BF16_S32,
+ *           CGNN_P_BF16_S16 or CGNN_P_F16_S32) from the registers that hold the new rows -- the arithmetic and the
+ *           stores of cgnn_node_block's projection epilogue; y is bit-equal with and without it.
+ * Other shapes of this packing are refused (CGNN_ERR_UNSUPPORTED), nothing is launched. */
+int cgnn_mlp_rows_project(const cgnn_mlp* mlp, const float* x, const int32_t* index, int64_t n, int32_t ld_x, float* y,
+                          int32_t ld_y, const cgnn_linear* ws, const cgnn_linear* wd, int32_t proj_precision, void* ps,
+                          void* pd, int32_t p_format, void* stream);
 
 /* rows of a CGNN_TILED32 buffer holding n logical rows (n rounded up to 32) */
 int64_t cgnn_tiled_rows(int64_t n);
