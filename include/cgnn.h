@@ -84,7 +84,10 @@ typedef enum {
  *                    (whole-line stores) and both halves of a gathered sub-row share one line.  The table format of
  *                    cgnn_edge_stream_run_w8, which adds Ps[src] + Pd[dst] on the vector pipe with one v_fma_mix_f32 per
  *                    value (fp16 widens for free there; bf16 rows need four selector MFMAs per row tile instead)
- * i.e. each lane of the consuming kernel reads one contiguous run. */
+ * i.e. each lane of the consuming kernel reads one contiguous run.
+ * What a bf16 / fp16 table element holds: the rows x and the weights rounded to bf16 (to nearest, ties to even), exact
+ * products, the K products and Pd's f32 bias summed in f32 (matrix-core order), and that ONE f32 number rounded to the
+ * table's type, again to nearest even -- by cgnn_project_nodes and by every projection epilogue alike. */
 typedef enum { CGNN_P_F32 = 0, CGNN_P_BF16_S32 = 1, CGNN_P_BF16_S16 = 2, CGNN_P_F16_S32 = 3 } cgnn_ptable;
 
 /*
@@ -182,6 +185,11 @@ int cgnn_project_nodes(const cgnn_linear* ws, const cgnn_linear* wd, int32_t pre
  * tiles; weights resident in LDS up to 128 x 128, streamed through an LDS ring at latent = hidden = 256, where the
  * fused aggregation below is not available), CGNN_F16X2_N16 (f32 accuracy on the fp16 matrix cores, latent = hidden =
  * 128, 1..3 hidden layers, a bias on every Linear, CGNN_P_F32 tables).
+ * Where the CGNN_BF16 / CGNN_BF16_N16 kernels round: e_in and every post-ReLU activation to bf16 (nearest even) as they
+ * become matrix-core operands (the weights were rounded when packed); table values widen exactly; ps[src] + pd[dst],
+ * every sum over K, the biases, LayerNorm and the residual e_in + u are f32.  e_upd holds u itself, e_out differs from
+ * e_in + e_upd by that one f32 addition.  The bf16 edge encoders of cgnn_mlp_rows round their input features and
+ * activations the same way (tests/test_gpu_bf16_kernels.py holds every row to this arithmetic).
  *
  * Optional fused aggregation (agg_out != NULL; CGNN_BF16_N16 kernels, receiver-sorted edges with
  * fixed in-degree seg_k in {8, 16}): the same launch also writes the receivers' aggregate

@@ -18,6 +18,12 @@ two-waves-per-SIMD kernel); biases, LayerNorm (eps 1e-5, biased variance) and th
 feeds the two-waves-per-SIMD kernel folded LayerNorms (:func:`fold_state_dict`): the emulation of THAT path is this same
 arithmetic on the folded parameters (the bf16 roundings of the residual stream then fall on ``e_r - B_r``).
 
+The per-round kernels (``cgnn_project_nodes`` with bf16 weights, ``cgnn_edge_block`` with CGNN_BF16 / CGNN_BF16_N16
+weights, the bf16 edge encoders of ``cgnn_mlp_rows``) round at the same places; they are restated one call at a time by
+:func:`emulate_project`, :func:`emulate_edge_update` and :func:`emulate_encoder` below, with the table layouts of
+include/cgnn.h (:func:`s32_position`, :func:`s16_position`, :func:`logical_to_table`, :func:`table_to_logical`), and
+pinned against ``cpu_ref`` by ``tests/test_bf16_kernel_gates_cpu.py``.
+
 Pinning: :func:`emulate_from_node_latents` runs this arithmetic on the node latents of ``cpu_ref`` itself, and
 ``tests/test_oracle_bf16_stream.py`` (CPU, every run) holds it within the stated bf16 bound (3e-2 relative L2) of
 ``cpu_ref.encode_process_decode``'s f32 edge latents on the reference-generated fixture graphs.
@@ -36,6 +42,26 @@ def bf(t):
 def dot_bf16(a, w):
     """bf16 operands, wide accumulation (the MFMA's f32 accumulation order is not reproduced; f64 is the midpoint)."""
     return (bf(a).double() @ bf(w).double().t()).float()
+
+
+def bf_truncated(t):
+    """f32 -> bf16 by dropping the low 16 bits (round toward zero): what the kernels must NOT do; a mutation for the gates."""
+    return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def identity(t):
+    return t
+
+
+def make_dot(round_a=bf, round_w=bf, wide: bool = True):
+    """A ``dot(a, w) = round_a(a) @ round_w(w).T`` for the emulations below.  ``wide``: float64 sums (the midpoint of every
+    f32 summation order, :func:`dot_bf16`); else one torch float32 matmul -- a second, independent f32 summation order,
+    the stand-in for a kernel when the gates are tested on the CPU.  ``round_a = round_w = identity``: no operand
+    rounding (the f32 arithmetic of ``cpu_ref``)."""
+    def dot(a, w):
+        a, w = round_a(a.float()), round_w(w.float())
+        return (a.double() @ w.double().t()).float() if wide else a @ w.t()
+    return dot
 
 
 
@@ -61,15 +87,114 @@ def s32_table_to_logical(table: torch.Tensor) -> torch.Tensor:
     return table[..., s32_position(table.shape[-1], table.dtype, table.device)].float()
 
 
-def _mlp_tail(h0, lins, ln, centred: bool = False):
+def s16_position(H: int, device=None) -> torch.Tensor:
+    """Where feature f = 16 O + 4 q + i (q < 4, i < 4) of a row sits in a CGNN_P_BF16_S16 table (include/cgnn.h,
+    cgnn_ptable): (4 (O / 2) + q) * 8 + 4 (O % 2) + i -- restated from the header's text, not from a kernel."""
+    f = torch.arange(H, device=device)
+    O, q, i = f // 16, (f % 16) // 4, f % 4
+    return (4 * (O // 2) + q) * 8 + 4 * (O % 2) + i
+
+
+def s16_table_to_logical(table: torch.Tensor) -> torch.Tensor:
+    """A CGNN_P_BF16_S16 table -> float32 values in feature order (last dimension)."""
+    return table[..., s16_position(table.shape[-1], table.device)].float()
+
+
+# cgnn_ptable (include/cgnn.h), restated: this module imports nothing from the engine
+P_BF16_S32, P_BF16_S16, P_F16_S32 = 1, 2, 3
+P_FORMAT_DTYPE = {P_BF16_S32: torch.bfloat16, P_BF16_S16: torch.bfloat16, P_F16_S32: torch.float16}
+
+
+def table_position(H: int, p_format: int, device=None) -> torch.Tensor:
+    """position[f] of feature f in a row of H values of the table format ``p_format``."""
+    if p_format == P_BF16_S16:
+        return s16_position(H, device)
+    if p_format == P_F16_S32 and H != 128:
+        raise ValueError("CGNN_P_F16_S32 is defined for rows of 128 values (include/cgnn.h)")
+    return s32_position(H, P_FORMAT_DTYPE[p_format], device)
+
+
+def logical_to_table(values: torch.Tensor, p_format: int) -> torch.Tensor:
+    """Values in feature order (last dimension) -> a table in ``p_format`` order, rounded (to nearest even) to the format's
+    storage type: the inverse of :func:`table_to_logical`."""
+    pos = table_position(values.shape[-1], p_format, values.device)
+    out = torch.empty_like(values)
+    out[..., pos] = values
+    return out.to(P_FORMAT_DTYPE[p_format]).contiguous()
+
+
+def table_to_logical(table: torch.Tensor, p_format: int) -> torch.Tensor:
+    """A table in ``p_format`` order -> float32 values in feature order (last dimension)."""
+    assert table.dtype == P_FORMAT_DTYPE[p_format]
+    return table[..., table_position(table.shape[-1], p_format, table.device)].float()
+
+
+def emulate_project(x: torch.Tensor, w: torch.Tensor, b, dtype: torch.dtype):
+    """``cgnn_project_nodes`` with bf16 weights (mlp_rows.hip, project_kernel; the projection epilogues of the node and
+    encoder kernels do the same arithmetic): the f32 rows ``x`` and the weights are rounded to bf16 (nearest even), the
+    products are exact, the sum over K and the bias ``b`` (f32, Pd only; None for Ps) are accumulated in f32 in the matrix
+    core's order, and the result is rounded ONCE to the table's storage type ``dtype``.
+
+    -> (exact, bound), float64, in feature order:
+    exact = bf(x) @ bf(w).T (+ b) without any rounding of the sum; bound = (K + 2) 2^-23 (|bf(x)| @ |bf(w)|.T + |b|), the
+    a-priori bound on |s - exact| for the result s of ANY f32 summation order of those K products and the bias (K + 1
+    additions, each with relative error <= 2^-23: the unit of the last place, not half of it, because the matrix core's
+    internal additions need not round to nearest; first order in 2^-23 with one spare term).  What a correct table holds
+    is ``s`` rounded to ``dtype``: tests/edge_checks.py, assert_table_is_rounded_exact.  ``dtype`` only names the storage
+    type the pair is meant for (bfloat16 or float16; the sums must be finite in it)."""
+    assert dtype in (torch.bfloat16, torch.float16)
+    xb, wb = bf(x.float()).double(), bf(w.float()).double()
+    exact = xb @ wb.t()
+    mag = xb.abs() @ wb.abs().t()
+    if b is not None:
+        exact = exact + b.double()
+        mag = mag + b.double().abs()
+    return exact, (x.shape[1] + 2) * 2.0 ** -23 * mag
+
+
+def _layer_norm64(out, ln):
+    return F.layer_norm(out.double(), (out.shape[1],), ln[0].double(), ln[1].double(), 1e-5).float()
+
+
+def emulate_edge_update(ps, pd, src, dst, e, lins, ln, dot=dot_bf16, act=bf):
+    """One round of ``cgnn_edge_block`` with CGNN_BF16 (edge_block.hip: edge_block_kernel, edge_block_lds_kernel) or
+    CGNN_BF16_N16 weights (edge_block_n16_kernel; edge_block_ring256.hip), from LOGICAL table values (float32 [n, H] in
+    feature order, bf16- or fp16-representable, the layer-0 bias inside ``pd``):
+
+        first = (ps[src] + pd[dst]) + dot(e, We)          lins[0] = (We, ignored)
+        u     = LayerNorm(W_nh act(relu(.. act(relu(first)) ..)) + b_nh)          lins[1:] = [(w, b)], ln = (gamma, beta)
+
+    -> u (the update: ``e_upd``, or ``e_out`` when residual = 0); ``e_out = e + u`` in f32 otherwise.  Rounding points of
+    all four kernels: ``e`` and every post-ReLU activation are rounded to bf16 (nearest even) as they become MFMA
+    operands, weights were rounded to bf16 when packed; table values widen exactly and are ADDED in f32 (the 32-edge
+    kernels add the two rows on the vector pipe before the products, the 16-edge kernels feed them through selector MFMAs:
+    both are f32 sums of the same terms); sums, biases, LayerNorm (eps 1e-5, biased variance) and the residual are f32.
+    LayerNorm is evaluated here in float64 from the f32 pre-activations, the yardstick for any f32 evaluation order.
+    ``dot`` / ``act``: :func:`make_dot` variants, for the CPU tests of the gates (second summation order, mutations)."""
+    first = (ps[src.long()] + pd[dst.long()]) + dot(e, lins[0][0])
+    return _mlp_tail(first, lins[1:], ln, dot=dot, act=act, wide_ln=True)
+
+
+def emulate_encoder(attr, lins, ln, dot=dot_bf16, act=bf):
+    """The bf16 edge encoders of ``cgnn_mlp_rows`` (CGNN_BF16: mlp_rows.hip, mlp_rows_kernel; CGNN_BF16_N16:
+    edge_block.hip, edge_encode_n16_kernel): ``LayerNorm(MLP(attr))`` with the input features and every post-ReLU
+    activation rounded to bf16 as MFMA operands, bf16 weights, f32 sums starting from the f32 bias, f32 LayerNorm (here
+    float64, as in :func:`emulate_edge_update`).  lins = [(w, b)] of all Linears."""
+    return _mlp_tail(dot(attr, lins[0][0]) + lins[0][1], lins[1:], ln, dot=dot, act=act, wide_ln=True)
+
+
+def _mlp_tail(h0, lins, ln, centred: bool = False, dot=dot_bf16, act=bf, wide_ln: bool = False):
     """h0 = pre-activation of layer 0 (bias included); lins = [(w, b)] of layers 1..; ln = (gamma, beta).
-    ``centred``: the output Linear was centred (:func:`fold_state_dict`) and the kernel normalises WITHOUT a mean
+    ``dot`` / ``act``: the product (:func:`make_dot`) and the rounding of the post-ReLU activations; ``wide_ln``: LayerNorm
+    in float64 from the f32 pre-activations.  ``centred``: the output Linear was centred (:func:`fold_state_dict`) and the kernel normalises WITHOUT a mean
     (``y * rsqrt(E[y^2] + eps)``: what is left of the mean is the bf16 rounding of the centred weights, ~1e-4 sigma)."""
-    h = bf(torch.relu(h0))
+    h = act(torch.relu(h0))
     for w, b in lins[:-1]:
-        h = bf(torch.relu(dot_bf16(h, w) + b))
+        h = act(torch.relu(dot(h, w) + b))
     w, b = lins[-1]
-    out = dot_bf16(h, w) + b
+    out = dot(h, w) + b
+    if wide_ln:
+        return _layer_norm64(out, ln)
     if centred:
         return out * torch.rsqrt((out * out).mean(dim=1, keepdim=True) + 1e-5) * ln[0] + ln[1]
     return F.layer_norm(out, (out.shape[1],), ln[0], ln[1], 1e-5)

@@ -23,13 +23,10 @@ def _dot(a, w):      # bf16 operands, wide accumulation
 
 
 def _s32_table(p, dtype=torch.bfloat16):
-    """logical [R, N, H] values -> table in CGNN_P_BF16_S32 order (include/cgnn.h): feature f = 32t+8g+4h+c sits at
-    h*(H/2) + (4t+g)*4 + c; ``dtype`` float16 = CGNN_P_F16_S32 (halves interleaved in 64-byte segments)."""
-    from oracle.bf16_stream import s32_position
-    pos = s32_position(p.shape[-1], dtype, p.device)
-    out = torch.empty_like(p)
-    out[..., pos] = p
-    return out.to(dtype).contiguous()
+    """logical [R, N, H] values -> table in CGNN_P_BF16_S32 order, or (``dtype`` float16) CGNN_P_F16_S32: the layout maps
+    live with the rest of the restated arithmetic, oracle/bf16_stream.py (logical_to_table)."""
+    from oracle.bf16_stream import P_BF16_S32, P_F16_S32, logical_to_table
+    return logical_to_table(p, P_F16_S32 if dtype == torch.float16 else P_BF16_S32)
 
 
 def _rand_mlp(gen, fin, d, nh):
