@@ -156,7 +156,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void mlp_backward_kernel(
 #pragma unroll
             for (int t = 0; t < HT; ++t)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) gh[t][i] = hv[t][i] > 0.f ? gh[t][i] : 0.f;
+                for (int i = 0; i < 16; ++i) gh[t][i] = hv[t][i] <= 0.f ? 0.f : gh[t][i];      // a NaN activation keeps its (NaN) gradient
             if (live) store_rows_full<HT>(gh, buf.g_a[l] + row * H, h);
             og.template from_acc<false>(gh);
         };

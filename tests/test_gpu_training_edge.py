@@ -6,49 +6,14 @@ latent 256 (every dot product twice as long)."""
 import pytest
 import torch
 
+import backward_checks as bc
+from backward_checks import GTOL, Lin as _Lin, close as _close, edge_sd as _edge_sd, edges as _edges
 from cosmology_gnn_simulation_amd import _lib, data_utils, graph_network, losses, ops, synthetic, training
 from cosmology_gnn_simulation_amd.graph import Batch, Data
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GTOL = 2e-5
-
-
-def _close(got, want, tol=GTOL):
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = max(float(want.abs().max()), 1e-12)
-    err = float((got - want).abs().max()) / scale
-    if err > tol:
-        print(f"_close: max |got - want| / max |want| = {err:.3e} > {tol:.1e}")
-    return err <= tol
-
-
-class _Lin:   # what training._TrainEdge needs from an nn.Linear / nn.LayerNorm
-    def __init__(self, w, b):
-        self.weight, self.bias = w, b
-
-
-def _edge_sd(gen, D, H, nh):
-    dims = [3 * D] + [H] * nh + [D]
-    sd = {}
-    for i in range(nh + 1):
-        sd[f"m.0.{2 * i}.weight"] = (torch.rand(dims[i + 1], dims[i], generator=gen) * 2 - 1) / dims[i] ** 0.5
-        sd[f"m.0.{2 * i}.bias"] = torch.rand(dims[i + 1], generator=gen) - 0.5
-    sd["m.1.weight"] = 1 + 0.1 * torch.randn(D, generator=gen)
-    sd["m.1.bias"] = 0.1 * torch.randn(D, generator=gen)
-    return sd
-
-
-def _edges(gen, n, graph):
-    """(src, dst, fixed_k): receiver-sorted fixed in-degree k, or a general (unsorted, ragged) edge list."""
-    if graph == "general":
-        e = 5 * n + 3
-        return (torch.randint(0, n, (e,), generator=gen, dtype=torch.int32),
-                torch.randint(0, n, (e,), generator=gen, dtype=torch.int32), 0)
-    k = int(graph[1:])
-    src = torch.randint(0, n, (n * k,), generator=gen, dtype=torch.int32)
-    return src, torch.arange(n, dtype=torch.int32).repeat_interleave(k), k
 
 
 _PAIRS = [(32, 32), (64, 64), (128, 128), (256, 256), (128, 64), (128, 256)]      # (hidden, latent)
@@ -61,18 +26,28 @@ def test_edge_mlp_backward_matches_autograd(pair_i, precision, graph):
     """ops.edge_mlp_backward + the reductions of one round (training.edge_round_grads, linear2_rows) against torch autograd
     of L = <e + u, de_next> + <agg(u), d_agg>, u = mlp_ln(cat[x[src], x[dst], e]): de, every weight / bias / LayerNorm
     gradient, dPs / dPd and dx.  Every (hidden, latent) pair, 1..3 hidden layers (cycled), the three arithmetic pairings,
-    E not a multiple of 32, fixed in-degree 8 / 16 / 32 and a general edge list."""
+    E not a multiple of 32, fixed in-degree 8 / 16 / 32 and a general edge list.  Besides the 2e-5 of each tensor's
+    largest entry, EVERY row of de, dPs, dPd and dx is held to 2e-5 of its own norm against float64 autograd
+    (backward_checks.py).  For that gate the edges are margin-filtered: an edge with a ReLU input at rounding distance from
+    zero (min |a| / max |a| <= 1e-5 over a hidden layer) has a discontinuous gradient that any f32 evaluation may get wrong
+    by 1 / sqrt(H), so its e row is re-drawn from the same generator (most seeds have none).  All sizes here run one tile
+    per wave; test_gpu_backward_gates.py runs more."""
     H, D = _PAIRS[pair_i]
     nh = 1 + (pair_i + len(graph)) % 3
     gen = torch.Generator().manual_seed(17 * pair_i + len(graph) + len(precision))
     n = 37 if graph != "k32" else 29      # 296, 592, 188 edges (ragged last tile); 928 at k = 32 (whole tiles)
     src, dst, fixed_k = _edges(gen, n, graph)
     ne = src.numel()
-    sd = {k: v.requires_grad_(True) for k, v in _edge_sd(gen, D, H, nh).items()}
-    x = torch.randn(n, D, generator=gen).requires_grad_(True)
-    e = torch.randn(ne, D, generator=gen).requires_grad_(True)
+    sd = _edge_sd(gen, D, H, nh)
+    x = torch.randn(n, D, generator=gen)
+    e = torch.randn(ne, D, generator=gen)
     de_next = torch.randn(ne, D, generator=gen)
     d_agg = torch.randn(n, D, generator=gen)
+    bc.redraw_fragile_edge_rows(gen, sd, x, src, dst, e, nh, cap=None)
+    want64 = bc.edge_reference(dict(sd=sd, x=x, e=e, src=src, dst=dst, de_next=de_next, d_agg=d_agg, n=n, ne=ne, H=H, D=D, nh=nh))
+    sd = {k: v.requires_grad_(True) for k, v in sd.items()}
+    x.requires_grad_(True)
+    e.requires_grad_(True)
     u = cpu_ref.mlp_ln(sd, "m", torch.cat([x[src.long()], x[dst.long()], e], dim=-1), nh)
     agg = torch.zeros(n, D).index_add(0, dst.long(), u)
     ((e + u) * de_next).sum().add((agg * d_agg).sum()).backward()
@@ -102,6 +77,8 @@ def test_edge_mlp_backward_matches_autograd(pair_i, precision, graph):
     assert _close(dy_first, de_next + d_agg[dst.long()], 1e-6)
     assert _close(de_sep.to_rows(), e.grad)
     assert _close(dx, x.grad)
+    for name, got in (("de", de_sep.to_rows()), ("dps", dps), ("dpd", dpd), ("dx", dx)):
+        bc.assert_rows(got, want64[name], name)
     names = [f"m.0.{2 * i}.{p}" for i in range(nh + 1) for p in ("weight", "bias")] + ["m.1.weight", "m.1.bias"]
     gtol = GTOL if D <= 128 else 1.5 * GTOL
     for name, g in zip(names, grads, strict=True):
