@@ -47,7 +47,9 @@ EXPORTS = (
     "cgnn_migrate_unpack", "cgnn_knn_periodic_mode", "cgnn_knn_periodic_adaptive_mode",
     "cgnn_training_sample_backward", "cgnn_rollout_integrate_backward", "cgnn_edge_attr_backward",
     "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows", "cgnn_mlp_rows_project",
+    "cgnn_knn_batched_workspace_bytes", "cgnn_knn_periodic_batched", "cgnn_knn_batched_sorted_order",
 )
+KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
 MIGRATE_BLOCK = 256     # CGNN_MIGRATE_BLOCK: rows per workgroup of the migration kernels (block_counts / offsets rows)
@@ -129,6 +131,10 @@ def load() -> C.CDLL:
     lib.cgnn_knn_adaptive_sorted_order.argtypes = [vp, i64, vp, vp]
     lib.cgnn_knn_periodic_mode.argtypes = lib.cgnn_knn_periodic.argtypes + [i32]
     lib.cgnn_knn_periodic_adaptive_mode.argtypes = lib.cgnn_knn_periodic_adaptive.argtypes + [i32]
+    lib.cgnn_knn_batched_workspace_bytes.restype = sz
+    lib.cgnn_knn_batched_workspace_bytes.argtypes = [C.POINTER(i64), i32, i32]      # offsets: host memory
+    lib.cgnn_knn_periodic_batched.argtypes = [vp, C.POINTER(i64), i32, f32, i32, vp, vp, vp, sz, vp, i32]
+    lib.cgnn_knn_batched_sorted_order.argtypes = [vp, C.POINTER(i64), i32, vp, vp]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

@@ -528,6 +528,212 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
     }
 }
 
+// ===================================================================================================================
+// Batched: B independent periodic boxes in one call (cgnn_knn_periodic_batched).
+//
+// Graph g keeps the uniform grid it would get alone (knn_layout(n_g): the same G, h and inv_h, so the same cells, the
+// same shells and the same stopping rule) and its cell table is one stretch of a single table over all graphs:
+// cells [cell_base[g], cell_base[g] + cells_g).  One scan over that table gives global slots of `sorted`; the graphs'
+// stretches follow one another, so graph g's particles fill exactly the slots [row_base[g], row_base[g] + n_g) and
+// start[cell_base[g] + cells_g] = start[cell_base[g + 1]] closes graph g's last cell.  `sorted` carries the LOCAL
+// particle index (the key of the ordering contract); the row base is added when a sender or a perm entry is written.
+// A search thread only ever reads cells of its own graph's stretch: two simulations cannot be linked.
+//
+// The per-graph numbers travel by value in the kernel arguments, CGNN_KNN_BATCH_GROUP graphs per launch; a thread
+// finds its graph by a binary search over the row bases.
+struct KnnBatchTable {
+    int32_t count;                                 // graphs in this group
+    int32_t row_base[CGNN_KNN_BATCH_GROUP + 1];    // first global row of each graph; [count] ends the group
+    int32_t cell_base[CGNN_KNN_BATCH_GROUP];       // first cell of each graph in the shared table
+    int32_t G[CGNN_KNN_BATCH_GROUP];
+    float h[CGNN_KNN_BATCH_GROUP];
+    float inv_h[CGNN_KNN_BATCH_GROUP];
+};
+
+// graph of global row i, row_base[0] <= i < row_base[count]
+__device__ __forceinline__ int knn_batch_graph(const KnnBatchTable& T, int i) {
+    int lo = 0, hi = T.count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (T.row_base[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void knn_batched_count_kernel(const float* __restrict__ pos, const KnnBatchTable T,
+                                         int32_t* __restrict__ cell_of, int32_t* __restrict__ count) {
+    const int64_t i = (int64_t)T.row_base[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.row_base[T.count]) return;
+    const int g = knn_batch_graph(T, (int)i);
+    const float inv_h = T.inv_h[g];
+    const int G = T.G[g];
+    const int cell = T.cell_base[g] + morton3(cell_coord(pos[3 * i + 0], inv_h, G), cell_coord(pos[3 * i + 1], inv_h, G),
+                                              cell_coord(pos[3 * i + 2], inv_h, G));
+    cell_of[i] = cell;
+    atomicAdd(&count[cell], 1);
+}
+
+__global__ void knn_batched_fill_kernel(const float* __restrict__ pos, const KnnBatchTable T,
+                                        const int32_t* __restrict__ cell_of, const int32_t* __restrict__ start,
+                                        int32_t* __restrict__ cursor, float4* __restrict__ sorted) {
+    const int64_t i = (int64_t)T.row_base[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.row_base[T.count]) return;
+    const int local = (int)i - T.row_base[knn_batch_graph(T, (int)i)];
+    const int cell = cell_of[i];
+    const int slot = start[cell] + atomicAdd(&cursor[cell], 1);
+    sorted[slot] = make_float4(pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], __int_as_float(local));
+}
+
+// knn_search_kernel for the sorted slot t of a batch: the same shell walk, candidate loop (knn_scan_range), stopping
+// rule and epilogue on graph g's own positions and cells.
+template <int K, int MODE>
+__global__ __launch_bounds__(CGNN_BLOCK) void knn_batched_search_kernel(const float* __restrict__ pos_all,
+                                                                        const KnnBatchTable T, float box,
+                                                                        const int32_t* __restrict__ start_all,
+                                                                        const float4* __restrict__ sorted, int k,
+                                                                        int32_t* __restrict__ senders,
+                                                                        float* __restrict__ edge_attr) {
+    const int64_t t = (int64_t)T.row_base[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T.row_base[T.count]) return;
+    const int g = knn_batch_graph(T, (int)t);
+    const int row_base = T.row_base[g];
+    const int G = T.G[g];
+    const float h = T.h[g], inv_h = T.inv_h[g];
+    const float* __restrict__ pos = pos_all + 3 * (int64_t)row_base;     // graph g's own rows
+    const int32_t* __restrict__ start = start_all + T.cell_base[g];      // graph g's own cells (global slots)
+    const float4 s = sorted[t];
+    const float qx = s.x, qy = s.y, qz = s.z;
+    const int64_t out_row = (int64_t)row_base + __float_as_int(s.w);
+    const int cx = cell_coord(qx, inv_h, G), cy = cell_coord(qy, inv_h, G), cz = cell_coord(qz, inv_h, G);
+
+    float bd[K];
+    unsigned bi[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        bd[j] = __builtin_inff();
+        bi[j] = 0xFFFFFFFFu;
+    }
+    const int rmax = 2 * G - 1;  // beyond this every one of the 27 images has been visited
+    for (int r = 0; r <= rmax; ++r) {
+        for (int dx = -r; dx <= r; ++dx) {
+            const int ux = cx + dx;
+            if (ux < -G || ux >= 2 * G) continue;
+            const int sx = ux < 0 ? -1 : (ux >= G ? 1 : 0);
+            const int wx = ux - sx * G;
+            const float shx = (float)sx * box;
+            const bool edge_x = (dx == -r) || (dx == r);
+            for (int dy = -r; dy <= r; ++dy) {
+                const int uy = cy + dy;
+                if (uy < -G || uy >= 2 * G) continue;
+                const int sy = uy < 0 ? -1 : (uy >= G ? 1 : 0);
+                const int wy = uy - sy * G;
+                const float shy = (float)sy * box;
+                const bool edge_xy = edge_x || (dy == -r) || (dy == r);
+                const int zstep = edge_xy ? 1 : (2 * r > 0 ? 2 * r : 1);  // interior columns: only the two end caps
+                for (int dz = -r; dz <= r; dz += zstep) {
+                    const int uz = cz + dz;
+                    if (uz < -G || uz >= 2 * G) continue;
+                    const int sz = uz < 0 ? -1 : (uz >= G ? 1 : 0);
+                    const int wz = uz - sz * G;
+                    const float shz = (float)sz * box;
+                    const unsigned shift_id = (unsigned)((sx + 1) * 9 + (sy + 1) * 3 + (sz + 1));
+                    const int cell = morton3(wx, wy, wz);
+                    knn_scan_range<K>(bd, bi, sorted, start[cell], start[cell + 1], shx, shy, shz, shift_id, qx, qy, qz);
+                }
+            }
+        }
+        const float bound = (float)r * h * (1.0f - 1e-5f) - 1e-5f * box;
+        float kth = bd[K - 1];
+#pragma unroll
+        for (int j = 0; j < K; ++j) kth = (j == k - 1) ? bd[j] : kth;  // static indices: bd stays in registers
+        if (bound > 0.f && kth <= bound * bound) break;
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (j < k) {
+            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);    // local to graph g
+            senders[out_row * k + j] = row_base + snd;
+            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
+                if (edge_attr != nullptr)
+                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
+                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, qx, qy, qz);
+            } else if (edge_attr != nullptr) {
+                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], qx);
+                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], qy);
+                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], qz);
+                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
+                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
+            }
+        }
+    }
+}
+
+__global__ void knn_batched_perm_kernel(const float4* __restrict__ sorted, const KnnBatchTable T,
+                                        int32_t* __restrict__ perm) {
+    const int64_t i = (int64_t)T.row_base[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.row_base[T.count]) return;
+    perm[i] = T.row_base[knn_batch_graph(T, (int)i)] + __float_as_int(sorted[i].w);
+}
+
+struct KnnBatchedLayout {
+    int64_t n_total, cells;   // cells: all graphs' cell slots
+    size_t off_count, off_start, off_cursor, off_bsum, off_cellof, off_sorted, total;
+};
+
+// CGNN_OK, or why the offsets are refused (nothing is written to L then)
+static int knn_batched_layout(const char* who, const int64_t* offsets, int32_t num_graphs, KnnBatchedLayout& L) {
+    if (!offsets || num_graphs < 1 || offsets[0] != 0) {
+        set_error("%s: offsets must hold num_graphs + 1 >= 2 values starting at 0", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    int64_t cells = 0;
+    bool too_large = false;
+    for (int32_t g = 0; g < num_graphs; ++g) {
+        const int64_t n = offsets[g + 1] - offsets[g];
+        if (n <= 0) {
+            set_error("%s: graph %d is empty or offsets do not increase", who, (int)g);
+            return CGNN_ERR_INVALID_ARG;
+        }
+        if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) too_large = true;
+        else cells += knn_layout(n).cells;
+    }
+    // the shared cell table is indexed with int32 (cells < 4 n per graph: reached only far beyond 2^29 particles)
+    if (too_large || offsets[num_graphs] >= ((int64_t)1 << 31) || cells + 1 >= ((int64_t)1 << 31)) {
+        set_error("%s: 2^%d or more particles in one graph, or 2^31 or more rows or cells in all, are not supported", who,
+                  CGNN_KNN_IDX_BITS);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    L.n_total = offsets[num_graphs];
+    L.cells = cells;
+    size_t off = 0;
+    L.off_count = off;  off = align256(off + (size_t)(cells + 1) * 4);
+    L.off_start = off;  off = align256(off + (size_t)(cells + 1) * 4);
+    L.off_cursor = off; off = align256(off + (size_t)(cells + 1) * 4);
+    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(cells + 1) + 1) * 4);
+    L.off_cellof = off; off = align256(off + (size_t)L.n_total * 4);
+    L.off_sorted = off; off = align256(off + (size_t)L.n_total * 16);
+    L.total = off;
+    return CGNN_OK;
+}
+
+// the table of graphs [g0, g0 + count); cell_base: the first cell of graph g0, advanced past the group
+static KnnBatchTable knn_batch_table(const int64_t* offsets, int32_t g0, int32_t count, float box_size,
+                                     int64_t& cell_base) {
+    KnnBatchTable T = {};
+    T.count = count;
+    for (int32_t j = 0; j < count; ++j) {
+        const KnnLayout U = knn_layout(offsets[g0 + j + 1] - offsets[g0 + j]);
+        T.row_base[j] = (int32_t)offsets[g0 + j];
+        T.cell_base[j] = (int32_t)cell_base;
+        T.G[j] = U.G;
+        T.h[j] = box_size / (float)U.G;          // as the single-graph entry computes them
+        T.inv_h[j] = (float)U.G / box_size;
+        cell_base += U.cells;
+    }
+    T.row_base[count] = (int32_t)offsets[g0 + count];
+    return T;
+}
+
 }  // namespace cgnn
 
 using namespace cgnn;
@@ -649,6 +855,131 @@ int cgnn_knn_sorted_order(const void* workspace, int64_t n, int32_t* perm, void*
     knn_perm_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, n,
                                                                                                         perm);
     return check_hip(hipGetLastError(), "cgnn_knn_sorted_order launch");
+}
+
+size_t cgnn_knn_batched_workspace_bytes(const int64_t* offsets, int32_t num_graphs, int32_t k) {
+    (void)k;
+    KnnBatchedLayout L;
+    if (knn_batched_layout("cgnn_knn_batched_workspace_bytes", offsets, num_graphs, L) != CGNN_OK) return 256;
+    return L.total;
+}
+
+int cgnn_knn_periodic_batched(const float* pos, const int64_t* offsets, int32_t num_graphs, float box_size, int32_t k,
+                              int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                              void* stream, int32_t edge_attr_mode) {
+    const char* who = "cgnn_knn_periodic_batched";
+    if (!pos || !offsets || !senders || !workspace || k <= 0 || !(box_size > 0.f)) {
+        set_error("%s: invalid argument", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (edge_attr_mode != CGNN_KNN_EDGE_ATTR_REFERENCE && edge_attr_mode != CGNN_KNN_EDGE_ATTR_IMAGE) {
+        set_error("%s: unknown edge-feature mode %d", who, (int)edge_attr_mode);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    if (k > 64) {
+        set_error("%s: k=%d > 64 is not compiled", who, k);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    KnnBatchedLayout L;
+    int rc = knn_batched_layout(who, offsets, num_graphs, L);
+    if (rc) return rc;
+    for (int32_t g = 0; g < num_graphs; ++g) {
+        const int64_t n = offsets[g + 1] - offsets[g];
+        if ((int64_t)k > 27 * n) {
+            set_error("%s: k=%d exceeds the 27*n=%lld periodic images of graph %d", who, k, (long long)(27 * n), (int)g);
+            return CGNN_ERR_INVALID_ARG;
+        }
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+        set_error("%s: workspace must be 16-byte aligned", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (workspace_bytes < L.total) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
+        return CGNN_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    int32_t* count = reinterpret_cast<int32_t*>(ws + L.off_count);
+    int32_t* start = reinterpret_cast<int32_t*>(ws + L.off_start);
+    int32_t* cursor = reinterpret_cast<int32_t*>(ws + L.off_cursor);
+    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
+    int32_t* cell_of = reinterpret_cast<int32_t*>(ws + L.off_cellof);
+    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
+    const int64_t m = L.cells + 1;  // count[cells] = 0 so that start[cells] = n_total
+    rc = check_hip(hipMemsetAsync(count, 0, (size_t)m * 4, st), "knn batched memset count");
+    if (rc) return rc;
+    rc = check_hip(hipMemsetAsync(cursor, 0, (size_t)m * 4, st), "knn batched memset cursor");
+    if (rc) return rc;
+    // Each stage takes every graph: one launch per group of CGNN_KNN_BATCH_GROUP graphs, one scan over all cell tables.
+    const int32_t groups = (num_graphs + CGNN_KNN_BATCH_GROUP - 1) / CGNN_KNN_BATCH_GROUP;
+    auto group_table = [&](int32_t gi, int64_t& cell_base) {
+        const int32_t g0 = gi * CGNN_KNN_BATCH_GROUP;
+        const int32_t cnt = num_graphs - g0 < CGNN_KNN_BATCH_GROUP ? num_graphs - g0 : CGNN_KNN_BATCH_GROUP;
+        return knn_batch_table(offsets, g0, cnt, box_size, cell_base);
+    };
+    auto blocks_of = [](const KnnBatchTable& T) {
+        return (unsigned)(((int64_t)T.row_base[T.count] - T.row_base[0] + CGNN_BLOCK - 1) / CGNN_BLOCK);
+    };
+    int64_t cell_base = 0;
+    for (int32_t gi = 0; gi < groups; ++gi) {
+        const KnnBatchTable T = group_table(gi, cell_base);
+        knn_batched_count_kernel<<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, cell_of, count);
+    }
+    exclusive_scan_i32(count, m, bsum, start, st);
+    cell_base = 0;
+    for (int32_t gi = 0; gi < groups; ++gi) {
+        const KnnBatchTable T = group_table(gi, cell_base);
+        knn_batched_fill_kernel<<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, cell_of, start, cursor, sorted);
+    }
+    rc = check_hip(hipGetLastError(), who);
+    if (rc) return rc;
+#define CGNN_KNNB_LAUNCH_MODE(KK, MM)                                                                          \
+    knn_batched_search_kernel<KK, MM><<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, box_size, start, sorted, k, \
+                                                                           senders, edge_attr)
+#define CGNN_KNNB_LAUNCH(KK)                                                     \
+    do {                                                                         \
+        if (edge_attr_mode == CGNN_KNN_EDGE_ATTR_IMAGE)                          \
+            CGNN_KNNB_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                 \
+        else                                                                     \
+            CGNN_KNNB_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);             \
+    } while (0)
+    cell_base = 0;
+    for (int32_t gi = 0; gi < groups; ++gi) {
+        const KnnBatchTable T = group_table(gi, cell_base);
+        if (k <= 8)
+            CGNN_KNNB_LAUNCH(8);
+        else if (k <= 16)
+            CGNN_KNNB_LAUNCH(16);
+        else if (k <= 32)
+            CGNN_KNNB_LAUNCH(32);
+        else
+            CGNN_KNNB_LAUNCH(64);
+    }
+#undef CGNN_KNNB_LAUNCH
+#undef CGNN_KNNB_LAUNCH_MODE
+    return check_hip(hipGetLastError(), who);
+}
+
+int cgnn_knn_batched_sorted_order(const void* workspace, const int64_t* offsets, int32_t num_graphs, int32_t* perm,
+                                  void* stream) {
+    const char* who = "cgnn_knn_batched_sorted_order";
+    if (!workspace || !perm) {
+        set_error("%s: invalid argument", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    KnnBatchedLayout L;
+    const int rc = knn_batched_layout(who, offsets, num_graphs, L);
+    if (rc) return rc;
+    const float4* sorted = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(workspace) + L.off_sorted);
+    int64_t cell_base = 0;
+    for (int32_t g0 = 0; g0 < num_graphs; g0 += CGNN_KNN_BATCH_GROUP) {
+        const int32_t cnt = num_graphs - g0 < CGNN_KNN_BATCH_GROUP ? num_graphs - g0 : CGNN_KNN_BATCH_GROUP;
+        const KnnBatchTable T = knn_batch_table(offsets, g0, cnt, 1.0f, cell_base);
+        const unsigned nb = (unsigned)(((int64_t)T.row_base[cnt] - T.row_base[0] + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        knn_batched_perm_kernel<<<nb, CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, T, perm);
+    }
+    return check_hip(hipGetLastError(), who);
 }
 
 size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k) {

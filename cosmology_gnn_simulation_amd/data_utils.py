@@ -28,10 +28,10 @@ import torch
 
 from . import ops
 from ._lib import CgnnError
-from .graph import Data
+from .graph import Batch, Data
 
 __all__ = ["extend_positions_torch", "generate_position_noise", "generate_temperature_noise", "preprocess",
-           "knn_graph_periodic"]
+           "preprocess_batch", "knn_graph_periodic"]
 
 
 def _default_device() -> torch.device:
@@ -253,6 +253,116 @@ def _graph(x, edge_index, edge_attr, y_acc, y_temp_rate, recent_position, order,
     graph._cgnn_fixed_k_for = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape))
     graph._cgnn_order = order          # spatial (cell-sorted) particle order: a locality hint for the engine
     return graph
+
+
+def _batch_members(who: str, **named):
+    """The per-simulation tensors of batched arguments: each is one tensor whose first dimension counts the B
+    simulations, or a sequence of B tensors (ragged sizes); ``None`` stays ``None``.  All of them take the same form
+    and agree on B >= 1.  -> (dict of lists, B).  Touches no device."""
+    given = {name: v for name, v in named.items() if v is not None}
+    whole = [name for name, v in given.items() if torch.is_tensor(v)]
+    if whole and len(whole) != len(given):
+        raise TypeError(f"{who}: {whole} are tensors and {sorted(set(given) - set(whole))} are sequences; a batch is "
+                        f"either tensors with a leading batch dimension or sequences of per-simulation tensors")
+    out, sizes = {}, {}
+    for name, v in given.items():
+        if torch.is_tensor(v) and v.dim() < 2:
+            raise ValueError(f"{who}: {name} {tuple(v.shape)} has no batch dimension")
+        members = list(v.unbind(0)) if torch.is_tensor(v) else list(v)
+        if not all(torch.is_tensor(m) for m in members):
+            raise TypeError(f"{who}: {name} must hold tensors")
+        out[name], sizes[name] = members, len(members)
+    if len(set(sizes.values())) != 1:
+        raise ValueError(f"{who}: the arguments disagree on the number of simulations: {sizes}")
+    b = next(iter(sizes.values()))
+    if b < 1:
+        raise ValueError(f"{who}: a batch holds at least one simulation")
+    for name in named:
+        out.setdefault(name, None)
+    return out, b
+
+
+def preprocess_batch(position_seqs, temperature_seqs, metadata, target_positions=None, target_temperatures=None,
+                     noise_std=0.0, num_neighbors=16, dt=None, box_size=None, device: Optional[torch.device] = None,
+                     noise_seed: Optional[int] = None, noise_draw: int = 0, *, min_image_edge_attr: bool = False,
+                     knn_grid: str = "uniform") -> Batch:
+    """B windows -> one ``Batch``: what ``Batch.from_data_list([preprocess(..., noise_rng="device", noise_draw=
+    noise_draw + b, check_bounds=False) for b in range(B)])`` returns (the reference's batch, train.py:243-247), built
+    with ONE neighbour search over all simulations (``ops.knn_periodic_batched``) and without the list form's second
+    copy of every tensor.
+
+    ``position_seqs``: ``[B, W, N, 3]``, or a sequence of B tensors ``[W, N_b, 3]`` (simulations of different sizes);
+    ``temperature_seqs`` (``[W, N_b(, 1)]`` each) and the optional targets (``[N_b, 3]`` / ``[N_b(, 1)]`` each) take the
+    same form.  Every simulation is a periodic box of side ``box_size`` and shares ``metadata`` and ``dt``.
+
+    ``x``, ``edge_index``, ``edge_attr``, ``y_acc``, ``y_temp_rate``, ``pos``, ``dt``, ``box_size``, ``batch`` are equal
+    to the list form's bit for bit, ``num_graphs`` and the fixed in-degree hint as well; the locality hint
+    (``_cgnn_order``) is the batched search's own, block by block a cell-sorted order of each simulation.
+
+    Noise is the device generator only (``noise_seed``, ``noise_draw`` as in ``preprocess``): simulation b is sampled by
+    one ``cgnn_training_sample`` launch on its own window with draw ``noise_draw + b``, exactly the sample it gets alone.
+    No host synchronisation.  ``knn_grid="adaptive"`` searches graph by graph (``ops.knn_periodic_batched``)."""
+    who = "preprocess_batch"
+    ops.check_knn_grid(knn_grid, who)
+    ops.check_min_image(min_image_edge_attr, who)
+    m, nb = _batch_members(who, position_seqs=position_seqs, temperature_seqs=temperature_seqs,
+                           target_positions=target_positions, target_temperatures=target_temperatures)
+    k, dt, box_size = int(num_neighbors), float(dt), float(box_size)
+    offsets, w = [0], None
+    for b, p in enumerate(m["position_seqs"]):
+        if p.dim() != 3 or p.shape[2] != 3 or p.shape[1] < 1 or (w is not None and p.shape[0] != w):
+            raise ValueError(f"{who}: window {b} must be [W, N, 3] with the batch's W, got {tuple(p.shape)}")
+        w, n = int(p.shape[0]), int(p.shape[1])
+        if m["temperature_seqs"][b].numel() != w * n:
+            raise ValueError(f"{who}: temperature window {b} {tuple(m['temperature_seqs'][b].shape)} does not hold "
+                             f"[{w}, {n}(, 1)]")
+        if m["target_positions"] is not None and m["target_positions"][b].numel() != n * 3:
+            raise ValueError(f"{who}: target_positions {b} {tuple(m['target_positions'][b].shape)} does not hold "
+                             f"[{n}, 3]")
+        if m["target_temperatures"] is not None and m["target_temperatures"][b].numel() != n:
+            raise ValueError(f"{who}: target_temperatures {b} {tuple(m['target_temperatures'][b].shape)} does not "
+                             f"hold {n} values")
+        offsets.append(offsets[-1] + n)
+    if device is None:
+        first = m["position_seqs"][0]
+        device = first.device if first.is_cuda else _default_device()
+    device = torch.device(device)
+    want = ["x", "recent_pos"] + (["y_acc"] if m["target_positions"] is not None else []) + \
+        (["y_temp_rate"] if m["target_temperatures"] is not None else [])
+    seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
+    samples = []
+    for b in range(nb):
+        n = offsets[b + 1] - offsets[b]
+        tmp_w = m["temperature_seqs"][b].to(device)
+        if tmp_w.dim() == 3 and tmp_w.shape[0] == n and tmp_w.shape[1] == w:
+            tmp_w = tmp_w.permute(1, 0, 2)                                # [N, W, 1] -> [W, N, 1], as preprocess takes it
+        tp = m["target_positions"][b].to(device).reshape(n, 3) if "y_acc" in want else None
+        tt = m["target_temperatures"][b].to(device).reshape(n) if "y_temp_rate" in want else None
+        samples.append(ops.training_sample(m["position_seqs"][b].to(device), tmp_w, metadata, dt, box_size,
+                                           float(noise_std), seed % 2 ** 64, noise_draw + b, tp, tt, None, want))
+    s = {name: torch.cat([smp[name] for smp in samples]) for name in want}
+    recent = s["recent_pos"]
+    senders, edge_attr, order = ops.knn_periodic_batched(recent, offsets, box_size, k, True, True,
+                                                         min_image_edge_attr=min_image_edge_attr, grid=knn_grid)
+    n_total = offsets[-1]
+    receivers = torch.arange(n_total, device=device, dtype=torch.int64).repeat_interleave(k)
+    y_tr = s.get("y_temp_rate")
+    out = Batch(x=s["x"], edge_index=torch.stack([senders.to(torch.int64), receivers], dim=0), edge_attr=edge_attr,
+                y_acc=s.get("y_acc"), y_temp_rate=y_tr.reshape(n_total, 1) if y_tr is not None else None, pos=recent,
+                dt=torch.full((nb,), dt, dtype=torch.float32, device=device),
+                box_size=torch.full((nb,), box_size, dtype=torch.float32, device=device),
+                batch=batch_vector(offsets, device), num_graphs=nb)
+    out._cgnn_fixed_k = k
+    out._cgnn_fixed_k_for = (out.edge_index.data_ptr(), out.edge_index._version, tuple(out.edge_index.shape))
+    out._cgnn_order = order
+    return out
+
+
+def batch_vector(offsets, device) -> torch.Tensor:
+    """``batch[i]`` = the graph of row i (int64 ``[offsets[-1]]``), as ``Batch.from_data_list`` writes it: one fill per
+    graph, nothing copied from the host."""
+    return torch.cat([torch.full((b - a,), g, dtype=torch.long, device=device)
+                      for g, (a, b) in enumerate(zip(offsets, offsets[1:]))])
 
 
 def _preprocess_device_noise(position_seq, temperature_seq, metadata, target_position, target_temperature, noise_std,

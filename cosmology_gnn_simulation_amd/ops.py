@@ -670,6 +670,68 @@ def knn_periodic(pos: torch.Tensor, box_size: float, k: int, query_ids: Optional
     return senders, edge_attr, order
 
 
+def check_batch_offsets(offsets, who: str) -> List[int]:
+    """``offsets`` of a batch of graphs as a list of ints: B + 1 >= 2 values, the first 0, strictly increasing.  Host
+    values (a list, or a CPU tensor): a device tensor would have to be read back, and is refused."""
+    if torch.is_tensor(offsets):
+        if offsets.is_cuda:
+            raise CgnnError(f"{who}: offsets are host values (a list or a CPU tensor), got a tensor on {offsets.device}")
+        offsets = offsets.tolist()
+    offsets = [int(o) for o in offsets]
+    if len(offsets) < 2 or offsets[0] != 0 or any(b <= a for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"{who}: offsets must hold B + 1 >= 2 strictly increasing values starting at 0, got {offsets}")
+    return offsets
+
+
+def knn_periodic_batched(pos: torch.Tensor, offsets, box_size: float, k: int, want_edge_attr: bool = True,
+                         want_order: bool = False, *, min_image_edge_attr: bool = False, grid: str = "uniform"):
+    """:func:`knn_periodic` over a batch of B independent periodic boxes of side ``box_size`` in one search
+    (``cgnn_knn_periodic_batched``): ``pos [n_total, 3]`` holds the simulations one after another, ``offsets`` (B + 1
+    host ints, see :func:`check_batch_offsets`) says where each begins.  Returns the same triple, ``(senders int32
+    [n_total * k], edge_attr [n_total * k, 4] | None, order int32 [n_total] | None)``: block g holds the bits
+    ``knn_periodic(pos[offsets[g]:offsets[g + 1]], ...)`` gives, ``offsets[g]`` added to every sender and to every entry
+    of ``order`` (whose order inside a cell is unspecified, as there).  No edge joins two simulations.  The number of
+    launches does not grow with B (one more of each stage per ``_lib.KNN_BATCH_GROUP`` graphs); a batch of one graph runs
+    the same kernels.
+
+    ``grid="adaptive"`` has no batched kernel: it loops over per-graph ``knn_periodic(..., grid="adaptive")`` calls and
+    offsets their results.  ``senders`` and ``edge_attr`` are the same bits either way, so the option stays usable
+    wherever a ``knn_grid`` is passed down; it only forgoes the single search."""
+    what = "knn_periodic_batched"
+    check_knn_grid(grid, what)
+    check_min_image(min_image_edge_attr, what)
+    offsets = check_batch_offsets(offsets, what)
+    pos = f32c(pos, "pos")
+    if pos.dim() != 2 or pos.shape[1] != 3 or pos.shape[0] != offsets[-1]:
+        raise CgnnError(f"{what}: pos must be [{offsets[-1]}, 3] (offsets[-1] rows), got {tuple(pos.shape)}")
+    n, num_graphs, k = offsets[-1], len(offsets) - 1, int(k)
+    if grid == "adaptive":
+        parts = [knn_periodic(pos[a:b], box_size, k, None, want_edge_attr, want_order,
+                              min_image_edge_attr=min_image_edge_attr, grid="adaptive")
+                 for a, b in zip(offsets, offsets[1:])]
+        return (torch.cat([p[0] + a for p, a in zip(parts, offsets)]),
+                torch.cat([p[1] for p in parts]) if want_edge_attr else None,
+                torch.cat([p[2] + a for p, a in zip(parts, offsets)]) if want_order else None)
+    lib = _lib.load()
+    offs = (C.c_int64 * (num_graphs + 1))(*offsets)
+    ws_bytes = lib.cgnn_knn_batched_workspace_bytes(offs, num_graphs, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+    senders = torch.empty(n * k, dtype=torch.int32, device=pos.device)
+    edge_attr = torch.empty((n * k, 4), dtype=torch.float32, device=pos.device) if want_edge_attr else None
+    mode = _lib.KNN_EDGE_ATTR_IMAGE if min_image_edge_attr else _lib.KNN_EDGE_ATTR_REFERENCE
+    st = stream_ptr(pos.device)
+    with _timed(what, pos.device):
+        check(lib.cgnn_knn_periodic_batched(pos.data_ptr(), offs, num_graphs, float(box_size), k, senders.data_ptr(),
+                                            ptr(edge_attr), ws.data_ptr(), ws_bytes, st, mode),
+              "cgnn_knn_periodic_batched")
+    order = None
+    if want_order:
+        order = torch.empty(n, dtype=torch.int32, device=pos.device)
+        check(lib.cgnn_knn_batched_sorted_order(ws.data_ptr(), offs, num_graphs, order.data_ptr(), st),
+              "cgnn_knn_batched_sorted_order")
+    return senders, edge_attr, order
+
+
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,
                     pos_noise: Optional[torch.Tensor] = None, temp_noise: Optional[torch.Tensor] = None):
     """``[W, N, 3]`` positions and ``[W, N(, 1)]`` temperatures -> ``(x [N, 3(W-1)+W], recent_pos [N, 3])``

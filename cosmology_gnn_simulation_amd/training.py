@@ -535,13 +535,38 @@ def permute_rows(rows: torch.Tensor, idx: torch.Tensor, inv: torch.Tensor) -> to
 
 class _LinkConfig:
     """What the links of one :func:`unrolled_loss` call share: metadata with ``dt`` / ``box_size``, the host statistics
-    block and the identity row list of ``ops.rollout_integrate``, each made once."""
+    block and the identity row list of ``ops.rollout_integrate``, each made once.  ``offsets`` (B + 1 host ints, ``n`` the
+    last) makes the ``n`` rows a batch of B simulations (:func:`unrolled_batch_loss`): the graph builds then take the
+    batched forms, whose per-row tables are made once here as well, and every step's graph carries ``batch`` /
+    ``num_graphs``."""
 
-    def __init__(self, metadata: dict, dt: float, box_size: float, n: int, device):
+    def __init__(self, metadata: dict, dt: float, box_size: float, n: int, device, offsets: Optional[Sequence[int]] = None):
         self.meta = dict(metadata, dt=float(dt), box_size=float(box_size))
         self.dt, self.box = float(dt), float(box_size)
         self.stats = ops.integration_stats(self.meta)
         self.ids = torch.arange(n, dtype=torch.int64, device=device)
+        self.offsets = None if offsets is None else [int(o) for o in offsets]
+        self.order_rows = None if offsets is None else _spatial_order_rows(self.offsets, self.box, device)
+
+    def graph_lists(self, recent, edge: bool, k: int, knn_grid: str, min_image: bool):
+        """-> (edge_attr, senders, order) of the step graph on the last frame ``recent``; the edge features carry
+        gradient only where the model reads them (``edge``)."""
+        src = recent if edge else recent.detach()
+        if self.offsets is None:
+            edge_attr, senders = _KnnEdgeAttr.apply(src, self.box, k, knn_grid, min_image)
+            return edge_attr, senders, spatial_order(recent, self.box)
+        edge_attr, senders = _KnnEdgeAttrBatched.apply(src, self.offsets, self.box, k, knn_grid, min_image)
+        return edge_attr, senders, spatial_order_batched(recent, self.offsets, self.box, rows=self.order_rows)
+
+    def graph(self, x, edge_index, edge_attr, y_acc, y_tr, recent, order, k: int):
+        """The step's ``Data`` (``data_utils._graph``), with ``batch`` / ``num_graphs`` for a batch."""
+        from . import data_utils
+        n = x.shape[0]
+        graph = data_utils._graph(x, edge_index, edge_attr, y_acc, y_tr.reshape(n, 1), recent, order, self.dt, self.box,
+                                  k, x.device)
+        if self.offsets is not None:
+            graph.batch, graph.num_graphs = self.order_rows[0], len(self.offsets) - 1
+        return graph
 
 
 class _SampleLink(torch.autograd.Function):
@@ -599,6 +624,30 @@ class _KnnEdgeAttr(torch.autograd.Function):
         return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender), None, None, None, None
 
 
+class _KnnEdgeAttrBatched(torch.autograd.Function):
+    """:class:`_KnnEdgeAttr` over a batch of simulations (``ops.knn_periodic_batched`` on ``offsets``).  The senders are
+    global rows and never leave their graph, so the backward is the single graph's on all rows."""
+
+    @staticmethod
+    def forward(ctx, recent, offsets, box: float, k: int, grid: str, min_image: bool):
+        senders, edge_attr, _ = ops.knn_periodic_batched(recent, offsets, box, k, True, False,
+                                                         min_image_edge_attr=min_image, grid=grid)
+        ctx.k, ctx.n = k, recent.shape[0]
+        ctx.save_for_backward(edge_attr, senders)
+        ctx.mark_non_differentiable(senders)
+        ctx.set_materialize_grads(False)
+        return edge_attr, senders
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_edge_attr, _d_senders):
+        if d_edge_attr is None:
+            return (None,) * 6
+        edge_attr, senders = ctx.saved_tensors
+        by_sender = ops.SenderCsr(senders, None, ctx.n)
+        return (ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender),) + (None,) * 5
+
+
 def _spread3(v: torch.Tensor) -> torch.Tensor:
     """10 bits -> every third bit (the Morton spread of csrc/knn.hip, on int64 tensors)."""
     v = (v | (v << 16)) & 0x030000FF
@@ -619,6 +668,38 @@ def spatial_order(pos: torch.Tensor, box: float, per_cell: int = 8) -> torch.Ten
     g = 1 << bits
     c = _spread3((pos.detach() * (g / float(box))).floor_().clamp_(0, g - 1).to(torch.int64))
     key = (c[:, 0] << 2) | (c[:, 1] << 1) | c[:, 2]
+    return torch.argsort(key, stable=True).to(torch.int32)
+
+
+def _spatial_order_cells(n: int, per_cell: int = 8) -> int:
+    """Cells per axis of :func:`spatial_order` for ``n`` particles."""
+    return 1 << max(0, min(10, int(math.log2(max(n / per_cell, 1.0)) / 3)))
+
+
+def _spatial_order_rows(offsets: Sequence[int], box: float, device, per_cell: int = 8):
+    """Per-row tables of :func:`spatial_order_batched`: (graph of the row int64 ``[n]``, its graph's cell scale and last
+    cell coordinate float32 ``[n, 1]``), written by one fill per graph."""
+    from . import data_utils
+    cells = [_spatial_order_cells(b - a, per_cell) for a, b in zip(offsets, offsets[1:])]
+
+    def rows(values):
+        return torch.cat([torch.full((b - a, 1), v, dtype=torch.float32, device=device)
+                          for v, a, b in zip(values, offsets, offsets[1:])])
+    return data_utils.batch_vector(offsets, device), rows([g / float(box) for g in cells]), rows([g - 1 for g in cells])
+
+
+def spatial_order_batched(pos: torch.Tensor, offsets: Sequence[int], box: float, per_cell: int = 8, *,
+                          rows=None) -> torch.Tensor:
+    """:func:`spatial_order` of a batch of simulations in one sort: block g of the result (int32 ``[offsets[-1]]``) is
+    ``offsets[g] + spatial_order(pos[offsets[g]:offsets[g + 1]], box)``, every graph with the grid its own size gives
+    it.  The graph index is the top of the sort key and the sort is stable, so a block holds its own rows in the single
+    graph's order.  ``rows``: the per-row tables (:func:`_spatial_order_rows`) when the caller keeps them across calls."""
+    offsets = ops.check_batch_offsets(offsets, "spatial_order_batched")
+    if pos.shape[0] != offsets[-1]:
+        raise ValueError(f"spatial_order_batched: {pos.shape[0]} rows for offsets ending at {offsets[-1]}")
+    batch, scale, top = rows if rows is not None else _spatial_order_rows(offsets, box, pos.device, per_cell)
+    c = _spread3(torch.minimum((pos.detach() * scale).floor_(), top).clamp_min_(0).to(torch.int64))
+    key = (batch << 30) | (c[:, 0] << 2) | (c[:, 1] << 1) | c[:, 2]
     return torch.argsort(key, stable=True).to(torch.int32)
 
 
@@ -796,10 +877,12 @@ class UnrolledLoss:
     acceleration, temperature-rate and momentum term per step), ``frames`` (detached predicted ``Coordinates [S, N, 3]``
     and ``InternalEnergy [S, N, 1]``) and ``graphs`` (the S ``Data`` objects under ``keep_graphs``, else ``None``).
     ``value``: ``None`` on one GPU; from ``dist.sharded_unrolled_loss`` the all-reduced global loss (0-d float64, the same
-    on every rank), ``loss`` then being this rank's part to differentiate."""
+    on every rank), ``loss`` then being this rank's part to differentiate.  ``offsets``: ``None``; from
+    :func:`unrolled_batch_loss` the B + 1 row offsets of the simulations in the frames' ``n_total`` rows."""
 
     def __init__(self, loss, step_losses, frames, graphs, value=None):
         self.loss, self.step_losses, self.frames, self.graphs, self.value = loss, step_losses, frames, graphs, value
+        self.offsets = None     # unrolled_batch_loss: B + 1 ints, simulation b holds rows offsets[b]:offsets[b + 1]
 
 
 # ---- activation checkpointing across steps (unrolled_loss(checkpoint="steps")) -------------------------------------------
@@ -850,23 +933,21 @@ class _CheckpointedUnroll:
         self.knn_grid, self.min_image, self.loss_weights, self.keep_graphs = knn_grid, min_image, loss_weights, keep_graphs
         self.params = list(model.parameters())
         self.receivers = cfg.ids.repeat_interleave(k)
-        self.first = None       # step 0's true window, target and noise arguments
+        self.first = None       # step 0's sample from the true window again: first(want) -> ops.training_sample's dict
         self.s0 = None          # step 0's sample of the first run
 
     def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool, integrate: bool):
         """-> (weighted loss term, new_pos | None, new_temp | None).  ``frames``: the W position frames, then the W
         temperature frames.  ``kept``: build the graph from ``rec``'s lists; else search and, without autograd, fill
         ``rec``."""
-        from . import data_utils, losses
+        from . import losses
         cfg, w, n, k, edge = self.cfg, self.w, self.n, self.k, self.edge
         grad = torch.is_grad_enabled()
         if rec.s == 0:
             if self.s0 is not None:
                 s0, self.s0 = self.s0, None
             else:
-                pos_w, tmp_w, tgt_p0, tgt_t0, std, seed, draw = self.first
-                s0 = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, std, seed, draw, tgt_p0, tgt_t0, None,
-                                         ["x", "recent_pos", "y_acc", "y_temp_rate"], stats=cfg.stats)
+                s0 = self.first(["x", "recent_pos", "y_acc", "y_temp_rate"])
             x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
         else:
             x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p, tgt_t, *frames)
@@ -877,16 +958,12 @@ class _CheckpointedUnroll:
             else:       # x_j reads the width of the edge features only (the edge stream is dead): no N k rows for it
                 edge_attr = recent.new_zeros((1, 4)).expand(n * k, 4)
         else:
-            # the edge features carry gradient only where the model reads them
-            edge_attr, senders = _KnnEdgeAttr.apply(recent if edge else recent.detach(), cfg.box, k, self.knn_grid,
-                                                    self.min_image)
-            order = spatial_order(recent, cfg.box)
+            edge_attr, senders, order = cfg.graph_lists(recent, edge, k, self.knn_grid, self.min_image)
             if not grad:
                 rec.senders, rec.order = senders, order
                 rec.edge_attr = edge_attr if edge else None
         edge_index = torch.stack([senders.to(torch.int64), self.receivers], dim=0)
-        graph = data_utils._graph(x, edge_index, edge_attr, y_acc, y_tr.reshape(n, 1), recent.detach(), order, cfg.dt,
-                                  cfg.box, k, x.device)
+        graph = cfg.graph(x, edge_index, edge_attr, y_acc, y_tr, recent.detach(), order, k)
         pred = self.model._forward_train(graph)         # the training forward with or without autograd: the same kernels
         acc, rate = pred["acceleration"], pred["temp_rate"]
         mse = torch.nn.functional.mse_loss
@@ -896,9 +973,8 @@ class _CheckpointedUnroll:
         if not kept:
             rec.terms = torch.stack([t.detach() for t in terms])
             if self.keep_graphs:        # detached tensors: the last step's graph does not hold its autograd graph
-                rec.graph = graph if not grad else data_utils._graph(
-                    x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach().reshape(n, 1),
-                    recent.detach(), order, cfg.dt, cfg.box, k, x.device)
+                rec.graph = graph if not grad else cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(),
+                                                             y_tr.detach(), recent.detach(), order, k)
         new_p = new_t = None
         if integrate:
             p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
@@ -979,12 +1055,14 @@ class _CheckpointedStep(torch.autograd.Function):
 
 
 def _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures, step_weights,
-                      backprop_steps, num_neighbors, knn_grid, min_image_edge_attr, checkpoint="none"):
-    """The checks of :func:`unrolled_loss` that need no device: -> (W, N, S, weights)."""
+                      backprop_steps, num_neighbors, knn_grid, min_image_edge_attr, checkpoint="none",
+                      who="unrolled_loss"):
+    """The checks of :func:`unrolled_loss` that need no device: -> (W, N, S, weights).  ``who`` names the caller in the
+    messages about shapes and options."""
     from .graph_network import EncodeProcessDecode
-    check_checkpoint(checkpoint, "unrolled_loss")
-    ops.check_knn_grid(knn_grid, "unrolled_loss")
-    ops.check_min_image(min_image_edge_attr, "unrolled_loss")
+    check_checkpoint(checkpoint, who)
+    ops.check_knn_grid(knn_grid, who)
+    ops.check_min_image(min_image_edge_attr, who)
     if not isinstance(model, EncodeProcessDecode):
         raise NotImplementedError("unrolled_loss trains one EncodeProcessDecode on one GPU; over spatial shards "
                                   "dist.sharded_unrolled_loss unrolls the steps (dist.ShardedTraining is one step)")
@@ -992,28 +1070,28 @@ def _unroll_arguments(model, position_seq, temperature_seq, target_positions, ta
         raise NotImplementedError("unrolled_loss takes one graph per call ([W, N, 3]); multi-graph batches are not "
                                   "unrolled")
     if position_seq.dim() != 3 or position_seq.shape[2] != 3:
-        raise ValueError(f"unrolled_loss: position_seq must be [W, N, 3], got {tuple(position_seq.shape)}")
+        raise ValueError(f"{who}: position_seq must be [W, N, 3], got {tuple(position_seq.shape)}")
     w, n = int(position_seq.shape[0]), int(position_seq.shape[1])
     if w < 2:
-        raise ValueError(f"unrolled_loss: a window holds at least 2 frames, got {w}")
+        raise ValueError(f"{who}: a window holds at least 2 frames, got {w}")
     if w > ops.UNROLL_MAX_WINDOW:
-        raise ValueError(f"unrolled_loss: windows of up to {ops.UNROLL_MAX_WINDOW} frames, got {w}")
+        raise ValueError(f"{who}: windows of up to {ops.UNROLL_MAX_WINDOW} frames, got {w}")
     if temperature_seq.numel() != w * n or temperature_seq.shape[0] != w:
-        raise ValueError(f"unrolled_loss: temperature_seq {tuple(temperature_seq.shape)} does not hold [{w}, {n}(, 1)]")
+        raise ValueError(f"{who}: temperature_seq {tuple(temperature_seq.shape)} does not hold [{w}, {n}(, 1)]")
     if target_positions.dim() != 3 or target_positions.shape[0] < 1 or tuple(target_positions.shape[1:]) != (n, 3):
-        raise ValueError(f"unrolled_loss: target_positions {tuple(target_positions.shape)} does not hold [S, {n}, 3] "
+        raise ValueError(f"{who}: target_positions {tuple(target_positions.shape)} does not hold [S, {n}, 3] "
                          f"with S >= 1")
     s = int(target_positions.shape[0])
     if target_temperatures.dim() < 2 or target_temperatures.shape[0] != s or target_temperatures.numel() != s * n:
-        raise ValueError(f"unrolled_loss: target_temperatures {tuple(target_temperatures.shape)} does not hold "
+        raise ValueError(f"{who}: target_temperatures {tuple(target_temperatures.shape)} does not hold "
                          f"[{s}, {n}(, 1)]")
     if backprop_steps is not None and (int(backprop_steps) != backprop_steps or backprop_steps < 0):
-        raise ValueError(f"unrolled_loss: backprop_steps must be None or an integer >= 0, got {backprop_steps!r}")
+        raise ValueError(f"{who}: backprop_steps must be None or an integer >= 0, got {backprop_steps!r}")
     if int(num_neighbors) < 1:
-        raise ValueError(f"unrolled_loss: num_neighbors must be positive, got {num_neighbors}")
+        raise ValueError(f"{who}: num_neighbors must be positive, got {num_neighbors}")
     weights = [1.0 / s] * s if step_weights is None else [float(v) for v in step_weights]
     if len(weights) != s:
-        raise ValueError(f"unrolled_loss: {len(weights)} step weights for {s} steps")
+        raise ValueError(f"{who}: {len(weights)} step weights for {s} steps")
     if getattr(model, "train_edge_stream", False):
         raise NotImplementedError("unrolled_loss does not run the dead edge stream (model.train_edge_stream)")
     source = getattr(model, "message_source", "x_j")
@@ -1022,7 +1100,7 @@ def _unroll_arguments(model, position_seq, temperature_seq, target_positions, ta
                                   "True")
     prec = getattr(model, "train_precision", "fp32")
     if ops._prec(prec) not in (_lib.F32, _lib.F32X3):
-        raise CgnnError(f"unrolled_loss: train_precision must be 'fp32' or 'fp32x3', got {prec!r}")
+        raise CgnnError(f"{who}: train_precision must be 'fp32' or 'fp32x3', got {prec!r}")
     return w, n, s, weights
 
 
@@ -1071,7 +1149,7 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     every step (``(4 W - 3 + 4 k) 4 N`` bytes each): not part of the small record, and not counted by the estimate.
     S = 1, or a model without a parameter that requires a gradient, takes the ``"none"`` path.  Any other value raises
     ``ValueError`` before a launch."""
-    from . import data_utils, losses
+    from . import data_utils
     w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
                                          step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr,
                                          checkpoint)
@@ -1079,28 +1157,49 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     if device is None:
         device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
     device = torch.device(device)
-    edge = getattr(model, "message_source", "x_j") == "edge"
-    need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                   len(model.processor), S, edge, checkpoint)
-    free = free_device_bytes(device)
-    if need > free:
-        raise CgnnError(f"unrolled_loss needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
-                        f"steps under checkpoint={checkpoint!r} ({n} particles, {k} neighbours, latent {model._latent_size}, {len(model.processor)} "
-                        f"rounds); {free / 2**30:.1f} GiB are free")
+    _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device)
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
     pos_w = _lib.f32c(position_seq.to(device), "position_seq")
     tmp_w = _lib.f32c(temperature_seq.to(device), "temperature_seq").reshape(w, n)
     tgt_p = _lib.f32c(target_positions.to(device), "target_positions")
     tgt_t = _lib.f32c(target_temperatures.to(device), "target_temperatures").reshape(S, n)
-    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
-
-    # step 0: the one-step sample, with noise from the counter-based generator
     seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
-    noisy = float(noise_std) != 0.0
-    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
-    s0 = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
-                             tgt_p[0], tgt_t[0], None, want, stats=cfg.stats)
     true_window = (pos_w, tmp_w, tgt_p[0], tgt_t[0])
+
+    def sample0(want):      # step 0: the one-step sample, with noise from the counter-based generator
+        pos0, tmp0, tgt_p0, tgt_t0 = true_window
+        return ops.training_sample(pos0, tmp0, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
+                                   tgt_p0, tgt_t0, None, want, stats=cfg.stats)
+    return _unroll(model, cfg, w, n, k, weights, backprop_steps, sample0, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p,
+                   tgt_t, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), knn_grid, min_image_edge_attr,
+                   keep_graphs, checkpoint)
+
+
+def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device) -> None:
+    """``CgnnError`` when :func:`unrolled_training_bytes` for ``n`` rows exceeds the free device memory."""
+    edge = getattr(model, "message_source", "x_j") == "edge"
+    need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
+                                   len(model.processor), S, edge, checkpoint)
+    free = free_device_bytes(device)
+    if need > free:
+        raise CgnnError(f"{who} needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
+                        f"steps under checkpoint={checkpoint!r} ({n} particles, {k} neighbours, latent {model._latent_size}, {len(model.processor)} "
+                        f"rounds); {free / 2**30:.1f} GiB are free")
+
+
+def _unroll(model, cfg: _LinkConfig, w: int, n: int, k: int, weights, backprop_steps, sample0, noisy: bool, pos_w, tmp_w,
+            tgt_p, tgt_t, loss_weights, knn_grid: str, min_image_edge_attr: bool, keep_graphs: bool,
+            checkpoint: str) -> UnrolledLoss:
+    """The steps of :func:`unrolled_loss` / :func:`unrolled_batch_loss` over the ``n`` rows of ``cfg``: the true window
+    ``pos_w [W, n, 3]`` / ``tmp_w [W, n]``, the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``, and ``sample0(want)``,
+    which makes step 0's (noisy) sample of the true window as ``ops.training_sample`` returns it."""
+    from . import losses
+    S = len(weights)
+    acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight = loss_weights
+    edge = getattr(model, "message_source", "x_j") == "edge"
+    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
+    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
+    s0 = sample0(want)
     if noisy:       # the noisy frames later windows read, and the shift of every later target
         pos_w = pos_w + s0["pos_noise"].permute(1, 0, 2)
         tmp_w = tmp_w + s0["temp_noise"].t()
@@ -1109,10 +1208,9 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
             tgt_t = tgt_t + s0["temp_noise"][:, -1]
     pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
     if checkpoint == "steps" and S > 1 and any(q.requires_grad for q in model.parameters()):
-        unroll = _CheckpointedUnroll(model, cfg, w, n, k, edge, knn_grid, min_image_edge_attr,
-                                     (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), keep_graphs)
+        unroll = _CheckpointedUnroll(model, cfg, w, n, k, edge, knn_grid, min_image_edge_attr, loss_weights, keep_graphs)
         # step 0 draws again from the true window in its recomputation: the same (seed, draw), the same sample
-        unroll.first = (*true_window, float(noise_std), seed % 2 ** 64, noise_draw)
+        unroll.first = sample0
         return unroll.run(s0, pos_frames, tmp_frames, tgt_p, tgt_t, weights, links)
 
     total = None
@@ -1124,13 +1222,9 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
             x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
         else:
             x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p[s], tgt_t[s], *pos_frames[-w:], *tmp_frames[-w:])
-        # the edge features carry gradient only where the model reads them
-        edge_attr, senders = _KnnEdgeAttr.apply(recent if edge else recent.detach(), cfg.box, k, knn_grid,
-                                                min_image_edge_attr)
-        order = spatial_order(recent, cfg.box)
+        edge_attr, senders, order = cfg.graph_lists(recent, edge, k, knn_grid, min_image_edge_attr)
         edge_index = torch.stack([senders.to(torch.int64), receivers], dim=0)
-        graph = data_utils._graph(x, edge_index, edge_attr, y_acc, y_tr.reshape(n, 1), recent.detach(), order, cfg.dt,
-                                  cfg.box, k, device)
+        graph = cfg.graph(x, edge_index, edge_attr, y_acc, y_tr, recent.detach(), order, k)
         pred = model(graph)
         acc, rate = pred["acceleration"], pred["temp_rate"]
         terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
@@ -1154,3 +1248,73 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
         tmp_frames.append(new_t)
     frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
     return UnrolledLoss(total, torch.stack(step_losses), frames, graphs if keep_graphs else None)
+
+
+def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions, target_temperatures, metadata: dict, *,
+                        dt: float, box_size: float, num_neighbors: int = 16, noise_std: float = 0.0,
+                        noise_seed: Optional[int] = None, noise_draw: int = 0, acc_loss_weight: float = 1.0,
+                        temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
+                        step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
+                        min_image_edge_attr: bool = False, knn_grid: str = "uniform", keep_graphs: bool = False,
+                        device: Optional[torch.device] = None, checkpoint: str = "none") -> UnrolledLoss:
+    """:func:`unrolled_loss` for a batch of B simulations, each a periodic box of side ``box_size``: every step is ONE
+    graph batch over ``n_total = sum N_b`` rows in batch order -- one batched neighbour search
+    (``ops.knn_periodic_batched``), one model forward and backward, one integration -- instead of B of each.
+
+    ``position_seqs``: ``[B, W, N, 3]``, or a sequence of B windows ``[W, N_b, 3]`` (simulations of different sizes);
+    ``temperature_seqs`` (``[W, N_b(, 1)]`` each), ``target_positions`` (``[S, N_b, 3]`` each) and
+    ``target_temperatures`` (``[S, N_b(, 1)]`` each) take the same form.  The frames are concatenated once.
+
+    A step's loss is the reference's batch loss (train.py:255-260): the two MSE terms over all rows of the batch, the
+    momentum term averaged over the graphs; ``loss = sum_s step_weights[s] * loss_s``.  Simulation b's noise is the one
+    it gets alone with draw ``noise_draw + b`` (one ``cgnn_training_sample`` launch per simulation in step 0, as in
+    ``data_utils.preprocess_batch``).  Every other keyword keeps its meaning; the memory estimate is taken at
+    ``n_total`` rows.  ``knn_grid="adaptive"`` searches graph by graph.
+
+    Returns an :class:`UnrolledLoss` whose ``frames`` are ``[S, n_total, 3]`` / ``[S, n_total, 1]`` in batch row order,
+    with ``offsets`` (B + 1 ints: simulation b holds rows ``offsets[b]:offsets[b + 1]``).  Every kernel between the
+    frames and the predictions works row by row on its own graph's rows, so simulation b's frames are the bits of its
+    own :func:`unrolled_loss` call with ``noise_draw + b``; the loss and the gradients are the same sums taken over all
+    rows at once."""
+    from . import data_utils
+    who = "unrolled_batch_loss"
+    m, nb = data_utils._batch_members(who, position_seqs=position_seqs, temperature_seqs=temperature_seqs,
+                                      target_positions=target_positions, target_temperatures=target_temperatures)
+    if any(v is None for v in m.values()):
+        raise TypeError(f"{who}: windows and targets are all required")
+    offsets, shape = [0], None
+    for b in range(nb):
+        w, n_b, S, weights = _unroll_arguments(model, m["position_seqs"][b], m["temperature_seqs"][b],
+                                               m["target_positions"][b], m["target_temperatures"][b], step_weights,
+                                               backprop_steps, num_neighbors, knn_grid, min_image_edge_attr, checkpoint,
+                                               who=f"{who} (simulation {b})")
+        if shape is not None and shape != (w, S):
+            raise ValueError(f"{who}: simulation {b} has a window of {w} frames and {S} target steps, the ones before "
+                             f"{shape[0]} and {shape[1]}")
+        shape = (w, S)
+        offsets.append(offsets[-1] + n_b)
+    k, n = int(num_neighbors), offsets[-1]
+    if device is None:
+        first = m["position_seqs"][0]
+        device = first.device if first.is_cuda else data_utils._default_device()
+    device = torch.device(device)
+    _check_unroll_memory(who, model, n, k, w, S, checkpoint, device)
+    cfg = _LinkConfig(metadata, dt, box_size, n, device, offsets)
+    sizes = [b - a for a, b in zip(offsets, offsets[1:])]
+    pos_b = [_lib.f32c(p.to(device), "position_seqs") for p in m["position_seqs"]]
+    tmp_b = [_lib.f32c(t.to(device), "temperature_seqs").reshape(w, n_b) for t, n_b in zip(m["temperature_seqs"], sizes)]
+    tgt_p = torch.cat([_lib.f32c(t.to(device), "target_positions") for t in m["target_positions"]], dim=1)
+    tgt_t = torch.cat([_lib.f32c(t.to(device), "target_temperatures").reshape(S, n_b)
+                       for t, n_b in zip(m["target_temperatures"], sizes)], dim=1)
+    seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
+
+    def sample0(want):      # step 0: every simulation's own sample (its particle ids and its draw), rows joined
+        parts = [ops.training_sample(pos_b[b], tmp_b[b], cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64,
+                                     noise_draw + b, tgt_p[0, offsets[b]:offsets[b + 1]],
+                                     tgt_t[0, offsets[b]:offsets[b + 1]], None, want, stats=cfg.stats) for b in range(nb)]
+        return {name: torch.cat([part[name] for part in parts]) for name in want}
+    out = _unroll(model, cfg, w, n, k, weights, backprop_steps, sample0, float(noise_std) != 0.0, torch.cat(pos_b, dim=1),
+                  torch.cat(tmp_b, dim=1), tgt_p, tgt_t, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight),
+                  knn_grid, min_image_edge_attr, keep_graphs, checkpoint)
+    out.offsets = offsets
+    return out

@@ -517,6 +517,27 @@ int cgnn_knn_periodic_adaptive_mode(const float* pos, int64_t n, float box_size,
                                     int32_t* senders, float* edge_attr,
                                     void* workspace, size_t workspace_bytes, void* stream, int32_t edge_attr_mode);
 
+/* One neighbour search over a batch of num_graphs independent periodic boxes of side box_size (the graphs a training
+ * batch joins, reference train.py:247): pos [n_total, 3] holds the simulations one after another, offsets (HOST memory,
+ * num_graphs + 1 values, offsets[0] = 0, strictly increasing, offsets[num_graphs] = n_total) says where each begins.
+ * With o = offsets[g] and n_g the size of graph g, rows [o k, (o + n_g) k) of senders (and the same rows times 4 of
+ * edge_attr, which may be NULL) hold the bits cgnn_knn_periodic_mode gives for pos[o : o + n_g] alone, o added to every
+ * sender: no edge joins two graphs.  The ordering contract is per graph, ascending (d2, image index) with image index
+ * = shift_id * n_g + local particle.  Uniform grid, all particles are queries.  Nothing waits for the device; every
+ * stage (count, one scan over all graphs' cell tables, fill, search) takes all graphs in one launch per
+ * CGNN_KNN_BATCH_GROUP graphs, whose per-graph grid data travel by value in the kernel arguments.
+ * Checks as cgnn_knn_periodic_mode (n_total >= 2^31 or a graph of 2^27 or more particles: CGNN_ERR_UNSUPPORTED), and
+ * num_graphs < 1, an empty graph, offsets that do not increase, k > 27 n_g for some g: CGNN_ERR_INVALID_ARG.
+ * cgnn_knn_batched_sorted_order: perm [n_total] of the last search on this workspace; block g is a cell-sorted
+ * permutation of graph g's own rows, as global row numbers (inside a cell the order is unspecified). */
+#define CGNN_KNN_BATCH_GROUP 64
+size_t cgnn_knn_batched_workspace_bytes(const int64_t* offsets, int32_t num_graphs, int32_t k);
+int cgnn_knn_periodic_batched(const float* pos, const int64_t* offsets, int32_t num_graphs, float box_size, int32_t k,
+                              int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                              void* stream, int32_t edge_attr_mode);
+int cgnn_knn_batched_sorted_order(const void* workspace, const int64_t* offsets, int32_t num_graphs,
+                                  int32_t* perm, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes
