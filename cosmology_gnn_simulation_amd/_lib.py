@@ -48,7 +48,9 @@ EXPORTS = (
     "cgnn_training_sample_backward", "cgnn_rollout_integrate_backward", "cgnn_edge_attr_backward",
     "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows", "cgnn_mlp_rows_project",
     "cgnn_knn_batched_workspace_bytes", "cgnn_knn_periodic_batched", "cgnn_knn_batched_sorted_order",
+    "cgnn_pair_counts_workspace_bytes", "cgnn_pair_counts", "cgnn_frame_errors_workspace_bytes", "cgnn_frame_errors",
 )
+PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -135,6 +137,12 @@ def load() -> C.CDLL:
     lib.cgnn_knn_batched_workspace_bytes.argtypes = [C.POINTER(i64), i32, i32]      # offsets: host memory
     lib.cgnn_knn_periodic_batched.argtypes = [vp, C.POINTER(i64), i32, f32, i32, vp, vp, vp, sz, vp, i32]
     lib.cgnn_knn_batched_sorted_order.argtypes = [vp, C.POINTER(i64), i32, vp, vp]
+    lib.cgnn_pair_counts_workspace_bytes.restype = sz
+    lib.cgnn_pair_counts_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cgnn_pair_counts.argtypes = [vp, i64, vp, i64, f32, C.POINTER(f32), i32, vp, vp, sz, vp]   # edges: host memory
+    lib.cgnn_frame_errors_workspace_bytes.restype = sz
+    lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
+    lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

@@ -732,6 +732,113 @@ def knn_periodic_batched(pos: torch.Tensor, offsets, box_size: float, k: int, wa
     return senders, edge_attr, order
 
 
+def check_pair_count_edges(edges, box_size: float, who: str) -> List[float]:
+    """The radii of :func:`pair_counts` as float32 host values, or ``ValueError``: ``1 <= nb <= 256`` bins, finite,
+    ``edges[0] >= 0``, strictly ascending in float32, ``edges[nb] <= fl32(0.5 * box_size)``, ``box_size > 0``.  Callers
+    check before any device work."""
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{who}: box_size must be positive and finite, got {box_size!r}")
+    e = torch.as_tensor(edges).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    nb = e.numel() - 1
+    if not 1 <= nb <= _lib.PAIR_COUNTS_MAX_BINS:
+        raise ValueError(f"{who}: edges must hold nb + 1 radii with 1 <= nb <= {_lib.PAIR_COUNTS_MAX_BINS}, got "
+                         f"{e.numel()} values")
+    if not bool(torch.isfinite(e).all()) or float(e[0]) < 0.0 or not bool((e[1:] > e[:-1]).all()):
+        raise ValueError(f"{who}: edges must be finite, start at 0 or above and ascend strictly (in float32)")
+    if not bool(e[-1] <= box * 0.5):
+        raise ValueError(f"{who}: the largest radius {float(e[-1])} exceeds half the box, {float(box) * 0.5}")
+    return e.tolist()
+
+
+def pair_counts(pos_a: torch.Tensor, box_size: float, edges, pos_b: Optional[torch.Tensor] = None, *,
+                check_bounds: bool = False) -> torch.Tensor:
+    """Exact pair counts by separation in a periodic box (``cgnn_pair_counts``): ``int64 [nb]`` for ``pos_a [N, 3]``,
+    ``int64 [T, nb]`` for ``pos_a [T, N, 3]`` (one call per frame on the same stream, no host synchronisation between
+    them).  ``edges``: ``nb + 1`` ascending radii (host values); bin ``b`` holds the pairs with ``e2[b] <= d2 < e2[b + 1]``,
+    ``e2 = fl32(edges ** 2)`` and ``d2`` the float32 minimum-image squared distance of ``include/cgnn.h``.
+
+    ``pos_b is None`` (auto): every unordered pair of ``pos_a`` once.  Otherwise (cross) ``pos_b`` is ``[M, 3]`` (or
+    ``[T, M, 3]``) and every ordered pair ``(a, b)`` counts once; passing the same tensor twice pairs every particle
+    with itself too.  Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host
+    synchronisation, the default verifies nothing.  The counts equal the brute-force count exactly and are the same bits
+    on every run.
+
+    One box per call: batches of simulations (``offsets``) and counting across spatial shards are out of scope
+    (an owned-storage rollout goes through ``dist.assemble_frames`` first)."""
+    what = "pair_counts"
+    e = check_pair_count_edges(edges, box_size, what)
+    nb = len(e) - 1
+    pos_a = f32c(pos_a, "pos_a")
+    batched = pos_a.dim() == 3
+    if pos_a.dim() not in (2, 3) or pos_a.shape[-1] != 3 or pos_a.shape[-2] < 1:
+        raise CgnnError(f"{what}: pos_a must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos_a.shape)}")
+    if pos_b is not None:
+        pos_b = f32c(pos_b, "pos_b")
+        if pos_b.dim() != pos_a.dim() or pos_b.shape[-1] != 3 or pos_b.shape[-2] < 1 or \
+                (batched and pos_b.shape[0] != pos_a.shape[0]):
+            raise CgnnError(f"{what}: pos_b must be [M, 3] (or [T, M, 3] with pos_a's T) with M >= 1, got "
+                            f"{tuple(pos_b.shape)} for pos_a {tuple(pos_a.shape)}")
+        _same_device(pos_a, pos_b)
+    if check_bounds:
+        for name, p in (("pos_a", pos_a), ("pos_b", pos_b)):
+            if p is not None and not bool(((p >= 0) & (p <= float(box_size))).all()):
+                raise ValueError(f"{what}: {name} leaves [0, box_size]")
+    frames_a = pos_a if batched else pos_a.unsqueeze(0)
+    frames_b = None if pos_b is None else (pos_b if batched else pos_b.unsqueeze(0))
+    t, n_a = frames_a.shape[0], frames_a.shape[1]
+    n_b = 0 if frames_b is None else frames_b.shape[1]
+    lib = _lib.load()
+    edges_c = (C.c_float * (nb + 1))(*e)
+    ws_bytes = lib.cgnn_pair_counts_workspace_bytes(n_a, n_b, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos_a.device)
+    counts = torch.empty((t, nb), dtype=torch.int64, device=pos_a.device)
+    st = stream_ptr(pos_a.device)
+    with _timed(what, pos_a.device):
+        for f in range(t):
+            check(lib.cgnn_pair_counts(frames_a[f].data_ptr(), n_a, None if frames_b is None else frames_b[f].data_ptr(),
+                                       n_b, float(box_size), edges_c, nb, counts[f].data_ptr(), ws.data_ptr(), ws_bytes,
+                                       st), "cgnn_pair_counts")
+    return counts if batched else counts[0]
+
+
+def frame_errors(pred_pos: torch.Tensor, true_pos: torch.Tensor, pred_tmp: Optional[torch.Tensor],
+                 true_tmp: Optional[torch.Tensor], box_size: float) -> torch.Tensor:
+    """Per-frame mean squared errors of a rollout (``cgnn_frame_errors``): ``float64 [T, 2]`` on the device, column 0
+    the position error under the minimum image (a particle that crossed a box face is scored by its real
+    displacement, not by a box length), column 1 the temperature error (0 when both temperature arguments are
+    ``None``).  ``pred_pos`` / ``true_pos``: ``[T, N, 3]``; ``pred_tmp`` / ``true_tmp``: ``[T, N(, 1)]``.  Means as
+    ``rollout.calculate_errors`` takes them (over ``3 N`` and ``N`` values), summed in float64 in a fixed order: two
+    runs give the same bits.  All frames in one launch sequence, no host synchronisation."""
+    what = "frame_errors"
+    if not (float(box_size) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive, got {box_size!r}")
+    if (pred_tmp is None) != (true_tmp is None):
+        raise ValueError(f"{what}: give both temperature tensors or neither")
+    pred_pos, true_pos = f32c(pred_pos, "pred_pos"), f32c(true_pos, "true_pos")
+    if pred_pos.dim() != 3 or pred_pos.shape[2] != 3 or pred_pos.shape != true_pos.shape or pred_pos.numel() == 0:
+        raise CgnnError(f"{what}: positions must be two non-empty [T, N, 3] tensors, got {tuple(pred_pos.shape)} / "
+                        f"{tuple(true_pos.shape)}")
+    t, n = pred_pos.shape[0], pred_pos.shape[1]
+    if pred_tmp is not None:
+        pred_tmp, true_tmp = f32c(pred_tmp, "pred_tmp"), f32c(true_tmp, "true_tmp")
+        if pred_tmp.numel() != t * n or true_tmp.numel() != t * n:
+            raise CgnnError(f"{what}: temperatures must be [T, N(, 1)], got {tuple(pred_tmp.shape)} / "
+                            f"{tuple(true_tmp.shape)}")
+    _same_device(pred_pos, true_pos, pred_tmp, true_tmp)
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_frame_errors_workspace_bytes(t, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pred_pos.device)
+    out = torch.empty((t, 2), dtype=torch.float64, device=pred_pos.device)
+    with _timed(what, pred_pos.device):
+        check(lib.cgnn_frame_errors(pred_pos.data_ptr(), true_pos.data_ptr(), ptr(pred_tmp), ptr(true_tmp), t, n,
+                                    float(box_size), out.data_ptr(), ws.data_ptr(), ws_bytes,
+                                    stream_ptr(pred_pos.device)), "cgnn_frame_errors")
+    out[:, 0] /= 3 * n
+    out[:, 1] /= n
+    return out
+
+
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,
                     pos_noise: Optional[torch.Tensor] = None, temp_noise: Optional[torch.Tensor] = None):
     """``[W, N, 3]`` positions and ``[W, N(, 1)]`` temperatures -> ``(x [N, 3(W-1)+W], recent_pos [N, 3])``

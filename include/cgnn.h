@@ -538,6 +538,40 @@ int cgnn_knn_periodic_batched(const float* pos, const int64_t* offsets, int32_t 
 int cgnn_knn_batched_sorted_order(const void* workspace, const int64_t* offsets, int32_t num_graphs,
                                   int32_t* perm, void* stream);
 
+/* ---- judging a rollout: pair counts by separation, minimum-image frame errors -----------------------------
+ * Exact pair counts in a periodic box of side box_size (the DD / D1D2 terms of the two-point correlation function).
+ * pos_a [n_a, 3] and pos_b [n_b, 3] hold positions in [0, box_size] (a value of exactly box_size falls into the edge
+ * cell); edges (HOST memory, num_bins + 1 floats) are the radii.  For a of A and b of B, per axis
+ *     d = fl32(b - a);   half = fl32(0.5f * box_size);   d > half: d = fl32(d - box_size);  d < -half: d = fl32(d + box_size)
+ *     d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy)) + fl32(dz*dz))
+ * one float32 rounding per operation, no FMA; with e2[i] = fl32(edges[i] * edges[i]) the pair belongs to bin i iff
+ * e2[i] <= d2 < e2[i + 1] (half-open).  The expression is symmetric in a and b.
+ *   pos_b == NULL (auto; n_b is ignored): every unordered pair i < j of A once, no particle with itself; two distinct
+ *                  particles at one position have d2 = 0 and count in bin 0 exactly when edges[0] == 0.
+ *   pos_b != NULL (cross): every ordered pair (a, b) once; n_a != n_b is allowed; with pos_b == pos_a every particle
+ *                  pairs with itself as well and distinct pairs appear twice.
+ * counts (device, int64 [num_bins]) is overwritten.  Integer sums: the result does not depend on any order and equals the
+ * brute-force count exactly.  No host synchronisation, everything on `stream`.
+ * CGNN_ERR_INVALID_ARG unless 1 <= num_bins <= 256, edges finite, edges[0] >= 0, strictly ascending,
+ * edges[num_bins] <= half and box_size > 0; 2^31 or more particles in a set: CGNN_ERR_UNSUPPORTED.
+ * Workspace: a function of n_a and n_b alone (n_b = 0: auto), O(n_a + n_b), 16-byte aligned. */
+size_t cgnn_pair_counts_workspace_bytes(int64_t n_a, int64_t n_b, int32_t num_bins);
+int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, float box_size,
+                     const float* edges, int32_t num_bins, int64_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Per-frame errors of a rollout against the truth: pred_pos / true_pos [frames, n, 3], pred_tmp / true_tmp [frames, n]
+ * (both NULL: no temperatures, the second sum is 0).  out (device, double [frames, 2]):
+ *   out[f, 0] = sum over particles and axes of fold(fl32(pred - true))^2     (fold: the minimum image of the entry above)
+ *   out[f, 1] = sum over particles of fl32(pred_tmp - true_tmp)^2
+ * each difference widened to float64, squared and summed in float64 by a two-stage reduction whose additions have a
+ * fixed order (no float atomics): two runs give the same bits.  One launch sequence for all frames, no host
+ * synchronisation.  Workspace: cgnn_frame_errors_workspace_bytes(frames, n), 8-byte aligned. */
+size_t cgnn_frame_errors_workspace_bytes(int64_t frames, int64_t n);
+int cgnn_frame_errors(const float* pred_pos, const float* true_pos, const float* pred_tmp, const float* true_tmp,
+                      int64_t frames, int64_t n, float box_size, double* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes

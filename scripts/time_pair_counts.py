@@ -1,0 +1,105 @@
+"""Developer tool: ``ops.pair_counts`` (auto mode) on one frame of 1 M particles, uniform and clustered, with 20 log bins up
+to 4 mean interparticle spacings; for context the k-NN build of the same frame (``ops.knn_periodic``, k = 16) in the
+same process.  Every shape is warmed, then the two alternate; each call sits between two device events.  Prints the
+median, min and max of 7 calls in ms per frame and, for the pair counter, pair evaluations per second: the (query,
+candidate) pairs the walk evaluates, computed here from the cell occupancies (every query against every partner of the
+cells its cell walks).  Not part of the product or tests.
+    python scripts/time_pair_counts.py [--iters 7] [--inputs uniform:1000000 clustered:1000000]
+clustered:N is synthetic.make_clustered_positions(N) (half of the particles in one Gaussian halo of 0.05 box)."""
+import argparse
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cosmology_gnn_simulation_amd import ops, synthetic  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--iters", type=int, default=7)
+ap.add_argument("--neighbors", type=int, default=16)
+ap.add_argument("--bins", type=int, default=20)
+ap.add_argument("--spacings", type=float, default=4.0, help="largest radius in mean interparticle spacings")
+ap.add_argument("--inputs", nargs="+", default=["uniform:1000000", "clustered:1000000"])
+a = ap.parse_args()
+if a.iters < 7:
+    ap.error("--iters: medians of at least 7")
+dev = torch.device("cuda")
+box = 1.0
+
+
+def frame(spec):
+    kind, n = spec.split(":")
+    n = int(n)
+    if kind == "clustered":
+        return synthetic.make_clustered_positions(n, box, seed=3).to(dev)
+    if kind == "uniform":
+        return (torch.rand(n, 3, generator=torch.Generator().manual_seed(41)) * box).to(dev)
+    raise SystemExit(f"unknown input {spec!r}: uniform:N or clustered:N")
+
+
+def cells_per_axis(n, reach):
+    """The grid rule of csrc/pair_counts.hip (pc_cells_per_axis)."""
+    cap = 1
+    while cap < 256 and (cap + 1) ** 3 <= n:
+        cap += 1
+    g = math.floor(box / (reach * (1 + 1e-5) + 2e-5 * box))
+    return max(1, min(g, 256, cap))
+
+
+def pair_evaluations(pos, reach):
+    """Sum over cells of (queries in the cell) x (partners in the cells it walks): what the walk kernel evaluates."""
+    n = pos.shape[0]
+    g = cells_per_axis(n, reach)
+    c = (pos * (g / box)).floor().long().clamp_(0, g - 1)
+    occ = torch.zeros(g * g * g, dtype=torch.float64, device=pos.device)
+    occ.index_add_(0, (c[:, 0] * g + c[:, 1]) * g + c[:, 2], torch.ones(n, dtype=torch.float64, device=pos.device))
+    occ = occ.view(g, g, g)
+    if g <= 3:
+        return float(n) * float(n), g
+    near = occ
+    for dim in range(3):
+        near = near + near.roll(1, dim) + near.roll(-1, dim)
+    return float((occ * near).sum()), g
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+frames = {spec: frame(spec) for spec in a.inputs}
+print(f"{a.bins} log bins up to {a.spacings} mean spacings; k-NN build with k = {a.neighbors}; device events around each "
+      f"call, the two alternating, {a.iters} timed calls each after 2 warm-up calls", flush=True)
+for spec, pos in frames.items():
+    n = pos.shape[0]
+    reach = a.spacings * box / n ** (1.0 / 3.0)
+    edges = torch.logspace(math.log10(reach / 100.0), math.log10(reach), a.bins + 1, dtype=torch.float64)
+    calls = {"pair_counts": lambda: ops.pair_counts(pos, box, edges),
+             "knn_periodic": lambda: ops.knn_periodic(pos, box, a.neighbors, want_order=True)}
+    for fn in calls.values():
+        for _ in range(2):
+            timed(fn)
+    times = {name: [] for name in calls}
+    first = None
+    same = True
+    for _ in range(a.iters):
+        for name, fn in calls.items():
+            ms, out = timed(fn)
+            times[name].append(ms)
+            if name == "pair_counts":
+                first = out if first is None else first
+                same = same and torch.equal(out, first)
+    evals, g = pair_evaluations(pos, reach)
+    for name, t in times.items():
+        med = statistics.median(t)
+        rate = f"   {evals / (med * 1e-3):.3e} pair evaluations / s ({evals:.3e} per frame, {g} cells per axis)" \
+            if name == "pair_counts" else ""
+        print(f"  {spec:>18s}  {name:>12s}: median {med:9.3f} ms   min {min(t):9.3f}   max {max(t):9.3f}{rate}", flush=True)
+    print(f"  {spec:>18s}  pairs counted: {int(first.sum())}; same counts on every call: {same}", flush=True)
