@@ -2065,12 +2065,11 @@ def sharded_unrolled_training_bytes(n_owned: int, n_ghost: int, num_particles: i
     frames of all N particles, 16 bytes per particle and frame.  ``checkpoint="steps"``: one step's activations, the
     scratch, the W true frames and S small records (:func:`shard_record_bytes`, which holds a step's predicted frame)."""
     training.check_checkpoint(checkpoint, "sharded_unrolled_training_bytes")
-    n, ne, S = int(n_owned), int(n_owned) * int(num_neighbors), int(steps)
-    per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
-    scratch = (2 * num_hidden_layers + 3) * n * hidden
-    if edge_messages:
-        per_step += rounds * ne * latent + rounds * (n + int(n_ghost)) * latent + 3 * int(n_ghost)
-        scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    n, S = int(n_owned), int(steps)
+    per_step, scratch = training._activation_floats(n, n * int(num_neighbors), window, latent, hidden, num_hidden_layers,
+                                                    rounds, edge_messages)
+    if edge_messages:       # the local node table of every round, with its ghost rows, and the ghosts' positions
+        per_step += rounds * (n + int(n_ghost)) * latent + 3 * int(n_ghost)
     if checkpoint == "steps":
         return 4 * (per_step + scratch + int(window) * int(num_particles) * 4) + \
             S * shard_record_bytes(n, n_ghost, num_particles, num_neighbors)
@@ -2090,26 +2089,61 @@ def _step_capacity(sh: Shard, world: int) -> int:
     return max(counts)
 
 
-class _ShardedCheckpointedUnroll:
-    """The steps of one ``sharded_unrolled_loss(checkpoint="steps")`` call on one rank: :meth:`step` is one step of the
-    plain loop behind the shard build -- the samples of the owned (and ghost) rows, :class:`ShardedTraining` with its halo
-    exchanges, :func:`sharded_training_loss` with its all-reduces, the integration of the owned rows -- for the first run
-    of a checkpointed step (no autograd), its recomputation on the kept shard, and the last step.  Whatever a rank holds,
-    a step issues the same collectives in the same order: a rank that owns nothing runs it on empty blocks."""
+class _ShardedUnroll(training._Unroll):
+    """``training._Unroll`` on one rank of :func:`sharded_unrolled_loss`: the same loop and checkpoint Function, with the
+    step of a rank.  :meth:`plan` builds the step's shard; :meth:`step` is the step behind the shard build -- the samples
+    of the owned (and ghost) rows, :class:`ShardedTraining` with its halo exchanges, :func:`sharded_training_loss` with
+    its all-reduces, the integration of the owned rows -- written once for the plain step, the first run of a checkpointed
+    step (no autograd), its recomputation on the kept shard, and the last step; :meth:`publish` gathers the rows into the
+    next frame.  Whatever a rank holds, a step issues the same collectives in the same order: a rank that owns nothing
+    runs it on empty blocks.  ``sample0(rows, want, targets=True)`` samples rows of the true window with step 0's noise."""
 
-    def __init__(self, model, cfg, w: int, n: int, k: int, edge: bool, group, distributed: bool, loss_weights, sample0):
-        self.model, self.cfg, self.w, self.n, self.k, self.edge = model, cfg, w, n, k, edge
-        self.group, self.distributed, self.loss_weights, self.sample0 = group, distributed, loss_weights, sample0
-        self.params = list(model.parameters())
+    def __init__(self, model, cfg, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0, group, knn_grid: str,
+                 min_image: bool, decomposition: str):
+        super().__init__(model, cfg, w, n, k, loss_weights, checkpoint, sample0, knn_grid, min_image)
+        self.group, self.decomposition, self.distributed = group, decomposition, _group_up()
+        self.world, self.rank = _world_of(group)
 
-    def step(self, rec, tgt_p, tgt_t, frames, integrate: bool):
-        """-> (this rank's weighted loss term, rows_pos | None, rows_temp | None, block | None); fills ``rec.value`` and
-        ``rec.terms`` (the global figures).  ``frames``: the W whole position frames, then the W temperature frames."""
+    def plan(self, rec, pos_frames, tmp_frames, steps: int) -> None:
+        """The step's :class:`Shard` and send capacity into ``rec``, from the wrapped last frame of all particles; before
+        step 0 runs, the memory guard, agreed by all ranks."""
+        cfg, model, s = self.cfg, self.model, rec.s
+        with torch.no_grad():
+            if s == 0:
+                recent_all = self.sample0(None, ("recent_pos",), targets=False)["recent_pos"]
+            else:
+                recent_all = ops.training_sample(torch.stack([f.detach() for f in pos_frames[-2:]]),
+                                                 torch.stack([f.detach() for f in tmp_frames[-2:]]), cfg.meta, cfg.dt,
+                                                 cfg.box, 0.0, 0, 0, want=("recent_pos",), stats=cfg.stats)["recent_pos"]
+            if not bool(torch.isfinite(recent_all).all()):        # the neighbour search must never see a NaN position
+                raise CgnnError(f"sharded_unrolled_loss: the frame before step {s} holds non-finite positions (rows that "
+                                f"were never published, or a diverged model)")
+            sh = build_shard(recent_all, cfg.box, self.k, self.world, self.rank, decomposition=self.decomposition,
+                             knn_grid=self.knn_grid, min_image_edge_attr=self.min_image, row_order="spatial")
+            sh = exchange_requests(sh, self.group) if self.distributed else finish_shard(sh, sh.want_global)
+            rec.shard, rec.cap = sh, _step_capacity(sh, self.world)
+        sh._g2l = sh._owner = None      # the whole-box maps have served (send plan, capacity): not part of the record
+        if s == 0:      # one all-reduce (max) of a flag
+            need = sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, self.n, self.k, self.w, model._latent_size,
+                                                   model._mlp_hidden_size, model._mlp_num_hidden_layers,
+                                                   len(model.processor), steps, self.edge, self.checkpoint)
+            free = training.free_device_bytes(recent_all.device)
+            flag = _all_reduce_max_(torch.tensor([1.0 if need > free else 0.0], device=recent_all.device), self.group)
+            if float(flag[0]) > 0.0:
+                raise CgnnError(f"sharded_unrolled_loss: a rank lacks device memory for the activations of {steps} steps "
+                                f"under checkpoint={self.checkpoint!r} (rank {self.rank}: about {need / 2**30:.2f} GiB for {sh.n_owned} owned and {sh.n_ghost} ghost "
+                                f"rows of {self.n} particles, {self.k} neighbours, latent {model._latent_size}, "
+                                f"{len(model.processor)} rounds; {free / 2**30:.2f} GiB are free)")
+
+    def step(self, rec, tgt_p, tgt_t, frames, kept: bool = False, integrate: bool = True):
+        """-> (this rank's weighted loss term, rows_pos | None, rows_temp | None, block | None) on ``rec.shard``, kept or
+        not; fills ``rec.value`` and ``rec.terms`` (the global figures).  ``frames``: the W whole position frames, then
+        the W temperature frames."""
         cfg, w, n, k, sh = self.cfg, self.w, self.n, self.k, rec.shard
         grad = torch.is_grad_enabled()
         own, ghosts = sh.owned_global, sh.ghost_global
         want = ("x", "recent_pos", "y_acc", "y_temp_rate")
-        if rec.s == 0:      # the counter-based noise again: the same (seed, draw), the same sample
+        if rec.s == 0:      # in a recomputation the counter-based noise again: the same (seed, draw), the same sample
             s0 = self.sample0(own, want)
             x, recent, y_acc, y_tr = (s0[name] for name in want)
         else:
@@ -2140,44 +2174,14 @@ class _ShardedCheckpointedUnroll:
                                                                               *(f.detach() for f in frames_in))
         return rec.weight * loss_s, rows_p, rows_t, block
 
-
-class _ShardedCheckpointedStep(torch.autograd.Function):
-    """``training._CheckpointedStep`` on one rank: ``(this rank's weighted loss term, rows_pos, rows_temp, block) =
-    step(W whole position frames, W temperature frames; parameters)`` on the step's shard.  The backward runs the step
-    again on the kept shard with autograd (halo exchanges and loss all-reduces included) and differentiates it at once
-    (reverse halo exchanges, the all-reduce of the parameter gradients).  The publish link stays outside: the frame is
-    known, and its backward hands this Function the gradient of the rows."""
-
-    @staticmethod
-    def forward(ctx, unroll: _ShardedCheckpointedUnroll, rec, tgt_p, tgt_t, *tensors):
-        frames = tensors[:2 * unroll.w]
-        loss_c, rows_p, rows_t, block = unroll.step(rec, tgt_p, tgt_t, frames, integrate=True)
-        ctx.unroll, ctx.rec = unroll, rec
-        ctx.save_for_backward(tgt_p, tgt_t, *frames)
-        ctx.mark_non_differentiable(*((block,) if rec.live else (rows_p, rows_t, block)))
-        ctx.set_materialize_grads(False)
-        return loss_c, rows_p, rows_t, block
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_loss, d_rows_p, d_rows_t, _d_block):
-        unroll, rec = ctx.unroll, ctx.rec
-        tgt_p, tgt_t, *frames = ctx.saved_tensors
-        n_frames = len(frames)
-        link = rec.live and (d_rows_p is not None or d_rows_t is not None)
-        if d_loss is None and not link:     # no rank gets here: every step's loss term is part of the loss
-            return (None,) * (4 + n_frames + len(unroll.params))
-        needs = ctx.needs_input_grad[4:4 + n_frames]
-        with torch.enable_grad():
-            ins = [f.detach().requires_grad_(need) for f, need in zip(frames, needs)]
-            loss_c, rows_p, rows_t, _ = unroll.step(rec, tgt_p, tgt_t, ins, integrate=link)
-            outs = [(o, g) for o, g in ((loss_c, d_loss), (rows_p, d_rows_p), (rows_t, d_rows_t))
-                    if g is not None and o is not None and o.requires_grad]
-            wrt = [f for f, need in zip(ins, needs) if need] + [q for q in unroll.params if q.requires_grad]
-            grads = iter(torch.autograd.grad([o for o, _ in outs], wrt, [g for _, g in outs], allow_unused=True))
-        d_frames = [next(grads) if need else None for need in needs]
-        d_params = [next(grads) if q.requires_grad else None for q in unroll.params]
-        return (None, None, None, None, *d_frames, *d_params)
+    def publish(self, rec, rows_p, rows_t, block):
+        """One all-gather of the ranks' blocks into the next frame of all particles, outside the checkpoint Function: the
+        frame is gathered once, and its backward hands the step the gradient of the rows it integrated."""
+        link = (rows_p, rows_t, block, rec.shard.owned_global, self.n, self.group, self.distributed)
+        if rec.live:
+            return _PublishLink.apply(*link)
+        with torch.no_grad():
+            return _PublishLink.apply(*link)
 
 
 def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tensor,
@@ -2219,34 +2223,24 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
     owned rows again; the published frame is known and is not gathered again, its backward stays where it is.  Every
     rank issues the same collectives in the same order whatever it holds: a rank that owns nothing recomputes with empty
     blocks.  Frames, ``value`` and ``step_losses`` are those of ``"none"`` bit for bit."""
-    from . import data_utils
     w, n, S, weights = training._unroll_arguments(model, position_seq, temperature_seq, target_positions,
                                                   target_temperatures, step_weights, backprop_steps, num_neighbors,
                                                   knn_grid, min_image_edge_attr, checkpoint)
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"sharded_unrolled_loss: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
-    world, rank = _world_of(group)
+    world, _ = _world_of(group)
     noisy = float(noise_std) != 0.0
     if noisy and noise_seed is None and world > 1:
         raise ValueError("sharded_unrolled_loss: noise needs an explicit noise_seed in a world above one "
                          "(torch.initial_seed() differs between ranks)")
-    k = int(num_neighbors)
-    distributed = _group_up()
-    if device is None:
-        device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
-    device = torch.device(device)
-    edge = getattr(model, "message_source", "x_j") == "edge"
-    tmp_in = temperature_seq.reshape(w, n)
-    tgt_t_in = target_temperatures.reshape(S, n)
-    if distributed:
+    device = training._device_of(position_seq, device)
+    if _group_up():
+        tmp_in, tgt_t_in = temperature_seq.reshape(w, n), target_temperatures.reshape(S, n)
         check_same_data(torch.cat([position_seq, target_positions.to(position_seq.device)]),
                         torch.cat([tmp_in, tgt_t_in.to(tmp_in.device)]), device, group)
     cfg = training._LinkConfig(metadata, dt, box_size, n, device)
-    pos_w = _lib.f32c(position_seq.to(device), "position_seq")
-    tmp_w = _lib.f32c(tmp_in.to(device), "temperature_seq")
-    tgt_p = _lib.f32c(target_positions.to(device), "target_positions")
-    tgt_t = _lib.f32c(tgt_t_in.to(device), "target_temperatures")
-    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
+    pos_w, tmp_w, tgt_p, tgt_t = training._device_window(position_seq, temperature_seq, target_positions,
+                                                         target_temperatures, device)
     seed = (torch.initial_seed() if noise_seed is None else int(noise_seed)) % 2 ** 64
     std = float(noise_std)
 
@@ -2254,111 +2248,9 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
         return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, std, seed, noise_draw,
                                    tgt_p[0] if targets else None, tgt_t[0] if targets else None, rows, want,
                                    stats=cfg.stats)
-
-    pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
-    tgt_p_s, tgt_t_s = tgt_p, tgt_t
-    if noisy:       # replicated, like the frames: the noisy frames later windows read, and the shift of every later target
-        nz = sample0(None, ("pos_noise", "temp_noise"), targets=False)
-        pos_frames = list((pos_w + nz["pos_noise"].permute(1, 0, 2)).unbind(0))
-        tmp_frames = list((tmp_w + nz["temp_noise"].t()).unbind(0))
-        if S > 1:
-            tgt_p_s = tgt_p + nz["pos_noise"][:, -1]
-            tgt_t_s = tgt_t + nz["temp_noise"][:, -1]
-        del nz
-    sample_want = ("x", "recent_pos", "y_acc", "y_temp_rate")
-    unroll, params = None, list(model.parameters())
-    if checkpoint == "steps" and S > 1 and any(q.requires_grad for q in params):
-        unroll = _ShardedCheckpointedUnroll(model, cfg, w, n, k, edge, group, distributed,
-                                            (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), sample0)
-    total, value = None, None
-    step_losses, out_p, out_t = [], [], []
-    for s in range(S):
-        with torch.no_grad():
-            if s == 0:
-                recent_all = sample0(None, ("recent_pos",), targets=False)["recent_pos"]
-            else:
-                recent_all = ops.training_sample(torch.stack([f.detach() for f in pos_frames[-2:]]),
-                                                 torch.stack([f.detach() for f in tmp_frames[-2:]]), cfg.meta, cfg.dt,
-                                                 cfg.box, 0.0, 0, 0, want=("recent_pos",), stats=cfg.stats)["recent_pos"]
-            if not bool(torch.isfinite(recent_all).all()):        # the neighbour search must never see a NaN position
-                raise CgnnError(f"sharded_unrolled_loss: the frame before step {s} holds non-finite positions (rows that "
-                                f"were never published, or a diverged model)")
-            sh = build_shard(recent_all, cfg.box, k, world, rank, decomposition=decomposition, knn_grid=knn_grid,
-                             min_image_edge_attr=min_image_edge_attr, row_order="spatial")
-            sh = exchange_requests(sh, group) if distributed else finish_shard(sh, sh.want_global)
-            cap = _step_capacity(sh, world)
-        if s == 0:      # the memory guard, agreed by all ranks: one all-reduce (max) of a flag
-            need = sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, n, k, w, model._latent_size,
-                                                   model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                                   len(model.processor), S, edge, checkpoint)
-            free = training.free_device_bytes(device)
-            flag = _all_reduce_max_(torch.tensor([1.0 if need > free else 0.0], device=device), group)
-            if float(flag[0]) > 0.0:
-                raise CgnnError(f"sharded_unrolled_loss: a rank lacks device memory for the activations of {S} steps "
-                                f"under checkpoint={checkpoint!r} (rank {rank}: about {need / 2**30:.2f} GiB for {sh.n_owned} owned and {sh.n_ghost} ghost "
-                                f"rows of {n} particles, {k} neighbours, latent {model._latent_size}, "
-                                f"{len(model.processor)} rounds; {free / 2**30:.2f} GiB are free)")
-        own, ghosts = sh.owned_global, sh.ghost_global
-        window = (*pos_frames[-w:], *tmp_frames[-w:])
-        if unroll is not None:
-            # link s feeds step s + 1 and carries gradient when it is one of the last `links`
-            rec = training._StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
-            sh._g2l = sh._owner = None      # the whole-box maps have served (send plan, capacity): not part of the record
-            rec.shard, rec.cap = sh, cap
-            if s < S - 1:
-                loss_c, rows_p, rows_t, block = _ShardedCheckpointedStep.apply(unroll, rec, tgt_p_s[s], tgt_t_s[s], *window,
-                                                                               *params)
-            else:       # the plain path: its activations are the ones the backward needs first
-                loss_c, rows_p, rows_t, block = unroll.step(rec, tgt_p_s[s], tgt_t_s[s], window, integrate=True)
-            total = loss_c if total is None else total + loss_c
-            value = weights[s] * rec.value if value is None else value + weights[s] * rec.value
-            step_losses.append(rec.terms)
-            if rec.live:
-                new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
-            else:
-                with torch.no_grad():
-                    new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
-            out_p.append(new_p.detach())
-            out_t.append(new_t.detach())
-            pos_frames.append(new_p)
-            tmp_frames.append(new_t)
-            continue
-        if s == 0:
-            s0 = sample0(own, sample_want)
-            x, recent, y_acc, y_tr = (s0[name] for name in sample_want)
-        else:
-            x, recent, y_acc, y_tr = training._SampleRowsLink.apply(cfg, own, sample_want, tgt_p_s[s], tgt_t_s[s], *window)
-        runner = ShardedTraining(model, sh, None if distributed else _LocalHalo(), group)
-        if edge:        # the shard's edge features as a function of the local rows [owned | ghosts]
-            if s == 0:
-                recent_g = sample0(ghosts, ("recent_pos",), targets=False)["recent_pos"]
-            else:
-                recent_g, = training._SampleRowsLink.apply(cfg, ghosts, ("recent_pos",), None, None, *window)
-            edge_attr = training._EdgeAttrRowsLink.apply(torch.cat([recent, recent_g]), sh.edge_attr, sh.src_local, k,
-                                                         sh.n_owned, lambda runner=runner: runner._csr)
-            pred = runner(x, edge_attr)
-        else:
-            pred = runner(x)
-        acc, rate = pred["acceleration"], pred["temp_rate"]
-        loss_s, value_s, terms = sharded_training_loss(pred, y_acc, y_tr.reshape(-1, 1), n, cfg.dt, acc_loss_weight,
-                                                       temp_rate_loss_weight, momentum_loss_weight, group, terms=True)
-        total = weights[s] * loss_s if total is None else total + weights[s] * loss_s
-        value = weights[s] * value_s if value is None else value + weights[s] * value_s
-        step_losses.append(terms.to(torch.float32))
-        # the next frame; link s feeds step s + 1 and carries gradient when it is one of the last `links`
-        live = s < S - 1 and s >= S - 1 - links
-        frames_in = (pos_frames[-2], pos_frames[-1], tmp_frames[-1])
-        if live:
-            rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, cap, acc, rate, *frames_in)
-            new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
-        else:
-            with torch.no_grad():
-                rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, cap, acc.detach(), rate.detach(),
-                                                                          *(f.detach() for f in frames_in))
-                new_p, new_t = _PublishLink.apply(rows_p, rows_t, block, own, n, group, distributed)
-        out_p.append(new_p.detach())
-        out_t.append(new_t.detach())
-        pos_frames.append(new_p)
-        tmp_frames.append(new_t)
-    frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
-    return training.UnrolledLoss(total, torch.stack(step_losses), frames, None, value)
+    unroll = _ShardedUnroll(model, cfg, w, n, int(num_neighbors), (acc_loss_weight, temp_rate_loss_weight,
+                            momentum_loss_weight), checkpoint, sample0, group, knn_grid, min_image_edge_attr, decomposition)
+    # the noise is replicated, like the frames, and not kept beyond the window
+    window = training._noisy_window(pos_w, tmp_w, tgt_p, tgt_t,
+                                    sample0(None, ("pos_noise", "temp_noise"), targets=False) if noisy else None)
+    return unroll.run(*window, weights, backprop_steps)

@@ -599,6 +599,15 @@ class _SampleLink(torch.autograd.Function):
                 *(d_temp[t] if needs[w + t] else None for t in range(w)))
 
 
+def _edge_attr_grad(ctx, d_edge_attr):
+    """The backward the edge-feature Functions share: d ``recent`` from d ``edge_attr`` (``cgnn_edge_attr_backward``) on
+    the ``(edge_attr, senders)`` the forward saved with ``ctx.k`` / ``ctx.n``; ``None`` when no gradient arrived."""
+    if d_edge_attr is None:
+        return None
+    edge_attr, senders = ctx.saved_tensors
+    return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, ops.SenderCsr(senders, None, ctx.n))
+
+
 class _KnnEdgeAttr(torch.autograd.Function):
     """``(edge_attr, senders) = ops.knn_periodic(recent)``: the graph build, differentiable in its edge features
     (``cgnn_edge_attr_backward``; the senders are discrete).  The sender-major edge CSR is built in the backward, so a
@@ -617,11 +626,7 @@ class _KnnEdgeAttr(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_edge_attr, _d_senders):
-        if d_edge_attr is None:
-            return None, None, None, None, None
-        edge_attr, senders = ctx.saved_tensors
-        by_sender = ops.SenderCsr(senders, None, ctx.n)
-        return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender), None, None, None, None
+        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 4
 
 
 class _KnnEdgeAttrBatched(torch.autograd.Function):
@@ -641,11 +646,7 @@ class _KnnEdgeAttrBatched(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_edge_attr, _d_senders):
-        if d_edge_attr is None:
-            return (None,) * 6
-        edge_attr, senders = ctx.saved_tensors
-        by_sender = ops.SenderCsr(senders, None, ctx.n)
-        return (ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender),) + (None,) * 5
+        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 5
 
 
 def _spread3(v: torch.Tensor) -> torch.Tensor:
@@ -852,6 +853,18 @@ def step_record_bytes(num_particles: int, num_neighbors: int, edge_messages: boo
     return 16 * n + 4 * ne + 4 * n + (16 * ne if edge_messages else 0)
 
 
+def _activation_floats(n: int, ne: int, window: int, latent: int, hidden: int, num_hidden_layers: int, rounds: int,
+                       edge_messages: bool):
+    """-> (floats one step keeps over ``n`` node rows and ``ne`` edges, floats of the backward scratch): the part of
+    :func:`unrolled_training_bytes` that ``dist.sharded_unrolled_training_bytes`` counts the same way."""
+    per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
+    scratch = (2 * num_hidden_layers + 3) * n * hidden
+    if edge_messages:
+        per_step += rounds * ne * latent
+        scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    return per_step, scratch
+
+
 def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
                             num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False,
                             checkpoint: str = "none") -> int:
@@ -861,12 +874,9 @@ def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int,
     scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn.
     ``checkpoint="steps"``: one step's activations, the scratch, and S small records (:func:`step_record_bytes`)."""
     check_checkpoint(checkpoint, "unrolled_training_bytes")
-    n, ne = int(num_particles), int(num_particles) * int(num_neighbors)
-    per_step = n * (4 * window - 3) + (2 * rounds + 1) * n * latent + 4 * ne + 8 * n
-    scratch = (2 * num_hidden_layers + 3) * n * hidden
-    if edge_messages:
-        per_step += rounds * ne * latent
-        scratch += (2 * num_hidden_layers + 3) * ne * hidden
+    n = int(num_particles)
+    per_step, scratch = _activation_floats(n, n * int(num_neighbors), window, latent, hidden, num_hidden_layers, rounds,
+                                           edge_messages)
     if checkpoint == "steps":
         return 4 * (per_step + scratch) + int(steps) * step_record_bytes(n, num_neighbors, edge_messages)
     return 4 * (int(steps) * per_step + scratch)
@@ -906,15 +916,13 @@ class _KeptEdgeAttr(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_edge_attr):
-        if d_edge_attr is None:
-            return None, None, None, None
-        edge_attr, senders = ctx.saved_tensors
-        by_sender = ops.SenderCsr(senders, None, ctx.n)
-        return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, by_sender), None, None, None
+        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 3
 
 
 class _StepRecord:
-    """What a checkpointed step keeps (:func:`step_record_bytes`; the frames are the tensors autograd holds anyway)."""
+    """One step of :class:`_Unroll`: its number, weight and whether its outgoing link carries gradient; what the step
+    reports (``terms``, ``graph``, ``value``); and under ``checkpoint="steps"`` what a checkpointed step keeps
+    (:func:`step_record_bytes`; the frames are the tensors autograd holds anyway)."""
 
     def __init__(self, s: int, weight: float, live: bool):
         self.s, self.weight, self.live = s, weight, live
@@ -922,32 +930,45 @@ class _StepRecord:
         self.shard = self.cap = self.value = None       # dist.sharded_unrolled_loss: the step's Shard and send capacity
 
 
-class _CheckpointedUnroll:
-    """The steps of one ``unrolled_loss(checkpoint="steps")`` call: :meth:`step` is one step of the plain loop, written
-    once for its three uses -- the first run of a checkpointed step (no autograd, it fills the record), its
-    recomputation (autograd, the kept graph) and the last step (autograd, a search: the plain path)."""
+class _Unroll:
+    """The steps of one :func:`unrolled_loss` / :func:`unrolled_batch_loss` call over the ``n`` rows of ``cfg``, in either
+    checkpoint mode.  :meth:`run` is the loop over the steps.  :meth:`step` is the step, written once for its four uses:
+    the plain step (``model(graph)``, a search), and under ``checkpoint="steps"`` the first run of a checkpointed step (no
+    autograd, it fills the record), its recomputation (autograd, the kept graph) and the last step (autograd, a search);
+    the three of ``"steps"`` run the training forward whether autograd records or not, so that they are the same kernels.
+    ``dist._ShardedUnroll`` is the same loop over the rows of a rank: it overrides :meth:`plan`, :meth:`step` and
+    :meth:`publish`.  ``sample0(want)`` makes step 0's sample of the true window, as ``ops.training_sample`` returns it."""
 
-    def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, edge: bool, knn_grid: str, min_image: bool,
-                 loss_weights, keep_graphs: bool):
-        self.model, self.cfg, self.w, self.n, self.k, self.edge = model, cfg, w, n, k, edge
-        self.knn_grid, self.min_image, self.loss_weights, self.keep_graphs = knn_grid, min_image, loss_weights, keep_graphs
+    def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0,
+                 knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False):
+        self.model, self.cfg, self.w, self.n, self.k = model, cfg, w, n, k
+        self.loss_weights, self.checkpoint, self.sample0 = loss_weights, checkpoint, sample0
+        self.knn_grid, self.min_image, self.keep_graphs = knn_grid, min_image, keep_graphs
+        self.edge = getattr(model, "message_source", "x_j") == "edge"
         self.params = list(model.parameters())
-        self.receivers = cfg.ids.repeat_interleave(k)
-        self.first = None       # step 0's sample from the true window again: first(want) -> ops.training_sample's dict
-        self.s0 = None          # step 0's sample of the first run
+        self.checkpointed = False       # run(): "steps" with more than one step and a parameter to differentiate
+        self.receivers = None
+        self.s0 = None          # step 0's sample of the first run; its recomputation draws again through sample0
 
-    def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool, integrate: bool):
+    def plan(self, rec: _StepRecord, pos_frames, tmp_frames, steps: int) -> None:
+        """What a step needs settled before it runs, without autograd: nothing on one GPU."""
+
+    def publish(self, rec: _StepRecord, new_p, new_t):
+        """What :meth:`step` returned behind its loss term -> the next frame of all rows: on one GPU they are it."""
+        return new_p, new_t
+
+    def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool = False, integrate: bool = True):
         """-> (weighted loss term, new_pos | None, new_temp | None).  ``frames``: the W position frames, then the W
-        temperature frames.  ``kept``: build the graph from ``rec``'s lists; else search and, without autograd, fill
-        ``rec``."""
+        temperature frames.  ``kept``: build the graph from ``rec``'s lists; else search and, in the first run of a
+        checkpointed step, fill ``rec``."""
         from . import losses
         cfg, w, n, k, edge = self.cfg, self.w, self.n, self.k, self.edge
         grad = torch.is_grad_enabled()
         if rec.s == 0:
             if self.s0 is not None:
                 s0, self.s0 = self.s0, None
-            else:
-                s0 = self.first(["x", "recent_pos", "y_acc", "y_temp_rate"])
+            else:       # the same (seed, draw), the same sample
+                s0 = self.sample0(["x", "recent_pos", "y_acc", "y_temp_rate"])
             x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
         else:
             x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p, tgt_t, *frames)
@@ -959,12 +980,16 @@ class _CheckpointedUnroll:
                 edge_attr = recent.new_zeros((1, 4)).expand(n * k, 4)
         else:
             edge_attr, senders, order = cfg.graph_lists(recent, edge, k, self.knn_grid, self.min_image)
-            if not grad:
+            if self.checkpointed and not grad:
                 rec.senders, rec.order = senders, order
                 rec.edge_attr = edge_attr if edge else None
+        if self.receivers is None:
+            self.receivers = cfg.ids.repeat_interleave(k)
         edge_index = torch.stack([senders.to(torch.int64), self.receivers], dim=0)
         graph = cfg.graph(x, edge_index, edge_attr, y_acc, y_tr, recent.detach(), order, k)
-        pred = self.model._forward_train(graph)         # the training forward with or without autograd: the same kernels
+        # "steps": the training forward with or without autograd.  "none": the model's own choice (inference kernels
+        # when nothing is differentiated)
+        pred = self.model._forward_train(graph) if self.checkpointed else self.model(graph)
         acc, rate = pred["acceleration"], pred["temp_rate"]
         mse = torch.nn.functional.mse_loss
         terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
@@ -972,9 +997,10 @@ class _CheckpointedUnroll:
         loss_s = self.loss_weights[0] * terms[0] + self.loss_weights[1] * terms[1] + terms[2]
         if not kept:
             rec.terms = torch.stack([t.detach() for t in terms])
-            if self.keep_graphs:        # detached tensors: the last step's graph does not hold its autograd graph
-                rec.graph = graph if not grad else cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(),
-                                                             y_tr.detach(), recent.detach(), order, k)
+            if self.keep_graphs:        # "steps": detached tensors, the last step's graph does not hold its autograd graph
+                rec.graph = graph if not (self.checkpointed and grad) else \
+                    cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach(), recent.detach(),
+                              order, k)
         new_p = new_t = None
         if integrate:
             p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
@@ -986,65 +1012,71 @@ class _CheckpointedUnroll:
                                                         t1.detach())
         return rec.weight * loss_s, new_p, new_t
 
-    def run(self, s0, pos_frames, tmp_frames, tgt_p, tgt_t, weights, links: int) -> UnrolledLoss:
+    def run(self, pos_frames, tmp_frames, tgt_p, tgt_t, weights, backprop_steps, s0=None) -> UnrolledLoss:
+        """The S steps from the (noisy) window ``pos_frames`` / ``tmp_frames`` (W frames each; the predicted ones are
+        appended) against the (shifted) targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``."""
         w, S = self.w, len(weights)
+        links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
+        self.checkpointed = self.checkpoint == "steps" and S > 1 and any(q.requires_grad for q in self.params)
         self.s0 = s0
-        total = None
-        records, out_p, out_t = [], [], []
+        total = value = None
+        terms, graphs, out_p, out_t = [], [], [], []
         for s in range(S):
-            last = s == S - 1
             # link s feeds step s + 1 and carries gradient when it is one of the last `links`
             rec = _StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
+            self.plan(rec, pos_frames, tmp_frames, S)
             frames = (*pos_frames[-w:], *tmp_frames[-w:])
-            if last:        # the plain path: its activations are the ones the backward needs first
-                loss_c, new_p, new_t = self.step(rec, tgt_p[s], tgt_t[s], frames, kept=False, integrate=True)
-            else:
-                loss_c, new_p, new_t = _CheckpointedStep.apply(self, rec, tgt_p[s], tgt_t[s], *frames, *self.params)
+            if self.checkpointed and s < S - 1:
+                loss_c, *made = _CheckpointedStep.apply(self, rec, tgt_p[s], tgt_t[s], *frames, *self.params)
+            else:       # the last step of "steps" too: its activations are the ones the backward needs first
+                loss_c, *made = self.step(rec, tgt_p[s], tgt_t[s], frames)
             total = loss_c if total is None else total + loss_c
-            records.append(rec)
+            if rec.value is not None:
+                value = weights[s] * rec.value if value is None else value + weights[s] * rec.value
+            terms.append(rec.terms)
+            graphs.append(rec.graph)
+            rec.graph = None
+            new_p, new_t = self.publish(rec, *made)
             out_p.append(new_p.detach())
             out_t.append(new_t.detach())
             pos_frames.append(new_p)
             tmp_frames.append(new_t)
         frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
-        graphs = [rec.graph for rec in records] if self.keep_graphs else None
-        for rec in records:
-            rec.graph = None
-        return UnrolledLoss(total, torch.stack([rec.terms for rec in records]), frames, graphs)
+        return UnrolledLoss(total, torch.stack(terms), frames, graphs if self.keep_graphs else None, value)
 
 
 class _CheckpointedStep(torch.autograd.Function):
-    """One checkpointed step: ``(weighted loss term, new_pos, new_temp) = step(W position frames, W temperature frames;
-    parameters)`` with the step's targets as constants.  The forward runs the step without autograd and keeps the record;
-    the backward runs it again with autograd from detached copies of the frames, on the kept graph, takes
-    ``torch.autograd.grad`` of the outputs a gradient arrived for, and drops the rebuilt step.  Autograd sums a frame's
-    gradient over the steps that read it, and a parameter's over the steps, as it does on the plain path."""
+    """One checkpointed step of an :class:`_Unroll`: ``(weighted loss term, new_pos, new_temp, *extras) = step(W position
+    frames, W temperature frames; parameters)`` with the step's targets as constants.  ``new_pos`` / ``new_temp`` are what
+    the step's link hands on (the frame on one GPU, the rows a rank integrated over shards); ``extras`` is whatever the
+    step returns behind them and is never differentiable (a rank's packed block).  The forward runs the step without
+    autograd and keeps the record; the backward runs it again with autograd from detached copies of the frames, on the
+    kept graph, takes ``torch.autograd.grad`` of the outputs a gradient arrived for, and drops the rebuilt step.  Autograd
+    sums a frame's gradient over the steps that read it, and a parameter's over the steps, as it does on the plain path."""
 
     @staticmethod
-    def forward(ctx, unroll: "_CheckpointedUnroll", rec: _StepRecord, tgt_p, tgt_t, *tensors):
+    def forward(ctx, unroll: _Unroll, rec: _StepRecord, tgt_p, tgt_t, *tensors):
         frames = tensors[:2 * unroll.w]
-        loss_c, new_p, new_t = unroll.step(rec, tgt_p, tgt_t, frames, kept=False, integrate=True)
+        loss_c, new_p, new_t, *extras = unroll.step(rec, tgt_p, tgt_t, frames)
         ctx.unroll, ctx.rec = unroll, rec
         ctx.save_for_backward(tgt_p, tgt_t, *frames)
-        if not rec.live:
-            ctx.mark_non_differentiable(new_p, new_t)
+        ctx.mark_non_differentiable(*(() if rec.live else (new_p, new_t)), *extras)
         ctx.set_materialize_grads(False)
-        return loss_c, new_p, new_t
+        return (loss_c, new_p, new_t, *extras)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, d_loss, d_new_p, d_new_t):
+    def backward(ctx, d_loss, d_new_p, d_new_t, *_d_extras):
         unroll, rec = ctx.unroll, ctx.rec
         tgt_p, tgt_t, *frames = ctx.saved_tensors
         n_frames = len(frames)
-        nothing = (None,) * (4 + n_frames + len(unroll.params))
         link = rec.live and (d_new_p is not None or d_new_t is not None)
-        if d_loss is None and not link:
-            return nothing
+        if d_loss is None and not link:     # over shards no rank gets here: every step's loss term is part of the loss
+            return (None,) * (4 + n_frames + len(unroll.params))
         needs = ctx.needs_input_grad[4:4 + n_frames]
         with torch.enable_grad():
             ins = [f.detach().requires_grad_(need) for f, need in zip(frames, needs)]
-            loss_c, new_p, new_t = unroll.step(rec, tgt_p, tgt_t, ins, kept=True, integrate=link)
+            loss_c, new_p, new_t, *_ = unroll.step(rec, tgt_p, tgt_t, ins, kept=True, integrate=link)
             outs = [(o, g) for o, g in ((loss_c, d_loss), (new_p, d_new_p), (new_t, d_new_t))
                     if g is not None and o is not None and o.requires_grad]
             wrt = [f for f, need in zip(ins, needs) if need] + [q for q in unroll.params if q.requires_grad]
@@ -1149,30 +1181,24 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     every step (``(4 W - 3 + 4 k) 4 N`` bytes each): not part of the small record, and not counted by the estimate.
     S = 1, or a model without a parameter that requires a gradient, takes the ``"none"`` path.  Any other value raises
     ``ValueError`` before a launch."""
-    from . import data_utils
     w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
                                          step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr,
                                          checkpoint)
     k = int(num_neighbors)
-    if device is None:
-        device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
-    device = torch.device(device)
+    device = _device_of(position_seq, device)
     _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device)
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
-    pos_w = _lib.f32c(position_seq.to(device), "position_seq")
-    tmp_w = _lib.f32c(temperature_seq.to(device), "temperature_seq").reshape(w, n)
-    tgt_p = _lib.f32c(target_positions.to(device), "target_positions")
-    tgt_t = _lib.f32c(target_temperatures.to(device), "target_temperatures").reshape(S, n)
+    pos_w, tmp_w, tgt_p, tgt_t = _device_window(position_seq, temperature_seq, target_positions, target_temperatures,
+                                                device)
     seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
-    true_window = (pos_w, tmp_w, tgt_p[0], tgt_t[0])
+    tgt_p0, tgt_t0 = tgt_p[0], tgt_t[0]
 
     def sample0(want):      # step 0: the one-step sample, with noise from the counter-based generator
-        pos0, tmp0, tgt_p0, tgt_t0 = true_window
-        return ops.training_sample(pos0, tmp0, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
+        return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
                                    tgt_p0, tgt_t0, None, want, stats=cfg.stats)
-    return _unroll(model, cfg, w, n, k, weights, backprop_steps, sample0, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p,
-                   tgt_t, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), knn_grid, min_image_edge_attr,
-                   keep_graphs, checkpoint)
+    unroll = _Unroll(model, cfg, w, n, k, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), checkpoint,
+                     sample0, knn_grid, min_image_edge_attr, keep_graphs)
+    return _unroll(unroll, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps)
 
 
 def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device) -> None:
@@ -1187,67 +1213,42 @@ def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkp
                         f"rounds); {free / 2**30:.1f} GiB are free")
 
 
-def _unroll(model, cfg: _LinkConfig, w: int, n: int, k: int, weights, backprop_steps, sample0, noisy: bool, pos_w, tmp_w,
-            tgt_p, tgt_t, loss_weights, knn_grid: str, min_image_edge_attr: bool, keep_graphs: bool,
-            checkpoint: str) -> UnrolledLoss:
-    """The steps of :func:`unrolled_loss` / :func:`unrolled_batch_loss` over the ``n`` rows of ``cfg``: the true window
-    ``pos_w [W, n, 3]`` / ``tmp_w [W, n]``, the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``, and ``sample0(want)``,
-    which makes step 0's (noisy) sample of the true window as ``ops.training_sample`` returns it."""
-    from . import losses
-    S = len(weights)
-    acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight = loss_weights
-    edge = getattr(model, "message_source", "x_j") == "edge"
-    links = S - 1 if backprop_steps is None else min(int(backprop_steps), S - 1)
-    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
-    s0 = sample0(want)
-    if noisy:       # the noisy frames later windows read, and the shift of every later target
-        pos_w = pos_w + s0["pos_noise"].permute(1, 0, 2)
-        tmp_w = tmp_w + s0["temp_noise"].t()
-        if S > 1:
-            tgt_p = tgt_p + s0["pos_noise"][:, -1]
-            tgt_t = tgt_t + s0["temp_noise"][:, -1]
-    pos_frames, tmp_frames = list(pos_w.unbind(0)), list(tmp_w.unbind(0))
-    if checkpoint == "steps" and S > 1 and any(q.requires_grad for q in model.parameters()):
-        unroll = _CheckpointedUnroll(model, cfg, w, n, k, edge, knn_grid, min_image_edge_attr, loss_weights, keep_graphs)
-        # step 0 draws again from the true window in its recomputation: the same (seed, draw), the same sample
-        unroll.first = sample0
-        return unroll.run(s0, pos_frames, tmp_frames, tgt_p, tgt_t, weights, links)
+def _device_of(position_seq: torch.Tensor, device=None) -> torch.device:
+    """The device of a multi-step loss call: the one asked for, else the window's when it is on one, else the current."""
+    from . import data_utils
+    if device is None:
+        device = position_seq.device if position_seq.is_cuda else data_utils._default_device()
+    return torch.device(device)
 
-    total = None
-    receivers = cfg.ids.repeat_interleave(k)
-    step_losses, graphs, out_p, out_t = [], [], [], []
-    mse = torch.nn.functional.mse_loss
-    for s in range(S):
-        if s == 0:
-            x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
-        else:
-            x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p[s], tgt_t[s], *pos_frames[-w:], *tmp_frames[-w:])
-        edge_attr, senders, order = cfg.graph_lists(recent, edge, k, knn_grid, min_image_edge_attr)
-        edge_index = torch.stack([senders.to(torch.int64), receivers], dim=0)
-        graph = cfg.graph(x, edge_index, edge_attr, y_acc, y_tr, recent.detach(), order, k)
-        pred = model(graph)
-        acc, rate = pred["acceleration"], pred["temp_rate"]
-        terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
-                 losses.momentum_conservation_loss(acc, graph, cfg.dt, momentum_loss_weight))
-        loss_s = acc_loss_weight * terms[0] + temp_rate_loss_weight * terms[1] + terms[2]
-        total = weights[s] * loss_s if total is None else total + weights[s] * loss_s
-        step_losses.append(torch.stack([t.detach() for t in terms]))
-        if keep_graphs:
-            graphs.append(graph)
-        # the next frame; link s feeds step s + 1 and carries gradient when it is one of the last `links`
-        live = s < S - 1 and s >= S - 1 - links
-        if live:
-            new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, pos_frames[-2], pos_frames[-1], tmp_frames[-1])
-        else:
-            with torch.no_grad():
-                new_p, new_t = _IntegrateLink.apply(cfg, acc.detach(), rate.detach(), pos_frames[-2].detach(),
-                                                    pos_frames[-1].detach(), tmp_frames[-1].detach())
-        out_p.append(new_p.detach())
-        out_t.append(new_t.detach())
-        pos_frames.append(new_p)
-        tmp_frames.append(new_t)
-    frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
-    return UnrolledLoss(total, torch.stack(step_losses), frames, graphs if keep_graphs else None)
+
+def _device_window(position_seq, temperature_seq, target_positions, target_temperatures, device):
+    """-> (``pos_w [W, n, 3]``, ``tmp_w [W, n]``, ``tgt_p [S, n, 3]``, ``tgt_t [S, n]``): contiguous float32 on ``device``."""
+    w, n, S = position_seq.shape[0], position_seq.shape[1], target_positions.shape[0]
+    return (_lib.f32c(position_seq.to(device), "position_seq"),
+            _lib.f32c(temperature_seq.to(device), "temperature_seq").reshape(w, n),
+            _lib.f32c(target_positions.to(device), "target_positions"),
+            _lib.f32c(target_temperatures.to(device), "target_temperatures").reshape(S, n))
+
+
+def _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, noise):
+    """-> (W position frames, W temperature frames, ``tgt_p``, ``tgt_t``) as the steps read them.  ``noise``: ``None``, or
+    ``pos_noise [n, W, 3]`` / ``temp_noise [n, W]`` of step 0's sample: added to the true frames, which later windows
+    read, and for S > 1 every target is shifted by the last frame's noise."""
+    if noise is not None:
+        pos_w = pos_w + noise["pos_noise"].permute(1, 0, 2)
+        tmp_w = tmp_w + noise["temp_noise"].t()
+        if tgt_p.shape[0] > 1:
+            tgt_p = tgt_p + noise["pos_noise"][:, -1]
+            tgt_t = tgt_t + noise["temp_noise"][:, -1]
+    return list(pos_w.unbind(0)), list(tmp_w.unbind(0)), tgt_p, tgt_t
+
+
+def _unroll(unroll: _Unroll, noisy: bool, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps) -> UnrolledLoss:
+    """:func:`unrolled_loss` / :func:`unrolled_batch_loss` from the true window ``pos_w [W, n, 3]`` / ``tmp_w [W, n]`` and
+    the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``: step 0's sample is drawn here, with its noise in the same launch."""
+    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
+    s0 = unroll.sample0(want)
+    return unroll.run(*_noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None), weights, backprop_steps, s0)
 
 
 def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions, target_temperatures, metadata: dict, *,
@@ -1294,10 +1295,7 @@ def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions
         shape = (w, S)
         offsets.append(offsets[-1] + n_b)
     k, n = int(num_neighbors), offsets[-1]
-    if device is None:
-        first = m["position_seqs"][0]
-        device = first.device if first.is_cuda else data_utils._default_device()
-    device = torch.device(device)
+    device = _device_of(m["position_seqs"][0], device)
     _check_unroll_memory(who, model, n, k, w, S, checkpoint, device)
     cfg = _LinkConfig(metadata, dt, box_size, n, device, offsets)
     sizes = [b - a for a, b in zip(offsets, offsets[1:])]
@@ -1313,8 +1311,9 @@ def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions
                                      noise_draw + b, tgt_p[0, offsets[b]:offsets[b + 1]],
                                      tgt_t[0, offsets[b]:offsets[b + 1]], None, want, stats=cfg.stats) for b in range(nb)]
         return {name: torch.cat([part[name] for part in parts]) for name in want}
-    out = _unroll(model, cfg, w, n, k, weights, backprop_steps, sample0, float(noise_std) != 0.0, torch.cat(pos_b, dim=1),
-                  torch.cat(tmp_b, dim=1), tgt_p, tgt_t, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight),
-                  knn_grid, min_image_edge_attr, keep_graphs, checkpoint)
+    unroll = _Unroll(model, cfg, w, n, k, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), checkpoint,
+                     sample0, knn_grid, min_image_edge_attr, keep_graphs)
+    out = _unroll(unroll, float(noise_std) != 0.0, torch.cat(pos_b, dim=1), torch.cat(tmp_b, dim=1), tgt_p, tgt_t, weights,
+                  backprop_steps)
     out.offsets = offsets
     return out

@@ -261,3 +261,37 @@ def test_memory_guard_follows_the_checkpoint_mode(monkeypatch):
     out = training.unrolled_loss(model, p, t, tp, tt, uc.META, checkpoint="steps", **kw)
     out.loss.backward()
     assert bool(torch.isfinite(out.loss))
+
+
+# ---- 8. which forward runs -------------------------------------------------------------------------------------------------
+
+def test_frozen_parameters_take_the_inference_forward_in_both_modes():
+    """No parameter requires a gradient: ``"steps"`` takes the ``"none"`` path, whose ``model(graph)`` is then the
+    inference forward (``node_precision`` kernels), not the training forward a checkpointed step runs."""
+    w, s = 3, 2
+    model, _ = _model(w, "x_j", "fp32")
+    model.node_precision, model.train_precision = "fp16x2", "fp32"
+    for q in model.parameters():
+        q.requires_grad_(False)
+    p, t, tp, tt = (v.to(DEV) for v in _data(w, s))
+    kw = dict(dt=DT, box_size=1.0, num_neighbors=K, momentum_loss_weight=WEIGHTS[2], keep_graphs=True)
+    none = training.unrolled_loss(model, p, t, tp, tt, uc.META, checkpoint="none", **kw)
+    steps = training.unrolled_loss(model, p, t, tp, tt, uc.META, checkpoint="steps", **kw)
+    mse = torch.nn.functional.mse_loss
+    with torch.no_grad():       # not vacuous: the two forwards differ in their bits on this graph
+        inference, train = model(none.graphs[0]), model._forward_train(none.graphs[0])
+    differing = int((inference["acceleration"] != train["acceleration"]).sum())
+    print(f"inference (fp16x2) against training (fp32) forward on step 0's graph: {differing} of "
+          f"{train['acceleration'].numel()} acceleration entries differ")
+    assert not torch.equal(inference["acceleration"], train["acceleration"])
+    for out in (none, steps):
+        assert not out.loss.requires_grad
+    assert torch.equal(steps.loss, none.loss) and torch.equal(steps.step_losses, none.step_losses)
+    for name in ("Coordinates", "InternalEnergy"):
+        assert torch.equal(steps.frames[name], none.frames[name]), name
+    for out in (none, steps):
+        assert len(out.graphs) == s
+        for i, g in enumerate(out.graphs):
+            with torch.no_grad():
+                pred = model(g)
+            assert torch.equal(out.step_losses[i, 0], mse(pred["acceleration"], g.y_acc)), i
