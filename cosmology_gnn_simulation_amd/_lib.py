@@ -49,8 +49,13 @@ EXPORTS = (
     "cgnn_edge_attr_backward_rows", "cgnn_rows_to_frames", "cgnn_frame_grad_rows", "cgnn_mlp_rows_project",
     "cgnn_knn_batched_workspace_bytes", "cgnn_knn_periodic_batched", "cgnn_knn_batched_sorted_order",
     "cgnn_pair_counts_workspace_bytes", "cgnn_pair_counts", "cgnn_frame_errors_workspace_bytes", "cgnn_frame_errors",
+    "cgnn_mass_assign", "cgnn_power_bin_ids", "cgnn_power_bins_workspace_bytes", "cgnn_power_bins",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
+MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
+MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
+MASS_ASSIGN_MAX_PARTICLES = 1 << 24
+POWER_MAX_BINS = 256          # CGNN_PB_MAX_BINS
 KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -143,6 +148,11 @@ def load() -> C.CDLL:
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]
+    lib.cgnn_mass_assign.argtypes = [vp, i64, i64, f32, i32, i32, vp, vp]
+    lib.cgnn_power_bin_ids.argtypes = [i32, C.POINTER(f32), i32, vp, vp]                            # k_edges: host memory
+    lib.cgnn_power_bins_workspace_bytes.restype = sz
+    lib.cgnn_power_bins_workspace_bytes.argtypes = [i64, i32]
+    lib.cgnn_power_bins.argtypes = [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

@@ -1,0 +1,361 @@
+// The matter power spectrum of a frame on the device: cgnn_mass_assign deposits particles onto a periodic mesh in exact
+// integers, cgnn_power_bin_ids and cgnn_power_bins reduce the modes of the mesh's real FFT (torch.fft.rfftn, between the
+// two) into shells of |k| with float64 sums whose additions have fixed places.  Contracts: include/cgnn.h;
+// tests/power_spectrum_checks.py restates them in numpy.
+//
+// Deposit.  s = fl32(fl32(M) / fl32(L)) on the host; per axis u = fl32(p s), and integer weights that sum to Q = 2^13:
+//     NGP  j = floor(fl32(u + 0.5)):  Q on j
+//     CIC  i = floor(u), f = fl32(u - i):  a1 = rint(f Q) on i + 1,  Q - a1 on i
+//     TSC  j = floor(fl32(u + 0.5)), d = fl32(u - j), tm = fl32(0.5 - d), tp = fl32(0.5 + d):
+//          am = rint(fl32(fl32(tm tm) 0.5) Q) on j - 1,  ap likewise from tp on j + 1,  Q - am - ap on j
+// (f Q and the TSC product with Q are exact: Q is a power of two; rint rounds ties to even.)  A particle adds the product
+// of its three axis weights to each of its order^3 cells, wrapped with a true modulo: Q^3 = 2^39 per particle in all.
+// Float weights would make a cell's sum depend on the order in which the atomics arrive; integers do not, so the mesh is
+// the same bits on every run and equals the restatement exactly, and the density contrast derived from it is exact
+// up to its one conversion to float64.  One thread per particle, one 64-bit integer atomic per cell with a non-zero
+// weight.  Many particles in one cell serialise on one address (scripts/time_power_spectrum.py times a clustered frame).
+//
+// Binning.  A mode of the rfft array [M, M, M/2 + 1] has signed frequencies nx, ny in (-M/2, M/2] and nz in [0, M/2];
+// n2 = nx^2 + ny^2 + nz^2 <= 3 * 256^2 is exact in integers and in float32.  With e2[i] = fl32(k_edges[i]^2) the mode
+// is in bin i iff e2[i] <= (float)n2 < e2[i + 1]; n2 = 0 is never counted.  Its Hermitian weight h is 1 on the planes
+// that are their own conjugates (nz == 0, and nz == M/2 when M is even) and 2 elsewhere: the half array then sums what
+// the full cube would.  cgnn_power_bin_ids writes the bin of every mode (-1: none); the caller sorts the ids stably
+// (once per mesh and edges: ops.PowerPlan) into `perm`, the counted modes grouped by bin in ascending mode index, and
+// `bin_start`, where each bin begins.  cgnn_power_bins then sums in two stages: workgroup (frame, bin, part) takes the
+// part-th of CGNN_PB_PARTS equal slices of the bin's run of perm, each thread its strided share in index order, a tree
+// over the threads; one thread per (frame, bin, sum) then adds the parts in part order.  No float atomics: two runs give
+// the same bits.  A slice without modes writes zeros and leaves before the tree.  Compiled with -ffp-contract=off (Makefile): every operation below rounds once, in float32 and float64.
+#include <math.h>
+
+#include "cgnn_common.hpp"
+
+#define CGNN_MA_Q 8192           // 2^13: the axis weights of a particle sum to this
+#define CGNN_MA_MAX_MESH 512
+#define CGNN_PB_MAX_BINS 256
+#define CGNN_PB_PARTS 64          // slices per bin (stage 1 of cgnn_power_bins)
+#define CGNN_PS_MAX_THREADS ((int64_t)1 << 24)   // threads per launch: many frames go through in several launches
+#define CGNN_PB_SUMS 4            // float64 sums per (frame, bin): |a|^2, |b|^2, Re(a conj b), sqrt(n2)
+
+namespace cgnn {
+
+__device__ __forceinline__ int ma_wrap(int c, int M) {
+    c %= M;
+    return c < 0 ? c + M : c;
+}
+
+// cells and weights of one axis; ORDER entries of each are written
+template <int ORDER>
+__device__ __forceinline__ void ma_axis(float u, int M, int* cell, int* w) {
+    if (ORDER == 1) {
+        cell[0] = ma_wrap((int)floorf(__fadd_rn(u, 0.5f)), M);
+        w[0] = CGNN_MA_Q;
+    } else if (ORDER == 2) {
+        const float fi = floorf(u);
+        const float f = __fsub_rn(u, fi);
+        const int i = (int)fi;
+        const int a1 = (int)rintf(__fmul_rn(f, (float)CGNN_MA_Q));
+        cell[0] = ma_wrap(i, M);
+        cell[1] = ma_wrap(i + 1, M);
+        w[0] = CGNN_MA_Q - a1;
+        w[1] = a1;
+    } else {
+        const float fj = floorf(__fadd_rn(u, 0.5f));
+        const int j = (int)fj;
+        const float d = __fsub_rn(u, fj);
+        const float tm = __fsub_rn(0.5f, d), tp = __fadd_rn(0.5f, d);
+        const int am = (int)rintf(__fmul_rn(__fmul_rn(__fmul_rn(tm, tm), 0.5f), (float)CGNN_MA_Q));
+        const int ap = (int)rintf(__fmul_rn(__fmul_rn(__fmul_rn(tp, tp), 0.5f), (float)CGNN_MA_Q));
+        cell[0] = ma_wrap(j - 1, M);
+        cell[1] = ma_wrap(j, M);
+        cell[2] = ma_wrap(j + 1, M);
+        w[0] = am;
+        w[1] = CGNN_MA_Q - am - ap;
+        w[2] = ap;
+    }
+}
+
+// one thread per particle of every frame; mesh [frames, M, M, M], zeroed by the caller
+template <int ORDER>
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __restrict__ pos, int64_t total, int64_t n,
+                                                                float s, int M, unsigned long long* __restrict__ mesh) {
+    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    int cell[3][ORDER], w[3][ORDER];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        float u = __fmul_rn(pos[3 * i + ax], s);
+        // NaN or far outside the contract ([0, M]): a float -> int conversion out of range is undefined, and nothing may
+        // index outside the mesh; inside the contract this never acts
+        if (!(fabsf(u) < 1.0e9f)) u = 0.f;
+        ma_axis<ORDER>(u, M, cell[ax], w[ax]);
+    }
+    unsigned long long* base = mesh + (i / n) * ((int64_t)M * M * M);
+#pragma unroll
+    for (int a = 0; a < ORDER; ++a)
+#pragma unroll
+        for (int b = 0; b < ORDER; ++b)
+#pragma unroll
+            for (int c = 0; c < ORDER; ++c) {
+                const long long v = (long long)w[0][a] * w[1][b] * w[2][c];
+                if (v != 0) atomicAdd(base + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c], (unsigned long long)v);
+            }
+}
+
+static inline size_t pb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct PbEdges2 {
+    float e2[CGNN_PB_MAX_BINS + 1];
+};
+
+// mode index -> (nx, ny, nz) of the rfft array [M, M, Mh]
+__device__ __forceinline__ void pb_mode(int idx, int M, int Mh, int& nx, int& ny, int& nz) {
+    nz = idx % Mh;
+    const int r = idx / Mh;
+    const int iy = r % M, ix = r / M;
+    nx = ix <= M / 2 ? ix : ix - M;
+    ny = iy <= M / 2 ? iy : iy - M;
+}
+
+__global__ __launch_bounds__(CGNN_BLOCK) void pb_ids_kernel(int M, int Mh, int modes, const PbEdges2 E, int num_bins,
+                                                            int32_t* __restrict__ ids) {
+    const int idx = blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (idx >= modes) return;
+    int nx, ny, nz;
+    pb_mode(idx, M, Mh, nx, ny, nz);
+    const int n2 = nx * nx + ny * ny + nz * nz;
+    const float v = (float)n2;                   // exact: n2 < 2^24
+    int bin = -1;
+    if (n2 != 0 && v >= E.e2[0] && v < E.e2[num_bins]) {
+        int lo = 0, up = num_bins;               // e2[lo] <= v < e2[up]
+        while (up - lo > 1) {
+            const int mid = (lo + up) >> 1;
+            if (E.e2[mid] <= v) lo = mid; else up = mid;
+        }
+        bin = lo;
+    }
+    ids[idx] = bin;
+}
+
+// inv_w2[i] = 1 / sinc(pi i / M)^(2 order) for i in [0, M/2]: the deconvolution of one axis (|n| indexes it)
+__global__ void pb_window_kernel(int M, int order, double* __restrict__ inv_w2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > M / 2) return;
+    double v = 1.0;
+    if (i > 0 && order > 0) {
+        const double x = 3.14159265358979323846 * (double)i / (double)M;
+        const double sc = sin(x) / x;
+        const double s2 = sc * sc;
+        double p = s2;
+        for (int j = 1; j < order; ++j) p *= s2;
+        v = 1.0 / p;
+    }
+    inv_w2[i] = v;
+}
+
+// stage 1: workgroup ((f * num_bins + bin) * PARTS + part); partial [frames, num_bins, PARTS, SUMS], cnt likewise one value
+__global__ __launch_bounds__(CGNN_BLOCK) void pb_partial_kernel(const double2* __restrict__ a, const double2* __restrict__ b,
+                                                                int M, int Mh, int64_t modes_per_frame,
+                                                                const int32_t* __restrict__ perm,
+                                                                const int32_t* __restrict__ bin_start, int num_bins,
+                                                                const double* __restrict__ inv_w2,
+                                                                double* __restrict__ partial, long long* __restrict__ cnt) {
+    __shared__ double red[CGNN_PB_SUMS][CGNN_BLOCK];
+    __shared__ long long redc[CGNN_BLOCK];
+    const int part = blockIdx.x % CGNN_PB_PARTS;
+    const int bin = (blockIdx.x / CGNN_PB_PARTS) % num_bins;
+    const int64_t f = blockIdx.x / (CGNN_PB_PARTS * num_bins);
+    // clamped: a plan that does not belong to this mesh reads nothing outside perm [modes_per_frame]
+    const int p0 = max(0, min(bin_start[bin], (int)modes_per_frame));
+    const int p1 = max(p0, min(bin_start[bin + 1], (int)modes_per_frame));
+    const int per = (p1 - p0 + CGNN_PB_PARTS - 1) / CGNN_PB_PARTS;
+    const int q0 = p0 + part * per, q1 = min(q0 + per, p1);
+    if (q0 >= q1) {     // an empty slice (a bin of few modes fills only its first slices): uniform over the workgroup
+        if (threadIdx.x < CGNN_PB_SUMS) partial[(int64_t)blockIdx.x * CGNN_PB_SUMS + threadIdx.x] = 0.0;
+        if (threadIdx.x == 0) cnt[blockIdx.x] = 0;
+        return;
+    }
+    const double2* af = a + f * modes_per_frame;
+    const double2* bf = b ? b + f * modes_per_frame : nullptr;
+    double saa = 0.0, sbb = 0.0, sab = 0.0, sk = 0.0;
+    long long sc = 0;
+    for (int p = q0 + (int)threadIdx.x; p < q1; p += CGNN_BLOCK) {
+        const int idx = perm[p];
+        if (idx < 0 || idx >= modes_per_frame) continue;      // a plan of another mesh: nothing is read out of bounds
+        int nx, ny, nz;
+        pb_mode(idx, M, Mh, nx, ny, nz);
+        const double h = (nz == 0 || 2 * nz == M) ? 1.0 : 2.0;
+        const double wt = h * ((inv_w2[abs(nx)] * inv_w2[abs(ny)]) * inv_w2[nz]);
+        const double2 x = af[idx];
+        saa += wt * (x.x * x.x + x.y * x.y);
+        if (bf) {
+            const double2 y = bf[idx];
+            sbb += wt * (y.x * y.x + y.y * y.y);
+            sab += wt * (x.x * y.x + x.y * y.y);
+        }
+        sk += h * sqrt((double)(nx * nx + ny * ny + nz * nz));
+        sc += (long long)h;
+    }
+    red[0][threadIdx.x] = saa;
+    red[1][threadIdx.x] = sbb;
+    red[2][threadIdx.x] = sab;
+    red[3][threadIdx.x] = sk;
+    redc[threadIdx.x] = sc;
+    __syncthreads();
+    for (int off = CGNN_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+#pragma unroll
+            for (int q = 0; q < CGNN_PB_SUMS; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + off];
+            redc[threadIdx.x] += redc[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < CGNN_PB_SUMS) partial[(int64_t)blockIdx.x * CGNN_PB_SUMS + threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x == 0) cnt[blockIdx.x] = redc[0];
+}
+
+// stage 2: thread (f, bin, q) adds the parts in part order; q == SUMS is the mode count.
+// sums [frames, SUMS, num_bins] (rows 1 and 2 untouched without b), modes [frames, num_bins]
+__global__ __launch_bounds__(CGNN_BLOCK) void pb_final_kernel(const double* __restrict__ partial,
+                                                              const long long* __restrict__ cnt, int64_t frames,
+                                                              int num_bins, int have_b, double* __restrict__ sums,
+                                                              long long* __restrict__ modes) {
+    const int64_t t = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (t >= frames * num_bins * (CGNN_PB_SUMS + 1)) return;
+    const int q = (int)(t % (CGNN_PB_SUMS + 1));
+    const int64_t fb = t / (CGNN_PB_SUMS + 1);        // f * num_bins + bin
+    const int64_t f = fb / num_bins, bin = fb % num_bins;
+    if (q == CGNN_PB_SUMS) {
+        long long s = 0;
+        for (int j = 0; j < CGNN_PB_PARTS; ++j) s += cnt[fb * CGNN_PB_PARTS + j];
+        modes[fb] = s;
+        return;
+    }
+    if (!have_b && (q == 1 || q == 2)) return;
+    double s = 0.0;
+    for (int j = 0; j < CGNN_PB_PARTS; ++j) s += partial[(fb * CGNN_PB_PARTS + j) * CGNN_PB_SUMS + q];
+    sums[(f * CGNN_PB_SUMS + q) * num_bins + bin] = s;
+}
+
+static bool pb_edges(const float* k_edges, int32_t num_bins, PbEdges2& E, const char* who) {
+    if (num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
+        set_error("%s: num_bins=%d outside [1, %d]", who, (int)num_bins, CGNN_PB_MAX_BINS);
+        return false;
+    }
+    for (int i = 0; i <= num_bins; ++i) {
+        if (!isfinite(k_edges[i]) || k_edges[i] < 0.f || (i > 0 && !(k_edges[i] > k_edges[i - 1]))) {
+            set_error("%s: k_edges must be finite, non-negative and strictly ascending (k_edges[%d])", who, i);
+            return false;
+        }
+        E.e2[i] = k_edges[i] * k_edges[i];       // fl32 product, rounded once
+    }
+    for (int i = num_bins + 1; i <= CGNN_PB_MAX_BINS; ++i) E.e2[i] = 0.f;
+    return true;
+}
+
+static size_t pb_window_bytes() { return pb_align256((size_t)(CGNN_MA_MAX_MESH / 2 + 1) * sizeof(double)); }
+
+}  // namespace cgnn
+
+using namespace cgnn;
+
+extern "C" {
+
+int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
+                     int64_t* out, void* stream) {
+    if (!pos || !out || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
+        set_error("cgnn_mass_assign: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (mesh < 2 || mesh > CGNN_MA_MAX_MESH || order < 1 || order > 3) {
+        set_error("cgnn_mass_assign: mesh=%d outside [2, %d] or order=%d outside [1, 3]", (int)mesh, CGNN_MA_MAX_MESH,
+                  (int)order);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n > ((int64_t)1 << 24)) {
+        set_error("cgnn_mass_assign: more than 2^24 particles in a frame (n 2^39 must stay inside int64)");
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    const float s = (float)mesh / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)frames * mesh * mesh * mesh * sizeof(int64_t);
+    int rc = check_hip(hipMemsetAsync(out, 0, bytes, st), "cgnn_mass_assign memset");
+    if (rc) return rc;
+    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^24: at least one frame)
+    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
+        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        const float* p = pos + f0 * n * 3;
+        unsigned long long* m = reinterpret_cast<unsigned long long*>(out) + f0 * cells;
+        if (order == 1) ma_deposit_kernel<1><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
+        else if (order == 2) ma_deposit_kernel<2><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
+        else ma_deposit_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
+    }
+    return check_hip(hipGetLastError(), "cgnn_mass_assign");
+}
+
+int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream) {
+    if (!k_edges || !ids || mesh < 2 || mesh > CGNN_MA_MAX_MESH) {
+        set_error("cgnn_power_bin_ids: invalid argument (mesh in [2, %d])", CGNN_MA_MAX_MESH);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    PbEdges2 E;
+    if (!pb_edges(k_edges, num_bins, E, "cgnn_power_bin_ids")) return CGNN_ERR_INVALID_ARG;
+    const int Mh = mesh / 2 + 1, modes = mesh * mesh * Mh;       // <= 512 * 512 * 257 < 2^31
+    pb_ids_kernel<<<(unsigned)((modes + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(
+        mesh, Mh, modes, E, num_bins, ids);
+    return check_hip(hipGetLastError(), "cgnn_power_bin_ids");
+}
+
+size_t cgnn_power_bins_workspace_bytes(int64_t frames, int32_t num_bins) {
+    if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
+    const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
+    return pb_window_bytes() + pb_align256(blocks * CGNN_PB_SUMS * sizeof(double)) + pb_align256(blocks * sizeof(long long));
+}
+
+int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t mesh, int32_t order, const int32_t* perm,
+                    const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    if (!a || !perm || !bin_start || !modes || !sums || !workspace || frames <= 0 || mesh < 2 ||
+        mesh > CGNN_MA_MAX_MESH || order < 0 || order > 3 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
+        set_error("cgnn_power_bins: invalid argument (mesh in [2, %d], order in [0, 3], num_bins in [1, %d])",
+                  CGNN_MA_MAX_MESH, CGNN_PB_MAX_BINS);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const int64_t per_frame = (int64_t)num_bins * CGNN_PB_PARTS, blocks = frames * per_frame;
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(a) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(b) & 15) != 0) {
+        set_error("cgnn_power_bins: a, b and the workspace must be 16-byte aligned");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const size_t need = cgnn_power_bins_workspace_bytes(frames, num_bins);
+    if (workspace_bytes < need) {
+        set_error("cgnn_power_bins: workspace %zu < required %zu bytes", workspace_bytes, need);
+        return CGNN_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    double* inv_w2 = reinterpret_cast<double*>(ws);
+    double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
+    long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() +
+                                                  pb_align256((size_t)blocks * CGNN_PB_SUMS * sizeof(double)));
+    const int Mh = mesh / 2 + 1;
+    pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
+    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (at least 4 frames)
+    const int64_t step = CGNN_PS_MAX_THREADS / (per_frame * CGNN_BLOCK), modes_per_frame = (int64_t)mesh * mesh * Mh;
+    const double2* a2 = reinterpret_cast<const double2*>(a);
+    const double2* b2 = reinterpret_cast<const double2*>(b);
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t nf = frames - f0 < step ? frames - f0 : step;
+        pb_partial_kernel<<<(unsigned)(nf * per_frame), CGNN_BLOCK, 0, st>>>(
+            a2 + f0 * modes_per_frame, b2 ? b2 + f0 * modes_per_frame : nullptr, mesh, Mh, modes_per_frame, perm, bin_start,
+            num_bins, inv_w2, partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame);
+        const int64_t outs = nf * num_bins * (CGNN_PB_SUMS + 1);
+        pb_final_kernel<<<(unsigned)((outs + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
+            partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame, nf, num_bins, b != nullptr,
+            sums + f0 * CGNN_PB_SUMS * num_bins, reinterpret_cast<long long*>(modes) + f0 * num_bins);
+    }
+    return check_hip(hipGetLastError(), "cgnn_power_bins");
+}
+
+}  // extern "C"

@@ -531,6 +531,65 @@ class AggregatePlan:
         return plan
 
 
+def power_bin_ids(mesh: int, k_edges, device) -> torch.Tensor:
+    """The bin of every mode of the rfft array (``cgnn_power_bin_ids``): int32 ``[M, M, M/2 + 1]`` on ``device``, -1 where a
+    mode is not counted (``n2 = 0``, or outside the edges).  No host synchronisation."""
+    what = "power_bin_ids"
+    e = check_power_edges(k_edges, what)
+    m = check_mesh(mesh, what)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise CgnnError(f"{what}: needs a HIP device (got {device}); this engine has no CPU path")
+    ids = torch.empty((m, m, m // 2 + 1), dtype=torch.int32, device=device)
+    edges_c = (C.c_float * len(e))(*e)
+    with _timed(what, ids.device):
+        check(_lib.load().cgnn_power_bin_ids(m, edges_c, len(e) - 1, ids.data_ptr(), stream_ptr(ids.device)),
+              "cgnn_power_bin_ids")
+    return ids
+
+
+class PowerPlan:
+    """The mode order of ``cgnn_power_bins`` for one ``(mesh, k_edges)`` on one device: a stable sort of
+    :func:`power_bin_ids` groups the modes by bin in ascending mode index (``perm``, int32 ``[modes]``) and a search of
+    the sorted ids gives where each bin begins (``bin_start``, int32 ``[nb + 1]``).  Built without a host
+    synchronisation.  A plan keeps 4 bytes per mode (``perm``; the ids are dropped once it exists): 270 MB at mesh 512;
+    while it is built the ids, their sorted copy and the sort's int64 order are alive too, 20 bytes per mode at the
+    peak.  ``PowerPlan.of`` keeps the last plan of each device for the life of the process (``PowerPlan.forget()``
+    drops them)."""
+
+    _last = {}
+
+    def __init__(self, mesh: int, k_edges, device):
+        self.edges = tuple(check_power_edges(k_edges, "PowerPlan"))
+        self.mesh, self.num_bins = check_mesh(mesh, "PowerPlan"), len(self.edges) - 1
+        ids = power_bin_ids(self.mesh, self.edges, device).reshape(-1)
+        self.device, self.num_modes = ids.device, ids.numel()
+        sorted_ids, perm = torch.sort(ids, stable=True)
+        del ids
+        self.perm = perm.to(torch.int32)
+        del perm
+        self.bin_start = torch.searchsorted(
+            sorted_ids, torch.arange(self.num_bins + 1, dtype=torch.int32, device=self.device)).to(torch.int32)
+
+    @staticmethod
+    def forget() -> None:
+        """Drop the plans ``PowerPlan.of`` holds."""
+        PowerPlan._last.clear()
+
+    @staticmethod
+    def of(mesh: int, k_edges, device) -> "PowerPlan":
+        """The plan for ``(mesh, k_edges)`` on ``device``: the device's last one when it fits, else a new one."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (int(mesh), tuple(check_power_edges(k_edges, "PowerPlan")))
+        plan = PowerPlan._last.get(device)
+        if plan is None or (plan.mesh, plan.edges) != key:
+            plan = PowerPlan(mesh, k_edges, device)
+            PowerPlan._last[device] = plan
+        return plan
+
+
 def aggregate(table, gather: Optional[torch.Tensor], dst: Optional[torch.Tensor], num_nodes: int,
               fixed_k: int = 0, num_edges: Optional[int] = None, out: Optional[torch.Tensor] = None,
               plan: Optional[AggregatePlan] = None) -> torch.Tensor:
@@ -837,6 +896,113 @@ def frame_errors(pred_pos: torch.Tensor, true_pos: torch.Tensor, pred_tmp: Optio
     out[:, 0] /= 3 * n
     out[:, 1] /= n
     return out
+
+
+def check_mesh(mesh, who: str) -> int:
+    """``mesh`` as an int in ``[2, 512]``, or ``ValueError``."""
+    if isinstance(mesh, bool) or int(mesh) != mesh or not 2 <= int(mesh) <= _lib.MASS_ASSIGN_MAX_MESH:
+        raise ValueError(f"{who}: mesh must be an integer in [2, {_lib.MASS_ASSIGN_MAX_MESH}], got {mesh!r}")
+    return int(mesh)
+
+
+def check_power_edges(k_edges, who: str) -> List[float]:
+    """The bin edges of :func:`power_bins` as float32 host values (units of the fundamental frequency), or
+    ``ValueError``: ``1 <= nb <= 256`` bins, finite, ``k_edges[0] >= 0``, strictly ascending in float32."""
+    e = torch.as_tensor(k_edges).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    nb = e.numel() - 1
+    if not 1 <= nb <= _lib.POWER_MAX_BINS:
+        raise ValueError(f"{who}: k_edges must hold nb + 1 values with 1 <= nb <= {_lib.POWER_MAX_BINS}, got "
+                         f"{e.numel()} values")
+    if not bool(torch.isfinite(e).all()) or float(e[0]) < 0.0 or not bool((e[1:] > e[:-1]).all()):
+        raise ValueError(f"{who}: k_edges must be finite, start at 0 or above and ascend strictly (in float32)")
+    return e.tolist()
+
+
+def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, check_bounds: bool = False) -> torch.Tensor:
+    """Particles onto a periodic ``mesh^3`` grid in exact integers (``cgnn_mass_assign``): ``int64 [M, M, M]`` for ``pos
+    [N, 3]``, ``int64 [T, M, M, M]`` for ``pos [T, N, 3]`` (all frames in one launch sequence, no host synchronisation).
+    ``order``: 1 = NGP, 2 = CIC, 3 = TSC.  Every particle deposits exactly ``Q^3 = 2^39`` (``_lib.MASS_ASSIGN_Q ** 3``),
+    split over its ``order^3`` cells by the integer weights of ``include/cgnn.h``, so ``mesh.sum() == N * 2^39``, the
+    mesh equals the numpy restatement exactly and is the same bits on every run.  The density contrast is
+    ``mesh.double() * (M^3 / (N Q^3)) - 1``.
+
+    Refused on the host before any device work (``ValueError``): ``mesh`` outside 2..512, ``order`` outside 1..3, more
+    than 2^24 particles per frame, ``box_size <= 0``.  Positions lie in ``[0, box_size]`` (``box_size`` itself lands in
+    cell 0); ``check_bounds=True`` verifies that (and that they are finite) with one host synchronisation, the default
+    verifies nothing.  One box per call."""
+    what = "mass_assign"
+    mesh = check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if pos.shape[-2] > _lib.MASS_ASSIGN_MAX_PARTICLES:
+        raise ValueError(f"{what}: {pos.shape[-2]} particles per frame exceed 2^24 (N 2^39 must stay inside int64)")
+    pos = f32c(pos, "pos")
+    if check_bounds and not bool(((pos >= 0) & (pos <= float(box_size))).all()):
+        raise ValueError(f"{what}: pos leaves [0, box_size] or is not finite")
+    batched = pos.dim() == 3
+    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
+    out = torch.empty((t, mesh, mesh, mesh), dtype=torch.int64, device=pos.device)
+    with _timed(what, pos.device):
+        check(_lib.load().cgnn_mass_assign(pos.data_ptr(), t, n, float(box_size), mesh, int(order), out.data_ptr(),
+                                           stream_ptr(pos.device)), "cgnn_mass_assign")
+    return out if batched else out[0]
+
+
+def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b: Optional[torch.Tensor] = None,
+               plan: Optional[PowerPlan] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Shell sums of the modes of ``delta_k = torch.fft.rfftn(delta)`` (``cgnn_power_bins``): complex128 ``[M, M, M/2 + 1]``
+    or ``[T, M, M, M/2 + 1]``.  Returns ``(modes, sums)`` on the device: ``modes`` int64 ``[nb]`` (``[T, nb]``), the
+    number of modes of the full cube in each bin, and ``sums`` float64 ``[4, nb]`` (``[T, 4, nb]``) with the rows
+
+    0. ``sum h |a|^2 / W2``,  1. ``sum h |b|^2 / W2``,  2. ``sum h Re(a conj b) / W2``,  3. ``sum h sqrt(n2)``
+
+    (``a = delta_k``, ``b = delta_k_b``; without ``delta_k_b`` rows 1 and 2 are ``nan``).  ``h`` is the Hermitian
+    weight of the half array, ``W2`` the window of a deposit of that ``order`` (0: none), ``k_edges`` the ``nb + 1``
+    bin edges in units of the fundamental frequency (host values; bin ``i`` holds ``fl32(k_edges[i]^2) <= n2 <
+    fl32(k_edges[i+1]^2)``, ``n2 = 0`` never).  Every float64 addition has a fixed place: two calls give the same bits.
+    ``plan``: a :class:`PowerPlan` of ``(mesh, k_edges)`` (default ``PowerPlan.of``).  No host synchronisation."""
+    what = "power_bins"
+    mesh = check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in (0, 1, 2, 3):
+        raise ValueError(f"{what}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
+    e = check_power_edges(k_edges, what)
+    nb = len(e) - 1
+    shape = (mesh, mesh, mesh // 2 + 1)
+    for name, d in (("delta_k", delta_k), ("delta_k_b", delta_k_b)):
+        if d is None:
+            continue
+        require_device(d, name)
+        if d.dtype != torch.complex128 or d.dim() not in (3, 4) or tuple(d.shape[-3:]) != shape:
+            raise CgnnError(f"{what}: {name} must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got {d.dtype} "
+                            f"{tuple(d.shape)}")
+    if delta_k_b is not None and delta_k_b.shape != delta_k.shape:
+        raise CgnnError(f"{what}: delta_k_b is {tuple(delta_k_b.shape)}, delta_k {tuple(delta_k.shape)}")
+    _same_device(delta_k, delta_k_b)
+    if plan is None:
+        plan = PowerPlan.of(mesh, e, delta_k.device)
+    elif plan.mesh != mesh or plan.edges != tuple(e) or plan.perm.device != delta_k.device:
+        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
+    batched = delta_k.dim() == 4
+    a = delta_k.contiguous()
+    b = None if delta_k_b is None else delta_k_b.contiguous()
+    t = a.shape[0] if batched else 1
+    if t < 1:
+        raise CgnnError(f"{what}: no frames")
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_power_bins_workspace_bytes(t, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    modes = torch.empty((t, nb), dtype=torch.int64, device=a.device)
+    sums = torch.full((t, 4, nb), float("nan"), dtype=torch.float64, device=a.device)
+    with _timed(what, a.device):
+        check(lib.cgnn_power_bins(a.data_ptr(), ptr(b), t, mesh, int(order), plan.perm.data_ptr(),
+                                  plan.bin_start.data_ptr(), nb, modes.data_ptr(), sums.data_ptr(), ws.data_ptr(),
+                                  ws_bytes, stream_ptr(a.device)), "cgnn_power_bins")
+    return (modes, sums) if batched else (modes[0], sums[0])
 
 
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,

@@ -7,6 +7,14 @@ clustering is right is what xi(r) of the predicted frame against the true one, a
 ``rollout.calculate_errors`` (the reference's function) stays as it is: one host synchronisation per frame, and a
 particle that crossed a box face scored as wrong by a whole box length.
 
+In Fourier space (what a learned cosmological simulator is normally judged by, and what reaches scales far beyond
+the few interparticle spacings pair counting can afford): ``power_spectrum`` gives the matter power spectrum P(k) of
+a frame -- an exact integer mass assignment (``ops.mass_assign``), one ``torch.fft.rfftn`` in complex128 and shell sums
+in a fixed order (``ops.power_bins``) -- and, with a second set, the cross spectrum, the cross-correlation coefficient
+r(k) = P_ab / sqrt(P_aa P_bb) and the transfer function T(k) = sqrt(P_aa / P_bb); ``rollout_power_spectra`` does that
+for every selected frame of a rollout against the truth; ``spectra_from_sums`` is the host arithmetic behind both
+and ``default_k_edges`` the unit-wide bins centred on the integer frequencies.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -17,7 +25,7 @@ from typing import Dict, Optional, Sequence
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 def _radii(edges, box_size: float, who: str) -> torch.Tensor:
@@ -97,3 +105,164 @@ def rollout_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict
             "xi_pred": correlation_from_counts(counts[0], n, None, box_size, edges, True),
             "xi_true": correlation_from_counts(counts[1], n, None, box_size, edges, True),
             "xi_cross": correlation_from_counts(counts[2], n, n, box_size, edges, False)}
+
+
+def default_k_edges(mesh: int) -> torch.Tensor:
+    """``0.5 + arange(0, mesh // 2 + 1)``: unit-wide bins centred on the frequencies n = 1 .. mesh // 2, in units of the
+    fundamental frequency ``2 pi / L`` (float64)."""
+    mesh = ops.check_mesh(mesh, "default_k_edges")
+    return 0.5 + torch.arange(0, mesh // 2 + 1, dtype=torch.float64)
+
+
+def spectra_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: float, mesh: int, k_edges,
+                      subtract_shot_noise: bool = True) -> Dict:
+    """Spectra from the shell sums of ``ops.power_bins``, on the host in float64 (``modes [..., nb]`` int64, ``sums
+    [..., 4, nb]``; the results have the shape of ``modes``, on the CPU).  With ``L = box_size``, ``M = mesh``:
+
+    * ``k_lo``, ``k_hi`` ``[nb]``: the bin edges (the float32 values the kernel bins by) times ``2 pi / L``;
+      ``k_mean``: the mean ``|k|`` over the modes of each bin;
+    * ``power``: ``P = L^3 S_aa / modes / M^6``, minus the shot noise ``L^3 / n_a`` when ``subtract_shot_noise``;
+
+    and with a second set (``n_b`` is not None)
+
+    * ``power_b``: likewise from ``S_bb`` and ``n_b``;   ``cross``: ``L^3 S_ab / modes / M^6`` (no shot noise);
+    * ``r = cross / sqrt(P_aa P_bb)`` from the spectra BEFORE the shot-noise subtraction, so ``|r| <= 1`` by
+      Cauchy-Schwarz up to rounding;
+    * ``transfer = sqrt(power / power_b)`` from the spectra AFTER it: ``nan`` where the subtraction leaves a spectrum
+      negative (shot-noise dominated bins) or ``power_b`` zero.
+
+    A bin without modes gives ``nan`` everywhere."""
+    what = "spectra_from_sums"
+    mesh = ops.check_mesh(mesh, what)
+    box = float(box_size)
+    if not (box > 0.0 and math.isfinite(box)):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    k = torch.tensor(ops.check_power_edges(k_edges, what), dtype=torch.float64) * (2.0 * math.pi / box)
+    modes = torch.as_tensor(modes).detach().to(device="cpu", dtype=torch.int64)
+    sums = torch.as_tensor(sums).detach().to(device="cpu", dtype=torch.float64)
+    nb = k.numel() - 1
+    if modes.shape[-1] != nb or sums.shape[-2:] != (4, nb) or sums.shape[:-2] != modes.shape[:-1]:
+        raise ValueError(f"{what}: modes {tuple(modes.shape)} and sums {tuple(sums.shape)} do not fit {nb} bins")
+    count = modes.to(torch.float64)
+    count = torch.where(modes > 0, count, torch.full_like(count, float("nan")))
+    norm = box ** 3 / float(mesh) ** 6
+
+    def spectrum(row):
+        return norm * sums[..., row, :] / count
+
+    p_a = spectrum(0)
+    out = {"k_lo": k[:-1].clone(), "k_hi": k[1:].clone(), "k_mean": sums[..., 3, :] / count * (2.0 * math.pi / box),
+           "modes": modes, "power": p_a - box ** 3 / n_a if subtract_shot_noise else p_a}
+    if n_b is not None:
+        p_b, p_ab = spectrum(1), spectrum(2)
+        out["power_b"] = p_b - box ** 3 / n_b if subtract_shot_noise else p_b
+        out["cross"] = p_ab
+        out["r"] = p_ab / torch.sqrt(p_a * p_b)
+        out["transfer"] = torch.sqrt(out["power"] / out["power_b"])
+    return out
+
+
+def _frames3(pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: {name} must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    return pos if pos.dim() == 3 else pos.unsqueeze(0)
+
+
+def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int):
+    """``ops.power_bins`` of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b [F, N_b, 3]``):
+    device tensors ``modes [F, nb]``, ``sums [F, 4, nb]``.  Frames go through in chunks whose meshes fit the free
+    device memory: per frame and set ``8 M^3`` (the contrast) + ``16 M^2 (M/2 + 1)`` (its transform) + ``8 M^3`` (the
+    int64 mesh) bytes and as much again for the FFT's own scratch, and per frame the workspace of ``cgnn_power_bins``
+    (``nb * 64`` slices of four float64 sums and a count) and its outputs (``5 nb`` values)."""
+    from .training import free_device_bytes
+    n_frames, nb = pos_a.shape[0], len(k_edges) - 1
+    per_frame = (16 * mesh ** 3 + 16 * mesh * mesh * (mesh // 2 + 1)) * (1 if pos_b is None else 2) * 2 \
+        + nb * 64 * 5 * 8 + nb * 5 * 8
+    chunk = max(1, min(n_frames, free_device_bytes(pos_a.device) // per_frame))
+    plan = ops.PowerPlan.of(mesh, k_edges, pos_a.device)
+
+    def transform(pos):
+        grid = ops.mass_assign(pos, box_size, mesh, order)
+        delta = grid.to(torch.float64) * (mesh ** 3 / (pos.shape[1] * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
+        del grid
+        return torch.fft.rfftn(delta, dim=(-3, -2, -1))
+
+    modes, sums = [], []
+    for f0 in range(0, n_frames, chunk):
+        a = transform(pos_a[f0:f0 + chunk])
+        b = None if pos_b is None else transform(pos_b[f0:f0 + chunk])
+        m, s = ops.power_bins(a, mesh, order, k_edges, b, plan)
+        modes.append(m)
+        sums.append(s)
+    return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
+
+
+def _to_host(modes: torch.Tensor, sums: torch.Tensor):
+    """One transfer: the float64 sums travel as their bits among the integers."""
+    packed = torch.cat([modes.reshape(-1), sums.view(torch.int64).reshape(-1)]).cpu()
+    return packed[:modes.numel()].reshape(modes.shape), packed[modes.numel():].view(torch.float64).reshape(sums.shape)
+
+
+def power_spectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, pos_b: Optional[torch.Tensor] = None,
+                   order: int = 2, subtract_shot_noise: bool = True) -> Dict:
+    """The matter power spectrum of ``pos [N, 3]`` (or of every frame of ``[T, N, 3]``) on a ``mesh^3`` grid, deposited
+    with ``order`` (1 = NGP, 2 = CIC, 3 = TSC) and deconvolved by that window; with ``pos_b`` (``[N_b, 3]`` or ``[T, N_b,
+    3]``) also its spectrum and the cross spectrum of the two.  ``k_edges``: ``nb + 1`` bin edges in units of ``2 pi / L``
+    (default :func:`default_k_edges`).  Returns the dict of :func:`spectra_from_sums` (CPU, float64 / int64; ``[nb]`` or
+    ``[T, nb]``): ``k_lo``, ``k_hi``, ``k_mean``, ``modes``, ``power`` and with ``pos_b`` also ``power_b``, ``cross``,
+    ``r``, ``transfer``.  ``transfer`` may be ``nan`` (see there); an empty bin is ``nan``.  Aliasing is not corrected
+    beyond the window deconvolution: bins past half the Nyquist frequency are lifted by it.  Everything is computed on
+    the device of ``pos`` without a host synchronisation and comes back in one transfer."""
+    what = "power_spectrum"
+    mesh = ops.check_mesh(mesh, what)
+    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    frames_a = _frames3(pos, "pos", what)
+    frames_b = None if pos_b is None else _frames3(pos_b, "pos_b", what)
+    if frames_b is not None and (pos_b.dim() != pos.dim() or frames_b.shape[0] != frames_a.shape[0]):
+        raise ValueError(f"{what}: pos_b {tuple(pos_b.shape)} does not go with pos {tuple(pos.shape)}")
+    modes, sums = _to_host(*_shell_sums(frames_a, frames_b, box_size, mesh, k_edges, order))
+    if pos.dim() == 2:
+        modes, sums = modes[0], sums[0]
+    return spectra_from_sums(modes, sums, frames_a.shape[1], None if frames_b is None else frames_b.shape[1], box_size,
+                             mesh, k_edges, subtract_shot_noise)
+
+
+def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                          mesh: int, k_edges=None, frames: Optional[Sequence[int]] = None, order: int = 2) -> Dict:
+    """Fourier-space statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns
+    (``Coordinates [T, N, 3]``).  ``frames``: the frame numbers to judge (default: every frame both hold).  Per selected
+    frame (``[F, nb]``, CPU, float64):
+
+    * ``power_pred``, ``power_true``: the shot-noise-subtracted power spectra of the predicted and the true frame;
+    * ``cross``: their cross spectrum;  ``r``: the cross-correlation coefficient (``|r| <= 1``);
+    * ``transfer``: ``sqrt(power_pred / power_true)``, ``nan`` where a subtracted spectrum is negative,
+
+    plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean`` (``[nb]``) and ``modes`` (``[nb]``, int64).  Everything is computed on
+    the device of the rollout without a host synchronisation per frame; the results come back in one transfer."""
+    what = "rollout_power_spectra"
+    mesh = ops.check_mesh(mesh, what)
+    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    tc = ground_truth["Coordinates"].to(dev)
+    avail = min(len(pc), len(tc))
+    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
+    if not sel or min(sel) < 0 or max(sel) >= avail:
+        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
+    if pc.shape[1:] != tc.shape[1:]:
+        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
+    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
+    pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
+    _frames3(pc, "Coordinates", what)
+    n = pc.shape[1]
+    modes, sums = _to_host(*_shell_sums(pc, tc, box_size, mesh, k_edges, order))
+    sp = spectra_from_sums(modes, sums, n, n, box_size, mesh, k_edges, True)
+    return {"frames": sel, "k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "k_mean": sp["k_mean"][0].clone(),
+            "modes": sp["modes"][0].clone(), "power_pred": sp["power"], "power_true": sp["power_b"],
+            "cross": sp["cross"], "r": sp["r"], "transfer": sp["transfer"]}

@@ -572,6 +572,52 @@ int cgnn_frame_errors(const float* pred_pos, const float* true_pos, const float*
                       int64_t frames, int64_t n, float box_size, double* out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- judging a rollout in Fourier space: mass assignment and shell sums of the matter power spectrum ----------------
+ * cgnn_mass_assign deposits pos [frames, n, 3] (positions in [0, box_size]) onto a periodic mesh^3 grid per frame,
+ * out (device, int64 [frames, mesh, mesh, mesh], cell (cx, cy, cz) at (cx mesh + cy) mesh + cz), overwritten.
+ * order: 1 = NGP, 2 = CIC, 3 = TSC.  s = fl32(fl32(mesh) / fl32(box_size)), computed once on the host; per axis
+ * u = fl32(p * s) and integer weights that sum to Q = 8192 (2^13):
+ *   NGP  j = floor(fl32(u + 0.5f)):  Q on cell j
+ *   CIC  i = floor(u), f = fl32(u - i), a1 = (int)rintf(f * Q):  Q - a1 on cell i, a1 on cell i + 1
+ *   TSC  j = floor(fl32(u + 0.5f)), d = fl32(u - j), tm = fl32(0.5f - d), tp = fl32(0.5f + d),
+ *        am = (int)rintf(fl32(fl32(tm * tm) * 0.5f) * Q), ap likewise from tp:  am on j - 1, Q - am - ap on j, ap on j + 1
+ * one float32 rounding per operation, no FMA, rint to nearest even.  Cell indices wrap with a true modulo (p ==
+ * box_size lands in cell 0; nothing is clamped).  A particle adds the product of its three axis weights to each of its
+ * order^3 cells: exactly Q^3 = 2^39 per particle, so a frame's mesh sums to n 2^39.  Integer sums (64-bit integer
+ * atomics, no float atomics): the mesh does not depend on any order, is the same bits on every run and equals the
+ * numpy restatement exactly.  One launch sequence for all frames (whole frames per launch, 2^24 threads at most), no
+ * host synchronisation.
+ * CGNN_ERR_INVALID_ARG unless 2 <= mesh <= 512, 1 <= order <= 3, box_size > 0; n > 2^24 (n 2^39 must stay inside int64):
+ * CGNN_ERR_UNSUPPORTED.  A position outside [0, box_size] is outside the contract; it never writes outside the mesh.
+ *
+ * A mode of the real FFT [mesh, mesh, mesh/2 + 1] of such a mesh has signed frequencies nx, ny in (-mesh/2, mesh/2]
+ * and nz in [0, mesh/2]; n2 = nx^2 + ny^2 + nz^2 in integers.  k_edges (HOST memory, num_bins + 1 floats, in units of
+ * the fundamental frequency 2 pi / box_size): finite, non-negative, strictly ascending, 1 <= num_bins <= 256.  With
+ * e2[i] = fl32(k_edges[i] * k_edges[i]) the mode is in bin i iff e2[i] <= (float)n2 < e2[i + 1] (no sqrt); n2 == 0 is
+ * never counted.  cgnn_power_bin_ids writes that bin, or -1, for every mode: ids (device, int32 [mesh^2 (mesh/2 + 1)]).
+ *
+ * cgnn_power_bins: per frame and bin, over the modes of the bin, with the Hermitian weight h = 1 on the planes that are
+ * their own conjugates (nz == 0, and nz == mesh/2 when mesh is even) and h = 2 on every other plane, and
+ * W2 = (sinc(pi nx/mesh) sinc(pi ny/mesh) sinc(pi nz/mesh))^(2 order) in float64 (order 0..3; 0: W2 = 1):
+ *   modes [frames, num_bins] int64       sum of h
+ *   sums  [frames, 4, num_bins] double   row 0: sum h |a|^2 / W2    row 1: sum h |b|^2 / W2
+ *                                        row 2: sum h Re(a conj b) / W2    row 3: sum h sqrt(n2)
+ * a, b (device, complex128 as (re, im) pairs, [frames, mesh, mesh, mesh/2 + 1], 16-byte aligned); b may be NULL, then
+ * rows 1 and 2 are not written.  perm (device, int32 [mesh^2 (mesh/2 + 1)]): the mode indices sorted stably by their
+ * cgnn_power_bin_ids value; bin_start (device, int32 [num_bins + 1]): bin i owns perm[bin_start[i] .. bin_start[i+1]).
+ * Two stages whose float64 additions have fixed places (a bin's run cut into 64 equal slices; per slice each thread
+ * its strided share in index order, a tree over the threads; the slices of a bin added in slice order), no float
+ * atomics: two runs give the same bits.  All frames in one launch sequence (whole frames per launch, 2^24 threads at
+ * most, so any number of frames the workspace holds is legal), no host synchronisation.
+ * Workspace: cgnn_power_bins_workspace_bytes(frames, num_bins), 16-byte aligned. */
+int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
+                     int64_t* out, void* stream);
+int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream);
+size_t cgnn_power_bins_workspace_bytes(int64_t frames, int32_t num_bins);
+int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t mesh, int32_t order, const int32_t* perm,
+                    const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes

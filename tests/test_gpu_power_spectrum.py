@@ -1,0 +1,354 @@
+"""GPU: ``ops.mass_assign`` (``cgnn_mass_assign``) and ``ops.PowerPlan`` (``cgnn_power_bin_ids``) against the numpy
+restatement of their contracts (tests/power_spectrum_checks.py): integers, so every case is ``torch.equal``.
+``ops.power_bins`` (``cgnn_power_bins``) on ``torch.fft.rfftn`` of the restated density contrast against numpy float64,
+and ``statistics.power_spectrum`` / ``rollout_power_spectra`` on a synthetic trajectory.
+
+The float64 tolerance.  A sum is compared within 1e-9 of the largest bin of its row.  The roundoff of a float64 FFT of
+2^15 points is about 1e-14 of the rms amplitude, and the two summation orders differ by less; one mis-weighted plane
+moves a bin by about 1 / modes of its value, at least 1e-4.  1e-9 separates the two by five orders on either side."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import power_spectrum_checks as psc
+from cosmology_gnn_simulation_amd import _lib, ops, statistics, training
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+BOX = 25.0
+TOL = 1e-9
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _grid(x, box, mesh, order, **kw):
+    return ops.mass_assign(_dev(x), box, mesh, order, **kw)
+
+
+def _want(grid):
+    return torch.from_numpy(grid)
+
+
+# ---- mass assignment ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("mesh", [2, 4, 5, 16, 32])
+@pytest.mark.parametrize("n", [1, 7, 1000, 8192])
+def test_mass_assign_equals_the_restatement(n, mesh, order):
+    x = psc.uniform(n, seed=n + mesh, box=BOX)
+    got = _grid(x, BOX, mesh, order)
+    assert got.dtype == torch.int64 and got.shape == (mesh, mesh, mesh)
+    assert torch.equal(got.cpu(), _want(psc.mass_assign(x, BOX, mesh, order)))
+    assert int(got.sum()) == n * _lib.MASS_ASSIGN_Q ** 3
+    assert torch.equal(_grid(x, BOX, mesh, order), got)                    # a repeat gives the same bits
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("mesh,box", [(16, 16.0), (5, 5.0), (16, BOX), (5, BOX)])
+def test_mass_assign_on_box_faces_and_cell_boundaries(mesh, box, order):
+    """Coordinates of exactly 0 and L, and u on every integer and half-integer (exactly so when s = M / L = 1; with
+    L = 25 as near as float32 comes): where floor, rint's ties and the wrap decide."""
+    cell = np.float32(box) / np.float32(mesh)
+    ticks = (np.arange(2 * mesh + 1, dtype=np.float32) * np.float32(0.5) * cell).astype(np.float32)
+    ticks[-1] = np.float32(box)
+    x = np.stack(np.meshgrid(ticks, ticks[::3], ticks[::5], indexing="ij"), axis=-1).reshape(-1, 3)
+    x = np.concatenate([x, x[:, [2, 0, 1]], x[:, [1, 2, 0]]]).astype(np.float32)
+    assert (x == 0).any() and (x == np.float32(box)).any() and x.max() <= np.float32(box)
+    got = _grid(x, box, mesh, order, check_bounds=True)
+    assert torch.equal(got.cpu(), _want(psc.mass_assign(x, box, mesh, order)))
+    assert int(got.sum()) == x.shape[0] * 2 ** 39 and int(got.min()) >= 0
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_mass_assign_of_4096_particles_in_one_cell(order):
+    """Every particle adds to the same few addresses: the atomics contend, the integers do not care.  u lies in [7, 8)
+    on every axis: NGP and CIC reach two cells per axis (7 and 8), TSC four (6 .. 9)."""
+    rng = np.random.default_rng(11)
+    x = ((np.float32(7.0) + rng.random((4096, 3), dtype=np.float32)) * np.float32(BOX / 16)).astype(np.float32)
+    got = _grid(x, BOX, 16, order)
+    assert torch.equal(got.cpu(), _want(psc.mass_assign(x, BOX, 16, order)))
+    assert int((got != 0).sum()) <= {1: 2, 2: 2, 3: 4}[order] ** 3 and int(got.sum()) == 4096 * 2 ** 39
+
+
+def test_mass_assign_of_frames_is_one_call_per_frame():
+    frames = np.stack([psc.uniform(1000, seed=20 + t, box=BOX) for t in range(3)])
+    got = ops.mass_assign(_dev(frames), BOX, 9, 3)
+    assert got.shape == (3, 9, 9, 9)
+    assert torch.equal(got, torch.stack([ops.mass_assign(_dev(frames[t]), BOX, 9, 3) for t in range(3)]))
+    assert torch.equal(got.cpu(), _want(psc.mass_assign(frames, BOX, 9, 3)))
+    assert torch.equal(ops.mass_assign(_dev(frames), BOX, 9, 3), got)
+
+
+def test_mass_assign_of_more_frames_than_one_launch_takes():
+    """2100 frames of 8192 particles are 2^24.04 threads: the entry splits them into launches of whole frames."""
+    base = _dev(np.stack([psc.uniform(8192, seed=30 + t, box=BOX) for t in range(3)]))
+    want = ops.mass_assign(base, BOX, 2, 1)
+    got = ops.mass_assign(base.repeat(700, 1, 1), BOX, 2, 1)
+    assert got.shape == (2100, 2, 2, 2) and torch.equal(got, want.repeat(700, 1, 1, 1))
+    assert torch.equal(got.sum(dim=(1, 2, 3)), torch.full((2100,), 8192 * 2 ** 39, device=DEV))
+
+
+def test_the_c_entry_refuses_by_itself_before_any_launch():
+    """With real buffers of the sizes named: were a refusal ever to come after a launch, nothing would fault."""
+    lib = _lib.load()
+    pos = torch.zeros(((1 << 24) + 1, 3), device=DEV)
+    out = torch.full((16, 16, 16), -1, dtype=torch.int64, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    for n, box, mesh, order in ((10, 1.0, 1, 2), (10, 1.0, 513, 2), (10, 1.0, 16, 0), (10, 1.0, 16, 4),
+                                ((1 << 24) + 1, 1.0, 16, 2), (10, 0.0, 16, 2), (10, -1.0, 16, 2), (0, 1.0, 16, 2)):
+        assert lib.cgnn_mass_assign(pos.data_ptr(), 1, n, box, mesh, order, out.data_ptr(), st) != 0, (n, box, mesh, order)
+    assert bool((out == -1).all())
+    assert lib.cgnn_mass_assign(pos.data_ptr(), 1, 10, 1.0, 16, 2, out.data_ptr(), st) == 0
+    assert int(out[0, 0, 0]) == 10 * 2 ** 39
+
+
+def test_mass_assign_check_bounds():
+    x = psc.with_special_positions(psc.uniform(100, 1, BOX), BOX)
+    ops.mass_assign(_dev(x), BOX, 8, check_bounds=True)                     # exactly 0 and exactly L are inside
+    for bad in (-1e-3, BOX * 1.0001, float("nan"), float("inf")):
+        y = x.copy()
+        y[50, 1] = bad
+        with pytest.raises(ValueError):
+            ops.mass_assign(_dev(y), BOX, 8, check_bounds=True)
+
+
+# ---- binning -----------------------------------------------------------------------------------------------------------
+
+def _edge_sets(mesh):
+    top = mesh * math.sqrt(3) / 2 + 1
+    return {"one": np.array([0.0, top]), "eight": np.linspace(0.5, mesh / 2 + 0.5, 9),
+            "most": np.linspace(0.0, top, 257), "on_integers": np.array([1.0, 2.0, 3.0]),
+            "default": psc.default_k_edges(mesh)}
+
+
+@pytest.mark.parametrize("which", ["one", "eight", "most", "on_integers", "default"])
+@pytest.mark.parametrize("mesh", [4, 5, 9, 16])
+def test_bin_ids_and_plan_equal_the_restatement(mesh, which):
+    edges = _edge_sets(mesh)[which]
+    plan = ops.PowerPlan(mesh, edges, DEV)
+    want = psc.bin_ids(mesh, edges)
+    ids = ops.power_bin_ids(mesh, edges, DEV)
+    assert ids.dtype == torch.int32 and torch.equal(ids.cpu(), torch.from_numpy(want))
+    flat = want.reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    assert torch.equal(plan.perm.cpu(), torch.from_numpy(order.astype(np.int32)))
+    assert plan.bin_start.tolist() == np.searchsorted(flat[order], np.arange(len(edges))).tolist()
+    if which == "on_integers":
+        assert int(ids[1, 0, 0]) == 0 and int(ids[2, 0, 0]) == 1      # an edge on n belongs to the upper bin
+    assert ops.PowerPlan.of(mesh, edges, DEV) is ops.PowerPlan.of(mesh, edges, DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _contrasts(mesh, n=3000):
+    """Two frames of two correlated sets: the restated density contrast, float64 [2, M, M, M] each."""
+    a = np.stack([psc.uniform(n, seed=40 + t, box=BOX) for t in range(2)])
+    shift = np.random.default_rng(50).normal(0.0, 0.3 * BOX / mesh, a.shape).astype(np.float32)
+    b = np.mod(a + shift, np.float32(BOX)).astype(np.float32)
+    return tuple(psc.density_contrast(psc.mass_assign(x, BOX, mesh, 2), n) for x in (a, b))
+
+
+def _close(got, want, what):
+    got, want = got.cpu().numpy(), np.asarray(want)
+    for row in range(want.shape[-2]):
+        scale = np.nanmax(np.abs(want[..., row, :]))
+        err = np.abs(got[..., row, :] - want[..., row, :]).max()
+        print(f"{what} row {row}: largest error {err / scale:.2e} of the largest bin")
+        assert err <= TOL * scale, (what, row, err / scale)
+
+
+@pytest.mark.parametrize("order", [0, 2])
+@pytest.mark.parametrize("mesh", [5, 9, 16, 32])
+def test_power_bins_equal_numpy_float64_and_repeat_bit_for_bit(mesh, order):
+    da, db = _contrasts(mesh)
+    ak, bk = (torch.fft.rfftn(_dev(d), dim=(-3, -2, -1)) for d in (da, db))
+    assert ak.dtype == torch.complex128 and ak.shape == (2, mesh, mesh, mesh // 2 + 1)
+    for edges in (psc.default_k_edges(mesh), np.array([0.0, mesh])):        # the second: one bin with nearly every mode
+        want = [psc.power_bins(np.fft.rfftn(da[t]), np.fft.rfftn(db[t]), mesh, order, edges) for t in range(2)]
+        modes, sums = ops.power_bins(ak, mesh, order, edges, bk)
+        assert modes.dtype == torch.int64 and modes.shape == (2, len(edges) - 1) and sums.shape == (2, 4, len(edges) - 1)
+        assert torch.equal(modes.cpu(), torch.from_numpy(np.stack([w[0] for w in want])))
+        _close(sums, np.stack([w[1] for w in want]), f"cross M={mesh} order={order}")
+        again = ops.power_bins(ak, mesh, order, edges, bk)
+        assert torch.equal(again[0], modes) and torch.equal(again[1], sums)
+        # auto: rows 1 and 2 are not written (nan); rows 0 and 3 are the cross call's bits
+        m1, s1 = ops.power_bins(ak, mesh, order, edges)
+        assert torch.equal(m1, modes) and torch.equal(s1[:, [0, 3]], sums[:, [0, 3]]) and bool(s1[:, 1:3].isnan().all())
+        # one frame alone: the same bits as its slice of the batch
+        m0, s0 = ops.power_bins(ak[1], mesh, order, edges, bk[1])
+        assert m0.shape == (len(edges) - 1,) and torch.equal(m0, modes[1]) and torch.equal(s0, sums[1])
+        # cross of a set with itself: the three spectra are the same bits
+        _, same = ops.power_bins(ak[0], mesh, order, edges, ak[0])
+        assert torch.equal(same[0], same[1]) and torch.equal(same[0], same[2])
+
+
+def test_power_bins_of_more_frames_than_one_launch_takes():
+    """256 bins are 2^22 threads per frame: four frames fill a launch, ten take three.  Each frame's sums are the bits
+    of the same frame summed alone."""
+    da, db = _contrasts(5)
+    ak = torch.fft.rfftn(_dev(np.concatenate([da, db] * 3)[:10]), dim=(-3, -2, -1))
+    edges = np.linspace(0.0, 5.5, 257)
+    modes, sums = ops.power_bins(ak, 5, 2, edges, ak.flip(0))
+    for t in (0, 3, 4, 7, 8, 9):
+        m1, s1 = ops.power_bins(ak[t], 5, 2, edges, ak[9 - t])
+        assert torch.equal(modes[t], m1) and torch.equal(sums[t], s1)
+    assert int(modes[0].sum()) == 5 ** 3 - 1
+
+
+def test_power_bins_refuses_a_plan_of_another_mesh_or_other_edges():
+    ak = torch.fft.rfftn(_dev(_contrasts(16)[0][0]))
+    edges = psc.default_k_edges(16)
+    ops.power_bins(ak, 16, 2, edges, plan=ops.PowerPlan(16, edges, DEV))
+    with pytest.raises(_lib.CgnnError):
+        ops.power_bins(ak, 16, 2, edges, plan=ops.PowerPlan(16, edges[:-1], DEV))
+    with pytest.raises(_lib.CgnnError):
+        ops.power_bins(ak, 16, 2, psc.default_k_edges(8), plan=ops.PowerPlan(8, psc.default_k_edges(8), DEV))
+    with pytest.raises(_lib.CgnnError):
+        ops.power_bins(ak.to(torch.complex64), 16, 2, edges)
+
+
+# ---- end to end --------------------------------------------------------------------------------------------------------
+
+N, MESH, FRAMES = 1000, 16, 4
+
+
+@functools.lru_cache(maxsize=None)
+def _trajectory():
+    """A synthetic 4-frame trajectory: the truth drifts, the prediction strays from it by a growing random error."""
+    rng = np.random.default_rng(60)
+    base = psc.uniform(N, seed=61, box=BOX)
+    true = np.stack([np.mod(base + np.float32(0.2 * t), np.float32(BOX)) for t in range(FRAMES)]).astype(np.float32)
+    pred = np.mod(true + rng.normal(0.0, 0.3, true.shape).astype(np.float32) * np.arange(FRAMES, dtype=np.float32)[:, None, None],
+                  np.float32(BOX)).astype(np.float32)
+    return pred, true
+
+
+@functools.lru_cache(maxsize=None)
+def _restated_spectra(order, subtract):
+    """Per frame, in numpy alone (psc.spectra writes P, r and T out from their definitions): the spectra, the mode
+    counts, and the unsubtracted auto spectra "raw_a" / "raw_b" the tolerances below are derived from."""
+    pred, true = _trajectory()
+    edges = psc.default_k_edges(MESH)
+    out = []
+    for t in range(FRAMES):
+        a = np.fft.rfftn(psc.density_contrast(psc.mass_assign(pred[t], BOX, MESH, order), N))
+        b = np.fft.rfftn(psc.density_contrast(psc.mass_assign(true[t], BOX, MESH, order), N))
+        modes, sums = psc.power_bins(a, b, MESH, order, edges)
+        sp = psc.spectra(modes, sums, N, N, BOX, MESH, subtract)
+        raw = psc.spectra(modes, sums, N, N, BOX, MESH, False)
+        sp.update(modes=modes, raw_a=raw["power"], raw_b=raw["power_b"],
+                  k_lo=edges[:-1] * (2 * math.pi / BOX), k_hi=edges[1:] * (2 * math.pi / BOX))
+        out.append(sp)
+    return out
+
+
+def _scale(want):
+    return max(float(max(w["raw_a"].max(), w["raw_b"].max())) for w in want)
+
+
+def _spectra_close(got, want, scale):
+    """Against the numpy definitions.  Every spectrum is held to eps = TOL times the largest unsubtracted bin, what
+    the sums are held to.  r and T are quotients of such spectra, so their bounds follow by first-order propagation:
+        |dr| <= eps (1 / sqrt(Pa Pb) + |r| / 2 (1 / Pa + 1 / Pb))       (unsubtracted Pa, Pb)
+        |dT| <= T / 2 eps (1 / |pa| + 1 / |pb|)                        (subtracted pa, pb)
+    T is compared (and must be nan exactly where numpy's is) in the bins where both subtracted spectra are at least
+    1000 eps from zero: nearer than that, eps itself decides the sign."""
+    eps = TOL * scale
+    g = {k: v.numpy() for k, v in got.items()}
+    for key in ("power", "power_b", "cross"):
+        assert np.abs(g[key] - want[key]).max() <= eps, key
+    assert (g["modes"] == want["modes"]).all()
+    for key in ("k_lo", "k_hi", "k_mean"):
+        np.testing.assert_allclose(g[key], want[key], rtol=1e-12)
+    pa, pb = want["raw_a"], want["raw_b"]
+    bound_r = eps * (1 / np.sqrt(pa * pb) + np.abs(want["r"]) / 2 * (1 / pa + 1 / pb)) + 1e-15
+    assert (np.abs(g["r"] - want["r"]) <= bound_r).all()
+    assert (np.abs(g["r"]) <= 1.0).all()
+    sa, sb = np.abs(want["power"]), np.abs(want["power_b"])
+    firm = np.minimum(sa, sb) >= 1000 * eps
+    assert firm.sum() >= firm.size - 1
+    t_got, t_want = g["transfer"][firm], want["transfer"][firm]
+    assert (np.isnan(t_got) == np.isnan(t_want)).all()
+    ok = ~np.isnan(t_want)
+    bound_t = t_want[ok] / 2 * eps * (1 / sa[firm][ok] + 1 / sb[firm][ok]) + 1e-15 * t_want[ok]
+    assert (np.abs(t_got[ok] - t_want[ok]) <= bound_t).all()
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_power_spectrum_equals_the_restatement(order):
+    pred, true = _trajectory()
+    want = _restated_spectra(order, True)
+    scale = _scale(want)
+    for t in (0, 3):
+        got = statistics.power_spectrum(_dev(pred[t]), BOX, MESH, pos_b=_dev(true[t]), order=order)
+        assert all(not v.is_cuda and v.shape == (MESH // 2,) for v in got.values())
+        _spectra_close(got, want[t], scale)
+    auto = statistics.power_spectrum(_dev(pred[3]), BOX, MESH, order=order, subtract_shot_noise=False)
+    assert set(auto) == {"k_lo", "k_hi", "k_mean", "modes", "power"}
+    raw = _restated_spectra(order, False)[3]
+    assert np.abs(auto["power"].numpy() - raw["power"]).max() <= TOL * scale
+    frames = statistics.power_spectrum(_dev(pred), BOX, MESH, pos_b=_dev(true), order=order)
+    assert frames["power"].shape == (FRAMES, MESH // 2)
+    for t in range(FRAMES):
+        _spectra_close({k: (v if k in ("k_lo", "k_hi") else v[t]) for k, v in frames.items()}, want[t], scale)
+    # frame 0: the prediction IS the truth
+    assert torch.equal(frames["power"][0], frames["power_b"][0])
+    assert float((frames["r"][0] - 1.0).abs().max()) <= 1e-15
+
+
+def test_rollout_power_spectra_match_single_calls_and_chunked_runs(monkeypatch):
+    pred, true = _trajectory()
+    data = {"Coordinates": _dev(pred), "InternalEnergy": torch.zeros(FRAMES, N, device=DEV)}
+    truth = {"Coordinates": torch.from_numpy(true), "InternalEnergy": torch.zeros(FRAMES, N)}
+    stats = statistics.rollout_power_spectra(data, truth, BOX, MESH)
+    assert stats["frames"] == list(range(FRAMES))
+    want = _restated_spectra(2, True)
+    scale = _scale(want)
+    assert stats["modes"].shape == (MESH // 2,) and (stats["modes"].numpy() == want[0]["modes"]).all()
+    for t in range(FRAMES):
+        one = statistics.power_spectrum(data["Coordinates"][t], BOX, MESH, pos_b=_dev(true[t]))
+        for key, name in (("power_pred", "power"), ("power_true", "power_b"), ("cross", "cross")):
+            assert stats[key].shape == (FRAMES, MESH // 2) and stats[key].dtype == torch.float64 and not stats[key].is_cuda
+            assert float((stats[key][t] - one[name]).abs().max()) <= TOL * scale
+        _spectra_close({"power": stats["power_pred"][t], "power_b": stats["power_true"][t], "cross": stats["cross"][t],
+                        "r": stats["r"][t], "transfer": stats["transfer"][t], "modes": stats["modes"],
+                        "k_lo": stats["k_lo"], "k_hi": stats["k_hi"], "k_mean": stats["k_mean"]}, want[t], scale)
+    assert bool((stats["r"].abs() <= 1.0).all())
+    assert bool((stats["r"][1:, 0] > stats["r"][1:, -1]).all())            # a random error decorrelates small scales first
+    last = statistics.rollout_power_spectra(data, truth, BOX, MESH, frames=[3, 1])
+    assert last["frames"] == [3, 1] and last["power_pred"].shape == (2, MESH // 2)
+    assert float((last["power_pred"] - stats["power_pred"][[3, 1]]).abs().max()) <= TOL * scale
+    with pytest.raises(ValueError):
+        statistics.rollout_power_spectra(data, truth, BOX, MESH, frames=[FRAMES])
+    # one frame per chunk (no room for more): the deposit is exact, the transform and the sums are per frame
+    monkeypatch.setattr(training, "free_device_bytes", lambda device: 1)
+    chunked = statistics.rollout_power_spectra(data, truth, BOX, MESH)
+    for key in ("power_pred", "power_true", "cross"):
+        assert float((chunked[key] - stats[key]).abs().max()) <= TOL * scale
+    assert torch.equal(chunked["modes"], stats["modes"])
+
+
+def test_ops_make_no_host_synchronisation():
+    x = _dev(psc.uniform(N, 70, BOX)).view(1, N, 3)
+    edges = psc.default_k_edges(MESH)
+
+    def run():
+        grid = ops.mass_assign(x, BOX, MESH, 2)
+        delta = grid.to(torch.float64) * (MESH ** 3 / (N * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
+        ak = torch.fft.rfftn(delta, dim=(-3, -2, -1))
+        return grid, ops.power_bins(ak, MESH, 2, edges, ak)
+
+    warm = run()                                        # builds the plan, loads the FFT
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        grid, (modes, sums) = run()
+        plan = ops.PowerPlan(MESH, edges, DEV)          # building a plan does not wait for the device either
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert torch.equal(grid, warm[0]) and torch.equal(modes, warm[1][0]) and torch.equal(sums, warm[1][1])
+    assert torch.equal(plan.perm, ops.PowerPlan.of(MESH, edges, DEV).perm)
