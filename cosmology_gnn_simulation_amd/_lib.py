@@ -50,12 +50,15 @@ EXPORTS = (
     "cgnn_knn_batched_workspace_bytes", "cgnn_knn_periodic_batched", "cgnn_knn_batched_sorted_order",
     "cgnn_pair_counts_workspace_bytes", "cgnn_pair_counts", "cgnn_frame_errors_workspace_bytes", "cgnn_frame_errors",
     "cgnn_mass_assign", "cgnn_power_bin_ids", "cgnn_power_bins_workspace_bytes", "cgnn_power_bins",
+    "cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
 POWER_MAX_BINS = 256          # CGNN_PB_MAX_BINS
+FOF_MAX_BINS = 256            # CGNN_FOF_MAX_BINS in csrc/fof.hip
+FOF_DISP_UNITS = 1 << 30      # cgnn_fof_catalogue: disp counts displacements in box_size / 2^30
 KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -149,6 +152,10 @@ def load() -> C.CDLL:
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]
     lib.cgnn_mass_assign.argtypes = [vp, i64, i64, f32, i32, i32, vp, vp]
+    lib.cgnn_fof_labels_workspace_bytes.restype = sz
+    lib.cgnn_fof_labels_workspace_bytes.argtypes = [i64]
+    lib.cgnn_fof_labels.argtypes = [vp, i64, f32, f32, vp, vp, sz, vp]
+    lib.cgnn_fof_catalogue.argtypes = [vp, vp, i64, f32, vp, vp, C.POINTER(i32), i32, vp, vp]   # size_edges: host memory
     lib.cgnn_power_bin_ids.argtypes = [i32, C.POINTER(f32), i32, vp, vp]                            # k_edges: host memory
     lib.cgnn_power_bins_workspace_bytes.restype = sz
     lib.cgnn_power_bins_workspace_bytes.argtypes = [i64, i32]

@@ -1,0 +1,458 @@
+// cgnn_fof_labels: friends-of-friends groups of one frame in a periodic box (the connected components of "closer than the
+// linking length"), and cgnn_fof_catalogue: their sizes, displacement sums and mass function in exact integers.  With
+// pair_counts.hip and power_spectrum.hip they judge a rollout on the device: the halo mass function tells whether a
+// predicted frame collapses the right number of bound objects of each size, which no two-point statistic can.
+//
+// Linking contract (include/cgnn.h; tests/fof_checks.py restates it in numpy).  d2(i, j) is the float32 minimum-image
+// squared distance of cgnn_pair_counts, per axis
+//     d = fl32(b - a);   d > half ? fl32(d - L) : d < -half ? fl32(d + L) : d        half = fl32(0.5f * L)
+//     d2 = fl32(fl32(fl32(dx dx) + fl32(dy dy)) + fl32(dz dz))
+// one rounding per operation, nothing contracted (the Makefile compiles this file with -ffp-contract=off, as it does
+// pair_counts.hip, and for the same reason); with l2 = fl32(l l) particles i != j are linked iff d2 < l2, strictly: the
+// links are the pairs cgnn_pair_counts counts for the edges [0, l].  labels[i] is the smallest particle index of i's
+// connected component.
+//
+// Grid.  The particles are sorted into the Morton cell grid of cell_grid.hpp with G cells per axis of side h = L / G,
+// G the largest count with
+//     h >= l (1 + 1e-5) + 2e-5 L
+// (the margin derived in pair_counts.hip: two linked particles then lie in the same cell or in periodically adjacent
+// cells), capped so that G^3 <= CGNN_FOF_CELLS_PER_PARTICLE N and G <= 512 (spread3 has 10 bits).  The cap is the pair
+// counter's, G^3 <= N: at the conventional 0.2 mean spacings it decides, and leaves cells five linking lengths wide.  A
+// finer cap, G^3 <= 8 N, halves the side and cuts the distance evaluations eightfold where the particles are dense,
+// but it was measured not to pay (scripts/time_fof.py, 1 M particles; DESIGN.md, the friends-of-friends section): with
+// eight cells per particle nearly every work item holds one query, and what an item costs before its first distance is
+// the time.  The grid only proposes candidates: the contract alone decides a link.  When G <= 3 all G cells of an axis
+// are walked once (c - 1 and c + 1 wrap onto each other or onto c).
+//
+// Walk (fof_walk_kernel), as pc_walk_kernel: a work item is up to CGNN_FOF_QCHUNK queries of one cell, staged in LDS
+// (the items are numbered by a scan of ceil(count / QCHUNK) over the cells and listed by fof_items_kernel, all on the
+// device: no host synchronisation); a persistent workgroup strides over the items, lists the at most 27 partner
+// ranges of the neighbourhood and runs the concatenated candidates through in tiles of one candidate per lane against
+// every staged query.  A linked pair is met twice, once from each side; the side whose candidate has the smaller
+// original index (carried in .w of the sorted float4) calls unite, so every link is united exactly once and no
+// particle with itself.
+//
+// Union-find over parent[n] (the labels array itself, over ORIGINAL indices), lock-free: no locks, no spin-waits.
+//   find(x)      follows parent until parent[x] == x.
+//   unite(a, b)  finds both roots, and hooks the LARGER root under the smaller with atomicCAS(&parent[big], big, small);
+//                when the CAS loses it goes on from the value it saw.
+// Invariants that bound every loop:
+//   (1) parent[x] <= x always.  It starts as x; a CAS writes small < big; path halving writes an ancestor, which is
+//       smaller by induction.  So indices fall strictly along a chain and find takes at most as many steps as there
+//       are indices; no cycle can form.
+//   (2) A CAS only ever replaces a root's self-pointer (it expects parent[big] == big), by a smaller index of a particle
+//       linked to its tree.  A particle that has stopped being a root never becomes one again, and every value parent[x]
+//       ever held is an ancestor of x from then on: trees only merge.
+//   (3) A failed CAS means parent[big] was changed by another thread's successful CAS: that thread made progress, and
+//       there are at most n - 1 successful hooks in all, so the retry loop is lock-free and finite.
+// Path halving inside find (parent[x] = parent[parent[x]]) writes an ancestor of a non-root, which no CAS targets:
+// both invariants survive, in whatever order racing halvings land.  Every access to parent inside the walk is an
+// agent-scope atomic (relaxed): the compiler may not hoist or cache them, and the L2s of the chip's dies are not coherent
+// with each other for plain accesses.  A read that is late all the same returns a former ancestor, which (2) makes
+// harmless: find may return a particle that is no longer a root, and the CAS, which is decided at the memory side,
+// then fails and the loop goes on.  unite returns only when both sides have one root or its own CAS has joined them.
+// Because larger always hooks under smaller, the root of a finished tree is the minimum of its component: the last
+// kernel writes labels[i] = find(i) (without halving: see fof_labels_kernel), the same on every run however the threads
+// raced.
+//
+// Catalogue.  size[r] and disp[r] are integer sums over the members of root r (32- and 64-bit integer atomics; the
+// result does not depend on any order), q = llrint((double)d * scale) per axis of the folded float32 displacement from
+// the root, scale = 2^30 / (double)L; |q| <= 2^29 and fewer than 2^31 members keep the int64 sums from overflowing.
+// A wave sums its members per root before it touches memory (fof_members_kernel).
+// The mass function bins the non-zero sizes in LDS per workgroup and adds each non-empty bin once.
+#include <math.h>
+
+#include "cgnn_common.hpp"
+#include "scan.hpp"
+#include "cell_grid.hpp"
+
+#define CGNN_FOF_QCHUNK 256             // queries per work item = threads per workgroup = candidates per tile
+#define CGNN_FOF_RANGES 27
+#define CGNN_FOF_MAX_BLOCKS 2048
+#define CGNN_FOF_MAX_BINS 256
+#ifndef CGNN_FOF_CELLS_PER_PARTICLE
+#define CGNN_FOF_CELLS_PER_PARTICLE 1   // the cap G^3 <= N (see the header; a build flag, for timing another cap)
+#endif
+#define CGNN_FOF_MAX_G 512
+
+namespace cgnn {
+
+// cells per axis for n particles and a linking length `reach` (see the header); reach < 0: the cap alone
+static int fof_cells_per_axis(int64_t n, float box, float reach) {
+    int cap = 1;
+    while (cap < CGNN_FOF_MAX_G && (int64_t)(cap + 1) * (cap + 1) * (cap + 1) <= CGNN_FOF_CELLS_PER_PARTICLE * n) ++cap;
+    if (reach < 0.f) return cap;
+    const double need = (double)reach * (1.0 + 1e-5) + 2e-5 * (double)box;
+    const double g = floor((double)box / need);
+    int G = g < 1.0 ? 1 : (g > (double)CGNN_FOF_MAX_G ? CGNN_FOF_MAX_G : (int)g);
+    return G < cap ? G : cap;
+}
+
+static int64_t fof_cell_slots(int G) {
+    int Gp = 1;
+    while (Gp < G) Gp <<= 1;
+    return (int64_t)Gp * Gp * Gp;
+}
+
+// at most one partly filled item per cell that holds queries, plus the full ones
+static int64_t fof_max_items(int64_t cells, int64_t n) { return (cells < n ? cells : n) + n / CGNN_FOF_QCHUNK; }
+
+struct FofLayout {
+    int64_t cells_max;   // cell slots of the finest grid n allows: the tables are sized for it
+    size_t off_count, off_start, off_cursor, off_cellof, off_sorted, off_bsum, off_nchunk, off_cstart, off_itemq0, total;
+};
+
+static FofLayout fof_layout(int64_t n) {
+    FofLayout L;
+    L.cells_max = fof_cell_slots(fof_cells_per_axis(n, 1.f, -1.f));
+    const size_t table = (size_t)(L.cells_max + 1) * 4;
+    size_t off = 0;
+    L.off_count = off;  off = align256(off + table);
+    L.off_start = off;  off = align256(off + table);
+    L.off_cursor = off; off = align256(off + table);
+    L.off_cellof = off; off = align256(off + (size_t)n * 4);
+    L.off_sorted = off; off = align256(off + (size_t)n * 16);
+    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(L.cells_max + 1) + 1) * 4);
+    L.off_nchunk = off; off = align256(off + table);
+    L.off_cstart = off; off = align256(off + table);
+    L.off_itemq0 = off; off = align256(off + (size_t)fof_max_items(L.cells_max, n) * 4);
+    L.total = off;
+    return L;
+}
+
+// nchunk[c] = work items of cell c; entry `cells` stays 0 so that the scan ends in the item total
+__global__ void fof_chunks_kernel(const int32_t* __restrict__ start, int64_t cells, int32_t* __restrict__ nchunk) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > cells) return;
+    nchunk[c] = c < cells ? (start[c + 1] - start[c] + CGNN_FOF_QCHUNK - 1) / CGNN_FOF_QCHUNK : 0;
+}
+
+// item_q0[item] = the sorted slot of the item's first query: slot s of cell c begins item chunk_start[c] + k when it is
+// the (k QCHUNK)-th of its cell.  One thread per slot, so a crowded cell costs no thread a long loop, and the walk finds
+// its item with one load instead of a search over the cell table.
+__global__ void fof_items_kernel(const float4* __restrict__ sorted, const int32_t* __restrict__ cell_of,
+                                 const int32_t* __restrict__ start, const int32_t* __restrict__ chunk_start, int64_t n,
+                                 int32_t* __restrict__ item_q0) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const int c = cell_of[__float_as_int(sorted[s].w)];
+    const int off = (int)s - start[c];
+    if (off % CGNN_FOF_QCHUNK == 0) item_q0[chunk_start[c] + off / CGNN_FOF_QCHUNK] = (int32_t)s;
+}
+
+__global__ void fof_init_kernel(int32_t* __restrict__ parent, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) parent[i] = (int32_t)i;
+}
+
+__device__ __forceinline__ float fof_fold(float d, float box, float half) {
+    if (d > half) d = __fsub_rn(d, box);
+    else if (d < -half) d = __fadd_rn(d, box);
+    return d;
+}
+
+__device__ __forceinline__ int fof_load(const int32_t* parent, int x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of x's tree as far as this thread can see, halving the path on the way; at most x steps by invariant (1)
+__device__ __forceinline__ int fof_find(int32_t* parent, int x) {
+    int p = fof_load(parent, x);
+    while (p != x) {
+        const int gp = fof_load(parent, p);
+        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void fof_unite(int32_t* parent, int a, int b) {
+    for (;;) {
+        a = fof_find(parent, a);
+        b = fof_find(parent, b);
+        if (a == b) return;
+        const int big = a > b ? a : b, small = a > b ? b : a;
+        const int seen = atomicCAS(parent + big, big, small);
+        if (seen == big) return;
+        a = seen;      // big was hooked by another thread meanwhile, under seen < big: go on from there
+        b = small;
+    }
+}
+
+__global__ __launch_bounds__(CGNN_FOF_QCHUNK) void fof_walk_kernel(const float4* __restrict__ sorted,
+                                                                   const int32_t* __restrict__ start,
+                                                                   const int32_t* __restrict__ cell_of,
+                                                                   const int32_t* __restrict__ chunk_start,
+                                                                   const int32_t* __restrict__ item_q0, int cells,
+                                                                   int G, float box, float half, float l2,
+                                                                   int32_t* parent) {
+    __shared__ float4 q_s[CGNN_FOF_QCHUNK];
+    __shared__ int rng_p0[CGNN_FOF_RANGES], rng_len[CGNN_FOF_RANGES], rng_off[CGNN_FOF_RANGES + 1];
+    const int tid = threadIdx.x;
+    const int items = chunk_start[cells];
+    const int na = G < 3 ? G : 3;      // cells walked per axis
+    for (int item = blockIdx.x; item < items; item += gridDim.x) {
+        const int q0 = item_q0[item];
+        const int c = cell_of[__float_as_int(sorted[q0].w)];      // the item's cell: that of its first query
+        const int nq = min(CGNN_FOF_QCHUNK, start[c + 1] - q0);
+        const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
+        __syncthreads();               // the previous item's readers of q_s and rng_* are done
+        if (tid < nq) q_s[tid] = sorted[q0 + tid];
+        if (tid < CGNN_FOF_RANGES) {
+            const int ix = tid / 9, iy = (tid / 3) % 3, iz = tid % 3;
+            int p0 = 0, len = 0;
+            if (ix < na && iy < na && iz < na) {
+                // G <= 3: all cells of the axis, each once; otherwise c - 1, c, c + 1 wrapped (three distinct cells)
+                const int wx = G <= 3 ? ix : (cx - 1 + ix + G) % G;
+                const int wy = G <= 3 ? iy : (cy - 1 + iy + G) % G;
+                const int wz = G <= 3 ? iz : (cz - 1 + iz + G) % G;
+                const int cell = morton3(wx, wy, wz);
+                p0 = start[cell];
+                len = start[cell + 1] - p0;
+            }
+            rng_p0[tid] = p0;
+            rng_len[tid] = len;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int run = 0;
+            for (int j = 0; j < CGNN_FOF_RANGES; ++j) {
+                rng_off[j] = run;
+                run += rng_len[j];
+            }
+            rng_off[CGNN_FOF_RANGES] = run;
+        }
+        __syncthreads();
+        const int nc = rng_off[CGNN_FOF_RANGES];
+        for (int t0 = 0; t0 < nc; t0 += CGNN_FOF_QCHUNK) {
+            const int t = t0 + tid;
+            if (t < nc) {
+                int j = 0;
+                while (rng_off[j + 1] <= t) ++j;            // t < rng_off[RANGES]: j stays below RANGES
+                const float4 b = sorted[rng_p0[j] + (t - rng_off[j])];
+                const int bi = __float_as_int(b.w);
+                for (int qi = 0; qi < nq; ++qi) {
+                    const float4 a = q_s[qi];
+                    const float dx = fof_fold(__fsub_rn(b.x, a.x), box, half);
+                    const float dy = fof_fold(__fsub_rn(b.y, a.y), box, half);
+                    const float dz = fof_fold(__fsub_rn(b.z, a.z), box, half);
+                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    // the pair is met from both sides: this one unites it (and never a particle with itself)
+                    if (d2 < l2 && bi < __float_as_int(a.w)) fof_unite(parent, __float_as_int(a.w), bi);
+                }
+            }
+        }
+    }
+}
+
+// labels[i] = the root of i = the minimum of its component (parent is labels: a root already reads itself).  The walk
+// is over, so the forest no longer changes shape; this find must NOT halve: a halving store into another particle's
+// slot could land after that particle's own final store and leave an ancestor there instead of the root.  Every slot is
+// written by its own thread alone, with the root, which keeps it an ancestor for the threads that read through it.
+__global__ void fof_labels_kernel(int32_t* parent, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int x = (int)i, p = fof_load(parent, x);
+    while (p != x) {
+        x = p;
+        p = fof_load(parent, x);
+    }
+    if (x != (int)i) __hip_atomic_store(parent + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- cgnn_fof_catalogue --------------------------------------------------------------------------------------------
+struct FofSizeEdges {
+    int32_t e[CGNN_FOF_MAX_BINS + 1];
+};
+
+// One thread per particle.  A root adds itself to its size; the other members of a wave are summed per root first
+// (a loop over the distinct roots among them, each round led by the first lane still waiting), so a group of many
+// members puts one atomic per wave on its slots instead of one per member.  Integer sums: any grouping gives the
+// same bits.
+__global__ __launch_bounds__(CGNN_BLOCK) void fof_members_kernel(const float* __restrict__ pos,
+                                                                 const int32_t* __restrict__ labels, int64_t n, float box,
+                                                                 float half, double scale, int32_t* __restrict__ size,
+                                                                 unsigned long long* __restrict__ disp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & (CGNN_WAVE - 1);
+    int r = -1;
+    if (i < n) {
+        r = labels[i];
+        if (r < 0 || r >= n) r = -1;   // not a label of cgnn_fof_labels: outside the contract, never outside the arrays
+    }
+    if (r >= 0 && r == i) atomicAdd(&size[r], 1);
+    const bool member = r >= 0 && r != i;
+    long long q0 = 0, q1 = 0, q2 = 0;  // the root's own displacement is 0
+    if (member && disp != nullptr) {
+        q0 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 0], pos[3 * (int64_t)r + 0]), box, half), scale));
+        q1 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 1], pos[3 * (int64_t)r + 1]), box, half), scale));
+        q2 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 2], pos[3 * (int64_t)r + 2]), box, half), scale));
+    }
+    unsigned long long todo = __ballot(member);      // wave-uniform: every lane runs every round
+    while (todo != 0) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int lr = __shfl(r, leader);
+        const bool mine = member && r == lr;
+        const unsigned long long m = __ballot(mine);
+        todo &= ~m;
+        long long s0 = mine ? q0 : 0, s1 = mine ? q1 : 0, s2 = mine ? q2 : 0;
+        if (m != (1ull << leader) && disp != nullptr) {
+            for (int off = CGNN_WAVE / 2; off > 0; off >>= 1) {
+                s0 += __shfl_xor(s0, off);
+                s1 += __shfl_xor(s1, off);
+                s2 += __shfl_xor(s2, off);
+            }
+        }
+        if (lane == leader) {
+            atomicAdd(&size[lr], __popcll(m));
+            if (disp != nullptr) {     // two's complement: the sum of the unsigned images is the image of the signed sum
+                if (s0 != 0) atomicAdd(&disp[3 * (int64_t)lr + 0], (unsigned long long)s0);
+                if (s1 != 0) atomicAdd(&disp[3 * (int64_t)lr + 1], (unsigned long long)s1);
+                if (s2 != 0) atomicAdd(&disp[3 * (int64_t)lr + 2], (unsigned long long)s2);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(CGNN_BLOCK) void fof_hist_kernel(const int32_t* __restrict__ size, int64_t n,
+                                                              const FofSizeEdges E, int num_bins,
+                                                              unsigned long long* __restrict__ hist) {
+    __shared__ unsigned h_s[CGNN_FOF_MAX_BINS];
+    for (int b = threadIdx.x; b < num_bins; b += CGNN_BLOCK) h_s[b] = 0u;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = i < n ? size[i] : 0;
+    if (s >= E.e[0] && s < E.e[num_bins]) {
+        int lo = 0, up = num_bins;     // e[lo] <= s < e[up]
+        while (up - lo > 1) {
+            const int mid = (lo + up) >> 1;
+            if (E.e[mid] <= s) lo = mid; else up = mid;
+        }
+        atomicAdd(&h_s[lo], 1u);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < num_bins; b += CGNN_BLOCK)
+        if (h_s[b] != 0u) atomicAdd(&hist[b], (unsigned long long)h_s[b]);
+}
+
+}  // namespace cgnn
+
+using namespace cgnn;
+
+extern "C" {
+
+size_t cgnn_fof_labels_workspace_bytes(int64_t n) {
+    if (n <= 0 || n >= ((int64_t)1 << 31)) return 256;
+    return fof_layout(n).total;
+}
+
+int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_length, int32_t* labels, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    if (!pos || !labels || !workspace || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
+        set_error("cgnn_fof_labels: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const float half = 0.5f * box_size;
+    if (!isfinite(linking_length) || !(linking_length > 0.f) || linking_length > half) {
+        set_error("cgnn_fof_labels: linking_length=%g must be finite, positive and at most half the box, %g",
+                  (double)linking_length, (double)half);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n >= ((int64_t)1 << 31)) {
+        set_error("cgnn_fof_labels: 2^31 or more particles are not supported");
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+        set_error("cgnn_fof_labels: workspace must be 16-byte aligned");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const FofLayout L = fof_layout(n);
+    if (workspace_bytes < L.total) {
+        set_error("cgnn_fof_labels: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+        return CGNN_ERR_WORKSPACE;
+    }
+    const int G = fof_cells_per_axis(n, box_size, linking_length);
+    const int64_t cells = fof_cell_slots(G);   // <= L.cells_max: G never exceeds the cap the layout is sized for
+    const float inv_h = (float)G / box_size;
+    const float l2 = linking_length * linking_length;   // fl32 product, rounded once
+
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    int32_t* count = reinterpret_cast<int32_t*>(ws + L.off_count);
+    int32_t* start = reinterpret_cast<int32_t*>(ws + L.off_start);
+    int32_t* cursor = reinterpret_cast<int32_t*>(ws + L.off_cursor);
+    int32_t* cell_of = reinterpret_cast<int32_t*>(ws + L.off_cellof);
+    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
+    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
+    int32_t* nchunk = reinterpret_cast<int32_t*>(ws + L.off_nchunk);
+    int32_t* cstart = reinterpret_cast<int32_t*>(ws + L.off_cstart);
+    int32_t* item_q0 = reinterpret_cast<int32_t*>(ws + L.off_itemq0);
+
+    const int64_t m = cells + 1;   // count[cells] = 0 so that start[cells] = n
+    int rc = check_hip(hipMemsetAsync(count, 0, (size_t)m * 4, st), "fof_labels memset count");
+    if (rc) return rc;
+    rc = check_hip(hipMemsetAsync(cursor, 0, (size_t)m * 4, st), "fof_labels memset cursor");
+    if (rc) return rc;
+    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
+    const unsigned mb = (unsigned)((m + CGNN_BLOCK - 1) / CGNN_BLOCK);
+    fof_init_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
+    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, cell_of, count);
+    exclusive_scan_i32(count, m, bsum, start, st);
+    knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, cell_of, start, cursor, sorted);
+    fof_chunks_kernel<<<mb, CGNN_BLOCK, 0, st>>>(start, cells, nchunk);
+    exclusive_scan_i32(nchunk, m, bsum, cstart, st);
+    fof_items_kernel<<<nb, CGNN_BLOCK, 0, st>>>(sorted, cell_of, start, cstart, n, item_q0);
+    const int64_t max_items = fof_max_items(cells, n);
+    const unsigned blocks = (unsigned)(max_items < CGNN_FOF_MAX_BLOCKS ? max_items : CGNN_FOF_MAX_BLOCKS);
+    fof_walk_kernel<<<blocks, CGNN_FOF_QCHUNK, 0, st>>>(sorted, start, cell_of, cstart, item_q0, (int)cells, G, box_size,
+                                                        half, l2, labels);
+    fof_labels_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
+    return check_hip(hipGetLastError(), "cgnn_fof_labels");
+}
+
+int cgnn_fof_catalogue(const float* pos, const int32_t* labels, int64_t n, float box_size, int32_t* size, int64_t* disp,
+                       const int32_t* size_edges, int32_t num_bins, int64_t* hist, void* stream) {
+    if (!pos || !labels || !size || n <= 0 || !(box_size > 0.f) || !isfinite(box_size) || (hist && !size_edges)) {
+        set_error("cgnn_fof_catalogue: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n >= ((int64_t)1 << 31)) {
+        set_error("cgnn_fof_catalogue: 2^31 or more particles are not supported");
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    FofSizeEdges E;
+    if (hist) {
+        if (num_bins < 1 || num_bins > CGNN_FOF_MAX_BINS) {
+            set_error("cgnn_fof_catalogue: num_bins=%d outside [1, %d]", (int)num_bins, CGNN_FOF_MAX_BINS);
+            return CGNN_ERR_INVALID_ARG;
+        }
+        for (int i = 0; i <= num_bins; ++i) {
+            if (size_edges[i] < 1 || (i > 0 && size_edges[i] <= size_edges[i - 1])) {
+                set_error("cgnn_fof_catalogue: size_edges must start at 1 or above and ascend strictly (size_edges[%d])", i);
+                return CGNN_ERR_INVALID_ARG;
+            }
+            E.e[i] = size_edges[i];
+        }
+        for (int i = num_bins + 1; i <= CGNN_FOF_MAX_BINS; ++i) E.e[i] = 0;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_hip(hipMemsetAsync(size, 0, (size_t)n * 4, st), "fof_catalogue memset size");
+    if (rc) return rc;
+    if (disp) {
+        rc = check_hip(hipMemsetAsync(disp, 0, (size_t)n * 24, st), "fof_catalogue memset disp");
+        if (rc) return rc;
+    }
+    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
+    const double scale = 1073741824.0 / (double)box_size;
+    fof_members_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, labels, n, box_size, 0.5f * box_size, scale, size,
+                                                  reinterpret_cast<unsigned long long*>(disp));
+    if (hist) {
+        rc = check_hip(hipMemsetAsync(hist, 0, (size_t)num_bins * 8, st), "fof_catalogue memset hist");
+        if (rc) return rc;
+        fof_hist_kernel<<<nb, CGNN_BLOCK, 0, st>>>(size, n, E, num_bins, reinterpret_cast<unsigned long long*>(hist));
+    }
+    return check_hip(hipGetLastError(), "cgnn_fof_catalogue");
+}
+
+}  // extern "C"

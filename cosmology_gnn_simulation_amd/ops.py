@@ -1005,6 +1005,115 @@ def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b:
     return (modes, sums) if batched else (modes[0], sums[0])
 
 
+def check_linking_length(linking_length, box_size: float, who: str) -> float:
+    """The linking length of :func:`fof_labels` as a float32 host value, or ``ValueError``: finite, positive and at most
+    ``fl32(0.5 * box_size)``, ``box_size`` finite and positive.  Callers check before any device work."""
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{who}: box_size must be positive and finite, got {box_size!r}")
+    ll = torch.tensor(float(linking_length), dtype=torch.float32)
+    if not (bool(torch.isfinite(ll)) and float(ll) > 0.0):
+        raise ValueError(f"{who}: linking_length must be positive and finite (in float32), got {linking_length!r}")
+    if not bool(ll <= box * 0.5):
+        raise ValueError(f"{who}: linking_length {float(ll)} exceeds half the box, {float(box) * 0.5}")
+    return float(ll)
+
+
+def check_size_edges(size_edges, who: str) -> List[int]:
+    """The group-size bin edges of :func:`fof_catalogue` as host integers, or ``ValueError``: ``1 <= nb <= 256`` bins,
+    whole numbers below 2^31, ``size_edges[0] >= 1``, strictly ascending."""
+    e = torch.as_tensor(size_edges).detach().to(device="cpu").reshape(-1)
+    nb = e.numel() - 1
+    if not 1 <= nb <= _lib.FOF_MAX_BINS:
+        raise ValueError(f"{who}: size_edges must hold nb + 1 sizes with 1 <= nb <= {_lib.FOF_MAX_BINS}, got "
+                         f"{e.numel()} values")
+    if e.is_floating_point() and not (bool(torch.isfinite(e).all()) and bool((e == e.round()).all())):
+        raise ValueError(f"{who}: size_edges must be whole numbers")
+    e = e.to(torch.int64)
+    if int(e[0]) < 1 or int(e[-1]) >= 1 << 31 or not bool((e[1:] > e[:-1]).all()):
+        raise ValueError(f"{who}: size_edges must start at 1 or above, stay below 2^31 and ascend strictly")
+    return e.tolist()
+
+
+def fof_labels(pos: torch.Tensor, box_size: float, linking_length: float, *, check_bounds: bool = False) -> torch.Tensor:
+    """Friends-of-friends group labels in a periodic box (``cgnn_fof_labels``): ``int32 [N]`` for ``pos [N, 3]``, ``int32
+    [T, N]`` for ``pos [T, N, 3]`` (one call per frame on the same stream, no host synchronisation between them).  Two
+    particles ``i != j`` are linked iff ``d2 < fl32(linking_length ** 2)``, strictly, with ``d2`` the float32
+    minimum-image squared distance of ``include/cgnn.h``: exactly the pairs ``pair_counts(pos, box_size, [0,
+    linking_length])`` counts.  ``labels[i]`` is the smallest particle index of ``i``'s connected component: the same
+    bits on every run.
+
+    Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host synchronisation, the default
+    verifies nothing.  ``linking_length`` is a host value (:func:`check_linking_length`).  One box per call, positions
+    only: batches of simulations (``offsets``), spatial shards (an owned-storage rollout goes through
+    ``dist.assemble_frames`` first), unbinding, spherical-overdensity masses and velocities are out of scope."""
+    what = "fof_labels"
+    ll = check_linking_length(linking_length, box_size, what)
+    pos = f32c(pos, "pos")
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise CgnnError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if check_bounds and not bool(((pos >= 0) & (pos <= float(box_size))).all()):
+        raise ValueError(f"{what}: pos leaves [0, box_size]")
+    batched = pos.dim() == 3
+    frames = pos if batched else pos.unsqueeze(0)
+    t, n = frames.shape[0], frames.shape[1]
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_fof_labels_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+    labels = torch.empty((t, n), dtype=torch.int32, device=pos.device)
+    st = stream_ptr(pos.device)
+    with _timed(what, pos.device):
+        for f in range(t):
+            check(lib.cgnn_fof_labels(frames[f].data_ptr(), n, float(box_size), ll, labels[f].data_ptr(), ws.data_ptr(),
+                                      ws_bytes, st), "cgnn_fof_labels")
+    return labels if batched else labels[0]
+
+
+def fof_catalogue(pos: torch.Tensor, labels: torch.Tensor, box_size: float, size_edges=None, want_disp: bool = True):
+    """The groups of a labelling of :func:`fof_labels` in exact integers (``cgnn_fof_catalogue``): ``pos [N, 3]`` with
+    ``labels [N]``, or ``[T, N, 3]`` with ``[T, N]``.  Returns device tensors ``(size, disp, hist)``:
+
+    * ``size`` int32 ``[N]`` (``[T, N]``): at a root slot ``r`` (``labels[r] == r``) the number of members, elsewhere 0;
+    * ``disp`` int64 ``[N, 3]`` (``[T, N, 3]``), or ``None`` without ``want_disp``: at a root slot the sum over the
+      members of their folded float32 displacement from ``pos[r]`` in units of ``box_size / 2^30`` (``llrint`` of the
+      float64 product), elsewhere 0; the centre of the group is ``(pos[r] + disp / size * box_size / 2^30) mod box_size``;
+    * ``hist`` int64 ``[nb]`` (``[T, nb]``), or ``None`` without ``size_edges``: the groups with ``size_edges[b] <= size <
+      size_edges[b + 1]`` (``nb + 1`` ascending host integers, ``size_edges[0] >= 1``, ``nb <= 256``).
+
+    Integer sums: the same bits on every run.  No host synchronisation.  One box per call; matching groups between
+    two frames is out of scope."""
+    what = "fof_catalogue"
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    e = None if size_edges is None else check_size_edges(size_edges, what)
+    pos = f32c(pos, "pos")
+    labels = i32c(labels, "labels")
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise CgnnError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if labels.shape != pos.shape[:-1]:
+        raise CgnnError(f"{what}: labels must be {tuple(pos.shape[:-1])}, got {tuple(labels.shape)}")
+    _same_device(pos, labels)
+    batched = pos.dim() == 3
+    frames, lab = (pos, labels) if batched else (pos.unsqueeze(0), labels.unsqueeze(0))
+    t, n = frames.shape[0], frames.shape[1]
+    nb = 0 if e is None else len(e) - 1
+    size = torch.empty((t, n), dtype=torch.int32, device=pos.device)
+    disp = torch.empty((t, n, 3), dtype=torch.int64, device=pos.device) if want_disp else None
+    hist = torch.empty((t, nb), dtype=torch.int64, device=pos.device) if e is not None else None
+    edges_c = None if e is None else (C.c_int32 * (nb + 1))(*e)
+    lib = _lib.load()
+    st = stream_ptr(pos.device)
+    with _timed(what, pos.device):
+        for f in range(t):
+            check(lib.cgnn_fof_catalogue(frames[f].data_ptr(), lab[f].data_ptr(), n, float(box_size), size[f].data_ptr(),
+                                         None if disp is None else disp[f].data_ptr(), edges_c, nb,
+                                         None if hist is None else hist[f].data_ptr(), st), "cgnn_fof_catalogue")
+    if batched:
+        return size, disp, hist
+    return size[0], None if disp is None else disp[0], None if hist is None else hist[0]
+
+
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,
                     pos_noise: Optional[torch.Tensor] = None, temp_noise: Optional[torch.Tensor] = None):
     """``[W, N, 3]`` positions and ``[W, N(, 1)]`` temperatures -> ``(x [N, 3(W-1)+W], recent_pos [N, 3])``

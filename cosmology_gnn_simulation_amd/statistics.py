@@ -15,6 +15,15 @@ r(k) = P_ab / sqrt(P_aa P_bb) and the transfer function T(k) = sqrt(P_aa / P_bb)
 for every selected frame of a rollout against the truth; ``spectra_from_sums`` is the host arithmetic behind both
 and ``default_k_edges`` the unit-wide bins centred on the integer frequencies.
 
+Halos (what neither two-point statistic can tell: a rollout may match P(k) to a few per cent and still smear every
+halo into a puff): friends-of-friends groups, the connected components of "closer than the linking length" (0.2 mean
+interparticle spacings by convention, ``default_linking_length``), labelled by a lock-free union-find on the device
+(``ops.fof_labels``) and reduced in exact integers (``ops.fof_catalogue``).  ``halo_catalogue`` lists the groups of a
+frame with their sizes and centres, ``halo_mass_function`` counts them by size (``default_size_edges``: doubling bins
+from 20 members) and ``rollout_halo_statistics`` does that for every selected frame of a rollout against the truth.
+Matching halos between the predicted and the true frame, unbinding, spherical-overdensity masses and velocities are
+out of scope.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -266,3 +275,161 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     return {"frames": sel, "k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "k_mean": sp["k_mean"][0].clone(),
             "modes": sp["modes"][0].clone(), "power_pred": sp["power"], "power_true": sp["power_b"],
             "cross": sp["cross"], "r": sp["r"], "transfer": sp["transfer"]}
+
+
+def default_linking_length(n: int, box_size: float, b: float = 0.2) -> float:
+    """``b`` mean interparticle spacings: ``b * box_size / n ** (1 / 3)``."""
+    if int(n) < 1:
+        raise ValueError(f"default_linking_length: n must be at least 1, got {n!r}")
+    return float(b) * float(box_size) / float(n) ** (1.0 / 3.0)
+
+
+def default_size_edges(n: int, min_members: int = 20) -> list:
+    """Doubling group-size edges ``min_members, 2 min_members, 4 min_members, ...`` up to the first value above ``n``
+    (at least two edges, so that there is a bin): no group of ``n`` particles lies beyond the last one."""
+    if isinstance(min_members, bool) or int(min_members) != min_members or int(min_members) < 1:
+        raise ValueError(f"default_size_edges: min_members must be a whole number of at least 1, got {min_members!r}")
+    edges = [int(min_members)]
+    while len(edges) < 2 or edges[-1] <= int(n):
+        edges.append(2 * edges[-1])
+    return edges
+
+
+def halo_centres(root_pos, size, disp, box_size: float) -> torch.Tensor:
+    """The centres of groups from the sums of ``ops.fof_catalogue``, on the host in float64: ``(pos[root] + disp / size *
+    L / 2^30) mod L`` for ``root_pos [H, 3]``, ``size [H]``, ``disp [H, 3]`` (int64, displacements from the root under
+    the minimum image in units of ``L / 2^30``), with ``L`` the float32 value of ``box_size`` the kernels use.  The
+    mean of minimum-image displacements from one member is the centre of mass of a group that spans less than half
+    the box, wherever it lies (a group across a box corner has its centre at the corner); a group that spans more
+    than half the box has no meaningful centre."""
+    box = float(torch.tensor(float(box_size), dtype=torch.float32))
+    root_pos = torch.as_tensor(root_pos).detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3)
+    size = torch.as_tensor(size).detach().to(device="cpu", dtype=torch.float64).reshape(-1, 1)
+    disp = torch.as_tensor(disp).detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3)
+    return torch.remainder(root_pos + disp / size * (box / _lib.FOF_DISP_UNITS), box)
+
+
+def halo_catalogue(pos: torch.Tensor, box_size: float, linking_length: Optional[float] = None,
+                   min_members: int = 20) -> Dict:
+    """The friends-of-friends groups of one frame ``pos [N, 3]`` with at least ``min_members`` members
+    (``linking_length``: default :func:`default_linking_length`, 0.2 mean spacings).  Returns on the CPU
+
+    * ``labels`` int32 ``[N]``: every particle's group, named by its smallest member (``ops.fof_labels``);
+    * ``root`` int64 ``[H]``, ``size`` int64 ``[H]``: the listed groups, sorted by size descending, then by root
+      ascending;  ``centre`` float64 ``[H, 3]``: :func:`halo_centres` (a group that spans more than half the box has no
+      meaningful centre).
+
+    The number of groups is only known on the device: this function synchronises once (``nonzero``) after the kernels
+    and before its single transfer.  Positions only: no unbinding, no spherical-overdensity masses, no velocities; one
+    box, no spatial shards (``dist.assemble_frames`` first)."""
+    what = "halo_catalogue"
+    if pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be one frame [N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if isinstance(min_members, bool) or int(min_members) != min_members or int(min_members) < 1:
+        raise ValueError(f"{what}: min_members must be a whole number of at least 1, got {min_members!r}")
+    n = pos.shape[0]
+    ll = default_linking_length(n, box_size) if linking_length is None else linking_length
+    ops.check_linking_length(ll, box_size, what)
+    labels = ops.fof_labels(pos, box_size, ll)
+    size, disp, _ = ops.fof_catalogue(pos, labels, box_size)
+    root = torch.nonzero(size >= int(min_members)).reshape(-1)                        # the one synchronisation
+    rp = pos.index_select(0, root).to(torch.float32).contiguous()
+    # one transfer: the float32 root positions travel as their bits among the integers
+    packed = torch.cat([labels.to(torch.int64), root, size.index_select(0, root).to(torch.int64),
+                        disp.index_select(0, root).reshape(-1), rp.view(torch.int32).to(torch.int64).reshape(-1)]).cpu()
+    h = root.numel()
+    labels_h = packed[:n].to(torch.int32)
+    root_h, size_h = packed[n:n + h], packed[n + h:n + 2 * h]
+    disp_h = packed[n + 2 * h:n + 5 * h].reshape(h, 3)
+    rp_h = packed[n + 5 * h:].to(torch.int32).view(torch.float32).reshape(h, 3)
+    order = sorted(range(h), key=lambda i: (-int(size_h[i]), int(root_h[i])))
+    order = torch.tensor(order, dtype=torch.int64)
+    return {"labels": labels_h, "root": root_h[order], "size": size_h[order],
+            "centre": halo_centres(rp_h[order], size_h[order], disp_h[order], box_size)}
+
+
+def halo_counts_on_device(frames: torch.Tensor, box_size: float, linking_length: float, size_edges) -> torch.Tensor:
+    """The device part of :func:`halo_mass_function`: for ``frames [F, N, 3]`` an int64 ``[F, nb + 3]`` device tensor
+    whose rows hold the ``nb`` group counts, then the number of groups with at least ``size_edges[0]`` members, the
+    particles in them, and the size of the largest group.  No host synchronisation."""
+    labels = ops.fof_labels(frames, box_size, linking_length)
+    size, _, hist = ops.fof_catalogue(frames, labels, box_size, size_edges, want_disp=False)
+    listed = size >= int(size_edges[0])
+    members = torch.where(listed, size, torch.zeros_like(size)).sum(dim=1, dtype=torch.int64)
+    return torch.cat([hist, listed.sum(dim=1, dtype=torch.int64).unsqueeze(1), members.unsqueeze(1),
+                      size.max(dim=1).values.to(torch.int64).unsqueeze(1)], dim=1)
+
+
+def _halo_arguments(n: int, box_size: float, linking_length, size_edges, what: str):
+    ll = default_linking_length(n, box_size) if linking_length is None else linking_length
+    ll = ops.check_linking_length(ll, box_size, what)
+    return ll, ops.check_size_edges(default_size_edges(n) if size_edges is None else size_edges, what)
+
+
+def halo_mass_function(pos: torch.Tensor, box_size: float, linking_length: Optional[float] = None,
+                       size_edges=None) -> Dict:
+    """The friends-of-friends mass function of ``pos [N, 3]`` (or of every frame of ``[T, N, 3]``): the number of groups
+    by size.  ``linking_length``: default 0.2 mean spacings; ``size_edges``: ``nb + 1`` ascending whole numbers
+    (default :func:`default_size_edges`, doubling from 20).  Returns on the CPU
+
+    * ``size_lo``, ``size_hi`` int64 ``[nb]``; ``counts`` int64 ``[nb]`` (``[T, nb]``): the groups with ``size_lo <= size <
+      size_hi``;
+    * ``n_groups`` (int64) and ``fraction_in_groups`` (float64): the groups with at least ``size_edges[0]`` members
+      (beyond the last edge too) and the fraction of the particles they hold;  ``largest``: the largest group.
+
+    Everything is computed on the device of ``pos`` without a host synchronisation and comes back in one transfer.
+    One box per call, positions only (no unbinding, spherical-overdensity masses or velocities; no ``offsets``
+    batches; no spatial shards: ``dist.assemble_frames`` first)."""
+    what = "halo_mass_function"
+    frames = _frames3(pos, "pos", what)
+    n = frames.shape[1]
+    ll, e = _halo_arguments(n, box_size, linking_length, size_edges, what)
+    out = halo_counts_on_device(frames, box_size, ll, e).cpu()
+    if pos.dim() == 2:
+        out = out[0]
+    nb = len(e) - 1
+    edges = torch.tensor(e, dtype=torch.int64)
+    return {"size_lo": edges[:-1].clone(), "size_hi": edges[1:].clone(), "counts": out[..., :nb].clone(),
+            "n_groups": out[..., nb].clone(), "fraction_in_groups": out[..., nb + 1].to(torch.float64) / n,
+            "largest": out[..., nb + 2].clone()}
+
+
+def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
+                            box_size: float, linking_length: Optional[float] = None, size_edges=None,
+                            frames: Optional[Sequence[int]] = None) -> Dict:
+    """Halo statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N,
+    3]``).  ``frames``: the frame numbers to judge (default: every frame both hold).  Per selected frame (CPU):
+
+    * ``counts_pred``, ``counts_true`` int64 ``[F, nb]``: the mass functions (:func:`halo_mass_function`);
+    * ``n_groups_pred``, ``n_groups_true`` (int64 ``[F]``), ``fraction_pred``, ``fraction_true`` (float64): groups with
+      at least ``size_edges[0]`` members and the fraction of the particles in them;
+    * ``largest_pred``, ``largest_true`` (int64): the largest group,
+
+    plus ``frames``, ``size_lo`` and ``size_hi``.  No synchronisation per frame; the results come back in one packed
+    transfer.  The two frames' halos are not matched with each other; no unbinding, spherical-overdensity masses or
+    velocities; one box, no spatial shards (an owned-storage rollout goes through ``dist.assemble_frames`` first)."""
+    what = "rollout_halo_statistics"
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    tc = ground_truth["Coordinates"].to(dev)
+    avail = min(len(pc), len(tc))
+    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
+    if not sel or min(sel) < 0 or max(sel) >= avail:
+        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
+    if pc.shape[1:] != tc.shape[1:]:
+        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
+    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
+    pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
+    _frames3(pc, "Coordinates", what)
+    n = pc.shape[1]
+    ll, e = _halo_arguments(n, box_size, linking_length, size_edges, what)
+    out = torch.stack([halo_counts_on_device(pc, box_size, ll, e), halo_counts_on_device(tc, box_size, ll, e)]).cpu()
+    nb = len(e) - 1
+    edges = torch.tensor(e, dtype=torch.int64)
+    res = {"frames": sel, "size_lo": edges[:-1].clone(), "size_hi": edges[1:].clone()}
+    for which, name in enumerate(("pred", "true")):
+        res["counts_" + name] = out[which, :, :nb].clone()
+        res["n_groups_" + name] = out[which, :, nb].clone()
+        res["fraction_" + name] = out[which, :, nb + 1].to(torch.float64) / n
+        res["largest_" + name] = out[which, :, nb + 2].clone()
+    return res

@@ -618,6 +618,42 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
                     const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- judging a rollout by its halos: friends-of-friends groups and their catalogue ------------------------------------
+ * cgnn_fof_labels labels the connected components of "closer than the linking length" among pos [n, 3] (positions in
+ * [0, box_size]; a value of exactly box_size falls into the edge cell) in a periodic box of side box_size.  With d2(i, j)
+ * exactly the float32 minimum-image squared distance of cgnn_pair_counts, per axis
+ *     d = fl32(b - a);   half = fl32(0.5f * box_size);   d > half: d = fl32(d - box_size);  d < -half: d = fl32(d + box_size)
+ *     d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy)) + fl32(dz*dz))
+ * one float32 rounding per operation, no FMA, and l2 = fl32(linking_length * linking_length), particles i != j are linked
+ * iff d2 < l2.  The inequality is strict: the links are precisely the pairs cgnn_pair_counts counts for the edges
+ * [0, linking_length]; two distinct particles at one position are linked.  A group is a connected component of the links.
+ * labels (device, int32 [n]) is overwritten: labels[i] is the smallest particle index of i's component, a canonical
+ * labelling, the same on every run and independent of how the threads raced (a lock-free union-find that hooks the
+ * larger root under the smaller; csrc/fof.hip).  No host synchronisation, everything on `stream`.
+ * CGNN_ERR_INVALID_ARG for a null pointer, n <= 0, box_size not finite or <= 0, linking_length not finite, <= 0 or
+ * > half, a workspace that is not 16-byte aligned; n >= 2^31: CGNN_ERR_UNSUPPORTED; a short workspace:
+ * CGNN_ERR_WORKSPACE.  Workspace: cgnn_fof_labels_workspace_bytes(n), a function of n alone, O(n).
+ *
+ * cgnn_fof_catalogue reduces such a labelling.  A root slot is a particle r with labels[r] == r.
+ *   size (device, int32 [n])     size[r] = members of r's group (r included); every other slot 0
+ *   disp (device, int64 [n, 3])  may be NULL.  disp[r, c] = sum over the members i of q = llrint((double)d * scale), d the
+ *                                folded float32 displacement fold(fl32(pos[i, c] - pos[r, c])) of the contract above and
+ *                                scale = 2^30 / (double)box_size, computed once on the host; every other slot 0.
+ *                                |q| <= 2^29 and fewer than 2^31 members: the sums cannot overflow.  The group's centre
+ *                                is pos[r] + disp[r] / size[r] * box_size / 2^30, modulo the box (meaningless for a
+ *                                group that spans more than half the box).
+ *   hist (device, int64 [num_bins])  may be NULL.  hist[b] = groups with size_edges[b] <= size < size_edges[b + 1];
+ *                                size_edges (HOST memory, num_bins + 1 int32): strictly ascending, size_edges[0] >= 1,
+ *                                1 <= num_bins <= 256 (otherwise CGNN_ERR_INVALID_ARG; ignored when hist is NULL).
+ * All three are overwritten.  Integer sums (integer atomics, no float atomics): the results do not depend on any order
+ * and are the same bits on every run.  labels outside [0, n) are outside the contract and are skipped.  No workspace,
+ * no host synchronisation.  n >= 2^31: CGNN_ERR_UNSUPPORTED. */
+size_t cgnn_fof_labels_workspace_bytes(int64_t n);
+int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_length, int32_t* labels,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int cgnn_fof_catalogue(const float* pos, const int32_t* labels, int64_t n, float box_size, int32_t* size, int64_t* disp,
+                       const int32_t* size_edges, int32_t num_bins, int64_t* hist, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes

@@ -1,0 +1,237 @@
+"""CPU: the linking contract of ``cgnn_fof_labels`` as tests/fof_checks.py restates it, on cases with analytic answers; the
+host refusals and defaults of the halo functions; the centre arithmetic; the bookkeeping of the new C entries."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import fof_checks as fc
+import pair_count_checks as pcc
+from conftest import ROOT
+from cosmology_gnn_simulation_amd import _lib, ops, statistics
+
+ENTRIES = ("cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue")
+NEXT_ABOVE_ONE = float(np.nextafter(np.float32(1), np.float32(2)))
+
+
+def test_lattice_at_the_spacing_is_all_singletons_and_just_above_it_one_group():
+    """d2 == l2 is not a link: the inequality is strict."""
+    pts = pcc.lattice_points()
+    at = fc.fof_labels(pts, 8.0, 1.0)
+    assert (at == np.arange(512)).all()
+    for ll in (1.0001, NEXT_ABOVE_ONE):
+        above = fc.fof_labels(pts, 8.0, ll)
+        assert (above == 0).all() and above.dtype == np.int32
+        assert len(fc.link_pairs(pts, 8.0, ll)) == 3 * 512                      # six neighbours each, wrapped
+    size, disp, hist = fc.catalogue(pts, fc.fof_labels(pts, 8.0, 1.0001), 8.0, [1, 512, 513])
+    assert size[0] == 512 and size.sum() == 512 and hist.tolist() == [0, 1]
+    # seen from the corner particle the lattice folds to coordinates -3 .. 4: the sum per axis is 64 * 4 spacings
+    assert disp[0].tolist() == [64 * 4 * 2 ** 27] * 3 and (disp[1:] == 0).all()
+
+
+def _two_blobs(n_a=40, n_b=25, seed=5, box=10.0):
+    rng = np.random.default_rng(seed)
+    a = 2.0 + 0.1 * rng.random((n_a, 3))
+    b = 7.0 + 0.1 * rng.random((n_b, 3))
+    x = np.concatenate([a, b]).astype(np.float32)
+    perm = rng.permutation(len(x))
+    return x[perm], perm < n_a                                                  # which blob each row came from
+
+
+def test_two_well_separated_blobs_are_two_groups():
+    x, in_a = _two_blobs()
+    labels = fc.fof_labels(x, 10.0, 0.2)                                        # every pair inside a blob is linked
+    la, lb = np.flatnonzero(in_a).min(), np.flatnonzero(~in_a).min()
+    assert (labels[in_a] == la).all() and (labels[~in_a] == lb).all()
+    size, disp, hist = fc.catalogue(x, labels, 10.0, statistics.default_size_edges(len(x)))
+    assert size[la] == 40 and size[lb] == 25 and size.sum() == 65
+    assert hist.tolist() == [1, 1]                                              # edges 20, 40, 80
+    c = fc.centres(x, np.array([la, lb]), size, disp, 10.0)
+    np.testing.assert_allclose(c[0], x[in_a].astype(np.float64).mean(axis=0), atol=1e-6)
+    np.testing.assert_allclose(c[1], x[~in_a].astype(np.float64).mean(axis=0), atol=1e-6)
+
+
+def test_a_pair_linked_only_across_a_box_face():
+    x = np.array([[0.05, 5.0, 5.0], [9.95, 5.0, 5.0], [5.0, 5.0, 5.0]], dtype=np.float32)
+    assert fc.fof_labels(x, 10.0, 0.2).tolist() == [0, 0, 2]
+    assert fc.fof_labels(x, 10.0, 0.05).tolist() == [0, 1, 2]
+    size, disp, _ = fc.catalogue(x, [0, 0, 2], 10.0)
+    assert size.tolist() == [2, 0, 1] and disp[0, 0] < 0                        # the partner lies BEHIND the face
+    c = fc.centres(x, np.array([0]), size, disp, 10.0)
+    np.testing.assert_allclose(c[0, 1:], [5.0, 5.0], atol=1e-6)
+    assert min(c[0, 0], 10.0 - c[0, 0]) < 1e-6                                  # at the face, not at the box centre
+
+
+def test_the_links_are_the_pairs_the_pair_counter_counts():
+    rng = np.random.default_rng(3)
+    x = rng.random((2000, 3), dtype=np.float32) * np.float32(25.0)
+    for spacings in (0.2, 0.6, 1.0):
+        ll = np.float32(spacings * 25.0 / 2000 ** (1 / 3))
+        pairs = fc.link_pairs(x, 25.0, ll)
+        assert len(pairs) == pcc.auto_counts(x, 25.0, np.array([0.0, ll], dtype=np.float32))[0]
+        assert len(pairs) > 0 and (pairs[:, 0] < pairs[:, 1]).all()
+
+
+def test_restatement_agrees_with_scipy_connected_components():
+    sparse = pytest.importorskip("scipy.sparse")
+    from scipy.sparse.csgraph import connected_components
+    rng = np.random.default_rng(4)
+    x = rng.random((3000, 3), dtype=np.float32) * np.float32(25.0)
+    ll = 0.8 * 25.0 / 3000 ** (1 / 3)
+    pairs = fc.link_pairs(x, 25.0, ll)
+    labels = fc.fof_labels(x, 25.0, ll)
+    graph = sparse.coo_matrix((np.ones(len(pairs)), (pairs[:, 0], pairs[:, 1])), shape=(3000, 3000))
+    count, comp = connected_components(graph, directed=False)
+    assert count == len(np.unique(labels)) and np.bincount(labels).max() >= 8
+    first = np.full(count, 3000)
+    np.minimum.at(first, comp, np.arange(3000))
+    assert (first[comp] == labels).all()
+
+
+@pytest.mark.parametrize("ll,box", [(0.0, 1.0), (-0.1, 1.0), (float("nan"), 1.0), (float("inf"), 1.0),
+                                    (0.5000001, 1.0), (1e-50, 1.0), (0.1, 0.0), (0.1, -1.0), (0.1, float("nan")),
+                                    (0.1, float("inf"))])
+def test_check_linking_length_refuses(ll, box):
+    with pytest.raises(ValueError):
+        ops.check_linking_length(ll, box, "test")
+    pos = torch.rand(10, 3)                             # a host tensor: refused later, were the length right
+    with pytest.raises(ValueError):
+        ops.fof_labels(pos, box, ll)
+    with pytest.raises(ValueError):
+        statistics.halo_mass_function(pos, box, ll)
+    with pytest.raises(ValueError):
+        statistics.halo_catalogue(pos, box, ll)
+
+
+def test_check_linking_length_accepts_exactly_half_the_float32_box():
+    box = 25.1
+    half = float(np.float32(0.5) * np.float32(box))
+    assert ops.check_linking_length(half, box, "test") == half
+    assert ops.check_linking_length(0.2, 1.0, "test") == float(np.float32(0.2))
+    with pytest.raises(ValueError):
+        ops.check_linking_length(float(np.nextafter(np.float32(half), np.float32(100))), box, "test")
+
+
+@pytest.mark.parametrize("edges", [[20], [], list(range(1, 259)), [0, 5], [-1, 5], [3, 3], [5, 3], [1.5, 3], [1, 2 ** 31],
+                                   [1, float("nan")]])
+def test_check_size_edges_refuses(edges):
+    with pytest.raises(ValueError):
+        ops.check_size_edges(edges, "test")
+    with pytest.raises(ValueError):
+        statistics.halo_mass_function(torch.rand(10, 3), 1.0, 0.1, edges)
+
+
+def test_defaults():
+    assert statistics.default_size_edges(100) == [20, 40, 80, 160]
+    assert statistics.default_size_edges(160) == [20, 40, 80, 160, 320]        # the first value ABOVE n
+    assert statistics.default_size_edges(159) == [20, 40, 80, 160]
+    assert statistics.default_size_edges(5) == [20, 40]                         # always a bin
+    assert statistics.default_size_edges(100, min_members=32) == [32, 64, 128]
+    assert ops.check_size_edges(statistics.default_size_edges(2 ** 24), "test")[-1] == 20 * 2 ** 20
+    assert ops.check_size_edges(torch.tensor([1.0, 2.0, 4.0]), "test") == [1, 2, 4]
+    assert ops.check_size_edges(list(range(1, 258)), "test")[-1] == 257         # 256 bins
+    with pytest.raises(ValueError):
+        statistics.default_size_edges(100, min_members=0)
+    assert statistics.default_linking_length(1000, 50.0) == pytest.approx(0.2 * 50.0 / 10.0, rel=1e-15)
+    assert statistics.default_linking_length(8, 1.0, b=0.5) == pytest.approx(0.25, rel=1e-15)
+    with pytest.raises(ValueError):
+        statistics.default_linking_length(0, 1.0)
+
+
+def test_halo_centres_from_hand_made_sums():
+    box = 8.0
+    unit = 2 ** 30 / 8                                  # one length unit in the integers of disp
+    root_pos = torch.tensor([[1.0, 2.0, 3.0], [0.25, 7.75, 4.0], [7.0, 0.0, 0.0]])
+    size = torch.tensor([4, 2, 3])
+    disp = torch.tensor([[4 * unit, -2 * unit, 0], [-unit, unit, 0], [3 * unit, 0, -3 * unit]], dtype=torch.int64)
+    c = statistics.halo_centres(root_pos, size, disp, box)
+    assert c.dtype == torch.float64 and c.shape == (3, 3)
+    want = [[2.0, 1.5, 3.0], [7.75, 0.25, 4.0], [0.0, 0.0, 7.0]]                # the last two wrap through a face
+    np.testing.assert_allclose(c.numpy(), want, rtol=0, atol=1e-12 * box)
+    # the unit is the float32 box's: L = 0.1 is not a float32 number
+    one = statistics.halo_centres([[0.0, 0.0, 0.0]], [1], [[2 ** 29, 0, 0]], 0.1)
+    assert float(one[0, 0]) == float(np.float64(np.float32(0.1)) / 2)
+    # and it agrees with the restatement's centres on a real catalogue
+    x, in_a = _two_blobs()
+    labels = fc.fof_labels(x, 10.0, 0.2)
+    s, d, _ = fc.catalogue(x, labels, 10.0)
+    roots = np.flatnonzero(s > 0)
+    got = statistics.halo_centres(torch.from_numpy(x[roots]), torch.from_numpy(s[roots]), torch.from_numpy(d[roots]), 10.0)
+    np.testing.assert_allclose(got.numpy(), fc.centres(x, roots, s, d, 10.0), rtol=0, atol=1e-11)
+
+
+def test_there_is_no_cpu_path():
+    pos = torch.rand(10, 3)
+    labels = torch.arange(10, dtype=torch.int32)
+    with pytest.raises(_lib.CgnnError):
+        ops.fof_labels(pos, 1.0, 0.1)
+    with pytest.raises(_lib.CgnnError):
+        ops.fof_labels(pos.view(1, 10, 3), 1.0, 0.5)
+    with pytest.raises(_lib.CgnnError):
+        ops.fof_catalogue(pos, labels, 1.0)
+    with pytest.raises(_lib.CgnnError):
+        statistics.halo_catalogue(pos, 1.0)
+    with pytest.raises(_lib.CgnnError):
+        statistics.halo_mass_function(pos, 1.0)
+    with pytest.raises(_lib.CgnnError):
+        statistics.rollout_halo_statistics({"Coordinates": pos.view(1, 10, 3)}, {"Coordinates": pos.view(1, 10, 3)}, 1.0)
+    with pytest.raises(ValueError):
+        statistics.rollout_halo_statistics({"Coordinates": pos.view(1, 10, 3)}, {"Coordinates": pos.view(1, 10, 3)}, 1.0,
+                                           frames=[1])
+    with pytest.raises(ValueError):
+        statistics.halo_catalogue(pos.view(1, 10, 3), 1.0)                      # one frame only
+
+
+def test_new_entries_are_declared_exported_built_and_documented():
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "cgnn.h")).read()
+    notes = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in ENTRIES:
+        assert name in _lib.EXPORTS and hasattr(lib, name)
+        assert name + "(" in header and name in notes
+    assert callable(ops.fof_labels) and callable(ops.fof_catalogue) and callable(ops.check_linking_length)
+    for fn in ("default_linking_length", "default_size_edges", "halo_catalogue", "halo_mass_function",
+               "rollout_halo_statistics"):
+        assert callable(getattr(statistics, fn))
+    makefile = open(os.path.join(ROOT, "cosmology_gnn_simulation_amd", "csrc", "Makefile")).read()
+    assert "fof.hip" in makefile and "FLAGS_fof := -ffp-contract=off" in makefile
+
+
+def test_workspace_size_and_the_host_refusals_of_the_c_entries():
+    """The refusals come before any device work: no GPU is needed to meet them."""
+    lib = _lib.load()
+    ws = lib.cgnn_fof_labels_workspace_bytes(4096)
+    # sorted float4, cell id and item slot per particle, five tables over at most 8 n cell slots (n cells, padded to a
+    # power of two per axis)
+    assert 4096 * 20 <= ws <= 4096 * (20 + 8 + 5 * 8 * 4) + 16 * 256 + 4096
+    assert lib.cgnn_fof_labels_workspace_bytes(0) == 256 and lib.cgnn_fof_labels_workspace_bytes(2 ** 31) == 256
+    assert lib.cgnn_fof_labels_workspace_bytes(8192) > ws
+    fake, odd = 1 << 20, (1 << 20) + 4                  # never dereferenced: every call below is refused on the host
+    inv, unsup, short = -1, -2, -3                      # CGNN_ERR_INVALID_ARG, _UNSUPPORTED, _WORKSPACE
+    half = float(np.float32(0.5))
+
+    def labels(pos=fake, n=100, box=1.0, ll=0.1, out=fake, w=fake, wb=1 << 30):
+        return lib.cgnn_fof_labels(pos, n, box, ll, out, w, wb, None)
+
+    assert labels(pos=None) == inv and labels(out=None) == inv and labels(w=None) == inv
+    assert labels(n=0) == inv and labels(n=-5) == inv and labels(n=2 ** 31, wb=1 << 62) == unsup
+    for box in (0.0, -1.0, float("nan"), float("inf")):
+        assert labels(box=box) == inv
+    for ll in (0.0, -0.1, float("nan"), float("inf"), float(np.nextafter(np.float32(0.5), np.float32(1)))):
+        assert labels(ll=ll) == inv
+    assert labels(w=odd) == inv
+    assert labels(wb=lib.cgnn_fof_labels_workspace_bytes(100) - 1) == short
+    assert b"workspace" in lib.cgnn_last_error()
+    assert labels(ll=half, wb=16) == short              # exactly half the box passes the length check
+
+    edges = (C.c_int32 * 3)(1, 2, 4)
+
+    def cat(pos=fake, lab=fake, n=100, box=1.0, size=fake, e=edges, nb=2, hist=fake):
+        return lib.cgnn_fof_catalogue(pos, lab, n, box, size, None, e, nb, hist, None)
+
+    assert cat(pos=None) == inv and cat(lab=None) == inv and cat(size=None) == inv and cat(n=0) == inv
+    assert cat(box=0.0) == inv and cat(box=float("nan")) == inv and cat(n=2 ** 31) == unsup
+    assert cat(e=None) == inv and cat(nb=0) == inv and cat(nb=257) == inv
+    assert cat(e=(C.c_int32 * 3)(0, 2, 4)) == inv and cat(e=(C.c_int32 * 3)(1, 2, 2)) == inv
