@@ -50,7 +50,7 @@ EXPORTS = (
     "cgnn_knn_batched_workspace_bytes", "cgnn_knn_periodic_batched", "cgnn_knn_batched_sorted_order",
     "cgnn_pair_counts_workspace_bytes", "cgnn_pair_counts", "cgnn_frame_errors_workspace_bytes", "cgnn_frame_errors",
     "cgnn_mass_assign", "cgnn_power_bin_ids", "cgnn_power_bins_workspace_bytes", "cgnn_power_bins",
-    "cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue",
+    "cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue", "cgnn_mass_assign_backward",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
@@ -152,6 +152,7 @@ def load() -> C.CDLL:
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]
     lib.cgnn_mass_assign.argtypes = [vp, i64, i64, f32, i32, i32, vp, vp]
+    lib.cgnn_mass_assign_backward.argtypes = [vp, vp, i64, i64, f32, i32, i32, C.c_double, vp, vp]
     lib.cgnn_fof_labels_workspace_bytes.restype = sz
     lib.cgnn_fof_labels_workspace_bytes.argtypes = [i64]
     lib.cgnn_fof_labels.argtypes = [vp, i64, f32, f32, vp, vp, sz, vp]

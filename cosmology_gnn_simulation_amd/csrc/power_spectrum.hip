@@ -15,6 +15,12 @@
 // up to its one conversion to float64.  One thread per particle, one 64-bit integer atomic per cell with a non-zero
 // weight.  Many particles in one cell serialise on one address (scripts/time_power_spectrum.py times a clustered frame).
 //
+// Gradient.  cgnn_mass_assign_backward is the deposit's transpose for training on the density field: given the gradient
+// of a scalar with respect to the mesh, every particle gathers its order^3 cells once and forms the gradient with
+// respect to its three coordinates, straight through the quantisation (the derivative of the unquantised assignment
+// function at the forward's u, in the forward's cells, the other two axes' weights being the forward's integers / Q).
+// Float64, every operation in a fixed place (ma_gather_kernel), no atomics: the numpy restatement gives the same bits.
+//
 // Binning.  A mode of the rfft array [M, M, M/2 + 1] has signed frequencies nx, ny in (-M/2, M/2] and nz in [0, M/2];
 // n2 = nx^2 + ny^2 + nz^2 <= 3 * 256^2 is exact in integers and in float32.  With e2[i] = fl32(k_edges[i]^2) the mode
 // is in bin i iff e2[i] <= (float)n2 < e2[i + 1]; n2 = 0 is never counted.  Its Hermitian weight h is 1 on the planes
@@ -99,6 +105,80 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __r
                 const long long v = (long long)w[0][a] * w[1][b] * w[2][c];
                 if (v != 0) atomicAdd(base + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c], (unsigned long long)v);
             }
+}
+
+// The transpose of the deposit (cgnn_mass_assign_backward): ma_axis at the forward's u, plus the derivative of the
+// unquantised assignment function with respect to u in difference form.  With g[0 .. ORDER - 2] the differences of the
+// mesh gradient between neighbouring cells along the axis, the axis' derivative is  sum_t dw[t] g[t]:
+//     CIC  dw = {1}:       d/du (1 - f, f) = (-1, +1)                       ->  D[i + 1] - D[i]
+//     TSC  dw = {tm, tp}:  d/du (tm^2/2, 3/4 - d^2, tp^2/2) = (-tm, tm - tp, tp)  ->  tm (D[j] - D[j-1]) + tp (D[j+1] - D[j])
+// the same sum as -tm D[j-1] + (tm - tp) D[j] + tp D[j+1], in an order in which a constant mesh gives exactly 0.
+// `wv` are the forward's integer weights divided by Q (exact).  An axis the forward read as u = 0 has dw = 0.
+template <int ORDER>
+__device__ __forceinline__ void ma_axis_grad(float p, float s, int M, int* cell, double* wv, double* dw) {
+    float u = __fmul_rn(p, s);
+    const bool ok = fabsf(u) < 1.0e9f;       // the deposit's guard: NaN or far outside the contract reads as u = 0
+    if (!ok) u = 0.f;
+    int w[ORDER];
+    ma_axis<ORDER>(u, M, cell, w);
+#pragma unroll
+    for (int t = 0; t < ORDER; ++t) wv[t] = (double)w[t] * (1.0 / CGNN_MA_Q);
+    if (ORDER == 2) {
+        dw[0] = ok ? 1.0 : 0.0;
+    } else {
+        const float d = __fsub_rn(u, floorf(__fadd_rn(u, 0.5f)));        // ma_axis' d, tm, tp: the same operations
+        dw[0] = ok ? (double)__fsub_rn(0.5f, d) : 0.0;
+        dw[1] = ok ? (double)__fadd_rn(0.5f, d) : 0.0;
+    }
+}
+
+// sum_t dw[t] (v[t + 1] - v[t]) in float64, left to right
+template <int ORDER>
+__device__ __forceinline__ double ma_diff(const double* v, const double* dw) {
+    if (ORDER == 2) return dw[0] * (v[1] - v[0]);
+    return dw[0] * (v[1] - v[0]) + dw[1] * (v[2] - v[1]);
+}
+
+// one thread per particle of every frame: gathers its ORDER^3 cells of d_mesh [frames, M, M, M] once and writes its own
+// three values of d_pos [frames, n, 3]; no atomics.  Summation order per axis: the two other axes in ascending axis
+// order, the first outer, the second inner; term = (ma_diff * w_outer) * w_inner; acc starts at 0.0 and adds the terms
+// in loop order.  d_pos = fl32((acc * (double)s) * scale).
+template <int ORDER>
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_kernel(const float* __restrict__ pos,
+                                                               const double* __restrict__ d_mesh, int64_t total, int64_t n,
+                                                               float s, int M, double scale, float* __restrict__ d_pos) {
+    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    int cell[3][ORDER];
+    double wv[3][ORDER], dw[3][ORDER - 1];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) ma_axis_grad<ORDER>(pos[3 * i + ax], s, M, cell[ax], wv[ax], dw[ax]);
+    const double* base = d_mesh + (i / n) * ((int64_t)M * M * M);
+    double D[ORDER][ORDER][ORDER];
+#pragma unroll
+    for (int a = 0; a < ORDER; ++a)
+#pragma unroll
+        for (int b = 0; b < ORDER; ++b)
+#pragma unroll
+            for (int c = 0; c < ORDER; ++c) D[a][b][c] = base[((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c]];
+    double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int p = 0; p < ORDER; ++p)
+#pragma unroll
+        for (int q = 0; q < ORDER; ++q) {
+            double line[ORDER];
+#pragma unroll
+            for (int t = 0; t < ORDER; ++t) line[t] = D[t][p][q];
+            acc[0] += (ma_diff<ORDER>(line, dw[0]) * wv[1][p]) * wv[2][q];
+#pragma unroll
+            for (int t = 0; t < ORDER; ++t) line[t] = D[p][t][q];
+            acc[1] += (ma_diff<ORDER>(line, dw[1]) * wv[0][p]) * wv[2][q];
+#pragma unroll
+            for (int t = 0; t < ORDER; ++t) line[t] = D[p][q][t];
+            acc[2] += (ma_diff<ORDER>(line, dw[2]) * wv[0][p]) * wv[1][q];
+        }
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) d_pos[3 * i + ax] = (float)((acc[ax] * (double)s) * scale);
 }
 
 static inline size_t pb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -292,6 +372,37 @@ int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size
         else ma_deposit_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
     }
     return check_hip(hipGetLastError(), "cgnn_mass_assign");
+}
+
+int cgnn_mass_assign_backward(const float* pos, const double* d_mesh, int64_t frames, int64_t n, float box_size,
+                              int32_t mesh, int32_t order, double scale, float* d_pos, void* stream) {
+    if (!pos || !d_mesh || !d_pos || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
+        set_error("cgnn_mass_assign_backward: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (mesh < 2 || mesh > CGNN_MA_MAX_MESH || order < 2 || order > 3) {
+        set_error("cgnn_mass_assign_backward: mesh=%d outside [2, %d] or order=%d outside [2, 3] (NGP has no gradient)",
+                  (int)mesh, CGNN_MA_MAX_MESH, (int)order);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n > ((int64_t)1 << 24)) {
+        set_error("cgnn_mass_assign_backward: more than 2^24 particles in a frame (the deposit's limit)");
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    const float s = (float)mesh / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^24: at least one frame)
+    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
+        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        const float* p = pos + f0 * n * 3;
+        const double* m = d_mesh + f0 * cells;
+        float* g = d_pos + f0 * n * 3;
+        if (order == 2) ma_gather_kernel<2><<<blocks, CGNN_BLOCK, 0, st>>>(p, m, total, n, s, mesh, scale, g);
+        else ma_gather_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, m, total, n, s, mesh, scale, g);
+    }
+    return check_hip(hipGetLastError(), "cgnn_mass_assign_backward");
 }
 
 int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream) {

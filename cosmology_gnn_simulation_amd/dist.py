@@ -2191,7 +2191,9 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
                           temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
                           step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
                           min_image_edge_attr: bool = False, knn_grid: str = "uniform", decomposition: str = "uniform",
-                          group=None, device=None, checkpoint: str = "none") -> "training.UnrolledLoss":
+                          group=None, device=None, checkpoint: str = "none", density_loss_weight: float = 0.0,
+                          density_mesh: Optional[int] = None, density_order: int = 2,
+                          density_smoothing: float = 0.0) -> "training.UnrolledLoss":
     """``training.unrolled_loss`` over the ranks of ``group`` (a world of one when no process group is up): the same
     arguments and meaning, S model steps unrolled from one window and differentiated through the whole chain, each rank
     computing the rows of its spatial tile.  Every rank passes the same windows and targets of all N particles (checked
@@ -2222,10 +2224,18 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
     halo exchanges, :func:`sharded_training_loss` with its all-reduces, the sample links and the integration of the
     owned rows again; the published frame is known and is not gathered again, its backward stays where it is.  Every
     rank issues the same collectives in the same order whatever it holds: a rank that owns nothing recomputes with empty
-    blocks.  Frames, ``value`` and ``step_losses`` are those of ``"none"`` bit for bit."""
+    blocks.  Frames, ``value`` and ``step_losses`` are those of ``"none"`` bit for bit.
+
+    The density term of ``training.unrolled_loss`` is not computed over shards (a rank deposits its own rows, and
+    meshes are not summed across ranks): the ``density_*`` arguments are named so that the two signatures stay one,
+    and a non-zero ``density_loss_weight`` raises ``NotImplementedError`` before any device work."""
     w, n, S, weights = training._unroll_arguments(model, position_seq, temperature_seq, target_positions,
                                                   target_temperatures, step_weights, backprop_steps, num_neighbors,
                                                   knn_grid, min_image_edge_attr, checkpoint)
+    if training._density_arguments(density_loss_weight, density_mesh, density_order, density_smoothing,
+                                   "sharded_unrolled_loss") is not None:
+        raise NotImplementedError("sharded_unrolled_loss: the density term is one box on one GPU (training.unrolled_loss); "
+                                  "meshes are not summed across spatial shards")
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"sharded_unrolled_loss: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")
     world, _ = _world_of(group)

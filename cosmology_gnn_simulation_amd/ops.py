@@ -918,6 +918,23 @@ def check_power_edges(k_edges, who: str) -> List[float]:
     return e.tolist()
 
 
+def _check_deposit(what: str, pos: torch.Tensor, box_size: float, mesh, order, orders) -> int:
+    """The host checks of :func:`mass_assign` and :func:`mass_assign_backward` (``ValueError``) -> ``mesh`` as an int."""
+    mesh = check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in orders:
+        if orders == (1, 2, 3):
+            raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+        raise ValueError(f"{what}: order must be 2 (CIC) or 3 (TSC), got {order!r} (NGP has no gradient)")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if pos.shape[-2] > _lib.MASS_ASSIGN_MAX_PARTICLES:
+        raise ValueError(f"{what}: {pos.shape[-2]} particles per frame exceed 2^24 (N 2^39 must stay inside int64)")
+    return mesh
+
+
 def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, check_bounds: bool = False) -> torch.Tensor:
     """Particles onto a periodic ``mesh^3`` grid in exact integers (``cgnn_mass_assign``): ``int64 [M, M, M]`` for ``pos
     [N, 3]``, ``int64 [T, M, M, M]`` for ``pos [T, N, 3]`` (all frames in one launch sequence, no host synchronisation).
@@ -931,16 +948,7 @@ def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, c
     cell 0); ``check_bounds=True`` verifies that (and that they are finite) with one host synchronisation, the default
     verifies nothing.  One box per call."""
     what = "mass_assign"
-    mesh = check_mesh(mesh, what)
-    if isinstance(order, bool) or order not in (1, 2, 3):
-        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
-    box = torch.tensor(float(box_size), dtype=torch.float32)
-    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
-        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
-    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
-        raise ValueError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
-    if pos.shape[-2] > _lib.MASS_ASSIGN_MAX_PARTICLES:
-        raise ValueError(f"{what}: {pos.shape[-2]} particles per frame exceed 2^24 (N 2^39 must stay inside int64)")
+    mesh = _check_deposit(what, pos, box_size, mesh, order, (1, 2, 3))
     pos = f32c(pos, "pos")
     if check_bounds and not bool(((pos >= 0) & (pos <= float(box_size))).all()):
         raise ValueError(f"{what}: pos leaves [0, box_size] or is not finite")
@@ -951,6 +959,70 @@ def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, c
         check(_lib.load().cgnn_mass_assign(pos.data_ptr(), t, n, float(box_size), mesh, int(order), out.data_ptr(),
                                            stream_ptr(pos.device)), "cgnn_mass_assign")
     return out if batched else out[0]
+
+
+def mass_assign_backward(pos: torch.Tensor, d_mesh: torch.Tensor, box_size: float, mesh: int, order: int = 2,
+                         scale: float = 1.0) -> torch.Tensor:
+    """The transpose of :func:`mass_assign` (``cgnn_mass_assign_backward``): ``d_mesh`` (float64 ``[M, M, M]`` for ``pos
+    [N, 3]``, ``[T, M, M, M]`` for ``[T, N, 3]``) is the gradient of a scalar with respect to ``mass_assign(pos) / Q^3``
+    (mass in particles per cell); returns ``scale`` times its gradient with respect to ``pos``, float32 in the shape of
+    ``pos``.  Straight through the quantisation: the derivative of the unquantised CIC / TSC assignment function at the
+    forward's ``u``, in the forward's cells, the other axes' weights being the forward's integers over ``Q``
+    (``include/cgnn.h``).  One thread per particle gathers its ``order^3`` cells once; float64 with every operation in
+    a fixed place and no atomics, so two calls and the numpy restatement give the same bits.  A coordinate the forward
+    reads as ``u = 0`` (NaN) gets gradient 0 on its axis.  ``order`` 2 or 3: NGP has no gradient (``ValueError``, as for
+    the other refusals of :func:`mass_assign`).  No host synchronisation."""
+    what = "mass_assign_backward"
+    mesh = _check_deposit(what, pos, box_size, mesh, order, (2, 3))
+    pos = f32c(pos, "pos")
+    batched = pos.dim() == 3
+    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
+    require_device(d_mesh, "d_mesh")
+    if d_mesh.dtype != torch.float64 or tuple(d_mesh.shape) != ((t,) if batched else ()) + (mesh,) * 3:
+        raise CgnnError(f"{what}: d_mesh must be float64 {((t,) if batched else ()) + (mesh,) * 3}, got {d_mesh.dtype} "
+                        f"{tuple(d_mesh.shape)}")
+    _same_device(pos, d_mesh)
+    d_mesh = d_mesh.contiguous()
+    out = torch.empty_like(pos)
+    with _timed(what, pos.device):
+        check(_lib.load().cgnn_mass_assign_backward(pos.data_ptr(), d_mesh.data_ptr(), t, n, float(box_size), mesh,
+                                                    int(order), float(scale), out.data_ptr(), stream_ptr(pos.device)),
+              "cgnn_mass_assign_backward")
+    return out
+
+
+class _DensityContrast(torch.autograd.Function):
+    """:func:`density_contrast`: the exact integer deposit forward, ``cgnn_mass_assign_backward`` behind it."""
+
+    @staticmethod
+    def forward(ctx, pos, box_size, mesh, order):
+        grid = mass_assign(pos, box_size, mesh, order)
+        ctx.args = (box_size, mesh, order)
+        ctx.save_for_backward(pos)
+        return grid.to(torch.float64) * (mesh ** 3 / (pos.shape[-2] * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_delta):
+        pos, = ctx.saved_tensors
+        box_size, mesh, order = ctx.args
+        d_pos = mass_assign_backward(pos, d_delta, box_size, mesh, order, scale=mesh ** 3 / pos.shape[-2])
+        return d_pos.to(pos.dtype), None, None, None
+
+
+def density_contrast(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2) -> torch.Tensor:
+    """The density contrast ``delta = mass_assign(pos).double() * (M^3 / (N Q^3)) - 1`` of ``pos [N, 3]`` (float64 ``[M,
+    M, M]``) or of every frame of ``pos [T, N, 3]`` (``[T, M, M, M]``): the expression and the bits of
+    ``statistics.power_spectrum``.  Differentiable in ``pos`` through :func:`mass_assign_backward` with ``scale = M^3 /
+    N`` (once); the result requires a gradient only when ``pos`` does.  ``order=1`` (NGP) has no gradient: ``ValueError``
+    when one is requested, the plain contrast otherwise."""
+    if pos.requires_grad and torch.is_grad_enabled():
+        if order == 1:
+            raise ValueError("density_contrast: order 1 (NGP) is piecewise constant in pos and has no gradient; use "
+                             "order 2 (CIC) or 3 (TSC), or detach pos")
+        return _DensityContrast.apply(pos, box_size, mesh, order)
+    with torch.no_grad():
+        return _DensityContrast.apply(pos, box_size, mesh, order)
 
 
 def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b: Optional[torch.Tensor] = None,

@@ -865,21 +865,32 @@ def _activation_floats(n: int, ne: int, window: int, latent: int, hidden: int, n
     return per_step, scratch
 
 
+def density_loss_bytes(density_mesh: int, smoothed: bool = False) -> int:
+    """What the density term of :func:`unrolled_loss` keeps of one step until the backward: two float64 meshes (the
+    difference of the contrasts and the gradient on its way to the particles), and when the term is smoothed the
+    difference's transform and its filtered copy (complex128 ``[M, M, M/2 + 1]`` each) with the filter itself."""
+    m = int(density_mesh)
+    return 16 * m ** 3 + (40 * m * m * (m // 2 + 1) if smoothed else 0)
+
+
 def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
                             num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False,
-                            checkpoint: str = "none") -> int:
+                            checkpoint: str = "none", density_mesh: int = 0, density_smoothed: bool = False) -> int:
     """Device memory S unrolled steps keep alive until the backward: S times the one-step activations -- the node
     features, ``x_i`` and ``agg_i`` of every round (:class:`NodeStreamSteps`), the edge features, and under
     ``message_source="edge"`` every round's input edge latents (:func:`edge_training_bytes`) -- plus one backward
     scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn.
-    ``checkpoint="steps"``: one step's activations, the scratch, and S small records (:func:`step_record_bytes`)."""
+    ``checkpoint="steps"``: one step's activations, the scratch, and S small records (:func:`step_record_bytes`).
+    ``density_mesh = M > 0``: the density term is on and every step whose activations are kept keeps
+    :func:`density_loss_bytes` as well (``density_smoothed``: with a smoothing length); 0, the default, adds nothing."""
     check_checkpoint(checkpoint, "unrolled_training_bytes")
     n = int(num_particles)
     per_step, scratch = _activation_floats(n, n * int(num_neighbors), window, latent, hidden, num_hidden_layers, rounds,
                                            edge_messages)
+    field = density_loss_bytes(density_mesh, density_smoothed) if density_mesh else 0
     if checkpoint == "steps":
-        return 4 * (per_step + scratch) + int(steps) * step_record_bytes(n, num_neighbors, edge_messages)
-    return 4 * (int(steps) * per_step + scratch)
+        return 4 * (per_step + scratch) + field + int(steps) * step_record_bytes(n, num_neighbors, edge_messages)
+    return 4 * (int(steps) * per_step + scratch) + int(steps) * field
 
 
 class UnrolledLoss:
@@ -888,11 +899,14 @@ class UnrolledLoss:
     and ``InternalEnergy [S, N, 1]``) and ``graphs`` (the S ``Data`` objects under ``keep_graphs``, else ``None``).
     ``value``: ``None`` on one GPU; from ``dist.sharded_unrolled_loss`` the all-reduced global loss (0-d float64, the same
     on every rank), ``loss`` then being this rank's part to differentiate.  ``offsets``: ``None``; from
-    :func:`unrolled_batch_loss` the B + 1 row offsets of the simulations in the frames' ``n_total`` rows."""
+    :func:`unrolled_batch_loss` the B + 1 row offsets of the simulations in the frames' ``n_total`` rows.
+    ``density_losses``: ``None``; with ``unrolled_loss(density_loss_weight != 0)`` the detached float64 ``[S]`` of every
+    step's ``losses.density_field_loss``, unweighted (``step_losses`` stays ``[S, 3]``)."""
 
     def __init__(self, loss, step_losses, frames, graphs, value=None):
         self.loss, self.step_losses, self.frames, self.graphs, self.value = loss, step_losses, frames, graphs, value
         self.offsets = None     # unrolled_batch_loss: B + 1 ints, simulation b holds rows offsets[b]:offsets[b + 1]
+        self.density_losses = None
 
 
 # ---- activation checkpointing across steps (unrolled_loss(checkpoint="steps")) -------------------------------------------
@@ -927,6 +941,7 @@ class _StepRecord:
     def __init__(self, s: int, weight: float, live: bool):
         self.s, self.weight, self.live = s, weight, live
         self.senders = self.order = self.edge_attr = self.terms = self.graph = None
+        self.density = None     # the step's unweighted density term (detached 0-d float64) when that term is on
         self.shard = self.cap = self.value = None       # dist.sharded_unrolled_loss: the step's Shard and send capacity
 
 
@@ -940,8 +955,9 @@ class _Unroll:
     :meth:`publish`.  ``sample0(want)`` makes step 0's sample of the true window, as ``ops.training_sample`` returns it."""
 
     def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0,
-                 knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False):
+                 knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False, density=None):
         self.model, self.cfg, self.w, self.n, self.k = model, cfg, w, n, k
+        self.density = density          # None, or (weight, mesh, order, smoothing) of the density term
         self.loss_weights, self.checkpoint, self.sample0 = loss_weights, checkpoint, sample0
         self.knn_grid, self.min_image, self.keep_graphs = knn_grid, min_image, keep_graphs
         self.edge = getattr(model, "message_source", "x_j") == "edge"
@@ -1002,14 +1018,26 @@ class _Unroll:
                     cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach(), recent.detach(),
                               order, k)
         new_p = new_t = None
-        if integrate:
+        if integrate or self.density is not None:
             p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
             if rec.live and grad:
                 new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, p2, p1, t1)
+            elif self.density is not None and grad:
+                # the step's own integration carries the density term's gradient where its outgoing link is cut or
+                # absent; the frame handed on is detached below, and no gradient can arrive through the temperature
+                new_p, new_t = _IntegrateLink.apply(cfg, acc, rate.detach(), p2, p1, t1.detach())
             else:
                 with torch.no_grad():
                     new_p, new_t = _IntegrateLink.apply(cfg, acc.detach(), rate.detach(), p2.detach(), p1.detach(),
                                                         t1.detach())
+        if self.density is not None:
+            weight, mesh, order, smoothing = self.density
+            field = losses.density_field_loss(new_p, tgt_p, cfg.box, mesh, order, smoothing)
+            loss_s = loss_s + (weight * field).to(torch.float32)
+            if not kept:
+                rec.density = field.detach()
+            if not rec.live:
+                new_p, new_t = new_p.detach(), new_t.detach()
         return rec.weight * loss_s, new_p, new_t
 
     def run(self, pos_frames, tmp_frames, tgt_p, tgt_t, weights, backprop_steps, s0=None) -> UnrolledLoss:
@@ -1020,7 +1048,7 @@ class _Unroll:
         self.checkpointed = self.checkpoint == "steps" and S > 1 and any(q.requires_grad for q in self.params)
         self.s0 = s0
         total = value = None
-        terms, graphs, out_p, out_t = [], [], [], []
+        terms, graphs, out_p, out_t, fields = [], [], [], [], []
         for s in range(S):
             # link s feeds step s + 1 and carries gradient when it is one of the last `links`
             rec = _StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
@@ -1034,6 +1062,7 @@ class _Unroll:
             if rec.value is not None:
                 value = weights[s] * rec.value if value is None else value + weights[s] * rec.value
             terms.append(rec.terms)
+            fields.append(rec.density)
             graphs.append(rec.graph)
             rec.graph = None
             new_p, new_t = self.publish(rec, *made)
@@ -1042,7 +1071,10 @@ class _Unroll:
             pos_frames.append(new_p)
             tmp_frames.append(new_t)
         frames = {"Coordinates": torch.stack(out_p), "InternalEnergy": torch.stack(out_t).unsqueeze(-1)}
-        return UnrolledLoss(total, torch.stack(terms), frames, graphs if self.keep_graphs else None, value)
+        out = UnrolledLoss(total, torch.stack(terms), frames, graphs if self.keep_graphs else None, value)
+        if self.density is not None:
+            out.density_losses = torch.stack(fields)
+        return out
 
 
 class _CheckpointedStep(torch.autograd.Function):
@@ -1142,7 +1174,9 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
                   acc_loss_weight: float = 1.0, temp_rate_loss_weight: float = 1.0, momentum_loss_weight: float = 0.0,
                   step_weights: Optional[Sequence[float]] = None, backprop_steps: Optional[int] = None,
                   min_image_edge_attr: bool = False, knn_grid: str = "uniform", keep_graphs: bool = False,
-                  device: Optional[torch.device] = None, checkpoint: str = "none") -> UnrolledLoss:
+                  device: Optional[torch.device] = None, checkpoint: str = "none", density_loss_weight: float = 0.0,
+                  density_mesh: Optional[int] = None, density_order: int = 2,
+                  density_smoothing: float = 0.0) -> UnrolledLoss:
     """The multi-step training loss: S model steps unrolled from one window ``position_seq [W, N, 3]`` /
     ``temperature_seq [W, N(, 1)]``, every step compared with the true frames ``target_positions [S, N, 3]`` /
     ``target_temperatures [S, N(, 1)]``, differentiable through the whole chain.
@@ -1180,13 +1214,29 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     neighbour search.  ``keep_graphs=True`` returns graphs of detached tensors, which hold ``x`` and ``edge_attr`` of
     every step (``(4 W - 3 + 4 k) 4 N`` bytes each): not part of the small record, and not counted by the estimate.
     S = 1, or a model without a parameter that requires a gradient, takes the ``"none"`` path.  Any other value raises
-    ``ValueError`` before a launch."""
+    ``ValueError`` before a launch.
+
+    The density term (``density_loss_weight = lambda != 0`` with ``density_mesh = M``): step s also scores the frame it
+    makes against the true one on the density field, ``loss_s += lambda * losses.density_field_loss(new_pos_s,
+    target_positions[s], box_size, M, density_order, density_smoothing)`` -- the (noise-shifted) target of the other
+    terms, exact CIC / TSC deposits of both frames, optionally Gaussian-smoothed over the length ``density_smoothing``.
+    Per-particle errors lose their meaning as trajectories diverge over the S steps; the density field does not.  The
+    term is added in float32 inside the step, so ``step_weights`` and ``checkpoint="steps"`` cover it like the others;
+    ``UnrolledLoss.density_losses`` reports it per step.  Its gradient reaches the model through the step's own
+    integration (``cgnn_mass_assign_backward``, then ``cgnn_rollout_integrate_backward``) and, through the live links,
+    the steps before; a step whose outgoing link is cut or absent (``backprop_steps``, the last step) still integrates
+    with autograd for its own term, and hands on a detached frame as before.  With ``lambda = 0``, the default, the
+    call is the one without these arguments, bit for bit.  ``ValueError`` before any device work: a non-zero weight
+    without ``density_mesh``, a negative or non-finite weight, ``density_order`` 1, the refusals of
+    ``losses.density_field_loss``.  One box on one GPU: :func:`unrolled_batch_loss` and ``dist.sharded_unrolled_loss``
+    do not take the term (a deposit is one box per call, and meshes are not summed across shards)."""
     w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
                                          step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr,
                                          checkpoint)
+    density = _density_arguments(density_loss_weight, density_mesh, density_order, density_smoothing)
     k = int(num_neighbors)
     device = _device_of(position_seq, device)
-    _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device)
+    _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device, density)
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
     pos_w, tmp_w, tgt_p, tgt_t = _device_window(position_seq, temperature_seq, target_positions, target_temperatures,
                                                 device)
@@ -1197,15 +1247,30 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
         return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
                                    tgt_p0, tgt_t0, None, want, stats=cfg.stats)
     unroll = _Unroll(model, cfg, w, n, k, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), checkpoint,
-                     sample0, knn_grid, min_image_edge_attr, keep_graphs)
+                     sample0, knn_grid, min_image_edge_attr, keep_graphs, density)
     return _unroll(unroll, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps)
 
 
-def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device) -> None:
+def _density_arguments(weight, mesh, order, smoothing, who: str = "unrolled_loss"):
+    """The density term's checks, which need no device: -> ``None`` when the term is off (weight 0), else ``(weight,
+    mesh, order, smoothing)``."""
+    from . import losses
+    if isinstance(weight, bool) or not math.isfinite(weight) or weight < 0:
+        raise ValueError(f"{who}: density_loss_weight must be finite and >= 0, got {weight!r}")
+    if weight == 0:
+        return None
+    if mesh is None:
+        raise ValueError(f"{who}: density_loss_weight={weight!r} needs density_mesh (the cells per side of the mesh)")
+    mesh = losses.check_density_loss(f"{who} (density term)", mesh, order, smoothing)
+    return float(weight), mesh, int(order), float(smoothing)
+
+
+def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device, density=None) -> None:
     """``CgnnError`` when :func:`unrolled_training_bytes` for ``n`` rows exceeds the free device memory."""
     edge = getattr(model, "message_source", "x_j") == "edge"
     need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                   len(model.processor), S, edge, checkpoint)
+                                   len(model.processor), S, edge, checkpoint,
+                                   *(() if density is None else (density[1], density[3] > 0)))
     free = free_device_bytes(device)
     if need > free:
         raise CgnnError(f"{who} needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
@@ -1230,14 +1295,15 @@ def _device_window(position_seq, temperature_seq, target_positions, target_tempe
             _lib.f32c(target_temperatures.to(device), "target_temperatures").reshape(S, n))
 
 
-def _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, noise):
+def _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, noise, shift_one: bool = False):
     """-> (W position frames, W temperature frames, ``tgt_p``, ``tgt_t``) as the steps read them.  ``noise``: ``None``, or
     ``pos_noise [n, W, 3]`` / ``temp_noise [n, W]`` of step 0's sample: added to the true frames, which later windows
-    read, and for S > 1 every target is shifted by the last frame's noise."""
+    read, and for S > 1 every target is shifted by the last frame's noise (step 0's sample shifts its own target; with
+    ``shift_one`` the target of S = 1 is shifted too, for a term that reads it outside the sample)."""
     if noise is not None:
         pos_w = pos_w + noise["pos_noise"].permute(1, 0, 2)
         tmp_w = tmp_w + noise["temp_noise"].t()
-        if tgt_p.shape[0] > 1:
+        if tgt_p.shape[0] > 1 or shift_one:
             tgt_p = tgt_p + noise["pos_noise"][:, -1]
             tgt_t = tgt_t + noise["temp_noise"][:, -1]
     return list(pos_w.unbind(0)), list(tmp_w.unbind(0)), tgt_p, tgt_t
@@ -1248,7 +1314,8 @@ def _unroll(unroll: _Unroll, noisy: bool, pos_w, tmp_w, tgt_p, tgt_t, weights, b
     the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``: step 0's sample is drawn here, with its noise in the same launch."""
     want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
     s0 = unroll.sample0(want)
-    return unroll.run(*_noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None), weights, backprop_steps, s0)
+    window = _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None, unroll.density is not None)
+    return unroll.run(*window, weights, backprop_steps, s0)
 
 
 def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions, target_temperatures, metadata: dict, *,

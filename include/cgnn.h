@@ -609,9 +609,34 @@ int cgnn_frame_errors(const float* pred_pos, const float* true_pos, const float*
  * its strided share in index order, a tree over the threads; the slices of a bin added in slice order), no float
  * atomics: two runs give the same bits.  All frames in one launch sequence (whole frames per launch, 2^24 threads at
  * most, so any number of frames the workspace holds is legal), no host synchronisation.
- * Workspace: cgnn_power_bins_workspace_bytes(frames, num_bins), 16-byte aligned. */
+ * Workspace: cgnn_power_bins_workspace_bytes(frames, num_bins), 16-byte aligned.
+ *
+ * cgnn_mass_assign_backward is the transpose of the deposit: d_mesh (device, double [frames, mesh, mesh, mesh]) is the
+ * gradient of a scalar with respect to out / Q^3 (mass in particles per cell); d_pos (device, float [frames, n, 3],
+ * overwritten) receives scale times its gradient with respect to pos.  Straight through the quantisation: the forward
+ * stays the integer deposit, the backward differentiates the unquantised assignment function at the same u in the same
+ * cells.  Per axis, u, the (wrapped) cells c[0 .. order-1], the integer weights and f (CIC) or d, tm, tp (TSC) are the
+ * forward's, by the same float32 operations; wv[t] = weight[t] / Q in float64 (exact).  The derivative of the axis'
+ * weights with respect to u is (-1, +1) for CIC and (-tm, tm - tp, +tp) for TSC (tm, tp the forward's float32 values
+ * widened to float64); it is applied in difference form along the axis, for a line v[0 .. order-1] of d_mesh values:
+ *   CIC  diff(v) = 1.0 * (v[1] - v[0])
+ *   TSC  diff(v) = tm * (v[1] - v[0]) + tp * (v[2] - v[1])
+ * (float64, one rounding per operation, no FMA, left to right), so that a constant d_mesh gives exactly 0.  With
+ * D[a][b][c] = d_mesh[c_x[a], c_y[b], c_z[c]], each of the order^3 values loaded once:
+ *   acc_x = sum over b (outer), c (inner) of (diff_x(D[.][b][c]) * wv_y[b]) * wv_z[c]
+ *   acc_y = sum over a (outer), c (inner) of (diff_y(D[a][.][c]) * wv_x[a]) * wv_z[c]
+ *   acc_z = sum over a (outer), b (inner) of (diff_z(D[a][b][.]) * wv_x[a]) * wv_y[b]
+ * each acc starting at 0.0 and adding its terms in loop order, and d_pos = fl32((acc * (double)s) * scale).  An axis
+ * the forward reads as u = 0 (NaN, or |u| >= 1e9) uses tm = tp = 0 (CIC: 0.0 in place of 1.0): its gradient is 0, and
+ * its weights in the other axes' sums are the forward's.  One thread per particle of every frame, whole frames per
+ * launch, 2^24 threads at most; no atomics (a particle writes its own three values), no host synchronisation; every
+ * float64 operation has a fixed place, so two runs and the numpy restatement give the same bits.
+ * CGNN_ERR_INVALID_ARG unless 2 <= mesh <= 512, order 2 or 3 (NGP is piecewise constant: it has no gradient),
+ * box_size > 0, no null pointer; n > 2^24: CGNN_ERR_UNSUPPORTED; all before any launch. */
 int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
                      int64_t* out, void* stream);
+int cgnn_mass_assign_backward(const float* pos, const double* d_mesh, int64_t frames, int64_t n, float box_size,
+                              int32_t mesh, int32_t order, double scale, float* d_pos, void* stream);
 int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream);
 size_t cgnn_power_bins_workspace_bytes(int64_t frames, int32_t num_bins);
 int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t mesh, int32_t order, const int32_t* perm,
