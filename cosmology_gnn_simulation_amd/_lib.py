@@ -39,7 +39,7 @@ EXPORTS = (
     "cgnn_col_dot", "cgnn_col_dot2", "cgnn_col_dot_workspace_bytes", "cgnn_col_dot_ordered", "cgnn_weight_grad_workspace_bytes", "cgnn_weight_grad_ordered", "cgnn_csr_workspace_bytes", "cgnn_csr_build",
     "cgnn_aggregate_csr", "cgnn_aggregate_csr_add", "cgnn_edge_stream", "cgnn_edge_stream_image_bytes", "cgnn_edge_stream_image_build",
     "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
-    "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
+    "cgnn_aggregate_planned_form", "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
     "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
     "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
     "cgnn_knn_adaptive_workspace_bytes", "cgnn_knn_periodic_adaptive", "cgnn_knn_adaptive_sorted_order",
@@ -129,6 +129,8 @@ def load() -> C.CDLL:
     lib.cgnn_aggregate_plan_build.argtypes = [vp, i64, i32, vp, vp]
     lib.cgnn_aggregate_planned.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_aggregate_planned_rows.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, vp]
+    lib.cgnn_aggregate_planned_form.restype = i32
+    lib.cgnn_aggregate_planned_form.argtypes = [i64, i64, i32, i32]
     lib.cgnn_node_block.argtypes = [C.POINTER(Mlp), C.POINTER(Linear), C.POINTER(Linear), vp, vp, i64, vp, i32, i32,
                                     C.POINTER(Linear), C.POINTER(Linear), i32, vp, vp, i32, vp]
     lib.cgnn_knn_workspace_bytes.restype = sz

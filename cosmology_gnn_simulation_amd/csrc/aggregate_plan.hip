@@ -322,9 +322,9 @@ int cgnn_aggregate_planned(const float* table, const int32_t* gather, const void
     return cgnn_aggregate_planned_rows(table, 0, gather, plan, num_nodes, fixed_k, width, out, stream);
 }
 
-int cgnn_aggregate_planned_rows(const float* table, int64_t table_rows, const int32_t* gather, const void* plan,
-                                int64_t num_nodes, int32_t fixed_k, int32_t width, float* out, void* stream) {
-    if (!table || !gather || !plan || !out || num_nodes < 0 || fixed_k <= 0 || width <= 0 || table_rows < 0) {
+// The one place that chooses among the nine compiled forms (host only, no device work): K * 16 + SL.
+int32_t cgnn_aggregate_planned_form(int64_t table_rows, int64_t num_nodes, int32_t fixed_k, int32_t width) {
+    if (num_nodes < 0 || fixed_k <= 0 || width <= 0 || table_rows < 0) {
         set_error("cgnn_aggregate_planned: invalid argument");
         return CGNN_ERR_INVALID_ARG;
     }
@@ -333,30 +333,45 @@ int cgnn_aggregate_planned_rows(const float* table, int64_t table_rows, const in
                   CGNN_AP_MAX_K);
         return CGNN_ERR_UNSUPPORTED;
     }
-    if (num_nodes == 0) return CGNN_OK;
-    const int64_t nblocks = (num_nodes + ap_block_rows(fixed_k) - 1) / ap_block_rows(fixed_k);
-    const PlanView pv = plan_view(const_cast<void*>(plan), nblocks);
-    const int lds = CGNN_AP_STAGE_ROWS * CGNN_AP_ROW_F4 * 16;
-    hipStream_t st = (hipStream_t)stream;
     // unrolled slice loop + branch-free buffer loads / stores: latent 128 / 256 with table and output below 4 GiB (32-bit
     // row offsets).  The table may hold more rows than there are receivers (ghost rows of a spatial shard): its row count
     // must be known (cgnn_aggregate_planned_rows), else the general kernel runs
     const int64_t most_rows = table_rows > num_nodes ? table_rows : num_nodes;
     const int sl = (table_rows > 0 && most_rows * width * 4 <= (int64_t)CGNN_AP_NO_ROW && (width == 128 || width == 256)) ? width / 32 : 0;
-#define CGNN_AP_GO(Kk)                                                                                              \
-    if (sl == 4) CGNN_AP_GO2(Kk, 4) else if (sl == 8) CGNN_AP_GO2(Kk, 8) else CGNN_AP_GO2(Kk, 0)
-#define CGNN_AP_GO2(Kk, SLl)                                                                                        \
-    {                                                                                                               \
+    const int kk = (fixed_k == 16 || fixed_k == 8) ? fixed_k : 0;
+    return kk * 16 + sl;
+}
+
+int cgnn_aggregate_planned_rows(const float* table, int64_t table_rows, const int32_t* gather, const void* plan,
+                                int64_t num_nodes, int32_t fixed_k, int32_t width, float* out, void* stream) {
+    if (!table || !gather || !plan || !out) {
+        set_error("cgnn_aggregate_planned: invalid argument");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    const int32_t form = cgnn_aggregate_planned_form(table_rows, num_nodes, fixed_k, width);
+    if (form < 0) return form;
+    if (num_nodes == 0) return CGNN_OK;
+    const int64_t nblocks = (num_nodes + ap_block_rows(fixed_k) - 1) / ap_block_rows(fixed_k);
+    const PlanView pv = plan_view(const_cast<void*>(plan), nblocks);
+    const int lds = CGNN_AP_STAGE_ROWS * CGNN_AP_ROW_F4 * 16;
+    hipStream_t st = (hipStream_t)stream;
+#define CGNN_AP_GO(Kk, SLl)                                                                                         \
+    case Kk * 16 + SLl: {                                                                                           \
         auto kern = aggregate_planned_kernel<Kk, SLl>;                                                              \
         int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)(lds), "hipFuncSetAttribute(aggregate_planned)");                                               \
         if (rc != CGNN_OK) return rc;                                                                               \
         kern<<<(unsigned)nblocks, CGNN_AP_THREADS, lds, st>>>(table, gather, pv, fixed_k, num_nodes, width, out);    \
+        break;                                                                                                      \
     }
-    if (fixed_k == 16) CGNN_AP_GO(16)
-    else if (fixed_k == 8) CGNN_AP_GO(8)
-    else CGNN_AP_GO(0)
+    switch (form) {      // cgnn_aggregate_planned_form decides, here the form is only looked up
+        CGNN_AP_GO(16, 4) CGNN_AP_GO(16, 8) CGNN_AP_GO(16, 0)
+        CGNN_AP_GO(8, 4) CGNN_AP_GO(8, 8) CGNN_AP_GO(8, 0)
+        CGNN_AP_GO(0, 4) CGNN_AP_GO(0, 8) CGNN_AP_GO(0, 0)
+        default:
+            set_error("cgnn_aggregate_planned: no kernel for form %d", (int)form);
+            return CGNN_ERR_UNSUPPORTED;
+    }
 #undef CGNN_AP_GO
-#undef CGNN_AP_GO2
     return check_hip(hipGetLastError(), "cgnn_aggregate_planned launch");
 }
 

@@ -233,6 +233,13 @@ int cgnn_aggregate_planned(const float* table, const int32_t* gather, const void
  * offsets without branches (faster, same bits). */
 int cgnn_aggregate_planned_rows(const float* table, int64_t table_rows, const int32_t* gather, const void* plan,
                                 int64_t num_nodes, int32_t fixed_k, int32_t width, float* out, void* stream);
+/* Which compiled form of the kernel such a call runs (host only: no pointer, no device work; table_rows = 0 stands for
+ * cgnn_aggregate_planned): K * 16 + SL with K in {8, 16, 0 = runtime k, left to right} and SL in {4, 8, 0 = runtime
+ * slice loop, 64-bit addresses}, e.g. 260 for k = 16 at width 128.  SL != 0 needs width 128 / 256, table_rows > 0 and
+ * max(table_rows, num_nodes) * width * 4 <= 0xfffffbf0.  Negative: the call would be refused with this status
+ * (CGNN_ERR_INVALID_ARG: a negative count, fixed_k <= 0, width <= 0; CGNN_ERR_UNSUPPORTED: width % 32 != 0 or fixed_k >
+ * 32).  The launcher itself chooses through this function. */
+int32_t cgnn_aggregate_planned_form(int64_t table_rows, int64_t num_nodes, int32_t fixed_k, int32_t width);
 
 /* ---- K8+K9: fused node update --------------------------------------------------
  *   u = LayerNorm(MLP(cat[x, agg]))                          graph_network.py:94-96
