@@ -145,12 +145,6 @@ __global__ void fof_init_kernel(int32_t* __restrict__ parent, int64_t n) {
     if (i < n) parent[i] = (int32_t)i;
 }
 
-__device__ __forceinline__ float fof_fold(float d, float box, float half) {
-    if (d > half) d = __fsub_rn(d, box);
-    else if (d < -half) d = __fadd_rn(d, box);
-    return d;
-}
-
 __device__ __forceinline__ int fof_load(const int32_t* parent, int x) {
     return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -191,7 +185,6 @@ __global__ __launch_bounds__(CGNN_FOF_QCHUNK) void fof_walk_kernel(const float4*
     __shared__ int rng_p0[CGNN_FOF_RANGES], rng_len[CGNN_FOF_RANGES], rng_off[CGNN_FOF_RANGES + 1];
     const int tid = threadIdx.x;
     const int items = chunk_start[cells];
-    const int na = G < 3 ? G : 3;      // cells walked per axis
     for (int item = blockIdx.x; item < items; item += gridDim.x) {
         const int q0 = item_q0[item];
         const int c = cell_of[__float_as_int(sorted[q0].w)];      // the item's cell: that of its first query
@@ -199,31 +192,7 @@ __global__ __launch_bounds__(CGNN_FOF_QCHUNK) void fof_walk_kernel(const float4*
         const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
         __syncthreads();               // the previous item's readers of q_s and rng_* are done
         if (tid < nq) q_s[tid] = sorted[q0 + tid];
-        if (tid < CGNN_FOF_RANGES) {
-            const int ix = tid / 9, iy = (tid / 3) % 3, iz = tid % 3;
-            int p0 = 0, len = 0;
-            if (ix < na && iy < na && iz < na) {
-                // G <= 3: all cells of the axis, each once; otherwise c - 1, c, c + 1 wrapped (three distinct cells)
-                const int wx = G <= 3 ? ix : (cx - 1 + ix + G) % G;
-                const int wy = G <= 3 ? iy : (cy - 1 + iy + G) % G;
-                const int wz = G <= 3 ? iz : (cz - 1 + iz + G) % G;
-                const int cell = morton3(wx, wy, wz);
-                p0 = start[cell];
-                len = start[cell + 1] - p0;
-            }
-            rng_p0[tid] = p0;
-            rng_len[tid] = len;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int run = 0;
-            for (int j = 0; j < CGNN_FOF_RANGES; ++j) {
-                rng_off[j] = run;
-                run += rng_len[j];
-            }
-            rng_off[CGNN_FOF_RANGES] = run;
-        }
-        __syncthreads();
+        cell_grid_stage_ranges<CGNN_FOF_RANGES>(tid, cx, cy, cz, G, start, rng_p0, rng_len, rng_off);
         const int nc = rng_off[CGNN_FOF_RANGES];
         for (int t0 = 0; t0 < nc; t0 += CGNN_FOF_QCHUNK) {
             const int t = t0 + tid;
@@ -234,9 +203,9 @@ __global__ __launch_bounds__(CGNN_FOF_QCHUNK) void fof_walk_kernel(const float4*
                 const int bi = __float_as_int(b.w);
                 for (int qi = 0; qi < nq; ++qi) {
                     const float4 a = q_s[qi];
-                    const float dx = fof_fold(__fsub_rn(b.x, a.x), box, half);
-                    const float dy = fof_fold(__fsub_rn(b.y, a.y), box, half);
-                    const float dz = fof_fold(__fsub_rn(b.z, a.z), box, half);
+                    const float dx = cell_grid_fold(__fsub_rn(b.x, a.x), box, half);
+                    const float dy = cell_grid_fold(__fsub_rn(b.y, a.y), box, half);
+                    const float dz = cell_grid_fold(__fsub_rn(b.z, a.z), box, half);
                     const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
                     // the pair is met from both sides: this one unites it (and never a particle with itself)
                     if (d2 < l2 && bi < __float_as_int(a.w)) fof_unite(parent, __float_as_int(a.w), bi);
@@ -285,9 +254,9 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fof_members_kernel(const float* __
     const bool member = r >= 0 && r != i;
     long long q0 = 0, q1 = 0, q2 = 0;  // the root's own displacement is 0
     if (member && disp != nullptr) {
-        q0 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 0], pos[3 * (int64_t)r + 0]), box, half), scale));
-        q1 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 1], pos[3 * (int64_t)r + 1]), box, half), scale));
-        q2 = __double2ll_rn(__dmul_rn((double)fof_fold(__fsub_rn(pos[3 * i + 2], pos[3 * (int64_t)r + 2]), box, half), scale));
+        q0 = __double2ll_rn(__dmul_rn((double)cell_grid_fold(__fsub_rn(pos[3 * i + 0], pos[3 * (int64_t)r + 0]), box, half), scale));
+        q1 = __double2ll_rn(__dmul_rn((double)cell_grid_fold(__fsub_rn(pos[3 * i + 1], pos[3 * (int64_t)r + 1]), box, half), scale));
+        q2 = __double2ll_rn(__dmul_rn((double)cell_grid_fold(__fsub_rn(pos[3 * i + 2], pos[3 * (int64_t)r + 2]), box, half), scale));
     }
     unsigned long long todo = __ballot(member);      // wave-uniform: every lane runs every round
     while (todo != 0) {

@@ -17,37 +17,117 @@
 #include "scan.hpp"
 #include "cell_grid.hpp"   // spread3 / morton3 / cell_coord and the count / fill kernels of the counting sort
 
+#include <string>
+#include <type_traits>
+
 namespace cgnn {
 
-struct KnnLayout {
-    int G;                // cells per axis
-    int64_t cells;        // Gp^3 cell slots, Gp = G rounded up to a power of two (Morton-coded ids)
-    size_t off_count, off_start, off_cursor, off_bsum, off_cellof, off_sorted, total;
+// The uniform grid of a box of n particles: G cells per axis (about two particles per cell), and Gp^3 cell slots,
+// Gp = G rounded up to a power of two (Morton-coded ids).
+struct KnnGrid {
+    int G;
+    int64_t cells;
 };
 
-static KnnLayout knn_layout(int64_t n) {
-    KnnLayout L;
+static KnnGrid knn_grid(int64_t n) {
+    KnnGrid U;
     int G = (int)floor(cbrt((double)n / 2.0));
     if (G < 1) G = 1;
     if (G > 256) G = 256;
-    L.G = G;
+    U.G = G;
     int Gp = 1;
     while (Gp < G) Gp <<= 1;
-    L.cells = (int64_t)Gp * Gp * Gp;
+    U.cells = (int64_t)Gp * Gp * Gp;
+    return U;
+}
+
+// One workspace, seen through typed pointers (over a null workspace: only `total`, its size in bytes, means anything).
+// Uniform and batched: count / start / cursor over the cell table.  Adaptive: count / start are the leaves per cell and
+// their scan (the leaf base), lcount / lstart the leaf table; the pointers of the other layout stay null.
+struct KnnWorkspace {
+    int G;                // cells per axis (single-graph layouts)
+    int64_t cells;        // cell slots; batched: those of all graphs
+    int64_t max_leaves;   // adaptive: cells + 2 n bounds the number of leaves for every input
+    int32_t *count, *start, *cursor, *lcount, *lstart, *bsum, *item_of;   // item_of: a particle's cell or leaf
+    float4* sorted;
+    size_t total;
+};
+
+template <typename T>
+static T* knn_carve(void* workspace, size_t& off, size_t items) {
+    T* p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(workspace) + off);
+    off = align256(off + items * sizeof(T));
+    return p;
+}
+
+// `rows` particles over `cells` cell slots: one graph's grid, or the batch's shared table
+static KnnWorkspace knn_uniform_workspace(void* workspace, KnnGrid U, int64_t rows) {
+    KnnWorkspace W = {};
+    W.G = U.G;
+    W.cells = U.cells;
+    const int64_t cells = U.cells;
     size_t off = 0;
-    L.off_count = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
-    L.off_start = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
-    L.off_cursor = off; off = align256(off + (size_t)(L.cells + 1) * 4);
-    const size_t nblk = (size_t)((L.cells + 1 + CGNN_SCAN_ITEMS - 1) / CGNN_SCAN_ITEMS);
-    L.off_bsum = off;   off = align256(off + (nblk + 1) * 4);
-    L.off_cellof = off; off = align256(off + (size_t)n * 4);
-    L.off_sorted = off; off = align256(off + (size_t)n * 16);
-    L.total = off;
-    return L;
+    W.count = knn_carve<int32_t>(workspace, off, (size_t)(cells + 1));
+    W.start = knn_carve<int32_t>(workspace, off, (size_t)(cells + 1));
+    W.cursor = knn_carve<int32_t>(workspace, off, (size_t)(cells + 1));
+    W.bsum = knn_carve<int32_t>(workspace, off, (size_t)(scan_blocks(cells + 1) + 1));
+    W.item_of = knn_carve<int32_t>(workspace, off, (size_t)rows);
+    W.sorted = knn_carve<float4>(workspace, off, (size_t)rows);
+    W.total = off;
+    return W;
 }
 
 #define CGNN_KNN_IDX_BITS 27
 #define CGNN_KNN_IDX_MASK ((1u << CGNN_KNN_IDX_BITS) - 1u)
+
+// ---- what the three searches share on the device ----------------------------------------------------------------------
+// The query prologue, the candidate loop (adaptive and batched) and the epilogue.  The shell walk with its stopping rule
+// stays written out in each kernel, word for word: through one shared walk with a per-kernel visitor the uniform search
+// ran 7-10 % slower on clustered input and the other two 1-3 % slower at k = 16 (the parent-relative speed check).
+
+// A query: the particle query_ids[t] into output row t, or, without query_ids, the particle of sorted slot t into its
+// own row -- queries then walk in cell (leaf) order and neighbouring lanes touch the same cells.
+__device__ __forceinline__ float3 knn_load_query(const float* __restrict__ pos, const float4* __restrict__ sorted,
+                                                 const int32_t* __restrict__ query_ids, int64_t t, int64_t& out_row) {
+    if (query_ids != nullptr) {
+        const int q = query_ids[t];
+        out_row = t;
+        return make_float3(pos[3 * (int64_t)q + 0], pos[3 * (int64_t)q + 1], pos[3 * (int64_t)q + 2]);
+    }
+    const float4 s = sorted[t];
+    out_row = __float_as_int(s.w);
+    return make_float3(s.x, s.y, s.z);
+}
+
+// The candidate loop over sorted[p0..p1): every candidate is the image fl32(pos + shift) the reference would have put in
+// its extended array, ranked by (d2, key) into the sorted list bd / bi.  The uniform kernel keeps its own copy: calling
+// this one there costs K = 32 a wave per SIMD (123 -> 152 VGPRs, the occupancy check).
+template <int K>
+__device__ __forceinline__ void knn_scan_range(float (&bd)[K], unsigned (&bi)[K], const float4* __restrict__ sorted,
+                                               int p0, int p1, float shx, float shy, float shz, unsigned shift_id,
+                                               float qx, float qy, float qz) {
+    for (int p = p0; p < p1; ++p) {
+        const float4 c = sorted[p];
+        const float ex = __fadd_rn(c.x, shx), ey = __fadd_rn(c.y, shy), ez = __fadd_rn(c.z, shz);
+        const float ddx = __fsub_rn(ex, qx), ddy = __fsub_rn(ey, qy), ddz = __fsub_rn(ez, qz);
+        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)), __fmul_rn(ddz, ddz));
+        const unsigned key = (shift_id << CGNN_KNN_IDX_BITS) | (unsigned)__float_as_int(c.w);
+        if (d2 < bd[K - 1] || (d2 == bd[K - 1] && key < bi[K - 1])) {
+            bd[K - 1] = d2;
+            bi[K - 1] = key;
+#pragma unroll
+            for (int j = K - 1; j > 0; --j) {
+                const bool sw = bd[j] < bd[j - 1] || (bd[j] == bd[j - 1] && bi[j] < bi[j - 1]);
+                const float td = bd[j];
+                const unsigned ti = bi[j];
+                bd[j] = sw ? bd[j - 1] : td;
+                bi[j] = sw ? bi[j - 1] : ti;
+                bd[j - 1] = sw ? td : bd[j - 1];
+                bi[j - 1] = sw ? ti : bi[j - 1];
+            }
+        }
+    }
+}
 
 // Edge features of CGNN_KNN_EDGE_ATTR_IMAGE (cgnn.h): the displacement to the image the scan loop ranked,
 // fl32(fl32(pos[snd] + shift) - q), shift decoded from the top bits of the candidate's key
@@ -63,8 +143,35 @@ __device__ __forceinline__ float4 knn_image_edge_attr(const float* __restrict__ 
     return make_float4(ax, ay, az, nn);
 }
 
-// MODE (both search kernels): CGNN_KNN_EDGE_ATTR_REFERENCE or CGNN_KNN_EDGE_ATTR_IMAGE, a compile-time parameter of
-// the epilogue alone; the reference instantiation is instruction for instruction the kernel without the parameter.
+// Row out_row of the outputs from the finished list: senders (bi's particle index, local to `pos`, plus sender_base) and,
+// where edge_attr is given, the edge features.  MODE is CGNN_KNN_EDGE_ATTR_REFERENCE or CGNN_KNN_EDGE_ATTR_IMAGE, a
+// compile-time parameter of this epilogue alone.
+template <int K, int MODE>
+__device__ __forceinline__ void knn_write_row(const float* __restrict__ pos, float box, float3 q, const unsigned (&bi)[K],
+                                              int k, int64_t out_row, int sender_base, int32_t* __restrict__ senders,
+                                              float* __restrict__ edge_attr) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (j < k) {
+            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
+            senders[out_row * k + j] = sender_base + snd;
+            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
+                if (edge_attr != nullptr)
+                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
+                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, q.x, q.y, q.z);
+            } else if (edge_attr != nullptr) {
+                // reference data_utils.py:162-164: mapped (un-shifted) sender minus receiver
+                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], q.x);
+                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], q.y);
+                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], q.z);
+                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
+                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
+            }
+        }
+    }
+}
+
+// grid = "uniform": a visited cell is one range of `sorted`; the candidate loop is written out (see knn_scan_range).
 template <int K, int MODE>
 __global__ __launch_bounds__(CGNN_BLOCK) void knn_search_kernel(const float* __restrict__ pos, int64_t n, float box,
                                                                 float h, float inv_h, int G,
@@ -76,21 +183,9 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_search_kernel(const float* __r
                                                                 float* __restrict__ edge_attr) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nq) return;
-    float qx, qy, qz;
     int64_t out_row;  // row of the outputs this query fills
-    if (query_ids != nullptr) {
-        const int q = query_ids[t];
-        qx = pos[3 * (int64_t)q + 0];
-        qy = pos[3 * (int64_t)q + 1];
-        qz = pos[3 * (int64_t)q + 2];
-        out_row = t;
-    } else {
-        const float4 s = sorted[t];  // walk queries in cell order: neighbouring lanes touch the same cells
-        qx = s.x;
-        qy = s.y;
-        qz = s.z;
-        out_row = __float_as_int(s.w);
-    }
+    const float3 q = knn_load_query(pos, sorted, query_ids, t, out_row);
+    const float qx = q.x, qy = q.y, qz = q.z;
     const int cx = cell_coord(qx, inv_h, G), cy = cell_coord(qy, inv_h, G), cz = cell_coord(qz, inv_h, G);
 
     float bd[K];
@@ -160,26 +255,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_search_kernel(const float* __r
         for (int j = 0; j < K; ++j) kth = (j == k - 1) ? bd[j] : kth;  // static indices: bd stays in registers
         if (bound > 0.f && kth <= bound * bound) break;
     }
-    const float px = qx, py = qy, pz = qz;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j < k) {
-            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
-            senders[out_row * k + j] = snd;
-            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
-                if (edge_attr != nullptr)
-                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
-                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, px, py, pz);
-            } else if (edge_attr != nullptr) {
-                // reference data_utils.py:162-164: mapped (un-shifted) sender minus receiver
-                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], px);
-                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], py);
-                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], pz);
-                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
-                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
-            }
-        }
-    }
+    knn_write_row<K, MODE>(pos, box, q, bi, k, out_row, 0, senders, edge_attr);
 }
 
 __global__ void knn_perm_kernel(const float4* __restrict__ sorted, int64_t n, int32_t* __restrict__ perm) {
@@ -209,29 +285,22 @@ __global__ void knn_perm_kernel(const float4* __restrict__ sorted, int64_t n, in
 #define CGNN_KNNA_SMAX 6   // at most 64 leaves per axis and cell (G <= 256: fine coordinates stay below 2^14)
 #define CGNN_KNNA_DIRECT 8 // a block with at most this many particles is scanned without descending further
 
-struct KnnAdaptiveLayout {
-    int G;
-    int64_t cells;        // as KnnLayout
-    int64_t max_leaves;   // cells + 2 n bounds the number of leaves for every input
-    size_t off_nleaf, off_lbase, off_lcount, off_lstart, off_bsum, off_leafof, off_sorted, total;
-};
-
-static KnnAdaptiveLayout knn_adaptive_layout(int64_t n) {
-    const KnnLayout U = knn_layout(n);
-    KnnAdaptiveLayout L;
-    L.G = U.G;
-    L.cells = U.cells;
-    L.max_leaves = U.cells + 2 * n;
+static KnnWorkspace knn_adaptive_workspace(void* workspace, int64_t n) {
+    const KnnGrid U = knn_grid(n);
+    KnnWorkspace W = {};
+    W.G = U.G;
+    W.cells = U.cells;
+    W.max_leaves = U.cells + 2 * n;
     size_t off = 0;
-    L.off_nleaf = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
-    L.off_lbase = off;  off = align256(off + (size_t)(L.cells + 1) * 4);
-    L.off_lcount = off; off = align256(off + (size_t)(L.max_leaves + 1) * 4);
-    L.off_lstart = off; off = align256(off + (size_t)(L.max_leaves + 1) * 4);
-    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(L.max_leaves + 1) + 1) * 4);
-    L.off_leafof = off; off = align256(off + (size_t)n * 4);
-    L.off_sorted = off; off = align256(off + (size_t)n * 16);
-    L.total = off;
-    return L;
+    W.count = knn_carve<int32_t>(workspace, off, (size_t)(W.cells + 1));
+    W.start = knn_carve<int32_t>(workspace, off, (size_t)(W.cells + 1));
+    W.lcount = knn_carve<int32_t>(workspace, off, (size_t)(W.max_leaves + 1));
+    W.lstart = knn_carve<int32_t>(workspace, off, (size_t)(W.max_leaves + 1));
+    W.bsum = knn_carve<int32_t>(workspace, off, (size_t)(scan_blocks(W.max_leaves + 1) + 1));
+    W.item_of = knn_carve<int32_t>(workspace, off, (size_t)n);
+    W.sorted = knn_carve<float4>(workspace, off, (size_t)n);
+    W.total = off;
+    return W;
 }
 
 // Leaf coordinate inside coarse cell coordinate c at depth s.  u = fl32(p * inv_h) is the product cell_coord floors,
@@ -286,34 +355,6 @@ __global__ void knna_fill_kernel(const float* __restrict__ pos, int64_t n, const
     sorted[slot] = make_float4(pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], __int_as_float((int)i));
 }
 
-// The uniform kernel's candidate loop over sorted[p0..p1): same expressions, same insertion.
-template <int K>
-__device__ __forceinline__ void knn_scan_range(float (&bd)[K], unsigned (&bi)[K], const float4* __restrict__ sorted,
-                                               int p0, int p1, float shx, float shy, float shz, unsigned shift_id,
-                                               float qx, float qy, float qz) {
-    for (int p = p0; p < p1; ++p) {
-        const float4 c = sorted[p];
-        const float ex = __fadd_rn(c.x, shx), ey = __fadd_rn(c.y, shy), ez = __fadd_rn(c.z, shz);
-        const float ddx = __fsub_rn(ex, qx), ddy = __fsub_rn(ey, qy), ddz = __fsub_rn(ez, qz);
-        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)), __fmul_rn(ddz, ddz));
-        const unsigned key = (shift_id << CGNN_KNN_IDX_BITS) | (unsigned)__float_as_int(c.w);
-        if (d2 < bd[K - 1] || (d2 == bd[K - 1] && key < bi[K - 1])) {
-            bd[K - 1] = d2;
-            bi[K - 1] = key;
-#pragma unroll
-            for (int j = K - 1; j > 0; --j) {
-                const bool sw = bd[j] < bd[j - 1] || (bd[j] == bd[j - 1] && bi[j] < bi[j - 1]);
-                const float td = bd[j];
-                const unsigned ti = bi[j];
-                bd[j] = sw ? bd[j - 1] : td;
-                bi[j] = sw ? bi[j - 1] : ti;
-                bd[j - 1] = sw ? td : bd[j - 1];
-                bi[j - 1] = sw ? ti : bi[j - 1];
-            }
-        }
-    }
-}
-
 // True only when no image in the box [lo, hi) (per axis, already shifted) can enter a list whose last entry is
 // `worst`.  A particle sorted into the box lies inside it up to the rounding of p * inv_h, of lo / hi themselves and
 // of fl32(p + shift): under 1e-6 box together, covered by the 1e-5 box taken off every gap.  The candidate loop's d2
@@ -335,21 +376,9 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
     float* __restrict__ edge_attr) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nq) return;
-    float qx, qy, qz;
-    int64_t out_row;
-    if (query_ids != nullptr) {
-        const int q = query_ids[t];
-        qx = pos[3 * (int64_t)q + 0];
-        qy = pos[3 * (int64_t)q + 1];
-        qz = pos[3 * (int64_t)q + 2];
-        out_row = t;
-    } else {
-        const float4 s = sorted[t];  // leaf order: neighbouring lanes share cells and, in a refined cell, leaves
-        qx = s.x;
-        qy = s.y;
-        qz = s.z;
-        out_row = __float_as_int(s.w);
-    }
+    int64_t out_row;  // row of the outputs this query fills
+    const float3 q = knn_load_query(pos, sorted, query_ids, t, out_row);
+    const float qx = q.x, qy = q.y, qz = q.z;
     const int cx = cell_coord(qx, inv_h, G), cy = cell_coord(qy, inv_h, G), cz = cell_coord(qz, inv_h, G);
     const float slack = 1e-5f * box;
 
@@ -454,25 +483,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_adaptive_search_kernel(
         for (int j = 0; j < K; ++j) kth = (j == k - 1) ? bd[j] : kth;
         if (bound > 0.f && kth <= bound * bound) break;
     }
-    const float px = qx, py = qy, pz = qz;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j < k) {
-            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);
-            senders[out_row * k + j] = snd;
-            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
-                if (edge_attr != nullptr)
-                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
-                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, px, py, pz);
-            } else if (edge_attr != nullptr) {
-                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], px);
-                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], py);
-                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], pz);
-                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
-                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
-            }
-        }
-    }
+    knn_write_row<K, MODE>(pos, box, q, bi, k, out_row, 0, senders, edge_attr);
 }
 
 // ===================================================================================================================
@@ -531,8 +542,8 @@ __global__ void knn_batched_fill_kernel(const float* __restrict__ pos, const Knn
     sorted[slot] = make_float4(pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], __int_as_float(local));
 }
 
-// knn_search_kernel for the sorted slot t of a batch: the same shell walk, candidate loop (knn_scan_range), stopping
-// rule and epilogue on graph g's own positions and cells.
+// knn_search_kernel for the sorted slot t of a batch: the same shell walk and stopping rule on graph g's own positions
+// and cells; the epilogue adds the row base to the row and to every sender.
 template <int K, int MODE>
 __global__ __launch_bounds__(CGNN_BLOCK) void knn_batched_search_kernel(const float* __restrict__ pos_all,
                                                                         const KnnBatchTable T, float box,
@@ -595,24 +606,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void knn_batched_search_kernel(const fl
         for (int j = 0; j < K; ++j) kth = (j == k - 1) ? bd[j] : kth;  // static indices: bd stays in registers
         if (bound > 0.f && kth <= bound * bound) break;
     }
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j < k) {
-            const int snd = (int)(bi[j] & CGNN_KNN_IDX_MASK);    // local to graph g
-            senders[out_row * k + j] = row_base + snd;
-            if (MODE == CGNN_KNN_EDGE_ATTR_IMAGE) {
-                if (edge_attr != nullptr)
-                    *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) =
-                        knn_image_edge_attr(pos, snd, bi[j] >> CGNN_KNN_IDX_BITS, box, qx, qy, qz);
-            } else if (edge_attr != nullptr) {
-                const float ax = __fsub_rn(pos[3 * (int64_t)snd + 0], qx);
-                const float ay = __fsub_rn(pos[3 * (int64_t)snd + 1], qy);
-                const float az = __fsub_rn(pos[3 * (int64_t)snd + 2], qz);
-                const float nn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az)));
-                *reinterpret_cast<float4*>(edge_attr + (out_row * k + j) * 4) = make_float4(ax, ay, az, nn);
-            }
-        }
-    }
+    knn_write_row<K, MODE>(pos, box, make_float3(qx, qy, qz), bi, k, out_row, row_base, senders, edge_attr);
 }
 
 __global__ void knn_batched_perm_kernel(const float4* __restrict__ sorted, const KnnBatchTable T,
@@ -622,54 +616,13 @@ __global__ void knn_batched_perm_kernel(const float4* __restrict__ sorted, const
     perm[i] = T.row_base[knn_batch_graph(T, (int)i)] + __float_as_int(sorted[i].w);
 }
 
-struct KnnBatchedLayout {
-    int64_t n_total, cells;   // cells: all graphs' cell slots
-    size_t off_count, off_start, off_cursor, off_bsum, off_cellof, off_sorted, total;
-};
-
-// CGNN_OK, or why the offsets are refused (nothing is written to L then)
-static int knn_batched_layout(const char* who, const int64_t* offsets, int32_t num_graphs, KnnBatchedLayout& L) {
-    if (!offsets || num_graphs < 1 || offsets[0] != 0) {
-        set_error("%s: offsets must hold num_graphs + 1 >= 2 values starting at 0", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    int64_t cells = 0;
-    bool too_large = false;
-    for (int32_t g = 0; g < num_graphs; ++g) {
-        const int64_t n = offsets[g + 1] - offsets[g];
-        if (n <= 0) {
-            set_error("%s: graph %d is empty or offsets do not increase", who, (int)g);
-            return CGNN_ERR_INVALID_ARG;
-        }
-        if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) too_large = true;
-        else cells += knn_layout(n).cells;
-    }
-    // the shared cell table is indexed with int32 (cells < 4 n per graph: reached only far beyond 2^29 particles)
-    if (too_large || offsets[num_graphs] >= ((int64_t)1 << 31) || cells + 1 >= ((int64_t)1 << 31)) {
-        set_error("%s: 2^%d or more particles in one graph, or 2^31 or more rows or cells in all, are not supported", who,
-                  CGNN_KNN_IDX_BITS);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    L.n_total = offsets[num_graphs];
-    L.cells = cells;
-    size_t off = 0;
-    L.off_count = off;  off = align256(off + (size_t)(cells + 1) * 4);
-    L.off_start = off;  off = align256(off + (size_t)(cells + 1) * 4);
-    L.off_cursor = off; off = align256(off + (size_t)(cells + 1) * 4);
-    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(cells + 1) + 1) * 4);
-    L.off_cellof = off; off = align256(off + (size_t)L.n_total * 4);
-    L.off_sorted = off; off = align256(off + (size_t)L.n_total * 16);
-    L.total = off;
-    return CGNN_OK;
-}
-
 // the table of graphs [g0, g0 + count); cell_base: the first cell of graph g0, advanced past the group
 static KnnBatchTable knn_batch_table(const int64_t* offsets, int32_t g0, int32_t count, float box_size,
                                      int64_t& cell_base) {
     KnnBatchTable T = {};
     T.count = count;
     for (int32_t j = 0; j < count; ++j) {
-        const KnnLayout U = knn_layout(offsets[g0 + j + 1] - offsets[g0 + j]);
+        const KnnGrid U = knn_grid(offsets[g0 + j + 1] - offsets[g0 + j]);
         T.row_base[j] = (int32_t)offsets[g0 + j];
         T.cell_base[j] = (int32_t)cell_base;
         T.G[j] = U.G;
@@ -681,23 +634,12 @@ static KnnBatchTable knn_batch_table(const int64_t* offsets, int32_t g0, int32_t
     return T;
 }
 
-}  // namespace cgnn
+// ---- the host side the entries share -----------------------------------------------------------------------------------
 
-using namespace cgnn;
-
-extern "C" {
-
-size_t cgnn_knn_workspace_bytes(int64_t n, int32_t k) {
-    (void)k;
-    if (n <= 0) return 256;
-    return knn_layout(n).total;
-}
-
-// cgnn_knn_periodic and cgnn_knn_periodic_mode: `who` names the entry in error messages
-static int knn_periodic_run(const char* who, int32_t mode, const float* pos, int64_t n, float box_size, int32_t k,
-                            const int32_t* query_ids, int64_t nq, int32_t* senders, float* edge_attr, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    if (!pos || !senders || !workspace || n <= 0 || k <= 0 || !(box_size > 0.f)) {
+// `who` names the entry in error messages
+static int knn_check_common(const char* who, int32_t mode, const float* pos, const int32_t* senders,
+                            const void* workspace, int32_t k, float box_size) {
+    if (!pos || !senders || !workspace || k <= 0 || !(box_size > 0.f)) {
         set_error("%s: invalid argument", who);
         return CGNN_ERR_INVALID_ARG;
     }
@@ -709,202 +651,268 @@ static int knn_periodic_run(const char* who, int32_t mode, const float* pos, int
         set_error("%s: k=%d > 64 is not compiled", who, k);
         return CGNN_ERR_UNSUPPORTED;
     }
+    return CGNN_OK;
+}
+
+static int knn_batch_too_large(const char* who) {
+    set_error("%s: 2^%d or more particles in one graph, or 2^31 or more rows or cells in all, are not supported", who,
+              CGNN_KNN_IDX_BITS);
+    return CGNN_ERR_UNSUPPORTED;
+}
+
+// One graph of n particles: n > 0, k <= 27 n images, n < 2^27 (the index bits of a candidate's key).  g is the graph's
+// number in a batch, or -1 in a single-graph entry; k = 1 where the entry has no k to check.
+static int knn_check_graph(const char* who, int64_t n, int32_t k, int32_t g) {
+    if (n <= 0) {
+        if (g < 0) set_error("%s: invalid argument", who);
+        else set_error("%s: graph %d is empty or offsets do not increase", who, (int)g);
+        return CGNN_ERR_INVALID_ARG;
+    }
     if ((int64_t)k > 27 * n) {
-        set_error("%s: k=%d exceeds the 27*n=%lld periodic images", who, k, (long long)(27 * n));
+        if (g < 0) set_error("%s: k=%d exceeds the 27*n=%lld periodic images", who, k, (long long)(27 * n));
+        else set_error("%s: k=%d exceeds the 27*n=%lld periodic images of graph %d", who, k, (long long)(27 * n), (int)g);
         return CGNN_ERR_INVALID_ARG;
     }
     if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) {
-        set_error("%s: n=%lld >= 2^%d particles per call is not supported", who, (long long)n,
-                  CGNN_KNN_IDX_BITS);
+        if (g < 0)
+            set_error("%s: n=%lld >= 2^%d particles per call is not supported", who, (long long)n, CGNN_KNN_IDX_BITS);
+        else
+            return knn_batch_too_large(who);
         return CGNN_ERR_UNSUPPORTED;
     }
+    return CGNN_OK;
+}
+
+static int knn_check_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t required) {
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
         set_error("%s: workspace must be 16-byte aligned", who);
         return CGNN_ERR_INVALID_ARG;
     }
-    const KnnLayout L = knn_layout(n);
-    if (workspace_bytes < L.total) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
+    if (workspace_bytes < required) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, required);
         return CGNN_ERR_WORKSPACE;
     }
+    return CGNN_OK;
+}
+
+// launch(K, M) with the list length K = 8 / 16 / 32 / 64 that holds k and the edge-feature mode M as
+// std::integral_constant values: the one place where the 4 x 2 instantiations of a search kernel are chosen
+template <typename Launch>
+static void knn_dispatch(int32_t k, int32_t mode, Launch&& launch) {
+    auto with_mode = [&](auto K) {
+        if (mode == CGNN_KNN_EDGE_ATTR_IMAGE) launch(K, std::integral_constant<int, CGNN_KNN_EDGE_ATTR_IMAGE>());
+        else launch(K, std::integral_constant<int, CGNN_KNN_EDGE_ATTR_REFERENCE>());
+    };
+    if (k <= 8) with_mode(std::integral_constant<int, 8>());
+    else if (k <= 16) with_mode(std::integral_constant<int, 16>());
+    else if (k <= 32) with_mode(std::integral_constant<int, 32>());
+    else with_mode(std::integral_constant<int, 64>());
+}
+
+static unsigned knn_blocks(int64_t rows) { return (unsigned)((rows + CGNN_BLOCK - 1) / CGNN_BLOCK); }
+
+// W.sorted of the uniform grid: count, scan, fill
+static int knn_build_uniform(const KnnWorkspace& W, const float* pos, int64_t n, float inv_h, hipStream_t st) {
+    const int64_t m = W.cells + 1;  // count[cells] = 0 so that start[cells] = n
+    int rc = check_hip(hipMemsetAsync(W.count, 0, (size_t)m * 4, st), "knn memset count");
+    if (rc) return rc;
+    rc = check_hip(hipMemsetAsync(W.cursor, 0, (size_t)m * 4, st), "knn memset cursor");
+    if (rc) return rc;
+    knn_count_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, st>>>(pos, n, inv_h, W.G, W.item_of, W.count);
+    exclusive_scan_i32(W.count, m, W.bsum, W.start, st);
+    knn_fill_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, st>>>(pos, n, W.item_of, W.start, W.cursor, W.sorted);
+    return CGNN_OK;
+}
+
+// W.sorted of the adaptive grid: coarse counts -> leaves per cell -> leaf bases; leaf counts -> leaf starts -> fill
+static int knn_build_adaptive(const KnnWorkspace& W, const float* pos, int64_t n, float inv_h, hipStream_t st) {
+    const int64_t mc = W.cells + 1;       // count[cells] = 0 so that start[cells] = number of leaves
+    const int64_t ml = W.max_leaves + 1;  // lcount is 0 from the last leaf on so that lstart = n there
+    int rc = check_hip(hipMemsetAsync(W.count, 0, (size_t)mc * 4, st), "knn adaptive memset cell counts");
+    if (rc) return rc;
+    rc = check_hip(hipMemsetAsync(W.lcount, 0, (size_t)ml * 4, st), "knn adaptive memset leaf counts");
+    if (rc) return rc;
+    knn_count_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, st>>>(pos, n, inv_h, W.G, W.item_of, W.count);  // item_of: overwritten below
+    knna_depth_kernel<<<knn_blocks(W.cells), CGNN_BLOCK, 0, st>>>(W.count, W.cells);
+    exclusive_scan_i32(W.count, mc, W.bsum, W.start, st);
+    knna_leaf_count_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, st>>>(pos, n, inv_h, W.G, W.start, W.item_of, W.lcount);
+    exclusive_scan_i32(W.lcount, ml, W.bsum, W.lstart, st);
+    knna_fill_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, st>>>(pos, n, W.item_of, W.lstart, W.lcount, W.sorted);
+    return CGNN_OK;
+}
+
+// The four single-graph entries: cgnn_knn_periodic[_adaptive][_mode]
+static int knn_periodic_run(const char* who, bool adaptive, int32_t mode, const float* pos, int64_t n, float box_size,
+                            int32_t k, const int32_t* query_ids, int64_t nq, int32_t* senders, float* edge_attr,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = knn_check_common(who, mode, pos, senders, workspace, k, box_size);
+    if (rc) return rc;
+    rc = knn_check_graph(who, n, k, -1);
+    if (rc) return rc;
+    const KnnWorkspace W = adaptive ? knn_adaptive_workspace(workspace, n) : knn_uniform_workspace(workspace, knn_grid(n), n);
+    rc = knn_check_workspace(who, workspace, workspace_bytes, W.total);
+    if (rc) return rc;
     if (query_ids == nullptr) nq = n;
     if (nq < 0) {
         set_error("%s: negative query count", who);
         return CGNN_ERR_INVALID_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* count = reinterpret_cast<int32_t*>(ws + L.off_count);
-    int32_t* start = reinterpret_cast<int32_t*>(ws + L.off_start);
-    int32_t* cursor = reinterpret_cast<int32_t*>(ws + L.off_cursor);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
-    int32_t* cell_of = reinterpret_cast<int32_t*>(ws + L.off_cellof);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
-    const int G = L.G;
+    const int G = W.G;
     const float h = box_size / (float)G;
     const float inv_h = (float)G / box_size;
-    const int64_t m = L.cells + 1;  // count[cells] = 0 so that start[cells] = n
-    int rc = check_hip(hipMemsetAsync(count, 0, (size_t)m * 4, st), "knn memset count");
+    rc = adaptive ? knn_build_adaptive(W, pos, n, inv_h, st) : knn_build_uniform(W, pos, n, inv_h, st);
     if (rc) return rc;
-    rc = check_hip(hipMemsetAsync(cursor, 0, (size_t)m * 4, st), "knn memset cursor");
-    if (rc) return rc;
-    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
-    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, cell_of, count);
-    exclusive_scan_i32(count, m, bsum, start, st);
-    knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, cell_of, start, cursor, sorted);
     rc = check_hip(hipGetLastError(), who);
     if (rc) return rc;
     if (nq == 0) return CGNN_OK;
-    const unsigned qb = (unsigned)((nq + CGNN_BLOCK - 1) / CGNN_BLOCK);
-#define CGNN_KNN_LAUNCH_MODE(KK, MM)                                                                              \
-    knn_search_kernel<KK, MM><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, start, cell_of, sorted,       \
-                                                         query_ids, nq, k, senders, edge_attr)
-#define CGNN_KNN_LAUNCH(KK)                                                      \
-    do {                                                                         \
-        if (mode == CGNN_KNN_EDGE_ATTR_IMAGE)                                    \
-            CGNN_KNN_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                  \
-        else                                                                     \
-            CGNN_KNN_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);              \
-    } while (0)
-    if (k <= 8)
-        CGNN_KNN_LAUNCH(8);
-    else if (k <= 16)
-        CGNN_KNN_LAUNCH(16);
-    else if (k <= 32)
-        CGNN_KNN_LAUNCH(32);
-    else
-        CGNN_KNN_LAUNCH(64);
-#undef CGNN_KNN_LAUNCH
-#undef CGNN_KNN_LAUNCH_MODE
+    knn_dispatch(k, mode, [&](auto K, auto M) {
+        if (adaptive)
+            knn_adaptive_search_kernel<decltype(K)::value, decltype(M)::value><<<knn_blocks(nq), CGNN_BLOCK, 0, st>>>(
+                pos, n, box_size, h, inv_h, G, W.start, W.lstart, W.sorted, query_ids, nq, k, senders, edge_attr);
+        else
+            knn_search_kernel<decltype(K)::value, decltype(M)::value><<<knn_blocks(nq), CGNN_BLOCK, 0, st>>>(
+                pos, n, box_size, h, inv_h, G, W.start, W.item_of, W.sorted, query_ids, nq, k, senders, edge_attr);
+    });
     return check_hip(hipGetLastError(), who);
+}
+
+// cgnn_knn_sorted_order and cgnn_knn_adaptive_sorted_order
+static int knn_sorted_order_run(const char* who, bool adaptive, const void* workspace, int64_t n, int32_t* perm,
+                                void* stream) {
+    if (!workspace || !perm || n <= 0) {
+        set_error("%s: invalid argument", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    void* ws = const_cast<void*>(workspace);
+    const KnnWorkspace W = adaptive ? knn_adaptive_workspace(ws, n) : knn_uniform_workspace(ws, knn_grid(n), n);
+    knn_perm_kernel<<<knn_blocks(n), CGNN_BLOCK, 0, (hipStream_t)stream>>>(W.sorted, n, perm);
+    return check_hip(hipGetLastError(), (std::string(who) + " launch").c_str());
+}
+
+// The batch's workspace over `workspace` (null: sizes only): CGNN_OK, or why the offsets are refused (nothing is written
+// to W then).  k as knn_check_graph takes it.
+static int knn_batched_workspace(const char* who, const int64_t* offsets, int32_t num_graphs, int32_t k, void* workspace,
+                                 KnnWorkspace& W) {
+    if (!offsets || num_graphs < 1 || offsets[0] != 0) {
+        set_error("%s: offsets must hold num_graphs + 1 >= 2 values starting at 0", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    int64_t cells = 0;
+    for (int32_t g = 0; g < num_graphs; ++g) {
+        const int64_t n = offsets[g + 1] - offsets[g];
+        const int rc = knn_check_graph(who, n, k, g);
+        if (rc) return rc;
+        cells += knn_grid(n).cells;
+    }
+    // the shared cell table is indexed with int32 (cells < 4 n per graph: reached only far beyond 2^29 particles)
+    if (offsets[num_graphs] >= ((int64_t)1 << 31) || cells + 1 >= ((int64_t)1 << 31))
+        return knn_batch_too_large(who);
+    W = knn_uniform_workspace(workspace, KnnGrid{0, cells}, offsets[num_graphs]);   // G: each graph's own, in its table
+    return CGNN_OK;
+}
+
+}  // namespace cgnn
+
+using namespace cgnn;
+
+extern "C" {
+
+size_t cgnn_knn_workspace_bytes(int64_t n, int32_t k) {
+    (void)k;
+    if (n <= 0) return 256;
+    return knn_uniform_workspace(nullptr, knn_grid(n), n).total;
 }
 
 int cgnn_knn_periodic(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids, int64_t nq,
                       int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
-    return knn_periodic_run("cgnn_knn_periodic", CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k, query_ids, nq,
+    return knn_periodic_run("cgnn_knn_periodic", false, CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k, query_ids, nq,
                             senders, edge_attr, workspace, workspace_bytes, stream);
 }
 
 int cgnn_knn_periodic_mode(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
                            int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
                            void* stream, int32_t edge_attr_mode) {
-    return knn_periodic_run("cgnn_knn_periodic_mode", edge_attr_mode, pos, n, box_size, k, query_ids, nq, senders,
+    return knn_periodic_run("cgnn_knn_periodic_mode", false, edge_attr_mode, pos, n, box_size, k, query_ids, nq, senders,
                             edge_attr, workspace, workspace_bytes, stream);
 }
 
 int cgnn_knn_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {
-    if (!workspace || !perm || n <= 0) {
-        set_error("cgnn_knn_sorted_order: invalid argument");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const KnnLayout L = knn_layout(n);
-    const float4* sorted = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(workspace) + L.off_sorted);
-    knn_perm_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, n,
-                                                                                                        perm);
-    return check_hip(hipGetLastError(), "cgnn_knn_sorted_order launch");
+    return knn_sorted_order_run("cgnn_knn_sorted_order", false, workspace, n, perm, stream);
+}
+
+size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k) {
+    (void)k;
+    if (n <= 0) return 256;
+    return knn_adaptive_workspace(nullptr, n).total;
+}
+
+int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                               int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return knn_periodic_run("cgnn_knn_periodic_adaptive", true, CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k,
+                            query_ids, nq, senders, edge_attr, workspace, workspace_bytes, stream);
+}
+
+int cgnn_knn_periodic_adaptive_mode(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
+                                    int64_t nq, int32_t* senders, float* edge_attr, void* workspace,
+                                    size_t workspace_bytes, void* stream, int32_t edge_attr_mode) {
+    return knn_periodic_run("cgnn_knn_periodic_adaptive_mode", true, edge_attr_mode, pos, n, box_size, k, query_ids, nq,
+                            senders, edge_attr, workspace, workspace_bytes, stream);
+}
+
+int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {
+    return knn_sorted_order_run("cgnn_knn_adaptive_sorted_order", true, workspace, n, perm, stream);
 }
 
 size_t cgnn_knn_batched_workspace_bytes(const int64_t* offsets, int32_t num_graphs, int32_t k) {
     (void)k;
-    KnnBatchedLayout L;
-    if (knn_batched_layout("cgnn_knn_batched_workspace_bytes", offsets, num_graphs, L) != CGNN_OK) return 256;
-    return L.total;
+    KnnWorkspace W;
+    if (knn_batched_workspace("cgnn_knn_batched_workspace_bytes", offsets, num_graphs, 1, nullptr, W) != CGNN_OK) return 256;
+    return W.total;
 }
 
 int cgnn_knn_periodic_batched(const float* pos, const int64_t* offsets, int32_t num_graphs, float box_size, int32_t k,
                               int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
                               void* stream, int32_t edge_attr_mode) {
     const char* who = "cgnn_knn_periodic_batched";
-    if (!pos || !offsets || !senders || !workspace || k <= 0 || !(box_size > 0.f)) {
-        set_error("%s: invalid argument", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (edge_attr_mode != CGNN_KNN_EDGE_ATTR_REFERENCE && edge_attr_mode != CGNN_KNN_EDGE_ATTR_IMAGE) {
-        set_error("%s: unknown edge-feature mode %d", who, (int)edge_attr_mode);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    if (k > 64) {
-        set_error("%s: k=%d > 64 is not compiled", who, k);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    KnnBatchedLayout L;
-    int rc = knn_batched_layout(who, offsets, num_graphs, L);
+    int rc = knn_check_common(who, edge_attr_mode, pos, senders, workspace, k, box_size);
     if (rc) return rc;
-    for (int32_t g = 0; g < num_graphs; ++g) {
-        const int64_t n = offsets[g + 1] - offsets[g];
-        if ((int64_t)k > 27 * n) {
-            set_error("%s: k=%d exceeds the 27*n=%lld periodic images of graph %d", who, k, (long long)(27 * n), (int)g);
-            return CGNN_ERR_INVALID_ARG;
-        }
-    }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("%s: workspace must be 16-byte aligned", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (workspace_bytes < L.total) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
+    KnnWorkspace W;
+    rc = knn_batched_workspace(who, offsets, num_graphs, k, workspace, W);
+    if (rc) return rc;
+    rc = knn_check_workspace(who, workspace, workspace_bytes, W.total);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* count = reinterpret_cast<int32_t*>(ws + L.off_count);
-    int32_t* start = reinterpret_cast<int32_t*>(ws + L.off_start);
-    int32_t* cursor = reinterpret_cast<int32_t*>(ws + L.off_cursor);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
-    int32_t* cell_of = reinterpret_cast<int32_t*>(ws + L.off_cellof);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
-    const int64_t m = L.cells + 1;  // count[cells] = 0 so that start[cells] = n_total
-    rc = check_hip(hipMemsetAsync(count, 0, (size_t)m * 4, st), "knn batched memset count");
+    const int64_t m = W.cells + 1;  // count[cells] = 0 so that start[cells] = n_total
+    rc = check_hip(hipMemsetAsync(W.count, 0, (size_t)m * 4, st), "knn batched memset count");
     if (rc) return rc;
-    rc = check_hip(hipMemsetAsync(cursor, 0, (size_t)m * 4, st), "knn batched memset cursor");
+    rc = check_hip(hipMemsetAsync(W.cursor, 0, (size_t)m * 4, st), "knn batched memset cursor");
     if (rc) return rc;
     // Each stage takes every graph: one launch per group of CGNN_KNN_BATCH_GROUP graphs, one scan over all cell tables.
-    const int32_t groups = (num_graphs + CGNN_KNN_BATCH_GROUP - 1) / CGNN_KNN_BATCH_GROUP;
-    auto group_table = [&](int32_t gi, int64_t& cell_base) {
-        const int32_t g0 = gi * CGNN_KNN_BATCH_GROUP;
-        const int32_t cnt = num_graphs - g0 < CGNN_KNN_BATCH_GROUP ? num_graphs - g0 : CGNN_KNN_BATCH_GROUP;
-        return knn_batch_table(offsets, g0, cnt, box_size, cell_base);
+    auto for_each_group = [&](auto&& launch) {
+        int64_t cell_base = 0;
+        for (int32_t g0 = 0; g0 < num_graphs; g0 += CGNN_KNN_BATCH_GROUP) {
+            const int32_t cnt = num_graphs - g0 < CGNN_KNN_BATCH_GROUP ? num_graphs - g0 : CGNN_KNN_BATCH_GROUP;
+            const KnnBatchTable T = knn_batch_table(offsets, g0, cnt, box_size, cell_base);
+            launch(T, knn_blocks((int64_t)T.row_base[cnt] - T.row_base[0]));
+        }
     };
-    auto blocks_of = [](const KnnBatchTable& T) {
-        return (unsigned)(((int64_t)T.row_base[T.count] - T.row_base[0] + CGNN_BLOCK - 1) / CGNN_BLOCK);
-    };
-    int64_t cell_base = 0;
-    for (int32_t gi = 0; gi < groups; ++gi) {
-        const KnnBatchTable T = group_table(gi, cell_base);
-        knn_batched_count_kernel<<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, cell_of, count);
-    }
-    exclusive_scan_i32(count, m, bsum, start, st);
-    cell_base = 0;
-    for (int32_t gi = 0; gi < groups; ++gi) {
-        const KnnBatchTable T = group_table(gi, cell_base);
-        knn_batched_fill_kernel<<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, cell_of, start, cursor, sorted);
-    }
+    for_each_group([&](const KnnBatchTable& T, unsigned nb) {
+        knn_batched_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, T, W.item_of, W.count);
+    });
+    exclusive_scan_i32(W.count, m, W.bsum, W.start, st);
+    for_each_group([&](const KnnBatchTable& T, unsigned nb) {
+        knn_batched_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, T, W.item_of, W.start, W.cursor, W.sorted);
+    });
     rc = check_hip(hipGetLastError(), who);
     if (rc) return rc;
-#define CGNN_KNNB_LAUNCH_MODE(KK, MM)                                                                          \
-    knn_batched_search_kernel<KK, MM><<<blocks_of(T), CGNN_BLOCK, 0, st>>>(pos, T, box_size, start, sorted, k, \
-                                                                           senders, edge_attr)
-#define CGNN_KNNB_LAUNCH(KK)                                                     \
-    do {                                                                         \
-        if (edge_attr_mode == CGNN_KNN_EDGE_ATTR_IMAGE)                          \
-            CGNN_KNNB_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                 \
-        else                                                                     \
-            CGNN_KNNB_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);             \
-    } while (0)
-    cell_base = 0;
-    for (int32_t gi = 0; gi < groups; ++gi) {
-        const KnnBatchTable T = group_table(gi, cell_base);
-        if (k <= 8)
-            CGNN_KNNB_LAUNCH(8);
-        else if (k <= 16)
-            CGNN_KNNB_LAUNCH(16);
-        else if (k <= 32)
-            CGNN_KNNB_LAUNCH(32);
-        else
-            CGNN_KNNB_LAUNCH(64);
-    }
-#undef CGNN_KNNB_LAUNCH
-#undef CGNN_KNNB_LAUNCH_MODE
+    for_each_group([&](const KnnBatchTable& T, unsigned nb) {
+        knn_dispatch(k, edge_attr_mode, [&](auto K, auto M) {
+            knn_batched_search_kernel<decltype(K)::value, decltype(M)::value><<<nb, CGNN_BLOCK, 0, st>>>(
+                pos, T, box_size, W.start, W.sorted, k, senders, edge_attr);
+        });
+    });
     return check_hip(hipGetLastError(), who);
 }
 
@@ -915,140 +923,17 @@ int cgnn_knn_batched_sorted_order(const void* workspace, const int64_t* offsets,
         set_error("%s: invalid argument", who);
         return CGNN_ERR_INVALID_ARG;
     }
-    KnnBatchedLayout L;
-    const int rc = knn_batched_layout(who, offsets, num_graphs, L);
+    KnnWorkspace W;
+    const int rc = knn_batched_workspace(who, offsets, num_graphs, 1, const_cast<void*>(workspace), W);
     if (rc) return rc;
-    const float4* sorted = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(workspace) + L.off_sorted);
     int64_t cell_base = 0;
     for (int32_t g0 = 0; g0 < num_graphs; g0 += CGNN_KNN_BATCH_GROUP) {
         const int32_t cnt = num_graphs - g0 < CGNN_KNN_BATCH_GROUP ? num_graphs - g0 : CGNN_KNN_BATCH_GROUP;
         const KnnBatchTable T = knn_batch_table(offsets, g0, cnt, 1.0f, cell_base);
-        const unsigned nb = (unsigned)(((int64_t)T.row_base[cnt] - T.row_base[0] + CGNN_BLOCK - 1) / CGNN_BLOCK);
-        knn_batched_perm_kernel<<<nb, CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, T, perm);
+        knn_batched_perm_kernel<<<knn_blocks((int64_t)T.row_base[cnt] - T.row_base[0]), CGNN_BLOCK, 0,
+                                  (hipStream_t)stream>>>(W.sorted, T, perm);
     }
     return check_hip(hipGetLastError(), who);
-}
-
-size_t cgnn_knn_adaptive_workspace_bytes(int64_t n, int32_t k) {
-    (void)k;
-    if (n <= 0) return 256;
-    return knn_adaptive_layout(n).total;
-}
-
-static int knn_periodic_adaptive_run(const char* who, int32_t mode, const float* pos, int64_t n, float box_size,
-                                     int32_t k, const int32_t* query_ids, int64_t nq, int32_t* senders,
-                                     float* edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!pos || !senders || !workspace || n <= 0 || k <= 0 || !(box_size > 0.f)) {
-        set_error("%s: invalid argument", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (mode != CGNN_KNN_EDGE_ATTR_REFERENCE && mode != CGNN_KNN_EDGE_ATTR_IMAGE) {
-        set_error("%s: unknown edge-feature mode %d", who, (int)mode);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    if (k > 64) {
-        set_error("%s: k=%d > 64 is not compiled", who, k);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    if ((int64_t)k > 27 * n) {
-        set_error("%s: k=%d exceeds the 27*n=%lld periodic images", who, k, (long long)(27 * n));
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (n >= ((int64_t)1 << CGNN_KNN_IDX_BITS)) {
-        set_error("%s: n=%lld >= 2^%d particles per call is not supported", who, (long long)n,
-                  CGNN_KNN_IDX_BITS);
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("%s: workspace must be 16-byte aligned", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const KnnAdaptiveLayout L = knn_adaptive_layout(n);
-    if (workspace_bytes < L.total) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
-    if (query_ids == nullptr) nq = n;
-    if (nq < 0) {
-        set_error("%s: negative query count", who);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* nleaf = reinterpret_cast<int32_t*>(ws + L.off_nleaf);    // coarse counts, then leaves per cell
-    int32_t* lbase = reinterpret_cast<int32_t*>(ws + L.off_lbase);
-    int32_t* lcount = reinterpret_cast<int32_t*>(ws + L.off_lcount);
-    int32_t* lstart = reinterpret_cast<int32_t*>(ws + L.off_lstart);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
-    int32_t* leaf_of = reinterpret_cast<int32_t*>(ws + L.off_leafof);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
-    const int G = L.G;
-    const float h = box_size / (float)G;
-    const float inv_h = (float)G / box_size;
-    const int64_t mc = L.cells + 1;       // nleaf[cells] = 0 so that lbase[cells] = number of leaves
-    const int64_t ml = L.max_leaves + 1;  // lcount is 0 from the last leaf on so that lstart = n there
-    int rc = check_hip(hipMemsetAsync(nleaf, 0, (size_t)mc * 4, st), "knn adaptive memset cell counts");
-    if (rc) return rc;
-    rc = check_hip(hipMemsetAsync(lcount, 0, (size_t)ml * 4, st), "knn adaptive memset leaf counts");
-    if (rc) return rc;
-    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
-    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, leaf_of, nleaf);   // leaf_of: overwritten below
-    knna_depth_kernel<<<(unsigned)((L.cells + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(nleaf, L.cells);
-    exclusive_scan_i32(nleaf, mc, bsum, lbase, st);
-    knna_leaf_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, lbase, leaf_of, lcount);
-    exclusive_scan_i32(lcount, ml, bsum, lstart, st);
-    knna_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, leaf_of, lstart, lcount, sorted);
-    rc = check_hip(hipGetLastError(), who);
-    if (rc) return rc;
-    if (nq == 0) return CGNN_OK;
-    const unsigned qb = (unsigned)((nq + CGNN_BLOCK - 1) / CGNN_BLOCK);
-#define CGNN_KNNA_LAUNCH_MODE(KK, MM)                                                                           \
-    knn_adaptive_search_kernel<KK, MM><<<qb, CGNN_BLOCK, 0, st>>>(pos, n, box_size, h, inv_h, G, lbase, lstart,      \
-                                                                  sorted, query_ids, nq, k, senders, edge_attr)
-#define CGNN_KNNA_LAUNCH(KK)                                                     \
-    do {                                                                         \
-        if (mode == CGNN_KNN_EDGE_ATTR_IMAGE)                                    \
-            CGNN_KNNA_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_IMAGE);                 \
-        else                                                                     \
-            CGNN_KNNA_LAUNCH_MODE(KK, CGNN_KNN_EDGE_ATTR_REFERENCE);             \
-    } while (0)
-    if (k <= 8)
-        CGNN_KNNA_LAUNCH(8);
-    else if (k <= 16)
-        CGNN_KNNA_LAUNCH(16);
-    else if (k <= 32)
-        CGNN_KNNA_LAUNCH(32);
-    else
-        CGNN_KNNA_LAUNCH(64);
-#undef CGNN_KNNA_LAUNCH
-#undef CGNN_KNNA_LAUNCH_MODE
-    return check_hip(hipGetLastError(), who);
-}
-
-int cgnn_knn_periodic_adaptive(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
-                               int64_t nq, int32_t* senders, float* edge_attr, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-    return knn_periodic_adaptive_run("cgnn_knn_periodic_adaptive", CGNN_KNN_EDGE_ATTR_REFERENCE, pos, n, box_size, k,
-                                     query_ids, nq, senders, edge_attr, workspace, workspace_bytes, stream);
-}
-
-int cgnn_knn_periodic_adaptive_mode(const float* pos, int64_t n, float box_size, int32_t k, const int32_t* query_ids,
-                                    int64_t nq, int32_t* senders, float* edge_attr, void* workspace,
-                                    size_t workspace_bytes, void* stream, int32_t edge_attr_mode) {
-    return knn_periodic_adaptive_run("cgnn_knn_periodic_adaptive_mode", edge_attr_mode, pos, n, box_size, k,
-                                     query_ids, nq, senders, edge_attr, workspace, workspace_bytes, stream);
-}
-
-int cgnn_knn_adaptive_sorted_order(const void* workspace, int64_t n, int32_t* perm, void* stream) {
-    if (!workspace || !perm || n <= 0) {
-        set_error("cgnn_knn_adaptive_sorted_order: invalid argument");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const KnnAdaptiveLayout L = knn_adaptive_layout(n);
-    const float4* sorted = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(workspace) + L.off_sorted);
-    knn_perm_kernel<<<(unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, (hipStream_t)stream>>>(sorted, n,
-                                                                                                        perm);
-    return check_hip(hipGetLastError(), "cgnn_knn_adaptive_sorted_order launch");
 }
 
 }  // extern "C"

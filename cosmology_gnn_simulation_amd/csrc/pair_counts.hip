@@ -107,12 +107,6 @@ __global__ void pc_chunks_kernel(const int32_t* __restrict__ start_a, int64_t ce
     nchunk[c] = c < cells ? (start_a[c + 1] - start_a[c] + CGNN_PC_QCHUNK - 1) / CGNN_PC_QCHUNK : 0;
 }
 
-__device__ __forceinline__ float pc_fold(float d, float box, float half) {
-    if (d > half) d = __fsub_rn(d, box);
-    else if (d < -half) d = __fadd_rn(d, box);
-    return d;
-}
-
 // the waves' histograms -> global counts, and back to zero; every thread of the workgroup calls it
 __device__ __forceinline__ void pc_flush(unsigned (*hist)[CGNN_PC_MAX_BINS], int num_bins,
                                          unsigned long long* __restrict__ counts) {
@@ -143,7 +137,6 @@ __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
     __syncthreads();
     const float e2_lo = e2_s[0], e2_hi = e2_s[num_bins];
     const int items = chunk_start[cells];
-    const int na = G < 3 ? G : 3;      // cells walked per axis
     unsigned pending = 0;              // bound on what any one LDS counter holds since the last flush
     for (int item = blockIdx.x; item < items; item += gridDim.x) {
         // the item's cell: chunk_start[c] <= item < chunk_start[c + 1] (cells without queries have no items)
@@ -157,31 +150,7 @@ __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
         const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
         __syncthreads();               // the previous item's readers of q_s and rng_* are done
         if (tid < nq) q_s[tid] = sorted_a[q0 + tid];
-        if (tid < CGNN_PC_RANGES) {
-            const int ix = tid / 9, iy = (tid / 3) % 3, iz = tid % 3;
-            int p0 = 0, len = 0;
-            if (ix < na && iy < na && iz < na) {
-                // G <= 3: all cells of the axis, each once; otherwise c - 1, c, c + 1 wrapped (three distinct cells)
-                const int wx = G <= 3 ? ix : (cx - 1 + ix + G) % G;
-                const int wy = G <= 3 ? iy : (cy - 1 + iy + G) % G;
-                const int wz = G <= 3 ? iz : (cz - 1 + iz + G) % G;
-                const int cell = morton3(wx, wy, wz);
-                p0 = start_b[cell];
-                len = start_b[cell + 1] - p0;
-            }
-            rng_p0[tid] = p0;
-            rng_len[tid] = len;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int run = 0;
-            for (int j = 0; j < CGNN_PC_RANGES; ++j) {
-                rng_off[j] = run;
-                run += rng_len[j];
-            }
-            rng_off[CGNN_PC_RANGES] = run;
-        }
-        __syncthreads();
+        cell_grid_stage_ranges<CGNN_PC_RANGES>(tid, cx, cy, cz, G, start_b, rng_p0, rng_len, rng_off);
         const int nc = rng_off[CGNN_PC_RANGES];
         for (int t0 = 0; t0 < nc; t0 += CGNN_PC_QCHUNK) {
             if (pending >= 0x7F000000u) {      // uniform over the workgroup
@@ -198,9 +167,9 @@ __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
                 const int self = auto_mode ? p - q0 : -1;   // the query that is this very particle, if any
                 for (int qi = 0; qi < nq; ++qi) {
                     const float4 a = q_s[qi];
-                    const float dx = pc_fold(__fsub_rn(b.x, a.x), box, half);
-                    const float dy = pc_fold(__fsub_rn(b.y, a.y), box, half);
-                    const float dz = pc_fold(__fsub_rn(b.z, a.z), box, half);
+                    const float dx = cell_grid_fold(__fsub_rn(b.x, a.x), box, half);
+                    const float dy = cell_grid_fold(__fsub_rn(b.y, a.y), box, half);
+                    const float dz = cell_grid_fold(__fsub_rn(b.z, a.z), box, half);
                     const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
                     if (d2 >= e2_lo && d2 < e2_hi && qi != self) {
                         int lo = 0, up = num_bins;          // e2[lo] <= d2 < e2[up]
@@ -284,7 +253,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fe_partial_kernel(const float* __r
         const int64_t row = f * n + i;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const double d = (double)pc_fold(__fsub_rn(pred_pos[3 * row + c], true_pos[3 * row + c]), box, half);
+            const double d = (double)cell_grid_fold(__fsub_rn(pred_pos[3 * row + c], true_pos[3 * row + c]), box, half);
             sp = __dadd_rn(sp, __dmul_rn(d, d));
         }
         if (pred_tmp != nullptr) {

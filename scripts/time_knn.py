@@ -3,6 +3,7 @@ queries, in ONE process: every shape is warmed in both modes, then the modes alt
 device events.  Prints median, min and max per mode and input.  Not part of the product or tests.
     python scripts/time_knn.py [--iters 12] [--neighbors 16] [--inputs uniform:1000000 clustered:1000000 clustered:4000000]
     python scripts/time_knn.py --edge-attr reference image      (both edge-feature modes on both grids, all alternating)
+    python scripts/time_knn.py --batch 4      (ops.knn_periodic_batched on 4 copies of the first input, nothing else)
     rocprofv3 --kernel-trace --stats -- python scripts/time_knn.py --iters 10       (build kernels against the search)
 clustered:N is synthetic.make_clustered_positions(N) (half of the particles in one Gaussian halo of 0.05 box)."""
 import argparse
@@ -22,6 +23,8 @@ ap.add_argument("--inputs", nargs="+", default=["uniform:1000000", "clustered:10
 ap.add_argument("--edge-attr", nargs="+", choices=["reference", "image"], default=["reference"],
                 help="edge-feature modes to time: reference (the default of ops.knn_periodic) and / or image "
                      "(min_image_edge_attr=True)")
+ap.add_argument("--batch", type=int, default=0, metavar="B",
+                help="time ops.knn_periodic_batched (uniform grid) on B copies of the first input instead")
 ap.add_argument("--no-order", action="store_true", help="leave the sorted-order by-product out of the timed call")
 a = ap.parse_args()
 if a.iters < 10:
@@ -44,13 +47,38 @@ VARIANTS = [(grid, mode) for grid in ops.KNN_GRIDS for mode in dict.fromkeys(a.e
 
 
 def call(pos, grid, mode):
+    return timed(lambda: ops.knn_periodic(pos, box, k, want_order=not a.no_order, grid=grid,
+                                          min_image_edge_attr=mode == "image"))
+
+
+def timed(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = ops.knn_periodic(pos, box, k, want_order=not a.no_order, grid=grid, min_image_edge_attr=mode == "image")
+    out = fn()
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1), out
 
+
+if a.batch:
+    one = frame(a.inputs[0])
+    n, modes = one.shape[0], list(dict.fromkeys(a.edge_attr))
+    pos, offsets = one.repeat(a.batch, 1), [g * one.shape[0] for g in range(a.batch + 1)]
+    calls = {mode: (lambda mode=mode: ops.knn_periodic_batched(pos, offsets, box, k, True, not a.no_order,
+                                                               min_image_edge_attr=mode == "image")) for mode in modes}
+    for fn in calls.values():                        # warm every mode before any timing
+        for _ in range(2):
+            timed(fn)
+    print(f"ops.knn_periodic_batched, {a.batch} x {a.inputs[0]}, k={k}, edge_attr{'' if a.no_order else ' and order'}; "
+          f"device events around the call, modes alternating, {a.iters} timed calls per mode", flush=True)
+    times = {mode: [timed(fn)[0]] for mode, fn in calls.items()}
+    for _ in range(a.iters - 1):
+        for mode, fn in calls.items():
+            times[mode].append(timed(fn)[0])
+    for mode, t in times.items():
+        print(f"  {a.batch} x {a.inputs[0]:>14s}   batched {mode:>9s}: median {statistics.median(t):8.3f} ms   "
+              f"min {min(t):8.3f}   max {max(t):8.3f}", flush=True)
+    raise SystemExit(0)
 
 frames = {spec: frame(spec) for spec in a.inputs}
 for pos in frames.values():                          # warm every shape in every mode before any timing

@@ -63,6 +63,8 @@ def _loop(case, k, min_image):
 
 # graphs of 8-12 particles are compared at k = 5 and 8 (at k = 16 a miss could only show as a time-out)
 PAIRS = [(case, k) for case in CASES for k in (5, 8, 16) if not (case == "many-graphs" and k == 16)]
+# the two longer lists of the search kernel (k <= 32, k <= 64): n = 5 among "ragged" gives one sender as several images
+PAIRS += [("ragged", 32), ("coincident", 32), ("one-cell", 33), ("ragged", 64)]
 
 
 @pytest.mark.parametrize("min_image", [False, True], ids=["reference", "image"])
