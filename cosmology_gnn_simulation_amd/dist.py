@@ -29,7 +29,7 @@ import torch
 from . import _lib, ops, synthetic, training
 from ._lib import CgnnError
 from .graph_network import _next_projection, _node_half, _run_edge_stream, _run_round
-from .training import NodeStreamSteps
+from .training import NodeStreamSteps, _edge_rows  # noqa: F401  (_edge_rows: its tests reach it here)
 
 
 # ----------------------------------------------------------------------------
@@ -866,11 +866,11 @@ class ShardedTraining(NodeStreamSteps):
             return
         super().decode_backward(d_acc, d_tr)
 
-    def encode_backward(self, need_dx0: bool = True) -> Optional[torch.Tensor]:
+    def encode_backward(self, need_dx0: bool = True, **more) -> Optional[torch.Tensor]:
         if self.sh.n_owned == 0:
             self.dx = None
             return torch.zeros_like(self.x0) if need_dx0 else None
-        return super().encode_backward(need_dx0)
+        return super().encode_backward(need_dx0, **more)
 
     def round_backward_local(self, i: int) -> torch.Tensor:
         """Steps 1-2 of round ``i``: the node MLP's backward on the owned rows, then ``A^T du2`` for the ghost rows,
@@ -968,33 +968,24 @@ def shard_edge_training_bytes(n_owned: int, n_ghost: int, k: int, latent: int, h
         4 * rounds * (n_owned + n_ghost) * latent
 
 
-def _edge_rows(t: "ops.TiledRows", lo: int, hi: int) -> "ops.TiledRows":
-    """Edges [lo, hi) of TILED32 edge rows as a view of ``t.buf`` (``lo`` on a tile boundary)."""
-    if lo % 32 or not 0 <= lo <= hi <= t.n:
-        raise CgnnError(f"edge rows [{lo}, {hi}) of {t.n} do not start on a 32-edge tile")
-    rows = (hi - lo + 31) // 32 * 32
-    return ops.TiledRows(hi - lo, t.width, t.device, buf=t.buf[lo:lo + rows])
-
-
-class ShardedEdgeTraining(ShardedTraining):
+class ShardedEdgeTraining(ShardedTraining, training.EdgeStreamSteps):
     """A training step of an ``EncodeProcessDecode`` with ``message_source="edge"`` and ``model.train_edge_messages`` over
-    one spatial tile: :class:`training._EdgeStreams` on the shard's local rows, both streams differentiated.
-    ``ShardedTraining(model, shard)`` returns one for such a model.
+    one spatial tile: the pieces of :class:`training.EdgeStreamSteps`, which :class:`training._EdgeStreams` runs over a
+    whole graph, on the shard's local rows (``ShardedTraining(model, shard)`` returns one for such a model).  Here is
+    only what a tile adds: ghost rows behind the owned ones in every table, two receiver ranges around the forward
+    exchange, the ``dPs`` rows that cross ranks, and the rank that owns nothing (guarded here and in
+    :class:`ShardedTraining`, never inside the pieces).
 
     Forward of round i: ``x_i`` sits in the owned rows of the kept local table ``[owned | ghosts]`` (:meth:`stage`), the
-    exchange fills the ghosts.  Under it the interior part projects ``Ps`` / ``Pd`` of the owned rows, runs the edge
-    block over the edges of receivers ``[0, n_split)``, their fixed-k aggregate of ``e_upd`` and the node block; after
-    it the boundary part projects ``Ps`` of the ghosts and does the same for ``[n_split, n_owned)``.  ``n_split``
-    (:func:`edge_split_rows`) puts the split on a 32-edge tile.  Kept: every round's local table (ghost rows included),
-    ``agg_i`` of the owned rows and the input edge latents ``e_i`` of every round but the last's output.
+    exchange fills the ghosts.  Under it the interior part projects the owned rows and runs receivers ``[0, n_split)``;
+    after it the boundary part projects the ghosts and runs ``[n_split, n_owned)``.  ``n_split``
+    (:func:`edge_split_rows`) puts the split on a 32-edge tile.
 
-    Backward of round i (``dx`` = dL/dx_{i+1} on the owned rows): node MLP backward; ``Ps`` / ``Pd`` recomputed from the
-    kept table; ``edge_mlp_backward`` over the local edges; ``dPs`` of the ghost senders into the send buffer (a ghost row
-    reaches the loss only through its ``Ps`` row, so ``dPs``, H wide, is what crosses ranks); under the reverse exchange
-    the edge-row reductions, ``dPs`` of the owned rows and ``dPd``; then the returned rows are added into ``dPs``
-    (``ops.halo_return_add``), ``dWs`` / ``dWd`` / ``db1`` are reduced over the owned rows and
-    ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``.  The encoders' backwards give ``dx0`` of the owned rows and
-    ``d edge_attr`` of the local edges; one all-reduce sums the parameter gradients in ``EdgeTrainPacks.params()`` order."""
+    Backward of round i: the step up to dh1 of every local edge; ``dPs`` of the ghost senders into the send buffer (a
+    ghost row reaches the loss only through its ``Ps`` row, so ``dPs``, H wide, is what crosses ranks); under the
+    reverse exchange the edge-row reductions, ``dPs`` of the owned rows and ``dPd``; then the returned rows are added
+    into ``dPs`` (``ops.halo_return_add``) and the step finishes the round.  One all-reduce sums the parameter
+    gradients in ``EdgeTrainPacks.params()`` order."""
 
     def __init__(self, model, shard: Shard, halo=None, group=None):
         super().__init__(model, shard, halo, group)
@@ -1031,157 +1022,69 @@ class ShardedEdgeTraining(ShardedTraining):
             raise CgnnError(f"ShardedTraining: {x0.shape[0]} input rows and {ea.shape[0]} edges for {sh.n_owned} owned "
                             f"particles with k = {sh.k}")
         self._prepare(x0, ea)
-        p = self.packs
-        self.x0, self.edge_attr = x0, ea
-        D, H, dev = p.latent, p.hidden, x0.device
         if sh.n_owned == 0:         # no rows, no edges, no ghosts: nothing to encode
-            self.xs, self.es, self.aggs = [x0.new_empty((0, D))], [], []
+            self.x0, self.edge_attr = x0, ea
+            self.xs, self.es, self.aggs = [x0.new_empty((0, self.packs.latent))], [], []
             return
-        self.xs = [torch.empty((sh.n_local if p.rounds else sh.n_owned, D), dtype=torch.float32, device=dev)]
-        ops.mlp_rows(p.enc.fwd, x0, out=self.xs[0][:sh.n_owned])
-        self.es = [ops.mlp_rows(p.enc_edge.fwd, ea, tiled=True)]       # raw features: three bf16 terms or exact
-        self.aggs = []
-        self._e_upd = self.es[0].empty_like()
-        self._ps = torch.empty((sh.n_local, H), dtype=torch.float32, device=dev)
-        self._pd = torch.empty((sh.n_owned, H), dtype=torch.float32, device=dev)
+        self._encode(self.packs, x0, ea, sh.src_local, sh.dst_local, sh.k, sh.n_local)
 
     def stage(self, i: int) -> torch.Tensor:
         """Round ``i``'s local table, kept for the backward: ``x_i`` is in its owned rows, the exchange is to fill the
-        ghost rows.  Makes room for ``agg_i``, ``x_{i+1}`` and ``e_{i+1}``."""
-        sh, p = self.sh, self.packs
-        last = i + 1 == len(p.rounds)
-        dev = self.x0.device
-        if sh.n_owned == 0:
-            self.xs.append(self.x0.new_empty((0, p.latent)))
-            return self.xs[i]
-        self.aggs.append(torch.empty((sh.n_owned, p.latent), dtype=torch.float32, device=dev))
-        self.xs.append(torch.empty((sh.n_owned if last else sh.n_local, p.latent), dtype=torch.float32, device=dev))
-        if not last:
-            self.es.append(self.es[i].empty_like())
+        ghost rows.  Makes room for the round's results."""
+        if self.sh.n_owned == 0:
+            self.xs.append(self.x0.new_empty((0, self.packs.latent)))
+        else:
+            self._new_round()
         return self.xs[i]
-
-    def _project(self, i: int, part: str) -> None:
-        """Round ``i``'s P_F32 tables: ``Ps`` / ``Pd`` of the owned rows (``"owned"``) or ``Ps`` of the ghost rows."""
-        sh, ep, x = self.sh, self.packs.edges[i], self.xs[i]
-        no = sh.n_owned
-        if part == "owned":
-            ops.project_nodes(ep.ws, ep.wd, x[:no], self._ps[:no], self._pd, p_format=_lib.P_F32)
-        elif sh.n_ghost:
-            ops.project_nodes(ep.ws, None, x[no:], self._ps[no:], None, p_format=_lib.P_F32)
 
     def round_nodes(self, i: int, part: str = "all") -> None:
         """Round ``i`` for the owned receivers of ``part``: ``"interior"`` ([0, n_split): no ghost sender, may run under
         the exchange; projects the owned rows), ``"boundary"`` (after it; projects the ghost rows) or ``"all"``."""
-        sh, p = self.sh, self.packs
-        no, k = sh.n_owned, sh.k
+        sh = self.sh
+        no = sh.n_owned
         if no == 0:
             return
         a, b = {"all": (0, no), "interior": (0, self.n_split), "boundary": (self.n_split, no)}[part]
         if part != "boundary":
-            self._project(i, "owned")
-        if part != "interior":
-            self._project(i, "ghosts")
-        if b <= a:
-            return
-        ep, r, x = p.edges[i], p.rounds[i], self.xs[i]
-        src, dst = sh.src_local[a * k:b * k], sh.dst_local[a * k:b * k]
-        e, e_upd = _edge_rows(self.es[i], a * k, b * k), _edge_rows(self._e_upd, a * k, b * k)
-        if i + 1 == len(p.rounds):          # e_L is not kept: the update alone, as on one GPU
-            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, e_upd, None, residual=False)
-        else:
-            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, _edge_rows(self.es[i + 1], a * k, b * k), e_upd,
-                           residual=True)
-        agg = self.aggs[i][a:b]
-        ops.aggregate(e_upd, None, dst, b - a, k, (b - a) * k, agg)
-        ops.node_block(r.run, r.run.layers[0], r.run2, x[a:b], agg, self.xs[i + 1][a:b], True)
+            self._project(i, 0, no)
+        if part != "interior" and sh.n_ghost:
+            self._project(i, no, sh.n_local)
+        if b > a:
+            self._round_forward(i, a, b)
 
     # -- backward pieces ---------------------------------------------------------------------------------------------
-    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
-        super().decode_backward(d_acc, d_tr)
-        if self.sh.n_owned == 0:
-            self._zero_grads([self.packs.enc_edge] + self.packs.edges)
-            return
-        p, ne, dev = self.packs, self.es[0].n, self.x0.device
-        self._escratch = ops.BackwardScratch(ne, p.hidden, max(p.latent, 32), p.nh, dev)
-        self._dy = torch.empty((max(ne, 1), p.latent), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i
-        self._de = self.es[0].empty_like()      # d e_i, in place: TILED32 between rounds, rows after round 0
-
     def round_backward_local(self, i: int) -> torch.Tensor:
-        """Steps 1-4 of round ``i``: node MLP backward on the owned rows, the forward's ``Ps`` / ``Pd`` recomputed, the edge
-        model's backward over the local edges, then ``dPs`` of the ghost senders, written into (and returned as) the send
-        buffer of the reverse exchange, [n_ghost, H]."""
-        sh, p = self.sh, self.packs
-        no = sh.n_owned
-        if no == 0:
-            self._round = i
-            return self.x0.new_empty((0, p.hidden))
-        r, ep = p.rounds[i], p.edges[i]
-        agg = self.aggs[i]
-        self.aggs[i] = None
+        """Round ``i`` up to dh1 of every local edge, then ``dPs`` of the ghost senders, written into (and returned as) the
+        send buffer of the reverse exchange, [n_ghost, H]."""
+        sh, H = self.sh, self.packs.hidden
         self._round = i
-        self._du1, d_agg, self.grads_of[id(r)] = r.backward(self.xs[i][:no], agg, self.dx, self.scratch, True, True)
-        self._project(i, "owned")           # the forward's tables, bit for bit (the same calls on the same rows)
-        self._project(i, "ghosts")
-        de, first = self._de, i == 0
-        ops.edge_mlp_backward(ep.rec, ep.bwd, self._ps, self._pd, sh.src_local, sh.dst_local, self.es[i], d_agg,
-                              None if i + 1 == len(p.rounds) else de, self._escratch, self._dy, de.buf if first else de,
-                              de_out_rows=first, n_recv=no)
-        shape = (sh.n_ghost, p.hidden)
-        if self._ghost is None or tuple(self._ghost.shape) != shape or self._ghost.device != d_agg.device:
-            self._ghost = torch.empty(shape, dtype=torch.float32, device=d_agg.device)
+        if sh.n_owned == 0:
+            return self.x0.new_empty((0, H))
+        g_a0 = self._round_backward_edges(i)
+        if self._ghost is None or tuple(self._ghost.shape) != (sh.n_ghost, H) or self._ghost.device != g_a0.device:
+            self._ghost = torch.empty((sh.n_ghost, H), dtype=torch.float32, device=g_a0.device)
         if sh.n_ghost:
-            ops.aggregate_csr(self._escratch.g_a[0], self._csr, out=self._ghost, row_range=(no, sh.n_local))
+            ops.aggregate_csr(g_a0, self._csr, out=self._ghost, row_range=(sh.n_owned, sh.n_local))
         return self._ghost
 
     def round_backward_owned(self, i: int) -> None:
-        """Step 6 (runs under the reverse exchange): the edge-row reductions, ``dPs`` of the owned rows and ``dPd``."""
-        sh, ep = self.sh, self.packs.edges[i]
-        if sh.n_owned == 0:
-            return
-        no, g_a0 = sh.n_owned, self._escratch.g_a[0]
-        self._row_grads = training.edge_row_grads(ep, self._escratch, self._dy, self.es[i])
-        self._dps = ops.aggregate_csr(g_a0, self._csr, row_range=(0, no))
-        self._dpd = ops.aggregate(g_a0, None, sh.dst_local, no, sh.k, no * sh.k)
-        self.es[i] = None
+        """Runs under the reverse exchange: the edge-row reductions, ``dPs`` of the owned rows and ``dPd``."""
+        if self.sh.n_owned:
+            self._round_backward_sums(i, self._csr)
 
     def round_backward_return(self, ret: torch.Tensor) -> None:
-        """Steps 7-8: the ``dPs`` rows the peers returned, added at the rows they had requested; ``dWs`` / ``dWd`` / ``db1``
-        over the owned rows; ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``."""
-        i, no = self._round, self.sh.n_owned
-        if no == 0:
+        """The ``dPs`` rows the peers returned, added at the rows they had requested; then the round's finish."""
+        if self.sh.n_owned == 0:
             return
-        ep = self.packs.edges[i]
         if ret.shape[0]:
             ops.halo_return_add(self._dps, ret, *self._plan)
-        dw0, layer_grads, dgamma, dbeta = self._row_grads
-        db0 = training.edge_node_grads(ep, dw0, self._dps, self._dpd, self.xs[i][:no])
-        self.grads_of[id(ep)] = [dw0, db0] + layer_grads + [dgamma, dbeta]
-        self.dx = ops.linear2_rows(ep.wst, ep.wdt, self._dps, self._dpd, add1=self.dx, add2=self._du1, out=self.dx)
-        self._du1 = self._dps = self._dpd = self._row_grads = None
-        self.xs[i + 1] = None
+        self._round_backward_finish(self._round)
 
     def encode_backward(self, need_dx0: bool = True, need_dea: bool = False) -> Optional[torch.Tensor]:
-        """The node encoder's backward (-> ``dx0`` of the owned rows) and the edge encoder's: ``d_edge_attr`` of the local
-        edges when ``need_dea``, else None."""
-        p = self.packs
-        dx0 = super().encode_backward(need_dx0)
+        dx0 = super().encode_backward(need_dx0, need_dea=need_dea)
         if self.sh.n_owned == 0:
             self.d_edge_attr = torch.zeros_like(self.edge_attr) if need_dea else None
-            return dx0
-        de = self._de
-        if not p.rounds:
-            de.buf.zero_()                  # no round reads the edge encoder's output
-        dea, _, self.grads_of[id(p.enc_edge)] = p.enc_edge.backward(self.edge_attr, None, de.buf[:de.n], self._escratch,
-                                                                    need_dea)
-        self.d_edge_attr = dea if need_dea else None
-        self._de = self._dy = self._escratch = None
         return dx0
-
-    def local_grads(self) -> List[torch.Tensor]:
-        """The parameter gradients of the rows held here, in ``EdgeTrainPacks.params()`` order."""
-        p = self.packs
-        order = [p.enc, p.enc_edge] + [m for pair in zip(p.edges, p.rounds) for m in pair] + [p.dec_acc, p.dec_tr]
-        return [g for m in order for g in self.grads_of[id(m)]]
 
     # -- one step through a process group ----------------------------------------------------------------------------
     def run_forward(self, x0: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None):
@@ -1201,7 +1104,6 @@ class ShardedEdgeTraining(ShardedTraining):
         dx0 = self.encode_backward(need_dx0, need_dea)
         grads = self.local_grads()
         self.xs = self.aggs = self.es = None
-        self._e_upd = self._ps = self._pd = None
         return dx0, self.d_edge_attr, _all_reduce_grads(grads, self.group)
 
     def __call__(self, x0: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None) -> dict:

@@ -199,6 +199,18 @@ def _graph_arrays(data, num_nodes: int):
     return src, dst, fixed_k
 
 
+def _cached_on(data, name: str, src: torch.Tensor, make):
+    """``make()`` (a tuple) once per graph and sender list ``src``, kept on the graph as ``(src, *made)`` under ``name``."""
+    cached = getattr(data, name, None)
+    if cached is None or cached[0] is not src:
+        cached = (src,) + make()
+        try:
+            setattr(data, name, cached)
+        except Exception:  # foreign Data types may refuse private attributes
+            pass
+    return cached[1:]
+
+
 def _locality_plan(data, n: int, k: int, src: torch.Tensor):
     """Renumber the particles in the spatial (cell-sorted) order the k-NN build produced, so that a receiver's
     senders sit in nearby rows and the per-edge gathers hit L2 instead of HBM.  Returns ``(order, inverse,
@@ -722,6 +734,29 @@ class EncodeProcessDecode(nn.Module):
                                           "'edge' extension trains with model.train_edge_messages = True (it keeps "
                                           "every round's edge latents: see training.edge_training_bytes)")
             return self._forward_train_edge(g)
+
+        def step(x, edge_attr, n, src, dst, fixed_k, plan):
+            with torch.no_grad():
+                packs = self._train_packs()
+            by_sender, = _cached_on(g, "_cgnn_by_sender", src, lambda: (ops.SenderCsr(src, dst, n),))   # transposed adjacency
+            packs.edge_stream_fn = None
+            if getattr(self, "train_edge_stream", False):
+                # like-for-like with the reference's step, which computes the edge stream although nothing reads it
+                ea = edge_attr.detach().float().contiguous()
+                if plan is not None:
+                    ea = ops.gather_rows(ea.view(n, -1), plan[0]).view(n * fixed_k, -1)
+                node_in = x.shape[1]
+                packs.edge_stream_fn = lambda xs: training.edge_stream_of(self, xs, src, dst, fixed_k, ea, node_in)
+            out = training.forward_train(self, x, src, dst, fixed_k, packs, by_sender)
+            packs.edge_stream_fn = None
+            return out
+        return self._train_through(g, step)
+
+    def _train_through(self, g, step) -> dict:
+        """What the two training forwards share: the checks, ``globals``, the graph arrays, the locality plan and the
+        materialised modules; the rows of ``x`` permuted into the plan's order, ``step(x, edge_attr, n, src, dst, fixed_k,
+        plan) -> (acceleration, temp_rate)`` in that order, and the predictions permuted back."""
+        from . import training
         x = g.x
         require_device(x, "input_graph.x")
         edge_attr = getattr(g, "edge_attr", None)
@@ -736,27 +771,10 @@ class EncodeProcessDecode(nn.Module):
             src, dst, fixed_k = _graph_arrays(g, n)
             plan = _locality_plan(g, n, fixed_k, src) if (self.locality_sort and fixed_k > 0) else None
             self._materialize_all(x.shape[1], edge_attr.shape[1])
-            packs = self._train_packs()
         if plan is not None:
             order, inv, src, dst = plan
             x = training.permute_rows(x, order, inv)
-        cached = getattr(g, "_cgnn_by_sender", None)      # transposed adjacency, once per graph
-        if cached is None or cached[0] is not src:
-            cached = (src, ops.SenderCsr(src, dst, n))
-            try:
-                g._cgnn_by_sender = cached
-            except Exception:
-                pass
-        packs.edge_stream_fn = None
-        if getattr(self, "train_edge_stream", False):
-            # like-for-like with the reference's step, which computes the edge stream although nothing reads it
-            ea = edge_attr.detach().float().contiguous()
-            if plan is not None:
-                ea = ops.gather_rows(ea.view(n, -1), order).view(n * fixed_k, -1)
-            node_in = x.shape[1]
-            packs.edge_stream_fn = lambda xs: training.edge_stream_of(self, xs, src, dst, fixed_k, ea, node_in)
-        acc, tr = training.forward_train(self, x, src, dst, fixed_k, packs, cached[1])
-        packs.edge_stream_fn = None
+        acc, tr = step(x, edge_attr, n, src, dst, fixed_k, plan)
         if plan is not None:
             acc = training.permute_rows(acc, inv, order)
             tr = training.permute_rows(tr, inv, order)
@@ -767,47 +785,26 @@ class EncodeProcessDecode(nn.Module):
         parameter (edge models included) receives a gradient, and ``edge_attr`` one when it requires it.  See
         :class:`.training._EdgeStreams`."""
         from . import training
-        x = g.x
-        require_device(x, "input_graph.x")
-        edge_attr = getattr(g, "edge_attr", None)
-        if edge_attr is None:
-            raise ValueError("edge_attr must not be None in InteractionNetwork")
-        glob = getattr(g, "globals", None)
-        if glob is not None:
-            x = torch.cat([x, glob.unsqueeze(0).expand(x.shape[0], -1)], dim=-1)
-        x = x.float().contiguous()
-        ea = edge_attr.float().contiguous()
-        n, ne = x.shape[0], ea.shape[0]
-        with torch.no_grad():
-            src, dst, fixed_k = _graph_arrays(g, n)
-            plan = _locality_plan(g, n, fixed_k, src) if (self.locality_sort and fixed_k > 0) else None
-            self._materialize_all(x.shape[1], ea.shape[1])
-            D, H = self._latent_size, self._mlp_hidden_size
-            need = training.edge_training_bytes(ne, D, H, self._mlp_num_hidden_layers, len(self.processor))
-            free = training.free_device_bytes(x.device)
-            if need > free:
-                raise CgnnError(f"edge-mode training needs about {need / 2**30:.1f} GiB of device memory for the edge "
-                                f"latents of every round and the edge-row backward scratch ({ne} edges, latent {D}, hidden "
-                                f"{H}, {len(self.processor)} rounds); {free / 2**30:.1f} GiB are free")
-            packs = self._train_packs(edge=True)
-        if plan is not None:
-            order, inv, src, dst = plan
-            x = training.permute_rows(x, order, inv)
-            # edges are receiver-major, fixed_k per receiver: permute whole receiver blocks (un-permuted in the backward)
-            ea = training.permute_rows(ea.view(n, -1), order, inv).view(ne, -1)
-        cached = getattr(g, "_cgnn_edges_by_node", None)      # edge CSRs (sender-major, receiver-major), once per graph
-        if cached is None or cached[0] is not src:
-            by_receiver = ops.SenderCsr(dst, None, n) if fixed_k == 0 else None
-            cached = (src, ops.SenderCsr(src, None, n), by_receiver)
-            try:
-                g._cgnn_edges_by_node = cached
-            except Exception:
-                pass
-        acc, tr = training.forward_train_edge(self, x, ea, src, dst, fixed_k, packs, cached[1], cached[2])
-        if plan is not None:
-            acc = training.permute_rows(acc, inv, order)
-            tr = training.permute_rows(tr, inv, order)
-        return {"acceleration": acc, "temp_rate": tr}
+
+        def step(x, edge_attr, n, src, dst, fixed_k, plan):
+            ea = edge_attr.float().contiguous()
+            ne = ea.shape[0]
+            with torch.no_grad():
+                D, H = self._latent_size, self._mlp_hidden_size
+                need = training.edge_training_bytes(ne, D, H, self._mlp_num_hidden_layers, len(self.processor))
+                free = training.free_device_bytes(x.device)
+                if need > free:
+                    raise CgnnError(f"edge-mode training needs about {need / 2**30:.1f} GiB of device memory for the edge "
+                                    f"latents of every round and the edge-row backward scratch ({ne} edges, latent {D}, hidden "
+                                    f"{H}, {len(self.processor)} rounds); {free / 2**30:.1f} GiB are free")
+                packs = self._train_packs(edge=True)
+            if plan is not None:
+                # edges are receiver-major, fixed_k per receiver: permute whole receiver blocks (un-permuted in the backward)
+                ea = training.permute_rows(ea.view(n, -1), plan[0], plan[1]).view(ne, -1)
+            csrs = _cached_on(g, "_cgnn_edges_by_node", src, lambda: (      # edge CSRs (sender-major, receiver-major)
+                ops.SenderCsr(src, None, n), ops.SenderCsr(dst, None, n) if fixed_k == 0 else None))
+            return training.forward_train_edge(self, x, ea, src, dst, fixed_k, packs, *csrs)
+        return self._train_through(g, step)
 
     def _forward(self, g, want_latents: bool) -> dict:
         if torch.is_grad_enabled() and (_needs_grad(self) or g.x.requires_grad):

@@ -16,12 +16,16 @@ the sender-major adjacency (``cgnn_csr_build`` once per graph, ``cgnn_aggregate_
 gradients with ``cgnn_weight_grad`` / ``cgnn_col_dot``.
 
 ``message_source="edge"`` (the engine's extension, not the reference's behaviour) trains with
-``model.train_edge_messages = True`` (:class:`_EdgeStreams`): both streams are differentiated, every parameter -- the edge
+``model.train_edge_messages = True``: both streams are differentiated, every parameter -- the edge
 models' included -- receives a gradient, ``edge_attr`` one when it requires it.  Per round the backward recomputes the edge
 model tile by tile (``cgnn_edge_mlp_backward``: dy = d_agg[dst] + de formed in registers, de <- de + We^T dh1), reduces its
 parameter gradients over the edge rows, sums dh1 at the senders (edge CSR) and receivers (fixed-k segments or a CSR) and
 adds Ws^T dPs + Wd^T dPd to dx in one N-row pass (``cgnn_linear2_rows``).  That mode keeps every round's edge latents:
 see :func:`edge_training_bytes`.
+
+Each mode's step is written once, as pieces over the rows a runner holds (:class:`NodeStreamSteps`,
+:class:`EdgeStreamSteps`): :class:`_NodeStream` / :class:`_EdgeStreams` run them over a whole graph, ``dist.ShardedTraining``
+/ ``dist.ShardedEdgeTraining`` over one spatial tile, with its halo exchanges between the pieces.
 """
 from __future__ import annotations
 
@@ -118,7 +122,8 @@ class _TrainMLP:
 
 
 class TrainPacks:
-    """All node-stream MLPs of an ``EncodeProcessDecode`` packed for training."""
+    """All node-stream MLPs of an ``EncodeProcessDecode`` packed for training.  ``all`` lists them in
+    ``model.parameters()`` order: the order of :meth:`params` and of every flat gradient list."""
 
     def __init__(self, model):
         from .graph_network import _split_mlp
@@ -155,7 +160,8 @@ class NodeStreamSteps:
     ``agg_i`` per round; the backward seeds ``dx`` from the decoders, runs each round's node MLP backward and ends with
     the encoder's, collecting the parameter gradients.  :class:`_NodeStream` runs them over a whole graph;
     ``dist.ShardedTraining`` over one spatial tile's owned rows, with its halo exchanges in between.  Between
-    :meth:`round_backward` of round i and the next, the caller adds ``A^T du2`` (and ``du1``) into ``dx``."""
+    :meth:`round_backward` of round i and the next, the caller adds ``A^T du2`` (and ``du1``) into ``dx``.
+    :class:`EdgeStreamSteps` adds the edge stream's pieces (``message_source="edge"``) and inherits the rest."""
 
     def _encode(self, packs: TrainPacks, x0: torch.Tensor) -> None:
         self.packs, self.x0 = packs, x0
@@ -195,7 +201,8 @@ class NodeStreamSteps:
         """Round ``i``'s node MLP backward: -> ``(du1, du2)``.  With x_{i+1} = x_i + f(x_i, agg(x_i)) the caller then
         forms dx_i = dx_{i+1} + du1 + A^T du2 (A^T: senders <- receivers)."""
         r = self.packs.rounds[i]
-        du1, du2, self.grads_of[id(r)] = r.backward(self.xs[i], self.aggs[i], self.dx, self.scratch, True, True)
+        x = self.xs[i][:self.x0.shape[0]]       # the receiver rows (an edge-mode table may hold sender-only rows behind them)
+        du1, du2, self.grads_of[id(r)] = r.backward(x, self.aggs[i], self.dx, self.scratch, True, True)
         self.aggs[i] = None
         return du1, du2
 
@@ -299,13 +306,9 @@ class EdgeTrainPacks(TrainPacks):
             raise CgnnError("edge-mode training needs one hidden width and depth across the model's MLPs")
         if self.enc_edge.in1 > 32:
             raise CgnnError(f"edge-mode training takes at most 32 edge features (got {self.enc_edge.in1})")
-
-    def params(self) -> List[torch.Tensor]:
-        """In ``model.parameters()`` order: encoder (node, edge), per round (edge, node), decoders."""
-        out = self.enc.params() + self.enc_edge.params()
-        for e, r in zip(self.edges, self.rounds):
-            out += e.params() + r.params()
-        return out + self.dec_acc.params() + self.dec_tr.params()
+        # in model.parameters() order: encoder (node, edge), per round (edge, node), decoders
+        self.all = [self.enc, self.enc_edge] + [m for pair in zip(self.edges, self.rounds) for m in pair] + \
+            [self.dec_acc, self.dec_tr]
 
 
 def edge_training_bytes(num_edges: int, latent: int, hidden: int, num_hidden_layers: int, rounds: int) -> int:
@@ -321,83 +324,173 @@ def free_device_bytes(device) -> int:
     return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
+def _edge_rows(t: "ops.TiledRows", lo: int, hi: int) -> "ops.TiledRows":
+    """Edges [lo, hi) of TILED32 edge rows as a view of ``t.buf`` (``lo`` on a tile boundary)."""
+    if lo % 32 or not 0 <= lo <= hi <= t.n:
+        raise CgnnError(f"edge rows [{lo}, {hi}) of {t.n} do not start on a 32-edge tile")
+    rows = (hi - lo + 31) // 32 * 32
+    return ops.TiledRows(hi - lo, t.width, t.device, buf=t.buf[lo:lo + rows])
+
+
+class EdgeStreamSteps(NodeStreamSteps):
+    """One training step under ``message_source="edge"`` (node AND edge stream) as pieces over the rows a runner holds.
+    The receivers are the rows of ``x0``, the first rows of every table ``xs[i]``; a table may hold ``n_rows`` rows, the
+    rest sender-only (a tile's ghosts, which the runner fills).  ``src`` / ``dst`` are the local edge lists,
+    receiver-major; ``fixed_k`` edges per receiver, 0 for a general edge list (whole range only).
+    :class:`_EdgeStreams` runs the pieces over a whole graph, ``dist.ShardedEdgeTraining`` over one spatial tile in two
+    receiver ranges, with its halo exchanges in between.
+
+    Forward, per round i: :meth:`_new_round`, :meth:`_project` of the rows whose ``x_i`` is there, :meth:`_round_forward` for
+    receiver ranges whose senders are projected; then :meth:`decode`.  Kept: every table ``x_i``, ``agg_i`` and the input
+    edge latents ``e_i`` of every round.  The ``P_F32`` tables ``Ps`` / ``Pd`` live from a round's first projection to
+    their last reader: one pair through the forward, dropped by :meth:`decode`; one pair per round in the backward,
+    dropped once ``cgnn_edge_mlp_backward`` has run.
+
+    Backward (``dx`` = dL/dx_{i+1} on the receivers), per round from the last: :meth:`_round_backward_edges` (a tile
+    then sums dh1 at its ghost senders), :meth:`_round_backward_sums` (a tile then adds the ``dPs`` rows its peers
+    return), :meth:`_round_backward_finish`; then :meth:`encode_backward`."""
+
+    def _encode(self, packs: "EdgeTrainPacks", x0: torch.Tensor, edge_attr: torch.Tensor, src: torch.Tensor,
+                dst: torch.Tensor, fixed_k: int, n_rows: Optional[int] = None) -> None:
+        """Node encoder into the receiver rows of ``xs[0]``, edge encoder into ``es[0]`` (TILED32), the shared ``e_upd``."""
+        n = x0.shape[0]
+        self.packs, self.x0, self.edge_attr = packs, x0, edge_attr
+        self.src, self.dst, self.fixed_k = src, dst, fixed_k
+        self.n_rows = n if n_rows is None else n_rows
+        self.xs = [self._rows(self.n_rows if packs.rounds else n, packs.latent)]
+        ops.mlp_rows(packs.enc.fwd, x0, out=self.xs[0][:n])             # raw features: three bf16 terms or exact
+        self.es = [ops.mlp_rows(packs.enc_edge.fwd, edge_attr, tiled=True)]
+        self.aggs = []
+        self._e_upd = self.es[0].empty_like()
+        self._ps = self._pd = None
+
+    def _rows(self, n: int, width: int) -> torch.Tensor:
+        return torch.empty((n, width), dtype=torch.float32, device=self.x0.device)
+
+    def _new_round(self) -> None:
+        """Room for the next round's ``agg_i``, ``x_{i+1}`` (a table of ``n_rows`` unless the decoders read it) and
+        ``e_{i+1}`` (e_i is kept for the backward; the last round's e_L is not needed)."""
+        i, n, D = len(self.aggs), self.x0.shape[0], self.packs.latent
+        last = i + 1 == len(self.packs.rounds)
+        self.aggs.append(self._rows(n, D))
+        self.xs.append(self._rows(n if last else self.n_rows, D))
+        if not last:
+            self.es.append(self.es[i].empty_like())
+
+    def _project(self, i: int, a: int, b: int) -> None:
+        """Round ``i``'s ``P_F32`` tables for rows [a, b) of ``xs[i]``: ``Ps`` and ``Pd`` for receivers, ``Ps`` alone for
+        sender-only rows.  The backward recomputes the forward's tables by the same calls on the same rows, bit for bit."""
+        ep, x, n = self.packs.edges[i], self.xs[i], self.x0.shape[0]
+        if self._ps is None:
+            self._ps, self._pd = self._rows(self.n_rows, ep.hidden), self._rows(n, ep.hidden)
+        wd, pd = (ep.wd, self._pd[a:b]) if a < n else (None, None)
+        ops.project_nodes(ep.ws, wd, x[a:b], self._ps[a:b], pd, p_format=_lib.P_F32)
+
+    def _round_forward(self, i: int, a: int, b: int) -> None:
+        """Round ``i`` for receivers [a, b) (``a * fixed_k`` on a 32-edge tile): edge block, aggregate, node block."""
+        p, k = self.packs, self.fixed_k
+        if k == 0 and (a, b) != (0, self.x0.shape[0]):
+            raise CgnnError("a general edge list runs for all receivers at once")
+        lo, hi = (a * k, b * k) if k else (0, self.es[i].n)
+        ep, r, x = p.edges[i], p.rounds[i], self.xs[i]
+        src, dst = self.src[lo:hi], self.dst[lo:hi]
+        e, e_upd = _edge_rows(self.es[i], lo, hi), _edge_rows(self._e_upd, lo, hi)
+        if i + 1 == len(p.rounds):          # e_L is not kept: the update alone
+            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, e_upd, None, residual=False)
+        else:
+            ops.edge_block(ep.fwd, self._ps, self._pd, src, dst, e, _edge_rows(self.es[i + 1], lo, hi), e_upd,
+                           residual=True)
+        agg = self.aggs[i][a:b]
+        ops.aggregate(e_upd, None, dst, b - a, k, hi - lo, agg)
+        ops.node_block(r.run, r.run.layers[0], r.run2, x[a:b], agg, self.xs[i + 1][a:b], True)
+
+    def decode(self):
+        self._e_upd = self._ps = self._pd = None        # the forward's scratch
+        return super().decode()
+
+    def decode_backward(self, d_acc: Optional[torch.Tensor], d_tr: Optional[torch.Tensor]) -> None:
+        super().decode_backward(d_acc, d_tr)
+        p, ne, dev = self.packs, self.es[0].n, self.x0.device
+        self._escratch = ops.BackwardScratch(ne, p.hidden, max(p.latent, 32), p.nh, dev)
+        self._dy = torch.empty((max(ne, 1), p.latent), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i
+        self._de = self.es[0].empty_like()      # d e_i, in place: TILED32 between rounds, rows after round 0
+
+    def _round_backward_edges(self, i: int) -> torch.Tensor:
+        """Node MLP backward of round ``i``, the forward's ``Ps`` / ``Pd`` recomputed, the edge model's backward over the
+        local edges: -> ``escratch.g_a[0]`` = dh1 of every edge, which all that follows in the round reads."""
+        ep, n = self.packs.edges[i], self.x0.shape[0]
+        self._du1, d_agg = self.round_backward(i)
+        self._project(i, 0, n)
+        if self.n_rows > n:
+            self._project(i, n, self.n_rows)
+        de, first = self._de, i == 0
+        ops.edge_mlp_backward(ep.rec, ep.bwd, self._ps, self._pd, self.src, self.dst, self.es[i], d_agg,
+                              None if i + 1 == len(self.packs.rounds) else de, self._escratch, self._dy,
+                              de.buf if first else de, de_out_rows=first, n_recv=n)
+        self._ps = self._pd = None
+        return self._escratch.g_a[0]
+
+    def _round_backward_sums(self, i: int, by_sender_e: "ops.SenderCsr", by_receiver_e=None) -> None:
+        """The edge-row reductions of round ``i`` (:func:`edge_row_grads`; ``dy`` receives ``e_i`` in rows), then ``dPs`` /
+        ``dPd`` of the receiver rows (:func:`edge_receiver_sums`); ``dPs`` of sender-only rows is the runner's."""
+        self._row_grads = edge_row_grads(self.packs.edges[i], self._escratch, self._dy, self.es[i])
+        self._dps, self._dpd = edge_receiver_sums(self._escratch.g_a[0], self.es[0].n, self.x0.shape[0], self.dst,
+                                                  self.fixed_k, by_sender_e, by_receiver_e)
+
+    def _round_backward_finish(self, i: int) -> None:
+        """Given the complete ``dPs``: ``dWs`` / ``dWd`` / ``db1`` over the receiver rows, the round's edge-model gradients,
+        ``dx <- dx + du1 + Ws^T dPs + Wd^T dPd``; releases ``e_i`` and ``x_{i+1}``."""
+        ep = self.packs.edges[i]
+        dw0, layer_grads, dgamma, dbeta = self._row_grads
+        db0 = edge_node_grads(ep, dw0, self._dps, self._dpd, self.xs[i][:self.x0.shape[0]])
+        self.grads_of[id(ep)] = [dw0, db0] + layer_grads + [dgamma, dbeta]
+        self.dx = ops.linear2_rows(ep.wst, ep.wdt, self._dps, self._dpd, add1=self.dx, add2=self._du1, out=self.dx)
+        self._du1 = self._dps = self._dpd = self._row_grads = None
+        self.es[i] = self.xs[i + 1] = None
+
+    def encode_backward(self, need_dx0: bool = True, need_dea: bool = False) -> Optional[torch.Tensor]:
+        """The node encoder's backward (-> ``dx0`` of the receivers) and the edge encoder's: ``d_edge_attr`` of the local
+        edges when ``need_dea``, else None."""
+        p, de = self.packs, self._de
+        dx0 = super().encode_backward(need_dx0)
+        if not p.rounds:
+            de.buf.zero_()                  # no round reads the edge encoder's output
+        # round 0 wrote d e_0 in rows: what the encoder's backward reads as dy
+        dea, _, self.grads_of[id(p.enc_edge)] = p.enc_edge.backward(self.edge_attr, None, de.buf[:de.n], self._escratch,
+                                                                    need_dea)
+        self.d_edge_attr = dea if need_dea else None
+        self._de = self._dy = self._escratch = None
+        return dx0
+
+
 class _EdgeStreams(torch.autograd.Function):
-    """acceleration, temp_rate = f(x0, edge_attr; all parameters) under ``message_source="edge"``: node AND edge stream.
-    Non-tensor context first, then ``x0``, ``edge_attr`` and the parameters in ``EdgeTrainPacks.params()`` order."""
+    """acceleration, temp_rate = f(x0, edge_attr; all parameters) under ``message_source="edge"``: the pieces of
+    :class:`EdgeStreamSteps` over a whole graph (every row a receiver, all receivers in one range).  Non-tensor context
+    first, then ``x0``, ``edge_attr`` and the parameters in ``EdgeTrainPacks.params()`` order."""
 
     @staticmethod
     def forward(ctx, packs: EdgeTrainPacks, graph, x0: torch.Tensor, edge_attr: torch.Tensor, *params: torch.Tensor):
-        src, dst, fixed_k, _, _ = graph
-        n, ne = x0.shape[0], src.numel()
-        xs = [ops.mlp_rows(packs.enc.fwd, x0)]
-        es = [ops.mlp_rows(packs.enc_edge.fwd, edge_attr, tiled=True)]       # raw features: three bf16 terms or exact
-        aggs = []
-        e_upd = es[0].empty_like()
-        for i, (ep, r) in enumerate(zip(packs.edges, packs.rounds)):
-            x, e = xs[-1], es[-1]
-            ps, pd = ops.project_nodes(ep.ws, ep.wd, x, p_format=_lib.P_F32)
-            last = i == len(packs.rounds) - 1
-            # e_{i+1} = e_i + u into a new buffer (e_i is kept for the backward); the last round's e_L is not needed
-            e_next = None if last else e.empty_like()
-            if last:
-                ops.edge_block(ep.fwd, ps, pd, src, dst, e, e_upd, None, residual=False)
-            else:
-                ops.edge_block(ep.fwd, ps, pd, src, dst, e, e_next, e_upd, residual=True)
-            agg = ops.aggregate(e_upd, None, dst, n, fixed_k, ne)
-            aggs.append(agg)
-            xs.append(ops.node_block(r.run, r.run.layers[0], r.run2, x, agg, None, residual=True))
-            if not last:
-                es.append(e_next)
-        del e_upd
-        acc = ops.mlp_rows(packs.dec_acc.run, xs[-1])
-        tr = ops.mlp_rows(packs.dec_tr.run, xs[-1])
-        ctx.packs, ctx.graph, ctx.x0, ctx.edge_attr, ctx.xs, ctx.es, ctx.aggs = packs, graph, x0, edge_attr, xs, es, aggs
-        return acc, tr
+        run = EdgeStreamSteps()
+        run._encode(packs, x0, edge_attr, *graph[:3])           # src, dst, fixed_k
+        for i in range(len(packs.rounds)):
+            run._new_round()
+            run._project(i, 0, x0.shape[0])
+            run._round_forward(i, 0, x0.shape[0])
+        ctx.run, ctx.graph = run, graph
+        return run.decode()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_acc, d_tr):
-        packs, (src, dst, fixed_k, by_sender_e, by_receiver_e), x0, xs, es = ctx.packs, ctx.graph, ctx.x0, ctx.xs, ctx.es
-        n, D, H, nh = x0.shape[0], packs.latent, packs.hidden, packs.nh
-        ne = src.numel()
-        dev = x0.device
-        scratch = ops.BackwardScratch(n, H, max(D, 32), nh, dev)
-        escratch = ops.BackwardScratch(ne, H, max(D, 32), nh, dev)
-        dy = torch.empty((max(ne, 1), D), dtype=torch.float32, device=dev)   # dy of the edge rows; then e_i as rows
-        de = es[0].empty_like()        # d e_i, updated in place: TILED32 between rounds, row-major after round 0
-        grads_of = {}
-        xl = xs[-1]
-        zero = lambda t, w: torch.zeros((n, w), dtype=torch.float32, device=dev) if t is None else t  # noqa: E731
-        dx, _, grads_of[id(packs.dec_acc)] = packs.dec_acc.backward(xl, None, zero(d_acc, packs.dec_acc.out_dim), scratch, True)
-        dx2, _, grads_of[id(packs.dec_tr)] = packs.dec_tr.backward(xl, None, zero(d_tr, packs.dec_tr.out_dim), scratch, True)
-        dx = dx.add_(dx2)
-        L = len(packs.rounds)
-        for i in range(L - 1, -1, -1):
-            r, ep, x, e = packs.rounds[i], packs.edges[i], xs[i], es[i]
-            agg = ctx.aggs[i]
-            ctx.aggs[i] = None
-            du1, d_agg, grads_of[id(r)] = r.backward(x, agg, dx, scratch, True, True)
-            ps, pd = ops.project_nodes(ep.ws, ep.wd, x, p_format=_lib.P_F32)     # the forward's tables, bit for bit
-            first = i == 0
-            ops.edge_mlp_backward(ep.rec, ep.bwd, ps, pd, src, dst, e, d_agg, None if i == L - 1 else de, escratch, dy,
-                                  de.buf if first else de, de_out_rows=first)
-            del ps, pd
-            grads_of[id(ep)], dps, dpd = edge_round_grads(ep, escratch, dy, e, x, dst, fixed_k, by_sender_e, by_receiver_e)
-            # dx_i = dx_{i+1} + du1 + Ws^T dPs + Wd^T dPd
-            dx = ops.linear2_rows(ep.wst, ep.wdt, dps, dpd, add1=dx, add2=du1, out=dx)
-            es[i] = None
-        need_dx0, need_dea = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        dx0, _, grads_of[id(packs.enc)] = packs.enc.backward(x0, None, dx, scratch, need_dx0)
-        if L == 0:
-            de.buf.zero_()             # no round reads the edge encoder's output
-        de_rows = de.buf[:ne]          # round 0 wrote d e_0 in rows: what the encoder's backward reads as dy
-        dea, _, grads_of[id(packs.enc_edge)] = packs.enc_edge.backward(ctx.edge_attr, None, de_rows, escratch, need_dea)
-        flat = grads_of[id(packs.enc)] + grads_of[id(packs.enc_edge)]
-        for ep, r in zip(packs.edges, packs.rounds):
-            flat += grads_of[id(ep)] + grads_of[id(r)]
-        flat += grads_of[id(packs.dec_acc)] + grads_of[id(packs.dec_tr)]
-        ctx.xs = ctx.es = None
-        return (None, None, dx0 if need_dx0 else None, dea if need_dea else None, *flat)
+        run, (_, _, _, by_sender_e, by_receiver_e) = ctx.run, ctx.graph
+        ctx.run = None
+        run.decode_backward(d_acc, d_tr)
+        for i in range(len(run.packs.rounds) - 1, -1, -1):
+            run._round_backward_edges(i)
+            run._round_backward_sums(i, by_sender_e, by_receiver_e)
+            run._round_backward_finish(i)
+        dx0 = run.encode_backward(ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        return (None, None, dx0, run.d_edge_attr, *run.local_grads())
 
 
 def edge_round_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Tensor, e: "ops.TiledRows", x: torch.Tensor,
@@ -406,19 +499,22 @@ def edge_round_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Te
     """After ``ops.edge_mlp_backward`` of round ``ep`` (``escratch`` / ``dy`` filled, ``e`` the round's input edge latents,
     ``x`` its node latents): -> (parameter gradients in ``ep.params()`` order, dPs, dPd) with every reduction in a fixed
     order.  ``dy`` is overwritten (it receives ``e`` in rows for ``dWe``)."""
-    ne, n = e.n, x.shape[0]
-    H = ep.hidden
-    dev = x.device
-    g_a0 = escratch.g_a[0]
     dw0, layer_grads, dgamma, dbeta = edge_row_grads(ep, escratch, dy, e)
-    if ne:
-        dps = ops.aggregate_csr(g_a0, by_sender_e)
-        dpd = ops.aggregate(g_a0, None, dst, n, fixed_k, ne) if fixed_k > 0 else ops.aggregate_csr(g_a0, by_receiver_e)
-    else:
-        dps = torch.zeros((n, H), dtype=torch.float32, device=dev)
-        dpd = torch.zeros_like(dps)
+    dps, dpd = edge_receiver_sums(escratch.g_a[0], e.n, x.shape[0], dst, fixed_k, by_sender_e, by_receiver_e)
     db0 = edge_node_grads(ep, dw0, dps, dpd, x)
     return [dw0, db0] + layer_grads + [dgamma, dbeta], dps, dpd
+
+
+def edge_receiver_sums(g_a0: torch.Tensor, ne: int, n: int, dst: torch.Tensor, fixed_k: int, by_sender_e: "ops.SenderCsr",
+                       by_receiver_e: Optional["ops.SenderCsr"]):
+    """dh1 (``g_a0``, one row per edge) summed at the first ``n`` rows of the edge CSR ``by_sender_e`` -> ``dPs``, and at
+    the ``n`` receivers (fixed-k segments, or ``by_receiver_e`` for a general list) -> ``dPd``; zeros without edges."""
+    if not ne:
+        dps = torch.zeros((n, g_a0.shape[1]), dtype=torch.float32, device=g_a0.device)
+        return dps, torch.zeros_like(dps)
+    dps = ops.aggregate_csr(g_a0, by_sender_e, row_range=(0, n))
+    dpd = ops.aggregate(g_a0, None, dst, n, fixed_k, ne) if fixed_k > 0 else ops.aggregate_csr(g_a0, by_receiver_e)
+    return dps, dpd
 
 
 def edge_row_grads(ep: _TrainEdge, escratch: ops.BackwardScratch, dy: torch.Tensor, e: "ops.TiledRows"):

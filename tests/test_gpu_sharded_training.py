@@ -283,6 +283,33 @@ def test_loopback_shards_train_like_one_gpu(world, n, k, d, L, prec):
     assert all(torch.equal(a, b) for o, o2 in zip(outs, outs2) for a, b in zip(o, o2))
 
 
+def test_world_of_one_is_the_one_gpu_step_bit_for_bit():
+    """One tile that is the whole graph in the graph's own row order, its receivers run in two ranges around a no-op
+    halo: the launches of the one-GPU step on the same rows, so predictions, parameter gradients and dx0 are the same bits."""
+    n, k, d, L, prec, n_interior = 1000, 16, 64, 2, "fp32x3", 500
+    g, sd, dt = _problem(n, k, d, L, seed=67)
+    model = _model(sd, d, L, prec)
+    model.locality_sort = False                         # the one-GPU step sums its rows in the graph's order too
+    want_pred, _, want_grads, want_dx = _unsharded_step(model, g, dt)
+    ids = torch.arange(n, dtype=torch.int64, device=DEV)
+    sh = cdist.Shard(rank=0, world=1, k=k, n_owned=n, n_ghost=0, owned_global=ids, ghost_global=ids[:0],
+                     src_local=g.edge_index[0].to(torch.int32).contiguous(),
+                     dst_local=g.edge_index[1].to(torch.int32).contiguous(), edge_attr=g.edge_attr.detach().contiguous(),
+                     recv_counts=[0], send_counts=[0], send_idx=torch.empty(0, dtype=torch.int32, device=DEV),
+                     x_feat=g.x.detach().contiguous(), n_interior=n_interior)
+    runner = cdist.ShardedTraining(model, sh, halo=cdist._LocalHalo())
+    assert type(runner) is cdist.ShardedTraining
+    x = sh.x_feat.clone().requires_grad_(True)
+    pred = runner(x)
+    _global_loss(pred["acceleration"], pred["temp_rate"], g, dt).backward()
+    assert torch.equal(pred["acceleration"].detach(), want_pred["acceleration"])
+    assert torch.equal(pred["temp_rate"].detach(), want_pred["temp_rate"])
+    got = {name: p.grad for name, p in model.named_parameters() if p.grad is not None}
+    assert set(got) == set(want_grads)
+    assert [name for name in got if not torch.equal(got[name], want_grads[name])] == []
+    assert torch.equal(x.grad, want_dx)
+
+
 def test_full_size_cfg4_shape_trains_through_eight_loopback_tiles():
     """cfg4's shape (4 M particles, k = 16, latent 128, 10 rounds) on 8 tiles, one step, against the unsharded HIP step
     (no CPU oracle at this size)."""

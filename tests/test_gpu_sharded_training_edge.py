@@ -278,6 +278,52 @@ def test_full_size_cfg2_shape_trains_through_eight_loopback_tiles():
     assert _err(dx0, want_dx) <= GTOL and _err(dea, want_dea) <= GTOL
 
 
+# ---- a world of one is the one-GPU step ---------------------------------------------------------------------------------
+
+def _whole_graph_shard(g, k, n_interior):
+    """The whole graph as the one tile of a world of one, in the graph's own row order: no ghosts, nothing to send."""
+    n, dev = g.x.shape[0], g.x.device
+    ids = torch.arange(n, dtype=torch.int64, device=dev)
+    return cdist.Shard(rank=0, world=1, k=k, n_owned=n, n_ghost=0, owned_global=ids, ghost_global=ids[:0],
+                       src_local=g.edge_index[0].to(torch.int32).contiguous(),
+                       dst_local=g.edge_index[1].to(torch.int32).contiguous(),
+                       edge_attr=g.edge_attr.detach().contiguous(), recv_counts=[0], send_counts=[0],
+                       send_idx=torch.empty(0, dtype=torch.int32, device=dev), x_feat=g.x.detach().contiguous(),
+                       n_interior=n_interior)
+
+
+@pytest.mark.parametrize("n,k,d,L,prec,n_interior,n_split", [
+    (1000, 12, 32, 2, "fp32", 517, 512),                # rounded to a 32-edge tile, both ranges non-empty
+    (1000, 12, 32, 2, "fp32", 0, 0),                    # everything in the boundary part
+    (1000, 12, 32, 2, "fp32", 1000, 1000),              # everything in the interior part
+    (1000, 16, 128, 2, "fp32x3", 500, 500),             # the two-fp16-term edge kernel and its two-term recomputation
+    (1000, 16, 64, 1, "fp32x3", 500, 500),              # the last round is also round 0, with de_out_rows
+    (1000, 16, 64, 0, "fp32", 500, 500),                # no round: the encoders and the decoders alone
+])
+def test_world_of_one_is_the_one_gpu_step_bit_for_bit(n, k, d, L, prec, n_interior, n_split):
+    """One tile that is the whole graph, run in two receiver ranges around a no-op halo, makes the launches of the one-GPU
+    step on the same rows (the partial launches are row-independent, every reduction runs over the same rows in a fixed
+    order): predictions, every parameter gradient, dx0 and d edge_attr are the same bits."""
+    g, sd, dt = _problem(n, k, d, L, seed=29 + d + k + L)
+    model = _model(sd, d, L, prec)
+    model.locality_sort = False                         # the one-GPU step sums its rows in the graph's order too
+    want_pred, _, want_grads, want_dx, want_dea = _unsharded_step(model, g, dt)
+    sh = _whole_graph_shard(g, k, n_interior)
+    runner = cdist.ShardedTraining(model, sh, halo=cdist._LocalHalo())
+    assert isinstance(runner, cdist.ShardedEdgeTraining) and runner.n_split == n_split
+    x = sh.x_feat.clone().requires_grad_(True)
+    ea = sh.edge_attr.clone().requires_grad_(True)
+    pred = runner(x, ea)
+    _global_loss(pred["acceleration"], pred["temp_rate"], g, dt).backward()
+    assert torch.equal(pred["acceleration"].detach(), want_pred["acceleration"])
+    assert torch.equal(pred["temp_rate"].detach(), want_pred["temp_rate"])
+    got = {name: p.grad for name, p in model.named_parameters() if p.grad is not None}
+    assert set(got) == set(want_grads) == {name for name, _ in model.named_parameters()}
+    assert [name for name in got if not torch.equal(got[name], want_grads[name])] == []
+    assert torch.equal(x.grad, want_dx)
+    assert torch.equal(ea.grad, want_dea)
+
+
 # ---- refusals and the memory guard -----------------------------------------------------------------------------------
 
 def test_sharded_edge_training_refusals_and_guard(monkeypatch):
