@@ -51,11 +51,15 @@ EXPORTS = (
     "cgnn_pair_counts_workspace_bytes", "cgnn_pair_counts", "cgnn_frame_errors_workspace_bytes", "cgnn_frame_errors",
     "cgnn_mass_assign", "cgnn_power_bin_ids", "cgnn_power_bins_workspace_bytes", "cgnn_power_bins",
     "cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue", "cgnn_mass_assign_backward",
+    "cgnn_mass_assign_weighted", "cgnn_mass_assign_weighted_backward",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
+WEIGHT_BITS = 20              # CGNN_MA_WEIGHT_BITS: a quantised weight of 2^20 is one value scale (cgnn_mass_assign_weighted)
+WEIGHTED_MAX_PARTICLES = 1 << 23   # n (2^39 + 14) must stay inside int64
+WEIGHTED_MAX_CHANNELS = 4     # CGNN_MA_MAX_CHANNELS
 POWER_MAX_BINS = 256          # CGNN_PB_MAX_BINS
 FOF_MAX_BINS = 256            # CGNN_FOF_MAX_BINS in csrc/fof.hip
 FOF_DISP_UNITS = 1 << 30      # cgnn_fof_catalogue: disp counts displacements in box_size / 2^30
@@ -155,6 +159,9 @@ def load() -> C.CDLL:
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]
     lib.cgnn_mass_assign.argtypes = [vp, i64, i64, f32, i32, i32, vp, vp]
     lib.cgnn_mass_assign_backward.argtypes = [vp, vp, i64, i64, f32, i32, i32, C.c_double, vp, vp]
+    lib.cgnn_mass_assign_weighted.argtypes = [vp, vp, i64, i64, i32, f32, i32, i32, vp, vp]
+    lib.cgnn_mass_assign_weighted_backward.argtypes = [vp, vp, vp, i64, i64, i32, f32, i32, i32, C.c_double, C.c_double,
+                                                       vp, vp, vp]
     lib.cgnn_fof_labels_workspace_bytes.restype = sz
     lib.cgnn_fof_labels_workspace_bytes.argtypes = [i64]
     lib.cgnn_fof_labels.argtypes = [vp, i64, f32, f32, vp, vp, sz, vp]

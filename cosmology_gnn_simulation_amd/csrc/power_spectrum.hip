@@ -21,6 +21,13 @@
 // function at the forward's u, in the forward's cells, the other two axes' weights being the forward's integers / Q).
 // Float64, every operation in a fixed place (ma_gather_kernel), no atomics: the numpy restatement gives the same bits.
 //
+// Weighted deposit.  cgnn_mass_assign_weighted deposits up to four quantised per-particle weights q (|q| <= 2^20 = one
+// value scale) at once: the cells, the axis weights and the guard are the plain deposit's (ma_axis), and a cell whose
+// product is v receives (v q + 2^19) >> 20 in channel c, in int64 with an arithmetic shift.  Signed contributions are
+// added as two's complement on the unsigned mesh; the sums are still integers, so the bits do not depend on the order
+// of arrival.  cgnn_mass_assign_weighted_backward is its transpose with respect to the weights and the positions,
+// straight through both quantisations (ma_gather_weighted_kernel).
+//
 // Binning.  A mode of the rfft array [M, M, M/2 + 1] has signed frequencies nx, ny in (-M/2, M/2] and nz in [0, M/2];
 // n2 = nx^2 + ny^2 + nz^2 <= 3 * 256^2 is exact in integers and in float32.  With e2[i] = fl32(k_edges[i]^2) the mode
 // is in bin i iff e2[i] <= (float)n2 < e2[i + 1]; n2 = 0 is never counted.  Its Hermitian weight h is 1 on the planes
@@ -107,6 +114,53 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __r
             }
 }
 
+#define CGNN_MA_WEIGHT_BITS 20    // a quantised weight of 2^20 is one value scale
+#define CGNN_MA_MAX_CHANNELS 4
+
+__device__ __forceinline__ int ma_clamp_q(int q) {
+    const int one = 1 << CGNN_MA_WEIGHT_BITS;
+    return q < -one ? -one : (q > one ? one : q);
+}
+
+// one thread per particle of every frame, cells and weights once for its C channels; q [total, C]; mesh [frames, C, M,
+// M, M], zeroed by the caller.  |v q| <= 2^59; >> of a negative long long is arithmetic (hipcc, as every two's
+// complement target).
+template <int ORDER, int C>
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_weighted_kernel(const float* __restrict__ pos,
+                                                                         const int32_t* __restrict__ q, int64_t total,
+                                                                         int64_t n, float s, int M,
+                                                                         unsigned long long* __restrict__ mesh) {
+    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    int cell[3][ORDER], w[3][ORDER];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        float u = __fmul_rn(pos[3 * i + ax], s);
+        if (!(fabsf(u) < 1.0e9f)) u = 0.f;          // the guard of ma_deposit_kernel
+        ma_axis<ORDER>(u, M, cell[ax], w[ax]);
+    }
+    long long qc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) qc[c] = ma_clamp_q(q[C * i + c]);
+    const int64_t cells = (int64_t)M * M * M;
+    unsigned long long* base = mesh + (i / n) * (C * cells);
+#pragma unroll
+    for (int a = 0; a < ORDER; ++a)
+#pragma unroll
+        for (int b = 0; b < ORDER; ++b)
+#pragma unroll
+            for (int c3 = 0; c3 < ORDER; ++c3) {
+                const long long v = (long long)w[0][a] * w[1][b] * w[2][c3];
+                if (v == 0) continue;
+                unsigned long long* at = base + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c3];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const long long add = (v * qc[c] + ((long long)1 << (CGNN_MA_WEIGHT_BITS - 1))) >> CGNN_MA_WEIGHT_BITS;
+                    if (add != 0) atomicAdd(at + c * cells, (unsigned long long)add);
+                }
+            }
+}
+
 // The transpose of the deposit (cgnn_mass_assign_backward): ma_axis at the forward's u, plus the derivative of the
 // unquantised assignment function with respect to u in difference form.  With g[0 .. ORDER - 2] the differences of the
 // mesh gradient between neighbouring cells along the axis, the axis' derivative is  sum_t dw[t] g[t]:
@@ -179,6 +233,76 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_kernel(const float* __re
         }
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) d_pos[3 * i + ax] = (float)((acc[ax] * (double)s) * scale);
+}
+
+// The transpose of the weighted deposit (cgnn_mass_assign_weighted_backward), one thread per particle of every frame,
+// no atomics.  d_field [frames, C, M, M, M]; per channel the thread gathers its ORDER^3 cells once (D) and forms
+//     val = sum over a (outer), b, c (inner) of ((wv0[a] * wv1[b]) * wv2[c]) * D[a][b][c]        from 0.0, in loop order
+//     g[ax] = ma_gather_kernel's acc[ax] on D                                                     (the same order)
+// d_val[i, ch] = fl32(val * scale_val);  chan[ax] += a_ch * g[ax] over the channels in ascending order, from 0.0, with
+// a_ch = (double)clamp(q) * 2^-20;  d_pos[i, ax] = fl32((chan[ax] * (double)s) * scale_pos).  Either output may be null.
+template <int ORDER, int C>
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_weighted_kernel(const float* __restrict__ pos,
+                                                                        const int32_t* __restrict__ q,
+                                                                        const double* __restrict__ d_field, int64_t total,
+                                                                        int64_t n, float s, int M, double scale_pos,
+                                                                        double scale_val, float* __restrict__ d_pos,
+                                                                        float* __restrict__ d_val) {
+    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    int cell[3][ORDER];
+    double wv[3][ORDER], dw[3][ORDER - 1];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) ma_axis_grad<ORDER>(pos[3 * i + ax], s, M, cell[ax], wv[ax], dw[ax]);
+    const int64_t cells = (int64_t)M * M * M;
+    const double* base = d_field + (i / n) * (C * cells);
+    double chan[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+        double D[ORDER][ORDER][ORDER];
+#pragma unroll
+        for (int a = 0; a < ORDER; ++a)
+#pragma unroll
+            for (int b = 0; b < ORDER; ++b)
+#pragma unroll
+                for (int c = 0; c < ORDER; ++c)
+                    D[a][b][c] = base[ch * cells + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c]];
+        if (d_val) {
+            double val = 0.0;
+#pragma unroll
+            for (int a = 0; a < ORDER; ++a)
+#pragma unroll
+                for (int b = 0; b < ORDER; ++b)
+#pragma unroll
+                    for (int c = 0; c < ORDER; ++c) val += ((wv[0][a] * wv[1][b]) * wv[2][c]) * D[a][b][c];
+            d_val[C * i + ch] = (float)(val * scale_val);
+        }
+        if (d_pos) {
+            double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int p = 0; p < ORDER; ++p)
+#pragma unroll
+                for (int r = 0; r < ORDER; ++r) {
+                    double line[ORDER];
+#pragma unroll
+                    for (int t = 0; t < ORDER; ++t) line[t] = D[t][p][r];
+                    acc[0] += (ma_diff<ORDER>(line, dw[0]) * wv[1][p]) * wv[2][r];
+#pragma unroll
+                    for (int t = 0; t < ORDER; ++t) line[t] = D[p][t][r];
+                    acc[1] += (ma_diff<ORDER>(line, dw[1]) * wv[0][p]) * wv[2][r];
+#pragma unroll
+                    for (int t = 0; t < ORDER; ++t) line[t] = D[p][r][t];
+                    acc[2] += (ma_diff<ORDER>(line, dw[2]) * wv[0][p]) * wv[1][r];
+                }
+            const double a_ch = (double)ma_clamp_q(q[C * i + ch]) * (1.0 / (double)(1 << CGNN_MA_WEIGHT_BITS));
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) chan[ax] += a_ch * acc[ax];
+        }
+    }
+    if (d_pos) {
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) d_pos[3 * i + ax] = (float)((chan[ax] * (double)s) * scale_pos);
+    }
 }
 
 static inline size_t pb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -338,6 +462,54 @@ static size_t pb_window_bytes() { return pb_align256((size_t)(CGNN_MA_MAX_MESH /
 
 using namespace cgnn;
 
+#define CGNN_MA_WEIGHTED_MAX_N ((int64_t)1 << 23)
+
+// the refusals the two weighted entries share; 0 when the arguments are legal
+static int ma_weighted_refuses(const char* who, bool null_pointer, int64_t frames, int64_t n, int32_t channels,
+                               float box_size, int32_t mesh, int32_t order, int32_t min_order) {
+    if (null_pointer || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
+        set_error("%s: invalid argument", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (mesh < 2 || mesh > CGNN_MA_MAX_MESH || order < min_order || order > 3) {
+        set_error("%s: mesh=%d outside [2, %d] or order=%d outside [%d, 3]%s", who, (int)mesh, CGNN_MA_MAX_MESH, (int)order,
+                  (int)min_order, min_order == 2 ? " (NGP has no gradient)" : "");
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (channels < 1 || channels > CGNN_MA_MAX_CHANNELS) {
+        set_error("%s: channels=%d outside [1, %d]", who, (int)channels, CGNN_MA_MAX_CHANNELS);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n > CGNN_MA_WEIGHTED_MAX_N) {
+        set_error("%s: more than 2^23 particles in a frame (a particle adds up to 2^39 + 14 in magnitude per channel: "
+                  "n of them in one cell must stay inside int64)", who);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    return CGNN_OK;
+}
+
+template <int ORDER>
+static void ma_launch_weighted(int channels, unsigned blocks, hipStream_t st, const float* p, const int32_t* q,
+                               int64_t total, int64_t n, float s, int M, unsigned long long* m) {
+    if (channels == 1) ma_deposit_weighted_kernel<ORDER, 1><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
+    else if (channels == 2) ma_deposit_weighted_kernel<ORDER, 2><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
+    else if (channels == 3) ma_deposit_weighted_kernel<ORDER, 3><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
+    else ma_deposit_weighted_kernel<ORDER, 4><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
+}
+
+template <int ORDER>
+static void ma_launch_weighted_gather(int channels, unsigned blocks, hipStream_t st, const float* p, const int32_t* q,
+                                      const double* d, int64_t total, int64_t n, float s, int M, double scale_pos,
+                                      double scale_val, float* d_pos, float* d_val) {
+#define CGNN_MA_GATHER(C) \
+    ma_gather_weighted_kernel<ORDER, C><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, d, total, n, s, M, scale_pos, scale_val, d_pos, d_val)
+    if (channels == 1) CGNN_MA_GATHER(1);
+    else if (channels == 2) CGNN_MA_GATHER(2);
+    else if (channels == 3) CGNN_MA_GATHER(3);
+    else CGNN_MA_GATHER(4);
+#undef CGNN_MA_GATHER
+}
+
 extern "C" {
 
 int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
@@ -403,6 +575,56 @@ int cgnn_mass_assign_backward(const float* pos, const double* d_mesh, int64_t fr
         else ma_gather_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, m, total, n, s, mesh, scale, g);
     }
     return check_hip(hipGetLastError(), "cgnn_mass_assign_backward");
+}
+
+int cgnn_mass_assign_weighted(const float* pos, const int32_t* q, int64_t frames, int64_t n, int32_t channels,
+                              float box_size, int32_t mesh, int32_t order, int64_t* out, void* stream) {
+    int rc = ma_weighted_refuses("cgnn_mass_assign_weighted", !pos || !q || !out, frames, n, channels, box_size, mesh,
+                                 order, 1);
+    if (rc) return rc;
+    const float s = (float)mesh / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t cells = (int64_t)mesh * mesh * mesh;
+    rc = check_hip(hipMemsetAsync(out, 0, (size_t)frames * channels * cells * sizeof(int64_t), st),
+                   "cgnn_mass_assign_weighted memset");
+    if (rc) return rc;
+    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^23: at least two frames)
+    const int64_t step = CGNN_PS_MAX_THREADS / n;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
+        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        const float* p = pos + f0 * n * 3;
+        const int32_t* w = q + f0 * n * channels;
+        unsigned long long* m = reinterpret_cast<unsigned long long*>(out) + f0 * channels * cells;
+        if (order == 1) ma_launch_weighted<1>(channels, blocks, st, p, w, total, n, s, mesh, m);
+        else if (order == 2) ma_launch_weighted<2>(channels, blocks, st, p, w, total, n, s, mesh, m);
+        else ma_launch_weighted<3>(channels, blocks, st, p, w, total, n, s, mesh, m);
+    }
+    return check_hip(hipGetLastError(), "cgnn_mass_assign_weighted");
+}
+
+int cgnn_mass_assign_weighted_backward(const float* pos, const int32_t* q, const double* d_field, int64_t frames,
+                                       int64_t n, int32_t channels, float box_size, int32_t mesh, int32_t order,
+                                       double scale_pos, double scale_val, float* d_pos, float* d_val, void* stream) {
+    int rc = ma_weighted_refuses("cgnn_mass_assign_weighted_backward", !pos || !q || !d_field || (!d_pos && !d_val),
+                                 frames, n, channels, box_size, mesh, order, 2);
+    if (rc) return rc;
+    const float s = (float)mesh / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^23: at least two frames)
+    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
+        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        const float* p = pos + f0 * n * 3;
+        const int32_t* w = q + f0 * n * channels;
+        const double* d = d_field + f0 * channels * cells;
+        float* gp = d_pos ? d_pos + f0 * n * 3 : nullptr;
+        float* gv = d_val ? d_val + f0 * n * channels : nullptr;
+        if (order == 2) ma_launch_weighted_gather<2>(channels, blocks, st, p, w, d, total, n, s, mesh, scale_pos, scale_val, gp, gv);
+        else ma_launch_weighted_gather<3>(channels, blocks, st, p, w, d, total, n, s, mesh, scale_pos, scale_val, gp, gv);
+    }
+    return check_hip(hipGetLastError(), "cgnn_mass_assign_weighted_backward");
 }
 
 int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream) {

@@ -2095,7 +2095,7 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
                           min_image_edge_attr: bool = False, knn_grid: str = "uniform", decomposition: str = "uniform",
                           group=None, device=None, checkpoint: str = "none", density_loss_weight: float = 0.0,
                           density_mesh: Optional[int] = None, density_order: int = 2,
-                          density_smoothing: float = 0.0) -> "training.UnrolledLoss":
+                          density_smoothing: float = 0.0, thermal_loss_weight: float = 0.0) -> "training.UnrolledLoss":
     """``training.unrolled_loss`` over the ranks of ``group`` (a world of one when no process group is up): the same
     arguments and meaning, S model steps unrolled from one window and differentiated through the whole chain, each rank
     computing the rows of its spatial tile.  Every rank passes the same windows and targets of all N particles (checked
@@ -2130,13 +2130,18 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
 
     The density term of ``training.unrolled_loss`` is not computed over shards (a rank deposits its own rows, and
     meshes are not summed across ranks): the ``density_*`` arguments are named so that the two signatures stay one,
-    and a non-zero ``density_loss_weight`` raises ``NotImplementedError`` before any device work."""
+    and a non-zero ``density_loss_weight`` raises ``NotImplementedError`` before any device work.  The thermal term
+    likewise: ``thermal_loss_weight`` is named, and refused when it is not zero."""
     w, n, S, weights = training._unroll_arguments(model, position_seq, temperature_seq, target_positions,
                                                   target_temperatures, step_weights, backprop_steps, num_neighbors,
                                                   knn_grid, min_image_edge_attr, checkpoint)
     if training._density_arguments(density_loss_weight, density_mesh, density_order, density_smoothing,
                                    "sharded_unrolled_loss") is not None:
         raise NotImplementedError("sharded_unrolled_loss: the density term is one box on one GPU (training.unrolled_loss); "
+                                  "meshes are not summed across spatial shards")
+    if training._density_arguments(thermal_loss_weight, density_mesh, density_order, density_smoothing,
+                                   "sharded_unrolled_loss", name="thermal_loss_weight") is not None:
+        raise NotImplementedError("sharded_unrolled_loss: the thermal term is one box on one GPU (training.unrolled_loss); "
                                   "meshes are not summed across spatial shards")
     if decomposition not in DECOMPOSITIONS:
         raise ValueError(f"sharded_unrolled_loss: decomposition {decomposition!r}; known: {DECOMPOSITIONS}")

@@ -89,3 +89,33 @@ def density_field_loss(pos_pred: torch.Tensor, pos_true: torch.Tensor, box_size:
         delta_true = ops.density_contrast(pos_true, box_size, mesh, order)
     kernel = gaussian_filter(mesh, box_size, smoothing, delta_pred.device) if smoothing > 0 else None
     return _mean_square(delta_pred - delta_true, kernel)
+
+
+def thermal_field_loss(pos_pred: torch.Tensor, temp_pred: torch.Tensor, pos_true: torch.Tensor, temp_true: torch.Tensor,
+                       box_size: float, mesh: int, order: int = 2, smoothing: float = 0.0) -> torch.Tensor:
+    """The field-level loss of a predicted frame's internal energy: ``mean((F_pred - F_true)^2) / mean(temp_true)^2`` over
+    the ``mesh^3`` cells, ``F = ops.weighted_field(pos, temp)`` the internal-energy-weighted field (exact integer CIC /
+    TSC deposits of the quantised temperatures, ``order`` 2 / 3; its mean over the cells is the mean temperature).  Both
+    deposits share ``value_scale = 2 max|temp_true|`` (a detached 0-d device tensor: a prediction up to twice the
+    largest true value is not clamped).  0-d float64, differentiable in ``pos_pred`` and ``temp_pred``
+    (``cgnn_mass_assign_weighted_backward``); the true frame is deposited without autograd.  ``[N, 3]`` with ``[N]`` or
+    ``[N, 1]``, or with a leading ``T`` for the mean over T frames as well.  ``smoothing``: as in
+    :func:`density_field_loss`.  A true frame whose temperatures are all zero has no scale: the result is ``nan``.
+
+    ``ValueError`` before any device work: the refusals of :func:`density_field_loss`, temperatures that do not go with
+    the positions.  One box, one GPU; no host synchronisation."""
+    who = "thermal_field_loss"
+    mesh = check_density_loss(who, mesh, order, smoothing)
+    if pos_pred.shape != pos_true.shape:
+        raise ValueError(f"{who}: pos_pred {tuple(pos_pred.shape)} and pos_true {tuple(pos_true.shape)} differ in shape")
+    lead = tuple(pos_pred.shape[:-1])
+    for name, t in (("temp_pred", temp_pred), ("temp_true", temp_true)):
+        if tuple(t.shape) not in (lead, lead + (1,)):
+            raise ValueError(f"{who}: {name} must be {list(lead)} or {list(lead) + [1]}, got {tuple(t.shape)}")
+    temp_true = temp_true.detach()
+    scale = 2.0 * temp_true.abs().max().to(torch.float64)
+    f_pred = ops.weighted_field(pos_pred, temp_pred.reshape(lead), box_size, mesh, order, scale)
+    with torch.no_grad():
+        f_true = ops.weighted_field(pos_true, temp_true.reshape(lead), box_size, mesh, order, scale)
+    kernel = gaussian_filter(mesh, box_size, smoothing, f_pred.device) if smoothing > 0 else None
+    return _mean_square(f_pred - f_true, kernel) / temp_true.to(torch.float64).mean() ** 2

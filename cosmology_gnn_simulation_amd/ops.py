@@ -1025,6 +1025,202 @@ def density_contrast(pos: torch.Tensor, box_size: float, mesh: int, order: int =
         return _DensityContrast.apply(pos, box_size, mesh, order)
 
 
+def _check_value_scale(value_scale, who: str):
+    """``value_scale`` as a positive finite float, or a 0-d tensor left as it is (not read: no synchronisation)."""
+    if torch.is_tensor(value_scale):
+        if value_scale.dim() != 0:
+            raise ValueError(f"{who}: a tensor value_scale must be 0-d, got {tuple(value_scale.shape)}")
+        return value_scale
+    if isinstance(value_scale, bool) or not isinstance(value_scale, (int, float)) or not math.isfinite(value_scale) \
+            or not value_scale > 0:
+        raise ValueError(f"{who}: value_scale must be a positive finite number or a 0-d tensor, got {value_scale!r}")
+    return float(value_scale)
+
+
+def quantize_weights(values: torch.Tensor, value_scale) -> torch.Tensor:
+    """The int32 weights ``cgnn_mass_assign_weighted`` deposits: ``round(clamp(values.double() / value_scale, -1, 1) *
+    2^20)``, ties to even (``_lib.WEIGHT_BITS = 20``), in the shape of ``values``, on their device.  ``value_scale``: a
+    positive float, or a 0-d tensor on the device of ``values`` (not read on the host: no synchronisation).  A value
+    beyond the scale is clamped to it; the step is ``value_scale / 2^20``."""
+    value_scale = _check_value_scale(value_scale, "quantize_weights")
+    if not torch.is_tensor(values) or not (values.is_floating_point() or values.dtype in (torch.int64, torch.int32)):
+        raise ValueError("quantize_weights: values must be a real tensor")
+    scale = value_scale.to(device=values.device, dtype=torch.float64) if torch.is_tensor(value_scale) else value_scale
+    a = torch.clamp(values.to(torch.float64) / scale, -1.0, 1.0)
+    return torch.round(a * float(1 << _lib.WEIGHT_BITS)).to(torch.int32)
+
+
+def _check_weights(what: str, pos: torch.Tensor, values: torch.Tensor, name: str = "values") -> torch.Tensor:
+    """``values`` against ``pos``: ``[N]`` / ``[N, C]`` for ``pos [N, 3]``, ``[T, N]`` / ``[T, N, C]`` for ``[T, N, 3]``, ``1 <= C
+    <= 4`` (``ValueError``) -> ``values`` with its channel axis."""
+    lead = tuple(pos.shape[:-1])
+    if not torch.is_tensor(values) or values.dim() not in (pos.dim() - 1, pos.dim()) or \
+            tuple(values.shape[:pos.dim() - 1]) != lead:
+        raise ValueError(f"{what}: {name} must be {list(lead)} or {list(lead) + ['C']} for pos {tuple(pos.shape)}, got "
+                         f"{tuple(values.shape) if torch.is_tensor(values) else values!r}")
+    if values.dim() == pos.dim() - 1:
+        values = values.unsqueeze(-1)
+    if not 1 <= values.shape[-1] <= _lib.WEIGHTED_MAX_CHANNELS:
+        raise ValueError(f"{what}: {values.shape[-1]} channels; one deposit takes 1 to {_lib.WEIGHTED_MAX_CHANNELS}")
+    if pos.shape[-2] > _lib.WEIGHTED_MAX_PARTICLES:
+        raise ValueError(f"{what}: {pos.shape[-2]} particles per frame exceed 2^23 (a particle adds up to 2^39 + 14 per "
+                         f"channel: N of them in one cell must stay inside int64)")
+    return values
+
+
+def _max_abs_scale(values: torch.Tensor) -> torch.Tensor:
+    """The largest ``|value|`` as a 0-d float64 device tensor (1 when every value is 0, so that 0 / scale is 0)."""
+    m = values.detach().abs().max().to(torch.float64)
+    return torch.where(m > 0, m, torch.ones_like(m))
+
+
+def mass_assign_weighted(pos: torch.Tensor, values: torch.Tensor, box_size: float, mesh: int, order: int = 2,
+                         value_scale=None) -> torch.Tensor:
+    """Per-particle values onto a periodic ``mesh^3`` grid in exact integers (``cgnn_mass_assign_weighted``), up to four
+    channels in one pass: ``values`` is ``[N]`` or ``[N, C]`` for ``pos [N, 3]``, ``[T, N]`` or ``[T, N, C]`` for ``pos [T,
+    N, 3]``; the result is int64 ``[(T,) C, M, M, M]``.  The cells and integer axis weights are those of
+    :func:`mass_assign`; the values are quantised by :func:`quantize_weights` to ``q`` (2^20 per ``value_scale``,
+    clamped beyond it) and a cell whose product of axis weights is ``v`` receives ``(v q + 2^19) >> 20``.  So the mesh
+    stands for ``sum_i W_i(cell) value_i`` in units of ``value_scale / 2^39``: values of exactly ``value_scale`` give the
+    bits of :func:`mass_assign`, zeros give zeros, and the mesh equals the numpy restatement and is the same bits on
+    every run.  ``value_scale=None``: the largest ``|value|`` of the call, taken on the device.  int32 ``values`` are
+    taken as weights that are quantised already (``value_scale`` must then be ``None``).
+
+    Refused on the host before any device work (``ValueError``): the refusals of :func:`mass_assign`, more than 2^23
+    particles per frame, ``C`` outside 1..4, shapes that do not go with ``pos``, a ``value_scale`` that is not positive.
+    No host synchronisation.  One box per call."""
+    what = "mass_assign_weighted"
+    mesh = _check_deposit(what, pos, box_size, mesh, order, (1, 2, 3))
+    values = _check_weights(what, pos, values)
+    if values.dtype == torch.int32:
+        if value_scale is not None:
+            raise ValueError(f"{what}: int32 values are quantised weights already; value_scale must be None")
+        q = values
+    else:
+        if value_scale is not None:
+            value_scale = _check_value_scale(value_scale, what)
+        require_device(values, "values")
+        q = quantize_weights(values, _max_abs_scale(values) if value_scale is None else value_scale)
+    pos = f32c(pos, "pos")
+    q = i32c(q, "values")
+    _same_device(pos, q)
+    batched = pos.dim() == 3
+    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
+    c = q.shape[-1]
+    out = torch.empty((t, c, mesh, mesh, mesh), dtype=torch.int64, device=pos.device)
+    with _timed(what, pos.device):
+        check(_lib.load().cgnn_mass_assign_weighted(pos.data_ptr(), q.data_ptr(), t, n, c, float(box_size), mesh,
+                                                    int(order), out.data_ptr(), stream_ptr(pos.device)),
+              "cgnn_mass_assign_weighted")
+    return out if batched else out[0]
+
+
+def mass_assign_weighted_backward(pos: torch.Tensor, q: torch.Tensor, d_field: torch.Tensor, box_size: float, mesh: int,
+                                  order: int = 2, scale_pos: float = 1.0, scale_val: float = 1.0, want_pos: bool = True,
+                                  want_val: bool = True):
+    """The transpose of :func:`mass_assign_weighted` (``cgnn_mass_assign_weighted_backward``) -> ``(d_pos, d_val)``, float32
+    in the shapes of ``pos`` and of ``q`` with its channel axis (``None`` for the one not wanted).  ``q``: the int32
+    quantised weights (:func:`quantize_weights`), ``[(T,) N]`` or ``[(T,) N, C]``; ``d_field``: float64 ``[(T,) C, M, M, M]``,
+    the gradient of a scalar with respect to ``A_c = sum_i W_i a_ic`` (``W`` in particles per cell, ``a = q / 2^20``).
+    ``d_val = scale_val * dL/da``, ``d_pos = scale_pos * dL/dpos``, straight through both quantisations; float64 with
+    every operation in a fixed place, no atomics, the bits of the numpy restatement.  ``order`` 2 or 3.  No host
+    synchronisation."""
+    what = "mass_assign_weighted_backward"
+    mesh = _check_deposit(what, pos, box_size, mesh, order, (2, 3))
+    q = _check_weights(what, pos, q, "q")
+    if q.dtype != torch.int32:
+        raise ValueError(f"{what}: q must be int32 quantised weights (ops.quantize_weights), got {q.dtype}")
+    if not (want_pos or want_val):
+        raise ValueError(f"{what}: nothing wanted")
+    pos = f32c(pos, "pos")
+    q = i32c(q, "q")
+    batched = pos.dim() == 3
+    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
+    c = q.shape[-1]
+    require_device(d_field, "d_field")
+    shape = ((t,) if batched else ()) + (c,) + (mesh,) * 3
+    if d_field.dtype != torch.float64 or tuple(d_field.shape) != shape:
+        raise CgnnError(f"{what}: d_field must be float64 {shape}, got {d_field.dtype} {tuple(d_field.shape)}")
+    _same_device(pos, q, d_field)
+    d_field = d_field.contiguous()
+    d_pos = torch.empty_like(pos) if want_pos else None
+    d_val = torch.empty(q.shape, dtype=torch.float32, device=pos.device) if want_val else None
+    with _timed(what, pos.device):
+        check(_lib.load().cgnn_mass_assign_weighted_backward(
+            pos.data_ptr(), q.data_ptr(), d_field.data_ptr(), t, n, c, float(box_size), mesh, int(order),
+            float(scale_pos), float(scale_val), ptr(d_pos), ptr(d_val), stream_ptr(pos.device)),
+            "cgnn_mass_assign_weighted_backward")
+    return d_pos, d_val
+
+
+class _WeightedField(torch.autograd.Function):
+    """:func:`weighted_field`: the exact integer weighted deposit forward, ``cgnn_mass_assign_weighted_backward`` behind it."""
+
+    @staticmethod
+    def forward(ctx, pos, values, box_size, mesh, order, scale):
+        q = quantize_weights(values.detach(), scale)
+        grid = mass_assign_weighted(pos.detach(), q, box_size, mesh, order)
+        ctx.args = (box_size, mesh, order, scale)
+        ctx.save_for_backward(pos, q)
+        ctx.values_dtype = values.dtype
+        return grid.to(torch.float64) * (scale * (mesh ** 3 / (pos.shape[-2] * _lib.MASS_ASSIGN_Q ** 3)))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_field):
+        pos, q = ctx.saved_tensors
+        box_size, mesh, order, scale = ctx.args
+        want_pos, want_val = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        per = mesh ** 3 / pos.shape[-2]
+        on_device = torch.is_tensor(scale)
+        d_pos, d_val = mass_assign_weighted_backward(pos, q, d_field, box_size, mesh, order,
+                                                     scale_pos=per if on_device else scale * per, scale_val=per,
+                                                     want_pos=want_pos, want_val=want_val)
+        if want_pos:
+            if on_device:       # the scale is only known on the device: applied behind the kernel, in float64
+                d_pos = (d_pos.to(torch.float64) * scale).to(torch.float32)
+            d_pos = d_pos.to(pos.dtype)
+        if want_val:
+            d_val = d_val.to(ctx.values_dtype)
+        return d_pos, d_val, None, None, None, None
+
+
+def weighted_field(pos: torch.Tensor, values: torch.Tensor, box_size: float, mesh: int, order: int = 2,
+                   value_scale=None) -> torch.Tensor:
+    """The field of per-particle ``values`` on the mesh, float64 ``[(T,) C, M, M, M]``: ``mass_assign_weighted(pos, values)
+    .double() * (value_scale * M^3 / (N 2^39))``, whose mean over the cells is the mean of the values (values of 1 give
+    ``1 + delta``).  ``values``: ``[(T,) N]`` or ``[(T,) N, C]`` (kept with their channel axis: ``[(T,) N]`` gives ``C =
+    1``).  ``value_scale``: a positive float or a 0-d device tensor; ``None`` is the largest ``|value|`` of the call, taken
+    on the device (float64, detached).  Differentiable in ``pos`` and in ``values`` through
+    :func:`mass_assign_weighted_backward`, straight through both quantisations: ``d values = (M^3 / N) sum_cells W d
+    field`` and ``d pos = (value_scale M^3 / N) sum_c a_c grad W . d field_c`` (a ``value_scale`` that lives on the device
+    multiplies ``d pos`` behind the kernel, in float64, at the price of a second rounding to float32).  No gradient flows
+    into ``value_scale``.  ``order=1`` (NGP) with a gradient with respect to ``pos`` requested raises ``ValueError``, like
+    :func:`density_contrast`.  No host synchronisation."""
+    what = "weighted_field"
+    mesh = _check_deposit(what, pos, box_size, mesh, order, (1, 2, 3))
+    values = _check_weights(what, pos, values)
+    if not values.is_floating_point():
+        raise ValueError(f"{what}: values must be floating point, got {values.dtype}")
+    if value_scale is not None:
+        value_scale = _check_value_scale(value_scale, what)
+    grad = torch.is_grad_enabled() and (pos.requires_grad or values.requires_grad)
+    if grad and order == 1:
+        raise ValueError(f"{what}: order 1 (NGP) is piecewise constant in pos and has no gradient; use order 2 (CIC) or "
+                         "3 (TSC), or detach pos and values")
+    require_device(values, "values")
+    if value_scale is None:
+        scale = _max_abs_scale(values)
+    elif torch.is_tensor(value_scale):
+        scale = value_scale.detach().to(device=values.device, dtype=torch.float64)
+    else:
+        scale = value_scale
+    if grad:
+        return _WeightedField.apply(pos, values, box_size, mesh, order, scale)
+    with torch.no_grad():
+        return _WeightedField.apply(pos, values, box_size, mesh, order, scale)
+
+
 def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b: Optional[torch.Tensor] = None,
                plan: Optional[PowerPlan] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Shell sums of the modes of ``delta_k = torch.fft.rfftn(delta)`` (``cgnn_power_bins``): complex128 ``[M, M, M/2 + 1]``

@@ -277,6 +277,308 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
             "cross": sp["cross"], "r": sp["r"], "transfer": sp["transfer"]}
 
 
+# ---- gas fields on the mesh: thermal and momentum spectra ---------------------------------------------------------------
+#
+# ``ops.mass_assign_weighted`` deposits per-particle values in exact integers; what follows forms the fields' spectra with
+# the pieces above.  The weighted shot noise (sums over the particles) is formed on the device in float64 and travels
+# with the shell sums in the one transfer.  Sharded and batched variants, an owned-storage variant (``dist.
+# assemble_frames`` first), redshift-space quantities and an aliasing correction beyond the window deconvolution are
+# not built.
+
+def _check_spectrum_arguments(what: str, box_size, mesh, k_edges, order):
+    mesh = ops.check_mesh(mesh, what)
+    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    return mesh, k_edges
+
+
+def _scalar_values(values: torch.Tensor, frames: torch.Tensor, pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    """Scalar per-particle ``values`` (``[N]`` / ``[N, 1]`` for ``pos [N, 3]``, with a leading ``T`` for frames) -> ``[F, N]``."""
+    lead = tuple(pos.shape[:-1])
+    if not torch.is_tensor(values) or tuple(values.shape) not in (lead, lead + (1,)):
+        raise ValueError(f"{what}: {name} must be {list(lead)} or {list(lead) + [1]} (one scalar per particle), got "
+                         f"{tuple(values.shape) if torch.is_tensor(values) else values!r}")
+    return values.reshape(frames.shape[:2])
+
+
+def _frame_fields(pos: torch.Tensor, values: torch.Tensor, box_size: float, mesh: int, order: int) -> torch.Tensor:
+    """The fields of ``values [F, N, C]`` at ``pos [F, N, 3]`` in value units (float64 ``[F, C, M, M, M]``, the cell mean is
+    the mean value), every frame quantised over its own largest ``|value|``: a frame's field does not depend on the
+    frames it is computed with."""
+    v64 = values.to(torch.float64)
+    scale = v64.abs().amax(dim=(1, 2))
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = ops.quantize_weights(v64 / scale[:, None, None], 1.0)
+    grid = ops.mass_assign_weighted(pos, q, box_size, mesh, order)
+    per = mesh ** 3 / (pos.shape[1] * _lib.MASS_ASSIGN_Q ** 3)
+    return grid.to(torch.float64) * (scale * per)[:, None, None, None, None]
+
+
+def _field_transform(pos: torch.Tensor, values: torch.Tensor, box_size: float, mesh: int, order: int, normalise: str):
+    """-> (``rfftn`` of the scalar field of ``values [F, N]`` at ``pos [F, N, 3]``, complex128 ``[F, M, M, M/2 + 1]``; its
+    shot noise float64 ``[F]``), on the device.  ``"mean"``: the field over its mean, minus one, ``L^3 sum a^2 / (sum
+    a)^2``; ``"none"``: the field in value units (cell mean = mean value), ``L^3 sum value^2 / N^2``."""
+    n, vol = pos.shape[1], float(box_size) ** 3
+    v64 = values.to(torch.float64)
+    s2, s1 = (v64 * v64).sum(dim=1), v64.sum(dim=1)
+    field = _frame_fields(pos, values.unsqueeze(-1), box_size, mesh, order)[:, 0]
+    if normalise == "mean":
+        field = field / (s1 / float(n))[:, None, None, None] - 1.0
+        shot = vol * s2 / (s1 * s1)
+    else:
+        shot = vol * s2 / float(n) ** 2
+    return torch.fft.rfftn(field, dim=(-3, -2, -1)), shot
+
+
+def _to_host_with(modes: torch.Tensor, sums: torch.Tensor, extra: torch.Tensor):
+    """:func:`_to_host` with a float64 tensor of further values in the same transfer."""
+    packed = torch.cat([modes.reshape(-1), sums.view(torch.int64).reshape(-1),
+                        extra.contiguous().view(torch.int64).reshape(-1)]).cpu()
+    a, b = modes.numel(), modes.numel() + sums.numel()
+    return (packed[:a].reshape(modes.shape), packed[a:b].view(torch.float64).reshape(sums.shape),
+            packed[b:].view(torch.float64).reshape(extra.shape))
+
+
+def field_sums_on_device(pos, values, pos_b, values_b, box_size: float, mesh: int, k_edges, order: int, normalise: str):
+    """The device part of :func:`field_power_spectrum` for ``pos [F, N, 3]``, ``values [F, N]`` (and the second set, or
+    ``None``): device tensors ``modes [F, nb]``, ``sums [F, 4, nb]`` (``ops.power_bins``) and the shot noise of the two
+    fields ``[2, F]`` (the first twice without a second set).  No host synchronisation."""
+    a, shot_a = _field_transform(pos, values, box_size, mesh, order, normalise)
+    b, shot_b = (None, shot_a) if pos_b is None else _field_transform(pos_b, values_b, box_size, mesh, order, normalise)
+    modes, sums = ops.power_bins(a, mesh, order, k_edges, b)
+    return modes, sums, torch.stack([shot_a, shot_b])
+
+
+def field_power_spectrum(pos: torch.Tensor, values: torch.Tensor, box_size: float, mesh: int, k_edges=None,
+                         pos_b: Optional[torch.Tensor] = None, values_b: Optional[torch.Tensor] = None, order: int = 2,
+                         normalise: str = "mean", subtract_shot_noise: bool = True) -> Dict:
+    """The power spectrum of the field of scalar per-particle ``values`` (``[N]`` / ``[N, 1]`` at ``pos [N, 3]``, or with a
+    leading ``T``): the thermal-energy field when the values are internal energies.  Deposited in exact integers
+    (``ops.mass_assign_weighted``), deconvolved by the window of ``order``.  ``normalise="mean"``: the spectrum of ``field /
+    mean(field) - 1`` (values of 1 give :func:`power_spectrum`), with the shot noise ``L^3 sum a_i^2 / (sum a_i)^2``;
+    ``"none"``: the spectrum of the field in value units (its cell mean is the mean value), shot noise ``L^3 sum value_i^2
+    / N^2``.  With ``pos_b`` and ``values_b`` also the second field's spectrum and the cross spectrum.  Returns the dict
+    of :func:`power_spectrum` plus ``shot_noise`` (and ``shot_noise_b``), float64 ``[]`` or ``[T]``; the shot noise is
+    subtracted from the auto spectra when ``subtract_shot_noise``, ``r`` comes from the spectra before the subtraction.
+    Everything is computed on the device without a host synchronisation and comes back in one transfer."""
+    what = "field_power_spectrum"
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
+    if normalise not in ("mean", "none"):
+        raise ValueError(f"{what}: normalise must be 'mean' or 'none', got {normalise!r}")
+    if (pos_b is None) != (values_b is None):
+        raise ValueError(f"{what}: pos_b and values_b go together")
+    frames_a = _frames3(pos, "pos", what)
+    val_a = _scalar_values(values, frames_a, pos, "values", what)
+    frames_b = val_b = None
+    if pos_b is not None:
+        frames_b = _frames3(pos_b, "pos_b", what)
+        if pos_b.dim() != pos.dim() or frames_b.shape[0] != frames_a.shape[0]:
+            raise ValueError(f"{what}: pos_b {tuple(pos_b.shape)} does not go with pos {tuple(pos.shape)}")
+        val_b = _scalar_values(values_b, frames_b, pos_b, "values_b", what)
+    modes, sums, shot = _to_host_with(*field_sums_on_device(frames_a, val_a, frames_b, val_b, box_size, mesh, k_edges,
+                                                            order, normalise))
+    single = pos.dim() == 2
+    if single:
+        modes, sums = modes[0], sums[0]
+    out = spectra_from_sums(modes, sums, 1, None if frames_b is None else 1, box_size, mesh, k_edges, False)
+    sa, sb = (shot[0, 0], shot[1, 0]) if single else (shot[0], shot[1])
+    out["shot_noise"] = sa.clone()
+    if frames_b is not None:
+        out["shot_noise_b"] = sb.clone()
+    if subtract_shot_noise:
+        out["power"] = out["power"] - (sa if single else sa[:, None])
+        if frames_b is not None:
+            out["power_b"] = out["power_b"] - (sb if single else sb[:, None])
+            out["transfer"] = torch.sqrt(out["power"] / out["power_b"])
+    return out
+
+
+def _long_weights(mesh: int, device):
+    """``n_c / |n|`` of every mode of the rfft array (float64 ``[3, M, M, M/2 + 1]``; 0 at ``n = 0``), over the signed
+    integer frequencies of ``cgnn_power_bins``: ``n`` in ``(-M/2, M/2]`` on the two full axes, ``[0, M/2]`` on the last."""
+    i = torch.arange(mesh, dtype=torch.float64, device=device)
+    full = torch.where(i <= mesh // 2, i, i - mesh)
+    half = torch.arange(mesh // 2 + 1, dtype=torch.float64, device=device)
+    nx, ny, nz = full[:, None, None], full[None, :, None], half[None, None, :]
+    norm = torch.sqrt(nx * nx + ny * ny + nz * nz)
+    inv = torch.where(norm > 0, 1.0 / norm, torch.zeros_like(norm))
+    return torch.stack([(nx * inv).expand_as(norm), (ny * inv).expand_as(norm), (nz * inv).expand_as(norm)])
+
+
+def momentum_sums_on_device(pos_prev: torch.Tensor, pos: torch.Tensor, dt: float, box_size: float, mesh: int, k_edges, order: int):
+    """The device part of :func:`momentum_power_spectrum`, without a host synchronisation.  For frames ``[F, N, 3]``: device tensors ``modes [F, nb]``, ``total [F, nb]`` and ``div [F, nb]`` (the shell sums of
+    ``sum_c |p_c(k)|^2`` and of ``|a_L(k)|^2``), ``k_sums [F, nb]`` (row 3 of ``ops.power_bins``) and the shot noise ``[F]``."""
+    box = float(box_size)
+    d = (pos - pos_prev).to(torch.float64)
+    vel = (d - box * torch.round(d / box)) / float(dt)                       # the minimum image
+    shot = box ** 3 * (vel * vel).sum(dim=(1, 2)) / float(pos.shape[1]) ** 2
+    field = _frame_fields(pos, vel, box_size, mesh, order)                      # [F, 3, M, M, M]
+    pk = torch.fft.rfftn(field, dim=(-3, -2, -1))                               # [F, 3, M, M, M/2 + 1]
+    del field
+    plan = ops.PowerPlan.of(mesh, k_edges, pos.device)
+    total = None
+    for c in range(3):
+        modes, sums = ops.power_bins(pk[:, c].contiguous(), mesh, order, k_edges, None, plan)
+        total = sums[:, 0] if total is None else total + sums[:, 0]
+    a_long = (pk * _long_weights(mesh, pos.device)).sum(dim=1)
+    modes, sums = ops.power_bins(a_long.contiguous(), mesh, order, k_edges, None, plan)
+    return modes, total, sums[:, 0], sums[:, 3], shot
+
+
+def momentum_power_spectrum(pos_prev: torch.Tensor, pos: torch.Tensor, dt: float, box_size: float, mesh: int,
+                            k_edges=None, order: int = 2, subtract_shot_noise: bool = True) -> Dict:
+    """The power spectrum of the momentum field of a frame ``pos`` (``[N, 3]`` or ``[T, N, 3]``) whose velocities are
+    ``minimum_image(pos - pos_prev) / dt``, and its split into the longitudinal (divergence) and the transverse (curl)
+    part.  One three-channel deposit at ``pos`` (``ops.mass_assign_weighted``; the field in velocity units, its cell mean
+    the mean velocity), three ``rfftn``.  Returns (CPU, float64 / int64, ``[nb]`` or ``[T, nb]``) ``k_lo``, ``k_hi``,
+    ``k_mean``, ``modes`` and
+
+    * ``power_total``: ``L^3 / M^6`` times the mean over the shell of ``sum_c |p_c(k)|^2 / W2``;
+    * ``power_div``: likewise of ``|a_L|^2``, ``a_L = sum_c n_c p_c(k) / |n|`` over the signed integer frequencies
+      (``a_L = 0`` at ``n = 0``, which is never counted);
+    * ``power_curl = power_total - power_div``;
+    * ``shot_noise``: ``L^3 sum |v_i|^2 / N^2``, subtracted from ``power_total`` (a third of it from ``power_div``, the
+      rest from ``power_curl``) when ``subtract_shot_noise``.
+
+    No host synchronisation; one transfer."""
+    what = "momentum_power_spectrum"
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
+    if isinstance(dt, bool) or not (float(dt) > 0.0 and math.isfinite(float(dt))):
+        raise ValueError(f"{what}: dt must be positive and finite, got {dt!r}")
+    frames = _frames3(pos, "pos", what)
+    if tuple(pos_prev.shape) != tuple(pos.shape):
+        raise ValueError(f"{what}: pos_prev {tuple(pos_prev.shape)} and pos {tuple(pos.shape)} differ in shape")
+    prev = _frames3(pos_prev, "pos_prev", what)
+    modes, total, div, k_sums, shot = momentum_sums_on_device(prev, frames, dt, box_size, mesh, k_edges, order)
+    nan = torch.full_like(total, float("nan"))
+    modes, sums, shot = _to_host_with(modes, torch.stack([total, div, nan, k_sums], dim=1), shot)
+    return _momentum_spectra(modes, sums, shot, box_size, mesh, k_edges, subtract_shot_noise, pos.dim() == 2)
+
+
+def _momentum_spectra(modes, sums, shot, box_size, mesh, k_edges, subtract_shot_noise: bool, single: bool) -> Dict:
+    """Host arithmetic of :func:`momentum_power_spectrum` from ``modes [F, nb]``, ``sums [F, 4, nb]`` (rows: total, div,
+    unused, ``sqrt(n2)``) and ``shot [F]``."""
+    # the two rows go through spectra_from_sums as a pair of auto spectra
+    sp = spectra_from_sums(modes, sums, 1, 1, box_size, mesh, k_edges, False)
+    total, div = sp["power"], sp["power_b"]
+    if subtract_shot_noise:
+        total, div = total - shot[:, None], div - shot[:, None] / 3.0
+    out = {"k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "k_mean": sp["k_mean"], "modes": sp["modes"], "power_total": total,
+           "power_div": div, "power_curl": total - div, "shot_noise": shot}
+    if single:
+        out = {k: (v if k in ("k_lo", "k_hi") else v[0].clone()) for k, v in out.items()}
+    return out
+
+
+def rollout_gas_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                        mesh: int, dt: Optional[float] = None, k_edges=None, frames: Optional[Sequence[int]] = None,
+                        order: int = 2) -> Dict:
+    """Gas statistics of a rollout against the truth in Fourier space, for the dicts ``rollout.rollout`` returns
+    (``Coordinates [T, N, 3]``, ``InternalEnergy [T, N(, 1)]``).  ``frames``: the frame numbers to judge (default: every
+    frame both hold).  Per selected frame (``[F, nb]``, CPU, float64):
+
+    * ``thermal_power_pred``, ``thermal_power_true``: the shot-noise-subtracted spectra of the internal-energy-weighted
+      field over its mean (:func:`field_power_spectrum`, ``normalise="mean"``), positions and weights of the same frame;
+      ``thermal_cross``, ``thermal_r`` (``|r| <= 1``) and ``thermal_transfer`` (``sqrt(pred / true)``, ``nan`` where a
+      subtracted spectrum is negative) of the predicted against the true field;
+    * ``thermal_density_r_pred``, ``thermal_density_r_true``: the correlation coefficient of that field with the density
+      contrast of the same frame ("is the hot gas where the dense gas is");
+    * with ``dt``: ``momentum_div_pred``, ``momentum_div_true``, ``momentum_curl_pred``, ``momentum_curl_true``
+      (:func:`momentum_power_spectrum`, shot noise subtracted), velocities from the frame before in the same dict;
+      frame 0 has no predecessor and is ``nan``,
+
+    plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean`` and ``modes`` (``[nb]``).  Everything is computed on the device of the
+    rollout without a host synchronisation per frame; the results come back in one transfer."""
+    what = "rollout_gas_spectra"
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
+    if dt is not None and (isinstance(dt, bool) or not (float(dt) > 0.0 and math.isfinite(float(dt)))):
+        raise ValueError(f"{what}: dt must be positive and finite, got {dt!r}")
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    tc = ground_truth["Coordinates"].to(dev)
+    pe, te = rollout_data["InternalEnergy"].to(dev), ground_truth["InternalEnergy"].to(dev)
+    avail = min(len(pc), len(tc), len(pe), len(te))
+    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
+    if not sel or min(sel) < 0 or max(sel) >= avail:
+        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
+    if pc.shape[1:] != tc.shape[1:]:
+        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
+    _frames3(pc, "Coordinates", what)
+    n, nf = pc.shape[1], len(sel)
+    if pe.numel() != len(pe) * n or te.numel() != len(te) * n:
+        raise ValueError(f"{what}: InternalEnergy does not hold one value per particle and frame")
+    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
+    cp, ct = pc.index_select(0, idx), tc.index_select(0, idx)
+    ep, et = pe.index_select(0, idx).reshape(nf, n), te.index_select(0, idx).reshape(nf, n)
+    moving = None
+    rows = [i for i, f in enumerate(sel) if f > 0]
+    if dt is not None and rows:
+        prev = torch.tensor([sel[i] - 1 for i in rows], dtype=torch.int64).to(dev)
+        rows = torch.tensor(rows, dtype=torch.int64).to(dev)
+        moving = (rows, pc.index_select(0, prev), tc.index_select(0, prev))
+    modes, sums, extra = _to_host_with(*gas_sums_on_device(cp, ct, ep, et, box_size, mesh, k_edges, order, dt, moving))
+    return _gas_spectra(modes, sums, extra, sel, box_size, mesh, dt, k_edges)
+
+
+def gas_sums_on_device(cp, ct, ep, et, box_size: float, mesh: int, k_edges, order: int, dt=None, moving=None):
+    """The device part of :func:`rollout_gas_spectra` for the selected predicted and true frames ``cp``, ``ct [F, N, 3]``
+    and their internal energies ``ep``, ``et [F, N]``: ``modes [F, nb]``, ``sums [3 or 5, F, 4, nb]`` (thermal pred x true,
+    thermal x density of the predicted and of the true frames, and with ``moving`` the momentum rows of the two) and
+    ``extra [2 or 4, F]`` (the shot noises).  ``moving``: ``None``, or ``(rows, prev_p, prev_t)``, the (device) indices of
+    the selected frames that have a predecessor and those predecessors ``[len(rows), N, 3]``.  No host synchronisation."""
+    dev = cp.device
+    n, nf, nb = cp.shape[1], cp.shape[0], len(k_edges) - 1
+    plan = ops.PowerPlan.of(mesh, k_edges, dev)
+    fp, shot_p = _field_transform(cp, ep, box_size, mesh, order, "mean")
+    ft, shot_t = _field_transform(ct, et, box_size, mesh, order, "mean")
+
+    def contrast(pos):
+        grid = ops.mass_assign(pos, box_size, mesh, order)
+        return torch.fft.rfftn(grid.to(torch.float64) * (mesh ** 3 / (n * _lib.MASS_ASSIGN_Q ** 3)) - 1.0, dim=(-3, -2, -1))
+
+    modes, thermal = ops.power_bins(fp, mesh, order, k_edges, ft, plan)
+    _, with_p = ops.power_bins(fp, mesh, order, k_edges, contrast(cp), plan)
+    _, with_t = ops.power_bins(ft, mesh, order, k_edges, contrast(ct), plan)
+    sums, extra = [thermal, with_p, with_t], [shot_p, shot_t]
+    if moving is not None:
+        rows, prev_p, prev_t = moving
+        for cur, prev in ((cp, prev_p), (ct, prev_t)):
+            _, total, div, k_sums, shot = momentum_sums_on_device(prev, cur.index_select(0, rows), dt, box_size, mesh,
+                                                                  k_edges, order)
+            block = torch.full((nf, 4, nb), float("nan"), dtype=torch.float64, device=dev)
+            block.index_copy_(0, rows, torch.stack([total, div, torch.full_like(total, float("nan")), k_sums], dim=1))
+            shot_all = torch.full((nf,), float("nan"), dtype=torch.float64, device=dev)
+            shot_all.index_copy_(0, rows, shot)
+            sums.append(block)
+            extra.append(shot_all)
+    return modes, torch.stack(sums), torch.stack(extra)
+
+
+def _gas_spectra(modes, sums, extra, sel, box_size, mesh, dt, k_edges) -> Dict:
+    """Host arithmetic of :func:`rollout_gas_spectra`."""
+    nf, nb = modes.shape
+    sp = spectra_from_sums(modes, sums[0], 1, 1, box_size, mesh, k_edges, False)
+    power_p, power_t = sp["power"] - extra[0][:, None], sp["power_b"] - extra[1][:, None]
+    out = {"frames": sel, "k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "k_mean": sp["k_mean"][0].clone(),
+           "modes": sp["modes"][0].clone(), "thermal_power_pred": power_p, "thermal_power_true": power_t,
+           "thermal_cross": sp["cross"], "thermal_r": sp["r"], "thermal_transfer": torch.sqrt(power_p / power_t),
+           "thermal_shot_noise_pred": extra[0].clone(), "thermal_shot_noise_true": extra[1].clone()}
+    for which, name in ((1, "pred"), (2, "true")):
+        out["thermal_density_r_" + name] = spectra_from_sums(modes, sums[which], 1, 1, box_size, mesh, k_edges, False)["r"]
+    if dt is not None:
+        for which, name in ((3, "pred"), (4, "true")):
+            if len(sums) > 3:
+                mom = _momentum_spectra(modes, sums[which], extra[which - 1], box_size, mesh, k_edges, True, False)
+                out["momentum_div_" + name], out["momentum_curl_" + name] = mom["power_div"], mom["power_curl"]
+            else:
+                nan = torch.full((nf, nb), float("nan"), dtype=torch.float64)
+                out["momentum_div_" + name], out["momentum_curl_" + name] = nan, nan.clone()
+    return out
+
+
 def default_linking_length(n: int, box_size: float, b: float = 0.2) -> float:
     """``b`` mean interparticle spacings: ``b * box_size / n ** (1 / 3)``."""
     if int(n) < 1:

@@ -969,21 +969,33 @@ def density_loss_bytes(density_mesh: int, smoothed: bool = False) -> int:
     return 16 * m ** 3 + (40 * m * m * (m // 2 + 1) if smoothed else 0)
 
 
+def thermal_loss_bytes(num_particles: int, thermal_mesh: int, smoothed: bool = False) -> int:
+    """What the thermal term of :func:`unrolled_loss` keeps of one step until the backward: the meshes of
+    :func:`density_loss_bytes` (the difference of the two fields and the gradient on its way to the particles, one
+    channel) and the particles' quantised temperatures (int32)."""
+    return density_loss_bytes(thermal_mesh, smoothed) + 4 * int(num_particles)
+
+
 def unrolled_training_bytes(num_particles: int, num_neighbors: int, window: int, latent: int, hidden: int,
                             num_hidden_layers: int, rounds: int, steps: int, edge_messages: bool = False,
-                            checkpoint: str = "none", density_mesh: int = 0, density_smoothed: bool = False) -> int:
+                            checkpoint: str = "none", density_mesh: int = 0, density_smoothed: bool = False,
+                            thermal_mesh: int = 0) -> int:
     """Device memory S unrolled steps keep alive until the backward: S times the one-step activations -- the node
     features, ``x_i`` and ``agg_i`` of every round (:class:`NodeStreamSteps`), the edge features, and under
     ``message_source="edge"`` every round's input edge latents (:func:`edge_training_bytes`) -- plus one backward
     scratch (``(2 nh + 3) H`` floats per node row, and per edge row in edge mode), which the steps' backwards use in turn.
     ``checkpoint="steps"``: one step's activations, the scratch, and S small records (:func:`step_record_bytes`).
     ``density_mesh = M > 0``: the density term is on and every step whose activations are kept keeps
-    :func:`density_loss_bytes` as well (``density_smoothed``: with a smoothing length); 0, the default, adds nothing."""
+    :func:`density_loss_bytes` as well (``density_smoothed``: with a smoothing length); 0, the default, adds nothing.
+    ``thermal_mesh = M > 0``: the thermal term is on and adds :func:`thermal_loss_bytes` in the same way (it shares
+    ``density_smoothed``); 0, the default, adds nothing."""
     check_checkpoint(checkpoint, "unrolled_training_bytes")
     n = int(num_particles)
     per_step, scratch = _activation_floats(n, n * int(num_neighbors), window, latent, hidden, num_hidden_layers, rounds,
                                            edge_messages)
     field = density_loss_bytes(density_mesh, density_smoothed) if density_mesh else 0
+    if thermal_mesh:
+        field += thermal_loss_bytes(n, thermal_mesh, density_smoothed)
     if checkpoint == "steps":
         return 4 * (per_step + scratch) + field + int(steps) * step_record_bytes(n, num_neighbors, edge_messages)
     return 4 * (int(steps) * per_step + scratch) + int(steps) * field
@@ -997,12 +1009,14 @@ class UnrolledLoss:
     on every rank), ``loss`` then being this rank's part to differentiate.  ``offsets``: ``None``; from
     :func:`unrolled_batch_loss` the B + 1 row offsets of the simulations in the frames' ``n_total`` rows.
     ``density_losses``: ``None``; with ``unrolled_loss(density_loss_weight != 0)`` the detached float64 ``[S]`` of every
-    step's ``losses.density_field_loss``, unweighted (``step_losses`` stays ``[S, 3]``)."""
+    step's ``losses.density_field_loss``, unweighted (``step_losses`` stays ``[S, 3]``).  ``thermal_losses``: likewise for
+    ``unrolled_loss(thermal_loss_weight != 0)`` and ``losses.thermal_field_loss``."""
 
     def __init__(self, loss, step_losses, frames, graphs, value=None):
         self.loss, self.step_losses, self.frames, self.graphs, self.value = loss, step_losses, frames, graphs, value
         self.offsets = None     # unrolled_batch_loss: B + 1 ints, simulation b holds rows offsets[b]:offsets[b + 1]
         self.density_losses = None
+        self.thermal_losses = None
 
 
 # ---- activation checkpointing across steps (unrolled_loss(checkpoint="steps")) -------------------------------------------
@@ -1038,6 +1052,7 @@ class _StepRecord:
         self.s, self.weight, self.live = s, weight, live
         self.senders = self.order = self.edge_attr = self.terms = self.graph = None
         self.density = None     # the step's unweighted density term (detached 0-d float64) when that term is on
+        self.thermal = None     # likewise the thermal term
         self.shard = self.cap = self.value = None       # dist.sharded_unrolled_loss: the step's Shard and send capacity
 
 
@@ -1051,9 +1066,10 @@ class _Unroll:
     :meth:`publish`.  ``sample0(want)`` makes step 0's sample of the true window, as ``ops.training_sample`` returns it."""
 
     def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0,
-                 knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False, density=None):
+                 knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False, density=None, thermal=None):
         self.model, self.cfg, self.w, self.n, self.k = model, cfg, w, n, k
         self.density = density          # None, or (weight, mesh, order, smoothing) of the density term
+        self.thermal = thermal          # None, or (weight, mesh, order, smoothing) of the thermal term
         self.loss_weights, self.checkpoint, self.sample0 = loss_weights, checkpoint, sample0
         self.knn_grid, self.min_image, self.keep_graphs = knn_grid, min_image, keep_graphs
         self.edge = getattr(model, "message_source", "x_j") == "edge"
@@ -1114,9 +1130,13 @@ class _Unroll:
                     cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach(), recent.detach(),
                               order, k)
         new_p = new_t = None
-        if integrate or self.density is not None:
+        field_terms = self.density is not None or self.thermal is not None
+        if integrate or field_terms:
             p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
-            if rec.live and grad:
+            if (rec.live or self.thermal is not None) and grad:
+                # the thermal term reads the temperature the step makes: where the outgoing link is cut or absent the
+                # step's own integration carries its gradient, through ``rate`` as well; the frame handed on is detached
+                # below
                 new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, p2, p1, t1)
             elif self.density is not None and grad:
                 # the step's own integration carries the density term's gradient where its outgoing link is cut or
@@ -1132,8 +1152,14 @@ class _Unroll:
             loss_s = loss_s + (weight * field).to(torch.float32)
             if not kept:
                 rec.density = field.detach()
-            if not rec.live:
-                new_p, new_t = new_p.detach(), new_t.detach()
+        if self.thermal is not None:
+            weight, mesh, order, smoothing = self.thermal
+            field = losses.thermal_field_loss(new_p, new_t, tgt_p, tgt_t, cfg.box, mesh, order, smoothing)
+            loss_s = loss_s + (weight * field).to(torch.float32)
+            if not kept:
+                rec.thermal = field.detach()
+        if field_terms and not rec.live:
+            new_p, new_t = new_p.detach(), new_t.detach()
         return rec.weight * loss_s, new_p, new_t
 
     def run(self, pos_frames, tmp_frames, tgt_p, tgt_t, weights, backprop_steps, s0=None) -> UnrolledLoss:
@@ -1144,7 +1170,7 @@ class _Unroll:
         self.checkpointed = self.checkpoint == "steps" and S > 1 and any(q.requires_grad for q in self.params)
         self.s0 = s0
         total = value = None
-        terms, graphs, out_p, out_t, fields = [], [], [], [], []
+        terms, graphs, out_p, out_t, fields, thermals = [], [], [], [], [], []
         for s in range(S):
             # link s feeds step s + 1 and carries gradient when it is one of the last `links`
             rec = _StepRecord(s, weights[s], s < S - 1 and s >= S - 1 - links)
@@ -1159,6 +1185,7 @@ class _Unroll:
                 value = weights[s] * rec.value if value is None else value + weights[s] * rec.value
             terms.append(rec.terms)
             fields.append(rec.density)
+            thermals.append(rec.thermal)
             graphs.append(rec.graph)
             rec.graph = None
             new_p, new_t = self.publish(rec, *made)
@@ -1170,6 +1197,8 @@ class _Unroll:
         out = UnrolledLoss(total, torch.stack(terms), frames, graphs if self.keep_graphs else None, value)
         if self.density is not None:
             out.density_losses = torch.stack(fields)
+        if self.thermal is not None:
+            out.thermal_losses = torch.stack(thermals)
         return out
 
 
@@ -1272,7 +1301,7 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
                   min_image_edge_attr: bool = False, knn_grid: str = "uniform", keep_graphs: bool = False,
                   device: Optional[torch.device] = None, checkpoint: str = "none", density_loss_weight: float = 0.0,
                   density_mesh: Optional[int] = None, density_order: int = 2,
-                  density_smoothing: float = 0.0) -> UnrolledLoss:
+                  density_smoothing: float = 0.0, thermal_loss_weight: float = 0.0) -> UnrolledLoss:
     """The multi-step training loss: S model steps unrolled from one window ``position_seq [W, N, 3]`` /
     ``temperature_seq [W, N(, 1)]``, every step compared with the true frames ``target_positions [S, N, 3]`` /
     ``target_temperatures [S, N(, 1)]``, differentiable through the whole chain.
@@ -1325,14 +1354,27 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     call is the one without these arguments, bit for bit.  ``ValueError`` before any device work: a non-zero weight
     without ``density_mesh``, a negative or non-finite weight, ``density_order`` 1, the refusals of
     ``losses.density_field_loss``.  One box on one GPU: :func:`unrolled_batch_loss` and ``dist.sharded_unrolled_loss``
-    do not take the term (a deposit is one box per call, and meshes are not summed across shards)."""
+    do not take the term (a deposit is one box per call, and meshes are not summed across shards).
+
+    The thermal term (``thermal_loss_weight = mu != 0``; it needs ``density_mesh`` and uses ``density_order`` and
+    ``density_smoothing``): step s also scores the internal energy it makes on the mesh, ``loss_s += mu *
+    losses.thermal_field_loss(new_pos_s, new_temp_s, target_positions[s], target_temperatures[s], ...)``, the
+    internal-energy-weighted fields of the predicted and the true frame; ``UnrolledLoss.thermal_losses`` reports it per
+    step (float64 ``[S]``).  Its gradient reaches the ``temp_rate`` decoder through the temperature the step integrates
+    and the acceleration decoder through the positions the energy is deposited at
+    (``cgnn_mass_assign_weighted_backward``, then ``cgnn_rollout_integrate_backward``); a step whose outgoing link is
+    cut or absent integrates with autograd for its own term and hands on a detached frame, as for the density term.
+    ``checkpoint="steps"`` recomputes the term with its step.  With ``mu = 0``, the default, the call is the one without
+    the argument, bit for bit, with and without the density term.  The same refusals; one box on one GPU."""
     w, n, S, weights = _unroll_arguments(model, position_seq, temperature_seq, target_positions, target_temperatures,
                                          step_weights, backprop_steps, num_neighbors, knn_grid, min_image_edge_attr,
                                          checkpoint)
     density = _density_arguments(density_loss_weight, density_mesh, density_order, density_smoothing)
+    thermal = _density_arguments(thermal_loss_weight, density_mesh, density_order, density_smoothing,
+                                 name="thermal_loss_weight")
     k = int(num_neighbors)
     device = _device_of(position_seq, device)
-    _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device, density)
+    _check_unroll_memory("unrolled_loss", model, n, k, w, S, checkpoint, device, density, thermal)
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
     pos_w, tmp_w, tgt_p, tgt_t = _device_window(position_seq, temperature_seq, target_positions, target_temperatures,
                                                 device)
@@ -1343,30 +1385,35 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
         return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
                                    tgt_p0, tgt_t0, None, want, stats=cfg.stats)
     unroll = _Unroll(model, cfg, w, n, k, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), checkpoint,
-                     sample0, knn_grid, min_image_edge_attr, keep_graphs, density)
+                     sample0, knn_grid, min_image_edge_attr, keep_graphs, density, thermal)
     return _unroll(unroll, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps)
 
 
-def _density_arguments(weight, mesh, order, smoothing, who: str = "unrolled_loss"):
-    """The density term's checks, which need no device: -> ``None`` when the term is off (weight 0), else ``(weight,
-    mesh, order, smoothing)``."""
+def _density_arguments(weight, mesh, order, smoothing, who: str = "unrolled_loss", name: str = "density_loss_weight"):
+    """The checks of a field term (``name``: the density term's weight or the thermal term's), which need no device: ->
+    ``None`` when the term is off (weight 0), else ``(weight, mesh, order, smoothing)``."""
     from . import losses
     if isinstance(weight, bool) or not math.isfinite(weight) or weight < 0:
-        raise ValueError(f"{who}: density_loss_weight must be finite and >= 0, got {weight!r}")
+        raise ValueError(f"{who}: {name} must be finite and >= 0, got {weight!r}")
     if weight == 0:
         return None
     if mesh is None:
-        raise ValueError(f"{who}: density_loss_weight={weight!r} needs density_mesh (the cells per side of the mesh)")
-    mesh = losses.check_density_loss(f"{who} (density term)", mesh, order, smoothing)
+        raise ValueError(f"{who}: {name}={weight!r} needs density_mesh (the cells per side of the mesh)")
+    mesh = losses.check_density_loss(f"{who} ({name.split('_')[0]} term)", mesh, order, smoothing)
     return float(weight), mesh, int(order), float(smoothing)
 
 
-def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device, density=None) -> None:
+def _check_unroll_memory(who: str, model, n: int, k: int, w: int, S: int, checkpoint: str, device, density=None,
+                         thermal=None) -> None:
     """``CgnnError`` when :func:`unrolled_training_bytes` for ``n`` rows exceeds the free device memory."""
     edge = getattr(model, "message_source", "x_j") == "edge"
+    field = {}      # the two field terms share the mesh and the smoothing length
+    if density is not None:
+        field.update(density_mesh=density[1], density_smoothed=density[3] > 0)
+    if thermal is not None:
+        field.update(thermal_mesh=thermal[1], density_smoothed=thermal[3] > 0)
     need = unrolled_training_bytes(n, k, w, model._latent_size, model._mlp_hidden_size, model._mlp_num_hidden_layers,
-                                   len(model.processor), S, edge, checkpoint,
-                                   *(() if density is None else (density[1], density[3] > 0)))
+                                   len(model.processor), S, edge, checkpoint, **field)
     free = free_device_bytes(device)
     if need > free:
         raise CgnnError(f"{who} needs about {need / 2**30:.1f} GiB of device memory for the activations of {S} "
@@ -1410,7 +1457,8 @@ def _unroll(unroll: _Unroll, noisy: bool, pos_w, tmp_w, tgt_p, tgt_t, weights, b
     the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``: step 0's sample is drawn here, with its noise in the same launch."""
     want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
     s0 = unroll.sample0(want)
-    window = _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None, unroll.density is not None)
+    window = _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None,
+                           unroll.density is not None or unroll.thermal is not None)
     return unroll.run(*window, weights, backprop_steps, s0)
 
 

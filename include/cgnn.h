@@ -639,7 +639,46 @@ int cgnn_frame_errors(const float* pred_pos, const float* true_pos, const float*
  * launch, 2^24 threads at most; no atomics (a particle writes its own three values), no host synchronisation; every
  * float64 operation has a fixed place, so two runs and the numpy restatement give the same bits.
  * CGNN_ERR_INVALID_ARG unless 2 <= mesh <= 512, order 2 or 3 (NGP is piecewise constant: it has no gradient),
- * box_size > 0, no null pointer; n > 2^24: CGNN_ERR_UNSUPPORTED; all before any launch. */
+ * box_size > 0, no null pointer; n > 2^24: CGNN_ERR_UNSUPPORTED; all before any launch.
+ *
+ * cgnn_mass_assign_weighted deposits per-particle weights, up to four channels at once, for fields other than the
+ * number density (thermal energy, momentum): q (device, int32 [frames, n, channels], 1 <= channels <= 4) are weights
+ * quantised to 2^20 per value scale (a = q / 2^20 in [-1, 1]); out (device, int64 [frames, channels, mesh, mesh, mesh],
+ * overwritten).  Every particle uses exactly the cells and the integer axis weights of cgnn_mass_assign (the same s, u,
+ * guard and rounding), computed once for its channels.  A cell whose product of axis weights is v (0 <= v <= 2^39)
+ * receives in channel c, in int64 arithmetic,
+ *     qc = clamp(q[i, c], -2^20, 2^20);   (v * qc + 2^19) >> 20        (arithmetic shift; |v * qc| <= 2^59)
+ * one 64-bit integer atomic per non-zero contribution; negative contributions are added as two's complement, so the
+ * mesh read as int64 holds the signed sums.  q == 2^20 everywhere gives the bits of cgnn_mass_assign, q == 0 zeros;
+ * integer sums make the mesh the same bits on every run and equal to the numpy restatement.  The rounding moves a
+ * cell's contribution by at most 1/2, and the order^3 <= 27 cells of a particle sum to q 2^19 within 14, so a particle
+ * adds at most 2^39 + 14 in magnitude to a channel: n <= 2^23 particles in one cell stay inside int64.  Whole frames
+ * per launch, 2^24 threads at most, no host synchronisation.
+ * CGNN_ERR_INVALID_ARG for every case cgnn_mass_assign refuses so, a null q, or channels outside [1, 4]; n > 2^23:
+ * CGNN_ERR_UNSUPPORTED; all before any launch.
+ *
+ * cgnn_mass_assign_weighted_backward is its transpose.  The integer mesh stands for the real field A_c[cell] =
+ * sum_i W_i(cell) a_ic with W = v / Q^3 and a = q / 2^20; d_field (device, double [frames, channels, mesh, mesh, mesh])
+ * is the gradient of a scalar with respect to A.  Straight through both quantisations: W is differentiated as the
+ * unquantised assignment function at the forward's u in the forward's cells (cgnn_mass_assign_backward), and a as the
+ * real value q stands for (its rounding and its clamp have derivative one).  One thread per particle, no atomics; per
+ * channel c the thread gathers D_c[a][b][c'] = d_field[c][c_x[a], c_y[b], c_z[c']] once, and with wv, diff as above:
+ *   d_val (device, float [frames, n, channels], may be NULL):
+ *     acc = 0.0;  acc += ((wv_x[a] * wv_y[b]) * wv_z[c']) * D_c[a][b][c']   for a (outer), b, c' (inner)
+ *     d_val[i, c] = fl32(acc * scale_val)
+ *   d_pos (device, float [frames, n, 3], may be NULL):
+ *     g_c[ax] = acc_ax of cgnn_mass_assign_backward on D_c (the same terms in the same order)
+ *     chan[ax] = 0.0;  chan[ax] += a_ic * g_c[ax]   for c ascending, a_ic = (double)qc * 2^-20
+ *     d_pos[i, ax] = fl32((chan[ax] * (double)s) * scale_pos)
+ * float64, one rounding per operation, no FMA.  With channels == 1 and q == 2^20 d_pos is cgnn_mass_assign_backward's
+ * for the same d_field and scale; a constant d_field gives d_pos == 0 exactly.  Two runs and the numpy restatement
+ * give the same bits.  CGNN_ERR_INVALID_ARG as for the forward, for order 1 (NGP has no gradient), and when both d_pos
+ * and d_val are NULL; n > 2^23: CGNN_ERR_UNSUPPORTED; all before any launch. */
+int cgnn_mass_assign_weighted(const float* pos, const int32_t* q, int64_t frames, int64_t n, int32_t channels,
+                              float box_size, int32_t mesh, int32_t order, int64_t* out, void* stream);
+int cgnn_mass_assign_weighted_backward(const float* pos, const int32_t* q, const double* d_field, int64_t frames,
+                                       int64_t n, int32_t channels, float box_size, int32_t mesh, int32_t order,
+                                       double scale_pos, double scale_val, float* d_pos, float* d_val, void* stream);
 int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
                      int64_t* out, void* stream);
 int cgnn_mass_assign_backward(const float* pos, const double* d_mesh, int64_t frames, int64_t n, float box_size,

@@ -1,0 +1,655 @@
+"""GPU: ``ops.mass_assign_weighted`` / ``ops.mass_assign_weighted_backward`` (``cgnn_mass_assign_weighted``,
+``cgnn_mass_assign_weighted_backward``) against the numpy restatement of their contracts (tests/gas_field_checks.py) --
+integers forward, float64 with every operation in a fixed place backward, so every case is ``torch.equal`` --
+``ops.weighted_field`` as an autograd function, ``losses.thermal_field_loss`` against its numpy float64 definition, and the
+thermal and momentum spectra of ``statistics`` on fields with known answers.
+
+Tolerances.  A loss value is held to 1e-9 relative and a gradient element to 2^-23 of itself plus 1e-9 of the largest
+element, as argued at the top of tests/test_gpu_density_loss.py (the mesh gradients agree to FFT roundoff, the transpose
+is linear in them and rounds once to float32; where the value scale lives on the device ``d pos`` is rounded to float32
+a second time after a float64 product, 2^-24 (1 + 2^-24) + 2^-24 of itself, inside the same bound with the second term).
+Spectra are float64 sums of FFT output: 1e-12 relative where two routes form the same field, 1e-9 of the signal for
+bins that hold only roundoff and the quantisation of the values (2^-21 of the scale per particle, uncorrelated between
+particles: about 1e-14 of the signal's power per mode at these shapes).
+
+The bound of ``test_weighted_field_is_near_the_unquantised_deposit``.  In a cell, a particle's integer contribution
+times value_scale / 2^39 differs from W value (W the unquantised float64 CIC / TSC weight, |value| <= value_scale) by at
+most value_scale times
+    (1 + e)^3 - 1      the three axis weights, each at most 1 and off by at most e = 2^-13 + (M + 4) 2^-24: one rint is
+                       2^-14 of Q, the TSC centre is Q minus two rints, u = fl32(p s) is off by at most M 2^-24 cells
+                       and the float32 operations behind a weight by at most 4 2^-24 (the weights' slopes are at most 1)
+  + 2^-21              the value: q / 2^20 is within 2^-21 of value / value_scale
+  + 2^-40              the rounding of (v q + 2^19) >> 20, half a unit of 2^-39.
+A cell sums that over the particles that touch it, counted from above by ``gfc.touch_count`` (the integer and the float64
+stencil can differ where u falls on a cell boundary), and the field multiplies by M^3 / N; float64 roundoff of the
+reference's sum is charged as 1e-12 of the same count.
+
+Measured on an MI355X.  The field against the unquantised deposit: at most 0.105 of the bound (M = 16, CIC; 0.045 for
+TSC, 0.002 at M = 5), the 13-bit axis weights being nearly all of it.  Thermal loss gradients: ``d / d temp`` equal to the
+restatement in every case, ``d / d pos`` at most 0.99 of its bound (the second rounding to float32 behind the kernel).
+Plane waves: the largest other bin 1.5e-12 of the peak or less; ``power_div`` of a transverse wave 1e-14 of
+``power_total``, ``power_curl`` of a longitudinal one exactly 0."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import density_loss_checks as dlc
+import gas_field_checks as gfc
+import power_spectrum_checks as psc
+from cosmology_gnn_simulation_amd import _lib, losses, ops, statistics
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+BOX = 25.0
+TOL = 1e-9
+ONE = 1 << 20
+SCALE = 2.0
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _normal(shape, seed):
+    return np.random.default_rng(seed).normal(size=shape)
+
+
+def _values(n, channels, seed, roll=0):
+    """float32 [n, channels]: normal draws (mixed in sign) with, among the first entries, exact +-SCALE, exact 0 and a
+    value beyond the scale; ``roll`` chooses which of them a single entry gets"""
+    v = np.random.default_rng(seed).normal(size=(n, channels)).astype(np.float32)
+    flat = v.reshape(-1)
+    special = np.roll(np.array([SCALE, -SCALE, 0.0, 2.5 * SCALE, -7.0 * SCALE], dtype=np.float32), roll)
+    flat[:min(flat.size, special.size)] = special[:min(flat.size, special.size)]
+    return v
+
+
+def _same_deposit(x, q, box, mesh, order):
+    """the entry on quantised weights q (int64 numpy) against the restatement, and a repeat"""
+    got = ops.mass_assign_weighted(_dev(x), _dev(q.astype(np.int32)), box, mesh, order)
+    channels = 1 if q.ndim == x.ndim - 1 else q.shape[-1]
+    assert got.dtype == torch.int64 and got.shape == x.shape[:-2] + (channels,) + (mesh,) * 3
+    assert torch.equal(got.cpu(), torch.from_numpy(gfc.mass_assign_weighted(x, q, box, mesh, order)))
+    assert torch.equal(ops.mass_assign_weighted(_dev(x), _dev(q.astype(np.int32)), box, mesh, order), got)
+    return got
+
+
+def _same_transpose(x, q, d_field, box, mesh, order, scale_pos=1.0, scale_val=1.0):
+    """d_val only, d_pos only and both against the restatement -> (d_pos, d_val) of the call for both"""
+    want_pos, want_val = gfc.mass_assign_weighted_backward(x, q, d_field, box, mesh, order, scale_pos, scale_val)
+    args = (_dev(x), _dev(q.astype(np.int32)), _dev(d_field), box, mesh, order, scale_pos, scale_val)
+    only_val = ops.mass_assign_weighted_backward(*args, want_pos=False)
+    only_pos = ops.mass_assign_weighted_backward(*args, want_val=False)
+    both = ops.mass_assign_weighted_backward(*args)
+    assert only_val[0] is None and only_pos[1] is None
+    for got in (only_val[1], both[1]):
+        assert got.dtype == torch.float32 and torch.equal(got.cpu(), torch.from_numpy(want_val))
+    for got in (only_pos[0], both[0]):
+        assert got.dtype == torch.float32 and got.shape == x.shape and torch.equal(got.cpu(), torch.from_numpy(want_pos))
+    return both
+
+
+# ---- the forward kernel against the restatement -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("mesh", [2, 4, 5, 16])
+@pytest.mark.parametrize("n", [1, 7, 1000])
+def test_mass_assign_weighted_equals_the_restatement(n, mesh, order, channels):
+    x = psc.uniform(n, seed=n + mesh, box=BOX)
+    v = _values(n, channels, seed=10 * mesh + channels, roll=mesh + order + channels)
+    q = gfc.quantize(v, SCALE)
+    assert np.abs(q).max() <= ONE
+    got = _same_deposit(x, q, BOX, mesh, order)
+    # the float route quantises on the device to the same integers, and clamps what lies beyond the scale
+    assert torch.equal(ops.quantize_weights(_dev(v), SCALE).cpu(), torch.from_numpy(q.astype(np.int32)))
+    assert torch.equal(ops.mass_assign_weighted(_dev(x), _dev(v), BOX, mesh, order, value_scale=SCALE), got)
+    if n == 1000 and mesh == 16:            # a few particles per cell: sums of both signs
+        assert bool((got < 0).any()) and bool((got > 0).any())
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_special_weights_and_the_kernels_own_clamp(order):
+    x = psc.with_special_positions(psc.uniform(1000, 3, BOX), BOX)
+    plain = ops.mass_assign(_dev(x), BOX, 9, order)
+    for channels in (1, 2, 4):
+        one = torch.full((1000, channels), ONE, dtype=torch.int32, device=DEV)
+        got = ops.mass_assign_weighted(_dev(x), one, BOX, 9, order)
+        for ch in range(channels):
+            assert torch.equal(got[ch], plain)
+        assert not bool(ops.mass_assign_weighted(_dev(x), torch.zeros_like(one), BOX, 9, order).any())
+    ones = ops.mass_assign_weighted(_dev(x), torch.ones(1000, device=DEV), BOX, 9, order)            # value_scale=None
+    assert torch.equal(ones[0], plain)
+    assert not bool(ops.mass_assign_weighted(_dev(x), torch.zeros(1000, device=DEV), BOX, 9, order).any())
+    # weights beyond +-2^20 never come out of quantize_weights; the kernel clamps them all the same
+    q = np.random.default_rng(4).integers(-3 * ONE, 3 * ONE, (1000, 3))
+    q[:2] = [[2 ** 31 - 1, -2 ** 31, ONE + 1], [-ONE - 1, 0, 5]]
+    assert (np.abs(q) > ONE).sum() > 100
+    _same_deposit(x, q, BOX, 9, order)
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_4096_particles_in_one_cell_with_mixed_signs(order):
+    """Many atomics on few addresses, positive and negative contributions cancelling in two's complement."""
+    rng = np.random.default_rng(11)
+    x = ((np.float32(7.0) + rng.random((4096, 3), dtype=np.float32)) * np.float32(BOX / 16)).astype(np.float32)
+    q = gfc.quantize(rng.normal(size=(4096, 4)), SCALE)
+    q[:, 1] = np.where(np.arange(4096) % 2 == 0, ONE, -ONE)               # cancels to almost nothing
+    got = _same_deposit(x, q, BOX, 16, order)
+    assert bool((got < 0).any()) and bool((got > 0).any())
+    assert int(got[1].abs().max()) < 2 ** 39 * 200                       # far below the 4096 2^39 of equal signs
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("mesh,box", [(16, 16.0), (5, 5.0), (16, BOX), (5, BOX)])
+def test_mass_assign_weighted_on_box_faces_and_cell_boundaries(mesh, box, order):
+    x = _face_points(mesh, box)
+    q = gfc.quantize(_normal((x.shape[0], 3), 200 + mesh), SCALE)
+    _same_deposit(x, q, box, mesh, order)
+
+
+def _face_points(mesh, box):
+    """Coordinates of exactly 0 and L, and u on every integer and half-integer (exactly so when s = M / L = 1): the
+    construction of test_mass_assign_backward_on_box_faces_and_cell_boundaries."""
+    cell = np.float32(box) / np.float32(mesh)
+    ticks = (np.arange(2 * mesh + 1, dtype=np.float32) * np.float32(0.5) * cell).astype(np.float32)
+    ticks[-1] = np.float32(box)
+    x = np.stack(np.meshgrid(ticks, ticks[::3], ticks[::5], indexing="ij"), axis=-1).reshape(-1, 3)
+    x = np.concatenate([x, x[:, [2, 0, 1]], x[:, [1, 2, 0]]]).astype(np.float32)
+    assert (x == 0).any() and (x == np.float32(box)).any() and x.max() <= np.float32(box)
+    return x
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_a_nan_coordinate_reads_as_zero_on_its_axis_and_disturbs_nobody(order):
+    x = psc.uniform(300, 41, BOX)
+    q = gfc.quantize(_normal((300, 2), 42), SCALE)
+    clean = ops.mass_assign_weighted(_dev(x), _dev(q.astype(np.int32)), BOX, 8, order)
+    y = x.copy()
+    y[100, 1] = np.nan
+    y[200, 0] = np.inf
+    got = _same_deposit(y, q, BOX, 8, order)
+    for row in (100, 200):                             # the two particles alone, moved to u = 0 on the bad axis
+        z = np.where(np.isfinite(y[row]), y[row], np.float32(0.0))[None]
+        moved = gfc.mass_assign_weighted(z, q[row][None], BOX, 8, order) - gfc.mass_assign_weighted(x[row][None], q[row][None],
+                                                                                                    BOX, 8, order)
+        clean = clean + _dev(moved)
+    assert torch.equal(got, clean)
+
+
+def test_frames_and_channels_are_one_call_per_frame():
+    frames = np.stack([psc.uniform(1000, seed=20 + t, box=BOX) for t in range(3)])
+    v = np.stack([_values(1000, 3, 23 + t) for t in range(3)])
+    got = ops.mass_assign_weighted(_dev(frames), _dev(v), BOX, 9, 3, value_scale=SCALE)
+    assert got.shape == (3, 3, 9, 9, 9)
+    single = [ops.mass_assign_weighted(_dev(frames[t]), _dev(v[t]), BOX, 9, 3, value_scale=SCALE) for t in range(3)]
+    assert torch.equal(got, torch.stack(single))
+    assert torch.equal(got.cpu(), torch.from_numpy(gfc.mass_assign_weighted(frames, gfc.quantize(v, SCALE), BOX, 9, 3)))
+    one = ops.mass_assign_weighted(_dev(frames), _dev(v[..., 1]), BOX, 9, 3, value_scale=SCALE)       # [T, N]: C = 1
+    assert one.shape == (3, 1, 9, 9, 9) and torch.equal(one[:, 0], got[:, 1])
+    # value_scale=None: the largest |value| of the call, taken on the device
+    auto = ops.mass_assign_weighted(_dev(frames), _dev(v), BOX, 9, 3)
+    top = np.float64(np.abs(v).max())
+    assert torch.equal(auto.cpu(), torch.from_numpy(gfc.mass_assign_weighted(frames, gfc.quantize(v, top), BOX, 9, 3)))
+
+
+def test_more_frames_than_one_launch_takes():
+    """2100 frames of 8192 particles are 2^24.04 threads: the entries split them into launches of whole frames."""
+    base = _dev(np.stack([psc.uniform(8192, seed=30 + t, box=BOX) for t in range(3)]))
+    q = _dev(gfc.quantize(_normal((3, 8192, 2), 31), SCALE).astype(np.int32))
+    d_field = _dev(_normal((3, 2, 2, 2, 2), 32))
+    want = ops.mass_assign_weighted(base, q, BOX, 2, 2)
+    got = ops.mass_assign_weighted(base.repeat(700, 1, 1), q.repeat(700, 1, 1), BOX, 2, 2)
+    assert got.shape == (2100, 2, 2, 2, 2) and torch.equal(got, want.repeat(700, 1, 1, 1, 1))
+    want_pos, want_val = ops.mass_assign_weighted_backward(base, q, d_field, BOX, 2, 2)
+    got_pos, got_val = ops.mass_assign_weighted_backward(base.repeat(700, 1, 1), q.repeat(700, 1, 1),
+                                                         d_field.repeat(700, 1, 1, 1, 1), BOX, 2, 2)
+    assert got_pos.shape == (2100, 8192, 3) and torch.equal(got_pos, want_pos.repeat(700, 1, 1))
+    assert got_val.shape == (2100, 8192, 2) and torch.equal(got_val, want_val.repeat(700, 1, 1))
+
+
+# ---- the transpose against the restatement ----------------------------------------------------------------------------
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("mesh", [2, 4, 5, 16])
+@pytest.mark.parametrize("n", [1, 7, 1000])
+def test_mass_assign_weighted_backward_equals_the_restatement(n, mesh, order, channels):
+    x = psc.uniform(n, seed=n + mesh, box=BOX)
+    q = gfc.quantize(_values(n, channels, seed=10 * mesh + channels, roll=mesh + order + channels), SCALE)
+    d_field = _normal((channels, mesh, mesh, mesh), 100 + mesh + channels)
+    d_pos, d_val = _same_transpose(x, q, d_field, BOX, mesh, order, scale_pos=SCALE * mesh ** 3 / n, scale_val=mesh ** 3 / n)
+    assert float(d_val.abs().max()) > 0.0
+    if n > 1:
+        assert float(d_pos.abs().max()) > 0.0
+    again = ops.mass_assign_weighted_backward(_dev(x), _dev(q.astype(np.int32)), _dev(d_field), BOX, mesh, order,
+                                              SCALE * mesh ** 3 / n, mesh ** 3 / n)
+    assert torch.equal(again[0], d_pos) and torch.equal(again[1], d_val)
+
+
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("mesh,box", [(16, 16.0), (5, 5.0), (16, BOX), (5, BOX)])
+def test_transpose_on_box_faces_one_scale_and_constant_fields(mesh, box, order):
+    x = _face_points(mesh, box)
+    n = x.shape[0]
+    d_field = _normal((3, mesh, mesh, mesh), 300 + mesh)
+    _same_transpose(x, gfc.quantize(_normal((n, 3), 301 + mesh), SCALE), d_field, box, mesh, order)
+    # one channel of weight one scale: the plain transpose, bit for bit
+    one = torch.full((n,), ONE, dtype=torch.int32, device=DEV)
+    got, _ = ops.mass_assign_weighted_backward(_dev(x), one, _dev(d_field[:1]), box, mesh, order, scale_pos=3.0)
+    assert torch.equal(got, ops.mass_assign_backward(_dev(x), _dev(d_field[0]), box, mesh, order, scale=3.0))
+    # a constant field: no force at all, and every particle reads the constant back (its value weights sum to one)
+    q = _dev(gfc.quantize(_normal((n, 4), 302), SCALE).astype(np.int32))
+    const = torch.full((4,) + (mesh,) * 3, 0.7, dtype=torch.float64, device=DEV)
+    d_pos, d_val = ops.mass_assign_weighted_backward(_dev(x), q, const, box, mesh, order, scale_pos=5.0, scale_val=3.0)
+    assert bool((d_pos == 0).all())
+    assert float((d_val.double() - 2.1).abs().max()) <= 2.1 * 2.0 ** -23
+
+
+@pytest.mark.parametrize("order", [2, 3])
+def test_transpose_of_4096_particles_in_one_cell_and_of_bad_coordinates(order):
+    rng = np.random.default_rng(11)
+    x = ((np.float32(7.0) + rng.random((4096, 3), dtype=np.float32)) * np.float32(BOX / 16)).astype(np.float32)
+    x[100, 1] = np.nan
+    x[200, 0] = np.inf
+    q = gfc.quantize(rng.normal(size=(4096, 3)), SCALE)
+    d_pos, d_val = _same_transpose(x, q, _normal((3, 16, 16, 16), 12), BOX, 16, order, scale_pos=3.0)
+    assert float(d_pos[100, 1]) == 0.0 and float(d_pos[200, 0]) == 0.0
+    assert bool(torch.isfinite(d_pos).all()) and bool(torch.isfinite(d_val).all())
+
+
+def test_transpose_of_frames_is_one_call_per_frame():
+    frames = np.stack([psc.uniform(1000, seed=20 + t, box=BOX) for t in range(3)])
+    q = gfc.quantize(np.stack([_values(1000, 3, 23 + t) for t in range(3)]), SCALE)
+    d_field = _normal((3, 3, 9, 9, 9), 24)
+    d_pos, d_val = _same_transpose(frames, q, d_field, BOX, 9, 3, 0.5, 2.0)
+    assert d_pos.shape == (3, 1000, 3) and d_val.shape == (3, 1000, 3)
+    for t in range(3):
+        one = ops.mass_assign_weighted_backward(_dev(frames[t]), _dev(q[t].astype(np.int32)), _dev(d_field[t]), BOX, 9, 3, 0.5, 2.0)
+        assert torch.equal(one[0], d_pos[t]) and torch.equal(one[1], d_val[t])
+
+
+def test_the_c_entries_refuse_by_themselves_before_any_launch():
+    """With real buffers of the sizes named: were a refusal ever to come after a launch, nothing would fault."""
+    lib = _lib.load()
+    big = (1 << 23) + 1
+    pos = torch.zeros((big, 3), device=DEV)
+    q = torch.zeros((big, 5), dtype=torch.int32, device=DEV)
+    out = torch.full((5, 16, 16, 16), -1, dtype=torch.int64, device=DEV)
+    d_field = torch.ones((5, 16, 16, 16), dtype=torch.float64, device=DEV)
+    d_pos = torch.full((big, 3), -1.0, device=DEV)
+    d_val = torch.full((big, 5), -1.0, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    fwd, bwd = lib.cgnn_mass_assign_weighted, lib.cgnn_mass_assign_weighted_backward
+    P, Q_, O, D, GP, GV = (t.data_ptr() for t in (pos, q, out, d_field, d_pos, d_val))
+    cases = [(big, 1, 1.0, 16, 2), (10, 0, 1.0, 16, 2), (10, 5, 1.0, 16, 2), (10, -1, 1.0, 16, 2), (10, 1, 1.0, 1, 2),
+             (10, 1, 1.0, 513, 2), (10, 1, 1.0, 16, 0), (10, 1, 1.0, 16, 4), (10, 1, 0.0, 16, 2), (10, 1, -1.0, 16, 2),
+             (10, 1, float("nan"), 16, 2), (10, 1, float("inf"), 16, 2), (0, 1, 1.0, 16, 2)]
+    for n, channels, box, mesh, order in cases:
+        assert fwd(P, Q_, 1, n, channels, box, mesh, order, O, st) != 0, (n, channels, box, mesh, order)
+        assert bwd(P, Q_, D, 1, n, channels, box, mesh, order, 1.0, 1.0, GP, GV, st) != 0, (n, channels, box, mesh, order)
+    assert fwd(P, Q_, 1, big, 1, 1.0, 16, 2, O, st) != 0 and b"2^23" in lib.cgnn_last_error()         # with the reason
+    assert bwd(P, Q_, D, 1, big, 1, 1.0, 16, 2, 1.0, 1.0, GP, GV, st) != 0 and b"2^23" in lib.cgnn_last_error()
+    assert fwd(P, Q_, 0, 10, 1, 1.0, 16, 2, O, st) != 0                                 # no frames
+    assert bwd(P, Q_, D, 1, 10, 1, 1.0, 16, 1, 1.0, 1.0, GP, GV, st) != 0               # NGP has no gradient
+    assert fwd(None, Q_, 1, 10, 1, 1.0, 16, 2, O, st) != 0
+    assert fwd(P, None, 1, 10, 1, 1.0, 16, 2, O, st) != 0
+    assert fwd(P, Q_, 1, 10, 1, 1.0, 16, 2, None, st) != 0
+    assert bwd(None, Q_, D, 1, 10, 1, 1.0, 16, 2, 1.0, 1.0, GP, GV, st) != 0
+    assert bwd(P, None, D, 1, 10, 1, 1.0, 16, 2, 1.0, 1.0, GP, GV, st) != 0
+    assert bwd(P, Q_, None, 1, 10, 1, 1.0, 16, 2, 1.0, 1.0, GP, GV, st) != 0
+    assert bwd(P, Q_, D, 1, 10, 1, 1.0, 16, 2, 1.0, 1.0, None, None, st) != 0           # nothing to write
+    assert bool((out == -1).all()) and bool((d_pos == -1).all()) and bool((d_val == -1).all())
+    # a valid call then writes exactly its rows
+    assert fwd(P, Q_, 1, 10, 2, 1.0, 16, 2, O, st) == 0
+    assert bool((out[:2] == 0).all()) and bool((out[2:] == -1).all())                   # weights of zero: two zeroed channels
+    assert bwd(P, Q_, D, 1, 10, 2, 1.0, 16, 2, 1.0, 1.0, GP, GV, st) == 0
+    assert bool((d_pos[:10] == 0).all()) and bool((d_pos[10:] == -1).all())             # a constant field
+    flat = d_val.reshape(-1)
+    assert bool((flat[:20] == 1).all()) and bool((flat[20:] == -1).all())               # ten particles, two channels
+    assert bwd(P, Q_, D, 1, 10, 2, 1.0, 16, 2, 1.0, 1.0, None, GV, st) == 0             # either output alone is legal
+    assert bwd(P, Q_, D, 1, 10, 2, 1.0, 16, 2, 1.0, 1.0, GP, None, st) == 0
+    torch.cuda.synchronize()
+
+
+# ---- ops.weighted_field -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_weighted_field_forward_is_the_restated_expression(order):
+    for x, seed in ((psc.uniform(1000, 50, BOX), 51), (np.stack([psc.uniform(700, 52 + t, BOX) for t in range(2)]), 54)):
+        n = x.shape[-2]
+        v = _values(n, 3, seed) if x.ndim == 2 else np.stack([_values(n, 3, seed + t) for t in range(2)])
+        top = np.float64(np.abs(v).max())
+        for scale, given in ((SCALE, SCALE), (top, None), (1.7, torch.tensor(1.7, dtype=torch.float64, device=DEV))):
+            got = ops.weighted_field(_dev(x), _dev(v), BOX, 9, order, given)
+            assert got.dtype == torch.float64 and got.shape == x.shape[:-2] + (3, 9, 9, 9) and not got.requires_grad
+            want = gfc.weighted_field(gfc.mass_assign_weighted(x, gfc.quantize(v, scale), BOX, 9, order), n, scale)
+            assert torch.equal(got.cpu(), torch.from_numpy(want))
+    ones = ops.weighted_field(_dev(x), torch.ones(x.shape[:-1], device=DEV), BOX, 9, order)            # 1 + delta
+    assert float((ones[:, 0] - 1.0 - ops.density_contrast(_dev(x), BOX, 9, order)).abs().max()) <= 1e-12
+    with pytest.raises(ValueError):
+        ops.weighted_field(_dev(psc.uniform(10, 52, BOX)).requires_grad_(True), torch.ones(10, device=DEV), BOX, 9, 1)
+    with torch.no_grad():                                                      # no gradient requested: just the field
+        ops.weighted_field(_dev(psc.uniform(10, 52, BOX)).requires_grad_(True), torch.ones(10, device=DEV), BOX, 9, 1)
+
+
+@pytest.mark.parametrize("order", [2, 3])
+def test_weighted_field_backward_is_the_plain_call_with_the_fields_scales(order):
+    mesh = 8
+    for x, seed in ((psc.uniform(1000, 60, BOX), 61), (np.stack([psc.uniform(700, 62 + t, BOX) for t in range(2)]), 64)):
+        n = x.shape[-2]
+        v = _values(n, 2, seed) if x.ndim == 2 else np.stack([_values(n, 2, seed + t) for t in range(2)])
+        w = _dev(_normal(x.shape[:-2] + (2,) + (mesh,) * 3, seed + 1))
+        q = ops.quantize_weights(_dev(v), SCALE)
+        for given in (SCALE, torch.tensor(SCALE, dtype=torch.float64, device=DEV)):
+            pos, val = _dev(x).requires_grad_(True), _dev(v).requires_grad_(True)
+            field = ops.weighted_field(pos, val, BOX, mesh, order, given)
+            assert field.requires_grad
+            (w * field).sum().backward()
+            assert pos.grad.dtype == torch.float32 and val.grad.dtype == torch.float32 and val.grad.shape == v.shape
+            if torch.is_tensor(given):          # the scale lives on the device: applied behind the kernel, in float64
+                d_pos, d_val = ops.mass_assign_weighted_backward(_dev(x), q, w, BOX, mesh, order, mesh ** 3 / n, mesh ** 3 / n)
+                d_pos = (d_pos.double() * given).float()
+            else:
+                d_pos, d_val = ops.mass_assign_weighted_backward(_dev(x), q, w, BOX, mesh, order, SCALE * (mesh ** 3 / n),
+                                                                 mesh ** 3 / n)
+                want = gfc.mass_assign_weighted_backward(x, gfc.quantize(v, SCALE), w.cpu().numpy(), BOX, mesh, order,
+                                                         SCALE * (mesh ** 3 / n), mesh ** 3 / n)
+                assert torch.equal(pos.grad.cpu(), torch.from_numpy(want[0]))
+                assert torch.equal(val.grad.cpu(), torch.from_numpy(want[1]))
+            assert torch.equal(pos.grad, d_pos) and torch.equal(val.grad, d_val)
+        # one of the two alone
+        pos = _dev(x).requires_grad_(True)
+        (w * ops.weighted_field(pos, _dev(v), BOX, mesh, order, SCALE)).sum().backward()
+        assert torch.equal(pos.grad, d_pos)
+        val = _dev(v).requires_grad_(True)
+        (w * ops.weighted_field(_dev(x), val, BOX, mesh, order, SCALE)).sum().backward()
+        assert torch.equal(val.grad, d_val)
+
+
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("mesh", [5, 16])
+def test_weighted_field_is_near_the_unquantised_deposit(mesh, order):
+    """The bound derived at the top of this file."""
+    n = 1000
+    x = psc.with_special_positions(psc.uniform(n, 70 + mesh, BOX), BOX)
+    v = np.clip(_normal((n, 2), 71 + mesh), -SCALE, SCALE).astype(np.float32)
+    got = ops.weighted_field(_dev(x), _dev(v), BOX, mesh, order, SCALE).cpu().numpy()
+    want = gfc.field_unquantised(x.astype(np.float64), v.astype(np.float64), BOX, mesh, order) * (mesh ** 3 / n)
+    e = 2.0 ** -13 + (mesh + 4) * 2.0 ** -24
+    per_particle = SCALE * ((1 + e) ** 3 - 1 + 2.0 ** -21 + 2.0 ** -40 + 1e-12)
+    bound = (mesh ** 3 / n) * gfc.touch_count(x, BOX, mesh, order) * per_particle
+    err = np.abs(got - want)
+    print(f"M={mesh} order={order}: largest error {err.max():.3e}, largest error / bound "
+          f"{np.max(err / np.maximum(bound[None], 1e-300)):.3f}, "
+          f"field rms {want.std():.3e}")
+    assert bound.max() > 0 and (err <= bound[None]).all()            # a cell nobody touches is 0 in both
+    assert err.max() > 0                                                    # the two are not the same computation
+
+
+# ---- losses.thermal_field_loss ----------------------------------------------------------------------------------------
+
+N = 3000
+SMOOTHINGS = (0.0, 0.7 * BOX / 16, 3.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(frames=False):
+    """(pos_pred, temp_pred, pos_true, temp_true): a set with positive temperatures, and a displaced copy whose
+    temperatures are off by ten per cent or so; float32 [N, 3] / [N], or [2, N, 3] / [2, N] with ``frames``"""
+    true = np.stack([psc.uniform(N, seed=70 + t, box=BOX) for t in range(2)])
+    rng = np.random.default_rng(72)
+    pred = np.mod(true + rng.normal(0.0, 0.4, true.shape).astype(np.float32), np.float32(BOX)).astype(np.float32)
+    t_true = np.exp(rng.normal(0.0, 0.5, (2, N))).astype(np.float32) * np.float32(300.0)
+    t_pred = (t_true * (1.0 + 0.1 * rng.normal(size=(2, N)))).astype(np.float32)
+    assert np.abs(t_pred).max() < 2 * t_true.max()
+    out = (pred, t_pred, true, t_true)
+    return out if frames else tuple(a[0] for a in out)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(mesh, order, smoothing, frames=False):
+    args = _pair(frames)
+    value, _ = gfc.thermal_field_loss(*args, BOX, mesh, order, smoothing)
+    return value, gfc.thermal_field_loss_gradients(*args, BOX, mesh, order, smoothing)
+
+
+def _loss_and_gradients(pos_pred, temp_pred, pos_true, temp_true, mesh, order, smoothing):
+    pos, temp = _dev(pos_pred).requires_grad_(True), _dev(temp_pred).requires_grad_(True)
+    loss = losses.thermal_field_loss(pos, temp, _dev(pos_true), _dev(temp_true), BOX, mesh, order, smoothing)
+    assert loss.dtype == torch.float64 and loss.dim() == 0 and loss.requires_grad
+    loss.backward()
+    return loss.detach(), pos.grad, temp.grad
+
+
+def _within(name, got, want):
+    g, w = got.cpu().double().numpy(), want.astype(np.float64).reshape(got.shape)
+    bound = 2.0 ** -23 * np.abs(w) + TOL * np.abs(w).max()
+    print(f"    {name}: largest |got - want| / bound {np.max(np.abs(g - w) / bound):.3f}, largest element {np.abs(w).max():.3e}")
+    assert np.abs(w).max() > 0 and (np.abs(g - w) <= bound).all()
+
+
+@pytest.mark.parametrize("frames", [False, True], ids=["one", "frames"])
+@pytest.mark.parametrize("smoothing", SMOOTHINGS)
+@pytest.mark.parametrize("mesh,order", [(16, 2), (16, 3), (9, 2), (9, 3)])
+def test_thermal_field_loss_and_its_gradients_equal_numpy_float64(mesh, order, smoothing, frames):
+    args = _pair(frames)
+    want, (want_pos, want_temp) = _restated(mesh, order, smoothing, frames)
+    loss, g_pos, g_temp = _loss_and_gradients(*args, mesh, order, smoothing)
+    err = abs(float(loss) - want) / want
+    print(f"M={mesh} order={order} R={smoothing:.3g}: loss {float(loss):.6e}, relative error {err:.2e}")
+    assert want > 0 and err <= TOL
+    assert g_pos.dtype == torch.float32 and g_pos.shape == args[0].shape
+    assert g_temp.dtype == torch.float32 and g_temp.shape == args[1].shape
+    _within("d / d pos", g_pos, want_pos)
+    _within("d / d temp", g_temp, want_temp)
+
+
+@pytest.mark.parametrize("smoothing", SMOOTHINGS[:2])
+def test_thermal_loss_limits(smoothing):
+    pos_pred, temp_pred, pos_true, temp_true = _pair()
+    same, g_pos, g_temp = _loss_and_gradients(pos_true, temp_true, pos_true, temp_true, 16, 3, smoothing)
+    assert float(same) == 0.0 and bool((g_pos == 0).all()) and bool((g_temp == 0).all())
+    # equal positions: the gradient with respect to them comes from the temperature difference alone
+    loss, g_pos, g_temp = _loss_and_gradients(pos_true, temp_pred, pos_true, temp_true, 16, 3, smoothing)
+    assert float(loss) > 0 and float(g_pos.abs().max()) > 0 and float(g_temp.abs().max()) > 0
+    # [N, 1] temperatures are the [N] ones
+    col = losses.thermal_field_loss(_dev(pos_pred), _dev(temp_pred)[:, None], _dev(pos_true), _dev(temp_true)[:, None], BOX,
+                                    16, 3, smoothing)
+    assert torch.equal(col, losses.thermal_field_loss(_dev(pos_pred), _dev(temp_pred), _dev(pos_true), _dev(temp_true), BOX,
+                                                      16, 3, smoothing))
+    # the normalisation: temperatures in other units, the same loss
+    scaled = losses.thermal_field_loss(_dev(pos_pred), _dev(temp_pred) * 8.0, _dev(pos_true), _dev(temp_true) * 8.0, BOX, 16,
+                                       3, smoothing)
+    assert abs(float(scaled) - float(col)) <= TOL * float(col)
+
+
+# ---- spectra on fields with known answers -----------------------------------------------------------------------------
+
+LM, LBOX = 16, 16.0
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice():
+    """4096 particles at the centres of the 16^3 cells of a box of side 16 (s = 1: u is exactly i + 1/2), float32 [N, 3]"""
+    c = (np.arange(LM, dtype=np.float32) + np.float32(0.5))
+    return np.stack(np.meshgrid(c, c, c, indexing="ij"), axis=-1).reshape(-1, 3).astype(np.float32)
+
+
+def _bin_of(m):
+    return m - 1                                       # default_k_edges: bin i holds |n| in [i + 1/2, i + 3/2)
+
+
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("m", [1, 3])
+def test_thermal_power_of_a_plane_wave_sits_in_its_bin(m, order):
+    x = _lattice()
+    temp = (1.0 + 0.1 * np.cos(2.0 * np.pi * m * x[:, 0].astype(np.float64) / LBOX)).astype(np.float32)
+    sp = statistics.field_power_spectrum(_dev(x), _dev(temp), LBOX, LM, order=order, subtract_shot_noise=False)
+    power = sp["power"]
+    peak = float(power[_bin_of(m)])
+    others = torch.cat([power[:_bin_of(m)], power[_bin_of(m) + 1:]])
+    print(f"m={m} order={order}: peak {peak:.6e}, largest other bin {float(others.abs().max()):.3e}")
+    assert peak > 0 and float(others.abs().max()) <= TOL * peak
+    # the amplitude.  A particle at i + 1/2 gives half of itself to cell i and half to cell i + 1 under CIC and TSC alike,
+    # so the mesh holds the wave times cos(pi m / M): two modes of |delta_k|^2 = (0.05 cos(pi m / M) M^3)^2 among the
+    # bin's modes, over the window sinc(pi m / M)^(2 order) the binning deconvolves
+    want = LBOX ** 3 * 2 * (0.05 * np.cos(np.pi * m / LM)) ** 2 / np.sinc(m / LM) ** (2 * order) / float(sp["modes"][_bin_of(m)])
+    assert abs(peak - want) <= 1e-5 * want              # the temperatures are float32 and quantised to 2^-21 of the scale
+    # the same through the rollout statistics (shot noise subtracted there: added back)
+    data = {"Coordinates": _dev(x)[None], "InternalEnergy": _dev(temp)[None, :, None]}
+    gas = statistics.rollout_gas_spectra(data, data, LBOX, LM, order=order)
+    raw = gas["thermal_power_pred"][0] + gas["thermal_shot_noise_pred"][0]
+    assert float((raw - power).abs().max()) <= 1e-12 * peak
+    assert abs(float(gas["thermal_shot_noise_pred"][0]) - float(gfc.shot_noise(temp, LBOX, "mean"))) <= 1e-12 * LBOX ** 3
+
+
+@pytest.mark.parametrize("m", [1, 3])
+def test_momentum_of_plane_waves_splits_into_divergence_and_curl(m):
+    x = _lattice().astype(np.float64)
+    dt, amp = 0.1, 40.0                                # amp dt = 4 cells: particles near a face come from beyond it
+    wave = amp * np.sin(2.0 * np.pi * m * x[:, 0] / LBOX)
+    for axis, longitudinal in ((0, True), (1, False)):
+        vel = np.zeros_like(x)
+        vel[:, axis] = wave
+        straight = x - vel * dt
+        prev = np.mod(straight, LBOX)
+        assert (np.abs(prev - straight) > 1).sum() > 50                   # displaced across a box face
+        sp = statistics.momentum_power_spectrum(_dev(prev.astype(np.float32)), _dev(x.astype(np.float32)), dt, LBOX, LM,
+                                                subtract_shot_noise=False)
+        total, div = float(sp["power_total"][_bin_of(m)]), float(sp["power_div"][_bin_of(m)])
+        print(f"m={m} axis={axis}: total {total:.6e}, div {div:.6e}, curl {float(sp['power_curl'][_bin_of(m)]):.3e}")
+        # half of a particle at i + 1/2 to each of the cells i and i + 1: the wave times cos(pi m / M), over the CIC window
+        want = LBOX ** 3 * 2 * (amp / 2 * np.cos(np.pi * m / LM)) ** 2 / np.sinc(m / LM) ** 4 / float(sp["modes"][_bin_of(m)])
+        assert abs(total - want) <= 1e-5 * want
+        if longitudinal:
+            assert abs(div - total) <= TOL * total
+        else:
+            assert abs(div) <= TOL * total
+        assert torch.equal(sp["power_curl"], sp["power_total"] - sp["power_div"])
+        others = torch.cat([sp["power_total"][:_bin_of(m)], sp["power_total"][_bin_of(m) + 1:]])
+        assert float(others.abs().max()) <= TOL * total
+        # the minimum image: the frame before, not wrapped into the box, gives the same velocities
+        # (float32 positions: the velocities agree to 2^-24 L / (amp dt) or so, the spectra to twice that)
+        free = statistics.momentum_power_spectrum(_dev(straight.astype(np.float32)), _dev(x.astype(np.float32)), dt, LBOX, LM,
+                                                  subtract_shot_noise=False)
+        assert abs(float(free["power_total"][_bin_of(m)]) - total) <= 1e-5 * total
+        shot = LBOX ** 3 * float((vel * vel).sum()) / x.shape[0] ** 2
+        assert abs(float(sp["shot_noise"]) - shot) <= 1e-5 * shot
+        sub = statistics.momentum_power_spectrum(_dev(prev.astype(np.float32)), _dev(x.astype(np.float32)), dt, LBOX, LM)
+        assert float((sub["power_total"] - (sp["power_total"] - sp["shot_noise"])).abs().max()) <= 1e-12 * total
+        assert float((sub["power_div"] - (sp["power_div"] - sp["shot_noise"] / 3)).abs().max()) <= 1e-12 * total
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_values_of_one_give_the_matter_power_spectrum(order):
+    x = np.stack([psc.uniform(N, 80 + t, BOX) for t in range(2)])
+    y = np.stack([psc.uniform(N, 82 + t, BOX) for t in range(2)])
+    ones = torch.ones((2, N), device=DEV)
+    want = statistics.power_spectrum(_dev(x), BOX, 16, pos_b=_dev(y), order=order)
+    for normalise in ("mean", "none"):
+        got = statistics.field_power_spectrum(_dev(x), ones, BOX, 16, pos_b=_dev(y), values_b=ones, order=order,
+                                              normalise=normalise)
+        for key in ("power", "power_b", "cross"):
+            scale = float(want["power"].abs().max()) + BOX ** 3 / N
+            assert float((got[key] - want[key]).abs().max()) <= 1e-12 * scale, (normalise, key)
+        assert float((got["r"] - want["r"]).abs().max()) <= 1e-12
+        assert torch.equal(got["modes"], want["modes"]) and torch.equal(got["k_mean"], want["k_mean"])
+        assert float((got["shot_noise"] - BOX ** 3 / N).abs().max()) <= 1e-12 * BOX ** 3 / N
+    one = statistics.field_power_spectrum(_dev(x[0]), ones[0], BOX, 16, order=order)                   # one frame, one set
+    assert one["power"].shape == (8,) and one["shot_noise"].dim() == 0 and "power_b" not in one
+    assert float((one["power"] - want["power"][0]).abs().max()) <= 1e-12 * scale
+
+
+@functools.lru_cache(maxsize=None)
+def _gas_rollout():
+    """Four frames of 3000 uniform particles that drift, with a temperature that is a fixed function of the local CIC
+    density (mesh 8): hot where dense"""
+    rng = np.random.default_rng(90)
+    x0 = psc.uniform(N, 91, BOX)
+    drift = rng.normal(0.0, 0.3, (N, 3)).astype(np.float32)
+    frames = np.stack([np.mod(x0 + np.float32(t) * drift, np.float32(BOX)) for t in range(4)]).astype(np.float32)
+    frames = np.minimum(frames, np.float32(BOX))
+    temps = []
+    for x in frames:
+        delta = psc.density_contrast(psc.mass_assign(x, BOX, 8, 2), N)
+        cell = np.minimum((x.astype(np.float64) * 8 / BOX).astype(np.int64), 7)
+        temps.append((100.0 * (1.5 + np.tanh(delta[cell[:, 0], cell[:, 1], cell[:, 2]]))).astype(np.float32))
+    return frames, np.stack(temps)
+
+
+def test_rollout_gas_spectra():
+    frames, temps = _gas_rollout()
+    truth = {"Coordinates": _dev(frames), "InternalEnergy": _dev(temps)[..., None]}
+    gas = statistics.rollout_gas_spectra(truth, truth, BOX, 16, dt=0.5)
+    nb = 8
+    assert gas["frames"] == [0, 1, 2, 3] and gas["modes"].shape == (nb,) and gas["k_mean"].shape == (nb,)
+    for key in ("thermal_power_pred", "thermal_power_true", "thermal_cross", "thermal_r", "thermal_transfer",
+                "thermal_density_r_pred", "thermal_density_r_true", "momentum_div_pred", "momentum_div_true",
+                "momentum_curl_pred", "momentum_curl_true"):
+        assert gas[key].shape == (4, nb) and gas[key].dtype == torch.float64, key
+    # a rollout equal to the truth
+    assert float((gas["thermal_r"] - 1.0).abs().max()) <= 1e-12
+    t = gas["thermal_transfer"]
+    assert bool(torch.isfinite(t).any()) and float((t[torch.isfinite(t)] - 1.0).abs().max()) <= 1e-12
+    assert torch.equal(gas["thermal_power_pred"], gas["thermal_power_true"])
+    # hot gas where the dense gas is
+    assert bool((gas["thermal_density_r_pred"][:, :3] > 0).all()) and bool((gas["thermal_density_r_true"][:, :3] > 0).all())
+    assert bool((gas["thermal_density_r_pred"].abs() <= 1 + 1e-12).all())
+    # frame 0 has no predecessor
+    for key in ("momentum_div_pred", "momentum_curl_true"):
+        assert bool(torch.isnan(gas[key][0]).all()) and bool(torch.isfinite(gas[key][1:]).all())
+    # the pieces are the single-frame functions
+    one = statistics.field_power_spectrum(_dev(frames[2]), _dev(temps[2]), BOX, 16)
+    assert float((gas["thermal_power_pred"][2] - one["power"]).abs().max()) <= 1e-12 * float(one["power"].abs().max())
+    mom = statistics.momentum_power_spectrum(_dev(frames[1]), _dev(frames[2]), 0.5, BOX, 16)
+    for key, name in (("power_div", "momentum_div_pred"), ("power_curl", "momentum_curl_true")):
+        assert float((gas[name][2] - mom[key]).abs().max()) <= 1e-12 * float(mom["power_total"].abs().max())
+    both = statistics.field_power_spectrum(_dev(frames[2]), _dev(temps[2]), BOX, 16, pos_b=_dev(frames[2]),
+                                           values_b=torch.ones(N, device=DEV))
+    assert float((gas["thermal_density_r_true"][2] - both["r"]).abs().max()) <= 1e-12
+    # a prediction that differs: frames chosen, no momentum without dt
+    pred = {"Coordinates": _dev(frames[[0, 0, 1, 2]]), "InternalEnergy": _dev(temps[[0, 0, 1, 2]])[..., None]}
+    part = statistics.rollout_gas_spectra(pred, truth, BOX, 16, frames=[1, 3])
+    assert part["frames"] == [1, 3] and part["thermal_r"].shape == (2, nb) and "momentum_div_pred" not in part
+    assert float(part["thermal_r"][:, :3].max()) < 1.0 - 1e-6
+    assert torch.equal(part["thermal_power_true"], gas["thermal_power_true"][[1, 3]])
+    only0 = statistics.rollout_gas_spectra(truth, truth, BOX, 16, dt=0.5, frames=[0])
+    assert bool(torch.isnan(only0["momentum_div_pred"]).all())
+
+
+def test_no_host_synchronisation():
+    frames, temps = (_dev(a) for a in _gas_rollout())
+    swapped, swapped_temps = frames[[1, 0, 3, 2]], temps[[1, 0, 3, 2]]
+    rows = torch.tensor([1, 2, 3], device=DEV)
+    moving = (rows, frames[:3].contiguous(), swapped[:3].contiguous())
+    pos_pred, temp_pred, pos_true, temp_true = (_dev(a) for a in _pair())
+    edges = ops.check_power_edges(statistics.default_k_edges(16), "test")
+    d_field = _dev(_normal((2, 16, 16, 16), 95))
+    q = ops.quantize_weights(torch.stack([temp_pred, temp_true], dim=1), 1000.0)
+
+    def run():
+        out = [ops.mass_assign_weighted(pos_pred, torch.stack([temp_pred, temp_true], dim=1), BOX, 16, 3)]
+        out += list(ops.mass_assign_weighted_backward(pos_pred, q, d_field, BOX, 16, 3, 2.0, 0.5))
+        for smoothing in SMOOTHINGS[:2]:
+            pos, temp = pos_pred.clone().requires_grad_(True), temp_pred.clone().requires_grad_(True)
+            loss = losses.thermal_field_loss(pos, temp, pos_true, temp_true, BOX, 16, 2, smoothing)
+            loss.backward()
+            out += [loss.detach(), pos.grad, temp.grad]
+        for normalise in ("mean", "none"):
+            out += list(statistics.field_sums_on_device(frames, temps, swapped, swapped_temps, BOX, 16, edges, 2, normalise))
+        out += list(statistics.momentum_sums_on_device(frames[:-1], frames[1:], 0.5, BOX, 16, edges, 2))
+        out += list(statistics.gas_sums_on_device(frames, swapped, temps, swapped_temps, BOX, 16, edges, 2, 0.5, moving))
+        return out
+
+    warm = run()                                        # builds the plan, loads the FFT
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        again = run()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    for a, b in zip(again, warm):
+        assert bool(((a == b) | (a.isnan() & b.isnan())).all()) if a.is_floating_point() else torch.equal(a, b)
