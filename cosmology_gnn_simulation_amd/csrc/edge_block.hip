@@ -420,6 +420,13 @@ extern "C" int cgnn_edge_block(const cgnn_mlp* mlp, const void* ps, const void* 
         set_error("cgnn_edge_block: no CGNN_BF16_N16 kernel for latent=%d hidden=%d", latent, hidden);
         return CGNN_ERR_UNSUPPORTED;
     }
+    if (prec != CGNN_F32 && prec != CGNN_BF16) {
+        // CGNN_F32X3, CGNN_F32X3_N16 and CGNN_F16X2 pack for the node / row kernels: there is no edge kernel that reads them
+        // (the bf16 kernel below would take their fragments and the f32 tables for bf16 values)
+        set_error("cgnn_edge_block: no edge kernel for precision %d (CGNN_F32, CGNN_BF16, CGNN_BF16_N16 or CGNN_F16X2_N16)",
+                  prec);
+        return CGNN_ERR_UNSUPPORTED;
+    }
     const bool want_lds = prec == CGNN_BF16 && lds <= CGNN_LDS_WEIGHT_BUDGET && num_edges >= 4096;
 #define CGNN_PAIR(Hh, Dd)                                                                                        \
     if (HT == Hh && DT == Dd) {                                                                                   \

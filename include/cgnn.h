@@ -184,7 +184,8 @@ int cgnn_project_nodes(const cgnn_linear* ws, const cgnn_linear* wd, int32_t pre
  * Kernels by mlp->precision: CGNN_F32 (exact, any compiled shape), CGNN_BF16 (32-edge tiles), CGNN_BF16_N16 (16-edge
  * tiles; weights resident in LDS up to 128 x 128, streamed through an LDS ring at latent = hidden = 256, where the
  * fused aggregation below is not available), CGNN_F16X2_N16 (f32 accuracy on the fp16 matrix cores, latent = hidden =
- * 128, 1..3 hidden layers, a bias on every Linear, CGNN_P_F32 tables).
+ * 128, 1..3 hidden layers, a bias on every Linear, CGNN_P_F32 tables).  The packings of the node / row kernels (CGNN_F32X3,
+ * CGNN_F32X3_N16, CGNN_F16X2) have no edge kernel: CGNN_ERR_UNSUPPORTED, nothing is launched.
  * Where the CGNN_BF16 / CGNN_BF16_N16 kernels round: e_in and every post-ReLU activation to bf16 (nearest even) as they
  * become matrix-core operands (the weights were rounded when packed); table values widen exactly; ps[src] + pd[dst],
  * every sum over K, the biases, LayerNorm and the residual e_in + u are f32.  e_upd holds u itself, e_out differs from
