@@ -1348,8 +1348,8 @@ def fof_catalogue(pos: torch.Tensor, labels: torch.Tensor, box_size: float, size
     * ``hist`` int64 ``[nb]`` (``[T, nb]``), or ``None`` without ``size_edges``: the groups with ``size_edges[b] <= size <
       size_edges[b + 1]`` (``nb + 1`` ascending host integers, ``size_edges[0] >= 1``, ``nb <= 256``).
 
-    Integer sums: the same bits on every run.  No host synchronisation.  One box per call; matching groups between
-    two frames is out of scope."""
+    Integer sums: the same bits on every run.  No host synchronisation.  One box per call; :func:`halo_match` matches
+    the groups of two frames, :func:`fof_group_sums` sums per-particle values over them."""
     what = "fof_catalogue"
     box = torch.tensor(float(box_size), dtype=torch.float32)
     if not (bool(torch.isfinite(box)) and float(box) > 0.0):
@@ -1380,6 +1380,141 @@ def fof_catalogue(pos: torch.Tensor, labels: torch.Tensor, box_size: float, size
     if batched:
         return size, disp, hist
     return size[0], None if disp is None else disp[0], None if hist is None else hist[0]
+
+
+def check_min_members(min_members, who: str, name: str = "min_members") -> int:
+    """A smallest listed group size as a host integer, or ``ValueError``: a whole number in ``[1, 2^31)``."""
+    if isinstance(min_members, bool) or not isinstance(min_members, (int, float)) or min_members != min_members or \
+            int(min_members) != min_members or not 1 <= int(min_members) < 1 << 31:
+        raise ValueError(f"{who}: {name} must be a whole number of at least 1, got {min_members!r}")
+    return int(min_members)
+
+
+def _check_group_ints(t, name: str, shape, who: str) -> None:
+    if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"{who}: {name} must be an integer tensor, got "
+                         f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be {tuple(shape)} like labels_a, got {tuple(t.shape)}")
+
+
+def halo_match(labels_a: torch.Tensor, size_a: torch.Tensor, labels_b: torch.Tensor, size_b: torch.Tensor,
+               min_members: int = 20, min_members_b: Optional[int] = None, size_edges=None):
+    """Match the friends-of-friends groups of two frames that hold the same particles under the same indices, by the
+    members they share (``cgnn_halo_match``).  ``labels_a``, ``labels_b``: labellings of :func:`fof_labels`, ``[N]`` or
+    ``[T, N]`` (one call per frame on the same stream); ``size_a``, ``size_b``: the sizes of :func:`fof_catalogue`.  A
+    group is listed with at least ``min_members`` members (side B: ``min_members_b``, by default the same); a particle
+    counts when both of its groups are listed.  Returns device tensors ``(match_ab, shared_ab, match_ba, shared_ba,
+    summary)``:
+
+    * ``match_ab`` int32 ``[N]`` (``[T, N]``): at a listed root ``ra`` of A with a counting member, the root ``rb`` of B
+      that shares the most counting particles with it, ties to the smallest ``rb``; elsewhere -1;  ``shared_ab``: that
+      number of particles, elsewhere 0;
+    * ``match_ba``, ``shared_ba``: the same from B to A;
+    * ``summary`` int64 ``[nb, 6]`` (``[T, nb, 6]``), or ``None`` without ``size_edges`` (those of
+      :func:`fof_catalogue`): for the listed groups of A with ``size_edges[b] <= size < size_edges[b + 1]`` the number of
+      groups, those with a match, the mutual ones (``match_ba[match_ab[r]] == r``), and over the mutual ones the sums
+      of ``shared_ab``, of ``size_a`` and of the partner's ``size_b``.
+
+    Integers throughout: the same bits on every run, whatever the order of the threads.  Labels outside ``[0, N)`` are
+    ignored.  Refused on the host before any device work (``ValueError``): tensors that are not integers or not of one
+    shape ``[N]`` / ``[T, N]`` with ``N >= 1``, a minimum that is no whole number of at least 1, bad ``size_edges``.  No
+    host synchronisation.  Membership only, one box, one device: no unbinding, no spherical-overdensity masses, no
+    merger trees over more than two frames."""
+    what = "halo_match"
+    min_a = check_min_members(min_members, what)
+    min_b = min_a if min_members_b is None else check_min_members(min_members_b, what, "min_members_b")
+    e = None if size_edges is None else check_size_edges(size_edges, what)
+    _check_group_ints(labels_a, "labels_a", None, what)
+    if labels_a.dim() not in (1, 2) or labels_a.shape[-1] < 1 or labels_a.shape[0] < 1:
+        raise ValueError(f"{what}: labels_a must be [N] or [T, N] with N >= 1, got {tuple(labels_a.shape)}")
+    for t_, name in ((size_a, "size_a"), (labels_b, "labels_b"), (size_b, "size_b")):
+        _check_group_ints(t_, name, labels_a.shape, what)
+    la, sa = i32c(labels_a, "labels_a"), i32c(size_a, "size_a")
+    lb, sb = i32c(labels_b, "labels_b"), i32c(size_b, "size_b")
+    _same_device(la, sa, lb, sb)
+    batched = la.dim() == 2
+    if not batched:
+        la, sa, lb, sb = la.unsqueeze(0), sa.unsqueeze(0), lb.unsqueeze(0), sb.unsqueeze(0)
+    t, n = la.shape
+    nb = 0 if e is None else len(e) - 1
+    dev = la.device
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_halo_match_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((4, t, n), dtype=torch.int32, device=dev)
+    summary = torch.empty((t, nb, _lib.HALO_MATCH_COLS), dtype=torch.int64, device=dev) if e is not None else None
+    edges_c = None if e is None else (C.c_int32 * (nb + 1))(*e)
+    st = stream_ptr(dev)
+    with _timed(what, dev):
+        for f in range(t):
+            check(lib.cgnn_halo_match(la[f].data_ptr(), sa[f].data_ptr(), lb[f].data_ptr(), sb[f].data_ptr(), n, min_a,
+                                      min_b, out[0, f].data_ptr(), out[1, f].data_ptr(), out[2, f].data_ptr(),
+                                      out[3, f].data_ptr(), edges_c, nb, None if summary is None else summary[f].data_ptr(),
+                                      ws.data_ptr(), ws_bytes, st), "cgnn_halo_match")
+    if batched:
+        return out[0], out[1], out[2], out[3], summary
+    return out[0, 0], out[1, 0], out[2, 0], out[3, 0], None if summary is None else summary[0]
+
+
+def fof_group_sums(labels: torch.Tensor, values: torch.Tensor, value_scale=None):
+    """Per-group sums of per-particle values in exact integers (``cgnn_fof_group_sums``): the gas side of a halo.
+    ``labels``: a labelling of :func:`fof_labels`, ``[N]`` or ``[T, N]``; ``values``: ``[(T,) N]`` or ``[(T,) N, C]`` with
+    ``1 <= C <= 4``.  Float values are quantised by :func:`quantize_weights` (2^20 per ``value_scale``, clamped beyond it;
+    ``value_scale=None``: the largest ``|value|`` of the call, taken on the device as :func:`mass_assign_weighted` does);
+    int32 values are taken as quantised already (``value_scale`` must then be ``None``).  Returns ``(sums, scale)``:
+
+    * ``sums`` int64 in the shape of ``values``: at a root slot the sum of its members' weights (the root's own
+      included), elsewhere 0; the group's mean value is ``sums / size * scale / 2^20``, exact up to the quantisation;
+    * ``scale``: the value scale used (the float given, a 0-d float64 device tensor when taken on the device, ``None``
+      for int32 values).
+
+    64-bit integer atomics: the same bits on every run.  Labels outside ``[0, N)`` are ignored.  Refused on the host
+    before any device work (``ValueError``): labels that are not integers or not ``[N]`` / ``[T, N]``, values whose shape
+    does not go with them, ``C`` outside 1..4, a ``value_scale`` that is not positive.  No host synchronisation."""
+    what = "fof_group_sums"
+    _check_group_ints(labels, "labels", None, what)
+    if labels.dim() not in (1, 2) or labels.shape[-1] < 1 or labels.shape[0] < 1:
+        raise ValueError(f"{what}: labels must be [N] or [T, N] with N >= 1, got {tuple(labels.shape)}")
+    lead = tuple(labels.shape)
+    if not torch.is_tensor(values) or values.dim() not in (labels.dim(), labels.dim() + 1) or \
+            tuple(values.shape[:labels.dim()]) != lead or values.is_complex() or values.dtype == torch.bool:
+        raise ValueError(f"{what}: values must be a real tensor {list(lead)} or {list(lead) + ['C']} for labels "
+                         f"{lead}, got {tuple(values.shape) if torch.is_tensor(values) else values!r}")
+    flat = values.dim() == labels.dim()
+    vals = values.unsqueeze(-1) if flat else values
+    if not 1 <= vals.shape[-1] <= _lib.GROUP_SUMS_MAX_CHANNELS:
+        raise ValueError(f"{what}: {vals.shape[-1]} channels; one call takes 1 to {_lib.GROUP_SUMS_MAX_CHANNELS}")
+    if vals.dtype == torch.int32:
+        if value_scale is not None:
+            raise ValueError(f"{what}: int32 values are quantised weights already; value_scale must be None")
+        q, scale = vals, None
+    else:
+        if not (vals.is_floating_point() or vals.dtype == torch.int64):
+            raise ValueError(f"{what}: values must be float values or int32 quantised weights, got {vals.dtype}")
+        scale = None if value_scale is None else _check_value_scale(value_scale, what)
+        require_device(vals, "values")
+        if scale is None:
+            scale = _max_abs_scale(vals)
+        q = quantize_weights(vals, scale)
+    lab = i32c(labels, "labels")
+    q = i32c(q, "values")
+    _same_device(lab, q)
+    batched = lab.dim() == 2
+    if not batched:
+        lab, q = lab.unsqueeze(0), q.unsqueeze(0)
+    t, n = lab.shape
+    c = q.shape[-1]
+    sums = torch.empty((t, n, c), dtype=torch.int64, device=lab.device)
+    lib = _lib.load()
+    st = stream_ptr(lab.device)
+    with _timed(what, lab.device):
+        for f in range(t):
+            check(lib.cgnn_fof_group_sums(lab[f].data_ptr(), q[f].data_ptr(), n, c, sums[f].data_ptr(), st),
+                  "cgnn_fof_group_sums")
+    if flat:
+        sums = sums.squeeze(-1)
+    return (sums if batched else sums[0]), scale
 
 
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,

@@ -21,8 +21,13 @@ interparticle spacings by convention, ``default_linking_length``), labelled by a
 (``ops.fof_labels``) and reduced in exact integers (``ops.fof_catalogue``).  ``halo_catalogue`` lists the groups of a
 frame with their sizes and centres, ``halo_mass_function`` counts them by size (``default_size_edges``: doubling bins
 from 20 members) and ``rollout_halo_statistics`` does that for every selected frame of a rollout against the truth.
-Matching halos between the predicted and the true frame, unbinding, spherical-overdensity masses and velocities are
-out of scope.
+The mass function tells whether a frame has the right number of groups of each size, not whether they are the same
+groups: the predicted and the true frame hold the same particles under the same indices, so ``halo_matches`` pairs
+the groups of two frames by the members they share (``ops.halo_match``; a pair is mutual when each is the other's
+best partner), with sizes, centre offsets and, given per-particle values such as the temperature, each group's mean
+(``ops.fof_group_sums``), and ``rollout_halo_matching`` gives per frame and per size bin of the true groups the
+completeness, the shared fraction and the size ratio.  Membership only: unbinding, spherical-overdensity masses,
+velocities and merger trees over more than two frames are out of scope.
 
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
@@ -696,21 +701,8 @@ def halo_mass_function(pos: torch.Tensor, box_size: float, linking_length: Optio
             "largest": out[..., nb + 2].clone()}
 
 
-def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
-                            box_size: float, linking_length: Optional[float] = None, size_edges=None,
-                            frames: Optional[Sequence[int]] = None) -> Dict:
-    """Halo statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N,
-    3]``).  ``frames``: the frame numbers to judge (default: every frame both hold).  Per selected frame (CPU):
-
-    * ``counts_pred``, ``counts_true`` int64 ``[F, nb]``: the mass functions (:func:`halo_mass_function`);
-    * ``n_groups_pred``, ``n_groups_true`` (int64 ``[F]``), ``fraction_pred``, ``fraction_true`` (float64): groups with
-      at least ``size_edges[0]`` members and the fraction of the particles in them;
-    * ``largest_pred``, ``largest_true`` (int64): the largest group,
-
-    plus ``frames``, ``size_lo`` and ``size_hi``.  No synchronisation per frame; the results come back in one packed
-    transfer.  The two frames' halos are not matched with each other; no unbinding, spherical-overdensity masses or
-    velocities; one box, no spatial shards (an owned-storage rollout goes through ``dist.assemble_frames`` first)."""
-    what = "rollout_halo_statistics"
+def _rollout_frames(rollout_data, ground_truth, frames, what: str):
+    """The selected predicted and true frames ``[F, N, 3]`` on the rollout's device, and their numbers."""
     pc = rollout_data["Coordinates"]
     dev = pc.device
     tc = ground_truth["Coordinates"].to(dev)
@@ -723,6 +715,26 @@ def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth:
     idx = torch.tensor(sel, dtype=torch.int64).to(dev)
     pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
     _frames3(pc, "Coordinates", what)
+    return pc, tc, sel
+
+
+def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
+                            box_size: float, linking_length: Optional[float] = None, size_edges=None,
+                            frames: Optional[Sequence[int]] = None) -> Dict:
+    """Halo statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N,
+    3]``).  ``frames``: the frame numbers to judge (default: every frame both hold).  Per selected frame (CPU):
+
+    * ``counts_pred``, ``counts_true`` int64 ``[F, nb]``: the mass functions (:func:`halo_mass_function`);
+    * ``n_groups_pred``, ``n_groups_true`` (int64 ``[F]``), ``fraction_pred``, ``fraction_true`` (float64): groups with
+      at least ``size_edges[0]`` members and the fraction of the particles in them;
+    * ``largest_pred``, ``largest_true`` (int64): the largest group,
+
+    plus ``frames``, ``size_lo`` and ``size_hi``.  No synchronisation per frame; the results come back in one packed
+    transfer.  The two frames' halos are not matched with each other here (:func:`rollout_halo_matching` does that); no
+    unbinding, spherical-overdensity masses or velocities; one box, no spatial shards (an owned-storage rollout goes
+    through ``dist.assemble_frames`` first)."""
+    what = "rollout_halo_statistics"
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
     n = pc.shape[1]
     ll, e = _halo_arguments(n, box_size, linking_length, size_edges, what)
     out = torch.stack([halo_counts_on_device(pc, box_size, ll, e), halo_counts_on_device(tc, box_size, ll, e)]).cpu()
@@ -735,3 +747,174 @@ def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth:
         res["fraction_" + name] = out[which, :, nb + 1].to(torch.float64) / n
         res["largest_" + name] = out[which, :, nb + 2].clone()
     return res
+
+
+def _group_values(values, n: int, name: str, what: str):
+    if values is None:
+        return None
+    if not torch.is_tensor(values) or values.dim() not in (1, 2) or values.shape[0] != n or values.is_complex() \
+            or values.dtype == torch.bool or (values.dim() == 2 and not 1 <= values.shape[1] <= _lib.GROUP_SUMS_MAX_CHANNELS):
+        raise ValueError(f"{what}: {name} must be a real tensor [{n}] or [{n}, C] with 1 <= C <= "
+                         f"{_lib.GROUP_SUMS_MAX_CHANNELS}, got {tuple(values.shape) if torch.is_tensor(values) else values!r}")
+    return values
+
+
+def halo_matches(pos_a: torch.Tensor, pos_b: torch.Tensor, box_size: float, linking_length: Optional[float] = None,
+                 min_members: int = 20, values_a: Optional[torch.Tensor] = None,
+                 values_b: Optional[torch.Tensor] = None) -> Dict:
+    """The friends-of-friends groups of frame ``pos_a [N, 3]`` (the truth, by convention) with at least ``min_members``
+    members, each with its partner among the groups of ``pos_b [N, 3]``, a frame of the same particles under the same
+    indices: the listed group of B that shares the most members with it (``ops.halo_match``; ties to the smaller root).
+    Returns on the CPU, for every listed group of A sorted as :func:`halo_catalogue` sorts (size descending, then root
+    ascending):
+
+    * ``root``, ``size`` int64 ``[H]``, ``centre`` float64 ``[H, 3]``: as :func:`halo_catalogue`;
+    * ``match_root`` int64 (-1 without a match), ``match_size`` and ``shared`` int64 (0 without), ``mutual`` bool: the
+      partner, its size, the members the two share, and whether the group is its partner's best partner too;
+    * ``match_centre`` float64 ``[H, 3]`` and ``centre_offset`` float64 ``[H]``: the partner's centre and the
+      minimum-image distance of the two :func:`halo_centres`; ``nan`` without a match;
+    * with ``values_a`` (``[N]`` or ``[N, C]``, ``C <= 4``, e.g. the temperature): ``mean_value`` float64 ``[H]`` (``[H,
+      C]``), the mean over the group's members (``ops.fof_group_sums``: exact up to the quantisation to 2^-20 of the
+      largest ``|value|``; int32 values are taken as quantised weights, in units of their scale); with ``values_b``:
+      ``match_mean_value``, the partner's mean over its members in frame B, ``nan`` without a match.
+
+    The number of groups is only known on the device: one synchronisation (``nonzero``) after the kernels and one
+    transfer, as :func:`halo_catalogue`.  One box, one device, membership only: no unbinding, no spherical-overdensity
+    masses, no merger trees over more than two frames; no spatial shards (``dist.assemble_frames`` first)."""
+    what = "halo_matches"
+    for pos, name in ((pos_a, "pos_a"), (pos_b, "pos_b")):
+        if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
+            raise ValueError(f"{what}: {name} must be one frame [N, 3] with N >= 1, got "
+                             f"{tuple(pos.shape) if torch.is_tensor(pos) else pos!r}")
+    if pos_a.shape != pos_b.shape:
+        raise ValueError(f"{what}: the frames hold the same particles: pos_a is {tuple(pos_a.shape)}, pos_b "
+                         f"{tuple(pos_b.shape)}")
+    min_members = ops.check_min_members(min_members, what)
+    n = pos_a.shape[0]
+    ll = default_linking_length(n, box_size) if linking_length is None else linking_length
+    ops.check_linking_length(ll, box_size, what)
+    values = (_group_values(values_a, n, "values_a", what), _group_values(values_b, n, "values_b", what))
+    pos_b = pos_b.to(pos_a.device)
+    la, lb = ops.fof_labels(pos_a, box_size, ll), ops.fof_labels(pos_b, box_size, ll)
+    sa, da, _ = ops.fof_catalogue(pos_a, la, box_size)
+    sb, db, _ = ops.fof_catalogue(pos_b, lb, box_size)
+    m_ab, s_ab, m_ba, _, _ = ops.halo_match(la, sa, lb, sb, min_members)
+    sums = [None if v is None else ops.fof_group_sums(lab, v.to(pos_a.device))
+            for lab, v in zip((la, lb), values)]
+    root = torch.nonzero(sa >= min_members).reshape(-1)                               # the one synchronisation
+    m = m_ab.index_select(0, root).to(torch.int64)
+    has = m >= 0
+    mc = m.clamp(min=0)
+    mutual = has & (m_ba.index_select(0, mc).to(torch.int64) == root)
+    h = root.numel()
+
+    def bits(pos, idx):     # the float32 positions travel as their bits among the integers
+        return pos.index_select(0, idx).to(torch.float32).contiguous().view(torch.int32)
+
+    blocks = [("root", root), ("size", sa.index_select(0, root)), ("match_root", m),
+              ("match_size", torch.where(has, sb.index_select(0, mc), torch.zeros_like(mc, dtype=torch.int32))),
+              ("shared", s_ab.index_select(0, root)), ("mutual", mutual),
+              ("disp_a", da.index_select(0, root)), ("disp_b", db.index_select(0, mc)),
+              ("pos_a", bits(pos_a, root)), ("pos_b", bits(pos_b, mc))]
+    scales = []             # of the value blocks, in their order: float64 bits behind the table
+    for name, s, idx in (("sums_a", sums[0], root), ("sums_b", sums[1], mc)):
+        if s is not None:
+            blocks.append((name, s[0].reshape(n, -1).index_select(0, idx)))
+            scales.append(torch.ones(1, dtype=torch.float64, device=root.device) if s[1] is None
+                          else s[1].to(torch.float64).reshape(1))
+    widths = [1 if t.dim() == 1 else t.shape[1] for _, t in blocks]
+    table = torch.cat([t.to(torch.int64).reshape(h, w) for (_, t), w in zip(blocks, widths)], dim=1)
+    packed = torch.cat([table.reshape(-1)] + [sc.view(torch.int64) for sc in scales]).cpu()     # the one transfer
+    table_h = packed[:table.numel()].reshape(h, table.shape[1])
+    scales_h = packed[table.numel():].view(torch.float64).tolist()
+    order = sorted(range(h), key=lambda i: (-int(table_h[i, 1]), int(table_h[i, 0])))
+    table_h = table_h[torch.tensor(order, dtype=torch.int64)]
+    f, at = {}, 0
+    for (name, _), w in zip(blocks, widths):
+        f[name] = table_h[:, at:at + w]
+        at += w
+
+    def f32(b):
+        return b.to(torch.int32).contiguous().view(torch.float32)
+
+    size_h, msize_h = f["size"].reshape(h), f["match_size"].reshape(h)
+    matched = (f["match_root"] >= 0).reshape(h, 1)
+    nan = float("nan")
+    centre = halo_centres(f32(f["pos_a"]), size_h, f["disp_a"], box_size)
+    mcentre = halo_centres(f32(f["pos_b"]), msize_h.clamp(min=1), f["disp_b"], box_size)
+    mcentre = torch.where(matched, mcentre, torch.full_like(mcentre, nan))
+    box = float(torch.tensor(float(box_size), dtype=torch.float32))
+    d = mcentre - centre
+    d = d - box * torch.round(d / box)
+    res = {"root": f["root"].reshape(h).clone(), "size": size_h.clone(), "centre": centre,
+           "match_root": f["match_root"].reshape(h).clone(), "match_size": msize_h.clone(),
+           "shared": f["shared"].reshape(h).clone(), "mutual": f["mutual"].reshape(h).to(torch.bool),
+           "match_centre": mcentre, "centre_offset": torch.sqrt((d * d).sum(dim=1))}
+    for v, block, name, count in ((values[0], "sums_a", "mean_value", size_h),
+                                  (values[1], "sums_b", "match_mean_value", msize_h)):
+        if v is None:
+            continue
+        mean = f[block].to(torch.float64) / count.clamp(min=1).to(torch.float64).unsqueeze(1) \
+            * (scales_h.pop(0) / float(1 << _lib.WEIGHT_BITS))
+        if name == "match_mean_value":
+            mean = torch.where(matched, mean, torch.full_like(mean, nan))
+        res[name] = mean.reshape(h) if v.dim() == 1 else mean
+    return res
+
+
+def halo_matching_on_device(true_frames: torch.Tensor, pred_frames: torch.Tensor, box_size: float, linking_length: float,
+                            size_edges, min_members: int) -> torch.Tensor:
+    """The device part of :func:`rollout_halo_matching`: for ``[F, N, 3]`` true and predicted frames an int64 ``[F, 6 nb
+    + 3]`` device tensor whose rows hold the summary of ``ops.halo_match`` (A the truth), then the listed true groups,
+    the listed predicted groups, and the mutual pairs among all of them.  No host synchronisation."""
+    lt, lp = ops.fof_labels(true_frames, box_size, linking_length), ops.fof_labels(pred_frames, box_size, linking_length)
+    st = ops.fof_catalogue(true_frames, lt, box_size, want_disp=False)[0]
+    sp = ops.fof_catalogue(pred_frames, lp, box_size, want_disp=False)[0]
+    m_ab, _, m_ba, _, summary = ops.halo_match(lt, st, lp, sp, min_members, size_edges=size_edges)
+    m = m_ab.to(torch.int64)
+    back = torch.gather(m_ba.to(torch.int64), 1, m.clamp(min=0))
+    mutual = (m >= 0) & (back == torch.arange(m.shape[1], device=m.device).unsqueeze(0))
+    return torch.cat([summary.reshape(summary.shape[0], -1),
+                      (st >= min_members).sum(dim=1, dtype=torch.int64).unsqueeze(1),
+                      (sp >= min_members).sum(dim=1, dtype=torch.int64).unsqueeze(1),
+                      mutual.sum(dim=1, dtype=torch.int64).unsqueeze(1)], dim=1)
+
+
+def rollout_halo_matching(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                          linking_length: Optional[float] = None, size_edges=None,
+                          frames: Optional[Sequence[int]] = None, min_members: Optional[int] = None) -> Dict:
+    """Whether a rollout forms the SAME halos as the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T,
+    N, 3]``; both hold the same particles under the same indices).  Per selected frame the groups of the true frame
+    with at least ``min_members`` members (default ``size_edges[0]``) are matched with those of the predicted frame
+    (``ops.halo_match``, A the truth).  Per frame and per size bin of the TRUE groups (CPU):
+
+    * ``n_true``, ``n_matched``, ``n_mutual`` int64 ``[F, nb]``: the listed true groups of the bin, those that share a
+      member with a listed predicted group, and those whose best partner has them as its best partner too;
+    * ``completeness`` float64: ``n_mutual / n_true`` (``nan`` for an empty bin);
+    * ``shared_fraction``, ``size_ratio`` float64: over the mutual ones, the members shared / the true sizes, and the
+      predicted sizes / the true sizes (``nan`` without a mutual pair),
+
+    per frame ``n_groups_true``, ``n_groups_pred`` (int64 ``[F]``, the listed groups, beyond the last edge too) and
+    ``n_unmatched_pred`` (the listed predicted groups without a mutual partner), plus ``frames``, ``size_lo`` and
+    ``size_hi``.  The ratios are formed on the host from the integer sums.  No synchronisation per frame, one packed
+    transfer.  Arguments and refusals are those of :func:`rollout_halo_statistics`.  One box, one device, membership
+    only: no unbinding, no spherical-overdensity masses, no merger trees over more than two frames; an owned-storage
+    rollout goes through ``dist.assemble_frames`` first."""
+    what = "rollout_halo_matching"
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
+    n = pc.shape[1]
+    ll, e = _halo_arguments(n, box_size, linking_length, size_edges, what)
+    min_members = e[0] if min_members is None else ops.check_min_members(min_members, what)
+    out = halo_matching_on_device(tc, pc, box_size, ll, e, min_members).cpu()
+    nb = len(e) - 1
+    edges = torch.tensor(e, dtype=torch.int64)
+    summary = out[:, :nb * _lib.HALO_MATCH_COLS].reshape(len(sel), nb, _lib.HALO_MATCH_COLS)
+    n_true, n_matched, n_mutual = summary[..., 0].clone(), summary[..., 1].clone(), summary[..., 2].clone()
+    shared, size_true, size_pred = (summary[..., c].to(torch.float64) for c in (3, 4, 5))
+    base = nb * _lib.HALO_MATCH_COLS
+    return {"frames": sel, "size_lo": edges[:-1].clone(), "size_hi": edges[1:].clone(),
+            "n_true": n_true, "n_matched": n_matched, "n_mutual": n_mutual,
+            "completeness": n_mutual.to(torch.float64) / n_true.to(torch.float64),
+            "shared_fraction": shared / size_true, "size_ratio": size_pred / size_true,
+            "n_groups_true": out[:, base].clone(), "n_groups_pred": out[:, base + 1].clone(),
+            "n_unmatched_pred": out[:, base + 1] - out[:, base + 2]}

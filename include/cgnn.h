@@ -726,6 +726,47 @@ int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_l
 int cgnn_fof_catalogue(const float* pos, const int32_t* labels, int64_t n, float box_size, int32_t* size, int64_t* disp,
                        const int32_t* size_edges, int32_t num_bins, int64_t* hist, void* stream);
 
+/* ---- the same halos in two frames: matching groups by shared members; per-group sums ----------------------------------
+ * Two frames of a rollout hold the same particles under the same indices.  labels_a, labels_b (device, int32 [n]) are
+ * labellings in the sense of cgnn_fof_labels (a root slot r has labels[r] == r), size_a, size_b (device, int32 [n]) as
+ * cgnn_fof_catalogue writes them; min_a, min_b >= 1.
+ *   A group is LISTED when its size at its root is at least its side's minimum.
+ *   Particle i COUNTS when labels_a[i] and labels_b[i] both lie in [0, n) and both groups are listed.  A label outside
+ *   [0, n) is ignored, never dereferenced (cgnn_fof_catalogue's rule).
+ *   shared(ra, rb) = the counting particles with labels_a == ra and labels_b == rb.
+ *   match_ab[ra]   = the rb with the largest shared(ra, rb), ties to the SMALLEST rb;  shared_ab[ra] = that count.
+ *                    Every slot that is not a listed root of A with at least one counting member: match_ab = -1,
+ *                    shared_ab = 0.
+ *   match_ba, shared_ba: the same with the sides exchanged.
+ * All four (device, int32 [n]) are overwritten.  summary (device, int64 [num_bins, 6]) may be NULL; with it size_edges
+ * (HOST memory, num_bins + 1 int32, the rules of cgnn_fof_catalogue, 1 <= num_bins <= 256) bins the listed groups r of A
+ * with size_edges[b] <= size_a[r] < size_edges[b + 1], and row b holds: the number of groups; those with a match; the
+ * MUTUAL ones (match_ba[match_ab[r]] == r); and over the mutual ones the sums of shared_ab[r], of size_a[r] and of
+ * size_b[match_ab[r]].
+ * Everything is an integer and the result does not depend on the order of the threads, on the hash function or on the
+ * table size: the same bits on every run.  The pairs are counted in an open-addressing table of the workspace (64-bit
+ * keys (ra << 32) | rb claimed by compare-and-swap, 32-bit counts; lock-free, no spin-wait; csrc/halo_match.hip), the
+ * best partner is a 64-bit atomic max of (count << 32) | (0xFFFFFFFF - root).  No host synchronisation, everything on
+ * `stream`.  CGNN_ERR_INVALID_ARG for a null pointer (summary without size_edges included), n <= 0, a minimum below 1,
+ * num_bins outside 1..256 or size_edges that do not start at 1 or above and ascend strictly, a workspace that is not
+ * 16-byte aligned; n >= 2^31: CGNN_ERR_UNSUPPORTED; a short workspace: CGNN_ERR_WORKSPACE.  Workspace:
+ * cgnn_halo_match_workspace_bytes(n), a function of n alone, between 40 n and 64 n bytes plus alignment (256 for n <= 0
+ * or n >= 2^31).
+ *
+ * cgnn_fof_group_sums: sums (device, int64 [n, channels]) is overwritten; at a root slot r it holds the sum over the
+ * members i (labels[i] == r, r itself included) of q[i, :] (device, int32 [n, channels], 1 <= channels <= 4: the weights
+ * of cgnn_mass_assign_weighted, 2^20 per value scale), every other slot 0.  |q| <= 2^20 and fewer than 2^31 members
+ * stay inside int64.  64-bit integer atomics: the same bits on every run.  Labels outside [0, n) are ignored.  No
+ * workspace, no host synchronisation.  CGNN_ERR_INVALID_ARG for a null pointer, n <= 0 or channels outside 1..4;
+ * n >= 2^31: CGNN_ERR_UNSUPPORTED. */
+size_t cgnn_halo_match_workspace_bytes(int64_t n);
+int cgnn_halo_match(const int32_t* labels_a, const int32_t* size_a, const int32_t* labels_b, const int32_t* size_b,
+                    int64_t n, int32_t min_a, int32_t min_b, int32_t* match_ab, int32_t* shared_ab, int32_t* match_ba,
+                    int32_t* shared_ba, const int32_t* size_edges, int32_t num_bins, int64_t* summary, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int cgnn_fof_group_sums(const int32_t* labels, const int32_t* q, int64_t n, int32_t channels, int64_t* sums,
+                        void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes
