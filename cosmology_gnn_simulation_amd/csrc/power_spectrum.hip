@@ -26,7 +26,12 @@
 // product is v receives (v q + 2^19) >> 20 in channel c, in int64 with an arithmetic shift.  Signed contributions are
 // added as two's complement on the unsigned mesh; the sums are still integers, so the bits do not depend on the order
 // of arrival.  cgnn_mass_assign_weighted_backward is its transpose with respect to the weights and the positions,
-// straight through both quantisations (ma_gather_weighted_kernel).
+// straight through both quantisations.
+//
+// One kernel each.  ma_deposit_kernel<ORDER, C> and ma_gather_kernel<ORDER, C> serve the plain and the weighted
+// entries: C = 0 is the unit-weight form, one channel whose weight is the compile-time constant 2^20 (a = 1.0).  It is
+// the plain arithmetic exactly -- (v 2^20 + 2^19) >> 20 = v for 0 <= v <= 2^39, and 0.0 + 1.0 g = g -- and emits none
+// of it: no q is read, nothing is multiplied or shifted, d_val does not exist.
 //
 // Binning.  A mode of the rfft array [M, M, M/2 + 1] has signed frequencies nx, ny in (-M/2, M/2] and nz in [0, M/2];
 // n2 = nx^2 + ny^2 + nz^2 <= 3 * 256^2 is exact in integers and in float32.  With e2[i] = fl32(k_edges[i]^2) the mode
@@ -87,10 +92,23 @@ __device__ __forceinline__ void ma_axis(float u, int M, int* cell, int* w) {
     }
 }
 
-// one thread per particle of every frame; mesh [frames, M, M, M], zeroed by the caller
-template <int ORDER>
-__global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __restrict__ pos, int64_t total, int64_t n,
+#define CGNN_MA_WEIGHT_BITS 20    // a quantised weight of 2^20 is one value scale
+#define CGNN_MA_MAX_CHANNELS 4
+
+__device__ __forceinline__ int ma_clamp_q(int q) {
+    const int one = 1 << CGNN_MA_WEIGHT_BITS;
+    return q < -one ? -one : (q > one ? one : q);
+}
+
+// one thread per particle of every frame, cells and weights once for its channels; mesh [frames, channels, M, M, M],
+// zeroed by the caller.  C >= 1: q [total, C], and a cell receives (v q + 2^19) >> 20 per channel (|v q| <= 2^59; >> of
+// a negative long long is arithmetic: hipcc, as every two's complement target).  C == 0, the unit-weight form: one
+// channel, q is not read, and a cell receives v.
+template <int ORDER, int C>
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __restrict__ pos,
+                                                                const int32_t* __restrict__ q, int64_t total, int64_t n,
                                                                 float s, int M, unsigned long long* __restrict__ mesh) {
+    constexpr int CH = C == 0 ? 1 : C;
     const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
     if (i >= total) return;
     int cell[3][ORDER], w[3][ORDER];
@@ -102,48 +120,13 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_kernel(const float* __r
         if (!(fabsf(u) < 1.0e9f)) u = 0.f;
         ma_axis<ORDER>(u, M, cell[ax], w[ax]);
     }
-    unsigned long long* base = mesh + (i / n) * ((int64_t)M * M * M);
+    long long qc[CH];
+    if constexpr (C != 0) {
 #pragma unroll
-    for (int a = 0; a < ORDER; ++a)
-#pragma unroll
-        for (int b = 0; b < ORDER; ++b)
-#pragma unroll
-            for (int c = 0; c < ORDER; ++c) {
-                const long long v = (long long)w[0][a] * w[1][b] * w[2][c];
-                if (v != 0) atomicAdd(base + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c], (unsigned long long)v);
-            }
-}
-
-#define CGNN_MA_WEIGHT_BITS 20    // a quantised weight of 2^20 is one value scale
-#define CGNN_MA_MAX_CHANNELS 4
-
-__device__ __forceinline__ int ma_clamp_q(int q) {
-    const int one = 1 << CGNN_MA_WEIGHT_BITS;
-    return q < -one ? -one : (q > one ? one : q);
-}
-
-// one thread per particle of every frame, cells and weights once for its C channels; q [total, C]; mesh [frames, C, M,
-// M, M], zeroed by the caller.  |v q| <= 2^59; >> of a negative long long is arithmetic (hipcc, as every two's
-// complement target).
-template <int ORDER, int C>
-__global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_weighted_kernel(const float* __restrict__ pos,
-                                                                         const int32_t* __restrict__ q, int64_t total,
-                                                                         int64_t n, float s, int M,
-                                                                         unsigned long long* __restrict__ mesh) {
-    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
-    if (i >= total) return;
-    int cell[3][ORDER], w[3][ORDER];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        float u = __fmul_rn(pos[3 * i + ax], s);
-        if (!(fabsf(u) < 1.0e9f)) u = 0.f;          // the guard of ma_deposit_kernel
-        ma_axis<ORDER>(u, M, cell[ax], w[ax]);
+        for (int c = 0; c < C; ++c) qc[c] = ma_clamp_q(q[C * i + c]);
     }
-    long long qc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) qc[c] = ma_clamp_q(q[C * i + c]);
     const int64_t cells = (int64_t)M * M * M;
-    unsigned long long* base = mesh + (i / n) * (C * cells);
+    unsigned long long* base = mesh + (i / n) * (CH * cells);
 #pragma unroll
     for (int a = 0; a < ORDER; ++a)
 #pragma unroll
@@ -153,10 +136,14 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_deposit_weighted_kernel(const f
                 const long long v = (long long)w[0][a] * w[1][b] * w[2][c3];
                 if (v == 0) continue;
                 unsigned long long* at = base + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c3];
+                if constexpr (C == 0) {
+                    atomicAdd(at, (unsigned long long)v);
+                } else {
 #pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const long long add = (v * qc[c] + ((long long)1 << (CGNN_MA_WEIGHT_BITS - 1))) >> CGNN_MA_WEIGHT_BITS;
-                    if (add != 0) atomicAdd(at + c * cells, (unsigned long long)add);
+                    for (int c = 0; c < C; ++c) {
+                        const long long add = (v * qc[c] + ((long long)1 << (CGNN_MA_WEIGHT_BITS - 1))) >> CGNN_MA_WEIGHT_BITS;
+                        if (add != 0) atomicAdd(at + c * cells, (unsigned long long)add);
+                    }
                 }
             }
 }
@@ -193,61 +180,24 @@ __device__ __forceinline__ double ma_diff(const double* v, const double* dw) {
     return dw[0] * (v[1] - v[0]) + dw[1] * (v[2] - v[1]);
 }
 
-// one thread per particle of every frame: gathers its ORDER^3 cells of d_mesh [frames, M, M, M] once and writes its own
-// three values of d_pos [frames, n, 3]; no atomics.  Summation order per axis: the two other axes in ascending axis
-// order, the first outer, the second inner; term = (ma_diff * w_outer) * w_inner; acc starts at 0.0 and adds the terms
-// in loop order.  d_pos = fl32((acc * (double)s) * scale).
-template <int ORDER>
-__global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_kernel(const float* __restrict__ pos,
-                                                               const double* __restrict__ d_mesh, int64_t total, int64_t n,
-                                                               float s, int M, double scale, float* __restrict__ d_pos) {
-    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
-    if (i >= total) return;
-    int cell[3][ORDER];
-    double wv[3][ORDER], dw[3][ORDER - 1];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) ma_axis_grad<ORDER>(pos[3 * i + ax], s, M, cell[ax], wv[ax], dw[ax]);
-    const double* base = d_mesh + (i / n) * ((int64_t)M * M * M);
-    double D[ORDER][ORDER][ORDER];
-#pragma unroll
-    for (int a = 0; a < ORDER; ++a)
-#pragma unroll
-        for (int b = 0; b < ORDER; ++b)
-#pragma unroll
-            for (int c = 0; c < ORDER; ++c) D[a][b][c] = base[((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c]];
-    double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int p = 0; p < ORDER; ++p)
-#pragma unroll
-        for (int q = 0; q < ORDER; ++q) {
-            double line[ORDER];
-#pragma unroll
-            for (int t = 0; t < ORDER; ++t) line[t] = D[t][p][q];
-            acc[0] += (ma_diff<ORDER>(line, dw[0]) * wv[1][p]) * wv[2][q];
-#pragma unroll
-            for (int t = 0; t < ORDER; ++t) line[t] = D[p][t][q];
-            acc[1] += (ma_diff<ORDER>(line, dw[1]) * wv[0][p]) * wv[2][q];
-#pragma unroll
-            for (int t = 0; t < ORDER; ++t) line[t] = D[p][q][t];
-            acc[2] += (ma_diff<ORDER>(line, dw[2]) * wv[0][p]) * wv[1][q];
-        }
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) d_pos[3 * i + ax] = (float)((acc[ax] * (double)s) * scale);
-}
-
-// The transpose of the weighted deposit (cgnn_mass_assign_weighted_backward), one thread per particle of every frame,
-// no atomics.  d_field [frames, C, M, M, M]; per channel the thread gathers its ORDER^3 cells once (D) and forms
+// The transpose of the deposit, one thread per particle of every frame, no atomics: it gathers its ORDER^3 cells of
+// every channel of d_field [frames, channels, M, M, M] once (D) and writes its own values of d_pos [frames, n, 3] and
+// d_val [frames, n, C].  Per channel
 //     val = sum over a (outer), b, c (inner) of ((wv0[a] * wv1[b]) * wv2[c]) * D[a][b][c]        from 0.0, in loop order
-//     g[ax] = ma_gather_kernel's acc[ax] on D                                                     (the same order)
-// d_val[i, ch] = fl32(val * scale_val);  chan[ax] += a_ch * g[ax] over the channels in ascending order, from 0.0, with
-// a_ch = (double)clamp(q) * 2^-20;  d_pos[i, ax] = fl32((chan[ax] * (double)s) * scale_pos).  Either output may be null.
+//     g[ax] = the gradient with respect to u on axis ax.  Summation order: the two other axes in ascending axis order,
+//             the first outer, the second inner; term = (ma_diff * w_outer) * w_inner; from 0.0, in loop order
+// C >= 1 (cgnn_mass_assign_weighted_backward): d_val[i, ch] = fl32(val * scale_val);  chan[ax] += a_ch * g[ax] over the
+// channels in ascending order, from 0.0, with a_ch = (double)clamp(q) * 2^-20;  d_pos[i, ax] = fl32((chan[ax] *
+// (double)s) * scale_pos).  Either output may be null.  C == 0, the unit-weight form (cgnn_mass_assign_backward): one
+// channel, chan = g, d_pos is written, q and d_val are not touched.
 template <int ORDER, int C>
-__global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_weighted_kernel(const float* __restrict__ pos,
-                                                                        const int32_t* __restrict__ q,
-                                                                        const double* __restrict__ d_field, int64_t total,
-                                                                        int64_t n, float s, int M, double scale_pos,
-                                                                        double scale_val, float* __restrict__ d_pos,
-                                                                        float* __restrict__ d_val) {
+__global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_kernel(const float* __restrict__ pos, const int32_t* __restrict__ q,
+                                                               const double* __restrict__ d_field, int64_t total,
+                                                               int64_t n, float s, int M, double scale_pos,
+                                                               double scale_val, float* __restrict__ d_pos,
+                                                               float* __restrict__ d_val) {
+    constexpr bool UNIT = C == 0;
+    constexpr int CH = UNIT ? 1 : C;
     const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
     if (i >= total) return;
     int cell[3][ORDER];
@@ -255,29 +205,30 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_weighted_kernel(const fl
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) ma_axis_grad<ORDER>(pos[3 * i + ax], s, M, cell[ax], wv[ax], dw[ax]);
     const int64_t cells = (int64_t)M * M * M;
-    const double* base = d_field + (i / n) * (C * cells);
+    const double* base = d_field + (i / n) * (CH * cells);
     double chan[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int ch = 0; ch < C; ++ch) {
+    for (int ch = 0; ch < CH; ++ch) {
         double D[ORDER][ORDER][ORDER];
 #pragma unroll
         for (int a = 0; a < ORDER; ++a)
 #pragma unroll
             for (int b = 0; b < ORDER; ++b)
 #pragma unroll
-                for (int c = 0; c < ORDER; ++c)
-                    D[a][b][c] = base[ch * cells + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c]];
-        if (d_val) {
-            double val = 0.0;
+                for (int c = 0; c < ORDER; ++c) D[a][b][c] = base[ch * cells + ((int64_t)cell[0][a] * M + cell[1][b]) * M + cell[2][c]];
+        if constexpr (!UNIT) {
+            if (d_val) {
+                double val = 0.0;
 #pragma unroll
-            for (int a = 0; a < ORDER; ++a)
+                for (int a = 0; a < ORDER; ++a)
 #pragma unroll
-                for (int b = 0; b < ORDER; ++b)
+                    for (int b = 0; b < ORDER; ++b)
 #pragma unroll
-                    for (int c = 0; c < ORDER; ++c) val += ((wv[0][a] * wv[1][b]) * wv[2][c]) * D[a][b][c];
-            d_val[C * i + ch] = (float)(val * scale_val);
+                        for (int c = 0; c < ORDER; ++c) val += ((wv[0][a] * wv[1][b]) * wv[2][c]) * D[a][b][c];
+                d_val[C * i + ch] = (float)(val * scale_val);
+            }
         }
-        if (d_pos) {
+        if (UNIT || d_pos) {
             double acc[3] = {0.0, 0.0, 0.0};
 #pragma unroll
             for (int p = 0; p < ORDER; ++p)
@@ -294,12 +245,17 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_weighted_kernel(const fl
                     for (int t = 0; t < ORDER; ++t) line[t] = D[p][r][t];
                     acc[2] += (ma_diff<ORDER>(line, dw[2]) * wv[0][p]) * wv[1][r];
                 }
-            const double a_ch = (double)ma_clamp_q(q[C * i + ch]) * (1.0 / (double)(1 << CGNN_MA_WEIGHT_BITS));
+            if constexpr (UNIT) {
 #pragma unroll
-            for (int ax = 0; ax < 3; ++ax) chan[ax] += a_ch * acc[ax];
+                for (int ax = 0; ax < 3; ++ax) chan[ax] = acc[ax];
+            } else {
+                const double a_ch = (double)ma_clamp_q(q[C * i + ch]) * (1.0 / (double)(1 << CGNN_MA_WEIGHT_BITS));
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) chan[ax] += a_ch * acc[ax];
+            }
         }
     }
-    if (d_pos) {
+    if (UNIT || d_pos) {
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) d_pos[3 * i + ax] = (float)((chan[ax] * (double)s) * scale_pos);
     }
@@ -462,11 +418,10 @@ static size_t pb_window_bytes() { return pb_align256((size_t)(CGNN_MA_MAX_MESH /
 
 using namespace cgnn;
 
-#define CGNN_MA_WEIGHTED_MAX_N ((int64_t)1 << 23)
-
-// the refusals the two weighted entries share; 0 when the arguments are legal
-static int ma_weighted_refuses(const char* who, bool null_pointer, int64_t frames, int64_t n, int32_t channels,
-                               float box_size, int32_t mesh, int32_t order, int32_t min_order) {
+// the refusals the four mass-assignment entries share; 0 when the arguments are legal.  weighted: the entry takes q
+// (channels is checked, and n <= 2^23: a particle adds up to 2^39 + 14 in magnitude per channel); else n <= 2^24
+static int ma_refuses(const char* who, bool null_pointer, int64_t frames, int64_t n, bool weighted, int32_t channels,
+                      float box_size, int32_t mesh, int32_t order, int32_t min_order) {
     if (null_pointer || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
         set_error("%s: invalid argument", who);
         return CGNN_ERR_INVALID_ARG;
@@ -476,155 +431,109 @@ static int ma_weighted_refuses(const char* who, bool null_pointer, int64_t frame
                   (int)min_order, min_order == 2 ? " (NGP has no gradient)" : "");
         return CGNN_ERR_INVALID_ARG;
     }
-    if (channels < 1 || channels > CGNN_MA_MAX_CHANNELS) {
+    if (weighted && (channels < 1 || channels > CGNN_MA_MAX_CHANNELS)) {
         set_error("%s: channels=%d outside [1, %d]", who, (int)channels, CGNN_MA_MAX_CHANNELS);
         return CGNN_ERR_INVALID_ARG;
     }
-    if (n > CGNN_MA_WEIGHTED_MAX_N) {
-        set_error("%s: more than 2^23 particles in a frame (a particle adds up to 2^39 + 14 in magnitude per channel: "
-                  "n of them in one cell must stay inside int64)", who);
+    if (n > ((int64_t)1 << (weighted ? 23 : 24))) {
+        set_error("%s: more than 2^%d particles in a frame (%s must stay inside int64)", who, weighted ? 23 : 24,
+                  weighted ? "a particle adds up to 2^39 + 14 in magnitude per channel: n of them in one cell" : "n 2^39");
         return CGNN_ERR_UNSUPPORTED;
     }
     return CGNN_OK;
 }
 
-template <int ORDER>
-static void ma_launch_weighted(int channels, unsigned blocks, hipStream_t st, const float* p, const int32_t* q,
-                               int64_t total, int64_t n, float s, int M, unsigned long long* m) {
-    if (channels == 1) ma_deposit_weighted_kernel<ORDER, 1><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
-    else if (channels == 2) ma_deposit_weighted_kernel<ORDER, 2><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
-    else if (channels == 3) ma_deposit_weighted_kernel<ORDER, 3><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
-    else ma_deposit_weighted_kernel<ORDER, 4><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, total, n, s, M, m);
+// whole frames per launch, at most CGNN_PS_MAX_THREADS threads each: launch(f0, nf) for every batch of nf >= 1 frames
+// from frame f0 (threads_per_frame <= CGNN_PS_MAX_THREADS)
+template <class F>
+static void ps_for_frame_batches(int64_t frames, int64_t threads_per_frame, F launch) {
+    const int64_t step = CGNN_PS_MAX_THREADS / threads_per_frame;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) launch(f0, frames - f0 < step ? frames - f0 : step);
 }
 
-template <int ORDER>
-static void ma_launch_weighted_gather(int channels, unsigned blocks, hipStream_t st, const float* p, const int32_t* q,
-                                      const double* d, int64_t total, int64_t n, float s, int M, double scale_pos,
-                                      double scale_val, float* d_pos, float* d_val) {
-#define CGNN_MA_GATHER(C) \
-    ma_gather_weighted_kernel<ORDER, C><<<blocks, CGNN_BLOCK, 0, st>>>(p, q, d, total, n, s, M, scale_pos, scale_val, d_pos, d_val)
-    if (channels == 1) CGNN_MA_GATHER(1);
-    else if (channels == 2) CGNN_MA_GATHER(2);
-    else if (channels == 3) CGNN_MA_GATHER(3);
-    else CGNN_MA_GATHER(4);
-#undef CGNN_MA_GATHER
+// KERNEL<ORDER, C> for the run-time `channels` (0: the unit-weight form), one thread per particle of `total`
+#define CGNN_MA_LAUNCH(KERNEL, ORDER, ...)                                                          \
+    do {                                                                                            \
+        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);                  \
+        if (channels == 0) KERNEL<ORDER, 0><<<blocks, CGNN_BLOCK, 0, st>>>(__VA_ARGS__);            \
+        else if (channels == 1) KERNEL<ORDER, 1><<<blocks, CGNN_BLOCK, 0, st>>>(__VA_ARGS__);       \
+        else if (channels == 2) KERNEL<ORDER, 2><<<blocks, CGNN_BLOCK, 0, st>>>(__VA_ARGS__);       \
+        else if (channels == 3) KERNEL<ORDER, 3><<<blocks, CGNN_BLOCK, 0, st>>>(__VA_ARGS__);       \
+        else KERNEL<ORDER, 4><<<blocks, CGNN_BLOCK, 0, st>>>(__VA_ARGS__);                          \
+    } while (0)
+
+// the deposit of checked arguments; channels == 0 (q is null): the unit-weight form, out [frames, M, M, M]
+static int ma_deposit(const char* who, const float* pos, const int32_t* q, int64_t frames, int64_t n, int channels,
+                      float box_size, int M, int order, int64_t* out, void* stream) {
+    const float s = (float)M / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t qs = channels, ms = (channels ? channels : 1) * ((int64_t)M * M * M);      // strides of a frame
+    int rc = check_hip(hipMemsetAsync(out, 0, (size_t)(frames * ms) * sizeof(int64_t), st), who);
+    if (rc) return rc;
+    ps_for_frame_batches(frames, n, [&](int64_t f0, int64_t nf) {
+        const int64_t total = nf * n;
+        const float* p = pos + f0 * n * 3;
+        const int32_t* w = q ? q + f0 * n * qs : nullptr;
+        unsigned long long* m = reinterpret_cast<unsigned long long*>(out) + f0 * ms;
+        if (order == 1) CGNN_MA_LAUNCH(ma_deposit_kernel, 1, p, w, total, n, s, M, m);
+        else if (order == 2) CGNN_MA_LAUNCH(ma_deposit_kernel, 2, p, w, total, n, s, M, m);
+        else CGNN_MA_LAUNCH(ma_deposit_kernel, 3, p, w, total, n, s, M, m);
+    });
+    return check_hip(hipGetLastError(), who);
+}
+
+// the gather of checked arguments (order 2 or 3); channels == 0 (q and d_val are null): the unit-weight form
+static int ma_gather(const char* who, const float* pos, const int32_t* q, const double* d_field, int64_t frames, int64_t n,
+                     int channels, float box_size, int M, int order, double scale_pos, double scale_val, float* d_pos,
+                     float* d_val, void* stream) {
+    const float s = (float)M / box_size;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t qs = channels, ms = (channels ? channels : 1) * ((int64_t)M * M * M);      // strides of a frame
+    ps_for_frame_batches(frames, n, [&](int64_t f0, int64_t nf) {
+        const int64_t total = nf * n;
+        const float* p = pos + f0 * n * 3;
+        const int32_t* w = q ? q + f0 * n * qs : nullptr;
+        const double* d = d_field + f0 * ms;
+        float* gp = d_pos ? d_pos + f0 * n * 3 : nullptr;
+        float* gv = d_val ? d_val + f0 * n * qs : nullptr;
+        if (order == 2) CGNN_MA_LAUNCH(ma_gather_kernel, 2, p, w, d, total, n, s, M, scale_pos, scale_val, gp, gv);
+        else CGNN_MA_LAUNCH(ma_gather_kernel, 3, p, w, d, total, n, s, M, scale_pos, scale_val, gp, gv);
+    });
+    return check_hip(hipGetLastError(), who);
 }
 
 extern "C" {
 
 int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
                      int64_t* out, void* stream) {
-    if (!pos || !out || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
-        set_error("cgnn_mass_assign: invalid argument");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (mesh < 2 || mesh > CGNN_MA_MAX_MESH || order < 1 || order > 3) {
-        set_error("cgnn_mass_assign: mesh=%d outside [2, %d] or order=%d outside [1, 3]", (int)mesh, CGNN_MA_MAX_MESH,
-                  (int)order);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (n > ((int64_t)1 << 24)) {
-        set_error("cgnn_mass_assign: more than 2^24 particles in a frame (n 2^39 must stay inside int64)");
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    const float s = (float)mesh / box_size;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)frames * mesh * mesh * mesh * sizeof(int64_t);
-    int rc = check_hip(hipMemsetAsync(out, 0, bytes, st), "cgnn_mass_assign memset");
-    if (rc) return rc;
-    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^24: at least one frame)
-    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
-        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
-        const float* p = pos + f0 * n * 3;
-        unsigned long long* m = reinterpret_cast<unsigned long long*>(out) + f0 * cells;
-        if (order == 1) ma_deposit_kernel<1><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
-        else if (order == 2) ma_deposit_kernel<2><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
-        else ma_deposit_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, total, n, s, mesh, m);
-    }
-    return check_hip(hipGetLastError(), "cgnn_mass_assign");
+    const char* who = "cgnn_mass_assign";
+    const int rc = ma_refuses(who, !pos || !out, frames, n, false, 0, box_size, mesh, order, 1);
+    return rc ? rc : ma_deposit(who, pos, nullptr, frames, n, 0, box_size, mesh, order, out, stream);
 }
 
 int cgnn_mass_assign_backward(const float* pos, const double* d_mesh, int64_t frames, int64_t n, float box_size,
                               int32_t mesh, int32_t order, double scale, float* d_pos, void* stream) {
-    if (!pos || !d_mesh || !d_pos || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
-        set_error("cgnn_mass_assign_backward: invalid argument");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (mesh < 2 || mesh > CGNN_MA_MAX_MESH || order < 2 || order > 3) {
-        set_error("cgnn_mass_assign_backward: mesh=%d outside [2, %d] or order=%d outside [2, 3] (NGP has no gradient)",
-                  (int)mesh, CGNN_MA_MAX_MESH, (int)order);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    if (n > ((int64_t)1 << 24)) {
-        set_error("cgnn_mass_assign_backward: more than 2^24 particles in a frame (the deposit's limit)");
-        return CGNN_ERR_UNSUPPORTED;
-    }
-    const float s = (float)mesh / box_size;
-    hipStream_t st = (hipStream_t)stream;
-    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^24: at least one frame)
-    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
-        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
-        const float* p = pos + f0 * n * 3;
-        const double* m = d_mesh + f0 * cells;
-        float* g = d_pos + f0 * n * 3;
-        if (order == 2) ma_gather_kernel<2><<<blocks, CGNN_BLOCK, 0, st>>>(p, m, total, n, s, mesh, scale, g);
-        else ma_gather_kernel<3><<<blocks, CGNN_BLOCK, 0, st>>>(p, m, total, n, s, mesh, scale, g);
-    }
-    return check_hip(hipGetLastError(), "cgnn_mass_assign_backward");
+    const char* who = "cgnn_mass_assign_backward";
+    const int rc = ma_refuses(who, !pos || !d_mesh || !d_pos, frames, n, false, 0, box_size, mesh, order, 2);
+    return rc ? rc : ma_gather(who, pos, nullptr, d_mesh, frames, n, 0, box_size, mesh, order, scale, 1.0, d_pos, nullptr,
+                               stream);
 }
 
 int cgnn_mass_assign_weighted(const float* pos, const int32_t* q, int64_t frames, int64_t n, int32_t channels,
                               float box_size, int32_t mesh, int32_t order, int64_t* out, void* stream) {
-    int rc = ma_weighted_refuses("cgnn_mass_assign_weighted", !pos || !q || !out, frames, n, channels, box_size, mesh,
-                                 order, 1);
-    if (rc) return rc;
-    const float s = (float)mesh / box_size;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t cells = (int64_t)mesh * mesh * mesh;
-    rc = check_hip(hipMemsetAsync(out, 0, (size_t)frames * channels * cells * sizeof(int64_t), st),
-                   "cgnn_mass_assign_weighted memset");
-    if (rc) return rc;
-    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^23: at least two frames)
-    const int64_t step = CGNN_PS_MAX_THREADS / n;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
-        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
-        const float* p = pos + f0 * n * 3;
-        const int32_t* w = q + f0 * n * channels;
-        unsigned long long* m = reinterpret_cast<unsigned long long*>(out) + f0 * channels * cells;
-        if (order == 1) ma_launch_weighted<1>(channels, blocks, st, p, w, total, n, s, mesh, m);
-        else if (order == 2) ma_launch_weighted<2>(channels, blocks, st, p, w, total, n, s, mesh, m);
-        else ma_launch_weighted<3>(channels, blocks, st, p, w, total, n, s, mesh, m);
-    }
-    return check_hip(hipGetLastError(), "cgnn_mass_assign_weighted");
+    const char* who = "cgnn_mass_assign_weighted";
+    const int rc = ma_refuses(who, !pos || !q || !out, frames, n, true, channels, box_size, mesh, order, 1);
+    return rc ? rc : ma_deposit(who, pos, q, frames, n, channels, box_size, mesh, order, out, stream);
 }
 
 int cgnn_mass_assign_weighted_backward(const float* pos, const int32_t* q, const double* d_field, int64_t frames,
                                        int64_t n, int32_t channels, float box_size, int32_t mesh, int32_t order,
                                        double scale_pos, double scale_val, float* d_pos, float* d_val, void* stream) {
-    int rc = ma_weighted_refuses("cgnn_mass_assign_weighted_backward", !pos || !q || !d_field || (!d_pos && !d_val),
-                                 frames, n, channels, box_size, mesh, order, 2);
-    if (rc) return rc;
-    const float s = (float)mesh / box_size;
-    hipStream_t st = (hipStream_t)stream;
-    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (n <= 2^23: at least two frames)
-    const int64_t step = CGNN_PS_MAX_THREADS / n, cells = (int64_t)mesh * mesh * mesh;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t total = (frames - f0 < step ? frames - f0 : step) * n;
-        const unsigned blocks = (unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK);
-        const float* p = pos + f0 * n * 3;
-        const int32_t* w = q + f0 * n * channels;
-        const double* d = d_field + f0 * channels * cells;
-        float* gp = d_pos ? d_pos + f0 * n * 3 : nullptr;
-        float* gv = d_val ? d_val + f0 * n * channels : nullptr;
-        if (order == 2) ma_launch_weighted_gather<2>(channels, blocks, st, p, w, d, total, n, s, mesh, scale_pos, scale_val, gp, gv);
-        else ma_launch_weighted_gather<3>(channels, blocks, st, p, w, d, total, n, s, mesh, scale_pos, scale_val, gp, gv);
-    }
-    return check_hip(hipGetLastError(), "cgnn_mass_assign_weighted_backward");
+    const char* who = "cgnn_mass_assign_weighted_backward";
+    const int rc = ma_refuses(who, !pos || !q || !d_field || (!d_pos && !d_val), frames, n, true, channels, box_size, mesh,
+                              order, 2);
+    return rc ? rc : ma_gather(who, pos, q, d_field, frames, n, channels, box_size, mesh, order, scale_pos, scale_val,
+                               d_pos, d_val, stream);
 }
 
 int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int32_t* ids, void* stream) {
@@ -674,12 +583,10 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
                                                   pb_align256((size_t)blocks * CGNN_PB_SUMS * sizeof(double)));
     const int Mh = mesh / 2 + 1;
     pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
-    // whole frames per launch, at most CGNN_PS_MAX_THREADS threads each (at least 4 frames)
-    const int64_t step = CGNN_PS_MAX_THREADS / (per_frame * CGNN_BLOCK), modes_per_frame = (int64_t)mesh * mesh * Mh;
+    const int64_t modes_per_frame = (int64_t)mesh * mesh * Mh;
     const double2* a2 = reinterpret_cast<const double2*>(a);
     const double2* b2 = reinterpret_cast<const double2*>(b);
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t nf = frames - f0 < step ? frames - f0 : step;
+    ps_for_frame_batches(frames, per_frame * CGNN_BLOCK, [&](int64_t f0, int64_t nf) {       // at least 4 frames each
         pb_partial_kernel<<<(unsigned)(nf * per_frame), CGNN_BLOCK, 0, st>>>(
             a2 + f0 * modes_per_frame, b2 ? b2 + f0 * modes_per_frame : nullptr, mesh, Mh, modes_per_frame, perm, bin_start,
             num_bins, inv_w2, partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame);
@@ -687,7 +594,7 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
         pb_final_kernel<<<(unsigned)((outs + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
             partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame, nf, num_bins, b != nullptr,
             sums + f0 * CGNN_PB_SUMS * num_bins, reinterpret_cast<long long*>(modes) + f0 * num_bins);
-    }
+    });
     return check_hip(hipGetLastError(), "cgnn_power_bins");
 }
 

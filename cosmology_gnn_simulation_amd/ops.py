@@ -935,6 +935,26 @@ def _check_deposit(what: str, pos: torch.Tensor, box_size: float, mesh, order, o
     return mesh
 
 
+def _deposit_frames(pos: torch.Tensor):
+    """``pos`` (checked by :func:`_check_deposit`) as the kernels take it -> ``(pos, T, N, lead)``: float32, contiguous, on
+    the device; ``T`` frames of ``N`` particles; ``lead`` the leading shape of a mesh of it, ``(T,)`` for ``[T, N, 3]`` and
+    ``()`` for ``[N, 3]``."""
+    pos = f32c(pos, "pos")
+    if pos.dim() == 3:
+        return pos, pos.shape[0], pos.shape[1], (pos.shape[0],)
+    return pos, 1, pos.shape[0], ()
+
+
+def _mesh_gradient(what: str, name: str, d: torch.Tensor, shape: tuple, *others) -> torch.Tensor:
+    """The gradient with respect to a mesh as the gathers take it: float64 of ``shape`` on the device of ``others``
+    (``CgnnError``), contiguous."""
+    require_device(d, name)
+    if d.dtype != torch.float64 or tuple(d.shape) != shape:
+        raise CgnnError(f"{what}: {name} must be float64 {shape}, got {d.dtype} {tuple(d.shape)}")
+    _same_device(*others, d)
+    return d.contiguous()
+
+
 def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, check_bounds: bool = False) -> torch.Tensor:
     """Particles onto a periodic ``mesh^3`` grid in exact integers (``cgnn_mass_assign``): ``int64 [M, M, M]`` for ``pos
     [N, 3]``, ``int64 [T, M, M, M]`` for ``pos [T, N, 3]`` (all frames in one launch sequence, no host synchronisation).
@@ -949,16 +969,14 @@ def mass_assign(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2, c
     verifies nothing.  One box per call."""
     what = "mass_assign"
     mesh = _check_deposit(what, pos, box_size, mesh, order, (1, 2, 3))
-    pos = f32c(pos, "pos")
+    pos, t, n, lead = _deposit_frames(pos)
     if check_bounds and not bool(((pos >= 0) & (pos <= float(box_size))).all()):
         raise ValueError(f"{what}: pos leaves [0, box_size] or is not finite")
-    batched = pos.dim() == 3
-    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
-    out = torch.empty((t, mesh, mesh, mesh), dtype=torch.int64, device=pos.device)
+    out = torch.empty(lead + (mesh,) * 3, dtype=torch.int64, device=pos.device)
     with _timed(what, pos.device):
         check(_lib.load().cgnn_mass_assign(pos.data_ptr(), t, n, float(box_size), mesh, int(order), out.data_ptr(),
                                            stream_ptr(pos.device)), "cgnn_mass_assign")
-    return out if batched else out[0]
+    return out
 
 
 def mass_assign_backward(pos: torch.Tensor, d_mesh: torch.Tensor, box_size: float, mesh: int, order: int = 2,
@@ -974,15 +992,8 @@ def mass_assign_backward(pos: torch.Tensor, d_mesh: torch.Tensor, box_size: floa
     the other refusals of :func:`mass_assign`).  No host synchronisation."""
     what = "mass_assign_backward"
     mesh = _check_deposit(what, pos, box_size, mesh, order, (2, 3))
-    pos = f32c(pos, "pos")
-    batched = pos.dim() == 3
-    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
-    require_device(d_mesh, "d_mesh")
-    if d_mesh.dtype != torch.float64 or tuple(d_mesh.shape) != ((t,) if batched else ()) + (mesh,) * 3:
-        raise CgnnError(f"{what}: d_mesh must be float64 {((t,) if batched else ()) + (mesh,) * 3}, got {d_mesh.dtype} "
-                        f"{tuple(d_mesh.shape)}")
-    _same_device(pos, d_mesh)
-    d_mesh = d_mesh.contiguous()
+    pos, t, n, lead = _deposit_frames(pos)
+    d_mesh = _mesh_gradient(what, "d_mesh", d_mesh, lead + (mesh,) * 3, pos)
     out = torch.empty_like(pos)
     with _timed(what, pos.device):
         check(_lib.load().cgnn_mass_assign_backward(pos.data_ptr(), d_mesh.data_ptr(), t, n, float(box_size), mesh,
@@ -996,10 +1007,9 @@ class _DensityContrast(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pos, box_size, mesh, order):
-        grid = mass_assign(pos, box_size, mesh, order)
         ctx.args = (box_size, mesh, order)
         ctx.save_for_backward(pos)
-        return grid.to(torch.float64) * (mesh ** 3 / (pos.shape[-2] * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
+        return grid_contrast(mass_assign(pos, box_size, mesh, order), pos.shape[-2])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1008,6 +1018,12 @@ class _DensityContrast(torch.autograd.Function):
         box_size, mesh, order = ctx.args
         d_pos = mass_assign_backward(pos, d_delta, box_size, mesh, order, scale=mesh ** 3 / pos.shape[-2])
         return d_pos.to(pos.dtype), None, None, None
+
+
+def grid_contrast(grid: torch.Tensor, n: int) -> torch.Tensor:
+    """``delta = grid.double() * (M^3 / (n Q^3)) - 1`` of the integer mesh ``[..., M, M, M]`` that :func:`mass_assign` made
+    of ``n`` particles per frame: the one place the expression stands, so the one set of bits.  No gradient."""
+    return grid.to(torch.float64) * (grid.shape[-1] ** 3 / (n * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
 
 
 def density_contrast(pos: torch.Tensor, box_size: float, mesh: int, order: int = 2) -> torch.Tensor:
@@ -1101,18 +1117,16 @@ def mass_assign_weighted(pos: torch.Tensor, values: torch.Tensor, box_size: floa
             value_scale = _check_value_scale(value_scale, what)
         require_device(values, "values")
         q = quantize_weights(values, _max_abs_scale(values) if value_scale is None else value_scale)
-    pos = f32c(pos, "pos")
+    pos, t, n, lead = _deposit_frames(pos)
     q = i32c(q, "values")
     _same_device(pos, q)
-    batched = pos.dim() == 3
-    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
     c = q.shape[-1]
-    out = torch.empty((t, c, mesh, mesh, mesh), dtype=torch.int64, device=pos.device)
+    out = torch.empty(lead + (c,) + (mesh,) * 3, dtype=torch.int64, device=pos.device)
     with _timed(what, pos.device):
         check(_lib.load().cgnn_mass_assign_weighted(pos.data_ptr(), q.data_ptr(), t, n, c, float(box_size), mesh,
                                                     int(order), out.data_ptr(), stream_ptr(pos.device)),
               "cgnn_mass_assign_weighted")
-    return out if batched else out[0]
+    return out
 
 
 def mass_assign_weighted_backward(pos: torch.Tensor, q: torch.Tensor, d_field: torch.Tensor, box_size: float, mesh: int,
@@ -1132,17 +1146,10 @@ def mass_assign_weighted_backward(pos: torch.Tensor, q: torch.Tensor, d_field: t
         raise ValueError(f"{what}: q must be int32 quantised weights (ops.quantize_weights), got {q.dtype}")
     if not (want_pos or want_val):
         raise ValueError(f"{what}: nothing wanted")
-    pos = f32c(pos, "pos")
+    pos, t, n, lead = _deposit_frames(pos)
     q = i32c(q, "q")
-    batched = pos.dim() == 3
-    t, n = (pos.shape[0], pos.shape[1]) if batched else (1, pos.shape[0])
     c = q.shape[-1]
-    require_device(d_field, "d_field")
-    shape = ((t,) if batched else ()) + (c,) + (mesh,) * 3
-    if d_field.dtype != torch.float64 or tuple(d_field.shape) != shape:
-        raise CgnnError(f"{what}: d_field must be float64 {shape}, got {d_field.dtype} {tuple(d_field.shape)}")
-    _same_device(pos, q, d_field)
-    d_field = d_field.contiguous()
+    d_field = _mesh_gradient(what, "d_field", d_field, lead + (c,) + (mesh,) * 3, pos, q)
     d_pos = torch.empty_like(pos) if want_pos else None
     d_val = torch.empty(q.shape, dtype=torch.float32, device=pos.device) if want_val else None
     with _timed(what, pos.device):

@@ -182,6 +182,43 @@ def _frames3(pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
     return pos if pos.dim() == 3 else pos.unsqueeze(0)
 
 
+def _check_spectrum_arguments(what: str, box_size, mesh, k_edges, order):
+    mesh = ops.check_mesh(mesh, what)
+    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    return mesh, k_edges
+
+
+def _rollout_frames(rollout_data, ground_truth, frames, what: str, also=()):
+    """The selected predicted and true frames ``[F, N, 3]`` on the rollout's device, and their numbers.  ``also``: further
+    tensors on that device with one entry per frame; they bound the frames there are, and their selected entries
+    follow."""
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    tc = ground_truth["Coordinates"].to(dev)
+    avail = min(len(pc), len(tc), *(len(x) for x in also))
+    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
+    if not sel or min(sel) < 0 or max(sel) >= avail:
+        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
+    if pc.shape[1:] != tc.shape[1:]:
+        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
+    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
+    pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
+    _frames3(pc, "Coordinates", what)
+    return (pc, tc, sel) + tuple(x.index_select(0, idx) for x in also)
+
+
+def _contrast_modes(pos: torch.Tensor, box_size: float, mesh: int, order: int) -> torch.Tensor:
+    """``rfftn`` of the density contrast of every frame of ``pos [F, N, 3]``: complex128 ``[F, M, M, M/2 + 1]``."""
+    grid = ops.mass_assign(pos, box_size, mesh, order)
+    delta = ops.grid_contrast(grid, pos.shape[1])
+    del grid                    # the int64 mesh goes before the transform takes its memory
+    return torch.fft.rfftn(delta, dim=(-3, -2, -1))
+
+
 def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int):
     """``ops.power_bins`` of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b [F, N_b, 3]``):
     device tensors ``modes [F, nb]``, ``sums [F, 4, nb]``.  Frames go through in chunks whose meshes fit the free
@@ -194,27 +231,23 @@ def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: fl
         + nb * 64 * 5 * 8 + nb * 5 * 8
     chunk = max(1, min(n_frames, free_device_bytes(pos_a.device) // per_frame))
     plan = ops.PowerPlan.of(mesh, k_edges, pos_a.device)
-
-    def transform(pos):
-        grid = ops.mass_assign(pos, box_size, mesh, order)
-        delta = grid.to(torch.float64) * (mesh ** 3 / (pos.shape[1] * _lib.MASS_ASSIGN_Q ** 3)) - 1.0
-        del grid
-        return torch.fft.rfftn(delta, dim=(-3, -2, -1))
-
     modes, sums = [], []
     for f0 in range(0, n_frames, chunk):
-        a = transform(pos_a[f0:f0 + chunk])
-        b = None if pos_b is None else transform(pos_b[f0:f0 + chunk])
+        a = _contrast_modes(pos_a[f0:f0 + chunk], box_size, mesh, order)
+        b = None if pos_b is None else _contrast_modes(pos_b[f0:f0 + chunk], box_size, mesh, order)
         m, s = ops.power_bins(a, mesh, order, k_edges, b, plan)
         modes.append(m)
         sums.append(s)
     return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
 
 
-def _to_host(modes: torch.Tensor, sums: torch.Tensor):
-    """One transfer: the float64 sums travel as their bits among the integers."""
-    packed = torch.cat([modes.reshape(-1), sums.view(torch.int64).reshape(-1)]).cpu()
-    return packed[:modes.numel()].reshape(modes.shape), packed[modes.numel():].view(torch.float64).reshape(sums.shape)
+def _to_host(modes: torch.Tensor, sums: torch.Tensor, extra: Optional[torch.Tensor] = None):
+    """One transfer: the float64 sums, and the float64 ``extra`` if there is one, travel as their bits among the
+    integers -> ``(modes, sums)`` or ``(modes, sums, extra)`` on the CPU."""
+    parts = [modes, sums] if extra is None else [modes, sums, extra.contiguous()]
+    packed = torch.cat([p.view(torch.int64).reshape(-1) for p in parts]).cpu()
+    host = packed.split([p.numel() for p in parts])
+    return tuple(h.view(p.dtype).reshape(p.shape) for h, p in zip(host, parts))
 
 
 def power_spectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, pos_b: Optional[torch.Tensor] = None,
@@ -228,12 +261,7 @@ def power_spectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, 
     beyond the window deconvolution: bins past half the Nyquist frequency are lifted by it.  Everything is computed on
     the device of ``pos`` without a host synchronisation and comes back in one transfer."""
     what = "power_spectrum"
-    mesh = ops.check_mesh(mesh, what)
-    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
-    if isinstance(order, bool) or order not in (1, 2, 3):
-        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
-    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
-        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
     frames_a = _frames3(pos, "pos", what)
     frames_b = None if pos_b is None else _frames3(pos_b, "pos_b", what)
     if frames_b is not None and (pos_b.dim() != pos.dim() or frames_b.shape[0] != frames_a.shape[0]):
@@ -258,22 +286,8 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean`` (``[nb]``) and ``modes`` (``[nb]``, int64).  Everything is computed on
     the device of the rollout without a host synchronisation per frame; the results come back in one transfer."""
     what = "rollout_power_spectra"
-    mesh = ops.check_mesh(mesh, what)
-    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
-    if isinstance(order, bool) or order not in (1, 2, 3):
-        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
-    pc = rollout_data["Coordinates"]
-    dev = pc.device
-    tc = ground_truth["Coordinates"].to(dev)
-    avail = min(len(pc), len(tc))
-    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
-    if not sel or min(sel) < 0 or max(sel) >= avail:
-        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
-    if pc.shape[1:] != tc.shape[1:]:
-        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
-    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
-    pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
-    _frames3(pc, "Coordinates", what)
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
     n = pc.shape[1]
     modes, sums = _to_host(*_shell_sums(pc, tc, box_size, mesh, k_edges, order))
     sp = spectra_from_sums(modes, sums, n, n, box_size, mesh, k_edges, True)
@@ -289,16 +303,6 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
 # with the shell sums in the one transfer.  Sharded and batched variants, an owned-storage variant (``dist.
 # assemble_frames`` first), redshift-space quantities and an aliasing correction beyond the window deconvolution are
 # not built.
-
-def _check_spectrum_arguments(what: str, box_size, mesh, k_edges, order):
-    mesh = ops.check_mesh(mesh, what)
-    k_edges = ops.check_power_edges(default_k_edges(mesh) if k_edges is None else k_edges, what)
-    if isinstance(order, bool) or order not in (1, 2, 3):
-        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
-    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
-        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
-    return mesh, k_edges
-
 
 def _scalar_values(values: torch.Tensor, frames: torch.Tensor, pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
     """Scalar per-particle ``values`` (``[N]`` / ``[N, 1]`` for ``pos [N, 3]``, with a leading ``T`` for frames) -> ``[F, N]``."""
@@ -338,15 +342,6 @@ def _field_transform(pos: torch.Tensor, values: torch.Tensor, box_size: float, m
     return torch.fft.rfftn(field, dim=(-3, -2, -1)), shot
 
 
-def _to_host_with(modes: torch.Tensor, sums: torch.Tensor, extra: torch.Tensor):
-    """:func:`_to_host` with a float64 tensor of further values in the same transfer."""
-    packed = torch.cat([modes.reshape(-1), sums.view(torch.int64).reshape(-1),
-                        extra.contiguous().view(torch.int64).reshape(-1)]).cpu()
-    a, b = modes.numel(), modes.numel() + sums.numel()
-    return (packed[:a].reshape(modes.shape), packed[a:b].view(torch.float64).reshape(sums.shape),
-            packed[b:].view(torch.float64).reshape(extra.shape))
-
-
 def field_sums_on_device(pos, values, pos_b, values_b, box_size: float, mesh: int, k_edges, order: int, normalise: str):
     """The device part of :func:`field_power_spectrum` for ``pos [F, N, 3]``, ``values [F, N]`` (and the second set, or
     ``None``): device tensors ``modes [F, nb]``, ``sums [F, 4, nb]`` (``ops.power_bins``) and the shot noise of the two
@@ -383,8 +378,8 @@ def field_power_spectrum(pos: torch.Tensor, values: torch.Tensor, box_size: floa
         if pos_b.dim() != pos.dim() or frames_b.shape[0] != frames_a.shape[0]:
             raise ValueError(f"{what}: pos_b {tuple(pos_b.shape)} does not go with pos {tuple(pos.shape)}")
         val_b = _scalar_values(values_b, frames_b, pos_b, "values_b", what)
-    modes, sums, shot = _to_host_with(*field_sums_on_device(frames_a, val_a, frames_b, val_b, box_size, mesh, k_edges,
-                                                            order, normalise))
+    modes, sums, shot = _to_host(*field_sums_on_device(frames_a, val_a, frames_b, val_b, box_size, mesh, k_edges, order,
+                                                       normalise))
     single = pos.dim() == 2
     if single:
         modes, sums = modes[0], sums[0]
@@ -459,7 +454,7 @@ def momentum_power_spectrum(pos_prev: torch.Tensor, pos: torch.Tensor, dt: float
     prev = _frames3(pos_prev, "pos_prev", what)
     modes, total, div, k_sums, shot = momentum_sums_on_device(prev, frames, dt, box_size, mesh, k_edges, order)
     nan = torch.full_like(total, float("nan"))
-    modes, sums, shot = _to_host_with(modes, torch.stack([total, div, nan, k_sums], dim=1), shot)
+    modes, sums, shot = _to_host(modes, torch.stack([total, div, nan, k_sums], dim=1), shot)
     return _momentum_spectra(modes, sums, shot, box_size, mesh, k_edges, subtract_shot_noise, pos.dim() == 2)
 
 
@@ -503,28 +498,20 @@ def rollout_gas_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dic
         raise ValueError(f"{what}: dt must be positive and finite, got {dt!r}")
     pc = rollout_data["Coordinates"]
     dev = pc.device
-    tc = ground_truth["Coordinates"].to(dev)
+    truth = {"Coordinates": ground_truth["Coordinates"].to(dev)}       # moved once: the predecessors come from it too
     pe, te = rollout_data["InternalEnergy"].to(dev), ground_truth["InternalEnergy"].to(dev)
-    avail = min(len(pc), len(tc), len(pe), len(te))
-    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
-    if not sel or min(sel) < 0 or max(sel) >= avail:
-        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
-    if pc.shape[1:] != tc.shape[1:]:
-        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
-    _frames3(pc, "Coordinates", what)
-    n, nf = pc.shape[1], len(sel)
+    cp, ct, sel, ep, et = _rollout_frames(rollout_data, truth, frames, what, also=(pe, te))
+    n, nf = cp.shape[1], len(sel)
     if pe.numel() != len(pe) * n or te.numel() != len(te) * n:
         raise ValueError(f"{what}: InternalEnergy does not hold one value per particle and frame")
-    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
-    cp, ct = pc.index_select(0, idx), tc.index_select(0, idx)
-    ep, et = pe.index_select(0, idx).reshape(nf, n), te.index_select(0, idx).reshape(nf, n)
+    ep, et = ep.reshape(nf, n), et.reshape(nf, n)
     moving = None
     rows = [i for i, f in enumerate(sel) if f > 0]
     if dt is not None and rows:
         prev = torch.tensor([sel[i] - 1 for i in rows], dtype=torch.int64).to(dev)
         rows = torch.tensor(rows, dtype=torch.int64).to(dev)
-        moving = (rows, pc.index_select(0, prev), tc.index_select(0, prev))
-    modes, sums, extra = _to_host_with(*gas_sums_on_device(cp, ct, ep, et, box_size, mesh, k_edges, order, dt, moving))
+        moving = (rows, pc.index_select(0, prev), truth["Coordinates"].index_select(0, prev))
+    modes, sums, extra = _to_host(*gas_sums_on_device(cp, ct, ep, et, box_size, mesh, k_edges, order, dt, moving))
     return _gas_spectra(modes, sums, extra, sel, box_size, mesh, dt, k_edges)
 
 
@@ -535,18 +522,13 @@ def gas_sums_on_device(cp, ct, ep, et, box_size: float, mesh: int, k_edges, orde
     ``extra [2 or 4, F]`` (the shot noises).  ``moving``: ``None``, or ``(rows, prev_p, prev_t)``, the (device) indices of
     the selected frames that have a predecessor and those predecessors ``[len(rows), N, 3]``.  No host synchronisation."""
     dev = cp.device
-    n, nf, nb = cp.shape[1], cp.shape[0], len(k_edges) - 1
+    nf, nb = cp.shape[0], len(k_edges) - 1
     plan = ops.PowerPlan.of(mesh, k_edges, dev)
     fp, shot_p = _field_transform(cp, ep, box_size, mesh, order, "mean")
     ft, shot_t = _field_transform(ct, et, box_size, mesh, order, "mean")
-
-    def contrast(pos):
-        grid = ops.mass_assign(pos, box_size, mesh, order)
-        return torch.fft.rfftn(grid.to(torch.float64) * (mesh ** 3 / (n * _lib.MASS_ASSIGN_Q ** 3)) - 1.0, dim=(-3, -2, -1))
-
     modes, thermal = ops.power_bins(fp, mesh, order, k_edges, ft, plan)
-    _, with_p = ops.power_bins(fp, mesh, order, k_edges, contrast(cp), plan)
-    _, with_t = ops.power_bins(ft, mesh, order, k_edges, contrast(ct), plan)
+    _, with_p = ops.power_bins(fp, mesh, order, k_edges, _contrast_modes(cp, box_size, mesh, order), plan)
+    _, with_t = ops.power_bins(ft, mesh, order, k_edges, _contrast_modes(ct, box_size, mesh, order), plan)
     sums, extra = [thermal, with_p, with_t], [shot_p, shot_t]
     if moving is not None:
         rows, prev_p, prev_t = moving
@@ -699,23 +681,6 @@ def halo_mass_function(pos: torch.Tensor, box_size: float, linking_length: Optio
     return {"size_lo": edges[:-1].clone(), "size_hi": edges[1:].clone(), "counts": out[..., :nb].clone(),
             "n_groups": out[..., nb].clone(), "fraction_in_groups": out[..., nb + 1].to(torch.float64) / n,
             "largest": out[..., nb + 2].clone()}
-
-
-def _rollout_frames(rollout_data, ground_truth, frames, what: str):
-    """The selected predicted and true frames ``[F, N, 3]`` on the rollout's device, and their numbers."""
-    pc = rollout_data["Coordinates"]
-    dev = pc.device
-    tc = ground_truth["Coordinates"].to(dev)
-    avail = min(len(pc), len(tc))
-    sel = list(range(avail)) if frames is None else [int(f) for f in frames]
-    if not sel or min(sel) < 0 or max(sel) >= avail:
-        raise ValueError(f"{what}: frames must be numbers in [0, {avail}), got {sel}")
-    if pc.shape[1:] != tc.shape[1:]:
-        raise ValueError(f"{what}: predicted frames are {tuple(pc.shape[1:])}, true frames {tuple(tc.shape[1:])}")
-    idx = torch.tensor(sel, dtype=torch.int64).to(dev)
-    pc, tc = pc.index_select(0, idx), tc.index_select(0, idx)
-    _frames3(pc, "Coordinates", what)
-    return pc, tc, sel
 
 
 def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],

@@ -62,7 +62,7 @@ def mass_assign(pos, box_size, mesh, order):
 
 
 def density_contrast(grid, n):
-    """delta = grid (M^3 / (N Q^3)) - 1 in float64, the expression of statistics._shell_sums"""
+    """delta = grid (M^3 / (N Q^3)) - 1 in float64, the expression of ops.grid_contrast"""
     mesh = grid.shape[-1]
     return grid.astype(np.float64) * (mesh ** 3 / (n * Q ** 3)) - 1.0
 

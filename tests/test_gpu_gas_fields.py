@@ -130,6 +130,36 @@ def test_special_weights_and_the_kernels_own_clamp(order):
     _same_deposit(x, q, BOX, 9, order)
 
 
+def _unit_weight_frames(mesh):
+    """[2, 1000, 3] on the device: uniform positions with the special ones among them, and a second uniform frame"""
+    x = np.stack([psc.with_special_positions(psc.uniform(1000, 20 + mesh, BOX), BOX), psc.uniform(1000, 21 + mesh, BOX)])
+    return _dev(x), torch.full((2, 1000), ONE, dtype=torch.int32, device=DEV)
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("mesh", [5, 2])
+def test_unit_weights_give_the_plain_deposits_bits(mesh, order):
+    """The plain deposit is the weighted one at q = 2^20: (v 2^20 + 2^19) >> 20 = v for 0 <= v <= 2^39.  Mesh 5 wraps
+    on every axis, on mesh 2 every stencil wraps onto itself."""
+    pos, one = _unit_weight_frames(mesh)
+    assert torch.equal(ops.mass_assign_weighted(pos[0], one[0], BOX, mesh, order)[0], ops.mass_assign(pos[0], BOX, mesh, order))
+    assert torch.equal(ops.mass_assign_weighted(pos, one, BOX, mesh, order)[:, 0], ops.mass_assign(pos, BOX, mesh, order))
+
+
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("mesh", [5, 2])
+def test_unit_weights_give_the_plain_gathers_bits(mesh, order):
+    """The plain gather is the weighted one with one channel of a = 1.0: 0.0 + 1.0 g = g, then the same fl32((g s)
+    scale), here with a scale that is no power of two."""
+    pos, one = _unit_weight_frames(mesh)
+    d_mesh = _dev(_normal((2, mesh, mesh, mesh), 30 + mesh))
+    s = mesh ** 3 / 1000
+    got = ops.mass_assign_weighted_backward(pos[0], one[0], d_mesh[0][None], BOX, mesh, order, scale_pos=s, want_val=False)
+    assert got[1] is None and torch.equal(got[0], ops.mass_assign_backward(pos[0], d_mesh[0], BOX, mesh, order, scale=s))
+    got = ops.mass_assign_weighted_backward(pos, one, d_mesh[:, None], BOX, mesh, order, scale_pos=s, want_val=False)
+    assert torch.equal(got[0], ops.mass_assign_backward(pos, d_mesh, BOX, mesh, order, scale=s))
+
+
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_4096_particles_in_one_cell_with_mixed_signs(order):
     """Many atomics on few addresses, positive and negative contributions cancelling in two's complement."""
