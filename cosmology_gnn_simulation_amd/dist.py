@@ -1180,6 +1180,18 @@ def rollout_capacity(owner: torch.Tensor, world: int) -> Tuple[List[int], int]:
     return counts, max(counts)
 
 
+def _step_capacity(sh: Shard, world: int) -> Tuple[List[int], int]:
+    """``(owned count of every rank, cap)`` of a step's shard: the common send-block size is the largest owned count,
+    known on every rank from the replicated owner map without a collective."""
+    if sh._counts is not None:      # the balanced plan on the device: cgnn_tile_classify counted every rank's rows
+        counts = sh._counts.tolist()
+    else:
+        counts, _ = rollout_capacity(sh._owner, world)
+    if counts[sh.rank] != sh.n_owned:
+        raise CgnnError(f"rank {sh.rank}: {sh.n_owned} owned particles, the owner map says {counts[sh.rank]}")
+    return counts, max(counts)
+
+
 def window_checksum(coords_w: torch.Tensor, energy_w: torch.Tensor) -> torch.Tensor:
     """float64 [4] fingerprint of an initial window (plain and position-weighted sums, frame by frame), computed on the
     window's own device; non-finite sums are mapped to fixed values so that equal data compare equal."""
@@ -1280,13 +1292,7 @@ class ShardedRollout:
                             f"or a diverged model)")
         sh = build_shard(recent, self.box, self.k, self.world, self.rank, decomposition=self.decomposition,
                          knn_grid=self.knn_grid, min_image_edge_attr=self.min_image_edge_attr)
-        if sh._counts is not None:      # the balanced plan on the device: cgnn_tile_classify counted every rank's rows
-            self.counts = sh._counts.tolist()
-            self.cap = max(self.counts)
-        else:
-            self.counts, self.cap = rollout_capacity(sh._owner, self.world)
-        if self.counts[self.rank] != sh.n_owned:
-            raise CgnnError(f"rank {self.rank}: {sh.n_owned} owned particles, the owner map says {self.counts[self.rank]}")
+        self.counts, self.cap = _step_capacity(sh, self.world)
         return sh
 
     def features(self, sh: Shard, t: int) -> torch.Tensor:
@@ -1936,7 +1942,7 @@ def publish_frame(new_pos: torch.Tensor, new_temp: torch.Tensor, ids: torch.Tens
     """The publish link on its own: the rows ``new_pos [R, 3]`` / ``new_temp [R]`` of the particles ``ids`` a rank
     integrated -> ``(pos [N, 3], temp [N])`` of all particles on every rank, differentiable in the rows.  ``cap``: the
     common block size (at least every rank's row count); ``block``: the packed rows when ``cgnn_rollout_integrate``
-    made them already (``training._IntegrateRowsLink``), else they are packed here."""
+    made them already (``training._IntegrateLink``), else they are packed here."""
     r = ids.numel()
     if block is None:
         block = torch.zeros((int(cap), _lib.ROLLOUT_ROW), dtype=torch.float32, device=new_pos.device)
@@ -1979,26 +1985,15 @@ def sharded_unrolled_training_bytes(n_owned: int, n_ghost: int, num_particles: i
     return 4 * (S * per_step + scratch + frames)
 
 
-def _step_capacity(sh: Shard, world: int) -> int:
-    """The common send-block size of a step (``ShardedRollout.plan``): the largest owned count over the ranks, known on
-    every rank from the replicated owner map without a collective."""
-    if sh._counts is not None:
-        counts = sh._counts.tolist()
-    else:
-        counts, _ = rollout_capacity(sh._owner, world)
-    if counts[sh.rank] != sh.n_owned:
-        raise CgnnError(f"rank {sh.rank}: {sh.n_owned} owned particles, the owner map says {counts[sh.rank]}")
-    return max(counts)
-
-
 class _ShardedUnroll(training._Unroll):
     """``training._Unroll`` on one rank of :func:`sharded_unrolled_loss`: the same loop and checkpoint Function, with the
-    step of a rank.  :meth:`plan` builds the step's shard; :meth:`step` is the step behind the shard build -- the samples
-    of the owned (and ghost) rows, :class:`ShardedTraining` with its halo exchanges, :func:`sharded_training_loss` with
-    its all-reduces, the integration of the owned rows -- written once for the plain step, the first run of a checkpointed
-    step (no autograd), its recomputation on the kept shard, and the last step; :meth:`publish` gathers the rows into the
-    next frame.  Whatever a rank holds, a step issues the same collectives in the same order: a rank that owns nothing
-    runs it on empty blocks.  ``sample0(rows, want, targets=True)`` samples rows of the true window with step 0's noise."""
+    step over the rows of a rank.  :meth:`plan` builds the step's shard; ``step`` then samples and integrates the owned
+    rows (:meth:`_rows`) around :meth:`_predict` -- the sample of the ghost rows, :class:`ShardedTraining` with its halo
+    exchanges, :func:`sharded_training_loss` with its all-reduces -- in each of its four uses (the plain step, the first
+    run of a checkpointed step, its recomputation on the kept shard, the last step); :meth:`publish` gathers the rows
+    into the next frame.  Whatever a rank holds, a step issues the same collectives in the same order: a rank that owns
+    nothing runs it on empty blocks.  ``sample0(rows, want, targets=True)`` samples rows of the true window with step 0's
+    noise."""
 
     def __init__(self, model, cfg, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0, group, knn_grid: str,
                  min_image: bool, decomposition: str):
@@ -2023,7 +2018,7 @@ class _ShardedUnroll(training._Unroll):
             sh = build_shard(recent_all, cfg.box, self.k, self.world, self.rank, decomposition=self.decomposition,
                              knn_grid=self.knn_grid, min_image_edge_attr=self.min_image, row_order="spatial")
             sh = exchange_requests(sh, self.group) if self.distributed else finish_shard(sh, sh.want_global)
-            rec.shard, rec.cap = sh, _step_capacity(sh, self.world)
+            rec.shard, rec.cap = sh, _step_capacity(sh, self.world)[1]
         sh._g2l = sh._owner = None      # the whole-box maps have served (send plan, capacity): not part of the record
         if s == 0:      # one all-reduce (max) of a flag
             need = sharded_unrolled_training_bytes(sh.n_owned, sh.n_ghost, self.n, self.k, self.w, model._latent_size,
@@ -2037,44 +2032,28 @@ class _ShardedUnroll(training._Unroll):
                                 f"rows of {self.n} particles, {self.k} neighbours, latent {model._latent_size}, "
                                 f"{len(model.processor)} rounds; {free / 2**30:.2f} GiB are free)")
 
-    def step(self, rec, tgt_p, tgt_t, frames, kept: bool = False, integrate: bool = True):
-        """-> (this rank's weighted loss term, rows_pos | None, rows_temp | None, block | None) on ``rec.shard``, kept or
-        not; fills ``rec.value`` and ``rec.terms`` (the global figures).  ``frames``: the W whole position frames, then
-        the W temperature frames."""
-        cfg, w, n, k, sh = self.cfg, self.w, self.n, self.k, rec.shard
-        grad = torch.is_grad_enabled()
-        own, ghosts = sh.owned_global, sh.ghost_global
-        want = ("x", "recent_pos", "y_acc", "y_temp_rate")
-        if rec.s == 0:      # in a recomputation the counter-based noise again: the same (seed, draw), the same sample
-            s0 = self.sample0(own, want)
-            x, recent, y_acc, y_tr = (s0[name] for name in want)
-        else:
-            x, recent, y_acc, y_tr = training._SampleRowsLink.apply(cfg, own, want, tgt_p, tgt_t, *frames)
+    def _rows(self, rec):
+        return rec.shard.owned_global
+
+    def _predict(self, rec, x, recent, y_acc, y_tr, frames, kept: bool):
+        """On ``rec.shard``, kept or not: -> (acceleration, temp_rate, this rank's loss term) of the owned rows; fills
+        ``rec.value`` and ``rec.terms`` (the global figures)."""
+        cfg, sh = self.cfg, rec.shard
         runner = ShardedTraining(self.model, sh, None if self.distributed else _LocalHalo(), self.group)
         if self.edge:       # the shard's edge features as a function of the local rows [owned | ghosts]
             if rec.s == 0:
-                recent_g = self.sample0(ghosts, ("recent_pos",), targets=False)["recent_pos"]
+                recent_g = self.sample0(sh.ghost_global, ("recent_pos",), targets=False)["recent_pos"]
             else:
-                recent_g, = training._SampleRowsLink.apply(cfg, ghosts, ("recent_pos",), None, None, *frames)
-            edge_attr = training._EdgeAttrRowsLink.apply(torch.cat([recent, recent_g]), sh.edge_attr, sh.src_local, k,
-                                                         sh.n_owned, lambda runner=runner: runner._csr)
+                recent_g, = training._SampleLink.apply(cfg, sh.ghost_global, ("recent_pos",), None, None, *frames)
+            edge_attr = training._EdgeAttrLink.apply(torch.cat([recent, recent_g]), sh.edge_attr, sh.src_local, self.k,
+                                                     sh.n_owned, lambda runner=runner: runner._csr)
             pred = runner(x, edge_attr)
         else:
             pred = runner(x)
-        acc, rate = pred["acceleration"], pred["temp_rate"]
-        loss_s, rec.value, terms = sharded_training_loss(pred, y_acc, y_tr.reshape(-1, 1), n, cfg.dt, *self.loss_weights,
-                                                         self.group, terms=True)
+        loss_s, rec.value, terms = sharded_training_loss(pred, y_acc, y_tr.reshape(-1, 1), self.n, cfg.dt,
+                                                         *self.loss_weights, self.group, terms=True)
         rec.terms = terms.to(torch.float32)
-        rows_p = rows_t = block = None
-        if integrate:
-            frames_in = (frames[w - 2], frames[w - 1], frames[2 * w - 1])
-            if rec.live and grad:
-                rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, rec.cap, acc, rate, *frames_in)
-            else:
-                with torch.no_grad():
-                    rows_p, rows_t, block = training._IntegrateRowsLink.apply(cfg, own, rec.cap, acc.detach(), rate.detach(),
-                                                                              *(f.detach() for f in frames_in))
-        return rec.weight * loss_s, rows_p, rows_t, block
+        return pred["acceleration"], pred["temp_rate"], loss_s
 
     def publish(self, rec, rows_p, rows_t, block):
         """One all-gather of the ranks' blocks into the next frame of all particles, outside the checkpoint Function: the
@@ -2158,13 +2137,7 @@ def sharded_unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: to
     cfg = training._LinkConfig(metadata, dt, box_size, n, device)
     pos_w, tmp_w, tgt_p, tgt_t = training._device_window(position_seq, temperature_seq, target_positions,
                                                          target_temperatures, device)
-    seed = (torch.initial_seed() if noise_seed is None else int(noise_seed)) % 2 ** 64
-    std = float(noise_std)
-
-    def sample0(rows, want, targets=True):      # step 0: the counter-based noise is a function of the particle id
-        return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, std, seed, noise_draw,
-                                   tgt_p[0] if targets else None, tgt_t[0] if targets else None, rows, want,
-                                   stats=cfg.stats)
+    sample0 = training._step0_sampler(cfg, pos_w, tmp_w, tgt_p[0], tgt_t[0], noise_std, noise_seed, noise_draw)
     unroll = _ShardedUnroll(model, cfg, w, n, int(num_neighbors), (acc_loss_weight, temp_rate_loss_weight,
                             momentum_loss_weight), checkpoint, sample0, group, knn_grid, min_image_edge_attr, decomposition)
     # the noise is replicated, like the frames, and not kept beyond the window

@@ -1780,26 +1780,11 @@ def rollout_integrate_backward(d_new_pos: Optional[torch.Tensor], d_new_temp: Op
 
 def edge_attr_backward(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, senders: torch.Tensor, k: int,
                        by_sender: "SenderCsr") -> torch.Tensor:
-    """``d_pos [N, 3]`` from the gradient of the k-NN's edge features (``cgnn_edge_attr_backward``): ``edge_attr [N k, 4]``
-    as :func:`knn_periodic` made it (either ``min_image_edge_attr`` mode), ``senders`` its int32 sender list,
-    ``by_sender = SenderCsr(senders, None, N)``.  Fixed summation order, no atomics."""
-    what = "edge_attr_backward"
-    d_edge_attr, edge_attr = f32c(d_edge_attr, "d_edge_attr"), f32c(edge_attr, "edge_attr")
-    senders = i32c(senders, "senders").reshape(-1)
-    k, n = int(k), int(by_sender.rows)
-    if k < 1 or edge_attr.shape != (n * k, 4) or d_edge_attr.shape != (n * k, 4) or senders.numel() != n * k:
-        raise CgnnError(f"{what}: edge_attr / d_edge_attr must be [{n} * {k}, 4] with as many senders, got "
-                        f"{tuple(edge_attr.shape)}, {tuple(d_edge_attr.shape)}, {senders.numel()} senders")
-    if by_sender.col.numel() < n * k:
-        raise CgnnError(f"{what}: the CSR holds {by_sender.col.numel()} edges, the list {n * k}")
-    _same_device(d_edge_attr, edge_attr, senders, by_sender.row_ptr, by_sender.col)
-    d_pos = torch.empty((n, 3), dtype=torch.float32, device=edge_attr.device)
-    with _timed(what, edge_attr.device):
-        check(_lib.load().cgnn_edge_attr_backward(d_edge_attr.data_ptr(), edge_attr.data_ptr(), senders.data_ptr(), n, k,
-                                                  by_sender.row_ptr.data_ptr(), by_sender.col.data_ptr(),
-                                                  d_pos.data_ptr(), stream_ptr(edge_attr.device)),
-              "cgnn_edge_attr_backward")
-    return d_pos
+    """``d_pos [N, 3]`` from the gradient of the k-NN's edge features: ``edge_attr [N k, 4]`` as :func:`knn_periodic`
+    made it (either ``min_image_edge_attr`` mode), ``senders`` its int32 sender list, ``by_sender = SenderCsr(senders,
+    None, N)``.  Fixed summation order, no atomics.  :func:`edge_attr_backward_rows` with every position row a receiver
+    (what ``cgnn_edge_attr_backward`` is on the C side), under its own name in messages and timings."""
+    return _edge_attr_backward("edge_attr_backward", d_edge_attr, edge_attr, senders, k, by_sender.rows, by_sender)
 
 
 def edge_attr_backward_rows(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, senders: torch.Tensor, k: int,
@@ -1809,7 +1794,10 @@ def edge_attr_backward_rows(d_edge_attr: torch.Tensor, edge_attr: torch.Tensor, 
     ghosts]``, ``by_sender = SenderCsr(senders, None, n_pos)``.  -> ``d_pos [n_pos, 3]``: a row below ``n_recv`` receives
     minus the sum of its own ``k`` edges plus the edges it sends, a row from ``n_recv`` on only the edges it sends.
     ``n_pos == n_recv`` gives :func:`edge_attr_backward`'s bits.  Zero rows launch nothing."""
-    what = "edge_attr_backward_rows"
+    return _edge_attr_backward("edge_attr_backward_rows", d_edge_attr, edge_attr, senders, k, n_recv, by_sender)
+
+
+def _edge_attr_backward(what: str, d_edge_attr, edge_attr, senders, k, n_recv, by_sender) -> torch.Tensor:
     d_edge_attr, edge_attr = f32c(d_edge_attr, "d_edge_attr"), f32c(edge_attr, "edge_attr")
     senders = i32c(senders, "senders").reshape(-1)
     k, nr, n = int(k), int(n_recv), int(by_sender.rows)

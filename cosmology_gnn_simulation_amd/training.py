@@ -29,6 +29,7 @@ Each mode's step is written once, as pieces over the rows a runner holds (:class
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -647,11 +648,10 @@ class _LinkConfig:
     def graph_lists(self, recent, edge: bool, k: int, knn_grid: str, min_image: bool):
         """-> (edge_attr, senders, order) of the step graph on the last frame ``recent``; the edge features carry
         gradient only where the model reads them (``edge``)."""
-        src = recent if edge else recent.detach()
+        edge_attr, senders = _KnnEdgeAttr.apply(recent if edge else recent.detach(), self.offsets, self.box, k, knn_grid,
+                                                min_image)
         if self.offsets is None:
-            edge_attr, senders = _KnnEdgeAttr.apply(src, self.box, k, knn_grid, min_image)
             return edge_attr, senders, spatial_order(recent, self.box)
-        edge_attr, senders = _KnnEdgeAttrBatched.apply(src, self.offsets, self.box, k, knn_grid, min_image)
         return edge_attr, senders, spatial_order_batched(recent, self.offsets, self.box, rows=self.order_rows)
 
     def graph(self, x, edge_index, edge_attr, y_acc, y_tr, recent, order, k: int):
@@ -665,75 +665,80 @@ class _LinkConfig:
         return graph
 
 
+SAMPLE_OUTPUTS = ("x", "recent_pos", "y_acc", "y_temp_rate")
+
+
 class _SampleLink(torch.autograd.Function):
-    """``(x, recent_pos, y_acc, y_temp_rate) = cgnn_training_sample(window)`` without noise, the window given as W position
-    frames ``[N, 3]`` followed by W temperature frames ``[N]``; the targets are constants.  The backward
-    (``cgnn_training_sample_backward``) writes the frames from the first one that requires a gradient on."""
+    """``cgnn_training_sample(window)`` without noise, the window given as W whole position frames ``[N, 3]`` followed by W
+    temperature frames ``[N]``; the targets are constants.  ``rows``: ``None`` for all rows, or the particles (int64 ids)
+    a rank holds, output row i then belonging to particle ``rows[i]``.  ``want``: the outputs to make, in this order
+    (``None``: :data:`SAMPLE_OUTPUTS`).  The backward (``cgnn_training_sample_backward``) writes the frames from the
+    first one that requires a gradient on; a row list's compact gradients then go back into whole-frame gradients, zero
+    elsewhere (``cgnn_rows_to_frames``), which the publish link (``dist._PublishLink``) sums over the ranks.  Zero rows
+    launch nothing and still return (zero) frame gradients: a rank that owns nothing keeps the autograd structure of
+    every other rank."""
 
     @staticmethod
-    def forward(ctx, cfg: _LinkConfig, target_pos, target_temp, *frames):
+    def forward(ctx, cfg: _LinkConfig, rows, want, target_pos, target_temp, *frames):
         w = len(frames) // 2
+        want = SAMPLE_OUTPUTS if want is None else tuple(want)
         pos_w, tmp_w = torch.stack(frames[:w]), torch.stack(frames[w:])
-        s = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, 0.0, 0, 0, target_pos, target_temp,
+        s = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, 0.0, 0, 0, target_pos, target_temp, rows, want,
                                 stats=cfg.stats)
-        ctx.cfg, ctx.w, ctx.n = cfg, w, pos_w.shape[1]
+        ctx.cfg, ctx.w, ctx.n, ctx.rows, ctx.want = cfg, w, pos_w.shape[1], rows, want
         ctx.set_materialize_grads(False)
-        return s["x"], s["recent_pos"], s["y_acc"], s["y_temp_rate"]
+        return tuple(s[name] for name in want)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, d_x, d_recent, d_y_acc, d_y_tr):
-        w, cfg = ctx.w, ctx.cfg
-        needs = ctx.needs_input_grad[3:]
+    def backward(ctx, *d_out):
+        w, n, cfg, rows = ctx.w, ctx.n, ctx.cfg, ctx.rows
+        needs = ctx.needs_input_grad[5:]
         first = min(t % w for t in range(2 * w) if needs[t])
-        if d_x is None and d_recent is None and d_y_acc is None and d_y_tr is None:
-            return (None,) * (3 + 2 * w)
-        d_pos, d_temp = ops.training_sample_backward(w, ctx.n, cfg.meta, cfg.dt, cfg.box, d_x=d_x, d_recent_pos=d_recent,
-                                                     d_y_acc=d_y_acc, d_y_temp_rate=d_y_tr, first_frame=first,
-                                                     stats=cfg.stats)
-        return (None, None, None, *(d_pos[t] if needs[t] else None for t in range(w)),
-                *(d_temp[t] if needs[w + t] else None for t in range(w)))
+        g = dict(zip(ctx.want, d_out))
+        if all(d is None for d in d_out):
+            return (None,) * (5 + 2 * w)
+        d_pos, d_temp = ops.training_sample_backward(w, n if rows is None else rows.numel(), cfg.meta, cfg.dt, cfg.box,
+                                                     d_x=g.get("x"), d_recent_pos=g.get("recent_pos"),
+                                                     d_y_acc=g.get("y_acc"), d_y_temp_rate=g.get("y_temp_rate"), rows=rows,
+                                                     n_total=n, first_frame=first, stats=cfg.stats)
+        d_pos, d_temp = d_pos[first:], d_temp[first:]
+        if rows is not None:
+            d_pos, d_temp = ops.rows_to_frames(rows, n, d_pos, d_temp)
+        return (None,) * 5 + tuple(d_pos[t - first] if needs[t] else None for t in range(w)) + \
+            tuple(d_temp[t - first] if needs[w + t] else None for t in range(w))
 
 
 def _edge_attr_grad(ctx, d_edge_attr):
-    """The backward the edge-feature Functions share: d ``recent`` from d ``edge_attr`` (``cgnn_edge_attr_backward``) on
-    the ``(edge_attr, senders)`` the forward saved with ``ctx.k`` / ``ctx.n``; ``None`` when no gradient arrived."""
+    """The backward the edge-feature Functions share: d position rows from d ``edge_attr`` on the ``(edge_attr, senders)``
+    the forward saved with ``ctx.k``, ``ctx.n_recv`` and ``ctx.by_sender`` (a callable that gives the sender-major edge
+    CSR, so that a call nobody differentiates pays nothing for it); ``None`` when no gradient arrived.  ``n_recv``:
+    ``None`` where every position row is a receiver (``cgnn_edge_attr_backward``), else the receivers of a shard's local
+    rows ``[owned | ghosts]`` (``cgnn_edge_attr_backward_rows``)."""
     if d_edge_attr is None:
         return None
     edge_attr, senders = ctx.saved_tensors
-    return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, ops.SenderCsr(senders, None, ctx.n))
+    if ctx.n_recv is None:
+        return ops.edge_attr_backward(d_edge_attr, edge_attr, senders, ctx.k, ctx.by_sender())
+    return ops.edge_attr_backward_rows(d_edge_attr, edge_attr, senders, ctx.k, ctx.n_recv, ctx.by_sender())
 
 
 class _KnnEdgeAttr(torch.autograd.Function):
     """``(edge_attr, senders) = ops.knn_periodic(recent)``: the graph build, differentiable in its edge features
-    (``cgnn_edge_attr_backward``; the senders are discrete).  The sender-major edge CSR is built in the backward, so a
-    call nobody differentiates (``message_source="x_j"``) pays nothing for it."""
-
-    @staticmethod
-    def forward(ctx, recent, box: float, k: int, grid: str, min_image: bool):
-        senders, edge_attr, _ = ops.knn_periodic(recent, box, k, None, True, False, min_image_edge_attr=min_image,
-                                                 grid=grid)
-        ctx.k, ctx.n = k, recent.shape[0]
-        ctx.save_for_backward(edge_attr, senders)
-        ctx.mark_non_differentiable(senders)
-        ctx.set_materialize_grads(False)
-        return edge_attr, senders
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_edge_attr, _d_senders):
-        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 4
-
-
-class _KnnEdgeAttrBatched(torch.autograd.Function):
-    """:class:`_KnnEdgeAttr` over a batch of simulations (``ops.knn_periodic_batched`` on ``offsets``).  The senders are
-    global rows and never leave their graph, so the backward is the single graph's on all rows."""
+    (:func:`_edge_attr_grad`; the senders are discrete).  ``offsets``: ``None`` for one graph, else the row offsets of a
+    batch of simulations (``ops.knn_periodic_batched``); there the senders are global rows and never leave their graph,
+    so the backward is the single graph's on all rows."""
 
     @staticmethod
     def forward(ctx, recent, offsets, box: float, k: int, grid: str, min_image: bool):
-        senders, edge_attr, _ = ops.knn_periodic_batched(recent, offsets, box, k, True, False,
-                                                         min_image_edge_attr=min_image, grid=grid)
-        ctx.k, ctx.n = k, recent.shape[0]
+        if offsets is None:
+            senders, edge_attr, _ = ops.knn_periodic(recent, box, k, None, True, False, min_image_edge_attr=min_image,
+                                                     grid=grid)
+        else:
+            senders, edge_attr, _ = ops.knn_periodic_batched(recent, offsets, box, k, True, False,
+                                                             min_image_edge_attr=min_image, grid=grid)
+        ctx.k, ctx.n_recv = k, None
+        ctx.by_sender = functools.partial(ops.SenderCsr, senders, None, recent.shape[0])
         ctx.save_for_backward(edge_attr, senders)
         ctx.mark_non_differentiable(senders)
         ctx.set_materialize_grads(False)
@@ -742,6 +747,29 @@ class _KnnEdgeAttrBatched(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_edge_attr, _d_senders):
+        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 5
+
+
+class _EdgeAttrLink(torch.autograd.Function):
+    """Edge features an earlier search made, handed on as a differentiable function of the position rows ``pos [n_pos,
+    3]`` (:func:`_edge_attr_grad` on the kept ``senders``); no second search.  Two callers.  The recomputation of a
+    checkpointed step: the kept lists of the first run, ``n_recv=None`` (all rows of ``recent``), ``by_sender`` building
+    ``ops.SenderCsr(senders, None, n)`` in the backward.  A shard: the features of its neighbour search (the global
+    graph's rows) over its local rows ``[owned | ghosts]``, ``n_recv`` the owned count, ``by_sender`` returning the CSR
+    the shard's training runner keeps."""
+
+    @staticmethod
+    def forward(ctx, pos, edge_attr, senders, k: int, n_recv: Optional[int], by_sender):
+        ctx.k, ctx.n_recv, ctx.n_pos, ctx.by_sender = int(k), n_recv, pos.shape[0], by_sender
+        ctx.save_for_backward(edge_attr, senders)
+        ctx.set_materialize_grads(False)
+        return edge_attr.view_as(edge_attr)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_edge_attr):
+        if d_edge_attr is not None and ctx.n_pos == 0:      # a rank that holds nothing: no runner CSR to ask for
+            return (d_edge_attr.new_zeros((0, 3)),) + (None,) * 5
         return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 5
 
 
@@ -760,9 +788,7 @@ def spatial_order(pos: torch.Tensor, box: float, per_cell: int = 8) -> torch.Ten
     the particles of a cell differently, and the engine's float32 sums over rows then differ in their last bits; an
     unrolled step builds its graphs inside the call and has to give the same bits twice.  Index bookkeeping (a few
     integer element-wise kernels and one stable sort per graph), no host synchronisation."""
-    n = pos.shape[0]
-    bits = max(0, min(10, int(math.log2(max(n / per_cell, 1.0)) / 3)))
-    g = 1 << bits
+    g = _spatial_order_cells(pos.shape[0], per_cell)
     c = _spread3((pos.detach() * (g / float(box))).floor_().clamp_(0, g - 1).to(torch.int64))
     key = (c[:, 0] << 2) | (c[:, 1] << 1) | c[:, 2]
     return torch.argsort(key, stable=True).to(torch.int32)
@@ -801,108 +827,18 @@ def spatial_order_batched(pos: torch.Tensor, offsets: Sequence[int], box: float,
 
 
 class _IntegrateLink(torch.autograd.Function):
-    """``(new_pos, new_temp) = one_step.integrate_one_step`` through ``cgnn_rollout_integrate`` (its bits), with
-    ``cgnn_rollout_integrate_backward`` behind it."""
+    """``one_step.integrate_one_step`` through ``cgnn_rollout_integrate`` (its bits), with
+    ``cgnn_rollout_integrate_backward`` behind it: -> ``(new_pos [R, 3], new_temp [R], block)`` from predictions of R rows
+    and the whole frames ``p2`` / ``p1`` ``[N, 3]`` and ``t1 [N]``.  ``ids``: ``None`` for all rows (``cfg.ids``), or the
+    particles a rank holds (predictions row i = particle ``ids[i]``); the frames' gradients of those rows then go back
+    into whole frames, zero elsewhere (``cgnn_rows_to_frames``).  ``block [n_out, ROLLOUT_ROW]`` is the packed output of
+    the kernel itself (what the ranks gather; not differentiable -- the two row tensors are its differentiable view)."""
 
     @staticmethod
-    def forward(ctx, cfg: _LinkConfig, acc_pred, rate_pred, p2, p1, t1):
-        out = ops.rollout_integrate(acc_pred, rate_pred, p2, p1, t1, cfg.ids, cfg.meta, stats=cfg.stats)
-        ctx.cfg = cfg
-        ctx.shapes = (rate_pred.shape, t1.shape)
-        ctx.set_materialize_grads(False)
-        return out[:, :3].contiguous(), out[:, 3].contiguous()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_new_pos, d_new_temp):
-        names = ("acc_pred", "temp_rate_pred", "p2", "p1", "t1")
-        want = [name for name, need in zip(names, ctx.needs_input_grad[1:]) if need]
-        if (d_new_pos is None and d_new_temp is None) or not want:
-            return (None,) * 6
-        g = ops.rollout_integrate_backward(d_new_pos, d_new_temp, ctx.cfg.meta, want, stats=ctx.cfg.stats)
-        if "temp_rate_pred" in g:
-            g["temp_rate_pred"] = g["temp_rate_pred"].view(ctx.shapes[0])
-        if "t1" in g:
-            g["t1"] = g["t1"].view(ctx.shapes[1])
-        return (None, *(g.get(name) for name in names))
-
-
-# ---- the same links over the rows one rank holds (dist.sharded_unrolled_loss) ---------------------------------------------
-#
-# Frames are whole ([N, 3] / [N], replicated on every rank); a rank samples and integrates the rows it owns.  The forward
-# kernels take a row list already; the backward puts the rows' gradients back into whole-frame gradients, zero elsewhere
-# (``cgnn_rows_to_frames``), which the publish link (dist._PublishLink) sums over the ranks.  Zero rows launch nothing and
-# still return (zero) frame gradients: a rank that owns nothing keeps the autograd structure of every other rank.
-
-class _SampleRowsLink(torch.autograd.Function):
-    """:class:`_SampleLink` for the particles ``rows`` (int64 ids) of whole frames: the outputs named in ``want`` (of
-    ``x``, ``recent_pos``, ``y_acc``, ``y_temp_rate``), row i belonging to particle ``rows[i]``.  The backward is
-    ``cgnn_training_sample_backward`` on the compact rows followed by ``cgnn_rows_to_frames``."""
-
-    @staticmethod
-    def forward(ctx, cfg: _LinkConfig, rows, want, target_pos, target_temp, *frames):
-        w = len(frames) // 2
-        pos_w, tmp_w = torch.stack(frames[:w]), torch.stack(frames[w:])
-        s = ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, 0.0, 0, 0, target_pos, target_temp, rows, want,
-                                stats=cfg.stats)
-        ctx.cfg, ctx.w, ctx.n, ctx.rows, ctx.want = cfg, w, pos_w.shape[1], rows, tuple(want)
-        ctx.set_materialize_grads(False)
-        return tuple(s[name] for name in want)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *d_out):
-        w, cfg, rows = ctx.w, ctx.cfg, ctx.rows
-        needs = ctx.needs_input_grad[5:]
-        first = min(t % w for t in range(2 * w) if needs[t])
-        g = dict(zip(ctx.want, d_out))
-        if all(d is None for d in d_out):
-            return (None,) * (5 + 2 * w)
-        d_pos, d_temp = ops.training_sample_backward(w, rows.numel(), cfg.meta, cfg.dt, cfg.box, d_x=g.get("x"),
-                                                     d_recent_pos=g.get("recent_pos"), d_y_acc=g.get("y_acc"),
-                                                     d_y_temp_rate=g.get("y_temp_rate"), rows=rows, n_total=ctx.n,
-                                                     first_frame=first, stats=cfg.stats)
-        f_pos, f_temp = ops.rows_to_frames(rows, ctx.n, d_pos[first:], d_temp[first:])
-        return (None,) * 5 + tuple(f_pos[t - first] if needs[t] else None for t in range(w)) + \
-            tuple(f_temp[t - first] if needs[w + t] else None for t in range(w))
-
-
-class _EdgeAttrRowsLink(torch.autograd.Function):
-    """A shard's edge features as a function of its local position rows ``[owned | ghosts]`` (``pos_local [n_local, 3]``):
-    the forward hands on the features the shard's neighbour search made (the global graph's rows), the backward is
-    ``cgnn_edge_attr_backward_rows``.  ``by_sender()`` returns ``ops.SenderCsr(src_local, None, n_local)`` (the one the
-    shard's training runner keeps)."""
-
-    @staticmethod
-    def forward(ctx, pos_local, edge_attr, src_local, k: int, n_recv: int, by_sender):
-        ctx.k, ctx.n_recv, ctx.n_local, ctx.by_sender = int(k), int(n_recv), pos_local.shape[0], by_sender
-        ctx.save_for_backward(edge_attr, src_local)
-        ctx.set_materialize_grads(False)
-        return edge_attr.view_as(edge_attr)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_edge_attr):
-        if d_edge_attr is None:
-            return (None,) * 6
-        edge_attr, src_local = ctx.saved_tensors
-        if ctx.n_local == 0:
-            return (torch.zeros((0, 3), dtype=torch.float32, device=edge_attr.device),) + (None,) * 5
-        return (ops.edge_attr_backward_rows(d_edge_attr, edge_attr, src_local, ctx.k, ctx.n_recv, ctx.by_sender()),) + \
-            (None,) * 5
-
-
-class _IntegrateRowsLink(torch.autograd.Function):
-    """:class:`_IntegrateLink` for the particles ``ids`` of whole frames ``p2`` / ``p1`` ``[N, 3]`` and ``t1 [N]``
-    (predictions row i = particle ``ids[i]``): -> ``(new_pos [R, 3], new_temp [R], block)``, ``block [n_out,
-    ROLLOUT_ROW]`` the packed rows ``cgnn_rollout_integrate`` made (what the ranks gather; not differentiable -- the two
-    row tensors are its differentiable view).  The backward is ``cgnn_rollout_integrate_backward`` on the rows, the frames'
-    gradients then go back to whole frames (``cgnn_rows_to_frames``)."""
-
-    @staticmethod
-    def forward(ctx, cfg: _LinkConfig, ids, n_out: int, acc_pred, rate_pred, p2, p1, t1):
-        block = ops.rollout_integrate(acc_pred, rate_pred, p2, p1, t1, ids, cfg.meta, n_out=n_out, stats=cfg.stats)
-        r = ids.numel()
+    def forward(ctx, cfg: _LinkConfig, ids, n_out: Optional[int], acc_pred, rate_pred, p2, p1, t1):
+        rows = cfg.ids if ids is None else ids
+        block = ops.rollout_integrate(acc_pred, rate_pred, p2, p1, t1, rows, cfg.meta, n_out=n_out, stats=cfg.stats)
+        r = rows.numel()
         ctx.cfg, ctx.ids, ctx.n = cfg, ids, p1.shape[0]
         ctx.shapes = (rate_pred.shape, t1.shape)
         ctx.mark_non_differentiable(block)
@@ -917,16 +853,19 @@ class _IntegrateRowsLink(torch.autograd.Function):
         if (d_new_pos is None and d_new_temp is None) or not want:
             return (None,) * 8
         g = ops.rollout_integrate_backward(d_new_pos, d_new_temp, ctx.cfg.meta, want, stats=ctx.cfg.stats)
+        if ctx.ids is not None:
+            if "p1" in g or "t1" in g:
+                f_pos, f_temp = ops.rows_to_frames(ctx.ids, ctx.n, g.get("p1"), g.get("t1"))
+                if "p1" in g:
+                    g["p1"] = f_pos[0]
+                if "t1" in g:
+                    g["t1"] = f_temp[0]
+            if "p2" in g:
+                g["p2"] = ops.rows_to_frames(ctx.ids, ctx.n, g["p2"], None)[0][0]
         if "temp_rate_pred" in g:
             g["temp_rate_pred"] = g["temp_rate_pred"].view(ctx.shapes[0])
-        if "p1" in g or "t1" in g:
-            f_pos, f_temp = ops.rows_to_frames(ctx.ids, ctx.n, g.get("p1"), g.get("t1"))
-            if "p1" in g:
-                g["p1"] = f_pos[0]
-            if "t1" in g:
-                g["t1"] = f_temp[0].view(ctx.shapes[1])
-        if "p2" in g:
-            g["p2"] = ops.rows_to_frames(ctx.ids, ctx.n, g["p2"], None)[0][0]
+        if "t1" in g:
+            g["t1"] = g["t1"].view(ctx.shapes[1])
         return (None, None, None, *(g.get(name) for name in names))
 
 
@@ -1026,23 +965,6 @@ class UnrolledLoss:
 # without autograd, keep their graph's lists, and run again -- the same kernels on the same inputs -- when the backward
 # reaches them.
 
-class _KeptEdgeAttr(torch.autograd.Function):
-    """:class:`_KnnEdgeAttr` on kept lists: ``edge_attr`` as the search of the first run made it, handed on as a
-    differentiable function of ``recent`` (``cgnn_edge_attr_backward`` on the kept ``senders``); no second search."""
-
-    @staticmethod
-    def forward(ctx, recent, edge_attr, senders, k: int):
-        ctx.k, ctx.n = int(k), recent.shape[0]
-        ctx.save_for_backward(edge_attr, senders)
-        ctx.set_materialize_grads(False)
-        return edge_attr.view_as(edge_attr)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_edge_attr):
-        return (_edge_attr_grad(ctx, d_edge_attr),) + (None,) * 3
-
-
 class _StepRecord:
     """One step of :class:`_Unroll`: its number, weight and whether its outgoing link carries gradient; what the step
     reports (``terms``, ``graph``, ``value``); and under ``checkpoint="steps"`` what a checkpointed step keeps
@@ -1062,8 +984,10 @@ class _Unroll:
     the plain step (``model(graph)``, a search), and under ``checkpoint="steps"`` the first run of a checkpointed step (no
     autograd, it fills the record), its recomputation (autograd, the kept graph) and the last step (autograd, a search);
     the three of ``"steps"`` run the training forward whether autograd records or not, so that they are the same kernels.
-    ``dist._ShardedUnroll`` is the same loop over the rows of a rank: it overrides :meth:`plan`, :meth:`step` and
-    :meth:`publish`.  ``sample0(want)`` makes step 0's sample of the true window, as ``ops.training_sample`` returns it."""
+    ``dist._ShardedUnroll`` is the same loop and the same step over the rows of a rank: it overrides :meth:`plan`,
+    :meth:`_rows`, :meth:`_predict` (what lies between the sample and the integration) and :meth:`publish`.
+    ``sample0(rows, want, targets=True)`` makes step 0's sample of the true window, as ``ops.training_sample`` returns
+    it (``rows=None``: all rows)."""
 
     def __init__(self, model, cfg: _LinkConfig, w: int, n: int, k: int, loss_weights, checkpoint: str, sample0,
                  knn_grid: str = "uniform", min_image: bool = False, keep_graphs: bool = False, density=None, thermal=None):
@@ -1081,29 +1005,26 @@ class _Unroll:
     def plan(self, rec: _StepRecord, pos_frames, tmp_frames, steps: int) -> None:
         """What a step needs settled before it runs, without autograd: nothing on one GPU."""
 
-    def publish(self, rec: _StepRecord, new_p, new_t):
+    def publish(self, rec: _StepRecord, new_p, new_t, _block):
         """What :meth:`step` returned behind its loss term -> the next frame of all rows: on one GPU they are it."""
         return new_p, new_t
 
-    def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool = False, integrate: bool = True):
-        """-> (weighted loss term, new_pos | None, new_temp | None).  ``frames``: the W position frames, then the W
-        temperature frames.  ``kept``: build the graph from ``rec``'s lists; else search and, in the first run of a
-        checkpointed step, fill ``rec``."""
+    def _rows(self, rec: _StepRecord):
+        """The rows the step samples and integrates: all (``None``), or the particle ids a rank holds."""
+        return None
+
+    def _predict(self, rec: _StepRecord, x, recent, y_acc, y_tr, frames, kept: bool):
+        """The part of :meth:`step` between the sample and the integration -> (acceleration, temp_rate, loss term) of the
+        step's rows; fills ``rec.terms`` and ``rec.graph``.  ``kept``: build the graph from ``rec``'s lists; else search
+        and, in the first run of a checkpointed step, fill ``rec``."""
         from . import losses
-        cfg, w, n, k, edge = self.cfg, self.w, self.n, self.k, self.edge
+        cfg, n, k, edge = self.cfg, self.n, self.k, self.edge
         grad = torch.is_grad_enabled()
-        if rec.s == 0:
-            if self.s0 is not None:
-                s0, self.s0 = self.s0, None
-            else:       # the same (seed, draw), the same sample
-                s0 = self.sample0(["x", "recent_pos", "y_acc", "y_temp_rate"])
-            x, recent, y_acc, y_tr = s0["x"], s0["recent_pos"], s0["y_acc"], s0["y_temp_rate"]
-        else:
-            x, recent, y_acc, y_tr = _SampleLink.apply(cfg, tgt_p, tgt_t, *frames)
         if kept:
             senders, order = rec.senders, rec.order
             if edge:
-                edge_attr = _KeptEdgeAttr.apply(recent, rec.edge_attr, senders, k)
+                edge_attr = _EdgeAttrLink.apply(recent, rec.edge_attr, senders, k, None,
+                                                functools.partial(ops.SenderCsr, senders, None, n))
             else:       # x_j reads the width of the edge features only (the edge stream is dead): no N k rows for it
                 edge_attr = recent.new_zeros((1, 4)).expand(n * k, 4)
         else:
@@ -1122,30 +1043,47 @@ class _Unroll:
         mse = torch.nn.functional.mse_loss
         terms = (mse(acc, graph.y_acc), mse(rate, graph.y_temp_rate),
                  losses.momentum_conservation_loss(acc, graph, cfg.dt, self.loss_weights[2]))
-        loss_s = self.loss_weights[0] * terms[0] + self.loss_weights[1] * terms[1] + terms[2]
         if not kept:
             rec.terms = torch.stack([t.detach() for t in terms])
             if self.keep_graphs:        # "steps": detached tensors, the last step's graph does not hold its autograd graph
                 rec.graph = graph if not (self.checkpointed and grad) else \
                     cfg.graph(x.detach(), edge_index, edge_attr.detach(), y_acc.detach(), y_tr.detach(), recent.detach(),
                               order, k)
-        new_p = new_t = None
+        return acc, rate, self.loss_weights[0] * terms[0] + self.loss_weights[1] * terms[1] + terms[2]
+
+    def step(self, rec: _StepRecord, tgt_p, tgt_t, frames, kept: bool = False, integrate: bool = True):
+        """-> (weighted loss term, new_pos | None, new_temp | None, block | None): the step's rows of the next frame and
+        the packed block the integration made of them.  ``frames``: the W whole position frames, then the W temperature
+        frames.  ``kept``: the recomputation of a checkpointed step, on what ``rec`` keeps."""
+        from . import losses
+        cfg, w, rows = self.cfg, self.w, self._rows(rec)
+        grad = torch.is_grad_enabled()
+        if rec.s > 0:
+            x, recent, y_acc, y_tr = _SampleLink.apply(cfg, rows, None, tgt_p, tgt_t, *frames)
+        else:
+            if self.s0 is not None:
+                s0, self.s0 = self.s0, None
+            else:       # in a recomputation the counter-based noise again: the same (seed, draw), the same sample
+                s0 = self.sample0(rows, SAMPLE_OUTPUTS)
+            x, recent, y_acc, y_tr = (s0[name] for name in SAMPLE_OUTPUTS)
+        acc, rate, loss_s = self._predict(rec, x, recent, y_acc, y_tr, frames, kept)
+        new_p = new_t = block = None
         field_terms = self.density is not None or self.thermal is not None
         if integrate or field_terms:
-            p2, p1, t1 = frames[w - 2], frames[w - 1], frames[2 * w - 1]
+            link, p2, p1, t1 = (cfg, rows, rec.cap), frames[w - 2], frames[w - 1], frames[2 * w - 1]
             if (rec.live or self.thermal is not None) and grad:
                 # the thermal term reads the temperature the step makes: where the outgoing link is cut or absent the
                 # step's own integration carries its gradient, through ``rate`` as well; the frame handed on is detached
                 # below
-                new_p, new_t = _IntegrateLink.apply(cfg, acc, rate, p2, p1, t1)
+                new_p, new_t, block = _IntegrateLink.apply(*link, acc, rate, p2, p1, t1)
             elif self.density is not None and grad:
                 # the step's own integration carries the density term's gradient where its outgoing link is cut or
                 # absent; the frame handed on is detached below, and no gradient can arrive through the temperature
-                new_p, new_t = _IntegrateLink.apply(cfg, acc, rate.detach(), p2, p1, t1.detach())
+                new_p, new_t, block = _IntegrateLink.apply(*link, acc, rate.detach(), p2, p1, t1.detach())
             else:
                 with torch.no_grad():
-                    new_p, new_t = _IntegrateLink.apply(cfg, acc.detach(), rate.detach(), p2.detach(), p1.detach(),
-                                                        t1.detach())
+                    new_p, new_t, block = _IntegrateLink.apply(*link, acc.detach(), rate.detach(), p2.detach(),
+                                                               p1.detach(), t1.detach())
         if self.density is not None:
             weight, mesh, order, smoothing = self.density
             field = losses.density_field_loss(new_p, tgt_p, cfg.box, mesh, order, smoothing)
@@ -1160,7 +1098,7 @@ class _Unroll:
                 rec.thermal = field.detach()
         if field_terms and not rec.live:
             new_p, new_t = new_p.detach(), new_t.detach()
-        return rec.weight * loss_s, new_p, new_t
+        return rec.weight * loss_s, new_p, new_t, block
 
     def run(self, pos_frames, tmp_frames, tgt_p, tgt_t, weights, backprop_steps, s0=None) -> UnrolledLoss:
         """The S steps from the (noisy) window ``pos_frames`` / ``tmp_frames`` (W frames each; the predicted ones are
@@ -1378,15 +1316,23 @@ def unrolled_loss(model, position_seq: torch.Tensor, temperature_seq: torch.Tens
     cfg = _LinkConfig(metadata, dt, box_size, n, device)
     pos_w, tmp_w, tgt_p, tgt_t = _device_window(position_seq, temperature_seq, target_positions, target_temperatures,
                                                 device)
-    seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
-    tgt_p0, tgt_t0 = tgt_p[0], tgt_t[0]
-
-    def sample0(want):      # step 0: the one-step sample, with noise from the counter-based generator
-        return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64, noise_draw,
-                                   tgt_p0, tgt_t0, None, want, stats=cfg.stats)
+    sample0 = _step0_sampler(cfg, pos_w, tmp_w, tgt_p[0], tgt_t[0], noise_std, noise_seed, noise_draw)
     unroll = _Unroll(model, cfg, w, n, k, (acc_loss_weight, temp_rate_loss_weight, momentum_loss_weight), checkpoint,
                      sample0, knn_grid, min_image_edge_attr, keep_graphs, density, thermal)
     return _unroll(unroll, float(noise_std) != 0.0, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps)
+
+
+def _step0_sampler(cfg: _LinkConfig, pos_w, tmp_w, tgt_p0, tgt_t0, noise_std: float, noise_seed: Optional[int],
+                   noise_draw: int):
+    """``sample0(rows, want, targets=True)`` of an :class:`_Unroll`: step 0's sample of the true window, the one-step
+    sample with noise from the counter-based generator (a function of the particle id: any row list draws its rows' own
+    noise)."""
+    seed = (torch.initial_seed() if noise_seed is None else int(noise_seed)) % 2 ** 64
+
+    def sample0(rows, want, targets=True):
+        return ops.training_sample(pos_w, tmp_w, cfg.meta, cfg.dt, cfg.box, float(noise_std), seed, noise_draw,
+                                   tgt_p0 if targets else None, tgt_t0 if targets else None, rows, want, stats=cfg.stats)
+    return sample0
 
 
 def _density_arguments(weight, mesh, order, smoothing, who: str = "unrolled_loss", name: str = "density_loss_weight"):
@@ -1455,8 +1401,7 @@ def _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, noise, shift_one: bool = False):
 def _unroll(unroll: _Unroll, noisy: bool, pos_w, tmp_w, tgt_p, tgt_t, weights, backprop_steps) -> UnrolledLoss:
     """:func:`unrolled_loss` / :func:`unrolled_batch_loss` from the true window ``pos_w [W, n, 3]`` / ``tmp_w [W, n]`` and
     the targets ``tgt_p [S, n, 3]`` / ``tgt_t [S, n]``: step 0's sample is drawn here, with its noise in the same launch."""
-    want = ["x", "recent_pos", "y_acc", "y_temp_rate"] + (["pos_noise", "temp_noise"] if noisy else [])
-    s0 = unroll.sample0(want)
+    s0 = unroll.sample0(None, SAMPLE_OUTPUTS + (("pos_noise", "temp_noise") if noisy else ()))
     window = _noisy_window(pos_w, tmp_w, tgt_p, tgt_t, s0 if noisy else None,
                            unroll.density is not None or unroll.thermal is not None)
     return unroll.run(*window, weights, backprop_steps, s0)
@@ -1517,7 +1462,7 @@ def unrolled_batch_loss(model, position_seqs, temperature_seqs, target_positions
                        for t, n_b in zip(m["target_temperatures"], sizes)], dim=1)
     seed = torch.initial_seed() if noise_seed is None else int(noise_seed)
 
-    def sample0(want):      # step 0: every simulation's own sample (its particle ids and its draw), rows joined
+    def sample0(_rows, want, targets=True):     # step 0: every simulation's own sample (its ids and its draw), all rows, joined
         parts = [ops.training_sample(pos_b[b], tmp_b[b], cfg.meta, cfg.dt, cfg.box, float(noise_std), seed % 2 ** 64,
                                      noise_draw + b, tgt_p[0, offsets[b]:offsets[b + 1]],
                                      tgt_t[0, offsets[b]:offsets[b + 1]], None, want, stats=cfg.stats) for b in range(nb)]

@@ -51,7 +51,7 @@ def test_differentiable_links_give_the_forward_kernels_bits(w, box):
     meta = dict(META3, dt=DT, box_size=box)
     cfg = _cfg(meta, box, n)
     frames = [p.clone().requires_grad_(True) for p in pos[:w]] + [t.clone().requires_grad_(True) for t in tmp[:w]]
-    got = training._SampleLink.apply(cfg, pos[w], tmp[w], *frames)
+    got = training._SampleLink.apply(cfg, None, None, pos[w], tmp[w], *frames)
     want = ops.training_sample(pos[:w], tmp[:w], meta, DT, box, 0.0, 0, 0, pos[w], tmp[w])
     rows = torch.randperm(n, generator=torch.Generator().manual_seed(1))[:333].to(DEV)
     want_rows = ops.training_sample(pos[:w], tmp[:w], meta, DT, box, 0.0, 0, 0, pos[w], tmp[w], rows)
@@ -59,18 +59,91 @@ def test_differentiable_links_give_the_forward_kernels_bits(w, box):
         assert g.requires_grad and torch.equal(g, want[name]), name
         assert torch.equal(g[rows], want_rows[name]), name
     acc, rate = torch.randn(n, 3, device=DEV), torch.randn(n, 1, device=DEV)
-    new_p, new_t = training._IntegrateLink.apply(cfg, acc.requires_grad_(True), rate, pos[w - 2], pos[w - 1], tmp[w - 1])
+    new_p, new_t, _ = training._IntegrateLink.apply(cfg, None, None, acc.requires_grad_(True), rate, pos[w - 2], pos[w - 1],
+                                                    tmp[w - 1])
     want_p, want_t = integrate_one_step(acc.detach(), rate, pos[:w], tmp[:w].unsqueeze(-1), meta)
     assert new_p.requires_grad and torch.equal(new_p, want_p) and torch.equal(new_t.reshape(n, 1), want_t)
     recent = got[1]
     for min_image in (False, True):
-        ea, snd = training._KnnEdgeAttr.apply(recent, box, k, "uniform", min_image)
+        ea, snd = training._KnnEdgeAttr.apply(recent, None, box, k, "uniform", min_image)
         want_snd, want_ea, _ = ops.knn_periodic(recent.detach(), box, k, min_image_edge_attr=min_image)
         assert ea.requires_grad and not snd.requires_grad
         assert torch.equal(ea, want_ea) and torch.equal(snd, want_snd)
     order = training.spatial_order(recent, box)                 # the locality hint: a permutation, cell after cell
     assert order.dtype == torch.int32 and torch.equal(order.long().sort().values, torch.arange(n, device=DEV))
     assert torch.equal(order, training.spatial_order(recent.detach().clone(), box))
+
+
+def _frame_grads(link, frames, d_outs):
+    """The outputs of ``link(*leaves)`` on fresh leaves of ``frames`` and the leaves' gradients for ``d_outs``."""
+    leaves = [f.clone().requires_grad_(True) for f in frames]
+    outs = link(*leaves)
+    return outs, torch.autograd.grad(outs, leaves, d_outs)
+
+
+@pytest.mark.parametrize("w", [2, 6])
+def test_all_rows_and_an_identity_row_list_are_one_link(w):
+    """``rows=None`` / ``ids=None`` (whole frames: no row list, no scatter) against the row forms of the same Functions
+    on n = 257 rows: one row past a 256-thread block and past four 64-row blocks of the sample backward.  Exact equality
+    throughout: the same float32 operations in the same order, followed by an index copy."""
+    n, box = 257, 2.5
+    pos, tmp = uc.crossing_window(n, w, box, seed=20 + w, extra=1)
+    pos, tmp = pos.to(DEV), tmp.to(DEV)
+    cfg = _cfg(dict(META3, dt=DT, box_size=box), box, n)
+    gen = torch.Generator().manual_seed(w)
+    every = torch.arange(n, device=DEV)
+    some = torch.randperm(n, generator=gen)[:100].to(DEV)
+    rest = torch.ones(n, dtype=torch.bool, device=DEV)
+    rest[some] = False
+    assert int(rest.sum()) == n - 100
+
+    def sample(rows):
+        return lambda *leaves: training._SampleLink.apply(cfg, rows, None, pos[w], tmp[w], *leaves)
+
+    def integrate(ids, acc, rate):
+        return lambda p2, p1, t1: training._IntegrateLink.apply(cfg, ids, None, acc, rate, p2, p1, t1)[:2]
+
+    def masked(d_outs):     # the other rows' output gradients set to zero
+        return [d.masked_fill(rest.view(-1, *[1] * (d.dim() - 1)), 0.0) for d in d_outs]
+
+    def check_subset(sub, full):    # a subset's frame gradients: the all-rows ones of masked gradients, zero rows exactly zero
+        for got, want in zip(sub, full):
+            assert torch.equal(got, want)
+            assert int(torch.count_nonzero(got[rest])) == 0
+
+    # the sample link: all 2W frames
+    frames = list(pos[:w]) + list(tmp[:w])
+    d_outs = [torch.randn(shape, generator=gen).to(DEV) for shape in ((n, 4 * w - 3), (n, 3), (n, 3), (n,))]
+    outs_all, grads_all = _frame_grads(sample(None), frames, d_outs)
+    outs_id, grads_id = _frame_grads(sample(every), frames, d_outs)
+    assert len(grads_all) == 2 * w
+    for a, b in zip(outs_all + grads_all, outs_id + grads_id):
+        assert a.shape == b.shape and torch.equal(a, b)
+    outs_sub, grads_sub = _frame_grads(sample(some), frames, [d[some] for d in d_outs])
+    for a, b in zip(outs_sub, outs_all):
+        assert torch.equal(a, b[some])
+    check_subset(grads_sub, _frame_grads(sample(None), frames, masked(d_outs))[1])
+
+    # the integrate link: the frames p2, p1 and t1 (the predictions' gradients are rows on either side)
+    acc, rate = torch.randn(n, 3, generator=gen).to(DEV), torch.randn(n, 1, generator=gen).to(DEV)
+    last = [pos[w - 2], pos[w - 1], tmp[w - 1]]
+    d_new = [torch.randn(n, 3, generator=gen).to(DEV), torch.randn(n, generator=gen).to(DEV)]
+    outs_all, grads_all = _frame_grads(integrate(None, acc, rate), last, d_new)
+    outs_id, grads_id = _frame_grads(integrate(every, acc, rate), last, d_new)
+    for a, b in zip(outs_all + grads_all, outs_id + grads_id):
+        assert a.shape == b.shape and torch.equal(a, b)
+    outs_sub, grads_sub = _frame_grads(integrate(some, acc[some], rate[some]), last, [d[some] for d in d_new])
+    for a, b in zip(outs_sub, outs_all):
+        assert torch.equal(a, b[some])
+    check_subset(grads_sub, _frame_grads(integrate(None, acc, rate), last, masked(d_new))[1])
+    # the predictions' gradients as well, and the packed block both forms return behind the rows
+    a_all, a_id = acc.clone().requires_grad_(True), acc.clone().requires_grad_(True)
+    r_all, r_id = rate.clone().requires_grad_(True), rate.clone().requires_grad_(True)
+    made_all = training._IntegrateLink.apply(cfg, None, None, a_all, r_all, *last)
+    made_id = training._IntegrateLink.apply(cfg, every, None, a_id, r_id, *last)
+    assert not made_all[2].requires_grad and torch.equal(made_all[2], made_id[2])
+    for a, b in zip(torch.autograd.grad(made_all[:2], (a_all, r_all), d_new), torch.autograd.grad(made_id[:2], (a_id, r_id), d_new)):
+        assert a.shape == b.shape and torch.equal(a, b)
 
 
 # ---- 2. cgnn_training_sample_backward -----------------------------------------------------------------------------------
