@@ -624,8 +624,12 @@ def aggregate(table, gather: Optional[torch.Tensor], dst: Optional[torch.Tensor]
         dst = i32c(dst, "dst")
     if num_edges is None:
         num_edges = gather.numel() if gather is not None else (dst.numel() if dst is not None else nrows)
+    if gather is None and nrows < num_edges:
+        raise CgnnError(f"aggregate: a table of {nrows} rows read by edge id for {num_edges} edges")
     if out is None:
         out = torch.empty((num_nodes, width), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (num_nodes, width) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise CgnnError(f"aggregate: out must be contiguous float32 {(num_nodes, width)}")
     _same_device(tb, gather, dst, out)
     with _timed("aggregate", dev):
         check(_lib.load().cgnn_aggregate(tb.data_ptr(), layout, ptr(gather), ptr(dst), num_edges, fixed_k, num_nodes,
@@ -2222,9 +2226,14 @@ def segment_colsum(acc: torch.Tensor, batch: Optional[torch.Tensor], num_graphs:
 
 def gather_rows(table: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     table, idx = f32c(table, "table"), i32c(idx, "idx")
+    shape = (idx.numel(), table.shape[1])
     if out is None:
-        out = torch.empty((idx.numel(), table.shape[1]), dtype=torch.float32, device=table.device)
+        out = torch.empty(shape, dtype=torch.float32, device=table.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != table.device:
+        raise CgnnError(f"gather_rows: out must be contiguous float32 {shape} on the table's device")
     _same_device(table, idx, out)
+    if idx.numel() == 0:            # nothing to move (and an empty tensor has no address to pass on)
+        return out
     with _timed("gather_rows", table.device):
         check(_lib.load().cgnn_gather_rows(table.data_ptr(), idx.data_ptr(), idx.numel(), table.shape[1], out.data_ptr(),
                                            stream_ptr(table.device)), "cgnn_gather_rows")
@@ -2236,7 +2245,12 @@ def scatter_rows(rows: torch.Tensor, idx: torch.Tensor, table: torch.Tensor) -> 
     require_device(table, "table")
     if not table.is_contiguous() or table.dtype != torch.float32:
         raise CgnnError("scatter_rows: table must be contiguous float32")
+    if table.dim() != 2 or tuple(rows.shape) != (idx.numel(), table.shape[1]):
+        raise CgnnError(f"scatter_rows: rows is {tuple(rows.shape)}, need {(idx.numel(), table.shape[-1])} "
+                        f"(one row of the table's width per index)")
     _same_device(rows, idx, table)
+    if idx.numel() == 0:
+        return table
     with _timed("scatter_rows", table.device):
         check(_lib.load().cgnn_scatter_rows(rows.data_ptr(), idx.data_ptr(), idx.numel(), table.shape[1],
                                             table.data_ptr(), stream_ptr(table.device)), "cgnn_scatter_rows")
@@ -2379,6 +2393,8 @@ def aggregate_csr(table: torch.Tensor, csr: SenderCsr, out: Optional[torch.Tenso
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
                               or t.device != table.device):
             raise CgnnError(f"aggregate_csr: {name} must be contiguous float32 {shape} on the table's device")
+    if a == b:                      # an empty range writes nothing (and an empty tensor has no address to pass on)
+        return out
     with _timed("aggregate_csr", table.device):
         check(_lib.load().cgnn_aggregate_csr_add(table.data_ptr(), csr.row_ptr.data_ptr() + 4 * a, csr.col.data_ptr(),
                                                  b - a, table.shape[1], ptr(add1), ptr(add2), out.data_ptr(),

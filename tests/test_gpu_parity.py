@@ -9,6 +9,7 @@ import torch
 from conftest import edge_index_from, rel_err, rel_l2
 from cosmology_gnn_simulation_amd import data_utils, graph_network, losses, one_step, ops, synthetic
 from cosmology_gnn_simulation_amd.graph import Batch, Data
+from gather_checks import _kernel_order_sum
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -54,21 +55,6 @@ def test_mlp_rows(n, fin, hid, out, nh, ln, prec, tol):
     got = ops.mlp_rows(ops.PackedMLP(lin, lnp, prec), x.to(DEV)).cpu()
     assert got.shape == want.shape
     assert rel_l2(got, want) <= tol
-
-
-def _kernel_order_sum(rows):
-    """[n, k, width] -> [n, width] in the kernels' order: a balanced pairwise tree for k in {8, 16} (the order of the
-    cross-lane reduction fused into the edge kernel), sequential otherwise."""
-    n, k, _ = rows.shape
-    if k in (8, 16):
-        v = rows
-        while v.shape[1] > 1:
-            v = v[:, 0::2] + v[:, 1::2]
-        return v[:, 0]
-    out = rows[:, 0].clone()
-    for j in range(1, k):
-        out += rows[:, j]
-    return out
 
 
 @pytest.mark.parametrize("n,k,width", [(1000, 16, 128), (77, 8, 64), (5, 32, 256), (300, 3, 32)])
