@@ -62,7 +62,7 @@ WEIGHT_BITS = 20              # CGNN_MA_WEIGHT_BITS: a quantised weight of 2^20 
 WEIGHTED_MAX_PARTICLES = 1 << 23   # n (2^39 + 14) must stay inside int64
 WEIGHTED_MAX_CHANNELS = 4     # CGNN_MA_MAX_CHANNELS
 POWER_MAX_BINS = 256          # CGNN_PB_MAX_BINS
-FOF_MAX_BINS = 256            # CGNN_FOF_MAX_BINS in csrc/fof.hip
+FOF_MAX_BINS = 256            # CGNN_SIZE_MAX_BINS in csrc/cgnn_util.hpp
 FOF_DISP_UNITS = 1 << 30      # cgnn_fof_catalogue: disp counts displacements in box_size / 2^30
 HALO_MATCH_COLS = 6           # CGNN_HM_COLS in csrc/halo_match.hip: columns of the summary of cgnn_halo_match
 GROUP_SUMS_MAX_CHANNELS = 4   # CGNN_GS_MAX_CHANNELS

@@ -1,14 +1,12 @@
-// Morton cell grid over a periodic box [0, L)^3 and its counting sort, shared by the k-NN builder (knn.hip), the pair
-// counter (pair_counts.hip) and the group finder (fof.hip): cell numbering, the cell coordinate of a position, the
-// count / fill kernels that sort particles by cell (the scan between them is scan.hpp), and what the two walks over a
-// cell's 27 neighbours share: the minimum-image fold and the staging of the neighbour ranges.
+// Morton cell grid over a periodic box [0, L)^3 and its counting sort, shared by the k-NN builder (knn.hip) and the
+// pair walk of the pair counter and the group finder (pair_walk.hpp): cell numbering, the cell coordinate of a position,
+// the count / fill kernels that sort particles by cell (the scan between them is scan.hpp), the minimum-image fold and
+// the staging of the ranges of a cell's 27 neighbours.
 #pragma once
-#include "cgnn_common.hpp"
+#include "cgnn_util.hpp"
 #include "scan.hpp"
 
 namespace cgnn {
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Cells are numbered along a Z-order (Morton) curve, so the cell-sorted particle order -- which the engine
 // adopts as its node numbering -- keeps 3-D neighbours close in memory in all three directions (a row-major

@@ -5,6 +5,7 @@
 // gradients at every *sender* -- has a variable degree per row; scattering it with float atomics cost 27 ms at
 // 10^6 particles, k = 16, against 0.7 ms for the forward.  Grouping the edges by sender once per graph makes the
 // transpose the same kind of atomic-free gather as the forward, and its summation order deterministic.
+#include "cgnn_util.hpp"
 #include "scan.hpp"
 
 namespace cgnn {
@@ -12,7 +13,6 @@ namespace cgnn {
 struct CsrLayout {
     size_t off_count, off_cursor, off_bsum, total;
 };
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static CsrLayout csr_layout(int64_t rows) {
     CsrLayout L;
     size_t off = 0;

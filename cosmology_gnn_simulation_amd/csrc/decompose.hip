@@ -15,7 +15,7 @@
 // Histograms are integer counts, kept per workgroup in LDS and flushed with integer atomics, so the result does not
 // depend on the order the atomics land in: the planes are a pure function of the position bits.  No host
 // synchronisation; the planes stay on the device.
-#include "cgnn_common.hpp"
+#include "cgnn_util.hpp"
 
 namespace cgnn {
 
@@ -30,7 +30,6 @@ struct DecTarget {
     int32_t rank;       // rank of the wanted element among the keys that match the prefix; -1: empty segment
 };
 
-static inline size_t dec_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct DecLayout {
     size_t off_part, off_count, off_target, off_hist, total;
@@ -41,10 +40,10 @@ static DecLayout dec_layout(int64_t n, int64_t world) {
     DecLayout L;
     L.max_targets = world > 1 ? world - 1 : 1;      // a level has segments * (p - 1) < world targets
     size_t off = 0;
-    L.off_part = off;   off = dec_align(off + (size_t)(n > 0 ? n : 1) * 4);
-    L.off_count = off;  off = dec_align(off + 2 * (size_t)world * 4);       // segment counts: this level's, the next's
-    L.off_target = off; off = dec_align(off + (size_t)L.max_targets * sizeof(DecTarget));
-    L.off_hist = off;   off = dec_align(off + (size_t)L.max_targets * CGNN_DEC_BINS * 4);
+    L.off_part = off;   off = align256(off + (size_t)(n > 0 ? n : 1) * 4);
+    L.off_count = off;  off = align256(off + 2 * (size_t)world * 4);       // segment counts: this level's, the next's
+    L.off_target = off; off = align256(off + (size_t)L.max_targets * sizeof(DecTarget));
+    L.off_hist = off;   off = align256(off + (size_t)L.max_targets * CGNN_DEC_BINS * 4);
     L.total = off;
     return L;
 }

@@ -4,33 +4,22 @@
 // predicted frame collapses the right number of bound objects of each size, which no two-point statistic can.
 //
 // Linking contract (include/cgnn.h; tests/fof_checks.py restates it in numpy).  d2(i, j) is the float32 minimum-image
-// squared distance of cgnn_pair_counts, per axis
-//     d = fl32(b - a);   d > half ? fl32(d - L) : d < -half ? fl32(d + L) : d        half = fl32(0.5f * L)
-//     d2 = fl32(fl32(fl32(dx dx) + fl32(dy dy)) + fl32(dz dz))
-// one rounding per operation, nothing contracted (the Makefile compiles this file with -ffp-contract=off, as it does
-// pair_counts.hip, and for the same reason); with l2 = fl32(l l) particles i != j are linked iff d2 < l2, strictly: the
-// links are the pairs cgnn_pair_counts counts for the edges [0, l].  labels[i] is the smallest particle index of i's
-// connected component.
+// squared distance of cgnn_pair_counts (pair_d2 of pair_walk.hpp: one rounding per operation, nothing contracted, so the
+// Makefile compiles this file, too, with -ffp-contract=off); with l2 = fl32(l l) particles i != j are linked iff
+// d2 < l2, strictly: the links are the pairs cgnn_pair_counts counts for the edges [0, l].  labels[i] is the smallest
+// particle index of i's connected component.
 //
-// Grid.  The particles are sorted into the Morton cell grid of cell_grid.hpp with G cells per axis of side h = L / G,
-// G the largest count with
-//     h >= l (1 + 1e-5) + 2e-5 L
-// (the margin derived in pair_counts.hip: two linked particles then lie in the same cell or in periodically adjacent
-// cells), capped so that G^3 <= CGNN_FOF_CELLS_PER_PARTICLE N and G <= 512 (spread3 has 10 bits).  The cap is the pair
-// counter's, G^3 <= N: at the conventional 0.2 mean spacings it decides, and leaves cells five linking lengths wide.  A
-// finer cap, G^3 <= 8 N, halves the side and cuts the distance evaluations eightfold where the particles are dense,
-// but it was measured not to pay (scripts/time_fof.py, 1 M particles; DESIGN.md, the friends-of-friends section): with
-// eight cells per particle nearly every work item holds one query, and what an item costs before its first distance is
-// the time.  The grid only proposes candidates: the contract alone decides a link.  When G <= 3 all G cells of an axis
-// are walked once (c - 1 and c + 1 wrap onto each other or onto c).
+// Grid (the grid rule of pair_walk.hpp for reach = l), capped so that G^3 <= CGNN_FOF_CELLS_PER_PARTICLE N and G <= 512
+// (spread3 has 10 bits).  The cap is the pair counter's, G^3 <= N: at the conventional 0.2 mean spacings it decides, and
+// leaves cells five linking lengths wide.  A finer cap, G^3 <= 8 N, halves the side and cuts the distance evaluations
+// eightfold where the particles are dense, but it was measured not to pay (scripts/time_fof.py, 1 M particles;
+// DESIGN.md, the friends-of-friends section): with eight cells per particle nearly every work item holds one query, and
+// what an item costs before its first distance is the time.  The grid only proposes candidates: the contract alone
+// decides a link.
 //
-// Walk (fof_walk_kernel), as pc_walk_kernel: a work item is up to CGNN_FOF_QCHUNK queries of one cell, staged in LDS
-// (the items are numbered by a scan of ceil(count / QCHUNK) over the cells and listed by fof_items_kernel, all on the
-// device: no host synchronisation); a persistent workgroup strides over the items, lists the at most 27 partner
-// ranges of the neighbourhood and runs the concatenated candidates through in tiles of one candidate per lane against
-// every staged query.  A linked pair is met twice, once from each side; the side whose candidate has the smaller
-// original index (carried in .w of the sorted float4) calls unite, so every link is united exactly once and no
-// particle with itself.
+// Walk (fof_walk_kernel): pair_walk of pair_walk.hpp over work items of up to CGNN_FOF_QCHUNK queries of one cell.  A
+// linked pair is met twice, once from each side; the side whose candidate has the smaller original index (carried in
+// .w of the sorted float4) calls unite, so every link is united exactly once and no particle with itself.
 //
 // Union-find over parent[n] (the labels array itself, over ORIGINAL indices), lock-free: no locks, no spin-waits.
 //   find(x)      follows parent until parent[x] == x.
@@ -58,18 +47,14 @@
 // Catalogue.  size[r] and disp[r] are integer sums over the members of root r (32- and 64-bit integer atomics; the
 // result does not depend on any order), q = llrint((double)d * scale) per axis of the folded float32 displacement from
 // the root, scale = 2^30 / (double)L; |q| <= 2^29 and fewer than 2^31 members keep the int64 sums from overflowing.
-// A wave sums its members per root before it touches memory (fof_members_kernel).
+// A wave sums its members per root before it touches memory (fof_members_kernel, wave_for_each_key of cgnn_util.hpp).
 // The mass function bins the non-zero sizes in LDS per workgroup and adds each non-empty bin once.
 #include <math.h>
 
-#include "cgnn_common.hpp"
-#include "scan.hpp"
-#include "cell_grid.hpp"
+#include "pair_walk.hpp"   // its contract needs -ffp-contract=off
+#include "cgnn_util.hpp"
 
 #define CGNN_FOF_QCHUNK 256             // queries per work item = threads per workgroup = candidates per tile
-#define CGNN_FOF_RANGES 27
-#define CGNN_FOF_MAX_BLOCKS 2048
-#define CGNN_FOF_MAX_BINS 256
 #ifndef CGNN_FOF_CELLS_PER_PARTICLE
 #define CGNN_FOF_CELLS_PER_PARTICLE 1   // the cap G^3 <= N (see the header; a build flag, for timing another cap)
 #endif
@@ -77,67 +62,19 @@
 
 namespace cgnn {
 
-// cells per axis for n particles and a linking length `reach` (see the header); reach < 0: the cap alone
-static int fof_cells_per_axis(int64_t n, float box, float reach) {
-    int cap = 1;
-    while (cap < CGNN_FOF_MAX_G && (int64_t)(cap + 1) * (cap + 1) * (cap + 1) <= CGNN_FOF_CELLS_PER_PARTICLE * n) ++cap;
-    if (reach < 0.f) return cap;
-    const double need = (double)reach * (1.0 + 1e-5) + 2e-5 * (double)box;
-    const double g = floor((double)box / need);
-    int G = g < 1.0 ? 1 : (g > (double)CGNN_FOF_MAX_G ? CGNN_FOF_MAX_G : (int)g);
-    return G < cap ? G : cap;
-}
-
-static int64_t fof_cell_slots(int G) {
-    int Gp = 1;
-    while (Gp < G) Gp <<= 1;
-    return (int64_t)Gp * Gp * Gp;
-}
-
-// at most one partly filled item per cell that holds queries, plus the full ones
-static int64_t fof_max_items(int64_t cells, int64_t n) { return (cells < n ? cells : n) + n / CGNN_FOF_QCHUNK; }
-
 struct FofLayout {
     int64_t cells_max;   // cell slots of the finest grid n allows: the tables are sized for it
-    size_t off_count, off_start, off_cursor, off_cellof, off_sorted, off_bsum, off_nchunk, off_cstart, off_itemq0, total;
+    SortedSetLayout set;
+    ItemTableLayout items;
+    size_t total;
 };
 
 static FofLayout fof_layout(int64_t n) {
     FofLayout L;
-    L.cells_max = fof_cell_slots(fof_cells_per_axis(n, 1.f, -1.f));
-    const size_t table = (size_t)(L.cells_max + 1) * 4;
-    size_t off = 0;
-    L.off_count = off;  off = align256(off + table);
-    L.off_start = off;  off = align256(off + table);
-    L.off_cursor = off; off = align256(off + table);
-    L.off_cellof = off; off = align256(off + (size_t)n * 4);
-    L.off_sorted = off; off = align256(off + (size_t)n * 16);
-    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(L.cells_max + 1) + 1) * 4);
-    L.off_nchunk = off; off = align256(off + table);
-    L.off_cstart = off; off = align256(off + table);
-    L.off_itemq0 = off; off = align256(off + (size_t)fof_max_items(L.cells_max, n) * 4);
-    L.total = off;
+    L.cells_max = pair_cell_slots(pair_cells_per_axis(n, 1.f, -1.f, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE));
+    const size_t off = sorted_set_layout(L.set, 0, L.cells_max, n);
+    L.total = item_table_layout(L.items, off, L.cells_max, n, CGNN_FOF_QCHUNK);
     return L;
-}
-
-// nchunk[c] = work items of cell c; entry `cells` stays 0 so that the scan ends in the item total
-__global__ void fof_chunks_kernel(const int32_t* __restrict__ start, int64_t cells, int32_t* __restrict__ nchunk) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > cells) return;
-    nchunk[c] = c < cells ? (start[c + 1] - start[c] + CGNN_FOF_QCHUNK - 1) / CGNN_FOF_QCHUNK : 0;
-}
-
-// item_q0[item] = the sorted slot of the item's first query: slot s of cell c begins item chunk_start[c] + k when it is
-// the (k QCHUNK)-th of its cell.  One thread per slot, so a crowded cell costs no thread a long loop, and the walk finds
-// its item with one load instead of a search over the cell table.
-__global__ void fof_items_kernel(const float4* __restrict__ sorted, const int32_t* __restrict__ cell_of,
-                                 const int32_t* __restrict__ start, const int32_t* __restrict__ chunk_start, int64_t n,
-                                 int32_t* __restrict__ item_q0) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    const int c = cell_of[__float_as_int(sorted[s].w)];
-    const int off = (int)s - start[c];
-    if (off % CGNN_FOF_QCHUNK == 0) item_q0[chunk_start[c] + off / CGNN_FOF_QCHUNK] = (int32_t)s;
 }
 
 __global__ void fof_init_kernel(int32_t* __restrict__ parent, int64_t n) {
@@ -181,38 +118,13 @@ __global__ __launch_bounds__(CGNN_FOF_QCHUNK) void fof_walk_kernel(const float4*
                                                                    const int32_t* __restrict__ item_q0, int cells,
                                                                    int G, float box, float half, float l2,
                                                                    int32_t* parent) {
-    __shared__ float4 q_s[CGNN_FOF_QCHUNK];
-    __shared__ int rng_p0[CGNN_FOF_RANGES], rng_len[CGNN_FOF_RANGES], rng_off[CGNN_FOF_RANGES + 1];
-    const int tid = threadIdx.x;
-    const int items = chunk_start[cells];
-    for (int item = blockIdx.x; item < items; item += gridDim.x) {
-        const int q0 = item_q0[item];
-        const int c = cell_of[__float_as_int(sorted[q0].w)];      // the item's cell: that of its first query
-        const int nq = min(CGNN_FOF_QCHUNK, start[c + 1] - q0);
-        const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
-        __syncthreads();               // the previous item's readers of q_s and rng_* are done
-        if (tid < nq) q_s[tid] = sorted[q0 + tid];
-        cell_grid_stage_ranges<CGNN_FOF_RANGES>(tid, cx, cy, cz, G, start, rng_p0, rng_len, rng_off);
-        const int nc = rng_off[CGNN_FOF_RANGES];
-        for (int t0 = 0; t0 < nc; t0 += CGNN_FOF_QCHUNK) {
-            const int t = t0 + tid;
-            if (t < nc) {
-                int j = 0;
-                while (rng_off[j + 1] <= t) ++j;            // t < rng_off[RANGES]: j stays below RANGES
-                const float4 b = sorted[rng_p0[j] + (t - rng_off[j])];
-                const int bi = __float_as_int(b.w);
-                for (int qi = 0; qi < nq; ++qi) {
-                    const float4 a = q_s[qi];
-                    const float dx = cell_grid_fold(__fsub_rn(b.x, a.x), box, half);
-                    const float dy = cell_grid_fold(__fsub_rn(b.y, a.y), box, half);
-                    const float dz = cell_grid_fold(__fsub_rn(b.z, a.z), box, half);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                    // the pair is met from both sides: this one unites it (and never a particle with itself)
-                    if (d2 < l2 && bi < __float_as_int(a.w)) fof_unite(parent, __float_as_int(a.w), bi);
-                }
-            }
-        }
-    }
+    pair_walk<CGNN_FOF_QCHUNK>(
+        sorted, start, cell_of, sorted, start, chunk_start, item_q0, cells, G, box, half, [](int) {},
+        [=](const float4& a, const float4& b, float d2, int, int, int) {
+            // the pair is met from both sides: this one unites it (and never a particle with itself)
+            const int ai = __float_as_int(a.w), bi = __float_as_int(b.w);
+            if (d2 < l2 && bi < ai) fof_unite(parent, ai, bi);
+        });
 }
 
 // labels[i] = the root of i = the minimum of its component (parent is labels: a root already reads itself).  The walk
@@ -231,14 +143,9 @@ __global__ void fof_labels_kernel(int32_t* parent, int64_t n) {
 }
 
 // ---- cgnn_fof_catalogue --------------------------------------------------------------------------------------------
-struct FofSizeEdges {
-    int32_t e[CGNN_FOF_MAX_BINS + 1];
-};
-
 // One thread per particle.  A root adds itself to its size; the other members of a wave are summed per root first
-// (a loop over the distinct roots among them, each round led by the first lane still waiting), so a group of many
-// members puts one atomic per wave on its slots instead of one per member.  Integer sums: any grouping gives the
-// same bits.
+// (wave_for_each_key: a round per distinct root among them), so a group of many members puts one atomic per wave on its
+// slots instead of one per member.  Integer sums: any grouping gives the same bits.
 __global__ __launch_bounds__(CGNN_BLOCK) void fof_members_kernel(const float* __restrict__ pos,
                                                                  const int32_t* __restrict__ labels, int64_t n, float box,
                                                                  float half, double scale, int32_t* __restrict__ size,
@@ -258,13 +165,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fof_members_kernel(const float* __
         q1 = __double2ll_rn(__dmul_rn((double)cell_grid_fold(__fsub_rn(pos[3 * i + 1], pos[3 * (int64_t)r + 1]), box, half), scale));
         q2 = __double2ll_rn(__dmul_rn((double)cell_grid_fold(__fsub_rn(pos[3 * i + 2], pos[3 * (int64_t)r + 2]), box, half), scale));
     }
-    unsigned long long todo = __ballot(member);      // wave-uniform: every lane runs every round
-    while (todo != 0) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lr = __shfl(r, leader);
-        const bool mine = member && r == lr;
-        const unsigned long long m = __ballot(mine);
-        todo &= ~m;
+    wave_for_each_key(member, r, [&](int leader, int lr, bool mine, unsigned long long m) {
         long long s0 = mine ? q0 : 0, s1 = mine ? q1 : 0, s2 = mine ? q2 : 0;
         if (m != (1ull << leader) && disp != nullptr) {
             for (int off = CGNN_WAVE / 2; off > 0; off >>= 1) {
@@ -281,25 +182,18 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fof_members_kernel(const float* __
                 if (s2 != 0) atomicAdd(&disp[3 * (int64_t)lr + 2], (unsigned long long)s2);
             }
         }
-    }
+    });
 }
 
 __global__ __launch_bounds__(CGNN_BLOCK) void fof_hist_kernel(const int32_t* __restrict__ size, int64_t n,
-                                                              const FofSizeEdges E, int num_bins,
+                                                              const SizeEdges E, int num_bins,
                                                               unsigned long long* __restrict__ hist) {
-    __shared__ unsigned h_s[CGNN_FOF_MAX_BINS];
+    __shared__ unsigned h_s[CGNN_SIZE_MAX_BINS];
     for (int b = threadIdx.x; b < num_bins; b += CGNN_BLOCK) h_s[b] = 0u;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int s = i < n ? size[i] : 0;
-    if (s >= E.e[0] && s < E.e[num_bins]) {
-        int lo = 0, up = num_bins;     // e[lo] <= s < e[up]
-        while (up - lo > 1) {
-            const int mid = (lo + up) >> 1;
-            if (E.e[mid] <= s) lo = mid; else up = mid;
-        }
-        atomicAdd(&h_s[lo], 1u);
-    }
+    if (s >= E.e[0] && s < E.e[num_bins]) atomicAdd(&h_s[bin_of(E.e, num_bins, s)], 1u);
     __syncthreads();
     for (int b = threadIdx.x; b < num_bins; b += CGNN_BLOCK)
         if (h_s[b] != 0u) atomicAdd(&hist[b], (unsigned long long)h_s[b]);
@@ -341,41 +235,22 @@ int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_l
         set_error("cgnn_fof_labels: workspace %zu < required %zu bytes", workspace_bytes, L.total);
         return CGNN_ERR_WORKSPACE;
     }
-    const int G = fof_cells_per_axis(n, box_size, linking_length);
-    const int64_t cells = fof_cell_slots(G);   // <= L.cells_max: G never exceeds the cap the layout is sized for
+    const int G = pair_cells_per_axis(n, box_size, linking_length, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE);
+    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
     const float inv_h = (float)G / box_size;
     const float l2 = linking_length * linking_length;   // fl32 product, rounded once
 
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* count = reinterpret_cast<int32_t*>(ws + L.off_count);
-    int32_t* start = reinterpret_cast<int32_t*>(ws + L.off_start);
-    int32_t* cursor = reinterpret_cast<int32_t*>(ws + L.off_cursor);
-    int32_t* cell_of = reinterpret_cast<int32_t*>(ws + L.off_cellof);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.off_sorted);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
-    int32_t* nchunk = reinterpret_cast<int32_t*>(ws + L.off_nchunk);
-    int32_t* cstart = reinterpret_cast<int32_t*>(ws + L.off_cstart);
-    int32_t* item_q0 = reinterpret_cast<int32_t*>(ws + L.off_itemq0);
-
-    const int64_t m = cells + 1;   // count[cells] = 0 so that start[cells] = n
-    int rc = check_hip(hipMemsetAsync(count, 0, (size_t)m * 4, st), "fof_labels memset count");
-    if (rc) return rc;
-    rc = check_hip(hipMemsetAsync(cursor, 0, (size_t)m * 4, st), "fof_labels memset cursor");
-    if (rc) return rc;
+    const SortedSet S = sorted_set(ws, L.set);
+    const ItemTable I = item_table(ws, L.items);
     const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
-    const unsigned mb = (unsigned)((m + CGNN_BLOCK - 1) / CGNN_BLOCK);
     fof_init_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
-    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, cell_of, count);
-    exclusive_scan_i32(count, m, bsum, start, st);
-    knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, cell_of, start, cursor, sorted);
-    fof_chunks_kernel<<<mb, CGNN_BLOCK, 0, st>>>(start, cells, nchunk);
-    exclusive_scan_i32(nchunk, m, bsum, cstart, st);
-    fof_items_kernel<<<nb, CGNN_BLOCK, 0, st>>>(sorted, cell_of, start, cstart, n, item_q0);
-    const int64_t max_items = fof_max_items(cells, n);
-    const unsigned blocks = (unsigned)(max_items < CGNN_FOF_MAX_BLOCKS ? max_items : CGNN_FOF_MAX_BLOCKS);
-    fof_walk_kernel<<<blocks, CGNN_FOF_QCHUNK, 0, st>>>(sorted, start, cell_of, cstart, item_q0, (int)cells, G, box_size,
-                                                        half, l2, labels);
+    const int rc = sorted_set_sort(pos, n, inv_h, G, cells, S, I.bsum, st, "fof_labels", "cgnn_fof_labels");
+    if (rc) return rc;
+    item_table_build<CGNN_FOF_QCHUNK>(S, n, cells, I, st);
+    fof_walk_kernel<<<pair_walk_blocks(cells, n, CGNN_FOF_QCHUNK), CGNN_FOF_QCHUNK, 0, st>>>(
+        S.sorted, S.start, S.cell_of, I.chunk_start, I.item_q0, (int)cells, G, box_size, half, l2, labels);
     fof_labels_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
     return check_hip(hipGetLastError(), "cgnn_fof_labels");
 }
@@ -390,23 +265,11 @@ int cgnn_fof_catalogue(const float* pos, const int32_t* labels, int64_t n, float
         set_error("cgnn_fof_catalogue: 2^31 or more particles are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    FofSizeEdges E;
-    if (hist) {
-        if (num_bins < 1 || num_bins > CGNN_FOF_MAX_BINS) {
-            set_error("cgnn_fof_catalogue: num_bins=%d outside [1, %d]", (int)num_bins, CGNN_FOF_MAX_BINS);
-            return CGNN_ERR_INVALID_ARG;
-        }
-        for (int i = 0; i <= num_bins; ++i) {
-            if (size_edges[i] < 1 || (i > 0 && size_edges[i] <= size_edges[i - 1])) {
-                set_error("cgnn_fof_catalogue: size_edges must start at 1 or above and ascend strictly (size_edges[%d])", i);
-                return CGNN_ERR_INVALID_ARG;
-            }
-            E.e[i] = size_edges[i];
-        }
-        for (int i = num_bins + 1; i <= CGNN_FOF_MAX_BINS; ++i) E.e[i] = 0;
-    }
+    SizeEdges E = {};
+    int rc = hist ? load_size_edges("cgnn_fof_catalogue", size_edges, num_bins, E) : CGNN_OK;
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    int rc = check_hip(hipMemsetAsync(size, 0, (size_t)n * 4, st), "fof_catalogue memset size");
+    rc = check_hip(hipMemsetAsync(size, 0, (size_t)n * 4, st), "fof_catalogue memset size");
     if (rc) return rc;
     if (disp) {
         rc = check_hip(hipMemsetAsync(disp, 0, (size_t)n * 24, st), "fof_catalogue memset disp");

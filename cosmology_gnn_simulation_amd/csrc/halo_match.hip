@@ -13,16 +13,17 @@
 //
 // Count (hm_count_kernel).  An open-addressing table in the workspace: `cap` slots, cap the smallest power of two
 // >= 2 n, of a 64-bit key (ra << 32) | rb and a 32-bit count.  The empty key is all ones, which is no key: n < 2^31.
-// One thread per particle.  A wave first finds the distinct keys among its lanes (the leader loop of
-// fof_members_kernel: every round the first lane still waiting broadcasts its key and the lanes that hold it leave
-// with it), so a group of many members that stays together costs one probe and one add per wave, not per member.  The
+// One thread per particle.  A wave first finds the distinct keys among its lanes (wave_for_each_key of cgnn_util.hpp:
+// every round the first lane still waiting broadcasts its key and the lanes that hold it leave with it), so a group
+// of many members that stays together costs one probe and one add per wave, not per member.  The
 // leaders then insert all at once: a 64-bit compare-and-swap of the empty key by this key either claims the slot, or
 // returns this key (another wave claimed it for the same pair: the slot is ours too), or returns another key; only then
 // does the probe move to the next slot.  There is no spin-wait and no lock: no thread ever waits for another one's
 // store.  A key, once in a slot, never leaves it, and there are at most n distinct keys in 2 n or more slots, so a probe
 // of `cap` steps always ends at its key's slot; the loop is bounded by cap all the same.  The count is added with an
 // atomic add after the claim: the count of a slot is only read by the next launch.  Every table access of this kernel
-// is an agent-scope atomic (as in fof_walk_kernel): the L2s of the chip's dies are not coherent for plain accesses.
+// is an agent-scope atomic (as the union-find's of fof.hip): the L2s of the chip's dies are not coherent for plain
+// accesses.
 //
 // Select (hm_select_kernel), a later launch: plain loads.  One thread per slot; an occupied slot (ra, rb, c) raises
 //     best_ab[ra]  to  (c << 32) | (0xFFFFFFFF - rb)          best_ba[rb]  to  (c << 32) | (0xFFFFFFFF - ra)
@@ -32,21 +33,19 @@
 // the threads raced, of the hash function and of the table size.
 //
 // Finish (hm_finish_kernel): unpacks the four outputs, and bins the listed groups of A by size for the summary, in LDS
-// per workgroup; each non-empty cell is added once (fof_hist_kernel's scheme).  Whether r's match is MUTUAL
+// per workgroup (bin_of of cgnn_util.hpp); each non-empty cell is added once.  Whether r's match is MUTUAL
 // (match_ba[match_ab[r]] == r) is read from best_ba, which the select launch completed.
 //
-// Group sums (fof_sums_kernel): fof_members_kernel's wave reduction over up to four int32 channels, the root included,
-// 64-bit integer atomics (two's complement: the sum of the unsigned images is the image of the signed sum).
-#include "cgnn_common.hpp"
+// Group sums (fof_sums_kernel): a wave sums its members per root (wave_for_each_key again) over up to four int32
+// channels, the root included, before it touches memory; 64-bit integer atomics (two's complement: the sum of the
+// unsigned images is the image of the signed sum).
+#include "cgnn_util.hpp"
 
-#define CGNN_HM_MAX_BINS 256
 #define CGNN_HM_COLS 6
 #define CGNN_HM_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define CGNN_GS_MAX_CHANNELS 4
 
 namespace cgnn {
-
-static size_t hm_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct HmLayout {
     int64_t cap;     // table slots: the smallest power of two >= 2 n
@@ -58,17 +57,13 @@ static HmLayout hm_layout(int64_t n) {
     L.cap = 2;
     while (L.cap < 2 * n) L.cap <<= 1;
     size_t off = 0;
-    L.off_keys = off;    off = hm_align256(off + (size_t)L.cap * 8);
-    L.off_counts = off;  off = hm_align256(off + (size_t)L.cap * 4);     // counts and both best arrays: one memset
-    L.off_best_ab = off; off = hm_align256(off + (size_t)n * 8);
-    L.off_best_ba = off; off = hm_align256(off + (size_t)n * 8);
+    L.off_keys = off;    off = align256(off + (size_t)L.cap * 8);
+    L.off_counts = off;  off = align256(off + (size_t)L.cap * 4);     // counts and both best arrays: one memset
+    L.off_best_ab = off; off = align256(off + (size_t)n * 8);
+    L.off_best_ba = off; off = align256(off + (size_t)n * 8);
     L.total = off;
     return L;
 }
-
-struct HmSizeEdges {
-    int32_t e[CGNN_HM_MAX_BINS + 1];
-};
 
 // any mixing of the key will do (the result does not depend on it): the finaliser of MurmurHash3
 __device__ __forceinline__ unsigned long long hm_hash(unsigned long long k) {
@@ -96,14 +91,9 @@ __global__ __launch_bounds__(CGNN_BLOCK) void hm_count_kernel(const int32_t* __r
     }
     const bool counting = key != CGNN_HM_EMPTY;
     unsigned add = 0;                                  // a leader's: the lanes of this wave that hold its key
-    unsigned long long todo = __ballot(counting);      // wave-uniform: every lane runs every round
-    while (todo != 0) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned long long lk = __shfl(key, leader);
-        const unsigned long long m = __ballot(counting && key == lk);
-        todo &= ~m;
+    wave_for_each_key(counting, key, [&](int leader, unsigned long long, bool, unsigned long long m) {
         if (lane == leader) add = (unsigned)__popcll(m);
-    }
+    });
     if (add == 0) return;
     const unsigned long long mask = cap - 1;
     unsigned long long slot = hm_hash(key) & mask;
@@ -141,13 +131,13 @@ __global__ __launch_bounds__(CGNN_BLOCK) void hm_finish_kernel(const unsigned lo
                                                                const unsigned long long* __restrict__ best_ba,
                                                                const int32_t* __restrict__ size_a,
                                                                const int32_t* __restrict__ size_b, int64_t n, int min_a,
-                                                               const HmSizeEdges E, int num_bins,
+                                                               const SizeEdges E, int num_bins,
                                                                int32_t* __restrict__ match_ab,
                                                                int32_t* __restrict__ shared_ab,
                                                                int32_t* __restrict__ match_ba,
                                                                int32_t* __restrict__ shared_ba,
                                                                unsigned long long* __restrict__ summary) {
-    __shared__ unsigned long long s_s[CGNN_HM_MAX_BINS * CGNN_HM_COLS];
+    __shared__ unsigned long long s_s[CGNN_SIZE_MAX_BINS * CGNN_HM_COLS];
     for (int b = threadIdx.x; b < num_bins * CGNN_HM_COLS; b += CGNN_BLOCK) s_s[b] = 0ull;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -160,12 +150,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void hm_finish_kernel(const unsigned lo
         shared_ba[i] = (int)(vb >> 32);
         const int s = num_bins > 0 ? size_a[i] : 0;
         if (num_bins > 0 && s >= min_a && s >= E.e[0] && s < E.e[num_bins]) {
-            int lo = 0, up = num_bins;     // e[lo] <= s < e[up]
-            while (up - lo > 1) {
-                const int mid = (lo + up) >> 1;
-                if (E.e[mid] <= s) lo = mid; else up = mid;
-            }
-            unsigned long long* row = s_s + lo * CGNN_HM_COLS;
+            unsigned long long* row = s_s + bin_of(E.e, num_bins, s) * CGNN_HM_COLS;
             atomicAdd(row + 0, 1ull);
             if (ma >= 0) {                 // a root of B that holds a counting particle: inside [0, n)
                 atomicAdd(row + 1, 1ull);
@@ -183,8 +168,8 @@ __global__ __launch_bounds__(CGNN_BLOCK) void hm_finish_kernel(const unsigned lo
         if (s_s[b] != 0ull) atomicAdd(&summary[b], s_s[b]);
 }
 
-// One thread per particle; the members of a wave are summed per root first (fof_members_kernel's leader loop; here the
-// root is a member like any other), so a group of many members puts one atomic per wave and channel on its slot.
+// One thread per particle; the members of a wave are summed per root first (wave_for_each_key; here the root is a
+// member like any other), so a group of many members puts one atomic per wave and channel on its slot.
 template <int C>
 __global__ __launch_bounds__(CGNN_BLOCK) void fof_sums_kernel(const int32_t* __restrict__ labels,
                                                               const int32_t* __restrict__ q, int64_t n,
@@ -200,13 +185,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fof_sums_kernel(const int32_t* __r
     long long v[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = member ? (long long)q[i * C + c] : 0;
-    unsigned long long todo = __ballot(member);      // wave-uniform: every lane runs every round
-    while (todo != 0) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lr = __shfl(r, leader);
-        const bool mine = member && r == lr;
-        const unsigned long long m = __ballot(mine);
-        todo &= ~m;
+    wave_for_each_key(member, r, [&](int leader, int lr, bool mine, unsigned long long m) {
         long long s[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) s[c] = mine ? v[c] : 0;
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void fof_sums_kernel(const int32_t* __r
             for (int c = 0; c < C; ++c)
                 if (s[c] != 0) atomicAdd(&sums[(int64_t)lr * C + c], (unsigned long long)s[c]);
         }
-    }
+    });
 }
 
 }  // namespace cgnn
@@ -252,24 +231,10 @@ int cgnn_halo_match(const int32_t* labels_a, const int32_t* size_a, const int32_
         set_error("cgnn_halo_match: 2^31 or more particles are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    HmSizeEdges E;
-    if (summary) {
-        if (num_bins < 1 || num_bins > CGNN_HM_MAX_BINS) {
-            set_error("cgnn_halo_match: num_bins=%d outside [1, %d]", (int)num_bins, CGNN_HM_MAX_BINS);
-            return CGNN_ERR_INVALID_ARG;
-        }
-        for (int i = 0; i <= num_bins; ++i) {
-            if (size_edges[i] < 1 || (i > 0 && size_edges[i] <= size_edges[i - 1])) {
-                set_error("cgnn_halo_match: size_edges must start at 1 or above and ascend strictly (size_edges[%d])", i);
-                return CGNN_ERR_INVALID_ARG;
-            }
-            E.e[i] = size_edges[i];
-        }
-        for (int i = num_bins + 1; i <= CGNN_HM_MAX_BINS; ++i) E.e[i] = 0;
-    } else {
-        num_bins = 0;
-        for (int i = 0; i <= CGNN_HM_MAX_BINS; ++i) E.e[i] = 0;
-    }
+    SizeEdges E = {};
+    if (!summary) num_bins = 0;
+    int rc = summary ? load_size_edges("cgnn_halo_match", size_edges, num_bins, E) : CGNN_OK;
+    if (rc) return rc;
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
         set_error("cgnn_halo_match: workspace must be 16-byte aligned");
         return CGNN_ERR_INVALID_ARG;
@@ -286,7 +251,7 @@ int cgnn_halo_match(const int32_t* labels_a, const int32_t* size_a, const int32_
     unsigned long long* best_ab = reinterpret_cast<unsigned long long*>(ws + L.off_best_ab);
     unsigned long long* best_ba = reinterpret_cast<unsigned long long*>(ws + L.off_best_ba);
 
-    int rc = check_hip(hipMemsetAsync(keys, 0xFF, (size_t)L.cap * 8, st), "halo_match memset keys");
+    rc = check_hip(hipMemsetAsync(keys, 0xFF, (size_t)L.cap * 8, st), "halo_match memset keys");
     if (rc) return rc;
     rc = check_hip(hipMemsetAsync(counts, 0, L.total - L.off_counts, st), "halo_match memset counts");
     if (rc) return rc;

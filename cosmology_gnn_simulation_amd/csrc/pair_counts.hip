@@ -8,42 +8,25 @@
 // e2[i] <= d2 < e2[i + 1].  The expression is symmetric in a and b, so the auto mode counts ordered pairs i != j and
 // halves the exact even totals at the end.
 //
-// Grid.  The partner set (B, or A in auto mode) is sorted into the k-NN builder's Morton cell grid (cell_grid.hpp) with
-// G cells per axis of side h = L / G, where G is the largest count with
-//     h >= reach (1 + 1e-5) + 2e-5 L,   reach = edges[num_bins],
-// capped so that G^3 <= partners and G <= 256.  A counted pair has d2 < e2[num_bins], so on every axis its folded
-// separation is below reach (1 + 2^-22); the cell coordinate of a position is off by less than 1e-6 L (roundings of
-// G / L and of p * inv_h).  Hence two counted particles lie in the same cell or in periodically adjacent cells: the walk
-// of a query cell is the 3 x 3 x 3 block around it, wrapped.  It only proposes candidates; the contract above alone
-// decides what is counted.  When G <= 3 an axis has no three DISTINCT neighbours (c - 1 and c + 1 wrap onto each other or
-// onto c), so all G cells of the axis are walked once: every distinct cell is met exactly once per query and no pair
+// Grid and walk (pair_walk.hpp).  The partner set (B, or A in auto mode) is sorted into the Morton cell grid with the
+// shared grid rule for reach = edges[num_bins], capped so that G^3 <= partners and G <= 256; a counted pair has
+// d2 < e2[num_bins], so the 27 cells around a query's hold all its counted partners.  The walk only proposes candidates;
+// the contract above alone decides what is counted, and every distinct cell is met exactly once per query, so no pair
 // is counted twice.  A, too, is sorted into the same grid (in auto mode it is the same sort), so a run of sorted A
-// particles shares one neighbourhood.
+// particles shares one neighbourhood: a work item is up to CGNN_PC_QCHUNK queries of one cell.
 //
-// Walk.  A work item is up to CGNN_PC_QCHUNK queries of one cell (a crowded cell makes several items; the item table is a
-// scan of ceil(count / QCHUNK) over the cells, read on the device: no host synchronisation).  A persistent workgroup
-// strides over the items.  Per item it stages the queries in LDS, lists the at most 27 partner ranges of the
-// neighbourhood, and runs the concatenated candidates through in tiles of one candidate per lane (coalesced float4 from
-// the sorted array, kept in registers) against every staged query (an LDS broadcast read): every partner of the
-// neighbourhood is read once per item instead of once per query.  The bin is found by comparing d2 with the e2 table in
-// LDS (no sqrt, no log), counted with a 32-bit LDS atomic into the wave's own histogram, and the histograms are added
-// to the global int64 counts with one 64-bit atomic per non-empty bin, once per workgroup -- or earlier, before a
-// 32-bit counter could wrap (a wave adds at most 64 * QCHUNK per tile).
+// Count (pc_walk_kernel).  The bin of a proposed pair is found by comparing d2 with the e2 table in LDS (no sqrt, no
+// log), counted with a 32-bit LDS atomic into the wave's own histogram, and the histograms are added to the global int64
+// counts with one 64-bit atomic per non-empty bin, once per workgroup -- or earlier, ahead of a tile, before a 32-bit
+// counter could wrap (a wave adds at most 64 * QCHUNK per tile).
 #include <math.h>
 
-#include "cgnn_common.hpp"
-#include "scan.hpp"
-#include "cell_grid.hpp"
-
-// The contract rounds every operation once.  hipcc's default (-ffp-contract=fast) fuses fl32(x x) + fl32(y y) into an
-// fma even when the operands come from __fmul_rn / __fadd_rn (they are inline functions whose operations carry the
-// default's permission to contract; a pragma here does not reach them), which moves a pair across a bin edge once in
-// some 10^7 pairs.  The Makefile therefore compiles this file with -ffp-contract=off.
+#include "pair_walk.hpp"   // its contract needs -ffp-contract=off: the Makefile compiles this file with it
+#include "cgnn_util.hpp"
 
 #define CGNN_PC_QCHUNK 256    // queries per work item = threads per workgroup = candidates per tile
 #define CGNN_PC_MAX_BINS 256
-#define CGNN_PC_RANGES 27
-#define CGNN_PC_MAX_BLOCKS 2048
+#define CGNN_PC_MAX_G 256      // cells per axis at most, and one cell per partner at most
 #define CGNN_FE_PARTS 64       // partial sums per frame (stage 1 of cgnn_frame_errors)
 
 namespace cgnn {
@@ -52,59 +35,21 @@ struct PcEdges2 {
     float e2[CGNN_PC_MAX_BINS + 1];
 };
 
-// cells per axis for `partners` particles and a largest radius `reach` (see the header); reach < 0: the cap alone
-static int pc_cells_per_axis(int64_t partners, float box, float reach) {
-    int cap = 1;
-    while (cap < 256 && (int64_t)(cap + 1) * (cap + 1) * (cap + 1) <= partners) ++cap;
-    if (reach < 0.f) return cap;
-    const double need = (double)reach * (1.0 + 1e-5) + 2e-5 * (double)box;
-    const double g = floor((double)box / need);
-    int G = g < 1.0 ? 1 : (g > 256.0 ? 256 : (int)g);
-    return G < cap ? G : cap;
-}
-
-static int64_t pc_cell_slots(int G) {
-    int Gp = 1;
-    while (Gp < G) Gp <<= 1;
-    return (int64_t)Gp * Gp * Gp;
-}
-
-struct PcSetLayout {
-    size_t off_count, off_start, off_cursor, off_cellof, off_sorted;
-};
 struct PcLayout {
-    int64_t cells_max;   // cell slots of the finest grid the partner count allows: the tables are sized for it
-    PcSetLayout a, b;    // auto mode: b == a
-    size_t off_bsum, off_nchunk, off_cstart, total;
+    int64_t cells_max;       // cell slots of the finest grid the partner count allows: the tables are sized for it
+    SortedSetLayout a, b;    // auto mode: b == a
+    ItemTableLayout items;
+    size_t total;
 };
-
-static size_t pc_set_layout(PcSetLayout& S, size_t off, int64_t cells, int64_t n) {
-    S.off_count = off;  off = align256(off + (size_t)(cells + 1) * 4);
-    S.off_start = off;  off = align256(off + (size_t)(cells + 1) * 4);
-    S.off_cursor = off; off = align256(off + (size_t)(cells + 1) * 4);
-    S.off_cellof = off; off = align256(off + (size_t)n * 4);
-    S.off_sorted = off; off = align256(off + (size_t)n * 16);
-    return off;
-}
 
 static PcLayout pc_layout(int64_t n_a, int64_t n_b, bool cross) {
     PcLayout L;
-    L.cells_max = pc_cell_slots(pc_cells_per_axis(cross ? n_b : n_a, 1.f, -1.f));
-    size_t off = pc_set_layout(L.a, 0, L.cells_max, n_a);
-    if (cross) off = pc_set_layout(L.b, off, L.cells_max, n_b);
+    L.cells_max = pair_cell_slots(pair_cells_per_axis(cross ? n_b : n_a, 1.f, -1.f, CGNN_PC_MAX_G, 1));
+    size_t off = sorted_set_layout(L.a, 0, L.cells_max, n_a);
+    if (cross) off = sorted_set_layout(L.b, off, L.cells_max, n_b);
     else L.b = L.a;
-    L.off_bsum = off;   off = align256(off + (size_t)(scan_blocks(L.cells_max + 1) + 1) * 4);
-    L.off_nchunk = off; off = align256(off + (size_t)(L.cells_max + 1) * 4);
-    L.off_cstart = off; off = align256(off + (size_t)(L.cells_max + 1) * 4);
-    L.total = off;
+    L.total = item_table_layout(L.items, off, L.cells_max, n_a, CGNN_PC_QCHUNK);
     return L;
-}
-
-// nchunk[c] = work items of cell c; entry `cells` stays 0 so that the scan ends in the item total
-__global__ void pc_chunks_kernel(const int32_t* __restrict__ start_a, int64_t cells, int32_t* __restrict__ nchunk) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > cells) return;
-    nchunk[c] = c < cells ? (start_a[c + 1] - start_a[c] + CGNN_PC_QCHUNK - 1) / CGNN_PC_QCHUNK : 0;
 }
 
 // the waves' histograms -> global counts, and back to zero; every thread of the workgroup calls it
@@ -124,65 +69,32 @@ __device__ __forceinline__ void pc_flush(unsigned (*hist)[CGNN_PC_MAX_BINS], int
 }
 
 __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
-    const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a, const float4* __restrict__ sorted_b,
-    const int32_t* __restrict__ start_b, const int32_t* __restrict__ chunk_start, int cells, int G, float box,
-    float half, const PcEdges2 E, int num_bins, int auto_mode, unsigned long long* __restrict__ counts) {
-    __shared__ float4 q_s[CGNN_PC_QCHUNK];
+    const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a, const int32_t* __restrict__ cell_of_a,
+    const float4* __restrict__ sorted_b, const int32_t* __restrict__ start_b, const int32_t* __restrict__ chunk_start,
+    const int32_t* __restrict__ item_q0, int cells, int G, float box, float half, const PcEdges2 E, int num_bins,
+    int auto_mode, unsigned long long* __restrict__ counts) {
     __shared__ float e2_s[CGNN_PC_MAX_BINS + 1];
     __shared__ unsigned hist[CGNN_PC_QCHUNK / CGNN_WAVE][CGNN_PC_MAX_BINS];
-    __shared__ int rng_p0[CGNN_PC_RANGES], rng_len[CGNN_PC_RANGES], rng_off[CGNN_PC_RANGES + 1];
     const int tid = threadIdx.x, wave = tid >> 6;
     for (int i = tid; i <= num_bins; i += CGNN_PC_QCHUNK) e2_s[i] = E.e2[i];
     for (int i = tid; i < (CGNN_PC_QCHUNK / CGNN_WAVE) * CGNN_PC_MAX_BINS; i += CGNN_PC_QCHUNK) (&hist[0][0])[i] = 0u;
     __syncthreads();
     const float e2_lo = e2_s[0], e2_hi = e2_s[num_bins];
-    const int items = chunk_start[cells];
     unsigned pending = 0;              // bound on what any one LDS counter holds since the last flush
-    for (int item = blockIdx.x; item < items; item += gridDim.x) {
-        // the item's cell: chunk_start[c] <= item < chunk_start[c + 1] (cells without queries have no items)
-        int c = 0, hi = cells;
-        while (hi - c > 1) {
-            const int mid = (c + hi) >> 1;
-            if (chunk_start[mid] <= item) c = mid; else hi = mid;
-        }
-        const int q0 = start_a[c] + (item - chunk_start[c]) * CGNN_PC_QCHUNK;
-        const int nq = min(CGNN_PC_QCHUNK, start_a[c + 1] - q0);
-        const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
-        __syncthreads();               // the previous item's readers of q_s and rng_* are done
-        if (tid < nq) q_s[tid] = sorted_a[q0 + tid];
-        cell_grid_stage_ranges<CGNN_PC_RANGES>(tid, cx, cy, cz, G, start_b, rng_p0, rng_len, rng_off);
-        const int nc = rng_off[CGNN_PC_RANGES];
-        for (int t0 = 0; t0 < nc; t0 += CGNN_PC_QCHUNK) {
+    pair_walk<CGNN_PC_QCHUNK>(
+        sorted_a, start_a, cell_of_a, sorted_b, start_b, chunk_start, item_q0, cells, G, box, half,
+        [&](int nq) {
             if (pending >= 0x7F000000u) {      // uniform over the workgroup
                 pc_flush(hist, num_bins, counts);
                 pending = 0;
             }
             pending += (unsigned)(CGNN_WAVE * nq);
-            const int t = t0 + tid;
-            if (t < nc) {
-                int j = 0;
-                while (rng_off[j + 1] <= t) ++j;            // t < rng_off[RANGES]: j stays below RANGES
-                const int p = rng_p0[j] + (t - rng_off[j]);
-                const float4 b = sorted_b[p];
-                const int self = auto_mode ? p - q0 : -1;   // the query that is this very particle, if any
-                for (int qi = 0; qi < nq; ++qi) {
-                    const float4 a = q_s[qi];
-                    const float dx = cell_grid_fold(__fsub_rn(b.x, a.x), box, half);
-                    const float dy = cell_grid_fold(__fsub_rn(b.y, a.y), box, half);
-                    const float dz = cell_grid_fold(__fsub_rn(b.z, a.z), box, half);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                    if (d2 >= e2_lo && d2 < e2_hi && qi != self) {
-                        int lo = 0, up = num_bins;          // e2[lo] <= d2 < e2[up]
-                        while (up - lo > 1) {
-                            const int mid = (lo + up) >> 1;
-                            if (e2_s[mid] <= d2) lo = mid; else up = mid;
-                        }
-                        atomicAdd(&hist[wave][lo], 1u);
-                    }
-                }
-            }
-        }
-    }
+        },
+        [&](const float4&, const float4&, float d2, int qi, int p, int q0) {
+            // in auto mode query p - q0 is this very particle
+            if (d2 >= e2_lo && d2 < e2_hi && (!auto_mode || qi != p - q0))
+                atomicAdd(&hist[wave][bin_of(e2_s, num_bins, d2)], 1u);
+        });
     pc_flush(hist, num_bins, counts);
 }
 
@@ -190,36 +102,6 @@ __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
 __global__ void pc_halve_kernel(unsigned long long* __restrict__ counts, int num_bins) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < num_bins) counts[b] >>= 1;
-}
-
-struct PcSet {
-    int32_t *count, *start, *cursor, *cell_of;
-    float4* sorted;
-};
-
-static PcSet pc_set(char* ws, const PcSetLayout& S) {
-    PcSet P;
-    P.count = reinterpret_cast<int32_t*>(ws + S.off_count);
-    P.start = reinterpret_cast<int32_t*>(ws + S.off_start);
-    P.cursor = reinterpret_cast<int32_t*>(ws + S.off_cursor);
-    P.cell_of = reinterpret_cast<int32_t*>(ws + S.off_cellof);
-    P.sorted = reinterpret_cast<float4*>(ws + S.off_sorted);
-    return P;
-}
-
-// counting sort of pos[0..n) by Morton cell: P.start [cells + 1], P.sorted [n]
-static int pc_sort(const float* pos, int64_t n, float inv_h, int G, int64_t cells, const PcSet& P, int32_t* bsum,
-                   hipStream_t st) {
-    const int64_t m = cells + 1;   // count[cells] = 0 so that start[cells] = n
-    int rc = check_hip(hipMemsetAsync(P.count, 0, (size_t)m * 4, st), "pair_counts memset count");
-    if (rc) return rc;
-    rc = check_hip(hipMemsetAsync(P.cursor, 0, (size_t)m * 4, st), "pair_counts memset cursor");
-    if (rc) return rc;
-    const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
-    knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, P.cell_of, P.count);
-    exclusive_scan_i32(P.count, m, bsum, P.start, st);
-    knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, P.cell_of, P.start, P.cursor, P.sorted);
-    return check_hip(hipGetLastError(), "cgnn_pair_counts sort");
 }
 
 // ---- cgnn_frame_errors -----------------------------------------------------------------------------------------------
@@ -331,8 +213,8 @@ int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_
         set_error("cgnn_pair_counts: workspace %zu < required %zu bytes", workspace_bytes, L.total);
         return CGNN_ERR_WORKSPACE;
     }
-    const int G = pc_cells_per_axis(cross ? n_b : n_a, box_size, edges[num_bins]);
-    const int64_t cells = pc_cell_slots(G);    // <= L.cells_max: G never exceeds the cap the layout is sized for
+    const int G = pair_cells_per_axis(cross ? n_b : n_a, box_size, edges[num_bins], CGNN_PC_MAX_G, 1);
+    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
     const float inv_h = (float)G / box_size;
     PcEdges2 E;
     for (int i = 0; i <= num_bins; ++i) E.e2[i] = edges[i] * edges[i];   // fl32 product, rounded once
@@ -340,27 +222,20 @@ int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_
 
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace);
-    const PcSet A = pc_set(ws, L.a), B = pc_set(ws, L.b);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + L.off_bsum);
-    int32_t* nchunk = reinterpret_cast<int32_t*>(ws + L.off_nchunk);
-    int32_t* cstart = reinterpret_cast<int32_t*>(ws + L.off_cstart);
+    const SortedSet A = sorted_set(ws, L.a), B = sorted_set(ws, L.b);
+    const ItemTable I = item_table(ws, L.items);
     int rc = check_hip(hipMemsetAsync(counts, 0, (size_t)num_bins * 8, st), "pair_counts memset counts");
     if (rc) return rc;
-    rc = pc_sort(pos_a, n_a, inv_h, G, cells, A, bsum, st);
+    rc = sorted_set_sort(pos_a, n_a, inv_h, G, cells, A, I.bsum, st, "pair_counts", "cgnn_pair_counts sort");
     if (rc) return rc;
     if (cross) {
-        rc = pc_sort(pos_b, n_b, inv_h, G, cells, B, bsum, st);
+        rc = sorted_set_sort(pos_b, n_b, inv_h, G, cells, B, I.bsum, st, "pair_counts", "cgnn_pair_counts sort");
         if (rc) return rc;
     }
-    const int64_t m = cells + 1;
-    pc_chunks_kernel<<<(unsigned)((m + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(A.start, cells, nchunk);
-    exclusive_scan_i32(nchunk, m, bsum, cstart, st);
-    // at most one partly filled item per cell that holds queries, plus the full ones
-    int64_t max_items = (cells < n_a ? cells : n_a) + n_a / CGNN_PC_QCHUNK;
-    const unsigned blocks = (unsigned)(max_items < CGNN_PC_MAX_BLOCKS ? max_items : CGNN_PC_MAX_BLOCKS);
-    pc_walk_kernel<<<blocks, CGNN_PC_QCHUNK, 0, st>>>(A.sorted, A.start, B.sorted, B.start, cstart, (int)cells, G,
-                                                      box_size, half, E, num_bins, cross ? 0 : 1,
-                                                      reinterpret_cast<unsigned long long*>(counts));
+    item_table_build<CGNN_PC_QCHUNK>(A, n_a, cells, I, st);
+    pc_walk_kernel<<<pair_walk_blocks(cells, n_a, CGNN_PC_QCHUNK), CGNN_PC_QCHUNK, 0, st>>>(
+        A.sorted, A.start, A.cell_of, B.sorted, B.start, I.chunk_start, I.item_q0, (int)cells, G, box_size, half, E,
+        num_bins, cross ? 0 : 1, reinterpret_cast<unsigned long long*>(counts));
     if (!cross)
         pc_halve_kernel<<<1, CGNN_PC_MAX_BINS, 0, st>>>(reinterpret_cast<unsigned long long*>(counts), num_bins);
     return check_hip(hipGetLastError(), "cgnn_pair_counts");

@@ -45,7 +45,7 @@
 // the same bits.  A slice without modes writes zeros and leaves before the tree.  Compiled with -ffp-contract=off (Makefile): every operation below rounds once, in float32 and float64.
 #include <math.h>
 
-#include "cgnn_common.hpp"
+#include "cgnn_util.hpp"
 
 #define CGNN_MA_Q 8192           // 2^13: the axis weights of a particle sum to this
 #define CGNN_MA_MAX_MESH 512
@@ -261,7 +261,6 @@ __global__ __launch_bounds__(CGNN_BLOCK) void ma_gather_kernel(const float* __re
     }
 }
 
-static inline size_t pb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct PbEdges2 {
     float e2[CGNN_PB_MAX_BINS + 1];
@@ -284,16 +283,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void pb_ids_kernel(int M, int Mh, int m
     pb_mode(idx, M, Mh, nx, ny, nz);
     const int n2 = nx * nx + ny * ny + nz * nz;
     const float v = (float)n2;                   // exact: n2 < 2^24
-    int bin = -1;
-    if (n2 != 0 && v >= E.e2[0] && v < E.e2[num_bins]) {
-        int lo = 0, up = num_bins;               // e2[lo] <= v < e2[up]
-        while (up - lo > 1) {
-            const int mid = (lo + up) >> 1;
-            if (E.e2[mid] <= v) lo = mid; else up = mid;
-        }
-        bin = lo;
-    }
-    ids[idx] = bin;
+    ids[idx] = n2 != 0 && v >= E.e2[0] && v < E.e2[num_bins] ? bin_of(E.e2, num_bins, v) : -1;
 }
 
 // inv_w2[i] = 1 / sinc(pi i / M)^(2 order) for i in [0, M/2]: the deconvolution of one axis (|n| indexes it)
@@ -412,7 +402,7 @@ static bool pb_edges(const float* k_edges, int32_t num_bins, PbEdges2& E, const 
     return true;
 }
 
-static size_t pb_window_bytes() { return pb_align256((size_t)(CGNN_MA_MAX_MESH / 2 + 1) * sizeof(double)); }
+static size_t pb_window_bytes() { return align256((size_t)(CGNN_MA_MAX_MESH / 2 + 1) * sizeof(double)); }
 
 }  // namespace cgnn
 
@@ -552,7 +542,7 @@ int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int
 size_t cgnn_power_bins_workspace_bytes(int64_t frames, int32_t num_bins) {
     if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
     const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
-    return pb_window_bytes() + pb_align256(blocks * CGNN_PB_SUMS * sizeof(double)) + pb_align256(blocks * sizeof(long long));
+    return pb_window_bytes() + align256(blocks * CGNN_PB_SUMS * sizeof(double)) + align256(blocks * sizeof(long long));
 }
 
 int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t mesh, int32_t order, const int32_t* perm,
@@ -580,7 +570,7 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
     double* inv_w2 = reinterpret_cast<double*>(ws);
     double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
     long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() +
-                                                  pb_align256((size_t)blocks * CGNN_PB_SUMS * sizeof(double)));
+                                                  align256((size_t)blocks * CGNN_PB_SUMS * sizeof(double)));
     const int Mh = mesh / 2 + 1;
     pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
     const int64_t modes_per_frame = (int64_t)mesh * mesh * Mh;

@@ -3,7 +3,7 @@ linking length of 0.2 mean interparticle spacings; for context ``ops.pair_counts
 the same process (the existing kernel; it makes the same distance tests).  Every shape is
 warmed, then the calls alternate; each call sits between two device events.  Prints the median, min and max of 7 calls
 in ms per frame, the ratio to the pair count, the number of groups, the largest group, and the distance evaluations of
-the walk under the grid rule of csrc/fof.hip (every query against every candidate of the cells its cell walks), computed
+the walk under the grid rule of csrc/pair_walk.hpp (every query against every candidate of the cells its cell walks), computed
 here from the cell occupancies.  Not part of the product or tests.
     python scripts/time_fof.py [--iters 7] [--spacings 0.2] [--inputs uniform:1000000 clustered:1000000]
 clustered:N is synthetic.make_clustered_positions(N) (half of the particles in one Gaussian halo of 0.05 box);
@@ -44,8 +44,8 @@ def frame(spec):
 
 
 def cells_per_axis(n, reach, per_particle=1, largest=512):
-    """The grid rule of csrc/fof.hip (fof_cells_per_axis; per_particle is its CGNN_FOF_CELLS_PER_PARTICLE); largest=256:
-    that of csrc/pair_counts.hip."""
+    """The grid rule (pair_cells_per_axis of csrc/pair_walk.hpp) with the caps of csrc/fof.hip (per_particle is its
+    CGNN_FOF_CELLS_PER_PARTICLE); largest=256: those of csrc/pair_counts.hip."""
     cap = 1
     while cap < largest and (cap + 1) ** 3 <= per_particle * n:
         cap += 1

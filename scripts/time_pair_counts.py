@@ -41,7 +41,7 @@ def frame(spec):
 
 
 def cells_per_axis(n, reach):
-    """The grid rule of csrc/pair_counts.hip (pc_cells_per_axis)."""
+    """The grid rule (pair_cells_per_axis of csrc/pair_walk.hpp) with the pair counter's caps."""
     cap = 1
     while cap < 256 and (cap + 1) ** 3 <= n:
         cap += 1

@@ -2,8 +2,9 @@
 of their contract (tests/fof_checks.py): integers throughout, so every comparison is ``torch.equal``; and the halo
 functions of ``statistics`` built on them.  N is at most 8192.
 
-Grids the cases reach (``_cells_per_axis`` restates the rule of csrc/fof.hip: the largest G with cells no smaller than
-the linking length plus its margin, capped by G^3 <= N and 512): one cell (l = L / 2), G = 2 and 3 (all cells of an
+Grids the cases reach (``_cells_per_axis`` restates the grid rule, ``pair_cells_per_axis`` of csrc/pair_walk.hpp, with the
+group finder's caps: the largest G with cells no smaller than the linking length plus its margin, capped by G^3 <= N and
+512): one cell (l = L / 2), G = 2 and 3 (all cells of an
 axis walked once), powers of two and others under the 27-cell walk, the cap (0.2 spacings) and the length (1.0)
 deciding."""
 import functools
@@ -230,6 +231,28 @@ def test_a_blob_puts_several_items_and_partial_tiles_in_one_cell():
     assert ((cell == 3).all(axis=1)).sum() >= 700       # three work items of one cell, the last one partial
     labels = _check(x, BOX, ll)
     assert np.bincount(labels).max() > 350
+
+
+@pytest.mark.parametrize("m", [256, 257, 512])
+def test_a_cell_of_exactly_full_work_items(m):
+    """m particles in one cell and nobody else in it: one full item, a full item and one query, two full items."""
+    rng = np.random.default_rng(31 + m)
+    d = rng.standard_normal((m, 3))
+    d *= (0.01 * BOX * rng.random((m, 1)) ** (1 / 3)) / np.linalg.norm(d, axis=1, keepdims=True)
+    blob = (0.35 * BOX + d).astype(np.float32)
+    ll = 0.05
+    g = _cells_per_axis(m + 300, BOX, ll)
+    assert g >= 4
+
+    def in_blob_cell(p):
+        return (np.floor(p * (g / BOX)) == np.floor(0.35 * g)).all(axis=1)
+
+    others = _uniform(400, seed=32)
+    x = np.concatenate([blob, others[~in_blob_cell(others)][:300]])
+    x = x[rng.permutation(len(x))]
+    assert len(x) == m + 300 and in_blob_cell(x).sum() == m
+    labels = _check(x, BOX, ll)
+    assert np.bincount(labels).max() > 1
 
 
 @functools.lru_cache(maxsize=None)

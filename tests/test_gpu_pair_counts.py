@@ -6,6 +6,7 @@ Grids the cases reach (G cells per axis: the largest with cells no smaller than 
 capped by cbrt(N) and 256): one cell (radius L / 2, N = 1 and 2), G = 2 and 3 (all cells of an axis walked once: a
 wrapped 3-cell walk would meet a cell twice), powers of two (4, 8, 16) and others (6, 7, 10, 19) under the 27-cell walk."""
 import functools
+import math
 
 import numpy as np
 import pytest
@@ -108,6 +109,45 @@ def test_a_blob_puts_several_workgroups_of_queries_in_one_cell():
     y = _uniform(500, seed=13)
     assert torch.equal(_cross(y, x, BOX, edges).cpu(), _want(pcc.cross_counts(y, x, BOX, edges)))
     assert torch.equal(_cross(x, y, BOX, edges).cpu(), _want(pcc.cross_counts(x, y, BOX, edges)))
+
+
+def _cells_per_axis(partners, box, reach):
+    """Restates the grid rule (``pair_cells_per_axis`` of csrc/pair_walk.hpp) with the pair counter's caps, G^3 <= partners
+    and G <= 256."""
+    cap = 1
+    while cap < 256 and (cap + 1) ** 3 <= partners:
+        cap += 1
+    g = math.floor(box / (float(np.float32(reach)) * (1 + 1e-5) + 2e-5 * box))
+    return max(1, min(g, 256, cap))
+
+
+@pytest.mark.parametrize("m", [256, 257, 512])
+def test_a_cell_of_exactly_full_work_items(m):
+    """m queries in one cell and nobody else in it: one full item, a full item and one query, two full items.  The cell
+    is alone under the grid of the auto count (and of a cross count whose partners are x) and under the grid that y's
+    500 partners make, so cross(x, y) walks the same full items."""
+    rng = np.random.default_rng(21 + m)
+    d = rng.standard_normal((m, 3))
+    d *= (0.01 * BOX * rng.random((m, 1)) ** (1 / 3)) / np.linalg.norm(d, axis=1, keepdims=True)
+    blob = (0.35 * BOX + d).astype(np.float32)
+    edges = np.geomspace(1e-3 * BOX, 0.05 * BOX, 13).astype(np.float32)
+    y = _uniform(500, seed=23)
+    grids = (_cells_per_axis(m + 300, BOX, edges[-1]), _cells_per_axis(len(y), BOX, edges[-1]))
+    assert min(grids) >= 4
+
+    def in_blob_cell(p, g):
+        return (np.floor(p * (g / BOX)) == np.floor(0.35 * g)).all(axis=1)
+
+    others = _uniform(400, seed=22)
+    others = others[~(in_blob_cell(others, grids[0]) | in_blob_cell(others, grids[1]))][:300]
+    x = np.concatenate([blob, others])
+    x = x[rng.permutation(len(x))]
+    assert len(x) == m + 300
+    for g in grids:
+        assert in_blob_cell(x, g).sum() == m
+    assert torch.equal(_auto(x, BOX, edges).cpu(), _want(pcc.auto_counts(x, BOX, edges)))
+    assert torch.equal(_cross(x, y, BOX, edges).cpu(), _want(pcc.cross_counts(x, y, BOX, edges)))
+    assert torch.equal(_cross(y, x, BOX, edges).cpu(), _want(pcc.cross_counts(y, x, BOX, edges)))
 
 
 def test_partners_at_the_last_radius_test_the_reach_margin():
