@@ -53,6 +53,7 @@ EXPORTS = (
     "cgnn_fof_labels_workspace_bytes", "cgnn_fof_labels", "cgnn_fof_catalogue", "cgnn_mass_assign_backward",
     "cgnn_mass_assign_weighted", "cgnn_mass_assign_weighted_backward",
     "cgnn_halo_match_workspace_bytes", "cgnn_halo_match", "cgnn_fof_group_sums",
+    "cgnn_halo_profiles_workspace_bytes", "cgnn_halo_profiles",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
@@ -66,6 +67,8 @@ FOF_MAX_BINS = 256            # CGNN_SIZE_MAX_BINS in csrc/cgnn_util.hpp
 FOF_DISP_UNITS = 1 << 30      # cgnn_fof_catalogue: disp counts displacements in box_size / 2^30
 HALO_MATCH_COLS = 6           # CGNN_HM_COLS in csrc/halo_match.hip: columns of the summary of cgnn_halo_match
 GROUP_SUMS_MAX_CHANNELS = 4   # CGNN_GS_MAX_CHANNELS
+HALO_PROFILES_MAX_BINS = 32   # CGNN_HP_MAX_BINS in csrc/halo_profiles.hip
+HALO_PROFILES_MAX_CHANNELS = 4   # CGNN_HP_MAX_CHANNELS
 KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -174,6 +177,10 @@ def load() -> C.CDLL:
     lib.cgnn_halo_match.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), i32, vp, vp, sz,
                                     vp]                                                     # size_edges: host memory
     lib.cgnn_fof_group_sums.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.cgnn_halo_profiles_workspace_bytes.restype = sz
+    lib.cgnn_halo_profiles_workspace_bytes.argtypes = [i64, i64]
+    lib.cgnn_halo_profiles.argtypes = [vp, i64, vp, i64, f32, C.POINTER(f32), i32, vp, i32, vp, vp, vp, sz,
+                                       vp]                                                  # edges: host memory
     lib.cgnn_power_bin_ids.argtypes = [i32, C.POINTER(f32), i32, vp, vp]                        # k_edges: host memory
     lib.cgnn_power_bins_workspace_bytes.restype = sz
     lib.cgnn_power_bins_workspace_bytes.argtypes = [i64, i32]

@@ -1,7 +1,7 @@
 // All pairs of a periodic box closer than a reach, walked over the Morton cell grid of cell_grid.hpp: what the pair
-// counter (pair_counts.hip) and the group finder (fof.hip) share.  The grid rule, a particle set sorted by cell, the table
-// of work items, the squared distance of the counting contract, and the walk itself; a kernel adds only what it does with
-// a (query, candidate, d2) triple.
+// counter (pair_counts.hip), the group finder (fof.hip) and the halo profiles (halo_profiles.hip) share.  The grid rule,
+// a particle set sorted by cell, the table of work items, the squared distance of the counting contract, and the walk
+// itself; a kernel adds only what it does with a (query, candidate, d2) triple.
 //
 // THE CONTRACT'S DISTANCE rounds every float32 operation once (pair_d2 below).  hipcc's default (-ffp-contract=fast)
 // fuses fl32(x x) + fl32(y y) into an fma even when the operands come from __fmul_rn / __fadd_rn (they are inline
@@ -180,23 +180,30 @@ __device__ __forceinline__ float pair_d2(const float4& a, const float4& b, float
 }
 
 // Every query of the sorted set A against every particle of the sorted set B (the same grid; B may be A) in the 27
-// cells around the query's, for a workgroup of QCHUNK threads.  The persistent workgroup strides over the items.  Per
-// item it stages the queries in LDS, lists the at most 27 partner ranges of the neighbourhood (when G <= 3 all G cells
-// of an axis, each once), and runs the concatenated candidates through in tiles of one candidate per lane (a coalesced
-// float4 from the sorted array, kept in registers) against every staged query (an LDS broadcast read): every partner of
-// the neighbourhood is read once per item instead of once per query.  The walk only proposes; pair_d2 goes with every
-// proposal and the caller decides.
+// cells around the query's, for a workgroup of TILE threads (at least the 27 that stage the ranges).  The persistent
+// workgroup strides over the items.  Per item it stages the up to QCHUNK <= TILE queries in LDS, lists the at most 27
+// partner ranges of the neighbourhood (when G <= 3 all G cells of an axis, each once), and runs the concatenated
+// candidates through in tiles of one candidate per lane (a coalesced float4 from the sorted array, kept in registers)
+// against every staged query (an LDS broadcast read): every partner of the neighbourhood is read once per item instead
+// of once per query.  The walk only proposes; pair_d2 goes with every proposal and the caller decides.
 //   before_tile(nq)                 uniform over the workgroup, ahead of each tile of an item with nq queries; may
 //                                   contain barriers
 //   visit(a, b, d2, qi, p, q0)      query a (the qi-th of the item, sorted slot q0 + qi of A) and candidate b (sorted
 //                                   slot p of B)
+//   after_item(q0, nq)              uniform over the workgroup, behind the last tile of an item (also of one without
+//                                   candidates); may contain barriers
 // The callables get scalars and float4 values only: what they reach beyond that, they capture themselves.
-template <int QCHUNK, typename BeforeTile, typename Visit>
-__device__ __forceinline__ void pair_walk(const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a,
-                                          const int32_t* __restrict__ cell_of_a, const float4* __restrict__ sorted_b,
-                                          const int32_t* __restrict__ start_b, const int32_t* __restrict__ chunk_start,
-                                          const int32_t* __restrict__ item_q0, int cells, int G, float box, float half,
-                                          BeforeTile before_tile, Visit visit) {
+// pair_walk<QCHUNK> is the walk of the pair counter and the group finder: as many queries per item as threads, nothing
+// kept per item.  pair_walk_tiled<QCHUNK, TILE> lets a kernel with state per query (the halo profiles: a histogram
+// each) take few queries per item with a full workgroup of candidates per tile.
+template <int QCHUNK, int TILE, typename BeforeTile, typename Visit, typename AfterItem>
+__device__ __forceinline__ void pair_walk_tiled(const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a,
+                                                const int32_t* __restrict__ cell_of_a,
+                                                const float4* __restrict__ sorted_b, const int32_t* __restrict__ start_b,
+                                                const int32_t* __restrict__ chunk_start,
+                                                const int32_t* __restrict__ item_q0, int cells, int G, float box,
+                                                float half, BeforeTile before_tile, Visit visit, AfterItem after_item) {
+    static_assert(QCHUNK <= TILE && TILE >= CGNN_PAIR_RANGES, "the first threads stage the queries and the ranges");
     __shared__ float4 q_s[QCHUNK];
     __shared__ int rng_p0[CGNN_PAIR_RANGES], rng_len[CGNN_PAIR_RANGES], rng_off[CGNN_PAIR_RANGES + 1];
     const int tid = threadIdx.x;
@@ -210,7 +217,7 @@ __device__ __forceinline__ void pair_walk(const float4* __restrict__ sorted_a, c
         if (tid < nq) q_s[tid] = sorted_a[q0 + tid];
         cell_grid_stage_ranges<CGNN_PAIR_RANGES>(tid, cx, cy, cz, G, start_b, rng_p0, rng_len, rng_off);
         const int nc = rng_off[CGNN_PAIR_RANGES];
-        for (int t0 = 0; t0 < nc; t0 += QCHUNK) {
+        for (int t0 = 0; t0 < nc; t0 += TILE) {
             before_tile(nq);
             const int t = t0 + tid;
             if (t < nc) {
@@ -224,7 +231,18 @@ __device__ __forceinline__ void pair_walk(const float4* __restrict__ sorted_a, c
                 }
             }
         }
+        after_item(q0, nq);
     }
+}
+
+template <int QCHUNK, typename BeforeTile, typename Visit>
+__device__ __forceinline__ void pair_walk(const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a,
+                                          const int32_t* __restrict__ cell_of_a, const float4* __restrict__ sorted_b,
+                                          const int32_t* __restrict__ start_b, const int32_t* __restrict__ chunk_start,
+                                          const int32_t* __restrict__ item_q0, int cells, int G, float box, float half,
+                                          BeforeTile before_tile, Visit visit) {
+    pair_walk_tiled<QCHUNK, QCHUNK>(sorted_a, start_a, cell_of_a, sorted_b, start_b, chunk_start, item_q0, cells, G, box,
+                                    half, before_tile, visit, [](int, int) {});
 }
 
 }  // namespace cgnn

@@ -1325,7 +1325,7 @@ def fof_labels(pos: torch.Tensor, box_size: float, linking_length: float, *, che
     Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host synchronisation, the default
     verifies nothing.  ``linking_length`` is a host value (:func:`check_linking_length`).  One box per call, positions
     only: batches of simulations (``offsets``), spatial shards (an owned-storage rollout goes through
-    ``dist.assemble_frames`` first), unbinding, spherical-overdensity masses and velocities are out of scope."""
+    ``dist.assemble_frames`` first), unbinding and velocities are out of scope (radial profiles: :func:`halo_profiles`)."""
     what = "fof_labels"
     ll = check_linking_length(linking_length, box_size, what)
     pos = f32c(pos, "pos")
@@ -1430,7 +1430,7 @@ def halo_match(labels_a: torch.Tensor, size_a: torch.Tensor, labels_b: torch.Ten
     Integers throughout: the same bits on every run, whatever the order of the threads.  Labels outside ``[0, N)`` are
     ignored.  Refused on the host before any device work (``ValueError``): tensors that are not integers or not of one
     shape ``[N]`` / ``[T, N]`` with ``N >= 1``, a minimum that is no whole number of at least 1, bad ``size_edges``.  No
-    host synchronisation.  Membership only, one box, one device: no unbinding, no spherical-overdensity masses, no
+    host synchronisation.  Membership only, one box, one device: no unbinding, no
     merger trees over more than two frames."""
     what = "halo_match"
     min_a = check_min_members(min_members, what)
@@ -1526,6 +1526,106 @@ def fof_group_sums(labels: torch.Tensor, values: torch.Tensor, value_scale=None)
     if flat:
         sums = sums.squeeze(-1)
     return (sums if batched else sums[0]), scale
+
+
+def check_profile_edges(edges, box_size: float, who: str) -> List[float]:
+    """The radii of :func:`halo_profiles` as float32 host values, or ``ValueError``: the rules of
+    :func:`check_pair_count_edges` with at most 32 bins (``_lib.HALO_PROFILES_MAX_BINS``: a centre's histogram is a row of
+    LDS counters)."""
+    e = check_pair_count_edges(edges, box_size, who)
+    if len(e) - 1 > _lib.HALO_PROFILES_MAX_BINS:
+        raise ValueError(f"{who}: {len(e) - 1} bins; one call takes 1 to {_lib.HALO_PROFILES_MAX_BINS}")
+    return e
+
+
+def halo_profiles(pos: torch.Tensor, centres: torch.Tensor, box_size: float, edges, values: Optional[torch.Tensor] = None,
+                  value_scale=None, *, check_bounds: bool = False):
+    """The particles around each of a few hundred centres by radius, one histogram PER CENTRE (``cgnn_halo_profiles``):
+    ``pos [N, 3]`` with ``centres [H, 3]``, or ``[T, N, 3]`` with ``[T, H, 3]`` (one call per frame on the same stream, no
+    host synchronisation between them).  ``edges``: ``nb + 1`` ascending radii (host values, ``nb <= 32``, otherwise the
+    rules of :func:`pair_counts`).  Returns ``counts`` int64 ``[(T,) H, nb]``: the particles with ``e2[b] <= d2 < e2[b +
+    1]``, ``e2 = fl32(edges ** 2)`` and ``d2`` the float32 minimum-image squared distance of ``include/cgnn.h`` from the
+    centre to the particle.  A centre is no particle: nothing is excluded, and a particle exactly at a centre counts
+    (in bin 0) iff ``edges[0] == 0``.  ``counts.sum(-2)`` equals ``pair_counts(centres, box_size, edges, pos_b=pos)`` bit
+    for bit.
+
+    With ``values`` (``[(T,) N]`` or ``[(T,) N, C]``, ``1 <= C <= 4``) returns ``(counts, sums)``, ``sums`` int64 ``[(T,) H, nb]``
+    (``[(T,) H, nb, C]``): the sum of the particles' integer weights per shell.  Float values are quantised by
+    :func:`quantize_weights` exactly as in :func:`fof_group_sums` (2^20 per ``value_scale``; ``None``: the largest
+    ``|value|`` of the call, taken on the device; a caller who needs the scale passes it); int32 values are taken as
+    quantised already (``value_scale`` must then be ``None``).  A shell's mean value is ``sums / counts * value_scale /
+    2^20``.
+
+    Positions and centres lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host synchronisation,
+    the default verifies nothing (a non-finite centre is outside the contract).  Integers and integer atomics only:
+    the same bits on every run.  No host synchronisation.  One box per call: no ``offsets`` batches, no spatial shards
+    (``dist.assemble_frames`` first)."""
+    what = "halo_profiles"
+    e = check_profile_edges(edges, box_size, what)
+    nb = len(e) - 1
+    if not torch.is_tensor(pos) or pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got "
+                         f"{tuple(pos.shape) if torch.is_tensor(pos) else pos!r}")
+    batched = pos.dim() == 3
+    if not torch.is_tensor(centres) or centres.dim() != pos.dim() or centres.shape[-1] != 3 or centres.shape[-2] < 1 or \
+            (batched and centres.shape[0] != pos.shape[0]):
+        raise ValueError(f"{what}: centres must be [H, 3] (or [T, H, 3] with pos's T) with H >= 1, got "
+                         f"{tuple(centres.shape) if torch.is_tensor(centres) else centres!r} for pos {tuple(pos.shape)}")
+    q = None
+    flat = False
+    if values is not None:
+        lead = tuple(pos.shape[:-1])
+        if not torch.is_tensor(values) or values.dim() not in (pos.dim() - 1, pos.dim()) or \
+                tuple(values.shape[:pos.dim() - 1]) != lead or values.is_complex() or values.dtype == torch.bool:
+            raise ValueError(f"{what}: values must be a real tensor {list(lead)} or {list(lead) + ['C']} for pos "
+                             f"{tuple(pos.shape)}, got {tuple(values.shape) if torch.is_tensor(values) else values!r}")
+        flat = values.dim() == pos.dim() - 1
+        vals = values.unsqueeze(-1) if flat else values
+        if not 1 <= vals.shape[-1] <= _lib.HALO_PROFILES_MAX_CHANNELS:
+            raise ValueError(f"{what}: {vals.shape[-1]} channels; one call takes 1 to {_lib.HALO_PROFILES_MAX_CHANNELS}")
+        if vals.dtype == torch.int32:
+            if value_scale is not None:
+                raise ValueError(f"{what}: int32 values are quantised weights already; value_scale must be None")
+            q = vals
+        else:
+            if not (vals.is_floating_point() or vals.dtype == torch.int64):
+                raise ValueError(f"{what}: values must be float values or int32 quantised weights, got {vals.dtype}")
+            scale = None if value_scale is None else _check_value_scale(value_scale, what)
+            require_device(vals, "values")
+            q = quantize_weights(vals, _max_abs_scale(vals) if scale is None else scale)
+        q = i32c(q, "values")
+    elif value_scale is not None:
+        raise ValueError(f"{what}: value_scale without values")
+    pos = f32c(pos, "pos")
+    centres = f32c(centres, "centres")
+    _same_device(pos, centres, q)
+    if check_bounds:
+        for name, p in (("pos", pos), ("centres", centres)):
+            if not bool(((p >= 0) & (p <= float(box_size))).all()):
+                raise ValueError(f"{what}: {name} leaves [0, box_size]")
+    frames, cen = (pos, centres) if batched else (pos.unsqueeze(0), centres.unsqueeze(0))
+    if q is not None and not batched:
+        q = q.unsqueeze(0)
+    t, n, h = frames.shape[0], frames.shape[1], cen.shape[1]
+    c = 0 if q is None else q.shape[-1]
+    lib = _lib.load()
+    edges_c = (C.c_float * (nb + 1))(*e)
+    ws_bytes = lib.cgnn_halo_profiles_workspace_bytes(n, h)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+    counts = torch.empty((t, h, nb), dtype=torch.int64, device=pos.device)
+    sums = None if q is None else torch.empty((t, h, nb, c), dtype=torch.int64, device=pos.device)
+    st = stream_ptr(pos.device)
+    with _timed(what, pos.device):
+        for f in range(t):
+            check(lib.cgnn_halo_profiles(frames[f].data_ptr(), n, cen[f].data_ptr(), h, float(box_size), edges_c, nb,
+                                         None if q is None else q[f].data_ptr(), c, counts[f].data_ptr(),
+                                         None if sums is None else sums[f].data_ptr(), ws.data_ptr(), ws_bytes, st),
+                  "cgnn_halo_profiles")
+    if sums is None:
+        return counts if batched else counts[0]
+    if flat:
+        sums = sums.squeeze(-1)
+    return (counts, sums) if batched else (counts[0], sums[0])
 
 
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,

@@ -26,8 +26,12 @@ groups: the predicted and the true frame hold the same particles under the same 
 the groups of two frames by the members they share (``ops.halo_match``; a pair is mutual when each is the other's
 best partner), with sizes, centre offsets and, given per-particle values such as the temperature, each group's mean
 (``ops.fof_group_sums``), and ``rollout_halo_matching`` gives per frame and per size bin of the true groups the
-completeness, the shared fraction and the size ratio.  Membership only: unbinding, spherical-overdensity masses,
-velocities and merger trees over more than two frames are out of scope.
+completeness, the shared fraction and the size ratio.  What is inside a halo, which neither tells (an emulator gets the
+number and the membership of its halos about right and smears their interiors): ``halo_profiles`` gives per group the
+radial density profile around its centre (``ops.halo_profiles``, one histogram per centre), with per-particle values the
+mean value per shell, and from the profile the spherical-overdensity radius and mass (``so_masses``);
+``rollout_halo_profiles`` stacks the profiles of the largest groups by size for every frame of a rollout and of the
+truth.  Unbinding, velocities and merger trees over more than two frames are out of scope.
 
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
@@ -609,8 +613,8 @@ def halo_catalogue(pos: torch.Tensor, box_size: float, linking_length: Optional[
       meaningful centre).
 
     The number of groups is only known on the device: this function synchronises once (``nonzero``) after the kernels
-    and before its single transfer.  Positions only: no unbinding, no spherical-overdensity masses, no velocities; one
-    box, no spatial shards (``dist.assemble_frames`` first)."""
+    and before its single transfer.  Positions only: no unbinding, no velocities (profiles and spherical-overdensity
+    masses: :func:`halo_profiles`); one box, no spatial shards (``dist.assemble_frames`` first)."""
     what = "halo_catalogue"
     if pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
         raise ValueError(f"{what}: pos must be one frame [N, 3] with N >= 1, got {tuple(pos.shape)}")
@@ -667,7 +671,7 @@ def halo_mass_function(pos: torch.Tensor, box_size: float, linking_length: Optio
       (beyond the last edge too) and the fraction of the particles they hold;  ``largest``: the largest group.
 
     Everything is computed on the device of ``pos`` without a host synchronisation and comes back in one transfer.
-    One box per call, positions only (no unbinding, spherical-overdensity masses or velocities; no ``offsets``
+    One box per call, positions only (no unbinding or velocities; no ``offsets``
     batches; no spatial shards: ``dist.assemble_frames`` first)."""
     what = "halo_mass_function"
     frames = _frames3(pos, "pos", what)
@@ -696,7 +700,7 @@ def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth:
 
     plus ``frames``, ``size_lo`` and ``size_hi``.  No synchronisation per frame; the results come back in one packed
     transfer.  The two frames' halos are not matched with each other here (:func:`rollout_halo_matching` does that); no
-    unbinding, spherical-overdensity masses or velocities; one box, no spatial shards (an owned-storage rollout goes
+    unbinding or velocities; one box, no spatial shards (an owned-storage rollout goes
     through ``dist.assemble_frames`` first)."""
     what = "rollout_halo_statistics"
     pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
@@ -744,8 +748,7 @@ def halo_matches(pos_a: torch.Tensor, pos_b: torch.Tensor, box_size: float, link
       ``match_mean_value``, the partner's mean over its members in frame B, ``nan`` without a match.
 
     The number of groups is only known on the device: one synchronisation (``nonzero``) after the kernels and one
-    transfer, as :func:`halo_catalogue`.  One box, one device, membership only: no unbinding, no spherical-overdensity
-    masses, no merger trees over more than two frames; no spatial shards (``dist.assemble_frames`` first)."""
+    transfer, as :func:`halo_catalogue`.  One box, one device, membership only: no unbinding, no merger trees over more than two frames; no spatial shards (``dist.assemble_frames`` first)."""
     what = "halo_matches"
     for pos, name in ((pos_a, "pos_a"), (pos_b, "pos_b")):
         if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
@@ -863,7 +866,7 @@ def rollout_halo_matching(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     ``n_unmatched_pred`` (the listed predicted groups without a mutual partner), plus ``frames``, ``size_lo`` and
     ``size_hi``.  The ratios are formed on the host from the integer sums.  No synchronisation per frame, one packed
     transfer.  Arguments and refusals are those of :func:`rollout_halo_statistics`.  One box, one device, membership
-    only: no unbinding, no spherical-overdensity masses, no merger trees over more than two frames; an owned-storage
+    only: no unbinding, no merger trees over more than two frames; an owned-storage
     rollout goes through ``dist.assemble_frames`` first."""
     what = "rollout_halo_matching"
     pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
@@ -883,3 +886,303 @@ def rollout_halo_matching(rollout_data: Dict[str, torch.Tensor], ground_truth: D
             "shared_fraction": shared / size_true, "size_ratio": size_pred / size_true,
             "n_groups_true": out[:, base].clone(), "n_groups_pred": out[:, base + 1].clone(),
             "n_unmatched_pred": out[:, base + 1] - out[:, base + 2]}
+
+
+def default_radial_edges(n: int, box_size: float) -> torch.Tensor:
+    """The default radii of the halo profiles: 0, then 24 log-spaced radii from 0.05 to 8 mean interparticle spacings
+    ``box_size / n ** (1 / 3)``, without those above ``fl32(0.5 * box_size)`` (the profile kernel's reach); at least two
+    edges remain, since 0.05 spacings never exceed a twentieth of the box.  Float32 values as float64, ascending."""
+    if int(n) < 1:
+        raise ValueError(f"default_radial_edges: n must be at least 1, got {n!r}")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"default_radial_edges: box_size must be positive and finite, got {box_size!r}")
+    spacing = float(box_size) / float(n) ** (1.0 / 3.0)
+    r = (spacing * torch.logspace(math.log10(0.05), math.log10(8.0), 24, dtype=torch.float64)).to(torch.float32)
+    r = r[r <= box * 0.5]
+    return torch.cat([torch.zeros(1, dtype=torch.float32), r]).to(torch.float64)
+
+
+def _profile_edges(edges, n: int, box_size: float, what: str):
+    """The radii of a profile (default :func:`default_radial_edges`) as checked host floats and as float64; they start
+    at 0, as the cumulative counts of :func:`so_masses` need."""
+    e = ops.check_profile_edges(default_radial_edges(n, box_size) if edges is None else edges, box_size, what)
+    if e[0] != 0.0:
+        raise ValueError(f"{what}: edges[0] must be 0 (the spherical-overdensity mass counts every particle inside a "
+                         f"radius), got {e[0]}")
+    return e, torch.tensor(e, dtype=torch.float64)
+
+
+def halo_centres_on_device(pos: torch.Tensor, size: torch.Tensor, disp: torch.Tensor, roots: torch.Tensor,
+                           box_size: float):
+    """:func:`halo_centres` on the device, for the kernels that take centres: ``(pos[root] + disp[root] / size[root] * L
+    / 2^30) mod L`` in float64 (``L`` the float32 value of ``box_size``), rounded to float32.  ``pos [N, 3]``, ``size [N]``
+    and ``disp [N, 3]`` as ``ops.fof_catalogue`` gives them, ``roots`` int64 ``[H]``; or all with one leading frame axis.
+    Returns ``(centres, valid)``: float32 ``[H, 3]`` in ``[0, L]`` (the rounding may reach ``L``) and bool ``[H]``.  A row
+    whose ``size[root] < 1`` (no root slot) has no centre: it is set to 0 and ``valid`` is false there, so that a kernel
+    never sees a non-finite centre.  No host synchronisation."""
+    box = float(torch.tensor(float(box_size), dtype=torch.float32))
+    idx = roots.to(torch.int64)
+    s = torch.take_along_dim(size, idx, dim=-1)
+    valid = s >= 1
+    idx3 = idx.unsqueeze(-1).expand(*idx.shape, 3)
+    rp = torch.take_along_dim(pos, idx3, dim=-2).to(torch.float64)
+    d = torch.take_along_dim(disp, idx3, dim=-2).to(torch.float64)
+    c = torch.remainder(rp + d / s.clamp(min=1).to(torch.float64).unsqueeze(-1) * (box / _lib.FOF_DISP_UNITS), box)
+    c = c.to(torch.float32)
+    return torch.where(valid.unsqueeze(-1), c, torch.zeros_like(c)), valid
+
+
+def so_masses(counts: torch.Tensor, n: int, box_size: float, edges, delta: float = 200.0):
+    """Spherical-overdensity radius and mass from a radial profile: ``counts [..., nb]`` (the counts of
+    ``ops.halo_profiles``; ``n`` particles in the box) -> ``(r_delta, m_delta)``, float64 ``[...]`` on the device of
+    ``counts``, ``m_delta`` in particles.  ``edges[0]`` must be 0 (``ValueError``).  The rule:
+
+    * ``N_i`` = the particles inside ``edges[i]`` (the cumulative sum of the counts), and for ``i >= 1`` the mean enclosed
+      density over the mean density of the box, ``D_i = N_i / (n * 4/3 pi edges[i]^3 / L^3)``;
+    * ``i*`` = the first ``i >= 1`` with ``D_i >= delta``, and ``k`` = the first ``k > i*`` with ``D_k < delta``;
+    * ``r_delta`` lies between ``edges[k - 1]`` and ``edges[k]``, where ``D`` crosses ``delta`` on the straight line through
+      ``(log r, log D)`` at the two edges; ``m_delta = delta * n / L^3 * 4/3 pi r_delta^3``.
+
+    ``nan`` where there is no ``i*`` (the halo is too diffuse for ``delta`` at every edge) or no ``k`` (the profile does not
+    reach out far enough).  An empty core (``D_1 < delta``) is passed over: the search for ``k`` begins at ``i*``.  The
+    limit of the rule: everything inside a radius counts, so a heavier neighbour inside the last edge can keep ``D``
+    above ``delta`` and move the crossing outward (no unbinding, no exclusion of other halos).  Cumulative sums and
+    comparisons in float64 torch: no host synchronisation."""
+    what = "so_masses"
+    r = _radii(edges, box_size, what)
+    if float(r[0]) != 0.0:
+        raise ValueError(f"{what}: edges[0] must be 0 (N_i counts every particle inside edges[i]), got {float(r[0])}")
+    if not (isinstance(delta, (int, float)) and not isinstance(delta, bool) and math.isfinite(delta) and delta > 0):
+        raise ValueError(f"{what}: delta must be a positive finite number, got {delta!r}")
+    if not torch.is_tensor(counts) or counts.dim() < 1 or counts.shape[-1] != r.numel() - 1:
+        raise ValueError(f"{what}: counts must be [..., {r.numel() - 1}] for {r.numel()} edges, got "
+                         f"{tuple(counts.shape) if torch.is_tensor(counts) else counts!r}")
+    nb = r.numel() - 1
+    r = r[1:].contiguous()                                                # edges[1 .. nb]: column j is edge j + 1
+    if counts.is_cuda:                                                    # pinned + non_blocking: no synchronisation
+        r = r.pin_memory().to(counts.device, non_blocking=True)
+    rho = float(n) / float(box_size) ** 3
+    dens = torch.cumsum(counts.to(torch.float64), dim=-1) / (rho * (4.0 / 3.0 * math.pi) * r ** 3)
+    above = dens >= float(delta)
+    seen = torch.cumsum(above.to(torch.int64), dim=-1) > 0                # at or behind i*
+    cand = seen & ~above                                                  # behind i* and below delta
+    k = (torch.cumsum(cand.to(torch.int64), dim=-1) == 0).sum(dim=-1)     # the columns ahead of the first one: k - 1
+    found = k < nb
+    if nb == 1:                                                           # one edge: never a k behind an i*
+        r_delta = torch.full(dens.shape[:-1], float("nan"), dtype=torch.float64, device=dens.device)
+        return r_delta, r_delta.clone()
+    k = k.clamp(min=1, max=nb - 1).unsqueeze(-1)                          # k >= 1 where found; elsewhere any column
+    d0, d1 = torch.gather(dens, -1, k - 1).squeeze(-1), torch.gather(dens, -1, k).squeeze(-1)
+    lr = torch.log(r).expand(*dens.shape[:-1], nb)
+    l0, l1 = torch.gather(lr, -1, k - 1).squeeze(-1), torch.gather(lr, -1, k).squeeze(-1)
+    r_delta = torch.exp(l0 + (math.log(float(delta)) - torch.log(d0)) / (torch.log(d1) - torch.log(d0)) * (l1 - l0))
+    r_delta = torch.where(found, r_delta, torch.full_like(r_delta, float("nan")))
+    return r_delta, float(delta) * rho * (4.0 / 3.0 * math.pi) * r_delta ** 3
+
+
+def _shell_volumes(r: torch.Tensor) -> torch.Tensor:
+    return 4.0 * math.pi / 3.0 * (r[1:] ** 3 - r[:-1] ** 3)
+
+
+def halo_profiles(pos: torch.Tensor, box_size: float, edges=None, linking_length: Optional[float] = None,
+                  min_members: int = 20, values: Optional[torch.Tensor] = None, delta: float = 200.0) -> Dict:
+    """What is INSIDE the halos of one frame ``pos [N, 3]``: around the centre of every friends-of-friends group with at
+    least ``min_members`` members (the steps of :func:`halo_catalogue`) the particles of the whole frame by radius
+    (``ops.halo_profiles``; ``edges``: default :func:`default_radial_edges`, at most 32 bins, ``edges[0] == 0``), and from
+    that profile the spherical-overdensity radius and mass (:func:`so_masses`).  Returns on the CPU, sorted as
+    :func:`halo_catalogue` sorts (size descending, then root ascending):
+
+    * ``root``, ``size`` int64 ``[H]``; ``centre`` float64 ``[H, 3]``: the float32 centres the kernel used
+      (:func:`halo_centres_on_device`), widened;
+    * ``r_lo``, ``r_hi`` float64 ``[nb]``; ``counts`` int64 ``[H, nb]``: the particles per shell, members or not;
+    * ``density`` float64 ``[H, nb]``: the counts over ``n * V_shell / L^3``, the density in units of the mean density;
+    * with ``values`` (``[N]`` or ``[N, C]``, ``C <= 4``, e.g. the temperature): ``mean_value`` float64 ``[H, nb]`` (``[H, nb,
+      C]``), the mean over the particles of the shell, exact up to the quantisation to 2^-20 of the largest ``|value|``
+      (int32 values are taken as quantised weights, in units of their scale); ``nan`` in an empty shell;
+    * ``r_delta``, ``m_delta`` float64 ``[H]``: :func:`so_masses` for ``delta``, ``nan`` where undefined.
+
+    The number of groups is only known on the device: one synchronisation (``nonzero``) and one transfer, as
+    :func:`halo_catalogue`.  One box, one device; no unbinding (every particle inside a radius counts); no spatial
+    shards (``dist.assemble_frames`` first), no ``offsets`` batches."""
+    what = "halo_profiles"
+    if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be one frame [N, 3] with N >= 1, got "
+                         f"{tuple(pos.shape) if torch.is_tensor(pos) else pos!r}")
+    min_members = ops.check_min_members(min_members, what)
+    n = pos.shape[0]
+    e, r = _profile_edges(edges, n, box_size, what)
+    nb = len(e) - 1
+    ll = default_linking_length(n, box_size) if linking_length is None else linking_length
+    ops.check_linking_length(ll, box_size, what)
+    values = _group_values(values, n, "values", what)
+    so_masses(torch.zeros(nb), n, box_size, e, delta)                     # refuses a bad delta before device work
+    labels = ops.fof_labels(pos, box_size, ll)
+    size, disp, _ = ops.fof_catalogue(pos, labels, box_size)
+    root = torch.nonzero(size >= min_members).reshape(-1)                 # the one synchronisation
+    h = root.numel()
+    c = 0 if values is None else (1 if values.dim() == 1 else values.shape[1])
+    shell = n * _shell_volumes(r) / float(box_size) ** 3
+    nan = float("nan")
+    if h == 0:
+        res = {"root": torch.zeros(0, dtype=torch.int64), "size": torch.zeros(0, dtype=torch.int64),
+               "centre": torch.zeros((0, 3), dtype=torch.float64), "r_lo": r[:-1].clone(), "r_hi": r[1:].clone(),
+               "counts": torch.zeros((0, nb), dtype=torch.int64), "density": torch.zeros((0, nb), dtype=torch.float64),
+               "r_delta": torch.zeros(0, dtype=torch.float64), "m_delta": torch.zeros(0, dtype=torch.float64)}
+        if values is not None:
+            res["mean_value"] = torch.zeros((0, nb) if values.dim() == 1 else (0, nb, c), dtype=torch.float64)
+        return res
+    centres, _ = halo_centres_on_device(pos, size, disp, root, box_size)
+    scale = None
+    if values is None:
+        counts = ops.halo_profiles(pos, centres, box_size, e)
+    elif values.dtype == torch.int32:
+        counts, sums = ops.halo_profiles(pos, centres, box_size, e, values.to(pos.device))
+    else:
+        values = values.to(pos.device)
+        m = values.detach().abs().max().to(torch.float64)
+        scale = torch.where(m > 0, m, torch.ones_like(m))                 # the scale ops.halo_profiles would take
+        counts, sums = ops.halo_profiles(pos, centres, box_size, e, values, scale)
+    r_delta, m_delta = so_masses(counts, n, box_size, e, delta)
+    # one transfer: the float32 centres and the float64 results travel as their bits among the integers
+    blocks = [root.reshape(h, 1), size.index_select(0, root).to(torch.int64).reshape(h, 1),
+              centres.contiguous().view(torch.int32).to(torch.int64), counts,
+              r_delta.view(torch.int64).reshape(h, 1), m_delta.view(torch.int64).reshape(h, 1)]
+    if values is not None:
+        blocks.append(sums.reshape(h, nb * c))
+    table = torch.cat(blocks, dim=1)
+    tail = [] if scale is None else [scale.reshape(1).view(torch.int64)]
+    packed = torch.cat([table.reshape(-1)] + tail).cpu()
+    table_h = packed[:table.numel()].reshape(h, table.shape[1])
+    order = sorted(range(h), key=lambda i: (-int(table_h[i, 1]), int(table_h[i, 0])))
+    table_h = table_h[torch.tensor(order, dtype=torch.int64)]
+    counts_h = table_h[:, 5:5 + nb].clone()
+    res = {"root": table_h[:, 0].clone(), "size": table_h[:, 1].clone(),
+           "centre": table_h[:, 2:5].to(torch.int32).contiguous().view(torch.float32).to(torch.float64),
+           "r_lo": r[:-1].clone(), "r_hi": r[1:].clone(), "counts": counts_h,
+           "density": counts_h.to(torch.float64) / shell,
+           "r_delta": table_h[:, 5 + nb].clone().view(torch.float64),
+           "m_delta": table_h[:, 6 + nb].clone().view(torch.float64)}
+    if values is not None:
+        unit = (1.0 if scale is None else float(packed[table.numel():].view(torch.float64))) / float(1 << _lib.WEIGHT_BITS)
+        sums_h = table_h[:, 7 + nb:].reshape(h, nb, c).to(torch.float64)
+        mean = torch.where(counts_h.unsqueeze(-1) > 0, sums_h / counts_h.clamp(min=1).unsqueeze(-1) * unit,
+                           torch.full_like(sums_h, nan))
+        res["mean_value"] = mean.reshape(h, nb) if values.dim() == 1 else mean
+    return res
+
+
+_TEMPERATURE_KEYS = ("Temperature", "InternalEnergy")   # the rollout dicts carry the temperature as InternalEnergy
+
+
+def halo_profile_stacks_on_device(frames: torch.Tensor, box_size: float, linking_length: float, size_edges, edges,
+                                  max_halos: int, delta: float, temperature: Optional[torch.Tensor] = None):
+    """The device part of :func:`rollout_halo_profiles` for one side: ``frames [F, N, 3]`` (``temperature``: the values
+    ``[F, N]`` and their scale, a 0-d device tensor) -> ``(ints, floats)``, an int64 ``[F, 1 + sb (2 + nb (1 + t))]`` tensor whose
+    rows hold the listed groups beyond
+    ``max_halos``, then per size bin the profiled groups, those with a defined ``m_delta``, the stacked counts and (``t =
+    1`` with a temperature) the stacked weight sums; and a float64 ``[F, 2 sb]`` tensor with the sums of ``m_delta`` and
+    ``r_delta`` over the groups where they are defined.  The ``max_halos`` largest listed groups are a ``topk`` of the key
+    ``size << 32 | (2^32 - 1 - root)``: ties go to the smaller root.  The sums over the groups are masked sums in a fixed
+    order, not atomics: the same bits on every run.  No host synchronisation."""
+    f, n = frames.shape[0], frames.shape[1]
+    dev = frames.device
+    nb, sb = len(edges) - 1, len(size_edges) - 1
+    labels = ops.fof_labels(frames, box_size, linking_length)
+    size, disp, _ = ops.fof_catalogue(frames, labels, box_size)
+    listed = size >= int(size_edges[0])
+    slot = torch.arange(n, dtype=torch.int64, device=dev)
+    key = torch.where(listed, (size.to(torch.int64) << 32) | ((1 << 32) - 1 - slot), torch.full_like(slot, -1))
+    kk = min(int(max_halos), n)
+    top, root = torch.topk(key, kk, dim=1)
+    taken = top >= 0                                                      # [F, K]: a listed group, not padding
+    centres, _ = halo_centres_on_device(frames, size, disp, root, box_size)
+    if temperature is None:
+        counts, sums = ops.halo_profiles(frames, centres, box_size, edges), None
+    else:
+        counts, sums = ops.halo_profiles(frames, centres, box_size, edges, temperature[0], temperature[1])
+    r_delta, m_delta = so_masses(counts, n, box_size, edges, delta)       # [F, K]
+    sz = torch.gather(size, 1, root)
+    in_bin = torch.stack([taken & (sz >= int(lo)) & (sz < int(hi)) for lo, hi in zip(size_edges[:-1], size_edges[1:])],
+                         dim=-1)                                          # [F, K, sb]
+    defined = in_bin & ~torch.isnan(m_delta).unsqueeze(-1)
+    stack = (in_bin.unsqueeze(-1) * counts.unsqueeze(2)).sum(dim=1)       # [F, sb, nb] int64
+    ints = [(listed.sum(dim=1, dtype=torch.int64) - kk).clamp(min=0).unsqueeze(1),
+            in_bin.sum(dim=1, dtype=torch.int64), defined.sum(dim=1, dtype=torch.int64), stack.reshape(f, sb * nb)]
+    if sums is not None:
+        ints.append((in_bin.unsqueeze(-1) * sums.unsqueeze(2)).sum(dim=1).reshape(f, sb * nb))
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    floats = [torch.where(defined, v.unsqueeze(-1), zero).sum(dim=1) for v in (m_delta, r_delta)]
+    return torch.cat(ints, dim=1), torch.cat(floats, dim=1)
+
+
+def rollout_halo_profiles(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                          edges=None, linking_length: Optional[float] = None, size_edges=None, max_halos: int = 1024,
+                          delta: float = 200.0, frames: Optional[Sequence[int]] = None) -> Dict:
+    """Whether a rollout gets the INSIDE of its halos right, for the dicts ``rollout.rollout`` returns (``Coordinates [T,
+    N, 3]``).  Per selected frame and per side (predicted, true) the ``max_halos`` largest friends-of-friends groups
+    with at least ``size_edges[0]`` members (ties to the smaller root) are profiled around their centres
+    (``ops.halo_profiles``; ``edges``: default :func:`default_radial_edges`) and stacked by size.  Per frame and per size
+    bin of the groups (``size_edges``: default :func:`default_size_edges`), for ``pred`` and ``true`` (CPU):
+
+    * ``n_halos_*`` int64 ``[F, sb]``: the profiled groups of the bin;
+    * ``counts_*`` int64 ``[F, sb, nb]``: their summed counts;  ``density_*`` float64: the stacked profile ``counts / (n_halos
+      n V_shell / L^3)`` in units of the mean density (``nan`` for an empty bin);
+    * ``m_delta_*``, ``r_delta_*`` float64 ``[F, sb]``: the mean of :func:`so_masses` over the groups where it is defined
+      (``nan`` without one), and ``n_delta_*`` int64: how many those are;
+    * with a temperature in both dicts (``Temperature``, or the ``InternalEnergy [T, N(, 1)]`` the rollout dicts carry):
+      ``temperature_*`` float64 ``[F, sb, nb]``, the mean temperature of the stacked shells (quantised to 2^-20 of the
+      side's largest ``|T|``; ``nan`` in an empty shell),
+
+    per frame ``not_profiled_pred``, ``not_profiled_true`` int64 ``[F]``: the listed groups beyond ``max_halos``, which are
+    in none of the sums (a truncation is never silent), plus ``frames``, ``size_lo``, ``size_hi``, ``r_lo`` and ``r_hi``.  A
+    group beyond the last size edge is profiled but in no bin.  No synchronisation per frame, one packed transfer.
+    Out of scope: profiles of matched pairs (a true halo against its partner: :func:`rollout_halo_matching` pairs
+    them), unbinding, ``offsets`` batches, and sharded or owned-storage inputs (``dist.assemble_frames`` first)."""
+    what = "rollout_halo_profiles"
+    key = next((k for k in _TEMPERATURE_KEYS if k in rollout_data and k in ground_truth), None)
+    dev = rollout_data["Coordinates"].device
+    also = () if key is None else (rollout_data[key].to(dev), ground_truth[key].to(dev))
+    got = _rollout_frames(rollout_data, ground_truth, frames, what, also)
+    pc, tc, sel = got[:3]
+    n = pc.shape[1]
+    ll, se = _halo_arguments(n, box_size, linking_length, size_edges, what)
+    e, r = _profile_edges(edges, n, box_size, what)
+    if isinstance(max_halos, bool) or not isinstance(max_halos, int) or max_halos < 1:
+        raise ValueError(f"{what}: max_halos must be a whole number of at least 1, got {max_halos!r}")
+    nb, sb, nf = len(e) - 1, len(se) - 1, len(sel)
+    so_masses(torch.zeros(nb), n, box_size, e, delta)                     # refuses a bad delta before device work
+    parts, scales = [], []
+    for side, frames_ in enumerate((pc, tc)):
+        temp = None
+        if key is not None:
+            t = _scalar_values(got[3 + side], frames_, frames_, key, what)
+            m = t.detach().abs().max().to(torch.float64)
+            scales.append(torch.where(m > 0, m, torch.ones_like(m)).reshape(1))
+            temp = (t, scales[-1].reshape(()))
+        ints, floats = halo_profile_stacks_on_device(frames_, box_size, ll, se, e, max_halos, float(delta), temp)
+        parts += [ints.reshape(-1), floats.contiguous().view(torch.int64).reshape(-1)]
+    packed = torch.cat(parts + [s.view(torch.int64) for s in scales]).cpu()                      # the one transfer
+    width_i = 1 + sb * (2 + nb * (1 + (key is not None)))
+    shell = n * _shell_volumes(r) / float(box_size) ** 3
+    sedges = torch.tensor(se, dtype=torch.int64)
+    res = {"frames": sel, "size_lo": sedges[:-1].clone(), "size_hi": sedges[1:].clone(), "r_lo": r[:-1].clone(),
+           "r_hi": r[1:].clone()}
+    at = 0
+    scales_h = packed[packed.numel() - len(scales):].view(torch.float64).tolist()
+    for side, name in enumerate(("pred", "true")):
+        ints = packed[at:at + nf * width_i].reshape(nf, width_i)
+        at += nf * width_i
+        floats = packed[at:at + nf * 2 * sb].view(torch.float64).reshape(nf, 2 * sb)
+        at += nf * 2 * sb
+        n_halos, n_def = ints[:, 1:1 + sb].clone(), ints[:, 1 + sb:1 + 2 * sb].clone()
+        counts = ints[:, 1 + 2 * sb:1 + 2 * sb + sb * nb].reshape(nf, sb, nb).clone()
+        res["not_profiled_" + name] = ints[:, 0].clone()
+        res["n_halos_" + name], res["n_delta_" + name], res["counts_" + name] = n_halos, n_def, counts
+        res["density_" + name] = counts.to(torch.float64) / (n_halos.to(torch.float64).unsqueeze(-1) * shell)
+        res["m_delta_" + name] = floats[:, :sb] / n_def.to(torch.float64)
+        res["r_delta_" + name] = floats[:, sb:] / n_def.to(torch.float64)
+        if key is not None:
+            sums = ints[:, 1 + 2 * sb + sb * nb:].reshape(nf, sb, nb).to(torch.float64)
+            res["temperature_" + name] = sums / counts.to(torch.float64) * (scales_h[side] / float(1 << _lib.WEIGHT_BITS))
+    return res

@@ -767,6 +767,32 @@ int cgnn_halo_match(const int32_t* labels_a, const int32_t* size_a, const int32_
 int cgnn_fof_group_sums(const int32_t* labels, const int32_t* q, int64_t n, int32_t channels, int64_t* sums,
                         void* stream);
 
+/* ---- inside a halo: the particles around each of many centres by radius, one histogram per centre ---------------------
+ * pos [n, 3] (device) holds the particles and centres [num_centres, 3] (device, float32) the centres, both in
+ * [0, box_size] (a value of exactly box_size falls into the edge cell; a non-finite centre is outside the contract);
+ * edges (HOST memory, num_bins + 1 floats) are the radii.  For centre h and particle p, d2 is the float32 minimum-image
+ * squared distance of cgnn_pair_counts from the centre (a) to the particle (b), one rounding per operation, no FMA; with
+ * e2[i] = fl32(edges[i] * edges[i]) the particle is in bin i of centre h iff e2[i] <= d2 < e2[i + 1].  A centre is no
+ * particle: nothing is excluded, and a particle with d2 == 0 counts, in bin 0, iff edges[0] == 0.
+ *   counts (device, int64 [num_centres, num_bins]):           the number of such particles;
+ *   sums   (device, int64 [num_centres, num_bins, channels]): the sum of q[p, :] over them (q: device, int32
+ *          [n, channels], 1 <= channels <= 4, |q| <= 2^20 as for cgnn_fof_group_sums).  q and sums are both NULL (channels
+ *          is then ignored) or both given.
+ * Both are overwritten.  Summed over the centres, counts equals what cgnn_pair_counts gives for (centres, pos) in cross
+ * mode, bit for bit.  Integers and integer atomics only: the same bits on every run.  No host synchronisation,
+ * everything on `stream`.
+ * CGNN_ERR_INVALID_ARG for a null pointer, n <= 0, num_centres <= 0, box_size not positive and finite, q without sums or
+ * the reverse, channels outside 1..4 (with q), a workspace that is not 16-byte aligned, and unless 1 <= num_bins <= 32
+ * (a centre's histogram is a row of LDS counters: the cap is lower than the 256 of cgnn_pair_counts), edges finite,
+ * edges[0] >= 0, strictly ascending, edges[num_bins] <= fl32(0.5f * box_size); 2^31 or more particles or centres:
+ * CGNN_ERR_UNSUPPORTED; a short workspace: CGNN_ERR_WORKSPACE.  Workspace: cgnn_halo_profiles_workspace_bytes(n,
+ * num_centres), a function of the two counts alone, O(n + num_centres), 16-byte aligned (256 for counts outside
+ * [1, 2^31)). */
+size_t cgnn_halo_profiles_workspace_bytes(int64_t n, int64_t num_centres);
+int cgnn_halo_profiles(const float* pos, int64_t n, const float* centres, int64_t num_centres, float box_size,
+                       const float* edges, int32_t num_bins, const int32_t* q, int32_t channels, int64_t* counts,
+                       int64_t* sums, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes
