@@ -54,6 +54,7 @@ EXPORTS = (
     "cgnn_mass_assign_weighted", "cgnn_mass_assign_weighted_backward",
     "cgnn_halo_match_workspace_bytes", "cgnn_halo_match", "cgnn_fof_group_sums",
     "cgnn_halo_profiles_workspace_bytes", "cgnn_halo_profiles",
+    "cgnn_redshift_positions", "cgnn_power_multipoles_workspace_bytes", "cgnn_power_multipoles",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
@@ -63,6 +64,7 @@ WEIGHT_BITS = 20              # CGNN_MA_WEIGHT_BITS: a quantised weight of 2^20 
 WEIGHTED_MAX_PARTICLES = 1 << 23   # n (2^39 + 14) must stay inside int64
 WEIGHTED_MAX_CHANNELS = 4     # CGNN_MA_MAX_CHANNELS
 POWER_MAX_BINS = 256          # CGNN_PB_MAX_BINS
+POWER_MULTIPOLE_SUMS = 12     # CGNN_PM_SUMS: rows of the sums of cgnn_power_multipoles
 FOF_MAX_BINS = 256            # CGNN_SIZE_MAX_BINS in csrc/cgnn_util.hpp
 FOF_DISP_UNITS = 1 << 30      # cgnn_fof_catalogue: disp counts displacements in box_size / 2^30
 HALO_MATCH_COLS = 6           # CGNN_HM_COLS in csrc/halo_match.hip: columns of the summary of cgnn_halo_match
@@ -185,6 +187,10 @@ def load() -> C.CDLL:
     lib.cgnn_power_bins_workspace_bytes.restype = sz
     lib.cgnn_power_bins_workspace_bytes.argtypes = [i64, i32]
     lib.cgnn_power_bins.argtypes = [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.cgnn_redshift_positions.argtypes = [vp, vp, i64, i64, f32, i32, f32, vp, vp]
+    lib.cgnn_power_multipoles_workspace_bytes.restype = sz
+    lib.cgnn_power_multipoles_workspace_bytes.argtypes = [i64, i32]
+    lib.cgnn_power_multipoles.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.cgnn_segment_colsum.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.cgnn_window_features.argtypes = [vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]
     lib.cgnn_window_features_rows.argtypes = [vp, vp, i32, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, vp]

@@ -43,6 +43,14 @@
 // part-th of CGNN_PB_PARTS equal slices of the bin's run of perm, each thread its strided share in index order, a tree
 // over the threads; one thread per (frame, bin, sum) then adds the parts in part order.  No float atomics: two runs give
 // the same bits.  A slice without modes writes zeros and leaves before the tree.  Compiled with -ffp-contract=off (Makefile): every operation below rounds once, in float32 and float64.
+//
+// Redshift space.  cgnn_redshift_positions displaces every particle along a box axis by `shift` times its minimum-image
+// step from the frame before (float32, one rounding per operation, wrapped into [0, L]: the deposit's contract).
+// cgnn_power_multipoles is cgnn_power_bins' two-stage sum with twelve sums per bin: |x|^2, |y|^2 and Re(x conj y), each
+// times 1, L2 and L4 of mu = n_los / |n|, then sqrt(n2), L2 and L4 alone.  With a second pair of transforms, of the same
+// particles displaced by half a cell, x = (a + a2 e^{i pi (nx + ny + nz) / M}) / 2: the mesh's odd aliases cancel.
+// pm_partial_kernel<HAS_B, INTER> keeps pb_partial_kernel's decomposition and, for the monopole rows, its expressions:
+// without a2 they are cgnn_power_bins' bits.  tests/multipole_checks.py restates both in numpy.
 #include <math.h>
 
 #include "cgnn_util.hpp"
@@ -386,6 +394,168 @@ __global__ __launch_bounds__(CGNN_BLOCK) void pb_final_kernel(const double* __re
     sums[(f * CGNN_PB_SUMS + q) * num_bins + bin] = s;
 }
 
+// ---- redshift space: cgnn_redshift_positions and cgnn_power_multipoles --------------------------------------------------
+#define CGNN_PM_SUMS 12           // float64 sums per (frame, bin) of cgnn_power_multipoles (rows: include/cgnn.h)
+
+// one thread per particle of every frame: out = pos with the `los` coordinate displaced by shift times the minimum-image
+// step from prev.  One float32 rounding per operation (the sequence of include/cgnn.h); whatever does not end in [0, L]
+// (a non-finite input, a shift of so many boxes that the wrap's own rounding exceeds one box) is written as 0.
+__global__ __launch_bounds__(CGNN_BLOCK) void rs_positions_kernel(const float* __restrict__ pos,
+                                                                  const float* __restrict__ prev, int64_t total, float L,
+                                                                  int los, float shift, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    float c[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    const float p = los == 0 ? c[0] : (los == 1 ? c[1] : c[2]);
+    const float q = prev[3 * i + los];
+    float d = __fsub_rn(p, q);
+    d = __fsub_rn(d, __fmul_rn(L, rintf(__fdiv_rn(d, L))));
+    float s = __fadd_rn(p, __fmul_rn(shift, d));
+    s = __fsub_rn(s, __fmul_rn(L, floorf(__fdiv_rn(s, L))));
+    if (s < 0.f) s = 0.f;
+    else if (s >= L) s = __fsub_rn(s, L);
+    if (!(s >= 0.f && s <= L)) s = 0.f;
+    out[3 * i] = los == 0 ? s : c[0];
+    out[3 * i + 1] = los == 1 ? s : c[1];
+    out[3 * i + 2] = los == 2 ? s : c[2];
+}
+
+// 0.5 (u + v e^{i pi t}) with (sn, cs) = sincospi(t): the interlaced pair of one mode
+__device__ __forceinline__ double2 pm_interlaced(const double2 u, const double2 v, double sn, double cs) {
+    double2 r;
+    r.x = 0.5 * (u.x + (v.x * cs - v.y * sn));
+    r.y = 0.5 * (u.y + (v.x * sn + v.y * cs));
+    return r;
+}
+
+// stage 1 of cgnn_power_multipoles: pb_partial_kernel's decomposition (workgroup ((f * num_bins + bin) * PARTS + part),
+// the same clamped slice, strided shares in index order, the same tree) with twelve sums.  Rows 0, 3, 6 and 9 are formed
+// by pb_partial_kernel's expressions in its order, so the plain form gives its bits.  HAS_B / INTER are compile-time:
+// the plain auto form loads a alone and keeps six rows of LDS.  partial [blocks, 12], cnt [blocks].
+template <bool HAS_B, bool INTER>
+__global__ __launch_bounds__(CGNN_BLOCK) void pm_partial_kernel(const double2* __restrict__ a, const double2* __restrict__ b,
+                                                                const double2* __restrict__ a2, const double2* __restrict__ b2,
+                                                                int M, int Mh, int los, int64_t modes_per_frame,
+                                                                const int32_t* __restrict__ perm,
+                                                                const int32_t* __restrict__ bin_start, int num_bins,
+                                                                const double* __restrict__ inv_w2,
+                                                                double* __restrict__ partial, long long* __restrict__ cnt) {
+    constexpr int ROWS = HAS_B ? CGNN_PM_SUMS : 6;        // without b: rows 0-2 and 9-11
+    __shared__ double red[ROWS][CGNN_BLOCK];
+    __shared__ long long redc[CGNN_BLOCK];
+    const int part = blockIdx.x % CGNN_PB_PARTS;
+    const int bin = (blockIdx.x / CGNN_PB_PARTS) % num_bins;
+    const int64_t f = blockIdx.x / (CGNN_PB_PARTS * num_bins);
+    const int p0 = max(0, min(bin_start[bin], (int)modes_per_frame));
+    const int p1 = max(p0, min(bin_start[bin + 1], (int)modes_per_frame));
+    const int per = (p1 - p0 + CGNN_PB_PARTS - 1) / CGNN_PB_PARTS;
+    const int q0 = p0 + part * per, q1 = min(q0 + per, p1);
+    if (q0 >= q1) {
+        if (threadIdx.x < CGNN_PM_SUMS) partial[(int64_t)blockIdx.x * CGNN_PM_SUMS + threadIdx.x] = 0.0;
+        if (threadIdx.x == 0) cnt[blockIdx.x] = 0;
+        return;
+    }
+    const double2* af = a + f * modes_per_frame;
+    const double2* bf = HAS_B ? b + f * modes_per_frame : nullptr;
+    const double2* af2 = INTER ? a2 + f * modes_per_frame : nullptr;
+    const double2* bf2 = (HAS_B && INTER) ? b2 + f * modes_per_frame : nullptr;
+    double sa[3] = {0.0, 0.0, 0.0}, sb[3] = {0.0, 0.0, 0.0}, sx[3] = {0.0, 0.0, 0.0};
+    double sk = 0.0, sl2 = 0.0, sl4 = 0.0;
+    long long sc = 0;
+    for (int p = q0 + (int)threadIdx.x; p < q1; p += CGNN_BLOCK) {
+        const int idx = perm[p];
+        if (idx < 0 || idx >= modes_per_frame) continue;
+        int nx, ny, nz;
+        pb_mode(idx, M, Mh, nx, ny, nz);
+        const double h = (nz == 0 || 2 * nz == M) ? 1.0 : 2.0;
+        const double wt = h * ((inv_w2[abs(nx)] * inv_w2[abs(ny)]) * inv_w2[nz]);
+        const int n2 = nx * nx + ny * ny + nz * nz;
+        const int nl = los == 0 ? nx : (los == 1 ? ny : nz);
+        const double mu2 = n2 != 0 ? (double)(nl * nl) / (double)n2 : 0.0;
+        const double l2 = 1.5 * mu2 - 0.5;
+        const double l4 = (4.375 * mu2 - 3.75) * mu2 + 0.375;
+        double sn = 0.0, cs = 1.0;
+        if constexpr (INTER) sincospi((double)(nx + ny + nz) / (double)M, &sn, &cs);
+        double2 x = af[idx];
+        if constexpr (INTER) x = pm_interlaced(x, af2[idx], sn, cs);
+        const double paa = wt * (x.x * x.x + x.y * x.y);
+        sa[0] += paa;
+        sa[1] += paa * l2;
+        sa[2] += paa * l4;
+        if constexpr (HAS_B) {
+            double2 y = bf[idx];
+            if constexpr (INTER) y = pm_interlaced(y, bf2[idx], sn, cs);
+            const double pbb = wt * (y.x * y.x + y.y * y.y);
+            sb[0] += pbb;
+            sb[1] += pbb * l2;
+            sb[2] += pbb * l4;
+            const double pab = wt * (x.x * y.x + x.y * y.y);
+            sx[0] += pab;
+            sx[1] += pab * l2;
+            sx[2] += pab * l4;
+        }
+        sk += h * sqrt((double)n2);
+        sl2 += h * l2;
+        sl4 += h * l4;
+        sc += (long long)h;
+    }
+    // LDS rows: with b the output rows themselves; without, rows 0-2 then 9-11
+    constexpr int TAIL = HAS_B ? 9 : 3;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        red[q][threadIdx.x] = sa[q];
+        if constexpr (HAS_B) {
+            red[3 + q][threadIdx.x] = sb[q];
+            red[6 + q][threadIdx.x] = sx[q];
+        }
+    }
+    red[TAIL][threadIdx.x] = sk;
+    red[TAIL + 1][threadIdx.x] = sl2;
+    red[TAIL + 2][threadIdx.x] = sl4;
+    redc[threadIdx.x] = sc;
+    __syncthreads();
+    for (int off = CGNN_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+#pragma unroll
+            for (int q = 0; q < ROWS; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + off];
+            redc[threadIdx.x] += redc[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < CGNN_PM_SUMS) {
+        const int q = threadIdx.x;
+        double v = 0.0;                                                     // rows 3-8 without b: not read by stage 2
+        if constexpr (HAS_B) v = red[q][0];
+        else if (q < 3) v = red[q][0];
+        else if (q >= 9) v = red[q - 6][0];
+        partial[(int64_t)blockIdx.x * CGNN_PM_SUMS + q] = v;
+    }
+    if (threadIdx.x == 0) cnt[blockIdx.x] = redc[0];
+}
+
+// stage 2: thread (f, bin, q) adds the parts in part order; q == 12 is the mode count.
+// sums [frames, 12, num_bins] (rows 3-8 untouched without b), modes [frames, num_bins]
+__global__ __launch_bounds__(CGNN_BLOCK) void pm_final_kernel(const double* __restrict__ partial,
+                                                              const long long* __restrict__ cnt, int64_t frames,
+                                                              int num_bins, int have_b, double* __restrict__ sums,
+                                                              long long* __restrict__ modes) {
+    const int64_t t = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
+    if (t >= frames * num_bins * (CGNN_PM_SUMS + 1)) return;
+    const int q = (int)(t % (CGNN_PM_SUMS + 1));
+    const int64_t fb = t / (CGNN_PM_SUMS + 1);        // f * num_bins + bin
+    const int64_t f = fb / num_bins, bin = fb % num_bins;
+    if (q == CGNN_PM_SUMS) {
+        long long s = 0;
+        for (int j = 0; j < CGNN_PB_PARTS; ++j) s += cnt[fb * CGNN_PB_PARTS + j];
+        modes[fb] = s;
+        return;
+    }
+    if (!have_b && q >= 3 && q <= 8) return;
+    double s = 0.0;
+    for (int j = 0; j < CGNN_PB_PARTS; ++j) s += partial[(fb * CGNN_PB_PARTS + j) * CGNN_PM_SUMS + q];
+    sums[(f * CGNN_PM_SUMS + q) * num_bins + bin] = s;
+}
+
 static bool pb_edges(const float* k_edges, int32_t num_bins, PbEdges2& E, const char* who) {
     if (num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
         set_error("%s: num_bins=%d outside [1, %d]", who, (int)num_bins, CGNN_PB_MAX_BINS);
@@ -586,6 +756,102 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
             sums + f0 * CGNN_PB_SUMS * num_bins, reinterpret_cast<long long*>(modes) + f0 * num_bins);
     });
     return check_hip(hipGetLastError(), "cgnn_power_bins");
+}
+
+int cgnn_redshift_positions(const float* pos, const float* pos_prev, int64_t frames, int64_t n, float box_size,
+                            int32_t los, float shift, float* out, void* stream) {
+    const char* who = "cgnn_redshift_positions";
+    if (!pos || !pos_prev || !out || frames <= 0 || n <= 0 || !(box_size > 0.f) || !isfinite(box_size)) {
+        set_error("%s: invalid argument (no null pointer, frames and n positive, box_size positive and finite)", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (los < 0 || los > 2 || !isfinite(shift)) {
+        set_error("%s: los=%d outside [0, 2] or shift not finite", who, (int)los);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (n > CGNN_PS_MAX_THREADS) {
+        set_error("%s: more than 2^24 particles in a frame", who);
+        return CGNN_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ps_for_frame_batches(frames, n, [&](int64_t f0, int64_t nf) {
+        const int64_t total = nf * n;
+        rs_positions_kernel<<<(unsigned)((total + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
+            pos + f0 * n * 3, pos_prev + f0 * n * 3, total, box_size, los, shift, out + f0 * n * 3);
+    });
+    return check_hip(hipGetLastError(), who);
+}
+
+size_t cgnn_power_multipoles_workspace_bytes(int64_t frames, int32_t num_bins) {
+    if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
+    const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
+    return pb_window_bytes() + align256(blocks * CGNN_PM_SUMS * sizeof(double)) + align256(blocks * sizeof(long long));
+}
+
+int cgnn_power_multipoles(const double* a, const double* b, const double* a2, const double* b2, int64_t frames,
+                          int32_t mesh, int32_t order, int32_t los, const int32_t* perm, const int32_t* bin_start,
+                          int32_t num_bins, int64_t* modes, double* sums, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    const char* who = "cgnn_power_multipoles";
+    if (!a || !perm || !bin_start || !modes || !sums || !workspace || frames <= 0 || mesh < 2 ||
+        mesh > CGNN_MA_MAX_MESH || order < 0 || order > 3 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
+        set_error("%s: invalid argument (mesh in [2, %d], order in [0, 3], num_bins in [1, %d])", who, CGNN_MA_MAX_MESH,
+                  CGNN_PB_MAX_BINS);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (los < 0 || los > 2) {
+        set_error("%s: los=%d outside [0, 2]", who, (int)los);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if ((b2 && (!b || !a2)) || (a2 && b && !b2)) {
+        set_error("%s: b2 goes with b and a2, and must be given when both are", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    for (const void* ptr : {(const void*)workspace, (const void*)a, (const void*)b, (const void*)a2, (const void*)b2})
+        if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) {
+            set_error("%s: a, b, a2, b2 and the workspace must be 16-byte aligned", who);
+            return CGNN_ERR_INVALID_ARG;
+        }
+    const size_t need = cgnn_power_multipoles_workspace_bytes(frames, num_bins);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+        return CGNN_ERR_WORKSPACE;
+    }
+    const int64_t per_frame = (int64_t)num_bins * CGNN_PB_PARTS, blocks = frames * per_frame;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    double* inv_w2 = reinterpret_cast<double*>(ws);
+    double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
+    long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() +
+                                                  align256((size_t)blocks * CGNN_PM_SUMS * sizeof(double)));
+    const int Mh = mesh / 2 + 1;
+    pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
+    const int64_t mpf = (int64_t)mesh * mesh * Mh;
+    const double2* ca = reinterpret_cast<const double2*>(a);
+    const double2* cb = reinterpret_cast<const double2*>(b);
+    const double2* ca2 = reinterpret_cast<const double2*>(a2);
+    const double2* cb2 = reinterpret_cast<const double2*>(b2);
+    ps_for_frame_batches(frames, per_frame * CGNN_BLOCK, [&](int64_t f0, int64_t nf) {       // at least 4 frames each
+        const unsigned grid = (unsigned)(nf * per_frame);
+        const int64_t off = f0 * mpf;
+        double* part = partial + f0 * per_frame * CGNN_PM_SUMS;
+        long long* c = cnt + f0 * per_frame;
+#define CGNN_PM_LAUNCH(HAS_B, INTER)                                                                                     \
+    pm_partial_kernel<HAS_B, INTER><<<grid, CGNN_BLOCK, 0, st>>>(ca + off, HAS_B ? cb + off : nullptr,                  \
+                                                                 INTER ? ca2 + off : nullptr,                            \
+                                                                 (HAS_B && INTER) ? cb2 + off : nullptr, mesh, Mh, los,  \
+                                                                 mpf, perm, bin_start, num_bins, inv_w2, part, c)
+        if (cb && ca2) CGNN_PM_LAUNCH(true, true);
+        else if (cb) CGNN_PM_LAUNCH(true, false);
+        else if (ca2) CGNN_PM_LAUNCH(false, true);
+        else CGNN_PM_LAUNCH(false, false);
+#undef CGNN_PM_LAUNCH
+        const int64_t outs = nf * num_bins * (CGNN_PM_SUMS + 1);
+        pm_final_kernel<<<(unsigned)((outs + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
+            part, c, nf, num_bins, b != nullptr, sums + f0 * CGNN_PM_SUMS * num_bins,
+            reinterpret_cast<long long*>(modes) + f0 * num_bins);
+    });
+    return check_hip(hipGetLastError(), who);
 }
 
 }  // extern "C"

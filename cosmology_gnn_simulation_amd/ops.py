@@ -1284,6 +1284,138 @@ def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b:
     return (modes, sums) if batched else (modes[0], sums[0])
 
 
+def check_los(los, who: str) -> int:
+    """The line of sight as a box axis 0, 1 or 2, or ``ValueError``."""
+    if isinstance(los, bool) or los not in (0, 1, 2):
+        raise ValueError(f"{who}: los must be a box axis 0, 1 or 2 (plane-parallel line of sight), got {los!r}")
+    return int(los)
+
+
+def redshift_shift(dt, velocity_scale, who: str) -> float:
+    """``fl32(velocity_scale / dt)`` as a host float, the ``shift`` of ``cgnn_redshift_positions``, or ``ValueError``:
+    ``dt`` positive and finite, ``velocity_scale`` finite, the quotient finite in float32."""
+    if isinstance(dt, bool) or not (float(dt) > 0.0 and math.isfinite(float(dt))):
+        raise ValueError(f"{who}: dt must be positive and finite, got {dt!r}")
+    if isinstance(velocity_scale, bool) or not math.isfinite(float(velocity_scale)):
+        raise ValueError(f"{who}: velocity_scale must be finite, got {velocity_scale!r}")
+    shift = float(torch.tensor(float(velocity_scale) / float(dt), dtype=torch.float64).to(torch.float32))
+    if not math.isfinite(shift):
+        raise ValueError(f"{who}: velocity_scale / dt = {float(velocity_scale) / float(dt)!r} is not finite in float32")
+    return shift
+
+
+def redshift_positions(pos: torch.Tensor, pos_prev: torch.Tensor, dt: float, box_size: float, los: int = 2,
+                       velocity_scale: float = 1.0) -> torch.Tensor:
+    """Positions in redshift space under a plane-parallel line of sight along the box axis ``los``
+    (``cgnn_redshift_positions``): ``pos`` (``[N, 3]`` or ``[T, N, 3]``) with its ``los`` coordinate displaced by
+    ``velocity_scale * v_los``, the velocity being ``minimum_image(pos - pos_prev) / dt`` (that of
+    ``statistics.momentum_power_spectrum``) and ``velocity_scale`` ``1 / (a H)`` in the caller's units, wrapped into
+    ``[0, box_size]``.  Float32 with one rounding per operation, in the sequence of ``include/cgnn.h``, with ``shift =
+    fl32(velocity_scale / dt)``: equal to the numpy restatement bit for bit.  A non-finite coordinate on the ``los``
+    axis gives 0.  Refused on the host (``ValueError``): shapes that differ or are not ``[N, 3]`` / ``[T, N, 3]``, more
+    than 2^24 particles per frame, ``box_size <= 0``, ``los`` outside 0..2, ``dt <= 0``, a non-finite ``shift``.  No host
+    synchronisation."""
+    what = "redshift_positions"
+    los = check_los(los, what)
+    shift = redshift_shift(dt, velocity_scale, what)
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    if tuple(pos_prev.shape) != tuple(pos.shape):
+        raise ValueError(f"{what}: pos_prev {tuple(pos_prev.shape)} and pos {tuple(pos.shape)} differ in shape")
+    if pos.shape[-2] > _lib.MASS_ASSIGN_MAX_PARTICLES:
+        raise ValueError(f"{what}: {pos.shape[-2]} particles per frame exceed 2^24")
+    pos, t, n, _ = _deposit_frames(pos)
+    pos_prev = f32c(pos_prev, "pos_prev")
+    _same_device(pos, pos_prev)
+    out = torch.empty_like(pos)
+    with _timed(what, pos.device):
+        check(_lib.load().cgnn_redshift_positions(pos.data_ptr(), pos_prev.data_ptr(), t, n, float(box_size), los, shift,
+                                                  out.data_ptr(), stream_ptr(pos.device)), "cgnn_redshift_positions")
+    return out
+
+
+def interlace_shift(pos: torch.Tensor, box_size: float, mesh: int) -> torch.Tensor:
+    """``pos`` displaced by half a cell along every axis, for the second mesh of an interlaced spectrum: with ``L =
+    fl32(box_size)`` and ``h = fl32(L / (2 mesh))`` (the quotient in float64, rounded once), ``s = fl32(p + h)`` and ``s
+    >= L: s = fl32(s - L)``.  Positions in ``[0, L]`` land in ``[0, L)``.  Float32, elementwise, on the device of
+    ``pos``; no host synchronisation."""
+    mesh = check_mesh(mesh, "interlace_shift")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"interlace_shift: box_size must be positive and finite, got {box_size!r}")
+    if pos.dtype != torch.float32:
+        raise ValueError(f"interlace_shift: pos must be float32, got {pos.dtype}")
+    length = float(box)
+    half = float(torch.tensor(length / (2 * mesh), dtype=torch.float64).to(torch.float32))
+    s = pos + half
+    return torch.where(s >= length, s - length, s)
+
+
+def power_multipoles(delta_k: torch.Tensor, mesh: int, order: int, k_edges, los: int = 2,
+                     delta_k_b: Optional[torch.Tensor] = None, shifted: Optional[torch.Tensor] = None,
+                     shifted_b: Optional[torch.Tensor] = None,
+                     plan: Optional[PowerPlan] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Legendre-weighted shell sums of the modes of ``delta_k`` about the line of sight ``los`` (a box axis), and
+    optionally of an interlaced pair (``cgnn_power_multipoles``).  Arguments as :func:`power_bins`; ``shifted`` (and
+    ``shifted_b`` with ``delta_k_b``) is the transform of the same particles displaced by :func:`interlace_shift`, which
+    the kernel combines with ``delta_k`` mode by mode, ``x = (a + a2 e^{i pi (nx + ny + nz) / M}) / 2``: the odd aliases
+    of the mesh cancel.  Returns ``(modes, sums)`` on the device, ``modes`` int64 ``[nb]`` (``[T, nb]``) and ``sums``
+    float64 ``[12, nb]`` (``[T, 12, nb]``) with the rows
+
+    0-2. ``sum h |x|^2 / W2 * (1, L2, L4)``,  3-5. likewise of ``|y|^2``,  6-8. of ``Re(x conj y)``,
+    9. ``sum h sqrt(n2)``,  10. ``sum h L2``,  11. ``sum h L4``
+
+    (``L2``, ``L4`` the Legendre polynomials of ``mu = n_los / |n|``; without ``delta_k_b`` rows 3-8 are ``nan``).
+    Without ``shifted`` rows 0, 3, 6, 9 and ``modes`` are :func:`power_bins`' rows 0-3 and modes bit for bit.  Two calls
+    give the same bits.  No host synchronisation."""
+    what = "power_multipoles"
+    mesh = check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in (0, 1, 2, 3):
+        raise ValueError(f"{what}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
+    los = check_los(los, what)
+    e = check_power_edges(k_edges, what)
+    nb = len(e) - 1
+    if shifted_b is not None and (delta_k_b is None or shifted is None):
+        raise ValueError(f"{what}: shifted_b goes with delta_k_b and shifted")
+    if shifted is not None and delta_k_b is not None and shifted_b is None:
+        raise ValueError(f"{what}: with delta_k_b and shifted, shifted_b must be given too")
+    shape = (mesh, mesh, mesh // 2 + 1)
+    given = (("delta_k", delta_k), ("delta_k_b", delta_k_b), ("shifted", shifted), ("shifted_b", shifted_b))
+    for name, d in given:
+        if d is None:
+            continue
+        require_device(d, name)
+        if d.dtype != torch.complex128 or d.dim() not in (3, 4) or tuple(d.shape[-3:]) != shape:
+            raise CgnnError(f"{what}: {name} must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got {d.dtype} "
+                            f"{tuple(d.shape)}")
+        if d.shape != delta_k.shape:
+            raise CgnnError(f"{what}: {name} is {tuple(d.shape)}, delta_k {tuple(delta_k.shape)}")
+    _same_device(delta_k, delta_k_b, shifted, shifted_b)
+    if plan is None:
+        plan = PowerPlan.of(mesh, e, delta_k.device)
+    elif plan.mesh != mesh or plan.edges != tuple(e) or plan.perm.device != delta_k.device:
+        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
+    batched = delta_k.dim() == 4
+    a, b, a2, b2 = (None if d is None else d.contiguous() for _, d in given)
+    t = a.shape[0] if batched else 1
+    if t < 1:
+        raise CgnnError(f"{what}: no frames")
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_power_multipoles_workspace_bytes(t, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    modes = torch.empty((t, nb), dtype=torch.int64, device=a.device)
+    sums = torch.full((t, _lib.POWER_MULTIPOLE_SUMS, nb), float("nan"), dtype=torch.float64, device=a.device)
+    with _timed(what, a.device):
+        check(lib.cgnn_power_multipoles(a.data_ptr(), ptr(b), ptr(a2), ptr(b2), t, mesh, int(order), los,
+                                        plan.perm.data_ptr(), plan.bin_start.data_ptr(), nb, modes.data_ptr(),
+                                        sums.data_ptr(), ws.data_ptr(), ws_bytes, stream_ptr(a.device)),
+              "cgnn_power_multipoles")
+    return (modes, sums) if batched else (modes[0], sums[0])
+
+
 def check_linking_length(linking_length, box_size: float, who: str) -> float:
     """The linking length of :func:`fof_labels` as a float32 host value, or ``ValueError``: finite, positive and at most
     ``fl32(0.5 * box_size)``, ``box_size`` finite and positive.  Callers check before any device work."""

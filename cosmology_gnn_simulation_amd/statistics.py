@@ -33,6 +33,12 @@ mean value per shell, and from the profile the spherical-overdensity radius and 
 ``rollout_halo_profiles`` stacks the profiles of the largest groups by size for every frame of a rollout and of the
 truth.  Unbinding, velocities and merger trees over more than two frames are out of scope.
 
+Redshift space (whether the velocities are right where they matter: coherent infall and the virial motions inside halos
+show in the quadrupole, not in P(k)): ``power_multipoles`` gives P_0, P_2 and P_4 about a box axis, of a frame displaced
+along it by its velocities (``ops.redshift_positions``), from Legendre-weighted shell sums of an interlaced pair of
+meshes (``ops.power_multipoles``); ``rollout_redshift_spectra`` does that for every frame of a rollout against the
+truth; ``multipoles_from_sums`` is the host arithmetic.  ``power_spectrum(interlace=True)`` uses the same reduction.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -254,23 +260,33 @@ def _to_host(modes: torch.Tensor, sums: torch.Tensor, extra: Optional[torch.Tens
     return tuple(h.view(p.dtype).reshape(p.shape) for h, p in zip(host, parts))
 
 
+def _interlaced_shell_sums(pos_a, pos_b, box_size: float, mesh: int, k_edges, order: int):
+    """:func:`_shell_sums` from an interlaced pair of meshes: rows 0, 3, 6 and 9 of ``ops.power_multipoles``."""
+    modes, sums = _multipole_sums(pos_a, pos_b, box_size, mesh, k_edges, order, 2, True)
+    return modes, torch.stack([sums[:, row] for row in (0, 3, 6, 9)], dim=1)
+
+
 def power_spectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, pos_b: Optional[torch.Tensor] = None,
-                   order: int = 2, subtract_shot_noise: bool = True) -> Dict:
+                   order: int = 2, subtract_shot_noise: bool = True, interlace: bool = False) -> Dict:
     """The matter power spectrum of ``pos [N, 3]`` (or of every frame of ``[T, N, 3]``) on a ``mesh^3`` grid, deposited
     with ``order`` (1 = NGP, 2 = CIC, 3 = TSC) and deconvolved by that window; with ``pos_b`` (``[N_b, 3]`` or ``[T, N_b,
     3]``) also its spectrum and the cross spectrum of the two.  ``k_edges``: ``nb + 1`` bin edges in units of ``2 pi / L``
     (default :func:`default_k_edges`).  Returns the dict of :func:`spectra_from_sums` (CPU, float64 / int64; ``[nb]`` or
     ``[T, nb]``): ``k_lo``, ``k_hi``, ``k_mean``, ``modes``, ``power`` and with ``pos_b`` also ``power_b``, ``cross``,
-    ``r``, ``transfer``.  ``transfer`` may be ``nan`` (see there); an empty bin is ``nan``.  Aliasing is not corrected
-    beyond the window deconvolution: bins past half the Nyquist frequency are lifted by it.  Everything is computed on
-    the device of ``pos`` without a host synchronisation and comes back in one transfer."""
+    ``r``, ``transfer``.  ``transfer`` may be ``nan`` (see there); an empty bin is ``nan``.  Without ``interlace``
+    aliasing is not corrected beyond the window deconvolution: bins past half the Nyquist frequency are lifted by it.
+    ``interlace=True`` deposits every set a second time, displaced by half a cell (``ops.interlace_shift``), and combines
+    the two transforms inside the reduction (``ops.power_multipoles``): the odd aliases cancel and the bins up to the
+    Nyquist frequency are usable, for twice the meshes and transforms.  Everything is computed on the device of ``pos``
+    without a host synchronisation and comes back in one transfer."""
     what = "power_spectrum"
     mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
     frames_a = _frames3(pos, "pos", what)
     frames_b = None if pos_b is None else _frames3(pos_b, "pos_b", what)
     if frames_b is not None and (pos_b.dim() != pos.dim() or frames_b.shape[0] != frames_a.shape[0]):
         raise ValueError(f"{what}: pos_b {tuple(pos_b.shape)} does not go with pos {tuple(pos.shape)}")
-    modes, sums = _to_host(*_shell_sums(frames_a, frames_b, box_size, mesh, k_edges, order))
+    shell_sums = _interlaced_shell_sums if interlace else _shell_sums
+    modes, sums = _to_host(*shell_sums(frames_a, frames_b, box_size, mesh, k_edges, order))
     if pos.dim() == 2:
         modes, sums = modes[0], sums[0]
     return spectra_from_sums(modes, sums, frames_a.shape[1], None if frames_b is None else frames_b.shape[1], box_size,
@@ -278,7 +294,8 @@ def power_spectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, 
 
 
 def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
-                          mesh: int, k_edges=None, frames: Optional[Sequence[int]] = None, order: int = 2) -> Dict:
+                          mesh: int, k_edges=None, frames: Optional[Sequence[int]] = None, order: int = 2,
+                          interlace: bool = False) -> Dict:
     """Fourier-space statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns
     (``Coordinates [T, N, 3]``).  ``frames``: the frame numbers to judge (default: every frame both hold).  Per selected
     frame (``[F, nb]``, CPU, float64):
@@ -287,17 +304,220 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     * ``cross``: their cross spectrum;  ``r``: the cross-correlation coefficient (``|r| <= 1``);
     * ``transfer``: ``sqrt(power_pred / power_true)``, ``nan`` where a subtracted spectrum is negative,
 
-    plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean`` (``[nb]``) and ``modes`` (``[nb]``, int64).  Everything is computed on
-    the device of the rollout without a host synchronisation per frame; the results come back in one transfer."""
+    plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean`` (``[nb]``) and ``modes`` (``[nb]``, int64).  ``interlace``: as in
+    :func:`power_spectrum`.  Everything is computed on the device of the rollout without a host synchronisation per
+    frame; the results come back in one transfer."""
     what = "rollout_power_spectra"
     mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
     pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
     n = pc.shape[1]
-    modes, sums = _to_host(*_shell_sums(pc, tc, box_size, mesh, k_edges, order))
+    shell_sums = _interlaced_shell_sums if interlace else _shell_sums
+    modes, sums = _to_host(*shell_sums(pc, tc, box_size, mesh, k_edges, order))
     sp = spectra_from_sums(modes, sums, n, n, box_size, mesh, k_edges, True)
     return {"frames": sel, "k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "k_mean": sp["k_mean"][0].clone(),
             "modes": sp["modes"][0].clone(), "power_pred": sp["power"], "power_true": sp["power_b"],
             "cross": sp["cross"], "r": sp["r"], "transfer": sp["transfer"]}
+
+
+# ---- redshift space: the multipoles of the power spectrum, interlaced -------------------------------------------------
+#
+# ``ops.redshift_positions`` displaces every particle along a box axis by its velocity (plane-parallel line of sight),
+# ``ops.power_multipoles`` sums the modes of the displaced frame's mesh with Legendre weights about that axis and combines
+# an interlaced pair of meshes inside the reduction.  Per-particle or wide-angle lines of sight, xi(s, mu) pair counts,
+# sharded, batched and owned-storage variants, a multipole loss and interlaced momentum and thermal spectra are not built.
+
+MULTIPOLES = (0, 2, 4)
+
+
+def multipoles_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: float, mesh: int, k_edges,
+                         subtract_shot_noise: bool = True) -> Dict:
+    """Multipoles from the shell sums of ``ops.power_multipoles``, on the host in float64 (``modes [..., nb]`` int64,
+    ``sums [..., 12, nb]``; the results have the shape of ``modes``, on the CPU).  With ``L = box_size``, ``M = mesh`` and
+    ``S_l`` the row of the Legendre polynomial ``L_l``:
+
+    * ``k_lo``, ``k_hi``, ``k_mean``, ``modes``: as in :func:`spectra_from_sums`;
+    * ``power_0``, ``power_2``, ``power_4``: ``P_l = (2 l + 1) L^3 S_l / modes / M^6``; the shot noise ``L^3 / n_a`` is
+      isotropic and leaves ``l = 0`` only (when ``subtract_shot_noise``);
+    * ``legendre_mean_2``, ``legendre_mean_4``: the mean of ``L_2``, ``L_4`` over the modes of the bin.  A discrete
+      shell is not a sphere: an isotropic spectrum ``P`` shows ``(2 l + 1) P legendre_mean_l`` in ``power_l``;
+
+    and with a second set (``n_b`` is not None) ``power_b_0/2/4`` (shot noise ``L^3 / n_b``), ``cross_0/2/4`` (no shot
+    noise) and the monopole's ``r`` and ``transfer``, defined as in :func:`spectra_from_sums`.  A bin without modes gives
+    ``nan`` everywhere."""
+    what = "multipoles_from_sums"
+    mesh = ops.check_mesh(mesh, what)
+    box = float(box_size)
+    if not (box > 0.0 and math.isfinite(box)):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    k = torch.tensor(ops.check_power_edges(k_edges, what), dtype=torch.float64) * (2.0 * math.pi / box)
+    modes = torch.as_tensor(modes).detach().to(device="cpu", dtype=torch.int64)
+    sums = torch.as_tensor(sums).detach().to(device="cpu", dtype=torch.float64)
+    nb, rows = k.numel() - 1, _lib.POWER_MULTIPOLE_SUMS
+    if modes.shape[-1] != nb or sums.shape[-2:] != (rows, nb) or sums.shape[:-2] != modes.shape[:-1]:
+        raise ValueError(f"{what}: modes {tuple(modes.shape)} and sums {tuple(sums.shape)} do not fit {nb} bins")
+    count = modes.to(torch.float64)
+    count = torch.where(modes > 0, count, torch.full_like(count, float("nan")))
+    norm = box ** 3 / float(mesh) ** 6
+
+    def multipole(first_row, i):
+        p = norm * sums[..., first_row + i, :] / count
+        return p if i == 0 else (2 * MULTIPOLES[i] + 1) * p
+
+    out = {"k_lo": k[:-1].clone(), "k_hi": k[1:].clone(), "k_mean": sums[..., 9, :] / count * (2.0 * math.pi / box),
+           "modes": modes, "legendre_mean_2": sums[..., 10, :] / count, "legendre_mean_4": sums[..., 11, :] / count}
+    sets = (("power_", 0, n_a),) if n_b is None else (("power_", 0, n_a), ("power_b_", 3, n_b), ("cross_", 6, None))
+    for name, first_row, n in sets:
+        for i, ell in enumerate(MULTIPOLES):
+            p = multipole(first_row, i)
+            out[f"{name}{ell}"] = p - box ** 3 / n if (ell == 0 and n is not None and subtract_shot_noise) else p
+    if n_b is not None:
+        out["r"] = out["cross_0"] / torch.sqrt(multipole(0, 0) * multipole(3, 0))
+        out["transfer"] = torch.sqrt(out["power_0"] / out["power_b_0"])
+    return out
+
+
+def _multipole_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int,
+                    los: int, interlace: bool):
+    """``ops.power_multipoles`` of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b``): device
+    tensors ``modes [F, nb]``, ``sums [F, 12, nb]``.  Frames go through in chunks whose meshes fit the free device memory:
+    per frame, set and mesh of the interlaced pair what :func:`_shell_sums` counts (``8 M^3`` for the contrast, ``16 M^2
+    (M/2 + 1)`` for its transform, ``8 M^3`` for the int64 mesh, as much again for the FFT's scratch), and per frame the
+    workspace (``nb * 64`` slices of twelve sums and a count) and the outputs (``13 nb`` values).  The int64 mesh and the
+    contrast of one transform are gone before the next is made."""
+    from .training import free_device_bytes
+    n_frames, nb = pos_a.shape[0], len(k_edges) - 1
+    meshes = (1 if pos_b is None else 2) * (2 if interlace else 1)
+    per_frame = (16 * mesh ** 3 + 16 * mesh * mesh * (mesh // 2 + 1)) * meshes * 2 + nb * 64 * 13 * 8 + nb * 13 * 8
+    chunk = max(1, min(n_frames, free_device_bytes(pos_a.device) // per_frame))
+    plan = ops.PowerPlan.of(mesh, k_edges, pos_a.device)
+
+    def transforms(pos):
+        if pos is None:
+            return None, None
+        first = _contrast_modes(pos, box_size, mesh, order)
+        if not interlace:
+            return first, None
+        return first, _contrast_modes(ops.interlace_shift(pos, box_size, mesh), box_size, mesh, order)
+
+    modes, sums = [], []
+    for f0 in range(0, n_frames, chunk):
+        a, a2 = transforms(pos_a[f0:f0 + chunk])
+        b, b2 = transforms(None if pos_b is None else pos_b[f0:f0 + chunk])
+        m, s = ops.power_multipoles(a, mesh, order, k_edges, los, b, a2, b2, plan)
+        del a, a2, b, b2
+        modes.append(m)
+        sums.append(s)
+    return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
+
+
+def _check_multipole_arguments(what: str, box_size, mesh, k_edges, order, los, dt, velocity_scale, moving: bool):
+    mesh, k_edges = _check_spectrum_arguments(what, box_size, mesh, k_edges, order)
+    los = ops.check_los(los, what)
+    if moving:
+        ops.redshift_shift(dt, velocity_scale, what)
+    return mesh, k_edges, los
+
+
+def _f32_frames(pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    frames = _frames3(pos, name, what)
+    return frames if frames.dtype == torch.float32 else frames.float()
+
+
+def power_multipoles(pos: torch.Tensor, box_size: float, mesh: int, pos_prev: Optional[torch.Tensor] = None,
+                     dt: Optional[float] = None, velocity_scale: float = 1.0, los: int = 2, k_edges=None,
+                     pos_b: Optional[torch.Tensor] = None, pos_b_prev: Optional[torch.Tensor] = None, order: int = 2,
+                     interlace: bool = True, subtract_shot_noise: bool = True) -> Dict:
+    """The multipoles ``P_0``, ``P_2``, ``P_4`` of the power spectrum of ``pos`` (``[N, 3]`` or ``[T, N, 3]``) about the
+    box axis ``los``, in redshift space when ``pos_prev`` (the frame before, the same shape) and ``dt`` are given: every
+    particle is first displaced along ``los`` by ``velocity_scale * minimum_image(pos - pos_prev) / dt``
+    (``ops.redshift_positions``; ``velocity_scale`` is ``1 / (a H)`` in the caller's units).  Without ``pos_prev`` they are
+    the real-space multipoles of ``pos``: ``P_2`` and ``P_4`` then hold only what the discrete shells leak (see
+    ``legendre_mean_l``).  With ``pos_b`` (and ``pos_b_prev`` when ``pos_prev`` is given) also the second set's multipoles
+    and the cross multipoles.  ``interlace`` (default on): a second mesh displaced by half a cell is combined with the
+    first inside the reduction, which removes the odd aliases; without it ``P_4`` is wrong past a quarter of the mesh even
+    on white noise.  Returns the dict of :func:`multipoles_from_sums`.  Everything is computed on the device of ``pos``
+    without a host synchronisation and comes back in one transfer."""
+    what = "power_multipoles"
+    moving = pos_prev is not None
+    if moving and dt is None:
+        raise ValueError(f"{what}: pos_prev needs dt")
+    mesh, k_edges, los = _check_multipole_arguments(what, box_size, mesh, k_edges, order, los, dt, velocity_scale, moving)
+    if (pos_b_prev is not None) != (pos_b is not None and moving):
+        raise ValueError(f"{what}: pos_b_prev is given exactly when pos_b and pos_prev both are")
+    sets = []
+    for name, cur, prev in (("pos", pos, pos_prev), ("pos_b", pos_b, pos_b_prev)):
+        if cur is None:
+            sets.append(None)
+            continue
+        frames = _f32_frames(cur, name, what)
+        if cur.dim() != pos.dim() or frames.shape[0] != (pos.shape[0] if pos.dim() == 3 else 1):
+            raise ValueError(f"{what}: {name} {tuple(cur.shape)} does not go with pos {tuple(pos.shape)}")
+        if prev is not None:
+            if tuple(prev.shape) != tuple(cur.shape):
+                raise ValueError(f"{what}: {name}_prev {tuple(prev.shape)} and {name} {tuple(cur.shape)} differ in shape")
+            frames = ops.redshift_positions(frames, _f32_frames(prev, name + "_prev", what).to(frames.device), dt,
+                                            box_size, los, velocity_scale)
+        sets.append(frames)
+    modes, sums = _to_host(*_multipole_sums(sets[0], sets[1], box_size, mesh, k_edges, order, los, bool(interlace)))
+    if pos.dim() == 2:
+        modes, sums = modes[0], sums[0]
+    return multipoles_from_sums(modes, sums, sets[0].shape[1], None if sets[1] is None else sets[1].shape[1], box_size,
+                                mesh, k_edges, subtract_shot_noise)
+
+
+def rollout_redshift_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
+                             box_size: float, mesh: int, dt: float, velocity_scale: float = 1.0, los: int = 2,
+                             frames: Optional[Sequence[int]] = None, k_edges=None, order: int = 2,
+                             interlace: bool = True) -> Dict:
+    """Redshift-space statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns
+    (``Coordinates [T, N, 3]``): whether the velocities are right where they matter.  Every judged frame of either side is
+    displaced along ``los`` by its own velocity, ``minimum_image`` of its step from the frame before in the same dict,
+    over ``dt`` and times ``velocity_scale`` (:func:`power_multipoles`).  ``frames``: the frame numbers to judge (default:
+    every frame from 1 on that both hold); frame 0 has no predecessor and is ``nan``, as in :func:`rollout_gas_spectra`.
+    Per selected frame (``[F, nb]``, CPU, float64), for ``l`` in 0, 2, 4:
+
+    * ``power_pred_l``, ``power_true_l``: the multipoles of the two sides (the shot noise leaves ``l = 0``);
+      ``cross_l``: their cross multipoles;
+    * ``r``, ``transfer``: of the monopoles, as in :func:`rollout_power_spectra`;
+    * ``quadrupole_ratio``: ``power_pred_2 / power_true_2``,
+
+    plus ``frames``, ``k_lo``, ``k_hi``, ``k_mean``, ``legendre_mean_2``, ``legendre_mean_4`` (``[nb]``) and ``modes``
+    (``[nb]``, int64).  No host synchronisation per frame; one transfer."""
+    what = "rollout_redshift_spectra"
+    mesh, k_edges, los = _check_multipole_arguments(what, box_size, mesh, k_edges, order, los, dt, velocity_scale, True)
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    truth = {"Coordinates": ground_truth["Coordinates"].to(dev)}       # moved once: the predecessors come from it too
+    if frames is None:
+        frames = range(1, min(len(pc), len(truth["Coordinates"])))
+    cp, ct, sel = _rollout_frames(rollout_data, truth, frames, what)
+    rows = [i for i, f in enumerate(sel) if f > 0]
+    if not rows:
+        raise ValueError(f"{what}: no selected frame has a predecessor (frames {sel})")
+    nf, nb, n = len(sel), len(k_edges) - 1, cp.shape[1]
+    prev = torch.tensor([sel[i] - 1 for i in rows], dtype=torch.int64).to(dev)
+    at = torch.tensor(rows, dtype=torch.int64).to(dev)
+    sides = []
+    for cur, source in ((cp, pc), (ct, truth["Coordinates"])):
+        sides.append(ops.redshift_positions(_f32_frames(cur.index_select(0, at), "Coordinates", what),
+                                            _f32_frames(source.index_select(0, prev), "Coordinates", what), dt, box_size,
+                                            los, velocity_scale))
+    modes, sums = _multipole_sums(sides[0], sides[1], box_size, mesh, k_edges, order, los, bool(interlace))
+    if len(rows) != nf:        # frame 0: nan sums; the mode counts are every frame's
+        block = torch.full((nf, _lib.POWER_MULTIPOLE_SUMS, nb), float("nan"), dtype=torch.float64, device=dev)
+        block.index_copy_(0, at, sums)
+        modes, sums = modes[:1].expand(nf, nb).contiguous(), block
+    modes, sums = _to_host(modes, sums)
+    sp = multipoles_from_sums(modes, sums, n, n, box_size, mesh, k_edges, True)
+    out = {"frames": sel, "k_lo": sp["k_lo"], "k_hi": sp["k_hi"], "modes": sp["modes"][0].clone(),
+           "r": sp["r"], "transfer": sp["transfer"], "quadrupole_ratio": sp["power_2"] / sp["power_b_2"]}
+    first = rows[0]                 # a frame that was computed: the shells are every frame's
+    for key in ("k_mean", "legendre_mean_2", "legendre_mean_4"):
+        out[key] = sp[key][first].clone()
+    for ell in MULTIPOLES:
+        out[f"power_pred_{ell}"], out[f"power_true_{ell}"] = sp[f"power_{ell}"], sp[f"power_b_{ell}"]
+        out[f"cross_{ell}"] = sp[f"cross_{ell}"]
+    return out
 
 
 # ---- gas fields on the mesh: thermal and momentum spectra ---------------------------------------------------------------
@@ -305,8 +525,8 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
 # ``ops.mass_assign_weighted`` deposits per-particle values in exact integers; what follows forms the fields' spectra with
 # the pieces above.  The weighted shot noise (sums over the particles) is formed on the device in float64 and travels
 # with the shell sums in the one transfer.  Sharded and batched variants, an owned-storage variant (``dist.
-# assemble_frames`` first), redshift-space quantities and an aliasing correction beyond the window deconvolution are
-# not built.
+# assemble_frames`` first), redshift-space gas fields and interlaced thermal and momentum spectra (the matter spectra have
+# both: the section above) are not built.
 
 def _scalar_values(values: torch.Tensor, frames: torch.Tensor, pos: torch.Tensor, name: str, what: str) -> torch.Tensor:
     """Scalar per-particle ``values`` (``[N]`` / ``[N, 1]`` for ``pos [N, 3]``, with a leading ``T`` for frames) -> ``[F, N]``."""

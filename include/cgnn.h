@@ -690,6 +690,55 @@ int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t me
                     const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- redshift space: displaced positions and the multipoles of the power spectrum -----------------------------------
+ * cgnn_redshift_positions: out (device, float [frames, n, 3], overwritten) is pos with the coordinate `los` (0..2, a
+ * plane-parallel line of sight along a box axis) displaced by `shift` times the minimum-image step from pos_prev; the
+ * two other coordinates are copied.  shift = fl32(velocity_scale / dt), formed once by the caller (velocity_scale is
+ * 1 / (a H) in the caller's units, the velocity minimum_image(pos - pos_prev) / dt).  With L = box_size, p and q the
+ * `los` coordinates of pos and pos_prev, in float32 with one rounding per operation, no FMA:
+ *     d = fl32(p - q);          d = fl32(d - fl32(L * rintf(fl32(d / L))))          (the minimum image; rint to even)
+ *     s = fl32(p + fl32(shift * d));   s = fl32(s - fl32(L * floorf(fl32(s / L))))
+ *     s < 0: s = 0;   else s >= L: s = fl32(s - L);   then, unless 0 <= s <= L: s = 0
+ * The result lies in [0, L], the contract of cgnn_mass_assign.  The last rule catches a non-finite p, q (they give 0)
+ * and shifts of so many boxes that the wrap's own rounding exceeds a box; nothing is converted to an integer.  pos_prev
+ * == pos returns pos bit for bit for p in [0, L) (p == L gives 0, the same cell).  One thread per particle and frame,
+ * no atomics, whole frames per launch, 2^24 threads at most, no host synchronisation.
+ * CGNN_ERR_INVALID_ARG for a null pointer, frames or n <= 0, box_size <= 0 or not finite, los outside 0..2 and a
+ * non-finite shift; n > 2^24: CGNN_ERR_UNSUPPORTED; all before any launch.
+ *
+ * cgnn_power_multipoles is the two-stage sum of cgnn_power_bins (the same perm and bin_start, the same 64 slices,
+ * strided shares in index order, a tree over the threads, slices added in slice order, clamped slice bounds and checked
+ * mode indices: every float64 addition has a fixed place and two runs give the same bits) with Legendre weights about
+ * the line of sight `los` and, optionally, an interlaced pair of transforms.  a, b as there (b may be NULL); a2, b2
+ * (device, complex128, the same shape, 16-byte aligned) are the transforms of the same particles displaced by half a
+ * cell, box_size / (2 mesh), along every axis; they may be NULL (no interlacing), b2 must be given exactly when b and
+ * a2 both are.  Per mode, with nx, ny, nz, n2, h and W2 those of cgnn_power_bins, n_los the frequency on axis `los`,
+ * in float64, one rounding per operation:
+ *     mu2 = (double)(n_los * n_los) / (double)n2;   L2 = 1.5 mu2 - 0.5;   L4 = (4.375 mu2 - 3.75) mu2 + 0.375
+ *     x = a, or with a2:  (sn, cs) = sincospi((double)(nx + ny + nz) / (double)mesh),
+ *         x = 0.5 (a + a2 (cs + i sn)):  re = 0.5 (a.re + (a2.re cs - a2.im sn)),  im = 0.5 (a.im + (a2.re sn + a2.im cs))
+ *     y likewise from b and b2;   wt = h / W2 as in cgnn_power_bins
+ *     paa = wt |x|^2,  pbb = wt |y|^2,  pab = wt Re(x conj y)           (the expressions of cgnn_power_bins)
+ *   modes [frames, num_bins] int64        sum of h
+ *   sums  [frames, 12, num_bins] double   rows 0-2: sum paa, sum paa L2, sum paa L4     rows 3-5: likewise of pbb
+ *                                         rows 6-8: likewise of pab     row 9: sum h sqrt(n2)
+ *                                         row 10: sum h L2    row 11: sum h L4
+ * Rows 10 and 11 are the discrete shell's own Legendre sums: what an isotropic spectrum leaks into l = 2 and 4.
+ * Without b rows 3-8 are not written.  Without a2 rows 0, 3, 6, 9 and modes are cgnn_power_bins' rows 0, 1, 2, 3 and
+ * modes bit for bit.  A Nyquist plane (index mesh/2 on an even mesh) is read at frequency +mesh/2, in the phase and in
+ * mu2, as in cgnn_power_bins; its Hermitian weight is the plain kernel's.  The partial kernel is compiled per (b, a2):
+ * the plain forms load nothing they do not use.  All frames in one launch sequence (whole frames per launch, 2^24
+ * threads at most), no host synchronisation.  Workspace: cgnn_power_multipoles_workspace_bytes(frames, num_bins),
+ * 16-byte aligned.  CGNN_ERR_INVALID_ARG for what cgnn_power_bins refuses, los outside 0..2, b2 without b or without
+ * a2, a2 with b but no b2; CGNN_ERR_WORKSPACE for a workspace too small; all before any launch. */
+int cgnn_redshift_positions(const float* pos, const float* pos_prev, int64_t frames, int64_t n, float box_size,
+                            int32_t los, float shift, float* out, void* stream);
+size_t cgnn_power_multipoles_workspace_bytes(int64_t frames, int32_t num_bins);
+int cgnn_power_multipoles(const double* a, const double* b, const double* a2, const double* b2, int64_t frames,
+                          int32_t mesh, int32_t order, int32_t los, const int32_t* perm, const int32_t* bin_start,
+                          int32_t num_bins, int64_t* modes, double* sums, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- judging a rollout by its halos: friends-of-friends groups and their catalogue ------------------------------------
  * cgnn_fof_labels labels the connected components of "closer than the linking length" among pos [n, 3] (positions in
  * [0, box_size]; a value of exactly box_size falls into the edge cell) in a periodic box of side box_size.  With d2(i, j)
