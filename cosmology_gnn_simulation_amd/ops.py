@@ -865,6 +865,80 @@ def pair_counts(pos_a: torch.Tensor, box_size: float, edges, pos_b: Optional[tor
     return counts if batched else counts[0]
 
 
+def check_mu_edges(mu_edges, who: str) -> List[float]:
+    """The mu edges of :func:`pair_counts_smu` as float32 host values, or ``ValueError``: ``1 <= nmu <= 128`` bins
+    (``_lib.PAIR_COUNTS_SMU_MAX_AXIS``), finite, strictly ascending in float32, from exactly 0 to exactly 1.  Callers
+    check before any device work."""
+    m = torch.as_tensor(mu_edges).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    nmu = m.numel() - 1
+    if not 1 <= nmu <= _lib.PAIR_COUNTS_SMU_MAX_AXIS:
+        raise ValueError(f"{who}: mu_edges must hold nmu + 1 values with 1 <= nmu <= {_lib.PAIR_COUNTS_SMU_MAX_AXIS}, "
+                         f"got {m.numel()} values")
+    if not bool(torch.isfinite(m).all()) or not bool((m[1:] > m[:-1]).all()):
+        raise ValueError(f"{who}: mu_edges must be finite and ascend strictly (in float32)")
+    if float(m[0]) != 0.0 or float(m[-1]) != 1.0:
+        raise ValueError(f"{who}: mu_edges must run from exactly 0 to exactly 1, got {float(m[0])} to {float(m[-1])}")
+    return m.tolist()
+
+
+def pair_counts_smu(pos_a: torch.Tensor, box_size: float, s_edges, mu_edges, pos_b: Optional[torch.Tensor] = None, *,
+                    los: int = 2, check_bounds: bool = False) -> torch.Tensor:
+    """Exact pair counts by separation ``s`` and by ``mu``, the |cosine| of the angle between the separation and a
+    plane-parallel line of sight along the box axis ``los`` (``cgnn_pair_counts_smu``): ``int64 [ns, nmu]`` for ``pos_a
+    [N, 3]``, ``int64 [T, ns, nmu]`` for ``pos_a [T, N, 3]`` (one call per frame on the same stream, no host
+    synchronisation between them).  ``s_edges``: ``ns + 1`` ascending radii as in :func:`pair_counts`; ``mu_edges``:
+    ``nmu + 1`` ascending values from exactly 0 to exactly 1 (host values both; at most 128 bins per axis and 4096 in
+    all).  With ``d2`` of :func:`pair_counts` and ``dl2 = fl32(dl * dl)`` its ``los`` term, a pair with ``e2[i] <= d2 <
+    e2[i + 1]`` falls in the mu-bin ``j = #{j' in 1 .. nmu - 1: fl32(fl32(mu_edges[j'] ** 2) * d2) <= dl2}``
+    (``include/cgnn.h``): a pair along the line of sight in the last, one across it in bin 0, a coincident cross pair in
+    the last.  ``counts.sum(-1)`` equals ``pair_counts(pos_a, box_size, s_edges, pos_b)`` bit for bit.
+
+    ``pos_b``, positions, ``check_bounds`` and the scope are those of :func:`pair_counts`; positions in redshift space
+    come from :func:`redshift_positions`."""
+    what = "pair_counts_smu"
+    e = check_pair_count_edges(s_edges, box_size, what)
+    m = check_mu_edges(mu_edges, what)
+    ns, nmu = len(e) - 1, len(m) - 1
+    if ns > _lib.PAIR_COUNTS_SMU_MAX_AXIS:
+        raise ValueError(f"{what}: s_edges must hold ns + 1 radii with 1 <= ns <= {_lib.PAIR_COUNTS_SMU_MAX_AXIS}, got "
+                         f"{len(e)} values")
+    if ns * nmu > _lib.PAIR_COUNTS_SMU_MAX_BINS:
+        raise ValueError(f"{what}: {ns} x {nmu} bins exceed {_lib.PAIR_COUNTS_SMU_MAX_BINS}")
+    los = check_los(los, what)
+    pos_a = f32c(pos_a, "pos_a")
+    batched = pos_a.dim() == 3
+    if pos_a.dim() not in (2, 3) or pos_a.shape[-1] != 3 or pos_a.shape[-2] < 1:
+        raise CgnnError(f"{what}: pos_a must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos_a.shape)}")
+    if pos_b is not None:
+        pos_b = f32c(pos_b, "pos_b")
+        if pos_b.dim() != pos_a.dim() or pos_b.shape[-1] != 3 or pos_b.shape[-2] < 1 or \
+                (batched and pos_b.shape[0] != pos_a.shape[0]):
+            raise CgnnError(f"{what}: pos_b must be [M, 3] (or [T, M, 3] with pos_a's T) with M >= 1, got "
+                            f"{tuple(pos_b.shape)} for pos_a {tuple(pos_a.shape)}")
+        _same_device(pos_a, pos_b)
+    if check_bounds:
+        for name, p in (("pos_a", pos_a), ("pos_b", pos_b)):
+            if p is not None and not bool(((p >= 0) & (p <= float(box_size))).all()):
+                raise ValueError(f"{what}: {name} leaves [0, box_size]")
+    frames_a = pos_a if batched else pos_a.unsqueeze(0)
+    frames_b = None if pos_b is None else (pos_b if batched else pos_b.unsqueeze(0))
+    t, n_a = frames_a.shape[0], frames_a.shape[1]
+    n_b = 0 if frames_b is None else frames_b.shape[1]
+    lib = _lib.load()
+    s_c, mu_c = (C.c_float * (ns + 1))(*e), (C.c_float * (nmu + 1))(*m)
+    ws_bytes = lib.cgnn_pair_counts_smu_workspace_bytes(n_a, n_b, ns, nmu)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos_a.device)
+    counts = torch.empty((t, ns, nmu), dtype=torch.int64, device=pos_a.device)
+    st = stream_ptr(pos_a.device)
+    with _timed(what, pos_a.device):
+        for f in range(t):
+            check(lib.cgnn_pair_counts_smu(frames_a[f].data_ptr(), n_a,
+                                           None if frames_b is None else frames_b[f].data_ptr(), n_b, float(box_size),
+                                           s_c, ns, mu_c, nmu, los, counts[f].data_ptr(), ws.data_ptr(), ws_bytes, st),
+                  "cgnn_pair_counts_smu")
+    return counts if batched else counts[0]
+
+
 def frame_errors(pred_pos: torch.Tensor, true_pos: torch.Tensor, pred_tmp: Optional[torch.Tensor],
                  true_tmp: Optional[torch.Tensor], box_size: float) -> torch.Tensor:
     """Per-frame mean squared errors of a rollout (``cgnn_frame_errors``): ``float64 [T, 2]`` on the device, column 0

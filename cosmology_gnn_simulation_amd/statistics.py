@@ -38,6 +38,12 @@ show in the quadrupole, not in P(k)): ``power_multipoles`` gives P_0, P_2 and P_
 along it by its velocities (``ops.redshift_positions``), from Legendre-weighted shell sums of an interlaced pair of
 meshes (``ops.power_multipoles``); ``rollout_redshift_spectra`` does that for every frame of a rollout against the
 truth; ``multipoles_from_sums`` is the host arithmetic.  ``power_spectrum(interlace=True)`` uses the same reduction.
+Below a few mean interparticle spacings a mesh cannot follow the field, and that is where the virial motions stretch
+structures along the line of sight (the fingers of god): ``correlation_multipoles`` gives xi(s, mu) and xi_0, xi_2,
+xi_4 of the displaced frame from exact pair counts by separation and by mu = |cos| of the angle to the line of sight
+(``ops.pair_counts_smu``), down to zero separation, in integers and with the same bits on every run;
+``rollout_redshift_correlation`` does that for every frame of a rollout against the truth;
+``correlation_multipoles_from_counts`` is the host arithmetic and ``default_mu_edges`` the 20 equal mu-bins.
 
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
@@ -323,8 +329,9 @@ def rollout_power_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth: D
 #
 # ``ops.redshift_positions`` displaces every particle along a box axis by its velocity (plane-parallel line of sight),
 # ``ops.power_multipoles`` sums the modes of the displaced frame's mesh with Legendre weights about that axis and combines
-# an interlaced pair of meshes inside the reduction.  Per-particle or wide-angle lines of sight, xi(s, mu) pair counts,
-# sharded, batched and owned-storage variants, a multipole loss and interlaced momentum and thermal spectra are not built.
+# an interlaced pair of meshes inside the reduction.  Per-particle or wide-angle lines of sight, sharded, batched and
+# owned-storage variants, a multipole loss and interlaced momentum and thermal spectra are not built (xi(s, mu) pair
+# counts: the section after this one).
 
 MULTIPOLES = (0, 2, 4)
 
@@ -517,6 +524,176 @@ def rollout_redshift_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth
     for ell in MULTIPOLES:
         out[f"power_pred_{ell}"], out[f"power_true_{ell}"] = sp[f"power_{ell}"], sp[f"power_b_{ell}"]
         out[f"cross_{ell}"] = sp[f"cross_{ell}"]
+    return out
+
+
+# ---- redshift space below the mesh: xi(s, mu) from exact pair counts, and its multipoles -------------------------------
+#
+# ``ops.pair_counts_smu`` counts the pairs of a frame by separation and by mu = |cos| of the angle to the line of sight;
+# what follows forms xi(s, mu) with the analytic random term of a periodic box and projects it on the Legendre
+# polynomials.  (r_p, pi) counts and w_p, per-particle or wide-angle lines of sight, random catalogues and Landy-Szalay,
+# weighted pairs, sharded, batched and owned-storage variants and a correlation-multipole loss are not built.
+
+def default_mu_edges(n_mu: int = 20) -> torch.Tensor:
+    """``linspace(0, 1, n_mu + 1)``: ``n_mu`` equal bins of mu = |cos| of the angle to the line of sight (float64)."""
+    if isinstance(n_mu, bool) or int(n_mu) != n_mu or not 1 <= n_mu <= _lib.PAIR_COUNTS_SMU_MAX_AXIS:
+        raise ValueError(f"default_mu_edges: n_mu must be an integer in [1, {_lib.PAIR_COUNTS_SMU_MAX_AXIS}], got {n_mu!r}")
+    return torch.linspace(0.0, 1.0, int(n_mu) + 1, dtype=torch.float64)
+
+
+def _mus(mu_edges, who: str) -> torch.Tensor:
+    """The mu edges the kernel bins by (float32 values), as float64."""
+    return torch.tensor(ops.check_mu_edges(default_mu_edges() if mu_edges is None else mu_edges, who),
+                        dtype=torch.float64)
+
+
+def legendre_bin_integrals(mu: torch.Tensor) -> torch.Tensor:
+    """``[3, nmu]``: the integrals of ``L_0``, ``L_2``, ``L_4`` over each bin of the edges ``mu``, in closed form from
+    the antiderivatives ``mu``, ``(mu^3 - mu) / 2`` and ``(7 mu^5 - 10 mu^3 + 3 mu) / 8``."""
+    prim = torch.stack([mu, (mu ** 3 - mu) / 2.0, (7.0 * mu ** 5 - 10.0 * mu ** 3 + 3.0 * mu) / 8.0])
+    return prim[:, 1:] - prim[:, :-1]
+
+
+def correlation_multipoles_from_counts(counts, n_a: int, n_b: Optional[int], box_size: float, s_edges, mu_edges,
+                                       auto: bool) -> Dict:
+    """xi(s, mu) and its multipoles from the ``ns x nmu`` integers of ``ops.pair_counts_smu``, on the host in float64
+    (``counts [ns, nmu]`` or ``[T, ns, nmu]``; everything comes back on the CPU).  The natural estimator with the
+    analytic random term of a periodic box, as in :func:`correlation_from_counts`:
+
+    * ``xi_smu = DD / RR - 1`` with ``RR[i, j] = pairs * 4 pi / 3 (s_{i+1}^3 - s_i^3) / L^3 * (mu_{j+1} - mu_j)`` and
+      ``pairs = N (N - 1) / 2`` (auto; ``n_b`` is ignored) or ``N_a N_b`` (cross): mu is |cos| folded into [0, 1], so a
+      mu-bin holds the fraction ``mu_{j+1} - mu_j`` of a shell;
+    * ``xi_0``, ``xi_2``, ``xi_4`` (``[..., ns]``): ``xi_l[i] = (2 l + 1) sum_j xi_smu[i, j] int_{mu_j}^{mu_{j+1}} L_l(mu)
+      dmu`` with the bin integrals in closed form (:func:`legendre_bin_integrals`).  They are exact for the bins and sum
+      to (1, 0, 0) over [0, 1], so the -1 leaves ``l = 2, 4`` altogether, and ``xi_0`` is
+      ``correlation_from_counts(counts.sum(-1), ...)`` to rounding;
+
+    plus ``s_lo``, ``s_hi`` (``[ns]``), ``mu_lo``, ``mu_hi`` (``[nmu]``) -- the float32 values the kernel binned by, as
+    float64 -- and ``counts`` (int64).  A bin that expects no pair at all (``N < 2``) gives ``nan``."""
+    what = "correlation_multipoles_from_counts"
+    s = _radii(s_edges, box_size, what)
+    mu = _mus(mu_edges, what)
+    ns, nmu = s.numel() - 1, mu.numel() - 1
+    counts = torch.as_tensor(counts).detach().to(device="cpu")
+    if counts.dim() < 2 or tuple(counts.shape[-2:]) != (ns, nmu):
+        raise ValueError(f"{what}: counts {tuple(counts.shape)} for {ns} x {nmu} bins")
+    shell = 4.0 * math.pi / 3.0 * (s[1:] ** 3 - s[:-1] ** 3) / float(box_size) ** 3
+    pairs = n_a * (n_a - 1) / 2.0 if auto else float(n_a) * float(n_b)
+    rr = pairs * shell[:, None] * (mu[1:] - mu[:-1])[None, :]
+    xi = counts.to(torch.float64) / rr - 1.0
+    out = {"s_lo": s[:-1].clone(), "s_hi": s[1:].clone(), "mu_lo": mu[:-1].clone(), "mu_hi": mu[1:].clone(),
+           "counts": counts.to(torch.int64), "xi_smu": xi}
+    for ell, w in zip(MULTIPOLES, legendre_bin_integrals(mu)):
+        out[f"xi_{ell}"] = (2 * ell + 1) * (xi * w).sum(-1)
+    return out
+
+
+def _check_smu_arguments(what: str, box_size, s_edges, mu_edges, los, dt, velocity_scale, moving: bool):
+    """The host refusals of the (s, mu) functions, before any device work; returns the mu edges to bin by and ``los``."""
+    s = ops.check_pair_count_edges(s_edges, box_size, what)
+    mu_edges = ops.check_mu_edges(default_mu_edges() if mu_edges is None else mu_edges, what)
+    ns, nmu = len(s) - 1, len(mu_edges) - 1
+    if ns > _lib.PAIR_COUNTS_SMU_MAX_AXIS or ns * nmu > _lib.PAIR_COUNTS_SMU_MAX_BINS:
+        raise ValueError(f"{what}: {ns} x {nmu} bins exceed {_lib.PAIR_COUNTS_SMU_MAX_AXIS} per axis or "
+                         f"{_lib.PAIR_COUNTS_SMU_MAX_BINS} in all")
+    los = ops.check_los(los, what)
+    if moving:
+        ops.redshift_shift(dt, velocity_scale, what)
+    return mu_edges, los
+
+
+def correlation_multipoles(pos: torch.Tensor, box_size: float, s_edges, mu_edges=None,
+                           pos_prev: Optional[torch.Tensor] = None, dt: Optional[float] = None,
+                           velocity_scale: float = 1.0, los: int = 2, pos_b: Optional[torch.Tensor] = None,
+                           pos_b_prev: Optional[torch.Tensor] = None) -> Dict:
+    """xi(s, mu) and the multipoles ``xi_0``, ``xi_2``, ``xi_4`` of ``pos`` (``[N, 3]`` or ``[T, N, 3]``) about the box
+    axis ``los`` from exact pair counts (``ops.pair_counts_smu``), in redshift space when ``pos_prev`` (the frame before,
+    the same shape) and ``dt`` are given: every particle is first displaced along ``los`` by ``velocity_scale *
+    minimum_image(pos - pos_prev) / dt`` (``ops.redshift_positions``), as in :func:`power_multipoles`.  Without
+    ``pos_prev`` they are the real-space multipoles of ``pos``.  With ``pos_b`` (and ``pos_b_prev`` when ``pos_prev`` is
+    given) the cross counts and cross multipoles of the two sets, and only those.  ``mu_edges`` defaults to
+    :func:`default_mu_edges`.  Returns the dict of :func:`correlation_multipoles_from_counts`.  Everything is counted on
+    the device of ``pos`` without a host synchronisation and comes back in one transfer."""
+    what = "correlation_multipoles"
+    moving = pos_prev is not None
+    if moving and dt is None:
+        raise ValueError(f"{what}: pos_prev needs dt")
+    mu_edges, los = _check_smu_arguments(what, box_size, s_edges, mu_edges, los, dt, velocity_scale, moving)
+    if (pos_b_prev is not None) != (pos_b is not None and moving):
+        raise ValueError(f"{what}: pos_b_prev is given exactly when pos_b and pos_prev both are")
+    sets = []
+    for name, cur, prev in (("pos", pos, pos_prev), ("pos_b", pos_b, pos_b_prev)):
+        if cur is None:
+            sets.append(None)
+            continue
+        frames = _f32_frames(cur, name, what)
+        if cur.dim() != pos.dim() or frames.shape[0] != (pos.shape[0] if pos.dim() == 3 else 1):
+            raise ValueError(f"{what}: {name} {tuple(cur.shape)} does not go with pos {tuple(pos.shape)}")
+        if prev is not None:
+            if tuple(prev.shape) != tuple(cur.shape):
+                raise ValueError(f"{what}: {name}_prev {tuple(prev.shape)} and {name} {tuple(cur.shape)} differ in shape")
+            frames = ops.redshift_positions(frames, _f32_frames(prev, name + "_prev", what).to(frames.device), dt,
+                                            box_size, los, velocity_scale)
+        sets.append(frames)
+    counts = ops.pair_counts_smu(sets[0], box_size, s_edges, mu_edges, sets[1], los=los).cpu()
+    if pos.dim() == 2:
+        counts = counts[0]
+    return correlation_multipoles_from_counts(counts, sets[0].shape[1], None if sets[1] is None else sets[1].shape[1],
+                                              box_size, s_edges, mu_edges, sets[1] is None)
+
+
+def rollout_redshift_correlation(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
+                                 box_size: float, s_edges, dt: float, velocity_scale: float = 1.0, los: int = 2,
+                                 frames: Optional[Sequence[int]] = None, mu_edges=None) -> Dict:
+    """Redshift-space correlation multipoles of a rollout against the truth, for the dicts ``rollout.rollout`` returns
+    (``Coordinates [T, N, 3]``): :func:`rollout_redshift_spectra` below the scales a mesh can follow, where the virial
+    motions inside halos stretch structures along the line of sight.  Every judged frame of either side is displaced
+    along ``los`` by its own velocity, ``minimum_image`` of its step from the frame before in the same dict, over ``dt``
+    and times ``velocity_scale`` (:func:`correlation_multipoles`).  ``frames``: the frame numbers to judge (default:
+    every frame from 1 on that both hold); frame 0 has no predecessor: its multipoles are ``nan`` and its counts 0.
+    Per selected frame (CPU), for ``l`` in 0, 2, 4:
+
+    * ``xi_pred_l``, ``xi_true_l``: the multipoles of the two sides; ``xi_cross_l``: of their cross counts (float64
+      ``[F, ns]``);
+    * ``counts_pred``, ``counts_true``, ``counts_cross``: the pair counts behind them (int64 ``[F, ns, nmu]``);
+    * ``quadrupole_ratio``: ``xi_pred_2 / xi_true_2``,
+
+    plus ``frames``, ``s_lo``, ``s_hi`` (``[ns]``) and ``mu_lo``, ``mu_hi`` (``[nmu]``).  No host synchronisation per
+    frame; one transfer."""
+    what = "rollout_redshift_correlation"
+    mu_edges, los = _check_smu_arguments(what, box_size, s_edges, mu_edges, los, dt, velocity_scale, True)
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    truth = {"Coordinates": ground_truth["Coordinates"].to(dev)}       # moved once: the predecessors come from it too
+    if frames is None:
+        frames = range(1, min(len(pc), len(truth["Coordinates"])))
+    cp, ct, sel = _rollout_frames(rollout_data, truth, frames, what)
+    rows = [i for i, f in enumerate(sel) if f > 0]
+    if not rows:
+        raise ValueError(f"{what}: no selected frame has a predecessor (frames {sel})")
+    n = cp.shape[1]
+    prev = torch.tensor([sel[i] - 1 for i in rows], dtype=torch.int64).to(dev)
+    at = torch.tensor(rows, dtype=torch.int64).to(dev)
+    sides = []
+    for cur, source in ((cp, pc), (ct, truth["Coordinates"])):
+        sides.append(ops.redshift_positions(_f32_frames(cur.index_select(0, at), "Coordinates", what),
+                                            _f32_frames(source.index_select(0, prev), "Coordinates", what), dt, box_size,
+                                            los, velocity_scale))
+    counted = torch.stack([ops.pair_counts_smu(sides[0], box_size, s_edges, mu_edges, los=los),
+                           ops.pair_counts_smu(sides[1], box_size, s_edges, mu_edges, los=los),
+                           ops.pair_counts_smu(sides[0], box_size, s_edges, mu_edges, sides[1], los=los)]).cpu()
+    counts = torch.zeros((3, len(sel)) + tuple(counted.shape[2:]), dtype=torch.int64)
+    counts[:, rows] = counted
+    out = {"frames": sel}
+    no_prev = torch.tensor([f == 0 for f in sel])[:, None]             # frame 0: nan
+    for i, (name, auto) in enumerate((("pred", True), ("true", True), ("cross", False))):
+        res = correlation_multipoles_from_counts(counts[i], n, n, box_size, s_edges, mu_edges, auto)
+        out[f"counts_{name}"] = res["counts"]
+        for ell in MULTIPOLES:
+            out[f"xi_{name}_{ell}"] = res[f"xi_{ell}"].masked_fill(no_prev, float("nan"))
+    for key in ("s_lo", "s_hi", "mu_lo", "mu_hi"):
+        out[key] = res[key]
+    out["quadrupole_ratio"] = out["xi_pred_2"] / out["xi_true_2"]
     return out
 
 

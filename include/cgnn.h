@@ -568,6 +568,31 @@ int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_
                      const float* edges, int32_t num_bins, int64_t* counts,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same pairs counted by separation s and by mu, the |cosine| of the angle between the separation and a plane-parallel
+ * line of sight along the box axis los (0, 1 or 2): the DD / D1D2 terms of the redshift-space correlation function
+ * xi(s, mu) and of its multipoles.  s_edges (HOST memory, num_s + 1 floats) are the radii, mu_edges (HOST memory,
+ * num_mu + 1 floats) run from exactly 0 to exactly 1.  dx, dy, dz and d2 are exactly those of the entry above, summed in
+ * the order x, y, z whatever los is; dl is the folded separation on axis los and dl2 = fl32(dl*dl), the very product that
+ * enters d2.  With e2[i] = fl32(s_edges[i] * s_edges[i]) the pair is counted iff e2[0] <= d2 < e2[num_s], in the s-bin i
+ * with e2[i] <= d2 < e2[i + 1]; with m2[j] = fl32(mu_edges[j] * mu_edges[j]) its mu-bin is
+ *     j = the number of j' in 1 .. num_mu - 1 with fl32(m2[j'] * d2) <= dl2
+ * one float32 rounding per operation, no FMA, no division.  Rounding is monotone: the thresholds ascend with j' (a
+ * binary search gives the same number) and dl2 <= d2 for every los.  mu_edges[0] and mu_edges[num_mu] are not tested per
+ * pair.  A pair exactly along the line of sight lands in the last mu-bin, one exactly across it in bin 0, and a
+ * coincident cross pair (d2 = 0, counted only when s_edges[0] == 0) meets every threshold and lands in the LAST mu-bin.
+ * The rule is symmetric in a and b; auto and cross as in the entry above.
+ * counts (device, int64 [num_s][num_mu]) is overwritten; summed over mu it equals what the entry above counts for
+ * edges = s_edges, bit for bit.  Exact integers, the same bits on every run.  No host synchronisation, everything on
+ * `stream`.
+ * CGNN_ERR_INVALID_ARG unless 1 <= num_s <= 128, 1 <= num_mu <= 128, num_s * num_mu <= 4096, s_edges as the edges of the
+ * entry above, mu_edges finite and strictly ascending from exactly 0 to exactly 1, 0 <= los <= 2 and box_size > 0; 2^31 or
+ * more particles in a set: CGNN_ERR_UNSUPPORTED.  All of it is refused on the host before any launch.
+ * Workspace: a function of n_a and n_b alone (n_b = 0: auto), O(n_a + n_b), 16-byte aligned. */
+size_t cgnn_pair_counts_smu_workspace_bytes(int64_t n_a, int64_t n_b, int32_t num_s, int32_t num_mu);
+int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, float box_size,
+                         const float* s_edges, int32_t num_s, const float* mu_edges, int32_t num_mu, int32_t los,
+                         int64_t* counts /* [num_s][num_mu] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-frame errors of a rollout against the truth: pred_pos / true_pos [frames, n, 3], pred_tmp / true_tmp [frames, n]
  * (both NULL: no temperatures, the second sum is 0).  out (device, double [frames, 2]):
  *   out[f, 0] = sum over particles and axes of fold(fl32(pred - true))^2     (fold: the minimum image of the entry above)
