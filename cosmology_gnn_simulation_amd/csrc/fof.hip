@@ -62,21 +62,6 @@
 
 namespace cgnn {
 
-struct FofLayout {
-    int64_t cells_max;   // cell slots of the finest grid n allows: the tables are sized for it
-    SortedSetLayout set;
-    ItemTableLayout items;
-    size_t total;
-};
-
-static FofLayout fof_layout(int64_t n) {
-    FofLayout L;
-    L.cells_max = pair_cell_slots(pair_cells_per_axis(n, 1.f, -1.f, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE));
-    const size_t off = sorted_set_layout(L.set, 0, L.cells_max, n);
-    L.total = item_table_layout(L.items, off, L.cells_max, n, CGNN_FOF_QCHUNK);
-    return L;
-}
-
 __global__ void fof_init_kernel(int32_t* __restrict__ parent, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) parent[i] = (int32_t)i;
@@ -207,7 +192,7 @@ extern "C" {
 
 size_t cgnn_fof_labels_workspace_bytes(int64_t n) {
     if (n <= 0 || n >= ((int64_t)1 << 31)) return 256;
-    return fof_layout(n).total;
+    return pair_job_layout(n, 0, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE, CGNN_FOF_QCHUNK).total;
 }
 
 int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_length, int32_t* labels, void* workspace,
@@ -226,31 +211,21 @@ int cgnn_fof_labels(const float* pos, int64_t n, float box_size, float linking_l
         set_error("cgnn_fof_labels: 2^31 or more particles are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_fof_labels: workspace must be 16-byte aligned");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const FofLayout L = fof_layout(n);
-    if (workspace_bytes < L.total) {
-        set_error("cgnn_fof_labels: workspace %zu < required %zu bytes", workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
-    const int G = pair_cells_per_axis(n, box_size, linking_length, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE);
-    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
-    const float inv_h = (float)G / box_size;
+    const PairJobLayout L = pair_job_layout(n, 0, CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE, CGNN_FOF_QCHUNK);
+    int rc = check_pair_workspace("cgnn_fof_labels", workspace, workspace_bytes, L.total);
+    if (rc) return rc;
     const float l2 = linking_length * linking_length;   // fl32 product, rounded once
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    const SortedSet S = sorted_set(ws, L.set);
-    const ItemTable I = item_table(ws, L.items);
     const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
     fof_init_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
-    const int rc = sorted_set_sort(pos, n, inv_h, G, cells, S, I.bsum, st, "fof_labels", "cgnn_fof_labels");
+    PairWalkArgs W;
+    unsigned blocks;
+    rc = pair_job_prepare<CGNN_FOF_QCHUNK>("cgnn_fof_labels", L, pos, n, nullptr, 0, box_size, linking_length,
+                                           CGNN_FOF_MAX_G, CGNN_FOF_CELLS_PER_PARTICLE, workspace, st, W, blocks);
     if (rc) return rc;
-    item_table_build<CGNN_FOF_QCHUNK>(S, n, cells, I, st);
-    fof_walk_kernel<<<pair_walk_blocks(cells, n, CGNN_FOF_QCHUNK), CGNN_FOF_QCHUNK, 0, st>>>(
-        S.sorted, S.start, S.cell_of, I.chunk_start, I.item_q0, (int)cells, G, box_size, half, l2, labels);
+    fof_walk_kernel<<<blocks, CGNN_FOF_QCHUNK, 0, st>>>(W.sorted_a, W.start_a, W.cell_of_a, W.chunk_start, W.item_q0,
+                                                        W.cells, W.G, W.box, W.half, l2, labels);
     fof_labels_kernel<<<nb, CGNN_BLOCK, 0, st>>>(labels, n);
     return check_hip(hipGetLastError(), "cgnn_fof_labels");
 }

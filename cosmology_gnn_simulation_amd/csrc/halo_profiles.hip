@@ -8,12 +8,11 @@
 // e2[i] <= d2 < e2[i + 1].  A centre is no particle: nothing is excluded, and d2 == 0 counts (in bin 0) iff edges[0] == 0.
 // Summed over the centres the counts are those of cgnn_pair_counts(centres, particles) in cross mode, bit for bit.
 //
-// Grid and walk (pair_walk.hpp).  The particles (set B) and the centres (set A) are sorted into one Morton cell grid with
-// the shared rule for reach = edges[num_bins], capped so that G^3 <= n and G <= 256.  A work item is up to CGNN_HP_QCHUNK
-// = 8 centres of one cell; its workgroup of CGNN_HP_TILE = 256 threads runs the 27 cells' particles through in tiles of
-// one particle per lane against every staged centre (pair_walk_tiled).  Few centres per item on purpose: halos crowd
-// where the particles do, a cell of a cluster holds dozens of centres and hundreds of thousands of candidates, and its
-// centres then spread over several workgroups instead of queueing in one.
+// Grid and walk: the job of pair_walk.hpp with the centres as set A and the particles as set B, reach = edges[num_bins],
+// capped so that G^3 <= n and G <= 256.  A work item is up to CGNN_HP_QCHUNK = 8 centres of one cell against tiles of
+// CGNN_HP_TILE = 256 particles (pair_walk_tiled).  Few centres per item on purpose: halos crowd where the particles do,
+// a cell of a cluster holds dozens of centres and hundreds of thousands of candidates, and its centres then spread over
+// several workgroups instead of queueing in one.
 //
 // Count (hp_walk_kernel<C>).  A hit adds 1 to the 32-bit LDS counter hist[qi][bin] of the item's qi-th centre, and with
 // values q[p, c] to the 64-bit LDS sums vsum[qi][bin][c]; a lane loads its particle's values once per tile, at its first
@@ -41,22 +40,6 @@ namespace cgnn {
 struct HpEdges2 {
     float e2[CGNN_HP_MAX_BINS + 1];
 };
-
-struct HpLayout {
-    int64_t cells_max;       // cell slots of the finest grid the particle count allows: the tables are sized for it
-    SortedSetLayout a, b;    // a: the centres, b: the particles
-    ItemTableLayout items;
-    size_t total;
-};
-
-static HpLayout hp_layout(int64_t n, int64_t num_centres) {
-    HpLayout L;
-    L.cells_max = pair_cell_slots(pair_cells_per_axis(n, 1.f, -1.f, CGNN_HP_MAX_G, 1));
-    size_t off = sorted_set_layout(L.a, 0, L.cells_max, num_centres);
-    off = sorted_set_layout(L.b, off, L.cells_max, n);
-    L.total = item_table_layout(L.items, off, L.cells_max, num_centres, CGNN_HP_QCHUNK);
-    return L;
-}
 
 template <int C>
 __global__ __launch_bounds__(CGNN_HP_TILE) void hp_walk_kernel(
@@ -128,7 +111,7 @@ extern "C" {
 
 size_t cgnn_halo_profiles_workspace_bytes(int64_t n, int64_t num_centres) {
     if (n <= 0 || num_centres <= 0 || n >= ((int64_t)1 << 31) || num_centres >= ((int64_t)1 << 31)) return 256;
-    return hp_layout(n, num_centres).total;
+    return pair_job_layout(num_centres, n, CGNN_HP_MAX_G, 1, CGNN_HP_QCHUNK).total;
 }
 
 int cgnn_halo_profiles(const float* pos, int64_t n, const float* centres, int64_t num_centres, float box_size,
@@ -151,61 +134,35 @@ int cgnn_halo_profiles(const float* pos, int64_t n, const float* centres, int64_
         set_error("cgnn_halo_profiles: num_bins=%d outside [1, %d]", (int)num_bins, CGNN_HP_MAX_BINS);
         return CGNN_ERR_INVALID_ARG;
     }
-    const float half = 0.5f * box_size;
-    for (int i = 0; i <= num_bins; ++i) {
-        if (!isfinite(edges[i]) || edges[i] < 0.f || (i > 0 && !(edges[i] > edges[i - 1]))) {
-            set_error("cgnn_halo_profiles: edges must be finite, non-negative and strictly ascending (edges[%d])", i);
-            return CGNN_ERR_INVALID_ARG;
-        }
-    }
-    if (edges[num_bins] > half) {
-        set_error("cgnn_halo_profiles: edges[num_bins]=%g exceeds half the box, %g", (double)edges[num_bins],
-                  (double)half);
-        return CGNN_ERR_INVALID_ARG;
-    }
+    HpEdges2 E;
+    int rc = load_radial_edges("cgnn_halo_profiles", "edges", "num_bins", edges, num_bins, 0.5f * box_size, E.e2,
+                               CGNN_HP_MAX_BINS + 1);
+    if (rc) return rc;
     if (n >= ((int64_t)1 << 31) || num_centres >= ((int64_t)1 << 31)) {
         set_error("cgnn_halo_profiles: 2^31 or more particles or centres are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_halo_profiles: workspace must be 16-byte aligned");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const HpLayout L = hp_layout(n, num_centres);
-    if (workspace_bytes < L.total) {
-        set_error("cgnn_halo_profiles: workspace %zu < required %zu bytes", workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
-    const int G = pair_cells_per_axis(n, box_size, edges[num_bins], CGNN_HP_MAX_G, 1);
-    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
-    const float inv_h = (float)G / box_size;
-    HpEdges2 E;
-    for (int i = 0; i <= num_bins; ++i) E.e2[i] = edges[i] * edges[i];   // fl32 product, rounded once
-    for (int i = num_bins + 1; i <= CGNN_HP_MAX_BINS; ++i) E.e2[i] = 0.f;
+    const PairJobLayout L = pair_job_layout(num_centres, n, CGNN_HP_MAX_G, 1, CGNN_HP_QCHUNK);
+    rc = check_pair_workspace("cgnn_halo_profiles", workspace, workspace_bytes, L.total);
+    if (rc) return rc;
     const int C = q != nullptr ? (int)channels : 0;
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    const SortedSet A = sorted_set(ws, L.a), B = sorted_set(ws, L.b);
-    const ItemTable I = item_table(ws, L.items);
-    int rc = check_hip(hipMemsetAsync(counts, 0, (size_t)num_centres * num_bins * 8, st), "halo_profiles memset counts");
+    rc = check_hip(hipMemsetAsync(counts, 0, (size_t)num_centres * num_bins * 8, st), "halo_profiles memset counts");
     if (rc) return rc;
     if (C > 0) {
         rc = check_hip(hipMemsetAsync(sums, 0, (size_t)num_centres * num_bins * C * 8, st), "halo_profiles memset sums");
         if (rc) return rc;
     }
-    rc = sorted_set_sort(centres, num_centres, inv_h, G, cells, A, I.bsum, st, "halo_profiles", "cgnn_halo_profiles sort");
+    PairWalkArgs W;
+    unsigned blocks;
+    rc = pair_job_prepare<CGNN_HP_QCHUNK>("cgnn_halo_profiles", L, centres, num_centres, pos, n, box_size, edges[num_bins],
+                                          CGNN_HP_MAX_G, 1, workspace, st, W, blocks);
     if (rc) return rc;
-    rc = sorted_set_sort(pos, n, inv_h, G, cells, B, I.bsum, st, "halo_profiles", "cgnn_halo_profiles sort");
-    if (rc) return rc;
-    item_table_build<CGNN_HP_QCHUNK>(A, num_centres, cells, I, st);
-    const unsigned blocks = pair_walk_blocks(cells, num_centres, CGNN_HP_QCHUNK);
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
     unsigned long long* sm = reinterpret_cast<unsigned long long*>(sums);
-#define CGNN_HP_LAUNCH(CH)                                                                                             \
-    hp_walk_kernel<CH><<<blocks, CGNN_HP_TILE, 0, st>>>(A.sorted, A.start, A.cell_of, B.sorted, B.start, I.chunk_start, \
-                                                        I.item_q0, (int)cells, G, box_size, half, E, num_bins, q, cnt, \
-                                                        sm)
+#define CGNN_HP_LAUNCH(CH) \
+    hp_walk_kernel<CH><<<blocks, CGNN_HP_TILE, 0, st>>>(CGNN_PAIR_WALK_ARGS(W), E, num_bins, q, cnt, sm)
     switch (C) {
         case 0: CGNN_HP_LAUNCH(0); break;
         case 1: CGNN_HP_LAUNCH(1); break;

@@ -8,12 +8,8 @@
 // e2[i] <= d2 < e2[i + 1].  The expression is symmetric in a and b, so the auto mode counts ordered pairs i != j and
 // halves the exact even totals at the end.
 //
-// Grid and walk (pair_walk.hpp).  The partner set (B, or A in auto mode) is sorted into the Morton cell grid with the
-// shared grid rule for reach = edges[num_bins], capped so that G^3 <= partners and G <= 256; a counted pair has
-// d2 < e2[num_bins], so the 27 cells around a query's hold all its counted partners.  The walk only proposes candidates;
-// the contract above alone decides what is counted, and every distinct cell is met exactly once per query, so no pair
-// is counted twice.  A, too, is sorted into the same grid (in auto mode it is the same sort), so a run of sorted A
-// particles shares one neighbourhood: a work item is up to CGNN_PC_QCHUNK queries of one cell.
+// Grid and walk: the job of pair_walk.hpp for reach = edges[num_bins], capped so that G^3 <= partners and G <= 256, in
+// work items of up to CGNN_PC_QCHUNK queries.  The walk only proposes; the contract above alone decides what counts.
 //
 // Count (pc_walk_kernel).  The bin of a proposed pair is found by comparing d2 with the e2 table in LDS (no sqrt, no
 // log), counted with a 32-bit LDS atomic into the wave's own histogram, and the histograms are added to the global int64
@@ -34,23 +30,6 @@ namespace cgnn {
 struct PcEdges2 {
     float e2[CGNN_PC_MAX_BINS + 1];
 };
-
-struct PcLayout {
-    int64_t cells_max;       // cell slots of the finest grid the partner count allows: the tables are sized for it
-    SortedSetLayout a, b;    // auto mode: b == a
-    ItemTableLayout items;
-    size_t total;
-};
-
-static PcLayout pc_layout(int64_t n_a, int64_t n_b, bool cross) {
-    PcLayout L;
-    L.cells_max = pair_cell_slots(pair_cells_per_axis(cross ? n_b : n_a, 1.f, -1.f, CGNN_PC_MAX_G, 1));
-    size_t off = sorted_set_layout(L.a, 0, L.cells_max, n_a);
-    if (cross) off = sorted_set_layout(L.b, off, L.cells_max, n_b);
-    else L.b = L.a;
-    L.total = item_table_layout(L.items, off, L.cells_max, n_a, CGNN_PC_QCHUNK);
-    return L;
-}
 
 // the waves' histograms -> global counts, and back to zero; every thread of the workgroup calls it
 __device__ __forceinline__ void pc_flush(unsigned (*hist)[CGNN_PC_MAX_BINS], int num_bins,
@@ -96,12 +75,6 @@ __global__ __launch_bounds__(CGNN_PC_QCHUNK) void pc_walk_kernel(
                 atomicAdd(&hist[wave][bin_of(e2_s, num_bins, d2)], 1u);
         });
     pc_flush(hist, num_bins, counts);
-}
-
-// auto mode: ordered pairs i != j -> unordered pairs (every total is even: the contract is symmetric)
-__global__ void pc_halve_kernel(unsigned long long* __restrict__ counts, int num_bins) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < num_bins) counts[b] >>= 1;
 }
 
 // ---- cgnn_frame_errors -----------------------------------------------------------------------------------------------
@@ -172,7 +145,7 @@ extern "C" {
 size_t cgnn_pair_counts_workspace_bytes(int64_t n_a, int64_t n_b, int32_t num_bins) {
     (void)num_bins;
     if (n_a <= 0 || n_b < 0 || n_a >= ((int64_t)1 << 31) || n_b >= ((int64_t)1 << 31)) return 256;
-    return pc_layout(n_a, n_b, n_b > 0).total;
+    return pair_job_layout(n_a, n_b, CGNN_PC_MAX_G, 1, CGNN_PC_QCHUNK).total;
 }
 
 int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, float box_size,
@@ -188,56 +161,30 @@ int cgnn_pair_counts(const float* pos_a, int64_t n_a, const float* pos_b, int64_
         set_error("cgnn_pair_counts: num_bins=%d outside [1, %d]", (int)num_bins, CGNN_PC_MAX_BINS);
         return CGNN_ERR_INVALID_ARG;
     }
-    const float half = 0.5f * box_size;
-    for (int i = 0; i <= num_bins; ++i) {
-        if (!isfinite(edges[i]) || edges[i] < 0.f || (i > 0 && !(edges[i] > edges[i - 1]))) {
-            set_error("cgnn_pair_counts: edges must be finite, non-negative and strictly ascending (edges[%d])", i);
-            return CGNN_ERR_INVALID_ARG;
-        }
-    }
-    if (edges[num_bins] > half) {
-        set_error("cgnn_pair_counts: edges[num_bins]=%g exceeds half the box, %g", (double)edges[num_bins], (double)half);
-        return CGNN_ERR_INVALID_ARG;
-    }
+    PcEdges2 E;
+    int rc = load_radial_edges("cgnn_pair_counts", "edges", "num_bins", edges, num_bins, 0.5f * box_size, E.e2,
+                               CGNN_PC_MAX_BINS + 1);
+    if (rc) return rc;
     if (n_a >= ((int64_t)1 << 31) || (cross && n_b >= ((int64_t)1 << 31))) {
         set_error("cgnn_pair_counts: 2^31 or more particles in one set are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_pair_counts: workspace must be 16-byte aligned");
-        return CGNN_ERR_INVALID_ARG;
-    }
     if (!cross) n_b = 0;
-    const PcLayout L = pc_layout(n_a, n_b, cross);
-    if (workspace_bytes < L.total) {
-        set_error("cgnn_pair_counts: workspace %zu < required %zu bytes", workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
-    const int G = pair_cells_per_axis(cross ? n_b : n_a, box_size, edges[num_bins], CGNN_PC_MAX_G, 1);
-    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
-    const float inv_h = (float)G / box_size;
-    PcEdges2 E;
-    for (int i = 0; i <= num_bins; ++i) E.e2[i] = edges[i] * edges[i];   // fl32 product, rounded once
-    for (int i = num_bins + 1; i <= CGNN_PC_MAX_BINS; ++i) E.e2[i] = 0.f;
+    const PairJobLayout L = pair_job_layout(n_a, n_b, CGNN_PC_MAX_G, 1, CGNN_PC_QCHUNK);
+    rc = check_pair_workspace("cgnn_pair_counts", workspace, workspace_bytes, L.total);
+    if (rc) return rc;
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    const SortedSet A = sorted_set(ws, L.a), B = sorted_set(ws, L.b);
-    const ItemTable I = item_table(ws, L.items);
-    int rc = check_hip(hipMemsetAsync(counts, 0, (size_t)num_bins * 8, st), "pair_counts memset counts");
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+    rc = check_hip(hipMemsetAsync(counts, 0, (size_t)num_bins * 8, st), "pair_counts memset counts");
     if (rc) return rc;
-    rc = sorted_set_sort(pos_a, n_a, inv_h, G, cells, A, I.bsum, st, "pair_counts", "cgnn_pair_counts sort");
+    PairWalkArgs W;
+    unsigned blocks;
+    rc = pair_job_prepare<CGNN_PC_QCHUNK>("cgnn_pair_counts", L, pos_a, n_a, pos_b, n_b, box_size, edges[num_bins],
+                                          CGNN_PC_MAX_G, 1, workspace, st, W, blocks);
     if (rc) return rc;
-    if (cross) {
-        rc = sorted_set_sort(pos_b, n_b, inv_h, G, cells, B, I.bsum, st, "pair_counts", "cgnn_pair_counts sort");
-        if (rc) return rc;
-    }
-    item_table_build<CGNN_PC_QCHUNK>(A, n_a, cells, I, st);
-    pc_walk_kernel<<<pair_walk_blocks(cells, n_a, CGNN_PC_QCHUNK), CGNN_PC_QCHUNK, 0, st>>>(
-        A.sorted, A.start, A.cell_of, B.sorted, B.start, I.chunk_start, I.item_q0, (int)cells, G, box_size, half, E,
-        num_bins, cross ? 0 : 1, reinterpret_cast<unsigned long long*>(counts));
-    if (!cross)
-        pc_halve_kernel<<<1, CGNN_PC_MAX_BINS, 0, st>>>(reinterpret_cast<unsigned long long*>(counts), num_bins);
+    pc_walk_kernel<<<blocks, CGNN_PC_QCHUNK, 0, st>>>(CGNN_PAIR_WALK_ARGS(W), E, num_bins, cross ? 0 : 1, out);
+    if (!cross) pair_halve(out, num_bins, st);
     return check_hip(hipGetLastError(), "cgnn_pair_counts");
 }
 

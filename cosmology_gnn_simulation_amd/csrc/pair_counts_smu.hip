@@ -14,9 +14,9 @@
 // is 0 <= 0) in the last.  Symmetric in a and b: the auto mode counts ordered pairs i != j and halves the even totals.
 // Summed over mu the counts are cgnn_pair_counts' for the same s_edges, bit for bit: the s-bin rule is the same code.
 //
-// Grid, sort, item table and walk are the pair counter's (pair_walk.hpp): G from reach = s_edges[num_s], capped so that
-// G^3 <= partners and G <= 256, pair_walk<256>, pair_walk_blocks workgroups.  The visit callback recomputes the folded
-// los separation from a and b; the kernel is instantiated per los, so the compiler shares it with pair_d2's.
+// Grid and walk: the job of pair_walk.hpp with the pair counter's constants (reach = s_edges[num_s], G^3 <= partners,
+// G <= 256, items of 256 queries).  The visit callback recomputes the folded los separation from a and b; the kernel is
+// instantiated per los, so the compiler shares it with pair_d2's.
 //
 // LDS form.  Only a pair inside [e2[0], e2[num_s]) searches the two threshold tables (LDS, 129 floats each), and adds
 // one to a 32-bit LDS histogram of num_s num_mu bins with an LDS atomic.  The histogram is dynamic LDS of
@@ -55,24 +55,6 @@ struct SmuTables {
     float e2[CGNN_SMU_MAX_AXIS + 1];   // fl32(s_edges^2)
     float m2[CGNN_SMU_MAX_AXIS + 1];   // fl32(mu_edges^2)
 };
-
-struct SmuLayout {
-    int64_t cells_max;       // cell slots of the finest grid the partner count allows: the tables are sized for it
-    SortedSetLayout a, b;    // auto mode: b == a
-    ItemTableLayout items;
-    size_t total;
-};
-
-// the pair counter's workspace: a function of the counts alone
-static SmuLayout smu_layout(int64_t n_a, int64_t n_b, bool cross) {
-    SmuLayout L;
-    L.cells_max = pair_cell_slots(pair_cells_per_axis(cross ? n_b : n_a, 1.f, -1.f, CGNN_SMU_MAX_G, 1));
-    size_t off = sorted_set_layout(L.a, 0, L.cells_max, n_a);
-    if (cross) off = sorted_set_layout(L.b, off, L.cells_max, n_b);
-    else L.b = L.a;
-    L.total = item_table_layout(L.items, off, L.cells_max, n_a, CGNN_SMU_QCHUNK);
-    return L;
-}
 
 // histograms per workgroup: one per wave, halved until they fit CGNN_SMU_HIST_COUNTERS (the file header has the reason)
 static int smu_copies(int bins) {
@@ -138,12 +120,6 @@ __global__ __launch_bounds__(CGNN_SMU_QCHUNK) void smu_walk_kernel(
     smu_flush(smu_hist, copies, bins, counts);
 }
 
-// auto mode: ordered pairs i != j -> unordered pairs (every total is even: the contract is symmetric)
-__global__ void smu_halve_kernel(unsigned long long* __restrict__ counts, int bins) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < bins) counts[b] >>= 1;
-}
-
 }  // namespace cgnn
 
 using namespace cgnn;
@@ -154,7 +130,7 @@ size_t cgnn_pair_counts_smu_workspace_bytes(int64_t n_a, int64_t n_b, int32_t nu
     (void)num_s;
     (void)num_mu;
     if (n_a <= 0 || n_b < 0 || n_a >= ((int64_t)1 << 31) || n_b >= ((int64_t)1 << 31)) return 256;
-    return smu_layout(n_a, n_b, n_b > 0).total;
+    return pair_job_layout(n_a, n_b, CGNN_SMU_MAX_G, 1, CGNN_SMU_QCHUNK).total;
 }
 
 int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, float box_size,
@@ -179,18 +155,10 @@ int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, in
         set_error("cgnn_pair_counts_smu: los=%d is no box axis 0, 1 or 2", (int)los);
         return CGNN_ERR_INVALID_ARG;
     }
-    const float half = 0.5f * box_size;
-    for (int i = 0; i <= num_s; ++i) {
-        if (!isfinite(s_edges[i]) || s_edges[i] < 0.f || (i > 0 && !(s_edges[i] > s_edges[i - 1]))) {
-            set_error("cgnn_pair_counts_smu: s_edges must be finite, non-negative and strictly ascending (s_edges[%d])", i);
-            return CGNN_ERR_INVALID_ARG;
-        }
-    }
-    if (s_edges[num_s] > half) {
-        set_error("cgnn_pair_counts_smu: s_edges[num_s]=%g exceeds half the box, %g", (double)s_edges[num_s],
-                  (double)half);
-        return CGNN_ERR_INVALID_ARG;
-    }
+    SmuTables E;
+    int rc = load_radial_edges("cgnn_pair_counts_smu", "s_edges", "num_s", s_edges, num_s, 0.5f * box_size, E.e2,
+                               CGNN_SMU_MAX_AXIS + 1);
+    if (rc) return rc;
     for (int i = 0; i <= num_mu; ++i) {
         if (!isfinite(mu_edges[i]) || (i > 0 && !(mu_edges[i] > mu_edges[i - 1]))) {
             set_error("cgnn_pair_counts_smu: mu_edges must be finite and strictly ascending (mu_edges[%d])", i);
@@ -206,41 +174,23 @@ int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, in
         set_error("cgnn_pair_counts_smu: 2^31 or more particles in one set are not supported");
         return CGNN_ERR_UNSUPPORTED;
     }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("cgnn_pair_counts_smu: workspace must be 16-byte aligned");
-        return CGNN_ERR_INVALID_ARG;
-    }
     if (!cross) n_b = 0;
-    const SmuLayout L = smu_layout(n_a, n_b, cross);
-    if (workspace_bytes < L.total) {
-        set_error("cgnn_pair_counts_smu: workspace %zu < required %zu bytes", workspace_bytes, L.total);
-        return CGNN_ERR_WORKSPACE;
-    }
-    const int G = pair_cells_per_axis(cross ? n_b : n_a, box_size, s_edges[num_s], CGNN_SMU_MAX_G, 1);
-    const int64_t cells = pair_cell_slots(G);  // <= L.cells_max: G never exceeds the cap the layout is sized for
-    const float inv_h = (float)G / box_size;
-    SmuTables E;
-    for (int i = 0; i <= CGNN_SMU_MAX_AXIS; ++i) {   // fl32 products, rounded once
-        E.e2[i] = i <= num_s ? s_edges[i] * s_edges[i] : 0.f;
-        E.m2[i] = i <= num_mu ? mu_edges[i] * mu_edges[i] : 0.f;
-    }
+    const PairJobLayout L = pair_job_layout(n_a, n_b, CGNN_SMU_MAX_G, 1, CGNN_SMU_QCHUNK);
+    rc = check_pair_workspace("cgnn_pair_counts_smu", workspace, workspace_bytes, L.total);
+    if (rc) return rc;
+    for (int i = 0; i <= CGNN_SMU_MAX_AXIS; ++i) E.m2[i] = i <= num_mu ? mu_edges[i] * mu_edges[i] : 0.f;   // as e2
     const int bins = num_s * num_mu, copies = smu_copies(bins);
     const size_t lds = (size_t)copies * bins * sizeof(unsigned);   // at most 16 KiB
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    const SortedSet A = sorted_set(ws, L.a), B = sorted_set(ws, L.b);
-    const ItemTable I = item_table(ws, L.items);
-    int rc = check_hip(hipMemsetAsync(counts, 0, (size_t)bins * 8, st), "pair_counts_smu memset counts");
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+    rc = check_hip(hipMemsetAsync(counts, 0, (size_t)bins * 8, st), "pair_counts_smu memset counts");
     if (rc) return rc;
-    rc = sorted_set_sort(pos_a, n_a, inv_h, G, cells, A, I.bsum, st, "pair_counts_smu", "cgnn_pair_counts_smu sort");
+    PairWalkArgs W;
+    unsigned blocks;
+    rc = pair_job_prepare<CGNN_SMU_QCHUNK>("cgnn_pair_counts_smu", L, pos_a, n_a, pos_b, n_b, box_size, s_edges[num_s],
+                                           CGNN_SMU_MAX_G, 1, workspace, st, W, blocks);
     if (rc) return rc;
-    if (cross) {
-        rc = sorted_set_sort(pos_b, n_b, inv_h, G, cells, B, I.bsum, st, "pair_counts_smu", "cgnn_pair_counts_smu sort");
-        if (rc) return rc;
-    }
-    item_table_build<CGNN_SMU_QCHUNK>(A, n_a, cells, I, st);
-    unsigned blocks = pair_walk_blocks(cells, n_a, CGNN_SMU_QCHUNK);
     if (bins > CGNN_SMU_HIST_COUNTERS) {   // one copy past 8 KiB: no more workgroups than are resident at once
         int device = 0, cus = 0, per_cu = 0;
         rc = check_hip(hipGetDevice(&device), "pair_counts_smu device");
@@ -258,17 +208,14 @@ int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, in
         const int64_t resident = (int64_t)cus * per_cu;
         if (resident >= 1 && resident < (int64_t)blocks) blocks = (unsigned)resident;
     }
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
-#define CGNN_SMU_LAUNCH(LOS)                                                                                          \
-    smu_walk_kernel<LOS><<<blocks, CGNN_SMU_QCHUNK, lds, st>>>(A.sorted, A.start, A.cell_of, B.sorted, B.start,      \
-                                                                I.chunk_start, I.item_q0, (int)cells, G, box_size,    \
-                                                                half, E, num_s, num_mu, copies, cross ? 0 : 1, out)
+#define CGNN_SMU_LAUNCH(LOS)                                                                                   \
+    smu_walk_kernel<LOS><<<blocks, CGNN_SMU_QCHUNK, lds, st>>>(CGNN_PAIR_WALK_ARGS(W), E, num_s, num_mu, copies, \
+                                                                cross ? 0 : 1, out)
     if (los == 0) CGNN_SMU_LAUNCH(0);
     else if (los == 1) CGNN_SMU_LAUNCH(1);
     else CGNN_SMU_LAUNCH(2);
 #undef CGNN_SMU_LAUNCH
-    if (!cross)
-        smu_halve_kernel<<<(unsigned)((bins + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(out, bins);
+    if (!cross) pair_halve(out, bins, st);
     return check_hip(hipGetLastError(), "cgnn_pair_counts_smu");
 }
 

@@ -1,14 +1,24 @@
 // All pairs of a periodic box closer than a reach, walked over the Morton cell grid of cell_grid.hpp: what the pair
-// counter (pair_counts.hip), the group finder (fof.hip) and the halo profiles (halo_profiles.hip) share.  The grid rule,
+// counters (pair_counts.hip, pair_counts_smu.hip), the group finder (fof.hip) and the halo profiles (halo_profiles.hip)
+// share.  The grid rule,
 // a particle set sorted by cell, the table of work items, the squared distance of the counting contract, and the walk
 // itself; a kernel adds only what it does with a (query, candidate, d2) triple.
 //
 // THE CONTRACT'S DISTANCE rounds every float32 operation once (pair_d2 below).  hipcc's default (-ffp-contract=fast)
 // fuses fl32(x x) + fl32(y y) into an fma even when the operands come from __fmul_rn / __fadd_rn (they are inline
 // functions whose operations carry the default's permission to contract; a pragma does not reach them), which moves a
-// pair across a bin edge once in some 10^7 pairs.  Every file that includes this header for pair_d2 or pair_walk must
-// therefore be compiled with -ffp-contract=off (the Makefile's FLAGS_<file>).
+// pair across a bin edge once in some 10^7 pairs.  Every file that includes this header must therefore be compiled with
+// -ffp-contract=off, and says that it is with -DCGNN_PAIR_CONTRACT_OFF beside the flag (the Makefile's FLAGS_<file>).
+//
+// THE JOB of an entry, written once below: check (load_radial_edges, check_pair_workspace), lay out (pair_job_layout),
+// prepare (pair_job_prepare: grid, sorts, item table -> PairWalkArgs and the block count), launch its own kernel.
 #pragma once
+#ifndef CGNN_PAIR_CONTRACT_OFF
+#error "pair_walk.hpp: pair_d2 rounds every float32 operation once, and hipcc's default -ffp-contract=fast fuses its \
+products and sums into fmas even through __fmul_rn / __fadd_rn, which moves a pair across a bin edge once in some 10^7 \
+pairs. Compile every file that includes this header with -ffp-contract=off -DCGNN_PAIR_CONTRACT_OFF (the Makefile's \
+FLAGS_<file>)."
+#endif
 #include <math.h>
 
 #include "cell_grid.hpp"
@@ -75,22 +85,23 @@ static SortedSet sorted_set(char* ws, const SortedSetLayout& S) {
 }
 
 // counting sort of pos[0..n) by Morton cell: P.start [cells + 1], P.cell_of [n], P.sorted [n].  bsum: the scan's scratch.
-// `who` names the entry in the memsets' error texts; `after` is the text for a launch that failed.
+// `who` is the entry, "cgnn_<entry>": the memsets' error texts name it without the prefix, a failed launch's with it.
 static int sorted_set_sort(const float* pos, int64_t n, float inv_h, int G, int64_t cells, const SortedSet& P,
-                           int32_t* bsum, hipStream_t st, const char* who, const char* after) {
+                           int32_t* bsum, hipStream_t st, const char* who) {
     const int64_t m = cells + 1;   // count[cells] = 0 so that start[cells] = n
     char what[96];
-    snprintf(what, sizeof what, "%s memset count", who);
+    snprintf(what, sizeof what, "%s memset count", who + 5);
     int rc = check_hip(hipMemsetAsync(P.count, 0, (size_t)m * 4, st), what);
     if (rc) return rc;
-    snprintf(what, sizeof what, "%s memset cursor", who);
+    snprintf(what, sizeof what, "%s memset cursor", who + 5);
     rc = check_hip(hipMemsetAsync(P.cursor, 0, (size_t)m * 4, st), what);
     if (rc) return rc;
     const unsigned nb = (unsigned)((n + CGNN_BLOCK - 1) / CGNN_BLOCK);
     knn_count_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, inv_h, G, P.cell_of, P.count);
     exclusive_scan_i32(P.count, m, bsum, P.start, st);
     knn_fill_kernel<<<nb, CGNN_BLOCK, 0, st>>>(pos, n, P.cell_of, P.start, P.cursor, P.sorted);
-    return check_hip(hipGetLastError(), after);
+    snprintf(what, sizeof what, "%s sort", who);
+    return check_hip(hipGetLastError(), what);
 }
 
 // ---- work items ------------------------------------------------------------------------------------------------------
@@ -165,6 +176,107 @@ static void item_table_build(const SortedSet& A, int64_t n, int64_t cells, const
 static unsigned pair_walk_blocks(int64_t cells, int64_t n, int qchunk) {
     const int64_t max_items = pair_max_items(cells, n, qchunk);
     return (unsigned)(max_items < CGNN_PAIR_MAX_BLOCKS ? max_items : CGNN_PAIR_MAX_BLOCKS);
+}
+
+// ---- the job ---------------------------------------------------------------------------------------------------------
+// What a walk kernel needs: the query set A and the partner set B sorted into one grid (B may be A), A's item table,
+// the grid and the box.  A host struct; a kernel takes the fields one by one (CGNN_PAIR_WALK_ARGS, in the order of
+// pair_walk's parameters) as __restrict__ pointers.  By value as one kernel argument it was measured to cost time: the
+// compiler then no longer knows the pointers apart from the kernel's outputs, and the per-item loads (item_q0, cell_of,
+// start) of fof_walk_kernel turn from scalar into vector loads, 8 % on a frame whose items hold one or two queries.
+struct PairWalkArgs {
+    const float4* sorted_a;
+    const int32_t *start_a, *cell_of_a;
+    const float4* sorted_b;
+    const int32_t *start_b, *chunk_start, *item_q0;
+    int cells, G;
+    float box, half;
+};
+#define CGNN_PAIR_WALK_ARGS(W)                                                                                      \
+    (W).sorted_a, (W).start_a, (W).cell_of_a, (W).sorted_b, (W).start_b, (W).chunk_start, (W).item_q0, (W).cells, \
+        (W).G, (W).box, (W).half
+
+// The workspace of a job: A's set, then B's if there is one (n_b == 0: B is A), then A's item table.  A function of the
+// counts alone: the tables are sized for the finest grid the partner count allows.
+struct PairJobLayout {
+    int64_t cells_max;
+    SortedSetLayout a, b;
+    ItemTableLayout items;
+    size_t total;
+};
+
+static PairJobLayout pair_job_layout(int64_t n_a, int64_t n_b, int max_g, int64_t cells_per_particle, int qchunk) {
+    PairJobLayout L;
+    L.cells_max = pair_cell_slots(pair_cells_per_axis(n_b > 0 ? n_b : n_a, 1.f, -1.f, max_g, cells_per_particle));
+    size_t off = sorted_set_layout(L.a, 0, L.cells_max, n_a);
+    if (n_b > 0) off = sorted_set_layout(L.b, off, L.cells_max, n_b);
+    else L.b = L.a;
+    L.total = item_table_layout(L.items, off, L.cells_max, n_a, qchunk);
+    return L;
+}
+
+// Everything between an entry's checks and its walk kernel, on the stream: the grid for `reach` (never finer than the
+// one L is sized for), the sort of A, of B if there is one, A's items of up to QCHUNK queries.  Fills W and the walk's
+// workgroup count; returns the first failure.
+template <int QCHUNK>
+static int pair_job_prepare(const char* who, const PairJobLayout& L, const float* pos_a, int64_t n_a, const float* pos_b,
+                            int64_t n_b, float box, float reach, int max_g, int64_t cells_per_particle, void* workspace,
+                            hipStream_t st, PairWalkArgs& W, unsigned& blocks) {
+    const int G = pair_cells_per_axis(n_b > 0 ? n_b : n_a, box, reach, max_g, cells_per_particle);
+    const int64_t cells = pair_cell_slots(G);
+    const float inv_h = (float)G / box;
+    char* ws = reinterpret_cast<char*>(workspace);
+    const SortedSet A = sorted_set(ws, L.a), B = sorted_set(ws, L.b);
+    const ItemTable I = item_table(ws, L.items);
+    int rc = sorted_set_sort(pos_a, n_a, inv_h, G, cells, A, I.bsum, st, who);
+    if (!rc && n_b > 0) rc = sorted_set_sort(pos_b, n_b, inv_h, G, cells, B, I.bsum, st, who);
+    if (rc) return rc;
+    item_table_build<QCHUNK>(A, n_a, cells, I, st);
+    W = {A.sorted, A.start, A.cell_of, B.sorted, B.start, I.chunk_start, I.item_q0, (int)cells, G, box, 0.5f * box};
+    blocks = pair_walk_blocks(cells, n_a, QCHUNK);
+    return CGNN_OK;
+}
+
+// edges[0 .. num_bins] validated (finite, non-negative, strictly ascending, the last within half the box) and squared
+// into e2[0 .. capacity): e2[i] = fl32(edges[i] edges[i]), zero beyond num_bins.  `name` and `count_name` are the
+// entry's names of the array and of its bin count; the caller has checked num_bins < capacity.
+static int load_radial_edges(const char* who, const char* name, const char* count_name, const float* edges, int num_bins,
+                             float half, float* e2, int capacity) {
+    for (int i = 0; i <= num_bins; ++i) {
+        if (!isfinite(edges[i]) || edges[i] < 0.f || (i > 0 && !(edges[i] > edges[i - 1]))) {
+            set_error("%s: %s must be finite, non-negative and strictly ascending (%s[%d])", who, name, name, i);
+            return CGNN_ERR_INVALID_ARG;
+        }
+    }
+    if (edges[num_bins] > half) {
+        set_error("%s: %s[%s]=%g exceeds half the box, %g", who, name, count_name, (double)edges[num_bins], (double)half);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < capacity; ++i) e2[i] = i <= num_bins ? edges[i] * edges[i] : 0.f;   // fl32 product, rounded once
+    return CGNN_OK;
+}
+
+// float4 loads from the sorted arrays: the workspace must be 16-byte aligned, and hold `need` bytes
+static int check_pair_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+        set_error("%s: workspace must be 16-byte aligned", who);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+        return CGNN_ERR_WORKSPACE;
+    }
+    return CGNN_OK;
+}
+
+// auto mode of the pair counters: ordered pairs i != j -> unordered pairs (every total is even: the contract is symmetric)
+static __global__ void pair_halve_kernel(unsigned long long* __restrict__ counts, int bins) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < bins) counts[b] >>= 1;
+}
+
+static void pair_halve(unsigned long long* counts, int bins, hipStream_t st) {
+    pair_halve_kernel<<<(unsigned)((bins + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(counts, bins);
 }
 
 // ---- the contract and the walk ---------------------------------------------------------------------------------------

@@ -814,6 +814,35 @@ def check_pair_count_edges(edges, box_size: float, who: str) -> List[float]:
     return e.tolist()
 
 
+def _check_in_box(what: str, box_size: float, **positions) -> None:
+    """``ValueError`` naming the first of the given position tensors (``None``: skipped) that leaves ``[0, box_size]``:
+    the ``check_bounds=True`` of the pair-walk ops, one host synchronisation per tensor."""
+    for name, p in positions.items():
+        if p is not None and not bool(((p >= 0) & (p <= float(box_size))).all()):
+            raise ValueError(f"{what}: {name} leaves [0, box_size]")
+
+
+def _pair_frames(what: str, pos_a, pos_b, box_size: float, check_bounds: bool):
+    """The two sets of :func:`pair_counts` and :func:`pair_counts_smu` checked (shapes, one device, bounds on request) and
+    viewed as frames: ``(pos_a [T, N, 3], pos_b [T, M, 3] or None, batched)``."""
+    pos_a = f32c(pos_a, "pos_a")
+    batched = pos_a.dim() == 3
+    if pos_a.dim() not in (2, 3) or pos_a.shape[-1] != 3 or pos_a.shape[-2] < 1:
+        raise CgnnError(f"{what}: pos_a must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos_a.shape)}")
+    if pos_b is not None:
+        pos_b = f32c(pos_b, "pos_b")
+        if pos_b.dim() != pos_a.dim() or pos_b.shape[-1] != 3 or pos_b.shape[-2] < 1 or \
+                (batched and pos_b.shape[0] != pos_a.shape[0]):
+            raise CgnnError(f"{what}: pos_b must be [M, 3] (or [T, M, 3] with pos_a's T) with M >= 1, got "
+                            f"{tuple(pos_b.shape)} for pos_a {tuple(pos_a.shape)}")
+        _same_device(pos_a, pos_b)
+    if check_bounds:
+        _check_in_box(what, box_size, pos_a=pos_a, pos_b=pos_b)
+    if batched:
+        return pos_a, pos_b, True
+    return pos_a.unsqueeze(0), None if pos_b is None else pos_b.unsqueeze(0), False
+
+
 def pair_counts(pos_a: torch.Tensor, box_size: float, edges, pos_b: Optional[torch.Tensor] = None, *,
                 check_bounds: bool = False) -> torch.Tensor:
     """Exact pair counts by separation in a periodic box (``cgnn_pair_counts``): ``int64 [nb]`` for ``pos_a [N, 3]``,
@@ -832,32 +861,16 @@ def pair_counts(pos_a: torch.Tensor, box_size: float, edges, pos_b: Optional[tor
     what = "pair_counts"
     e = check_pair_count_edges(edges, box_size, what)
     nb = len(e) - 1
-    pos_a = f32c(pos_a, "pos_a")
-    batched = pos_a.dim() == 3
-    if pos_a.dim() not in (2, 3) or pos_a.shape[-1] != 3 or pos_a.shape[-2] < 1:
-        raise CgnnError(f"{what}: pos_a must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos_a.shape)}")
-    if pos_b is not None:
-        pos_b = f32c(pos_b, "pos_b")
-        if pos_b.dim() != pos_a.dim() or pos_b.shape[-1] != 3 or pos_b.shape[-2] < 1 or \
-                (batched and pos_b.shape[0] != pos_a.shape[0]):
-            raise CgnnError(f"{what}: pos_b must be [M, 3] (or [T, M, 3] with pos_a's T) with M >= 1, got "
-                            f"{tuple(pos_b.shape)} for pos_a {tuple(pos_a.shape)}")
-        _same_device(pos_a, pos_b)
-    if check_bounds:
-        for name, p in (("pos_a", pos_a), ("pos_b", pos_b)):
-            if p is not None and not bool(((p >= 0) & (p <= float(box_size))).all()):
-                raise ValueError(f"{what}: {name} leaves [0, box_size]")
-    frames_a = pos_a if batched else pos_a.unsqueeze(0)
-    frames_b = None if pos_b is None else (pos_b if batched else pos_b.unsqueeze(0))
+    frames_a, frames_b, batched = _pair_frames(what, pos_a, pos_b, box_size, check_bounds)
     t, n_a = frames_a.shape[0], frames_a.shape[1]
     n_b = 0 if frames_b is None else frames_b.shape[1]
     lib = _lib.load()
     edges_c = (C.c_float * (nb + 1))(*e)
     ws_bytes = lib.cgnn_pair_counts_workspace_bytes(n_a, n_b, nb)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos_a.device)
-    counts = torch.empty((t, nb), dtype=torch.int64, device=pos_a.device)
-    st = stream_ptr(pos_a.device)
-    with _timed(what, pos_a.device):
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=frames_a.device)
+    counts = torch.empty((t, nb), dtype=torch.int64, device=frames_a.device)
+    st = stream_ptr(frames_a.device)
+    with _timed(what, frames_a.device):
         for f in range(t):
             check(lib.cgnn_pair_counts(frames_a[f].data_ptr(), n_a, None if frames_b is None else frames_b[f].data_ptr(),
                                        n_b, float(box_size), edges_c, nb, counts[f].data_ptr(), ws.data_ptr(), ws_bytes,
@@ -905,32 +918,16 @@ def pair_counts_smu(pos_a: torch.Tensor, box_size: float, s_edges, mu_edges, pos
     if ns * nmu > _lib.PAIR_COUNTS_SMU_MAX_BINS:
         raise ValueError(f"{what}: {ns} x {nmu} bins exceed {_lib.PAIR_COUNTS_SMU_MAX_BINS}")
     los = check_los(los, what)
-    pos_a = f32c(pos_a, "pos_a")
-    batched = pos_a.dim() == 3
-    if pos_a.dim() not in (2, 3) or pos_a.shape[-1] != 3 or pos_a.shape[-2] < 1:
-        raise CgnnError(f"{what}: pos_a must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos_a.shape)}")
-    if pos_b is not None:
-        pos_b = f32c(pos_b, "pos_b")
-        if pos_b.dim() != pos_a.dim() or pos_b.shape[-1] != 3 or pos_b.shape[-2] < 1 or \
-                (batched and pos_b.shape[0] != pos_a.shape[0]):
-            raise CgnnError(f"{what}: pos_b must be [M, 3] (or [T, M, 3] with pos_a's T) with M >= 1, got "
-                            f"{tuple(pos_b.shape)} for pos_a {tuple(pos_a.shape)}")
-        _same_device(pos_a, pos_b)
-    if check_bounds:
-        for name, p in (("pos_a", pos_a), ("pos_b", pos_b)):
-            if p is not None and not bool(((p >= 0) & (p <= float(box_size))).all()):
-                raise ValueError(f"{what}: {name} leaves [0, box_size]")
-    frames_a = pos_a if batched else pos_a.unsqueeze(0)
-    frames_b = None if pos_b is None else (pos_b if batched else pos_b.unsqueeze(0))
+    frames_a, frames_b, batched = _pair_frames(what, pos_a, pos_b, box_size, check_bounds)
     t, n_a = frames_a.shape[0], frames_a.shape[1]
     n_b = 0 if frames_b is None else frames_b.shape[1]
     lib = _lib.load()
     s_c, mu_c = (C.c_float * (ns + 1))(*e), (C.c_float * (nmu + 1))(*m)
     ws_bytes = lib.cgnn_pair_counts_smu_workspace_bytes(n_a, n_b, ns, nmu)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos_a.device)
-    counts = torch.empty((t, ns, nmu), dtype=torch.int64, device=pos_a.device)
-    st = stream_ptr(pos_a.device)
-    with _timed(what, pos_a.device):
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=frames_a.device)
+    counts = torch.empty((t, ns, nmu), dtype=torch.int64, device=frames_a.device)
+    st = stream_ptr(frames_a.device)
+    with _timed(what, frames_a.device):
         for f in range(t):
             check(lib.cgnn_pair_counts_smu(frames_a[f].data_ptr(), n_a,
                                            None if frames_b is None else frames_b[f].data_ptr(), n_b, float(box_size),
@@ -1537,8 +1534,8 @@ def fof_labels(pos: torch.Tensor, box_size: float, linking_length: float, *, che
     pos = f32c(pos, "pos")
     if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1 or pos.shape[0] < 1:
         raise CgnnError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
-    if check_bounds and not bool(((pos >= 0) & (pos <= float(box_size))).all()):
-        raise ValueError(f"{what}: pos leaves [0, box_size]")
+    if check_bounds:
+        _check_in_box(what, box_size, pos=pos)
     batched = pos.dim() == 3
     frames = pos if batched else pos.unsqueeze(0)
     t, n = frames.shape[0], frames.shape[1]
@@ -1806,9 +1803,7 @@ def halo_profiles(pos: torch.Tensor, centres: torch.Tensor, box_size: float, edg
     centres = f32c(centres, "centres")
     _same_device(pos, centres, q)
     if check_bounds:
-        for name, p in (("pos", pos), ("centres", centres)):
-            if not bool(((p >= 0) & (p <= float(box_size))).all()):
-                raise ValueError(f"{what}: {name} leaves [0, box_size]")
+        _check_in_box(what, box_size, pos=pos, centres=centres)
     frames, cen = (pos, centres) if batched else (pos.unsqueeze(0), centres.unsqueeze(0))
     if q is not None and not batched:
         q = q.unsqueeze(0)

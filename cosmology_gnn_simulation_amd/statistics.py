@@ -63,6 +63,11 @@ def _radii(edges, box_size: float, who: str) -> torch.Tensor:
     return torch.tensor(ops.check_pair_count_edges(edges, box_size, who), dtype=torch.float64)
 
 
+def _shell_volumes(r: torch.Tensor) -> torch.Tensor:
+    """The volumes of the shells between consecutive radii ``r`` (float64)."""
+    return 4.0 * math.pi / 3.0 * (r[1:] ** 3 - r[:-1] ** 3)
+
+
 def correlation_from_counts(counts, n_a: int, n_b: Optional[int], box_size: float, edges, auto: bool) -> torch.Tensor:
     """The natural estimator ``xi = DD / RR - 1`` with the analytic random term of a periodic box, on the host in
     float64 from the ``nb`` integers (``counts [nb]`` or ``[T, nb]``; returns the same shape, float64, on the CPU):
@@ -76,7 +81,7 @@ def correlation_from_counts(counts, n_a: int, n_b: Optional[int], box_size: floa
     c = torch.as_tensor(counts).detach().to(device="cpu", dtype=torch.float64)
     if c.shape[-1] != r.numel() - 1:
         raise ValueError(f"correlation_from_counts: {c.shape[-1]} counts for {r.numel() - 1} bins")
-    shell = 4.0 * math.pi / 3.0 * (r[1:] ** 3 - r[:-1] ** 3) / float(box_size) ** 3
+    shell = _shell_volumes(r) / float(box_size) ** 3
     pairs = n_a * (n_a - 1) / 2.0 if auto else float(n_a) * float(n_b)
     return c / (pairs * shell) - 1.0
 
@@ -577,7 +582,7 @@ def correlation_multipoles_from_counts(counts, n_a: int, n_b: Optional[int], box
     counts = torch.as_tensor(counts).detach().to(device="cpu")
     if counts.dim() < 2 or tuple(counts.shape[-2:]) != (ns, nmu):
         raise ValueError(f"{what}: counts {tuple(counts.shape)} for {ns} x {nmu} bins")
-    shell = 4.0 * math.pi / 3.0 * (s[1:] ** 3 - s[:-1] ** 3) / float(box_size) ** 3
+    shell = _shell_volumes(s) / float(box_size) ** 3
     pairs = n_a * (n_a - 1) / 2.0 if auto else float(n_a) * float(n_b)
     rr = pairs * shell[:, None] * (mu[1:] - mu[:-1])[None, :]
     xi = counts.to(torch.float64) / rr - 1.0
@@ -1376,10 +1381,6 @@ def so_masses(counts: torch.Tensor, n: int, box_size: float, edges, delta: float
     r_delta = torch.exp(l0 + (math.log(float(delta)) - torch.log(d0)) / (torch.log(d1) - torch.log(d0)) * (l1 - l0))
     r_delta = torch.where(found, r_delta, torch.full_like(r_delta, float("nan")))
     return r_delta, float(delta) * rho * (4.0 / 3.0 * math.pi) * r_delta ** 3
-
-
-def _shell_volumes(r: torch.Tensor) -> torch.Tensor:
-    return 4.0 * math.pi / 3.0 * (r[1:] ** 3 - r[:-1] ** 3)
 
 
 def halo_profiles(pos: torch.Tensor, box_size: float, edges=None, linking_length: Optional[float] = None,

@@ -5,6 +5,9 @@ alone.  Not part of the product or tests.
     hipcc ... -o after.s                                                                                   (new source)
     python scripts/dev/diff_kernel_isa.py before.s after.s
 
+A file with a ``FLAGS_<file>`` line in csrc/Makefile needs those flags on the hipcc line too: the files that include
+pair_walk.hpp do not compile without ``-ffp-contract=off -DCGNN_PAIR_CONTRACT_OFF``.
+
 Compared per function: instructions, labels and directives between the function's label and its end marker.  Dropped
 or normalised, because they change when functions are added to a file or a defaulted template argument appears:
 comments, the per-function number in ``.LBB<n>_<m>`` labels, and a trailing ``, 0`` integer template argument in the

@@ -225,6 +225,14 @@ def test_workspace_size_and_the_host_refusals_of_the_c_entries():
     assert labels(wb=lib.cgnn_fof_labels_workspace_bytes(100) - 1) == short
     assert b"workspace" in lib.cgnn_last_error()
     assert labels(ll=half, wb=16) == short              # exactly half the box passes the length check
+    # the checks this entry shares with the other pair walks, word for word (it has no edges)
+    need = lib.cgnn_fof_labels_workspace_bytes(100)
+    assert labels(w=odd) == inv and lib.cgnn_last_error() == b"cgnn_fof_labels: workspace must be 16-byte aligned"
+    assert labels(wb=need - 1) == short
+    assert lib.cgnn_last_error().decode() == f"cgnn_fof_labels: workspace {need - 1} < required {need} bytes"
+    # the parent's sizes, to the byte
+    for n, size in ((1, 2304), (100, 5376), (4096, 182016), (1000000, 65964544)):
+        assert lib.cgnn_fof_labels_workspace_bytes(n) == size, n
 
     edges = (C.c_int32 * 3)(1, 2, 4)
 

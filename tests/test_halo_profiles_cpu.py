@@ -302,3 +302,13 @@ def test_workspace_size_and_the_host_refusals_of_the_c_entry():
     assert call(edges=arr(0.0, 0.1, half), wb=wsb(100, 7) - 1) == short
     assert call(q=fake, sums=fake, c=4, wb=0) == short
     assert "workspace" in lib.cgnn_last_error().decode()
+    # the checks this entry shares with the other pair walks, word for word
+    for kw, code, text in (
+            (dict(edges=arr(0.0, 0.2, 0.2)), inv, "edges must be finite, non-negative and strictly ascending (edges[2])"),
+            (dict(edges=arr(0.0, 0.1, 0.6)), inv, "edges[num_bins]=0.6 exceeds half the box, 0.5"),
+            (dict(w=odd), inv, "workspace must be 16-byte aligned"),
+            (dict(wb=wsb(100, 7) - 1), short, f"workspace {wsb(100, 7) - 1} < required {wsb(100, 7)} bytes")):
+        assert call(**kw) == code and lib.cgnn_last_error().decode() == "cgnn_halo_profiles: " + text, kw
+    # the parent's sizes, to the byte
+    for n, h, size in ((1, 1, 3584), (4096, 10, 216064), (1000000, 600, 87130368)):
+        assert wsb(n, h) == size, (n, h)

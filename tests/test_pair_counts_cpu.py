@@ -1,5 +1,6 @@
 """CPU: the counting contract of ``cgnn_pair_counts`` as tests/pair_count_checks.py restates it, the estimator of
 ``statistics.correlation_from_counts``, the host refusals of ``ops.pair_counts`` and the bookkeeping of the new C entries."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -127,3 +128,22 @@ def test_workspace_sizes_are_functions_of_the_counts_alone():
     assert lib.cgnn_pair_counts_workspace_bytes(0, 0, 16) == 256
     assert lib.cgnn_frame_errors_workspace_bytes(3, 1000) == 3 * 64 * 2 * 8
     assert lib.cgnn_frame_errors_workspace_bytes(0, 1000) == 256
+    # the parent's sizes, to the byte
+    wsb = lib.cgnn_pair_counts_workspace_bytes
+    for n_a, n_b, size in ((1, 0, 2304), (100, 0, 5376), (4096, 0, 182016), (4096, 500, 113152), (500, 4096, 227584),
+                           (1000000, 0, 65964544)):
+        assert wsb(n_a, n_b, 8) == size, (n_a, n_b)
+    # the checks this entry shares with the other pair walks, word for word: refused on the host, before any pointer
+    # is dereferenced
+    fake, odd = 1 << 20, (1 << 20) + 4
+    inv, short = -1, -3                                 # CGNN_ERR_INVALID_ARG, _WORKSPACE
+
+    def call(edges=(0.0, 0.1, 0.2), w=fake, wb=1 << 30):
+        return lib.cgnn_pair_counts(fake, 100, None, 0, 1.0, (C.c_float * 3)(*edges), 2, fake, w, wb, None)
+
+    for kw, code, text in (
+            (dict(edges=(0.0, 0.2, 0.2)), inv, "edges must be finite, non-negative and strictly ascending (edges[2])"),
+            (dict(edges=(0.0, 0.1, 0.6)), inv, "edges[num_bins]=0.6 exceeds half the box, 0.5"),
+            (dict(w=odd), inv, "workspace must be 16-byte aligned"),
+            (dict(wb=wsb(100, 0, 2) - 1), short, f"workspace {wsb(100, 0, 2) - 1} < required {wsb(100, 0, 2)} bytes")):
+        assert call(**kw) == code and lib.cgnn_last_error().decode() == "cgnn_pair_counts: " + text, kw

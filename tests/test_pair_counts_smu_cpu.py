@@ -255,3 +255,15 @@ def test_workspace_size_and_the_host_refusals_of_the_c_entry():
     assert call(s=lin(0.5, 64), ns=64, mu=lin(1.0, 64), nmu=64, wb=0) == short
     assert call(s=lin(0.5, 128), ns=128, mu=arr(0.0, 1.0), nmu=1, b=fake, n_b=50, wb=wsb(100, 50, 128, 1) - 1) == short
     assert "workspace" in lib.cgnn_last_error().decode()
+    # the checks this entry shares with the other pair walks, word for word
+    for kw, code, text in (
+            (dict(s=arr(0.0, 0.2, 0.2)), inv,
+             "s_edges must be finite, non-negative and strictly ascending (s_edges[2])"),
+            (dict(s=arr(0.0, 0.1, 0.6)), inv, "s_edges[num_s]=0.6 exceeds half the box, 0.5"),
+            (dict(w=odd), inv, "workspace must be 16-byte aligned"),
+            (dict(wb=wsb(100, 0, 2, 2) - 1), short, f"workspace {wsb(100, 0, 2, 2) - 1} < required {wsb(100, 0, 2, 2)} bytes")):
+        assert call(**kw) == code and lib.cgnn_last_error().decode() == "cgnn_pair_counts_smu: " + text, kw
+    # the parent's sizes, to the byte
+    for n_a, n_b, size in ((1, 0, 2304), (100, 0, 5376), (4096, 0, 182016), (4096, 500, 113152), (500, 4096, 227584),
+                           (1000000, 0, 65964544)):
+        assert wsb(n_a, n_b, 8, 5) == size, (n_a, n_b)
