@@ -56,10 +56,12 @@ EXPORTS = (
     "cgnn_halo_profiles_workspace_bytes", "cgnn_halo_profiles",
     "cgnn_redshift_positions", "cgnn_power_multipoles_workspace_bytes", "cgnn_power_multipoles",
     "cgnn_pair_counts_smu_workspace_bytes", "cgnn_pair_counts_smu",
+    "cgnn_pair_velocity_sums_workspace_bytes", "cgnn_pair_velocity_sums",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
 PAIR_COUNTS_SMU_MAX_AXIS = 128    # CGNN_SMU_MAX_AXIS: bins per axis at most
+PAIR_VELOCITY_MAX_BINS = 64       # CGNN_PV_MAX_BINS in csrc/pair_velocities.hip
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
@@ -169,6 +171,10 @@ def load() -> C.CDLL:
     lib.cgnn_pair_counts_smu_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.cgnn_pair_counts_smu.argtypes = [vp, i64, vp, i64, f32, C.POINTER(f32), i32, C.POINTER(f32), i32, i32, vp, vp, sz,
                                          vp]                                                # both edge sets: host memory
+    lib.cgnn_pair_velocity_sums_workspace_bytes.restype = sz
+    lib.cgnn_pair_velocity_sums_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cgnn_pair_velocity_sums.argtypes = [vp, vp, i64, vp, vp, i64, f32, C.POINTER(f32), i32, vp, vp, vp, sz,
+                                            vp]                                             # edges: host memory
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]

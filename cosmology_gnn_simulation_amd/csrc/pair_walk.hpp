@@ -1,6 +1,6 @@
 // All pairs of a periodic box closer than a reach, walked over the Morton cell grid of cell_grid.hpp: what the pair
-// counters (pair_counts.hip, pair_counts_smu.hip), the group finder (fof.hip) and the halo profiles (halo_profiles.hip)
-// share.  The grid rule,
+// counters (pair_counts.hip, pair_counts_smu.hip), the group finder (fof.hip), the halo profiles (halo_profiles.hip) and
+// the pairwise velocities (pair_velocities.hip) share.  The grid rule,
 // a particle set sorted by cell, the table of work items, the squared distance of the counting contract, and the walk
 // itself; a kernel adds only what it does with a (query, candidate, d2) triple.
 //
@@ -301,20 +301,30 @@ __device__ __forceinline__ float pair_d2(const float4& a, const float4& b, float
 //   before_tile(nq)                 uniform over the workgroup, ahead of each tile of an item with nq queries; may
 //                                   contain barriers
 //   visit(a, b, d2, qi, p, q0)      query a (the qi-th of the item, sorted slot q0 + qi of A) and candidate b (sorted
-//                                   slot p of B)
+//                                   slot p of B); a lane meets its candidate of a tile with qi = 0 first, then 1, ...
 //   after_item(q0, nq)              uniform over the workgroup, behind the last tile of an item (also of one without
 //                                   candidates); may contain barriers
+//   item_start(q0, nq)              optional (default: nothing), uniform over the workgroup, beside the staging of the
+//                                   item's queries: behind the barrier that ends the previous item's readers and ahead
+//                                   of the one that publishes q_s, so what it stages per query in LDS of its own is
+//                                   published with them (the pairwise velocities: the queries' velocities); no barriers
 // The callables get scalars and float4 values only: what they reach beyond that, they capture themselves.
 // pair_walk<QCHUNK> is the walk of the pair counter and the group finder: as many queries per item as threads, nothing
 // kept per item.  pair_walk_tiled<QCHUNK, TILE> lets a kernel with state per query (the halo profiles: a histogram
 // each) take few queries per item with a full workgroup of candidates per tile.
-template <int QCHUNK, int TILE, typename BeforeTile, typename Visit, typename AfterItem>
+struct PairWalkNoItemStart {
+    __device__ __forceinline__ void operator()(int, int) const {}
+};
+
+template <int QCHUNK, int TILE, typename BeforeTile, typename Visit, typename AfterItem,
+          typename ItemStart = PairWalkNoItemStart>
 __device__ __forceinline__ void pair_walk_tiled(const float4* __restrict__ sorted_a, const int32_t* __restrict__ start_a,
                                                 const int32_t* __restrict__ cell_of_a,
                                                 const float4* __restrict__ sorted_b, const int32_t* __restrict__ start_b,
                                                 const int32_t* __restrict__ chunk_start,
                                                 const int32_t* __restrict__ item_q0, int cells, int G, float box,
-                                                float half, BeforeTile before_tile, Visit visit, AfterItem after_item) {
+                                                float half, BeforeTile before_tile, Visit visit, AfterItem after_item,
+                                                ItemStart item_start = ItemStart()) {
     static_assert(QCHUNK <= TILE && TILE >= CGNN_PAIR_RANGES, "the first threads stage the queries and the ranges");
     __shared__ float4 q_s[QCHUNK];
     __shared__ int rng_p0[CGNN_PAIR_RANGES], rng_len[CGNN_PAIR_RANGES], rng_off[CGNN_PAIR_RANGES + 1];
@@ -327,6 +337,7 @@ __device__ __forceinline__ void pair_walk_tiled(const float4* __restrict__ sorte
         const int cx = compact3((unsigned)c >> 2), cy = compact3((unsigned)c >> 1), cz = compact3((unsigned)c);
         __syncthreads();               // the previous item's readers of q_s and rng_* are done
         if (tid < nq) q_s[tid] = sorted_a[q0 + tid];
+        item_start(q0, nq);
         cell_grid_stage_ranges<CGNN_PAIR_RANGES>(tid, cx, cy, cz, G, start_b, rng_p0, rng_len, rng_off);
         const int nc = rng_off[CGNN_PAIR_RANGES];
         for (int t0 = 0; t0 < nc; t0 += TILE) {

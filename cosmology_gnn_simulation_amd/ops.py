@@ -936,6 +936,75 @@ def pair_counts_smu(pos_a: torch.Tensor, box_size: float, s_edges, mu_edges, pos
     return counts if batched else counts[0]
 
 
+def _pair_velocity_q(what: str, name: str, q, pos) -> torch.Tensor:
+    """The quantised velocities ``q`` of the set ``pos`` checked before any device work: an int32 tensor in the shape of
+    the set's positions, on their device (``ValueError``) -> contiguous ``[T, N, 3]``."""
+    if not torch.is_tensor(q) or q.dtype != torch.int32:
+        raise ValueError(f"{what}: {name} must be an int32 tensor (ops.quantize_weights), got "
+                         f"{q.dtype if torch.is_tensor(q) else type(q).__name__}")
+    if not torch.is_tensor(pos) or tuple(q.shape) != tuple(pos.shape):
+        raise ValueError(f"{what}: {name} {tuple(q.shape)} does not go with its positions "
+                         f"{tuple(pos.shape) if torch.is_tensor(pos) else type(pos).__name__}")
+    if q.device != pos.device:
+        raise ValueError(f"{what}: {name} is on {q.device}, its positions on {pos.device}")
+    return (q if q.dim() == 3 else q.unsqueeze(0)).contiguous()
+
+
+def pair_velocity_sums(pos_a: torch.Tensor, q_a: torch.Tensor, box_size: float, edges,
+                       pos_b: Optional[torch.Tensor] = None, q_b: Optional[torch.Tensor] = None, *,
+                       check_bounds: bool = False):
+    """The pairs of :func:`pair_counts` with the integer moments of their relative velocity
+    (``cgnn_pair_velocity_sums``): ``(counts int64 [nb], sums int64 [nb, 3, 2])`` for ``pos_a [N, 3]``, with a leading
+    ``T`` for ``pos_a [T, N, 3]`` (one call per frame on the same stream, no host synchronisation between them).
+    ``q_a`` (and ``q_b`` exactly when ``pos_b`` is given) are int32 velocities in the shape of their positions,
+    quantised by :func:`quantize_weights`: ``|q| <= 2^20``, one value scale = 2^20.  ``edges``: as in
+    :func:`pair_counts`, at most 64 bins (``_lib.PAIR_VELOCITY_MAX_BINS``).
+
+    A counted pair (the pair counter's rule and bin) with ``dq = q_b - q_a`` and the folded separation ``d`` adds
+    ``iu = rint(fl32(w / fl32(sqrt(d2))))``, ``w = fl32(fl32(fl32(dq_x dx) + fl32(dq_y dy)) + fl32(dq_z dz))`` (0 for
+    coincident particles), to ``S1``, ``iu^2`` to ``R2`` and ``|dq|^2`` to ``T2`` (``include/cgnn.h``); ``iu < 0`` is
+    approach.  ``sums[b, m]`` is moment ``m`` of (S1, R2, T2) as the words ``(lo, hi)``: the exact total is ``hi * 2^32 +
+    lo``, ``0 <= lo < 2^32`` (a large clustered frame passes int64).  ``counts`` equals :func:`pair_counts` bit for
+    bit; everything is an exact integer and the same bits on every run.  :func:`statistics.pairwise_velocity_moments`
+    turns the sums into ``v12``, ``sigma_par`` and ``sigma_perp``.
+
+    The C entry cannot check ``|q| <= 2^20`` and a larger value silently breaks the exactness bounds:
+    ``check_bounds=True`` verifies it, and that the positions lie in ``[0, box_size]``, with one host synchronisation
+    per tensor; the default verifies nothing.  Scope as :func:`pair_counts`: one box per call."""
+    what = "pair_velocity_sums"
+    e = check_pair_count_edges(edges, box_size, what)
+    nb = len(e) - 1
+    if nb > _lib.PAIR_VELOCITY_MAX_BINS:
+        raise ValueError(f"{what}: edges must hold nb + 1 radii with 1 <= nb <= {_lib.PAIR_VELOCITY_MAX_BINS}, got "
+                         f"{len(e)} values")
+    if (q_b is None) != (pos_b is None):
+        raise ValueError(f"{what}: q_b is given exactly when pos_b is")
+    qa = _pair_velocity_q(what, "q_a", q_a, pos_a)
+    qb = None if pos_b is None else _pair_velocity_q(what, "q_b", q_b, pos_b)
+    frames_a, frames_b, batched = _pair_frames(what, pos_a, pos_b, box_size, check_bounds)
+    if check_bounds:
+        for name, q in (("q_a", qa), ("q_b", qb)):
+            if q is not None and not bool((q.abs() <= (1 << _lib.WEIGHT_BITS)).all()):
+                raise ValueError(f"{what}: {name} leaves [-2^{_lib.WEIGHT_BITS}, 2^{_lib.WEIGHT_BITS}]")
+    t, n_a = frames_a.shape[0], frames_a.shape[1]
+    n_b = 0 if frames_b is None else frames_b.shape[1]
+    lib = _lib.load()
+    edges_c = (C.c_float * (nb + 1))(*e)
+    ws_bytes = lib.cgnn_pair_velocity_sums_workspace_bytes(n_a, n_b, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=frames_a.device)
+    counts = torch.empty((t, nb), dtype=torch.int64, device=frames_a.device)
+    sums = torch.empty((t, nb, 3, 2), dtype=torch.int64, device=frames_a.device)
+    st = stream_ptr(frames_a.device)
+    with _timed(what, frames_a.device):
+        for f in range(t):
+            check(lib.cgnn_pair_velocity_sums(frames_a[f].data_ptr(), qa[f].data_ptr(), n_a,
+                                              None if frames_b is None else frames_b[f].data_ptr(),
+                                              None if qb is None else qb[f].data_ptr(), n_b, float(box_size), edges_c,
+                                              nb, counts[f].data_ptr(), sums[f].data_ptr(), ws.data_ptr(), ws_bytes, st),
+                  "cgnn_pair_velocity_sums")
+    return (counts, sums) if batched else (counts[0], sums[0])
+
+
 def frame_errors(pred_pos: torch.Tensor, true_pos: torch.Tensor, pred_tmp: Optional[torch.Tensor],
                  true_tmp: Optional[torch.Tensor], box_size: float) -> torch.Tensor:
     """Per-frame mean squared errors of a rollout (``cgnn_frame_errors``): ``float64 [T, 2]`` on the device, column 0

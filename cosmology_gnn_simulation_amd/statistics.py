@@ -702,6 +702,216 @@ def rollout_redshift_correlation(rollout_data: Dict[str, torch.Tensor], ground_t
     return out
 
 
+# ---- pairwise velocities: the mean infall and the two dispersions by separation -------------------------------------------
+#
+# The redshift-space multipoles above are the real-space clustering convolved with the distribution of the pairwise
+# line-of-sight velocity (the streaming picture); its first two moments by separation are the mean infall v12(r), the
+# dispersion along the pair sigma_par(r) (the fingers of god) and across it sigma_perp(r).  ``ops.pair_velocity_sums``
+# sums them in exact integers over the pair counter's pairs; what follows quantises velocities on one scale, and does
+# the host arithmetic.  Line-of-sight pairwise velocities and the full pairwise velocity distribution, per-bin histograms
+# of ``u``, weighted pairs in general, batched, sharded and owned-storage variants and a loss are not built.
+
+def _moment_words(sums: torch.Tensor, m: int) -> torch.Tensor:
+    """Moment ``m`` of ``sums [..., 3, 2]`` (int64 words lo, hi) as float64: ``hi * 2^32 + lo``, rounded once."""
+    return sums[..., m, 1].to(torch.float64) * 4294967296.0 + sums[..., m, 0].to(torch.float64)
+
+
+def pairwise_velocity_moments(counts, sums, value_scale, edges=None) -> Dict:
+    """``v12``, ``sigma_par``, ``sigma_perp`` and ``mean_square_par`` per separation bin from the exact integers of
+    ``ops.pair_velocity_sums``: ``counts [..., nb]`` and ``sums [..., nb, 3, 2]`` (the moments S1, R2, T2 as words lo,
+    hi), host arithmetic in float64.  ``value_scale`` (a number, or a tensor that broadcasts against ``[..., nb]``) is
+    the scale the velocities were quantised on; with ``step = value_scale / 2^20``
+
+    * ``v12 = step S1 / counts``: the mean relative velocity along the pair, negative for infall;
+    * ``sigma_par = step sqrt(R2 / counts - (S1 / counts)^2)``: the dispersion along the pair;
+    * ``sigma_perp = step sqrt((T2 - R2) / (2 counts))``: the dispersion per axis across it (``T2 - R2`` is taken in
+      the integer words and clipped at 0: the rounding of ``iu`` can leave it a few units negative);
+    * ``mean_square_par = step^2 R2 / counts``.
+
+    All ``nan`` where ``counts == 0``.  The dict carries ``counts`` too, and ``r_lo``, ``r_hi`` when ``edges`` (the
+    ``nb + 1`` radii) are given."""
+    what = "pairwise_velocity_moments"
+    counts, sums = torch.as_tensor(counts).detach().cpu(), torch.as_tensor(sums).detach().cpu()
+    if counts.dim() < 1 or tuple(sums.shape) != tuple(counts.shape) + (3, 2) or sums.dtype != torch.int64:
+        raise ValueError(f"{what}: sums must be int64 {list(counts.shape) + [3, 2]} for counts {tuple(counts.shape)}, "
+                         f"got {sums.dtype} {tuple(sums.shape)}")
+    if torch.is_tensor(value_scale):
+        scale = value_scale.detach().cpu().to(torch.float64)
+    else:
+        scale = torch.tensor(ops._check_value_scale(value_scale, what), dtype=torch.float64)
+    if not bool((scale > 0).all()) or not bool(torch.isfinite(scale).all()):
+        raise ValueError(f"{what}: value_scale must be positive and finite")
+    step = scale / float(1 << _lib.WEIGHT_BITS)
+    c = counts.to(torch.float64)
+    c = torch.where(c > 0, c, torch.full_like(c, float("nan")))
+    s1, r2 = _moment_words(sums, 0), _moment_words(sums, 1)
+    across = ((sums[..., 2, 1] - sums[..., 1, 1]).to(torch.float64) * 4294967296.0
+              + (sums[..., 2, 0] - sums[..., 1, 0]).to(torch.float64))
+    mean = s1 / c
+    out = {"counts": counts,
+           "v12": step * mean,
+           "sigma_par": step * torch.sqrt(torch.clamp(r2 / c - mean * mean, min=0.0)),
+           "sigma_perp": step * torch.sqrt(torch.clamp(across, min=0.0) / (2.0 * c)),
+           "mean_square_par": step * step * r2 / c}
+    if edges is not None:
+        r = torch.as_tensor(edges).detach().to(device="cpu", dtype=torch.float32).reshape(-1).to(torch.float64)
+        if r.numel() != counts.shape[-1] + 1:
+            raise ValueError(f"{what}: {r.numel()} edges for {counts.shape[-1]} bins")
+        out["r_lo"], out["r_hi"] = r[:-1], r[1:]
+    return out
+
+
+def _check_pairwise_edges(what: str, box_size, edges):
+    e = ops.check_pair_count_edges(edges, box_size, what)
+    if len(e) - 1 > _lib.PAIR_VELOCITY_MAX_BINS:
+        raise ValueError(f"{what}: edges must hold nb + 1 radii with 1 <= nb <= {_lib.PAIR_VELOCITY_MAX_BINS}, got "
+                         f"{len(e)} values")
+    return e
+
+
+def _check_dt(what: str, dt) -> float:
+    if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or not dt > 0:
+        raise ValueError(f"{what}: dt must be a positive finite number, got {dt!r}")
+    return float(dt)
+
+
+def _step_velocities(pos: torch.Tensor, pos_prev: torch.Tensor, dt: float, box_size: float) -> torch.Tensor:
+    """``minimum_image(pos - pos_prev) / dt`` in float64, the velocity of :func:`momentum_power_spectrum`."""
+    box = float(box_size)
+    d = (pos - pos_prev).to(torch.float64)
+    return (d - box * torch.round(d / box)) / float(dt)
+
+
+def _scale_on_device(value_scale, velocities, what: str):
+    """The value scale of a call: the given one checked, or the largest ``|v|`` over all the given velocity tensors as
+    a 0-d float64 device tensor (not read on the host)."""
+    if value_scale is not None:
+        return ops._check_value_scale(value_scale, what)
+    m = torch.stack([ops._max_abs_scale(v) for v in velocities]).max()
+    return m
+
+
+def pairwise_velocities(pos: torch.Tensor, box_size: float, edges, vel: Optional[torch.Tensor] = None,
+                        pos_prev: Optional[torch.Tensor] = None, dt: Optional[float] = None,
+                        pos_b: Optional[torch.Tensor] = None, vel_b: Optional[torch.Tensor] = None,
+                        pos_b_prev: Optional[torch.Tensor] = None, value_scale=None) -> Dict:
+    """The mean pairwise velocity ``v12(r)`` and the dispersions ``sigma_par(r)``, ``sigma_perp(r)`` of ``pos`` (``[N, 3]``
+    or ``[T, N, 3]``) over the pairs :func:`correlation_function` counts for ``edges`` (at most 64 bins), from the exact
+    integer sums of ``ops.pair_velocity_sums``.  Exactly one of ``vel`` (velocities in the shape of ``pos``) or
+    ``pos_prev`` with ``dt`` gives the velocities; the second form is ``minimum_image(pos - pos_prev) / dt`` in float64,
+    as in :func:`momentum_power_spectrum`.  With ``pos_b`` (and ``vel_b`` or ``pos_b_prev``, matching the form) the
+    cross pairs of the two sets, and only those: ``u`` is then the velocity of the ``pos_b`` particle relative to the
+    ``pos`` one along their separation.  ``v12 < 0`` is infall.
+
+    The velocities are quantised by ``ops.quantize_weights`` on ``value_scale`` (2^20 steps per scale); the default is
+    the largest ``|v|`` of anything in the call, taken on the device.  One runaway particle therefore coarsens the step
+    for all the others; a given ``value_scale`` is the remedy: velocities beyond it are clamped to it.  Returns the
+    dict of :func:`pairwise_velocity_moments` with ``r_lo``, ``r_hi`` and ``value_scale`` (float64, 0-d).  Everything
+    is summed on the device of ``pos`` without a host synchronisation and comes back in one transfer."""
+    what = "pairwise_velocities"
+    _check_pairwise_edges(what, box_size, edges)
+    moving = pos_prev is not None
+    if (vel is not None) == moving:
+        raise ValueError(f"{what}: exactly one of vel or (pos_prev, dt) gives the velocities")
+    if moving:
+        dt = _check_dt(what, dt)
+    elif dt is not None:
+        raise ValueError(f"{what}: dt goes with pos_prev")
+    if pos_b is None:
+        if vel_b is not None or pos_b_prev is not None:
+            raise ValueError(f"{what}: vel_b and pos_b_prev go with pos_b")
+    elif (vel_b is not None) == moving or (pos_b_prev is not None) != moving:
+        raise ValueError(f"{what}: pos_b takes vel_b when vel is given, pos_b_prev when pos_prev is")
+    sets, vels = [], []
+    for name, cur, v, prev in (("pos", pos, vel, pos_prev), ("pos_b", pos_b, vel_b, pos_b_prev)):
+        if cur is None:
+            sets.append(None)
+            continue
+        frames = _f32_frames(cur, name, what)
+        if cur.dim() != pos.dim() or frames.shape[0] != (pos.shape[0] if pos.dim() == 3 else 1):
+            raise ValueError(f"{what}: {name} {tuple(cur.shape)} does not go with pos {tuple(pos.shape)}")
+        other = prev if moving else v
+        if not torch.is_tensor(other) or tuple(other.shape) != tuple(cur.shape):
+            raise ValueError(f"{what}: the {'previous positions' if moving else 'velocities'} of {name} must have its "
+                             f"shape {tuple(cur.shape)}")
+        other = other.to(frames.device).reshape(frames.shape)
+        vels.append(_step_velocities(frames, _f32_frames(other, name + "_prev", what), dt, box_size) if moving
+                    else other.to(torch.float64))
+        sets.append(frames)
+    scale = _scale_on_device(value_scale, vels, what)
+    q = [ops.quantize_weights(v, scale) for v in vels]
+    counts, sums = ops.pair_velocity_sums(sets[0], q[0], box_size, edges, sets[1], q[1] if len(q) > 1 else None)
+    scale_t = scale.reshape(1).to(counts.device) if torch.is_tensor(scale) else \
+        torch.tensor([scale], dtype=torch.float64).to(counts.device)
+    counts, sums, scale_t = _to_host(counts, sums, scale_t.to(torch.float64))
+    if pos.dim() == 2:
+        counts, sums = counts[0], sums[0]
+    out = pairwise_velocity_moments(counts, sums, scale_t[0], edges)
+    out["value_scale"] = scale_t[0]
+    return out
+
+
+def rollout_pairwise_velocities(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor],
+                                box_size: float, edges, dt: float, frames: Optional[Sequence[int]] = None,
+                                value_scale=None) -> Dict:
+    """Pairwise velocity statistics of a rollout against the truth, for the dicts ``rollout.rollout`` returns
+    (``Coordinates [T, N, 3]``): what :func:`rollout_redshift_correlation`'s ``quadrupole_ratio`` leaves unexplained --
+    whether the mean infall, the dispersion along the pair or the one across it is off, down to scales no mesh follows.
+    Every judged frame of either side takes its velocities from its own step, ``minimum_image`` of the frame minus the
+    frame before in the same dict, over ``dt`` (:func:`pairwise_velocities`).  ``frames``: the frame numbers to judge
+    (default: every frame from 1 on that both hold); frame 0 has no predecessor: its statistics are ``nan`` and its
+    counts 0.  One ``value_scale`` serves both sides and all frames (default: the largest ``|v|`` among them, on the
+    device; a runaway predicted particle coarsens the step of everything, a given scale clamps it instead).  Per
+    selected frame (CPU, float64 ``[F, nb]``):
+
+    * ``v12_pred``, ``v12_true``, ``sigma_par_pred``, ``sigma_par_true``, ``sigma_perp_pred``, ``sigma_perp_true``;
+    * ``counts_pred``, ``counts_true`` (int64 ``[F, nb]``);
+    * ``infall_ratio``: ``v12_pred / v12_true``; ``dispersion_ratio``: ``sigma_par_pred / sigma_par_true``,
+
+    plus ``frames``, ``r_lo``, ``r_hi`` (``[nb]``) and ``value_scale``.  No cross term: the relative velocity of a
+    predicted and a true particle judges nothing.  No host synchronisation per frame; one transfer."""
+    what = "rollout_pairwise_velocities"
+    e = _check_pairwise_edges(what, box_size, edges)
+    dt = _check_dt(what, dt)
+    if value_scale is not None:
+        ops._check_value_scale(value_scale, what)
+    pc = rollout_data["Coordinates"]
+    dev = pc.device
+    truth = {"Coordinates": ground_truth["Coordinates"].to(dev)}       # moved once: the predecessors come from it too
+    if frames is None:
+        frames = range(1, min(len(pc), len(truth["Coordinates"])))
+    cp, ct, sel = _rollout_frames(rollout_data, truth, frames, what)
+    rows = [i for i, f in enumerate(sel) if f > 0]
+    if not rows:
+        raise ValueError(f"{what}: no selected frame has a predecessor (frames {sel})")
+    prev = torch.tensor([sel[i] - 1 for i in rows], dtype=torch.int64).to(dev)
+    at = torch.tensor(rows, dtype=torch.int64).to(dev)
+    pos, vels = [], []
+    for cur, source in ((cp, pc), (ct, truth["Coordinates"])):
+        pos.append(_f32_frames(cur.index_select(0, at), "Coordinates", what))
+        vels.append(_step_velocities(pos[-1], _f32_frames(source.index_select(0, prev), "Coordinates", what), dt,
+                                     box_size))
+    scale = _scale_on_device(value_scale, vels, what)
+    counted = [ops.pair_velocity_sums(p, ops.quantize_weights(v, scale), box_size, edges) for p, v in zip(pos, vels)]
+    scale_t = scale.reshape(1).to(dev) if torch.is_tensor(scale) else torch.tensor([scale], dtype=torch.float64).to(dev)
+    got_c, got_s, scale_t = _to_host(torch.stack([c for c, _ in counted]), torch.stack([s for _, s in counted]),
+                                     scale_t.to(torch.float64))
+    nb = len(e) - 1
+    counts = torch.zeros((2, len(sel), nb), dtype=torch.int64)
+    sums = torch.zeros((2, len(sel), nb, 3, 2), dtype=torch.int64)
+    counts[:, rows], sums[:, rows] = got_c, got_s
+    out = {"frames": sel, "value_scale": scale_t[0]}
+    for i, name in enumerate(("pred", "true")):
+        res = pairwise_velocity_moments(counts[i], sums[i], scale_t[0], edges)     # frame 0: counts 0, hence nan
+        out[f"counts_{name}"] = res["counts"]
+        for key in ("v12", "sigma_par", "sigma_perp"):
+            out[f"{key}_{name}"] = res[key]
+    out["r_lo"], out["r_hi"] = res["r_lo"], res["r_hi"]
+    out["infall_ratio"] = out["v12_pred"] / out["v12_true"]
+    out["dispersion_ratio"] = out["sigma_par_pred"] / out["sigma_par_true"]
+    return out
+
+
 # ---- gas fields on the mesh: thermal and momentum spectra ---------------------------------------------------------------
 #
 # ``ops.mass_assign_weighted`` deposits per-particle values in exact integers; what follows forms the fields' spectra with

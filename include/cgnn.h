@@ -593,6 +593,37 @@ int cgnn_pair_counts_smu(const float* pos_a, int64_t n_a, const float* pos_b, in
                          const float* s_edges, int32_t num_s, const float* mu_edges, int32_t num_mu, int32_t los,
                          int64_t* counts /* [num_s][num_mu] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same pairs with their relative velocities: per separation bin the pair count and three integer moments of the
+ * pairwise velocity, what the mean infall v12(r) and the dispersions sigma_par(r), sigma_perp(r) are made of.  pos_a,
+ * pos_b, box_size and edges (HOST memory, num_bins + 1 floats) as in cgnn_pair_counts.  q_a [n_a, 3] and q_b [n_b, 3]
+ * (device, int32) are quantised velocities with |q| <= 2^20 (2^20 is one value scale); the entry cannot check that bound,
+ * the caller keeps it.  For a pair (a, b), dx, dy, dz (b minus a, folded) and d2 are exactly those of cgnn_pair_counts; the
+ * pair counts iff e2[0] <= d2 < e2[num_bins], in that entry's bin (the auto mode skips the particle itself), and yields
+ *     dq_c = q_b[c] - q_a[c]                          exact int32, |dq_c| <= 2^21
+ *     t2   = dq_x*dq_x + dq_y*dq_y + dq_z*dq_z        exact int64, < 2^44
+ *     w    = fl32(fl32(fl32(f(dq_x)*dx) + fl32(f(dq_y)*dy)) + fl32(f(dq_z)*dz))      f: the exact int -> float32 conversion
+ *     d2 > 0:   r = fl32(sqrt(d2)),  u = fl32(w / r),  iu = rint(u)
+ *     d2 == 0:  iu = 0                                (coincident particles: no direction; t2 still counts)
+ * one float32 rounding per operation, no FMA; sqrt and / are IEEE correctly rounded, rint rounds ties to even and gives an
+ * int32.  u < 0 is approach (infall).  Per bin: counts += 1, S1 += iu, R2 += iu*iu, T2 += t2.  d and dq both change sign
+ * under a <-> b, so the rule is symmetric: the auto mode (pos_b == NULL, q_b == NULL) walks ordered pairs i != j and
+ * halves the exact even totals (S1 by an arithmetic shift); cross as in cgnn_pair_counts.
+ * counts (device, int64 [num_bins]) and sums (device, int64 [num_bins][3][2]) are overwritten.  counts equals what
+ * cgnn_pair_counts gives for the same edges, bit for bit.  sums holds the moments in the order S1, R2, T2 as two words
+ * (lo, hi) each: the exact total is hi * 2^32 + lo with 0 <= lo < 2^32 and hi signed (negative only for S1) -- a frame of
+ * 10^6 clustered particles passes int64 in R2 and T2.  The words are normalised on the device and therefore canonical.
+ * Exact integers: the result does not depend on any order and is the same bits on every run.  No host synchronisation,
+ * everything on `stream`.
+ * CGNN_ERR_INVALID_ARG unless 1 <= num_bins <= 64, q_a != NULL, q_b given exactly when pos_b is, and edges and box_size
+ * as in cgnn_pair_counts; 2^31 or more particles in a set: CGNN_ERR_UNSUPPORTED.  All of it is refused on the host before
+ * any launch.
+ * Workspace: that of cgnn_pair_counts plus 16 bytes per particle of each set; a function of n_a and n_b alone (n_b = 0:
+ * auto), 16-byte aligned. */
+size_t cgnn_pair_velocity_sums_workspace_bytes(int64_t n_a, int64_t n_b, int32_t num_bins);
+int cgnn_pair_velocity_sums(const float* pos_a, const int32_t* q_a, int64_t n_a, const float* pos_b, const int32_t* q_b,
+                            int64_t n_b, float box_size, const float* edges, int32_t num_bins, int64_t* counts,
+                            int64_t* sums /* [num_bins][3][2] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-frame errors of a rollout against the truth: pred_pos / true_pos [frames, n, 3], pred_tmp / true_tmp [frames, n]
  * (both NULL: no temperatures, the second sum is 0).  out (device, double [frames, 2]):
  *   out[f, 0] = sum over particles and axes of fold(fl32(pred - true))^2     (fold: the minimum image of the entry above)
