@@ -39,18 +39,24 @@
 // that are their own conjugates (nz == 0, and nz == M/2 when M is even) and 2 elsewhere: the half array then sums what
 // the full cube would.  cgnn_power_bin_ids writes the bin of every mode (-1: none); the caller sorts the ids stably
 // (once per mesh and edges: ops.PowerPlan) into `perm`, the counted modes grouped by bin in ascending mode index, and
-// `bin_start`, where each bin begins.  cgnn_power_bins then sums in two stages: workgroup (frame, bin, part) takes the
-// part-th of CGNN_PB_PARTS equal slices of the bin's run of perm, each thread its strided share in index order, a tree
-// over the threads; one thread per (frame, bin, sum) then adds the parts in part order.  No float atomics: two runs give
-// the same bits.  A slice without modes writes zeros and leaves before the tree.  Compiled with -ffp-contract=off (Makefile): every operation below rounds once, in float32 and float64.
+// `bin_start`, where each bin begins.
+//
+// Shell sums.  cgnn_power_bins and cgnn_power_multipoles are one reduction (shell_sums) with two row sets.  It sums in
+// two stages: workgroup (frame, bin, part) of shell_partial_kernel<L, HAS_B, INTER> takes the part-th of CGNN_PB_PARTS
+// equal slices of the bin's run of perm, each thread its strided share in index order, a tree over the threads; one
+// thread per (frame, bin, sum) of shell_final_kernel<L> then adds the parts in part order.  No float atomics: two runs
+// give the same bits.  A slice without modes writes zeros and leaves before the tree.  Per bin there are 4 L sums:
+// |x|^2, |y|^2 and Re(x conj y), each times the L Legendre weights, then the L tail rows.  L = 1 (cgnn_power_bins) has
+// the weight 1 and the tail sqrt(n2).  L = 3 (cgnn_power_multipoles) has the weights 1, L2 and L4 of mu = n_los / |n|
+// and the tail sqrt(n2), L2, L4; with a second pair of transforms, of the same particles displaced by half a cell,
+// x = (a + a2 e^{i pi (nx + ny + nz) / M}) / 2: the mesh's odd aliases cancel.  L = 1 emits nothing of mu, L2, L4 or the
+// line of sight, and has no interlaced form.  The first row of each L is the same expression in both: without a2 rows
+// 0, 3, 6, 9 and modes of the multipoles are cgnn_power_bins' bits by construction.  tests/multipole_checks.py and
+// tests/power_spectrum_checks.py restate both in numpy.  Compiled with -ffp-contract=off (Makefile): every operation
+// below rounds once, in float32 and float64.
 //
 // Redshift space.  cgnn_redshift_positions displaces every particle along a box axis by `shift` times its minimum-image
 // step from the frame before (float32, one rounding per operation, wrapped into [0, L]: the deposit's contract).
-// cgnn_power_multipoles is cgnn_power_bins' two-stage sum with twelve sums per bin: |x|^2, |y|^2 and Re(x conj y), each
-// times 1, L2 and L4 of mu = n_los / |n|, then sqrt(n2), L2 and L4 alone.  With a second pair of transforms, of the same
-// particles displaced by half a cell, x = (a + a2 e^{i pi (nx + ny + nz) / M}) / 2: the mesh's odd aliases cancel.
-// pm_partial_kernel<HAS_B, INTER> keeps pb_partial_kernel's decomposition and, for the monopole rows, its expressions:
-// without a2 they are cgnn_power_bins' bits.  tests/multipole_checks.py restates both in numpy.
 #include <math.h>
 
 #include "cgnn_util.hpp"
@@ -60,7 +66,8 @@
 #define CGNN_PB_MAX_BINS 256
 #define CGNN_PB_PARTS 64          // slices per bin (stage 1 of cgnn_power_bins)
 #define CGNN_PS_MAX_THREADS ((int64_t)1 << 24)   // threads per launch: many frames go through in several launches
-#define CGNN_PB_SUMS 4            // float64 sums per (frame, bin): |a|^2, |b|^2, Re(a conj b), sqrt(n2)
+#define CGNN_PB_SUMS 4            // float64 sums per (frame, bin) of cgnn_power_bins: |a|^2, |b|^2, Re(a conj b), sqrt(n2)
+#define CGNN_PM_SUMS 12           // ... of cgnn_power_multipoles (rows: include/cgnn.h)
 
 namespace cgnn {
 
@@ -310,93 +317,7 @@ __global__ void pb_window_kernel(int M, int order, double* __restrict__ inv_w2) 
     inv_w2[i] = v;
 }
 
-// stage 1: workgroup ((f * num_bins + bin) * PARTS + part); partial [frames, num_bins, PARTS, SUMS], cnt likewise one value
-__global__ __launch_bounds__(CGNN_BLOCK) void pb_partial_kernel(const double2* __restrict__ a, const double2* __restrict__ b,
-                                                                int M, int Mh, int64_t modes_per_frame,
-                                                                const int32_t* __restrict__ perm,
-                                                                const int32_t* __restrict__ bin_start, int num_bins,
-                                                                const double* __restrict__ inv_w2,
-                                                                double* __restrict__ partial, long long* __restrict__ cnt) {
-    __shared__ double red[CGNN_PB_SUMS][CGNN_BLOCK];
-    __shared__ long long redc[CGNN_BLOCK];
-    const int part = blockIdx.x % CGNN_PB_PARTS;
-    const int bin = (blockIdx.x / CGNN_PB_PARTS) % num_bins;
-    const int64_t f = blockIdx.x / (CGNN_PB_PARTS * num_bins);
-    // clamped: a plan that does not belong to this mesh reads nothing outside perm [modes_per_frame]
-    const int p0 = max(0, min(bin_start[bin], (int)modes_per_frame));
-    const int p1 = max(p0, min(bin_start[bin + 1], (int)modes_per_frame));
-    const int per = (p1 - p0 + CGNN_PB_PARTS - 1) / CGNN_PB_PARTS;
-    const int q0 = p0 + part * per, q1 = min(q0 + per, p1);
-    if (q0 >= q1) {     // an empty slice (a bin of few modes fills only its first slices): uniform over the workgroup
-        if (threadIdx.x < CGNN_PB_SUMS) partial[(int64_t)blockIdx.x * CGNN_PB_SUMS + threadIdx.x] = 0.0;
-        if (threadIdx.x == 0) cnt[blockIdx.x] = 0;
-        return;
-    }
-    const double2* af = a + f * modes_per_frame;
-    const double2* bf = b ? b + f * modes_per_frame : nullptr;
-    double saa = 0.0, sbb = 0.0, sab = 0.0, sk = 0.0;
-    long long sc = 0;
-    for (int p = q0 + (int)threadIdx.x; p < q1; p += CGNN_BLOCK) {
-        const int idx = perm[p];
-        if (idx < 0 || idx >= modes_per_frame) continue;      // a plan of another mesh: nothing is read out of bounds
-        int nx, ny, nz;
-        pb_mode(idx, M, Mh, nx, ny, nz);
-        const double h = (nz == 0 || 2 * nz == M) ? 1.0 : 2.0;
-        const double wt = h * ((inv_w2[abs(nx)] * inv_w2[abs(ny)]) * inv_w2[nz]);
-        const double2 x = af[idx];
-        saa += wt * (x.x * x.x + x.y * x.y);
-        if (bf) {
-            const double2 y = bf[idx];
-            sbb += wt * (y.x * y.x + y.y * y.y);
-            sab += wt * (x.x * y.x + x.y * y.y);
-        }
-        sk += h * sqrt((double)(nx * nx + ny * ny + nz * nz));
-        sc += (long long)h;
-    }
-    red[0][threadIdx.x] = saa;
-    red[1][threadIdx.x] = sbb;
-    red[2][threadIdx.x] = sab;
-    red[3][threadIdx.x] = sk;
-    redc[threadIdx.x] = sc;
-    __syncthreads();
-    for (int off = CGNN_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-#pragma unroll
-            for (int q = 0; q < CGNN_PB_SUMS; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + off];
-            redc[threadIdx.x] += redc[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < CGNN_PB_SUMS) partial[(int64_t)blockIdx.x * CGNN_PB_SUMS + threadIdx.x] = red[threadIdx.x][0];
-    if (threadIdx.x == 0) cnt[blockIdx.x] = redc[0];
-}
-
-// stage 2: thread (f, bin, q) adds the parts in part order; q == SUMS is the mode count.
-// sums [frames, SUMS, num_bins] (rows 1 and 2 untouched without b), modes [frames, num_bins]
-__global__ __launch_bounds__(CGNN_BLOCK) void pb_final_kernel(const double* __restrict__ partial,
-                                                              const long long* __restrict__ cnt, int64_t frames,
-                                                              int num_bins, int have_b, double* __restrict__ sums,
-                                                              long long* __restrict__ modes) {
-    const int64_t t = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
-    if (t >= frames * num_bins * (CGNN_PB_SUMS + 1)) return;
-    const int q = (int)(t % (CGNN_PB_SUMS + 1));
-    const int64_t fb = t / (CGNN_PB_SUMS + 1);        // f * num_bins + bin
-    const int64_t f = fb / num_bins, bin = fb % num_bins;
-    if (q == CGNN_PB_SUMS) {
-        long long s = 0;
-        for (int j = 0; j < CGNN_PB_PARTS; ++j) s += cnt[fb * CGNN_PB_PARTS + j];
-        modes[fb] = s;
-        return;
-    }
-    if (!have_b && (q == 1 || q == 2)) return;
-    double s = 0.0;
-    for (int j = 0; j < CGNN_PB_PARTS; ++j) s += partial[(fb * CGNN_PB_PARTS + j) * CGNN_PB_SUMS + q];
-    sums[(f * CGNN_PB_SUMS + q) * num_bins + bin] = s;
-}
-
-// ---- redshift space: cgnn_redshift_positions and cgnn_power_multipoles --------------------------------------------------
-#define CGNN_PM_SUMS 12           // float64 sums per (frame, bin) of cgnn_power_multipoles (rows: include/cgnn.h)
-
+// ---- redshift space: cgnn_redshift_positions ----------------------------------------------------------------------------
 // one thread per particle of every frame: out = pos with the `los` coordinate displaced by shift times the minimum-image
 // step from prev.  One float32 rounding per operation (the sequence of include/cgnn.h); whatever does not end in [0, L]
 // (a non-finite input, a shift of so many boxes that the wrap's own rounding exceeds one box) is written as 0.
@@ -420,6 +341,7 @@ __global__ __launch_bounds__(CGNN_BLOCK) void rs_positions_kernel(const float* _
     out[3 * i + 2] = los == 2 ? s : c[2];
 }
 
+// ---- shell sums: cgnn_power_bins and cgnn_power_multipoles ---------------------------------------------------------------
 // 0.5 (u + v e^{i pi t}) with (sn, cs) = sincospi(t): the interlaced pair of one mode
 __device__ __forceinline__ double2 pm_interlaced(const double2 u, const double2 v, double sn, double cs) {
     double2 r;
@@ -428,30 +350,34 @@ __device__ __forceinline__ double2 pm_interlaced(const double2 u, const double2 
     return r;
 }
 
-// stage 1 of cgnn_power_multipoles: pb_partial_kernel's decomposition (workgroup ((f * num_bins + bin) * PARTS + part),
-// the same clamped slice, strided shares in index order, the same tree) with twelve sums.  Rows 0, 3, 6 and 9 are formed
-// by pb_partial_kernel's expressions in its order, so the plain form gives its bits.  HAS_B / INTER are compile-time:
-// the plain auto form loads a alone and keeps six rows of LDS.  partial [blocks, 12], cnt [blocks].
-template <bool HAS_B, bool INTER>
-__global__ __launch_bounds__(CGNN_BLOCK) void pm_partial_kernel(const double2* __restrict__ a, const double2* __restrict__ b,
-                                                                const double2* __restrict__ a2, const double2* __restrict__ b2,
-                                                                int M, int Mh, int los, int64_t modes_per_frame,
-                                                                const int32_t* __restrict__ perm,
-                                                                const int32_t* __restrict__ bin_start, int num_bins,
-                                                                const double* __restrict__ inv_w2,
-                                                                double* __restrict__ partial, long long* __restrict__ cnt) {
-    constexpr int ROWS = HAS_B ? CGNN_PM_SUMS : 6;        // without b: rows 0-2 and 9-11
+// stage 1 of the shell sums: workgroup ((f * num_bins + bin) * PARTS + part) takes its clamped slice of perm, every
+// thread its strided share in index order, then a tree over the threads.  L Legendre weights per product (1: the weight
+// 1 alone; 3: 1, L2, L4 of mu about `los`), 4 L sums: L each of |x|^2, |y|^2 and Re(x conj y), then the tail (sqrt(n2),
+// and L2, L4).  HAS_B / INTER are compile-time: without b only a is loaded and 2 L rows of LDS are kept; L = 1 computes
+// nothing of mu2, l2, l4 or los and has no interlaced form.  partial [blocks, 4 L], cnt [blocks].
+template <int L, bool HAS_B, bool INTER>
+__global__ __launch_bounds__(CGNN_BLOCK) void shell_partial_kernel(const double2* __restrict__ a, const double2* __restrict__ b,
+                                                                   const double2* __restrict__ a2, const double2* __restrict__ b2,
+                                                                   int M, int Mh, int los, int64_t modes_per_frame,
+                                                                   const int32_t* __restrict__ perm,
+                                                                   const int32_t* __restrict__ bin_start, int num_bins,
+                                                                   const double* __restrict__ inv_w2,
+                                                                   double* __restrict__ partial, long long* __restrict__ cnt) {
+    static_assert(L == 3 || (L == 1 && !INTER), "the forms the two entries reach");
+    constexpr int SUMS = 4 * L;
+    constexpr int ROWS = HAS_B ? SUMS : 2 * L;        // without b: the |x|^2 rows and the tail
     __shared__ double red[ROWS][CGNN_BLOCK];
     __shared__ long long redc[CGNN_BLOCK];
     const int part = blockIdx.x % CGNN_PB_PARTS;
     const int bin = (blockIdx.x / CGNN_PB_PARTS) % num_bins;
     const int64_t f = blockIdx.x / (CGNN_PB_PARTS * num_bins);
+    // clamped: a plan that does not belong to this mesh reads nothing outside perm [modes_per_frame]
     const int p0 = max(0, min(bin_start[bin], (int)modes_per_frame));
     const int p1 = max(p0, min(bin_start[bin + 1], (int)modes_per_frame));
     const int per = (p1 - p0 + CGNN_PB_PARTS - 1) / CGNN_PB_PARTS;
     const int q0 = p0 + part * per, q1 = min(q0 + per, p1);
-    if (q0 >= q1) {
-        if (threadIdx.x < CGNN_PM_SUMS) partial[(int64_t)blockIdx.x * CGNN_PM_SUMS + threadIdx.x] = 0.0;
+    if (q0 >= q1) {     // an empty slice (a bin of few modes fills only its first slices): uniform over the workgroup
+        if (threadIdx.x < SUMS) partial[(int64_t)blockIdx.x * SUMS + threadIdx.x] = 0.0;
         if (threadIdx.x == 0) cnt[blockIdx.x] = 0;
         return;
     }
@@ -459,59 +385,60 @@ __global__ __launch_bounds__(CGNN_BLOCK) void pm_partial_kernel(const double2* _
     const double2* bf = HAS_B ? b + f * modes_per_frame : nullptr;
     const double2* af2 = INTER ? a2 + f * modes_per_frame : nullptr;
     const double2* bf2 = (HAS_B && INTER) ? b2 + f * modes_per_frame : nullptr;
-    double sa[3] = {0.0, 0.0, 0.0}, sb[3] = {0.0, 0.0, 0.0}, sx[3] = {0.0, 0.0, 0.0};
-    double sk = 0.0, sl2 = 0.0, sl4 = 0.0;
+    double sa[L] = {}, sb[L] = {}, sx[L] = {}, st[L] = {};
     long long sc = 0;
     for (int p = q0 + (int)threadIdx.x; p < q1; p += CGNN_BLOCK) {
         const int idx = perm[p];
-        if (idx < 0 || idx >= modes_per_frame) continue;
+        if (idx < 0 || idx >= modes_per_frame) continue;      // a plan of another mesh: nothing is read out of bounds
         int nx, ny, nz;
         pb_mode(idx, M, Mh, nx, ny, nz);
         const double h = (nz == 0 || 2 * nz == M) ? 1.0 : 2.0;
         const double wt = h * ((inv_w2[abs(nx)] * inv_w2[abs(ny)]) * inv_w2[nz]);
         const int n2 = nx * nx + ny * ny + nz * nz;
-        const int nl = los == 0 ? nx : (los == 1 ? ny : nz);
-        const double mu2 = n2 != 0 ? (double)(nl * nl) / (double)n2 : 0.0;
-        const double l2 = 1.5 * mu2 - 0.5;
-        const double l4 = (4.375 * mu2 - 3.75) * mu2 + 0.375;
+        double leg[L];                                        // leg[0], the weight 1, is never multiplied by
+        if constexpr (L == 3) {
+            const int nl = los == 0 ? nx : (los == 1 ? ny : nz);
+            const double mu2 = n2 != 0 ? (double)(nl * nl) / (double)n2 : 0.0;
+            leg[1] = 1.5 * mu2 - 0.5;
+            leg[2] = (4.375 * mu2 - 3.75) * mu2 + 0.375;
+        }
         double sn = 0.0, cs = 1.0;
         if constexpr (INTER) sincospi((double)(nx + ny + nz) / (double)M, &sn, &cs);
         double2 x = af[idx];
         if constexpr (INTER) x = pm_interlaced(x, af2[idx], sn, cs);
         const double paa = wt * (x.x * x.x + x.y * x.y);
         sa[0] += paa;
-        sa[1] += paa * l2;
-        sa[2] += paa * l4;
+#pragma unroll
+        for (int q = 1; q < L; ++q) sa[q] += paa * leg[q];
         if constexpr (HAS_B) {
             double2 y = bf[idx];
             if constexpr (INTER) y = pm_interlaced(y, bf2[idx], sn, cs);
             const double pbb = wt * (y.x * y.x + y.y * y.y);
             sb[0] += pbb;
-            sb[1] += pbb * l2;
-            sb[2] += pbb * l4;
+#pragma unroll
+            for (int q = 1; q < L; ++q) sb[q] += pbb * leg[q];
             const double pab = wt * (x.x * y.x + x.y * y.y);
             sx[0] += pab;
-            sx[1] += pab * l2;
-            sx[2] += pab * l4;
+#pragma unroll
+            for (int q = 1; q < L; ++q) sx[q] += pab * leg[q];
         }
-        sk += h * sqrt((double)n2);
-        sl2 += h * l2;
-        sl4 += h * l4;
+        st[0] += h * sqrt((double)n2);
+#pragma unroll
+        for (int q = 1; q < L; ++q) st[q] += h * leg[q];
         sc += (long long)h;
     }
-    // LDS rows: with b the output rows themselves; without, rows 0-2 then 9-11
-    constexpr int TAIL = HAS_B ? 9 : 3;
+    // LDS rows: with b the output rows themselves; without, the |x|^2 rows then the tail
+    constexpr int TAIL = ROWS - L;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < L; ++q) {
         red[q][threadIdx.x] = sa[q];
         if constexpr (HAS_B) {
-            red[3 + q][threadIdx.x] = sb[q];
-            red[6 + q][threadIdx.x] = sx[q];
+            red[L + q][threadIdx.x] = sb[q];
+            red[2 * L + q][threadIdx.x] = sx[q];
         }
     }
-    red[TAIL][threadIdx.x] = sk;
-    red[TAIL + 1][threadIdx.x] = sl2;
-    red[TAIL + 2][threadIdx.x] = sl4;
+#pragma unroll
+    for (int q = 0; q < L; ++q) red[TAIL + q][threadIdx.x] = st[q];
     redc[threadIdx.x] = sc;
     __syncthreads();
     for (int off = CGNN_BLOCK / 2; off > 0; off >>= 1) {
@@ -522,38 +449,40 @@ __global__ __launch_bounds__(CGNN_BLOCK) void pm_partial_kernel(const double2* _
         }
         __syncthreads();
     }
-    if (threadIdx.x < CGNN_PM_SUMS) {
+    if (threadIdx.x < SUMS) {
         const int q = threadIdx.x;
-        double v = 0.0;                                                     // rows 3-8 without b: not read by stage 2
+        double v = 0.0;                                                     // rows [L, 3 L) without b: not read by stage 2
         if constexpr (HAS_B) v = red[q][0];
-        else if (q < 3) v = red[q][0];
-        else if (q >= 9) v = red[q - 6][0];
-        partial[(int64_t)blockIdx.x * CGNN_PM_SUMS + q] = v;
+        else if (q < L) v = red[q][0];
+        else if (q >= 3 * L) v = red[q - 2 * L][0];
+        partial[(int64_t)blockIdx.x * SUMS + q] = v;
     }
     if (threadIdx.x == 0) cnt[blockIdx.x] = redc[0];
 }
 
-// stage 2: thread (f, bin, q) adds the parts in part order; q == 12 is the mode count.
-// sums [frames, 12, num_bins] (rows 3-8 untouched without b), modes [frames, num_bins]
-__global__ __launch_bounds__(CGNN_BLOCK) void pm_final_kernel(const double* __restrict__ partial,
-                                                              const long long* __restrict__ cnt, int64_t frames,
-                                                              int num_bins, int have_b, double* __restrict__ sums,
-                                                              long long* __restrict__ modes) {
+// stage 2: thread (f, bin, q) adds the parts in part order; q == 4 L is the mode count.
+// sums [frames, 4 L, num_bins] (rows [L, 3 L) untouched without b), modes [frames, num_bins]
+template <int L>
+__global__ __launch_bounds__(CGNN_BLOCK) void shell_final_kernel(const double* __restrict__ partial,
+                                                                 const long long* __restrict__ cnt, int64_t frames,
+                                                                 int num_bins, int have_b, double* __restrict__ sums,
+                                                                 long long* __restrict__ modes) {
+    constexpr int SUMS = 4 * L;
     const int64_t t = (int64_t)blockIdx.x * CGNN_BLOCK + threadIdx.x;
-    if (t >= frames * num_bins * (CGNN_PM_SUMS + 1)) return;
-    const int q = (int)(t % (CGNN_PM_SUMS + 1));
-    const int64_t fb = t / (CGNN_PM_SUMS + 1);        // f * num_bins + bin
+    if (t >= frames * num_bins * (SUMS + 1)) return;
+    const int q = (int)(t % (SUMS + 1));
+    const int64_t fb = t / (SUMS + 1);        // f * num_bins + bin
     const int64_t f = fb / num_bins, bin = fb % num_bins;
-    if (q == CGNN_PM_SUMS) {
+    if (q == SUMS) {
         long long s = 0;
         for (int j = 0; j < CGNN_PB_PARTS; ++j) s += cnt[fb * CGNN_PB_PARTS + j];
         modes[fb] = s;
         return;
     }
-    if (!have_b && q >= 3 && q <= 8) return;
+    if (!have_b && q >= L && q < 3 * L) return;
     double s = 0.0;
-    for (int j = 0; j < CGNN_PB_PARTS; ++j) s += partial[(fb * CGNN_PB_PARTS + j) * CGNN_PM_SUMS + q];
-    sums[(f * CGNN_PM_SUMS + q) * num_bins + bin] = s;
+    for (int j = 0; j < CGNN_PB_PARTS; ++j) s += partial[(fb * CGNN_PB_PARTS + j) * SUMS + q];
+    sums[(f * SUMS + q) * num_bins + bin] = s;
 }
 
 static bool pb_edges(const float* k_edges, int32_t num_bins, PbEdges2& E, const char* who) {
@@ -662,6 +591,73 @@ static int ma_gather(const char* who, const float* pos, const int32_t* q, const 
     return check_hip(hipGetLastError(), who);
 }
 
+static size_t shell_workspace_bytes(int64_t frames, int32_t num_bins, int rows) {
+    if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
+    const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
+    return pb_window_bytes() + align256(blocks * rows * sizeof(double)) + align256(blocks * sizeof(long long));
+}
+
+// cgnn_power_bins (L = 1: a2, b2 null, los unused) and cgnn_power_multipoles (L = 3, its own refusals made): the
+// refusals the two share, the window, then both stages for whole frames per launch.  Nothing is launched after a refusal.
+static int shell_sums(const char* who, int L, const double* a, const double* b, const double* a2, const double* b2,
+                      int64_t frames, int32_t mesh, int32_t order, int32_t los, const int32_t* perm,
+                      const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!a || !perm || !bin_start || !modes || !sums || !workspace || frames <= 0 || mesh < 2 ||
+        mesh > CGNN_MA_MAX_MESH || order < 0 || order > 3 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
+        set_error("%s: invalid argument (mesh in [2, %d], order in [0, 3], num_bins in [1, %d])", who, CGNN_MA_MAX_MESH,
+                  CGNN_PB_MAX_BINS);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    for (const void* ptr : {(const void*)workspace, (const void*)a, (const void*)b, (const void*)a2, (const void*)b2})
+        if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) {
+            set_error("%s: %s and the workspace must be 16-byte aligned", who, L == 1 ? "a, b" : "a, b, a2, b2");
+            return CGNN_ERR_INVALID_ARG;
+        }
+    const int rows = 4 * L;
+    const size_t need = shell_workspace_bytes(frames, num_bins, rows);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+        return CGNN_ERR_WORKSPACE;
+    }
+    const int64_t per_frame = (int64_t)num_bins * CGNN_PB_PARTS, blocks = frames * per_frame;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    double* inv_w2 = reinterpret_cast<double*>(ws);
+    double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
+    long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() + align256((size_t)blocks * rows * sizeof(double)));
+    const int Mh = mesh / 2 + 1;
+    pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
+    const int64_t mpf = (int64_t)mesh * mesh * Mh;
+    const double2* ca = reinterpret_cast<const double2*>(a);
+    const double2* cb = reinterpret_cast<const double2*>(b);
+    const double2* ca2 = reinterpret_cast<const double2*>(a2);
+    const double2* cb2 = reinterpret_cast<const double2*>(b2);
+    ps_for_frame_batches(frames, per_frame * CGNN_BLOCK, [&](int64_t f0, int64_t nf) {       // at least 4 frames each
+        const unsigned grid = (unsigned)(nf * per_frame);
+        const int64_t off = f0 * mpf;
+        double* part = partial + f0 * per_frame * rows;
+        long long* c = cnt + f0 * per_frame;
+        const unsigned outs = (unsigned)((nf * num_bins * (rows + 1) + CGNN_BLOCK - 1) / CGNN_BLOCK);
+        long long* m = reinterpret_cast<long long*>(modes) + f0 * num_bins;
+#define CGNN_SHELL_LAUNCH(L, HAS_B, INTER)                                                                                \
+    do {                                                                                                                  \
+        shell_partial_kernel<L, HAS_B, INTER><<<grid, CGNN_BLOCK, 0, st>>>(                                               \
+            ca + off, HAS_B ? cb + off : nullptr, INTER ? ca2 + off : nullptr, (HAS_B && INTER) ? cb2 + off : nullptr,    \
+            mesh, Mh, los, mpf, perm, bin_start, num_bins, inv_w2, part, c);                                              \
+        shell_final_kernel<L><<<outs, CGNN_BLOCK, 0, st>>>(part, c, nf, num_bins, HAS_B, sums + f0 * rows * num_bins, m); \
+    } while (0)
+        if (L == 1 && cb) CGNN_SHELL_LAUNCH(1, true, false);
+        else if (L == 1) CGNN_SHELL_LAUNCH(1, false, false);
+        else if (cb && ca2) CGNN_SHELL_LAUNCH(3, true, true);
+        else if (cb) CGNN_SHELL_LAUNCH(3, true, false);
+        else if (ca2) CGNN_SHELL_LAUNCH(3, false, true);
+        else CGNN_SHELL_LAUNCH(3, false, false);
+#undef CGNN_SHELL_LAUNCH
+    });
+    return check_hip(hipGetLastError(), who);
+}
+
 extern "C" {
 
 int cgnn_mass_assign(const float* pos, int64_t frames, int64_t n, float box_size, int32_t mesh, int32_t order,
@@ -710,52 +706,14 @@ int cgnn_power_bin_ids(int32_t mesh, const float* k_edges, int32_t num_bins, int
 }
 
 size_t cgnn_power_bins_workspace_bytes(int64_t frames, int32_t num_bins) {
-    if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
-    const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
-    return pb_window_bytes() + align256(blocks * CGNN_PB_SUMS * sizeof(double)) + align256(blocks * sizeof(long long));
+    return shell_workspace_bytes(frames, num_bins, CGNN_PB_SUMS);
 }
 
 int cgnn_power_bins(const double* a, const double* b, int64_t frames, int32_t mesh, int32_t order, const int32_t* perm,
                     const int32_t* bin_start, int32_t num_bins, int64_t* modes, double* sums, void* workspace,
                     size_t workspace_bytes, void* stream) {
-    if (!a || !perm || !bin_start || !modes || !sums || !workspace || frames <= 0 || mesh < 2 ||
-        mesh > CGNN_MA_MAX_MESH || order < 0 || order > 3 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
-        set_error("cgnn_power_bins: invalid argument (mesh in [2, %d], order in [0, 3], num_bins in [1, %d])",
-                  CGNN_MA_MAX_MESH, CGNN_PB_MAX_BINS);
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const int64_t per_frame = (int64_t)num_bins * CGNN_PB_PARTS, blocks = frames * per_frame;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(a) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(b) & 15) != 0) {
-        set_error("cgnn_power_bins: a, b and the workspace must be 16-byte aligned");
-        return CGNN_ERR_INVALID_ARG;
-    }
-    const size_t need = cgnn_power_bins_workspace_bytes(frames, num_bins);
-    if (workspace_bytes < need) {
-        set_error("cgnn_power_bins: workspace %zu < required %zu bytes", workspace_bytes, need);
-        return CGNN_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    double* inv_w2 = reinterpret_cast<double*>(ws);
-    double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
-    long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() +
-                                                  align256((size_t)blocks * CGNN_PB_SUMS * sizeof(double)));
-    const int Mh = mesh / 2 + 1;
-    pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
-    const int64_t modes_per_frame = (int64_t)mesh * mesh * Mh;
-    const double2* a2 = reinterpret_cast<const double2*>(a);
-    const double2* b2 = reinterpret_cast<const double2*>(b);
-    ps_for_frame_batches(frames, per_frame * CGNN_BLOCK, [&](int64_t f0, int64_t nf) {       // at least 4 frames each
-        pb_partial_kernel<<<(unsigned)(nf * per_frame), CGNN_BLOCK, 0, st>>>(
-            a2 + f0 * modes_per_frame, b2 ? b2 + f0 * modes_per_frame : nullptr, mesh, Mh, modes_per_frame, perm, bin_start,
-            num_bins, inv_w2, partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame);
-        const int64_t outs = nf * num_bins * (CGNN_PB_SUMS + 1);
-        pb_final_kernel<<<(unsigned)((outs + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
-            partial + f0 * per_frame * CGNN_PB_SUMS, cnt + f0 * per_frame, nf, num_bins, b != nullptr,
-            sums + f0 * CGNN_PB_SUMS * num_bins, reinterpret_cast<long long*>(modes) + f0 * num_bins);
-    });
-    return check_hip(hipGetLastError(), "cgnn_power_bins");
+    return shell_sums("cgnn_power_bins", 1, a, b, nullptr, nullptr, frames, mesh, order, 0, perm, bin_start, num_bins, modes,
+                      sums, workspace, workspace_bytes, stream);
 }
 
 int cgnn_redshift_positions(const float* pos, const float* pos_prev, int64_t frames, int64_t n, float box_size,
@@ -783,9 +741,7 @@ int cgnn_redshift_positions(const float* pos, const float* pos_prev, int64_t fra
 }
 
 size_t cgnn_power_multipoles_workspace_bytes(int64_t frames, int32_t num_bins) {
-    if (frames <= 0 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) return 256;
-    const size_t blocks = (size_t)frames * num_bins * CGNN_PB_PARTS;
-    return pb_window_bytes() + align256(blocks * CGNN_PM_SUMS * sizeof(double)) + align256(blocks * sizeof(long long));
+    return shell_workspace_bytes(frames, num_bins, CGNN_PM_SUMS);
 }
 
 int cgnn_power_multipoles(const double* a, const double* b, const double* a2, const double* b2, int64_t frames,
@@ -793,12 +749,6 @@ int cgnn_power_multipoles(const double* a, const double* b, const double* a2, co
                           int32_t num_bins, int64_t* modes, double* sums, void* workspace, size_t workspace_bytes,
                           void* stream) {
     const char* who = "cgnn_power_multipoles";
-    if (!a || !perm || !bin_start || !modes || !sums || !workspace || frames <= 0 || mesh < 2 ||
-        mesh > CGNN_MA_MAX_MESH || order < 0 || order > 3 || num_bins < 1 || num_bins > CGNN_PB_MAX_BINS) {
-        set_error("%s: invalid argument (mesh in [2, %d], order in [0, 3], num_bins in [1, %d])", who, CGNN_MA_MAX_MESH,
-                  CGNN_PB_MAX_BINS);
-        return CGNN_ERR_INVALID_ARG;
-    }
     if (los < 0 || los > 2) {
         set_error("%s: los=%d outside [0, 2]", who, (int)los);
         return CGNN_ERR_INVALID_ARG;
@@ -807,51 +757,8 @@ int cgnn_power_multipoles(const double* a, const double* b, const double* a2, co
         set_error("%s: b2 goes with b and a2, and must be given when both are", who);
         return CGNN_ERR_INVALID_ARG;
     }
-    for (const void* ptr : {(const void*)workspace, (const void*)a, (const void*)b, (const void*)a2, (const void*)b2})
-        if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) {
-            set_error("%s: a, b, a2, b2 and the workspace must be 16-byte aligned", who);
-            return CGNN_ERR_INVALID_ARG;
-        }
-    const size_t need = cgnn_power_multipoles_workspace_bytes(frames, num_bins);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
-        return CGNN_ERR_WORKSPACE;
-    }
-    const int64_t per_frame = (int64_t)num_bins * CGNN_PB_PARTS, blocks = frames * per_frame;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
-    double* inv_w2 = reinterpret_cast<double*>(ws);
-    double* partial = reinterpret_cast<double*>(ws + pb_window_bytes());
-    long long* cnt = reinterpret_cast<long long*>(ws + pb_window_bytes() +
-                                                  align256((size_t)blocks * CGNN_PM_SUMS * sizeof(double)));
-    const int Mh = mesh / 2 + 1;
-    pb_window_kernel<<<(Mh + CGNN_BLOCK - 1) / CGNN_BLOCK, CGNN_BLOCK, 0, st>>>(mesh, order, inv_w2);
-    const int64_t mpf = (int64_t)mesh * mesh * Mh;
-    const double2* ca = reinterpret_cast<const double2*>(a);
-    const double2* cb = reinterpret_cast<const double2*>(b);
-    const double2* ca2 = reinterpret_cast<const double2*>(a2);
-    const double2* cb2 = reinterpret_cast<const double2*>(b2);
-    ps_for_frame_batches(frames, per_frame * CGNN_BLOCK, [&](int64_t f0, int64_t nf) {       // at least 4 frames each
-        const unsigned grid = (unsigned)(nf * per_frame);
-        const int64_t off = f0 * mpf;
-        double* part = partial + f0 * per_frame * CGNN_PM_SUMS;
-        long long* c = cnt + f0 * per_frame;
-#define CGNN_PM_LAUNCH(HAS_B, INTER)                                                                                     \
-    pm_partial_kernel<HAS_B, INTER><<<grid, CGNN_BLOCK, 0, st>>>(ca + off, HAS_B ? cb + off : nullptr,                  \
-                                                                 INTER ? ca2 + off : nullptr,                            \
-                                                                 (HAS_B && INTER) ? cb2 + off : nullptr, mesh, Mh, los,  \
-                                                                 mpf, perm, bin_start, num_bins, inv_w2, part, c)
-        if (cb && ca2) CGNN_PM_LAUNCH(true, true);
-        else if (cb) CGNN_PM_LAUNCH(true, false);
-        else if (ca2) CGNN_PM_LAUNCH(false, true);
-        else CGNN_PM_LAUNCH(false, false);
-#undef CGNN_PM_LAUNCH
-        const int64_t outs = nf * num_bins * (CGNN_PM_SUMS + 1);
-        pm_final_kernel<<<(unsigned)((outs + CGNN_BLOCK - 1) / CGNN_BLOCK), CGNN_BLOCK, 0, st>>>(
-            part, c, nf, num_bins, b != nullptr, sums + f0 * CGNN_PM_SUMS * num_bins,
-            reinterpret_cast<long long*>(modes) + f0 * num_bins);
-    });
-    return check_hip(hipGetLastError(), who);
+    return shell_sums(who, 3, a, b, a2, b2, frames, mesh, order, los, perm, bin_start, num_bins, modes, sums, workspace,
+                      workspace_bytes, stream);
 }
 
 }  // extern "C"

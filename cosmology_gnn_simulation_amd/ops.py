@@ -1372,6 +1372,50 @@ def weighted_field(pos: torch.Tensor, values: torch.Tensor, box_size: float, mes
         return _WeightedField.apply(pos, values, box_size, mesh, order, scale)
 
 
+def _power_sums(what: str, entry: str, rows: int, given, mesh, order, k_edges, los: Optional[int],
+                plan: Optional[PowerPlan]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`power_bins` (``los`` None) and :func:`power_multipoles`: the checks of ``mesh``, ``order``, ``k_edges``, the
+    transforms ``given`` (``(name, tensor or None)``, the first is ``delta_k``) and ``plan``, then the workspace,
+    ``modes`` and the nan-filled ``sums [T, rows, nb]``, and the timed call of ``entry``."""
+    mesh = check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in (0, 1, 2, 3):
+        raise ValueError(f"{what}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
+    e = check_power_edges(k_edges, what)
+    nb = len(e) - 1
+    delta_k = given[0][1]
+    shape = (mesh, mesh, mesh // 2 + 1)
+    for name, d in given:
+        if d is None:
+            continue
+        require_device(d, name)
+        if d.dtype != torch.complex128 or d.dim() not in (3, 4) or tuple(d.shape[-3:]) != shape:
+            raise CgnnError(f"{what}: {name} must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got {d.dtype} "
+                            f"{tuple(d.shape)}")
+        if d.shape != delta_k.shape:
+            raise CgnnError(f"{what}: {name} is {tuple(d.shape)}, delta_k {tuple(delta_k.shape)}")
+    _same_device(*(d for _, d in given))
+    if plan is None:
+        plan = PowerPlan.of(mesh, e, delta_k.device)
+    elif plan.mesh != mesh or plan.edges != tuple(e) or plan.perm.device != delta_k.device:
+        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
+    batched = delta_k.dim() == 4
+    data = [None if d is None else d.contiguous() for _, d in given]
+    a = data[0]
+    t = a.shape[0] if batched else 1
+    if t < 1:
+        raise CgnnError(f"{what}: no frames")
+    lib = _lib.load()
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(t, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    modes = torch.empty((t, nb), dtype=torch.int64, device=a.device)
+    sums = torch.full((t, rows, nb), float("nan"), dtype=torch.float64, device=a.device)
+    args = [a.data_ptr()] + [ptr(d) for d in data[1:]] + [t, mesh, int(order)] + ([] if los is None else [los])
+    with _timed(what, a.device):
+        check(getattr(lib, entry)(*args, plan.perm.data_ptr(), plan.bin_start.data_ptr(), nb, modes.data_ptr(),
+                                  sums.data_ptr(), ws.data_ptr(), ws_bytes, stream_ptr(a.device)), entry)
+    return (modes, sums) if batched else (modes[0], sums[0])
+
+
 def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b: Optional[torch.Tensor] = None,
                plan: Optional[PowerPlan] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Shell sums of the modes of ``delta_k = torch.fft.rfftn(delta)`` (``cgnn_power_bins``): complex128 ``[M, M, M/2 + 1]``
@@ -1385,43 +1429,8 @@ def power_bins(delta_k: torch.Tensor, mesh: int, order: int, k_edges, delta_k_b:
     bin edges in units of the fundamental frequency (host values; bin ``i`` holds ``fl32(k_edges[i]^2) <= n2 <
     fl32(k_edges[i+1]^2)``, ``n2 = 0`` never).  Every float64 addition has a fixed place: two calls give the same bits.
     ``plan``: a :class:`PowerPlan` of ``(mesh, k_edges)`` (default ``PowerPlan.of``).  No host synchronisation."""
-    what = "power_bins"
-    mesh = check_mesh(mesh, what)
-    if isinstance(order, bool) or order not in (0, 1, 2, 3):
-        raise ValueError(f"{what}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
-    e = check_power_edges(k_edges, what)
-    nb = len(e) - 1
-    shape = (mesh, mesh, mesh // 2 + 1)
-    for name, d in (("delta_k", delta_k), ("delta_k_b", delta_k_b)):
-        if d is None:
-            continue
-        require_device(d, name)
-        if d.dtype != torch.complex128 or d.dim() not in (3, 4) or tuple(d.shape[-3:]) != shape:
-            raise CgnnError(f"{what}: {name} must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got {d.dtype} "
-                            f"{tuple(d.shape)}")
-    if delta_k_b is not None and delta_k_b.shape != delta_k.shape:
-        raise CgnnError(f"{what}: delta_k_b is {tuple(delta_k_b.shape)}, delta_k {tuple(delta_k.shape)}")
-    _same_device(delta_k, delta_k_b)
-    if plan is None:
-        plan = PowerPlan.of(mesh, e, delta_k.device)
-    elif plan.mesh != mesh or plan.edges != tuple(e) or plan.perm.device != delta_k.device:
-        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
-    batched = delta_k.dim() == 4
-    a = delta_k.contiguous()
-    b = None if delta_k_b is None else delta_k_b.contiguous()
-    t = a.shape[0] if batched else 1
-    if t < 1:
-        raise CgnnError(f"{what}: no frames")
-    lib = _lib.load()
-    ws_bytes = lib.cgnn_power_bins_workspace_bytes(t, nb)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
-    modes = torch.empty((t, nb), dtype=torch.int64, device=a.device)
-    sums = torch.full((t, 4, nb), float("nan"), dtype=torch.float64, device=a.device)
-    with _timed(what, a.device):
-        check(lib.cgnn_power_bins(a.data_ptr(), ptr(b), t, mesh, int(order), plan.perm.data_ptr(),
-                                  plan.bin_start.data_ptr(), nb, modes.data_ptr(), sums.data_ptr(), ws.data_ptr(),
-                                  ws_bytes, stream_ptr(a.device)), "cgnn_power_bins")
-    return (modes, sums) if batched else (modes[0], sums[0])
+    return _power_sums("power_bins", "cgnn_power_bins", 4, (("delta_k", delta_k), ("delta_k_b", delta_k_b)), mesh, order,
+                       k_edges, None, plan)
 
 
 def check_los(los, who: str) -> int:
@@ -1512,48 +1521,13 @@ def power_multipoles(delta_k: torch.Tensor, mesh: int, order: int, k_edges, los:
     Without ``shifted`` rows 0, 3, 6, 9 and ``modes`` are :func:`power_bins`' rows 0-3 and modes bit for bit.  Two calls
     give the same bits.  No host synchronisation."""
     what = "power_multipoles"
-    mesh = check_mesh(mesh, what)
-    if isinstance(order, bool) or order not in (0, 1, 2, 3):
-        raise ValueError(f"{what}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
     los = check_los(los, what)
-    e = check_power_edges(k_edges, what)
-    nb = len(e) - 1
     if shifted_b is not None and (delta_k_b is None or shifted is None):
         raise ValueError(f"{what}: shifted_b goes with delta_k_b and shifted")
     if shifted is not None and delta_k_b is not None and shifted_b is None:
         raise ValueError(f"{what}: with delta_k_b and shifted, shifted_b must be given too")
-    shape = (mesh, mesh, mesh // 2 + 1)
     given = (("delta_k", delta_k), ("delta_k_b", delta_k_b), ("shifted", shifted), ("shifted_b", shifted_b))
-    for name, d in given:
-        if d is None:
-            continue
-        require_device(d, name)
-        if d.dtype != torch.complex128 or d.dim() not in (3, 4) or tuple(d.shape[-3:]) != shape:
-            raise CgnnError(f"{what}: {name} must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got {d.dtype} "
-                            f"{tuple(d.shape)}")
-        if d.shape != delta_k.shape:
-            raise CgnnError(f"{what}: {name} is {tuple(d.shape)}, delta_k {tuple(delta_k.shape)}")
-    _same_device(delta_k, delta_k_b, shifted, shifted_b)
-    if plan is None:
-        plan = PowerPlan.of(mesh, e, delta_k.device)
-    elif plan.mesh != mesh or plan.edges != tuple(e) or plan.perm.device != delta_k.device:
-        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
-    batched = delta_k.dim() == 4
-    a, b, a2, b2 = (None if d is None else d.contiguous() for _, d in given)
-    t = a.shape[0] if batched else 1
-    if t < 1:
-        raise CgnnError(f"{what}: no frames")
-    lib = _lib.load()
-    ws_bytes = lib.cgnn_power_multipoles_workspace_bytes(t, nb)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
-    modes = torch.empty((t, nb), dtype=torch.int64, device=a.device)
-    sums = torch.full((t, _lib.POWER_MULTIPOLE_SUMS, nb), float("nan"), dtype=torch.float64, device=a.device)
-    with _timed(what, a.device):
-        check(lib.cgnn_power_multipoles(a.data_ptr(), ptr(b), ptr(a2), ptr(b2), t, mesh, int(order), los,
-                                        plan.perm.data_ptr(), plan.bin_start.data_ptr(), nb, modes.data_ptr(),
-                                        sums.data_ptr(), ws.data_ptr(), ws_bytes, stream_ptr(a.device)),
-              "cgnn_power_multipoles")
-    return (modes, sums) if batched else (modes[0], sums[0])
+    return _power_sums(what, "cgnn_power_multipoles", _lib.POWER_MULTIPOLE_SUMS, given, mesh, order, k_edges, los, plan)
 
 
 def check_linking_length(linking_length, box_size: float, who: str) -> float:

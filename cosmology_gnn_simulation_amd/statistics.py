@@ -149,6 +149,25 @@ def default_k_edges(mesh: int) -> torch.Tensor:
     return 0.5 + torch.arange(0, mesh // 2 + 1, dtype=torch.float64)
 
 
+def _sums_on_host(what: str, modes, sums, rows: int, box_size: float, mesh: int, k_edges):
+    """The opening of :func:`spectra_from_sums` and :func:`multipoles_from_sums`: the checked arguments as ``(box, k,
+    modes, sums, count, norm)``: ``k`` the edges times ``2 pi / L``, ``modes [..., nb]`` and ``sums [..., rows, nb]`` on the
+    CPU, ``count`` the modes in float64 with ``nan`` for an empty bin, ``norm = L^3 / M^6``."""
+    mesh = ops.check_mesh(mesh, what)
+    box = float(box_size)
+    if not (box > 0.0 and math.isfinite(box)):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    k = torch.tensor(ops.check_power_edges(k_edges, what), dtype=torch.float64) * (2.0 * math.pi / box)
+    modes = torch.as_tensor(modes).detach().to(device="cpu", dtype=torch.int64)
+    sums = torch.as_tensor(sums).detach().to(device="cpu", dtype=torch.float64)
+    nb = k.numel() - 1
+    if modes.shape[-1] != nb or sums.shape[-2:] != (rows, nb) or sums.shape[:-2] != modes.shape[:-1]:
+        raise ValueError(f"{what}: modes {tuple(modes.shape)} and sums {tuple(sums.shape)} do not fit {nb} bins")
+    count = modes.to(torch.float64)
+    count = torch.where(modes > 0, count, torch.full_like(count, float("nan")))
+    return box, k, modes, sums, count, box ** 3 / float(mesh) ** 6
+
+
 def spectra_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: float, mesh: int, k_edges,
                       subtract_shot_noise: bool = True) -> Dict:
     """Spectra from the shell sums of ``ops.power_bins``, on the host in float64 (``modes [..., nb]`` int64, ``sums
@@ -167,20 +186,7 @@ def spectra_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: float
       negative (shot-noise dominated bins) or ``power_b`` zero.
 
     A bin without modes gives ``nan`` everywhere."""
-    what = "spectra_from_sums"
-    mesh = ops.check_mesh(mesh, what)
-    box = float(box_size)
-    if not (box > 0.0 and math.isfinite(box)):
-        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
-    k = torch.tensor(ops.check_power_edges(k_edges, what), dtype=torch.float64) * (2.0 * math.pi / box)
-    modes = torch.as_tensor(modes).detach().to(device="cpu", dtype=torch.int64)
-    sums = torch.as_tensor(sums).detach().to(device="cpu", dtype=torch.float64)
-    nb = k.numel() - 1
-    if modes.shape[-1] != nb or sums.shape[-2:] != (4, nb) or sums.shape[:-2] != modes.shape[:-1]:
-        raise ValueError(f"{what}: modes {tuple(modes.shape)} and sums {tuple(sums.shape)} do not fit {nb} bins")
-    count = modes.to(torch.float64)
-    count = torch.where(modes > 0, count, torch.full_like(count, float("nan")))
-    norm = box ** 3 / float(mesh) ** 6
+    box, k, modes, sums, count, norm = _sums_on_host("spectra_from_sums", modes, sums, 4, box_size, mesh, k_edges)
 
     def spectrum(row):
         return norm * sums[..., row, :] / count
@@ -240,23 +246,42 @@ def _contrast_modes(pos: torch.Tensor, box_size: float, mesh: int, order: int) -
     return torch.fft.rfftn(delta, dim=(-3, -2, -1))
 
 
-def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int):
-    """``ops.power_bins`` of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b [F, N_b, 3]``):
-    device tensors ``modes [F, nb]``, ``sums [F, 4, nb]``.  Frames go through in chunks whose meshes fit the free
-    device memory: per frame and set ``8 M^3`` (the contrast) + ``16 M^2 (M/2 + 1)`` (its transform) + ``8 M^3`` (the
-    int64 mesh) bytes and as much again for the FFT's own scratch, and per frame the workspace of ``cgnn_power_bins``
-    (``nb * 64`` slices of four float64 sums and a count) and its outputs (``5 nb`` values)."""
+def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int,
+                los: Optional[int] = None, interlace: bool = False):
+    """The shell sums of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b [F, N_b, 3]``) as device
+    tensors ``modes [F, nb]``, ``sums [F, rows, nb]``: ``ops.power_bins`` (4 rows) when ``los`` is None, else
+    ``ops.power_multipoles`` (12 rows) about ``los``, from an interlaced pair of meshes with ``interlace``.  Frames go
+    through in chunks whose meshes fit the free device memory: per frame, set and mesh of the interlaced pair ``8 M^3``
+    (the contrast) + ``16 M^2 (M/2 + 1)`` (its transform) + ``8 M^3`` (the int64 mesh) bytes and as much again for the
+    FFT's own scratch, and per frame the workspace (``nb * 64`` slices of ``rows`` float64 sums and a count) and the
+    outputs (``(rows + 1) nb`` values).  The int64 mesh and the contrast of one transform are gone before the next is
+    made, and the transforms of a chunk before the next chunk."""
     from .training import free_device_bytes
+    assert los is not None or not interlace       # no four-row interlaced entry: _interlaced_shell_sums selects the rows
     n_frames, nb = pos_a.shape[0], len(k_edges) - 1
-    per_frame = (16 * mesh ** 3 + 16 * mesh * mesh * (mesh // 2 + 1)) * (1 if pos_b is None else 2) * 2 \
-        + nb * 64 * 5 * 8 + nb * 5 * 8
+    values = 5 if los is None else _lib.POWER_MULTIPOLE_SUMS + 1
+    meshes = (1 if pos_b is None else 2) * (2 if interlace else 1)
+    per_frame = (16 * mesh ** 3 + 16 * mesh * mesh * (mesh // 2 + 1)) * meshes * 2 + nb * 64 * values * 8 + nb * values * 8
     chunk = max(1, min(n_frames, free_device_bytes(pos_a.device) // per_frame))
     plan = ops.PowerPlan.of(mesh, k_edges, pos_a.device)
+
+    def transforms(pos):
+        if pos is None:
+            return None, None
+        first = _contrast_modes(pos, box_size, mesh, order)
+        if not interlace:
+            return first, None
+        return first, _contrast_modes(ops.interlace_shift(pos, box_size, mesh), box_size, mesh, order)
+
     modes, sums = [], []
     for f0 in range(0, n_frames, chunk):
-        a = _contrast_modes(pos_a[f0:f0 + chunk], box_size, mesh, order)
-        b = None if pos_b is None else _contrast_modes(pos_b[f0:f0 + chunk], box_size, mesh, order)
-        m, s = ops.power_bins(a, mesh, order, k_edges, b, plan)
+        a, a2 = transforms(pos_a[f0:f0 + chunk])
+        b, b2 = transforms(None if pos_b is None else pos_b[f0:f0 + chunk])
+        if los is None:
+            m, s = ops.power_bins(a, mesh, order, k_edges, b, plan)
+        else:
+            m, s = ops.power_multipoles(a, mesh, order, k_edges, los, b, a2, b2, plan)
+        del a, a2, b, b2
         modes.append(m)
         sums.append(s)
     return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
@@ -273,7 +298,7 @@ def _to_host(modes: torch.Tensor, sums: torch.Tensor, extra: Optional[torch.Tens
 
 def _interlaced_shell_sums(pos_a, pos_b, box_size: float, mesh: int, k_edges, order: int):
     """:func:`_shell_sums` from an interlaced pair of meshes: rows 0, 3, 6 and 9 of ``ops.power_multipoles``."""
-    modes, sums = _multipole_sums(pos_a, pos_b, box_size, mesh, k_edges, order, 2, True)
+    modes, sums = _shell_sums(pos_a, pos_b, box_size, mesh, k_edges, order, 2, True)
     return modes, torch.stack([sums[:, row] for row in (0, 3, 6, 9)], dim=1)
 
 
@@ -356,20 +381,8 @@ def multipoles_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: fl
     and with a second set (``n_b`` is not None) ``power_b_0/2/4`` (shot noise ``L^3 / n_b``), ``cross_0/2/4`` (no shot
     noise) and the monopole's ``r`` and ``transfer``, defined as in :func:`spectra_from_sums`.  A bin without modes gives
     ``nan`` everywhere."""
-    what = "multipoles_from_sums"
-    mesh = ops.check_mesh(mesh, what)
-    box = float(box_size)
-    if not (box > 0.0 and math.isfinite(box)):
-        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
-    k = torch.tensor(ops.check_power_edges(k_edges, what), dtype=torch.float64) * (2.0 * math.pi / box)
-    modes = torch.as_tensor(modes).detach().to(device="cpu", dtype=torch.int64)
-    sums = torch.as_tensor(sums).detach().to(device="cpu", dtype=torch.float64)
-    nb, rows = k.numel() - 1, _lib.POWER_MULTIPOLE_SUMS
-    if modes.shape[-1] != nb or sums.shape[-2:] != (rows, nb) or sums.shape[:-2] != modes.shape[:-1]:
-        raise ValueError(f"{what}: modes {tuple(modes.shape)} and sums {tuple(sums.shape)} do not fit {nb} bins")
-    count = modes.to(torch.float64)
-    count = torch.where(modes > 0, count, torch.full_like(count, float("nan")))
-    norm = box ** 3 / float(mesh) ** 6
+    box, k, modes, sums, count, norm = _sums_on_host("multipoles_from_sums", modes, sums, _lib.POWER_MULTIPOLE_SUMS,
+                                                     box_size, mesh, k_edges)
 
     def multipole(first_row, i):
         p = norm * sums[..., first_row + i, :] / count
@@ -386,40 +399,6 @@ def multipoles_from_sums(modes, sums, n_a: int, n_b: Optional[int], box_size: fl
         out["r"] = out["cross_0"] / torch.sqrt(multipole(0, 0) * multipole(3, 0))
         out["transfer"] = torch.sqrt(out["power_0"] / out["power_b_0"])
     return out
-
-
-def _multipole_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: float, mesh: int, k_edges, order: int,
-                    los: int, interlace: bool):
-    """``ops.power_multipoles`` of the density contrast of every frame of ``pos_a [F, N, 3]`` (and ``pos_b``): device
-    tensors ``modes [F, nb]``, ``sums [F, 12, nb]``.  Frames go through in chunks whose meshes fit the free device memory:
-    per frame, set and mesh of the interlaced pair what :func:`_shell_sums` counts (``8 M^3`` for the contrast, ``16 M^2
-    (M/2 + 1)`` for its transform, ``8 M^3`` for the int64 mesh, as much again for the FFT's scratch), and per frame the
-    workspace (``nb * 64`` slices of twelve sums and a count) and the outputs (``13 nb`` values).  The int64 mesh and the
-    contrast of one transform are gone before the next is made."""
-    from .training import free_device_bytes
-    n_frames, nb = pos_a.shape[0], len(k_edges) - 1
-    meshes = (1 if pos_b is None else 2) * (2 if interlace else 1)
-    per_frame = (16 * mesh ** 3 + 16 * mesh * mesh * (mesh // 2 + 1)) * meshes * 2 + nb * 64 * 13 * 8 + nb * 13 * 8
-    chunk = max(1, min(n_frames, free_device_bytes(pos_a.device) // per_frame))
-    plan = ops.PowerPlan.of(mesh, k_edges, pos_a.device)
-
-    def transforms(pos):
-        if pos is None:
-            return None, None
-        first = _contrast_modes(pos, box_size, mesh, order)
-        if not interlace:
-            return first, None
-        return first, _contrast_modes(ops.interlace_shift(pos, box_size, mesh), box_size, mesh, order)
-
-    modes, sums = [], []
-    for f0 in range(0, n_frames, chunk):
-        a, a2 = transforms(pos_a[f0:f0 + chunk])
-        b, b2 = transforms(None if pos_b is None else pos_b[f0:f0 + chunk])
-        m, s = ops.power_multipoles(a, mesh, order, k_edges, los, b, a2, b2, plan)
-        del a, a2, b, b2
-        modes.append(m)
-        sums.append(s)
-    return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
 
 
 def _check_multipole_arguments(what: str, box_size, mesh, k_edges, order, los, dt, velocity_scale, moving: bool):
@@ -470,7 +449,7 @@ def power_multipoles(pos: torch.Tensor, box_size: float, mesh: int, pos_prev: Op
             frames = ops.redshift_positions(frames, _f32_frames(prev, name + "_prev", what).to(frames.device), dt,
                                             box_size, los, velocity_scale)
         sets.append(frames)
-    modes, sums = _to_host(*_multipole_sums(sets[0], sets[1], box_size, mesh, k_edges, order, los, bool(interlace)))
+    modes, sums = _to_host(*_shell_sums(sets[0], sets[1], box_size, mesh, k_edges, order, los, bool(interlace)))
     if pos.dim() == 2:
         modes, sums = modes[0], sums[0]
     return multipoles_from_sums(modes, sums, sets[0].shape[1], None if sets[1] is None else sets[1].shape[1], box_size,
@@ -514,7 +493,7 @@ def rollout_redshift_spectra(rollout_data: Dict[str, torch.Tensor], ground_truth
         sides.append(ops.redshift_positions(_f32_frames(cur.index_select(0, at), "Coordinates", what),
                                             _f32_frames(source.index_select(0, prev), "Coordinates", what), dt, box_size,
                                             los, velocity_scale))
-    modes, sums = _multipole_sums(sides[0], sides[1], box_size, mesh, k_edges, order, los, bool(interlace))
+    modes, sums = _shell_sums(sides[0], sides[1], box_size, mesh, k_edges, order, los, bool(interlace))
     if len(rows) != nf:        # frame 0: nan sums; the mode counts are every frame's
         block = torch.full((nf, _lib.POWER_MULTIPOLE_SUMS, nb), float("nan"), dtype=torch.float64, device=dev)
         block.index_copy_(0, at, sums)

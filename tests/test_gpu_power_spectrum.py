@@ -211,6 +211,44 @@ def test_power_bins_refuses_a_plan_of_another_mesh_or_other_edges():
         ops.power_bins(ak.to(torch.complex64), 16, 2, edges)
 
 
+def test_without_b_the_c_entry_leaves_rows_1_and_2_alone_and_refuses_by_itself():
+    lib = _lib.load()
+    mesh, nb, frames = 8, 4, 2
+    edges = psc.default_k_edges(mesh)
+    plan = ops.PowerPlan.of(mesh, edges, DEV)
+    a, other = (torch.fft.rfftn(_dev(d), dim=(-3, -2, -1)) for d in _contrasts(mesh))
+    assert a.shape[0] == frames and len(edges) - 1 == nb
+    ws_bytes = lib.cgnn_power_bins_workspace_bytes(frames, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+    canary = -12345.0
+    modes = torch.full((frames, nb), -7, dtype=torch.int64, device=DEV)
+    sums = torch.full((frames, 4, nb), canary, dtype=torch.float64, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(b=None, m=mesh, order=2, wb=ws_bytes, n=nb):
+        return lib.cgnn_power_bins(a.data_ptr(), b, frames, m, order, plan.perm.data_ptr(), plan.bin_start.data_ptr(), n,
+                                   modes.data_ptr(), sums.data_ptr(), ws.data_ptr(), wb, st)
+
+    # with real buffers of the sizes named: were a refusal ever to come after a launch, nothing would fault
+    for kw in (dict(order=4), dict(order=-1), dict(n=0), dict(n=257), dict(wb=ws_bytes - 1), dict(b=a.data_ptr() + 8),
+               dict(m=1)):
+        assert call(**kw) != 0, kw
+    torch.cuda.synchronize()
+    assert bool((sums == canary).all()) and bool((modes == -7).all())
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert bool((sums[:, 1:3] == canary).all())
+    assert not bool((sums[:, [0, 3]] == canary).any()) and not bool((modes == -7).any())
+    want_m, want_s = ops.power_bins(a, mesh, 2, edges)
+    assert torch.equal(modes, want_m) and torch.equal(sums[:, [0, 3]], want_s[:, [0, 3]])
+    sums.fill_(canary)
+    assert call(b=other.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert not bool((sums == canary).any())
+    want_m, want_s = ops.power_bins(a, mesh, 2, edges, other)
+    assert torch.equal(modes, want_m) and torch.equal(sums, want_s)
+
+
 # ---- end to end --------------------------------------------------------------------------------------------------------
 
 N, MESH, FRAMES = 1000, 16, 4
