@@ -21,6 +21,7 @@ F32, BF16, BF16_N16, F32X3, F32X3_N16, F16X2_N16, F16X2 = 0, 1, 2, 3, 4, 5, 6  #
 N16_NODE = (F32X3_N16, F16X2_N16)       # node-kernel packings whose epilogue fuses the next round's projections
 P_F32, P_BF16_S32, P_BF16_S16, P_F16_S32 = 0, 1, 2, 3  # cgnn_ptable
 STREAM_FOLDED = 1  # cgnn_edge_stream_run_w8 flags: CGNN_STREAM_FOLDED
+STREAM_TRAVELLING = 4  # ... CGNN_STREAM_TRAVELLING
 LDS_WEIGHT_BUDGET = 152 * 1024           # CGNN_LDS_WEIGHT_BUDGET in csrc/mlp_device.hpp
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "bf16_n16": BF16_N16,
               "fp32x3": F32X3, "f32x3": F32X3, "fp32x3_n16": F32X3_N16, "fp16x2_n16": F16X2_N16,
@@ -38,7 +39,7 @@ EXPORTS = (
     "cgnn_mlp_backward", "cgnn_weight_grad", "cgnn_weight_grad_x3_workspace_bytes", "cgnn_weight_grad_x3",
     "cgnn_col_dot", "cgnn_col_dot2", "cgnn_col_dot_workspace_bytes", "cgnn_col_dot_ordered", "cgnn_weight_grad_workspace_bytes", "cgnn_weight_grad_ordered", "cgnn_csr_workspace_bytes", "cgnn_csr_build",
     "cgnn_aggregate_csr", "cgnn_aggregate_csr_add", "cgnn_edge_stream", "cgnn_edge_stream_image_bytes", "cgnn_edge_stream_image_build",
-    "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
+    "cgnn_edge_stream_run", "cgnn_edge_stream_w8_supported", "cgnn_edge_stream_w8_vectors_resident", "cgnn_edge_stream_image_build_w8", "cgnn_edge_stream_run_w8", "cgnn_aggregate_plan_bytes", "cgnn_aggregate_plan_build", "cgnn_aggregate_planned", "cgnn_aggregate_planned_rows",
     "cgnn_aggregate_planned_form", "cgnn_edge_mlp_backward", "cgnn_linear2_rows", "cgnn_halo_return_add", "cgnn_window_features_rows",
     "cgnn_rollout_integrate", "cgnn_frame_unpack", "cgnn_training_sample",
     "cgnn_balanced_planes_workspace_bytes", "cgnn_balanced_planes", "cgnn_tile_classify",
@@ -138,6 +139,7 @@ def load() -> C.CDLL:
     lib.cgnn_edge_stream_image_build.argtypes = [C.POINTER(Mlp), i32, C.POINTER(Mlp), i32, vp, sz, vp]
     lib.cgnn_edge_stream_run.argtypes = [vp, sz, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp]
     lib.cgnn_edge_stream_w8_supported.argtypes = [i32, i32, i32]
+    lib.cgnn_edge_stream_w8_vectors_resident.argtypes = [i32, i32, i32, i32]
     lib.cgnn_edge_stream_image_build_w8.argtypes = [C.POINTER(Mlp), i32, C.POINTER(Mlp), i32, vp, sz, vp]
     lib.cgnn_edge_stream_run_w8.argtypes = [vp, sz, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.cgnn_aggregate.argtypes = [vp, i32, vp, vp, i64, i32, i64, i32, vp, vp]

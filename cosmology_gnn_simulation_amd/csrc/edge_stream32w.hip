@@ -38,24 +38,44 @@ namespace cgnn {
 #define CGNN_IC(x) std::integral_constant<int, (x)> {}
 #include "w8_dev.hpp"      // the schedule constants at their shipped values; cycle stamps and timing-only ablations of developer builds
 
-template <int DT>
+// Two forms of the ring (RESV).  Travelling (false): a slot holds a whole image chunk, weights and vectors (next bias,
+// gamma, beta), and LayerNorm's vectors are copied aside before their slot is refilled.  Resident (true): the workgroup's
+// prologue copies every vector the launch reads into a table behind the staging areas, once; a slot holds the 32 KiB of
+// weights only (four pieces per wave and step instead of five, none of them a surplus repeat) and nothing is copied aside.
+// The image is the same (chunk c at c * IMG_STRIDE); the table's size depends on the launch (w8_table_rows).
+template <int DT, bool RESV = false>
 struct W8Geom {
     typedef S32Geom<DT> G;
     static constexpr int D = G::D, KS = G::KS;
-    static constexpr unsigned STRIDE = G::STRIDE, VEC_OFF = G::VEC_OFF;
-    static constexpr int PIECES = (int)(STRIDE / 1024u);                           // 1-KiB LDS-DMA instructions per chunk
+    static constexpr unsigned IMG_STRIDE = G::STRIDE, VEC_OFF = G::VEC_OFF;
+    static constexpr unsigned STRIDE = RESV ? G::W_BYTES : G::STRIDE;              // of a slot in LDS
+    static constexpr int PIECES = (int)((RESV || w8dev::ABL_RING4 ? G::W_BYTES : G::STRIDE) / 1024u);   // 1-KiB LDS-DMA instructions per chunk
     static constexpr int NP = (PIECES + CGNN_W8_WAVES - 1) / CGNN_W8_WAVES;        // ... per wave
     static constexpr unsigned LNBUF_OFF = CGNN_W8_SLOTS * STRIDE;                  // two (gamma | beta) buffers behind the ring
-    static constexpr unsigned LNBUF_BYTES = 2u * D * 4u;
+    static constexpr unsigned LNBUF_BYTES = RESV ? 0u : 2u * D * 4u;
     static constexpr unsigned PDST_OFF = LNBUF_OFF + 2u * LNBUF_BYTES;           // per wave: the tile's receiver P rows (<= 4 rows)
     static constexpr unsigned PDST_ROW = 256u + 16u;                             // a receiver's row, padded by one 16-byte bank group:
                                                                                  // the (<= 4) rows a read touches start in different ones
     static constexpr unsigned PDST_BYTES = 4u * PDST_ROW;
     static constexpr unsigned PSST_OFF = PDST_OFF + CGNN_W8_WAVES * PDST_BYTES;  // per wave: half of every sender half-row of the tile
     static constexpr unsigned PSST_BYTES = 64u * (unsigned)D / 2u;               // 64 lines x D / 2 bytes (latent 128: 4 KiB)
-    static constexpr unsigned LDS = PSST_OFF + CGNN_W8_WAVES * PSST_BYTES;
+    static constexpr unsigned LDS = PSST_OFF + CGNN_W8_WAVES * PSST_BYTES;       // the fixed part
     static_assert(LDS <= 160u * 1024u, "LDS budget");
+    // resident form: rows of D floats behind the fixed part (which keeps every other offset a compile-time constant)
+    static constexpr unsigned TABLE_OFF = LDS, TABLE_ROW = (unsigned)D * 4u;
+    static constexpr unsigned TABLE_MAX = RESV ? 160u * 1024u - LDS : 0u;
 };
+
+// Rows of the resident form's vector table, in this order:
+//   chunks      row c = vector 0 of chunk c, the bias that step c reads (the NEXT layer's: the image stores it one chunk
+//               early).  A pass's last step reads no bias, so with an encoder the row of its last chunk (nh) carries the
+//               encoder's own first bias (vector 1 of chunk 0) instead;
+//   passes      gamma of the encoder's and of every round's LayerNorm (vector 1 of the pass's last chunk);
+//   1 or 2      the betas a folded image still adds: the encoder's, then the last round's (vector 2 of those chunks).
+static inline int64_t w8_table_rows(int nh, int rounds, bool has_encoder) {
+    const int64_t passes = (int64_t)rounds + (has_encoder ? 1 : 0);
+    return passes * (nh + 1) + passes + (has_encoder ? 2 : 1);
+}
 
 // ---- the ring -------------------------------------------------------------------------------------------------------
 // Three slots, one barrier per ring step ("interval").  In interval g waves 0-3 compute chunk g out of slot g % 3 and
@@ -68,17 +88,19 @@ struct W8Geom {
 // Every wave issues NP pieces per chunk; where 8 NP exceeds the chunk's pieces the surplus ones repeat an earlier
 // piece (same bytes to the same place), which keeps every wave's operation count, and so every wait count, the same.
 // (Measured and dropped: skipping the surplus pieces with a wave-uniform branch -- control flow inside the MFMA blocks
-// cost 173 spilled registers and a 2.7 x slower kernel.)
+// cost 173 spilled registers and a 2.7 x slower kernel.)  The resident form has 32 pieces per chunk, four per wave, and
+// no surplus; its source offsets still step by the image's chunk stride.
 template <class W, int LAG>
 struct RingW {
     const char* image;
     int count;           // chunks per tile
     int wave, lane;
     int slot;            // of this wave's current step
+    int step;            // chunk of this wave's current step (the resident form's table row)
     int dma_chunk, dma_slot;
     CGNN_W8_STAMP_MEMBER
     __device__ __forceinline__ RingW(const char* img, int cnt, int w, int l)
-        : image(img), count(cnt), wave(w), lane(l), slot(0), dma_chunk(0), dma_slot(0) {}
+        : image(img), count(cnt), wave(w), lane(l), slot(0), step(0), dma_chunk(0), dma_slot(0) {}
     __device__ __forceinline__ unsigned lds0() const { return (unsigned)(uintptr_t)(LdsWeightPtr)(cgnn_smem); }
     __device__ __forceinline__ unsigned base() const { return lds0() + (unsigned)slot * W::STRIDE; }
     __device__ __forceinline__ unsigned base_next() const {
@@ -86,19 +108,27 @@ struct RingW {
     }
     __device__ __forceinline__ unsigned vec_addr() const { return base() + W::VEC_OFF; }
     __device__ __forceinline__ unsigned lnbuf(int which) const { return lds0() + W::LNBUF_OFF + (unsigned)which * W::LNBUF_BYTES; }
-    __device__ __forceinline__ void piece(int i) {
+    __device__ __forceinline__ unsigned table_row(int row) const { return lds0() + W::TABLE_OFF + (unsigned)row * W::TABLE_ROW; }
+    // 1-KiB piece idx of image chunk `chunk` -> the same place of slot `to`
+    __device__ __forceinline__ void fetch(int idx, int chunk, int to) {
         asm volatile("" ::: "memory");
 #if defined(__HIP_DEVICE_COMPILE__)      // (the host pass of hipcc does not know the buffer builtins)
-        int idx = wave + CGNN_W8_WAVES * i;
-        if (idx >= W::PIECES) idx -= CGNN_W8_WAVES;
         const unsigned off = (unsigned)idx * 1024u;
-        char* dst = cgnn_smem + (unsigned)dma_slot * W::STRIDE + off;
+        char* dst = cgnn_smem + (unsigned)to * W::STRIDE + off;
         const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(image), 0, (int)((unsigned)count * W::STRIDE), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(image), 0, (int)((unsigned)count * W::IMG_STRIDE), 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsVoidPtrG)dst, 16, (unsigned)lane * 16u,
-                                                 (unsigned)dma_chunk * W::STRIDE + off, 0, 0);
+                                                 (unsigned)chunk * W::IMG_STRIDE + off, 0, 0);
+#else
+        (void)idx, (void)chunk, (void)to;
 #endif
         asm volatile("" ::: "memory");
+    }
+    __device__ __forceinline__ void piece(int i) {
+        int idx = wave + CGNN_W8_WAVES * i;
+        if constexpr (W::PIECES % CGNN_W8_WAVES != 0)
+            if (idx >= W::PIECES) idx -= CGNN_W8_WAVES;
+        fetch(idx, dma_chunk, dma_slot);
     }
     __device__ __forceinline__ void dma_done() {
         dma_chunk = dma_chunk + 1 == count ? 0 : dma_chunk + 1;
@@ -108,6 +138,9 @@ struct RingW {
         for (int c = 0; c < CGNN_W8_SLOTS - 1 - LAG; ++c) {
             for (int i = 0; i < W::NP; ++i) piece(i);
             dma_done();
+        }
+        if constexpr (w8dev::ABL_RING4) {      // (timing-only: every slot's vector part gets plausible numbers, once)
+            for (int s = 0; s < CGNN_W8_SLOTS; ++s) fetch(W::PIECES + (wave & 3), count - 1, s);
         }
         CGNN_S32_VMCNT(0);
         __builtin_amdgcn_s_barrier();
@@ -127,7 +160,10 @@ struct RingW {
         asm volatile("" ::: "memory");
         CGNN_W8_STAMP(K0 + 2);
     }
-    __device__ __forceinline__ void advance() { slot = slot + 1 == CGNN_W8_SLOTS ? 0 : slot + 1; }
+    __device__ __forceinline__ void advance() {
+        slot = slot + 1 == CGNN_W8_SLOTS ? 0 : slot + 1;
+        step = step + 1 == count ? 0 : step + 1;
+    }
     // an interval in which this wave computes nothing (the lagging waves' first, the leading waves' last)
     __device__ __forceinline__ void idle_interval() {
         for (int i = 0; i < W::NP; ++i) piece(i);
@@ -239,7 +275,8 @@ __device__ __forceinline__ void bias_rowsw(f32x16 (&acc)[DT], unsigned vec_addr,
 //                deviations; the centred two-pass form costs 64 more vector instructions per tile and round);
 //   ln_affine_w  slices [K0, K1) of 2 DT: eight values each (registers 8 s .. 8 s + 7 of row tile t, k = 2 t + s):
 //                RES: ev += y (graph_network.py:182)   !RES: ev = y (the encoder, :57)   and the bf16 pack of the new ev
-//                as k-step k of the next layer-0 operand.  gamma at lnv, beta at lnv + 4 D (LDS byte address).
+//                as k-step k of the next layer-0 operand.  gamma at lnv, beta at lnb (LDS byte addresses; travelling
+//                form: lnb = lnv + 4 D).
 struct LnStats {
     float rstd, nmr;      // normalised value = x * rstd + nmr
 };
@@ -282,16 +319,16 @@ __device__ __forceinline__ LnStats ln_stats_finish(const LnSums& a) {
 // hand-issued asm reads with early-clobber register quads cost this kernel 60-110 spilled registers); the scheduling
 // barrier per slice keeps the compiler from hoisting every slice's reads to the top (128 registers at latent 128).
 template <bool RES, bool BETA, bool ZM, int DT, int K0, int K1>
-__device__ __forceinline__ void ln_affine_w(const f32x16 (&acc)[DT], f32x16 (&ev)[DT], bf16x8 (&in)[2 * DT], unsigned lnv, int h,
-                                            LnStats st) {
+__device__ __forceinline__ void ln_affine_w(const f32x16 (&acc)[DT], f32x16 (&ev)[DT], bf16x8 (&in)[2 * DT], unsigned lnv, unsigned lnb,
+                                            int h, LnStats st) {
     if constexpr (K1 > K0) {
-        constexpr int D = 32 * DT;
-        const LdsVecPtr gp = (LdsVecPtr)(uintptr_t)lnv + 4 * h;
+        const LdsVecPtr gp = (LdsVecPtr)(uintptr_t)lnv + 4 * h, bp = (LdsVecPtr)(uintptr_t)lnb + 4 * h;
+        (void)bp;
         f32x4 gm[2][2], bt[2][2];
 #pragma unroll
         for (int gg = 0; gg < 2; ++gg) {
             gm[K0 & 1][gg] = *(LdsVec4Ptr)(gp + 32 * (K0 >> 1) + 8 * (2 * (K0 & 1) + gg));
-            if constexpr (BETA) bt[K0 & 1][gg] = *(LdsVec4Ptr)(gp + D + 32 * (K0 >> 1) + 8 * (2 * (K0 & 1) + gg));
+            if constexpr (BETA) bt[K0 & 1][gg] = *(LdsVec4Ptr)(bp + 32 * (K0 >> 1) + 8 * (2 * (K0 & 1) + gg));
         }
         __builtin_amdgcn_sched_barrier(0);
         static_for_each([&](auto kc) __attribute__((always_inline)) {
@@ -301,7 +338,7 @@ __device__ __forceinline__ void ln_affine_w(const f32x16 (&acc)[DT], f32x16 (&ev
 #pragma unroll
                 for (int gg = 0; gg < 2; ++gg) {
                     gm[nxt][gg] = *(LdsVec4Ptr)(gp + 32 * t1 + 8 * (2 * s1 + gg));
-                    if constexpr (BETA) bt[nxt][gg] = *(LdsVec4Ptr)(gp + D + 32 * t1 + 8 * (2 * s1 + gg));
+                    if constexpr (BETA) bt[nxt][gg] = *(LdsVec4Ptr)(bp + 32 * t1 + 8 * (2 * s1 + gg));
                 }
             }
             if constexpr (w8dev::ABL_LN) {      // (timing-only: pack and add, keeps the MFMAs alive)
@@ -395,20 +432,22 @@ __device__ __forceinline__ void addp_rows(f32x16 (&acc)[DT], const bf16x8 (&ps)[
 
 // ---- the kernel -----------------------------------------------------------------------------------------------------
 // One wave, one tile, per pass (= the encoder, or one round), NH hidden layers:
-//   first step   the previous pass's LayerNorm affine part (its vectors were copied aside before the barrier) with the
+//   first step   the previous pass's LayerNorm affine part (its vectors were copied aside before the barrier, or sit in the table) with the
 //                second half of the sender rows in flight; selector MFMAs (Ps[src] + Pd[dst] -> accumulators; encoder:
 //                bias); layer 0: 32 MFMAs, each finished row tile packed (ReLU) into the next operand under the next
 //                rows' MFMAs
 //   hidden steps bias, MFMAs, pack
 //   last step    bias, MFMAs (first half of the next pass's sender rows and the receiver rows requested from their first
-//                slots), LayerNorm statistics, (waves 0-3: LayerNorm vectors -> side buffer)
+//                slots), LayerNorm statistics, (travelling form, waves 0-3: LayerNorm vectors -> side buffer)
+// RESV: the resident form of the ring (W8Geom): every bias, gamma and beta comes from the workgroup's vector table.
 // Ring pieces go out in the first MFMA slots of every step; every step ends with RingW::interval_end.
-template <int DT, int NH, bool ENC, int LAG, bool PF16, bool FOLD>
+template <int DT, int NH, bool ENC, int LAG, bool PF16, bool FOLD, bool RESV = false>
 __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
     S32Args a, const __bf16* __restrict__ ps_all, const __bf16* __restrict__ pd_all, int64_t round_stride,
     const int32_t* __restrict__ src, const int32_t* __restrict__ dst, int64_t num_edges, const float* e_in, float* e_out,
     const float* __restrict__ attr, int ld_attr, int seg_k) {
-    typedef W8Geom<DT> W;
+    typedef W8Geom<DT, RESV> W;
+    static_assert(!RESV || (LAG == 0 && FOLD), "the resident form is built for folded images at lag 0");
     static_assert(DT == 4, "the sender-row staging is laid out for latent 128 (four lanes per 64-byte half line)");
     constexpr int D = W::D, KS = W::KS, NP = W::NP;
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -426,6 +465,30 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
     if (iters == 0) return;
     RingW<W, LAG> ring(a.image, steps_per_tile, wave, lane);
     CGNN_W8_STAMP_BEGIN(ring)
+    const int passes = L + (ENC ? 1 : 0);
+    (void)passes;
+    if constexpr (RESV) {
+        // the vector table (w8_table_rows; the launcher has checked that it fits): every thread copies one float per
+        // 512, from the image's chunks
+        const int rows = steps_per_tile + passes + (ENC ? 2 : 1);
+        for (int i = threadIdx.x; i < rows * D; i += CGNN_W8_BLOCK) {
+            const int row = i / D, j = i % D;
+            int chunk = row, vec = 0;
+            if (row >= steps_per_tile + passes) {
+                chunk = (ENC && row == steps_per_tile + passes) ? NH : steps_per_tile - 1;
+                vec = 2;
+            } else if (row >= steps_per_tile) {
+                chunk = (row - steps_per_tile + 1) * (NH + 1) - 1;
+                vec = 1;
+            } else if (ENC && row == NH) {
+                chunk = 0;
+                vec = 1;
+            }
+            const float v = *reinterpret_cast<const float*>(a.image + (size_t)chunk * W::IMG_STRIDE + W::VEC_OFF + (unsigned)(vec * D + j) * 4u);
+            ((__attribute__((address_space(3))) float*)(uintptr_t)ring.table_row(0))[i] = v;
+        }
+        __syncthreads();
+    }
     ring.prime();
     if (lagging) ring.idle_interval();
     const bf16x8 sel0 = p32_selector(lane, 0), sel1 = p32_selector(lane, 1);
@@ -444,6 +507,19 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
     bf16x8 inb[2][2 * DT];      // layer l reads inb[l & 1] and packs into inb[(l + 1) & 1]; LayerNorm writes inb[0]
     bf16x8 ps[2 * DT], pd[2 * DT];
     int lnpar = 0;              // which side buffer holds the pending LayerNorm's vectors
+    int pass = 0;               // resident form: the pass whose output layer comes next (the row of its gamma)
+    unsigned lng = 0, lnb = 0;  // ... and the table rows of the pending LayerNorm's gamma and beta
+    (void)lnpar, (void)pass;
+    // the bias that the current step reads (the next layer's), and the pending LayerNorm's vectors
+    auto bias_addr = [&]() __attribute__((always_inline)) -> unsigned {
+        if constexpr (RESV) return ring.table_row(ring.step); else return ring.vec_addr();
+    };
+    auto pending_ln = [&]() __attribute__((always_inline)) {
+        if constexpr (!RESV) {
+            lng = w8dev::ABL_RING4 ? ring.lds0() + W::VEC_OFF + (unsigned)D * 4u : ring.lnbuf(lnpar ^ 1);
+            lnb = lng + (unsigned)D * 4u;
+        }
+    };
     LnStats lnst = {0.f, 0.f};  // ... and its statistics
     constexpr int KA = CGNN_W8_LN_EARLY < 2 * DT ? CGNN_W8_LN_EARLY : 2 * DT;
     int64_t tile = tr.first < tr.end ? tr.first : tr.end - 1;
@@ -622,7 +698,8 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
                 }
                 // (measured and dropped: the selector MFMAs of a row tile right behind its two LayerNorm slices, so that they
                 // run under the next slices' vector work: no gain, four spilled registers)
-                ln_affine_w<PEND == 2, !(FOLD && PEND == 2), FOLD, DT, KA, 2 * DT>(acc, ev, inb[0], ring.lnbuf(lnpar ^ 1), h, lnst);
+                pending_ln();
+                ln_affine_w<PEND == 2, !(FOLD && PEND == 2), FOLD, DT, KA, 2 * DT>(acc, ev, inb[0], lng, lnb, h, lnst);
                 if constexpr (!IS_ENC) {
                     if constexpr (INBLK) read_pd_row(CGNN_IC(0)); else read_pd();
                 }
@@ -633,7 +710,8 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
             constexpr bool REQ = CARRY && !IS_ENC && CGNN_W8_REQ_EARLY;
             if constexpr (REQ) wblock_request<DT * KS0, 0>(fb, base);
             if constexpr (IS_ENC) {
-                bias_rowsw<DT, 0, DT>(acc, ring.vec_addr() + (unsigned)D * 4u, h);      // the encoder's first bias: vector 1 of its own chunk
+                // the encoder's first bias: vector 1 of its own chunk (resident form: the table row of chunk NH)
+                bias_rowsw<DT, 0, DT>(acc, RESV ? ring.table_row(NH) : ring.vec_addr() + (unsigned)D * 4u, h);
             } else if constexpr (PEND != 0) {
                 if constexpr (INBLK) {
                     addp_rows<DT, 0, 1>(acc, ps, pd);      // row tile 0 here, the others from the MFMA slots of the block below
@@ -675,12 +753,12 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
                 if constexpr (t >= 0 && w == (KS0 > 4 ? CGNN_W8_PK0 : (KS0 > 2 ? 1 : KS0 - 1))) packw_slice<true, DT, (t < 0 ? 0 : t), 0>(inb[1], acc);
                 if constexpr (t >= 0 && w == (KS0 > 4 ? CGNN_W8_PK1 : KS0 - 1)) {
                     packw_slice<true, DT, (t < 0 ? 0 : t), 1>(inb[1], acc);
-                    bias_rowsw<DT, (t < 0 ? 0 : t), (t < 0 ? 0 : t) + 1>(acc, ring.vec_addr(), h);
+                    bias_rowsw<DT, (t < 0 ? 0 : t), (t < 0 ? 0 : t) + 1>(acc, bias_addr(), h);
                 }
             }));
             packw_slice<true, DT, DT - 1, 0>(inb[1], acc);
             packw_slice<true, DT, DT - 1, 1>(inb[1], acc);
-            bias_rowsw<DT, DT - 1, DT>(acc, ring.vec_addr(), h);
+            bias_rowsw<DT, DT - 1, DT>(acc, bias_addr(), h);
             ring.dma_done();
             ring.template interval_end<0, 11>();
             ring.advance();
@@ -696,12 +774,12 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
                 if constexpr (t >= 0 && w == (KS > 4 ? CGNN_W8_PK0 : (KS > 2 ? 1 : KS - 1))) packw_slice<true, DT, (t < 0 ? 0 : t), 0>(inb[(l + 1) & 1], acc);
                 if constexpr (t >= 0 && w == (KS > 4 ? CGNN_W8_PK1 : KS - 1)) {
                     packw_slice<true, DT, (t < 0 ? 0 : t), 1>(inb[(l + 1) & 1], acc);
-                    bias_rowsw<DT, (t < 0 ? 0 : t), (t < 0 ? 0 : t) + 1>(acc, ring.vec_addr(), h);
+                    bias_rowsw<DT, (t < 0 ? 0 : t), (t < 0 ? 0 : t) + 1>(acc, bias_addr(), h);
                 }
             }));
             packw_slice<true, DT, DT - 1, 0>(inb[(l + 1) & 1], acc);
             packw_slice<true, DT, DT - 1, 1>(inb[(l + 1) & 1], acc);
-            bias_rowsw<DT, DT - 1, DT>(acc, ring.vec_addr(), h);
+            bias_rowsw<DT, DT - 1, DT>(acc, bias_addr(), h);
             ring.dma_done();
             ring.template interval_end<0, 15>();
             ring.advance();
@@ -730,18 +808,27 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
             ln_sums_add<FOLD, DT, DT - 1, 1>(sums, acc);
             lnst = ln_stats_finish<FOLD, DT>(sums);
             // FOLD: a round that has a successor (WITH_P) adds no beta (the caller folded it forward, include/cgnn.h)
-            ln_affine_w<RES, !(FOLD && RES && WITH_P), FOLD, DT, 0, KA>(acc, ev, inb[0], ring.vec_addr() + (unsigned)D * 4u, h, lnst);
-            // the LayerNorm vectors of this chunk, for the affine part that runs in the next interval (when this slot may
-            // already be refilled): waves 0-3 copy gamma | beta (2 D floats) aside
-            if (wave < CGNN_W8_WAVES / 2) {
-                const int idx = wave * 64 + lane;
-                if (idx < 2 * D) {
-                    const LdsVecPtr sp = (LdsVecPtr)(uintptr_t)(ring.vec_addr() + (unsigned)D * 4u);
-                    const float v = sp[idx];
-                    ((__attribute__((address_space(3))) float*)(uintptr_t)ring.lnbuf(lnpar))[idx] = v;
+            if constexpr (RESV) {
+                // this pass's rows of the table, for the slices here and for the rest in the next interval
+                lng = ring.table_row(steps_per_tile + pass);
+                lnb = ring.table_row(steps_per_tile + passes + (ENC && !IS_ENC ? 1 : 0));
+                pass = pass + 1 == passes ? 0 : pass + 1;
+                ln_affine_w<RES, !(FOLD && RES && WITH_P), FOLD, DT, 0, KA>(acc, ev, inb[0], lng, lnb, h, lnst);
+            } else {
+                ln_affine_w<RES, !(FOLD && RES && WITH_P), FOLD, DT, 0, KA>(acc, ev, inb[0], ring.vec_addr() + (unsigned)D * 4u,
+                                                                             ring.vec_addr() + (unsigned)D * 8u, h, lnst);
+                // the LayerNorm vectors of this chunk, for the affine part that runs in the next interval (when this slot may
+                // already be refilled): waves 0-3 copy gamma | beta (2 D floats) aside
+                if (!w8dev::ABL_RING4 && wave < CGNN_W8_WAVES / 2) {
+                    const int idx = wave * 64 + lane;
+                    if (idx < 2 * D) {
+                        const LdsVecPtr sp = (LdsVecPtr)(uintptr_t)(ring.vec_addr() + (unsigned)D * 4u);
+                        const float v = sp[idx];
+                        ((__attribute__((address_space(3))) float*)(uintptr_t)ring.lnbuf(lnpar))[idx] = v;
+                    }
                 }
+                lnpar ^= 1;
             }
-            lnpar ^= 1;
             ring.dma_done();
             ring.template interval_end<(WITH_P && (!CARRY || CGNN_W8_PIECE_SLOT == 0) ? 5 : 0), 3>();
             ring.advance();
@@ -770,7 +857,10 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
             hidden_steps(ROUND_PASS);
         }
         step_last(ROUND_PASS, std::false_type{}, std::true_type{}, ps_all, pd_all);
-        ln_affine_w<true, true, FOLD, DT, KA, 2 * DT>(acc, ev, inb[0], ring.lnbuf(lnpar ^ 1), h, lnst);
+        pending_ln();
+        // (resident form: only a tile that is stored.  The table never changes, so hipcc otherwise reads all of gamma and
+        // beta ahead of this wave-uniform branch and sinks the arithmetic behind it: 128 registers, 56 of them spilled)
+        if (!RESV || valid) ln_affine_w<true, true, FOLD, DT, KA, 2 * DT>(acc, ev, inb[0], lng, lnb, h, lnst);
 
         if (valid) {
             // the final latents go past the caches (written once, not read again in this launch: as plain stores they
@@ -796,20 +886,26 @@ __global__ __launch_bounds__(CGNN_W8_BLOCK, 2) void edge_stream32w_kernel(
     __builtin_amdgcn_s_barrier();
 }
 
-template <int DT, int NH, int LAG, bool PF16, bool FOLD>
+template <int DT, int NH, int LAG, bool PF16, bool FOLD, bool RESV = false>
 static int launch_w8(const S32Args& a, const __bf16* ps, const __bf16* pd, int64_t round_stride, const int32_t* src,
                      const int32_t* dst, int64_t num_edges, const float* e_in, float* e_out, const float* attr, int ld_attr,
                      int seg_k, hipStream_t st) {
-    typedef W8Geom<DT> W;
+    typedef W8Geom<DT, RESV> W;
     const bool enc = a.enc_in_dim > 0;
-    auto kern = enc ? edge_stream32w_kernel<DT, NH, true, LAG, PF16, FOLD> : edge_stream32w_kernel<DT, NH, false, LAG, PF16, FOLD>;
-    if (W::LDS > 48 * 1024) {
-        int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), W::LDS, "hipFuncSetAttribute(edge_stream32w)");
+    auto kern = enc ? edge_stream32w_kernel<DT, NH, true, LAG, PF16, FOLD, RESV> : edge_stream32w_kernel<DT, NH, false, LAG, PF16, FOLD, RESV>;
+    // resident form: the vector table behind the fixed part (cgnn_edge_stream_w8_vectors_resident has said that it fits)
+    const size_t lds = W::LDS + (RESV ? (size_t)w8_table_rows(NH, a.rounds, enc) * W::TABLE_ROW : 0);
+    if (lds > W::LDS + W::TABLE_MAX) {
+        set_error("cgnn_edge_stream_run_w8: the vector table of %d rounds does not fit in LDS", a.rounds);
+        return CGNN_ERR_INVALID_ARG;
+    }
+    if (lds > 48 * 1024) {
+        int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), W::LDS + W::TABLE_MAX, "hipFuncSetAttribute(edge_stream32w)");
         if (rc != CGNN_OK) return rc;
     }
     const int64_t tiles = (num_edges + 31) / 32;
     const int grid = grid_for_tiles(tiles, 1, CGNN_W8_WAVES);
-    kern<<<grid, CGNN_W8_BLOCK, W::LDS, st>>>(a, ps, pd, round_stride, src, dst, num_edges, e_in, e_out, attr, ld_attr, seg_k);
+    kern<<<grid, CGNN_W8_BLOCK, lds, st>>>(a, ps, pd, round_stride, src, dst, num_edges, e_in, e_out, attr, ld_attr, seg_k);
     CGNN_W8_STAMP_REPORT(st, num_edges, grid, a.rounds + (enc ? 1 : 0), LAG)
     return check_hip(hipGetLastError(), "cgnn_edge_stream_run_w8 launch");
 }
@@ -844,6 +940,16 @@ extern "C" int cgnn_edge_stream_w8_supported(int32_t latent, int32_t num_hidden_
     return (latent == 128 && num_hidden_layers >= 1 && num_hidden_layers <= 3 && k_ok) ? 1 : 0;
 }
 
+// Which form of the ring a CGNN_STREAM_FOLDED launch takes (W8Geom): 1 = the vectors stay resident in LDS, 0 = they travel
+// with the weights.  The one place that decides: the table must fit behind the fixed part, and the resident kernels are
+// built for one or two hidden layers.
+extern "C" int cgnn_edge_stream_w8_vectors_resident(int32_t latent, int32_t num_hidden_layers, int32_t num_rounds,
+                                                    int32_t has_encoder) {
+    typedef W8Geom<4, true> W;
+    if (latent != 128 || num_hidden_layers < 1 || num_hidden_layers > 2 || num_rounds < 1) return 0;
+    return w8_table_rows(num_hidden_layers, num_rounds, has_encoder != 0) * (int64_t)W::TABLE_ROW <= (int64_t)W::TABLE_MAX ? 1 : 0;
+}
+
 extern "C" int cgnn_edge_stream_run_w8(const void* image, size_t image_bytes, int32_t latent, int32_t num_hidden_layers,
                                        int32_t num_rounds, int32_t enc_in_dim, const void* ps_all, const void* pd_all,
                                        int64_t round_stride, const int32_t* src, const int32_t* dst, int64_t num_edges,
@@ -859,8 +965,9 @@ extern "C" int cgnn_edge_stream_run_w8(const void* image, size_t image_bytes, in
                   p_format);
         return CGNN_ERR_INVALID_ARG;
     }
-    if ((flags & ~CGNN_STREAM_FOLDED) != 0 || ((flags & CGNN_STREAM_FOLDED) && p_format != CGNN_P_F16_S32)) {
-        set_error("cgnn_edge_stream_run_w8: flags = %d (known: CGNN_STREAM_FOLDED, with CGNN_P_F16_S32 tables only)", flags);
+    if ((flags & ~(CGNN_STREAM_FOLDED | CGNN_STREAM_TRAVELLING)) != 0 || ((flags & CGNN_STREAM_FOLDED) && p_format != CGNN_P_F16_S32)) {
+        set_error("cgnn_edge_stream_run_w8: flags = %d (known: CGNN_STREAM_FOLDED, with CGNN_P_F16_S32 tables only, and "
+                  "CGNN_STREAM_TRAVELLING)", flags);
         return CGNN_ERR_INVALID_ARG;
     }
     if (p_format == CGNN_P_F16_S32 && lag != 0) {
@@ -895,6 +1002,13 @@ extern "C" int cgnn_edge_stream_run_w8(const void* image, size_t image_bytes, in
     return launch_w8<4, NHx, LAGx, PFx, FOLDx>(a, (const __bf16*)ps_all, (const __bf16*)pd_all, round_stride, src, dst, num_edges, \
                                                e_in, e_out, edge_attr, ld_attr, fixed_k, st)
     if (flags & CGNN_STREAM_FOLDED) {
+        if (!(flags & CGNN_STREAM_TRAVELLING) &&
+            cgnn_edge_stream_w8_vectors_resident(latent, num_hidden_layers, num_rounds, enc_in_dim > 0 ? 1 : 0)) {
+            if (num_hidden_layers == 1) return launch_w8<4, 1, 0, true, true, true>(a, (const __bf16*)ps_all, (const __bf16*)pd_all, round_stride, src, dst,
+                                                                                    num_edges, e_in, e_out, edge_attr, ld_attr, fixed_k, st);
+            return launch_w8<4, 2, 0, true, true, true>(a, (const __bf16*)ps_all, (const __bf16*)pd_all, round_stride, src, dst, num_edges, e_in,
+                                                        e_out, edge_attr, ld_attr, fixed_k, st);
+        }
         switch (num_hidden_layers) {
             case 1: CGNN_W8_GO(1, 0, true, true);
             case 2: CGNN_W8_GO(2, 0, true, true);

@@ -63,6 +63,13 @@ constexpr bool ABL_BIAS = true;      // no bias reads
 #else
 constexpr bool ABL_BIAS = false;
 #endif
+#ifdef CGNN_W8_ABL_RING4
+constexpr bool ABL_RING4 = true;     // the travelling ring fetches the 32 weight pieces of a chunk only (four per wave and step, the
+                                     // slots' vector parts filled once in the prologue) and no LayerNorm vectors are copied aside:
+                                     // what keeping the vectors resident can save at most
+#else
+constexpr bool ABL_RING4 = false;
+#endif
 #ifdef CGNN_W8_SLEEP
 constexpr int SLEEP = CGNN_W8_SLEEP; // idle cycles (x 64) per interval: is the kernel bound by cycles or by the clock it is given?
 #else

@@ -432,10 +432,16 @@ def stream_w8_supported(latent: int, nh: int, fixed_k: int) -> bool:
     return bool(_lib.load().cgnn_edge_stream_w8_supported(latent, nh, int(fixed_k)))
 
 
+def stream_w8_vectors_resident(latent: int, nh: int, rounds: int, has_encoder: bool) -> bool:
+    """Whether a folded ``cgnn_edge_stream_run_w8`` launch of this shape keeps its bias and LayerNorm vectors resident in
+    LDS (``cgnn_edge_stream_w8_vectors_resident``); otherwise they travel in the weight ring."""
+    return bool(_lib.load().cgnn_edge_stream_w8_vectors_resident(latent, nh, rounds, 1 if has_encoder else 0))
+
+
 def edge_stream_run(image: StreamImage, ps_all: torch.Tensor, pd_all: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,
                     e_in: Optional[TiledRows], e_out: Optional[TiledRows] = None,
                     edge_attr: Optional[torch.Tensor] = None, kernel: str = "tile32", lag: int = 1,
-                    fixed_k: int = 0, folded: Optional[bool] = None) -> TiledRows:
+                    fixed_k: int = 0, folded: Optional[bool] = None, travelling: bool = False) -> TiledRows:
     """All residual edge updates of ``image`` in one launch.  ``ps_all`` / ``pd_all``: ``[rounds, N, latent]`` bf16
     tables in ``CGNN_P_BF16_S32`` format -- or, ``"tile32w"`` with ``lag = 0`` only, float16 tables in ``CGNN_P_F16_S32``
     format (include/cgnn.h; the kernel then adds ``Ps[src] + Pd[dst]`` on the vector pipe instead of through selector
@@ -444,7 +450,9 @@ def edge_stream_run(image: StreamImage, ps_all: torch.Tensor, pd_all: torch.Tens
     tiles per wave), ``"tile32w"`` = ``cgnn_edge_stream_run_w8`` (two waves per SIMD, one tile each; ``lag`` and
     ``fixed_k`` as in include/cgnn.h: the graph's fixed in-degree, ``dst[e] == e // fixed_k``; see
     ``stream_w8_supported``).  ``folded`` (default: what the image says): pass ``CGNN_STREAM_FOLDED`` where the kernel has
-    the shorter LayerNorm for it (``"tile32w"`` on float16 tables); every other kernel runs a folded image as a plain one."""
+    the shorter LayerNorm for it (``"tile32w"`` on float16 tables); every other kernel runs a folded image as a plain one.
+    ``travelling``: pass ``CGNN_STREAM_TRAVELLING``, which keeps a folded ``"tile32w"`` launch from holding its bias and
+    LayerNorm vectors resident in LDS (``stream_w8_vectors_resident``; same bits either way: for tests and timing)."""
     if kernel not in ("tile32", "tile32w"):
         raise CgnnError(f"edge_stream_run: unknown kernel {kernel!r}")
     if image.kernel != kernel:
@@ -482,7 +490,8 @@ def edge_stream_run(image: StreamImage, ps_all: torch.Tensor, pd_all: torch.Tens
             fold = image.folded if folded is None else bool(folded)
             check(_lib.load().cgnn_edge_stream_run_w8(*args, int(lag), int(fixed_k),
                                                       _lib.P_F16_S32 if pdt == torch.float16 else _lib.P_BF16_S32,
-                                                      _lib.STREAM_FOLDED if (fold and pdt == torch.float16) else 0,
+                                                      (_lib.STREAM_FOLDED if (fold and pdt == torch.float16) else 0)
+                                                      | (_lib.STREAM_TRAVELLING if travelling else 0),
                                                       stream_ptr(src.device)), "cgnn_edge_stream_run_w8")
         else:
             check(_lib.load().cgnn_edge_stream_run(*args, stream_ptr(src.device)), "cgnn_edge_stream_run")

@@ -324,9 +324,17 @@ int cgnn_edge_stream_run(const void* image, size_t image_bytes, int32_t latent, 
  *       (the stored latents are e_L itself).  The encoder's LayerNorm keeps its beta.
  * 128 fewer vector instructions per tile and round (LayerNorm: 64 adds of the mean's sum, 64 adds of beta); results
  * differ from the unfolded kernel's by bf16 operand roundings of e_r - B_r instead of e_r (same error class).  Without
- * the flag any image runs as before (a folded image is also a valid plain image: mean ~ 0 is computed, beta = 0 added). */
+ * the flag any image runs as before (a folded image is also a valid plain image: mean ~ 0 is computed, beta = 0 added).
+ * A folded launch comes in two forms with the same arithmetic and bit-identical results.  Resident: the workgroup copies
+ * every bias, gamma and beta the launch reads into an LDS table once, and the weight ring carries the 32 KiB of weights
+ * per layer only.  Travelling: the vectors ride in the ring with every layer's weights, as in every launch that is not
+ * folded.  cgnn_edge_stream_w8_vectors_resident says which one a folded launch of a shape takes: 1 = resident (the table
+ * fits in LDS: one or two hidden layers, e.g. up to 10 rounds behind an encoder at two), 0 = travelling.
+ * CGNN_STREAM_TRAVELLING forces the travelling form (tests and same-process timing; the model never sets it). */
 #define CGNN_STREAM_FOLDED 1
+#define CGNN_STREAM_TRAVELLING 4
 int cgnn_edge_stream_w8_supported(int32_t latent, int32_t num_hidden_layers, int32_t fixed_k);
+int cgnn_edge_stream_w8_vectors_resident(int32_t latent, int32_t num_hidden_layers, int32_t num_rounds, int32_t has_encoder);
 int cgnn_edge_stream_image_build_w8(const cgnn_mlp* rounds, int32_t num_rounds, const cgnn_mlp* encoder, int32_t latent,
                                     void* image, size_t image_bytes, void* stream);
 int cgnn_edge_stream_run_w8(const void* image, size_t image_bytes, int32_t latent, int32_t num_hidden_layers,

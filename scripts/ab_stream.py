@@ -21,6 +21,8 @@ ap.add_argument("--neighbors", type=int, default=16)
 ap.add_argument("--latent", type=int, default=128)
 ap.add_argument("--mp-steps", type=int, default=10)
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=1, help="untimed interleaved rounds in front (clocks and caches settle)")
+ap.add_argument("--all-times", action="store_true", help="also print every round's time per variant")
 ap.add_argument("--variants", default="tile32,tile32w:0,tile32w:1")
 ap.add_argument("--no-encoder", action="store_true")
 ap.add_argument("--bf16-tables", action="store_true", help="tile32w: bf16 P tables (selector MFMAs) instead of the model's fp16 ones")
@@ -50,22 +52,25 @@ e = ops.TiledRows.from_rows(torch.randn(E, d, device=dev))
 flops = L * 6.0 * E * d * d + (0 if a.no_encoder else 2.0 * E * (32 * d + 2 * d * d))
 variants = []
 for v in a.variants.split(","):
-    kern, _, lag = v.partition(":")      # "tile32w:0f": timing of the CGNN_STREAM_FOLDED kernel (on an image that is not folded)
-    variants.append((v, kern, (int(lag.rstrip("f") or 0), lag.endswith("f"))))
+    # "tile32w:0f": timing of the CGNN_STREAM_FOLDED kernel (on an image that is not folded), "tile32w:0ft": the same with
+    # CGNN_STREAM_TRAVELLING (the vectors in the weight ring instead of resident in LDS)
+    kern, _, lag = v.partition(":")
+    variants.append((v, kern, (int(lag.rstrip("ft") or 0), "f" in lag, "t" in lag)))
 
 
 def run(kern, lag_fold):
-    lag, fold = lag_fold
+    lag, fold, trav = lag_fold
     ps_, pd_ = (ps16, pd16) if (kern == "tile32w" and (lag == 2 or (lag == 0 and not a.bf16_tables))) else (ps_all, pd_all)
     if a.no_encoder:
-        ops.edge_stream_run(images[kern], ps_, pd_, src, dst, e, e, None, kernel=kern, lag=lag, fixed_k=fk if a.fixed_k else 0, folded=fold)
+        ops.edge_stream_run(images[kern], ps_, pd_, src, dst, e, e, None, kernel=kern, lag=lag, fixed_k=fk if a.fixed_k else 0, folded=fold, travelling=trav)
     else:
-        ops.edge_stream_run(images[kern], ps_, pd_, src, dst, None, e, ea, kernel=kern, lag=lag, fixed_k=fk if a.fixed_k else 0, folded=fold)
+        ops.edge_stream_run(images[kern], ps_, pd_, src, dst, None, e, ea, kernel=kern, lag=lag, fixed_k=fk if a.fixed_k else 0, folded=fold, travelling=trav)
 
 
 times = {v[0]: [] for v in variants}
-for name, kern, lag in variants:
-    run(kern, lag)
+for _ in range(max(1, a.warmup)):
+    for name, kern, lag in variants:
+        run(kern, lag)
 torch.cuda.synchronize()
 for _ in range(a.rounds):
     for name, kern, lag in variants:
@@ -77,5 +82,7 @@ for _ in range(a.rounds):
         times[name].append(t0.elapsed_time(t1))
 for name, ts in times.items():
     med = statistics.median(ts)
-    print(f"{name:12s} median {med:8.3f} ms  min {min(ts):8.3f} ms  {flops / med / 1e9:7.1f} TFLOP/s issued = "
+    print(f"{name:12s} median {med:8.3f} ms  min {min(ts):8.3f} ms  max {max(ts):8.3f} ms  {flops / med / 1e9:7.1f} TFLOP/s issued = "
           f"{flops / med / 1e9 / 2500:.3f} of the bf16 peak   ({E * L / med / 1e6:.2f} G edge-updates/s)", flush=True)
+    if a.all_times:
+        print(f"{name:12s} " + " ".join(f"{t:.3f}" for t in ts), flush=True)
