@@ -58,11 +58,15 @@ EXPORTS = (
     "cgnn_redshift_positions", "cgnn_power_multipoles_workspace_bytes", "cgnn_power_multipoles",
     "cgnn_pair_counts_smu_workspace_bytes", "cgnn_pair_counts_smu",
     "cgnn_pair_velocity_sums_workspace_bytes", "cgnn_pair_velocity_sums",
+    "cgnn_knn_distances_workspace_bytes", "cgnn_knn_distances", "cgnn_knn_cdf_counts",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
 PAIR_COUNTS_SMU_MAX_AXIS = 128    # CGNN_SMU_MAX_AXIS: bins per axis at most
 PAIR_VELOCITY_MAX_BINS = 64       # CGNN_PV_MAX_BINS in csrc/pair_velocities.hip
+KNN_DISTANCES_MAX_RANKS = 16      # CGNN_KD_MAX_RANKS in csrc/knn_distances.hip: ranks per call
+KNN_DISTANCES_MAX_K = 64          # CGNN_KD_MAX_K: the largest rank
+KNN_CDF_MAX_RADII = 256           # CGNN_KCDF_MAX_RADII
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
@@ -177,6 +181,10 @@ def load() -> C.CDLL:
     lib.cgnn_pair_velocity_sums_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cgnn_pair_velocity_sums.argtypes = [vp, vp, i64, vp, vp, i64, f32, C.POINTER(f32), i32, vp, vp, vp, sz,
                                             vp]                                             # edges: host memory
+    lib.cgnn_knn_distances_workspace_bytes.restype = sz
+    lib.cgnn_knn_distances_workspace_bytes.argtypes = [i64, i64]
+    lib.cgnn_knn_distances.argtypes = [vp, i64, vp, i64, f32, C.POINTER(i32), i32, vp, vp, sz, vp]   # ranks: host memory
+    lib.cgnn_knn_cdf_counts.argtypes = [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]             # radii: host memory
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]

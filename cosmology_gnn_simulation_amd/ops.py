@@ -1014,6 +1014,127 @@ def pair_velocity_sums(pos_a: torch.Tensor, q_a: torch.Tensor, box_size: float, 
     return (counts, sums) if batched else (counts[0], sums[0])
 
 
+def check_knn_ranks(ks, who: str) -> List[int]:
+    """The ranks of :func:`knn_distances` as host ints, or ``ValueError``: ``1 <= nk <= 16`` whole numbers (no bools, no
+    fractions), strictly ascending, ``1 <= k <= 64``.  Callers check before any device work."""
+    if torch.is_tensor(ks):
+        ks = ks.detach().to("cpu").reshape(-1).tolist()
+    try:
+        ks = list(ks)
+    except TypeError:
+        raise ValueError(f"{who}: ks must be a sequence of ranks, got {ks!r}") from None
+    if not 1 <= len(ks) <= _lib.KNN_DISTANCES_MAX_RANKS:
+        raise ValueError(f"{who}: ks must hold 1 to {_lib.KNN_DISTANCES_MAX_RANKS} ranks, got {len(ks)}")
+    out = []
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or k != int(k):
+            raise ValueError(f"{who}: a rank must be a whole number, got {k!r}")
+        out.append(int(k))
+    if out[0] < 1 or out[-1] > _lib.KNN_DISTANCES_MAX_K or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"{who}: ks must ascend strictly within [1, {_lib.KNN_DISTANCES_MAX_K}], got {out}")
+    return out
+
+
+def check_knn_radii(radii, box_size: float, who: str) -> List[float]:
+    """The radii of :func:`knn_cdf_counts` as float32 host values, or ``ValueError``: the rules of
+    :func:`check_pair_count_edges` for ``1 <= nr <= 256`` radii: finite, ``>= 0``, strictly ascending in float32,
+    ``radii[-1] <= fl32(0.5 * box_size)``, ``box_size > 0``.  Up to half the box the distance to the nearest of the 27
+    images is the minimum-image distance, which is what the cap is for.  Callers check before any device work."""
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{who}: box_size must be positive and finite, got {box_size!r}")
+    r = torch.as_tensor(radii).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    if not 1 <= r.numel() <= _lib.KNN_CDF_MAX_RADII:
+        raise ValueError(f"{who}: radii must hold 1 to {_lib.KNN_CDF_MAX_RADII} values, got {r.numel()}")
+    if not bool(torch.isfinite(r).all()) or float(r[0]) < 0.0 or not bool((r[1:] > r[:-1]).all()):
+        raise ValueError(f"{who}: radii must be finite, start at 0 or above and ascend strictly (in float32)")
+    if not bool(r[-1] <= box * 0.5):
+        raise ValueError(f"{who}: the largest radius {float(r[-1])} exceeds half the box, {float(box) * 0.5}")
+    return r.tolist()
+
+
+def knn_distances(pos: torch.Tensor, queries: torch.Tensor, box_size: float, ks, *,
+                  check_bounds: bool = False) -> torch.Tensor:
+    """The squared distances from query points to their k-th nearest particles in a periodic box
+    (``cgnn_knn_distances``): float32 ``d2 [nq, nk]`` for ``pos [N, 3]``, ``[T, nq, nk]`` for ``pos [T, N, 3]`` (one call
+    per frame on the same stream, no host synchronisation between them).  ``queries [nq, 3]`` are independent points,
+    shared by the frames; one that coincides with a particle sees it at distance 0.  ``ks``: the ranks
+    (:func:`check_knn_ranks`), the largest at most ``27 N``.
+
+    ``d2[q, j]`` is the ``ks[j]``-th smallest of the float32 squared distances from query ``q`` to the ``27 N`` periodic
+    images the graph builder ranks, ``fl32(fl32(pos + s box) - q)`` squared and summed x, y, z with one rounding per
+    operation (``include/cgnn.h``): the same bits as the brute force, whatever the order of the queries or particles.
+    Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host synchronisation per tensor,
+    the default verifies nothing.  One box per call."""
+    what = "knn_distances"
+    ranks = check_knn_ranks(ks, what)
+    if not (math.isfinite(float(box_size)) and float(box_size) > 0.0):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    pos = f32c(pos, "pos")
+    batched = pos.dim() == 3
+    if pos.dim() not in (2, 3) or pos.shape[-1] != 3 or pos.shape[-2] < 1:
+        raise CgnnError(f"{what}: pos must be [N, 3] or [T, N, 3] with N >= 1, got {tuple(pos.shape)}")
+    queries = f32c(queries, "queries")
+    if queries.dim() != 2 or queries.shape[1] != 3:
+        raise CgnnError(f"{what}: queries must be [nq, 3], got {tuple(queries.shape)}")
+    _same_device(pos, queries)
+    n, nq, nk = pos.shape[-2], queries.shape[0], len(ranks)
+    if ranks[-1] > 27 * n:
+        raise ValueError(f"{what}: rank {ranks[-1]} exceeds the 27 N = {27 * n} periodic images")
+    if check_bounds:
+        _check_in_box(what, box_size, pos=pos, queries=queries)
+    frames = pos if batched else pos.unsqueeze(0)
+    t = frames.shape[0]
+    d2 = torch.empty((t, nq, nk), dtype=torch.float32, device=pos.device)
+    if nq > 0 and t > 0:
+        lib = _lib.load()
+        ranks_c = (C.c_int32 * nk)(*ranks)
+        ws_bytes = lib.cgnn_knn_distances_workspace_bytes(n, nq)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+        st = stream_ptr(pos.device)
+        with _timed(what, pos.device):
+            for f in range(t):
+                check(lib.cgnn_knn_distances(frames[f].data_ptr(), n, queries.data_ptr(), nq, float(box_size), ranks_c,
+                                             nk, d2[f].data_ptr(), ws.data_ptr(), ws_bytes, st), "cgnn_knn_distances")
+    return d2 if batched else d2[0]
+
+
+def knn_cdf_counts(d2_a: torch.Tensor, radii, box_size: float, d2_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """How many queries have their k-th neighbour within each radius (``cgnn_knn_cdf_counts``): int64 ``below [nk, nr]``
+    for a table ``d2_a [nq, nk]`` of :func:`knn_distances`, ``[T, nk, nr]`` for ``[T, nq, nk]``.  ``below[j, b]`` is the
+    number of queries with ``v[q, j] < fl32(radii[b] ** 2)`` (strict, the pair counter's threshold rule), ``v = d2_a``,
+    or with ``d2_b`` (a table of the same shape, of a second particle set seen from the same queries) ``v = max(d2_a,
+    d2_b)``: both k-th neighbours lie within the radius, the joint CDF.  ``radii``: :func:`check_knn_radii`.  Exact
+    integers, the same bits on every run; divided by ``nq`` they are the empirical CDFs
+    (:func:`statistics.knn_cdfs_from_counts`)."""
+    what = "knn_cdf_counts"
+    r = check_knn_radii(radii, box_size, what)
+    nr = len(r)
+    d2_a = f32c(d2_a, "d2_a")
+    batched = d2_a.dim() == 3
+    if d2_a.dim() not in (2, 3) or not 1 <= d2_a.shape[-1] <= _lib.KNN_DISTANCES_MAX_RANKS:
+        raise CgnnError(f"{what}: d2_a must be [nq, nk] or [T, nq, nk] with 1 <= nk <= {_lib.KNN_DISTANCES_MAX_RANKS}, "
+                        f"got {tuple(d2_a.shape)}")
+    if d2_b is not None:
+        d2_b = f32c(d2_b, "d2_b")
+        if d2_b.shape != d2_a.shape:
+            raise CgnnError(f"{what}: d2_b {tuple(d2_b.shape)} is not a table like d2_a {tuple(d2_a.shape)}")
+        _same_device(d2_a, d2_b)
+    ta = d2_a if batched else d2_a.unsqueeze(0)
+    tb = None if d2_b is None else (d2_b if batched else d2_b.unsqueeze(0))
+    t, nq, nk = ta.shape
+    lib = _lib.load()
+    radii_c = (C.c_float * nr)(*r)
+    below = torch.empty((t, nk, nr), dtype=torch.int64, device=d2_a.device)
+    st = stream_ptr(d2_a.device)
+    with _timed(what, d2_a.device):
+        for f in range(t):
+            check(lib.cgnn_knn_cdf_counts(ta[f].data_ptr() if nq else None,
+                                          None if tb is None or not nq else tb[f].data_ptr(), nq, nk, radii_c, nr,
+                                          below[f].data_ptr(), st), "cgnn_knn_cdf_counts")
+    return below if batched else below[0]
+
+
 def frame_errors(pred_pos: torch.Tensor, true_pos: torch.Tensor, pred_tmp: Optional[torch.Tensor],
                  true_tmp: Optional[torch.Tensor], box_size: float) -> torch.Tensor:
     """Per-frame mean squared errors of a rollout (``cgnn_frame_errors``): ``float64 [T, 2]`` on the device, column 0

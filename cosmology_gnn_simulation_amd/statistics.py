@@ -45,6 +45,13 @@ xi_4 of the displaced frame from exact pair counts by separation and by mu = |co
 ``rollout_redshift_correlation`` does that for every frame of a rollout against the truth;
 ``correlation_multipoles_from_counts`` is the host arithmetic and ``default_mu_edges`` the 20 equal mu-bins.
 
+Beyond two points (two frames can agree in everything above and differ in how empty their voids are): ``knn_cdfs`` gives
+the k-nearest-neighbour distance distributions of a frame seen from a lattice of query points (``ops.knn_distances``,
+``ops.knn_cdf_counts``; ``query_lattice``, ``default_knn_radii``), with the void probability function, the
+counts-in-spheres distribution and, for two sets, the joint CDF and its excess over independence;
+``rollout_knn_cdfs`` does that for every frame of a rollout against the truth and ``knn_cdfs_from_counts`` is the host
+arithmetic.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -1773,3 +1780,172 @@ def rollout_halo_profiles(rollout_data: Dict[str, torch.Tensor], ground_truth: D
             sums = ints[:, 1 + 2 * sb + sb * nb:].reshape(nf, sb, nb).to(torch.float64)
             res["temperature_" + name] = sums / counts.to(torch.float64) * (scales_h[side] / float(1 << _lib.WEIGHT_BITS))
     return res
+
+
+# ---- k-nearest-neighbour distance distributions ----------------------------------------------------------------------
+#
+# Everything above is a two-point statistic or a statistic of collapsed objects; two frames can agree in all of it and
+# differ in how empty their voids are or in any connected higher-order moment.  The kNN-CDFs (Banerjee & Abel 2021) are
+# sensitive to every N-point function at once: from volume-filling query points, the empirical distribution of the
+# distance to the k-th nearest particle (``ops.knn_distances``, ``ops.knn_cdf_counts``).  The void probability function
+# is ``1 - CDF_1``, the counts-in-spheres distribution ``P(N = k | r) = CDF_k - CDF_{k+1}``, and the joint CDF of two
+# particle sets seen from the same queries a cross-correlation beyond r(k).  One box per call; particle-centred
+# distributions, batched, sharded and owned-storage variants, random default queries and a loss are not built.
+
+
+def query_lattice(m: int, box_size: float, device=None) -> torch.Tensor:
+    """The volume-filling default queries of the kNN-CDFs: the ``m^3`` cell centres ``fl32((i + 0.5) box_size / m)`` of
+    a regular lattice as float32 ``[m^3, 3]``, x slowest.  Deterministic: no random numbers."""
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 1024:
+        raise ValueError(f"query_lattice: m must be a whole number in [1, 1024], got {m!r}")
+    if not (math.isfinite(float(box_size)) and float(box_size) > 0.0):
+        raise ValueError(f"query_lattice: box_size must be positive and finite, got {box_size!r}")
+    c = ((torch.arange(m, dtype=torch.float64) + 0.5) * float(box_size) / m).to(torch.float32)
+    q = torch.cartesian_prod(c, c, c).reshape(m ** 3, 3)
+    return q if device is None else q.to(device)
+
+
+def default_knn_radii(n: int, box_size: float) -> torch.Tensor:
+    """The default radii of the kNN-CDFs: 24 log-spaced radii from 0.1 to 4 mean interparticle spacings ``box_size /
+    n ** (1 / 3)``, without those above ``fl32(0.5 * box_size)`` (0.1 spacings never exceed a tenth of the box, so at
+    least one remains).  Float32 values as float64, ascending."""
+    if int(n) < 1:
+        raise ValueError(f"default_knn_radii: n must be at least 1, got {n!r}")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"default_knn_radii: box_size must be positive and finite, got {box_size!r}")
+    spacing = float(box_size) / float(n) ** (1.0 / 3.0)
+    r = (spacing * torch.logspace(math.log10(0.1), math.log10(4.0), 24, dtype=torch.float64)).to(torch.float32)
+    return r[r <= box * 0.5].to(torch.float64)
+
+
+def _cdf_counts_on_host(what: str, name: str, below, shape=None) -> torch.Tensor:
+    b = torch.as_tensor(below).detach().to(device="cpu")
+    if b.dtype.is_floating_point or b.dtype == torch.bool or b.dim() not in (2, 3):
+        raise ValueError(f"{what}: {name} must hold integer counts [nk, nr] or [T, nk, nr], got {b.dtype} "
+                         f"{tuple(b.shape)}")
+    if shape is not None and tuple(b.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} {tuple(b.shape)} does not go with below {tuple(shape)}")
+    return b.to(torch.float64)
+
+
+def knn_cdfs_from_counts(below, n_queries: int, ks, radii, below_b=None, below_joint=None) -> Dict:
+    """The kNN-CDFs from the integers of ``ops.knn_cdf_counts``, on the host in float64.  ``below [nk, nr]`` (or ``[T, nk,
+    nr]``) for the ranks ``ks`` and the ``nr`` radii, counted over ``n_queries`` queries.  Returns (CPU, float64, in the
+    shape of ``below``):
+
+    * ``cdf = below / n_queries``: the fraction of the volume within ``r`` of at least ``k`` particles;
+    * ``peaked_cdf = min(cdf, 1 - cdf)``, which shows both tails;
+    * ``vpf = 1 - cdf[k = 1]`` (``[nr]`` or ``[T, nr]``), the void probability function, when 1 is among ``ks``;
+    * ``counts_in_spheres``: a dict keyed by ``k`` with ``P(N = k | r) = cdf_k - cdf_{k+1}`` for every ``k`` with both
+      ``k`` and ``k + 1`` among ``ks``;
+    * with ``below_b`` and ``below_joint`` (a second particle set from the same queries, and the counts of the
+      elementwise maximum of the two tables; both or neither): ``cdf_b``, ``joint_cdf`` and ``joint_excess = joint_cdf -
+      cdf * cdf_b``, which is zero for independent sets,
+
+    plus ``ks`` (a list) and ``radii`` (float64 ``[nr]``)."""
+    what = "knn_cdfs_from_counts"
+    ranks = ops.check_knn_ranks(ks, what)
+    if isinstance(n_queries, bool) or int(n_queries) != n_queries or int(n_queries) < 1:
+        raise ValueError(f"{what}: n_queries must be a whole number of at least 1, got {n_queries!r}")
+    r = torch.as_tensor(radii).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    b = _cdf_counts_on_host(what, "below", below)
+    if b.shape[-2] != len(ranks) or b.shape[-1] != r.numel():
+        raise ValueError(f"{what}: below {tuple(b.shape)} for {len(ranks)} ranks and {r.numel()} radii")
+    if (below_b is None) != (below_joint is None):
+        raise ValueError(f"{what}: below_b and below_joint come together")
+    nq = float(int(n_queries))
+    cdf = b / nq
+    out = {"ks": ranks, "radii": r.clone(), "cdf": cdf, "peaked_cdf": torch.minimum(cdf, 1.0 - cdf)}
+    if 1 in ranks:
+        out["vpf"] = 1.0 - cdf[..., ranks.index(1), :]
+    out["counts_in_spheres"] = {k: cdf[..., i, :] - cdf[..., ranks.index(k + 1), :]
+                                for i, k in enumerate(ranks) if k + 1 in ranks}
+    if below_b is not None:
+        out["cdf_b"] = _cdf_counts_on_host(what, "below_b", below_b, b.shape) / nq
+        out["joint_cdf"] = _cdf_counts_on_host(what, "below_joint", below_joint, b.shape) / nq
+        out["joint_excess"] = out["joint_cdf"] - cdf * out["cdf_b"]
+    return out
+
+
+def _check_knn_cdf_arguments(what: str, n: int, box_size, radii, ks, queries, n_query_axis, device):
+    """Ranks, radii (default :func:`default_knn_radii`) and queries (default :func:`query_lattice`) of a kNN-CDF call,
+    checked on the host before any device work."""
+    ranks = ops.check_knn_ranks(ks, what)
+    if ranks[-1] > 27 * n:
+        raise ValueError(f"{what}: rank {ranks[-1]} exceeds the 27 N = {27 * n} periodic images")
+    r = ops.check_knn_radii(default_knn_radii(n, box_size) if radii is None else radii, box_size, what)
+    if queries is None:
+        queries = query_lattice(int(round(n ** (1.0 / 3.0))) if n_query_axis is None else n_query_axis, box_size, device)
+    elif n_query_axis is not None:
+        raise ValueError(f"{what}: queries and n_query_axis exclude each other")
+    elif not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != 3 or queries.shape[0] < 1:
+        raise ValueError(f"{what}: queries must be a tensor [nq, 3] with nq >= 1, got "
+                         f"{tuple(queries.shape) if torch.is_tensor(queries) else type(queries).__name__}")
+    return ranks, r, queries
+
+
+def knn_cdfs(pos: torch.Tensor, box_size: float, radii=None, ks=(1, 2, 4, 8), queries: Optional[torch.Tensor] = None,
+             n_query_axis: Optional[int] = None, pos_b: Optional[torch.Tensor] = None) -> Dict:
+    """The kNN-CDFs of ``pos [N, 3]`` (or of every frame of ``[T, N, 3]``): the keys of :func:`knn_cdfs_from_counts`, plus
+    ``below`` (the int64 counts behind ``cdf``) and ``n_queries``.  ``radii``: default :func:`default_knn_radii`;
+    ``queries [nq, 3]``: default ``query_lattice(n_query_axis or round(N ** (1 / 3)))``, as many queries as particles.
+    With ``pos_b`` (a second set in the shape of ``pos`` up to its number of particles) also ``cdf_b``, ``joint_cdf`` and
+    ``joint_excess``, from the same queries.  The counts come back in one transfer."""
+    what = "knn_cdfs"
+    if not torch.is_tensor(pos):
+        raise ValueError(f"{what}: pos must be a tensor, got {type(pos).__name__}")
+    frames = _frames3(pos, "pos", what)
+    n = frames.shape[1]
+    ranks, r, queries = _check_knn_cdf_arguments(what, n, box_size, radii, ks, queries, n_query_axis, pos.device)
+    if pos_b is not None:
+        if not torch.is_tensor(pos_b) or pos_b.dim() != pos.dim() or _frames3(pos_b, "pos_b", what).shape[0] != frames.shape[0]:
+            raise ValueError(f"{what}: pos_b must be frames like pos {tuple(pos.shape)}")
+        if ranks[-1] > 27 * pos_b.shape[-2]:
+            raise ValueError(f"{what}: rank {ranks[-1]} exceeds the 27 N = {27 * pos_b.shape[-2]} images of pos_b")
+    d2 = ops.knn_distances(pos, queries, box_size, ranks)
+    counts = [ops.knn_cdf_counts(d2, r, box_size)]
+    if pos_b is not None:
+        d2_b = ops.knn_distances(pos_b, queries, box_size, ranks)
+        counts += [ops.knn_cdf_counts(d2_b, r, box_size), ops.knn_cdf_counts(d2, r, box_size, d2_b)]
+    counts = torch.stack(counts).cpu()                                                  # the one transfer
+    nq = queries.shape[0]
+    out = knn_cdfs_from_counts(counts[0], nq, ranks, r, *(counts[1:] if pos_b is not None else ()))
+    out["below"], out["n_queries"] = counts[0], nq
+    return out
+
+
+def rollout_knn_cdfs(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                     radii=None, ks=(1, 2, 4, 8), n_query_axis: Optional[int] = None,
+                     frames: Optional[Sequence[int]] = None) -> Dict:
+    """kNN-CDFs of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N, 3]``): what
+    xi(r), P(k) and the halo statistics cannot tell -- whether the voids are as empty and the web as sharp as in the true
+    frame.  Both sides are seen from the same lattice of queries (:func:`query_lattice`, ``n_query_axis`` per axis,
+    default ``round(N ** (1 / 3))``).  Per selected frame (CPU, float64):
+
+    * ``cdf_pred``, ``cdf_true`` (``[F, nk, nr]``);
+    * ``joint_cdf``: the fraction of queries with the k-th neighbour of BOTH frames within ``r``, and ``joint_excess =
+      joint_cdf - cdf_pred * cdf_true``;
+    * ``vpf_pred``, ``vpf_true`` (``[F, nr]``), when 1 is among ``ks``;
+    * ``max_cdf_difference`` (``[F, nk]``): the Kolmogorov distance ``max_r |cdf_pred - cdf_true|`` between the predicted
+      and the true distribution per rank, over the given radii,
+
+    plus ``frames``, ``ks``, ``radii`` and ``n_queries``.  No host synchronisation per frame; one transfer."""
+    what = "rollout_knn_cdfs"
+    n = rollout_data["Coordinates"].shape[-2]
+    dev = rollout_data["Coordinates"].device
+    ranks, r, queries = _check_knn_cdf_arguments(what, n, box_size, radii, ks, None, n_query_axis, dev)
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
+    d2_p = ops.knn_distances(_f32_frames(pc, "Coordinates", what), queries, box_size, ranks)
+    d2_t = ops.knn_distances(_f32_frames(tc, "Coordinates", what), queries, box_size, ranks)
+    counts = torch.stack([ops.knn_cdf_counts(d2_p, r, box_size), ops.knn_cdf_counts(d2_t, r, box_size),
+                          ops.knn_cdf_counts(d2_p, r, box_size, d2_t)]).cpu()           # [3, F, nk, nr], the one transfer
+    nq = queries.shape[0]
+    res = knn_cdfs_from_counts(counts[0], nq, ranks, r, counts[1], counts[2])
+    out = {"frames": sel, "ks": ranks, "radii": res["radii"], "n_queries": nq, "cdf_pred": res["cdf"],
+           "cdf_true": res["cdf_b"], "joint_cdf": res["joint_cdf"], "joint_excess": res["joint_excess"],
+           "max_cdf_difference": (res["cdf"] - res["cdf_b"]).abs().amax(dim=-1)}
+    if 1 in ranks:
+        i = ranks.index(1)
+        out["vpf_pred"], out["vpf_true"] = res["vpf"], 1.0 - res["cdf_b"][..., i, :]
+    return out

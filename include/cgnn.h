@@ -554,6 +554,44 @@ int cgnn_knn_periodic_batched(const float* pos, const int64_t* offsets, int32_t 
 int cgnn_knn_batched_sorted_order(const void* workspace, const int64_t* offsets, int32_t num_graphs,
                                   int32_t* perm, void* stream);
 
+/* ---- k-nearest-neighbour distance distributions (kNN-CDFs): distances from query points, counts below radii ----
+ * The squared distances from nq independent query points to their ranks[j]-th nearest particles, j < nk, in a periodic
+ * box.  pos [n, 3] and queries [nq, 3] hold positions in [0, box_size]; a query need not be a particle, and one that
+ * coincides with a particle sees it at distance 0.  ranks (HOST memory, nk ints; passed to the kernel by value):
+ * 1 <= nk <= 16, strictly ascending, 1 <= ranks[j] <= 64, ranks[nk - 1] <= 27 n.
+ * d2_out (device, float [nq, nk]): d2_out[q, j] is the ranks[j]-th smallest value of the multiset {d2(q, image)} over the
+ * 27 n images cgnn_knn_periodic ranks, with that entry's squared distance:
+ *     e  = fl32(pos + fl32(s * box_size)),  s in {-1, 0, 1}, per axis;     d = fl32(e - q)
+ *     d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy)) + fl32(dz*dz))
+ * one float32 rounding per operation, no FMA.  Only the multiset matters: ties need no index, and the result depends on
+ * no order (of the walk, of the queries, of the particles) and is the same bits on every run.  Up to half the box the
+ * distance to the nearest of the 27 images is the minimum-image distance.
+ * The search is the uniform shell walk of cgnn_knn_periodic with its stopping rule and a list of distances alone (8, 16,
+ * 32 or 64 long by ranks[nk - 1]); the queries are first counting-sorted by their cell of the particles' grid, so the
+ * caller's order costs nothing.  No host synchronisation, everything on `stream`.  nq == 0: CGNN_OK, nothing is written.
+ * CGNN_ERR_INVALID_ARG for a null pointer, n <= 0, nq < 0, box_size not positive and finite, nk or ranks outside the
+ * above, a workspace that is not 16-byte aligned; CGNN_ERR_WORKSPACE for one too small; 2^31 or more particles, queries
+ * or cells: CGNN_ERR_UNSUPPORTED.  All of it is refused on the host before any launch.
+ * Workspace: a function of n and nq alone, O(n + nq), 16-byte aligned. */
+size_t cgnn_knn_distances_workspace_bytes(int64_t n, int64_t nq);
+int cgnn_knn_distances(const float* pos, int64_t n, const float* queries, int64_t nq, float box_size,
+                       const int32_t* ranks, int32_t nk, float* d2_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* How many queries have their k-th neighbour within each radius: the unnormalised empirical CDFs of the table above.
+ * d2_a (device, float [nq, nk]); d2_b (device, the same shape, or NULL); radii (HOST memory, nr floats): 1 <= nr <= 256,
+ * finite, radii[0] >= 0, strictly ascending.  With e2[b] = fl32(radii[b] * radii[b]) and
+ *     v[q, j] = d2_a[q, j]                         (d2_b == NULL)
+ *     v[q, j] = max(d2_a[q, j], d2_b[q, j])        (joint: the k-th neighbours of both sets lie within the radius)
+ * below (device, int64 [nk, nr]) is overwritten with below[j, b] = #{q : v[q, j] < e2[b]}: strict, the threshold rule
+ * of cgnn_pair_counts.  A NaN is below nothing.  Each value takes one binary search over e2; 32-bit LDS counters per
+ * workgroup of a grid-stride kernel, 64-bit integer atomics, a last pass that makes the sums cumulative: integers
+ * throughout, the same bits on every run.  nq == 0 gives zeros.  No workspace, no host synchronisation.
+ * CGNN_ERR_INVALID_ARG for a null pointer (d2_b excepted), nq < 0, nk outside [1, 16], nr or radii outside the above;
+ * 2^31 or more queries: CGNN_ERR_UNSUPPORTED. */
+int cgnn_knn_cdf_counts(const float* d2_a, const float* d2_b, int64_t nq, int32_t nk, const float* radii, int32_t nr,
+                        int64_t* below /* [nk][nr] */, void* stream);
+
 /* ---- judging a rollout: pair counts by separation, minimum-image frame errors -----------------------------
  * Exact pair counts in a periodic box of side box_size (the DD / D1D2 terms of the two-point correlation function).
  * pos_a [n_a, 3] and pos_b [n_b, 3] hold positions in [0, box_size] (a value of exactly box_size falls into the edge
