@@ -59,6 +59,7 @@ EXPORTS = (
     "cgnn_pair_counts_smu_workspace_bytes", "cgnn_pair_counts_smu",
     "cgnn_pair_velocity_sums_workspace_bytes", "cgnn_pair_velocity_sums",
     "cgnn_knn_distances_workspace_bytes", "cgnn_knn_distances", "cgnn_knn_cdf_counts",
+    "cgnn_bispectrum_shells", "cgnn_bispectrum_sums_workspace_bytes", "cgnn_bispectrum_sums",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
@@ -67,6 +68,10 @@ PAIR_VELOCITY_MAX_BINS = 64       # CGNN_PV_MAX_BINS in csrc/pair_velocities.hip
 KNN_DISTANCES_MAX_RANKS = 16      # CGNN_KD_MAX_RANKS in csrc/knn_distances.hip: ranks per call
 KNN_DISTANCES_MAX_K = 64          # CGNN_KD_MAX_K: the largest rank
 KNN_CDF_MAX_RADII = 256           # CGNN_KCDF_MAX_RADII
+BISPECTRUM_MAX_SHELLS = 32        # CGNN_BS_MAX_SHELLS in include/cgnn.h
+BISPECTRUM_MAX_TRIANGLES = 5984   # CGNN_BS_MAX_TRIANGLES: every i <= j <= l of 32 shells
+BISPECTRUM_CHUNK = 64             # CGNN_BS_CHUNK: cells a workgroup of cgnn_bispectrum_sums stages at a time
+BISPECTRUM_MAX_PARTS = 1024       # CGNN_BS_MAX_PARTS: slices of a frame's cells, at most
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
@@ -185,6 +190,10 @@ def load() -> C.CDLL:
     lib.cgnn_knn_distances_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_knn_distances.argtypes = [vp, i64, vp, i64, f32, C.POINTER(i32), i32, vp, vp, sz, vp]   # ranks: host memory
     lib.cgnn_knn_cdf_counts.argtypes = [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]             # radii: host memory
+    lib.cgnn_bispectrum_shells.argtypes = [vp, i64, i32, i32, vp, i32, vp, vp]
+    lib.cgnn_bispectrum_sums_workspace_bytes.restype = sz
+    lib.cgnn_bispectrum_sums_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cgnn_bispectrum_sums.argtypes = [vp, i64, i64, i32, C.POINTER(i32), i32, vp, vp, sz, vp]   # triangles: host memory
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]

@@ -1,7 +1,7 @@
 // Small pieces that several files share and that are no part of the fused MFMA kernels' cgnn_common.hpp: the alignment of
 // workspace arrays (every file that lays out a workspace), and what the device evaluators share (pair_counts.hip,
 // fof.hip, halo_match.hip, power_spectrum.hip): grouping the lanes of a wave by key, and binning a value by ascending
-// edges (with the int32 size edges of the group catalogues).
+// edges (with the int32 size edges of the group catalogues); the frequencies of a mode of the rfft array.
 #pragma once
 #include "cgnn_common.hpp"
 
@@ -38,6 +38,15 @@ __device__ __forceinline__ int bin_of(const T* e, int num_bins, T v) {
         if (e[mid] <= v) lo = mid; else up = mid;
     }
     return lo;
+}
+
+// mode index -> signed frequencies (nx, ny, nz) of the rfft array [M, M, Mh] (power_spectrum.hip, bispectrum.hip)
+__device__ __forceinline__ void pb_mode(int idx, int M, int Mh, int& nx, int& ny, int& nz) {
+    nz = idx % Mh;
+    const int r = idx / Mh;
+    const int iy = r % M, ix = r / M;
+    nx = ix <= M / 2 ? ix : ix - M;
+    ny = iy <= M / 2 ? iy : iy - M;
 }
 
 // group-size edges of a catalogue, by value in the kernel arguments

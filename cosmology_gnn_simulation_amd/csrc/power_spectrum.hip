@@ -281,15 +281,6 @@ struct PbEdges2 {
     float e2[CGNN_PB_MAX_BINS + 1];
 };
 
-// mode index -> (nx, ny, nz) of the rfft array [M, M, Mh]
-__device__ __forceinline__ void pb_mode(int idx, int M, int Mh, int& nx, int& ny, int& nz) {
-    nz = idx % Mh;
-    const int r = idx / Mh;
-    const int iy = r % M, ix = r / M;
-    nx = ix <= M / 2 ? ix : ix - M;
-    ny = iy <= M / 2 ? iy : iy - M;
-}
-
 __global__ __launch_bounds__(CGNN_BLOCK) void pb_ids_kernel(int M, int Mh, int modes, const PbEdges2 E, int num_bins,
                                                             int32_t* __restrict__ ids) {
     const int idx = blockIdx.x * CGNN_BLOCK + threadIdx.x;

@@ -1660,6 +1660,185 @@ def power_multipoles(delta_k: torch.Tensor, mesh: int, order: int, k_edges, los:
     return _power_sums(what, "cgnn_power_multipoles", _lib.POWER_MULTIPOLE_SUMS, given, mesh, order, k_edges, los, plan)
 
 
+def check_bispectrum_edges(mesh, k_edges, who: str) -> Tuple[int, List[float]]:
+    """``mesh`` and the shell edges of the bispectrum as ``(int, float32 host values)``, or ``ValueError``: what
+    :func:`check_mesh` and :func:`check_power_edges` refuse, more than 32 shells, and ``3 k_edges[-1] > mesh``.  Past that
+    limit three modes of the shells can add up to a multiple of ``mesh`` without adding up to zero, and the FFT
+    estimator counts such triples as closed triangles.  The limit is compared as the kernel bins, in float32
+    (:func:`bispectrum_top_edge`): ``mesh / 3`` itself is legal where float32 rounds it up, since no whole ``n2`` lies
+    between ``(mesh / 3)^2`` and the square of the rounded edge."""
+    mesh = check_mesh(mesh, who)
+    e = check_power_edges(k_edges, who)
+    if len(e) - 1 > _lib.BISPECTRUM_MAX_SHELLS:
+        raise ValueError(f"{who}: at most {_lib.BISPECTRUM_MAX_SHELLS} shells, got {len(e) - 1}")
+    if e[-1] > bispectrum_top_edge(mesh):
+        raise ValueError(f"{who}: 3 * k_edges[-1] = {3.0 * e[-1]:g} > mesh = {mesh}: modes of the shells would close "
+                         "triangles across the mesh's period")
+    return mesh, e
+
+
+def bispectrum_top_edge(mesh: int) -> float:
+    """The largest legal last edge of the bispectrum's shells: ``mesh / 3`` as a float32 value."""
+    return float(torch.tensor(mesh / 3.0, dtype=torch.float32))
+
+
+def bispectrum_triangles(k_edges) -> torch.Tensor:
+    """Every triple of shells ``i <= j <= l`` with ``k_edges[l] < k_edges[i + 1] + k_edges[j + 1]``: int32 ``[nt, 3]`` on
+    the HOST, ordered by ``(i, j, l)``.  A superset of the triples that hold a closed triangle of modes: the smallest
+    ``|k|`` of shell ``l`` must lie below the sum of the largest of the two others; a listed triple may be empty."""
+    e = check_power_edges(k_edges, "bispectrum_triangles")
+    nb = len(e) - 1
+    rows = [(i, j, l) for i in range(nb) for j in range(i, nb) for l in range(j, nb) if e[l] < e[i + 1] + e[j + 1]]
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 3)
+
+
+def check_triangles(triangles, num_shells: int, who: str) -> torch.Tensor:
+    """``triangles`` as a contiguous int32 ``[nt, 3]`` HOST tensor with ``0 <= i <= j <= l < num_shells`` and ``1 <= nt <=
+    5984``, or ``ValueError``; a device tensor is refused (``CgnnError``): the list is host data, like ``k_edges``."""
+    if isinstance(triangles, torch.Tensor) and triangles.is_cuda:
+        raise CgnnError(f"{who}: triangles are host values (the entry checks them before any device work); got a tensor "
+                        f"on {triangles.device}")
+    t = torch.as_tensor(triangles)
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{who}: triangles must be integers [nt, 3], got {t.dtype} {tuple(t.shape)}")
+    if not 1 <= t.shape[0] <= _lib.BISPECTRUM_MAX_TRIANGLES:
+        raise ValueError(f"{who}: 1 <= nt <= {_lib.BISPECTRUM_MAX_TRIANGLES} triangles, got {t.shape[0]}")
+    if bool((t[:, 0] < 0).any() | (t[:, 0] > t[:, 1]).any() | (t[:, 1] > t[:, 2]).any() | (t[:, 2] >= num_shells).any()):
+        raise ValueError(f"{who}: every triangle must be 0 <= i <= j <= l < {num_shells}")
+    return t.to(torch.int32).contiguous()
+
+
+def _check_window_order(order, who: str) -> int:
+    if isinstance(order, bool) or order not in (0, 1, 2, 3):
+        raise ValueError(f"{who}: order must be 0 (no deconvolution), 1, 2 or 3, got {order!r}")
+    return int(order)
+
+
+def _shell_filter(what: str, delta_k: Optional[torch.Tensor], frames: int, mesh: int, order: int, ids: torch.Tensor,
+                  nb: int) -> torch.Tensor:
+    """The timed call of ``cgnn_bispectrum_shells`` on checked arguments -> complex128 ``[frames, nb, M, M, M/2 + 1]``."""
+    out = torch.empty((frames, nb, mesh, mesh, mesh // 2 + 1), dtype=torch.complex128, device=ids.device)
+    with _timed(what, ids.device):
+        check(_lib.load().cgnn_bispectrum_shells(ptr(delta_k), frames, mesh, order, ids.data_ptr(), nb, out.data_ptr(),
+                                                 stream_ptr(ids.device)), "cgnn_bispectrum_shells")
+    return out
+
+
+def bispectrum_sums(fields: torch.Tensor, triangles) -> torch.Tensor:
+    """``sum_x D_i(x) D_j(x) D_l(x)`` for every listed triangle of shells (``cgnn_bispectrum_sums``): ``fields`` float64
+    ``[nb, cells]`` or ``[F, nb, cells]`` on the device (``nb <= 32`` shell fields of any number of cells), ``triangles``
+    integers ``[nt, 3]`` on the HOST (:func:`check_triangles`).  Returns float64 ``[nt]`` or ``[F, nt]`` on the device.
+    Every field value is read once, whatever ``nt`` is; a term is two single-rounded products, and every addition has a
+    place fixed by ``(cells, nt)``: two calls give the same bits.  No host synchronisation."""
+    what = "bispectrum_sums"
+    require_device(fields, "fields")
+    if fields.dtype != torch.float64 or fields.dim() not in (2, 3):
+        raise CgnnError(f"{what}: fields must be float64 [nb, cells] or [F, nb, cells], got {fields.dtype} "
+                        f"{tuple(fields.shape)}")
+    batched = fields.dim() == 3
+    f = fields.contiguous() if batched else fields.contiguous().unsqueeze(0)
+    frames, nb, cells = f.shape
+    if frames < 1 or cells < 1 or not 1 <= nb <= _lib.BISPECTRUM_MAX_SHELLS:
+        raise CgnnError(f"{what}: fields {tuple(fields.shape)}: at least one frame and one cell, 1 to "
+                        f"{_lib.BISPECTRUM_MAX_SHELLS} shells")
+    tri = check_triangles(triangles, nb, what)
+    nt = tri.shape[0]
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_bispectrum_sums_workspace_bytes(frames, cells, nt)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
+    sums = torch.full((frames, nt), float("nan"), dtype=torch.float64, device=f.device)
+    with _timed(what, f.device):
+        check(lib.cgnn_bispectrum_sums(f.data_ptr(), frames, cells, nb, C.cast(tri.data_ptr(), C.POINTER(C.c_int32)), nt,
+                                       sums.data_ptr(), ws.data_ptr(), ws_bytes, stream_ptr(f.device)),
+              "cgnn_bispectrum_sums")
+    return sums if batched else sums[0]
+
+
+def shell_fields(filtered: torch.Tensor, mesh: int) -> torch.Tensor:
+    """The shells of :func:`bispectrum_shells` in real space: ``torch.fft.irfftn(..., norm="forward")`` over the last
+    three axes (no ``1 / M^3``), float64 ``[..., M, M, M]``."""
+    return torch.fft.irfftn(filtered, s=(mesh, mesh, mesh), dim=(-3, -2, -1), norm="forward")
+
+
+class BispectrumPlan:
+    """What the bispectrum of one ``(mesh, k_edges)`` needs on one device: the bin of every mode (``ids``, int32, 4 bytes
+    per mode), the list of shell triples (``triangles``, int32 ``[nt, 3]`` on the HOST, :func:`bispectrum_triangles`) and
+    the number of closed triangles of modes in each (``counts``, int64 ``[nt]`` on the device; ``raw``, float64, what the
+    two entries and ``irfftn`` give for the fields of ones before ``rint``).  Refuses ``3 k_edges[-1] > mesh`` and more
+    than 32 shells on the host, before any device work.  Built without a host synchronisation; while it is built the
+    filtered ones and their fields are alive, ``nb (16 M^2 (M/2 + 1) + 8 M^3)`` bytes and the FFT's scratch.
+    ``BispectrumPlan.of`` keeps the last plan of each device (``BispectrumPlan.forget()`` drops them)."""
+
+    _last = {}
+
+    def __init__(self, mesh: int, k_edges, device):
+        self.mesh, edges = check_bispectrum_edges(mesh, k_edges, "BispectrumPlan")
+        self.edges, self.num_bins = tuple(edges), len(edges) - 1
+        self.triangles = bispectrum_triangles(edges)
+        self.ids = power_bin_ids(self.mesh, edges, device)
+        self.device = self.ids.device
+        ones = _shell_filter("BispectrumPlan", None, 1, self.mesh, 0, self.ids, self.num_bins)
+        fields = shell_fields(ones[0], self.mesh)
+        del ones
+        self.raw = bispectrum_sums(fields.reshape(self.num_bins, -1), self.triangles) / float(self.mesh) ** 3
+        self.counts = torch.round(self.raw).to(torch.int64)
+
+    @staticmethod
+    def forget() -> None:
+        """Drop the plans ``BispectrumPlan.of`` holds."""
+        BispectrumPlan._last.clear()
+
+    @staticmethod
+    def of(mesh: int, k_edges, device) -> "BispectrumPlan":
+        """The plan for ``(mesh, k_edges)`` on ``device``: the device's last one when it fits, else a new one."""
+        key = check_bispectrum_edges(mesh, k_edges, "BispectrumPlan")
+        key = (key[0], tuple(key[1]))
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        plan = BispectrumPlan._last.get(device)
+        if plan is None or (plan.mesh, plan.edges) != key:
+            plan = BispectrumPlan(mesh, k_edges, device)
+            BispectrumPlan._last[device] = plan
+        return plan
+
+
+def bispectrum_shells(delta_k: Optional[torch.Tensor], mesh: int, order: int, k_edges,
+                      plan: Optional[BispectrumPlan] = None) -> torch.Tensor:
+    """The modes of ``delta_k = torch.fft.rfftn(delta)`` filtered into the shells of ``k_edges`` with the window of a
+    deposit of ``order`` divided out (``cgnn_bispectrum_shells``): ``delta_k`` complex128 ``[M, M, M/2 + 1]`` or ``[F, M,
+    M, M/2 + 1]``; returns complex128 ``[nb, M, M, M/2 + 1]`` (``[F, nb, ...]``) with ``out[i] = delta_k / W`` on the modes
+    of shell ``i`` (``W = (sinc sinc sinc)^order``, the amplitude; order 0: the bits of ``delta_k``) and exactly 0
+    elsewhere.  ``delta_k=None`` (``plan`` must be given: it names the device) writes 1 on every shell's modes, the
+    fields that count triangles.  ``plan``: a :class:`BispectrumPlan` of ``(mesh, k_edges)`` (default
+    ``BispectrumPlan.of``).  :func:`shell_fields` takes the result to real space.  No host synchronisation."""
+    what = "bispectrum_shells"
+    mesh, e = check_bispectrum_edges(mesh, k_edges, what)
+    order = _check_window_order(order, what)
+    shape = (mesh, mesh, mesh // 2 + 1)
+    if delta_k is None:
+        if plan is None:
+            raise ValueError(f"{what}: without delta_k a plan must be given (it names the device)")
+    else:
+        require_device(delta_k, "delta_k")
+        if delta_k.dtype != torch.complex128 or delta_k.dim() not in (3, 4) or tuple(delta_k.shape[-3:]) != shape:
+            raise CgnnError(f"{what}: delta_k must be complex128 [..., {mesh}, {mesh}, {mesh // 2 + 1}], got "
+                            f"{delta_k.dtype} {tuple(delta_k.shape)}")
+        if plan is None:
+            plan = BispectrumPlan.of(mesh, e, delta_k.device)
+    if plan.mesh != mesh or plan.edges != tuple(e) or (delta_k is not None and plan.device != delta_k.device):
+        raise CgnnError(f"{what}: the plan was built for another mesh, other edges or another device")
+    if delta_k is None:
+        return _shell_filter(what, None, 1, mesh, 0, plan.ids, plan.num_bins)[0]
+    batched = delta_k.dim() == 4
+    d = delta_k.contiguous()
+    frames = d.shape[0] if batched else 1
+    if frames < 1:
+        raise CgnnError(f"{what}: no frames")
+    out = _shell_filter(what, d, frames, mesh, order, plan.ids, plan.num_bins)
+    return out if batched else out[0]
+
+
 def check_linking_length(linking_length, box_size: float, who: str) -> float:
     """The linking length of :func:`fof_labels` as a float32 host value, or ``ValueError``: finite, positive and at most
     ``fl32(0.5 * box_size)``, ``box_size`` finite and positive.  Callers check before any device work."""

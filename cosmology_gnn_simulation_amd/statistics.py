@@ -50,7 +50,11 @@ the k-nearest-neighbour distance distributions of a frame seen from a lattice of
 ``ops.knn_cdf_counts``; ``query_lattice``, ``default_knn_radii``), with the void probability function, the
 counts-in-spheres distribution and, for two sets, the joint CDF and its excess over independence;
 ``rollout_knn_cdfs`` does that for every frame of a rollout against the truth and ``knn_cdfs_from_counts`` is the host
-arithmetic.
+arithmetic.  At which scales and in which configurations the non-Gaussianity sits, which the kNN-CDFs do not say:
+``bispectrum`` gives B(k1, k2, k3) and the reduced Q of a frame by the FFT estimator -- the modes filtered into shells
+(``ops.bispectrum_shells``), every shell back in real space, the products of three shell fields summed over the mesh
+(``ops.bispectrum_sums``) -- ``rollout_bispectra`` does that for every frame of a rollout against the truth,
+``bispectrum_from_sums`` is the host arithmetic and ``default_bispectrum_edges`` the shells up to a third of the mesh.
 
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
@@ -294,10 +298,10 @@ def _shell_sums(pos_a: torch.Tensor, pos_b: Optional[torch.Tensor], box_size: fl
     return (modes[0], sums[0]) if len(modes) == 1 else (torch.cat(modes), torch.cat(sums))
 
 
-def _to_host(modes: torch.Tensor, sums: torch.Tensor, extra: Optional[torch.Tensor] = None):
-    """One transfer: the float64 sums, and the float64 ``extra`` if there is one, travel as their bits among the
-    integers -> ``(modes, sums)`` or ``(modes, sums, extra)`` on the CPU."""
-    parts = [modes, sums] if extra is None else [modes, sums, extra.contiguous()]
+def _to_host(modes: torch.Tensor, sums: torch.Tensor, *extra: Optional[torch.Tensor]):
+    """One transfer: the float64 sums, and every float64 or int64 ``extra`` that is not None, travel as their bits among
+    the integers -> ``(modes, sums, *extra)`` on the CPU."""
+    parts = [modes, sums] + [x.contiguous() for x in extra if x is not None]
     packed = torch.cat([p.view(torch.int64).reshape(-1) for p in parts]).cpu()
     host = packed.split([p.numel() for p in parts])
     return tuple(h.view(p.dtype).reshape(p.shape) for h, p in zip(host, parts))
@@ -1949,3 +1953,175 @@ def rollout_knn_cdfs(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[s
         i = ranks.index(1)
         out["vpf_pred"], out["vpf_true"] = res["vpf"], 1.0 - res["cdf_b"][..., i, :]
     return out
+
+
+# ---- the bispectrum --------------------------------------------------------------------------------------------------
+#
+# The three-point function in Fourier space, by the FFT estimator (Scoccimarro 2015).  For shell i of ``k_edges``,
+# ``D_i(x) = sum over the shell's modes of delta_k / W e^{ikx}`` (``ops.bispectrum_shells``, ``ops.shell_fields``) and
+# ``I_i(x)`` the same with 1 for ``delta_k / W``.  ``sum_x D_i D_j D_l / M^3`` is the sum of ``delta_k1 delta_k2 delta_k3``
+# over every closed triangle ``k1 + k2 + k3 = 0`` with one mode in each shell, ``sum_x I_i I_j I_l / M^3`` their number
+# (``ops.BispectrumPlan.counts``) -- as long as ``k1 + k2 + k3 = 0 (mod M)`` means ``= 0``: ``3 k_edges[-1] <= mesh``.
+# Cross-bispectra of two fields, interlacing (every shell lies at or below a third of the mesh, where aliasing is
+# mild), redshift-space multipoles of B, a float32 path, batched, sharded and owned-storage variants, a bispectrum
+# loss and more than 32 shells are not built.
+
+
+def default_bispectrum_edges(mesh: int, num_shells: Optional[int] = None) -> torch.Tensor:
+    """Equal-width shells from 0.5 up to the largest edge at or below ``mesh / 3`` (float64, units of ``2 pi / L``):
+    ``num_shells`` of them, by default ``min(16, floor(mesh / 3 - 0.5))`` and at least one.  The width is the largest
+    whole number that fits, so the shells stay centred on whole frequencies (mesh 256: 16 shells of width 5 up to 80.5;
+    mesh 32 with 4 shells: 0.5, 2.5, .., 8.5); where not even width 1 fits, the shells divide ``[0.5, mesh / 3]``."""
+    mesh = ops.check_mesh(mesh, "default_bispectrum_edges")
+    span = mesh / 3.0 - 0.5
+    if num_shells is None:
+        num_shells = max(1, min(16, int(math.floor(span))))
+    if isinstance(num_shells, bool) or int(num_shells) != num_shells or not 1 <= num_shells <= _lib.BISPECTRUM_MAX_SHELLS:
+        raise ValueError(f"default_bispectrum_edges: num_shells must be a whole number in [1, "
+                         f"{_lib.BISPECTRUM_MAX_SHELLS}], got {num_shells!r}")
+    num_shells = int(num_shells)
+    width = float(math.floor(span / num_shells))
+    if width < 1.0:
+        width = span / num_shells
+    edges = 0.5 + width * torch.arange(num_shells + 1, dtype=torch.float64)
+    edges[-1] = min(float(edges[-1]), ops.bispectrum_top_edge(mesh))      # a fractional width may overshoot by an ulp
+    return edges
+
+
+def bispectrum_from_sums(counts, triangle_sums, triangles, modes, sums, n: int, box_size: float, mesh: int, k_edges,
+                         subtract_shot_noise: bool = True) -> Dict:
+    """The bispectrum from the triangle sums, on the host in float64: a pure function of ``counts [nt]`` (the closed
+    triangles of modes per listed triple, ``ops.BispectrumPlan.counts``), ``triangle_sums [..., nt]`` (``sum_x D_i D_j
+    D_l`` as ``ops.bispectrum_sums`` gives it), ``triangles [nt, 3]``, the ``modes [..., nb]`` and ``sums [..., 4, nb]``
+    of ``ops.power_bins`` on the same edges, the number of particles ``n``, ``L = box_size`` and ``M = mesh``.  With
+    ``P^_i = L^3 S_i / modes_i / M^6`` the shell power with its shot noise, ``nbar = n / L^3`` and ``N`` the count:
+
+    * ``bispectrum``: ``B_meas = L^6 / M^9 (triangle_sums / M^3) / N``, and with ``subtract_shot_noise``
+      ``B = B_meas - (P^_i + P^_j + P^_l) / nbar + 2 / nbar^2``; ``nan`` where ``N == 0``;
+    * ``power`` ``[..., nb]``: ``P = P^ - 1 / nbar`` with ``subtract_shot_noise``, else ``P^``;
+    * ``reduced_bispectrum``: ``Q = B / (P_i P_j + P_j P_l + P_l P_i)`` from that ``power``;
+    * ``gaussian_sigma``: ``sqrt(s L^3 P^_i P^_j P^_l / N)`` with ``s`` = 6, 2 or 1 for three, two or no equal shell
+      indices: the scatter of ``B`` for a Gaussian field of that power;
+    * ``k1``, ``k2``, ``k3``: the mean ``|k|`` of the three shells (row 3 of ``power_bins``);
+
+    plus ``triangles`` (int64 ``[nt, 3]``) and ``count`` (int64 ``[nt]``).  CPU, float64, ``[..., nt]``."""
+    what = "bispectrum_from_sums"
+    box, _, modes, sums, shell_modes, norm = _sums_on_host(what, modes, sums, 4, box_size, mesh, k_edges)
+    nb = modes.shape[-1]
+    tri = ops.check_triangles(torch.as_tensor(triangles).detach().cpu(), nb, what).to(torch.int64)
+    count = torch.as_tensor(counts).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+    ts = torch.as_tensor(triangle_sums).detach().to(device="cpu", dtype=torch.float64)
+    if count.numel() != tri.shape[0] or ts.shape[-1] != tri.shape[0] or ts.shape[:-1] != modes.shape[:-1]:
+        raise ValueError(f"{what}: counts {tuple(count.shape)}, triangle_sums {tuple(ts.shape)} and modes "
+                         f"{tuple(modes.shape)} do not fit {tri.shape[0]} triangles")
+    if isinstance(n, bool) or int(n) != n or int(n) < 1:
+        raise ValueError(f"{what}: n must be a whole number of at least 1, got {n!r}")
+    m = float(mesh)
+    nbar = int(n) / box ** 3
+    p_hat = norm * sums[..., 0, :] / shell_modes
+    power = p_hat - 1.0 / nbar if subtract_shot_noise else p_hat
+    i, j, l = tri[:, 0], tri[:, 1], tri[:, 2]
+    num = count.to(torch.float64)
+    num = torch.where(count > 0, num, torch.full_like(num, float("nan")))
+    b = box ** 6 / m ** 9 * (ts / m ** 3) / num
+    hi, hj, hl = p_hat[..., i], p_hat[..., j], p_hat[..., l]
+    if subtract_shot_noise:
+        b = b - (hi + hj + hl) / nbar + 2.0 / nbar ** 2
+    pi, pj, pl = power[..., i], power[..., j], power[..., l]
+    sym = torch.where((i == j) & (j == l), 6.0, torch.where((i == j) | (j == l), 2.0, 1.0)).to(torch.float64)
+    k_mean = sums[..., 3, :] / shell_modes * (2.0 * math.pi / box)
+    return {"triangles": tri, "count": count, "k1": k_mean[..., i], "k2": k_mean[..., j], "k3": k_mean[..., l],
+            "bispectrum": b, "reduced_bispectrum": b / (pi * pj + pj * pl + pl * pi), "power": power,
+            "gaussian_sigma": torch.sqrt(sym * box ** 3 * hi * hj * hl / num)}
+
+
+def _check_bispectrum_arguments(what: str, box_size, mesh, k_edges, order):
+    mesh = ops.check_mesh(mesh, what)
+    mesh, k_edges = ops.check_bispectrum_edges(mesh, default_bispectrum_edges(mesh) if k_edges is None else k_edges, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    return mesh, k_edges
+
+
+def _triangle_sums(sets, box_size: float, mesh: int, k_edges, order: int):
+    """For every set of frames ``[F, N, 3]`` in ``sets`` the device tensors ``(modes [F, nb], sums [F, 4, nb],
+    triangle_sums [F, nt])`` of its density contrast, and the :class:`ops.BispectrumPlan`.  Frames go through in chunks
+    that fit the free device memory: per frame and set ``nb 16 M^2 (M/2 + 1)`` bytes of filtered modes, ``nb 8 M^3`` of
+    shell fields and the contrast, its transform and the int64 mesh of ``_shell_sums``, and as much again for the FFT's
+    scratch.  The filtered modes of a chunk are gone before its triangle sums are made, its fields before the next chunk."""
+    from .training import free_device_bytes
+    n_frames, nb, dev = sets[0].shape[0], len(k_edges) - 1, sets[0].device
+    half = mesh * mesh * (mesh // 2 + 1)
+    per_frame = 2 * (nb * (16 * half + 8 * mesh ** 3) + 16 * mesh ** 3 + 16 * half) * len(sets)
+    chunk = max(1, min(n_frames, free_device_bytes(dev) // per_frame))
+    plan = ops.BispectrumPlan.of(mesh, k_edges, dev)
+    power_plan = ops.PowerPlan.of(mesh, k_edges, dev)
+    out = [([], [], []) for _ in sets]
+    for f0 in range(0, n_frames, chunk):
+        for pos, (modes, sums, tsums) in zip(sets, out):
+            delta_k = _contrast_modes(pos[f0:f0 + chunk], box_size, mesh, order)
+            m, s = ops.power_bins(delta_k, mesh, order, k_edges, None, power_plan)
+            filtered = ops.bispectrum_shells(delta_k, mesh, order, k_edges, plan)
+            del delta_k
+            fields = ops.shell_fields(filtered, mesh)
+            del filtered
+            tsums.append(ops.bispectrum_sums(fields.reshape(fields.shape[0], nb, -1), plan.triangles))
+            del fields
+            modes.append(m)
+            sums.append(s)
+    return [tuple(p[0] if len(p) == 1 else torch.cat(p) for p in parts) for parts in out], plan
+
+
+def bispectrum(pos: torch.Tensor, box_size: float, mesh: int, k_edges=None, order: int = 2,
+               subtract_shot_noise: bool = True) -> Dict:
+    """The bispectrum of ``pos [N, 3]`` (or of every frame of ``[T, N, 3]``) on a ``mesh^3`` grid, deposited with
+    ``order`` (1 = NGP, 2 = CIC, 3 = TSC) and deconvolved by that window, for every triple of the shells ``k_edges``
+    (``nb + 1 <= 33`` edges in units of ``2 pi / L`` with ``3 k_edges[-1] <= mesh``; default
+    :func:`default_bispectrum_edges`) that can hold a closed triangle.  Returns the dict of :func:`bispectrum_from_sums`
+    (CPU; ``[nt]`` or ``[T, nt]``, ``power`` ``[nb]`` or ``[T, nb]``).  Everything is computed on the device of ``pos``
+    without a host synchronisation and comes back in one transfer."""
+    what = "bispectrum"
+    mesh, k_edges = _check_bispectrum_arguments(what, box_size, mesh, k_edges, order)
+    frames = _frames3(pos, "pos", what)
+    ((modes, sums, tsums),), plan = _triangle_sums([frames], box_size, mesh, k_edges, order)
+    modes, sums, tsums, counts = _to_host(modes, sums, tsums, plan.counts)
+    if pos.dim() == 2:
+        modes, sums, tsums = modes[0], sums[0], tsums[0]
+    return bispectrum_from_sums(counts, tsums, plan.triangles, modes, sums, frames.shape[1], box_size, mesh, k_edges,
+                                subtract_shot_noise)
+
+
+def rollout_bispectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                      mesh: int, k_edges=None, order: int = 2, frames: Optional[Sequence[int]] = None) -> Dict:
+    """Bispectra of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N, 3]``):
+    two frames can agree in P(k), r(k) and T(k) and still have the wrong filaments, and the amplitude and the shape
+    dependence of B are where that shows first.  ``frames``: the frame numbers to judge (default: every frame both
+    hold).  Per selected frame (CPU, float64, ``[F, nt]``; shot noise subtracted):
+
+    * ``bispectrum_pred``, ``bispectrum_true``, ``reduced_bispectrum_pred``, ``reduced_bispectrum_true``;
+    * ``power_pred``, ``power_true`` (``[F, nb]``): the shell power behind Q;
+    * ``bispectrum_ratio = B_pred / B_true``;
+    * ``gaussian_sigma_true`` and ``difference_sigma = (B_pred - B_true) / gaussian_sigma_true``,
+
+    plus ``frames``, ``triangles`` (``[nt, 3]``), ``count`` (``[nt]``), ``k1``, ``k2``, ``k3`` (``[nt]``, of the first
+    true frame: the shells' mean ``|k|`` depend on the mesh alone) and ``equilateral``, the indices of the ``i = j = l``
+    triangles.  No host synchronisation per frame; one transfer at the end."""
+    what = "rollout_bispectra"
+    mesh, k_edges = _check_bispectrum_arguments(what, box_size, mesh, k_edges, order)
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
+    n = pc.shape[1]
+    (pred, true), plan = _triangle_sums([pc, tc], box_size, mesh, k_edges, order)
+    host = _to_host(*pred, *true, plan.counts)
+    counts = host[6]
+    p = bispectrum_from_sums(counts, host[2], plan.triangles, host[0], host[1], n, box_size, mesh, k_edges)
+    t = bispectrum_from_sums(counts, host[5], plan.triangles, host[3], host[4], n, box_size, mesh, k_edges)
+    tri = t["triangles"]
+    return {"frames": sel, "triangles": tri, "count": t["count"], "k1": t["k1"][0].clone(), "k2": t["k2"][0].clone(),
+            "k3": t["k3"][0].clone(), "bispectrum_pred": p["bispectrum"], "bispectrum_true": t["bispectrum"],
+            "reduced_bispectrum_pred": p["reduced_bispectrum"], "reduced_bispectrum_true": t["reduced_bispectrum"],
+            "power_pred": p["power"], "power_true": t["power"], "gaussian_sigma_true": t["gaussian_sigma"],
+            "bispectrum_ratio": p["bispectrum"] / t["bispectrum"],
+            "difference_sigma": (p["bispectrum"] - t["bispectrum"]) / t["gaussian_sigma"],
+            "equilateral": torch.nonzero((tri[:, 0] == tri[:, 1]) & (tri[:, 1] == tri[:, 2])).reshape(-1).tolist()}

@@ -841,6 +841,55 @@ int cgnn_power_multipoles(const double* a, const double* b, const double* a2, co
                           int32_t num_bins, int64_t* modes, double* sums, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- the bispectrum: shell-filtered modes and triangle sums ----------------------------------------------------------
+ * The FFT estimator of the bispectrum (Scoccimarro 2015): the modes of a frame's transform are filtered into shells of
+ * |k|, every shell goes back to real space (torch.fft.irfftn between the two entries) and the product of three shell
+ * fields, summed over the mesh, is the sum of delta_k1 delta_k2 delta_k3 over all closed triangles of modes in the three
+ * shells.  This holds without wrap-around only: 3 k_edges[num_bins] <= mesh, which the CALLER guarantees.
+ *
+ * cgnn_bispectrum_shells: delta_k (device, complex128 as (re, im) pairs, [frames, mesh, mesh, mesh/2 + 1], 16-byte
+ * aligned, or NULL); ids (device, int32 [mesh^2 (mesh/2 + 1)]: what cgnn_power_bin_ids writes for num_bins bins);
+ * out (device, complex128 [frames, num_bins, mesh, mesh, mesh/2 + 1], 16-byte aligned, every element written).  For a
+ * mode with ids[mode] == i, 0 <= i < num_bins,
+ *     out[f, i, mode] = (delta_k[f, mode].re * invw, delta_k[f, mode].im * invw)
+ *     invw = (t[|nx|] * t[|ny|]) * t[nz],   t[n] = 1 / sinc(pi n / mesh)^order,  t[0] = 1
+ * in float64 with one rounding per operation (sinc = sin(x) / x, the power by repeated multiplication from sinc, then
+ * one division): the AMPLITUDE of the deposit's window, not the W2 of cgnn_power_bins; order 0..3, 0: invw = 1 and the
+ * values are delta_k's bits.  Everywhere else, and for every mode with an id outside [0, num_bins), out is exactly
+ * 0 + 0i.  With delta_k == NULL (frames must be 1) the shell's modes receive 1 + 0i instead, with no window: the
+ * fields whose triangle sums count the closed triangles.  t is built per workgroup in LDS; one thread per mode and
+ * frame reads delta_k and ids once and makes num_bins coalesced 16-byte stores.  No workspace, no host synchronisation.
+ * CGNN_ERR_INVALID_ARG for a null ids or out, frames <= 0 (or != 1 without delta_k), mesh outside [2, 512], order
+ * outside [0, 3], num_bins outside [1, CGNN_BS_MAX_SHELLS], pointers not 16-byte aligned; all before any launch.
+ *
+ * cgnn_bispectrum_sums: fields (device, double [frames, num_bins, cells]; cells any positive number, not only a cube);
+ * triangles (HOST memory, int32 [num_triangles, 3]: shell indices 0 <= i <= j <= l < num_bins; a triangle may be listed
+ * more than once; they reach the device by value in kernel arguments); sums (device, double [frames, num_triangles],
+ * overwritten):
+ *     sums[f, t] = sum over x < cells of (fields[f, i, x] * fields[f, j, x]) * fields[f, l, x]
+ * Float64, one rounding per operation, no FMA: two products, then one addition per cell.  The additions have fixed
+ * places that depend on (cells, num_triangles) alone, never on the device: with chunks = ceil(cells / CGNN_BS_CHUNK),
+ * per = ceil(chunks / CGNN_BS_MAX_PARTS) and parts = ceil(chunks / per), part p owns the cells [p per CGNN_BS_CHUNK,
+ * (p + 1) per CGNN_BS_CHUNK) below `cells` and adds their terms to 0.0 in ascending cell order; the parts are then
+ * added to 0.0 in ascending part order.  No float atomics: two runs give the same bits.  Every field value is read
+ * from device memory once per call, whatever num_triangles is: a workgroup stages CGNN_BS_CHUNK cells of all shells in
+ * LDS, and thread t of 256 owns the triangles t, t + 256, ... in registers.  No host synchronisation.
+ * CGNN_ERR_INVALID_ARG for a null pointer, frames or cells <= 0, num_bins outside [1, CGNN_BS_MAX_SHELLS],
+ * num_triangles outside [1, CGNN_BS_MAX_TRIANGLES], a triangle that is not 0 <= i <= j <= l < num_bins, a workspace
+ * that is not 16-byte aligned; CGNN_ERR_WORKSPACE for one too small; more than 2^20 frames: CGNN_ERR_UNSUPPORTED.  All
+ * of it is refused on the host before any device work.
+ * Workspace: cgnn_bispectrum_sums_workspace_bytes(frames, cells, num_triangles), a function of these three alone (256
+ * for arguments the entry refuses). */
+#define CGNN_BS_MAX_SHELLS 32
+#define CGNN_BS_MAX_TRIANGLES 5984   /* 32 * 33 * 34 / 6: every i <= j <= l of 32 shells */
+#define CGNN_BS_CHUNK 64             /* cells a workgroup stages at a time */
+#define CGNN_BS_MAX_PARTS 1024       /* slices of the cells of a frame, at most */
+int cgnn_bispectrum_shells(const double* delta_k, int64_t frames, int32_t mesh, int32_t order, const int32_t* ids,
+                           int32_t num_bins, double* out, void* stream);
+size_t cgnn_bispectrum_sums_workspace_bytes(int64_t frames, int64_t cells, int32_t num_triangles);
+int cgnn_bispectrum_sums(const double* fields, int64_t frames, int64_t cells, int32_t num_bins, const int32_t* triangles,
+                         int32_t num_triangles, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- judging a rollout by its halos: friends-of-friends groups and their catalogue ------------------------------------
  * cgnn_fof_labels labels the connected components of "closer than the linking length" among pos [n, 3] (positions in
  * [0, box_size]; a value of exactly box_size falls into the edge cell) in a periodic box of side box_size.  With d2(i, j)
