@@ -60,11 +60,15 @@ EXPORTS = (
     "cgnn_pair_velocity_sums_workspace_bytes", "cgnn_pair_velocity_sums",
     "cgnn_knn_distances_workspace_bytes", "cgnn_knn_distances", "cgnn_knn_cdf_counts",
     "cgnn_bispectrum_shells", "cgnn_bispectrum_sums_workspace_bytes", "cgnn_bispectrum_sums",
+    "cgnn_triplet_moments_workspace_bytes", "cgnn_triplet_moments",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
 PAIR_COUNTS_SMU_MAX_AXIS = 128    # CGNN_SMU_MAX_AXIS: bins per axis at most
 PAIR_VELOCITY_MAX_BINS = 64       # CGNN_PV_MAX_BINS in csrc/pair_velocities.hip
+THREE_POINT_MAX_BINS = 16         # CGNN_TP_MAX_BINS in csrc/three_point.hip
+THREE_POINT_MAX_L = 4             # CGNN_TP_MAX_L: monomials up to degree 4, 35 of them
+THREE_POINT_MAX_UNIT_BITS = 20    # CGNN_TP_MAX_UNIT_BITS: a monomial of 1 is 2^unit_bits
 KNN_DISTANCES_MAX_RANKS = 16      # CGNN_KD_MAX_RANKS in csrc/knn_distances.hip: ranks per call
 KNN_DISTANCES_MAX_K = 64          # CGNN_KD_MAX_K: the largest rank
 KNN_CDF_MAX_RADII = 256           # CGNN_KCDF_MAX_RADII
@@ -186,6 +190,10 @@ def load() -> C.CDLL:
     lib.cgnn_pair_velocity_sums_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cgnn_pair_velocity_sums.argtypes = [vp, vp, i64, vp, vp, i64, f32, C.POINTER(f32), i32, vp, vp, vp, sz,
                                             vp]                                             # edges: host memory
+    lib.cgnn_triplet_moments_workspace_bytes.restype = sz
+    lib.cgnn_triplet_moments_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.cgnn_triplet_moments.argtypes = [vp, i64, vp, i64, f32, C.POINTER(f32), i32, i32, i32, vp, vp, vp, vp, sz,
+                                         vp]                                                # edges: host memory
     lib.cgnn_knn_distances_workspace_bytes.restype = sz
     lib.cgnn_knn_distances_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_knn_distances.argtypes = [vp, i64, vp, i64, f32, C.POINTER(i32), i32, vp, vp, sz, vp]   # ranks: host memory

@@ -1014,6 +1014,77 @@ def pair_velocity_sums(pos_a: torch.Tensor, q_a: torch.Tensor, box_size: float, 
     return (counts, sums) if batched else (counts[0], sums[0])
 
 
+def triplet_monomials(lmax: int) -> int:
+    """Monomials ``x^a y^b z^c`` of degree ``a + b + c <= lmax``: 1, 4, 10, 20, 35 for ``lmax = 0 .. 4``."""
+    return (lmax + 1) * (lmax + 2) * (lmax + 3) // 6
+
+
+def check_triplet_arguments(edges, box_size: float, lmax, unit_bits, who: str) -> List[float]:
+    """The radii of :func:`triplet_moments` as float32 host values, or ``ValueError``: the rules of
+    :func:`check_pair_count_edges` with at most 16 bins (``_lib.THREE_POINT_MAX_BINS``: a primary's moments are rows of
+    LDS sums), ``0 <= lmax <= 4`` and ``1 <= unit_bits <= 20`` whole numbers.  Callers check before any device work."""
+    e = check_pair_count_edges(edges, box_size, who)
+    if len(e) - 1 > _lib.THREE_POINT_MAX_BINS:
+        raise ValueError(f"{who}: {len(e) - 1} bins; one call takes 1 to {_lib.THREE_POINT_MAX_BINS}")
+    for name, v, lo, hi in (("lmax", lmax, 0, _lib.THREE_POINT_MAX_L),
+                            ("unit_bits", unit_bits, 1, _lib.THREE_POINT_MAX_UNIT_BITS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{who}: {name} must be a whole number in [{lo}, {hi}], got {v!r}")
+    return e
+
+
+def triplet_moments(pos: torch.Tensor, box_size: float, edges, lmax: int = 4, pos_b: Optional[torch.Tensor] = None,
+                    unit_bits: int = 20, return_moments: bool = False, check_bounds: bool = False, *,
+                    return_pairs: bool = False):
+    """The power sums behind the multipoles ``zeta_l(r1, r2)`` of the three-point correlation function
+    (``cgnn_triplet_moments``; Slepian & Eisenstein 2015): ``T`` float64 ``[lmax + 1, nb, nb]`` for the primaries ``pos
+    [N, 3]``, with a leading ``T`` for ``[T, N, 3]`` (one call per frame on the same stream, no host synchronisation
+    between them).  The neighbours are ``pos_b`` (``[M, 3]`` or ``[T, M, 3]``), or the primaries themselves (auto: a
+    primary is not its own neighbour).  ``edges``: ``nb + 1`` ascending radii as in :func:`pair_counts`, ``nb <= 16``.
+
+    A neighbour counts for a primary iff ``d2 > 0`` and ``e2[0] <= d2 < e2[nb]`` (the pair counter's ``d2`` and bin;
+    coincident particles have no direction and count for nothing).  With ``u`` its float32 unit vector, every monomial
+    ``u_x^a u_y^b u_z^c`` of degree ``1 .. lmax`` is rounded to a whole number of ``2^-unit_bits`` and summed per primary
+    ``i`` and bin into the exact integers ``M[i, b, alpha]`` (``alpha = 0``: the count; the order and every rounding are
+    in ``include/cgnn.h``).  ``T[n, b1, b2] = sum_i sum_{|alpha| = n} mult(alpha) M[i, b1, alpha] M[i, b2, alpha]`` in
+    float64 and a fixed order: the sum of ``(u_ij . u_ik)^n 2^(2 unit_bits)`` over every primary ``i`` and its neighbours
+    ``j`` in ``b1``, ``k`` in ``b2`` -- ``j == k`` included when ``b1 == b2``.  :func:`statistics.three_point_from_sums`
+    turns them into Legendre multipoles.
+
+    ``return_moments=True`` appends ``M`` int64 ``[(T,) N, nb, n_mono]`` (:func:`triplet_monomials`) in the order of
+    ``pos``; ``return_pairs=True`` appends ``pairs`` int64 ``[(T,) nb]``, the counted ordered pairs ``sum_i M[i, b, 0]``
+    (twice :func:`pair_counts` in auto mode when no two particles coincide).  The integers are exact and everything is
+    the same bits on every run.  Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host
+    synchronisation, the default verifies nothing.  No host synchronisation.  Scope as :func:`pair_counts`: one box
+    per call."""
+    what = "triplet_moments"
+    e = check_triplet_arguments(edges, box_size, lmax, unit_bits, what)
+    nb = len(e) - 1
+    frames_a, frames_b, batched = _pair_frames(what, pos, pos_b, box_size, check_bounds)
+    t, n_a = frames_a.shape[0], frames_a.shape[1]
+    n_b = 0 if frames_b is None else frames_b.shape[1]
+    lib = _lib.load()
+    edges_c = (C.c_float * (nb + 1))(*e)
+    ws_bytes = lib.cgnn_triplet_moments_workspace_bytes(n_a, n_b, lmax, nb)
+    dev = frames_a.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    sums = torch.empty((t, lmax + 1, nb, nb), dtype=torch.float64, device=dev)
+    pairs = torch.empty((t, nb), dtype=torch.int64, device=dev)
+    moments = torch.empty((t, n_a, nb, triplet_monomials(lmax)), dtype=torch.int64, device=dev) if return_moments else None
+    st = stream_ptr(dev)
+    with _timed(what, dev):
+        for f in range(t):
+            check(lib.cgnn_triplet_moments(frames_a[f].data_ptr(), n_a,
+                                           None if frames_b is None else frames_b[f].data_ptr(), n_b, float(box_size),
+                                           edges_c, nb, lmax, unit_bits, sums[f].data_ptr(), pairs[f].data_ptr(),
+                                           None if moments is None else moments[f].data_ptr(), ws.data_ptr(), ws_bytes,
+                                           st), "cgnn_triplet_moments")
+    out = [sums] + ([moments] if return_moments else []) + ([pairs] if return_pairs else [])
+    if not batched:
+        out = [x[0] for x in out]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def check_knn_ranks(ks, who: str) -> List[int]:
     """The ranks of :func:`knn_distances` as host ints, or ``ValueError``: ``1 <= nk <= 16`` whole numbers (no bools, no
     fractions), strictly ascending, ``1 <= k <= 64``.  Callers check before any device work."""

@@ -55,6 +55,12 @@ arithmetic.  At which scales and in which configurations the non-Gaussianity sit
 (``ops.bispectrum_shells``), every shell back in real space, the products of three shell fields summed over the mesh
 (``ops.bispectrum_sums``) -- ``rollout_bispectra`` does that for every frame of a rollout against the truth,
 ``bispectrum_from_sums`` is the host arithmetic and ``default_bispectrum_edges`` the shells up to a third of the mesh.
+Its partner below the mesh, where filaments and halo outskirts live: ``three_point_correlation`` gives the Legendre
+multipoles zeta_l(r1, r2) of the connected three-point function from exact pair walks -- per primary and radial bin the
+integer sums of the monomials of the directions to its neighbours, contracted over two bins in float64
+(``ops.triplet_moments``), once around the particles and once around a lattice of query points;
+``rollout_three_point`` does that for every frame of a rollout against the truth, ``three_point_from_sums`` and
+``three_point_zeta`` are the host arithmetic and ``default_three_point_edges`` the 8 bins from 0.5 to 4.5 spacings.
 
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
@@ -2125,3 +2131,201 @@ def rollout_bispectra(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[
             "bispectrum_ratio": p["bispectrum"] / t["bispectrum"],
             "difference_sigma": (p["bispectrum"] - t["bispectrum"]) / t["gaussian_sigma"],
             "equilateral": torch.nonzero((tri[:, 0] == tri[:, 1]) & (tri[:, 1] == tri[:, 2])).reshape(-1).tolist()}
+
+
+# ---- the three-point correlation function ----------------------------------------------------------------------------
+#
+# The bispectrum's partner below the mesh: the connected three-point function in configuration space, as Legendre
+# multipoles in the angle between the two sides of a triangle that meet at a primary,
+#     zeta(r1, r2, u1 . u2) = sum_l zeta_l(r1, r2) P_l(u1 . u2),
+# by the O(N neighbours) algorithm of Slepian & Eisenstein (2015): per primary and radial bin the sums of the monomials
+# of the unit vectors to its neighbours, contracted over two bins of the same primary (``ops.triplet_moments``).  The
+# device returns the power sums of ``(u1 . u2)^n``; the Legendre polynomials are finite combinations of those.  Not
+# built: random catalogues and edge correction (a periodic box needs neither), ``l > 4`` and more than 16 bins, error
+# bars for zeta, the redshift-space 3PCF, batched, sharded and owned-storage variants, a loss, and the accumulation of
+# the moments on the float64 matrix instruction.
+
+# c[l][n]: P_l(x) = sum_n c[l][n] x^n; every coefficient up to l = 4 is a dyadic rational, exact in float64
+_LEGENDRE = ((1.0,), (0.0, 1.0), (-0.5, 0.0, 1.5), (0.0, -1.5, 0.0, 2.5), (0.375, 0.0, -3.75, 0.0, 4.375))
+
+
+def legendre_coefficients(lmax: int) -> torch.Tensor:
+    """``c [lmax + 1, lmax + 1]`` float64 with ``P_l(x) = sum_n c[l, n] x^n`` for ``0 <= lmax <= 4``."""
+    if isinstance(lmax, bool) or not isinstance(lmax, int) or not 0 <= lmax <= _lib.THREE_POINT_MAX_L:
+        raise ValueError(f"legendre_coefficients: lmax must be a whole number in [0, {_lib.THREE_POINT_MAX_L}], got {lmax!r}")
+    c = torch.zeros((lmax + 1, lmax + 1), dtype=torch.float64)
+    for l in range(lmax + 1):
+        c[l, :l + 1] = torch.tensor(_LEGENDRE[l], dtype=torch.float64)
+    return c
+
+
+def default_three_point_edges(n: int, box_size: float) -> torch.Tensor:
+    """The default radii of the three-point function: 8 equal bins from 0.5 to 4.5 mean interparticle spacings
+    ``box_size / n ** (1 / 3)``, without the radii above ``fl32(0.5 * box_size)``.  At least one bin remains from 8
+    particles on (one spacing is then at most half the box).  Float32 values as float64, ascending."""
+    if int(n) < 8:
+        raise ValueError(f"default_three_point_edges: n must be at least 8, got {n!r}")
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"default_three_point_edges: box_size must be positive and finite, got {box_size!r}")
+    spacing = float(box_size) / float(n) ** (1.0 / 3.0)
+    r = (spacing * torch.linspace(0.5, 4.5, 9, dtype=torch.float64)).to(torch.float32)
+    return r[r <= box * 0.5].to(torch.float64)
+
+
+def three_point_from_sums(T, n_primaries: int, n_partners: int, box_size: float, edges, unit_bits: int = 20,
+                          pairs=None) -> Dict:
+    """The Legendre multipoles of the triplet counts from the power sums of ``ops.triplet_moments``, on the host in
+    float64.  ``T [lmax + 1, nb, nb]`` (or ``[F, lmax + 1, nb, nb]``) and, to take the degenerate triangles out, ``pairs
+    [nb]`` (``[F, nb]``), counted over ``n_primaries`` primaries with ``n_partners`` neighbours in the box:
+
+    * ``S_n = T[n] / 2^(2 unit_bits)`` for ``n >= 1`` and ``S_0 = T[0]``: the sums of ``(u1 . u2)^n``;
+    * ``ddd[l] = sum_n c[l, n] S_n`` (:func:`legendre_coefficients`): the sum of ``P_l(u1 . u2)`` over every primary and
+      its neighbours ``j`` in ``b1`` and ``k`` in ``b2``.  On the diagonal ``b1 == b2`` the sum includes ``j == k``, a
+      triangle that is none and adds ``P_l(1) = 1``: with ``pairs`` the counted pairs of the bin are subtracted
+      there, for every ``l``; without, nothing is;
+    * ``triplet[l] = (2 l + 1) ddd[l] / (n_primaries nbar^2 V_b1 V_b2)`` with ``nbar = n_partners / L^3`` and ``V_b = 4 pi /
+      3 (r_{b+1}^3 - r_b^3)`` from the float64 values of the float32 edges: the l-th multipole of the triplet density
+      around a primary in units of the uncorrelated one (``triplet[0] = 1`` and the others 0 for neighbours without
+      correlations).
+
+    Returns ``{"ddd", "triplet", "r_lo", "r_hi"}`` (CPU, float64, in the shape of ``T``)."""
+    what = "three_point_from_sums"
+    t = torch.as_tensor(T).detach().to(device="cpu", dtype=torch.float64)
+    if t.dim() not in (3, 4) or t.shape[-1] != t.shape[-2] or not 1 <= t.shape[-3] <= _lib.THREE_POINT_MAX_L + 1:
+        raise ValueError(f"{what}: T must be [lmax + 1, nb, nb] or [F, lmax + 1, nb, nb] with lmax <= "
+                         f"{_lib.THREE_POINT_MAX_L}, got {tuple(t.shape)}")
+    lmax, nb = t.shape[-3] - 1, t.shape[-1]
+    r = torch.tensor(ops.check_triplet_arguments(edges, box_size, lmax, unit_bits, what), dtype=torch.float64)
+    if r.numel() - 1 != nb:
+        raise ValueError(f"{what}: T holds {nb} bins, edges {r.numel() - 1}")
+    for name, v in (("n_primaries", n_primaries), ("n_partners", n_partners)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{what}: {name} must be a whole number of at least 1, got {v!r}")
+    scale = torch.ones(lmax + 1, dtype=torch.float64)
+    scale[1:] = 2.0 ** (-2 * unit_bits)
+    s = t * scale[:, None, None]
+    ddd = torch.einsum("ln,...nab->...lab", legendre_coefficients(lmax), s)
+    if pairs is not None:
+        p = torch.as_tensor(pairs).detach().to(device="cpu")
+        if p.dtype.is_floating_point or p.dtype == torch.bool or tuple(p.shape) != tuple(t.shape[:-3]) + (nb,):
+            raise ValueError(f"{what}: pairs must hold integer counts {list(t.shape[:-3]) + [nb]}, got {p.dtype} "
+                             f"{tuple(p.shape)}")
+        ddd = ddd - torch.diag_embed(p.to(torch.float64)).unsqueeze(-3)
+    vol = _shell_volumes(r)
+    nbar = float(int(n_partners)) / float(box_size) ** 3
+    norm = float(int(n_primaries)) * nbar * nbar * vol[:, None] * vol[None, :]
+    ell = (2.0 * torch.arange(lmax + 1, dtype=torch.float64) + 1.0)[:, None, None]
+    return {"ddd": ddd, "triplet": ell * ddd / norm, "r_lo": r[:-1].clone(), "r_hi": r[1:].clone()}
+
+
+def three_point_zeta(T_data, pairs_data, T_queries, pairs_queries, n: int, n_queries: int, box_size: float, edges,
+                     unit_bits: int = 20) -> Dict:
+    """The connected multipoles from two calls of ``ops.triplet_moments`` on the same ``n`` particles, on the host in
+    float64: the particles as primaries (auto) and ``n_queries`` volume-filling points as primaries (cross).  Around a
+    particle the expected triplet density is ``1 + xi_1 + xi_2 + xi_3 + zeta``, around a random point ``1 + xi_3``:
+
+        ``zeta_l = triplet_l(data) - triplet_l(queries) - delta_{l0} (xibar_b1 + xibar_b2)``
+
+    with ``xibar_b = pairs_b / (n nbar V_b) - 1`` from the auto call's ``pairs``.  Returns ``zeta``, ``zeta_full`` (``=
+    triplet_l(data) - delta_{l0}``), ``triplet_queries``, ``xi`` (``[nb]`` or ``[F, nb]``), ``pairs`` (the auto call's,
+    int64), ``r_lo`` and ``r_hi``."""
+    d = three_point_from_sums(T_data, n, n, box_size, edges, unit_bits, pairs_data)
+    q = three_point_from_sums(T_queries, n_queries, n, box_size, edges, unit_bits, pairs_queries)
+    p = torch.as_tensor(pairs_data).detach().to(device="cpu")
+    vol = _shell_volumes(torch.cat([d["r_lo"], d["r_hi"][-1:]]))
+    xi = p.to(torch.float64) / (float(n) * (float(n) / float(box_size) ** 3) * vol) - 1.0
+    full = d["triplet"].clone()
+    full[..., 0, :, :] -= 1.0
+    zeta = d["triplet"] - q["triplet"]
+    zeta[..., 0, :, :] -= xi[..., :, None] + xi[..., None, :]
+    return {"zeta": zeta, "zeta_full": full, "triplet_queries": q["triplet"], "xi": xi, "pairs": p,
+            "r_lo": d["r_lo"], "r_hi": d["r_hi"]}
+
+
+def _check_three_point_arguments(what: str, n: int, box_size, edges, lmax, queries, n_query_axis, device):
+    """Radii (default :func:`default_three_point_edges`) and queries (default :func:`query_lattice`) of a three-point
+    call, checked on the host before any device work."""
+    e = ops.check_triplet_arguments(default_three_point_edges(n, box_size) if edges is None else edges, box_size, lmax,
+                                    _lib.THREE_POINT_MAX_UNIT_BITS, what)
+    if queries is None:
+        queries = query_lattice(max(1, int(round(n ** (1.0 / 3.0)))) if n_query_axis is None else n_query_axis, box_size,
+                                device)
+    elif n_query_axis is not None:
+        raise ValueError(f"{what}: queries and n_query_axis exclude each other")
+    elif not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != 3 or queries.shape[0] < 1:
+        raise ValueError(f"{what}: queries must be a tensor [nq, 3] with nq >= 1, got "
+                         f"{tuple(queries.shape) if torch.is_tensor(queries) else type(queries).__name__}")
+    return e, queries
+
+
+def triplet_sums_on_device(frames: torch.Tensor, queries: torch.Tensor, box_size: float, e, lmax: int) -> torch.Tensor:
+    """Both calls of a three-point estimate for ``frames [F, N, 3]`` as one int64 tensor ``[F, 2 ((lmax + 1) nb^2 + nb)]``:
+    per call the bits of the float64 sums, then the pairs; the particles as primaries first, then the queries."""
+    f = frames.shape[0]
+    out = []
+    for pos, pos_b in ((frames, None), (queries.to(frames.device).unsqueeze(0).expand(f, -1, -1), frames)):
+        sums, pairs = ops.triplet_moments(pos, box_size, e, lmax, pos_b, return_pairs=True)
+        out += [sums.reshape(f, -1).view(torch.int64), pairs]
+    return torch.cat(out, dim=1)
+
+
+def triplet_sums_on_host(packed: torch.Tensor, lmax: int, nb: int):
+    """``(T_data, pairs_data, T_queries, pairs_queries)`` from the host copy of :func:`triplet_sums_on_device`."""
+    m = (lmax + 1) * nb * nb
+    shape = (packed.shape[0], lmax + 1, nb, nb)
+    call = [packed[:, :m + nb], packed[:, m + nb:]]
+    return tuple(x for c in call for x in (c[:, :m].contiguous().view(torch.float64).reshape(shape), c[:, m:]))
+
+
+def three_point_correlation(pos: torch.Tensor, box_size: float, edges=None, lmax: int = 4,
+                            queries: Optional[torch.Tensor] = None, n_query_axis: Optional[int] = None) -> Dict:
+    """The multipoles ``zeta_l(r1, r2)``, ``l = 0 .. lmax``, of the connected three-point correlation function of ``pos
+    [N, 3]`` (or of every frame of ``[T, N, 3]``): the dict of :func:`three_point_zeta` (CPU; ``zeta [lmax + 1, nb, nb]``
+    with a leading ``T`` for frames), plus ``n_queries``.  ``edges``: default :func:`default_three_point_edges`, at most
+    16 bins; ``queries [nq, 3]``: default ``query_lattice(n_query_axis or round(N ** (1 / 3)))``, about as many queries
+    as particles.  Two device calls per frame -- the particles as primaries, and the queries as primaries against the
+    particles -- without a host synchronisation; the sums come back in one transfer.  On the diagonal ``r1 == r2`` the
+    degenerate triangles are taken out; the bins there still hold triangles with two sides in the same shell."""
+    what = "three_point_correlation"
+    if not torch.is_tensor(pos):
+        raise ValueError(f"{what}: pos must be a tensor, got {type(pos).__name__}")
+    frames = _frames3(pos, "pos", what)
+    n = frames.shape[1]
+    e, queries = _check_three_point_arguments(what, n, box_size, edges, lmax, queries, n_query_axis, pos.device)
+    packed = triplet_sums_on_device(_f32_frames(frames, "pos", what), queries, box_size, e, lmax).cpu()   # the one transfer
+    host = triplet_sums_on_host(packed, lmax, len(e) - 1)
+    if pos.dim() == 2:
+        host = tuple(x[0] for x in host)
+    out = three_point_zeta(*host, n, queries.shape[0], box_size, e)
+    out["n_queries"] = queries.shape[0]
+    return out
+
+
+def rollout_three_point(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                        edges=None, lmax: int = 4, frames: Optional[Sequence[int]] = None,
+                        n_query_axis: Optional[int] = None) -> Dict:
+    """Three-point multipoles of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates
+    [T, N, 3]``): in which configurations, below the mesh, the predicted frame differs -- filaments raise ``zeta_2``
+    against ``zeta_0``, round blobs do not.  Both sides are seen from the same lattice of queries (``n_query_axis`` per
+    axis, default ``round(N ** (1 / 3))``).  Per selected frame (CPU, float64, ``[F, lmax + 1, nb, nb]``):
+
+    * ``zeta_pred``, ``zeta_true``;
+    * ``zeta_difference = zeta_pred - zeta_true`` and ``zeta_ratio = zeta_pred / zeta_true``;
+    * ``xi_pred``, ``xi_true`` (``[F, nb]``), the shell-averaged two-point function behind the ``l = 0`` subtraction,
+
+    plus ``frames``, ``r_lo``, ``r_hi`` and ``n_queries``.  No host synchronisation per frame; one transfer at the
+    end."""
+    what = "rollout_three_point"
+    n = rollout_data["Coordinates"].shape[-2]
+    dev = rollout_data["Coordinates"].device
+    e, queries = _check_three_point_arguments(what, n, box_size, edges, lmax, None, n_query_axis, dev)
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
+    packed = torch.stack([triplet_sums_on_device(_f32_frames(x, "Coordinates", what), queries, box_size, e, lmax)
+                          for x in (pc, tc)]).cpu()                                     # the one transfer
+    nb, nq = len(e) - 1, queries.shape[0]
+    p = three_point_zeta(*triplet_sums_on_host(packed[0], lmax, nb), n, nq, box_size, e)
+    t = three_point_zeta(*triplet_sums_on_host(packed[1], lmax, nb), n, nq, box_size, e)
+    return {"frames": sel, "r_lo": t["r_lo"], "r_hi": t["r_hi"], "n_queries": nq, "zeta_pred": p["zeta"],
+            "zeta_true": t["zeta"], "zeta_difference": p["zeta"] - t["zeta"], "zeta_ratio": p["zeta"] / t["zeta"],
+            "xi_pred": p["xi"], "xi_true": t["xi"]}

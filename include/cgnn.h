@@ -670,6 +670,49 @@ int cgnn_pair_velocity_sums(const float* pos_a, const int32_t* q_a, int64_t n_a,
                             int64_t n_b, float box_size, const float* edges, int32_t num_bins, int64_t* counts,
                             int64_t* sums /* [num_bins][3][2] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same pairs by direction: what the multipoles zeta_l(r1, r2) of the three-point correlation function are made of
+ * (Slepian & Eisenstein 2015).  pos_a [n_a, 3] are the primaries, pos_b [n_b, 3] their neighbours (pos_b == NULL: the
+ * neighbours are the primaries, auto mode); box_size and edges (HOST memory, num_bins + 1 floats) as in cgnn_pair_counts.
+ * Stage 1, exact integers.  For a primary a and a neighbour b, dx, dy, dz (b minus a, folded) and d2 are exactly those of
+ * cgnn_pair_counts.  The pair counts iff d2 > 0 and e2[0] <= d2 < e2[num_bins], in that entry's bin; the auto mode skips
+ * the primary's own slot; coincident particles (d2 == 0) have no direction and count for nothing, in either mode.  A
+ * counted pair yields
+ *     r = fl32(sqrt(d2)),  u_c = fl32(d_c / r)               c = x, y, z; sqrt and / IEEE correctly rounded
+ *     p_c[0] = 1,  p_c[k] = fl32(p_c[k-1] * u_c)             k = 1 .. lmax
+ *     degree 0:  1
+ *     monomial (a, b, c) of degree >= 1:  q = rint(fl32(fl32(p_x[a] * p_y[b]) * p_z[c]) * 2^unit_bits)
+ * one float32 rounding per operation, no FMA; rint rounds ties to even and the scaling by 2^unit_bits is exact.  The
+ * monomials are listed by degree n = 0 .. lmax, then a = n .. 0, then b = n - a .. 0, with c = n - a - b: n_mono = 1, 4,
+ * 10, 20, 35 of them for lmax = 0 .. 4.  M[i, bin, alpha] is the sum of q over the counted neighbours of primary i in that
+ * bin; alpha = 0 is their number.  |q| <= 2^20 + 1 and a primary has fewer than 2^31 candidates: exact int64, independent
+ * of any order.
+ * Stage 2, float64.  For every primary i, every b1 <= b2 and every degree n,
+ *     t = sum over |alpha| = n, in the order of the listing, of
+ *             fl64(fl64(mult(alpha) * double(M[i, b1, alpha])) * double(M[i, b2, alpha])),   mult = n! / (a! b! c!)
+ * (the multinomial expansion of (u1 . u2)^n), one float64 rounding per operation, no FMA; every int64 -> double
+ * conversion of |M| < 2^53 is exact.  sums[n][b1][b2] = sums[n][b2][b1] is the sum of t over the primaries in a fixed
+ * order: the primaries are sorted by cell and within a cell by their index in pos_a, and cut into work items of up to 8
+ * of one cell; each thread owns its (n, b1, b2), takes the primaries of an item in that order and the items of its
+ * persistent workgroup in the workgroup's order; one partial table per workgroup, added in workgroup order by a second
+ * kernel.  The workgroup count is a function of n_a, n_b and the grid alone: the same bits on every run.  No float
+ * atomics and no global atomics.
+ * sums (device, double [lmax + 1][num_bins][num_bins]) and pairs (device, int64 [num_bins]: the counted ordered pairs,
+ * the sum over i of M[i, bin, 0]) are overwritten.  moments (device, int64 [n_a][num_bins][n_mono], or NULL) is
+ * overwritten with every primary's M in the ORIGINAL order of pos_a, by plain stores.  When no two particles coincide,
+ * pairs equals twice what cgnn_pair_counts gives in auto mode, and its cross counts.  No host synchronisation,
+ * everything on `stream`.
+ * CGNN_ERR_INVALID_ARG unless 1 <= num_bins <= 16, 0 <= lmax <= 4, 1 <= unit_bits <= 20, and edges and box_size as in
+ * cgnn_pair_counts; 2^31 or more particles in a set: CGNN_ERR_UNSUPPORTED; a short workspace: CGNN_ERR_WORKSPACE.  All of
+ * it is refused on the host before any launch.
+ * Workspace: cgnn_triplet_moments_workspace_bytes(n_a, n_b, lmax, num_bins) (n_b = 0: auto), the pair job's layout plus
+ * 16 bytes per primary and the workgroups' partial tables; a function of these four alone (256 for arguments the entry refuses), 16-byte aligned. */
+size_t cgnn_triplet_moments_workspace_bytes(int64_t n_a, int64_t n_b, int32_t lmax, int32_t num_bins);
+int cgnn_triplet_moments(const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, float box_size,
+                         const float* edges, int32_t num_bins, int32_t lmax, int32_t unit_bits,
+                         double* sums /* [lmax + 1][num_bins][num_bins] */, int64_t* pairs /* [num_bins] */,
+                         int64_t* moments /* [n_a][num_bins][n_mono] or NULL */, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Per-frame errors of a rollout against the truth: pred_pos / true_pos [frames, n, 3], pred_tmp / true_tmp [frames, n]
  * (both NULL: no temperatures, the second sum is 0).  out (device, double [frames, 2]):
  *   out[f, 0] = sum over particles and axes of fold(fl32(pred - true))^2     (fold: the minimum image of the entry above)
