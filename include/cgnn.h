@@ -1231,11 +1231,14 @@ int cgnn_tile_classify(const float* pos, int64_t n, int32_t px, int32_t py, int3
  * counts as covered).  block_counts / counts over the set bits.
  *
  * cgnn_halo_pack: out [n_out, 4] row offsets[block, p] + rank = recent row i, for every set bit p of mask[i]
- * (storage order inside a peer's block; positions outside [0, n_out) are skipped).
+ * (storage order inside a peer's block; positions outside [0, n_out) are skipped: nothing is written, and the row
+ * still counts as a place of its group, so the rows behind it keep theirs).
  *
  * cgnn_migrate_pack: row i with dest[i] == rank goes to the second ring hist_out [window, cap_out] / ids_out (all
  * window slots, same slots) at its group position; any other row to send [n_send, window + 1, 4] at its group
- * position: (id bits, 0, 0, 0) then the window ring slots in slot order.  hist_out must not be hist.
+ * position: (id bits, 0, 0, 0) then the window ring slots in slot order.  hist_out must not be hist.  A dest outside
+ * [0, world) belongs to no group: the row takes no place and is written nowhere.  A position outside [0, cap_out)
+ * (stayers) or [0, n_send) (leavers) is skipped as in cgnn_halo_pack and still counts as a place.
  *
  * cgnn_migrate_unpack: recv [n_recv, window + 1, 4] rows (as packed above) become ring rows first .. first + n_recv - 1
  * of hist_out / ids_out; first + n_recv <= cap_out. */
