@@ -7,7 +7,9 @@ sum of float32 terms in a fixed order: ``GTOL = 2e-5`` of the tensor's largest e
 copies (``torch.equal``).  End to end the predicted frames are those of the one-GPU call bit for bit (a rank's predictions
 are the unsharded ones' bits), the global loss and each step's total lie within 1e-5 relative of the one-GPU ones, and
 every parameter gradient within ``max(GTOL, 3 e_ref)`` of the float64 restatement on the one-GPU run's graphs, ``e_ref``
-being the distance of the float32 restatement to the float64 one.  Every figure is printed before it is asserted.
+being the distance of the float32 restatement to the float64 one.  Every figure is printed before it is asserted.  The three
+kernels are also gated exactly (ghost rows on both sides of a block edge, invalid ids, order and guard probes) in
+tests/test_gpu_unroll_link_gates.py.
 
 Several ranks are real processes over gloo on one GPU (tests/test_gpu_sharded_training_edge.py's pattern); one pair of
 workers runs a list of jobs, so the start-up is paid once."""

@@ -7,7 +7,8 @@ entry (tests/test_gpu_training.py), expected about 1e-6.  End to end, S = 1 is h
 rounding of S float32 model steps is measured, not derived: ``e_ref`` is the distance of the same restatement run in
 float32 on the CPU to its float64 run (per tensor, relative to the largest entry), and the HIP result must lie within
 ``max(GTOL, 3 e_ref)`` of the float64 run (3: the kernels sum in other orders).  Every figure is printed before it is
-asserted.
+asserted.  The link kernels and the Python links are also gated exactly, on problems where float32 does not round and at
+every block edge, in tests/test_gpu_unroll_link_gates.py.
 
 Measured on an MI355X.  Link kernels: 1.8e-7 (sample), 1.1e-7 (integrate), 1.8e-7 (edge features).  End to end, the
 largest error over loss, step losses, frames and all parameter gradients, HIP error | e_ref of that tensor:
