@@ -61,6 +61,7 @@ EXPORTS = (
     "cgnn_knn_distances_workspace_bytes", "cgnn_knn_distances", "cgnn_knn_cdf_counts",
     "cgnn_bispectrum_shells", "cgnn_bispectrum_sums_workspace_bytes", "cgnn_bispectrum_sums",
     "cgnn_triplet_moments_workspace_bytes", "cgnn_triplet_moments",
+    "cgnn_excursion_counts",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
@@ -76,6 +77,8 @@ BISPECTRUM_MAX_SHELLS = 32        # CGNN_BS_MAX_SHELLS in include/cgnn.h
 BISPECTRUM_MAX_TRIANGLES = 5984   # CGNN_BS_MAX_TRIANGLES: every i <= j <= l of 32 shells
 BISPECTRUM_CHUNK = 64             # CGNN_BS_CHUNK: cells a workgroup of cgnn_bispectrum_sums stages at a time
 BISPECTRUM_MAX_PARTS = 1024       # CGNN_BS_MAX_PARTS: slices of a frame's cells, at most
+EX_MAX_THRESHOLDS = 255           # CGNN_EX_MAX_THRESHOLDS in include/cgnn.h: thresholds per call of cgnn_excursion_counts
+EX_TILE = (8, 8, 64)              # CGNN_EX_TX, CGNN_EX_TY, CGNN_EX_TZ: the voxels a workgroup stages at a time
 MASS_ASSIGN_Q = 8192          # CGNN_MA_Q in csrc/power_spectrum.hip: a particle's axis weights sum to this
 MASS_ASSIGN_MAX_MESH = 512    # CGNN_MA_MAX_MESH
 MASS_ASSIGN_MAX_PARTICLES = 1 << 24
@@ -202,6 +205,7 @@ def load() -> C.CDLL:
     lib.cgnn_bispectrum_sums_workspace_bytes.restype = sz
     lib.cgnn_bispectrum_sums_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cgnn_bispectrum_sums.argtypes = [vp, i64, i64, i32, C.POINTER(i32), i32, vp, vp, sz, vp]   # triangles: host memory
+    lib.cgnn_excursion_counts.argtypes = [vp, i64, i32, C.POINTER(C.c_double), i32, vp, vp]        # thresholds: host memory
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]

@@ -1910,6 +1910,51 @@ def bispectrum_shells(delta_k: Optional[torch.Tensor], mesh: int, order: int, k_
     return out if batched else out[0]
 
 
+def check_excursion_thresholds(thresholds, who: str) -> List[float]:
+    """The thresholds of :func:`excursion_counts` as float64 host values, or ``ValueError``: 1 to 255 of them, finite and
+    strictly ascending."""
+    t = torch.as_tensor(thresholds).detach().to(device="cpu", dtype=torch.float64).reshape(-1).tolist()
+    if not 1 <= len(t) <= _lib.EX_MAX_THRESHOLDS:
+        raise ValueError(f"{who}: thresholds must hold 1 to {_lib.EX_MAX_THRESHOLDS} values, got {len(t)}")
+    if not all(math.isfinite(v) for v in t) or not all(b > a for a, b in zip(t, t[1:])):
+        raise ValueError(f"{who}: thresholds must be finite and ascend strictly")
+    return t
+
+
+def excursion_counts(field: torch.Tensor, thresholds) -> torch.Tensor:
+    """The cubical complexes of the excursion sets of a periodic field (``cgnn_excursion_counts``): int64 ``counts [4,
+    nt]`` for a float64 ``field [M, M, M]``, ``[F, 4, nt]`` for ``[F, M, M, M]``.  ``counts[d, t]`` is the number of
+    vertices (``d = 0``), edges, faces and cubes (``d = 3``) of the union of the closed unit cubes of the voxels with
+    ``field >= thresholds[t]`` (a value equal to a threshold is in, a NaN is in no set), all neighbours modulo ``M``:
+    what the Minkowski functionals are made of (:func:`statistics.minkowski_from_counts`).  ``thresholds``:
+    :func:`check_excursion_thresholds`, host values.  Exact integers, bit-equal to the numpy restatement and the same on
+    every run; the field is read once for all thresholds.
+
+    Refused on the host before any device work (``ValueError``): a field that is not float64, not cubic, not contiguous,
+    a mesh outside 2..512, no frames, bad thresholds.  No host synchronisation."""
+    what = "excursion_counts"
+    nu = check_excursion_thresholds(thresholds, what)
+    if not isinstance(field, torch.Tensor) or field.dtype != torch.float64:
+        raise ValueError(f"{what}: field must be a float64 tensor, got {getattr(field, 'dtype', type(field))}")
+    if field.dim() not in (3, 4) or len(set(field.shape[-3:])) != 1 or field.shape[0] < 1:
+        raise ValueError(f"{what}: field must be [M, M, M] or [F, M, M, M] with F >= 1, got {tuple(field.shape)}")
+    mesh = check_mesh(field.shape[-1], what)
+    if not field.is_contiguous():
+        raise ValueError(f"{what}: field must be contiguous (strides {field.stride()})")
+    batched = field.dim() == 4
+    frames = field.shape[0] if batched else 1
+    if frames > 1 << 20:
+        raise ValueError(f"{what}: {frames} frames exceed 2^20 per call")
+    require_device(field, "field")
+    nt = len(nu)
+    nu_c = (C.c_double * nt)(*nu)
+    counts = torch.empty((frames, 4, nt), dtype=torch.int64, device=field.device)
+    with _timed(what, field.device):
+        check(_lib.load().cgnn_excursion_counts(field.data_ptr(), frames, mesh, nu_c, nt, counts.data_ptr(),
+                                                stream_ptr(field.device)), "cgnn_excursion_counts")
+    return counts if batched else counts[0]
+
+
 def check_linking_length(linking_length, box_size: float, who: str) -> float:
     """The linking length of :func:`fof_labels` as a float32 host value, or ``ValueError``: finite, positive and at most
     ``fl32(0.5 * box_size)``, ``box_size`` finite and positive.  Callers check before any device work."""

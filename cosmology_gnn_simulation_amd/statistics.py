@@ -62,6 +62,13 @@ integer sums of the monomials of the directions to its neighbours, contracted ov
 ``rollout_three_point`` does that for every frame of a rollout against the truth, ``three_point_from_sums`` and
 ``three_point_zeta`` are the host arithmetic and ``default_three_point_edges`` the 8 bins from 0.5 to 4.5 spacings.
 
+Morphology, which no N-point function of fixed order says: ``minkowski_functionals`` gives the four Minkowski functionals
+V0 .. V3 (volume, surface, mean curvature, Euler characteristic) of the excursion sets of the smoothed density field as
+functions of the threshold, from exact integer counts of the cubes, faces, edges and vertices of the sets on the mesh
+(``ops.excursion_counts``), next to the curves of a Gaussian field (``gaussian_minkowski``); ``rollout_minkowski`` does
+that for every frame of a rollout against the truth, ``minkowski_from_counts`` is the host arithmetic and
+``default_minkowski_thresholds`` the 25 thresholds from -3 to 3 standard deviations.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -2329,3 +2336,220 @@ def rollout_three_point(rollout_data: Dict[str, torch.Tensor], ground_truth: Dic
     return {"frames": sel, "r_lo": t["r_lo"], "r_hi": t["r_hi"], "n_queries": nq, "zeta_pred": p["zeta"],
             "zeta_true": t["zeta"], "zeta_difference": p["zeta"] - t["zeta"], "zeta_ratio": p["zeta"] / t["zeta"],
             "xi_pred": p["xi"], "xi_true": t["xi"]}
+
+
+# ---- morphology: the Minkowski functionals of the density field --------------------------------------------------------
+#
+# What none of the statistics above says: how much volume lies above a density threshold, how much surface bounds it, how
+# curved that surface is and how connected the set is.  Two frames can agree in P(k) and roughly in B and still differ
+# here -- in one the filaments percolate into a network, in the other they break into blobs.  The four Minkowski
+# functionals V0 .. V3 of the excursion sets of the smoothed density field measure exactly this, and their departure from
+# the Gaussian curves, as a function of the threshold, is sensitive to every order of correlation at once.  On a mesh
+# they reduce to exact integer counts of the cubes, faces, edges and vertices of a cubical complex (Schmalzing & Buchert
+# 1997, Crofton's formula): ``ops.excursion_counts`` reads the field once for all thresholds.  Not built: float32 fields,
+# per-voxel masks, Minkowski tensors and the Betti numbers, marching-cubes / Koenderink estimators, a genus convention
+# (``euler`` is reported; periodic conventions for the genus differ), error bars, redshift-space fields, batched, sharded
+# and owned-storage variants, and a morphology loss.
+
+def default_minkowski_thresholds() -> torch.Tensor:
+    """The default thresholds of the Minkowski functionals: 25 values from -3 to 3 (float64), in units of the field's
+    standard deviation under ``threshold_units="sigma"``."""
+    return torch.linspace(-3.0, 3.0, 25, dtype=torch.float64)
+
+
+def minkowski_from_counts(counts, mesh: int, box_size: float) -> Dict:
+    """The Minkowski functionals per unit volume from the integers of ``ops.excursion_counts``, on the host in float64.
+    ``counts [4, nt]`` (or ``[F, 4, nt]``): per threshold the vertices ``n0``, edges ``n1``, faces ``n2`` and cubes ``n3``
+    of the excursion set on a periodic ``mesh^3`` grid of cells of side ``a = box_size / mesh``; with ``N = mesh^3``
+
+    * ``v0 = n3 / N``: the volume fraction;
+    * ``v1 = 2 (n2 - 3 n3) / (9 a N)``: a sixth of the surface per unit volume;
+    * ``v2 = 2 (n1 - 2 n2 + 3 n3) / (9 a^2 N)``: the integrated mean curvature, over ``3 pi``, per unit volume;
+    * ``v3 = (n0 - n1 + n2 - n3) / (a^3 N)``: the Euler characteristic per unit volume;
+    * ``euler = n0 - n1 + n2 - n3`` (int64).  No genus: periodic conventions differ.
+
+    The factors 2/9 are Crofton's average over the orientations of a cubic lattice, the convention under which the
+    functionals of a mesh converge to those of the continuum for an isotropic field: a single cube therefore reports
+    2/3 of its geometric surface, by design.  Returns ``{"v0", "v1", "v2", "v3", "euler", "counts"}`` (CPU, in the shape
+    of ``counts`` without its axis of 4)."""
+    what = "minkowski_from_counts"
+    mesh = ops.check_mesh(mesh, what)
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    c = torch.as_tensor(counts).detach().to(device="cpu")
+    if c.dtype.is_floating_point or c.dtype == torch.bool or c.dim() not in (2, 3) or c.shape[-2] != 4 or c.shape[-1] < 1:
+        raise ValueError(f"{what}: counts must hold integers [4, nt] or [F, 4, nt], got {c.dtype} {tuple(c.shape)}")
+    c = c.to(torch.int64)
+    n0, n1, n2, n3 = c[..., 0, :], c[..., 1, :], c[..., 2, :], c[..., 3, :]
+    a, cells = float(box_size) / mesh, float(mesh) ** 3
+    euler = n0 - n1 + n2 - n3
+    return {"v0": n3.to(torch.float64) / cells,
+            "v1": 2.0 * (n2 - 3 * n3).to(torch.float64) / (9.0 * a * cells),
+            "v2": 2.0 * (n1 - 2 * n2 + 3 * n3).to(torch.float64) / (9.0 * a * a * cells),
+            "v3": euler.to(torch.float64) / (a ** 3 * cells), "euler": euler, "counts": c}
+
+
+def gaussian_minkowski(nu, sigma0, sigma1) -> Dict:
+    """What a Gaussian random field gives (Tomita 1986; Schmalzing & Buchert 1997), in float64 on the host: with ``lam =
+    sqrt(sigma1^2 / (6 pi sigma0^2))``, ``sigma0^2`` the variance of the field and ``sigma1^2`` that of its gradient,
+
+    * ``v0 = erfc(nu / sqrt 2) / 2``;
+    * ``v1 = (2 / 3) (lam / sqrt(2 pi)) exp(-nu^2 / 2)``;
+    * ``v2 = (2 / 3) (lam^2 / sqrt(2 pi)) nu exp(-nu^2 / 2)``;
+    * ``v3 = (lam^3 / sqrt(2 pi)) (nu^2 - 1) exp(-nu^2 / 2)``
+
+    in the normalisation of :func:`minkowski_from_counts`.  ``nu [nt]``: thresholds in units of ``sigma0``; ``sigma0``,
+    ``sigma1``: numbers, or ``[F]`` for curves ``[F, nt]``.  Returns ``{"v0", "v1", "v2", "v3", "lam"}``."""
+    what = "gaussian_minkowski"
+    nu = torch.as_tensor(nu).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    s0 = torch.as_tensor(sigma0).detach().to(device="cpu", dtype=torch.float64)
+    s1 = torch.as_tensor(sigma1).detach().to(device="cpu", dtype=torch.float64)
+    if nu.numel() < 1 or not bool(torch.isfinite(nu).all()):
+        raise ValueError(f"{what}: nu must hold at least one finite value")
+    if s0.shape != s1.shape or s0.dim() > 1:
+        raise ValueError(f"{what}: sigma0 and sigma1 must be two numbers or two tensors [F], got {tuple(s0.shape)} and "
+                         f"{tuple(s1.shape)}")
+    if bool((s0 <= 0).any()) or bool((s1 < 0).any()):
+        raise ValueError(f"{what}: sigma0 must be positive and sigma1 not negative")
+    lam = torch.sqrt(s1 * s1 / (6.0 * math.pi * s0 * s0))
+    l = lam[..., None] if lam.dim() else lam
+    g = torch.exp(-0.5 * nu * nu) / math.sqrt(2.0 * math.pi)
+    return {"v0": (0.5 * torch.erfc(nu / math.sqrt(2.0))).expand(tuple(s0.shape) + nu.shape).clone(),
+            "v1": (2.0 / 3.0) * l * g, "v2": (2.0 / 3.0) * l * l * nu * g, "v3": l ** 3 * (nu * nu - 1.0) * g, "lam": lam}
+
+
+def _check_minkowski_arguments(what: str, box_size, mesh, smoothing, thresholds, order, threshold_units):
+    """Mesh and thresholds (default :func:`default_minkowski_thresholds`) of a Minkowski call, checked on the host before
+    any device work -> ``(mesh, thresholds as float64 host values)``."""
+    mesh = ops.check_mesh(mesh, what)
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"{what}: order must be 1 (NGP), 2 (CIC) or 3 (TSC), got {order!r}")
+    if not (float(box_size) > 0.0 and math.isfinite(float(box_size))):
+        raise ValueError(f"{what}: box_size must be positive and finite, got {box_size!r}")
+    if isinstance(smoothing, bool) or not math.isfinite(smoothing) or smoothing < 0:
+        raise ValueError(f"{what}: smoothing must be a finite length >= 0, got {smoothing!r}")
+    if threshold_units not in ("sigma", "contrast"):
+        raise ValueError(f"{what}: threshold_units must be 'sigma' or 'contrast', got {threshold_units!r}")
+    nu = ops.check_excursion_thresholds(default_minkowski_thresholds() if thresholds is None else thresholds, what)
+    return mesh, nu
+
+
+def _minkowski_filters(mesh: int, box_size: float, smoothing: float, dev):
+    """``(kernel, k2w)`` on the modes of ``rfftn`` (float64 ``[M, M, M/2 + 1]``): the Gaussian of
+    ``losses.gaussian_filter`` (``None`` without smoothing), and ``|k|^2`` times the number of modes a stored one stands
+    for (the Hermitian weights of the half axis: 1 at ``n_z = 0`` and at the Nyquist plane of an even mesh, 2 between)."""
+    from .losses import gaussian_filter
+    n = torch.fft.fftfreq(mesh, 1.0 / mesh, dtype=torch.float64, device=dev)
+    nz = torch.fft.rfftfreq(mesh, 1.0 / mesh, dtype=torch.float64, device=dev)
+    k2 = ((n * n)[:, None, None] + (n * n)[None, :, None] + (nz * nz)[None, None, :]) * (2.0 * math.pi / float(box_size)) ** 2
+    herm = 2.0 - ((nz == 0) | (2.0 * nz == float(mesh))).to(torch.float64)
+    return (gaussian_filter(mesh, box_size, smoothing, dev) if smoothing > 0 else None), k2 * herm
+
+
+def _smoothed_frame(pos: torch.Tensor, box_size: float, mesh: int, order: int, threshold_units: str, kernel, k2w):
+    """One frame ``pos [N, 3]`` of :func:`smoothed_contrast`: ``(field [M, M, M], sigma0, sigma1)``."""
+    delta = ops.grid_contrast(ops.mass_assign(pos, box_size, mesh, order), pos.shape[0])
+    modes = torch.fft.rfftn(delta)
+    if kernel is not None:
+        modes = modes * kernel
+        delta = torch.fft.irfftn(modes, s=(mesh,) * 3)
+    sigma0 = torch.sqrt((delta * delta).mean())
+    sigma1 = torch.sqrt((k2w * (modes.real * modes.real + modes.imag * modes.imag)).sum()) / float(mesh) ** 3
+    return (delta / sigma0 if threshold_units == "sigma" else delta).contiguous(), sigma0, sigma1
+
+
+def smoothed_contrast(pos: torch.Tensor, box_size: float, mesh: int, smoothing: float, order: int = 2,
+                      threshold_units: str = "sigma"):
+    """The field whose excursion sets :func:`minkowski_functionals` counts, for frames ``pos [F, N, 3]``, on the device:
+    ``(field [F, M, M, M], sigma0 [F], sigma1 [F])`` in float64.  The exact deposit (``ops.mass_assign``,
+    ``ops.grid_contrast``), smoothed with the Gaussian ``exp(-|k|^2 R^2 / 2)`` of ``losses.gaussian_filter`` between
+    ``torch.fft.rfftn`` and ``irfftn`` (``smoothing = 0``: no FFT for the field); ``sigma0^2`` is the mean square of the
+    smoothed field and ``sigma1^2`` that of its gradient, ``sum |k|^2 |u_k|^2`` over the modes with the Hermitian
+    weights of the half axis.  With ``"sigma"`` the field is divided by its own ``sigma0``.  No host synchronisation."""
+    kernel, k2w = _minkowski_filters(mesh, box_size, smoothing, pos.device)
+    parts = [_smoothed_frame(pos[f], box_size, mesh, order, threshold_units, kernel, k2w) for f in range(pos.shape[0])]
+    return tuple(torch.stack([p[i] for p in parts]) for i in range(3))
+
+
+def minkowski_counts_on_device(frames: torch.Tensor, box_size: float, mesh: int, smoothing: float, nu, order: int = 2,
+                               threshold_units: str = "sigma") -> torch.Tensor:
+    """What a Minkowski estimate of ``frames [F, N, 3]`` brings back from the device, as one int64 tensor ``[F, 4 nt + 2]``:
+    the counts of ``ops.excursion_counts`` on the frames of :func:`smoothed_contrast`, then the bits of ``sigma0`` and
+    ``sigma1``.  One frame's field and transforms are alive at a time.  No host synchronisation."""
+    kernel, k2w = _minkowski_filters(mesh, box_size, smoothing, frames.device)
+    out = []
+    for f in range(frames.shape[0]):
+        field, s0, s1 = _smoothed_frame(frames[f], box_size, mesh, order, threshold_units, kernel, k2w)
+        out.append(torch.cat([ops.excursion_counts(field, nu).reshape(-1), torch.stack([s0, s1]).view(torch.int64)]))
+    return torch.stack(out)
+
+
+def minkowski_on_host(packed: torch.Tensor, nt: int):
+    """``(counts [F, 4, nt], sigma0 [F], sigma1 [F])`` from the host copy of :func:`minkowski_counts_on_device`."""
+    sig = packed[:, 4 * nt:].contiguous().view(torch.float64)
+    return packed[:, :4 * nt].reshape(-1, 4, nt), sig[:, 0].clone(), sig[:, 1].clone()
+
+
+def _minkowski_result(counts, s0, s1, mesh: int, box_size: float, nu, threshold_units: str) -> Dict:
+    out = minkowski_from_counts(counts, mesh, box_size)
+    out.update(sigma0=s0, sigma1=s1, thresholds=torch.tensor(nu, dtype=torch.float64))
+    if threshold_units == "sigma":
+        g = gaussian_minkowski(nu, s0, s1)
+        out.update({"gaussian_v%d" % d: g["v%d" % d] for d in range(4)})
+    return out
+
+
+def minkowski_functionals(pos: torch.Tensor, box_size: float, mesh: int, smoothing: float, thresholds=None, order: int = 2,
+                          threshold_units: str = "sigma") -> Dict:
+    """The Minkowski functionals of the excursion sets of the density field of ``pos [N, 3]`` (or of every frame of ``[T,
+    N, 3]``): deposited on a ``mesh^3`` grid with ``order`` (1 = NGP, 2 = CIC, 3 = TSC), smoothed with a Gaussian of
+    length ``smoothing`` (in the units of ``box_size``; 0: the raw mesh) and cut at ``thresholds`` (default
+    :func:`default_minkowski_thresholds`) -- with ``threshold_units="sigma"`` in units of the smoothed field's own
+    standard deviation (the field is divided by it on the device), with ``"contrast"`` values of delta.  Returns the dict
+    of :func:`minkowski_from_counts` (``[nt]`` or ``[T, nt]``) plus ``sigma0``, ``sigma1`` (of the smoothed contrast),
+    ``thresholds`` and, with ``"sigma"``, the curves ``gaussian_v0`` .. ``gaussian_v3`` of :func:`gaussian_minkowski`
+    for that ``sigma0`` and ``sigma1``.  The counts are exact integers of the field the device made; everything is
+    computed on the device of ``pos`` without a host synchronisation and comes back in one transfer."""
+    what = "minkowski_functionals"
+    mesh, nu = _check_minkowski_arguments(what, box_size, mesh, smoothing, thresholds, order, threshold_units)
+    if not torch.is_tensor(pos):
+        raise ValueError(f"{what}: pos must be a tensor, got {type(pos).__name__}")
+    frames = _frames3(pos, "pos", what)
+    packed = minkowski_counts_on_device(_f32_frames(frames, "pos", what), box_size, mesh, smoothing, nu, order,
+                                        threshold_units).cpu()                          # the one transfer
+    counts, s0, s1 = minkowski_on_host(packed, len(nu))
+    if pos.dim() == 2:
+        counts, s0, s1 = counts[0], s0[0], s1[0]
+    return _minkowski_result(counts, s0, s1, mesh, box_size, nu, threshold_units)
+
+
+def rollout_minkowski(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                      mesh: int, smoothing: float, thresholds=None, order: int = 2, threshold_units: str = "sigma",
+                      frames: Optional[Sequence[int]] = None) -> Dict:
+    """Minkowski functionals of a rollout against the truth, for the dicts ``rollout.rollout`` returns (``Coordinates [T,
+    N, 3]``): whether the predicted cosmic web has the volume, the surface, the curvature and the connectivity of the
+    true one at every density threshold.  ``frames``: the frame numbers to judge (default: every frame both hold).  Per
+    selected frame (CPU, ``[F, nt]``):
+
+    * ``v0_pred`` .. ``v3_pred``, ``v0_true`` .. ``v3_true`` and ``v0_difference`` .. ``v3_difference`` (pred - true);
+    * ``euler_pred``, ``euler_true`` (int64) and ``counts_pred``, ``counts_true`` (int64 ``[F, 4, nt]``);
+    * ``sigma0_pred``, ``sigma0_true``, ``sigma1_pred``, ``sigma1_true`` (``[F]``);
+    * with ``threshold_units="sigma"``: ``gaussian_v0_true`` .. ``gaussian_v3_true``,
+
+    plus ``frames`` and ``thresholds``.  With ``"sigma"`` each side is cut in units of its own standard deviation.  No
+    host synchronisation per frame; one transfer at the end."""
+    what = "rollout_minkowski"
+    mesh, nu = _check_minkowski_arguments(what, box_size, mesh, smoothing, thresholds, order, threshold_units)
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
+    packed = torch.stack([minkowski_counts_on_device(_f32_frames(x, "Coordinates", what), box_size, mesh, smoothing, nu,
+                                                     order, threshold_units) for x in (pc, tc)]).cpu()   # the one transfer
+    p = _minkowski_result(*minkowski_on_host(packed[0], len(nu)), mesh, box_size, nu, threshold_units)
+    t = _minkowski_result(*minkowski_on_host(packed[1], len(nu)), mesh, box_size, nu, threshold_units)
+    out = {"frames": sel, "thresholds": t["thresholds"]}
+    for key in ("v0", "v1", "v2", "v3"):
+        out.update({key + "_pred": p[key], key + "_true": t[key], key + "_difference": p[key] - t[key]})
+        if threshold_units == "sigma":
+            out["gaussian_" + key + "_true"] = t["gaussian_" + key]
+    for key in ("euler", "counts", "sigma0", "sigma1"):
+        out.update({key + "_pred": p[key], key + "_true": t[key]})
+    return out

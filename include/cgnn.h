@@ -933,6 +933,40 @@ size_t cgnn_bispectrum_sums_workspace_bytes(int64_t frames, int64_t cells, int32
 int cgnn_bispectrum_sums(const double* fields, int64_t frames, int64_t cells, int32_t num_bins, const int32_t* triangles,
                          int32_t num_triangles, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- morphology: the excursion sets of a field on the mesh, counted as cubical complexes --------------------------------
+ * What the four Minkowski functionals V0 .. V3 of the excursion sets of a density field are made of (Schmalzing & Buchert
+ * 1997): on a mesh they are integer counts of the cubes, faces, edges and vertices of a cubical complex.
+ * field (device, double [frames, mesh, mesh, mesh], periodic, never written); thresholds (HOST memory, num_thresholds
+ * doubles, finite, strictly ascending; they reach the device by value in kernel arguments).  For a voxel v
+ *     idx(v) = #{t : thresholds[t] <= field(v)}
+ * by exact comparisons: a value equal to a threshold is in; NaN and -inf give 0, +inf gives num_thresholds.  The excursion
+ * set at threshold t is the union of the CLOSED unit cubes of the voxels with idx > t.  Its elements and their indices:
+ *     cubes     mesh^3     voxel (i, j, k): idx(i, j, k)
+ *     faces     3 mesh^3   the lower face of (i, j, k) normal to axis a: the maximum of idx over (i, j, k) and its
+ *                          neighbour at -1 along a
+ *     edges     3 mesh^3   the edge from the lower corner of (i, j, k) along axis a: the maximum over the four voxels at
+ *                          offsets {0, -1}^2 in the other two axes
+ *     vertices  mesh^3     the lower corner of (i, j, k): the maximum over the eight voxels at offsets {0, -1}^3
+ * All offsets modulo mesh, by index arithmetic and not by geometric distinctness: this holds for mesh 2 and 3 as well,
+ * where the neighbour at -1 may be the neighbour at +1.
+ * counts (device, int64 [frames][4][num_thresholds]) is overwritten with, for d = 0, 1, 2, 3 (vertices, edges, faces,
+ * cubes), counts[f][d][t] = the number of elements of dimension d with an index above t.
+ * A workgroup of 256 threads stages the indices of a tile of CGNN_EX_TX x CGNN_EX_TY x CGNN_EX_TZ voxels and of its -1
+ * halo planes as bytes in LDS (one read of the field and one binary search per staged voxel, for all thresholds at
+ * once), every thread walks 16 consecutive z voxels and merges runs of equal index before it adds to 32-bit LDS
+ * counters; these go out with 64-bit integer atomics, and a last pass makes the suffix sums.  No float arithmetic beyond
+ * the comparisons: integers throughout, the same bits on every run and under every order.  No workspace, no host
+ * synchronisation, everything on `stream`.
+ * CGNN_ERR_INVALID_ARG for a null pointer, frames <= 0, mesh outside [2, 512], num_thresholds outside
+ * [1, CGNN_EX_MAX_THRESHOLDS], a threshold that is not finite or not above its predecessor; more than 2^20 frames:
+ * CGNN_ERR_UNSUPPORTED.  All of it is refused on the host before any device work. */
+#define CGNN_EX_MAX_THRESHOLDS 255
+#define CGNN_EX_TX 8                 /* the tile of a workgroup: voxels along x, y and z (the contiguous axis) */
+#define CGNN_EX_TY 8
+#define CGNN_EX_TZ 64
+int cgnn_excursion_counts(const double* field, int64_t frames, int32_t mesh, const double* thresholds /* HOST */,
+                          int32_t num_thresholds, int64_t* counts /* [frames][4][num_thresholds] */, void* stream);
+
 /* ---- judging a rollout by its halos: friends-of-friends groups and their catalogue ------------------------------------
  * cgnn_fof_labels labels the connected components of "closer than the linking length" among pos [n, 3] (positions in
  * [0, box_size]; a value of exactly box_size falls into the edge cell) in a periodic box of side box_size.  With d2(i, j)
