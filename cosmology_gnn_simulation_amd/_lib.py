@@ -62,6 +62,7 @@ EXPORTS = (
     "cgnn_bispectrum_shells", "cgnn_bispectrum_sums_workspace_bytes", "cgnn_bispectrum_sums",
     "cgnn_triplet_moments_workspace_bytes", "cgnn_triplet_moments",
     "cgnn_excursion_counts",
+    "cgnn_halo_potential_shift", "cgnn_halo_potentials_workspace_bytes", "cgnn_halo_potentials",
 )
 PAIR_COUNTS_MAX_BINS = 256   # CGNN_PC_MAX_BINS in csrc/pair_counts.hip
 PAIR_COUNTS_SMU_MAX_BINS = 4096   # CGNN_SMU_MAX_BINS in csrc/pair_counts_smu.hip: num_s * num_mu at most
@@ -93,6 +94,10 @@ HALO_MATCH_COLS = 6           # CGNN_HM_COLS in csrc/halo_match.hip: columns of 
 GROUP_SUMS_MAX_CHANNELS = 4   # CGNN_GS_MAX_CHANNELS
 HALO_PROFILES_MAX_BINS = 32   # CGNN_HP_MAX_BINS in csrc/halo_profiles.hip
 HALO_PROFILES_MAX_CHANNELS = 4   # CGNN_HP_MAX_CHANNELS
+HALO_BINDING_TILE = 256          # CGNN_HB_TILE in include/cgnn.h: threads per workgroup = sources per LDS tile of cgnn_halo_potentials
+HALO_BINDING_TARGETS = 512       # CGNN_HB_TARGETS: targets of a big work item, two per thread
+HALO_BINDING_SMALL = 64          # CGNN_HB_SMALL: a group of at most one wave takes a wave, four to a workgroup
+HALO_BINDING_MIN_SOFTENING_BITS = 16   # CGNN_HB_MIN_SOFTENING_BITS: softening >= box_size 2^-16
 KNN_BATCH_GROUP = 64    # CGNN_KNN_BATCH_GROUP: graphs per launch of the batched k-NN kernels
 KNN_EDGE_ATTR_REFERENCE, KNN_EDGE_ATTR_IMAGE = 0, 1   # CGNN_KNN_EDGE_ATTR_*
 ROLLOUT_ROW = 5     # CGNN_ROLLOUT_ROW: floats per packed frame row (x, y, z, temperature, id bits)
@@ -206,6 +211,11 @@ def load() -> C.CDLL:
     lib.cgnn_bispectrum_sums_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cgnn_bispectrum_sums.argtypes = [vp, i64, i64, i32, C.POINTER(i32), i32, vp, vp, sz, vp]   # triangles: host memory
     lib.cgnn_excursion_counts.argtypes = [vp, i64, i32, C.POINTER(C.c_double), i32, vp, vp]        # thresholds: host memory
+    lib.cgnn_halo_potential_shift.restype = i32
+    lib.cgnn_halo_potential_shift.argtypes = [f32, f32]
+    lib.cgnn_halo_potentials_workspace_bytes.restype = sz
+    lib.cgnn_halo_potentials_workspace_bytes.argtypes = [i64]
+    lib.cgnn_halo_potentials.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, vp, C.POINTER(i32), vp, sz, vp]   # shift: host memory
     lib.cgnn_frame_errors_workspace_bytes.restype = sz
     lib.cgnn_frame_errors_workspace_bytes.argtypes = [i64, i64]
     lib.cgnn_frame_errors.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp, vp, sz, vp]

@@ -1996,7 +1996,8 @@ def fof_labels(pos: torch.Tensor, box_size: float, linking_length: float, *, che
     Positions lie in ``[0, box_size]``; ``check_bounds=True`` verifies that with one host synchronisation, the default
     verifies nothing.  ``linking_length`` is a host value (:func:`check_linking_length`).  One box per call, positions
     only: batches of simulations (``offsets``), spatial shards (an owned-storage rollout goes through
-    ``dist.assemble_frames`` first), unbinding and velocities are out of scope (radial profiles: :func:`halo_profiles`)."""
+    ``dist.assemble_frames`` first) and velocities are out of scope (radial profiles: :func:`halo_profiles`; whether a group
+    is bound: :func:`halo_potentials`)."""
     what = "fof_labels"
     ll = check_linking_length(linking_length, box_size, what)
     pos = f32c(pos, "pos")
@@ -2101,7 +2102,7 @@ def halo_match(labels_a: torch.Tensor, size_a: torch.Tensor, labels_b: torch.Ten
     Integers throughout: the same bits on every run, whatever the order of the threads.  Labels outside ``[0, N)`` are
     ignored.  Refused on the host before any device work (``ValueError``): tensors that are not integers or not of one
     shape ``[N]`` / ``[T, N]`` with ``N >= 1``, a minimum that is no whole number of at least 1, bad ``size_edges``.  No
-    host synchronisation.  Membership only, one box, one device: no unbinding, no
+    host synchronisation.  Membership only, one box, one device (unbinding: :func:`halo_potentials`), no
     merger trees over more than two frames."""
     what = "halo_match"
     min_a = check_min_members(min_members, what)
@@ -2295,6 +2296,129 @@ def halo_profiles(pos: torch.Tensor, centres: torch.Tensor, box_size: float, edg
     if flat:
         sums = sums.squeeze(-1)
     return (counts, sums) if batched else (counts[0], sums[0])
+
+
+def check_softening(softening, box_size: float, who: str) -> Tuple[float, int]:
+    """The softening of :func:`halo_potentials` as a float32 host value with the shift ``S`` of the integer potential
+    terms, or ``ValueError``: finite, positive, at least ``box_size * 2^-16`` (below that the farthest pair of a
+    box-spanning group would be resolved by fewer than about 2^13 integer steps), its float32 square within ``[2^-100,
+    2^100]``; ``box_size`` finite and positive.  ``S`` puts ``w_max * 2^S`` into ``[2^29, 2^30)`` for ``w_max = fl32(1 /
+    fl32(sqrt(fl32(eps * eps))))``, the term of a pair at distance 0: what ``cgnn_halo_potential_shift`` gives."""
+    box = torch.tensor(float(box_size), dtype=torch.float32)
+    if not (bool(torch.isfinite(box)) and float(box) > 0.0):
+        raise ValueError(f"{who}: box_size must be positive and finite, got {box_size!r}")
+    if isinstance(softening, bool) or not isinstance(softening, (int, float)):
+        raise ValueError(f"{who}: softening must be a host number, got {softening!r}")
+    eps = torch.tensor(float(softening), dtype=torch.float32)
+    if not (bool(torch.isfinite(eps)) and float(eps) > 0.0):
+        raise ValueError(f"{who}: softening must be positive and finite (in float32), got {softening!r}")
+    floor = box * 2.0 ** -_lib.HALO_BINDING_MIN_SOFTENING_BITS
+    if bool(eps < floor):
+        raise ValueError(f"{who}: softening {float(eps)} is below box_size * 2^-{_lib.HALO_BINDING_MIN_SOFTENING_BITS} = "
+                         f"{float(floor)}: the integer potential terms would not resolve the far pairs")
+    eps2 = eps * eps
+    if not 2.0 ** -100 <= float(eps2) <= 2.0 ** 100:
+        raise ValueError(f"{who}: the float32 square of softening {float(eps)} leaves [2^-100, 2^100]")
+    w_max = 1.0 / torch.sqrt(eps2)                                        # float32, each step correctly rounded
+    return float(eps), 30 - math.frexp(float(w_max))[1]
+
+
+def halo_member_order(labels: torch.Tensor, size: torch.Tensor, min_members: int = 20):
+    """The members of the listed groups of a labelling, contiguously: for ``labels`` and ``size`` of :func:`fof_labels` and
+    :func:`fof_catalogue` (``[N]`` or ``[T, N]``, any integer tensors, on any device) returns int32 ``(order, start,
+    count)`` in their shape.  A particle is listed iff its label ``r`` lies in ``[0, N)`` and ``size[r] >= min_members``;
+    ``order`` is the stable sort of the particle indices by the key ``r`` for a listed particle and ``N`` for any other
+    (the unlisted particles end up behind all groups, in index order); ``count[r]`` is the number of listed particles
+    with label ``r`` and ``start[r]`` the exclusive prefix sum of ``count``: slot ``start[r] + j`` of ``order`` holds the
+    ``j``-th member of group ``r`` by index.  Fixed shapes, torch calls only: no host synchronisation."""
+    what = "halo_member_order"
+    min_members = check_min_members(min_members, what)
+    _check_group_ints(labels, "labels", None, what)
+    if labels.dim() not in (1, 2) or labels.shape[-1] < 1 or labels.shape[0] < 1:
+        raise ValueError(f"{what}: labels must be [N] or [T, N] with N >= 1, got {tuple(labels.shape)}")
+    _check_group_ints(size, "size", labels.shape, what)
+    _same_device(labels, size)
+    n = labels.shape[-1]
+    lab = labels.to(torch.int64)
+    inside = (lab >= 0) & (lab < n)
+    safe = lab.clamp(0, n - 1)
+    listed = inside & (torch.gather(size.to(torch.int64), -1, safe) >= min_members)
+    key = torch.where(listed, safe, torch.full_like(safe, n))
+    order = torch.argsort(key, dim=-1, stable=True)
+    count = torch.zeros(labels.shape[:-1] + (n + 1,), dtype=torch.int64, device=labels.device)
+    count.scatter_add_(-1, key, torch.ones_like(key))                     # integer sums: the same bits on every run
+    count = count[..., :n]
+    start = torch.cumsum(count, dim=-1) - count
+    return order.to(torch.int32), start.to(torch.int32), count.to(torch.int32).contiguous()
+
+
+def halo_potentials(pos: torch.Tensor, labels: torch.Tensor, size: torch.Tensor, box_size: float, softening: float,
+                    min_members: int = 20, active: Optional[torch.Tensor] = None, *, members=None):
+    """The softened potential sums inside the friends-of-friends groups of a frame, in exact integers
+    (``cgnn_halo_potentials``): ``pos [N, 3]`` with ``labels [N]`` and ``size [N]`` of :func:`fof_labels` and
+    :func:`fof_catalogue`, or ``[T, N, 3]`` with ``[T, N]`` (one call per frame on the same stream).  Returns ``(psum,
+    shift)``: int64 ``[(T,) N]`` and the host integer ``S``.  For every particle ``i`` that is active and whose group is
+    listed (its root's ``size >= min_members``)
+
+        ``psum[i] = sum over j != i, j in the same group and active, of rint(w_ij * 2^S)``,
+        ``w_ij = fl32(1 / fl32(sqrt(fl32(d2_ij + fl32(eps * eps)))))``
+
+    with ``d2`` the float32 minimum-image squared distance of :func:`pair_counts`, one rounding per operation, sqrt and
+    division correctly rounded; 0 at every other particle, which is no source either.  ``psum * 2^-S`` is ``sum 1 /
+    sqrt(r^2 + eps^2)`` in inverse units of the positions' length: the potential is ``-G m psum 2^-S``
+    (:func:`statistics.binding_energies`).  ``active``: bool or uint8 ``[(T,) N]``, ``None`` for all.  ``softening``:
+    :func:`check_softening`, a host value.  ``members``: the ``(order, start, count)`` of :func:`halo_member_order` for
+    these ``labels``, ``size`` and ``min_members`` when the caller holds them already (the unbinding passes).
+
+    Integer sums with ``iw_ij == iw_ji``: independent of the order of threads and particles, the same bits on every
+    run, bit-equal to the numpy restatement.  Labels outside ``[0, N)`` are ignored.  Refused on the host before any
+    device work (``ValueError`` / ``CgnnError``): wrong dtypes or shapes, a bad softening, a bad ``min_members``, tensors
+    on different devices.  No host synchronisation.  Equal masses, direct sums, members only: unequal masses, tree or
+    mesh potentials, particles outside a group as sources, sharded, batched (``offsets``) or owned-storage inputs
+    (``dist.assemble_frames`` first) are out of scope."""
+    what = "halo_potentials"
+    eps, shift = check_softening(softening, box_size, what)
+    min_members = check_min_members(min_members, what)
+    if not torch.is_tensor(pos) or not pos.is_floating_point() or pos.dim() not in (2, 3) or pos.shape[-1] != 3 or \
+            pos.shape[-2] < 1 or pos.shape[0] < 1:
+        raise ValueError(f"{what}: pos must be a float tensor [N, 3] or [T, N, 3] with N >= 1, got "
+                         f"{tuple(pos.shape) if torch.is_tensor(pos) else pos!r}")
+    lead = tuple(pos.shape[:-1])
+    _check_group_ints(labels, "labels", lead, what)
+    _check_group_ints(size, "size", lead, what)
+    if active is not None and (not torch.is_tensor(active) or active.dtype not in (torch.bool, torch.uint8) or
+                               tuple(active.shape) != lead):
+        raise ValueError(f"{what}: active must be a bool or uint8 tensor {list(lead)}, got "
+                         f"{(active.dtype, tuple(active.shape)) if torch.is_tensor(active) else active!r}")
+    if members is not None and (len(members) != 3 or any(not torch.is_tensor(m) or m.dtype != torch.int32 or
+                                                         tuple(m.shape) != lead for m in members)):
+        raise ValueError(f"{what}: members must be the (order, start, count) of halo_member_order, int32 {list(lead)} each")
+    _same_device(pos, labels, size, active, *(members or ()))
+    pos = f32c(pos, "pos")
+    if members is None:
+        members = halo_member_order(labels, size, min_members)
+    order, start, count = (i32c(m, "members") for m in members)
+    act = None if active is None else active.to(torch.uint8).contiguous()
+    batched = pos.dim() == 3
+    if not batched:
+        pos, order, start, count = pos.unsqueeze(0), order.unsqueeze(0), start.unsqueeze(0), count.unsqueeze(0)
+        act = None if act is None else act.unsqueeze(0)
+    t, n = pos.shape[0], pos.shape[1]
+    lib = _lib.load()
+    ws_bytes = lib.cgnn_halo_potentials_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+    psum = torch.empty((t, n), dtype=torch.int64, device=pos.device)
+    got = C.c_int32(0)
+    st = stream_ptr(pos.device)
+    with _timed(what, pos.device):
+        for f in range(t):
+            check(lib.cgnn_halo_potentials(pos[f].data_ptr(), order[f].data_ptr(), start[f].data_ptr(),
+                                           count[f].data_ptr(), None if act is None else act[f].data_ptr(), n,
+                                           float(box_size), eps, psum[f].data_ptr(), C.byref(got), ws.data_ptr(), ws_bytes,
+                                           st), "cgnn_halo_potentials")
+            if got.value != shift:
+                raise CgnnError(f"{what}: the library's shift {got.value} is not the host's {shift}")
+    return (psum if batched else psum[0]), shift
 
 
 def window_features(pos_seq: torch.Tensor, temp_seq: torch.Tensor, metadata: dict, dt: float, box_size: float,

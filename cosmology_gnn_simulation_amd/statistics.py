@@ -69,6 +69,13 @@ functions of the threshold, from exact integer counts of the cubes, faces, edges
 that for every frame of a rollout against the truth, ``minkowski_from_counts`` is the host arithmetic and
 ``default_minkowski_thresholds`` the 25 thresholds from -3 to 3 standard deviations.
 
+Whether the halos are gravitationally bound, which nothing above says (a friends-of-friends group is a set of particles
+that are close together): ``halo_binding`` unbinds the groups of one frame -- per member the softened potential of the
+other members in exact integers (``ops.halo_potentials``), the specific energies (``binding_energies``), a fixed number
+of passes that drop the members with ``e >= 0`` -- and lists bound masses, virial ratios and velocity dispersions;
+``rollout_halo_binding`` does that for every frame of a rollout from 1 on against the truth, ``binding_from_sums`` and
+``binding_size_bins`` are the host arithmetic.
+
 One box per call.  Batches of simulations (``offsets``) and counting across spatial shards are out of scope: an
 owned-storage rollout (``dist.sharded_rollout(storage="owned")``) goes through ``dist.assemble_frames`` first.
 """
@@ -1228,7 +1235,7 @@ def halo_catalogue(pos: torch.Tensor, box_size: float, linking_length: Optional[
       meaningful centre).
 
     The number of groups is only known on the device: this function synchronises once (``nonzero``) after the kernels
-    and before its single transfer.  Positions only: no unbinding, no velocities (profiles and spherical-overdensity
+    and before its single transfer.  Positions only: no velocities (unbinding: :func:`halo_binding`; profiles and spherical-overdensity
     masses: :func:`halo_profiles`); one box, no spatial shards (``dist.assemble_frames`` first)."""
     what = "halo_catalogue"
     if pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
@@ -1286,7 +1293,7 @@ def halo_mass_function(pos: torch.Tensor, box_size: float, linking_length: Optio
       (beyond the last edge too) and the fraction of the particles they hold;  ``largest``: the largest group.
 
     Everything is computed on the device of ``pos`` without a host synchronisation and comes back in one transfer.
-    One box per call, positions only (no unbinding or velocities; no ``offsets``
+    One box per call, positions only (no velocities -- unbinding: :func:`halo_binding`; no ``offsets``
     batches; no spatial shards: ``dist.assemble_frames`` first)."""
     what = "halo_mass_function"
     frames = _frames3(pos, "pos", what)
@@ -1315,7 +1322,7 @@ def rollout_halo_statistics(rollout_data: Dict[str, torch.Tensor], ground_truth:
 
     plus ``frames``, ``size_lo`` and ``size_hi``.  No synchronisation per frame; the results come back in one packed
     transfer.  The two frames' halos are not matched with each other here (:func:`rollout_halo_matching` does that); no
-    unbinding or velocities; one box, no spatial shards (an owned-storage rollout goes
+    velocities (whether the groups are bound: :func:`rollout_halo_binding`); one box, no spatial shards (an owned-storage rollout goes
     through ``dist.assemble_frames`` first)."""
     what = "rollout_halo_statistics"
     pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
@@ -1363,7 +1370,7 @@ def halo_matches(pos_a: torch.Tensor, pos_b: torch.Tensor, box_size: float, link
       ``match_mean_value``, the partner's mean over its members in frame B, ``nan`` without a match.
 
     The number of groups is only known on the device: one synchronisation (``nonzero``) after the kernels and one
-    transfer, as :func:`halo_catalogue`.  One box, one device, membership only: no unbinding, no merger trees over more than two frames; no spatial shards (``dist.assemble_frames`` first)."""
+    transfer, as :func:`halo_catalogue`.  One box, one device, membership only (unbinding: :func:`halo_binding`), no merger trees over more than two frames; no spatial shards (``dist.assemble_frames`` first)."""
     what = "halo_matches"
     for pos, name in ((pos_a, "pos_a"), (pos_b, "pos_b")):
         if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
@@ -1481,7 +1488,7 @@ def rollout_halo_matching(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     ``n_unmatched_pred`` (the listed predicted groups without a mutual partner), plus ``frames``, ``size_lo`` and
     ``size_hi``.  The ratios are formed on the host from the integer sums.  No synchronisation per frame, one packed
     transfer.  Arguments and refusals are those of :func:`rollout_halo_statistics`.  One box, one device, membership
-    only: no unbinding, no merger trees over more than two frames; an owned-storage
+    only (unbinding: :func:`rollout_halo_binding`), no merger trees over more than two frames; an owned-storage
     rollout goes through ``dist.assemble_frames`` first."""
     what = "rollout_halo_matching"
     pc, tc, sel = _rollout_frames(rollout_data, ground_truth, frames, what)
@@ -1562,7 +1569,7 @@ def so_masses(counts: torch.Tensor, n: int, box_size: float, edges, delta: float
     ``nan`` where there is no ``i*`` (the halo is too diffuse for ``delta`` at every edge) or no ``k`` (the profile does not
     reach out far enough).  An empty core (``D_1 < delta``) is passed over: the search for ``k`` begins at ``i*``.  The
     limit of the rule: everything inside a radius counts, so a heavier neighbour inside the last edge can keep ``D``
-    above ``delta`` and move the crossing outward (no unbinding, no exclusion of other halos).  Cumulative sums and
+    above ``delta`` and move the crossing outward (bound or not: :func:`halo_binding` unbinds; no exclusion of other halos).  Cumulative sums and
     comparisons in float64 torch: no host synchronisation."""
     what = "so_masses"
     r = _radii(edges, box_size, what)
@@ -1614,7 +1621,7 @@ def halo_profiles(pos: torch.Tensor, box_size: float, edges=None, linking_length
     * ``r_delta``, ``m_delta`` float64 ``[H]``: :func:`so_masses` for ``delta``, ``nan`` where undefined.
 
     The number of groups is only known on the device: one synchronisation (``nonzero``) and one transfer, as
-    :func:`halo_catalogue`.  One box, one device; no unbinding (every particle inside a radius counts); no spatial
+    :func:`halo_catalogue`.  One box, one device; every particle inside a radius counts, bound or not (:func:`halo_binding`); no spatial
     shards (``dist.assemble_frames`` first), no ``offsets`` batches."""
     what = "halo_profiles"
     if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1:
@@ -1749,7 +1756,7 @@ def rollout_halo_profiles(rollout_data: Dict[str, torch.Tensor], ground_truth: D
     in none of the sums (a truncation is never silent), plus ``frames``, ``size_lo``, ``size_hi``, ``r_lo`` and ``r_hi``.  A
     group beyond the last size edge is profiled but in no bin.  No synchronisation per frame, one packed transfer.
     Out of scope: profiles of matched pairs (a true halo against its partner: :func:`rollout_halo_matching` pairs
-    them), unbinding, ``offsets`` batches, and sharded or owned-storage inputs (``dist.assemble_frames`` first)."""
+    them; whether they are bound: :func:`rollout_halo_binding`), ``offsets`` batches, and sharded or owned-storage inputs (``dist.assemble_frames`` first)."""
     what = "rollout_halo_profiles"
     key = next((k for k in _TEMPERATURE_KEYS if k in rollout_data and k in ground_truth), None)
     dev = rollout_data["Coordinates"].device
@@ -1796,6 +1803,362 @@ def rollout_halo_profiles(rollout_data: Dict[str, torch.Tensor], ground_truth: D
         if key is not None:
             sums = ints[:, 1 + 2 * sb + sb * nb:].reshape(nf, sb, nb).to(torch.float64)
             res["temperature_" + name] = sums / counts.to(torch.float64) * (scales_h[side] / float(1 << _lib.WEIGHT_BITS))
+    return res
+
+
+# ---- is a halo bound: potentials inside the groups, unbinding, virial ratios ---------------------------------------------
+#
+# A friends-of-friends group is a set of particles that are close together; it is a halo only if they are also
+# gravitationally bound.  An emulator can put the right number of particles in the right places and still give them
+# velocities that fly apart in the next frames: the mass function, the matching and the profiles above all call such
+# a group a correct halo.  ``ops.halo_potentials`` gives every member its softened potential sum over the other members
+# in exact integers; what follows is elementwise float64 arithmetic and integer group sums on top of it.
+#
+# Units: ``gm`` is G times the particle mass in length^3 / time^2 of the caller's positions and velocities; energies are
+# specific (per unit particle mass).  Equal masses, direct sums over the members of a group only.  Out of scope: unequal
+# masses, tree or mesh potentials, particles outside a group as sources, subhalo finding, re-accretion of removed
+# particles, partial removal per pass, sharded, batched or owned-storage inputs (``dist.assemble_frames`` first), a loss.
+
+BINDING_VELOCITY_BITS = _lib.WEIGHT_BITS   # a group's bulk velocity: integer sums of velocities in 2^-20 of the scale
+BINDING_ENERGY_BITS = 32                   # group sums of energies: integers in 2^-32 of the largest term
+BINDING_SPLIT_BITS = 20                    # a potential sum enters a group sum as two words, P >> 20 and P & (2^20 - 1)
+
+
+def _check_gm(what: str, gm, hubble, iterations=None):
+    for name, v, positive in (("gm", gm, True), ("hubble", hubble, False)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (positive and not v > 0):
+            raise ValueError(f"{what}: {name} must be a {'positive ' if positive else ''}finite number, got {v!r}")
+    if iterations is not None and (isinstance(iterations, bool) or not isinstance(iterations, int) or
+                                   not 1 <= iterations <= 64):
+        raise ValueError(f"{what}: iterations must be a whole number in [1, 64], got {iterations!r}")
+
+
+def _slot_sums(key: torch.Tensor, values: torch.Tensor, n: int) -> torch.Tensor:
+    """Integer sums per root slot: ``out[r] = sum of values[i] over key[i] == r`` for int64 ``values [N]`` or ``[N, C]``,
+    ``key`` in ``[0, n]`` (slot ``n`` collects what is in no group and is dropped).  Integer ``index_add``: the same bits
+    on every run."""
+    out = torch.zeros((n + 1,) + tuple(values.shape[1:]), dtype=torch.int64, device=values.device)
+    out.index_add_(0, key, values)
+    return out[:n]
+
+
+def _quantised_slot_sums(key: torch.Tensor, values: torch.Tensor, mask: torch.Tensor, n: int):
+    """Group sums of float64 ``values [N]`` over the particles of ``mask`` as integers: ``(sums int64 [n], scale)`` with
+    ``scale`` the largest ``|value|`` under the mask (0-d float64, 1 where there is none) and a value entering as
+    ``rint(value / scale * 2^32)``; the group's sum is ``sums * scale / 2^32``, each term off by at most half a step."""
+    zero = torch.zeros((), dtype=torch.float64, device=values.device)
+    v = torch.where(mask, values, zero)
+    m = v.abs().max()
+    scale = torch.where(m > 0, m, torch.ones_like(m))
+    q = torch.round(v / scale * float(1 << BINDING_ENERGY_BITS)).to(torch.int64)
+    return _slot_sums(key, q, n), scale
+
+
+def binding_energies(psum: torch.Tensor, shift: int, gm: float, vel: torch.Tensor, labels: torch.Tensor,
+                     active: torch.Tensor, dx: Optional[torch.Tensor] = None, hubble: float = 0.0,
+                     internal_energy: Optional[torch.Tensor] = None, velocity_scale=None) -> Dict:
+    """The specific energies of the particles of one frame from the integer potential sums of ``ops.halo_potentials``
+    (``psum [N]``, ``shift``), elementwise in float64 on the device of ``psum``:
+
+    * ``potential``: ``phi_i = -gm * psum_i * 2^-shift``, ``gm`` = G times the particle mass;
+    * ``kinetic``: ``k_i = 1/2 |v_i - v_bulk + hubble * dx_i|^2 (+ internal_energy_i)`` with ``v_bulk`` the mean velocity
+      of the active members of ``i``'s group (``labels [N]``, ``active [N]`` bool) and ``dx [N, 3]`` the minimum-image
+      displacement from the group's centre (needed with ``hubble != 0``);
+    * ``energy``: ``e_i = k_i + phi_i``; a member is bound iff ``e_i < 0``;
+    * ``peculiar2``: ``|v_i - v_bulk|^2``; ``v_bulk`` float64 ``[N, 3]`` and ``n_active`` int64 ``[N]`` per root slot.
+
+    ``v_bulk`` comes from integer sums: the velocities enter as ``rint(v / velocity_scale * 2^20)`` (default scale: the
+    largest ``|v|`` component, taken on the device; components beyond a given scale are clamped), summed by integer
+    ``index_add``: the same bits on every run.  The values at inactive particles are computed like the others (against
+    their label's bulk velocity) and mean nothing.  No host synchronisation."""
+    what = "binding_energies"
+    _check_gm(what, gm, hubble)
+    if not torch.is_tensor(psum) or psum.dtype != torch.int64 or psum.dim() != 1 or psum.shape[0] < 1:
+        raise ValueError(f"{what}: psum must be an int64 tensor [N], got "
+                         f"{(psum.dtype, tuple(psum.shape)) if torch.is_tensor(psum) else psum!r}")
+    n = psum.shape[0]
+    if isinstance(shift, bool) or not isinstance(shift, int) or not -200 < shift < 200:
+        raise ValueError(f"{what}: shift must be the integer ops.halo_potentials returns, got {shift!r}")
+    if not torch.is_tensor(vel) or tuple(vel.shape) != (n, 3) or not vel.is_floating_point():
+        raise ValueError(f"{what}: vel must be a float tensor [{n}, 3]")
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (n,) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"{what}: labels must be an integer tensor [{n}]")
+    if not torch.is_tensor(active) or tuple(active.shape) != (n,) or active.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{what}: active must be a bool or uint8 tensor [{n}]")
+    if dx is None and float(hubble) != 0.0:
+        raise ValueError(f"{what}: hubble needs dx, the displacements from the group centres")
+    if dx is not None and (not torch.is_tensor(dx) or tuple(dx.shape) != (n, 3)):
+        raise ValueError(f"{what}: dx must be [{n}, 3]")
+    if internal_energy is not None and (not torch.is_tensor(internal_energy) or tuple(internal_energy.shape) != (n,)):
+        raise ValueError(f"{what}: internal_energy must be [{n}]")
+    dev = psum.device
+    v = vel.to(device=dev, dtype=torch.float64)
+    lab = labels.to(device=dev, dtype=torch.int64)
+    act = active.to(dev).bool() & (lab >= 0) & (lab < n)
+    key = torch.where(act, lab, torch.full_like(lab, n))
+    if velocity_scale is None:
+        m = v.abs().max()
+        scale = torch.where(m > 0, m, torch.ones_like(m))
+    else:
+        scale = ops._check_value_scale(velocity_scale, what)
+        scale = scale.to(device=dev, dtype=torch.float64) if torch.is_tensor(scale) else scale
+    unit = float(1 << BINDING_VELOCITY_BITS)
+    q = torch.round(torch.clamp(v / scale, -1.0, 1.0) * unit).to(torch.int64)
+    n_active = _slot_sums(key, torch.ones_like(key), n)
+    v_bulk = _slot_sums(key, q, n).to(torch.float64) / n_active.clamp(min=1).to(torch.float64).unsqueeze(-1) * (scale / unit)
+    u = v - v_bulk.index_select(0, lab.clamp(0, n - 1))
+    peculiar2 = (u * u).sum(dim=-1)
+    if dx is not None and float(hubble) != 0.0:
+        u = u + float(hubble) * dx.to(device=dev, dtype=torch.float64)
+    kinetic = 0.5 * (u * u).sum(dim=-1)
+    if internal_energy is not None:
+        kinetic = kinetic + internal_energy.to(device=dev, dtype=torch.float64)
+    potential = psum.to(torch.float64) * (-float(gm) * 2.0 ** -shift)
+    return {"kinetic": kinetic, "potential": potential, "energy": kinetic + potential, "peculiar2": peculiar2,
+            "v_bulk": v_bulk, "n_active": n_active}
+
+
+def binding_from_sums(size, n_bound, kinetic_q, kinetic_scale, peculiar_q, peculiar_scale, psum_hi, psum_lo, shift: int,
+                      gm: float) -> Dict:
+    """The per-group results of an unbinding from its integer group sums, float64, elementwise (on the device of the
+    sums, or on the host): for groups of ``size`` members of which ``n_bound`` stayed,
+
+    * ``bound_fraction = n_bound / size``;
+    * ``kinetic = kinetic_q * kinetic_scale / 2^32``, the sum of the bound members' ``k_i``;
+    * ``potential = -gm / 2 * (psum_hi * 2^20 + psum_lo) * 2^-shift``: ``W = 1/2 sum phi_i`` over the bound members, the
+      potential sums having entered as two words, ``P >> 20`` and ``P & (2^20 - 1)`` (the sum of whole ``P`` over a group of
+      10^5 members can pass int64);
+    * ``virial_ratio = 2 kinetic / |potential|``, ``nan`` without a potential (fewer than two bound members);
+    * ``sigma_v = sqrt(peculiar_q * peculiar_scale / 2^32 / n_bound)``, the three-dimensional velocity dispersion of the
+      bound members about their mean, ``nan`` without a bound member."""
+    f64 = torch.float64
+    size, n_bound = torch.as_tensor(size), torch.as_tensor(n_bound)
+    nb = n_bound.to(f64)
+    step = 2.0 ** -BINDING_ENERGY_BITS
+    kinetic = torch.as_tensor(kinetic_q).to(f64) * (torch.as_tensor(kinetic_scale).to(f64) * step)
+    words = torch.as_tensor(psum_hi).to(f64) * float(1 << BINDING_SPLIT_BITS) + torch.as_tensor(psum_lo).to(f64)
+    potential = words * (-0.5 * float(gm) * 2.0 ** -int(shift))
+    nan = torch.full_like(kinetic, float("nan"))
+    virial = torch.where(potential != 0, 2.0 * kinetic / potential.abs(), nan)
+    pec = torch.as_tensor(peculiar_q).to(f64) * (torch.as_tensor(peculiar_scale).to(f64) * step)
+    sigma = torch.where(n_bound > 0, torch.sqrt(pec / nb.clamp(min=1.0)), nan)
+    return {"bound_fraction": nb / size.to(f64).clamp(min=1.0), "kinetic": kinetic, "potential": potential,
+            "virial_ratio": virial, "sigma_v": sigma}
+
+
+def binding_size_bins(size, n_bound, bound_fraction, virial_ratio, sigma_v, size_edges, min_members: int):
+    """The groups of an unbinding by size, as masked sums in a fixed order: ``size``, ``n_bound`` (integers) and the three
+    float64 results of :func:`binding_from_sums`, one entry per group or per root slot (an entry with ``size <
+    min_members`` is no group and is in no sum).  With ``sb = len(size_edges) - 1`` bins ``size_edges[b] <= size <
+    size_edges[b + 1]`` returns ``(ints, floats)`` on the device of ``size``:
+
+    * ``ints`` int64 ``[5, sb]``: the groups of the bin; those left with fewer than ``min_members`` bound members (the
+      spurious halos); the groups whose BOUND size lies in the bin (the bound mass function); the groups of the bin with
+      a defined virial ratio; with a defined ``sigma_v``;
+    * ``floats`` float64 ``[3, sb]``: the sums over the groups of the bin of the bound fraction, of the defined virial
+      ratios and of the defined ``sigma_v``."""
+    size = torch.as_tensor(size).to(torch.int64)
+    n_bound = torch.as_tensor(n_bound).to(torch.int64).to(size.device)
+    listed = size >= int(min_members)
+    lo_hi = list(zip(size_edges[:-1], size_edges[1:]))
+    in_bin = torch.stack([listed & (size >= int(lo)) & (size < int(hi)) for lo, hi in lo_hi], dim=0)        # [sb, G]
+    bound_bin = torch.stack([listed & (n_bound >= int(lo)) & (n_bound < int(hi)) for lo, hi in lo_hi], dim=0)
+    vir_ok, sig_ok = ~torch.isnan(virial_ratio), ~torch.isnan(sigma_v)
+    ints = torch.stack([in_bin.sum(dim=1), (in_bin & (n_bound < int(min_members))).sum(dim=1), bound_bin.sum(dim=1),
+                        (in_bin & vir_ok).sum(dim=1), (in_bin & sig_ok).sum(dim=1)])
+    zero = torch.zeros((), dtype=torch.float64, device=size.device)
+    floats = torch.stack([torch.where(in_bin, bound_fraction, zero).sum(dim=1),
+                          torch.where(in_bin & vir_ok, virial_ratio, zero).sum(dim=1),
+                          torch.where(in_bin & sig_ok, sigma_v, zero).sum(dim=1)])
+    return ints.to(torch.int64), floats
+
+
+def _binding_velocities(what: str, pos: torch.Tensor, vel, pos_prev, dt, box_size: float) -> torch.Tensor:
+    """The float64 velocities of one frame, those of :func:`pairwise_velocities`: ``vel``, or ``minimum_image(pos -
+    pos_prev) / dt``."""
+    moving = pos_prev is not None
+    if (vel is not None) == moving:
+        raise ValueError(f"{what}: exactly one of vel or (pos_prev, dt) gives the velocities")
+    if moving:
+        dt = _check_dt(what, dt)
+    elif dt is not None:
+        raise ValueError(f"{what}: dt goes with pos_prev")
+    other = pos_prev if moving else vel
+    if not torch.is_tensor(other) or tuple(other.shape) != tuple(pos.shape) or not other.is_floating_point():
+        raise ValueError(f"{what}: the {'previous positions' if moving else 'velocities'} must be a float tensor "
+                         f"{tuple(pos.shape)} like pos")
+    other = other.to(pos.device)
+    return _step_velocities(pos.to(torch.float32), other.to(torch.float32), dt, box_size) if moving else other.to(torch.float64)
+
+
+def halo_unbinding_on_device(pos: torch.Tensor, vel: torch.Tensor, box_size: float, gm: float, softening: float,
+                             linking_length: float, min_members: int, hubble: float = 0.0,
+                             internal_energy: Optional[torch.Tensor] = None, iterations: int = 3) -> Dict:
+    """The device part of :func:`halo_binding` for one frame ``pos [N, 3]`` with float64 velocities ``vel [N, 3]``:
+    friends-of-friends groups, then ``iterations`` unbinding passes -- each recomputes the bulk velocities and the
+    potentials from the particles still active (``ops.halo_potentials``, :func:`binding_energies`) and drops every member
+    with ``e_i >= 0`` -- and one evaluation pass over the members that stayed, from which the reported sums come.  Returns
+    device tensors: ``labels``, ``size`` (of the catalogue), ``bound`` (bool ``[N]``), per root slot int64 ``[N]`` ``n_bound``,
+    ``removed_last`` (the members the last pass dropped), ``kinetic_q``, ``peculiar_q``, ``psum_hi``, ``psum_lo``, the 0-d
+    float64 ``kinetic_scale`` and ``peculiar_scale``, and the host integer ``shift``: the arguments of
+    :func:`binding_from_sums`.  Fixed shapes and a fixed number of passes: no host synchronisation."""
+    n = pos.shape[0]
+    box = float(torch.tensor(float(box_size), dtype=torch.float32))
+    labels = ops.fof_labels(pos, box_size, linking_length)
+    size, disp, _ = ops.fof_catalogue(pos, labels, box_size, want_disp=float(hubble) != 0.0)
+    members = ops.halo_member_order(labels, size, min_members)
+    lab = labels.to(torch.int64)
+    active = size.index_select(0, lab) >= int(min_members)
+    dx = None
+    if float(hubble) != 0.0:      # from the catalogue's centre (halo_centres), float64, under the minimum image
+        p64 = pos.to(torch.float64)
+        centre = p64.index_select(0, lab) + disp.index_select(0, lab).to(torch.float64) / \
+            size.index_select(0, lab).clamp(min=1).to(torch.float64).unsqueeze(-1) * (box / _lib.FOF_DISP_UNITS)
+        d = p64 - centre
+        dx = d - box * torch.round(d / box)
+    m = vel.abs().max()
+    vscale = torch.where(m > 0, m, torch.ones_like(m))
+    removed_last = torch.zeros(n, dtype=torch.int64, device=pos.device)
+    shift = 0
+    for it in range(int(iterations) + 1):
+        psum, shift = ops.halo_potentials(pos, labels, size, box_size, softening, min_members, active, members=members)
+        be = binding_energies(psum, shift, gm, vel, labels, active, dx, hubble, internal_energy, vscale)
+        if it == int(iterations):
+            break
+        keep = active & (be["energy"] < 0)
+        key = torch.where(active & ~keep, lab, torch.full_like(lab, n))
+        removed_last = _slot_sums(key, torch.ones_like(key), n)
+        active = keep
+    key = torch.where(active, lab, torch.full_like(lab, n))
+    kq, kscale = _quantised_slot_sums(key, be["kinetic"], active, n)
+    sq, sscale = _quantised_slot_sums(key, be["peculiar2"], active, n)
+    p = torch.where(active, psum, torch.zeros_like(psum))
+    return {"labels": labels, "size": size, "bound": active, "n_bound": be["n_active"], "removed_last": removed_last,
+            "kinetic_q": kq, "kinetic_scale": kscale, "peculiar_q": sq, "peculiar_scale": sscale,
+            "psum_hi": _slot_sums(key, p >> BINDING_SPLIT_BITS, n),
+            "psum_lo": _slot_sums(key, p & ((1 << BINDING_SPLIT_BITS) - 1), n), "shift": shift}
+
+
+def _check_binding_arguments(what: str, n: int, box_size, gm, softening, linking_length, hubble, iterations):
+    _check_gm(what, gm, hubble, iterations)
+    ops.check_softening(softening, box_size, what)
+    ll = default_linking_length(n, box_size) if linking_length is None else linking_length
+    return ops.check_linking_length(ll, box_size, what)
+
+
+def halo_binding(pos: torch.Tensor, box_size: float, gm: float, softening: float, vel: Optional[torch.Tensor] = None,
+                 pos_prev: Optional[torch.Tensor] = None, dt: Optional[float] = None,
+                 linking_length: Optional[float] = None, min_members: int = 20, hubble: float = 0.0,
+                 internal_energy: Optional[torch.Tensor] = None, iterations: int = 3) -> Dict:
+    """Which friends-of-friends groups of one frame ``pos [N, 3]`` are gravitationally BOUND, and how much of each: the
+    groups with at least ``min_members`` members (the steps of :func:`halo_catalogue`), unbound by ``iterations`` passes.
+    Velocities are those of :func:`pairwise_velocities`: ``vel [N, 3]``, or ``minimum_image(pos - pos_prev) / dt``.  A pass
+    gives every active member ``e_i = k_i + phi_i`` (:func:`binding_energies`: ``phi_i = -gm * P_i * 2^-S`` from the exact
+    integer sums of ``ops.halo_potentials`` with the Plummer ``softening``, ``k_i = 1/2 |v_i - v_bulk + hubble * dx_i|^2 +
+    internal_energy_i``, ``v_bulk`` the mean velocity of the group's active members, ``dx_i`` the minimum-image displacement
+    from the catalogue's centre) and drops every member with ``e_i >= 0``, all at once; a last evaluation over the members
+    that stayed gives the reported sums.  ``gm`` is G times the particle mass in length^3 / time^2.  Returns on the CPU,
+    sorted as :func:`halo_catalogue` sorts (size descending, then root ascending), per group:
+
+    * ``root``, ``size`` int64 ``[H]``; ``n_bound`` int64, ``bound_fraction`` float64;
+    * ``kinetic``, ``potential`` float64: ``K = sum k_i`` and ``W = 1/2 sum phi_i`` over the bound members, per unit particle
+      mass; ``virial_ratio = 2 K / |W|`` (``nan`` with fewer than two bound members); ``sigma_v``: their three-dimensional
+      velocity dispersion about ``v_bulk`` (``nan`` without one);
+    * ``removed_last`` int64: the members the last pass dropped -- not 0 means that the unbinding has not converged in
+      ``iterations`` passes, which is therefore never silent,
+
+    and ``bound`` bool ``[N]``, the per-particle mask, with ``shift``, the ``S`` of the potentials.  Group sums are integer
+    sums (:func:`binding_from_sums`): the same bits on every run.  One synchronisation (``nonzero``) and one transfer,
+    as :func:`halo_profiles`.  Out of scope: unequal masses, tree or mesh potentials, particles outside a group as
+    sources, subhalo finding, re-accretion of removed particles, partial removal per pass, sharded, batched or
+    owned-storage inputs (``dist.assemble_frames`` first), a loss."""
+    what = "halo_binding"
+    if not torch.is_tensor(pos) or pos.dim() != 2 or pos.shape[-1] != 3 or pos.shape[0] < 1 or not pos.is_floating_point():
+        raise ValueError(f"{what}: pos must be one frame [N, 3] of floats with N >= 1, got "
+                         f"{tuple(pos.shape) if torch.is_tensor(pos) else pos!r}")
+    n = pos.shape[0]
+    min_members = ops.check_min_members(min_members, what)
+    ll = _check_binding_arguments(what, n, box_size, gm, softening, linking_length, hubble, iterations)
+    v = _binding_velocities(what, pos, vel, pos_prev, dt, box_size)
+    u = _group_values(internal_energy, n, "internal_energy", what)
+    if u is not None and (u.dim() != 1 or not u.is_floating_point()):
+        raise ValueError(f"{what}: internal_energy must be a float tensor [{n}]")
+    _lib.require_device(pos, "pos")
+    d = halo_unbinding_on_device(pos, v, box_size, gm, softening, ll, min_members, hubble,
+                                 None if u is None else u.to(pos.device), iterations)
+    root = torch.nonzero(d["size"] >= min_members).reshape(-1)            # the one synchronisation
+    h = root.numel()
+    cols = [root] + [d[k].index_select(0, root).to(torch.int64) for k in
+                     ("size", "n_bound", "removed_last", "kinetic_q", "peculiar_q", "psum_hi", "psum_lo")]
+    scales = torch.stack([d["kinetic_scale"], d["peculiar_scale"]]).view(torch.int64)
+    packed = torch.cat([torch.stack(cols, dim=1).reshape(-1), scales, d["bound"].to(torch.int64)]).cpu()   # one transfer
+    table = packed[:8 * h].reshape(h, 8)
+    order = sorted(range(h), key=lambda i: (-int(table[i, 1]), int(table[i, 0])))
+    table = table[torch.tensor(order, dtype=torch.int64)]
+    kscale, sscale = packed[8 * h:8 * h + 2].view(torch.float64)
+    res = {"root": table[:, 0].clone(), "size": table[:, 1].clone(), "n_bound": table[:, 2].clone(),
+           "removed_last": table[:, 3].clone(), "bound": packed[8 * h + 2:].to(torch.bool), "shift": d["shift"]}
+    res.update(binding_from_sums(table[:, 1], table[:, 2], table[:, 4], kscale, table[:, 5], sscale, table[:, 6],
+                                 table[:, 7], d["shift"], gm))
+    return res
+
+
+def rollout_halo_binding(rollout_data: Dict[str, torch.Tensor], ground_truth: Dict[str, torch.Tensor], box_size: float,
+                         dt: float, gm: float, softening: float, linking_length: Optional[float] = None, size_edges=None,
+                         hubble: float = 0.0, iterations: int = 3, frames: Optional[Sequence[int]] = None) -> Dict:
+    """Whether a rollout's halos are BOUND, for the dicts ``rollout.rollout`` returns (``Coordinates [T, N, 3]``): per
+    selected frame ``f >= 1`` (default: every frame from 1 on that both hold) and per side the friends-of-friends groups
+    with at least ``size_edges[0]`` members are unbound as :func:`halo_binding` does, with the velocities
+    ``minimum_image(pos[f] - pos[f - 1]) / dt`` and no internal energy.  All listed groups are processed, at fixed shapes:
+    there is no ``max_halos``.  Per frame and per size bin of the FoF groups (``size_edges``: default
+    :func:`default_size_edges`), for ``pred`` and ``true`` (CPU):
+
+    * ``n_groups_*`` int64 ``[F, sb]``; ``spurious_*``: the groups of the bin left with fewer than ``size_edges[0]`` bound
+      members; ``bound_counts_*``: the mass function of the BOUND sizes on ``size_edges``;
+    * ``bound_fraction_*``, ``virial_ratio_*``, ``sigma_v_*`` float64 ``[F, sb]``: the means over the groups of the bin (the
+      last two over the groups where they are defined, ``n_virial_*`` and ``n_sigma_*`` many; ``nan`` without one),
+
+    the ratios ``bound_fraction_ratio`` and ``sigma_v_ratio`` (pred / true), plus ``frames``, ``size_lo``, ``size_hi``.  A group
+    beyond the last size edge is unbound but in no bin.  The bins are masked sums in a fixed order.  No synchronisation
+    per frame, one packed transfer.  Out of scope: as :func:`halo_binding`; the two sides' halos are not matched with
+    each other (:func:`rollout_halo_matching`)."""
+    what = "rollout_halo_binding"
+    dt = _check_dt(what, dt)
+    avail = min(len(rollout_data["Coordinates"]), len(ground_truth["Coordinates"]))
+    sel = list(range(1, avail)) if frames is None else [int(f) for f in frames]
+    if not sel or min(sel) < 1:
+        raise ValueError(f"{what}: frames must be numbers in [1, {avail}) (a frame needs its predecessor), got {sel}")
+    pc, tc, sel = _rollout_frames(rollout_data, ground_truth, sel, what)
+    pp, tp, _ = _rollout_frames(rollout_data, ground_truth, [f - 1 for f in sel], what)
+    n = pc.shape[1]
+    ll, se = _halo_arguments(n, box_size, linking_length, size_edges, what)
+    _check_binding_arguments(what, n, box_size, gm, softening, ll, hubble, iterations)
+    sb, nf = len(se) - 1, len(sel)
+    parts = []
+    for cur, prev in ((pc, pp), (tc, tp)):
+        for f in range(nf):
+            pos = cur[f].to(torch.float32).contiguous()
+            v = _step_velocities(pos, prev[f].to(torch.float32), dt, box_size)
+            d = halo_unbinding_on_device(pos, v, box_size, gm, softening, ll, se[0], hubble, None, iterations)
+            r = binding_from_sums(d["size"], d["n_bound"], d["kinetic_q"], d["kinetic_scale"], d["peculiar_q"],
+                                  d["peculiar_scale"], d["psum_hi"], d["psum_lo"], d["shift"], gm)
+            ints, floats = binding_size_bins(d["size"], d["n_bound"], r["bound_fraction"], r["virial_ratio"], r["sigma_v"],
+                                             se, se[0])
+            parts += [ints.reshape(-1), floats.contiguous().view(torch.int64).reshape(-1)]
+    packed = torch.cat(parts).cpu().reshape(2, nf, 8 * sb)                # the one transfer
+    sedges = torch.tensor(se, dtype=torch.int64)
+    res = {"frames": sel, "size_lo": sedges[:-1].clone(), "size_hi": sedges[1:].clone()}
+    for side, name in enumerate(("pred", "true")):
+        ints = packed[side, :, :5 * sb].reshape(nf, 5, sb)
+        floats = packed[side, :, 5 * sb:].contiguous().view(torch.float64).reshape(nf, 3, sb)
+        res["n_groups_" + name], res["spurious_" + name] = ints[:, 0].clone(), ints[:, 1].clone()
+        res["bound_counts_" + name] = ints[:, 2].clone()
+        res["n_virial_" + name], res["n_sigma_" + name] = ints[:, 3].clone(), ints[:, 4].clone()
+        res["bound_fraction_" + name] = floats[:, 0] / ints[:, 0].to(torch.float64)
+        res["virial_ratio_" + name] = floats[:, 1] / ints[:, 3].to(torch.float64)
+        res["sigma_v_" + name] = floats[:, 2] / ints[:, 4].to(torch.float64)
+    res["bound_fraction_ratio"] = res["bound_fraction_pred"] / res["bound_fraction_true"]
+    res["sigma_v_ratio"] = res["sigma_v_pred"] / res["sigma_v_true"]
     return res
 
 

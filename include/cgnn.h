@@ -1070,6 +1070,45 @@ int cgnn_halo_profiles(const float* pos, int64_t n, const float* centres, int64_
                        const float* edges, int32_t num_bins, const int32_t* q, int32_t channels, int64_t* counts,
                        int64_t* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- is a group bound: the softened potential sum of every member over the other members, in integers ----------------
+ * A friends-of-friends group is a set of particles that are close together; it is a halo only if they are also
+ * gravitationally bound.  cgnn_halo_potentials gives what unbinding needs: for every ACTIVE member i of a LISTED group
+ *     P_i = sum over j != i, j in the same group and active, of iw_ij
+ * pos [n, 3] (device, in [0, box_size]).  The members of the listed groups arrive contiguously: order [n] (device,
+ * particle indices), and per root slot r the segment start[r], count[r] (device, int32 [n]; count 0: no listed group at
+ * r); slot k of segment r holds particle order[k].  active (device, uint8 [n], or NULL for all): a particle with
+ * active == 0 is no target and no source.  Arithmetic, float32 with ONE rounding per operation and no FMA:
+ *     dx, dy, dz, d2   the folded minimum-image displacement and squared distance of cgnn_pair_counts
+ *     eps2 = fl32(softening softening);  s = fl32(d2 + eps2);  w = fl32(1 / fl32(sqrt(s)))   sqrt and / correctly rounded
+ *     iw   = rint(w 2^S), ties to even; the scaling by a power of two is exact
+ * with S fixed on the host from w_max = fl32(1 / fl32(sqrt(eps2))) so that w_max 2^S lies in [2^29, 2^30).  d2 >= 0 gives
+ * iw <= 2^30, and an int64 sum over a group of up to 2^31 members cannot overflow.  iw_ij == iw_ji; the sums are
+ * integers, so P depends on no order of threads or particles, is the same bits on every run and bit-equal to the numpy
+ * restatement (tests/halo_binding_checks.py).  No float atomics, no atomics at all.
+ * psum (device, int64 [n]) is overwritten: P_i for the active members of the segments, 0 everywhere else.  *shift (HOST
+ * memory) receives S; cgnn_halo_potential_shift(box_size, softening) gives it alone (INT32_MIN for a refused softening).
+ * Work: a group of more than CGNN_HB_SMALL members is cut into tiles of CGNN_HB_TARGETS targets, one workgroup of
+ * CGNN_HB_TILE threads each with two targets per thread in registers, which walks the group's members in LDS tiles of
+ * CGNN_HB_TILE float4; groups of at most CGNN_HB_SMALL members take one wave each, four to a workgroup.  The items are
+ * numbered on the device (two scans), the grid is bounded from n: no host synchronisation, everything on `stream`.
+ * Whatever order, start and count hold, nothing is read or written out of bounds (an order entry outside [0, n) is a
+ * padding slot; a segment outside [0, n) makes no work).
+ * CGNN_ERR_INVALID_ARG for a null pointer (active may be NULL), n <= 0, box_size not positive and finite, a softening
+ * that is not finite and positive, below box_size 2^-CGNN_HB_MIN_SOFTENING_BITS (the farthest pair of a box-spanning
+ * group would be resolved by fewer than about 2^13 integer steps) or whose float32 square leaves [2^-100, 2^100], a
+ * workspace that is not 16-byte aligned; 2^31 or more particles: CGNN_ERR_UNSUPPORTED; a short workspace:
+ * CGNN_ERR_WORKSPACE.  All of it is refused on the host before any device work.  Workspace:
+ * cgnn_halo_potentials_workspace_bytes(n), O(n) (256 for n outside [1, 2^31)). */
+#define CGNN_HB_TILE 256               /* threads per workgroup = sources per LDS tile */
+#define CGNN_HB_TARGETS 512            /* targets of a big work item: two per thread */
+#define CGNN_HB_SMALL 64               /* a group of at most one wave takes a wave, not a workgroup */
+#define CGNN_HB_MIN_SOFTENING_BITS 16  /* softening >= box_size 2^-16 */
+int32_t cgnn_halo_potential_shift(float box_size, float softening);
+size_t cgnn_halo_potentials_workspace_bytes(int64_t n);
+int cgnn_halo_potentials(const float* pos, const int32_t* order, const int32_t* start, const int32_t* count,
+                         const uint8_t* active, int64_t n, float box_size, float softening, int64_t* psum,
+                         int32_t* shift /* HOST */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- window -> node features (reference data_utils.py:91-92, :100-107, :127-145) -------------------
  * pos_seq [W, N, 3] and temp_seq [W, N] (frame-major, as the drivers hold a window), optional additive
  * noise pos_noise [N, W, 3] / temp_noise [N, W] (NULL = none).  Writes
